@@ -8,15 +8,27 @@ on host threads, block container — i.e. bsc_compress(lzp off, BWT, QLFC_STATIC
 compressed blocks are concatenated on rank 0 over RCCL/xGMI (send/recv of the variable-size blocks).
 Blocks are independent, so N GPUs = N blocks per step (weak scaling), one process per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task description) with two extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times K steps, writes
+its outputs (--dump-outputs) and prints the headline: metric, value (MB/s over the timed steps), unit, higher_is_better,
+dtype, ms_per_step, with the configuration and the GPU stage times the timed steps recorded anyway.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last timed step returned to the caller — the compressed
+block — as DIR/compressed_block.npy (one float32 per byte; a fixed, seeded sample of its bytes if the block is larger than
+the 64 MB budget, with DIR/compressed_block_index.npy then holding the sampled positions) and DIR/compressed_size.npy.
+
+--full adds, after the timed region and outside it, what else the bench measures and checks:
+  verified     — the last timed block against the committed reference output (tests/golden/golden_big.json), or the
+                 compiled reference (oracle/_ref) for --lzp / --input runs;
   roofline     — the dominant kernel (the LSD digit pass of the BWT's first sort: rs_onesweep_kernel, records read once and
                  written once): algorithmic bytes 2*m*(8+4) per full-size launch over the HIP-event time of those launches on
                  the kernel's own stream, against 8 TB/s HBM3E; sort_frac charges the whole sort (one histogram read +
-                 P passes, SURVEY 8d's B_sort) with every radix kernel's time;
-  cpu_baseline — the reference libbsc CPU path (oracle/_ref, built from /root/reference) timed on this box's cores.
+                 P passes, SURVEY 8d's B_sort) with every radix kernel's time; per-kernel times (the timed region runs
+                 with HIP-event profiling on);
+  boundary, configs, per_rank — the host-input leg, BASELINE's other configurations, PCIe / host DRAM figures;
+  cpu_baseline — the reference libbsc CPU path (oracle/_ref, compiled by oracle/Makefile) timed on this box's cores.
 """
 import argparse
 import json
@@ -127,8 +139,13 @@ def main():
                     help="what the blocks hold.  synth-text-v1 is BASELINE's workload and the only `value` that counts; python-source / binary are the image's "
                     "own *.py / *.so files (libbsc_amd.synth.image_corpus: long repeats, the sorter's hard classes) — separate, labelled lines, checked "
                     "against the compiled reference at run time")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also verify the output against the reference and run the "
+                    "roofline, pattern-ceiling, boundary, configs and cpu_baseline legs (off: the headline figure alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's compressed block as DIR/*.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     _process_affinity()            # (BSC_BENCH_AFFINITY=0: off)
     import torch
@@ -332,7 +349,7 @@ def main():
             for t in ths: t.join()
         if thread_errors:
             raise thread_errors[0]
-        return next(b for b in reversed(out) if b is not None)
+        return next((b for b in reversed(out) if b is not None), None)      # (None: no blocks, e.g. --warmup 0)
 
     def sync():
         if world > 1:
@@ -366,9 +383,10 @@ def main():
     if concat is not None:
         concat.close()
         concat = Concatenator(rank, world, comm_dev, staging=gather_buf)
-    for cx in ctxs:
-        cx.profile(True)
-        cx.profile_reset()
+    if args.full:                                       # per-kernel HIP events: the roofline and kernels figures of --full
+        for cx in ctxs:
+            cx.profile(True)
+            cx.profile_reset()
     sync()
     from libbsc_amd.gpu import coder_pool_stats
     coder_pool_stats(reset=True)
@@ -408,6 +426,15 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device=comm_dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:                 # before any later leg reuses the pipes' output buffers
+        dump_outputs(args.dump_outputs, blk)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(plain_line(args, world, n, dt, stage, ncx, coder_threads, blk)), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     for cx in ctxs:
         cx.profile(False)
 
@@ -674,6 +701,48 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def plain_line(args, world, n, dt, stage, ncx, coder_threads, blk):
+    """The result line of a run without --full: the headline figure of the timed steps and what produced it."""
+    return {
+        "metric": "MB/s compress (BWT+QLFC) on 64 MiB blocks", "value": round(world * args.steps * n / 1e6 / dt, 1), "unit": "MB/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
+        "data": "synthetic" if args.input == "synth-text-v1" else f"files of the container image ({args.input})",
+        "config": {"workload": f"{world} x {n >> 20} MiB {args.input} block(s) per step, bsc_compress(lzp {'-H%s -M%s' % tuple(args.lzp.split(',')) if args.lzp else 'off'}, "
+                               f"sorter={args.sorter}, coder={args.coder}); {ncx} GPU context(s) x {args.depth} block(s) in flight per GPU, "
+                               f"{coder_threads} coder threads",
+                   "block_bytes": n, "blocks_per_step": world, "sorter": "BWT" if args.sorter == 1 else f"ST{args.sorter}",
+                   "coder": {1: "QLFC static (-e1)", 2: "QLFC adaptive (-e2)", 3: "QLFC fast (-e0)"}[args.coder],
+                   "parallelism": f"block-parallel x{world}", "compressed_bytes_rank0": int(blk.size)},
+        "stage_ms_per_step": {"adler32_gpu": round(stage[0] / args.steps, 2), "sort_transform_gpu": round(stage[1] / args.steps, 2),
+                              "qlfc_front_gpu_and_d2h": round(stage[2] / args.steps, 2),
+                              "gpu_stage_total": round((stage[0] + stage[1] + stage[2]) / args.steps, 2),
+                              "contexts_per_gpu": ncx, "blocks_in_flight_per_gpu": ncx * args.depth},
+        "full": False,
+        "note": "headline only; --full adds the output check against the reference, roofline, per-kernel times, boundary, configs and cpu_baseline",
+    }
+
+
+DUMP_BUDGET = 64_000_000        # bytes of .npy files --dump-outputs may write in all
+
+
+def dump_outputs(d, blk):
+    """The last timed step's compressed block as float32 (exact for bytes), whole if it fits the budget, else a fixed, seeded
+    sample of its bytes with their positions (float64: exact for any block size)."""
+    os.makedirs(d, exist_ok=True)
+    b = np.asarray(blk).reshape(-1)
+    np.save(os.path.join(d, "compressed_size.npy"), np.array([b.size], np.float64))
+    if 4 * b.size <= DUMP_BUDGET - 4096:
+        np.save(os.path.join(d, "compressed_block.npy"), b.astype(np.float32))
+        if os.path.exists(os.path.join(d, "compressed_block_index.npy")):      # (a sampled dump's, from an earlier run into DIR)
+            os.remove(os.path.join(d, "compressed_block_index.npy"))
+        return
+    k = (DUMP_BUDGET - 4096) // 12
+    idx = np.sort(np.random.default_rng(20260915).choice(b.size, k, replace=False))
+    np.save(os.path.join(d, "compressed_block.npy"), b[idx].astype(np.float32))
+    np.save(os.path.join(d, "compressed_block_index.npy"), idx.astype(np.float64))
 
 
 def baseline_configs(torch, dev, local, ctx64, d_in64, n64, GpuContext, api):

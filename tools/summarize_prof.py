@@ -5,7 +5,7 @@ root = sys.argv[1]
 def find(pattern):
     return sorted(glob.glob(os.path.join(root, "**", pattern), recursive=True))
 
-cmd = sys.argv[2] if len(sys.argv) > 2 else "python bench.py --steps 8 --warmup 2 --no-cpu-baseline"
+cmd = sys.argv[2] if len(sys.argv) > 2 else "python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline"
 print(f"== rocprofv3 --kernel-trace --stats of: {cmd}")
 print("   (the GPU contexts of bench.py — six by default — run side by side in the timed region, so per-launch durations there measure sharing of the chip; the")
 print("    'solo' table below keeps only launches that no launch of another queue overlaps = bench.py's single-context leg, the")
