@@ -101,6 +101,35 @@ BSCGPU_API int64_t bscgpu_qlfc_static_pstream_packed(bscgpu_ctx* ctx, const uint
 BSCGPU_API int bscgpu_compress_device(bscgpu_ctx* ctx, const void* dInput, uint8_t* output, int n,
                            int blockSorter, int coder, int features);
 
+/* ---- batches of small blocks: one suffix sort for many blocks ------------------------------
+ * Blocks are laid out back to back: block b starts at off_b = sizes[0] + ... + sizes[b-1].  Blocks below
+ * BSCGPU_BATCH_MAX_N that the BWT sorts share one suffix sort per pass (at most max_n bytes and 4096 blocks,
+ * consecutive blocks); every other block takes the single-block path inside the same call.  Output is
+ * byte-identical to the single-block calls.  The context stays non-re-entrant.
+ *
+ * bscgpu_bwt_batch_device: dT / dL device pointers (may alias, dL in dT's layout).  primary[b] = what
+ *   bsc_bwt_encode returns for block b alone (error codes included); with num_indexes != NULL, num_indexes[b]
+ *   and indexes[16 b ..] are its aux indexes (at most 15).  Returns 0 or a batch-level error (bad arguments, GPU).
+ * bscgpu_compress_batch: host input; block b's output region starts at off_b + 28 b and holds sizes[b] + 28
+ *   bytes; results[b] = what bsc_compress(block b, ...) returns, with the same bytes — except for a block larger
+ *   than the context's max_n, which gets LIBBSC_GPU_NOT_ENOUGH_MEMORY (the call does not resize its context).
+ *   input and output must not overlap.  Returns 0 or a batch-level error (bad arguments: nothing written; a GPU failure).
+ * bscgpu_compress_batch_device: the same for input in HBM, without LZP, results as bscgpu_compress_device's (a block
+ *   larger than max_n: LIBBSC_BAD_PARAMETER).  Passes are sorted straight from dInput; checksums come from one
+ *   segmented Adler-32 launch per pass; only L (and a stored block's own bytes) crosses PCIe.
+ * Memory: on first use a context allocates the batch table (311 KB of HBM, counted by bscgpu_arena_bytes from then
+ *   on) and two pinned host buffers of max_n bytes each (not HBM; kept until bscgpu_destroy).
+ * bscgpu_batch_plan: the routing rule as a pure function: pass_of[b] = the pass of block b, or -1 for the
+ *   single-block path; returns the number of passes (cap = the context's max_n). */
+#define BSCGPU_BATCH_MAX_N (1 << 20)       /* = the device-model threshold; the batched route beats the call's per-block route below it */
+BSCGPU_API int bscgpu_batch_plan(const int* sizes, int count, int blockSorter, int64_t cap, int* pass_of);
+BSCGPU_API int bscgpu_bwt_batch_device(bscgpu_ctx* ctx, const void* dT, void* dL, const int* sizes, int count, int* primary,
+                                       unsigned char* num_indexes, int* indexes);
+BSCGPU_API int bscgpu_compress_batch(bscgpu_ctx* ctx, const unsigned char* input, const int* sizes, int count, unsigned char* output,
+                                     int* results, int lzpHashSize, int lzpMinLen, int blockSorter, int coder, int features);
+BSCGPU_API int bscgpu_compress_batch_device(bscgpu_ctx* ctx, const void* dInput, const int* sizes, int count, unsigned char* output,
+                                            int* results, int blockSorter, int coder, int features);
+
 /* Pipelined variant: up to `depth` (<= 8) blocks in flight on one GPU.  submit() runs the GPU stage of a block
  * (Adler-32, sort transform, QLFC front end, D2H of the run arrays) on the calling thread and hands the host stage
  * (QLFC modelling + range coding, one task per sub-block; container) to the process's coder threads, so block i+1 sorts

@@ -78,6 +78,10 @@ def lib():
     L.bscgpu_pipe_submit.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]
     L.bscgpu_pipe_wait.argtypes = [vp, C.c_int]
     L.bscgpu_pipe_submit_host.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.bscgpu_batch_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int64, vp]
+    L.bscgpu_bwt_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp]
+    L.bscgpu_compress_batch.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.bscgpu_compress_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int]
     if hasattr(L, "bscgpu_compress_device"):
         L.bscgpu_compress_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]
     _lib = L

@@ -29,6 +29,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 constexpr int SEG_ITEMS = 8;
 constexpr int SEG_TILE  = WG * SEG_ITEMS;      // 2048 records per tile, 8 consecutive per thread
@@ -948,6 +949,79 @@ __global__ __launch_bounds__(WG) void bwt_emit_pred_kernel(const u8* __restrict_
     else for (u32 q = 0; o0 + q < n; ++q) L[o0 + q] = (u8)(word >> (8 * q));
 }
 
+// ---------------------------------------------------------------------------------------------
+// Batched pass: many blocks back to back in one suffix sort (bwt_batch_device).  The block table `off` (count + 1 offsets) lives in a
+// small device array; a position finds its block by a binary search in it.  Block-major order is DESCENDING: block count - 1 takes the
+// lowest SA slots, block 0 the highest (block b: slots [N - off[b+1], N - off[b])).  The first-sort key carries count - 1 - b in its top
+// bits and the dense codes + 1 below (0 = past the block's own end: "shorter, hence smaller", no tail trick needed).  The doubling rounds
+// then need no block table at all: for a suffix s of block b, s + h past the block's end lies in a later block, whose ranks are all
+// below block b's slots, so next = ISA[s + h] + 1 orders it before every same-block next rank — exactly what 0 does at the block end.
+// (Only one suffix per group can reach the end: the members of a group share h characters and differ in length.)
+__device__ __forceinline__ u32 batch_block_of(const u32* __restrict__ off, u32 count, u32 i)
+{
+    u32 lo = 0, hi = count;                     // off[lo] <= i; empty blocks share an offset: the last such block wins
+    while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
+    return lo;
+}
+
+__global__ __launch_bounds__(WG) void bwt_batch_pack_kernel(const u8* __restrict__ T, u32 N, const u32* __restrict__ off, u32 count,
+                                                            u32 bb, u32 cb, u32 w, const u8* __restrict__ codes,
+                                                            u64* __restrict__ keys, u32* __restrict__ vals)
+{
+    __shared__ u8 lut[256];
+    lut[threadIdx.x] = codes[threadIdx.x];
+    __syncthreads();
+    const u32 i = blockIdx.x * WG + threadIdx.x;
+    if (i >= N) return;
+    const u32 b = batch_block_of(off, count, i), end = off[b + 1];
+    u64 key = bb ? (u64)(count - 1 - b) << (64 - bb) : 0ull;
+#pragma unroll
+    for (u32 t = 0; t < 16; ++t) {
+        if (t < w) {
+            const u32 p = i + t;
+            const u64 cd = (p < end) ? (u64)lut[T[p]] + 1ull : 0ull;
+            key |= cd << (64 - bb - cb * (t + 1));
+        }
+    }
+    keys[i] = key;
+    vals[i] = i;
+}
+
+// per block: I[t] = (row of suffix off_b + t * r_b inside the block) + 1, from the final ISA (slots)
+__global__ __launch_bounds__(WG) void bwt_batch_find_kernel(const u32* __restrict__ ISA, u32 N, const u32* __restrict__ off,
+                                                            const int* __restrict__ rate, u32 count, u32* __restrict__ res)
+{
+    const u32 b = blockIdx.x * WG + threadIdx.x;
+    if (b >= count) return;
+    const u32 o0 = off[b], end = off[b + 1], nb = end - o0;
+    const int r = rate[b];
+    if (nb == 0 || r < 0) return;
+    const u32 base = N - end;
+    res[16u * b] = ISA[o0] - base + 1u;
+    if (r > 0) {
+        u32 cnt = (nb - 1u) / (u32)r + 1u; if (cnt > 16u) cnt = 16u;
+        for (u32 t = 1; t < cnt; ++t) res[16u * b + t] = ISA[o0 + t * (u32)r] - base + 1u;
+    }
+}
+
+// L of block b at the block's own place: L[0] = T[end - 1]; L[j] = T[SA[base + row] - 1], row = j - 1 up to the primary row, j after it
+__global__ __launch_bounds__(WG) void bwt_batch_emit_kernel(const u8* __restrict__ T, const u32* __restrict__ SA, const u32* __restrict__ ISA,
+                                                            u32 N, const u32* __restrict__ off, const int* __restrict__ rate, u32 count,
+                                                            u8* __restrict__ L)
+{
+    const u32 o = blockIdx.x * WG + threadIdx.x;
+    if (o >= N) return;
+    const u32 b = batch_block_of(off, count, o), o0 = off[b], end = off[b + 1];
+    if (rate[b] < 0) { L[o] = T[o]; return; }
+    const u32 base = N - end, p = ISA[o0] - base, j = o - o0;
+    u8 byte;
+    if (j == 0) byte = T[end - 1];
+    else byte = T[SA[base + ((j <= p) ? j - 1 : j)] - 1u];
+    L[o] = byte;
+}
+
+struct BwtBatch { u32 count; const u32* off; const int* rate; u32* res; u32* res_host; };
+
 void launch_seg_scan(bscgpu_ctx* c, u32 num_chunks)
 {
     hipLaunchKernelGGL(seg_scan_kernel, dim3(1), dim3(WG), 0, c->stream, c->segsum, num_chunks, c->segoff, c->dscal);
@@ -981,7 +1055,8 @@ static int run_seg(bscgpu_ctx* c, const u64* keys, const u32* sa_sorted, const u
     return radix_onesweep_check(c);            // the sort in front of this seg, if it used the single-read passes
 }
 
-static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_t n64, int64_t r, u32* I_host, int64_t* primary_out, bool reuse_text);
+static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_t n64, int64_t r, u32* I_host, int64_t* primary_out, bool reuse_text,
+                           const BwtBatch* bt = nullptr);
 
 // A single-read digit pass that gave up a wait (radix_onesweep.hip: bounded polls; pre-emption, a debugger, a hogged CU) fails the
 // sort, not the block: the transform is redone once with the three-kernel passes, which have no cross-workgroup protocol at all.
@@ -1002,7 +1077,47 @@ int bwt_device(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_t n64, int64
     return rc;
 }
 
-static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_t n64, int64_t r, u32* I_host, int64_t* primary_out, bool reuse_text)
+// One batched pass (see bwt_batch_pack_kernel): the block table goes up, one transform of the whole pass runs, the per-block indexes come
+// back with the pass's last sync.  Same retry rule as bwt_device.
+int bwt_batch_device(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, const int* sizes, int count, const int* rates, u32* res, u32* adler_host)
+{
+    if (count <= 0 || count > BATCH_MAX_BLOCKS) return BSC_BAD_PARAMETER;
+    constexpr size_t TAB_WORDS = (size_t)(BATCH_MAX_BLOCKS + 1) + BATCH_MAX_BLOCKS + 16 * (size_t)BATCH_MAX_BLOCKS + BATCH_MAX_BLOCKS;   // offsets, rates, indexes, checksums
+    if (!c->batch_tab && hipMalloc((void**)&c->batch_tab, TAB_WORDS * 4) != hipSuccess) {
+        (void)hipGetLastError(); c->batch_tab = nullptr;
+        return ctx_fail(c, BSC_GPU_NOT_ENOUGH_MEMORY, "batched BWT: block table", hipSuccess);
+    }
+    c->batch_bytes = TAB_WORDS * 4;
+    std::vector<u32> tab((size_t)2 * count + 1);
+    u64 total = 0;
+    for (int b = 0; b < count; ++b) { tab[b] = (u32)total; total += (u64)sizes[b]; }
+    tab[count] = (u32)total;
+    memcpy(&tab[count + 1], rates, (size_t)count * 4);
+    if (total == 0) return BSC_NO_ERROR;
+    if (total > (u64)c->max_n || total >= 0x7fffffffull) return BSC_BAD_PARAMETER;
+    BwtBatch bt;
+    bt.count = (u32)count; bt.off = c->batch_tab; bt.rate = reinterpret_cast<const int*>(c->batch_tab + count + 1);
+    bt.res = c->batch_tab + 2 * BATCH_MAX_BLOCKS + 1; bt.res_host = res;
+    HIP_TRY(c, hipMemcpyAsync(c->batch_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (adler_host) {                           // (reads the caller's text before the transform may overwrite it; the transform's last sync covers the copy)
+        u32* dadler = c->batch_tab + 18 * BATCH_MAX_BLOCKS + 1;
+        launch_adler_batch(c, dT_user, c->batch_tab, (u32)count, dadler);
+        HIP_TRY(c, hipMemcpyAsync(adler_host, dadler, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    int64_t unused = 0;
+    c->os_gave_up = false;
+    int rc = bwt_device_once(c, dT_user, dL_user, (int64_t)total, 0, nullptr, &unused, false, &bt);
+    if (rc == BSC_GPU_ERROR && c->os_gave_up) {
+        const int mode = c->os_mode;
+        c->os_mode = 0; c->os_gave_up = false; ++c->os_retries;
+        rc = bwt_device_once(c, dT_user, dL_user, (int64_t)total, 0, nullptr, &unused, false, &bt);
+        c->os_mode = mode;
+    }
+    return rc;
+}
+
+static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_t n64, int64_t r, u32* I_host, int64_t* primary_out, bool reuse_text,
+                           const BwtBatch* bt)
 {
     if (n64 < 0 || n64 > c->max_n || n64 >= 0x7fffffffll) return BSC_BAD_PARAMETER;
     if (n64 == 0) { *primary_out = 0; return BSC_NO_ERROR; }
@@ -1026,10 +1141,13 @@ static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_
     u8 codes[256]; u32 K = 0;
     for (int b = 0; b < 256; ++b) { codes[b] = (u8)K; if (c->hscal[300 + b]) ++K; }
     PackParams pp;
-    pp.cb = 1; while ((1u << pp.cb) < K) ++pp.cb;
+    // a batched pass: codes 1..K (0 = past the block's end) below the block field; no text rounds, no predecessor codes (see bwt_batch_pack_kernel)
+    const u32 batch_bb = bt ? (u32)bit_length(bt->count - 1) : 0u;
+    pp.cb = 1; while ((1u << pp.cb) < K + (bt ? 1u : 0u)) ++pp.cb;
     if (pp.cb < 4) pp.cb = 4;                                   // at most 16 characters per key
     pp.w = 64 / pp.cb;
-    { static const int wmax = [] { const char* e = getenv("BSC_BWT_W"); return e ? atoi(e) : 0; }(); if (wmax >= 2 && (u32)wmax < pp.w) pp.w = (u32)wmax; }   // experiment: shorter first-sort keys
+    if (bt) { pp.w = (64 - batch_bb) / pp.cb; if (pp.w > 16) pp.w = 16; }
+    else { static const int wmax = [] { const char* e = getenv("BSC_BWT_W"); return e ? atoi(e) : 0; }(); if (wmax >= 2 && (u32)wmax < pp.w) pp.w = (u32)wmax; }   // experiment: shorter first-sort keys
     // Mixed-radix keys (round 6, BSC_BWT_RADIX=1): with K symbols the base-K number of w' characters fits 64 bits for w' = floor(64 / log2 K),
     // which is one character more than 64 / cb for K = 17..19, 24..30 (text: 28 symbols -> 13 characters instead of 12; same eight digit passes).
     // Measured and NOT the default (profiles/r06/first_sort_keys.txt): on the bench block 20.9 M instead of 27.8 M suffixes are unsorted after the
@@ -1038,21 +1156,21 @@ static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_
     pp.radix = 0; pp.top = 0;
     {
         static const int radix_on = [] { const char* e = getenv("BSC_BWT_RADIX"); return e ? atoi(e) : BWT_RADIX_DEFAULT; }();
-        if (radix_on && K >= 3 && getenv("BSC_BWT_W") == nullptr) {            // (BSC_BWT_W, the other key-width experiment, keeps the bit-packed keys)
+        if (radix_on && !bt && K >= 3 && getenv("BSC_BWT_W") == nullptr) {            // (BSC_BWT_W, the other key-width experiment, keeps the bit-packed keys)
             u32 wr = 0; unsigned __int128 pw = 1;
             while (pw * K <= ((unsigned __int128)1 << 64) - 1 && wr < 16) { pw *= K; ++wr; }      // K^wr <= 2^64 - 1
             if (wr > pp.w && wr <= 16) { pp.radix = K; pp.w = wr; u64 t = 1; for (u32 x = 1; x < wr; ++x) t *= K; pp.top = t; }
         }
     }
     pp.tc = n < pp.w - 1 ? n : pp.w - 1;
-    pp.low_shift = pp.radix ? 0u : 64 - pp.cb * pp.w;
+    pp.low_shift = pp.radix ? 0u : 64 - pp.cb * pp.w - batch_bb;
     // The sort's values have spare high bits when the block is not huge: carry the code of the character in FRONT of the
     // suffix there, so that the final L = T[SA - 1] needs no random gather from the text (BSC_BWT_PRED=0 keeps the gather)
     const int idx_bits = bit_length(n - 1);
     static const int pred_on = [] { const char* e = getenv("BSC_BWT_PRED"); return e ? atoi(e) : 1; }();
-    pp.pred_shift = (pred_on && idx_bits >= 1 && idx_bits + (int)pp.cb <= 32) ? (u32)idx_bits : 0u;
+    pp.pred_shift = (pred_on && !bt && idx_bits >= 1 && idx_bits + (int)pp.cb <= 32) ? (u32)idx_bits : 0u;
     const u32 smask = pp.pred_shift ? ((1u << pp.pred_shift) - 1u) : 0xffffffffu;
-    const u32 tail_lo = (n >= pp.w) ? (n - (pp.w - 1)) : 0;
+    const u32 tail_lo = bt ? 0xffffffffu : (n >= pp.w) ? (n - (pp.w - 1)) : 0;
     u8* dcodes = reinterpret_cast<u8*>(c->dscal + 560);         // 256 bytes of the scalar area
     u8* ddecode = reinterpret_cast<u8*>(c->dscal + 720);        // 256 bytes: code -> byte (640..703 is the QLFC front end's symbol table)
     u8 decode[256]; memset(decode, 0, sizeof decode);
@@ -1060,8 +1178,12 @@ static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_
     HIP_TRY(c, hipMemcpyAsync(dcodes, codes, 256, hipMemcpyHostToDevice, c->stream));
     if (pp.pred_shift) HIP_TRY(c, hipMemcpyAsync(ddecode, decode, 256, hipMemcpyHostToDevice, c->stream));
     prof_begin(c, BSCGPU_K_PACK, (u64)n * 13, n);
-    hipLaunchKernelGGL(bwt_pack_kernel, dim3((n + 4 * WG - 1) / (4 * WG)), dim3(WG), 0, c->stream,
-                       c->dT, n, pp, dcodes, c->kA, c->vA);
+    if (bt)
+        hipLaunchKernelGGL(bwt_batch_pack_kernel, dim3((n + WG - 1) / WG), dim3(WG), 0, c->stream,
+                           c->dT, n, bt->off, bt->count, batch_bb, pp.cb, pp.w, dcodes, c->kA, c->vA);
+    else
+        hipLaunchKernelGGL(bwt_pack_kernel, dim3((n + 4 * WG - 1) / (4 * WG)), dim3(WG), 0, c->stream,
+                           c->dT, n, pp, dcodes, c->kA, c->vA);
     prof_end(c);
 
     RadixPass passes[16]; int npass = 0;
@@ -1077,7 +1199,7 @@ static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_
     // 4 bits spare, else w - 1.  BSC_BWT_TEXTROUNDS=0 keeps the round-1 flow (ISA built by the first seg, doubling from h = w).
     static const int text_on = [] { const char* e = getenv("BSC_BWT_TEXTROUNDS"); return e ? atoi(e) : 1; }();
     const u32 ta = (pp.cb * pp.w + 4 <= 64) ? pp.w : pp.w - 1;
-    bool isa_valid = !(text_on && ta >= 2 && ta <= 15);
+    bool isa_valid = bt != nullptr || !(text_on && ta >= 2 && ta <= 15);       // (text rounds read the text past a suffix: not across block ends)
     int cur = 0;
     u32 U = 0;
     // SA: the sort's value array itself when the rounds do not write to it (they put their output into kB / vB), else a copy
@@ -1274,6 +1396,20 @@ static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_
     }
     c->stage_ms[5] = rounds;
 
+    if (bt) {
+        // every block's indexes from the final ISA, every block's L in place; one copy of the results, one sync for the pass
+        prof_begin(c, BSCGPU_K_EMIT, (u64)n * 10, n);
+        HIP_TRY(c, hipMemsetAsync(bt->res, 0, (size_t)bt->count * 16 * 4, c->stream));
+        hipLaunchKernelGGL(bwt_batch_find_kernel, dim3((bt->count + WG - 1) / WG), dim3(WG), 0, c->stream, c->ISA, n, bt->off, bt->rate, bt->count, bt->res);
+        hipLaunchKernelGGL(bwt_batch_emit_kernel, dim3((n + WG - 1) / WG), dim3(WG), 0, c->stream, c->dT, SA, c->ISA, n, bt->off, bt->rate, bt->count, dL_user);
+        prof_end(c);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(bt->res_host, bt->res, (size_t)bt->count * 16 * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, ctx_sync(c));
+        prof_collect(c);
+        *primary_out = 0;
+        return BSC_NO_ERROR;
+    }
     // primary index and aux indexes from SA, then the last column
     u32 cnt = 0, rshift = 0;
     if (I_host != nullptr) {

@@ -230,6 +230,8 @@ extern "C" void bscgpu_destroy(bscgpu_ctx* c)
     if (c->os_agg) { (void)hipFree(c->os_agg); c->os_agg = nullptr; }
     if (c->os_zero) { (void)hipFree(c->os_zero); c->os_zero = nullptr; }
     if (c->long_tables) { (void)hipFree(c->long_tables); c->long_tables = nullptr; }
+    if (c->batch_tab) { (void)hipFree(c->batch_tab); c->batch_tab = nullptr; c->batch_bytes = 0; }
+    for (auto& hb : c->batch_host) if (hb) { (void)hipHostFree(hb); hb = nullptr; }
     if (c->copy_stream) { hipStreamSynchronize(c->copy_stream); hipStreamDestroy(c->copy_stream); }
     for (auto& p : c->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto& e : c->event_pool) hipEventDestroy(e);
@@ -253,7 +255,7 @@ extern "C" void bscgpu_destroy(bscgpu_ctx* c)
     delete c;
 }
 
-extern "C" int64_t bscgpu_arena_bytes(const bscgpu_ctx* c) { return c ? (int64_t)c->arena_bytes : 0; }
+extern "C" int64_t bscgpu_arena_bytes(const bscgpu_ctx* c) { return c ? (int64_t)(c->arena_bytes + c->batch_bytes) : 0; }
 extern "C" const char* bscgpu_last_error(const bscgpu_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 // ---- profiling --------------------------------------------------------------------------------

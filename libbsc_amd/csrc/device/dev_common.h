@@ -106,6 +106,9 @@ struct bscgpu_ctx {
     u64* adler_part = nullptr; // [MAX_CHUNKS][2]
     u32* tile_counts = nullptr; size_t tile_counts_cap = 0;   // [256][tiles of 8192 records]: BSC_RS_ORDER=1 experiment, allocated on first use
     u32* long_tables = nullptr;   // BWT text rounds: counting-sort tables of the long-group split (bwt.hip LongTables), allocated on first use
+    u32* batch_tab = nullptr;     // batched BWT pass: block table + per-block results (bwt.hip BwtBatch), allocated on first use
+    size_t batch_bytes = 0;       // HBM of batch_tab (bscgpu_arena_bytes counts it once allocated)
+    u8*  batch_host[2] = {nullptr, nullptr};   // pinned: a batched pass's text going up and its L coming back (two: coding overlaps the next pass)
     u64* wc_sink = nullptr;  // [512 * 1024] write sink for predicated-off lanes of rs_scatter_wc
     // single-read digit passes (radix_onesweep.hip), allocated on first use
     int  num_cus = 256;           // hipDeviceAttributeMultiprocessorCount of the context's device
@@ -185,6 +188,14 @@ int radix_engine_setup(bscgpu_ctx* c);     // per-device kernel attributes; bscg
 int bwt_device(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_t n, int64_t r, u32* I_host,
                int64_t* primary_out);
 int st_device(bscgpu_ctx* c, const u8* dT_user, u8* dOut_user, int n, int k, int* index_out);
+// Batched BWT pass (bwt.hip): `count` blocks of sizes[b] laid out back to back in dT_user, sum <= max_n, count <= BATCH_MAX_BLOCKS.
+// rates[b] > 0: the block's aux rate, 0: primary index only, < 0: not transformed (L = T).  res[16 b + t] = I[t] of block b as bwt_device
+// returns it (I[0] = the primary index), for t < (n_b - 1) / rates[b] + 1.
+constexpr int BATCH_MAX_BLOCKS = 4096;
+// adler_host != nullptr: also every block's Adler-32 of dT_user (st.hip: adler_batch_kernel, one launch), back with the same sync.
+int bwt_batch_device(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, const int* sizes, int count, const int* rates, u32* res,
+                     u32* adler_host = nullptr);
+void launch_adler_batch(bscgpu_ctx* c, const u8* d, const u32* doff, u32 count, u32* dout);     // st.hip (asynchronous)
 int adler32_device(bscgpu_ctx* c, const u8* d, int64_t n, u32* out);
 void launch_seg_scan(bscgpu_ctx* c, u32 num_chunks);
 int qlfc_front_split(bscgpu_ctx* c, const u8* dL, u32 n, int nblocks, int* start, int* size);

@@ -192,6 +192,34 @@ __global__ __launch_bounds__(WG) void adler_kernel(const u8* __restrict__ T, u64
     }
 }
 
+// Segmented Adler-32: one workgroup per block of a batch (blocks back to back, off[0..count]), every block's checksum in one launch.
+// Lanes read consecutive bytes (blocks start anywhere, so no 16-byte loads); per lane a = sum d, b = sum (end - p) d, folded as adler_kernel's
+// chunks are: s1 = 1 + a, s2 = n + b (mod 65521).
+__global__ __launch_bounds__(WG) void adler_batch_kernel(const u8* __restrict__ T, const u32* __restrict__ off, u32* __restrict__ out)
+{
+    __shared__ u64 red[2 * WAVES];
+    const u32 start = off[blockIdx.x], end = off[blockIdx.x + 1];
+    u64 a = 0, b = 0;
+    for (u32 p = start + threadIdx.x; p < end; p += WG) { const u32 d = T[p]; a += d; b += (u64)d * (end - p); }
+    a = wave_sum_u64(a); b = wave_sum_u64(b);
+    const u32 w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[w] = a; red[WAVES + w] = b; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u64 sa = 0, sb = 0;
+        for (int i = 0; i < WAVES; ++i) { sa += red[i]; sb += red[WAVES + i]; }
+        const u64 s1 = (1ull + sa) % 65521ull, s2 = ((u64)(end - start) + sb) % 65521ull;
+        out[blockIdx.x] = (u32)(s1 | (s2 << 16));
+    }
+}
+
+void launch_adler_batch(bscgpu_ctx* c, const u8* d, const u32* doff, u32 count, u32* dout)
+{
+    prof_begin(c, BSCGPU_K_MISC, 0, 0);
+    hipLaunchKernelGGL(adler_batch_kernel, dim3(count), dim3(WG), 0, c->stream, d, doff, dout);
+    prof_end(c);
+}
+
 int adler32_device(bscgpu_ctx* c, const u8* d, int64_t n, u32* out)
 {
     if (n < 0) return BSC_BAD_PARAMETER;

@@ -1455,3 +1455,343 @@ int bsc_synth_text_v1(unsigned long long seed, unsigned char* out, long long n)
 }
 
 }  // extern "C"
+
+// ---- batched compression of many small blocks (bscgpu_*_batch, include/bscgpu.h) ------------------------------------------------
+// Blocks below BSCGPU_BATCH_MAX_N that the BWT sorts go through one suffix sort per PASS (bwt.hip: bwt_batch_device), the
+// rest through the single-block path on the same context.  After a pass's sort its L comes back in one copy and every block is coded
+// on the host exactly as bsc_compress codes it (libbsc.cpp:283-337: bsc_coder_compress, the stored rule, the trailer); that coding
+// overlaps the next pass's sort.
+
+extern "C" BSCGPU_API int bscgpu_batch_plan(const int* sizes, int count, int blockSorter, int64_t cap, int* pass_of)
+{
+    if (count < 0 || (count > 0 && (!sizes || !pass_of))) return LIBBSC_BAD_PARAMETER;
+    int passes = 0, cur = -1, span = 0;
+    int64_t bytes = 0;
+    for (int b = 0; b < count; ++b) {
+        const int n = sizes[b];
+        if (n < 0) return LIBBSC_BAD_PARAMETER;
+        const bool batched = blockSorter == LIBBSC_BLOCKSORTER_BWT && n > 0 && n < BSCGPU_BATCH_MAX_N && (int64_t)n <= cap;
+        if (!batched) {
+            pass_of[b] = -1;
+            if (n > 0) cur = -1;                     // a pass is one contiguous range of the input: a block of its own ends it
+            else if (cur >= 0) ++span;               // (an empty block inside a pass is an empty entry of its table)
+            continue;
+        }
+        if (cur < 0 || bytes + n > cap || span + 1 > BATCH_MAX_BLOCKS) { cur = passes++; bytes = 0; span = 0; }
+        pass_of[b] = cur; bytes += n; ++span;
+    }
+    return passes;
+}
+
+extern "C" BSCGPU_API int bscgpu_bwt_batch_device(bscgpu_ctx* c, const void* dT, void* dL, const int* sizes, int count, int* primary,
+                                                  unsigned char* num_indexes, int* indexes)
+{
+    if (!c || count < 0 || (count > 0 && (!sizes || !primary)) || (num_indexes != nullptr && indexes == nullptr)) return LIBBSC_BAD_PARAMETER;
+    int64_t total = 0;
+    for (int b = 0; b < count; ++b) { if (sizes[b] < 0) return LIBBSC_BAD_PARAMETER; total += sizes[b]; }
+    if (total > 0 && (!dT || !dL)) return LIBBSC_BAD_PARAMETER;
+    if (count == 0) return LIBBSC_NO_ERROR;
+    if (hipSetDevice(c->device) != hipSuccess) return LIBBSC_GPU_ERROR;
+    const bool aux = num_indexes != nullptr;
+    std::vector<int> pass_of((size_t)count), rate((size_t)count);
+    const int npass = bscgpu_batch_plan(sizes, count, LIBBSC_BLOCKSORTER_BWT, c->max_n, pass_of.data());
+    if (npass < 0) return npass;
+    std::vector<int64_t> off((size_t)count + 1, 0);
+    for (int b = 0; b < count; ++b) off[b + 1] = off[b] + sizes[b];
+    // what bsc_bwt_encode says before sorting anything (n = 0; r < 2 with the indexes asked for)
+    for (int b = 0; b < count; ++b) {
+        const int n = sizes[b];
+        if (aux) num_indexes[b] = 0;
+        rate[b] = aux ? aux_rate(n) : 0;
+        if (n == 0) { primary[b] = aux ? LIBBSC_BAD_PARAMETER : 0; rate[b] = -1; }
+        else if (aux && rate[b] < 2) { primary[b] = LIBBSC_BAD_PARAMETER; rate[b] = -1; }
+    }
+    const u8* T = (const u8*)dT; u8* L = (u8*)dL;
+    auto put = [&](int b, const uint32_t* I) {
+        primary[b] = (int)I[0];
+        if (aux) {
+            const int cnt = (sizes[b] - 1) / rate[b];
+            num_indexes[b] = (unsigned char)cnt;
+            for (int t = 0; t < cnt; ++t) indexes[16 * b + t] = (int)I[t + 1] - 1;
+        }
+    };
+    std::vector<uint32_t> res((size_t)BATCH_MAX_BLOCKS * 16);
+    for (int b = 0; b < count;) {
+        if (pass_of[b] < 0) {
+            if (sizes[b] > 0 && rate[b] >= 0) {
+                uint32_t I[256]; int64_t p = 0;
+                const int rc = bwt_device(c, T + off[b], L + off[b], sizes[b], rate[b], aux ? I : nullptr, &p);
+                if (rc < 0) primary[b] = rc;
+                else if (aux) put(b, I);
+                else primary[b] = (int)p;
+            } else if (sizes[b] > 0 && L + off[b] != T + off[b]) {
+                if (hipMemcpyAsync(L + off[b], T + off[b], (size_t)sizes[b], hipMemcpyDeviceToDevice, c->stream) != hipSuccess || ctx_sync(c) != hipSuccess) return LIBBSC_GPU_ERROR;
+            }
+            ++b;
+            continue;
+        }
+        // the pass: its members and the empty blocks between them, one contiguous range
+        int e = b;
+        for (int q = b; q < count && (pass_of[q] == pass_of[b] || (pass_of[q] < 0 && sizes[q] == 0)); ++q) if (pass_of[q] == pass_of[b]) e = q + 1;
+        const int rc = bwt_batch_device(c, T + off[b], L + off[b], sizes + b, e - b, rate.data() + b, res.data());
+        if (rc < 0) return rc;
+        for (int q = b; q < e; ++q) if (rate[q] >= 0 && sizes[q] > 0) put(q, res.data() + 16 * (size_t)(q - b));
+        b = e;
+    }
+    return LIBBSC_NO_ERROR;
+}
+
+// bsc_compress on a given context (the body of bsc_compress without the default-context lookup)
+static int compress_one_on_ctx(bscgpu_ctx* c, const unsigned char* input, unsigned char* output, int n, int lzpHashSize, int lzpMinLen,
+                               int blockSorter, int coder, int features)
+{
+    int mode = 0;
+    int rc = make_mode(blockSorter, coder, lzpHashSize, lzpMinLen, &mode);
+    if (rc != LIBBSC_NO_ERROR) return rc;
+    if (n < 0 || n > 1073741824) return LIBBSC_BAD_PARAMETER;
+    if (n <= LIBBSC_HEADER_SIZE) return bsc_store(input, output, n, features);
+    if (n > c->max_n) return LIBBSC_GPU_NOT_ENOUGH_MEMORY;        // (the call's context is not resized: bscgpu.h)
+    std::unique_ptr<BlockJob> J(new BlockJob);
+    rc = stage_host_lzp(*J, input, output, n, lzpHashSize, lzpMinLen, &blockSorter, coder, features, mode);
+    if (rc < 0) return rc;
+    if (J->n > c->max_n) return LIBBSC_GPU_NOT_ENOUGH_MEMORY;
+    if (hipSetDevice(c->device) != hipSuccess) return LIBBSC_GPU_ERROR;
+    rc = ctx_ensure_slots(c, 1);
+    if (rc < 0) return rc;
+    J->slot = &c->slots[0];
+    rc = stage_host_h2d(*J, c);
+    if (rc < 0) return rc;
+    rc = gpu_stage(*J, blockSorter);
+    if (!J->use_ps) J->lz.reset();
+    if (rc < 0) return rc;
+    host_stage(*J);
+    if (J->redo.load(std::memory_order_relaxed)) return redo_on_host_model(*J);
+    return J->result;
+}
+
+namespace {
+struct BatchBlock {
+    int b = 0, lz = 0, mode = 0, index = 0, num_indexes = 0;
+    int indexes[16];
+    unsigned adler = 0;                          // Adler-32 of the block's input (device input: from the pass's segmented kernel)
+    bool sorted = false;                         // in the pass's sort (else result already set, or left to the single path)
+    bool single = false;                         // after LZP: the single-block path decides (a sorter input too short for the aux indexes)
+    bool store = false;                          // device input of <= 28 bytes: stored from its copy in the pass's L buffer (L = T there)
+    unsigned char* lzbuf = nullptr;
+};
+}
+
+// the stored rule (libbsc.cpp:188) for a block whose input is in HBM: one copy of it straight into the output region
+static int store_from_device(bscgpu_ctx* c, const unsigned char* dIn, unsigned char* output, int n, unsigned adler)
+{
+    if (hipSetDevice(c->device) != hipSuccess || hipMemcpy(output + LIBBSC_HEADER_SIZE, dIn, (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+        return LIBBSC_GPU_ERROR;
+    put_i32(output + 0, n + LIBBSC_HEADER_SIZE); put_i32(output + 4, n); put_i32(output + 8, 0); put_i32(output + 12, 0);
+    put_i32(output + 16, (int)adler); put_i32(output + 20, (int)adler);
+    put_i32(output + 24, (int)adler32(output, 24));
+    return n + LIBBSC_HEADER_SIZE;
+}
+
+// the host tail of bsc_compress (libbsc.cpp:296-336) for one block of a sorted pass; input: host bytes, or dIn in HBM
+static int code_sorted_block(bscgpu_ctx* c, const unsigned char* input, const unsigned char* dIn, unsigned char* output, int n,
+                             const BatchBlock& B, const unsigned char* Lb, int coder, int features)
+{
+    unsigned char* buffer = (unsigned char*)bsc_malloc((size_t)B.lz + 4096);
+    if (!buffer) return LIBBSC_NOT_ENOUGH_MEMORY;
+    int result = coder_compress(Lb, buffer, B.lz, coder, features);
+    if (result >= LIBBSC_NO_ERROR) memcpy(output + LIBBSC_HEADER_SIZE, buffer, (size_t)result);
+    bsc_free(buffer);
+    const int num = n < 64 * 1024 ? 0 : B.num_indexes;
+    if (result < LIBBSC_NO_ERROR || result + 1 + 4 * num >= n)
+        return input ? bsc_store(input, output, n, features) : store_from_device(c, dIn, output, n, B.adler);
+    if (num > 0) memcpy(output + LIBBSC_HEADER_SIZE + result, B.indexes, (size_t)4 * num);
+    output[LIBBSC_HEADER_SIZE + result + 4 * num] = (unsigned char)num;
+    result += 1 + 4 * num;
+    put_i32(output + 0, result + LIBBSC_HEADER_SIZE);
+    put_i32(output + 4, n);
+    put_i32(output + 8, B.mode);
+    put_i32(output + 12, B.index);
+    put_i32(output + 16, (int)(input ? adler32(input, (size_t)n) : B.adler));
+    put_i32(output + 20, (int)adler32(output + LIBBSC_HEADER_SIZE, (size_t)result));
+    put_i32(output + 24, (int)adler32(output, 24));
+    return result + LIBBSC_HEADER_SIZE;
+}
+
+// n tasks on at most `threads` threads (par.h: what cannot get a thread runs on the caller)
+template <class F>
+static void run_bounded(int n, int threads, F&& fn)
+{
+    if (n <= 0) return;
+    std::atomic<int> next{0};
+    run_tasks(threads < n ? threads : n, [&](int) { for (int i; (i = next.fetch_add(1)) < n;) fn(i); });
+}
+
+// One implementation for both entry points: host input (`input`, LZP per block) or input in HBM (`dInput`, no LZP).
+static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const unsigned char* dInput, const int* sizes, int count,
+                               unsigned char* output, int* results, int lzpHashSize, int lzpMinLen, int blockSorter, int coder, int features)
+{
+    int mode = 0;
+    const int mrc = make_mode(blockSorter, coder, lzpHashSize, lzpMinLen, &mode);
+    if (mrc != LIBBSC_NO_ERROR) { for (int b = 0; b < count; ++b) results[b] = mrc; return LIBBSC_NO_ERROR; }
+    if (hipSetDevice(c->device) != hipSuccess) return LIBBSC_GPU_ERROR;
+    const bool dev = dInput != nullptr;
+    std::vector<int> pass_of((size_t)count);
+    const int npass = bscgpu_batch_plan(sizes, count, blockSorter, c->max_n, pass_of.data());
+    if (npass < 0) return npass;
+    std::vector<int64_t> in_off((size_t)count + 1, 0);
+    for (int b = 0; b < count; ++b) in_off[b + 1] = in_off[b] + sizes[b];
+    auto in_of = [&](int b) { return input + in_off[b]; };
+    auto din_of = [&](int b) { return dInput + in_off[b]; };
+    auto out_of = [&](int b) { return output + in_off[b] + (int64_t)LIBBSC_HEADER_SIZE * b; };
+    if (npass > 0)
+        for (int k = 0; k < 2; ++k)
+            if (!c->batch_host[k] && hipHostMalloc((void**)&c->batch_host[k], (size_t)c->max_n + 64, hipHostMallocDefault) != hipSuccess) {
+                c->batch_host[k] = nullptr;
+                return ctx_fail(c, LIBBSC_GPU_NOT_ENOUGH_MEMORY, "batched compression: pinned pass buffers", hipSuccess);
+            }
+    const int threads = default_coder_threads();
+    std::vector<char> single((size_t)count, 0);
+    for (int b = 0; b < count; ++b) single[b] = pass_of[b] < 0;
+    std::thread coder_thread;                     // codes the previous pass while this one sorts
+    int rc = LIBBSC_NO_ERROR;
+    std::vector<std::vector<BatchBlock>> bufs(2);
+    std::vector<uint32_t> res((size_t)BATCH_MAX_BLOCKS * 16), adler((size_t)BATCH_MAX_BLOCKS);
+    for (int b = 0, p = 0; b < count && rc >= 0;) {
+        if (pass_of[b] < 0) { ++b; continue; }
+        int e = b;          // the pass: its members and the empty blocks between them, one contiguous range of the input
+        for (int q = b; q < count && (pass_of[q] == pass_of[b] || (pass_of[q] < 0 && sizes[q] == 0)); ++q) if (pass_of[q] == pass_of[b]) e = q + 1;
+        std::vector<BatchBlock>& blocks = bufs[p & 1];
+        blocks.assign((size_t)(e - b), BatchBlock());
+        // LZP of every member (libbsc.cpp:263-281), in parallel; without LZP there is nothing to spread over threads
+        auto prep = [&](int i) {
+            BatchBlock& B = blocks[i];
+            const int q = b + i, n = sizes[q];
+            B.b = q; B.mode = mode; B.lz = n;
+            if (pass_of[q] < 0) return;                                          // an empty block between members
+            if (n <= LIBBSC_HEADER_SIZE) {
+                if (dev) B.store = true;                                         // its bytes come back with the pass (rate -1: L = T)
+                else results[q] = bsc_store(in_of(q), out_of(q), n, features);
+                return;
+            }
+            if (mode != (mode & 0xff)) {
+                B.lzbuf = (unsigned char*)bigbuf_get((size_t)n);
+                const int r = B.lzbuf ? lzp_compress(in_of(q), B.lzbuf, n, lzpHashSize, lzpMinLen, features) : LIBBSC_NOT_ENOUGH_MEMORY;
+                if (r < LIBBSC_NO_ERROR) { B.mode &= 0xff; bigbuf_put(B.lzbuf); B.lzbuf = nullptr; }
+                else B.lz = r;
+            }
+            if (aux_rate(B.lz) < 2) { B.single = true; bigbuf_put(B.lzbuf); B.lzbuf = nullptr; return; }
+            B.sorted = true;
+        };
+        if (mode != (mode & 0xff)) run_bounded(e - b, threads, prep);
+        else for (int i = 0; i < e - b; ++i) prep(i);
+        u8* hb = c->batch_host[p & 1];     // free: the coder thread of the pass before last was joined before the previous pass's started
+        std::vector<int> psz((size_t)(e - b)), prate((size_t)(e - b));
+        std::vector<int64_t> at((size_t)(e - b) + 1, 0);                         // where block b + i's L lies in hb
+        int64_t pos = 0;
+        for (int i = 0; i < e - b; ++i) {
+            BatchBlock& B = blocks[i];
+            at[i] = pos;
+            if (dev) {                                                           // the pass is the caller's own range of HBM
+                psz[i] = sizes[b + i];
+                prate[i] = B.sorted ? aux_rate(B.lz) : -1;
+                pos += sizes[b + i];
+                continue;
+            }
+            psz[i] = B.sorted ? B.lz : 0;
+            prate[i] = B.sorted ? aux_rate(B.lz) : -1;
+            if (B.sorted) { memcpy(hb + pos, B.lzbuf ? B.lzbuf : in_of(B.b), (size_t)B.lz); pos += B.lz; }
+            if (B.lzbuf) { bigbuf_put(B.lzbuf); B.lzbuf = nullptr; }
+        }
+        if (pos > 0) {
+            const u8* src = dev ? din_of(b) : c->dL;
+            if (!dev && hipMemcpyAsync(c->dL, hb, (size_t)pos, hipMemcpyHostToDevice, c->stream) != hipSuccess) { rc = LIBBSC_GPU_ERROR; break; }
+            rc = bwt_batch_device(c, src, c->dL, psz.data(), e - b, prate.data(), res.data(), dev ? adler.data() : nullptr);
+            if (rc < 0) break;
+            if (hipMemcpyAsync(hb, c->dL, (size_t)pos, hipMemcpyDeviceToHost, c->stream) != hipSuccess || ctx_sync(c) != hipSuccess) { rc = LIBBSC_GPU_ERROR; break; }
+        }
+        for (int i = 0; i < e - b; ++i) {
+            BatchBlock& B = blocks[i];
+            if (B.single) single[B.b] = 1;
+            if (dev) B.adler = adler[i];
+            if (!B.sorted) continue;
+            const uint32_t* I = res.data() + 16 * (size_t)i;
+            B.index = (int)I[0];
+            B.num_indexes = (B.lz - 1) / aux_rate(B.lz);
+            for (int t = 0; t < B.num_indexes; ++t) B.indexes[t] = (int)I[t + 1] - 1;
+        }
+        if (coder_thread.joinable()) coder_thread.join();
+        auto code_pass = [c, &blocks, hb, at, dev, &in_of, &din_of, &out_of, results, sizes, coder, features, threads] {
+            run_bounded((int)blocks.size(), threads, [&](int i) {
+                const BatchBlock& B = blocks[i];
+                if (B.store) results[B.b] = bsc_store(hb + at[i], out_of(B.b), sizes[B.b], features);
+                else if (B.sorted) results[B.b] = code_sorted_block(c, dev ? nullptr : in_of(B.b), dev ? din_of(B.b) : nullptr, out_of(B.b), sizes[B.b],
+                                                                    B, hb + at[i], coder, features);
+            });
+        };
+        try { coder_thread = std::thread(code_pass); }
+        catch (const std::system_error&) { code_pass(); }                          // no thread to be had: code the pass here
+        b = e; ++p;
+    }
+    // the blocks of their own, beside the last pass's coding: through a pipe on this context (the GPU stage of one overlaps the host
+    // coding of the ones before it); the few it does not take (larger than the context, a too short sorter input) first, one by one
+    // (both use the context's pinned slots: never at the same time)
+    auto piped = [&](int b) { return pass_of[b] < 0 && sizes[b] <= c->max_n && (dev || sizes[b] > LIBBSC_HEADER_SIZE); };
+    for (int b = 0; b < count && rc >= 0; ++b)
+        if (single[b] && !piped(b))
+            results[b] = dev ? bscgpu_compress_device(c, din_of(b), out_of(b), sizes[b], blockSorter, coder, features)
+                             : compress_one_on_ctx(c, in_of(b), out_of(b), sizes[b], lzpHashSize, lzpMinLen, blockSorter, coder, features);
+    bscgpu_pipe* pipe = nullptr;
+    constexpr int PIPE_DEPTH = 4;
+    bool any = false;
+    for (int b = 0; b < count; ++b) any = any || (single[b] && piped(b));
+    if (any && rc >= 0 && bscgpu_pipe_create(c, PIPE_DEPTH, &pipe) < 0) {
+        pipe = nullptr;                                   // no pipe: one by one
+        for (int b = 0; b < count; ++b)
+            if (single[b] && piped(b))
+                results[b] = dev ? bscgpu_compress_device(c, din_of(b), out_of(b), sizes[b], blockSorter, coder, features)
+                                 : compress_one_on_ctx(c, in_of(b), out_of(b), sizes[b], lzpHashSize, lzpMinLen, blockSorter, coder, features);
+    }
+    if (pipe) {
+        std::deque<std::pair<int, int>> inflight;         // (block, ticket)
+        for (int b = 0; b < count; ++b) {
+            if (!single[b] || !piped(b)) continue;
+            if ((int)inflight.size() >= PIPE_DEPTH) { results[inflight.front().first] = bscgpu_pipe_wait(pipe, inflight.front().second); inflight.pop_front(); }
+            const int t = dev ? bscgpu_pipe_submit(pipe, din_of(b), out_of(b), sizes[b], blockSorter, coder, features)
+                              : bscgpu_pipe_submit_host(pipe, in_of(b), out_of(b), sizes[b], lzpHashSize, lzpMinLen, blockSorter, coder, features);
+            if (t < 0) results[b] = t; else inflight.push_back({b, t});
+        }
+        for (auto& ft : inflight) results[ft.first] = bscgpu_pipe_wait(pipe, ft.second);
+        bscgpu_pipe_destroy(pipe);
+    }
+    if (coder_thread.joinable()) coder_thread.join();
+    return rc;
+}
+
+static int batch_args(bscgpu_ctx* c, const void* in, const int* sizes, int count, unsigned char* output, int* results)
+{
+    if (!c || count < 0 || (count > 0 && (!sizes || !output || !results))) return LIBBSC_BAD_PARAMETER;
+    int64_t total = 0;
+    for (int b = 0; b < count; ++b) { if (sizes[b] < 0) return LIBBSC_BAD_PARAMETER; total += sizes[b]; }
+    if (total > 0 && !in) return LIBBSC_BAD_PARAMETER;
+    return LIBBSC_NO_ERROR;
+}
+
+extern "C" BSCGPU_API int bscgpu_compress_batch(bscgpu_ctx* c, const unsigned char* input, const int* sizes, int count, unsigned char* output,
+                                                int* results, int lzpHashSize, int lzpMinLen, int blockSorter, int coder, int features)
+{
+    const int rc = batch_args(c, input, sizes, count, output, results);
+    if (rc < 0 || count == 0) return rc;
+    return compress_batch_impl(c, input, nullptr, sizes, count, output, results, lzpHashSize, lzpMinLen, blockSorter, coder, features);
+}
+
+// Input in HBM: the passes are sorted straight from the caller's buffer, every block's Adler-32 comes from one segmented launch per
+// pass (st.hip: adler_batch_kernel); only L and, for a block that ends up stored, its own bytes cross PCIe.
+extern "C" BSCGPU_API int bscgpu_compress_batch_device(bscgpu_ctx* c, const void* dInput, const int* sizes, int count, unsigned char* output,
+                                                       int* results, int blockSorter, int coder, int features)
+{
+    const int rc = batch_args(c, dInput, sizes, count, output, results);
+    if (rc < 0 || count == 0) return rc;
+    static const unsigned char empty = 0;       // (a batch of empty blocks may come with no buffer at all)
+    return compress_batch_impl(c, nullptr, dInput ? (const unsigned char*)dInput : &empty, sizes, count, output, results, 0, 0,
+                               blockSorter, coder, features);
+}

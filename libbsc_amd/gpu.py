@@ -164,6 +164,58 @@ class GpuContext:
         rc = self._check(self.L.bscgpu_compress_device(self.h, _dptr(dInput), N.np_ptr(out), n, sorter, coder, features))
         return out[:rc]
 
+    # ---- batches of small blocks (one suffix sort per pass, include/bscgpu.h) ----------------
+    def bwt_batch(self, dT, sizes, aux=True, dL=None):
+        """BWT of every block of a batch laid out back to back in the uint8 device tensor dT -> [(L np.uint8, primary, indexes)];
+        primary / indexes as bsc_bwt_encode of the block alone (primary < 0: its error code; indexes None without aux)."""
+        import torch
+        sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32))
+        cnt = sz.size
+        out = dT if dL is None else dL
+        prim = np.zeros(max(cnt, 1), np.int32)
+        num = np.zeros(max(cnt, 1), np.uint8)
+        idx = np.zeros(16 * max(cnt, 1), np.int32)
+        self._check(self.L.bscgpu_bwt_batch_device(self.h, _dptr(dT), _dptr(out), N.np_ptr(sz), cnt, N.np_ptr(prim),
+                                                   N.np_ptr(num) if aux else None, N.np_ptr(idx) if aux else None))
+        torch.cuda.synchronize(out.device)
+        Lh = out[:int(sz.sum())].cpu().numpy() if cnt else np.zeros(0, np.uint8)
+        res, o = [], 0
+        for b in range(cnt):
+            n = int(sz[b])
+            res.append((Lh[o:o + n].copy(), int(prim[b]), [int(x) for x in idx[16 * b:16 * b + int(num[b])]] if aux else None))
+            o += n
+        return res
+
+    def _batch_results(self, out, sz, results):
+        blocks, o = [], 0
+        for b in range(sz.size):
+            r = int(results[b])
+            blocks.append(out[o:o + r].tobytes() if r >= 0 else r)
+            o += int(sz[b]) + 28
+        return blocks
+
+    def compress_batch(self, blocks, sorter=1, coder=1, lzp_hash=0, lzp_min=0, features=3):
+        """bsc_compress of every block (bytes / uint8 arrays) in one batched call -> list of compressed blocks (bytes), or the
+        libbsc error code of a block where bsc_compress would return one."""
+        arrs = [np.frombuffer(bytes(b), np.uint8) if not isinstance(b, np.ndarray) else np.asarray(b, np.uint8).ravel() for b in blocks]
+        sz = np.array([a.size for a in arrs], np.int32)
+        inp = np.concatenate(arrs) if arrs else np.zeros(0, np.uint8)
+        inp = np.ascontiguousarray(inp) if inp.size else np.zeros(1, np.uint8)
+        out = np.empty(int(sz.sum()) + 28 * sz.size + 1, np.uint8)
+        results = np.zeros(max(sz.size, 1), np.int32)
+        self._check(self.L.bscgpu_compress_batch(self.h, N.np_ptr(inp), N.np_ptr(sz), sz.size, N.np_ptr(out), N.np_ptr(results),
+                                                 lzp_hash, lzp_min, sorter, coder, features))
+        return self._batch_results(out, sz, results)
+
+    def compress_batch_device(self, dT, sizes, sorter=1, coder=1, features=3):
+        """compress_batch for blocks laid out back to back in a uint8 device tensor (no LZP, as compress_device)"""
+        sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32))
+        out = np.empty(int(sz.sum()) + 28 * sz.size + 1, np.uint8)
+        results = np.zeros(max(sz.size, 1), np.int32)
+        self._check(self.L.bscgpu_compress_batch_device(self.h, _dptr(dT), N.np_ptr(sz), sz.size, N.np_ptr(out), N.np_ptr(results),
+                                                        sorter, coder, features))
+        return self._batch_results(out, sz, results)
+
     def pipe(self, depth=2, reuse_outputs=False):
         return Pipe(self, depth, reuse_outputs)
 
@@ -199,6 +251,14 @@ class GpuContext:
         out = (C.c_double * 6)()
         self.L.bscgpu_last_stage_ms(self.h, out)
         return list(out)
+
+
+def batch_plan(sizes, sorter=1, cap=64 << 20):
+    """bscgpu_batch_plan: the pass of every block of a batch, -1 for the single-block path -> (passes, list)"""
+    sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32))
+    pass_of = np.zeros(max(sz.size, 1), np.int32)
+    n = N.lib().bscgpu_batch_plan(N.np_ptr(sz), sz.size, sorter, int(cap), N.np_ptr(pass_of))
+    return int(n), [int(x) for x in pass_of[:sz.size]]
 
 
 def coder_pool_stats(reset=False):

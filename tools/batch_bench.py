@@ -1,0 +1,184 @@
+"""Batched compression of many small blocks against the per-block paths (include/bscgpu.h: bscgpu_compress_batch).
+
+Workloads (inputs from synth_text_v1 seeds, nothing read from outside the tree):
+  W1  1024 x 64 KiB      W2  128 x 512 KiB      W3  1000 seeded sizes from 1 KiB to 900 KiB
+Each through
+  batch         GpuContext.compress_batch on one context (64 MiB + 4096), host input
+  batch_device  GpuContext.compress_batch_device on the same context, the blocks back to back in HBM
+  pipe          the existing Pipe: bench.py's shape (5 contexts, depth 2, one submitting thread per pipe), blocks from HBM
+  dropin16      16 threads calling this library's drop-in bsc_compress (GPU default contexts: NOT a CPU baseline)
+  ref_cpu16     16 threads calling the compiled reference's bsc_compress, one block per thread without its own
+                threads (features = fast mode only): the reference's block-parallel CPU mode (needs oracle/_ref)
+reporting MB/s, CPU-seconds per MB (this process's user + system time) and whether every output equals the pipe's (the
+single-block path).  Also the GPU time of one batched 64 MiB pass of W1 (bscgpu_bwt_batch_device) beside one 64 MiB block's BWT.
+One JSON line per measurement on stdout.
+    python tools/batch_bench.py [--reps 3] [--workloads W1,W2,W3]
+"""
+import argparse
+import json
+import os
+import resource
+import sys
+import threading
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def cpu_s():
+    r = resource.getrusage(resource.RUSAGE_SELF)
+    return r.ru_utime + r.ru_stime
+
+
+def workload(name):
+    from libbsc_amd.synth import synth_text_v1
+    rng = np.random.default_rng({"W1": 1, "W2": 2, "W3": 3}[name])
+    if name == "W1":
+        sizes = [64 << 10] * 1024
+    elif name == "W2":
+        sizes = [512 << 10] * 128
+    else:
+        sizes = [int(x) for x in rng.integers(1 << 10, 900 << 10, 1000)]
+    blocks = [synth_text_v1(1000 + i, n) for i, n in enumerate(sizes)]
+    return sizes, blocks
+
+
+def timed(fn):
+    c0, t0 = cpu_s(), time.perf_counter()
+    out = fn()
+    return out, time.perf_counter() - t0, cpu_s() - c0
+
+
+def run_batch(ctx, blocks, sorter, coder):
+    return ctx.compress_batch(blocks, sorter, coder)
+
+
+def run_pipe(pipes, dblocks, sizes, sorter, coder, depth):
+    out = [None] * len(sizes)
+
+    def worker(k):
+        p, tickets = pipes[k], []
+        for i in range(k, len(sizes), len(pipes)):
+            tickets.append((i, p.submit(dblocks[i], sizes[i], sorter, coder, 3)))
+            if len(tickets) >= depth:
+                j, t = tickets.pop(0)
+                out[j] = bytes(p.wait(t))
+        for j, t in tickets:
+            out[j] = bytes(p.wait(t))
+
+    th = [threading.Thread(target=worker, args=(k,)) for k in range(len(pipes))]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    return out
+
+
+def run_16(blocks, one):
+    out = [None] * len(blocks)
+    nxt = [0]
+    lock = threading.Lock()
+
+    def worker():
+        while True:
+            with lock:
+                i = nxt[0]
+                nxt[0] += 1
+            if i >= len(blocks):
+                return
+            out[i] = one(blocks[i])
+
+    th = [threading.Thread(target=worker) for _ in range(16)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--workloads", default="W1,W2,W3")
+    ap.add_argument("--coder", type=int, default=1)
+    ap.add_argument("--contexts", type=int, default=5)
+    ap.add_argument("--depth", type=int, default=2)
+    args = ap.parse_args()
+    import torch
+    from libbsc_amd import GpuContext
+    from libbsc_amd import _native as N
+    from libbsc_amd import api
+    from oracle.refbind import Ref, REF_SO
+    refc = Ref() if os.path.exists(REF_SO) else None
+    sorter, coder = 1, args.coder
+    ctx = GpuContext(0, max_n=(64 << 20) + 4096)
+    pctx = [GpuContext(0, max_n=(1 << 20) + 4096) for _ in range(args.contexts)]
+    pipes = [c.pipe(args.depth) for c in pctx]
+    try:
+        for name in args.workloads.split(","):
+            sizes, blocks = workload(name)
+            mb = sum(sizes) / 1e6
+            dblocks = [torch.from_numpy(b).cuda() for b in blocks]
+            torch.cuda.synchronize()
+            ref = run_pipe(pipes, dblocks, sizes, sorter, coder, args.depth)         # warm-up + the single-block outputs
+            run_batch(ctx, blocks[:8], sorter, coder)
+            flat = torch.from_numpy(np.concatenate(blocks)).cuda()
+            legs = ["batch", "batch_device", "pipe", "dropin16"] + (["ref_cpu16"] if refc else [])
+            for leg in legs:
+                best = None
+                ok = True
+                for _ in range(args.reps):
+                    if leg == "batch":
+                        out, wall, cpu = timed(lambda: run_batch(ctx, blocks, sorter, coder))
+                    elif leg == "pipe":
+                        out, wall, cpu = timed(lambda: run_pipe(pipes, dblocks, sizes, sorter, coder, args.depth))
+                    elif leg == "batch_device":
+                        out, wall, cpu = timed(lambda: ctx.compress_batch_device(flat, sizes, sorter, coder))
+                    elif leg == "dropin16":
+                        out, wall, cpu = timed(lambda: run_16(blocks, lambda b: bytes(api.bsc_compress(b, sorter, coder))))
+                    else:
+                        out, wall, cpu = timed(lambda: run_16(blocks, lambda b: refc.compress(b, sorter, coder, features=1)))
+                    ok = ok and all(a == b for a, b in zip(out, ref))
+                    if best is None or wall < best[0]:
+                        best = (wall, cpu)
+                print(json.dumps({"workload": name, "leg": leg, "blocks": len(sizes), "MB": round(mb, 2), "MB_s": round(mb / best[0], 1),
+                                  "ms": round(best[0] * 1e3, 1), "cpu_s_per_MB": round(best[1] / mb, 4),
+                                  "identical_to_single_block_path": bool(ok)}), flush=True)
+            if name == "W1":
+                # one 64 MiB batched pass of W1's blocks: GPU time of the sort alone
+                flat = torch.from_numpy(np.concatenate(blocks)).cuda()
+                dL = torch.empty_like(flat)
+                sz = np.array(sizes, np.int32)
+                prim = np.zeros(len(sizes), np.int32)
+                num = np.zeros(len(sizes), np.uint8)
+                idx = np.zeros(16 * len(sizes), np.int32)
+                torch.cuda.synchronize()
+                ts = []
+                for _ in range(max(args.reps, 3)):
+                    t0 = time.perf_counter()
+                    rc = ctx.L.bscgpu_bwt_batch_device(ctx.h, flat.data_ptr(), dL.data_ptr(), N.np_ptr(sz), len(sizes), N.np_ptr(prim),
+                                                       N.np_ptr(num), N.np_ptr(idx))
+                    ts.append(time.perf_counter() - t0)
+                    assert rc == 0, rc
+                one = torch.from_numpy(np.concatenate(blocks)).cuda()
+                t1 = []
+                for _ in range(max(args.reps, 3)):
+                    t0 = time.perf_counter()
+                    ctx.bwt_device(one, dL, one.numel(), None)
+                    t1.append(time.perf_counter() - t0)
+                print(json.dumps({"workload": "W1", "leg": "bwt_batch_device_64MiB_pass", "ms": round(min(ts) * 1e3, 2),
+                                  "single_64MiB_block_bwt_ms": round(min(t1) * 1e3, 2)}), flush=True)
+            del dblocks
+    finally:
+        for p in pipes:
+            p.close()
+        for c in pctx:
+            c.close()
+        ctx.close()
+
+
+if __name__ == "__main__":
+    main()
