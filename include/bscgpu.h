@@ -130,6 +130,40 @@ BSCGPU_API int bscgpu_compress_batch(bscgpu_ctx* ctx, const unsigned char* input
 BSCGPU_API int bscgpu_compress_batch_device(bscgpu_ctx* ctx, const void* dInput, const int* sizes, int count, unsigned char* output,
                                             int* results, int blockSorter, int coder, int features);
 
+/* ---- batched decompression: one inverse-BWT pass for many blocks -------------
+ * bscgpu_unbwt_batch_device: L of `count` blocks back to back in HBM (block b at Σ sizes[0..b), primary[b] its 1-based
+ *   primary index) -> T in the same layout; dT may be dL.  Passes of consecutive blocks, at most max_n bytes and
+ *   min(4096, max_n / 256 + 16) blocks each.  results[b] = what bscgpu_unbwt returns for block b alone (0, LIBBSC_DATA_CORRUPT,
+ *   LIBBSC_NOT_SUPPORTED: the step cap, use a host walk; LIBBSC_BAD_PARAMETER: primary out of 1..n_b; LIBBSC_GPU_NOT_ENOUGH_MEMORY:
+ *   n_b > max_n).  A failed block's T range is not written; the other blocks decode as if alone.  Returns 0 or a batch-level error.
+ * bscgpu_decompress_batch_sizes: reads the headers only.  data_sizes[b] = the block's dataSize, 0 where its header cannot be
+ *   read; returns the decoded total (Σ data_sizes) or LIBBSC_BAD_PARAMETER.
+ * bscgpu_decompress_batch: compressed blocks back to back in host memory (block b: in_sizes[b] bytes).  Block b decodes to
+ *   output + Σ data_sizes[0..b) (the layout bscgpu_compress_batch took its input in); out_cap must hold the total.
+ *   results[b] = what bsc_decompress(block b, in_sizes[b], ..., dataSize, features) returns, error codes included — with one
+ *   caveat: a forged block with valid checksums but inconsistent aux indexes may decode here where bsc_decompress's host walk
+ *   rejects it (bsc_decompress itself decodes such blocks from BSC_GPU_UNBWT_MIN_N on: the GPU walk ignores aux indexes).
+ *   BWT blocks of 2 .. max_n bytes share one GPU inverse BWT per pass (QLFC decoding on the host threads, pass k + 1's
+ *   overlapping pass k's GPU work; Adler-32 of the output on the GPU); stored, ST3..ST8, larger and damaged blocks go
+ *   through bsc_decompress itself.  input and output must not overlap.
+ * bscgpu_decompress_batch_device: the same with output in HBM (dOutput): without LZP the walk writes each block straight
+ *   to its place; LZP blocks are undone on the host and copied up.
+ * Both return 0 or a batch-level error: LIBBSC_BAD_PARAMETER (null pointers, count < 0, in_sizes[b] < 0, out_cap below
+ *   the total) with nothing written, or a GPU failure.  Memory: the batch table and the pinned pass buffers of the
+ *   compress batch.
+ * bscgpu_unbwt_batch_plan: the routing rule as a pure function.  sizes[b] = block b's BWT length (a bound: its dataSize),
+ *   or -1 for a block no pass takes (stored, ST3..ST8, a header that fails).  pass_of[b] = its pass, or -1 when
+ *   sizes[b] < 2 or > cap; passes take consecutive such blocks (other blocks between them do not end a pass), at most
+ *   cap bytes and min(4096, cap / 256 + 16) blocks each.  Returns the number of passes (cap = the context's max_n). */
+BSCGPU_API int bscgpu_unbwt_batch_plan(const int* sizes, int count, int64_t cap, int* pass_of);
+BSCGPU_API int bscgpu_unbwt_batch_device(bscgpu_ctx* ctx, const void* dL, void* dT, const int* sizes, int count, const int* primary,
+                                         int* results);
+BSCGPU_API int64_t bscgpu_decompress_batch_sizes(const unsigned char* input, const int* in_sizes, int count, int* data_sizes);
+BSCGPU_API int bscgpu_decompress_batch(bscgpu_ctx* ctx, const unsigned char* input, const int* in_sizes, int count, unsigned char* output,
+                                       int64_t out_cap, int* results, int features);
+BSCGPU_API int bscgpu_decompress_batch_device(bscgpu_ctx* ctx, const unsigned char* input, const int* in_sizes, int count, void* dOutput,
+                                              int64_t out_cap, int* results, int features);
+
 /* Pipelined variant: up to `depth` (<= 8) blocks in flight on one GPU.  submit() runs the GPU stage of a block
  * (Adler-32, sort transform, QLFC front end, D2H of the run arrays) on the calling thread and hands the host stage
  * (QLFC modelling + range coding, one task per sub-block; container) to the process's coder threads, so block i+1 sorts

@@ -82,6 +82,12 @@ def lib():
     L.bscgpu_bwt_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp]
     L.bscgpu_compress_batch.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.bscgpu_compress_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int]
+    L.bscgpu_unbwt_batch_plan.argtypes = [vp, C.c_int, C.c_int64, vp]
+    L.bscgpu_unbwt_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp]
+    L.bscgpu_decompress_batch_sizes.argtypes = [vp, vp, C.c_int, vp]
+    L.bscgpu_decompress_batch_sizes.restype = C.c_int64
+    L.bscgpu_decompress_batch.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int64, vp, C.c_int]
+    L.bscgpu_decompress_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int64, vp, C.c_int]
     if hasattr(L, "bscgpu_compress_device"):
         L.bscgpu_compress_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]
     _lib = L

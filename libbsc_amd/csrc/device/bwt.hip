@@ -1079,15 +1079,22 @@ int bwt_device(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_t n64, int64
 
 // One batched pass (see bwt_batch_pack_kernel): the block table goes up, one transform of the whole pass runs, the per-block indexes come
 // back with the pass's last sync.  Same retry rule as bwt_device.
-int bwt_batch_device(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, const int* sizes, int count, const int* rates, u32* res, u32* adler_host)
+int batch_tab_ensure(bscgpu_ctx* c)
 {
-    if (count <= 0 || count > BATCH_MAX_BLOCKS) return BSC_BAD_PARAMETER;
     constexpr size_t TAB_WORDS = (size_t)(BATCH_MAX_BLOCKS + 1) + BATCH_MAX_BLOCKS + 16 * (size_t)BATCH_MAX_BLOCKS + BATCH_MAX_BLOCKS;   // offsets, rates, indexes, checksums
     if (!c->batch_tab && hipMalloc((void**)&c->batch_tab, TAB_WORDS * 4) != hipSuccess) {
         (void)hipGetLastError(); c->batch_tab = nullptr;
         return ctx_fail(c, BSC_GPU_NOT_ENOUGH_MEMORY, "batched BWT: block table", hipSuccess);
     }
     c->batch_bytes = TAB_WORDS * 4;
+    return BSC_NO_ERROR;
+}
+
+int bwt_batch_device(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, const int* sizes, int count, const int* rates, u32* res, u32* adler_host)
+{
+    if (count <= 0 || count > BATCH_MAX_BLOCKS) return BSC_BAD_PARAMETER;
+    const int trc = batch_tab_ensure(c);
+    if (trc < 0) return trc;
     std::vector<u32> tab((size_t)2 * count + 1);
     u64 total = 0;
     for (int b = 0; b < count; ++b) { tab[b] = (u32)total; total += (u64)sizes[b]; }

@@ -19,6 +19,7 @@ typedef unsigned char      u8;
 #define BSC_NOT_ENOUGH_MEMORY      -2
 #define BSC_NOT_COMPRESSIBLE       -3
 #define BSC_NOT_SUPPORTED          -4
+#define BSC_DATA_CORRUPT           -6
 #define BSC_GPU_ERROR              -7
 #define BSC_GPU_NOT_SUPPORTED      -8
 #define BSC_GPU_NOT_ENOUGH_MEMORY  -9
@@ -195,7 +196,17 @@ constexpr int BATCH_MAX_BLOCKS = 4096;
 // adler_host != nullptr: also every block's Adler-32 of dT_user (st.hip: adler_batch_kernel, one launch), back with the same sync.
 int bwt_batch_device(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, const int* sizes, int count, const int* rates, u32* res,
                      u32* adler_host = nullptr);
-void launch_adler_batch(bscgpu_ctx* c, const u8* d, const u32* doff, u32 count, u32* dout);     // st.hip (asynchronous)
+// (stride 2: doff holds a (start, end) pair per block, blocks anywhere in d)
+void launch_adler_batch(bscgpu_ctx* c, const u8* d, const u32* doff, u32 count, u32* dout, u32 stride = 1);     // st.hip (asynchronous)
+int batch_tab_ensure(bscgpu_ctx* c);       // bwt.hip: batch_tab on first use
+// Batched inverse-BWT pass (unbwt.hip): `count` <= unbwt_batch_max_blocks(max_n) blocks, L of sizes[b] bytes back to back at
+// dL (sum <= max_n); idx[b] = the block's primary index (1..n_b), 0 = not decoded (nothing written).  Block b's T goes to out + dst[b]
+// (dst[b] + n_b < 2^32; out may be dL).  res[b] = 0, LIBBSC_DATA_CORRUPT or LIBBSC_NOT_SUPPORTED (0 for a block not decoded).
+// adler != nullptr: adler[b] = Adler-32 of out[dst[b], dst[b] + n_b); t_host != nullptr: out[0, max(dst[b] + n_b)) also comes down
+// there.  Both with the pass's last sync.
+int unbwt_batch_max_blocks(int64_t cap);
+int unbwt_batch_pass(bscgpu_ctx* c, const u8* dL, u8* out, const int* sizes, const int* idx, int count, const u32* dst, int* res,
+                     u32* adler, u8* t_host);
 int adler32_device(bscgpu_ctx* c, const u8* d, int64_t n, u32* out);
 void launch_seg_scan(bscgpu_ctx* c, u32 num_chunks);
 int qlfc_front_split(bscgpu_ctx* c, const u8* dL, u32 n, int nblocks, int* start, int* size);

@@ -195,10 +195,11 @@ __global__ __launch_bounds__(WG) void adler_kernel(const u8* __restrict__ T, u64
 // Segmented Adler-32: one workgroup per block of a batch (blocks back to back, off[0..count]), every block's checksum in one launch.
 // Lanes read consecutive bytes (blocks start anywhere, so no 16-byte loads); per lane a = sum d, b = sum (end - p) d, folded as adler_kernel's
 // chunks are: s1 = 1 + a, s2 = n + b (mod 65521).
-__global__ __launch_bounds__(WG) void adler_batch_kernel(const u8* __restrict__ T, const u32* __restrict__ off, u32* __restrict__ out)
+// (stride 2: off holds a (start, end) pair per block)
+__global__ __launch_bounds__(WG) void adler_batch_kernel(const u8* __restrict__ T, const u32* __restrict__ off, u32* __restrict__ out, u32 stride)
 {
     __shared__ u64 red[2 * WAVES];
-    const u32 start = off[blockIdx.x], end = off[blockIdx.x + 1];
+    const u32 start = off[stride * blockIdx.x], end = off[stride * blockIdx.x + 1];
     u64 a = 0, b = 0;
     for (u32 p = start + threadIdx.x; p < end; p += WG) { const u32 d = T[p]; a += d; b += (u64)d * (end - p); }
     a = wave_sum_u64(a); b = wave_sum_u64(b);
@@ -213,10 +214,10 @@ __global__ __launch_bounds__(WG) void adler_batch_kernel(const u8* __restrict__ 
     }
 }
 
-void launch_adler_batch(bscgpu_ctx* c, const u8* d, const u32* doff, u32 count, u32* dout)
+void launch_adler_batch(bscgpu_ctx* c, const u8* d, const u32* doff, u32 count, u32* dout, u32 stride)
 {
     prof_begin(c, BSCGPU_K_MISC, 0, 0);
-    hipLaunchKernelGGL(adler_batch_kernel, dim3(count), dim3(WG), 0, c->stream, d, doff, dout);
+    hipLaunchKernelGGL(adler_batch_kernel, dim3(count), dim3(WG), 0, c->stream, d, doff, dout, stride);
     prof_end(c);
 }
 

@@ -1617,14 +1617,7 @@ static int code_sorted_block(bscgpu_ctx* c, const unsigned char* input, const un
     return result + LIBBSC_HEADER_SIZE;
 }
 
-// n tasks on at most `threads` threads (par.h: what cannot get a thread runs on the caller)
-template <class F>
-static void run_bounded(int n, int threads, F&& fn)
-{
-    if (n <= 0) return;
-    std::atomic<int> next{0};
-    run_tasks(threads < n ? threads : n, [&](int) { for (int i; (i = next.fetch_add(1)) < n;) fn(i); });
-}
+int bschost::coder_threads() { return default_coder_threads(); }
 
 // One implementation for both entry points: host input (`input`, LZP per block) or input in HBM (`dInput`, no LZP).
 static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const unsigned char* dInput, const int* sizes, int count,

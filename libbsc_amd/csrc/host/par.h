@@ -5,6 +5,7 @@
 // on the calling thread instead, so the result is the same and only the parallelism degrades.  The last task always
 // runs on the caller (one thread fewer to create).
 #pragma once
+#include <atomic>
 #include <cstddef>
 #include <system_error>
 #include <thread>
@@ -26,6 +27,18 @@ inline void run_tasks(int n, F&& fn)
     for (int b = next; b < n; ++b) fn(b);
     for (auto& t : pool) t.join();
 }
+
+// n tasks on at most `threads` threads (what cannot get a thread runs on the caller)
+template <class F>
+inline void run_bounded(int n, int threads, F&& fn)
+{
+    if (n <= 0) return;
+    std::atomic<int> next{0};
+    run_tasks(threads < n ? threads : n, [&](int) { for (int i; (i = next.fetch_add(1)) < n;) fn(i); });
+}
+
+// the coder threads a batch spreads its blocks over (block.cpp: the CPUs the process may use, affinity and cgroup quota, 4..64)
+int coder_threads();
 
 // Block-sized scratch that lives for one block (the LZP output, the staging area of the parallel LZP encoder).  A fresh allocation of that
 // size is an mmap per block: 16 K page faults and 64 MiB of page zeroing each time, under the process's mmap lock with thirty threads around.

@@ -216,6 +216,58 @@ class GpuContext:
                                                         sorter, coder, features))
         return self._batch_results(out, sz, results)
 
+    # ---- batched decompression (one inverse-BWT pass for many blocks, include/bscgpu.h) -------
+    def unbwt_batch(self, dL, sizes, primary, dT=None):
+        """inverse BWT of every block of a batch laid out back to back in the uint8 device tensor dL (primary: 1-based indexes) ->
+        (T tensor in the same layout, results list as bscgpu_unbwt returns them per block); in place unless dT is given"""
+        sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32))
+        prim = np.ascontiguousarray(np.asarray(primary, dtype=np.int32))
+        assert prim.size == sz.size
+        out = dL if dT is None else dT
+        results = np.zeros(max(sz.size, 1), np.int32)
+        self._check(self.L.bscgpu_unbwt_batch_device(self.h, _dptr(dL), _dptr(out), N.np_ptr(sz), sz.size, N.np_ptr(prim), N.np_ptr(results)))
+        return out, [int(x) for x in results[:sz.size]]
+
+    @staticmethod
+    def _pack(blocks):
+        arrs = [np.frombuffer(bytes(b), np.uint8) if not isinstance(b, np.ndarray) else np.asarray(b, np.uint8).ravel() for b in blocks]
+        isz = np.array([a.size for a in arrs], np.int32)
+        inp = np.concatenate(arrs) if arrs else np.zeros(0, np.uint8)
+        return (np.ascontiguousarray(inp) if inp.size else np.zeros(1, np.uint8)), isz
+
+    def decompress_batch(self, blocks, features=3):
+        """bsc_decompress of every compressed block (bytes / uint8 arrays) in one batched call -> list of the decoded blocks (bytes),
+        or the libbsc error code of a block where bsc_decompress would return one"""
+        inp, isz = self._pack(blocks)
+        ds = np.zeros(max(isz.size, 1), np.int32)
+        total = self._check(int(self.L.bscgpu_decompress_batch_sizes(N.np_ptr(inp), N.np_ptr(isz), isz.size, N.np_ptr(ds))))
+        out = np.empty(max(total, 1), np.uint8)
+        results = np.zeros(max(isz.size, 1), np.int32)
+        self._check(self.L.bscgpu_decompress_batch(self.h, N.np_ptr(inp), N.np_ptr(isz), isz.size, N.np_ptr(out), total,
+                                                   N.np_ptr(results), features))
+        res, o = [], 0
+        for b in range(isz.size):
+            n = int(ds[b])
+            res.append(out[o:o + n].tobytes() if results[b] == 0 else int(results[b]))
+            o += n
+        return res
+
+    def decompress_batch_device(self, blocks, features=3):
+        """decompress_batch with the output in HBM -> (uint8 device tensor, offsets[count + 1], results list): block b's bytes are
+        out[offsets[b]:offsets[b + 1]] where results[b] == 0"""
+        import torch
+        inp, isz = self._pack(blocks)
+        ds = np.zeros(max(isz.size, 1), np.int32)
+        total = self._check(int(self.L.bscgpu_decompress_batch_sizes(N.np_ptr(inp), N.np_ptr(isz), isz.size, N.np_ptr(ds))))
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=f"cuda:{self.device}")
+        results = np.zeros(max(isz.size, 1), np.int32)
+        self._check(self.L.bscgpu_decompress_batch_device(self.h, N.np_ptr(inp), N.np_ptr(isz), isz.size, _dptr(out), total,
+                                                          N.np_ptr(results), features))
+        offs = [0]
+        for b in range(isz.size):
+            offs.append(offs[-1] + int(ds[b]))
+        return out[:total], offs, [int(x) for x in results[:isz.size]]
+
     def pipe(self, depth=2, reuse_outputs=False):
         return Pipe(self, depth, reuse_outputs)
 
@@ -258,6 +310,14 @@ def batch_plan(sizes, sorter=1, cap=64 << 20):
     sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32))
     pass_of = np.zeros(max(sz.size, 1), np.int32)
     n = N.lib().bscgpu_batch_plan(N.np_ptr(sz), sz.size, sorter, int(cap), N.np_ptr(pass_of))
+    return int(n), [int(x) for x in pass_of[:sz.size]]
+
+
+def unbwt_batch_plan(sizes, cap=64 << 20):
+    """bscgpu_unbwt_batch_plan: sizes[b] = a BWT block's length, -1 for a block of another route -> (passes, pass of every block)"""
+    sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32))
+    pass_of = np.zeros(max(sz.size, 1), np.int32)
+    n = N.lib().bscgpu_unbwt_batch_plan(N.np_ptr(sz), sz.size, int(cap), N.np_ptr(pass_of))
     return int(n), [int(x) for x in pass_of[:sz.size]]
 
 

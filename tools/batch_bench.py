@@ -13,6 +13,15 @@ reporting MB/s, CPU-seconds per MB (this process's user + system time) and wheth
 single-block path).  Also the GPU time of one batched 64 MiB pass of W1 (bscgpu_bwt_batch_device) beside one 64 MiB block's BWT.
 One JSON line per measurement on stdout.
     python tools/batch_bench.py [--reps 3] [--workloads W1,W2,W3]
+
+--decode: the decode side on W1..W3 and W4 = 8 x 64 MiB, blocks compressed with -e1 / -e2, without LZP and with
+-H15 -M128 (--configs picks some), MB/s of decoded output for
+  batch         GpuContext.decompress_batch (host output)
+  batch_device  GpuContext.decompress_batch_device (output in HBM)
+  dropin16      16 threads calling this library's drop-in bsc_decompress
+  ref_cpu16     16 threads calling the compiled reference's bsc_decompress, one block per thread (features = fast mode only)
+every output checked against the original.  --decode --profile-pass: one decompress_batch of W1 only (for rocprofv3).
+    python tools/batch_bench.py --decode [--reps 2] [--workloads W1,W2,W3,W4] [--configs e1,e2,e1-lzp,e2-lzp]
 """
 import argparse
 import json
@@ -35,11 +44,13 @@ def cpu_s():
 
 def workload(name):
     from libbsc_amd.synth import synth_text_v1
-    rng = np.random.default_rng({"W1": 1, "W2": 2, "W3": 3}[name])
+    rng = np.random.default_rng({"W1": 1, "W2": 2, "W3": 3, "W4": 4}[name])
     if name == "W1":
         sizes = [64 << 10] * 1024
     elif name == "W2":
         sizes = [512 << 10] * 128
+    elif name == "W4":
+        sizes = [64 << 20] * 8
     else:
         sizes = [int(x) for x in rng.integers(1 << 10, 900 << 10, 1000)]
     blocks = [synth_text_v1(1000 + i, n) for i, n in enumerate(sizes)]
@@ -99,14 +110,75 @@ def run_16(blocks, one):
     return out
 
 
+CONFIGS = {"e1": (1, 0, 0), "e2": (2, 0, 0), "e1-lzp": (1, 15, 128), "e2-lzp": (2, 15, 128)}
+
+
+def decode_main(args):
+    from libbsc_amd import GpuContext
+    from libbsc_amd import api
+    from oracle.refbind import Ref, REF_SO
+    refc = Ref() if os.path.exists(REF_SO) else None
+    ctx = GpuContext(0, max_n=(64 << 20) + 4096)
+    try:
+        for name in args.workloads.split(","):
+            sizes, datas = workload(name)
+            want = [d.tobytes() for d in datas]
+            mb = sum(sizes) / 1e6
+            for cfg in args.configs.split(","):
+                coder, lzp_hash, lzp_min = CONFIGS[cfg]
+                blocks = ctx.compress_batch(datas, 1, coder, lzp_hash, lzp_min)
+                assert all(isinstance(b, bytes) for b in blocks)
+                if args.profile_pass:
+                    got = ctx.decompress_batch(blocks)
+                    print(json.dumps({"workload": name, "config": cfg, "leg": "profile_pass", "ok": got == want}), flush=True)
+                    continue
+                ctx.decompress_batch(blocks[:8])                   # warm-up: pinned buffers, batch table
+                legs = ["batch", "batch_device", "dropin16"] + (["ref_cpu16"] if refc else [])
+                for leg in legs:
+                    best, ok = None, True
+                    for _ in range(args.reps):
+                        if leg == "batch":
+                            out, wall, cpu = timed(lambda: ctx.decompress_batch(blocks))
+                        elif leg == "batch_device":
+                            def dev():
+                                T, offs, res = ctx.decompress_batch_device(blocks)
+                                import torch
+                                torch.cuda.synchronize()
+                                return T, offs, res
+                            (T, offs, res), wall, cpu = timed(dev)
+                            Th = T.cpu().numpy()
+                            out = [Th[offs[b]:offs[b + 1]].tobytes() if res[b] == 0 else res[b] for b in range(len(blocks))]
+                            del T
+                        elif leg == "dropin16":
+                            out, wall, cpu = timed(lambda: run_16(blocks, lambda b: api.bsc_decompress(b)))
+                        else:
+                            out, wall, cpu = timed(lambda: run_16(blocks, lambda b: refc.decompress(b, features=1)))
+                        ok = ok and out == want
+                        if best is None or wall < best[0]:
+                            best = (wall, cpu)
+                    print(json.dumps({"workload": name, "config": cfg, "leg": leg, "blocks": len(sizes), "MB": round(mb, 2),
+                                      "MB_s": round(mb / best[0], 1), "ms": round(best[0] * 1e3, 1),
+                                      "cpu_s_per_MB": round(best[1] / mb, 4), "identical_to_input": bool(ok)}), flush=True)
+            del datas, want
+    finally:
+        ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--workloads", default="W1,W2,W3")
+    ap.add_argument("--workloads", default=None)
     ap.add_argument("--coder", type=int, default=1)
     ap.add_argument("--contexts", type=int, default=5)
     ap.add_argument("--depth", type=int, default=2)
+    ap.add_argument("--decode", action="store_true", help="the decode side: decompress_batch against the per-block paths")
+    ap.add_argument("--configs", default="e1,e2,e1-lzp,e2-lzp")
+    ap.add_argument("--profile-pass", action="store_true", help="with --decode: one decompress_batch per workload and config, nothing timed")
     args = ap.parse_args()
+    if args.decode:
+        args.workloads = args.workloads or "W1,W2,W3,W4"
+        return decode_main(args)
+    args.workloads = args.workloads or "W1,W2,W3"
     import torch
     from libbsc_amd import GpuContext
     from libbsc_amd import _native as N
