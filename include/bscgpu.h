@@ -189,10 +189,6 @@ BSCGPU_API int  bscgpu_pipe_create(bscgpu_ctx* ctx, int depth, bscgpu_pipe** out
 /* How the pool has coded the pipes' blocks so far: out[0] blocks as eight scalar tasks, [1] as four pair tasks, [2] as one eight-lane
  * task, [3] blocks on the host model (one task per sub-block).  reset != 0 clears the counts.  (bench.py reports them.) */
 BSCGPU_API void bscgpu_coder_pool_stats(uint64_t out[4], int reset);
-/* ... of the eight-lane blocks, how many were coded two at a time in the sixteen lanes of 512-bit registers (round 6: half the CPU time per
- * block at equal throughput on long jobs, a few per cent slower on 20-block jobs: opt-in with BSC_RC_X16=1 on AVX-512F/VL/BW hosts;
- * BSC_RC_X16_WAIT_MS is how long a block waits for a partner: 15) */
-BSCGPU_API uint64_t bscgpu_coder_pool_x16_blocks(int reset);
 /* Where a job ends: `blocks` more blocks will be submitted to the pipes of this process (all pipes together), which drive `gpus` GPUs.
  * The blocks whose GPU stages END last are then coded as short tasks — per GPU the last one as eight single-stream tasks, the few
  * before it as pairs (two fewer than the contexts that interleave on a GPU) (BSC_TAIL_SINGLES / BSC_TAIL_PAIRS) — whatever their order of submission (several contexts interleave on a GPU,
@@ -200,8 +196,8 @@ BSCGPU_API uint64_t bscgpu_coder_pool_x16_blocks(int reset);
  * marking blocks BSCGPU_FEATURE_LOW_LATENCY at submission; blocks < 0 withdraws the announcement.  Output is identical either way. */
 BSCGPU_API int  bscgpu_coder_pool_expect(long long blocks, int gpus);
 /* The pool's own record of its tasks (recorded when BSCGPU_POOL_TRACE=1 is in the environment): up to cap rows of six doubles — start, end
- * (seconds on the clock bscgpu_steady_now reads), the block's id inside its pipe, first sub-block, sub-blocks per task (1, 2, 8; 16 for a
- * sixteen-lane task), the block's features.  Returns the number of rows; reset != 0 clears the record.  (bench.py prints it with
+ * (seconds on the clock bscgpu_steady_now reads), the block's id inside its pipe, first sub-block, sub-blocks per task (1, 2, 8), the
+ * block's features.  Returns the number of rows; reset != 0 clears the record.  (bench.py prints it with
  * BSC_BENCH_TRACE=1: where a short job's last 100 ms go.) */
 BSCGPU_API int    bscgpu_coder_pool_trace(double* out, int cap, int reset);
 BSCGPU_API double bscgpu_steady_now(void);
@@ -291,8 +287,7 @@ enum {
     BSCGPU_K_DC_PSTREAM    = 11, /* device coder: probability stream */
     BSCGPU_K_RADIX_HISTALL = 12, /* single-read sorts: the one histogram read per sort (all digits at once) */
     BSCGPU_K_RADIX_AUX     = 13, /* keys-only passes that also emit the permutation (device coder's orders, inverse BWT): not the graded kernel */
-    BSCGPU_K_DC_STATIC     = 14, /* device coder: the context-free counter family walked in stream order (round 6) */
-    BSCGPU_K_COUNT         = 15
+    BSCGPU_K_COUNT         = 14
 };
 typedef struct bscgpu_kstat {
     double   ms;        /* accumulated HIP-event time */
@@ -319,17 +314,13 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          Results are identical.
  * BSCGPU_CNT_OS_RETRIES    (get only) transforms this context has redone through the three-kernel passes because a single-read pass
  *                          gave up a wait (bounded polls; the block still comes out right).
- * BSCGPU_OPT_DC_STREAM_STATIC  device model of the static coder: 1 (BSC_DC_SPF=1 in the environment) evaluates the context-free
- *                          counter family in stream order for blocks of at most 32 symbols per sub-block (devcoder_static.h);
- *                          0 (default) sends it through partition / evaluation / gather like the other two families.  Same
- *                          output either way; round 6 measured the stream-order form slower (profiles/r06/static_family_stream_order.txt).
  * BSCGPU_OPT_DC_PACKED_STREAM  1 (default; BSC_PS13=0 in the environment turns it off): the static coder's probability stream crosses
  *                          PCIe as 13 bits per decision — 12-bit probability + coded bit, eight decisions in 13 bytes — instead of
  *                          16-bit entries (298 instead of 366 MB per 64 MiB text block).  The run-start mark of the 16-bit entry only
  *                          placed the reference's output-budget test; a stream that reaches its budget is redone on the host model
  *                          either way.  Same output.
  * set returns the previous value or a negative libbsc error code; get the value or a negative error code. */
-enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_STREAM_STATIC = 3, BSCGPU_OPT_DC_PACKED_STREAM = 4 };
+enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACKED_STREAM = 4 };
 BSCGPU_API int bscgpu_option_set(bscgpu_ctx* ctx, int key, int value);
 BSCGPU_API int bscgpu_option_get(bscgpu_ctx* ctx, int key);
 /* Process-wide counts since start (tests, reports): blocks whose static model ran on the GPU, how many of those were LZP-preprocessed,

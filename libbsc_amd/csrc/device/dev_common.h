@@ -105,12 +105,12 @@ struct bscgpu_ctx {
     u32* dscal  = nullptr;   // small device scalars (1024 u32, mirrored slot by slot in hscal)
     u64* dscal64 = nullptr;  // small device u64 scalars (16)
     u64* adler_part = nullptr; // [MAX_CHUNKS][2]
-    u32* tile_counts = nullptr; size_t tile_counts_cap = 0;   // [256][tiles of 8192 records]: BSC_RS_ORDER=1 experiment, allocated on first use
+    u32* tile_counts = nullptr; size_t tile_counts_cap = 0;   // [256][tiles of 8192 records]: rs_scatter_tiled's offsets, allocated on first use
     u32* long_tables = nullptr;   // BWT text rounds: counting-sort tables of the long-group split (bwt.hip LongTables), allocated on first use
     u32* batch_tab = nullptr;     // batched BWT pass: block table + per-block results (bwt.hip BwtBatch), allocated on first use
     size_t batch_bytes = 0;       // HBM of batch_tab (bscgpu_arena_bytes counts it once allocated)
     u8*  batch_host[2] = {nullptr, nullptr};   // pinned: a batched pass's text going up and its L coming back (two: coding overlaps the next pass)
-    u64* wc_sink = nullptr;  // [512 * 1024] write sink for predicated-off lanes of rs_scatter_wc
+    u64* wc_sink = nullptr;  // [512 * 1024] scratch of the digit passes: phase stamps under RS_PHASE_TIMING (rs_scatter, the single-read passes)
     // single-read digit passes (radix_onesweep.hip), allocated on first use
     int  num_cus = 256;           // hipDeviceAttributeMultiprocessorCount of the context's device
     int  os_mode = 0;             // BSC_RS_ONESWEEP: 0 = off, 1 = large (key, value) sorts only, 2 = every sort of >= 4 tiles (tests), 3 = large sorts, keys-only too (default)
@@ -123,7 +123,6 @@ struct bscgpu_ctx {
     bool os_check_pending = false;   // hscal[OS_ERR_SLOT] has not been looked at since the last single-read sort
     bool os_available = true;        // the single-read kernels could be set up on this device (radix_onesweep_setup)
     int  os_retries = 0;             // transforms redone through the three-kernel passes after a give-up (bscgpu_debug_counter)
-    int  dc_spf = 0;                 // BSCGPU_OPT_DC_STREAM_STATIC (context.hip reads BSC_DC_SPF at creation)
     int  dc_p13 = 1;                 // BSCGPU_OPT_DC_PACKED_STREAM: the static coder's p stream leaves as 13 bits per decision (BSC_PS13=0: 16-bit entries)
     bool os_gave_up = false;         // radix_onesweep_check found a give-up: the caller may redo its sorts through the three-kernel passes
     // pinned host
@@ -137,7 +136,6 @@ struct bscgpu_ctx {
     bool     dc_alloc_failed = false;   // the device coder's arena did not fit: this context keeps the host model (not retried per block)
     int      dc_last_fail = 0;   // why the last block left the device coder (bit mask, devcoder.hip FAIL_*), 0 = it did not
     int      dc_replays = 0;     // evaluation chunks replayed serially in the last block
-    int      rs_wc_mode = 0;     // BSC_RS_WC as read at context creation (radix_engine_setup)
 
     // profiling
     bool         prof        = false;

@@ -272,7 +272,7 @@ class GpuContext:
         return Pipe(self, depth, reuse_outputs)
 
     # ---- measurement / test knobs (include/bscgpu.h: BSCGPU_OPT_*, BSCGPU_CNT_*) ---------------------------------
-    OPT_RS_ONESWEEP, CNT_OS_RETRIES, OPT_DC_STREAM_STATIC, OPT_DC_PACKED_STREAM = 1, 2, 3, 4
+    OPT_RS_ONESWEEP, CNT_OS_RETRIES, OPT_DC_PACKED_STREAM = 1, 2, 4
 
     def option_set(self, key, value):
         return self._check(self.L.bscgpu_option_set(self.h, key, value))
@@ -325,11 +325,7 @@ def coder_pool_stats(reset=False):
     """how the process's coder pool has coded the pipes' blocks: {scalar x8 tasks, pairs x4 tasks, eight_lanes x1 task, host_model}"""
     out = (C.c_uint64 * 4)()
     N.lib().bscgpu_coder_pool_stats(out, 1 if reset else 0)
-    L = N.lib()
-    L.bscgpu_coder_pool_x16_blocks.restype = C.c_uint64
-    x16 = int(L.bscgpu_coder_pool_x16_blocks(1 if reset else 0))
-    return {"scalar_tasks": int(out[0]), "pair_tasks": int(out[1]), "eight_lane_task": int(out[2]), "host_model": int(out[3]),
-            "of_the_eight_lane_blocks_coded_in_pairs_of_sixteen_lanes": x16}
+    return {"scalar_tasks": int(out[0]), "pair_tasks": int(out[1]), "eight_lane_task": int(out[2]), "host_model": int(out[3])}
 
 
 class Pipe:

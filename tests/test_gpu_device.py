@@ -483,31 +483,23 @@ def test_error_paths_and_two_contexts(torch_cuda, ref):
         a.close(); b.close()
 
 
-def test_contiguous_range_scatter_variants(torch_cuda):
-    """The digit-pass kernels that give a workgroup one contiguous tile range (BSC_RS_ORDER=0: the write-combining kernel, forced
-    on for every size with >= 4 chunks by BSC_RS_WC=2, and the plain 1024 x 8 kernel, BSC_RS_WC=0) must produce the same stable
-    order as the default XCD-interleaved kernel: the radix parity cases and a 16 MiB BWT in child processes."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for wc in ("2", "0"):
-        env = dict(os.environ, BSC_RS_WC=wc, BSC_RS_ORDER="0")
-        r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_device.py"), "-q", "-x",
-                            "-k", "radix_sort_matches or bwt_device_resident_16m"], capture_output=True, text=True, env=env, cwd=root)
-        assert r.returncode == 0, (wc, r.stdout[-2000:] + r.stderr[-2000:])
-
-
 def test_device_static_model_matches_oracle_trace(ctx):
     """bscgpu_qlfc_static_pstream (devcoder.hip): every probability of the static QLFC model computed on the GPU equals the
     oracle's trace of the reference model (oracle/bsc_oracle.c: encode_model1 with the trace hook), sub-block by sub-block,
-    including the run-start marks; a block the device path cannot hold (more than 4 decisions per byte) is declined, never approximated."""
+    including the run-start marks, and on blocks of up to 1 MiB so do the three counter values behind every probability (the
+    debug output); 1 / 2 / 4 sub-blocks, sub-blocks of different alphabet size (max_rank 0..4, and one with 40 symbols), a block of
+    a handful of runs and constant data.  A block the device path cannot hold (more than 4 decisions per byte) is declined, never
+    approximated."""
     from libbsc_amd import api
     from libbsc_amd.gpu import GpuError
     from oracle.refbind import Oracle, Ref
     orc, ref = Oracle(), Ref()
     rng = np.random.default_rng(11)
     bwt = lambda x: ref.bwt_encode(x)[0]
+    rng29 = np.random.default_rng(29)
+    def alpha(n, k, p=0.3):         # k symbols, geometric
+        return (rng29.geometric(p, n) % k).astype(np.uint8)
+    parts = [alpha(300_000, 2), alpha(700_000, 4), alpha(900_000, 7, 0.1), alpha(400_000, 32, 0.05), alpha(800_000, 17, 0.08), alpha(1_100_000, 3)]
     cases = [("text300k", bwt(api.synth_text_v1(3, 300_000))), ("text1m", bwt(api.synth_text_v1(1, 1 << 20))),
              ("low1m", bwt(rng.integers(0, 3, 1 << 20, dtype=np.uint8))), ("zeros", np.zeros(500_000, np.uint8)),
              ("sym40", bwt((rng.geometric(0.15, 700_000) % 40).astype(np.uint8))),
@@ -516,13 +508,20 @@ def test_device_static_model_matches_oracle_trace(ctx):
              # 224 symbols, text-like structure (each 64 KiB segment in its own 32-symbol band): several hundred decision types
              ("text224", bwt(((api.synth_text_v1(6, 3 << 20) & 31) + ((np.arange(3 << 20) >> 16) % 7 * 32).astype(np.uint8)).astype(np.uint8))),
              ("rand600k", rng.integers(0, 256, 600_000, dtype=np.uint8)),           # all 8-bit ranks, escape coding (avg_rank >= 32), ~340 decision types
-             ("skew1m", bwt((rng.geometric(0.02, 1 << 20) % 256).astype(np.uint8)))]
+             ("skew1m", bwt((rng.geometric(0.02, 1 << 20) % 256).astype(np.uint8))),
+             ("text5m", bwt(api.synth_text_v1(14, 5 << 20))),
+             ("mixed alphabets 4.2m", np.concatenate(parts)), ("mixed + 40 symbols", np.concatenate(parts[:3] + [alpha(500_000, 40, 0.03)] + parts[3:])),
+             ("tiny", np.array([1, 1, 2, 2, 2, 1, 3], np.uint8)), ("one run", np.zeros(70_000, np.uint8)), ("ab", (np.arange(600_000) % 2).astype(np.uint8)),
+             ("dna5m", bwt(rng29.integers(0, 4, 5 << 20, dtype=np.uint8))), ("32 symbols uniform", rng29.integers(0, 32, 2 << 20, dtype=np.uint8))]
     for name, L in cases:
-        ps, st, sz, poff, _ = ctx.qlfc_static_pstream(L)
+        debug = L.size <= (1 << 20)
+        ps, st, sz, poff, dbg = ctx.qlfc_static_pstream(L, debug=debug)
         assert poff[0] == 0 and poff[-1] == len(ps), name
         for b in range(len(st)):
-            tr, _ = orc.static_pstream(L[st[b]:st[b] + sz[b]])
+            tr, ct = orc.static_pstream(L[st[b]:st[b] + sz[b]], counters=debug)
             assert np.array_equal(tr, ps[poff[b]:poff[b + 1]]), (name, b)
+            if debug:                                                # state, char and static family, as the oracle's trace orders them
+                assert np.array_equal(dbg[:, poff[b]:poff[b + 1]], ct.T), (name, b)
     # capacity is the only thing the device path declines on such inputs: 4 decisions per byte of the CONTEXT's block size
     # (random bytes need ~9 per byte); a context sized for the block itself says LIBBSC_NOT_SUPPORTED, never approximates
     from libbsc_amd import GpuContext
@@ -581,50 +580,6 @@ def test_packed_probability_stream_equals_the_16_bit_entries(ctx):
             ctx.qlfc_static_pstream_packed(cases[0][1])
     finally:
         ctx.option_set(ctx.OPT_DC_PACKED_STREAM, 1)
-
-
-def test_stream_order_static_family_equals_partitioned_path(ctx):
-    """devcoder_static.h (round 6): for blocks of at most 32 symbols per sub-block the static coder's context-free counter family is
-    walked in stream order instead of being partitioned.  Same probability stream as the general path (BSCGPU_OPT_DC_STREAM_STATIC = 0)
-    and as the oracle's trace of the reference model, on 1 / 2 / 4 sub-blocks, sub-blocks of different alphabet size (max_rank 0..4 and
-    one with 40 symbols, which sends the whole block down the general path), a block of a handful of runs, and constant data (brackets
-    that cannot close: declined or exact, never approximate)."""
-    from libbsc_amd import api
-    from libbsc_amd.gpu import GpuError
-    from oracle.refbind import Oracle, Ref
-    orc, ref = Oracle(), Ref()
-    rng = np.random.default_rng(29)
-    bwt = lambda x: ref.bwt_encode(x)[0]
-    def alpha(n, k, p=0.3):         # k symbols, geometric
-        return (rng.geometric(p, n) % k).astype(np.uint8)
-    parts = [alpha(300_000, 2), alpha(700_000, 4), alpha(900_000, 7, 0.1), alpha(400_000, 32, 0.05), alpha(800_000, 17, 0.08), alpha(1_100_000, 3)]
-    cases = [("text200k", bwt(api.synth_text_v1(12, 200_000))), ("text1m", bwt(api.synth_text_v1(13, 1 << 20))), ("text5m", bwt(api.synth_text_v1(14, 5 << 20))),
-             ("mixed alphabets 4.2m", np.concatenate(parts)), ("mixed + 40 symbols", np.concatenate(parts[:3] + [alpha(500_000, 40, 0.03)] + parts[3:])),
-             ("tiny", np.array([1, 1, 2, 2, 2, 1, 3], np.uint8)), ("one run", np.zeros(70_000, np.uint8)), ("ab", (np.arange(600_000) % 2).astype(np.uint8)),
-             ("dna5m", bwt(rng.integers(0, 4, 5 << 20, dtype=np.uint8))), ("32 symbols uniform", rng.integers(0, 32, 2 << 20, dtype=np.uint8))]
-    assert ctx.option_get(ctx.OPT_DC_STREAM_STATIC) == 0          # off by default (measured slower: profiles/r06)
-    try:
-        for name, L in cases:
-            got = {}
-            for mode in (1, 0):
-                ctx.option_set(ctx.OPT_DC_STREAM_STATIC, mode)
-                try:
-                    got[mode] = ctx.qlfc_static_pstream(L, debug=(L.size <= (1 << 20)))
-                except GpuError as e:
-                    assert e.code == -4, (name, mode, e)            # declined: the block takes the host model
-                    got[mode] = None
-            if got[1] is None or got[0] is None:
-                continue
-            (ps1, st1, sz1, poff1, dbg1), (ps0, st0, sz0, poff0, dbg0) = got[1], got[0]
-            assert st1 == st0 and sz1 == sz0 and poff1 == poff0, name
-            assert np.array_equal(ps1, ps0), (name, int((ps1 != ps0).sum()))
-            if dbg1 is not None:
-                assert np.array_equal(dbg1, dbg0), name                 # the three counter values behind every probability
-            for b in range(len(st1)):
-                tr, _ = orc.static_pstream(L[st1[b]:st1[b] + sz1[b]])
-                assert np.array_equal(tr, ps1[poff1[b]:poff1[b + 1]]), (name, b)
-    finally:
-        ctx.option_set(ctx.OPT_DC_STREAM_STATIC, 0)
 
 
 def test_gpu_inverse_bwt(ctx, ref):

@@ -1,4 +1,4 @@
-"""Per-pass scatter times of the 64 MiB BWT's first sort: python tools/per_pass.py  (BSC_RS_WC=0/1 in the environment)."""
+"""Per-pass scatter times of the 64 MiB BWT's first sort: python tools/per_pass.py  (BSC_RS_ONESWEEP in the environment)."""
 import sys, os
 sys.path.insert(0, '.')
 import numpy as np, torch

@@ -1,5 +1,5 @@
 """Phase timing of the scatter kernels (debug build: bash tools/build_variant.sh pht -DRS_PHASE_TIMING=1).
-    BSC_LIB_OVERRIDE=libbsc_amd/lib/variants/libbsc_pht.so [BSC_RS_WC=1] python tools/phase_timing.py
+    BSC_LIB_OVERRIDE=libbsc_amd/lib/variants/libbsc_pht.so python tools/phase_timing.py
 Runs one 64 MiB BWT (the last first-sort pass is dumped by the library) and prints the mean time between the phase stamps
 of thread 0 of every workgroup, in s_memtime ticks and as a fraction of the tile."""
 import os, sys
@@ -19,6 +19,6 @@ tiles = a[:, 2:30, :11]                      # skip the first / last tiles of ev
 dt = np.diff(tiles, axis=2)
 tot = (tiles[:, :, 10] - tiles[:, :, 0]).mean()
 gap = (a[:, 3:30, 0] - a[:, 2:29, 10]).mean()
-print(f"mode BSC_RS_WC={os.environ.get('BSC_RS_WC', '0')}: tile {tot:.0f} ticks (+ {gap:.0f} between tiles)")
+print(f"tile {tot:.0f} ticks (+ {gap:.0f} between tiles)")
 for i, nm in enumerate(names):
     print(f"  {nm:24s} {dt[:, :, i].mean():8.0f}  {100 * dt[:, :, i].mean() / tot:5.1f} %")

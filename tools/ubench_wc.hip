@@ -3,7 +3,7 @@
 //   full     : every (tile, stream) run starts on a 32-record boundary and leaves in one instruction (2 full key lines + 1 full
 //              value line): what a scatter emits when old pending records are merged with the new ones before the write-out;
 //   split    : the same lines, but the first pk keys / pv values of every run leave in a separate instruction from 16- / 32-lane
-//              groups (flush of old pending records) and the rest from the main sweep: what rs_scatter_wc emits;
+//              groups (flush of old pending records) and the rest from the main sweep: what the write-combining scatter emitted (removed);
 //   misalign : runs shifted by 5 records (every run shares its first and last line with the neighbouring tiles' runs): what the
 //              plain rs_scatter emits on uniform digits.
 // hipcc -O3 --offload-arch=gfx950 tools/ubench_wc.hip -o tools/bin/ubench_wc
