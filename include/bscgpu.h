@@ -104,7 +104,8 @@ BSCGPU_API int bscgpu_compress_device(bscgpu_ctx* ctx, const void* dInput, uint8
 /* ---- batches of small blocks: one suffix sort for many blocks ------------------------------
  * Blocks are laid out back to back: block b starts at off_b = sizes[0] + ... + sizes[b-1].  Blocks below
  * BSCGPU_BATCH_MAX_N that the BWT sorts share one suffix sort per pass (at most max_n bytes and 4096 blocks,
- * consecutive blocks); every other block takes the single-block path inside the same call.  Output is
+ * consecutive blocks), blocks below BSCGPU_ST_BATCH_MAX_N that ST3..ST8 sort share one sort transform per pass
+ * (the same limits); every other block takes the single-block path inside the same call.  Output is
  * byte-identical to the single-block calls.  The context stays non-re-entrant.
  *
  * bscgpu_bwt_batch_device: dT / dL device pointers (may alias, dL in dT's layout).  primary[b] = what
@@ -123,6 +124,19 @@ BSCGPU_API int bscgpu_compress_device(bscgpu_ctx* ctx, const void* dInput, uint8
  *   single-block path; returns the number of passes (cap = the context's max_n). */
 #define BSCGPU_BATCH_MAX_N (1 << 20)       /* = the device-model threshold; the batched route beats the call's per-block route below it */
 BSCGPU_API int bscgpu_batch_plan(const int* sizes, int count, int blockSorter, int64_t cap, int* pass_of);
+/* The sort transform's batch: one sort of the records of many blocks per pass, block-cyclic contexts.
+ * bscgpu_st_batch_plan: the ST routing rule as a pure function (bscgpu_batch_plan keeps answering for the BWT only): blocks of
+ *   1 .. BSCGPU_ST_BATCH_MAX_N - 1 bytes and at most cap bytes join passes of consecutive blocks, at most cap bytes and
+ *   BSCGPU_ST_BATCH_MAX_BLOCKS blocks each (every k the same); pass_of[b] = -1 for larger blocks (they end a pass) and for empty
+ *   ones (an empty entry inside a pass).  Returns the number of passes; k outside 3..8 or a negative size: LIBBSC_BAD_PARAMETER,
+ *   nothing written.
+ * bscgpu_st_batch_device: dT / dOut device pointers, blocks back to back, may alias (dOut in dT's layout).  index[b] = what
+ *   bsc_st_encode returns for block b alone (0 for n_b <= 1, bytes unchanged; a block larger than max_n: LIBBSC_BAD_PARAMETER as
+ *   bscgpu_st_encode_device, its bytes not written).  Returns 0 or a batch-level error (bad arguments: nothing written; GPU). */
+#define BSCGPU_ST_BATCH_MAX_N BSCGPU_BATCH_MAX_N
+#define BSCGPU_ST_BATCH_MAX_BLOCKS 4096
+BSCGPU_API int bscgpu_st_batch_plan(const int* sizes, int count, int k, int64_t cap, int* pass_of);
+BSCGPU_API int bscgpu_st_batch_device(bscgpu_ctx* ctx, const void* dT, void* dOut, const int* sizes, int count, int k, int* index);
 BSCGPU_API int bscgpu_bwt_batch_device(bscgpu_ctx* ctx, const void* dT, void* dL, const int* sizes, int count, int* primary,
                                        unsigned char* num_indexes, int* indexes);
 BSCGPU_API int bscgpu_compress_batch(bscgpu_ctx* ctx, const unsigned char* input, const int* sizes, int count, unsigned char* output,

@@ -80,6 +80,8 @@ def lib():
     L.bscgpu_pipe_submit_host.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.bscgpu_batch_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int64, vp]
     L.bscgpu_bwt_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp]
+    L.bscgpu_st_batch_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int64, vp]
+    L.bscgpu_st_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp]
     L.bscgpu_compress_batch.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.bscgpu_compress_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int]
     L.bscgpu_unbwt_batch_plan.argtypes = [vp, C.c_int, C.c_int64, vp]

@@ -939,13 +939,7 @@ __global__ __launch_bounds__(WG) void bwt_emit_pred_kernel(const u8* __restrict_
 // then need no block table at all: for a suffix s of block b, s + h past the block's end lies in a later block, whose ranks are all
 // below block b's slots, so next = ISA[s + h] + 1 orders it before every same-block next rank — exactly what 0 does at the block end.
 // (Only one suffix per group can reach the end: the members of a group share h characters and differ in length.)
-__device__ __forceinline__ u32 batch_block_of(const u32* __restrict__ off, u32 count, u32 i)
-{
-    u32 lo = 0, hi = count;                     // off[lo] <= i; empty blocks share an offset: the last such block wins
-    while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
-    return lo;
-}
-
+// (batch_block_of: dev_common.h)
 __global__ __launch_bounds__(WG) void bwt_batch_pack_kernel(const u8* __restrict__ T, u32 N, const u32* __restrict__ off, u32 count,
                                                             u32 bb, u32 cb, u32 w, const u8* __restrict__ codes,
                                                             u64* __restrict__ keys, u32* __restrict__ vals)

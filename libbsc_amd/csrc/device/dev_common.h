@@ -107,7 +107,7 @@ struct bscgpu_ctx {
     u64* adler_part = nullptr; // [MAX_CHUNKS][2]
     u32* tile_counts = nullptr; size_t tile_counts_cap = 0;   // [256][tiles of 8192 records]: rs_scatter_tiled's offsets, allocated on first use
     u32* long_tables = nullptr;   // BWT text rounds: counting-sort tables of the long-group split (bwt.hip LongTables), allocated on first use
-    u32* batch_tab = nullptr;     // batched BWT pass: block table + per-block results (bwt.hip BwtBatch), allocated on first use
+    u32* batch_tab = nullptr;     // batched BWT / ST pass: block table + per-block results (bwt.hip BwtBatch, st.hip st_batch_device), allocated on first use
     size_t batch_bytes = 0;       // HBM of batch_tab (bscgpu_arena_bytes counts it once allocated)
     u8*  batch_host[2] = {nullptr, nullptr};   // pinned: a batched pass's text going up and its L coming back (two: coding overlaps the next pass)
     u64* wc_sink = nullptr;  // [512 * 1024] scratch of the digit passes: phase stamps under RS_PHASE_TIMING (rs_scatter, the single-read passes)
@@ -194,6 +194,10 @@ constexpr int BATCH_MAX_BLOCKS = 4096;
 // adler_host != nullptr: also every block's Adler-32 of dT_user (st.hip: adler_batch_kernel, one launch), back with the same sync.
 int bwt_batch_device(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, const int* sizes, int count, const int* rates, u32* res,
                      u32* adler_host = nullptr);
+// Batched ST pass (st.hip): the same layout and limits, order k = 3..8.  rates (optional): < 0 = the block is not transformed (out = T,
+// index 0).  index_out[b] = what st_device returns for block b alone (0 for n_b <= 1); dOut_user may be dT_user.  adler_host as above.
+int st_batch_device(bscgpu_ctx* c, const u8* dT_user, u8* dOut_user, const int* sizes, int count, int k, const int* rates, int* index_out,
+                    u32* adler_host = nullptr);
 // (stride 2: doff holds a (start, end) pair per block, blocks anywhere in d)
 void launch_adler_batch(bscgpu_ctx* c, const u8* d, const u32* doff, u32 count, u32* dout, u32 stride = 1);     // st.hip (asynchronous)
 int batch_tab_ensure(bscgpu_ctx* c);       // bwt.hip: batch_tab on first use
@@ -228,6 +232,15 @@ void devcoder_warm_tables();               // starts the model tables' computati
 // ---------------------------------------------------------------------------------------------
 #ifdef __HIPCC__
 __device__ __forceinline__ u32 lane_id() { return __lane_id(); }
+
+// Block of position i in a batch's offset table off[0..count] (bwt.hip, st.hip): the largest b in [lo, hi) with off[b] <= i, given
+// off[lo] <= i.  Empty blocks share an offset: the last such block wins, so the block found holds i.
+__device__ __forceinline__ u32 batch_block_of(const u32* __restrict__ off, u32 lo, u32 hi, u32 i)
+{
+    while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
+    return lo;
+}
+__device__ __forceinline__ u32 batch_block_of(const u32* __restrict__ off, u32 count, u32 i) { return batch_block_of(off, 0u, count, i); }
 
 __device__ __forceinline__ u64 lanemask_lt() {
     u32 l = lane_id();

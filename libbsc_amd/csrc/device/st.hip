@@ -7,7 +7,10 @@
 //   k <= 7 : key = T[i-1] | T[i] .. T[i+6]  (output byte rides in the top byte, never sorted on),
 //            keys-only passes over bits [(7-k)*8, 56)  -> k passes of 16 B/record;
 //   k == 8 : key = T[i..i+7], value = T[i-1] | (i == 0) << 8, 8 passes of 24 B/record.
+// Many small blocks go through one sort per pass with the block id as the top digits: st_batch_device, further down.
 #include "dev_common.h"
+#include <cstring>
+#include <vector>
 
 // cyclic padding around the private text copy: dT[-1] = T[n-1], dT[n+j] = T[j mod n] (j < 32)
 __global__ void st_pad_kernel(u8* __restrict__ dT, u32 n)
@@ -138,6 +141,192 @@ static int st_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dOut_user, int n
     prof_collect(c);
     *index_out = (int)c->hscal[2];
     return radix_onesweep_check(c);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Batched pass: the records of many blocks, laid out back to back, in one sort (st_batch_device).  A record's context is
+// BLOCK-CYCLIC (T_b[(i + j) mod n_b]: the blocks touch, so there is no padding to read) and the block id is the sort's most
+// significant digits: the engine is LSD and stable, so the block digits simply run last, and slot j of the sorted pass belongs to the
+// block that owns text position j.  Position 0 of a block is flagged, which gives the block's index without a comparison.
+//   k <= 5 : keys only, key = out byte [63:56] | block [55:44] | T[i .. i+4] [43:4] | (i == 0) [0];
+//            k context passes from bit 4 + 8 (5 - k), then the block digits from bit 44 (8 bits, then the rest): 16 B/record per pass;
+//   k >= 6 : key = T[i .. i+7], value = out byte | (i == 0) << 8 | block << 9; k context passes from bit 8 (8 - k), the key is
+//            rewritten as the block id (st_batch_rekey_kernel: 12 B/record), then the block digits: 24 B/record per pass.
+// A block with rate < 0 is not transformed: its records carry their own byte and an all-zero context, so the stable sort returns them
+// in text order (out = T, index 0).
+constexpr u32 STB_BLOCK_SHIFT = 44, STB_CTX_SHIFT = 4, STB_VAL_BLOCK_SHIFT = 9, STB_BLOCK_MASK = BATCH_MAX_BLOCKS - 1;
+
+template <bool KV>
+__device__ __forceinline__ void st_batch_put(u64* __restrict__ keys, u32* __restrict__ vals, u32 g, u32 b, bool first, u32 prev, u64 ctx)
+{
+    if (KV) {
+        keys[g] = ctx;
+        vals[g] = prev | (first ? 0x100u : 0u) | (b << STB_VAL_BLOCK_SHIFT);
+    } else {
+        keys[g] = ((u64)prev << 56) | ((u64)b << STB_BLOCK_SHIFT) | ((ctx >> 24) << STB_CTX_SHIFT) | (first ? 1ull : 0ull);
+    }
+}
+
+// Four consecutive positions of the pass per thread.  Interior of a block (the thread's bytes g0 - 1 .. g0 + 10 all inside it): the
+// single-block kernel's four aligned 4-byte loads.  Within eleven bytes of a block's ends, blocks shorter than that included: byte
+// reads that wrap at the block's ends.  The block of a workgroup's first and last position is found once per workgroup; a thread
+// searches the table only where its workgroup spans several blocks, and then only between those two.
+template <bool KV>
+__global__ __launch_bounds__(WG) void st_batch_pack_kernel(const u8* __restrict__ T, u32 N, const u32* __restrict__ off,
+                                                           const int* __restrict__ rate, u32 count, u64* __restrict__ keys,
+                                                           u32* __restrict__ vals)
+{
+    __shared__ u32 span[2];
+    const u32 p0 = 4u * WG * blockIdx.x;
+    if (threadIdx.x < 2) {
+        u32 p = p0 + threadIdx.x * (4u * WG - 1u);
+        if (p >= N) p = N - 1u;
+        span[threadIdx.x] = batch_block_of(off, count, p);
+    }
+    __syncthreads();
+    const u32 g0 = p0 + 4u * threadIdx.x;
+    if (g0 >= N) return;
+    u32 b = span[0];
+    if (span[1] != b) b = batch_block_of(off, b, span[1] + 1u, g0);
+    u32 o0 = off[b], end = off[b + 1];
+    if (g0 > o0 && g0 + 11u <= end && rate[b] >= 0) {
+        const u32* T32 = reinterpret_cast<const u32*>(T + g0) - 1;         // bytes g0-4 .. g0+11
+        const u64 w0 = ((u64)__builtin_bswap32(T32[0]) << 32) | __builtin_bswap32(T32[1]);
+        const u64 w1 = ((u64)__builtin_bswap32(T32[2]) << 32) | __builtin_bswap32(T32[3]);
+#pragma unroll
+        for (u32 j = 0; j < 4; ++j) {
+            const u32 s = 8 * (4 + j);                                   // window starts at byte g0 + j
+            st_batch_put<KV>(keys, vals, g0 + j, b, false, (u32)(w0 >> (8 * (4 - j))) & 0xffu, (w0 << s) | (w1 >> (64 - s)));
+        }
+        return;
+    }
+    for (u32 j = 0; j < 4; ++j) {
+        const u32 g = g0 + j;
+        if (g >= N) break;
+        while (g >= end) { ++b; o0 = off[b]; end = off[b + 1]; }         // (g < N = off[count]: ends; empty blocks are stepped over)
+        const u32 n = end - o0, i = g - o0;
+        u32 prev = T[g];
+        u64 ctx = 0;
+        if (rate[b] >= 0) {
+            prev = T[i ? g - 1u : end - 1u];
+            u32 p = i;
+            for (u32 t = 0; t < 8; ++t) { ctx = (ctx << 8) | T[o0 + p]; if (++p == n) p = 0; }
+        }
+        st_batch_put<KV>(keys, vals, g, b, i == 0, prev, ctx);
+    }
+}
+
+__global__ __launch_bounds__(WG) void st_batch_rekey_kernel(const u32* __restrict__ vals, u64* __restrict__ keys, u32 N)
+{
+    const u32 j = blockIdx.x * WG + threadIdx.x;
+    if (j < N) keys[j] = vals[j] >> STB_VAL_BLOCK_SHIFT;
+}
+
+// Slot j of the sorted pass is output byte j.  `out` is the caller's pointer rounded down to 4 bytes and `lead` what was cut off,
+// so that the 4-byte stores are aligned wherever the pass starts in the caller's buffer.  (The block id is masked to the table's
+// size: the records of a sort that gave up a wait are not to be trusted, and the retry writes everything again.)
+template <bool KV>
+__global__ __launch_bounds__(WG) void st_batch_post_kernel(const u64* __restrict__ keys, const u32* __restrict__ vals, u32 N, u32 lead,
+                                                           const u32* __restrict__ off, u8* __restrict__ out, u32* __restrict__ index)
+{
+    const u32 q0 = 4u * (blockIdx.x * WG + threadIdx.x);
+    if (q0 >= N + lead) return;
+    u32 word = 0, have = 0;
+#pragma unroll
+    for (u32 q = 0; q < 4; ++q) {
+        const u32 j = q0 + q - lead;
+        if (q0 + q >= lead && j < N) {
+            u32 byte, b; bool first;
+            if (KV) { const u32 v = vals[j]; byte = v & 0xffu; first = (v & 0x100u) != 0; b = (v >> STB_VAL_BLOCK_SHIFT) & STB_BLOCK_MASK; }
+            else { const u64 key = keys[j]; byte = (u32)(key >> 56); first = (key & 1ull) != 0; b = (u32)(key >> STB_BLOCK_SHIFT) & STB_BLOCK_MASK; }
+            word |= byte << (8 * q);
+            have |= 1u << q;
+            if (first) index[b] = j - off[b];
+        }
+    }
+    if (have == 0xfu) *reinterpret_cast<u32*>(out + q0) = word;
+    else for (u32 q = 0; q < 4; ++q) if (have & (1u << q)) out[q0 + q] = (u8)(word >> (8 * q));
+}
+
+static int st_batch_once(bscgpu_ctx* c, const u8* dT_user, u8* dOut_user, u32 N, u32 count, int k, const u32* doff, const int* drate,
+                         u32* dindex, int* index_out, bool reuse_text)
+{
+    if (!reuse_text) HIP_TRY(c, hipMemcpyAsync(c->dT, dT_user, N, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(dindex, 0, (size_t)count * 4, c->stream));
+    int bb = 0;
+    while ((1u << bb) < count) ++bb;                                       // bits of the block id
+    const bool kv = k >= 6;
+    const dim3 grid((N + 4 * WG - 1) / (4 * WG));
+    int in_alt = 0, rc, np = 0;
+    RadixPass passes[8];
+    u64 *kcur = c->kA, *kalt = c->kB;
+    u32 *vcur = kv ? c->vA : nullptr, *valt = kv ? c->vB : nullptr;
+    prof_begin(c, BSCGPU_K_PACK, (u64)N * (kv ? 13 : 9), N);
+    if (kv) hipLaunchKernelGGL(st_batch_pack_kernel<true>, grid, dim3(WG), 0, c->stream, c->dT, N, doff, drate, count, kcur, vcur);
+    else hipLaunchKernelGGL(st_batch_pack_kernel<false>, grid, dim3(WG), 0, c->stream, c->dT, N, doff, drate, count, kcur, vcur);
+    prof_end(c);
+    for (int p = 0; p < k; ++p) { passes[np].shift = (kv ? 8 * (8 - k) : (int)STB_CTX_SHIFT + 8 * (5 - k)) + 8 * p; passes[np++].bits = 8; }
+    const int block_shift = kv ? 0 : (int)STB_BLOCK_SHIFT;
+    if (kv && bb > 0) {
+        rc = radix_sort_passes(c, kcur, kalt, vcur, valt, N, passes, np, &in_alt);
+        if (rc < 0) return rc;
+        if (in_alt) { u64* tk = kcur; kcur = kalt; kalt = tk; u32* tv = vcur; vcur = valt; valt = tv; }
+        prof_begin(c, BSCGPU_K_MISC, (u64)N * 12, N);
+        hipLaunchKernelGGL(st_batch_rekey_kernel, dim3((N + WG - 1) / WG), dim3(WG), 0, c->stream, vcur, kcur, N);
+        prof_end(c);
+        np = 0;
+    }
+    if (bb > 0) { passes[np].shift = block_shift; passes[np++].bits = bb < 8 ? bb : 8; }
+    if (bb > 8) { passes[np].shift = block_shift + 8; passes[np++].bits = bb - 8; }
+    rc = radix_sort_passes(c, kcur, kalt, vcur, valt, N, passes, np, &in_alt);
+    if (rc < 0) return rc;
+    if (in_alt) { u64* tk = kcur; kcur = kalt; kalt = tk; u32* tv = vcur; vcur = valt; valt = tv; }
+    const u32 lead = (u32)((uintptr_t)dOut_user & 3u);
+    const dim3 pgrid((N + lead + 4 * WG - 1) / (4 * WG));
+    prof_begin(c, BSCGPU_K_EMIT, (u64)N * (kv ? 5 : 9), N);
+    if (kv) hipLaunchKernelGGL(st_batch_post_kernel<true>, pgrid, dim3(WG), 0, c->stream, kcur, vcur, N, lead, doff, dOut_user - lead, dindex);
+    else hipLaunchKernelGGL(st_batch_post_kernel<false>, pgrid, dim3(WG), 0, c->stream, kcur, vcur, N, lead, doff, dOut_user - lead, dindex);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(index_out, dindex, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    prof_collect(c);
+    return radix_onesweep_check(c);
+}
+
+// One batched pass.  As st_device: the pass is sorted from a private copy of the text (the caller's output may be its input), and a
+// single-read digit pass that gave up is answered by one more attempt through the three-kernel passes from that copy.
+int st_batch_device(bscgpu_ctx* c, const u8* dT_user, u8* dOut_user, const int* sizes, int count, int k, const int* rates, int* index_out,
+                    u32* adler_host)
+{
+    if (count <= 0 || count > BATCH_MAX_BLOCKS || k < 3 || k > 8) return BSC_BAD_PARAMETER;
+    const int trc = batch_tab_ensure(c);
+    if (trc < 0) return trc;
+    std::vector<u32> tab((size_t)2 * count + 1, 0u);
+    u64 total = 0;
+    for (int b = 0; b < count; ++b) { tab[b] = (u32)total; total += (u64)sizes[b]; index_out[b] = 0; }
+    tab[count] = (u32)total;
+    if (rates) memcpy(&tab[count + 1], rates, (size_t)count * 4);
+    if (total == 0) return BSC_NO_ERROR;
+    if (total > (u64)c->max_n || total >= 0x7fffffffull) return BSC_BAD_PARAMETER;
+    const u32* doff = c->batch_tab;
+    const int* drate = reinterpret_cast<const int*>(c->batch_tab + count + 1);
+    u32* dindex = c->batch_tab + 2 * BATCH_MAX_BLOCKS + 1;
+    HIP_TRY(c, hipMemcpyAsync(c->batch_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (adler_host) {                           // (reads the caller's text before the post kernel may overwrite it; the pass's last sync covers the copy)
+        u32* dadler = c->batch_tab + 18 * BATCH_MAX_BLOCKS + 1;
+        launch_adler_batch(c, dT_user, c->batch_tab, (u32)count, dadler);
+        HIP_TRY(c, hipMemcpyAsync(adler_host, dadler, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    c->os_gave_up = false;
+    int rc = st_batch_once(c, dT_user, dOut_user, (u32)total, (u32)count, k, doff, drate, dindex, index_out, false);
+    if (rc == BSC_GPU_ERROR && c->os_gave_up) {
+        const int mode = c->os_mode;
+        c->os_mode = 0; c->os_gave_up = false; ++c->os_retries;
+        rc = st_batch_once(c, dT_user, dOut_user, (u32)total, (u32)count, k, doff, drate, dindex, index_out, true);
+        c->os_mode = mode;
+    }
+    return rc;
 }
 
 // ---------------------------------------------------------------------------------------------

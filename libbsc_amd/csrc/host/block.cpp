@@ -1372,6 +1372,7 @@ int bsc_synth_text_v1(unsigned long long seed, unsigned char* out, long long n)
 
 // ---- batched compression of many small blocks (bscgpu_*_batch, include/bscgpu.h) ------------------------------------------------
 // Blocks below BSCGPU_BATCH_MAX_N that the BWT sorts go through one suffix sort per PASS (bwt.hip: bwt_batch_device), the
+// blocks that ST3..ST8 sort through one sort transform per pass (st.hip: st_batch_device, bscgpu_st_batch_plan), the
 // rest through the single-block path on the same context.  After a pass's sort its L comes back in one copy and every block is coded
 // on the host exactly as bsc_compress codes it (libbsc.cpp:283-337: bsc_coder_compress, the stored rule, the trailer); that coding
 // overlaps the next pass's sort.
@@ -1395,6 +1396,64 @@ extern "C" BSCGPU_API int bscgpu_batch_plan(const int* sizes, int count, int blo
         pass_of[b] = cur; bytes += n; ++span;
     }
     return passes;
+}
+
+// The same rule for the sort transform: blocks of 1 .. BSCGPU_ST_BATCH_MAX_N - 1 bytes ride in passes (a block of one byte too: its
+// record sorts like any other), an empty block is an empty entry of a pass's table, every k has the same block cap.
+extern "C" BSCGPU_API int bscgpu_st_batch_plan(const int* sizes, int count, int k, int64_t cap, int* pass_of)
+{
+    if (count < 0 || (count > 0 && (!sizes || !pass_of)) || k < LIBBSC_BLOCKSORTER_ST3 || k > LIBBSC_BLOCKSORTER_ST8) return LIBBSC_BAD_PARAMETER;
+    for (int b = 0; b < count; ++b) if (sizes[b] < 0) return LIBBSC_BAD_PARAMETER;
+    int passes = 0, cur = -1, span = 0;
+    int64_t bytes = 0;
+    for (int b = 0; b < count; ++b) {
+        const int n = sizes[b];
+        if (n == 0 || n >= BSCGPU_ST_BATCH_MAX_N || (int64_t)n > cap) {
+            pass_of[b] = -1;
+            if (n > 0) cur = -1;
+            else if (cur >= 0) ++span;
+            continue;
+        }
+        if (cur < 0 || bytes + n > cap || span + 1 > BSCGPU_ST_BATCH_MAX_BLOCKS) { cur = passes++; bytes = 0; span = 0; }
+        pass_of[b] = cur; bytes += n; ++span;
+    }
+    return passes;
+}
+
+static int plan_for(const int* sizes, int count, int blockSorter, int64_t cap, int* pass_of)
+{
+    if (blockSorter >= LIBBSC_BLOCKSORTER_ST3 && blockSorter <= LIBBSC_BLOCKSORTER_ST8) return bscgpu_st_batch_plan(sizes, count, blockSorter, cap, pass_of);
+    return bscgpu_batch_plan(sizes, count, blockSorter, cap, pass_of);
+}
+
+extern "C" BSCGPU_API int bscgpu_st_batch_device(bscgpu_ctx* c, const void* dT, void* dOut, const int* sizes, int count, int k, int* index)
+{
+    if (!c || count < 0 || (count > 0 && (!sizes || !index)) || k < LIBBSC_BLOCKSORTER_ST3 || k > LIBBSC_BLOCKSORTER_ST8) return LIBBSC_BAD_PARAMETER;
+    int64_t total = 0;
+    for (int b = 0; b < count; ++b) { if (sizes[b] < 0) return LIBBSC_BAD_PARAMETER; total += sizes[b]; }
+    if (total > 0 && (!dT || !dOut)) return LIBBSC_BAD_PARAMETER;
+    if (count == 0) return LIBBSC_NO_ERROR;
+    if (hipSetDevice(c->device) != hipSuccess) return LIBBSC_GPU_ERROR;
+    std::vector<int> pass_of((size_t)count);
+    const int npass = bscgpu_st_batch_plan(sizes, count, k, c->max_n, pass_of.data());
+    if (npass < 0) return npass;
+    std::vector<int64_t> off((size_t)count + 1, 0);
+    for (int b = 0; b < count; ++b) off[b + 1] = off[b] + sizes[b];
+    const u8* T = (const u8*)dT; u8* O = (u8*)dOut;
+    for (int b = 0; b < count;) {
+        if (pass_of[b] < 0) {                        // alone: what bscgpu_st_encode_device gives (a block above max_n: its error code)
+            index[b] = 0;
+            if (sizes[b] > 0) { const int rc = st_device(c, T + off[b], O + off[b], sizes[b], k, &index[b]); if (rc < 0) index[b] = rc; }
+            ++b;
+            continue;
+        }
+        int e = b;
+        for (int q = b; q < count && (pass_of[q] == pass_of[b] || (pass_of[q] < 0 && sizes[q] == 0)); ++q) if (pass_of[q] == pass_of[b]) e = q + 1;
+        const int rc = st_batch_device(c, T + off[b], O + off[b], sizes + b, e - b, k, nullptr, index + b);
+        if (rc < 0) return rc;
+        b = e;
+    }
+    return LIBBSC_NO_ERROR;
 }
 
 extern "C" BSCGPU_API int bscgpu_bwt_batch_device(bscgpu_ctx* c, const void* dT, void* dL, const int* sizes, int count, int* primary,
@@ -1543,7 +1602,8 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
     if (hipSetDevice(c->device) != hipSuccess) return LIBBSC_GPU_ERROR;
     const bool dev = dInput != nullptr;
     std::vector<int> pass_of((size_t)count);
-    const int npass = bscgpu_batch_plan(sizes, count, blockSorter, c->max_n, pass_of.data());
+    const bool st = blockSorter != LIBBSC_BLOCKSORTER_BWT;                  // (make_mode: BWT or ST3..ST8) the pass is one sort transform, no aux indexes
+    const int npass = plan_for(sizes, count, blockSorter, c->max_n, pass_of.data());
     if (npass < 0) return npass;
     std::vector<int64_t> in_off((size_t)count + 1, 0);
     for (int b = 0; b < count; ++b) in_off[b + 1] = in_off[b] + sizes[b];
@@ -1563,6 +1623,7 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
     int rc = LIBBSC_NO_ERROR;
     std::vector<std::vector<BatchBlock>> bufs(2);
     std::vector<uint32_t> res((size_t)BATCH_MAX_BLOCKS * 16), adler((size_t)BATCH_MAX_BLOCKS);
+    std::vector<int> stidx((size_t)BATCH_MAX_BLOCKS);
     for (int b = 0, p = 0; b < count && rc >= 0;) {
         if (pass_of[b] < 0) { ++b; continue; }
         int e = b;          // the pass: its members and the empty blocks between them, one contiguous range of the input
@@ -1586,7 +1647,7 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
                 if (r < LIBBSC_NO_ERROR) { B.mode &= 0xff; bigbuf_put(B.lzbuf); B.lzbuf = nullptr; }
                 else B.lz = r;
             }
-            if (aux_rate(B.lz) < 2) { B.single = true; bigbuf_put(B.lzbuf); B.lzbuf = nullptr; return; }
+            if (!st && aux_rate(B.lz) < 2) { B.single = true; bigbuf_put(B.lzbuf); B.lzbuf = nullptr; return; }
             B.sorted = true;
         };
         if (mode != (mode & 0xff)) run_bounded(e - b, threads, prep);
@@ -1600,19 +1661,20 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
             at[i] = pos;
             if (dev) {                                                           // the pass is the caller's own range of HBM
                 psz[i] = sizes[b + i];
-                prate[i] = B.sorted ? aux_rate(B.lz) : -1;
+                prate[i] = B.sorted ? (st ? 0 : aux_rate(B.lz)) : -1;
                 pos += sizes[b + i];
                 continue;
             }
             psz[i] = B.sorted ? B.lz : 0;
-            prate[i] = B.sorted ? aux_rate(B.lz) : -1;
+            prate[i] = B.sorted ? (st ? 0 : aux_rate(B.lz)) : -1;
             if (B.sorted) { memcpy(hb + pos, B.lzbuf ? B.lzbuf : in_of(B.b), (size_t)B.lz); pos += B.lz; }
             if (B.lzbuf) { bigbuf_put(B.lzbuf); B.lzbuf = nullptr; }
         }
         if (pos > 0) {
             const u8* src = dev ? din_of(b) : c->dL;
             if (!dev && hipMemcpyAsync(c->dL, hb, (size_t)pos, hipMemcpyHostToDevice, c->stream) != hipSuccess) { rc = LIBBSC_GPU_ERROR; break; }
-            rc = bwt_batch_device(c, src, c->dL, psz.data(), e - b, prate.data(), res.data(), dev ? adler.data() : nullptr);
+            rc = st ? st_batch_device(c, src, c->dL, psz.data(), e - b, blockSorter, prate.data(), stidx.data(), dev ? adler.data() : nullptr)
+                    : bwt_batch_device(c, src, c->dL, psz.data(), e - b, prate.data(), res.data(), dev ? adler.data() : nullptr);
             if (rc < 0) break;
             if (hipMemcpyAsync(hb, c->dL, (size_t)pos, hipMemcpyDeviceToHost, c->stream) != hipSuccess || ctx_sync(c) != hipSuccess) { rc = LIBBSC_GPU_ERROR; break; }
         }
@@ -1621,6 +1683,7 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
             if (B.single) single[B.b] = 1;
             if (dev) B.adler = adler[i];
             if (!B.sorted) continue;
+            if (st) { B.index = stidx[i]; B.num_indexes = 0; continue; }
             const uint32_t* I = res.data() + 16 * (size_t)i;
             B.index = (int)I[0];
             B.num_indexes = (B.lz - 1) / aux_rate(B.lz);

@@ -186,6 +186,24 @@ class GpuContext:
             o += n
         return res
 
+    def st_batch(self, dT, sizes, k, dOut=None):
+        """sort transform of order k of every block of a batch laid out back to back in the uint8 device tensor dT ->
+        [(bytes np.uint8, index)] as bsc_st_encode of the block alone (index < 0: its error code); in place unless dOut is given"""
+        import torch
+        sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32))
+        cnt = sz.size
+        out = dT if dOut is None else dOut
+        idx = np.zeros(max(cnt, 1), np.int32)
+        self._check(self.L.bscgpu_st_batch_device(self.h, _dptr(dT), _dptr(out), N.np_ptr(sz), cnt, int(k), N.np_ptr(idx)))
+        torch.cuda.synchronize(out.device)
+        Oh = out[:int(sz.sum())].cpu().numpy() if cnt else np.zeros(0, np.uint8)
+        res, o = [], 0
+        for b in range(cnt):
+            n = int(sz[b])
+            res.append((Oh[o:o + n].copy(), int(idx[b])))
+            o += n
+        return res
+
     def _batch_results(self, out, sz, results):
         blocks, o = [], 0
         for b in range(sz.size):
@@ -310,6 +328,17 @@ def batch_plan(sizes, sorter=1, cap=64 << 20):
     sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32))
     pass_of = np.zeros(max(sz.size, 1), np.int32)
     n = N.lib().bscgpu_batch_plan(N.np_ptr(sz), sz.size, sorter, int(cap), N.np_ptr(pass_of))
+    return int(n), [int(x) for x in pass_of[:sz.size]]
+
+
+ST_BATCH_MAX_N, ST_BATCH_MAX_BLOCKS = 1 << 20, 4096      # BSCGPU_ST_BATCH_MAX_N, BSCGPU_ST_BATCH_MAX_BLOCKS (include/bscgpu.h)
+
+
+def st_batch_plan(sizes, k, cap=64 << 20):
+    """bscgpu_st_batch_plan: the pass of every block of an ST batch of order k, -1 for the single-block path -> (passes, list)"""
+    sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32))
+    pass_of = np.full(max(sz.size, 1), -2, np.int32)
+    n = N.lib().bscgpu_st_batch_plan(N.np_ptr(sz), sz.size, int(k), int(cap), N.np_ptr(pass_of))
     return int(n), [int(x) for x in pass_of[:sz.size]]
 
 

@@ -14,6 +14,13 @@ single-block path).  Also the GPU time of one batched 64 MiB pass of W1 (bscgpu_
 One JSON line per measurement on stdout.
     python tools/batch_bench.py [--reps 3] [--workloads W1,W2,W3]
 
+--sorter K (default 1, the BWT: the legs above as they are): the same workloads and legs with the sort transform of order K = 3..8
+(bscgpu_st_batch_device's passes inside the batch calls; no ref_cpu16 leg for K = 7, 8, which the reference's CPU build does not
+encode), and per workload a transform-only leg, the blocks back to back in HBM: GpuContext's st_batch route (bscgpu_st_batch_device)
+against a loop of bscgpu_st_encode_device over the same blocks, repetitions interleaved (batch, loop, batch, loop, ...), every
+repetition reported.  --transform-only skips the compression legs.
+    python tools/batch_bench.py --sorter 5 [--transform-only] [--reps 5] [--workloads W1,W2]
+
 --decode: the decode side on W1..W3 and W4 = 8 x 64 MiB, blocks compressed with -e1 / -e2, without LZP and with
 -H15 -M128 (--configs picks some), MB/s of decoded output for
   batch         GpuContext.decompress_batch (host output)
@@ -164,6 +171,40 @@ def decode_main(args):
         ctx.close()
 
 
+def st_transform_leg(ctx, name, sizes, blocks, k, reps):
+    """the sort transform alone, input and output in HBM: one bscgpu_st_batch_device call against one bscgpu_st_encode_device call per block"""
+    import torch
+    from libbsc_amd import _native as N
+    from libbsc_amd.gpu import st_batch_plan
+    flat = torch.from_numpy(np.concatenate(blocks)).cuda()
+    out_a, out_b = torch.empty_like(flat), torch.empty_like(flat)
+    sz = np.array(sizes, np.int32)
+    offs = np.concatenate([[0], np.cumsum(sz, dtype=np.int64)])
+    idx_a, idx_b = np.zeros(len(sizes), np.int32), np.zeros(len(sizes), np.int32)
+    torch.cuda.synchronize()
+
+    def batch():
+        rc = ctx.L.bscgpu_st_batch_device(ctx.h, flat.data_ptr(), out_a.data_ptr(), N.np_ptr(sz), len(sizes), k, N.np_ptr(idx_a))
+        assert rc == 0, rc
+
+    def loop():
+        src, dst = flat.data_ptr(), out_b.data_ptr()
+        for b, n in enumerate(sizes):
+            idx_b[b] = ctx.L.bscgpu_st_encode_device(ctx.h, src + int(offs[b]), dst + int(offs[b]), n, k)
+
+    batch(), loop()                                         # warm-up: the batch table, both routes' first launches
+    tb, tl = [], []
+    for _ in range(reps):
+        for fn, ts in ((batch, tb), (loop, tl)):
+            t0 = time.perf_counter()
+            fn()                                            # (both routes are synchronous on return)
+            ts.append(round((time.perf_counter() - t0) * 1e3, 2))
+    same = bool(torch.equal(out_a, out_b)) and bool((idx_a == idx_b).all())
+    print(json.dumps({"workload": name, "sorter": k, "leg": "st_transform_only", "blocks": len(sizes), "MB": round(sum(sizes) / 1e6, 2),
+                      "passes": st_batch_plan(sizes, k, ctx.max_n)[0], "st_batch_ms": tb, "st_encode_device_loop_ms": tl,
+                      "speedup_of_medians": round(float(np.median(tl) / np.median(tb)), 2), "identical": same}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -171,6 +212,8 @@ def main():
     ap.add_argument("--coder", type=int, default=1)
     ap.add_argument("--contexts", type=int, default=5)
     ap.add_argument("--depth", type=int, default=2)
+    ap.add_argument("--sorter", type=int, default=1, help="1 = BWT (default), 3..8 = the sort transform of that order")
+    ap.add_argument("--transform-only", action="store_true", help="with --sorter 3..8: only the st_batch against st_encode_device leg")
     ap.add_argument("--decode", action="store_true", help="the decode side: decompress_batch against the per-block paths")
     ap.add_argument("--configs", default="e1,e2,e1-lzp,e2-lzp")
     ap.add_argument("--profile-pass", action="store_true", help="with --decode: one decompress_batch per workload and config, nothing timed")
@@ -185,20 +228,24 @@ def main():
     from libbsc_amd import api
     from oracle.refbind import Ref, REF_SO
     refc = Ref() if os.path.exists(REF_SO) else None
-    sorter, coder = 1, args.coder
+    sorter, coder = args.sorter, args.coder
     ctx = GpuContext(0, max_n=(64 << 20) + 4096)
-    pctx = [GpuContext(0, max_n=(1 << 20) + 4096) for _ in range(args.contexts)]
+    pctx = [GpuContext(0, max_n=(1 << 20) + 4096) for _ in range(0 if args.transform_only else args.contexts)]
     pipes = [c.pipe(args.depth) for c in pctx]
     try:
         for name in args.workloads.split(","):
             sizes, blocks = workload(name)
             mb = sum(sizes) / 1e6
+            if sorter != 1:
+                st_transform_leg(ctx, name, sizes, blocks, sorter, max(args.reps, 5))
+                if args.transform_only:
+                    continue
             dblocks = [torch.from_numpy(b).cuda() for b in blocks]
             torch.cuda.synchronize()
             ref = run_pipe(pipes, dblocks, sizes, sorter, coder, args.depth)         # warm-up + the single-block outputs
             run_batch(ctx, blocks[:8], sorter, coder)
             flat = torch.from_numpy(np.concatenate(blocks)).cuda()
-            legs = ["batch", "batch_device", "pipe", "dropin16"] + (["ref_cpu16"] if refc else [])
+            legs = ["batch", "batch_device", "pipe", "dropin16"] + (["ref_cpu16"] if refc and sorter <= 6 else [])
             for leg in legs:
                 best = None
                 ok = True
@@ -216,10 +263,11 @@ def main():
                     ok = ok and all(a == b for a, b in zip(out, ref))
                     if best is None or wall < best[0]:
                         best = (wall, cpu)
-                print(json.dumps({"workload": name, "leg": leg, "blocks": len(sizes), "MB": round(mb, 2), "MB_s": round(mb / best[0], 1),
+                print(json.dumps({"workload": name, **({"sorter": sorter} if sorter != 1 else {}),
+                                  "leg": leg, "blocks": len(sizes), "MB": round(mb, 2), "MB_s": round(mb / best[0], 1),
                                   "ms": round(best[0] * 1e3, 1), "cpu_s_per_MB": round(best[1] / mb, 4),
                                   "identical_to_single_block_path": bool(ok)}), flush=True)
-            if name == "W1":
+            if name == "W1" and sorter == 1:
                 # one 64 MiB batched pass of W1's blocks: GPU time of the sort alone
                 flat = torch.from_numpy(np.concatenate(blocks)).cuda()
                 dL = torch.empty_like(flat)
