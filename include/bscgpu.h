@@ -82,7 +82,8 @@ BSCGPU_API int bscgpu_radix_sort_u64(bscgpu_ctx* ctx, void* keys, void* keys_alt
  * + every probability of the static model (qlfc.cpp:896-1126, predictor.h:53-61,121) as a stream of 16-bit entries
  * {[11:0] probability, [12] coded bit, [13] first decision of a run}, stream order, all sub-blocks back to back
  * (poff[b]..poff[b+1] = sub-block b).  Returns the number of decisions, LIBBSC_NOT_SUPPORTED (-4) when the block has to take
- * the host model (more than 256 distinct decision types, ...; bscgpu_last_error says which), or a negative libbsc code.
+ * the host model (a context bracket that does not close, a chain that would be replayed over more than 64 chunks, capacity;
+ * bscgpu_last_error and BSCGPU_CNT_DC_LAST_FAIL say which), or a negative libbsc code.
  * dbg (optional, [3][cap]): the state- / char- / static-counter value behind every decision. */
 BSCGPU_API int64_t bscgpu_qlfc_static_pstream(bscgpu_ctx* ctx, const uint8_t* L, int n, uint16_t* out, int64_t cap, int* nblocks,
                                    int* sub_start /*[8]*/, int* sub_size /*[8]*/, int64_t* poff /*[9]*/, uint16_t* dbg);
@@ -333,8 +334,19 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          16-bit entries (298 instead of 366 MB per 64 MiB text block).  The run-start mark of the 16-bit entry only
  *                          placed the reference's output-budget test; a stream that reaches its budget is redone on the host model
  *                          either way.  Same output.
+ * BSCGPU_CNT_DC_*          (get only) the last block this context gave to the device model of the static / fast coder, whether it
+ *                          stayed there or was declined (the block is then coded through the host model, same bytes):
+ *     _REPLAYS             evaluation chunks whose start value had to be replayed serially (the predecessor's bracket had not met)
+ *     _LAST_FAIL           why the block was declined: a mask of BSCGPU_DC_FAIL_*, 0 when it stayed on the device
+ *     _AVG_UNDECIDED       runs whose avg_rank >= 32 flag the warmed-up bracket left open (any such run declines: _FAIL_AVG)
+ *     _HIST_EXTENDED       runs whose run_hist bracket was still open after nine predecessors of their symbol and went on to the
+ *                          extended look-back (36 .. 9216 predecessors; still open after that: _FAIL_HIST)
  * set returns the previous value or a negative libbsc error code; get the value or a negative error code. */
-enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACKED_STREAM = 4 };
+enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACKED_STREAM = 4,
+       BSCGPU_CNT_DC_REPLAYS = 5, BSCGPU_CNT_DC_LAST_FAIL = 6, BSCGPU_CNT_DC_AVG_UNDECIDED = 7, BSCGPU_CNT_DC_HIST_EXTENDED = 8 };
+/* _FAIL_AVG: undecided avg_rank flags; _FAIL_HIST: a run_hist bracket open after 9216 predecessors; _FAIL_CAP: more runs or decisions
+ * than the context's arena holds; _FAIL_REPLAY: a chain whose bracket stayed open over more than 64 evaluation chunks. */
+enum { BSCGPU_DC_FAIL_AVG = 2, BSCGPU_DC_FAIL_HIST = 4, BSCGPU_DC_FAIL_CAP = 8, BSCGPU_DC_FAIL_REPLAY = 16 };
 BSCGPU_API int bscgpu_option_set(bscgpu_ctx* ctx, int key, int value);
 BSCGPU_API int bscgpu_option_get(bscgpu_ctx* ctx, int key);
 /* Process-wide counts since start (tests, reports): blocks whose static model ran on the GPU, how many of those were LZP-preprocessed,

@@ -326,6 +326,10 @@ extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
     if (key == BSCGPU_OPT_RS_ONESWEEP) return c->os_mode;
     if (key == BSCGPU_CNT_OS_RETRIES) return c->os_retries;
     if (key == BSCGPU_OPT_DC_PACKED_STREAM) return c->dc_p13;
+    if (key == BSCGPU_CNT_DC_REPLAYS) return c->dc_replays;
+    if (key == BSCGPU_CNT_DC_LAST_FAIL) return c->dc_last_fail;
+    if (key == BSCGPU_CNT_DC_AVG_UNDECIDED) return c->dc_avg_und;
+    if (key == BSCGPU_CNT_DC_HIST_EXTENDED) return c->dc_hist_ext;
     return BSC_BAD_PARAMETER;
 }
 extern "C" int bscgpu_last_stage_ms(bscgpu_ctx* c, double* out6)

@@ -134,8 +134,11 @@ struct bscgpu_ctx {
     int      nslots = 0;
     DevCoder* dc = nullptr;
     bool     dc_alloc_failed = false;   // the device coder's arena did not fit: this context keeps the host model (not retried per block)
-    int      dc_last_fail = 0;   // why the last block left the device coder (bit mask, devcoder.hip FAIL_*), 0 = it did not
-    int      dc_replays = 0;     // evaluation chunks replayed serially in the last block
+    // the last block that went to the device coder (bscgpu_option_get: BSCGPU_CNT_DC_*), set whether the block stayed there or not
+    int      dc_last_fail = 0;   // why it left the device coder (bit mask, devcoder.hip FAIL_* = BSCGPU_DC_FAIL_*), 0 = it did not
+    int      dc_replays = 0;     // evaluation chunks replayed serially
+    int      dc_avg_und = 0;     // runs whose avg_rank >= 32 flag the two-sided bracket left undecided (any: FAIL_AVG)
+    int      dc_hist_ext = 0;    // runs whose run_hist bracket was still open after nine predecessors (the extended look-back)
 
     // profiling
     bool         prof        = false;

@@ -25,8 +25,9 @@
 //                    emit 16 bits per decision: probability, coded bit, start-of-run mark.
 //
 // The host (qlfc.cpp: encode_from_pstream) then runs only the range coder.  Whenever something is outside what this path
-// handles exactly (more than 256 distinct decision types in a block, an avg_rank bracket that does not decide, capacity),
-// a flag is raised and the caller falls back to the host model; nothing approximate is ever emitted.
+// handles exactly (an avg_rank bracket that does not decide, a run_hist bracket still open after 9216 predecessors, a chain whose
+// bracket stays open over more than 64 evaluation chunks, capacity), a flag is raised and the caller falls back to the host model;
+// nothing approximate is ever emitted.
 #include "dev_common.h"
 #include "dma_copy.h"
 #include <thread>
@@ -55,18 +56,14 @@ __device__ __forceinline__ u32 dc_virtual_block() {
 }
 
 constexpr int DC_WCH_MAX  = 4096;      // wave-chunks of a partition job (one wavefront walks one chunk of runs)
-#ifndef DC_EV_N
-#define DC_EV_N 8192
-#endif
-constexpr int DC_EV       = DC_EV_N;   // events per evaluation chunk: the minimum (see devcoder_pstream: long enough for the brackets to meet)
-constexpr int DC_AVG_CH   = 1024;      // runs per avg_rank lane
-constexpr int DC_AVG_WARM = 768;       // warm-up runs in front of an avg_rank chunk
+// (DC_EV, DC_AVG_CH, DC_AVG_WARM, DC_HIST_NP, DC_HIST_KMAX, DC_REPLAY_MAX: devcoder_model.h — the CPU probe of the exits shares them)
 constexpr u32 DC_SIGMASK  = 0x7ffu;    // event = X | sub-block << 8 | bit << 11
 constexpr int DC_ROWS     = 1088;      // rows of the chain-major layout = decision types (NUM_TAU = 1080), padded to whole wavefronts
 
 // meta scalars (device u32 array)
-enum { DM_FAIL = 0, DM_NTYPES, DM_NROUNDS, DM_AVG_UND, DM_REPLAYS, DM_D0, DM_D1, DM_D2, DM_D3, DM_HIST_FAIL, DM_P13_OVER /* a wavefront's piece did not fit the staging buffer: the packed stream is void */, DM_COUNT = 16 };
-enum { FAIL_TYPES = 1, FAIL_AVG = 2, FAIL_HIST = 4, FAIL_CAP = 8, FAIL_REPLAY = 16 };
+enum { DM_FAIL = 0, DM_NTYPES, DM_NROUNDS, DM_AVG_UND, DM_REPLAYS, DM_D0, DM_D1, DM_D2, DM_D3, DM_HIST_EXT /* runs that entered the extended run_hist look-back */, DM_P13_OVER /* a wavefront's piece did not fit the staging buffer: the packed stream is void */, DM_COUNT = 16 };
+// (bit 0 is not in use: every decision type has a row of its own, DC_ROWS >= NUM_TAU, so no number of types is too many)
+enum { FAIL_AVG = BSCGPU_DC_FAIL_AVG, FAIL_HIST = BSCGPU_DC_FAIL_HIST, FAIL_CAP = BSCGPU_DC_FAIL_CAP, FAIL_REPLAY = BSCGPU_DC_FAIL_REPLAY };
 
 struct DcSub { u32 nb; u32 first[9]; u32 maxr[8]; };           // run index range (first[nb] = m) and max_rank of each sub-block
 struct DcRowBins { u16 lo1, hi1, lo2, hi2; };                   // counting pass: count(row) = P[hi1] - P[lo1] + P[hi2] - P[lo2] over bin prefix sums
@@ -186,7 +183,7 @@ __global__ __launch_bounds__(WG) void dc_ctx_kernel(const u64* __restrict__ key_
         // enough that the bracket below almost always closes: on the bench block 1.9 % of the runs — a lane in 38 % of the wavefronts —
         // stay open after five predecessors (a symbol whose recent runs all have length 2 or 3 has two fixed points, 1 and 2), 0.015 %
         // after nine)
-        constexpr int NP = 9;
+        constexpr int NP = DC_HIST_NP;
         u64 pk[NP];
         if (q >= 10u) {
             // the nine predecessors are 72 consecutive bytes: five 16-byte loads instead of nine 8-byte ones (round 6: the kernel is bound by
@@ -219,6 +216,7 @@ __global__ __launch_bounds__(WG) void dc_ctx_kernel(const u64* __restrict__ key_
             u32 cl = lo < 7u ? lo : 7u, ch = hi < 7u ? hi : 7u;
             if (cl != ch) {
                 // rare: look further back (quadrupling) until the clamped values agree or the chain starts
+                atomicAdd(&meta[DM_HIST_EXT], 1u);
                 u32 K = 4 * NP;
                 for (;;) {
                     lo = 0; hi = 63; u32 first = q; bool exact = false;
@@ -230,7 +228,7 @@ __global__ __launch_bounds__(WG) void dc_ctx_kernel(const u64* __restrict__ key_
                     for (u32 p = first; p < q; ++p) { const u32 r = item_unpack(key_ch_s[p]).run; lo = run_hist_next(lo, r); hi = run_hist_next(hi, r); }
                     cl = lo < 7u ? lo : 7u; ch = hi < 7u ? hi : 7u;
                     if (cl == ch) break;
-                    if (K >= 4096) { atomicOr(&meta[DM_FAIL], (u32)FAIL_HIST); break; }
+                    if (K >= (u32)DC_HIST_KMAX) { atomicOr(&meta[DM_FAIL], (u32)FAIL_HIST); break; }
                     K *= 4;
                 }
             }
@@ -702,7 +700,6 @@ __device__ __forceinline__ u32 dc_find_row(P rowstart, u32 k)
 #ifndef DC_EVAL_TIMING
 #define DC_EVAL_TIMING 0
 #endif
-constexpr int DC_EB = 64;                       // events per lane per batch
 constexpr int DC_EROW = DC_EB * 2 + 16;         // LDS row pitch in bytes (padded)
 // all four jobs of a block in one launch (they are independent, and one job alone leaves most SIMDs idle: a lane is a serial chain)
 struct DcEvalAll { DcEvalJob job[4]; u32 wstart[5]; u32 cstart[5]; u16* V[4]; u16* sink; u32 ev; };   // first wavefront / first chunk of each job; events per chunk
@@ -923,7 +920,7 @@ __global__ __launch_bounds__(WG) void dc_eval_b_kernel(DcEvalAll A, const ModelP
         if (!dc_chunk_continues(J, j, EV)) { start = init_c; break; }
         if (elo[j - 1] == ehi[j - 1]) { start = elo[j - 1]; break; }
         --j; ++depth;
-        if (depth > 64) { atomicOr(&meta[DM_FAIL], (u32)FAIL_REPLAY); Sv[c] = (u16)init_c; return; }
+        if (depth > (u32)DC_REPLAY_MAX) { atomicOr(&meta[DM_FAIL], (u32)FAIL_REPLAY); Sv[c] = (u16)init_c; return; }
     }
     atomicAdd(&meta[DM_REPLAYS], depth);
     // Exact walk over chunks j .. c - 1.  None of them coalesced, so none contains a chain boundary (a boundary resets both ends of the
@@ -1363,6 +1360,15 @@ static void dc_launch_partition(bscgpu_ctx* c, DevCoder* d, const u64* items, u3
     prof_end(c);
 }
 
+// what bscgpu_option_get reports about the context's last block, from the meta words just read back (declined or not)
+static void dc_note_block(bscgpu_ctx* c, const DevCoder* d)
+{
+    c->dc_last_fail = (int)d->hmeta[DM_FAIL];
+    c->dc_replays = (int)d->hmeta[DM_REPLAYS];
+    c->dc_avg_und = (int)d->hmeta[DM_AVG_UND];
+    c->dc_hist_ext = (int)d->hmeta[DM_HIST_EXT];
+}
+
 // Probability stream of a whole block.  Inputs: the QLFC front end's run arrays on the device (sym / rank / start, m runs of
 // the n-byte sorted block), the sub-blocks' run ranges and max_rank values.  On success *D_out decisions were written to the
 // device p stream (d->ps) and poff[0..nb] (decision offsets of the sub-blocks) to hmeta[32..]; returns BSC_NOT_SUPPORTED when
@@ -1382,6 +1388,8 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
     int rc = devcoder_ensure(c);
     if (rc < 0) return rc;
     DevCoder* d = c->dc;
+    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = 0;
+    c->dc_last_fail = m > d->Mcap ? (int)FAIL_CAP : 0;                 // (more runs than the arena holds: capacity, as too many decisions are)
     if (m == 0 || m > d->Mcap || nb < 1 || nb > 8) return BSC_NOT_SUPPORTED;
     if (coder == 3) return devcoder_pstream_fast(c, d, dsym, drank, dstart, m, n, nb, run_first, D_out, poff_out, psbuf);
     DcSub S; S.nb = (u32)nb;
@@ -1432,7 +1440,7 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
     HIP_TRY(c, hipMemcpyAsync(d->hmeta + 32, d->poff, 16 * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
     prof_collect(c);
-    if (d->hmeta[DM_FAIL] != 0) { c->dc_last_fail = (int)d->hmeta[DM_FAIL]; return BSC_NOT_SUPPORTED; }
+    if (d->hmeta[DM_FAIL] != 0) { dc_note_block(c, d); return BSC_NOT_SUPPORTED; }
     u32 poff_h[9];
     for (int b = 0; b <= nb; ++b) poff_h[b] = d->hmeta[32 + b];
     u32 E[4];
@@ -1445,12 +1453,7 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
         // One lane is one serial chain, so the walks are VALU-issue bound with ONE wavefront per SIMD (1024 of them); a few
         // wavefronts more than that and some SIMDs get two, which doubles the kernel's time.  Chunks are therefore DC_EV events
         // (what the brackets need to meet) or as many as it takes to stay at <= 1000 wavefronts (+ <= 4 of padding) per launch.
-        {
-            const u64 Etot = (u64)E[0] + E[1] + E[2] + E[3];
-            u64 ev = (Etot + 64ull * 1000 - 1) / (64ull * 1000);
-            ev = (ev + DC_EB - 1) / DC_EB * DC_EB;
-            A.ev = ev < (u64)DC_EV ? (u32)DC_EV : (u32)ev;
-        }
+        A.ev = eval_chunk_events((u64)E[0] + E[1] + E[2] + E[3]);
         for (int job = 0; job < 4; ++job) {
             const int fam = job == 0 ? FAM_STATIC : job == 1 ? FAM_CHAR : FAM_STATE;
             A.job[job].events = d->events[job]; A.job[job].E = E[job]; A.job[job].rowstart = d->rowstart + (DC_ROWS + 8) * job;
@@ -1496,7 +1499,7 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
-    if (d->hmeta[DM_FAIL] != 0) { c->dc_last_fail = (int)d->hmeta[DM_FAIL]; return BSC_NOT_SUPPORTED; }
+    if (d->hmeta[DM_FAIL] != 0) { dc_note_block(c, d); return BSC_NOT_SUPPORTED; }
     if (packed && d->hmeta[DM_P13_OVER] != 0) {
         // 64 consecutive runs with more decisions than a wavefront's staging buffer holds (runs of thousands): this block's stream in the 2-byte form
         packed = false;
@@ -1507,8 +1510,7 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
         HIP_TRY(c, ctx_sync(c));
     }
     if (packed_out) *packed_out = packed ? 1 : 0;
-    c->dc_last_fail = 0;
-    c->dc_replays = (int)d->hmeta[DM_REPLAYS];
+    dc_note_block(c, d);
 #if DC_EVAL_TIMING
     {
         std::vector<u32> h(6 * 4096);
@@ -1561,15 +1563,13 @@ static int devcoder_pstream_fast(bscgpu_ctx* c, DevCoder* d, const u8* dsym, con
     HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
     prof_collect(c);
-    if (d->hmeta[DM_FAIL] != 0) { c->dc_last_fail = (int)d->hmeta[DM_FAIL]; return BSC_NOT_SUPPORTED; }
+    if (d->hmeta[DM_FAIL] != 0) { dc_note_block(c, d); return BSC_NOT_SUPPORTED; }
     const u32 E = d->hmeta[DM_D0 + 1];
     if (d->hmeta[DM_D0 + 0] != E) return ctx_fail(c, BSC_GPU_ERROR, "device coder (fast): decision counts of stream and chain order differ", hipSuccess);
     {
         DcEvalAll A;
         A.sink = d->sink;
-        u64 ev = ((u64)E + 64ull * 1000 - 1) / (64ull * 1000);
-        ev = (ev + DC_EB - 1) / DC_EB * DC_EB;
-        A.ev = ev < (u64)DC_EV ? (u32)DC_EV : (u32)ev;
+        A.ev = eval_chunk_events((u64)E);
         A.wstart[0] = 0; A.cstart[0] = 0;
         for (int job = 0; job < 4; ++job) {
             A.job[job].events = d->events[job]; A.job[job].E = job == 1 ? E : 0u; A.job[job].rowstart = d->rowstart + (DC_ROWS + 8) * job;
@@ -1604,9 +1604,8 @@ static int devcoder_pstream_fast(bscgpu_ctx* c, DevCoder* d, const u8* dsym, con
     HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(d->hmeta + 32, d->poff, 16 * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
-    if (d->hmeta[DM_FAIL] != 0) { c->dc_last_fail = (int)d->hmeta[DM_FAIL]; return BSC_NOT_SUPPORTED; }
-    c->dc_last_fail = 0;
-    c->dc_replays = (int)d->hmeta[DM_REPLAYS];
+    if (d->hmeta[DM_FAIL] != 0) { dc_note_block(c, d); return BSC_NOT_SUPPORTED; }
+    dc_note_block(c, d);
     if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder fast] decisions %u, chunks replayed %u\n", E, d->hmeta[DM_REPLAYS]);
     *D_out = E;
     for (int b = 0; b <= nb; ++b) poff_out[b] = d->hmeta[32 + b];

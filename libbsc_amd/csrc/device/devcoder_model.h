@@ -325,6 +325,27 @@ DC_HD uint32_t run_state_index(uint32_t ctx_rank0, uint32_t ctx_run, uint32_t ra
     return (ctx_rank0 << 10) | (ctx_run << 6) | ((r1 < 7u ? r1 : 7u) << 3) | (run_hist < 7u ? run_hist : 7u);
 }
 
+// ---- sizes of the device walk that decide which exit a block takes ------------------------------------------------------
+// (devcoder.hip walks by them; tools/devcoder_paths_probe.cpp predicts from them, on the CPU, which exits a given block must take)
+#ifndef DC_EV_N
+#define DC_EV_N 8192
+#endif
+constexpr int DC_EV          = DC_EV_N;  // events per evaluation chunk: the minimum (see devcoder_pstream: long enough for the brackets to meet)
+constexpr int DC_EVAL_WAVES_TARGET = 1000;   // ... or as many as keep a block's evaluation at this many wavefronts of 64 chunks
+constexpr int DC_EB          = 64;       // events per lane per batch of the evaluation walk (chunks are whole batches)
+constexpr int DC_REPLAY_MAX  = 64;       // chunks a serial replay walks back before the block is declined (FAIL_REPLAY)
+constexpr int DC_AVG_CH      = 1024;     // runs per avg_rank lane
+constexpr int DC_AVG_WARM    = 768;      // warm-up runs in front of an avg_rank chunk
+constexpr int DC_HIST_NP     = 9;        // predecessors of a run's symbol that the run_hist bracket always walks
+constexpr int DC_HIST_KMAX   = 4096;     // the extended look-back quadruples from 4 DC_HIST_NP and gives up (FAIL_HIST) at the first K >= this
+// events per evaluation chunk of a block with Etot events over all jobs
+inline uint32_t eval_chunk_events(uint64_t Etot)
+{
+    uint64_t ev = (Etot + 64ull * DC_EVAL_WAVES_TARGET - 1) / (64ull * DC_EVAL_WAVES_TARGET);
+    ev = (ev + DC_EB - 1) / DC_EB * DC_EB;
+    return ev < (uint64_t)DC_EV ? (uint32_t)DC_EV : (uint32_t)ev;
+}
+
 // p-stream entry handed to the range coder: [11:0] probability, [12] bit, [13] first decision of a run
 constexpr uint16_t PS_BIT = 1u << 12, PS_RUN = 1u << 13;
 // ... of the fast coder: [12:0] probability (13 bits on the rank side, 11 on the run side), [13] bit, [14] first decision of a run,

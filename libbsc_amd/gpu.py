@@ -291,6 +291,8 @@ class GpuContext:
 
     # ---- measurement / test knobs (include/bscgpu.h: BSCGPU_OPT_*, BSCGPU_CNT_*) ---------------------------------
     OPT_RS_ONESWEEP, CNT_OS_RETRIES, OPT_DC_PACKED_STREAM = 1, 2, 4
+    CNT_DC_REPLAYS, CNT_DC_LAST_FAIL, CNT_DC_AVG_UNDECIDED, CNT_DC_HIST_EXTENDED = 5, 6, 7, 8      # the last device-model block (get only)
+    DC_FAIL_AVG, DC_FAIL_HIST, DC_FAIL_CAP, DC_FAIL_REPLAY = 2, 4, 8, 16                          # BSCGPU_DC_FAIL_*
 
     def option_set(self, key, value):
         return self._check(self.L.bscgpu_option_set(self.h, key, value))

@@ -61,6 +61,29 @@ def bit_length(x):
     return int(x).bit_length()
 
 
+def key_geometry(K, n, batch_count=0):
+    """The first sort's key layout as bwt_device_once derives it from the alphabet size K of the text (of the whole pass for a batch), the
+    length n and the number of blocks of a batched pass (0: a single block):
+      cb          bits per character: the smallest with 2^cb >= K, at least 4; a batch codes 1..K (0 = past the block's end): K + 1
+      w           characters per key: 64 / cb; a batch keeps batch_bb bits for the block field on top, at most 16 characters
+      low_shift   lowest key bit in use; passes: the (shift, bits) digit passes, 8 bits each, the topmost with what is left
+      ta          characters per round on text keys (they need 4 bits beside the characters): w, or w - 1 where w cb + 4 > 64
+      pred_shift  where the value carries the code of the character in front of the suffix: idx_bits while idx_bits + cb <= 32 on a single
+                  block, else 0 (L is then gathered from the text)
+      batch_bb    bits of the block field"""
+    bt = batch_count > 0
+    batch_bb = bit_length(batch_count - 1) if bt else 0
+    kk = K + (1 if bt else 0)
+    cb = max(4, bit_length(kk - 1), 1)
+    w = min(16, (64 - batch_bb) // cb) if bt else 64 // cb
+    low_shift = 64 - cb * w - batch_bb
+    passes = [(s, min(8, 64 - s)) for s in range(low_shift, 64, 8)]
+    ta = w if cb * w + 4 <= 64 else w - 1
+    idx_bits = bit_length(n - 1)
+    pred_shift = idx_bits if (not bt and idx_bits >= 1 and idx_bits + cb <= 32) else 0
+    return dict(cb=cb, w=w, low_shift=low_shift, passes=passes, ta=ta, pred_shift=pred_shift, batch_bb=batch_bb)
+
+
 def bwt_model(T, r=None):
     """-> (L, primary (1-based), I array like libsais_bwt_aux), rounds"""
     T = np.asarray(T, np.uint8)

@@ -571,8 +571,13 @@ def test_packed_probability_stream_equals_the_16_bit_entries(ctx):
     with pytest.raises(GpuError) as e:
         ctx.qlfc_static_pstream_packed(long_runs)
     assert e.value.code == -4
-    ps, *_ = ctx.qlfc_static_pstream(long_runs)
-    assert len(ps) > 0
+    ps, st, sz, poff, _ = ctx.qlfc_static_pstream(long_runs)
+    assert len(ps) > 0 and poff[0] == 0 and poff[-1] == len(ps)
+    from oracle.refbind import Oracle
+    orc = Oracle()
+    for b in range(len(st)):                                        # ... and the 16-bit stream of that block is the reference model's
+        tr, _ = orc.static_pstream(long_runs[st[b]:st[b] + sz[b]])
+        assert np.array_equal(tr, ps[poff[b]:poff[b + 1]]), ("long runs", b)
     # option off: refused as well, the 16-bit stage unaffected
     ctx.option_set(ctx.OPT_DC_PACKED_STREAM, 0)
     try:
