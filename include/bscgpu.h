@@ -145,6 +145,46 @@ BSCGPU_API int bscgpu_compress_batch(bscgpu_ctx* ctx, const unsigned char* input
 BSCGPU_API int bscgpu_compress_batch_device(bscgpu_ctx* ctx, const void* dInput, const int* sizes, int count, unsigned char* output,
                                             int* results, int blockSorter, int coder, int features);
 
+/* ---- the QLFC front end of a whole pass ---------------------------------------
+ * What bsc_coder_compress does to a sorted block before any entropy coding — the sub-block split (coder.cpp:70-109), the run scan
+ * and the backward move-to-front rank (qlfc.cpp:398-455) — for every block of a pass at once, as flat arrays in ONE run index space.
+ * The caller owns every array of the layout and sets the pointers before the call; N = Σ sizes[b]:
+ *   blk_sub   [count + 1]   first sub-block of block b; block b has blk_sub[b + 1] - blk_sub[b] sub-blocks (0 for an empty block,
+ *                           else coder_num_blocks(n_b): 1 below 256 KiB, 2 from there on); blk_sub[count] = nsub
+ *   sub_start [2 count]     sub-block s: its first byte, relative to ITS BLOCK's first byte ...
+ *   sub_size  [2 count]     ... and its length
+ *   sub_run   [2 count + 1] runs sub_run[s] .. sub_run[s + 1] - 1 are sub-block s's; sub_run[nsub] = m
+ *   nsym      [2 count]     distinct symbols of sub-block s ...
+ *   first_seen[2 count][256] ... and those symbols in order of first appearance (the stream's alphabet header): entries [256 s, 256 s + nsym[s])
+ *   sym, rank [N]           run j: its symbol and its QLFC rank (the last run of every sub-block has rank 1)
+ *   start     [N]           run j: its first byte, relative to its block's first byte (a run ends where the next one starts, the
+ *                           last run of a sub-block at sub_start + sub_size); a head is forced at every sub-block start
+ * nsub and m are written by the call.  This is the layout the compress-batch calls use internally.
+ * bscgpu_qlfc_front_batch_device: dL = L of `count` sorted blocks back to back in HBM, under a pass's limits (count <= 4096, every
+ *   block below BSCGPU_BATCH_MAX_N, N <= max_n).  Synchronous.  Returns 0, LIBBSC_BAD_PARAMETER, or a GPU error.
+ * bscgpu_front_batch_host: the same layout built on the CPU from the reference's own rules (no GPU, no context) — the stand-in
+ *   the tests compare the device stage against.
+ * bscgpu_front_batch_code: codes block `block` of a layout into out (sizes[block] + 4096 bytes): what bsc_coder_compress(L_b, out,
+ *   n_b, coder, features) returns and writes; a sub-block that has to be stored raw is rebuilt from its runs.  Thread-safe for
+ *   different blocks of one layout. */
+typedef struct bscgpu_front_layout {
+    int count, nsub;
+    int64_t m;
+    const int* sizes;
+    int* blk_sub;
+    int* sub_start;
+    int* sub_size;
+    uint32_t* sub_run;
+    int* nsym;
+    uint8_t* first_seen;
+    uint8_t* sym;
+    uint8_t* rank;
+    uint32_t* start;
+} bscgpu_front_layout;
+BSCGPU_API int bscgpu_qlfc_front_batch_device(bscgpu_ctx* ctx, const void* dL, const int* sizes, int count, bscgpu_front_layout* out);
+BSCGPU_API int bscgpu_front_batch_host(const unsigned char* L, const int* sizes, int count, bscgpu_front_layout* out);
+BSCGPU_API int bscgpu_front_batch_code(const bscgpu_front_layout* layout, int block, unsigned char* out, int coder, int features);
+
 /* ---- batched decompression: one inverse-BWT pass for many blocks -------------
  * bscgpu_unbwt_batch_device: L of `count` blocks back to back in HBM (block b at Σ sizes[0..b), primary[b] its 1-based
  *   primary index) -> T in the same layout; dT may be dL.  Passes of consecutive blocks, at most max_n bytes and
@@ -341,9 +381,15 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *     _AVG_UNDECIDED       runs whose avg_rank >= 32 flag the warmed-up bracket left open (any such run declines: _FAIL_AVG)
  *     _HIST_EXTENDED       runs whose run_hist bracket was still open after nine predecessors of their symbol and went on to the
  *                          extended look-back (36 .. 9216 predecessors; still open after that: _FAIL_HIST)
+ * BSCGPU_OPT_BATCH_FRONT    1: the passes of bscgpu_compress_batch / _batch_device run the QLFC front end of the whole pass on the GPU and
+ *                          bring down its run arrays (sym, rank, start) instead of L; 0: L comes down and every block goes through
+ *                          bsc_coder_compress on the host.  Same output.  Default 1 (measured: DESIGN §2b).
+ * BSCGPU_CNT_BATCH_FRONT_PASSES, BSCGPU_CNT_BATCH_L_PASSES  (get only) passes of this context's compress-batch calls that took each
+ *                          of the two routes (a pass whose pinned run buffers cannot be had takes the L route).
  * set returns the previous value or a negative libbsc error code; get the value or a negative error code. */
 enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACKED_STREAM = 4,
-       BSCGPU_CNT_DC_REPLAYS = 5, BSCGPU_CNT_DC_LAST_FAIL = 6, BSCGPU_CNT_DC_AVG_UNDECIDED = 7, BSCGPU_CNT_DC_HIST_EXTENDED = 8 };
+       BSCGPU_CNT_DC_REPLAYS = 5, BSCGPU_CNT_DC_LAST_FAIL = 6, BSCGPU_CNT_DC_AVG_UNDECIDED = 7, BSCGPU_CNT_DC_HIST_EXTENDED = 8,
+       BSCGPU_OPT_BATCH_FRONT = 9, BSCGPU_CNT_BATCH_FRONT_PASSES = 10, BSCGPU_CNT_BATCH_L_PASSES = 11 };
 /* _FAIL_AVG: undecided avg_rank flags; _FAIL_HIST: a run_hist bracket open after 9216 predecessors; _FAIL_CAP: more runs or decisions
  * than the context's arena holds; _FAIL_REPLAY: a chain whose bracket stayed open over more than 64 evaluation chunks. */
 enum { BSCGPU_DC_FAIL_AVG = 2, BSCGPU_DC_FAIL_HIST = 4, BSCGPU_DC_FAIL_CAP = 8, BSCGPU_DC_FAIL_REPLAY = 16 };

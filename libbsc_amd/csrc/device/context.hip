@@ -140,6 +140,19 @@ int ctx_ensure_pstream_slot(bscgpu_ctx* c, HostSlot& slot, size_t entries)
     return BSC_NO_ERROR;
 }
 
+int ctx_ensure_front_host(bscgpu_ctx* c)
+{
+    const size_t N = align_up((size_t)c->max_n + 4096, 4096);
+    const size_t bytes = 6 * N + front_scratch_bytes(c->max_n);
+    for (int k = 0; k < 2; ++k) {
+        if (c->front_host[k]) continue;
+        c->front_host[k] = (u8*)pinned_alloc(bytes);
+        if (!c->front_host[k]) return BSC_NOT_ENOUGH_MEMORY;
+        c->front_host_bytes = bytes;
+    }
+    return BSC_NO_ERROR;
+}
+
 extern "C" int bscgpu_d2h_dma_available(void) { return dma_available(); }
 
 extern "C" int bscgpu_device_count(void)
@@ -231,6 +244,8 @@ extern "C" void bscgpu_destroy(bscgpu_ctx* c)
     if (c->long_tables) { (void)hipFree(c->long_tables); c->long_tables = nullptr; }
     if (c->batch_tab) { (void)hipFree(c->batch_tab); c->batch_tab = nullptr; c->batch_bytes = 0; }
     for (auto& hb : c->batch_host) if (hb) { (void)hipHostFree(hb); hb = nullptr; }
+    if (c->front_tab) { (void)hipFree(c->front_tab); c->front_tab = nullptr; c->front_bytes = 0; }
+    for (auto& hb : c->front_host) if (hb) { pinned_free(hb, c->front_host_bytes); hb = nullptr; }
     if (c->copy_stream) { hipStreamSynchronize(c->copy_stream); hipStreamDestroy(c->copy_stream); }
     for (auto& p : c->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto& e : c->event_pool) hipEventDestroy(e);
@@ -254,7 +269,7 @@ extern "C" void bscgpu_destroy(bscgpu_ctx* c)
     delete c;
 }
 
-extern "C" int64_t bscgpu_arena_bytes(const bscgpu_ctx* c) { return c ? (int64_t)(c->arena_bytes + c->batch_bytes) : 0; }
+extern "C" int64_t bscgpu_arena_bytes(const bscgpu_ctx* c) { return c ? (int64_t)(c->arena_bytes + c->batch_bytes + c->front_bytes) : 0; }
 extern "C" const char* bscgpu_last_error(const bscgpu_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 // ---- profiling --------------------------------------------------------------------------------
@@ -318,6 +333,7 @@ extern "C" int bscgpu_option_set(bscgpu_ctx* c, int key, int value)
     if (!c) return BSC_BAD_PARAMETER;
     if (key == BSCGPU_OPT_RS_ONESWEEP && value >= 0 && value <= 3 && (value == 0 || c->os_available)) { const int old = c->os_mode; c->os_mode = value; return old; }
     if (key == BSCGPU_OPT_DC_PACKED_STREAM && (value == 0 || value == 1)) { const int old = c->dc_p13; c->dc_p13 = value; return old; }
+    if (key == BSCGPU_OPT_BATCH_FRONT && (value == 0 || value == 1)) { const int old = c->batch_front; c->batch_front = value; return old; }
     return BSC_BAD_PARAMETER;
 }
 extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
@@ -330,6 +346,9 @@ extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
     if (key == BSCGPU_CNT_DC_LAST_FAIL) return c->dc_last_fail;
     if (key == BSCGPU_CNT_DC_AVG_UNDECIDED) return c->dc_avg_und;
     if (key == BSCGPU_CNT_DC_HIST_EXTENDED) return c->dc_hist_ext;
+    if (key == BSCGPU_OPT_BATCH_FRONT) return c->batch_front;
+    if (key == BSCGPU_CNT_BATCH_FRONT_PASSES) return c->cnt_front_passes;
+    if (key == BSCGPU_CNT_BATCH_L_PASSES) return c->cnt_l_passes;
     return BSC_BAD_PARAMETER;
 }
 extern "C" int bscgpu_last_stage_ms(bscgpu_ctx* c, double* out6)

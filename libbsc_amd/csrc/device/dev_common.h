@@ -110,6 +110,13 @@ struct bscgpu_ctx {
     u32* batch_tab = nullptr;     // batched BWT / ST pass: block table + per-block results (bwt.hip BwtBatch, st.hip st_batch_device), allocated on first use
     size_t batch_bytes = 0;       // HBM of batch_tab (bscgpu_arena_bytes counts it once allocated)
     u8*  batch_host[2] = {nullptr, nullptr};   // pinned: a batched pass's text going up and its L coming back (two: coding overlaps the next pass)
+    // the QLFC front end of a whole pass (qlfc_front.hip: qlfc_front_batch), allocated on first use
+    u32* front_tab = nullptr;     // sub-block table of the pass (offsets, block starts, first runs), split-flag table, first run of every symbol per sub-block
+    size_t front_bytes = 0;       // HBM of front_tab (bscgpu_arena_bytes counts it once allocated)
+    u8*  front_host[2] = {nullptr, nullptr};   // pinned: a pass's run arrays coming back (sym, rank, start for max_n runs + the first-run table); two: coding overlaps the next pass
+    size_t front_host_bytes = 0;
+    int  batch_front = 1;         // BSCGPU_OPT_BATCH_FRONT (default: DESIGN §2b, "The QLFC front end of a pass")
+    int  cnt_front_passes = 0, cnt_l_passes = 0;   // BSCGPU_CNT_BATCH_FRONT_PASSES / _L_PASSES
     u64* wc_sink = nullptr;  // [512 * 1024] scratch of the digit passes: phase stamps under RS_PHASE_TIMING (rs_scatter, the single-read passes)
     // single-read digit passes (radix_onesweep.hip), allocated on first use
     int  num_cus = 256;           // hipDeviceAttributeMultiprocessorCount of the context's device
@@ -218,6 +225,16 @@ int qlfc_front_split(bscgpu_ctx* c, const u8* dL, u32 n, int nblocks, int* start
 int qlfc_front_runs(bscgpu_ctx* c, const u8* dL, u32 n, int nblocks, const int* start, u32* m_out, u32* run_first, u32* first_run_host,
                     HostSlot& slot, bool copy_runs = true);
 int qlfc_front_copy_runs(bscgpu_ctx* c, u32 m, HostSlot& slot);
+// The front end of a whole pass: L of `count` blocks back to back at dL (16-byte aligned; sum <= max_n, every block
+// below 1 MiB) -> the layout of include/bscgpu.h, without nsym / first_seen: first_run_host[256 s + c] = first run of symbol c in
+// sub-block s (0xffffffff: none), which qlfc_front_first_seen turns into a sub-block's alphabet.  scratch_host: front_scratch_bytes()
+// bytes, the split-flag words land there and then the first-run table (first_run_host may point into it).  Synchronous.
+constexpr int FRONT_MAX_SUB = 2 * BATCH_MAX_BLOCKS;
+size_t front_scratch_bytes(int64_t max_n);
+int  qlfc_front_batch(bscgpu_ctx* c, const u8* dL, const int* sizes, int count, bscgpu_front_layout* out, void* scratch_host);
+void qlfc_front_first_seen(const u32* first_run /*[256]*/, u8* first_seen /*[256]*/, int* nsym);
+void qlfc_pick_cuts(const u64* w, u32 nwords, u32 n, int nblocks, int* start, int* size);   // coder.cpp:70-109 from the sampled flag words
+int  ctx_ensure_front_host(bscgpu_ctx* c);        // both pinned run buffers of the batch front end; < 0: not to be had (the pass takes the L route)
 int ctx_ensure_slots(bscgpu_ctx* c, int count);
 int ctx_ensure_pstream_slot(bscgpu_ctx* c, HostSlot& slot, size_t entries);     // pinned landing zone for a block's p stream
 int ctx_ensure_run_slot(bscgpu_ctx* c, HostSlot& slot);                           // pinned landing zone for a block's run arrays

@@ -33,6 +33,26 @@ __global__ __launch_bounds__(WG) void qf_split_flags_kernel(const u8* __restrict
     if ((threadIdx.x & 63) == 0 && (q >> 6) < ((nq + 63) >> 6)) words[q >> 6] = b;
 }
 
+// (the block-table front end's half of qf_heads16 below) 16-bit mask of the positions i0 .. i0 + 15 whose byte differs from the one
+// before it (position 0 included); the caller adds the table's forced heads and clips the mask to n
+__device__ __forceinline__ u32 qf_heads16_raw(const u8* __restrict__ L, u32 i0, u32 n, uint4& bytes)
+{
+    bytes = make_uint4(0, 0, 0, 0);
+    if (i0 + 16 <= n) bytes = *reinterpret_cast<const uint4*>(L + i0);
+    else { u8 tmp[16]; for (int p = 0; p < 16; ++p) tmp[p] = (i0 + p < n) ? L[i0 + p] : 0; bytes = *reinterpret_cast<uint4*>(tmp); }
+    const u32 prev = (i0 > 0) ? L[i0 - 1] : 0x100u;
+    const u32 w[4] = {bytes.x, bytes.y, bytes.z, bytes.w};
+    u32 mask = 0, last = prev;
+#pragma unroll
+    for (int p = 0; p < 16; ++p) {
+        const u32 c = (w[p >> 2] >> (8 * (p & 3))) & 0xffu;
+        if (c != last) mask |= 1u << p;
+        last = c;
+    }
+    if (i0 == 0) mask |= 1u;
+    return mask;
+}
+
 __device__ __forceinline__ u32 qf_heads16(const u8* __restrict__ L, u32 i0, u32 n, const QfSplit& sp, uint4& bytes)
 {
     // returns a 16-bit mask: bit p set iff position i0+p starts a run (and i0+p < n)
@@ -229,9 +249,36 @@ template <> struct QfSet<false> {
 #endif
 constexpr u32 QF_SHORT = QF_SHORT_N;
 
+// Where a run's sub-block ends, for the two shapes the bounds come in.  QfRuns: one block's at most eight sub-blocks, by value.
+// QfRunTab: a pass's table in HBM (first[s] = first run of sub-block s, strictly increasing) — the workgroup finds the sub-blocks of its
+// first and last run once (uniform addresses: scalar loads), a lane searches only between those two, and only when they differ.
+struct QfRunTab { const u32* first; u32 nsub; };
+template <class RB> struct QfBounds;
+template <> struct QfBounds<QfRuns> {
+    const QfRuns& rb; u32 m;
+    __device__ __forceinline__ QfBounds(const QfRuns& r, u32 /*first run*/, u32 /*last run*/, u32 m_) : rb(r), m(m_) {}
+    __device__ __forceinline__ u32 end(u32 j) const {
+        u32 re = m;
+#pragma unroll
+        for (int b = 8; b >= 1; --b) if ((u32)b <= rb.nblocks && j < rb.first[b]) re = rb.first[b];
+        return re;
+    }
+};
+template <> struct QfBounds<QfRunTab> {
+    const u32* __restrict__ first; u32 nsub, m, lo, hi;
+    __device__ __forceinline__ QfBounds(const QfRunTab& r, u32 j_first, u32 j_last, u32 m_) : first(r.first), nsub(r.nsub), m(m_) {
+        lo = batch_block_of(first, 0u, nsub, j_first);
+        hi = batch_block_of(first, lo, nsub, j_last);
+    }
+    __device__ __forceinline__ u32 end(u32 j) const {
+        const u32 s = (lo == hi) ? lo : batch_block_of(first, lo, hi + 1u, j);
+        return (s + 1u < nsub) ? first[s + 1u] : m;
+    }
+};
+
 // NARROW (<= 32 distinct symbols, any lower-case text): the lifted tables hold 32-bit sets.
-template <bool DENSE, bool NARROW>
-__global__ __launch_bounds__(WG) void qf_rank_kernel(const u8* __restrict__ sym, u32 m, QfRuns rb, const u8* __restrict__ lut,
+template <bool DENSE, bool NARROW, class RB>
+__global__ __launch_bounds__(WG) void qf_rank_kernel(const u8* __restrict__ sym, u32 m, RB rb, const u8* __restrict__ lut,
                                                      const u64* __restrict__ masks, const u64* __restrict__ super,
                                                      u8* __restrict__ rank)
 {
@@ -244,13 +291,9 @@ __global__ __launch_bounds__(WG) void qf_rank_kernel(const u8* __restrict__ sym,
     __shared__ u16 qi[WG];
     __shared__ u64 qset[WG * W];
     const u32 base = blockIdx.x * WG, t = threadIdx.x;
-    auto sub_end = [&](u32 j) {
-        u32 re = m;
-#pragma unroll
-        for (int b = 8; b >= 1; --b) if ((u32)b <= rb.nblocks && j < rb.first[b]) re = rb.first[b];
-        return re;
-    };
     const u32 tile_end = (base + WG < m) ? base + WG : m;
+    const QfBounds<RB> bounds(rb, base, tile_end - 1u, m);
+    auto sub_end = [&](u32 j) { return bounds.end(j); };
     const u32 re0 = sub_end(base);
     const u32 region_end = (base + R < re0) ? base + R : re0;             // the halo stops at the sub-block's end
     if (DENSE) slut[t] = lut[t];
@@ -394,7 +437,12 @@ int qlfc_front_split(bscgpu_ctx* c, const u8* dL, u32 n, int nblocks, int* start
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(c->hsplit, dwords, (size_t)nwords * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
-    const u64* w = c->hsplit;
+    qlfc_pick_cuts(c->hsplit, nwords, n, nblocks, start, size);
+    return BSC_NO_ERROR;
+}
+
+void qlfc_pick_cuts(const u64* w, u32 nwords, u32 n, int nblocks, int* start, int* size)
+{
     u64 changes = 0;
     for (u32 k = 0; k < nwords; ++k) changes += (u64)__builtin_popcountll(w[k]);
     if (changes > (u64)nblocks) {
@@ -420,7 +468,6 @@ int qlfc_front_split(bscgpu_ctx* c, const u8* dL, u32 n, int nblocks, int* start
         const int each = (int)n / nblocks;
         for (int p = 0; p < nblocks; ++p) { start[p] = each * p; size[p] = (p != nblocks - 1) ? each : (int)n - each * (nblocks - 1); }
     }
-    return BSC_NO_ERROR;
 }
 
 // Runs + ranks of all sub-blocks of dL.  Results in pinned host memory: c->hsym / c->hrank / c->hstart (m entries),
@@ -500,12 +547,309 @@ int qlfc_front_runs(bscgpu_ctx* c, const u8* dL, u32 n, int nblocks, const int* 
     }
     prof_end(c);
     prof_begin(c, BSCGPU_K_GATHER, (u64)m * 2, m);
-    if (dense && K <= 32) hipLaunchKernelGGL((qf_rank_kernel<true, true>), dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, dsym, m, rb, dlut, dmask, dsuper, drank);
-    else if (dense)       hipLaunchKernelGGL((qf_rank_kernel<true, false>), dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, dsym, m, rb, dlut, dmask, dsuper, drank);
-    else                  hipLaunchKernelGGL((qf_rank_kernel<false, false>), dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, dsym, m, rb, dlut, dmask, dsuper, drank);
+    if (dense && K <= 32) hipLaunchKernelGGL((qf_rank_kernel<true, true, QfRuns>), dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, dsym, m, rb, dlut, dmask, dsuper, drank);
+    else if (dense)       hipLaunchKernelGGL((qf_rank_kernel<true, false, QfRuns>), dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, dsym, m, rb, dlut, dmask, dsuper, drank);
+    else                  hipLaunchKernelGGL((qf_rank_kernel<false, false, QfRuns>), dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, dsym, m, rb, dlut, dmask, dsuper, drank);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     (void)dstart;
     if (copy_runs) return qlfc_front_copy_runs(c, m, slot);
     return BSC_NO_ERROR;           // the caller feeds the device coder from the arrays in HBM (and may still ask for the copy)
+}
+
+// -------------------------------------------------------------------------------------------------
+// The front end of a whole PASS: L of up to 4096 blocks back to back, up to 8192 sub-blocks.  The boundaries that the
+// kernels above take as by-value structs of eight entries are a table in HBM here:
+//   sub_off[s]   first byte of sub-block s in the pass (strictly increasing: empty blocks have no sub-block), sub_off[nsub] = N
+//   sub_base[s]  first byte of the BLOCK that holds sub-block s (run starts are relative to it, as RunView expects)
+//   sub_run[s]   first run of sub-block s — written by the apply kernel (the forced head at sub_off[s]), read by the rank kernel
+//   first_run[s][256]  first run of every symbol per sub-block
+// Table lookup: the sub-blocks of a tile's first and last byte come from two binary searches on workgroup-uniform values (scalar
+// loads, once per tile); a lane searches only in a tile that holds a boundary, and only between those two sub-blocks.
+// -------------------------------------------------------------------------------------------------
+struct QfbTab { const u32* sub_off; const u32* sub_base; u32 nsub; };
+
+// one grid row per block with two sub-blocks; ftab[3 y ..] = {first byte of the block in the pass, its length, its first flag word}
+__global__ __launch_bounds__(WG) void qfb_split_flags_kernel(const u8* __restrict__ L, const u32* __restrict__ ftab, u64* __restrict__ words)
+{
+    const u32 at = ftab[3u * blockIdx.y], n = ftab[3u * blockIdx.y + 1u], wb = ftab[3u * blockIdx.y + 2u];
+    const u32 nq = (n - 1u + 31u) / 32u;                      // (n >= 256 KiB)
+    if (blockIdx.x * WG >= nq) return;                        // whole workgroups: the ballot below needs whole wavefronts
+    const u32 q = blockIdx.x * WG + threadIdx.x;
+    bool f = false;
+    if (q < nq) { const u32 i = at + 1u + 32u * q; f = L[i] != L[i - 1u]; }      // sampled relative to the block's own start
+    const u64 b = __ballot(f);
+    if ((threadIdx.x & 63) == 0 && (q >> 6) < ((nq + 63u) >> 6)) words[wb + (q >> 6)] = b;
+}
+
+struct QfbTile { u32 lo, hi; bool cut; };       // sub-blocks of the tile's first and last byte; cut: a sub-block starts inside the tile
+__device__ __forceinline__ QfbTile qfb_tile(const QfbTab& tb, u32 tile, u32 n)
+{
+    const u32 t0 = tile * QF_TILE;
+    const u32 t1 = (t0 + QF_TILE < n ? t0 + QF_TILE : n) - 1u;
+    QfbTile r;
+    r.lo = batch_block_of(tb.sub_off, 0u, tb.nsub, t0);
+    r.hi = batch_block_of(tb.sub_off, r.lo, tb.nsub, t1);
+    r.cut = r.hi != r.lo || tb.sub_off[r.lo] == t0;
+    return r;
+}
+// the head mask of bytes i0 .. i0 + 15 with the table's forced heads; s = sub-block of byte i0
+__device__ __forceinline__ u32 qfb_heads16(const u8* __restrict__ L, u32 i0, u32 n, const QfbTab& tb, const QfbTile& tl, uint4& bytes, u32& s)
+{
+    u32 mask = qf_heads16_raw(L, i0, n, bytes);
+    s = tl.lo;
+    if (tl.cut) {
+        s = batch_block_of(tb.sub_off, tl.lo, tl.hi + 1u, i0);
+        if (tb.sub_off[s] == i0) mask |= 1u;
+        for (u32 t = s + 1u; t <= tl.hi; ++t) {               // (sub-blocks are not empty: at most fifteen steps)
+            const u32 o = tb.sub_off[t];
+            if (o >= i0 + 16u) break;
+            mask |= 1u << (o - i0);
+        }
+    }
+    if (i0 + 16 > n) mask &= (n > i0) ? ((1u << (n - i0)) - 1u) : 0u;
+    return mask;
+}
+
+__global__ __launch_bounds__(WG) void qfb_reduce_kernel(const u8* __restrict__ L, u32 n, QfbTab tb, u32 chunk_tiles, u32 num_tiles,
+                                                        u32* __restrict__ segsum)
+{
+    __shared__ u32 scr[8];
+    const u32 tile0 = blockIdx.x * chunk_tiles;
+    u32 tile1 = tile0 + chunk_tiles; if (tile1 > num_tiles) tile1 = num_tiles;
+    u32 cnt = 0;
+    for (u32 tile = tile0; tile < tile1; ++tile) {
+        if (tile * QF_TILE >= n) break;
+        const QfbTile tl = qfb_tile(tb, tile, n);
+        const u32 i0 = tile * QF_TILE + threadIdx.x * QF_BYTES;
+        if (i0 >= n) continue;
+        uint4 bytes; u32 s;
+        cnt += __popc(qfb_heads16(L, i0, n, tb, tl, bytes, s));
+    }
+    u32 tot;
+    block_excl_sum(cnt, scr, &tot);
+    if (threadIdx.x == 0) { segsum[blockIdx.x] = tot; segsum[MAX_CHUNKS + blockIdx.x] = 0; }
+}
+
+__global__ __launch_bounds__(WG) void qfb_apply_kernel(const u8* __restrict__ L, u32 n, QfbTab tb, u32 chunk_tiles, u32 num_tiles,
+                                                       const u32* __restrict__ segoff, u8* __restrict__ sym, u32* __restrict__ start,
+                                                       u32* __restrict__ first_run /*[nsub][256]*/, u32* __restrict__ sub_run)
+{
+    __shared__ u32 scr[8];
+    // First runs: while the tiles stay inside one sub-block the minima collect in LDS (one global atomicMin per symbol when the
+    // sub-block changes or the chunk ends); the runs of a tile that holds a boundary go to the table directly.
+    __shared__ u32 fmin[256];
+    __shared__ u32 sstart[QF_TILE];
+    __shared__ u8  ssym[QF_TILE];
+    fmin[threadIdx.x] = 0xffffffffu;
+    u32 fsub = 0xffffffffu;                         // the sub-block fmin belongs to (workgroup-uniform)
+    const u32 tile0 = blockIdx.x * chunk_tiles;
+    u32 tile1 = tile0 + chunk_tiles; if (tile1 > num_tiles) tile1 = num_tiles;
+    u32 off = segoff[blockIdx.x];
+    __syncthreads();
+    for (u32 tile = tile0; tile < tile1; ++tile) {
+        if (tile * QF_TILE >= n) break;
+        const QfbTile tl = qfb_tile(tb, tile, n);
+        const bool one = tl.hi == tl.lo;
+        if (fsub != 0xffffffffu && (!one || fsub != tl.lo)) {
+            const u32 v = fmin[threadIdx.x];
+            if (v != 0xffffffffu) { atomicMin(first_run + (size_t)fsub * 256u + threadIdx.x, v); fmin[threadIdx.x] = 0xffffffffu; }
+            fsub = 0xffffffffu;
+            __syncthreads();
+        }
+        if (one) fsub = tl.lo;
+        const u32 i0 = tile * QF_TILE + threadIdx.x * QF_BYTES;
+        uint4 bytes = make_uint4(0, 0, 0, 0);
+        u32 mask = 0, s = tl.lo;
+        if (i0 < n) mask = qfb_heads16(L, i0, n, tb, tl, bytes, s);
+        u32 tot;
+        u32 lj = block_excl_sum(__popc(mask), scr, &tot);      // run index inside the tile
+        const u32 w[4] = {bytes.x, bytes.y, bytes.z, bytes.w};
+        u32 s_start = tb.sub_off[s], s_next = tb.sub_off[s + 1u], base = tb.sub_base[s];      // (sub_off[nsub] = n: never reached)
+        while (mask) {
+            const u32 p = __ffs(mask) - 1; mask &= mask - 1;
+            const u32 c = (w[p >> 2] >> (8 * (p & 3))) & 0xffu;
+            const u32 pos = i0 + p;
+            while (pos >= s_next) { ++s; s_start = s_next; s_next = tb.sub_off[s + 1u]; base = tb.sub_base[s]; }
+            ssym[lj] = (u8)c;
+            sstart[lj] = pos - base;
+            if (pos == s_start) sub_run[s] = off + lj;
+            if (one) atomicMin(&fmin[c], off + lj);
+            else atomicMin(first_run + (size_t)s * 256u + c, off + lj);
+            ++lj;
+        }
+        __syncthreads();
+        for (u32 i = threadIdx.x; i < tot; i += WG) { sym[off + i] = ssym[i]; start[off + i] = sstart[i]; }
+        off += tot;
+        __syncthreads();
+    }
+    if (fsub != 0xffffffffu) {
+        const u32 v = fmin[threadIdx.x];
+        if (v != 0xffffffffu) atomicMin(first_run + (size_t)fsub * 256u + threadIdx.x, v);
+    }
+}
+
+// front_tab words: sub_off [nsub + 1] with sub_base [nsub] right behind it (one copy up; 2 FRONT_MAX_SUB + 1 words reserved),
+// sub_run [FRONT_MAX_SUB + 1], split-flag table [3 BATCH_MAX_BLOCKS], first_run [FRONT_MAX_SUB][256]
+constexpr size_t FT_OFF = 0, FT_RUN = FT_OFF + 2 * (size_t)FRONT_MAX_SUB + 1, FT_FLAG = FT_RUN + FRONT_MAX_SUB + 1,
+                 FT_FIRST = (FT_FLAG + 3 * (size_t)BATCH_MAX_BLOCKS + 63) / 64 * 64, FT_WORDS = FT_FIRST + (size_t)FRONT_MAX_SUB * 256;
+
+size_t front_scratch_bytes(int64_t max_n)
+{
+    // the larger of: the flag words of every block (n_b / 256 + 8 bytes each), the first-run table and sub_run
+    const size_t flags = (size_t)max_n / 256 + 8 * (size_t)BATCH_MAX_BLOCKS + 64, table = (size_t)FRONT_MAX_SUB * 1024 + 4 * (size_t)(FRONT_MAX_SUB + 1);
+    return (flags > table ? flags : table) + 4096;
+}
+
+void qlfc_front_first_seen(const u32* first_run, u8* first_seen, int* nsym)
+{
+    // alphabet in order of first appearance = symbols sorted by the index of their first run (as block.cpp: host_prepare)
+    u64 order[256]; int k = 0;
+    for (u32 s = 0; s < 256; ++s) if (first_run[s] != 0xffffffffu) order[k++] = ((u64)first_run[s] << 8) | s;
+    for (int i = 1; i < k; ++i) { const u64 v = order[i]; int j = i; while (j > 0 && order[j - 1] > v) { order[j] = order[j - 1]; --j; } order[j] = v; }
+    for (int i = 0; i < k; ++i) first_seen[i] = (u8)(order[i] & 0xffu);
+    *nsym = k;
+}
+
+int qlfc_front_batch(bscgpu_ctx* c, const u8* dL, const int* sizes, int count, bscgpu_front_layout* out, void* scratch_host)
+{
+    if (count < 0 || count > BATCH_MAX_BLOCKS || ((uintptr_t)dL & 15u)) return BSC_BAD_PARAMETER;
+    u64 total = 0;
+    int nbig = 0;
+    for (int b = 0; b < count; ++b) {
+        if (sizes[b] < 0 || sizes[b] >= BSCGPU_BATCH_MAX_N) return BSC_BAD_PARAMETER;
+        total += (u64)sizes[b]; nbig += sizes[b] >= 256 * 1024;
+    }
+    if (total > (u64)c->max_n) return BSC_BAD_PARAMETER;
+    out->count = count; out->sizes = sizes; out->nsub = 0; out->m = 0;
+    for (int b = 0; b <= count; ++b) out->blk_sub[b] = 0;
+    out->sub_run[0] = 0;
+    if (total == 0) return BSC_NO_ERROR;
+    const u32 n = (u32)total;
+    if (!c->front_tab) {
+        if (hipMalloc((void**)&c->front_tab, FT_WORDS * 4) != hipSuccess) {
+            (void)hipGetLastError(); c->front_tab = nullptr;
+            return ctx_fail(c, BSC_GPU_NOT_ENOUGH_MEMORY, "batched front end: sub-block table", hipSuccess);
+        }
+        c->front_bytes = FT_WORDS * 4;
+    }
+    u32* const dtab = c->front_tab;
+    u8*  dsym   = reinterpret_cast<u8*>(c->vA);           // the sort buffers are dead once the pass's L has been emitted
+    u8*  drank  = reinterpret_cast<u8*>(c->vB);
+    u32* dstart = c->SA;
+    u64* dmask  = c->kB;
+    u64* dsuper = reinterpret_cast<u64*>(c->cpos[0]);
+    u64* dwords = c->kA;
+
+    // 1. split flags of the blocks with two sub-blocks, cuts on the host (coder.cpp:70-109); no such block: no launch, no sync
+    std::vector<u32> ftab((size_t)3 * nbig);
+    u32 nwords = 0, maxq = 0;
+    {
+        u64 at = 0; int k = 0;
+        for (int b = 0; b < count; ++b) {
+            if (sizes[b] >= 256 * 1024) {
+                const u32 nq = ((u32)sizes[b] - 1 + 31) / 32;
+                ftab[3 * k] = (u32)at; ftab[3 * k + 1] = (u32)sizes[b]; ftab[3 * k + 2] = nwords; ++k;
+                nwords += (nq + 63) / 64; if (nq > maxq) maxq = nq;
+            }
+            at += (u64)sizes[b];
+        }
+    }
+    const u64* hwords = reinterpret_cast<const u64*>(scratch_host);
+    if (nbig > 0) {
+        HIP_TRY(c, hipMemcpyAsync(dtab + FT_FLAG, ftab.data(), ftab.size() * 4, hipMemcpyHostToDevice, c->stream));
+        prof_begin(c, BSCGPU_K_MISC, (u64)nwords * 128, 0);
+        hipLaunchKernelGGL(qfb_split_flags_kernel, dim3((maxq + WG - 1) / WG, (u32)nbig), dim3(WG), 0, c->stream, dL, dtab + FT_FLAG, dwords);
+        prof_end(c);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(scratch_host, dwords, (size_t)nwords * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, ctx_sync(c));
+    }
+    // 2. the sub-block table
+    std::vector<u32> tab;
+    tab.reserve((size_t)4 * count + 2);
+    std::vector<u32> sbase;
+    int nsub = 0;
+    {
+        u64 at = 0; int k = 0;
+        for (int b = 0; b < count; ++b) {
+            out->blk_sub[b] = nsub;
+            const int nb_ = sizes[b] == 0 ? 0 : (sizes[b] >= 256 * 1024 ? 2 : 1);
+            if (nb_ == 1) { out->sub_start[nsub] = 0; out->sub_size[nsub] = sizes[b]; }
+            if (nb_ == 2) {
+                const u32 nq = ((u32)sizes[b] - 1 + 31) / 32;
+                qlfc_pick_cuts(hwords + ftab[3 * k + 2], (nq + 63) / 64, (u32)sizes[b], 2, out->sub_start + nsub, out->sub_size + nsub);
+                ++k;
+            }
+            for (int q = 0; q < nb_; ++q) { tab.push_back((u32)at + (u32)out->sub_start[nsub + q]); sbase.push_back((u32)at); }
+            nsub += nb_;
+            at += (u64)sizes[b];
+        }
+        out->blk_sub[count] = nsub;
+    }
+    out->nsub = nsub;
+    tab.push_back(n);
+    tab.insert(tab.end(), sbase.begin(), sbase.end());
+    u32* const doff = dtab + FT_OFF;
+    u32* const dbase = dtab + FT_OFF + nsub + 1;              // (behind the offsets: one copy for both)
+    u32* const drun = dtab + FT_RUN;
+    u32* const dfirst = dtab + FT_FIRST;
+    if (2 * (size_t)nsub + 1 > FT_RUN - FT_OFF) return BSC_BAD_PARAMETER;      // (count <= BATCH_MAX_BLOCKS, two sub-blocks each at most: cannot happen)
+    HIP_TRY(c, hipMemcpyAsync(doff, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(dfirst, 0xff, (size_t)nsub * 1024, c->stream));
+    QfbTab tb; tb.sub_off = doff; tb.sub_base = dbase; tb.nsub = (u32)nsub;
+
+    // 3. run heads, compaction, first runs
+    const Chunking ch = make_chunking(n, QF_TILE);
+    prof_begin(c, BSCGPU_K_SEG, n, 0);
+    hipLaunchKernelGGL(qfb_reduce_kernel, dim3(ch.num_chunks), dim3(WG), 0, c->stream, dL, n, tb, ch.chunk_tiles, ch.num_tiles, c->segsum);
+    prof_end(c);
+    launch_seg_scan(c, ch.num_chunks);
+    prof_begin(c, BSCGPU_K_SEG, n, 0);
+    hipLaunchKernelGGL(qfb_apply_kernel, dim3(ch.num_chunks), dim3(WG), 0, c->stream, dL, n, tb, ch.chunk_tiles, ch.num_tiles,
+                       c->segoff, dsym, dstart, dfirst, drun);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    u32* const first_run_host = reinterpret_cast<u32*>(scratch_host);
+    HIP_TRY(c, hipMemcpyAsync(c->hscal, c->dscal, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(first_run_host, dfirst, (size_t)nsub * 1024, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out->sub_run, drun, (size_t)nsub * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    const u32 m = c->hscal[0];
+    if (m == 0 || m > n) return ctx_fail(c, BSC_GPU_ERROR, "batched front end: run count", hipSuccess);
+    out->m = m; out->sub_run[nsub] = m;
+
+    // 4. symbol sets from the pass's union alphabet, ranks
+    u8* hlut = reinterpret_cast<u8*>(c->hscal + 640);
+    u8* dlut = reinterpret_cast<u8*>(c->dscal + 640);
+    bool present[256] = {};
+    for (size_t i = 0; i < (size_t)nsub * 256; ++i) if (first_run_host[i] != 0xffffffffu) present[i & 255u] = true;
+    u32 K = 0;
+    for (int s = 0; s < 256; ++s) { hlut[s] = (u8)(present[s] ? (K < 255 ? K : 255) : 0); K += present[s]; }
+    const bool dense = K <= 64;
+    if (dense) HIP_TRY(c, hipMemcpyAsync(dlut, hlut, 256, hipMemcpyHostToDevice, c->stream));
+    const u32 ntiles = (m + 255) / 256, nsuper = (ntiles + 255) / 256;
+    prof_begin(c, BSCGPU_K_MISC, m, 0);
+    if (dense) {
+        hipLaunchKernelGGL(qf_tile_masks_kernel<true>, dim3((ntiles + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, dsym, m, dlut, dmask);
+        hipLaunchKernelGGL(qf_super_masks_kernel<true>, dim3(nsuper), dim3(WG), 0, c->stream, dmask, ntiles, dsuper);
+    } else {
+        hipLaunchKernelGGL(qf_tile_masks_kernel<false>, dim3((ntiles + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, dsym, m, dlut, dmask);
+        hipLaunchKernelGGL(qf_super_masks_kernel<false>, dim3(nsuper), dim3(WG), 0, c->stream, dmask, ntiles, dsuper);
+    }
+    prof_end(c);
+    QfRunTab rt; rt.first = drun; rt.nsub = (u32)nsub;
+    prof_begin(c, BSCGPU_K_GATHER, (u64)m * 2, m);
+    if (dense && K <= 32) hipLaunchKernelGGL((qf_rank_kernel<true, true, QfRunTab>), dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, dsym, m, rt, dlut, dmask, dsuper, drank);
+    else if (dense)       hipLaunchKernelGGL((qf_rank_kernel<true, false, QfRunTab>), dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, dsym, m, rt, dlut, dmask, dsuper, drank);
+    else                  hipLaunchKernelGGL((qf_rank_kernel<false, false, QfRunTab>), dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, dsym, m, rt, dlut, dmask, dsuper, drank);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    // 5. the run arrays
+    HIP_TRY(c, hipMemcpyAsync(out->sym, dsym, m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out->rank, drank, m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out->start, dstart, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    prof_collect(c);
+    return BSC_NO_ERROR;
 }

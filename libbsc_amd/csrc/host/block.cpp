@@ -1566,12 +1566,14 @@ static int store_from_device(bscgpu_ctx* c, const unsigned char* dIn, unsigned c
 }
 
 // the host tail of bsc_compress (libbsc.cpp:296-336) for one block of a sorted pass; input: host bytes, or dIn in HBM
+// (lay != nullptr: the block is entry li of a pass's front-end layout and is coded from its run arrays; else from its L at Lb)
 static int code_sorted_block(bscgpu_ctx* c, const unsigned char* input, const unsigned char* dIn, unsigned char* output, int n,
-                             const BatchBlock& B, const unsigned char* Lb, int coder, int features)
+                             const BatchBlock& B, const unsigned char* Lb, int coder, int features,
+                             const bscgpu_front_layout* lay = nullptr, int li = 0)
 {
     unsigned char* buffer = (unsigned char*)bsc_malloc((size_t)B.lz + 4096);
     if (!buffer) return LIBBSC_NOT_ENOUGH_MEMORY;
-    int result = coder_compress(Lb, buffer, B.lz, coder, features);
+    int result = lay ? bscgpu_front_batch_code(lay, li, buffer, coder, features) : coder_compress(Lb, buffer, B.lz, coder, features);
     if (result >= LIBBSC_NO_ERROR) memcpy(output + LIBBSC_HEADER_SIZE, buffer, (size_t)result);
     bsc_free(buffer);
     const int num = n < 64 * 1024 ? 0 : B.num_indexes;
@@ -1588,6 +1590,126 @@ static int code_sorted_block(bscgpu_ctx* c, const unsigned char* input, const un
     put_i32(output + 20, (int)adler32(output + LIBBSC_HEADER_SIZE, (size_t)result));
     put_i32(output + 24, (int)adler32(output, 24));
     return result + LIBBSC_HEADER_SIZE;
+}
+
+// ---- the QLFC front end of a whole pass: layout on the host, coding of one block from a layout (include/bscgpu.h) ----------------
+static int front_layout_args(const int* sizes, int count, const bscgpu_front_layout* out)
+{
+    if (count < 0 || count > BATCH_MAX_BLOCKS || !out || (count > 0 && !sizes) || !out->blk_sub || !out->sub_run) return LIBBSC_BAD_PARAMETER;
+    int64_t total = 0;
+    for (int b = 0; b < count; ++b) { if (sizes[b] < 0 || sizes[b] >= BSCGPU_BATCH_MAX_N) return LIBBSC_BAD_PARAMETER; total += sizes[b]; }
+    if (count > 0 && (!out->sub_start || !out->sub_size || !out->nsym || !out->first_seen)) return LIBBSC_BAD_PARAMETER;
+    if (total > 0 && (!out->sym || !out->rank || !out->start)) return LIBBSC_BAD_PARAMETER;
+    return LIBBSC_NO_ERROR;
+}
+
+extern "C" BSCGPU_API int bscgpu_front_batch_host(const unsigned char* L, const int* sizes, int count, bscgpu_front_layout* out)
+{
+    const int arc = front_layout_args(sizes, count, out);
+    if (arc < 0) return arc;
+    out->count = count; out->sizes = sizes;
+    int nsub = 0; int64_t m = 0, off = 0;
+    QlfcRuns R;
+    for (int b = 0; b < count; ++b) {
+        out->blk_sub[b] = nsub;
+        const int n = sizes[b];
+        if (n == 0) continue;
+        if (!L) return LIBBSC_BAD_PARAMETER;
+        const int nb = coder_num_blocks(n);
+        int st[8], sz[8];
+        if (nb == 1) { st[0] = 0; sz[0] = n; } else coder_split_blocks(L + off, n, nb, st, sz);
+        for (int q = 0; q < nb; ++q, ++nsub) {
+            qlfc_runs(L + off + st[q], sz[q], R);
+            const RunView& V = R.view;
+            out->sub_start[nsub] = st[q]; out->sub_size[nsub] = sz[q]; out->sub_run[nsub] = (uint32_t)m;
+            out->nsym[nsub] = V.nsym;
+            memcpy(out->first_seen + 256 * (size_t)nsub, V.first_seen, (size_t)V.nsym);
+            memcpy(out->sym + m, V.sym, V.count); memcpy(out->rank + m, V.rank, V.count);
+            for (uint32_t j = 0; j < V.count; ++j) out->start[m + j] = V.start[j] + (uint32_t)st[q];
+            m += V.count;
+        }
+        off += n;
+    }
+    out->blk_sub[count] = nsub; out->sub_run[nsub] = (uint32_t)m;
+    out->nsub = nsub; out->m = m;
+    return LIBBSC_NO_ERROR;
+}
+
+static void front_views(const bscgpu_front_layout* Lo, int block, RunView* views)
+{
+    const int s0 = Lo->blk_sub[block], nb = Lo->blk_sub[block + 1] - s0;
+    for (int q = 0; q < nb; ++q) {
+        const int s = s0 + q;
+        RunView& V = views[q];
+        V = RunView();
+        V.sym = Lo->sym + Lo->sub_run[s]; V.rank = Lo->rank + Lo->sub_run[s]; V.start = Lo->start + Lo->sub_run[s];
+        V.count = Lo->sub_run[s + 1] - Lo->sub_run[s];
+        V.end = (uint32_t)(Lo->sub_start[s] + Lo->sub_size[s]);
+        V.nsym = Lo->nsym[s];
+        memcpy(V.first_seen, Lo->first_seen + 256 * (size_t)s, (size_t)V.nsym);
+    }
+}
+
+extern "C" BSCGPU_API int bscgpu_front_batch_code(const bscgpu_front_layout* Lo, int block, unsigned char* out, int coder, int features)
+{
+    if (!Lo || !out || block < 0 || block >= Lo->count) return LIBBSC_BAD_PARAMETER;
+    const int s0 = Lo->blk_sub[block], nb = Lo->blk_sub[block + 1] - s0;
+    if (nb < 1 || nb > 8) return LIBBSC_BAD_PARAMETER;             // (an empty block: what bsc_coder_compress says to n = 0)
+    RunView views[8];
+    front_views(Lo, block, views);
+    struct Fetch : RawFetch {                                       // a sub-block stored raw is rebuilt from its runs
+        const RunView* views; const int* st; const int* sz; int nb;
+        int operator()(int start, int size, uint8_t* dst) override
+        {
+            for (int q = 0; q < nb; ++q) if (st[q] == start && sz[q] == size) { expand_runs(views[q], start, dst); return 0; }
+            return LIBBSC_BAD_PARAMETER;
+        }
+    } fetch;
+    fetch.views = views; fetch.st = Lo->sub_start + s0; fetch.sz = Lo->sub_size + s0; fetch.nb = nb;
+    return coder_compress_views(views, nb, Lo->sub_start + s0, Lo->sub_size + s0, Lo->sizes[block], out, coder, features, fetch);
+}
+
+extern "C" BSCGPU_API int bscgpu_qlfc_front_batch_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out)
+{
+    if (!c) return LIBBSC_BAD_PARAMETER;
+    const int arc = front_layout_args(sizes, count, out);
+    if (arc < 0) return arc;
+    int64_t total = 0;
+    for (int b = 0; b < count; ++b) total += sizes[b];
+    if (total > c->max_n || (total > 0 && !dL)) return LIBBSC_BAD_PARAMETER;
+    if (hipSetDevice(c->device) != hipSuccess) return LIBBSC_GPU_ERROR;
+    // the kernels read 16 bytes per lane: the pass goes through the context's own (aligned) L buffer, where the sorters leave it
+    if (total > 0 && dL != c->dL && hipMemcpyAsync(c->dL, dL, (size_t)total, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return LIBBSC_GPU_ERROR;
+    std::vector<uint64_t> scratch(front_scratch_bytes(c->max_n) / 8 + 1);
+    const int rc = qlfc_front_batch(c, c->dL, sizes, count, out, scratch.data());
+    if (rc < 0) return rc;
+    const uint32_t* first_run = reinterpret_cast<const uint32_t*>(scratch.data());
+    for (int s = 0; s < out->nsub; ++s) qlfc_front_first_seen(first_run + 256 * (size_t)s, out->first_seen + 256 * (size_t)s, &out->nsym[s]);
+    return LIBBSC_NO_ERROR;
+}
+
+namespace {
+// a pass's layout inside compress_batch_impl: the small arrays here, sym / rank / start and the first-run table in a pinned buffer
+struct PassLayout {
+    bscgpu_front_layout lay;
+    std::vector<int> sizes, blk_sub, sub_start, sub_size, nsym;
+    std::vector<uint32_t> sub_run;
+    std::vector<uint8_t> first_seen;
+    const uint32_t* first_run = nullptr;
+    bool used = false;
+    void bind(const std::vector<int>& psz, uint8_t* pinned, size_t N)
+    {
+        const size_t cnt = psz.size();
+        sizes = psz;
+        blk_sub.assign(cnt + 1, 0); sub_start.assign(2 * cnt, 0); sub_size.assign(2 * cnt, 0); nsym.assign(2 * cnt, 0);
+        sub_run.assign(2 * cnt + 1, 0); first_seen.resize(512 * cnt);
+        lay = bscgpu_front_layout();
+        lay.blk_sub = blk_sub.data(); lay.sub_start = sub_start.data(); lay.sub_size = sub_size.data(); lay.nsym = nsym.data();
+        lay.sub_run = sub_run.data(); lay.first_seen = first_seen.data();
+        lay.sym = pinned; lay.rank = pinned + N; lay.start = reinterpret_cast<uint32_t*>(pinned + 2 * N);
+        first_run = reinterpret_cast<const uint32_t*>(pinned + 6 * N);
+    }
+};
 }
 
 int bschost::coder_threads() { return default_coder_threads(); }
@@ -1616,6 +1738,10 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
                 c->batch_host[k] = nullptr;
                 return ctx_fail(c, LIBBSC_GPU_NOT_ENOUGH_MEMORY, "batched compression: pinned pass buffers", hipSuccess);
             }
+    // the front end of every pass on the GPU (BSCGPU_OPT_BATCH_FRONT): needs the two pinned run buffers; without them today's route
+    const bool front = npass > 0 && c->batch_front != 0 && ctx_ensure_front_host(c) == LIBBSC_NO_ERROR;
+    const size_t frontN = ((size_t)c->max_n + 4096 + 4095) / 4096 * 4096;
+    std::vector<PassLayout> lays(2);
     const int threads = default_coder_threads();
     std::vector<char> single((size_t)count, 0);
     for (int b = 0; b < count; ++b) single[b] = pass_of[b] < 0;
@@ -1652,6 +1778,8 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
         };
         if (mode != (mode & 0xff)) run_bounded(e - b, threads, prep);
         else for (int i = 0; i < e - b; ++i) prep(i);
+        PassLayout& PL = lays[p & 1];      // (free, as hb is)
+        PL.used = false;
         u8* hb = c->batch_host[p & 1];     // free: the coder thread of the pass before last was joined before the previous pass's started
         std::vector<int> psz((size_t)(e - b)), prate((size_t)(e - b));
         std::vector<int64_t> at((size_t)(e - b) + 1, 0);                         // where block b + i's L lies in hb
@@ -1676,7 +1804,17 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
             rc = st ? st_batch_device(c, src, c->dL, psz.data(), e - b, blockSorter, prate.data(), stidx.data(), dev ? adler.data() : nullptr)
                     : bwt_batch_device(c, src, c->dL, psz.data(), e - b, prate.data(), res.data(), dev ? adler.data() : nullptr);
             if (rc < 0) break;
-            if (hipMemcpyAsync(hb, c->dL, (size_t)pos, hipMemcpyDeviceToHost, c->stream) != hipSuccess || ctx_sync(c) != hipSuccess) { rc = LIBBSC_GPU_ERROR; break; }
+            if (front) {                            // the pass's run arrays come down instead of its L
+                // (the front end covers the whole range of the pass: with HBM input that includes members the layout is never read
+                // for — a block left to the single path rides along untransformed; correct, a little wasted work)
+                PL.bind(psz, c->front_host[p & 1], frontN);
+                rc = qlfc_front_batch(c, c->dL, PL.sizes.data(), e - b, &PL.lay, c->front_host[p & 1] + 6 * frontN);
+                if (rc < 0) break;
+                PL.used = true; ++c->cnt_front_passes;
+            } else {
+                if (hipMemcpyAsync(hb, c->dL, (size_t)pos, hipMemcpyDeviceToHost, c->stream) != hipSuccess || ctx_sync(c) != hipSuccess) { rc = LIBBSC_GPU_ERROR; break; }
+                ++c->cnt_l_passes;
+            }
         }
         for (int i = 0; i < e - b; ++i) {
             BatchBlock& B = blocks[i];
@@ -1690,9 +1828,23 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
             for (int t = 0; t < B.num_indexes; ++t) B.indexes[t] = (int)I[t + 1] - 1;
         }
         if (coder_thread.joinable()) coder_thread.join();
-        auto code_pass = [c, &blocks, hb, at, dev, &in_of, &din_of, &out_of, results, sizes, coder, features, threads] {
+        auto code_pass = [c, &blocks, &PL, hb, at, dev, &in_of, &din_of, &out_of, results, sizes, coder, features, threads] {
             run_bounded((int)blocks.size(), threads, [&](int i) {
                 const BatchBlock& B = blocks[i];
+                if (PL.used && (B.store || B.sorted)) {
+                    const bscgpu_front_layout& Y = PL.lay;
+                    for (int s = Y.blk_sub[i]; s < Y.blk_sub[i + 1]; ++s)
+                        qlfc_front_first_seen(PL.first_run + 256 * (size_t)s, Y.first_seen + 256 * (size_t)s, &Y.nsym[s]);
+                    if (B.store) {                  // <= 28 bytes that rode along (L = T): its bytes are its runs
+                        unsigned char tmp[LIBBSC_HEADER_SIZE + 1];
+                        RunView V[8];
+                        front_views(&Y, i, V);
+                        if (sizes[B.b] > 0) expand_runs(V[0], 0, tmp);
+                        results[B.b] = bsc_store(tmp, out_of(B.b), sizes[B.b], features);
+                    } else results[B.b] = code_sorted_block(c, dev ? nullptr : in_of(B.b), dev ? din_of(B.b) : nullptr, out_of(B.b), sizes[B.b],
+                                                            B, nullptr, coder, features, &Y, i);
+                    return;
+                }
                 if (B.store) results[B.b] = bsc_store(hb + at[i], out_of(B.b), sizes[B.b], features);
                 else if (B.sorted) results[B.b] = code_sorted_block(c, dev ? nullptr : in_of(B.b), dev ? din_of(B.b) : nullptr, out_of(B.b), sizes[B.b],
                                                                     B, hb + at[i], coder, features);

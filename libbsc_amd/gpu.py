@@ -234,6 +234,13 @@ class GpuContext:
                                                         sorter, coder, features))
         return self._batch_results(out, sz, results)
 
+    def qlfc_front_batch(self, dL, sizes):
+        """bscgpu_qlfc_front_batch_device: the QLFC front end of a pass whose sorted blocks lie back to back in the uint8 device tensor
+        dL -> FrontBatch (the layout of include/bscgpu.h)"""
+        fb = FrontBatch(sizes)
+        self._check(self.L.bscgpu_qlfc_front_batch_device(self.h, _dptr(dL), N.np_ptr(fb.sizes), fb.count, C.byref(fb.lay)))
+        return fb
+
     # ---- batched decompression (one inverse-BWT pass for many blocks, include/bscgpu.h) -------
     def unbwt_batch(self, dL, sizes, primary, dT=None):
         """inverse BWT of every block of a batch laid out back to back in the uint8 device tensor dL (primary: 1-based indexes) ->
@@ -291,6 +298,7 @@ class GpuContext:
 
     # ---- measurement / test knobs (include/bscgpu.h: BSCGPU_OPT_*, BSCGPU_CNT_*) ---------------------------------
     OPT_RS_ONESWEEP, CNT_OS_RETRIES, OPT_DC_PACKED_STREAM = 1, 2, 4
+    OPT_BATCH_FRONT, CNT_BATCH_FRONT_PASSES, CNT_BATCH_L_PASSES = 9, 10, 11     # the compress-batch passes' route and how many took each
     CNT_DC_REPLAYS, CNT_DC_LAST_FAIL, CNT_DC_AVG_UNDECIDED, CNT_DC_HIST_EXTENDED = 5, 6, 7, 8      # the last device-model block (get only)
     DC_FAIL_AVG, DC_FAIL_HIST, DC_FAIL_CAP, DC_FAIL_REPLAY = 2, 4, 8, 16                          # BSCGPU_DC_FAIL_*
 
@@ -323,6 +331,62 @@ class GpuContext:
         out = (C.c_double * 6)()
         self.L.bscgpu_last_stage_ms(self.h, out)
         return list(out)
+
+
+class _FrontLayout(C.Structure):
+    """bscgpu_front_layout (include/bscgpu.h)"""
+    _fields_ = [("count", C.c_int), ("nsub", C.c_int), ("m", C.c_int64), ("sizes", C.c_void_p), ("blk_sub", C.c_void_p),
+                ("sub_start", C.c_void_p), ("sub_size", C.c_void_p), ("sub_run", C.c_void_p), ("nsym", C.c_void_p),
+                ("first_seen", C.c_void_p), ("sym", C.c_void_p), ("rank", C.c_void_p), ("start", C.c_void_p)]
+
+
+class FrontBatch:
+    """The front end's layout of a pass (bscgpu_front_layout): owns the arrays, exposes them trimmed once a call has filled them.
+    blk_sub[count + 1]; per sub-block sub_start / sub_size / nsym / first_seen[., 256] and sub_run[nsub + 1]; per run sym / rank / start."""
+
+    def __init__(self, sizes):
+        self.sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32))
+        cnt = self.count = int(self.sizes.size)
+        total = int(self.sizes.sum()) if cnt else 0
+        self._a = dict(blk_sub=np.zeros(cnt + 1, np.int32), sub_start=np.zeros(2 * cnt + 1, np.int32), sub_size=np.zeros(2 * cnt + 1, np.int32),
+                       sub_run=np.zeros(2 * cnt + 1, np.uint32), nsym=np.zeros(2 * cnt + 1, np.int32),
+                       first_seen=np.zeros((2 * cnt + 1, 256), np.uint8), sym=np.zeros(total + 1, np.uint8),
+                       rank=np.zeros(total + 1, np.uint8), start=np.zeros(total + 1, np.uint32))
+        self.lay = _FrontLayout()
+        self.lay.sizes = self.sizes.ctypes.data
+        for k, v in self._a.items():
+            setattr(self.lay, k, v.ctypes.data)
+
+    nsub = property(lambda self: int(self.lay.nsub))
+    m = property(lambda self: int(self.lay.m))
+    blk_sub = property(lambda self: self._a["blk_sub"])
+    sub_start = property(lambda self: self._a["sub_start"][:self.nsub])
+    sub_size = property(lambda self: self._a["sub_size"][:self.nsub])
+    sub_run = property(lambda self: self._a["sub_run"][:self.nsub + 1])
+    nsym = property(lambda self: self._a["nsym"][:self.nsub])
+    sym = property(lambda self: self._a["sym"][:self.m])
+    rank = property(lambda self: self._a["rank"][:self.m])
+    start = property(lambda self: self._a["start"][:self.m])
+
+    def first_seen(self, s):
+        return self._a["first_seen"][s, :int(self._a["nsym"][s])]
+
+    def code(self, block, coder=1, features=3):
+        """bscgpu_front_batch_code: what bsc_coder_compress gives for this block's L -> bytes, or its negative code"""
+        out = np.empty(int(self.sizes[block]) + 4096, np.uint8)
+        r = int(N.lib().bscgpu_front_batch_code(C.byref(self.lay), int(block), N.np_ptr(out), int(coder), int(features)))
+        return out[:r].tobytes() if r >= 0 else r
+
+
+def front_batch_host(L, sizes):
+    """bscgpu_front_batch_host: the layout of a pass built on the CPU from L (uint8, the blocks back to back) -> FrontBatch"""
+    a = np.ascontiguousarray(L, dtype=np.uint8)
+    fb = FrontBatch(sizes)
+    assert a.size >= int(fb.sizes.sum())
+    rc = int(N.lib().bscgpu_front_batch_host(N.np_ptr(a) if a.size else None, N.np_ptr(fb.sizes), fb.count, C.byref(fb.lay)))
+    if rc < 0:
+        raise GpuError(rc, "bscgpu_front_batch_host")
+    return fb
 
 
 def batch_plan(sizes, sorter=1, cap=64 << 20):

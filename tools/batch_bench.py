@@ -29,8 +29,18 @@ repetition reported.  --transform-only skips the compression legs.
   ref_cpu16     16 threads calling the compiled reference's bsc_decompress, one block per thread (features = fast mode only)
 every output checked against the original.  --decode --profile-pass: one decompress_batch of W1 only (for rocprofv3).
     python tools/batch_bench.py --decode [--reps 2] [--workloads W1,W2,W3,W4] [--configs e1,e2,e1-lzp,e2-lzp]
+
+--front: the batch legs with BSCGPU_OPT_BATCH_FRONT on and off (the QLFC front end of a pass on the GPU, run arrays down
+instead of L), host and HBM input, and the pipe, repetitions interleaved (on, off, on_device, off_device, pipe, on, ...); every
+repetition's wall time, the medians, CPU-s per MB of the median repetition's neighbours (the mean), a hash check of every output.
+--front-only: per workload the stage alone on one pass's L in HBM — bscgpu_qlfc_front_batch_device, wall and the HIP-event time of
+its kernel classes (SEG, MISC, GATHER) — against a loop of the single-block front end over the same blocks (the front end of
+bscgpu_qlfc_static_pstream, isolated through the same three classes: the device model behind it books to other classes).
+--profile-pass with --front: one compress_batch of the workload with the option on, nothing timed (for rocprofv3).
+    python tools/batch_bench.py --front [--front-only] [--reps 3] [--workloads W1,W2,W3]
 """
 import argparse
+import ctypes as C
 import json
 import os
 import resource
@@ -205,6 +215,123 @@ def st_transform_leg(ctx, name, sizes, blocks, k, reps):
                       "speedup_of_medians": round(float(np.median(tl) / np.median(tb)), 2), "identical": same}), flush=True)
 
 
+def front_main(args):
+    """BSCGPU_OPT_BATCH_FRONT on against off inside one process, interleaved"""
+    import hashlib
+    import torch
+    from libbsc_amd import GpuContext
+    from libbsc_amd import _native as N
+    coder = args.coder
+    ctx = GpuContext(0, max_n=(64 << 20) + 4096)
+    OPT = ctx.OPT_BATCH_FRONT
+    FRONT_CLASSES = ("seg", "misc", "gather")
+    pctx = [GpuContext(0, max_n=(1 << 20) + 4096) for _ in range(0 if (args.front_only or args.profile_pass) else args.contexts)]
+    pipes = [c.pipe(args.depth) for c in pctx]
+
+    def digest(out):
+        h = hashlib.sha256()
+        for b in out:
+            h.update(b if isinstance(b, bytes) else str(b).encode())
+        return h.hexdigest()
+
+    def front_ms(c):
+        st = c.profile_get()
+        return sum(v["ms"] for k, v in st.items() if k in FRONT_CLASSES)
+
+    try:
+        for name in args.workloads.split(","):
+            sizes, blocks = workload(name)
+            mb = sum(sizes) / 1e6
+            flat = torch.from_numpy(np.concatenate(blocks)).cuda()
+            torch.cuda.synchronize()
+            if args.profile_pass:
+                ctx.option_set(OPT, 1)
+                ctx.compress_batch(blocks[:8], 1, coder)
+                out = ctx.compress_batch(blocks, 1, coder)
+                print(json.dumps({"workload": name, "leg": "profile_pass", "blocks": len(out)}), flush=True)
+                continue
+            if args.front_only:
+                # one pass's worth of L (the first blocks that fit a pass), from the batched BWT
+                from libbsc_amd.gpu import batch_plan
+                _, pass_of = batch_plan(sizes, 1, ctx.max_n)
+                cnt = sum(1 for x in pass_of if x == 0)
+                psz = sizes[:cnt]
+                total = sum(psz)
+                dL = torch.empty(total, dtype=torch.uint8, device="cuda")
+                ctx.bwt_batch(flat[:total], psz, aux=False, dL=dL)
+                Lh = dL.cpu().numpy()
+                offs = np.concatenate([[0], np.cumsum(psz)])
+                ctx.qlfc_front_batch(dL, psz)                              # warm-up: tables, first launches
+                ctx.profile(True)
+                tw, tk, tl = [], [], []
+                st, sz, nb, poff = (C.c_int * 8)(), (C.c_int * 8)(), C.c_int(0), (C.c_int64 * 9)()
+                dummy = np.empty(16, np.uint16)
+                f = ctx.L.bscgpu_qlfc_static_pstream
+                f.restype = C.c_int64
+                f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+                d16 = torch.zeros(16, dtype=torch.uint8, device="cuda")
+                declined, other_ms = 0, 0.0
+                for _ in range(args.reps):
+                    ctx.profile_reset()
+                    t0 = time.perf_counter()
+                    fb = ctx.qlfc_front_batch(dL, psz)
+                    tw.append(round((time.perf_counter() - t0) * 1e3, 2))
+                    tk.append(round(front_ms(ctx), 3))
+                    # the flush: a 16-byte Adler-32 syncs the stream and folds every pending event into the classes (a block the device
+                    # model declines returns before its own fold); its own kernel time is measured and taken off
+                    ctx.profile_reset()
+                    ctx.adler32_device(d16, 16)
+                    flush = front_ms(ctx)
+                    ctx.profile_reset()
+                    for b in range(cnt):                                   # (cap 0: the stream itself is not copied out)
+                        rc = f(ctx.h, Lh[offs[b]:].ctypes.data, psz[b], dummy.ctypes.data, 0, C.byref(nb), st, sz, poff, None)
+                        assert rc >= 0 or rc == -4, f"block {b}: bscgpu_qlfc_static_pstream returned {rc}"      # -4: the model declined, AFTER the front end ran
+                        declined += rc == -4
+                    ctx.adler32_device(d16, 16)
+                    st_all = ctx.profile_get()
+                    assert st_all["seg"]["launches"] >= 2 * cnt, "every block's front end must have been timed"
+                    tl.append(round(front_ms(ctx) - flush, 3))
+                    other_ms = sum(v["ms"] for k, v in st_all.items() if k not in FRONT_CLASSES)
+                ctx.profile(False)
+                print(json.dumps({"workload": name, "leg": "front_only", "blocks": cnt, "MB": round(total / 1e6, 2), "runs": fb.m, "sub_blocks": fb.nsub,
+                                  "front_batch_wall_ms": tw, "front_batch_kernel_ms": tk, "single_block_loop_kernel_ms": tl,
+                                  "loop_blocks_declined_by_device_model": declined // max(args.reps, 1), "loop_ms_in_other_classes_last_rep": round(other_ms, 2),
+                                  "kernel_speedup_of_medians": round(float(np.median(tl) / np.median(tk)), 2)}), flush=True)
+                continue
+            dblocks = [torch.from_numpy(b).cuda() for b in blocks]
+            torch.cuda.synchronize()
+            want = digest(run_pipe(pipes, dblocks, sizes, 1, coder, args.depth))        # warm-up + the single-block outputs
+            for v in (1, 0):
+                ctx.option_set(OPT, v)
+                ctx.compress_batch(blocks[:8], 1, coder)
+            legs = {"batch_on": (1, False), "batch_off": (0, False), "batch_device_on": (1, True), "batch_device_off": (0, True), "pipe": None}
+            walls = {k: [] for k in legs}
+            cpus = {k: [] for k in legs}
+            same = {k: True for k in legs}
+            for _ in range(args.reps):
+                for leg, how in legs.items():
+                    if how is None:
+                        out, wall, cpu = timed(lambda: run_pipe(pipes, dblocks, sizes, 1, coder, args.depth))
+                    else:
+                        ctx.option_set(OPT, how[0])
+                        out, wall, cpu = timed((lambda: ctx.compress_batch_device(flat, sizes, 1, coder)) if how[1] else (lambda: ctx.compress_batch(blocks, 1, coder)))
+                    walls[leg].append(wall); cpus[leg].append(cpu)
+                    same[leg] = same[leg] and digest(out) == want
+            for leg in legs:
+                w = np.array(walls[leg])
+                print(json.dumps({"workload": name, "leg": leg, "blocks": len(sizes), "MB": round(mb, 2), "coder": coder,
+                                  "ms": [round(x * 1e3, 1) for x in w], "median_MB_s": round(mb / float(np.median(w)), 1),
+                                  "MB_s_min_max": [round(mb / float(w.max()), 1), round(mb / float(w.min()), 1)],
+                                  "cpu_s_per_MB": round(float(np.mean(cpus[leg])) / mb, 4), "sha256_equals_pipe": bool(same[leg])}), flush=True)
+            del dblocks
+    finally:
+        for p in pipes:
+            p.close()
+        for c in pctx:
+            c.close()
+        ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -217,7 +344,12 @@ def main():
     ap.add_argument("--decode", action="store_true", help="the decode side: decompress_batch against the per-block paths")
     ap.add_argument("--configs", default="e1,e2,e1-lzp,e2-lzp")
     ap.add_argument("--profile-pass", action="store_true", help="with --decode: one decompress_batch per workload and config, nothing timed")
+    ap.add_argument("--front", action="store_true", help="BSCGPU_OPT_BATCH_FRONT on against off, interleaved (BWT, --coder)")
+    ap.add_argument("--front-only", action="store_true", help="with --front: the front-end stage alone against a loop of the single-block front end")
     args = ap.parse_args()
+    if args.front or args.front_only:
+        args.workloads = args.workloads or "W1,W2,W3"
+        return front_main(args)
     if args.decode:
         args.workloads = args.workloads or "W1,W2,W3,W4"
         return decode_main(args)
