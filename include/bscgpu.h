@@ -96,6 +96,49 @@ BSCGPU_API int64_t bscgpu_qlfc_static_pstream(bscgpu_ctx* ctx, const uint8_t* L,
 BSCGPU_API int64_t bscgpu_qlfc_static_pstream_packed(bscgpu_ctx* ctx, const uint8_t* L, int n, uint8_t* out, int64_t cap_bytes, int* nblocks,
                                    int* sub_start /*[8]*/, int* sub_size /*[8]*/, int64_t* poff /*[9]*/, int64_t* pbase /*[9]*/);
 
+/* ---- range coder: many probability streams in one launch -------------------------
+ * The back half of the static / fast coders as a stage of its own: a stream is a prefix (the header word and the alphabet, as plain
+ * entries) followed by a body in one of the three forms the device model writes.  One lane codes one stream; the bytes are those of
+ * the host coders of the same form (rangecoder.h:38-271: 32-bit range, 64-bit low with the carry in bit 32, 16-bit little-endian
+ * units, finish = one conditional and three unconditional shifts).
+ *   prefix entry (u32)   [15:0] multiplier p, [20:16] precision, [24] coded bit: range' = (range >> precision) * p for a 0 bit
+ *   bscgpu_rc_prefix     pure function: the decisions qlfc_encode_static_pstream / _p13 (coder 1) or qlfc_encode_fast_pstream (coder 3)
+ *                        issue before the body — EncodeWord(in_size) at precision 12, p 2048, then the alphabet (csrc/host/qlfc.cpp: encode_alphabet) at
+ *                        precision 12, p 2048 (static) or precision 1, p 1 (fast).  Returns the count (at most BSCGPU_RC_PREFIX_MAX; entries
+ *                        may be NULL to ask for it) or LIBBSC_BAD_PARAMETER (cap too small included).
+ * Stopping rule of a stream, per form (full = bytes written >= out_size - 16, rangecoder.h:127): STATIC16 gives up at a run-start
+ *   mark once full, STATIC13 at any body decision once full, FAST16 at a run-start mark once full — what the host coder of the same
+ *   form does.  On top of that no stream ever stores outside out[out_off, out_off + out_size + 64): a renormalisation (and the
+ *   finish) that finds bytes written + 2 * pending units + 10 > out_size + 64 ends the stream instead.  Either way res = LIBBSC_NOT_COMPRESSIBLE.
+ * res[i] = bytes written, or LIBBSC_NOT_COMPRESSIBLE.  The calls return 0, LIBBSC_BAD_PARAMETER (nothing launched) or a GPU error.
+ * bscgpu_rc_encode_host   the CPU stand-in (no GPU, no context): the same streams through the scalar range encoder of the host coders.
+ * bscgpu_rc_encode_device dBody / dOut device pointers (dOut 2-byte aligned), prefix / streams / res host arrays; streams_per_wave =
+ *                        64, 8 or 1 streams per wavefront (same bytes; 1 keeps a chain wave-uniform).  Synchronous.  A body is read
+ *                        in aligned 16-byte pieces: at most 15 bytes before its first and after its last byte are touched.
+ * bscgpu_rc_encode       the same with host pointers for body (body_bytes of it) and out (out_bytes): copies up and down. */
+#define BSCGPU_RC_STATIC16 0  /* dcm::PS_*: [11:0] p, [12] bit, [13] run start, precision 12 */
+#define BSCGPU_RC_STATIC13 1  /* DcP13: 13 bits per decision {[11:0] p, [12] bit}, eight in 13 bytes */
+#define BSCGPU_RC_FAST16   2  /* dcm::PSF_*: [12:0] p, [13] bit, [14] run start, [15] side: precision 11, else 13 */
+#define BSCGPU_RC_REFILL   128   /* decisions a wavefront stages per stream and refill (a multiple of 8) */
+#define BSCGPU_RC_PREFIX_MAX (32 + 256 * 8)
+typedef struct bscgpu_rc_stream {
+    int64_t  body;      /* first body entry (16-bit forms: entry index; packed: decision index in the packed space, multiple of 8) */
+    uint32_t count;     /* body decisions, may be 0 */
+    uint32_t prefix, nprefix;   /* range in the call's prefix array */
+    uint32_t out_off;   /* even; the stream owns out[out_off .. out_off + out_size + 64) */
+    int32_t  out_size;  /* the reference's outputSize; budget = out_size - 16 (rangecoder.h:127) */
+} bscgpu_rc_stream;
+BSCGPU_API int bscgpu_rc_prefix(const unsigned char* first_seen, int nsym, int in_size, int coder, uint32_t* entries, int cap);
+BSCGPU_API int bscgpu_rc_encode_host(int form, const void* body, const uint32_t* prefix, int nprefix_total,
+                                     const bscgpu_rc_stream* streams, int count, void* out, int* res);
+BSCGPU_API int bscgpu_rc_encode_device(bscgpu_ctx* ctx, int form, const void* dBody, const uint32_t* prefix, int nprefix_total,
+                                       const bscgpu_rc_stream* streams, int count, void* dOut, int* res, int streams_per_wave);
+BSCGPU_API int bscgpu_rc_encode(bscgpu_ctx* ctx, int form, const void* body, int64_t body_bytes, const uint32_t* prefix, int nprefix_total,
+                                const bscgpu_rc_stream* streams, int count, void* out, int64_t out_bytes, int* res, int streams_per_wave);
+/* The argument check of the three calls as a pure function: 0 or LIBBSC_BAD_PARAMETER (a form or stream shape outside the above;
+ * body_bytes / out_bytes < 0: that extent is not checked). */
+BSCGPU_API int bscgpu_rc_check(int form, int nprefix_total, const bscgpu_rc_stream* streams, int count, int64_t body_bytes, int64_t out_bytes);
+
 /* ---- full block compression with the BWT/ST + coder split across GPU and host ------------- */
 /* bsc_compress semantics (libbsc.cpp:213) for input already in HBM: Adler-32 + sort transform on
  * the GPU, QLFC coder on host threads.  output is a HOST buffer of n + 28 bytes. */
@@ -342,7 +385,8 @@ enum {
     BSCGPU_K_DC_PSTREAM    = 11, /* device coder: probability stream */
     BSCGPU_K_RADIX_HISTALL = 12, /* single-read sorts: the one histogram read per sort (all digits at once) */
     BSCGPU_K_RADIX_AUX     = 13, /* keys-only passes that also emit the permutation (device coder's orders, inverse BWT): not the graded kernel */
-    BSCGPU_K_COUNT         = 14
+    BSCGPU_K_RC            = 14, /* range coder: many probability streams in one launch (rangecoder.hip) */
+    BSCGPU_K_COUNT         = 15
 };
 typedef struct bscgpu_kstat {
     double   ms;        /* accumulated HIP-event time */
@@ -386,10 +430,17 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          bsc_coder_compress on the host.  Same output.  Default 1 (measured: DESIGN §2b).
  * BSCGPU_CNT_BATCH_FRONT_PASSES, BSCGPU_CNT_BATCH_L_PASSES  (get only) passes of this context's compress-batch calls that took each
  *                          of the two routes (a pass whose pinned run buffers cannot be had takes the L route).
+ * BSCGPU_OPT_DEVICE_RC     1: a block that took the device model (-e1 16-bit or packed, -e0) has its sub-block streams range-coded by one launch
+ *                          on the context's stream, straight from the device's probability stream (rangecoder.hip); only the compressed
+ *                          bytes come down and the host frames them.  A sub-block that ends LIBBSC_NOT_COMPRESSIBLE sends the block through
+ *                          the host model again, as on the host route.  0 (default): the stream crosses PCIe and host threads code it.  Same
+ *                          output.  Batched passes, -e2 and blocks the model declines are not affected.
+ * BSCGPU_CNT_DEVICE_RC_BLOCKS  (get only) blocks of this context whose streams were coded that way.
  * set returns the previous value or a negative libbsc error code; get the value or a negative error code. */
 enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACKED_STREAM = 4,
        BSCGPU_CNT_DC_REPLAYS = 5, BSCGPU_CNT_DC_LAST_FAIL = 6, BSCGPU_CNT_DC_AVG_UNDECIDED = 7, BSCGPU_CNT_DC_HIST_EXTENDED = 8,
-       BSCGPU_OPT_BATCH_FRONT = 9, BSCGPU_CNT_BATCH_FRONT_PASSES = 10, BSCGPU_CNT_BATCH_L_PASSES = 11 };
+       BSCGPU_OPT_BATCH_FRONT = 9, BSCGPU_CNT_BATCH_FRONT_PASSES = 10, BSCGPU_CNT_BATCH_L_PASSES = 11,
+       BSCGPU_OPT_DEVICE_RC = 12, BSCGPU_CNT_DEVICE_RC_BLOCKS = 13 };
 /* _FAIL_AVG: undecided avg_rank flags; _FAIL_HIST: a run_hist bracket open after 9216 predecessors; _FAIL_CAP: more runs or decisions
  * than the context's arena holds; _FAIL_REPLAY: a chain whose bracket stayed open over more than 64 evaluation chunks. */
 enum { BSCGPU_DC_FAIL_AVG = 2, BSCGPU_DC_FAIL_HIST = 4, BSCGPU_DC_FAIL_CAP = 8, BSCGPU_DC_FAIL_REPLAY = 16 };

@@ -13,7 +13,13 @@ i32p = C.POINTER(C.c_int)
 u32p = C.POINTER(C.c_uint32)
 
 K_NAMES = ["radix_scatter", "radix_hist", "radix_scan", "pack", "seg", "gather", "emit", "misc",
-           "dc_ctx", "dc_part", "dc_eval", "dc_pstream", "radix_hist_all", "radix_aux"]      # order of the BSCGPU_K_* enum (include/bscgpu.h)
+           "dc_ctx", "dc_part", "dc_eval", "dc_pstream", "radix_hist_all", "radix_aux", "rc"]      # order of the BSCGPU_K_* enum (include/bscgpu.h)
+
+
+class RcStream(C.Structure):
+    """bscgpu_rc_stream (include/bscgpu.h): one stream of a range coder launch"""
+    _fields_ = [("body", C.c_int64), ("count", C.c_uint32), ("prefix", C.c_uint32), ("nprefix", C.c_uint32),
+                ("out_off", C.c_uint32), ("out_size", C.c_int32)]
 
 
 class KStat(C.Structure):
@@ -93,6 +99,11 @@ def lib():
     L.bscgpu_decompress_batch_sizes.restype = C.c_int64
     L.bscgpu_decompress_batch.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int64, vp, C.c_int]
     L.bscgpu_decompress_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int64, vp, C.c_int]
+    L.bscgpu_rc_prefix.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int]
+    L.bscgpu_rc_check.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.c_int64, C.c_int64]
+    L.bscgpu_rc_encode_host.argtypes = [C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp]
+    L.bscgpu_rc_encode_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int]
+    L.bscgpu_rc_encode.argtypes = [vp, C.c_int, vp, C.c_int64, vp, C.c_int, vp, C.c_int, vp, C.c_int64, vp, C.c_int]
     if hasattr(L, "bscgpu_compress_device"):
         L.bscgpu_compress_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]
     _lib = L

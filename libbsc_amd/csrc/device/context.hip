@@ -244,6 +244,7 @@ extern "C" void bscgpu_destroy(bscgpu_ctx* c)
     if (c->long_tables) { (void)hipFree(c->long_tables); c->long_tables = nullptr; }
     if (c->batch_tab) { (void)hipFree(c->batch_tab); c->batch_tab = nullptr; c->batch_bytes = 0; }
     for (auto& hb : c->batch_host) if (hb) { (void)hipHostFree(hb); hb = nullptr; }
+    if (c->rc_tab) { (void)hipFree(c->rc_tab); c->rc_tab = nullptr; c->rc_tab_bytes = 0; }
     if (c->front_tab) { (void)hipFree(c->front_tab); c->front_tab = nullptr; c->front_bytes = 0; }
     for (auto& hb : c->front_host) if (hb) { pinned_free(hb, c->front_host_bytes); hb = nullptr; }
     if (c->copy_stream) { hipStreamSynchronize(c->copy_stream); hipStreamDestroy(c->copy_stream); }
@@ -269,7 +270,7 @@ extern "C" void bscgpu_destroy(bscgpu_ctx* c)
     delete c;
 }
 
-extern "C" int64_t bscgpu_arena_bytes(const bscgpu_ctx* c) { return c ? (int64_t)(c->arena_bytes + c->batch_bytes + c->front_bytes) : 0; }
+extern "C" int64_t bscgpu_arena_bytes(const bscgpu_ctx* c) { return c ? (int64_t)(c->arena_bytes + c->batch_bytes + c->front_bytes + c->rc_tab_bytes) : 0; }
 extern "C" const char* bscgpu_last_error(const bscgpu_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 // ---- profiling --------------------------------------------------------------------------------
@@ -334,6 +335,7 @@ extern "C" int bscgpu_option_set(bscgpu_ctx* c, int key, int value)
     if (key == BSCGPU_OPT_RS_ONESWEEP && value >= 0 && value <= 3 && (value == 0 || c->os_available)) { const int old = c->os_mode; c->os_mode = value; return old; }
     if (key == BSCGPU_OPT_DC_PACKED_STREAM && (value == 0 || value == 1)) { const int old = c->dc_p13; c->dc_p13 = value; return old; }
     if (key == BSCGPU_OPT_BATCH_FRONT && (value == 0 || value == 1)) { const int old = c->batch_front; c->batch_front = value; return old; }
+    if (key == BSCGPU_OPT_DEVICE_RC && (value == 0 || value == 1)) { const int old = c->device_rc; c->device_rc = value; return old; }
     return BSC_BAD_PARAMETER;
 }
 extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
@@ -349,6 +351,8 @@ extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
     if (key == BSCGPU_OPT_BATCH_FRONT) return c->batch_front;
     if (key == BSCGPU_CNT_BATCH_FRONT_PASSES) return c->cnt_front_passes;
     if (key == BSCGPU_CNT_BATCH_L_PASSES) return c->cnt_l_passes;
+    if (key == BSCGPU_OPT_DEVICE_RC) return c->device_rc;
+    if (key == BSCGPU_CNT_DEVICE_RC_BLOCKS) return c->cnt_device_rc;
     return BSC_BAD_PARAMETER;
 }
 extern "C" int bscgpu_last_stage_ms(bscgpu_ctx* c, double* out6)

@@ -117,6 +117,11 @@ struct bscgpu_ctx {
     size_t front_host_bytes = 0;
     int  batch_front = 1;         // BSCGPU_OPT_BATCH_FRONT (default: DESIGN §2b, "The QLFC front end of a pass")
     int  cnt_front_passes = 0, cnt_l_passes = 0;   // BSCGPU_CNT_BATCH_FRONT_PASSES / _L_PASSES
+    // the range coder stage (rangecoder.hip): stream table, prefix entries and results of one launch; grows on demand
+    u8*  rc_tab = nullptr;
+    size_t rc_tab_bytes = 0;      // HBM of rc_tab (bscgpu_arena_bytes counts it once allocated)
+    int  device_rc = 0;           // BSCGPU_OPT_DEVICE_RC: a device-model block's streams are range-coded on the device (default off)
+    int  cnt_device_rc = 0;       // BSCGPU_CNT_DEVICE_RC_BLOCKS
     u64* wc_sink = nullptr;  // [512 * 1024] scratch of the digit passes: phase stamps under RS_PHASE_TIMING (rs_scatter, the single-read passes)
     // single-read digit passes (radix_onesweep.hip), allocated on first use
     int  num_cus = 256;           // hipDeviceAttributeMultiprocessorCount of the context's device
@@ -244,6 +249,9 @@ int  devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32*
                       int* packed_out = nullptr /* non-null: the caller takes the 13-bit packed stream (devcoder.hip DcP13); *packed_out = 1 if that is what was written */);
 const u16* devcoder_pstream_ptr(const bscgpu_ctx* c, int psbuf = 0);
 void devcoder_destroy(bscgpu_ctx* c);
+// the range coder stage on c->stream (rangecoder.hip): bscgpu_rc_encode_device without the argument check; synchronous
+int  rc_encode_device(bscgpu_ctx* c, int form, const void* dBody, const u32* prefix, int nprefix_total, const bscgpu_rc_stream* streams,
+                      int count, void* dOut, int* res, int streams_per_wave);
 int64_t devcoder_arena_bytes(const bscgpu_ctx* c);
 void devcoder_warm_tables();               // starts the model tables' computation on a background thread (first context of the process)
 

@@ -360,6 +360,7 @@ struct BlockJob {
     hipEvent_t ps_ready = nullptr;   // the p stream's copy to the host (copy stream), all of it
     hipEvent_t ps_part[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // ... up to and including sub-block b: what a coder task waits on
     bool ps_dma = false; uint64_t ps_sig[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the pieces went through the DMA engine directly (dma_copy.h): signals instead of events
+    bool rc_done = false;            // BSCGPU_OPT_DEVICE_RC: the GPU stage has range-coded the sub-blocks as well (scratch / sub_res are final, nothing crossed PCIe but them)
     bool ps_landed(int b) const { return ps_dma ? dma_wait(ps_sig[b]) == 0 : hipEventSynchronize(ps_part[b]) == hipSuccess; }
     std::atomic<bool> redo{false};   // a sub-block did not compress: the block goes through the host model again (raw sub-blocks need the run arrays)
     bool stored_small = false;       // n <= header size: finished in the GPU stage
@@ -382,10 +383,54 @@ static int  devcoder_min_n() { static const int v = [] { const char* e = getenv(
 
 static std::atomic<uint64_t> g_count_devmodel{0}, g_count_redo{0}, g_count_devmodel_lzp{0};     // bscgpu_process_counter
 
+// BSCGPU_OPT_DEVICE_RC: the sub-block streams of a device-model block through the device's range coder (rangecoder.hip), one launch on
+// the context's stream straight from the device's p stream; only the coded bytes come down, into the sub-blocks' scratch buffers, and
+// host_finalize frames them as ever.  Every sub-block is coded with outputSize = its own size (coder.cpp:159-240), as host_encode_sub
+// does; one that ends LIBBSC_NOT_COMPRESSIBLE sets redo in the same way.  The output regions lie in the sorter's first key buffer, which
+// nothing reads once the p stream exists (8 max_n bytes; the regions take n + 8 * 128 at most).
+static int device_rc_block(BlockJob& J, int psbuf)
+{
+    bscgpu_ctx* c = J.c;
+    const int nb = J.nblocks;
+    std::vector<uint32_t> prefix;
+    bscgpu_rc_stream S[8];
+    int res[8];
+    uint32_t off = 0;
+    for (int b = 0; b < nb; ++b) {
+        uint8_t fs[256]; int nsym = 0;
+        qlfc_front_first_seen(J.first_run + 256 * (size_t)b, fs, &nsym);
+        const size_t at = prefix.size();
+        prefix.resize(at + BSCGPU_RC_PREFIX_MAX);
+        const int np = bscgpu_rc_prefix(fs, nsym, J.size[b], J.coder, prefix.data() + at, BSCGPU_RC_PREFIX_MAX);
+        if (np < 0) return np;
+        prefix.resize(at + (size_t)np);
+        S[b].body = J.ps_packed ? (int64_t)J.pbase[b] : (int64_t)J.poff[b];
+        S[b].count = J.poff[b + 1] - J.poff[b];
+        S[b].prefix = (uint32_t)at; S[b].nprefix = (uint32_t)np;
+        S[b].out_off = off; S[b].out_size = J.size[b];
+        off += ((uint32_t)J.size[b] + 64u + 63u) & ~63u;
+    }
+    if ((size_t)off > (size_t)8 * (size_t)c->max_n) return LIBBSC_NOT_SUPPORTED;
+    uint8_t* dOut = reinterpret_cast<uint8_t*>(c->kA);
+    const int form = J.ps_packed ? BSCGPU_RC_STATIC13 : J.coder == LIBBSC_CODER_QLFC_FAST ? BSCGPU_RC_FAST16 : BSCGPU_RC_STATIC16;
+    // (one stream per wavefront: with a block's 2 .. 8 streams the wave-uniform chain is the fastest shape measured)
+    int rc = rc_encode_device(c, form, devcoder_pstream_ptr(c, psbuf), prefix.data(), (int)prefix.size(), S, nb, dOut, res, 1);
+    if (rc < 0) return rc;
+    for (int b = 0; b < nb; ++b) {
+        const size_t need = (size_t)J.size[b] + 64;
+        if (J.scratch_cap[b] < need) { J.scratch[b].reset(new uint8_t[need + need / 8]); J.scratch_cap[b] = need + need / 8; }
+        if (res[b] < 0) { J.redo.store(true, std::memory_order_relaxed); J.sub_res[b] = J.size[b]; continue; }      // would be stored raw: that needs the run arrays
+        J.sub_res[b] = res[b];
+        if (hipMemcpyAsync(J.scratch[b].get(), dOut + S[b].out_off, (size_t)res[b], hipMemcpyDeviceToHost, c->stream) != hipSuccess) return LIBBSC_GPU_ERROR;
+    }
+    if (ctx_sync(c) != hipSuccess) return LIBBSC_GPU_ERROR;
+    return LIBBSC_NO_ERROR;
+}
+
 static int gpu_stage(BlockJob& J, int blockSorter, bool allow_devcoder = true)
 {
     CtxTimer tm_stage("gpu_stage of one block");
-    J.sorter = blockSorter; J.use_ps = false; J.ps_packed = false; J.redo.store(false, std::memory_order_relaxed);
+    J.sorter = blockSorter; J.use_ps = false; J.ps_packed = false; J.rc_done = false; J.redo.store(false, std::memory_order_relaxed);
     bscgpu_ctx* c = J.c;
     const int n = J.n;
     if (hipSetDevice(c->device) != hipSuccess) return LIBBSC_GPU_ERROR;
@@ -466,6 +511,15 @@ static int gpu_stage(BlockJob& J, int blockSorter, bool allow_devcoder = true)
                 J.pbase[J.nblocks] = pb13;
                 if (J.ps_packed) zone_entries = ((size_t)pb13 / 8u * 13u + 1u) / 2u + 64;
             }
+            if (r2 == LIBBSC_NO_ERROR && c->device_rc) {
+                // the range coder runs here as well: the stream stays in HBM (its buffer is free again when this returns: no guard, no toggle)
+                rc = device_rc_block(J, pb);
+                if (rc < 0) return rc;
+                J.use_ps = true; J.rc_done = true; J.ps = nullptr; J.ndec = ndec; ok = true;
+                ++c->cnt_device_rc;
+                g_count_devmodel.fetch_add(1, std::memory_order_relaxed);
+                if (J.lz) g_count_devmodel_lzp.fetch_add(1, std::memory_order_relaxed);
+            } else
             // (a pinned landing zone that cannot be had is a reason to take the host model, like an arena that does not fit)
             if (r2 == LIBBSC_NO_ERROR && ctx_ensure_pstream_slot(c, *J.slot, zone_entries) == LIBBSC_NO_ERROR) {
                 // the stream has been synchronised behind the last kernel; the copy goes to the copy stream and is NOT waited for
@@ -549,6 +603,7 @@ static void host_encode_sub(BlockJob& J, int b)
     const size_t need = (size_t)J.size[b] + 64;
     if (J.scratch_cap[b] < need) { J.scratch[b].reset(new uint8_t[need + need / 8]); J.scratch_cap[b] = need + need / 8; }
     if (J.use_ps) {
+        if (J.rc_done) return;
         if (!J.ps_landed(b)) { J.redo.store(true, std::memory_order_relaxed); J.sub_res[b] = J.size[b]; return; }
         const int r = J.ps_packed ? qlfc_encode_static_p13(J.views[b].first_seen, J.views[b].nsym, J.size[b], reinterpret_cast<const uint8_t*>(J.ps_of(b)),
                                                            (size_t)(J.poff[b + 1] - J.poff[b]), J.scratch[b].get(), J.size[b])
@@ -566,6 +621,7 @@ static void host_encode_sub(BlockJob& J, int b)
 static void host_encode_pair(BlockJob& J, int b)
 {
     if (!J.use_ps || b + 1 >= J.nblocks) { host_encode_sub(J, b); if (b + 1 < J.nblocks) host_encode_sub(J, b + 1); return; }
+    if (J.rc_done) return;
     PstreamJob P[2];
     for (int k = 0; k < 2; ++k) {
         const int q = b + k;
@@ -660,6 +716,7 @@ static int ps_group(const BlockJob& J)
 static void host_encode_group(BlockJob& J, int b)
 {
     const int g = J.ps_g;
+    if (J.rc_done) return;                          // coded in the GPU stage (device_rc_block)
     if (g == 2) { host_encode_pair(J, b); return; }
     if (g == 1) { host_encode_sub(J, b); return; }
     PstreamJob P[8];

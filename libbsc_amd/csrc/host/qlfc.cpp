@@ -5,6 +5,7 @@
 // counter update predictor.h:53-61; mixer predictor.h:121-183; range coder rangecoder.h:83-177.
 // The organisation (flat run arrays -> templated decision walker -> range encoder) is ours.
 #include "qlfc.h"
+#include "../../../include/bscgpu.h"
 #include <immintrin.h>
 
 #include <cstring>
@@ -113,6 +114,8 @@ public:
         low_ = 0; range_ = 0xffffffffu; cache_ = 0; held_ = 0;
     }
     bool full() const { return (out_ - begin_) >= limit_; }
+    // bytes the state so far will put out once its cached unit and its pending 0xffff units are released: every shift() adds 2
+    int committed() const { return (int)(out_ - begin_) + 2 * (int)held_ + 2; }
 
     // The coder's two hot words as plain locals of the caller: while a run is being coded they live in registers and are
     // written back to the object only around the (rare) renormalisation call and at the end of the run.
@@ -1438,5 +1441,94 @@ int qlfc_encode_block(const uint8_t* in, uint8_t* out, int in_size, int out_size
     return qlfc_encode_runs(R.view, in_size, out, out_size, coder);
 }
 
+// ---- the range coder as a stage: many streams of plain entries (include/bscgpu.h) ----------------------------------------
+// CPU stand-in of csrc/device/rangecoder.hip: the same streams through the RangeEncoder above, one after the other.
+static inline unsigned p13_get_exact(const uint8_t* b, size_t i)      // p13_get without the read past the field's last byte
+{
+    const size_t bit = i * 13u, at = bit >> 3;
+    const unsigned sh = (unsigned)(bit & 7u);
+    uint32_t w = (uint32_t)b[at] | ((uint32_t)b[at + 1] << 8);
+    if (sh + 13u > 16u) w |= (uint32_t)b[at + 2] << 16;
+    return (w >> sh) & 0x1fffu;
+}
+
+static int rc_stream_host(int form, const void* body, const uint32_t* prefix, const bscgpu_rc_stream& S, uint8_t* out)
+{
+    RangeEncoder rc;
+    rc.init(out, S.out_size);
+    const int region = S.out_size + 64;
+    RangeEncoder::Live L = rc.enter();
+    unsigned is_full = (unsigned)rc.full();
+    // the stage's own bound: a renormalisation that could carry the stream's bytes past its region ends the stream
+    auto no_room = [&]() { return L.range < 0x10000u && rc.committed() + 8 > region; };
+    for (uint32_t i = 0; i < S.nprefix; ++i) {
+        const uint32_t e = prefix[S.prefix + i];
+        if (no_room()) return NOT_COMPRESSIBLE;
+        rc.encode_live_var(L, (e >> 24) & 1u, e & 0xffffu, (e >> 16) & 31u, is_full);
+    }
+    if (form == BSCGPU_RC_STATIC13) {
+        const uint8_t* ps = static_cast<const uint8_t*>(body) + S.body / 8 * 13;
+        for (uint32_t i = 0; i < S.count; ++i) {
+            if (is_full || no_room()) return NOT_COMPRESSIBLE;
+            const unsigned x = p13_get_exact(ps, i);
+            rc.encode_live_f<12>(L, x >> 12, (int)(x & 0xfffu), is_full);
+        }
+    } else {
+        const uint16_t* ps = static_cast<const uint16_t*>(body) + S.body;
+        const bool fast = form == BSCGPU_RC_FAST16;
+        for (uint32_t i = 0; i < S.count; ++i) {
+            const unsigned x = ps[i];
+            if ((((x >> (fast ? 14 : 13)) & 1u) & is_full) || no_room()) return NOT_COMPRESSIBLE;
+            if (fast) rc.encode_live_var(L, (x >> 13) & 1u, x & 0x1fffu, psf_prec(x), is_full);
+            else      rc.encode_live_f<12>(L, (x >> 12) & 1u, (int)(x & 0xfffu), is_full);
+        }
+    }
+    rc.leave(L);
+    if (rc.committed() + 8 > region) return NOT_COMPRESSIBLE;
+    return rc.finish();
+}
+
 }  // namespace bschost
 
+extern "C" BSCGPU_API int bscgpu_rc_prefix(const unsigned char* first_seen, int nsym, int in_size, int coder, uint32_t* entries, int cap)
+{
+    using namespace bschost;
+    if (!first_seen || nsym <= 0 || nsym > 256 || in_size <= 0 || cap < 0 || (coder != CODER_STATIC && coder != CODER_FAST)) return BAD_PARAMETER;
+    RunView H; H.nsym = nsym; memcpy(H.first_seen, first_seen, (size_t)nsym);
+    int n = 0;
+    auto put = [&](unsigned bit, unsigned prec, unsigned p) { if (entries && n < cap) entries[n] = p | (prec << 16) | (bit << 24); ++n; };
+    for (int b = 31; b >= 0; --b) put(((uint32_t)in_size >> b) & 1u, 12, 2048);                 // RangeEncoder::encode_word
+    if (coder == CODER_FAST) (void)encode_alphabet(H, [&](unsigned b) { put(b, 1, 1); });       // encode<1>(b, 1): qlfc_encode_fast_pstream
+    else                     (void)encode_alphabet(H, [&](unsigned b) { put(b, 12, 2048); });   // encode_half
+    return (entries && n > cap) ? BAD_PARAMETER : n;
+}
+
+extern "C" BSCGPU_API int bscgpu_rc_check(int form, int nprefix_total, const bscgpu_rc_stream* streams, int count, int64_t body_bytes, int64_t out_bytes)
+{
+    using namespace bschost;
+    if (form < BSCGPU_RC_STATIC16 || form > BSCGPU_RC_FAST16 || count < 0 || nprefix_total < 0 || (count > 0 && !streams)) return BAD_PARAMETER;
+    for (int i = 0; i < count; ++i) {
+        const bscgpu_rc_stream& S = streams[i];
+        if (S.body < 0 || S.out_size < 0 || (S.out_off & 1u) || (uint64_t)S.prefix + S.nprefix > (uint64_t)nprefix_total) return BAD_PARAMETER;
+        if ((uint64_t)S.out_off + (uint64_t)S.out_size + 64u > 0xffffffffull) return BAD_PARAMETER;
+        if (form == BSCGPU_RC_STATIC13 && (S.body & 7)) return BAD_PARAMETER;
+        if (S.body > ((int64_t)1 << 40)) return BAD_PARAMETER;
+        const int64_t end = form == BSCGPU_RC_STATIC13 ? S.body / 8 * 13 + ((int64_t)S.count * 13 + 7) / 8 : (S.body + (int64_t)S.count) * 2;
+        if (body_bytes >= 0 && S.count > 0 && end > body_bytes) return BAD_PARAMETER;
+        if (out_bytes >= 0 && (int64_t)S.out_off + S.out_size + 64 > out_bytes) return BAD_PARAMETER;
+    }
+    return OK;
+}
+
+extern "C" BSCGPU_API int bscgpu_rc_encode_host(int form, const void* body, const uint32_t* prefix, int nprefix_total,
+                                                const bscgpu_rc_stream* streams, int count, void* out, int* res)
+{
+    using namespace bschost;
+    if (bscgpu_rc_check(form, nprefix_total, streams, count, -1, -1) != OK) return BAD_PARAMETER;
+    if (count > 0 && (!out || !res || (nprefix_total > 0 && !prefix))) return BAD_PARAMETER;
+    for (int i = 0; i < count; ++i) {
+        if (streams[i].count > 0 && !body) return BAD_PARAMETER;
+        res[i] = rc_stream_host(form, body, prefix, streams[i], static_cast<uint8_t*>(out) + streams[i].out_off);
+    }
+    return OK;
+}

@@ -159,6 +159,26 @@ class GpuContext:
             fields[po[b]:po[b + 1]] = ((w >> (bit & 7).astype(np.uint32)) & 0x1fff).astype(np.uint16)
         return fields, list(st[:k]), list(sz[:k]), po, pb, out[:nbytes]
 
+    # ---- the range coder as a stage: many probability streams in one launch (include/bscgpu.h) ----
+    def rc_encode(self, form, body, prefix, streams, streams_per_wave=64, out=None):
+        """bscgpu_rc_encode: code `streams` (tuples body, count, prefix, nprefix, out_off, out_size) of the host arrays body (uint16
+        entries, or the packed bytes for RC_STATIC13) and prefix (uint32 entries of rc_prefix) on the GPU -> (res list, out np.uint8).
+        out: the bytes the regions are laid into (a copy is used; default zeros up to the last region's end); res[i] = bytes of
+        stream i at out[out_off:], or LIBBSC_NOT_COMPRESSIBLE.  The bytes are rc_encode_host's."""
+        b, p, st, o, res = _rc_args(form, body, prefix, streams, out)
+        self._check(self.L.bscgpu_rc_encode(self.h, int(form), N.np_ptr(b), b.nbytes, N.np_ptr(p), p.size, st, len(st), N.np_ptr(o), o.size,
+                                            N.np_ptr(res), int(streams_per_wave)))
+        return [int(x) for x in res[:len(st)]], o
+
+    def rc_encode_device(self, form, dBody, prefix, streams, dOut, streams_per_wave=64):
+        """bscgpu_rc_encode_device: the same with the body and the output regions in device tensors (or raw device pointers) -> res list"""
+        p = np.ascontiguousarray(prefix, dtype=np.uint32)
+        st = rc_streams(streams)
+        res = np.zeros(max(len(st), 1), np.int32)
+        self._check(self.L.bscgpu_rc_encode_device(self.h, int(form), _dptr(dBody), N.np_ptr(p) if p.size else None, p.size, st, len(st),
+                                                   _dptr(dOut), N.np_ptr(res), int(streams_per_wave)))
+        return [int(x) for x in res[:len(st)]]
+
     def compress_device(self, dInput, n, sorter=1, coder=1, features=3):
         out = np.empty(n + 28, np.uint8)
         rc = self._check(self.L.bscgpu_compress_device(self.h, _dptr(dInput), N.np_ptr(out), n, sorter, coder, features))
@@ -299,6 +319,7 @@ class GpuContext:
     # ---- measurement / test knobs (include/bscgpu.h: BSCGPU_OPT_*, BSCGPU_CNT_*) ---------------------------------
     OPT_RS_ONESWEEP, CNT_OS_RETRIES, OPT_DC_PACKED_STREAM = 1, 2, 4
     OPT_BATCH_FRONT, CNT_BATCH_FRONT_PASSES, CNT_BATCH_L_PASSES = 9, 10, 11     # the compress-batch passes' route and how many took each
+    OPT_DEVICE_RC, CNT_DEVICE_RC_BLOCKS = 12, 13       # a device-model block's streams are range-coded on the GPU (default 0) and how many were
     CNT_DC_REPLAYS, CNT_DC_LAST_FAIL, CNT_DC_AVG_UNDECIDED, CNT_DC_HIST_EXTENDED = 5, 6, 7, 8      # the last device-model block (get only)
     DC_FAIL_AVG, DC_FAIL_HIST, DC_FAIL_CAP, DC_FAIL_REPLAY = 2, 4, 8, 16                          # BSCGPU_DC_FAIL_*
 
@@ -331,6 +352,53 @@ class GpuContext:
         out = (C.c_double * 6)()
         self.L.bscgpu_last_stage_ms(self.h, out)
         return list(out)
+
+
+RC_STATIC16, RC_STATIC13, RC_FAST16 = 0, 1, 2      # BSCGPU_RC_*: the form of a stream's body
+RC_REFILL = 128                                    # BSCGPU_RC_REFILL: decisions a wavefront stages per stream and refill
+RC_PREFIX_MAX = 32 + 256 * 8                       # BSCGPU_RC_PREFIX_MAX
+NOT_COMPRESSIBLE = -3                              # LIBBSC_NOT_COMPRESSIBLE
+
+
+def rc_streams(streams):
+    """a list of (body, count, prefix, nprefix, out_off, out_size) tuples (or an RcStream array) -> ctypes array of bscgpu_rc_stream"""
+    if isinstance(streams, C.Array):
+        return streams
+    arr = (N.RcStream * len(streams))()
+    for i, t in enumerate(streams):
+        arr[i] = N.RcStream(*[int(x) for x in t])
+    return arr
+
+
+def _rc_args(form, body, prefix, streams, out):
+    b = np.ascontiguousarray(body, dtype=np.uint8 if form == RC_STATIC13 else np.uint16)
+    p = np.ascontiguousarray(prefix, dtype=np.uint32)
+    st = rc_streams(streams)
+    end = max([int(s.out_off) + int(s.out_size) + 64 for s in st], default=0)
+    o = np.zeros(end, np.uint8) if out is None else np.array(out, dtype=np.uint8, copy=True)
+    if int(N.lib().bscgpu_rc_check(int(form), p.size, st, len(st), b.nbytes, o.size)) < 0:
+        raise GpuError(-1, "range coder streams: bad form, shape, or a stream outside body / prefix / out")
+    return b, p, st, o, np.zeros(max(len(st), 1), np.int32)
+
+
+def rc_prefix(first_seen, in_size, coder=1):
+    """bscgpu_rc_prefix: the decisions the p-stream coders issue before the body (header word, alphabet) as uint32 entries
+    {[15:0] p, [20:16] precision, [24] bit}; coder 1 (static) or 3 (fast)"""
+    fs = np.ascontiguousarray(first_seen, dtype=np.uint8)
+    out = np.zeros(RC_PREFIX_MAX, np.uint32)
+    n = int(N.lib().bscgpu_rc_prefix(N.np_ptr(fs), fs.size, int(in_size), int(coder), N.np_ptr(out), out.size))
+    if n < 0:
+        raise GpuError(n, "bscgpu_rc_prefix")
+    return out[:n].copy()
+
+
+def rc_encode_host(form, body, prefix, streams, out=None):
+    """bscgpu_rc_encode_host: GpuContext.rc_encode's CPU stand-in (no GPU): the same streams through the host's scalar range encoder"""
+    b, p, st, o, res = _rc_args(form, body, prefix, streams, out)
+    rc = int(N.lib().bscgpu_rc_encode_host(int(form), N.np_ptr(b), N.np_ptr(p), p.size, st, len(st), N.np_ptr(o), N.np_ptr(res)))
+    if rc < 0:
+        raise GpuError(rc, "bscgpu_rc_encode_host")
+    return [int(x) for x in res[:len(st)]], o
 
 
 class _FrontLayout(C.Structure):

@@ -5,10 +5,13 @@
 // max_rank 7, counters in a table indexed by (type, symbol) starting from ModelParams::init, dcm::step as the update, the entry
 // stream coded by qlfc_encode_fast_pstream (and the pair coder) — and the bytes must be those of the host's own fast coder
 // (encode_model2, which the CPU tests pin to the reference).  Also checks nth_decision against enumerate at max_rank 7.
+//   fast_sim --trace IN OUT   writes the entry stream of the sub-block in file IN (uint16, little endian) to OUT and nothing else: the fast
+//                             coder's trace on the CPU, for tests of the range coder stage (tests/test_rc_streams_host.py)
 #include "../libbsc_amd/csrc/host/qlfc.cpp"
 #include "../libbsc_amd/csrc/device/devcoder_model.h"
 #include <cstdio>
 #include <random>
+#include <string>
 #include <vector>
 using namespace bschost;
 
@@ -38,8 +41,27 @@ static std::vector<uint16_t> chain_stream(const RunView& R, const dcm::ModelPara
     return ps;
 }
 
-int main()
+static int write_trace(const char* in_path, const char* out_path)
 {
+    std::vector<uint8_t> in;
+    FILE* f = fopen(in_path, "rb");
+    if (!f) return 2;
+    for (int ch; (ch = fgetc(f)) != EOF;) in.push_back((uint8_t)ch);
+    fclose(f);
+    if (in.empty()) return 2;
+    dcm::ModelParams M; dcm::model_params_fast(M);
+    QlfcRuns R; qlfc_runs(in.data(), (int)in.size(), R);
+    int bad = 0;
+    const std::vector<uint16_t> ps = chain_stream(R.view, M, &bad);
+    f = fopen(out_path, "wb");
+    if (!f || fwrite(ps.data(), 2, ps.size(), f) != ps.size()) return 2;
+    fclose(f);
+    return bad != 0;
+}
+
+int main(int argc, char** argv)
+{
+    if (argc == 4 && std::string(argv[1]) == "--trace") return write_trace(argv[2], argv[3]);
     dcm::ModelParams M; dcm::model_params_fast(M);
     std::mt19937_64 rng(3);
     int bad = 0, cases = 0;
