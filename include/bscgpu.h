@@ -228,6 +228,27 @@ BSCGPU_API int bscgpu_qlfc_front_batch_device(bscgpu_ctx* ctx, const void* dL, c
 BSCGPU_API int bscgpu_front_batch_host(const unsigned char* L, const int* sizes, int count, bscgpu_front_layout* out);
 BSCGPU_API int bscgpu_front_batch_code(const bscgpu_front_layout* layout, int block, unsigned char* out, int coder, int features);
 
+/* ---- the static coder's model (-e1) of a whole pass ("The static coder's model of a pass") --------------------------
+ * The device model of bscgpu_qlfc_static_pstream over a pass's sub-block table: up to 4096 blocks and 8192 sub-blocks in one run
+ * index space, one set of launches.  Entries are 16 bits, {[11:0] probability, [12] coded bit, [13] first decision of a run}.
+ * bscgpu_static_pstream_batch_device: front end and model of `count` sorted blocks back to back in HBM (limits and layout as
+ *   bscgpu_qlfc_front_batch_device, which it includes).  out[0 .. cap): every sub-block's entries back to back in stream order,
+ *   sub-block s's at [poff[s], poff[s + 1]); poff has nsub + 1 <= 2 count + 1 entries.  Returns the number of decisions (nothing is
+ *   copied when it exceeds cap); LIBBSC_NOT_SUPPORTED when the device declines the PASS — BSCGPU_CNT_DC_LAST_FAIL says why (0: an
+ *   arena did not fit), the layout is filled and bscgpu_front_batch_code still codes every block; LIBBSC_BAD_PARAMETER; or a GPU
+ *   error.  Synchronous.  Memory: the first call adds 8 bytes per decision of capacity (32 bytes per byte of max_n, + 48 KB) to the
+ *   device model's arena, counted by bscgpu_arena_bytes from then on.
+ * bscgpu_static_pstream_host: the CPU stand-in (no GPU, no context): the host model's own walk over sub-block s of a layout,
+ *   recording instead of coding.  Returns the sub-block's number of decisions; entries past cap are counted, not written.
+ * bscgpu_front_batch_code_ps: bscgpu_front_batch_code for the static coder from the sub-blocks' streams (ps / poff as above) — the
+ *   host runs the range coder only.  A sub-block whose stream runs out of its budget is stored raw, rebuilt from its runs, as the
+ *   reference stores it.  Thread-safe for different blocks of one layout. */
+BSCGPU_API int64_t bscgpu_static_pstream_batch_device(bscgpu_ctx* ctx, const void* dL, const int* sizes, int count, bscgpu_front_layout* layout,
+                                                      uint16_t* out, int64_t cap, uint32_t* poff);
+BSCGPU_API int64_t bscgpu_static_pstream_host(const bscgpu_front_layout* layout, int s, uint16_t* out, int64_t cap);
+BSCGPU_API int bscgpu_front_batch_code_ps(const bscgpu_front_layout* layout, int block, const uint16_t* ps, const uint32_t* poff,
+                                          unsigned char* out, int features);
+
 /* ---- batched decompression: one inverse-BWT pass for many blocks -------------
  * bscgpu_unbwt_batch_device: L of `count` blocks back to back in HBM (block b at Σ sizes[0..b), primary[b] its 1-based
  *   primary index) -> T in the same layout; dT may be dL.  Passes of consecutive blocks, at most max_n bytes and
@@ -434,13 +455,24 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          on the context's stream, straight from the device's probability stream (rangecoder.hip); only the compressed
  *                          bytes come down and the host frames them.  A sub-block that ends LIBBSC_NOT_COMPRESSIBLE sends the block through
  *                          the host model again, as on the host route.  0 (default): the stream crosses PCIe and host threads code it.  Same
- *                          output.  Batched passes, -e2 and blocks the model declines are not affected.
+ *                          output.  -e2 and blocks the model declines are not affected.  A batched pass that took the device model
+ *                          (BSCGPU_OPT_BATCH_MODEL) has all its sub-block streams coded by one launch, eight streams per wavefront;
+ *                          only the coded bytes come down.  The counter below then counts the pass.
  * BSCGPU_CNT_DEVICE_RC_BLOCKS  (get only) blocks of this context whose streams were coded that way.
+ * BSCGPU_OPT_BATCH_MODEL    1: a pass of the compress-batch calls that takes the front-end route with the static coder (-e1) also runs the
+ *                          coder's adaptive model on the GPU (bscgpu_static_pstream_batch_device's stage) and brings the probability
+ *                          stream down; the coder threads run the range coder only (bscgpu_front_batch_code_ps).  A pass the device
+ *                          declines, a pass below 16 MiB (BSC_BATCH_MODEL_MIN_PASS in the environment: another minimum, in bytes), and
+ *                          every pass with -e0 / -e2 or without the front end, takes the host model.  Same output.  Default 0: it halves
+ *                          the host's CPU time per MB and wins on calls of several passes, but not on the one-pass workloads.
+ * BSCGPU_CNT_BATCH_MODEL_PASSES, BSCGPU_CNT_BATCH_MODEL_DECLINED  (get only) passes that were coded from the device model's stream, and
+ *                          passes given to it that it declined (BSCGPU_CNT_DC_LAST_FAIL: why the last one was).
  * set returns the previous value or a negative libbsc error code; get the value or a negative error code. */
 enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACKED_STREAM = 4,
        BSCGPU_CNT_DC_REPLAYS = 5, BSCGPU_CNT_DC_LAST_FAIL = 6, BSCGPU_CNT_DC_AVG_UNDECIDED = 7, BSCGPU_CNT_DC_HIST_EXTENDED = 8,
        BSCGPU_OPT_BATCH_FRONT = 9, BSCGPU_CNT_BATCH_FRONT_PASSES = 10, BSCGPU_CNT_BATCH_L_PASSES = 11,
-       BSCGPU_OPT_DEVICE_RC = 12, BSCGPU_CNT_DEVICE_RC_BLOCKS = 13 };
+       BSCGPU_OPT_DEVICE_RC = 12, BSCGPU_CNT_DEVICE_RC_BLOCKS = 13,
+       BSCGPU_OPT_BATCH_MODEL = 14, BSCGPU_CNT_BATCH_MODEL_PASSES = 15, BSCGPU_CNT_BATCH_MODEL_DECLINED = 16 };
 /* _FAIL_AVG: undecided avg_rank flags; _FAIL_HIST: a run_hist bracket open after 9216 predecessors; _FAIL_CAP: more runs or decisions
  * than the context's arena holds; _FAIL_REPLAY: a chain whose bracket stayed open over more than 64 evaluation chunks. */
 enum { BSCGPU_DC_FAIL_AVG = 2, BSCGPU_DC_FAIL_HIST = 4, BSCGPU_DC_FAIL_CAP = 8, BSCGPU_DC_FAIL_REPLAY = 16 };

@@ -93,6 +93,11 @@ def lib():
     L.bscgpu_qlfc_front_batch_device.argtypes = [vp, vp, vp, C.c_int, vp]
     L.bscgpu_front_batch_host.argtypes = [vp, vp, C.c_int, vp]
     L.bscgpu_front_batch_code.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
+    L.bscgpu_static_pstream_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int64, vp]
+    L.bscgpu_static_pstream_batch_device.restype = C.c_int64
+    L.bscgpu_static_pstream_host.argtypes = [vp, C.c_int, vp, C.c_int64]
+    L.bscgpu_static_pstream_host.restype = C.c_int64
+    L.bscgpu_front_batch_code_ps.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int]
     L.bscgpu_unbwt_batch_plan.argtypes = [vp, C.c_int, C.c_int64, vp]
     L.bscgpu_unbwt_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp]
     L.bscgpu_decompress_batch_sizes.argtypes = [vp, vp, C.c_int, vp]

@@ -153,6 +153,21 @@ int ctx_ensure_front_host(bscgpu_ctx* c)
     return BSC_NO_ERROR;
 }
 
+// the batch model's landing zones: the device model's capacity in decisions (devcoder_ensure: 4 per byte of max_n), 2 bytes each
+int ctx_ensure_model_host(bscgpu_ctx* c)
+{
+    if (c->model_host_failed) return BSC_NOT_ENOUGH_MEMORY;
+    const size_t N = align_up((size_t)c->max_n + 4096, 4096);
+    const size_t entries = 4 * N + 65536;
+    for (int k = 0; k < 2; ++k) {
+        if (c->model_host[k]) continue;
+        c->model_host[k] = (u16*)pinned_alloc(entries * 2);
+        if (!c->model_host[k]) { c->model_host_failed = true; return BSC_NOT_ENOUGH_MEMORY; }
+        c->model_host_entries = entries;
+    }
+    return BSC_NO_ERROR;
+}
+
 extern "C" int bscgpu_d2h_dma_available(void) { return dma_available(); }
 
 extern "C" int bscgpu_device_count(void)
@@ -247,6 +262,7 @@ extern "C" void bscgpu_destroy(bscgpu_ctx* c)
     if (c->rc_tab) { (void)hipFree(c->rc_tab); c->rc_tab = nullptr; c->rc_tab_bytes = 0; }
     if (c->front_tab) { (void)hipFree(c->front_tab); c->front_tab = nullptr; c->front_bytes = 0; }
     for (auto& hb : c->front_host) if (hb) { pinned_free(hb, c->front_host_bytes); hb = nullptr; }
+    for (auto& hb : c->model_host) if (hb) { pinned_free(hb, c->model_host_entries * 2); hb = nullptr; }
     if (c->copy_stream) { hipStreamSynchronize(c->copy_stream); hipStreamDestroy(c->copy_stream); }
     for (auto& p : c->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto& e : c->event_pool) hipEventDestroy(e);
@@ -270,7 +286,7 @@ extern "C" void bscgpu_destroy(bscgpu_ctx* c)
     delete c;
 }
 
-extern "C" int64_t bscgpu_arena_bytes(const bscgpu_ctx* c) { return c ? (int64_t)(c->arena_bytes + c->batch_bytes + c->front_bytes + c->rc_tab_bytes) : 0; }
+extern "C" int64_t bscgpu_arena_bytes(const bscgpu_ctx* c) { return c ? (int64_t)(c->arena_bytes + c->batch_bytes + c->front_bytes + c->rc_tab_bytes) + devcoder_batch_bytes(c) : 0; }
 extern "C" const char* bscgpu_last_error(const bscgpu_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 // ---- profiling --------------------------------------------------------------------------------
@@ -336,6 +352,7 @@ extern "C" int bscgpu_option_set(bscgpu_ctx* c, int key, int value)
     if (key == BSCGPU_OPT_DC_PACKED_STREAM && (value == 0 || value == 1)) { const int old = c->dc_p13; c->dc_p13 = value; return old; }
     if (key == BSCGPU_OPT_BATCH_FRONT && (value == 0 || value == 1)) { const int old = c->batch_front; c->batch_front = value; return old; }
     if (key == BSCGPU_OPT_DEVICE_RC && (value == 0 || value == 1)) { const int old = c->device_rc; c->device_rc = value; return old; }
+    if (key == BSCGPU_OPT_BATCH_MODEL && (value == 0 || value == 1)) { const int old = c->batch_model; c->batch_model = value; return old; }
     return BSC_BAD_PARAMETER;
 }
 extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
@@ -353,6 +370,9 @@ extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
     if (key == BSCGPU_CNT_BATCH_L_PASSES) return c->cnt_l_passes;
     if (key == BSCGPU_OPT_DEVICE_RC) return c->device_rc;
     if (key == BSCGPU_CNT_DEVICE_RC_BLOCKS) return c->cnt_device_rc;
+    if (key == BSCGPU_OPT_BATCH_MODEL) return c->batch_model;
+    if (key == BSCGPU_CNT_BATCH_MODEL_PASSES) return c->cnt_model_passes;
+    if (key == BSCGPU_CNT_BATCH_MODEL_DECLINED) return c->cnt_model_declined;
     return BSC_BAD_PARAMETER;
 }
 extern "C" int bscgpu_last_stage_ms(bscgpu_ctx* c, double* out6)

@@ -122,6 +122,12 @@ struct bscgpu_ctx {
     size_t rc_tab_bytes = 0;      // HBM of rc_tab (bscgpu_arena_bytes counts it once allocated)
     int  device_rc = 0;           // BSCGPU_OPT_DEVICE_RC: a device-model block's streams are range-coded on the device (default off)
     int  cnt_device_rc = 0;       // BSCGPU_CNT_DEVICE_RC_BLOCKS
+    // the static coder's model of a whole pass (devcoder.hip: devcoder_pstream_batch)
+    int  batch_model = 0;         // BSCGPU_OPT_BATCH_MODEL (default 0: DESIGN §2b, "The static coder's model of a pass")
+    int  cnt_model_passes = 0, cnt_model_declined = 0;   // BSCGPU_CNT_BATCH_MODEL_PASSES / _DECLINED
+    u16* model_host[2] = {nullptr, nullptr};   // pinned: a pass's probability stream coming down (two: coding overlaps the next pass), allocated on first use
+    size_t model_host_entries = 0;
+    bool model_host_failed = false;            // they could not be pinned: the route is off for this context
     u64* wc_sink = nullptr;  // [512 * 1024] scratch of the digit passes: phase stamps under RS_PHASE_TIMING (rs_scatter, the single-read passes)
     // single-read digit passes (radix_onesweep.hip), allocated on first use
     int  num_cus = 256;           // hipDeviceAttributeMultiprocessorCount of the context's device
@@ -238,7 +244,11 @@ constexpr int FRONT_MAX_SUB = 2 * BATCH_MAX_BLOCKS;
 size_t front_scratch_bytes(int64_t max_n);
 int  qlfc_front_batch(bscgpu_ctx* c, const u8* dL, const int* sizes, int count, bscgpu_front_layout* out, void* scratch_host);
 void qlfc_front_first_seen(const u32* first_run /*[256]*/, u8* first_seen /*[256]*/, int* nsym);
+// the table qlfc_front_batch left in HBM for its last pass of nsub sub-blocks (qlfc_front.hip: front_tab words)
+struct FrontTab { const u32* sub_off; const u32* sub_base; u32* sub_run; const u32* first_run; };
+FrontTab qlfc_front_tab(const bscgpu_ctx* c, int nsub);
 void qlfc_pick_cuts(const u64* w, u32 nwords, u32 n, int nblocks, int* start, int* size);   // coder.cpp:70-109 from the sampled flag words
+int  ctx_ensure_model_host(bscgpu_ctx* c);        // both pinned stream buffers of the batch model; < 0: not to be had (the pass takes the host model)
 int  ctx_ensure_front_host(bscgpu_ctx* c);        // both pinned run buffers of the batch front end; < 0: not to be had (the pass takes the L route)
 int ctx_ensure_slots(bscgpu_ctx* c, int count);
 int ctx_ensure_pstream_slot(bscgpu_ctx* c, HostSlot& slot, size_t entries);     // pinned landing zone for a block's p stream
@@ -248,6 +258,13 @@ int  devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32*
                       const int* max_rank, u32* D_out, u32* poff_out, u16* dbg, int psbuf = 0, int coder = 1 /* 1 static (-e1), 3 fast (-e0) */,
                       int* packed_out = nullptr /* non-null: the caller takes the 13-bit packed stream (devcoder.hip DcP13); *packed_out = 1 if that is what was written */);
 const u16* devcoder_pstream_ptr(const bscgpu_ctx* c, int psbuf = 0);
+// ... of a whole batched pass ("The static coder's model of a pass"): after qlfc_front_batch, from the run arrays and the
+// table it left in HBM -> *D_out decisions in devcoder_pstream_ptr(c, 0), sub-block s's at [poff[s], poff[s + 1]) with poff[0..nsub] at
+// devcoder_batch_poff_ptr (device).  BSC_NOT_SUPPORTED: the pass is declined (c->dc_last_fail: BSCGPU_DC_FAIL_*; 0: an arena did not
+// fit).  Synchronous.
+int  devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out);
+const u32* devcoder_batch_poff_ptr(const bscgpu_ctx* c);
+int64_t devcoder_batch_bytes(const bscgpu_ctx* c);      // HBM the batch model added on its first use
 void devcoder_destroy(bscgpu_ctx* c);
 // the range coder stage on c->stream (rangecoder.hip): bscgpu_rc_encode_device without the argument check; synchronous
 int  rc_encode_device(bscgpu_ctx* c, int form, const void* dBody, const u32* prefix, int nprefix_total, const bscgpu_rc_stream* streams,

@@ -5,7 +5,8 @@
 // each predicted from three adaptive counters and coded at once.  The counters, though, are independent chains (see
 // devcoder_model.h): chain = (sub-block, decision type, family, X), v <- step(v, bit) over the chain's decisions in stream
 // order.  This file lays the decisions of a whole block (8 sub-blocks, ~2e8 decisions for 64 MiB of text) out chain by
-// chain and walks all chains in parallel:
+// chain and walks all chains in parallel (a batched pass of small blocks, up to 8192 sub-blocks, goes through the same kernels
+// instantiated for a sub-block table: DcForm below, devcoder_pstream_batch):
 //
 //   1. contexts      avg_rank >= 32 flags (two-sided bracket walk with warm-up), per-run packed items; a stable 8-bit
 //                    radix pass by symbol gives the symbol-major order in which "previous run of the same symbol"
@@ -90,6 +91,11 @@ struct DevCoder {
     ModelParams* mp_fast = nullptr;                            // device copy (fast coder: dcm::model_params_fast)
     struct DcFrag* frag = nullptr;                              // packed stream: two fragment records per wavefront of dc_pstream (DcP13)
     u32 *hmeta = nullptr;                                      // pinned: meta + poff
+    // the model of a batched pass (devcoder_pstream_batch), allocated on its first use: the wider chain identity — every event's full
+    // sub-block id, 2 bytes per decision and family (8 Dcap bytes) —, max_rank and stream offset of every sub-block
+    char*  batch_arena = nullptr; size_t batch_bytes = 0; bool batch_alloc_failed = false;
+    u16 *esub[4] = {nullptr, nullptr, nullptr, nullptr};
+    u8  *sub_maxr = nullptr; u32 *poff_tab = nullptr;
 };
 
 __device__ __forceinline__ u32 dc_sb_of(u32 j, const DcSub& S)
@@ -113,25 +119,80 @@ __device__ __forceinline__ u32 dc_maxr_pack(const DcSub& S)
 __device__ __forceinline__ int dc_maxr_of(u32 sb, u32 packed) { return (int)((packed >> (4u * sb)) & 15u); }
 __device__ __forceinline__ u32 dc_run_len(const u32* __restrict__ start, u32 j, u32 m, u32 n) { return ((j + 1 < m) ? start[j + 1] : n) - start[j]; }
 
+// ---- where the sub-block enters: the two shapes its boundaries come in (as qlfc_front.hip: QfRuns / QfRunTab) ------------------------------
+// DcSub: one block's at most eight sub-blocks, by value.  DcSubTab: a batched pass's table in HBM (qlfc_front_batch leaves it: run[s] =
+// first run of sub-block s, strictly increasing, run[nsub] = m; off[s] = its first byte in the pass, off[nsub] = the pass's bytes;
+// base[s] = first byte of its block, which run starts are relative to) plus maxr[s] = max_rank of sub-block s (dc_tab_prep_kernel).
+// The kernels below are templates over the shape; DcForm<SB> is everything that differs: the packed item (devcoder_model.h: Item /
+// ItemB — the batch item carries 13 bits of sub-block and the sub-block's max_rank, so no kernel looks anything up by sub-block
+// except a sub-block's first run), the shift that leaves (X, sub-block), and the index of the "kinds of run" bitmap (sub-block for the
+// eight, max_rank for the table: 8 x 512 either way).
+struct DcSubTab { u32 nsub; const u32* run; const u32* off; const u32* base; const u8* maxr; };
+__device__ __forceinline__ u32 dc_sb_of(u32 j, const DcSubTab& S) { return batch_block_of(S.run, S.nsub, j); }
+template <class SB> struct DcForm;
+template <> struct DcForm<DcSub> {
+    static constexpr bool TAB = false;
+    static constexpr int CHAIN_SHIFT = ITEM_CHAIN_SHIFT;
+    typedef Item It;
+    static __device__ __forceinline__ It unpack(u64 k) { return item_unpack(k); }
+    static __device__ __forceinline__ u32 maxr_word(const DcSub& S) { return dc_maxr_pack(S); }      // one scalar word at the kernel's top
+    static __device__ __forceinline__ int maxr(const It& it, u32 w) { return dc_maxr_of(it.sb, w); }
+    static __device__ __forceinline__ u32 first_run(const DcSub& S, u32 sb) { return S.first[sb]; }
+    static __device__ __forceinline__ u32 next_first(const DcSub& S, u32 sb) { return (sb + 1 < S.nb) ? S.first[sb + 1] : 0xffffffffu; }
+    static __device__ __forceinline__ u32 avg_top(const DcSub&, u32) { return 255u; }
+    static __device__ __forceinline__ u32 kind(const It& it, int) { return it.sb; }
+    static __device__ __forceinline__ int kind_maxr(u32 k, u32 w) { return dc_maxr_of(k, w); }
+    static __device__ __forceinline__ u32 sig_sb(const It& it) { return it.sb; }
+    static __device__ __forceinline__ u64 item(const DcSub& S, const u8* __restrict__ sym, const u8* __restrict__ rank, const u32* __restrict__ start,
+                                               const u8* __restrict__ ge32, u32 j, u32 m, u32 n)
+    { return item_pack(sym[j], dc_sb_of(j, S), ge32[j], rank[j], dc_run_len(start, j, m, n)); }
+};
+template <> struct DcForm<DcSubTab> {
+    static constexpr bool TAB = true;
+    static constexpr int CHAIN_SHIFT = ITEMB_CHAIN_SHIFT;
+    typedef ItemB It;
+    static __device__ __forceinline__ It unpack(u64 k) { return item_unpack_b(k); }
+    static __device__ __forceinline__ u32 maxr_word(const DcSubTab&) { return 0u; }
+    static __device__ __forceinline__ int maxr(const It& it, u32) { return (int)it.maxr; }
+    static __device__ __forceinline__ u32 first_run(const DcSubTab& S, u32 sb) { return S.run[sb]; }
+    static __device__ __forceinline__ u32 next_first(const DcSubTab& S, u32 sb) { return (sb + 1 < S.nsub) ? S.run[sb + 1] : 0xffffffffu; }
+    // avg' = (124 avg + 4 rank) >> 7 <= max(avg, rank) and rank < 2^(max_rank + 1): a tighter top for the bracket than 255, so that a
+    // sub-block of at most 32 symbols in the middle of a pass can never leave a flag undecided (the eight-entry path does not even launch
+    // the kernel for such a block)
+    static __device__ __forceinline__ u32 avg_top(const DcSubTab& S, u32 sb) { return (2u << S.maxr[sb]) - 1u; }
+    static __device__ __forceinline__ u32 kind(const It&, int maxr) { return (u32)maxr; }
+    static __device__ __forceinline__ int kind_maxr(u32 k, u32) { return (int)k; }
+    static __device__ __forceinline__ u32 sig_sb(const It& it) { return it.sb & 7u; }                // (the full id goes to the parallel array)
+    static __device__ __forceinline__ u64 item(const DcSubTab& S, const u8* __restrict__ sym, const u8* __restrict__ rank, const u32* __restrict__ start,
+                                               const u8* __restrict__ ge32, u32 j, u32, u32)
+    {
+        const u32 sb = dc_sb_of(j, S);
+        const u32 end = (j + 1 < S.run[sb + 1]) ? start[j + 1] : S.off[sb + 1] - S.base[sb];      // the block's next run, or the sub-block's end
+        return item_pack_b(sym[j], sb, ge32[j], rank[j], S.maxr[sb], end - start[j]);
+    }
+};
+
 // ---------------------------------------------------------------------------------------------------------------------
 // 1a. avg_rank >= 32 (qlfc.cpp:903 / :978): avg' = (avg * 124 + rank * 4) >> 7, reset per sub-block.  One lane per chunk,
 // two-sided bracket [0, 255] started DC_AVG_WARM runs early; the flag of a run is decided when both ends agree.
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(WG) void dc_avg_kernel(const u8* __restrict__ rank, u32 m, DcSub S, u8* __restrict__ ge32, u32* __restrict__ meta)
+template <class SB>
+__global__ __launch_bounds__(WG) void dc_avg_kernel(const u8* __restrict__ rank, u32 m, SB S, u8* __restrict__ ge32, u32* __restrict__ meta)
 {
+    typedef DcForm<SB> F;
     const u32 c = blockIdx.x * WG + threadIdx.x;
     const u64 j0 = (u64)c * DC_AVG_CH;
     if (j0 >= m) return;
     const u32 j1 = (u32)((j0 + DC_AVG_CH < m) ? j0 + DC_AVG_CH : m);
     u32 sb = dc_sb_of((u32)j0, S);
-    const u32 sb_first = S.first[sb];
+    const u32 sb_first = F::first_run(S, sb);
     u32 w0 = ((u32)j0 > sb_first + DC_AVG_WARM) ? (u32)j0 - DC_AVG_WARM : sb_first;
-    u32 lo = 0, hi = (w0 == sb_first) ? 0u : 255u;
+    u32 lo = 0, hi = (w0 == sb_first) ? 0u : F::avg_top(S, sb);
     for (u32 j = w0; j < (u32)j0; ++j) { const u32 r = rank[j]; lo = avg_rank_next(lo, r); hi = avg_rank_next(hi, r); }
-    u32 next_first = (sb + 1 < S.nb) ? S.first[sb + 1] : 0xffffffffu;
+    u32 next_first = F::next_first(S, sb);                            // (a chunk of a batched pass can hold dozens of sub-block starts)
     u32 und = 0;
     for (u32 j = (u32)j0; j < j1; ++j) {
-        if (j == next_first) { lo = hi = 0; ++sb; next_first = (sb + 1 < S.nb) ? S.first[sb + 1] : 0xffffffffu; }
+        if (j == next_first) { lo = hi = 0; ++sb; next_first = F::next_first(S, sb); }
         const u32 f = lo >= 32u;
         und += (f != (u32)(hi >= 32u));
         ge32[j] = (u8)f;
@@ -142,19 +203,22 @@ __global__ __launch_bounds__(WG) void dc_avg_kernel(const u8* __restrict__ rank,
 }
 
 // 1b. packed items in stream order: X = symbol (the char family's sort digit; the static family ignores it)
+template <class SB>
 __global__ __launch_bounds__(WG) void dc_items_kernel(const u8* __restrict__ sym, const u8* __restrict__ rank, const u32* __restrict__ start,
-                                                      const u8* __restrict__ ge32, u32 m, u32 n, DcSub S, u64* __restrict__ key_ch)
+                                                      const u8* __restrict__ ge32, u32 m, u32 n, SB S, u64* __restrict__ key_ch)
 {
     const u32 j = blockIdx.x * WG + threadIdx.x;
-    if (j < m) key_ch[j] = item_pack(sym[j], dc_sb_of(j, S), ge32[j], rank[j], dc_run_len(start, j, m, n));
+    if (j < m) key_ch[j] = DcForm<SB>::item(S, sym, rank, start, ge32, j, m, n);
 }
 
-// kinds of run for the "which decision types occur" bitmap: 8 sub-blocks x escape flag x 256 ranks, then 96 run-length classes
+// kinds of run for the "which decision types occur" bitmap: 8 sub-blocks (a batched pass: 8 values of max_rank — all the sub-block
+// contributes to a run's decision types) x escape flag x 256 ranks, then 96 run-length classes
 constexpr u32 DC_KIND_RUN = 8 * 512, DC_KIND_WORDS = (DC_KIND_RUN + 96 + 31) / 32;
 
 // 1c. context states + the state family's items + which kinds of run occur.  Thread per run (stream order).
+template <class SB>
 __global__ __launch_bounds__(WG) void dc_ctx_kernel(const u64* __restrict__ key_ch, const u64* __restrict__ key_ch_s, const u32* __restrict__ inv_ch,
-                                                    u32 m, DcSub S, const u8* __restrict__ tab_rank, const u8* __restrict__ tab_run,
+                                                    u32 m, SB S, const u8* __restrict__ tab_rank, const u8* __restrict__ tab_run,
                                                     u64* __restrict__ key_sr, u64* __restrict__ key_sn, u32* __restrict__ present, u32* __restrict__ meta)
 {
     __shared__ u32 bits[DC_KIND_WORDS];
@@ -163,14 +227,16 @@ __global__ __launch_bounds__(WG) void dc_ctx_kernel(const u64* __restrict__ key_
     const u32 j = dc_virtual_block() * WG + threadIdx.x;
     if (j < m) {
         const u64 key = key_ch[j];
-        const Item it = item_unpack(key);
-        const u32 j0 = S.first[it.sb];
+        typedef DcForm<SB> F;
+        constexpr int CS = F::CHAIN_SHIFT;
+        const typename F::It it = F::unpack(key);
+        const u32 j0 = F::first_run(S, it.sb);                        // (a 64-run tile of a batched pass can hold dozens of sub-block starts)
         // window contexts: previous runs of the same sub-block (qlfc.cpp:1063-1068)
         u32 ctx_rank0 = 0, ctx_rank4 = 0, ctx_run = 0;
 #pragma unroll
         for (u32 k = 1; k <= 4; ++k) {
             if (j >= j0 + k) {
-                const Item p = item_unpack(key_ch[j - k]);
+                const typename F::It p = F::unpack(key_ch[j - k]);
                 if (k <= 3) ctx_rank0 |= (p.rank == 1u ? 1u : 0u) << (k - 1);
                 ctx_rank4 |= (p.rank - 1u < 3u ? p.rank - 1u : 3u) << (2 * (k - 1));
                 ctx_run |= (p.run < 3u ? 1u : 0u) << (k - 1);
@@ -178,7 +244,7 @@ __global__ __launch_bounds__(WG) void dc_ctx_kernel(const u64* __restrict__ key_
         }
         // symbol-major neighbours: the previous runs of this symbol in this sub-block, nearest first (loaded once)
         const u32 q = inv_ch[j];
-        const u64 chain_id = key >> 53;                               // X and sub-block
+        const u64 chain_id = key >> CS;                               // X and sub-block
         // (all NP loads are issued at once — the index does not depend on what the nearer neighbours turn out to be — and NP is large
         // enough that the bracket below almost always closes: on the bench block 1.9 % of the runs — a lane in 38 % of the wavefronts —
         // stay open after five predecessors (a symbol whose recent runs all have length 2 or 3 has two fixed points, 1 and 2), 0.015 %
@@ -200,8 +266,8 @@ __global__ __launch_bounds__(WG) void dc_ctx_kernel(const u64* __restrict__ key_
 #pragma unroll
         for (int t = 1; t <= NP; ++t) {
             bool have = false;
-            if (!at_start && q >= (u32)t && (pk[t - 1] >> 53) == chain_id) {
-                const Item pi = item_unpack(pk[t - 1]); prun[t - 1] = pi.run; if (t == 1) prank0 = pi.rank; have = true; np = t;
+            if (!at_start && q >= (u32)t && (pk[t - 1] >> CS) == chain_id) {
+                const typename F::It pi = F::unpack(pk[t - 1]); prun[t - 1] = pi.run; if (t == 1) prank0 = pi.rank; have = true; np = t;
             }
             if (!have) { at_start = true; prun[t - 1] = 1; }
         }
@@ -221,11 +287,11 @@ __global__ __launch_bounds__(WG) void dc_ctx_kernel(const u64* __restrict__ key_
                 for (;;) {
                     lo = 0; hi = 63; u32 first = q; bool exact = false;
                     for (u32 t = 1; t <= K; ++t) {
-                        if (q < t || (key_ch_s[q - t] >> 53) != chain_id) { exact = true; break; }
+                        if (q < t || (key_ch_s[q - t] >> CS) != chain_id) { exact = true; break; }
                         first = q - t;
                     }
                     if (exact) hi = 0;
-                    for (u32 p = first; p < q; ++p) { const u32 r = item_unpack(key_ch_s[p]).run; lo = run_hist_next(lo, r); hi = run_hist_next(hi, r); }
+                    for (u32 p = first; p < q; ++p) { const u32 r = F::unpack(key_ch_s[p]).run; lo = run_hist_next(lo, r); hi = run_hist_next(hi, r); }
                     cl = lo < 7u ? lo : 7u; ch = hi < 7u ? hi : 7u;
                     if (cl == ch) break;
                     if (K >= (u32)DC_HIST_KMAX) { atomicOr(&meta[DM_FAIL], (u32)FAIL_HIST); break; }
@@ -243,7 +309,7 @@ __global__ __launch_bounds__(WG) void dc_ctx_kernel(const u64* __restrict__ key_
         // which kinds of run occur: the decision types of a run are a function of (sub-block, escape flag, rank) on the rank side
         // and of the run-length class on the run side (dc_setup_kernel expands the kinds that occur into types)
         auto mark = [&](u32 k) { const u32 w = k >> 5, b = 1u << (k & 31); if (!(bits[w] & b)) atomicOr(&bits[w], b); };
-        mark((it.sb << 9) | (it.ge32 << 8) | it.rank);
+        mark((F::kind(it, F::maxr(it, 0u)) << 9) | (it.ge32 << 8) | it.rank);
         mark(DC_KIND_RUN + (it.run < 64u ? it.run : 64u + (u32)bsr(it.run)));
     }
     __syncthreads();
@@ -256,9 +322,11 @@ __global__ __launch_bounds__(WG) void dc_ctx_kernel(const u64* __restrict__ key_
 }
 
 // 1d. the canonical rounds that occur (and how many decision types: diagnostics).  One workgroup.
-__global__ __launch_bounds__(WG) void dc_setup_kernel(const u32* __restrict__ kinds, DcSub S, u8* __restrict__ rounds, u32* __restrict__ meta)
+template <class SB>
+__global__ __launch_bounds__(WG) void dc_setup_kernel(const u32* __restrict__ kinds, SB S, u8* __restrict__ rounds, u32* __restrict__ meta)
 {
-    const u32 mrp = dc_maxr_pack(S);                                  // max_rank of the eight sub-blocks, one scalar word
+    typedef DcForm<SB> F;
+    const u32 mrp = F::maxr_word(S);                                  // max_rank of the eight sub-blocks, one scalar word
     __shared__ u32 present[(NUM_TAU + 31) / 32];
     __shared__ u32 rbits[3];
     __shared__ u32 ntypes;
@@ -272,7 +340,7 @@ __global__ __launch_bounds__(WG) void dc_setup_kernel(const u32* __restrict__ ki
         Item it; it.sb = 0; it.ge32 = 0; it.rank = 1; it.run = 1;
         if (k < DC_KIND_RUN) {                                                    // the rank side of a run of this kind
             it.sb = k >> 9; it.ge32 = (k >> 8) & 1u; it.rank = k & 255u;
-            const int maxr = dc_maxr_of(it.sb, mrp);
+            const int maxr = F::kind_maxr(it.sb, mrp);                // (a batched pass: the kind IS the max_rank)
             if (it.ge32) { for (int d = 0; d <= maxr; ++d) { u32 bit; mark(decision(it, maxr, ROUND_RP + d, &bit)); } }
             else {
                 mark(TAU_RF);
@@ -428,11 +496,12 @@ constexpr int DC_BINS = 640;           // padded to 10 per lane
 __host__ __device__ __forceinline__ u32 dc_rank_bin(u32 rank, int maxr) { const int B = rank != 1u ? bsr(rank) : 0; return rank | ((B != 0 && B < maxr) ? 256u : 0u); }
 __host__ __device__ __forceinline__ u32 dc_run_bin(u32 run) { return (u32)DC_BIN_RUN + (run < 64u ? run : 64u + (u32)bsr(run)); }
 
-template <int SIDES>
-__global__ __launch_bounds__(WG) void dc_part_count_kernel(const u64* __restrict__ items, DcGeom g, DcSub S, const DcRowBins* __restrict__ rowbins,
+template <int SIDES, class SB>
+__global__ __launch_bounds__(WG) void dc_part_count_kernel(const u64* __restrict__ items, DcGeom g, SB S, const DcRowBins* __restrict__ rowbins,
                                                            u32* __restrict__ cnt /*[DC_ROWS][W]*/, u32* __restrict__ wdec)
 {
-    const u32 mrp = dc_maxr_pack(S);                                  // max_rank of the eight sub-blocks, one scalar word
+    typedef DcForm<SB> F;
+    const u32 mrp = F::maxr_word(S);                                  // max_rank of the eight sub-blocks, one scalar word
     __shared__ u32 bins[WAVES][DC_BINS + 8];
     __shared__ u32 hrp[WAVES][256];                                             // escape rows (TAU_RP + ctx - 1), counted directly
     for (u32 i = threadIdx.x; i < WAVES * (DC_BINS + 8); i += WG) (&bins[0][0])[i] = 0;
@@ -461,8 +530,8 @@ __global__ __launch_bounds__(WG) void dc_part_count_kernel(const u64* __restrict
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 if (base + 64u * (u32)u + lane >= i1) continue;
-                const Item it = item_unpack(kk[u]);
-                const int maxr = dc_maxr_of(it.sb, mrp);
+                const typename F::It it = F::unpack(kk[u]);
+                const int maxr = F::maxr(it, mrp);
                 if (SIDES & 1) {
                     total += (u32)count_rank_side(it, maxr);
                     if (it.ge32) {
@@ -561,13 +630,15 @@ __device__ __forceinline__ int dc_writelane(int v, int val, int lane)
 #endif
 constexpr u32 DC_POS_STAGE = DC_POS_STAGE_N;
 struct __attribute__((packed, aligned(4))) DcPos4 { u32 a, b, c, d; };      // four positions, 4-byte aligned: one dwordx4 store
-template <int SIDES>
-__global__ __launch_bounds__(WG) void dc_part_scatter_kernel(const u64* __restrict__ items, DcGeom g, DcSub S, const u32* __restrict__ meta,
+template <int SIDES, class SB>
+__global__ __launch_bounds__(WG) void dc_part_scatter_kernel(const u64* __restrict__ items, DcGeom g, SB S, const u32* __restrict__ meta,
                                                              const u32* __restrict__ cnt, const u32* __restrict__ rowstart,
                                                              const u32* __restrict__ wdecoff, u32 ignoreX,
-                                                             u16* __restrict__ events, u32* __restrict__ pos, u32* __restrict__ doff)
+                                                             u16* __restrict__ events, u32* __restrict__ pos, u32* __restrict__ doff,
+                                                             u16* __restrict__ esub /* batched pass: the sub-block of every event */)
 {
-    const u32 mrp = dc_maxr_pack(S);                                  // max_rank of the eight sub-blocks, one scalar word
+    typedef DcForm<SB> F;
+    const u32 mrp = F::maxr_word(S);                                  // max_rank of the eight sub-blocks, one scalar word
     __shared__ u32 goff[WAVES][DC_ROWS];
     __shared__ u32 spos[WAVES][DC_POS_STAGE];
     if (meta[DM_FAIL] != 0u) return;
@@ -593,8 +664,8 @@ __global__ __launch_bounds__(WG) void dc_part_scatter_kernel(const u64* __restri
         // wavefront, 0.35 ms of every partition job whatever it had to scatter.)
         asm volatile("" :: "v"(key) : "memory");
         knext = (i + 64 < i1) ? items[i + 64] : 0ull;
-        const Item it = item_unpack(key);
-        const int maxr = dc_maxr_of(it.sb, mrp);
+        const typename F::It it = F::unpack(key);
+        const int maxr = F::maxr(it, mrp);
         u32 nd = 0;
         if (valid) { if (SIDES & 1) nd += (u32)count_rank_side(it, maxr); if (SIDES & 2) nd += (u32)count_run_side(it); }
         const u32 incl = wave_incl_sum(nd);
@@ -602,7 +673,8 @@ __global__ __launch_bounds__(WG) void dc_part_scatter_kernel(const u64* __restri
         if (valid) doff[i] = running + loc;
         const u32 tile_total = (u32)__builtin_amdgcn_readlane((int)incl, 63);      // a scalar: `staged` below is then a scalar
         const bool staged = tile_total <= DC_POS_STAGE;               // branch around every round's position store, not an exec-mask dance
-        const u32 sig = (ignoreX ? 0u : item_X(key)) | (it.sb << 8);
+        const u32 sig = (ignoreX ? 0u : item_X(key)) | (F::sig_sb(it) << 8);
+        const u16 sub16 = (u16)it.sb;
         u32* mypos = pos + running + loc;
         // (two copies of the rounds, chosen once per tile: with the test inside `put` every round carried a branch around its position store)
         auto rounds = [&](auto staged_tag) __attribute__((always_inline)) {
@@ -616,6 +688,7 @@ __global__ __launch_bounds__(WG) void dc_part_scatter_kernel(const u64* __restri
                     if (on) {
                         const u32 p = bs + __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));   // peers in lower lanes
                         events[p] = (u16)(sig | (bit << 11));
+                        if (F::TAB) esub[p] = sub16;
                         put(p);
                     }
                     sreg = dc_writelane(sreg, (int)(bs + (u32)__popcll(m)), slot);                    // (was: compare, move, select)
@@ -629,6 +702,7 @@ __global__ __launch_bounds__(WG) void dc_part_scatter_kernel(const u64* __restri
                         const u32 p = before + rr;
                         vg[h] = before + cn;                                  // every peer writes the same value (was: the highest one, behind a compare and a branch)
                         events[p] = (u16)(sig | (bit << 11));
+                        if (F::TAB) esub[p] = sub16;
                         put(p);
                     }
                 });
@@ -717,6 +791,32 @@ __global__ __launch_bounds__(WG) void dc_mark_rows_kernel(DcEvalAll A)
     const u32 rs = J.rowstart[r], re = J.rowstart[r + 1];
     if (re > rs) const_cast<u16*>(J.events)[rs] |= (u16)DC_ROWMARK;
 }
+// A batched pass (up to 8192 sub-blocks) keeps the 16-bit event: its signature holds the sub-block modulo 8, which alone would walk
+// two chains as one wherever a symbol (or a decision type of the context-free family) occurs in sub-blocks s and s + 8 k and in none
+// between — their chains are neighbours in the row.  The scatter therefore also writes every event's full sub-block id to a parallel
+// array, and this pass turns it into the mark the walks already honour: an event whose id differs from its predecessor's starts a
+// chain.  Inside a row the events of one X are in stream order, i.e. sub-block-major, so (signature change) or (id change) or (row
+// start) is exactly "another chain" — the identity is exact, and the evaluation kernels read nothing new.  Thread per 8 events.
+struct DcMarkAll { u16* events[4]; const u16* esub[4]; u32 E[4]; };
+__global__ __launch_bounds__(WG) void dc_mark_chains_kernel(DcMarkAll A, const u32* __restrict__ meta)
+{
+    if (meta[DM_FAIL] != 0u) return;
+    const u32 E = A.E[blockIdx.y];
+    const u64 k0 = ((u64)blockIdx.x * WG + threadIdx.x) * 8u;
+    if (k0 >= E) return;
+    const u16* __restrict__ es = A.esub[blockIdx.y];
+    u16* __restrict__ ev = A.events[blockIdx.y];
+    const uint4 q = *reinterpret_cast<const uint4*>(es + k0);           // (the array has slack behind its last entry; entries past E are not used)
+    const u32 w[4] = {q.x, q.y, q.z, q.w};
+    u32 prev = k0 > 0 ? (u32)es[k0 - 1] : (w[0] & 0xffffu);
+#pragma unroll
+    for (u32 x = 0; x < 8; ++x) {
+        const u32 id = (w[x >> 1] >> (16u * (x & 1u))) & 0xffffu;
+        if (id != prev && k0 + x < E) ev[k0 + x] |= (u16)DC_ROWMARK;
+        prev = id;
+    }
+}
+
 // first row of each class, and one past the last
 __device__ __forceinline__ int dc_class_first_row(int cls)
 {
@@ -889,7 +989,9 @@ __device__ __forceinline__ bool dc_chunk_continues(const DcEvalJob& J, u32 c, u3
     u32 row = dc_find_row(J.rowstart, k0);
     if (J.rowstart[row] == k0) return false;                          // a row (hence a chain) starts exactly here
     // (an empty row cannot own k0: dc_find_row returns the last row starting at or before k0, which then is non-empty or k0 >= E)
-    return (((u32)J.events[k0 - 1] ^ (u32)J.events[k0]) & DC_SIGMASK) == 0;
+    // (a marked event starts a chain: a row — tested above — or, in a batched pass, another sub-block with the same signature)
+    const u32 e1 = J.events[k0];
+    return ((((u32)J.events[k0 - 1] ^ e1) & DC_SIGMASK) | (e1 & DC_ROWMARK)) == 0;
 }
 
 // exact value at the start of every chunk that begins inside a chain (all jobs in one launch; thread per chunk)
@@ -1085,11 +1187,13 @@ __global__ __launch_bounds__(WG) void dc_p13_join_kernel(const DcFrag* __restric
 #ifndef DC_PS_MINW
 #define DC_PS_MINW 1            // minimum waves per SIMD the register allocator must leave room for (A/B: 82 VGPRs = 5 waves by default)
 #endif
-template <bool FAST, bool P13>
-__global__ __launch_bounds__(WG, DC_PS_MINW) void dc_pstream_kernel(DcGather G, DcSub S, const ModelParams* __restrict__ mp,
+template <bool FAST, bool P13, class SB>
+__global__ __launch_bounds__(WG, DC_PS_MINW) void dc_pstream_kernel(DcGather G, SB S, const ModelParams* __restrict__ mp,
                                                         u32* __restrict__ meta, u16* __restrict__ out, u16* __restrict__ dbg /*[3][D] or null*/, u32 dbgD, DcP13 Q)
 {
-    const u32 mrp = dc_maxr_pack(S);                                  // max_rank of the eight sub-blocks, one scalar word
+    typedef DcForm<SB> F;
+    static_assert(!(P13 && F::TAB), "the packed stream is laid out by eight sub-blocks");
+    const u32 mrp = F::maxr_word(S);                                  // max_rank of the eight sub-blocks, one scalar word
     __shared__ u16 stage[WAVES][DC_PS_STAGE];
     __shared__ short s_lr[NUM_CLS][4];                                // blend weights per class: an LDS read per decision instead of global loads at a per-lane address
     if (meta[DM_FAIL] != 0u) return;
@@ -1100,8 +1204,8 @@ __global__ __launch_bounds__(WG, DC_PS_MINW) void dc_pstream_kernel(DcGather G, 
     const u32 j = dc_virtual_block() * WG + threadIdx.x;
     const u32 lane = threadIdx.x & 63u;
     const bool valid = j < G.m;                                       // (whole wavefronts past the end still take part in the shuffles below)
-    const Item it = item_unpack(valid ? G.key_ch[j] : 0ull);
-    const int maxr = dc_maxr_of(it.sb, mrp);
+    const typename F::It it = F::unpack(valid ? G.key_ch[j] : 0ull);
+    const int maxr = F::maxr(it, mrp);
     const int n_rank = valid ? count_rank_side(it, maxr) : 0, n_run = valid ? count_run_side(it) : 0, nd = n_rank + n_run;
     const u32 b_sp = valid ? G.doff_sp[j] : 0u;
     const u32 incl = wave_incl_sum((u32)nd);
@@ -1197,6 +1301,25 @@ __global__ void dc_poff_kernel(const u32* __restrict__ doff_sp, DcSub S, u32 m, 
     const u32 b = threadIdx.x;
     if (b <= S.nb) poff[b] = doff_sp[b < S.nb ? S.first[b] : m];
 }
+// ... of a batched pass: every sub-block of the table (run[nsub] = m, doff_sp[m] = the pass's decisions)
+__global__ __launch_bounds__(WG) void dc_poff_tab_kernel(const u32* __restrict__ doff_sp, DcSubTab S, u32* __restrict__ poff)
+{
+    const u32 b = blockIdx.x * WG + threadIdx.x;
+    if (b <= S.nsub) poff[b] = doff_sp[S.run[b]];
+}
+// max_rank of every sub-block of a pass from its first-run table: bsr(nsym - 1), nsym = symbols with a first run.  One wavefront per
+// sub-block.  Also closes the run table: run[nsub] = m.
+__global__ __launch_bounds__(WG) void dc_tab_prep_kernel(const u32* __restrict__ first_run /*[nsub][256]*/, u32 nsub, u32 m,
+                                                         u8* __restrict__ maxr, u32* __restrict__ sub_run)
+{
+    const u32 s = blockIdx.x * WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) sub_run[nsub] = m;
+    if (s >= nsub) return;
+    const uint4 q = reinterpret_cast<const uint4*>(first_run + (size_t)s * 256u)[lane];
+    u32 cnt = (q.x != 0xffffffffu) + (q.y != 0xffffffffu) + (q.z != 0xffffffffu) + (q.w != 0xffffffffu);
+    cnt = wave_incl_sum(cnt);
+    if (lane == 63u) maxr[s] = (u8)bsr(cnt - 1u);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
@@ -1250,6 +1373,7 @@ void devcoder_destroy(bscgpu_ctx* c)
     DevCoder* d = c->dc;
     if (!d) return;
     if (d->arena) hipFree(d->arena);
+    if (d->batch_arena) hipFree(d->batch_arena);
     if (d->hmeta) hipHostFree(d->hmeta);
     delete d;
     c->dc = nullptr;
@@ -1344,19 +1468,20 @@ int devcoder_ensure(bscgpu_ctx* c)
 }
 
 int64_t devcoder_arena_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)c->dc->arena_bytes : 0; }
+int64_t devcoder_batch_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)c->dc->batch_bytes : 0; }
 
-template <int SIDES>
-static void dc_launch_partition(bscgpu_ctx* c, DevCoder* d, const u64* items, u32 m, const DcSub& S, int job, u32 ignoreX)
+template <int SIDES, class SB>
+static void dc_launch_partition(bscgpu_ctx* c, DevCoder* d, const u64* items, u32 m, const SB& S, int job, u32 ignoreX)
 {
     const DcGeom g = dc_geom(m);
     const u32 grid = (g.W + WAVES - 1) / WAVES;
     u32* rowstart = d->rowstart + (DC_ROWS + 8) * job;
     prof_begin(c, BSCGPU_K_DC_PART, (u64)m * 8, m);
-    hipLaunchKernelGGL(dc_part_count_kernel<SIDES>, dim3(grid), dim3(WG), 0, c->stream, items, g, S, d->rowbins, d->cnt, d->wdec);
+    hipLaunchKernelGGL((dc_part_count_kernel<SIDES, SB>), dim3(grid), dim3(WG), 0, c->stream, items, g, S, d->rowbins, d->cnt, d->wdec);
     hipLaunchKernelGGL(dc_scan_rows_kernel, dim3(DC_ROWS), dim3(WG), 0, c->stream, d->cnt, g.W, d->rowtot);
     hipLaunchKernelGGL(dc_scan_misc_kernel, dim3(1), dim3(WG), 0, c->stream, d->rowtot, rowstart, d->wdec, g.W, d->wdecoff, d->meta, job, (u32)d->Dcap);
-    hipLaunchKernelGGL(dc_part_scatter_kernel<SIDES>, dim3(grid), dim3(WG), 0, c->stream, items, g, S, d->meta, d->cnt, rowstart,
-                       d->wdecoff, ignoreX, d->events[job], d->pos[job], d->doff[job]);
+    hipLaunchKernelGGL((dc_part_scatter_kernel<SIDES, SB>), dim3(grid), dim3(WG), 0, c->stream, items, g, S, d->meta, d->cnt, rowstart,
+                       d->wdecoff, ignoreX, d->events[job], d->pos[job], d->doff[job], d->esub[job]);
     prof_end(c);
 }
 
@@ -1367,6 +1492,41 @@ static void dc_note_block(bscgpu_ctx* c, const DevCoder* d)
     c->dc_replays = (int)d->hmeta[DM_REPLAYS];
     c->dc_avg_und = (int)d->hmeta[DM_AVG_UND];
     c->dc_hist_ext = (int)d->hmeta[DM_HIST_EXT];
+}
+
+// All chains of a block (or of a batched pass: tab) in one set of launches: E[job] events per family job, values to d->V[job].
+static int dc_eval_static(bscgpu_ctx* c, DevCoder* d, const u32* E, bool tab)
+{
+    DcEvalAll A;
+    A.wstart[0] = 0; A.cstart[0] = 0; A.sink = d->sink;
+    // One lane is one serial chain, so the walks are VALU-issue bound with ONE wavefront per SIMD (1024 of them); a few
+    // wavefronts more than that and some SIMDs get two, which doubles the kernel's time.  Chunks are therefore DC_EV events
+    // (what the brackets need to meet) or as many as it takes to stay at <= 1000 wavefronts (+ <= 4 of padding) per launch.
+    A.ev = eval_chunk_events((u64)E[0] + E[1] + E[2] + E[3]);
+    for (int job = 0; job < 4; ++job) {
+        const int fam = job == 0 ? FAM_STATIC : job == 1 ? FAM_CHAR : FAM_STATE;
+        A.job[job].events = d->events[job]; A.job[job].E = E[job]; A.job[job].rowstart = d->rowstart + (DC_ROWS + 8) * job;
+        A.job[job].fam = fam;
+        A.V[job] = d->V[job];
+        const u32 nch = (E[job] + A.ev - 1) / A.ev;
+        A.wstart[job + 1] = A.wstart[job] + (nch + 63) / 64;
+        A.cstart[job + 1] = A.cstart[job] + (nch + 63) / 64 * 64;           // chunk slots padded to whole wavefronts
+    }
+    if (A.cstart[4] > 4 * d->nch_cap) return ctx_fail(c, BSC_GPU_ERROR, "device coder: chunk table too small", hipSuccess);
+    prof_begin(c, BSCGPU_K_DC_EVAL, (u64)(E[0] + E[1] + E[2] + E[3]) * 6, (u64)E[0] + E[1] + E[2] + E[3]);
+    if (A.wstart[4] > 0) {
+        hipLaunchKernelGGL(dc_mark_rows_kernel, dim3((4 * DC_ROWS + WG - 1) / WG), dim3(WG), 0, c->stream, A);
+        if (tab) {                                                        // a batched pass: chain starts from the events' full sub-block ids
+            DcMarkAll K; u32 emax = 0;
+            for (int job = 0; job < 4; ++job) { K.events[job] = d->events[job]; K.esub[job] = d->esub[job]; K.E[job] = E[job]; if (E[job] > emax) emax = E[job]; }
+            hipLaunchKernelGGL(dc_mark_chains_kernel, dim3((emax + 8 * WG - 1) / (8 * WG), 4), dim3(WG), 0, c->stream, K, d->meta);
+        }
+        hipLaunchKernelGGL(dc_eval_wave_kernel<false>, dim3((A.wstart[4] + DC_EVAL_WAVES - 1) / DC_EVAL_WAVES), dim3(64 * DC_EVAL_WAVES), DC_EVAL_LDS, c->stream, A, d->mp, d->meta, d->elo, d->ehi, (const u16*)nullptr, d->cnt);
+        hipLaunchKernelGGL(dc_eval_b_kernel, dim3((A.cstart[4] + WG - 1) / WG), dim3(WG), 0, c->stream, A, d->mp, d->meta, d->elo, d->ehi, d->S);
+        hipLaunchKernelGGL(dc_eval_wave_kernel<true>, dim3((A.wstart[4] + DC_EVAL_WAVES - 1) / DC_EVAL_WAVES), dim3(64 * DC_EVAL_WAVES), DC_EVAL_LDS, c->stream, A, d->mp, d->meta, (u16*)nullptr, (u16*)nullptr, d->S, d->cnt + 3 * 4096);
+    }
+    prof_end(c);
+    return BSC_NO_ERROR;
 }
 
 // Probability stream of a whole block.  Inputs: the QLFC front end's run arrays on the device (sym / rank / start, m runs of
@@ -1407,10 +1567,10 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
     bool may_escape = false;
     for (int b = 0; b < nb; ++b) may_escape |= max_rank[b] > 4;
     if (may_escape)
-        hipLaunchKernelGGL(dc_avg_kernel, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta);
+        hipLaunchKernelGGL(dc_avg_kernel<DcSub>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta);
     else
         HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));
-    hipLaunchKernelGGL(dc_items_kernel, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, d->ge32, m, n, S, d->key_ch);
+    hipLaunchKernelGGL(dc_items_kernel<DcSub>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, d->ge32, m, n, S, d->key_ch);
     prof_end(c);
     RadixPass top; top.shift = 56; top.bits = 8;
     int in_alt = 0;
@@ -1418,9 +1578,9 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
     rc = radix_sort_passes(c, d->key_ch, d->key_ch_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_ch);
     if (rc < 0) return rc;
     prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
-    hipLaunchKernelGGL(dc_ctx_kernel, dim3(gm8), dim3(WG), 0, c->stream, d->key_ch, d->key_ch_s, d->inv_ch, m, S, d->tab_rank, d->tab_run,
+    hipLaunchKernelGGL(dc_ctx_kernel<DcSub>, dim3(gm8), dim3(WG), 0, c->stream, d->key_ch, d->key_ch_s, d->inv_ch, m, S, d->tab_rank, d->tab_run,
                        d->key_sr, d->key_sn, d->present, d->meta);
-    hipLaunchKernelGGL(dc_setup_kernel, dim3(1), dim3(WG), 0, c->stream, d->present, S, d->rounds, d->meta);
+    hipLaunchKernelGGL(dc_setup_kernel<DcSub>, dim3(1), dim3(WG), 0, c->stream, d->present, S, d->rounds, d->meta);
     prof_end(c);
     rc = radix_sort_passes(c, d->key_sr, d->key_sr_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_sr);
     if (rc < 0) return rc;
@@ -1447,32 +1607,8 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
     for (int job = 0; job < 4; ++job) E[job] = d->hmeta[DM_D0 + job];
     const u32 Efull = E[0];                                           // decisions of the block
     if (Efull != E[1] || Efull != E[2] + E[3]) return ctx_fail(c, BSC_GPU_ERROR, "device coder: decision counts of the families differ", hipSuccess);
-    {
-        DcEvalAll A;
-        A.wstart[0] = 0; A.cstart[0] = 0; A.sink = d->sink;
-        // One lane is one serial chain, so the walks are VALU-issue bound with ONE wavefront per SIMD (1024 of them); a few
-        // wavefronts more than that and some SIMDs get two, which doubles the kernel's time.  Chunks are therefore DC_EV events
-        // (what the brackets need to meet) or as many as it takes to stay at <= 1000 wavefronts (+ <= 4 of padding) per launch.
-        A.ev = eval_chunk_events((u64)E[0] + E[1] + E[2] + E[3]);
-        for (int job = 0; job < 4; ++job) {
-            const int fam = job == 0 ? FAM_STATIC : job == 1 ? FAM_CHAR : FAM_STATE;
-            A.job[job].events = d->events[job]; A.job[job].E = E[job]; A.job[job].rowstart = d->rowstart + (DC_ROWS + 8) * job;
-            A.job[job].fam = fam;
-            A.V[job] = d->V[job];
-            const u32 nch = (E[job] + A.ev - 1) / A.ev;
-            A.wstart[job + 1] = A.wstart[job] + (nch + 63) / 64;
-            A.cstart[job + 1] = A.cstart[job] + (nch + 63) / 64 * 64;           // chunk slots padded to whole wavefronts
-        }
-        if (A.cstart[4] > 4 * d->nch_cap) return ctx_fail(c, BSC_GPU_ERROR, "device coder: chunk table too small", hipSuccess);
-        prof_begin(c, BSCGPU_K_DC_EVAL, (u64)(E[0] + E[1] + E[2] + E[3]) * 6, (u64)E[0] + E[1] + E[2] + E[3]);
-        if (A.wstart[4] > 0) {
-            hipLaunchKernelGGL(dc_mark_rows_kernel, dim3((4 * DC_ROWS + WG - 1) / WG), dim3(WG), 0, c->stream, A);
-            hipLaunchKernelGGL(dc_eval_wave_kernel<false>, dim3((A.wstart[4] + DC_EVAL_WAVES - 1) / DC_EVAL_WAVES), dim3(64 * DC_EVAL_WAVES), DC_EVAL_LDS, c->stream, A, d->mp, d->meta, d->elo, d->ehi, (const u16*)nullptr, d->cnt);
-            hipLaunchKernelGGL(dc_eval_b_kernel, dim3((A.cstart[4] + WG - 1) / WG), dim3(WG), 0, c->stream, A, d->mp, d->meta, d->elo, d->ehi, d->S);
-            hipLaunchKernelGGL(dc_eval_wave_kernel<true>, dim3((A.wstart[4] + DC_EVAL_WAVES - 1) / DC_EVAL_WAVES), dim3(64 * DC_EVAL_WAVES), DC_EVAL_LDS, c->stream, A, d->mp, d->meta, (u16*)nullptr, (u16*)nullptr, d->S, d->cnt + 3 * 4096);
-        }
-        prof_end(c);
-    }
+    rc = dc_eval_static(c, d, E, false);
+    if (rc < 0) return rc;
 
     DcGather G;
     G.key_ch = d->key_ch; G.m = m; G.inv_ch = d->inv_ch; G.inv_sr = d->inv_sr; G.inv_sn = d->inv_sn;
@@ -1492,9 +1628,9 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
         if ((u64)pbase / 8u * 13u > 2ull * (u64)(d->Dcap + 64)) packed = false;        // (cannot happen: 13 / 8 of D + 8 x 64 decisions of padding against 2 D)
     }
     if (packed) {
-        hipLaunchKernelGGL((dc_pstream_kernel<false, true>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
+        hipLaunchKernelGGL((dc_pstream_kernel<false, true, DcSub>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
         hipLaunchKernelGGL(dc_p13_join_kernel, dim3((gm8 * WAVES + WG - 1) / WG), dim3(WG), 0, c->stream, d->frag, gm8 * WAVES, Q.out, d->meta);
-    } else hipLaunchKernelGGL((dc_pstream_kernel<false, false>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
+    } else hipLaunchKernelGGL((dc_pstream_kernel<false, false, DcSub>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1504,7 +1640,7 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
         // 64 consecutive runs with more decisions than a wavefront's staging buffer holds (runs of thousands): this block's stream in the 2-byte form
         packed = false;
         prof_begin(c, BSCGPU_K_DC_PSTREAM, (u64)Efull * 26, Efull);
-        hipLaunchKernelGGL((dc_pstream_kernel<false, false>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
+        hipLaunchKernelGGL((dc_pstream_kernel<false, false, DcSub>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
         prof_end(c);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, ctx_sync(c));
@@ -1530,6 +1666,114 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
     return BSC_NO_ERROR;
 }
 
+// ---- the model of a whole batched pass ------------------------------------------------------------------------------
+// What the wider chain identity needs on top of the arena, on the first pass that takes this route: every event's full sub-block
+// id (2 bytes per decision and family = 8 Dcap bytes, ~32 bytes per byte of max_n), max_rank and stream offset per sub-block.
+// Does not fit: the pass is declined (its blocks take the host model), not an error, and not retried per pass.
+static int devcoder_batch_ensure(bscgpu_ctx* c, DevCoder* d)
+{
+    if (d->batch_arena) return BSC_NO_ERROR;
+    if (d->batch_alloc_failed) return BSC_NOT_SUPPORTED;
+    CtxTimer tm("devcoder_batch_ensure (sub-block ids of the events)");
+    const size_t D = d->Dcap + 64;
+    struct Carve { void** p; size_t bytes; };
+    Carve carve[] = {
+        {(void**)&d->esub[0], 2 * D}, {(void**)&d->esub[1], 2 * D}, {(void**)&d->esub[2], 2 * D}, {(void**)&d->esub[3], 2 * D},
+        {(void**)&d->sub_maxr, (size_t)FRONT_MAX_SUB + 64}, {(void**)&d->poff_tab, 4 * ((size_t)FRONT_MAX_SUB + 64)},
+    };
+    size_t total = 0;
+    for (auto& cv : carve) total += dc_align(cv.bytes);
+    if (hipMalloc((void**)&d->batch_arena, total) != hipSuccess) {
+        (void)hipGetLastError(); d->batch_arena = nullptr; d->batch_alloc_failed = true;
+        return BSC_NOT_SUPPORTED;
+    }
+    d->batch_bytes = total;
+    size_t off = 0;
+    for (auto& cv : carve) { *cv.p = d->batch_arena + off; off += dc_align(cv.bytes); }
+    return BSC_NO_ERROR;
+}
+
+// Probability stream of a whole pass: the run arrays where qlfc_front_batch leaves them (vA / vB / SA: the buffers the single path
+// reads) and its table in front_tab -> every sub-block's entries back to back in stream order in the device p stream (buffer 0),
+// poff[0..nsub] in d->poff_tab.  The same four stages, the same kernels, instantiated for the table (DcSubTab); every guarded exit
+// keeps its meaning with the PASS as the unit: a raised flag declines the whole pass (BSC_NOT_SUPPORTED, c->dc_last_fail says why).
+// Two syncs: the families' sizes after the partition, the flags after the stream.
+int devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out)
+{
+    int rc = devcoder_ensure(c);
+    if (rc < 0) return rc;
+    DevCoder* d = c->dc;
+    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = 0;
+    c->dc_last_fail = m > d->Mcap ? (int)FAIL_CAP : 0;
+    if (m == 0 || m > d->Mcap || nsub < 1 || nsub > FRONT_MAX_SUB || !c->front_tab) return BSC_NOT_SUPPORTED;
+    rc = devcoder_batch_ensure(c, d);
+    if (rc < 0) return rc;
+    const FrontTab T = qlfc_front_tab(c, nsub);
+    const u8* dsym = reinterpret_cast<const u8*>(c->vA); const u8* drank = reinterpret_cast<const u8*>(c->vB); const u32* dstart = c->SA;
+    DcSubTab S; S.nsub = (u32)nsub; S.run = T.sub_run; S.off = T.sub_off; S.base = T.sub_base; S.maxr = d->sub_maxr;
+
+    HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d->present, 0, (size_t)DC_KIND_WORDS * 4, c->stream));
+    const u32 gm = (m + WG - 1) / WG;
+    const u32 gm8 = (gm + 7u) / 8u * 8u;            // kernels that use dc_virtual_block()
+    prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
+    hipLaunchKernelGGL(dc_tab_prep_kernel, dim3(((u32)nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, T.first_run, (u32)nsub, m, d->sub_maxr, T.sub_run);
+    // (always: which sub-blocks can escape is not known on the host here; one of at most 32 symbols never leaves a flag open — avg_top)
+    hipLaunchKernelGGL(dc_avg_kernel<DcSubTab>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta);
+    hipLaunchKernelGGL(dc_items_kernel<DcSubTab>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, d->ge32, m, 0u, S, d->key_ch);
+    prof_end(c);
+    RadixPass top; top.shift = 56; top.bits = 8;
+    int in_alt = 0;
+    rc = radix_sort_passes(c, d->key_ch, d->key_ch_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_ch);
+    if (rc < 0) return rc;
+    prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
+    hipLaunchKernelGGL(dc_ctx_kernel<DcSubTab>, dim3(gm8), dim3(WG), 0, c->stream, d->key_ch, d->key_ch_s, d->inv_ch, m, S, d->tab_rank, d->tab_run,
+                       d->key_sr, d->key_sn, d->present, d->meta);
+    hipLaunchKernelGGL(dc_setup_kernel<DcSubTab>, dim3(1), dim3(WG), 0, c->stream, d->present, S, d->rounds, d->meta);
+    prof_end(c);
+    rc = radix_sort_passes(c, d->key_sr, d->key_sr_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_sr);
+    if (rc < 0) return rc;
+    rc = radix_sort_passes(c, d->key_sn, d->key_sn_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_sn);
+    if (rc < 0) return rc;
+    dc_launch_partition<3>(c, d, d->key_ch, m, S, 0, 1u);
+    dc_launch_partition<3>(c, d, d->key_ch_s, m, S, 1, 0u);
+    dc_launch_partition<1>(c, d, d->key_sr_s, m, S, 2, 0u);
+    dc_launch_partition<2>(c, d, d->key_sn_s, m, S, 3, 0u);
+    hipLaunchKernelGGL(dc_poff_tab_kernel, dim3(((u32)nsub + 1 + WG - 1) / WG), dim3(WG), 0, c->stream, d->doff[0], S, d->poff_tab);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    prof_collect(c);
+    if (d->hmeta[DM_FAIL] != 0) { dc_note_block(c, d); return BSC_NOT_SUPPORTED; }
+    u32 E[4];
+    for (int job = 0; job < 4; ++job) E[job] = d->hmeta[DM_D0 + job];
+    const u32 Efull = E[0];
+    if (Efull != E[1] || Efull != E[2] + E[3]) return ctx_fail(c, BSC_GPU_ERROR, "device coder: decision counts of the families differ", hipSuccess);
+    rc = dc_eval_static(c, d, E, true);
+    if (rc < 0) return rc;
+
+    DcGather G;
+    G.key_ch = d->key_ch; G.m = m; G.inv_ch = d->inv_ch; G.inv_sr = d->inv_sr; G.inv_sn = d->inv_sn;
+    G.doff_sp = d->doff[0]; G.doff_ch = d->doff[1]; G.doff_sr = d->doff[2]; G.doff_sn = d->doff[3];
+    G.pos_sp = d->pos[0]; G.pos_ch = d->pos[1]; G.pos_sr = d->pos[2]; G.pos_sn = d->pos[3];
+    G.V_sp = d->V[0]; G.V_ch = d->V[1]; G.V_sr = d->V[2]; G.V_sn = d->V[3];
+    prof_begin(c, BSCGPU_K_DC_PSTREAM, (u64)Efull * 26, Efull);
+    if (c->ps_guard[0]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ps_guard[0], 0));     // the buffer's previous copy-out (a single-path block)
+    for (int b = 0; b < 8; ++b) if (c->ps_guard_sig[0][b]) (void)dma_wait(c->ps_guard_sig[0][b]);
+    hipLaunchKernelGGL((dc_pstream_kernel<false, false, DcSubTab>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[0], (u16*)nullptr, Efull, DcP13{});
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    prof_collect(c);
+    dc_note_block(c, d);
+    if (d->hmeta[DM_FAIL] != 0) return BSC_NOT_SUPPORTED;
+    if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder batch] sub-blocks %d, decisions %u, types %u, chunks replayed %u\n", nsub, Efull, d->hmeta[DM_NTYPES], d->hmeta[DM_REPLAYS]);
+    *D_out = Efull;
+    return BSC_NO_ERROR;
+}
+const u32* devcoder_batch_poff_ptr(const bscgpu_ctx* c) { return c->dc ? c->dc->poff_tab : nullptr; }
+
 static int devcoder_pstream_fast(bscgpu_ctx* c, DevCoder* d, const u8* dsym, const u8* drank, const u32* dstart, u32 m, u32 n, int nb,
                                  const u32* run_first, u32* D_out, u32* poff_out, int psbuf)
 {
@@ -1541,7 +1785,7 @@ static int devcoder_pstream_fast(bscgpu_ctx* c, DevCoder* d, const u8* dsym, con
     const u32 gm8 = (gm + 7u) / 8u * 8u;
     prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 14, m);
     HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));              // no escape coding in this coder
-    hipLaunchKernelGGL(dc_items_kernel, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, d->ge32, m, n, S, d->key_ch);
+    hipLaunchKernelGGL(dc_items_kernel<DcSub>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, d->ge32, m, n, S, d->key_ch);
     prof_end(c);
     RadixPass top; top.shift = 56; top.bits = 8;
     int in_alt = 0;
@@ -1552,7 +1796,7 @@ static int devcoder_pstream_fast(bscgpu_ctx* c, DevCoder* d, const u8* dsym, con
         const DcGeom g = dc_geom(m);
         const u32 grid = (g.W + WAVES - 1) / WAVES;
         prof_begin(c, BSCGPU_K_DC_PART, (u64)m * 8, m);
-        hipLaunchKernelGGL(dc_part_count_kernel<3>, dim3(grid), dim3(WG), 0, c->stream, d->key_ch, g, S, d->rowbins, d->cnt, d->wdec);
+        hipLaunchKernelGGL((dc_part_count_kernel<3, DcSub>), dim3(grid), dim3(WG), 0, c->stream, d->key_ch, g, S, d->rowbins, d->cnt, d->wdec);
         hipLaunchKernelGGL(dc_scan_rows_kernel, dim3(DC_ROWS), dim3(WG), 0, c->stream, d->cnt, g.W, d->rowtot);
         hipLaunchKernelGGL(dc_scan_misc_kernel, dim3(1), dim3(WG), 0, c->stream, d->rowtot, d->rowstart, d->wdec, g.W, d->wdecoff, d->meta, 0, (u32)d->Dcap);
         hipLaunchKernelGGL(dc_doff_kernel<3>, dim3(grid), dim3(WG), 0, c->stream, d->key_ch, g, S, d->meta, d->wdecoff, d->doff[0]);
@@ -1597,7 +1841,7 @@ static int devcoder_pstream_fast(bscgpu_ctx* c, DevCoder* d, const u8* dsym, con
     prof_begin(c, BSCGPU_K_DC_PSTREAM, (u64)E * 10, E);
     if (c->ps_guard[psbuf & 1]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ps_guard[psbuf & 1], 0));     // the buffer's previous copy-out
     for (int b = 0; b < 8; ++b) if (c->ps_guard_sig[psbuf & 1][b]) (void)dma_wait(c->ps_guard_sig[psbuf & 1][b]);   // ... when it went through the DMA engine directly (two blocks ago: long landed)
-    hipLaunchKernelGGL((dc_pstream_kernel<true, false>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp_fast, d->meta, d->ps[psbuf & 1], (u16*)nullptr, E, DcP13{});
+    hipLaunchKernelGGL((dc_pstream_kernel<true, false, DcSub>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp_fast, d->meta, d->ps[psbuf & 1], (u16*)nullptr, E, DcP13{});
     hipLaunchKernelGGL(dc_poff_kernel, dim3(1), dim3(16), 0, c->stream, d->doff[0], S, m, d->poff);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());

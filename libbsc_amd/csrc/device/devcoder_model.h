@@ -84,6 +84,22 @@ DC_HD Item item_unpack(uint64_t k)
     return it;
 }
 DC_HD uint32_t item_X(uint64_t k) { return (uint32_t)(k >> 56); }
+// packed item of a batched pass (up to 8192 sub-blocks, every block below 1 MiB):
+//   [63:56] X | [55:43] sub-block | [42] avg_rank >= 32 | [41:34] rank | [33:31] max_rank of the sub-block | [30:10] run length
+// The sub-block sits directly below X, as in the eight-entry form: "same chain" stays one shift (ITEMB_CHAIN_SHIFT) and one compare.
+struct ItemB : Item { uint32_t maxr; };
+constexpr int ITEM_CHAIN_SHIFT = 53, ITEMB_CHAIN_SHIFT = 43, ITEMB_SUB_BITS = 13, ITEMB_RUN_BITS = 21;
+DC_HD uint64_t item_pack_b(uint32_t X, uint32_t sb, uint32_t ge32, uint32_t rank, uint32_t maxr, uint32_t run)
+{
+    return ((uint64_t)X << 56) | ((uint64_t)sb << 43) | ((uint64_t)ge32 << 42) | ((uint64_t)rank << 34) | ((uint64_t)maxr << 31) | ((uint64_t)run << 10);
+}
+DC_HD ItemB item_unpack_b(uint64_t k)
+{
+    ItemB it;
+    it.sb = (uint32_t)(k >> 43) & 0x1fffu; it.ge32 = (uint32_t)(k >> 42) & 1u; it.rank = (uint32_t)(k >> 34) & 0xffu;
+    it.maxr = (uint32_t)(k >> 31) & 7u; it.run = (uint32_t)(k >> 10) & 0x1fffffu;
+    return it;
+}
 
 // number of decisions on each side (qlfc.cpp:904-975 / :990-1060)
 DC_HD int count_rank_side(const Item& it, int max_rank)

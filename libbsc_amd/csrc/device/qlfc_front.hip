@@ -701,6 +701,13 @@ size_t front_scratch_bytes(int64_t max_n)
     return (flags > table ? flags : table) + 4096;
 }
 
+FrontTab qlfc_front_tab(const bscgpu_ctx* c, int nsub)
+{
+    FrontTab t;
+    t.sub_off = c->front_tab + FT_OFF; t.sub_base = c->front_tab + FT_OFF + nsub + 1; t.sub_run = c->front_tab + FT_RUN; t.first_run = c->front_tab + FT_FIRST;
+    return t;
+}
+
 void qlfc_front_first_seen(const u32* first_run, u8* first_seen, int* nsym)
 {
     // alphabet in order of first appearance = symbols sorted by the index of their first run (as block.cpp: host_prepare)

@@ -1622,15 +1622,24 @@ static int store_from_device(bscgpu_ctx* c, const unsigned char* dIn, unsigned c
     return n + LIBBSC_HEADER_SIZE;
 }
 
+// a model pass's sub-blocks as the device's range coder left them (BSCGPU_OPT_DEVICE_RC; see front_batch_code_rc)
+struct PassCoded { const uint8_t* bytes; const uint32_t* off; const int* res; const int* room; };
+static int front_batch_code_rc(const bscgpu_front_layout* Lo, int block, const uint8_t* bytes, const uint32_t* off, const int* res, const int* room_of,
+                               unsigned char* out, int features);
+
 // the host tail of bsc_compress (libbsc.cpp:296-336) for one block of a sorted pass; input: host bytes, or dIn in HBM
 // (lay != nullptr: the block is entry li of a pass's front-end layout and is coded from its run arrays; else from its L at Lb)
 static int code_sorted_block(bscgpu_ctx* c, const unsigned char* input, const unsigned char* dIn, unsigned char* output, int n,
                              const BatchBlock& B, const unsigned char* Lb, int coder, int features,
-                             const bscgpu_front_layout* lay = nullptr, int li = 0)
+                             const bscgpu_front_layout* lay = nullptr, int li = 0, const uint16_t* ps = nullptr, const uint32_t* poff = nullptr,
+                             const struct PassCoded* pc = nullptr)
 {
     unsigned char* buffer = (unsigned char*)bsc_malloc((size_t)B.lz + 4096);
     if (!buffer) return LIBBSC_NOT_ENOUGH_MEMORY;
-    int result = lay ? bscgpu_front_batch_code(lay, li, buffer, coder, features) : coder_compress(Lb, buffer, B.lz, coder, features);
+    // (ps: the pass's probability stream from the device model — the static coder's range coder alone)
+    int result = lay ? (pc ? front_batch_code_rc(lay, li, pc->bytes, pc->off, pc->res, pc->room, buffer, features)
+                           : ps ? bscgpu_front_batch_code_ps(lay, li, ps, poff, buffer, features) : bscgpu_front_batch_code(lay, li, buffer, coder, features))
+                     : coder_compress(Lb, buffer, B.lz, coder, features);
     if (result >= LIBBSC_NO_ERROR) memcpy(output + LIBBSC_HEADER_SIZE, buffer, (size_t)result);
     bsc_free(buffer);
     const int num = n < 64 * 1024 ? 0 : B.num_indexes;
@@ -1726,6 +1735,77 @@ extern "C" BSCGPU_API int bscgpu_front_batch_code(const bscgpu_front_layout* Lo,
     return coder_compress_views(views, nb, Lo->sub_start + s0, Lo->sub_size + s0, Lo->sizes[block], out, coder, features, fetch);
 }
 
+namespace {
+struct RunsFetch : RawFetch {                                       // a sub-block stored raw is rebuilt from its runs
+    const RunView* views; const int* st; const int* sz; int nb;
+    int operator()(int start, int size, uint8_t* dst) override
+    {
+        for (int q = 0; q < nb; ++q) if (st[q] == start && sz[q] == size) { expand_runs(views[q], start, dst); return 0; }
+        return LIBBSC_BAD_PARAMETER;
+    }
+};
+}
+
+extern "C" BSCGPU_API int64_t bscgpu_static_pstream_host(const bscgpu_front_layout* Lo, int s, uint16_t* out, int64_t cap)
+{
+    if (!Lo || s < 0 || s >= Lo->nsub || cap < 0 || (cap > 0 && !out)) return LIBBSC_BAD_PARAMETER;
+    RunView V;
+    V.sym = Lo->sym + Lo->sub_run[s]; V.rank = Lo->rank + Lo->sub_run[s]; V.start = Lo->start + Lo->sub_run[s];
+    V.count = Lo->sub_run[s + 1] - Lo->sub_run[s];
+    V.end = (uint32_t)(Lo->sub_start[s] + Lo->sub_size[s]);
+    V.nsym = Lo->nsym[s];
+    memcpy(V.first_seen, Lo->first_seen + 256 * (size_t)s, (size_t)V.nsym);
+    return qlfc_static_pstream_runs(V, out, cap);
+}
+
+extern "C" BSCGPU_API int bscgpu_front_batch_code_ps(const bscgpu_front_layout* Lo, int block, const uint16_t* ps, const uint32_t* poff,
+                                                     unsigned char* out, int features)
+{
+    if (!Lo || !out || !ps || !poff || block < 0 || block >= Lo->count) return LIBBSC_BAD_PARAMETER;
+    const int s0 = Lo->blk_sub[block], nb = Lo->blk_sub[block + 1] - s0;
+    if (nb < 1 || nb > 8) return LIBBSC_BAD_PARAMETER;
+    RunView views[8];
+    front_views(Lo, block, views);
+    RunsFetch fetch;
+    fetch.views = views; fetch.st = Lo->sub_start + s0; fetch.sz = Lo->sub_size + s0; fetch.nb = nb;
+    struct FromStream : SubEncode {                                 // the range coder alone: the model ran on the GPU
+        const bscgpu_front_layout* Lo; int s0; const uint16_t* ps; const uint32_t* poff;
+        int operator()(int b, uint8_t* dst, int room) override
+        {
+            const int s = s0 + b;
+            return qlfc_encode_static_pstream(Lo->first_seen + 256 * (size_t)s, Lo->nsym[s], Lo->sub_size[s], ps + poff[s], (size_t)(poff[s + 1] - poff[s]), dst, room);
+        }
+    } enc;
+    enc.Lo = Lo; enc.s0 = s0; enc.ps = ps; enc.poff = poff;
+    return coder_compress_views(views, nb, Lo->sub_start + s0, Lo->sub_size + s0, Lo->sizes[block], out, LIBBSC_CODER_QLFC_STATIC, features, fetch, &enc);
+}
+
+// bscgpu_front_batch_code_ps with the range coder's work already done on the device: the framing alone.  A sub-block whose budget
+// under the caller's framing rule is not the one the device coded it with (the serial rule behind a sub-block stored raw) goes through
+// the host model from its runs; one that ended LIBBSC_NOT_COMPRESSIBLE is stored raw, rebuilt from its runs.
+static int front_batch_code_rc(const bscgpu_front_layout* Lo, int block, const uint8_t* bytes, const uint32_t* off, const int* res, const int* room_of,
+                               unsigned char* out, int features)
+{
+    const int s0 = Lo->blk_sub[block], nb = Lo->blk_sub[block + 1] - s0;
+    if (nb < 1 || nb > 8) return LIBBSC_BAD_PARAMETER;
+    RunView views[8];
+    front_views(Lo, block, views);
+    RunsFetch fetch;
+    fetch.views = views; fetch.st = Lo->sub_start + s0; fetch.sz = Lo->sub_size + s0; fetch.nb = nb;
+    struct Coded : SubEncode {
+        const bscgpu_front_layout* Lo; const RunView* views; int s0; const uint8_t* bytes; const uint32_t* off; const int* res; const int* room_of;
+        int operator()(int b, uint8_t* dst, int room) override
+        {
+            const int s = s0 + b;
+            if (room != room_of[s]) return qlfc_encode_runs(views[b], Lo->sub_size[s], dst, room, LIBBSC_CODER_QLFC_STATIC);
+            if (res[s] >= 0) memcpy(dst, bytes + off[s], (size_t)res[s]);
+            return res[s];
+        }
+    } enc;
+    enc.Lo = Lo; enc.views = views; enc.s0 = s0; enc.bytes = bytes; enc.off = off; enc.res = res; enc.room_of = room_of;
+    return coder_compress_views(views, nb, Lo->sub_start + s0, Lo->sub_size + s0, Lo->sizes[block], out, LIBBSC_CODER_QLFC_STATIC, features, fetch, &enc);
+}
+
 extern "C" BSCGPU_API int bscgpu_qlfc_front_batch_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out)
 {
     if (!c) return LIBBSC_BAD_PARAMETER;
@@ -1745,6 +1825,27 @@ extern "C" BSCGPU_API int bscgpu_qlfc_front_batch_device(bscgpu_ctx* c, const vo
     return LIBBSC_NO_ERROR;
 }
 
+extern "C" BSCGPU_API int64_t bscgpu_static_pstream_batch_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out,
+                                                                 uint16_t* ps, int64_t cap, uint32_t* poff)
+{
+    if (!c || !poff || cap < 0 || (cap > 0 && !ps)) return LIBBSC_BAD_PARAMETER;
+    const int frc = bscgpu_qlfc_front_batch_device(c, dL, sizes, count, out);
+    if (frc < 0) return frc;
+    poff[0] = 0;
+    if (out->nsub == 0) return 0;
+    u32 D = 0;
+    const int rc = devcoder_pstream_batch(c, (u32)out->m, out->nsub, &D);
+    if (rc == LIBBSC_NOT_SUPPORTED) {
+        char buf[96]; snprintf(buf, sizeof buf, "device coder declined the pass (reason mask %d)", c->dc_last_fail);
+        c->err = buf;
+    }
+    if (rc < 0) return rc;
+    if (hipMemcpyAsync(poff, devcoder_batch_poff_ptr(c), ((size_t)out->nsub + 1) * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return LIBBSC_GPU_ERROR;
+    if ((int64_t)D <= cap && D > 0 && hipMemcpyAsync(ps, devcoder_pstream_ptr(c, 0), (size_t)D * 2, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return LIBBSC_GPU_ERROR;
+    if (ctx_sync(c) != hipSuccess) return LIBBSC_GPU_ERROR;
+    return (int64_t)D;
+}
+
 namespace {
 // a pass's layout inside compress_batch_impl: the small arrays here, sym / rank / start and the first-run table in a pinned buffer
 struct PassLayout {
@@ -1754,6 +1855,13 @@ struct PassLayout {
     std::vector<uint8_t> first_seen;
     const uint32_t* first_run = nullptr;
     bool used = false;
+    const uint16_t* ps = nullptr;      // the device model's stream of the pass (BSCGPU_OPT_BATCH_MODEL), sub-block s at poff[s]; null: host model
+    std::vector<uint32_t> poff;
+    // ... or, with BSCGPU_OPT_DEVICE_RC, the sub-blocks' coded bytes from the device's range coder: sub-block s's rc_res[s] bytes (or
+    // LIBBSC_NOT_COMPRESSIBLE) at rc_bytes + rc_off[s], coded with an output budget of rc_room[s]
+    const uint8_t* rc_bytes = nullptr;
+    std::vector<uint32_t> rc_off;
+    std::vector<int> rc_res, rc_room;
     void bind(const std::vector<int>& psz, uint8_t* pinned, size_t N)
     {
         const size_t cnt = psz.size();
@@ -1770,6 +1878,57 @@ struct PassLayout {
 }
 
 int bschost::coder_threads() { return default_coder_threads(); }
+
+// Smallest pass (bytes of L) that is given to the device model: below it the model's fixed cost (about a hundred launches, three
+// syncs, the stream's copy) is more than the host spends on the pass's model.  Measured ("The static coder's model of a
+// pass": tools/batch_bench.py --model-sweep): a call of one pass loses up to 8 MiB and wins from 16 MiB.
+// BSC_BATCH_MODEL_MIN_PASS in the environment overrides it (read per call: the sweep and the tests run with 0).
+constexpr int64_t BATCH_MODEL_MIN_PASS_DEFAULT = 16 << 20;
+static int64_t batch_model_min_pass()
+{
+    const char* e = getenv("BSC_BATCH_MODEL_MIN_PASS");
+    return e ? (int64_t)atoll(e) : BATCH_MODEL_MIN_PASS_DEFAULT;
+}
+
+// BSCGPU_OPT_DEVICE_RC for a model pass: every sub-block stream of the pass through ONE launch of the device's range coder
+// (rangecoder.hip), eight streams per wavefront (DESIGN §3.8's table: the best shape for thousands of short streams), straight from
+// the device's p stream.  Prefixes (header word, alphabet) come from bscgpu_rc_prefix per sub-block; the output regions lie in the
+// sorter's first key buffer, dead until the next pass's sort (8 max_n bytes; the regions take n + 128 nsub at most); only the regions
+// and res[] come down.  A sub-block is coded with the budget both framing rules give it when nothing in front of it was stored raw:
+// its size, or n - 1 for a block of one sub-block.
+static int device_rc_pass(bscgpu_ctx* c, PassLayout& PL, uint8_t* host_bytes, size_t host_cap)
+{
+    const bscgpu_front_layout& Y = PL.lay;
+    const int nsub = Y.nsub;
+    std::vector<uint32_t> prefix;
+    std::vector<bscgpu_rc_stream> S((size_t)nsub);
+    PL.rc_off.assign((size_t)nsub, 0); PL.rc_res.assign((size_t)nsub, 0); PL.rc_room.assign((size_t)nsub, 0);
+    uint32_t off = 0;
+    for (int b = 0; b < Y.count; ++b) {
+        const int s0 = Y.blk_sub[b], nb = Y.blk_sub[b + 1] - s0;
+        for (int s = s0; s < s0 + nb; ++s) {
+            qlfc_front_first_seen(PL.first_run + 256 * (size_t)s, Y.first_seen + 256 * (size_t)s, &Y.nsym[s]);
+            const size_t at = prefix.size();
+            prefix.resize(at + BSCGPU_RC_PREFIX_MAX);
+            const int np = bscgpu_rc_prefix(Y.first_seen + 256 * (size_t)s, Y.nsym[s], Y.sub_size[s], LIBBSC_CODER_QLFC_STATIC, prefix.data() + at, BSCGPU_RC_PREFIX_MAX);
+            if (np < 0) return np;
+            prefix.resize(at + (size_t)np);
+            PL.rc_room[s] = nb == 1 ? Y.sub_size[s] - 1 : Y.sub_size[s];
+            S[s].body = (int64_t)PL.poff[s]; S[s].count = PL.poff[s + 1] - PL.poff[s];
+            S[s].prefix = (uint32_t)at; S[s].nprefix = (uint32_t)np;
+            S[s].out_off = off; S[s].out_size = (uint32_t)PL.rc_room[s];
+            PL.rc_off[s] = off;
+            off += ((uint32_t)Y.sub_size[s] + 64u + 63u) & ~63u;
+        }
+    }
+    if ((size_t)off > (size_t)8 * (size_t)c->max_n || (size_t)off > host_cap) return LIBBSC_NOT_SUPPORTED;
+    uint8_t* dOut = reinterpret_cast<uint8_t*>(c->kA);
+    const int rc = rc_encode_device(c, BSCGPU_RC_STATIC16, devcoder_pstream_ptr(c, 0), prefix.data(), (int)prefix.size(), S.data(), nsub, dOut, PL.rc_res.data(), 8);
+    if (rc < 0) return rc;
+    if (hipMemcpyAsync(host_bytes, dOut, (size_t)off, hipMemcpyDeviceToHost, c->stream) != hipSuccess || ctx_sync(c) != hipSuccess) return LIBBSC_GPU_ERROR;
+    PL.rc_bytes = host_bytes;
+    return LIBBSC_NO_ERROR;
+}
 
 // One implementation for both entry points: host input (`input`, LZP per block) or input in HBM (`dInput`, no LZP).
 static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const unsigned char* dInput, const int* sizes, int count,
@@ -1797,6 +1956,10 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
             }
     // the front end of every pass on the GPU (BSCGPU_OPT_BATCH_FRONT): needs the two pinned run buffers; without them today's route
     const bool front = npass > 0 && c->batch_front != 0 && ctx_ensure_front_host(c) == LIBBSC_NO_ERROR;
+    // ... and the static coder's model behind it (BSCGPU_OPT_BATCH_MODEL); its two pinned stream buffers are allocated by the first pass
+    // that qualifies, and without them the passes keep the host model
+    const bool model = front && c->batch_model != 0 && coder == LIBBSC_CODER_QLFC_STATIC;
+    const int64_t model_min_pass = batch_model_min_pass();
     const size_t frontN = ((size_t)c->max_n + 4096 + 4095) / 4096 * 4096;
     std::vector<PassLayout> lays(2);
     const int threads = default_coder_threads();
@@ -1868,6 +2031,29 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
                 rc = qlfc_front_batch(c, c->dL, PL.sizes.data(), e - b, &PL.lay, c->front_host[p & 1] + 6 * frontN);
                 if (rc < 0) break;
                 PL.used = true; ++c->cnt_front_passes;
+                PL.ps = nullptr; PL.rc_bytes = nullptr;
+                if (model && PL.lay.nsub > 0 && pos >= model_min_pass && ctx_ensure_model_host(c) == LIBBSC_NO_ERROR) {
+                    // the model behind the front end, on the same stream, before the next pass's sort; the run arrays came down all the
+                    // same: they serve a declined pass, a sub-block stored raw and the <= 28-byte blocks that rode along
+                    u32 D = 0;
+                    const int mrc = devcoder_pstream_batch(c, (u32)PL.lay.m, PL.lay.nsub, &D);
+                    if (mrc == LIBBSC_NOT_SUPPORTED) ++c->cnt_model_declined;
+                    else if (mrc < 0) { rc = mrc; break; }
+                    else if ((size_t)D <= c->model_host_entries) {
+                        PL.poff.resize((size_t)PL.lay.nsub + 1);
+                        u16* hps = c->model_host[p & 1];     // free: as hb is
+                        const bool drc = c->device_rc != 0;  // the streams stay in HBM: one launch of the device's range coder codes them
+                        if (hipMemcpyAsync(PL.poff.data(), devcoder_batch_poff_ptr(c), PL.poff.size() * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                            (!drc && D > 0 && hipMemcpyAsync(hps, devcoder_pstream_ptr(c, 0), (size_t)D * 2, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+                            ctx_sync(c) != hipSuccess) { rc = LIBBSC_GPU_ERROR; break; }
+                        if (drc) {
+                            rc = device_rc_pass(c, PL, reinterpret_cast<uint8_t*>(hps), c->model_host_entries * 2);
+                            if (rc < 0) break;
+                            ++c->cnt_device_rc;
+                        } else PL.ps = hps;
+                        ++c->cnt_model_passes;
+                    }
+                }
             } else {
                 if (hipMemcpyAsync(hb, c->dL, (size_t)pos, hipMemcpyDeviceToHost, c->stream) != hipSuccess || ctx_sync(c) != hipSuccess) { rc = LIBBSC_GPU_ERROR; break; }
                 ++c->cnt_l_passes;
@@ -1886,6 +2072,7 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
         }
         if (coder_thread.joinable()) coder_thread.join();
         auto code_pass = [c, &blocks, &PL, hb, at, dev, &in_of, &din_of, &out_of, results, sizes, coder, features, threads] {
+            const PassCoded coded{PL.rc_bytes, PL.rc_off.data(), PL.rc_res.data(), PL.rc_room.data()};
             run_bounded((int)blocks.size(), threads, [&](int i) {
                 const BatchBlock& B = blocks[i];
                 if (PL.used && (B.store || B.sorted)) {
@@ -1899,7 +2086,7 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
                         if (sizes[B.b] > 0) expand_runs(V[0], 0, tmp);
                         results[B.b] = bsc_store(tmp, out_of(B.b), sizes[B.b], features);
                     } else results[B.b] = code_sorted_block(c, dev ? nullptr : in_of(B.b), dev ? din_of(B.b) : nullptr, out_of(B.b), sizes[B.b],
-                                                            B, nullptr, coder, features, &Y, i);
+                                                            B, nullptr, coder, features, &Y, i, PL.ps, PL.poff.data(), PL.rc_bytes ? &coded : nullptr);
                     return;
                 }
                 if (B.store) results[B.b] = bsc_store(hb + at[i], out_of(B.b), sizes[B.b], features);

@@ -113,11 +113,14 @@ static int compress_parallel(const uint8_t* in, uint8_t* out, int n, int coder)
 }
 
 int coder_compress_views(const RunView* views, int nblocks, const int* start, const int* size, int n,
-                         uint8_t* out, int coder, int features, RawFetch& fetch_raw)
+                         uint8_t* out, int coder, int features, RawFetch& fetch_raw, SubEncode* encode_sub)
 {
     if (coder != CODER_STATIC && coder != CODER_ADAPTIVE && coder != CODER_FAST) return BAD_PARAMETER;
+    auto encode = [&](int b, int in_size, uint8_t* dst, int room) {
+        return encode_sub ? (*encode_sub)(b, dst, room) : qlfc_encode_runs(views[b], in_size, dst, room, coder);
+    };
     if (nblocks == 1) {
-        const int r = qlfc_encode_runs(views[0], n, out + 1, n - 1, coder);
+        const int r = encode(0, n, out + 1, n - 1);
         if (r < 0) return r;
         out[0] = 1;
         return r + 1;
@@ -130,7 +133,7 @@ int coder_compress_views(const RunView* views, int nblocks, const int* start, co
         run_tasks(nblocks, [&](int b) {
             const auto t0 = std::chrono::steady_clock::now();
             scratch[(size_t)b].reset(new uint8_t[(size_t)size[b] + 64]);        // uninitialised on purpose
-            int r = qlfc_encode_runs(views[b], size[b], scratch[(size_t)b].get(), size[b], coder);
+            int r = encode(b, size[b], scratch[(size_t)b].get(), size[b]);
             res[b] = (r < 0) ? size[b] : r;
             tms[b] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         });
@@ -152,7 +155,7 @@ int coder_compress_views(const RunView* views, int nblocks, const int* start, co
     for (int b = 0; b < nblocks; ++b) {
         int room = size[b];
         if (room > n - optr) room = n - optr;
-        int r = qlfc_encode_runs(views[b], size[b], out + optr, room, coder);
+        int r = encode(b, size[b], out + optr, room);
         if (r < 0) {
             if (optr + size[b] >= n) return NOT_COMPRESSIBLE;
             r = size[b];

@@ -876,6 +876,35 @@ int qlfc_encode_static_pstream(const uint8_t* first_seen, int nsym, int in_size,
     return rc.finish();
 }
 
+// The device model's CPU stand-in: the host model's own walk with a policy that records what the range coder would have been given —
+// {[11:0] p, [12] bit, [13] first decision of a run}, the entries devcoder.hip writes — instead of coding it.  Returns the number of
+// decisions; entries past cap are counted, not written.
+namespace {
+struct RecordPolicy {
+    uint16_t* out; int64_t cap; int64_t n = 0; unsigned first = 0;
+    struct Live {};
+    inline bool begin_run() { first = 1u << 13; return true; }
+    inline Live enter() { return Live(); }
+    inline void leave(const Live&) {}
+    template <int CLS> BSC_ALWAYS_INLINE void decide(Live&, unsigned bit, short& st, short& ch, short& sp, Mixer*)
+    {
+        const int p = static_step<CLS>(bit, st, ch, sp);
+        if (n < cap) out[n] = (uint16_t)((unsigned)p | (bit << 12) | first);
+        ++n; first = 0;
+    }
+};
+}
+int64_t qlfc_static_pstream_runs(const RunView& R, uint16_t* out, int64_t cap)
+{
+    if (R.nsym <= 0) return BAD_PARAMETER;
+    const QlfcTables& T = qlfc_tables();
+    Counters1* Cn = tl_counters();
+    const int max_rank = encode_alphabet(R, [](unsigned) {});
+    RecordPolicy pol{out, cap};
+    (void)walk_model1<false>(R, T, max_rank, *Cn, nullptr, pol);
+    return pol.n;
+}
+
 void qlfc_encode_static_pstream_pair(const PstreamJob& A, const PstreamJob& B, int* resA, int* resB)
 {
     RunView HA, HB;

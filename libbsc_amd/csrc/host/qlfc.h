@@ -62,6 +62,9 @@ int qlfc_encode_runs(const RunView& R, int in_size, uint8_t* out, int out_size, 
 // Static coder (-e1) from a precomputed probability stream (devcoder_model.h: [11:0] p, [12] bit, [13] run start): header,
 // alphabet and range coding only — the model ran on the GPU.  Returns bytes written or NOT_COMPRESSIBLE.
 int qlfc_encode_static_pstream(const uint8_t* first_seen, int nsym, int in_size, const uint16_t* ps, size_t count, uint8_t* out, int out_size);
+// The static model's probability stream of one sub-block on the CPU (the device model's stand-in: the host model's walk, recording
+// instead of coding): entries as above to out[0 .. cap); returns the number of decisions (those past cap are counted only).
+int64_t qlfc_static_pstream_runs(const RunView& R, uint16_t* out, int64_t cap);
 // Two independent sub-blocks coded in one loop: the range coder's recurrence (range -> shift -> multiply -> select) is latency
 // bound, two chains in flight nearly double a core's rate (1.9 -> 1.1 ns per decision on an EPYC 9575F).  res[k] as above.
 struct PstreamJob { const uint8_t* first_seen; int nsym; int in_size; const uint16_t* ps; size_t count; uint8_t* out; int out_size; };
@@ -98,8 +101,11 @@ int coder_num_blocks(int n);
 // Same framing, but the sub-blocks arrive as run arrays (GPU front end).  fetch_raw(start, size, dst) supplies the
 // original bytes of a sub-block that has to be stored raw.
 struct RawFetch { virtual int operator()(int start, int size, uint8_t* dst) = 0; virtual ~RawFetch() {} };
+// encode_sub (optional): codes sub-block b into out[0 .. room) in place of qlfc_encode_runs(views[b], ...) — the same bytes by other
+// means (a probability stream that the GPU computed); returns what that returns.
+struct SubEncode { virtual int operator()(int b, uint8_t* out, int room) = 0; virtual ~SubEncode() {} };
 int coder_compress_views(const RunView* views, int nblocks, const int* start, const int* size, int n,
-                         uint8_t* out, int coder, int features, RawFetch& fetch_raw);
+                         uint8_t* out, int coder, int features, RawFetch& fetch_raw, SubEncode* encode_sub = nullptr);
 void coder_split_blocks(const uint8_t* in, int n, int nblocks, int* start, int* size);
 
 uint32_t adler32(const uint8_t* p, size_t n);

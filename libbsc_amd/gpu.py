@@ -261,6 +261,21 @@ class GpuContext:
         self._check(self.L.bscgpu_qlfc_front_batch_device(self.h, _dptr(dL), N.np_ptr(fb.sizes), fb.count, C.byref(fb.lay)))
         return fb
 
+    def static_pstream_batch(self, dL, sizes):
+        """bscgpu_static_pstream_batch_device: front end and static-coder model (-e1) of a pass whose sorted blocks lie back to back in
+        the uint8 device tensor dL -> (FrontBatch, entries np.uint16[D], poff np.uint32[nsub + 1]); raises GpuError -4 when the device
+        declines the pass (option_get(CNT_DC_LAST_FAIL) says why)."""
+        fb = FrontBatch(sizes)
+        cap = 4 * int(self.max_n) + 65536                       # the device model's own capacity in decisions
+        out = np.empty(cap, np.uint16)
+        poff = np.zeros(2 * fb.count + 2, np.uint32)
+        D = int(self.L.bscgpu_static_pstream_batch_device(self.h, _dptr(dL), N.np_ptr(fb.sizes), fb.count, C.byref(fb.lay), N.np_ptr(out), cap,
+                                                          N.np_ptr(poff)))
+        self._check(D)
+        if D > cap:
+            raise GpuError(-2, f"{D} decisions exceed the buffer of {cap}")
+        return fb, out[:D], poff[:fb.nsub + 1]
+
     # ---- batched decompression (one inverse-BWT pass for many blocks, include/bscgpu.h) -------
     def unbwt_batch(self, dL, sizes, primary, dT=None):
         """inverse BWT of every block of a batch laid out back to back in the uint8 device tensor dL (primary: 1-based indexes) ->
@@ -320,6 +335,7 @@ class GpuContext:
     OPT_RS_ONESWEEP, CNT_OS_RETRIES, OPT_DC_PACKED_STREAM = 1, 2, 4
     OPT_BATCH_FRONT, CNT_BATCH_FRONT_PASSES, CNT_BATCH_L_PASSES = 9, 10, 11     # the compress-batch passes' route and how many took each
     OPT_DEVICE_RC, CNT_DEVICE_RC_BLOCKS = 12, 13       # a device-model block's streams are range-coded on the GPU (default 0) and how many were
+    OPT_BATCH_MODEL, CNT_BATCH_MODEL_PASSES, CNT_BATCH_MODEL_DECLINED = 14, 15, 16    # the static coder's model of a compress-batch pass on the GPU
     CNT_DC_REPLAYS, CNT_DC_LAST_FAIL, CNT_DC_AVG_UNDECIDED, CNT_DC_HIST_EXTENDED = 5, 6, 7, 8      # the last device-model block (get only)
     DC_FAIL_AVG, DC_FAIL_HIST, DC_FAIL_CAP, DC_FAIL_REPLAY = 2, 4, 8, 16                          # BSCGPU_DC_FAIL_*
 
@@ -455,6 +471,33 @@ def front_batch_host(L, sizes):
     if rc < 0:
         raise GpuError(rc, "bscgpu_front_batch_host")
     return fb
+
+
+def static_pstream_host(fb, s):
+    """bscgpu_static_pstream_host: GpuContext.static_pstream_batch's CPU stand-in for sub-block s of a FrontBatch (no GPU): the host
+    model's own walk, recording {[11:0] p, [12] bit, [13] run start} instead of coding -> np.uint16 entries"""
+    cap = 16 * int(fb.sub_size[s]) + 64
+    out = np.empty(cap, np.uint16)
+    n = int(N.lib().bscgpu_static_pstream_host(C.byref(fb.lay), int(s), N.np_ptr(out), cap))
+    if n < 0:
+        raise GpuError(n, "bscgpu_static_pstream_host")
+    if n > cap:
+        out = np.empty(n, np.uint16)
+        n = int(N.lib().bscgpu_static_pstream_host(C.byref(fb.lay), int(s), N.np_ptr(out), n))
+    return out[:n]
+
+
+def front_batch_code_ps(fb, block, ps, poff, features=3):
+    """bscgpu_front_batch_code_ps: FrontBatch.code for the static coder from the sub-blocks' probability streams (ps uint16 entries,
+    sub-block s at poff[s]) -> bytes, or its negative code"""
+    p = np.ascontiguousarray(ps, dtype=np.uint16)
+    o = np.ascontiguousarray(poff, dtype=np.uint32)
+    assert o.size == fb.nsub + 1 and (p.size >= int(o[-1]))
+    if p.size == 0:
+        p = np.zeros(1, np.uint16)
+    out = np.empty(int(fb.sizes[block]) + 4096, np.uint8)
+    r = int(N.lib().bscgpu_front_batch_code_ps(C.byref(fb.lay), int(block), N.np_ptr(p), N.np_ptr(o), N.np_ptr(out), int(features)))
+    return out[:r].tobytes() if r >= 0 else r
 
 
 def batch_plan(sizes, sorter=1, cap=64 << 20):

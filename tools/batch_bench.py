@@ -38,6 +38,16 @@ its kernel classes (SEG, MISC, GATHER) — against a loop of the single-block fr
 bscgpu_qlfc_static_pstream, isolated through the same three classes: the device model behind it books to other classes).
 --profile-pass with --front: one compress_batch of the workload with the option on, nothing timed (for rocprofv3).
     python tools/batch_bench.py --front [--front-only] [--reps 3] [--workloads W1,W2,W3]
+
+--model: the batch legs with BSCGPU_OPT_BATCH_MODEL on and off (the static coder's model of a pass on the GPU, the
+probability stream down, host threads run the range coder only), host and HBM input, and the pipe, repetitions interleaved (on, off,
+on_device, off_device, pipe, on, ...), coder -e1; every repetition's wall time, the medians, CPU-s per MB, how many passes the model
+kept and declined, a SHA-256 of every output against the pipe's.  --model-only: per workload the stage alone on one pass's L in HBM —
+bscgpu_static_pstream_batch_device, wall and the HIP-event time per kernel class (contexts, sorts, partition, evaluation, p stream;
+the front end beside them).  The on legs also run with BSCGPU_OPT_DEVICE_RC = 1 (the pass's streams coded by one launch of the
+device's range coder).  --model-sweep: on against off on passes of 64 KiB .. 16 MiB cut from the workload's text — the smallest pass
+the model route wins on (run it with BSC_BATCH_MODEL_MIN_PASS=0 in the environment).  Raw output belongs under profiles/batch_model/.
+    python tools/batch_bench.py --model [--model-only | --model-sweep] [--reps 3] [--workloads W1,W2,W3]
 """
 import argparse
 import ctypes as C
@@ -332,6 +342,125 @@ def front_main(args):
         ctx.close()
 
 
+def model_main(args):
+    """BSCGPU_OPT_BATCH_MODEL on against off inside one process, interleaved; or the stage alone"""
+    import hashlib
+    import torch
+    from libbsc_amd import GpuContext
+    from libbsc_amd.gpu import GpuError, batch_plan
+    coder = 1
+    ctx = GpuContext(0, max_n=(64 << 20) + 4096)
+    OPT = ctx.OPT_BATCH_MODEL
+    pctx = [GpuContext(0, max_n=(1 << 20) + 4096) for _ in range(0 if (args.model_only or args.model_sweep) else args.contexts)]
+    pipes = [c.pipe(args.depth) for c in pctx]
+    CLASSES = {"contexts": ("dc_ctx",), "sorts": ("radix_scatter", "radix_hist", "radix_scan", "radix_hist_all", "radix_aux"),
+               "partition": ("dc_part",), "evaluation": ("dc_eval",), "p_stream": ("dc_pstream",), "front_end": ("seg", "misc", "gather")}
+
+    def digest(out):
+        h = hashlib.sha256()
+        for b in out:
+            h.update(b if isinstance(b, bytes) else str(b).encode())
+        return h.hexdigest()
+
+    try:
+        for name in args.workloads.split(","):
+            sizes, blocks = workload(name)
+            mb = sum(sizes) / 1e6
+            flat = torch.from_numpy(np.concatenate(blocks)).cuda()
+            torch.cuda.synchronize()
+            if args.model_sweep:
+                # the smallest pass the model route wins on: passes of 2^k bytes cut from the workload's text, on / off interleaved
+                # (run with BSC_BATCH_MODEL_MIN_PASS=0 in the environment, so that every pass size is given to the model)
+                text = np.concatenate(blocks)
+                for total in [1 << k for k in range(16, 25)]:
+                    bs = min(total, 128 << 10)
+                    part = [text[o:o + bs] for o in range(0, total, bs)]
+                    for v in (1, 0):
+                        ctx.option_set(OPT, v)
+                        ctx.compress_batch(part, 1, coder)
+                    t = {1: [], 0: []}
+                    kept_n = 0
+                    for _ in range(max(args.reps, 5)):
+                        for v in (1, 0):
+                            ctx.option_set(OPT, v)
+                            p0 = ctx.option_get(ctx.CNT_BATCH_MODEL_PASSES)
+                            _, wall, _ = timed(lambda: ctx.compress_batch(part, 1, coder))
+                            t[v].append(round(wall * 1e3, 3))
+                            if v:
+                                kept_n = ctx.option_get(ctx.CNT_BATCH_MODEL_PASSES) - p0
+                    print(json.dumps({"workload": name, "leg": "model_sweep", "pass_bytes": total, "blocks": len(part), "model_passes_per_call": kept_n,
+                                      "on_ms": t[1], "off_ms": t[0], "on_median_ms": float(np.median(t[1])), "off_median_ms": float(np.median(t[0]))}), flush=True)
+                continue
+            if args.model_only:
+                _, pass_of = batch_plan(sizes, 1, ctx.max_n)
+                cnt = sum(1 for x in pass_of if x == 0)
+                psz = sizes[:cnt]
+                total = sum(psz)
+                dL = torch.empty(total, dtype=torch.uint8, device="cuda")
+                ctx.bwt_batch(flat[:total], psz, aux=False, dL=dL)
+                rec = {"workload": name, "leg": "model_only", "blocks": cnt, "MB": round(total / 1e6, 2)}
+                try:
+                    fb, ps, _ = ctx.static_pstream_batch(dL, psz)                 # warm-up: arenas, tables, first launches
+                except GpuError as e:
+                    print(json.dumps({**rec, "declined": e.code, "last_fail": ctx.option_get(ctx.CNT_DC_LAST_FAIL)}), flush=True)
+                    continue
+                ctx.profile(True)
+                tw, per = [], {k: [] for k in CLASSES}
+                for _ in range(args.reps):
+                    ctx.profile_reset()
+                    t0 = time.perf_counter()
+                    ctx.static_pstream_batch(dL, psz)
+                    tw.append(round((time.perf_counter() - t0) * 1e3, 2))
+                    st = ctx.profile_get()
+                    for k, names in CLASSES.items():
+                        per[k].append(round(sum(st[n]["ms"] for n in names), 3))
+                ctx.profile(False)
+                print(json.dumps({**rec, "runs": fb.m, "sub_blocks": fb.nsub, "decisions": int(ps.size), "replays": ctx.option_get(ctx.CNT_DC_REPLAYS),
+                                  "wall_ms_with_front_end_and_copy_out": tw, "kernel_ms": per,
+                                  "model_kernel_ms_median": round(float(sum(np.median(v) for k, v in per.items() if k != "front_end")), 3)}), flush=True)
+                continue
+            dblocks = [torch.from_numpy(b).cuda() for b in blocks]
+            torch.cuda.synchronize()
+            want = digest(run_pipe(pipes, dblocks, sizes, 1, coder, args.depth))        # warm-up + the single-block outputs
+            for v in (1, 0):
+                ctx.option_set(OPT, v)
+                ctx.compress_batch(blocks[:40], 1, coder)
+            legs = {"batch_on": (1, False, 0), "batch_off": (0, False, 0), "batch_on_device_rc": (1, False, 1),
+                    "batch_device_on": (1, True, 0), "batch_device_off": (0, True, 0), "batch_device_on_device_rc": (1, True, 1), "pipe": None}
+            walls = {k: [] for k in legs}
+            cpus = {k: [] for k in legs}
+            same = {k: True for k in legs}
+            kept = {k: 0 for k in legs}
+            declined = {k: 0 for k in legs}
+            for _ in range(args.reps):
+                for leg, how in legs.items():
+                    if how is None:
+                        out, wall, cpu = timed(lambda: run_pipe(pipes, dblocks, sizes, 1, coder, args.depth))
+                    else:
+                        ctx.option_set(OPT, how[0])
+                        ctx.option_set(ctx.OPT_DEVICE_RC, how[2])
+                        p0, d0 = ctx.option_get(ctx.CNT_BATCH_MODEL_PASSES), ctx.option_get(ctx.CNT_BATCH_MODEL_DECLINED)
+                        out, wall, cpu = timed((lambda: ctx.compress_batch_device(flat, sizes, 1, coder)) if how[1] else (lambda: ctx.compress_batch(blocks, 1, coder)))
+                        kept[leg] = ctx.option_get(ctx.CNT_BATCH_MODEL_PASSES) - p0
+                        declined[leg] = ctx.option_get(ctx.CNT_BATCH_MODEL_DECLINED) - d0
+                    walls[leg].append(wall); cpus[leg].append(cpu)
+                    same[leg] = same[leg] and digest(out) == want
+            for leg in legs:
+                w = np.array(walls[leg])
+                print(json.dumps({"workload": name, "leg": leg, "blocks": len(sizes), "MB": round(mb, 2), "coder": coder,
+                                  "ms": [round(x * 1e3, 1) for x in w], "median_MB_s": round(mb / float(np.median(w)), 1),
+                                  "MB_s_min_max": [round(mb / float(w.max()), 1), round(mb / float(w.min()), 1)],
+                                  "cpu_s_per_MB": round(float(np.mean(cpus[leg])) / mb, 4), "model_passes": kept[leg], "model_declined": declined[leg],
+                                  "sha256_equals_pipe": bool(same[leg])}), flush=True)
+            del dblocks
+    finally:
+        for p in pipes:
+            p.close()
+        for c in pctx:
+            c.close()
+        ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -346,7 +475,13 @@ def main():
     ap.add_argument("--profile-pass", action="store_true", help="with --decode: one decompress_batch per workload and config, nothing timed")
     ap.add_argument("--front", action="store_true", help="BSCGPU_OPT_BATCH_FRONT on against off, interleaved (BWT, --coder)")
     ap.add_argument("--front-only", action="store_true", help="with --front: the front-end stage alone against a loop of the single-block front end")
+    ap.add_argument("--model", action="store_true", help="BSCGPU_OPT_BATCH_MODEL on against off, interleaved (BWT, -e1)")
+    ap.add_argument("--model-only", action="store_true", help="with --model: the model stage alone on one pass, per kernel class")
+    ap.add_argument("--model-sweep", action="store_true", help="with --model: on against off on passes of 64 KiB .. 16 MiB (set BSC_BATCH_MODEL_MIN_PASS=0)")
     args = ap.parse_args()
+    if args.model or args.model_only or args.model_sweep:
+        args.workloads = args.workloads or "W1,W2,W3"
+        return model_main(args)
     if args.front or args.front_only:
         args.workloads = args.workloads or "W1,W2,W3"
         return front_main(args)
