@@ -249,6 +249,20 @@ BSCGPU_API int64_t bscgpu_static_pstream_host(const bscgpu_front_layout* layout,
 BSCGPU_API int bscgpu_front_batch_code_ps(const bscgpu_front_layout* layout, int block, const uint16_t* ps, const uint32_t* poff,
                                           unsigned char* out, int features);
 
+/* ---- the fast coder's model (-e0) of a whole pass ("The fast coder's model of a pass") ------------------------------
+ * The three calls above for the fast coder; every limit, return value and rule is theirs word for word ("counted, not copied" above
+ * cap, a declined pass still fills the layout, the memory of the first call).  Entries are in the BSCGPU_RC_FAST16 form:
+ * {[12:0] the counter's value before its update, [13] coded bit, [14] first decision of a run, [15] run side of the run = 11-bit
+ * precision, else 13}.  The fast model has no avg_rank flags and no run_hist look-back: the device declines a pass only for capacity
+ * (BSCGPU_DC_FAIL_CAP) or a chain whose bracket stays open too long (BSCGPU_DC_FAIL_REPLAY).
+ * bscgpu_fast_pstream_host is the host fast coder's own walk, recording instead of coding; bscgpu_front_batch_code_psf codes a block
+ * from its sub-blocks' fast streams (framing, stored-raw rule and LIBBSC_NOT_COMPRESSIBLE points as bscgpu_front_batch_code_ps). */
+BSCGPU_API int64_t bscgpu_fast_pstream_batch_device(bscgpu_ctx* ctx, const void* dL, const int* sizes, int count, bscgpu_front_layout* layout,
+                                                    uint16_t* out, int64_t cap, uint32_t* poff);
+BSCGPU_API int64_t bscgpu_fast_pstream_host(const bscgpu_front_layout* layout, int s, uint16_t* out, int64_t cap);
+BSCGPU_API int bscgpu_front_batch_code_psf(const bscgpu_front_layout* layout, int block, const uint16_t* ps, const uint32_t* poff,
+                                           unsigned char* out, int features);
+
 /* ---- batched decompression: one inverse-BWT pass for many blocks -------------
  * bscgpu_unbwt_batch_device: L of `count` blocks back to back in HBM (block b at Σ sizes[0..b), primary[b] its 1-based
  *   primary index) -> T in the same layout; dT may be dL.  Passes of consecutive blocks, at most max_n bytes and
@@ -456,23 +470,34 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          bytes come down and the host frames them.  A sub-block that ends LIBBSC_NOT_COMPRESSIBLE sends the block through
  *                          the host model again, as on the host route.  0 (default): the stream crosses PCIe and host threads code it.  Same
  *                          output.  -e2 and blocks the model declines are not affected.  A batched pass that took the device model
- *                          (BSCGPU_OPT_BATCH_MODEL) has all its sub-block streams coded by one launch, eight streams per wavefront;
+ *                          (BSCGPU_OPT_BATCH_MODEL, BSCGPU_OPT_BATCH_MODEL_FAST) has all its sub-block streams coded by one launch, eight streams per wavefront;
  *                          only the coded bytes come down.  The counter below then counts the pass.
  * BSCGPU_CNT_DEVICE_RC_BLOCKS  (get only) blocks of this context whose streams were coded that way.
  * BSCGPU_OPT_BATCH_MODEL    1: a pass of the compress-batch calls that takes the front-end route with the static coder (-e1) also runs the
  *                          coder's adaptive model on the GPU (bscgpu_static_pstream_batch_device's stage) and brings the probability
  *                          stream down; the coder threads run the range coder only (bscgpu_front_batch_code_ps).  A pass the device
  *                          declines, a pass below 16 MiB (BSC_BATCH_MODEL_MIN_PASS in the environment: another minimum, in bytes), and
- *                          every pass with -e0 / -e2 or without the front end, takes the host model.  Same output.  Default 0: it halves
+ *                          every pass with -e2 or without the front end, takes the host model (-e0: the option below).  Same output.  Default 0: it halves
  *                          the host's CPU time per MB and wins on calls of several passes, but not on the one-pass workloads.
  * BSCGPU_CNT_BATCH_MODEL_PASSES, BSCGPU_CNT_BATCH_MODEL_DECLINED  (get only) passes that were coded from the device model's stream, and
  *                          passes given to it that it declined (BSCGPU_CNT_DC_LAST_FAIL: why the last one was).
+ * BSCGPU_OPT_BATCH_MODEL_FAST  1: the same for the fast coder (-e0), an option of its own: a pass of the compress-batch calls that takes
+ *                          the front-end route with -e0 also runs the fast coder's model on the GPU (bscgpu_fast_pstream_batch_device's
+ *                          stage); the coder threads run the range coder only (bscgpu_front_batch_code_psf), or, with
+ *                          BSCGPU_OPT_DEVICE_RC, one launch of the device's range coder codes the pass.  A pass the device declines
+ *                          (capacity, or a chain open over too many evaluation chunks) and a pass below 32 MiB
+ *                          (BSC_BATCH_MODEL_MIN_PASS in the environment: another minimum for both routes) take the host model.  -e1 and
+ *                          -e2 are not affected, and BSCGPU_OPT_BATCH_MODEL and its counters are not moved by -e0 calls.  Same output.
+ *                          Default 0: measured, it gains on calls of several full passes (4 % from host input, 10 % from HBM, a quarter
+ *                          less CPU per MB) and loses 9 - 19 % on one-pass calls.
+ * BSCGPU_CNT_BATCH_FAST_PASSES, BSCGPU_CNT_BATCH_FAST_DECLINED  (get only) its passes coded from the device's stream, and declined.
  * set returns the previous value or a negative libbsc error code; get the value or a negative error code. */
 enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACKED_STREAM = 4,
        BSCGPU_CNT_DC_REPLAYS = 5, BSCGPU_CNT_DC_LAST_FAIL = 6, BSCGPU_CNT_DC_AVG_UNDECIDED = 7, BSCGPU_CNT_DC_HIST_EXTENDED = 8,
        BSCGPU_OPT_BATCH_FRONT = 9, BSCGPU_CNT_BATCH_FRONT_PASSES = 10, BSCGPU_CNT_BATCH_L_PASSES = 11,
        BSCGPU_OPT_DEVICE_RC = 12, BSCGPU_CNT_DEVICE_RC_BLOCKS = 13,
-       BSCGPU_OPT_BATCH_MODEL = 14, BSCGPU_CNT_BATCH_MODEL_PASSES = 15, BSCGPU_CNT_BATCH_MODEL_DECLINED = 16 };
+       BSCGPU_OPT_BATCH_MODEL = 14, BSCGPU_CNT_BATCH_MODEL_PASSES = 15, BSCGPU_CNT_BATCH_MODEL_DECLINED = 16,
+       BSCGPU_OPT_BATCH_MODEL_FAST = 17, BSCGPU_CNT_BATCH_FAST_PASSES = 18, BSCGPU_CNT_BATCH_FAST_DECLINED = 19 };
 /* _FAIL_AVG: undecided avg_rank flags; _FAIL_HIST: a run_hist bracket open after 9216 predecessors; _FAIL_CAP: more runs or decisions
  * than the context's arena holds; _FAIL_REPLAY: a chain whose bracket stayed open over more than 64 evaluation chunks. */
 enum { BSCGPU_DC_FAIL_AVG = 2, BSCGPU_DC_FAIL_HIST = 4, BSCGPU_DC_FAIL_CAP = 8, BSCGPU_DC_FAIL_REPLAY = 16 };

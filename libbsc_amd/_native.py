@@ -98,6 +98,11 @@ def lib():
     L.bscgpu_static_pstream_host.argtypes = [vp, C.c_int, vp, C.c_int64]
     L.bscgpu_static_pstream_host.restype = C.c_int64
     L.bscgpu_front_batch_code_ps.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int]
+    L.bscgpu_fast_pstream_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int64, vp]
+    L.bscgpu_fast_pstream_batch_device.restype = C.c_int64
+    L.bscgpu_fast_pstream_host.argtypes = [vp, C.c_int, vp, C.c_int64]
+    L.bscgpu_fast_pstream_host.restype = C.c_int64
+    L.bscgpu_front_batch_code_psf.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int]
     L.bscgpu_unbwt_batch_plan.argtypes = [vp, C.c_int, C.c_int64, vp]
     L.bscgpu_unbwt_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp]
     L.bscgpu_decompress_batch_sizes.argtypes = [vp, vp, C.c_int, vp]

@@ -353,6 +353,7 @@ extern "C" int bscgpu_option_set(bscgpu_ctx* c, int key, int value)
     if (key == BSCGPU_OPT_BATCH_FRONT && (value == 0 || value == 1)) { const int old = c->batch_front; c->batch_front = value; return old; }
     if (key == BSCGPU_OPT_DEVICE_RC && (value == 0 || value == 1)) { const int old = c->device_rc; c->device_rc = value; return old; }
     if (key == BSCGPU_OPT_BATCH_MODEL && (value == 0 || value == 1)) { const int old = c->batch_model; c->batch_model = value; return old; }
+    if (key == BSCGPU_OPT_BATCH_MODEL_FAST && (value == 0 || value == 1)) { const int old = c->batch_model_fast; c->batch_model_fast = value; return old; }
     return BSC_BAD_PARAMETER;
 }
 extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
@@ -373,6 +374,9 @@ extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
     if (key == BSCGPU_OPT_BATCH_MODEL) return c->batch_model;
     if (key == BSCGPU_CNT_BATCH_MODEL_PASSES) return c->cnt_model_passes;
     if (key == BSCGPU_CNT_BATCH_MODEL_DECLINED) return c->cnt_model_declined;
+    if (key == BSCGPU_OPT_BATCH_MODEL_FAST) return c->batch_model_fast;
+    if (key == BSCGPU_CNT_BATCH_FAST_PASSES) return c->cnt_model_fast_passes;
+    if (key == BSCGPU_CNT_BATCH_FAST_DECLINED) return c->cnt_model_fast_declined;
     return BSC_BAD_PARAMETER;
 }
 extern "C" int bscgpu_last_stage_ms(bscgpu_ctx* c, double* out6)

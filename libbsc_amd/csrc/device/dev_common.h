@@ -125,6 +125,9 @@ struct bscgpu_ctx {
     // the static coder's model of a whole pass (devcoder.hip: devcoder_pstream_batch)
     int  batch_model = 0;         // BSCGPU_OPT_BATCH_MODEL (default 0: DESIGN §2b, "The static coder's model of a pass")
     int  cnt_model_passes = 0, cnt_model_declined = 0;   // BSCGPU_CNT_BATCH_MODEL_PASSES / _DECLINED
+    // the fast coder's (devcoder.hip: devcoder_pstream_fast_batch); it shares the pinned stream buffers below
+    int  batch_model_fast = 0;    // BSCGPU_OPT_BATCH_MODEL_FAST (default 0: DESIGN §2b, "The fast coder's model of a pass")
+    int  cnt_model_fast_passes = 0, cnt_model_fast_declined = 0;   // BSCGPU_CNT_BATCH_FAST_PASSES / _DECLINED
     u16* model_host[2] = {nullptr, nullptr};   // pinned: a pass's probability stream coming down (two: coding overlaps the next pass), allocated on first use
     size_t model_host_entries = 0;
     bool model_host_failed = false;            // they could not be pinned: the route is off for this context
@@ -263,6 +266,9 @@ const u16* devcoder_pstream_ptr(const bscgpu_ctx* c, int psbuf = 0);
 // devcoder_batch_poff_ptr (device).  BSC_NOT_SUPPORTED: the pass is declined (c->dc_last_fail: BSCGPU_DC_FAIL_*; 0: an arena did not
 // fit).  Synchronous.
 int  devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out);
+// ... the fast coder's (-e0) model of the pass: same inputs, same outputs with entries in the dcm::PSF_* form, same exits (only
+// FAIL_CAP and FAIL_REPLAY can be raised: this coder has no avg_rank flags and no run_hist look-back)
+int  devcoder_pstream_fast_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out);
 const u32* devcoder_batch_poff_ptr(const bscgpu_ctx* c);
 int64_t devcoder_batch_bytes(const bscgpu_ctx* c);      // HBM the batch model added on its first use
 void devcoder_destroy(bscgpu_ctx* c);

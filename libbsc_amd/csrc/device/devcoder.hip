@@ -724,11 +724,12 @@ __global__ __launch_bounds__(WG) void dc_part_scatter_kernel(const u64* __restri
 
 // 2d. the fast coder (-e0) has ONE family, so the stream-order job has no chains to lay out — but the p stream still needs to know
 // where every run's entries go: doff[i] = decision index of item i's first decision, exactly what dc_part_scatter leaves behind.
-template <int SIDES>
-__global__ __launch_bounds__(WG) void dc_doff_kernel(const u64* __restrict__ items, DcGeom g, DcSub S, const u32* __restrict__ meta,
+template <int SIDES, class SB>
+__global__ __launch_bounds__(WG) void dc_doff_kernel(const u64* __restrict__ items, DcGeom g, SB S, const u32* __restrict__ meta,
                                                      const u32* __restrict__ wdecoff, u32* __restrict__ doff)
 {
-    const u32 mrp = dc_maxr_pack(S);                                  // max_rank of the eight sub-blocks, one scalar word
+    typedef DcForm<SB> F;
+    const u32 mrp = F::maxr_word(S);                                  // max_rank of the eight sub-blocks, one scalar word
     if (meta[DM_FAIL] != 0u) return;
     const u32 w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const u32 wc = blockIdx.x * WAVES + w;
@@ -742,9 +743,9 @@ __global__ __launch_bounds__(WG) void dc_doff_kernel(const u64* __restrict__ ite
         const bool valid = i < i1;
         const u64 key = knext;
         asm volatile("" :: "v"(key) : "memory");                     // (wait for this tile's items, THEN request the next tile's: dc_part_scatter_kernel)
-        const Item it = item_unpack(key);
+        const typename F::It it = F::unpack(key);
         knext = (i + 64 < i1) ? items[i + 64] : 0ull;
-        const int maxr = dc_maxr_of(it.sb, mrp);
+        const int maxr = F::maxr(it, mrp);
         u32 nd = 0;
         if (valid) { if (SIDES & 1) nd += (u32)count_rank_side(it, maxr); if (SIDES & 2) nd += (u32)count_run_side(it); }
         const u32 incl = wave_incl_sum(nd);
@@ -1308,13 +1309,15 @@ __global__ __launch_bounds__(WG) void dc_poff_tab_kernel(const u32* __restrict__
     if (b <= S.nsub) poff[b] = doff_sp[S.run[b]];
 }
 // max_rank of every sub-block of a pass from its first-run table: bsr(nsym - 1), nsym = symbols with a first run.  One wavefront per
-// sub-block.  Also closes the run table: run[nsub] = m.
-__global__ __launch_bounds__(WG) void dc_tab_prep_kernel(const u32* __restrict__ first_run /*[nsub][256]*/, u32 nsub, u32 m,
+// sub-block.  Also closes the run table: run[nsub] = m.  fixed >= 0: that value for every sub-block instead (the fast coder closes
+// the exponent below 7 bits whatever the alphabet: qlfc.cpp:1204).
+__global__ __launch_bounds__(WG) void dc_tab_prep_kernel(const u32* __restrict__ first_run /*[nsub][256]*/, u32 nsub, u32 m, int fixed,
                                                          u8* __restrict__ maxr, u32* __restrict__ sub_run)
 {
     const u32 s = blockIdx.x * WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (blockIdx.x == 0 && threadIdx.x == 0) sub_run[nsub] = m;
     if (s >= nsub) return;
+    if (fixed >= 0) { if (lane == 0u) maxr[s] = (u8)fixed; return; }
     const uint4 q = reinterpret_cast<const uint4*>(first_run + (size_t)s * 256u)[lane];
     u32 cnt = (q.x != 0xffffffffu) + (q.y != 0xffffffffu) + (q.z != 0xffffffffu) + (q.w != 0xffffffffu);
     cnt = wave_incl_sum(cnt);
@@ -1529,6 +1532,38 @@ static int dc_eval_static(bscgpu_ctx* c, DevCoder* d, const u32* E, bool tab)
     return BSC_NO_ERROR;
 }
 
+// The fast coder's one family (job 1: the char family's chains with shift updates, mp_fast), E events; tab: a batched pass.
+static int dc_eval_fast(bscgpu_ctx* c, DevCoder* d, u32 E, bool tab)
+{
+    DcEvalAll A;
+    A.sink = d->sink;
+    A.ev = eval_chunk_events((u64)E);
+    A.wstart[0] = 0; A.cstart[0] = 0;
+    for (int job = 0; job < 4; ++job) {
+        A.job[job].events = d->events[job]; A.job[job].E = job == 1 ? E : 0u; A.job[job].rowstart = d->rowstart + (DC_ROWS + 8) * job;
+        A.job[job].fam = FAM_CHAR;
+        A.V[job] = d->V[job];
+        const u32 nch = (A.job[job].E + A.ev - 1) / A.ev;
+        A.wstart[job + 1] = A.wstart[job] + (nch + 63) / 64;
+        A.cstart[job + 1] = A.cstart[job] + (nch + 63) / 64 * 64;
+    }
+    if (A.cstart[4] > 4 * d->nch_cap) return ctx_fail(c, BSC_GPU_ERROR, "device coder: chunk table too small", hipSuccess);
+    prof_begin(c, BSCGPU_K_DC_EVAL, (u64)E * 6, (u64)E);
+    if (A.wstart[4] > 0) {
+        hipLaunchKernelGGL(dc_mark_rows_kernel, dim3((4 * DC_ROWS + WG - 1) / WG), dim3(WG), 0, c->stream, A);
+        if (tab) {                                                        // a batched pass: chain starts from the events' full sub-block ids (job 1 alone)
+            DcMarkAll K;
+            for (int job = 0; job < 4; ++job) { K.events[job] = d->events[job]; K.esub[job] = d->esub[job]; K.E[job] = job == 1 ? E : 0u; }
+            hipLaunchKernelGGL(dc_mark_chains_kernel, dim3((E + 8 * WG - 1) / (8 * WG), 4), dim3(WG), 0, c->stream, K, d->meta);
+        }
+        hipLaunchKernelGGL(dc_eval_wave_kernel<false>, dim3((A.wstart[4] + DC_EVAL_WAVES - 1) / DC_EVAL_WAVES), dim3(64 * DC_EVAL_WAVES), DC_EVAL_LDS, c->stream, A, d->mp_fast, d->meta, d->elo, d->ehi, (const u16*)nullptr, d->cnt);
+        hipLaunchKernelGGL(dc_eval_b_kernel, dim3((A.cstart[4] + WG - 1) / WG), dim3(WG), 0, c->stream, A, d->mp_fast, d->meta, d->elo, d->ehi, d->S);
+        hipLaunchKernelGGL(dc_eval_wave_kernel<true>, dim3((A.wstart[4] + DC_EVAL_WAVES - 1) / DC_EVAL_WAVES), dim3(64 * DC_EVAL_WAVES), DC_EVAL_LDS, c->stream, A, d->mp_fast, d->meta, (u16*)nullptr, (u16*)nullptr, d->S, d->cnt + 3 * 4096);
+    }
+    prof_end(c);
+    return BSC_NO_ERROR;
+}
+
 // Probability stream of a whole block.  Inputs: the QLFC front end's run arrays on the device (sym / rank / start, m runs of
 // the n-byte sorted block), the sub-blocks' run ranges and max_rank values.  On success *D_out decisions were written to the
 // device p stream (d->ps) and poff[0..nb] (decision offsets of the sub-blocks) to hmeta[32..]; returns BSC_NOT_SUPPORTED when
@@ -1717,7 +1752,7 @@ int devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out)
     const u32 gm = (m + WG - 1) / WG;
     const u32 gm8 = (gm + 7u) / 8u * 8u;            // kernels that use dc_virtual_block()
     prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
-    hipLaunchKernelGGL(dc_tab_prep_kernel, dim3(((u32)nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, T.first_run, (u32)nsub, m, d->sub_maxr, T.sub_run);
+    hipLaunchKernelGGL(dc_tab_prep_kernel, dim3(((u32)nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, T.first_run, (u32)nsub, m, -1, d->sub_maxr, T.sub_run);
     // (always: which sub-blocks can escape is not known on the host here; one of at most 32 symbols never leaves a flag open — avg_top)
     hipLaunchKernelGGL(dc_avg_kernel<DcSubTab>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta);
     hipLaunchKernelGGL(dc_items_kernel<DcSubTab>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, d->ge32, m, 0u, S, d->key_ch);
@@ -1799,7 +1834,7 @@ static int devcoder_pstream_fast(bscgpu_ctx* c, DevCoder* d, const u8* dsym, con
         hipLaunchKernelGGL((dc_part_count_kernel<3, DcSub>), dim3(grid), dim3(WG), 0, c->stream, d->key_ch, g, S, d->rowbins, d->cnt, d->wdec);
         hipLaunchKernelGGL(dc_scan_rows_kernel, dim3(DC_ROWS), dim3(WG), 0, c->stream, d->cnt, g.W, d->rowtot);
         hipLaunchKernelGGL(dc_scan_misc_kernel, dim3(1), dim3(WG), 0, c->stream, d->rowtot, d->rowstart, d->wdec, g.W, d->wdecoff, d->meta, 0, (u32)d->Dcap);
-        hipLaunchKernelGGL(dc_doff_kernel<3>, dim3(grid), dim3(WG), 0, c->stream, d->key_ch, g, S, d->meta, d->wdecoff, d->doff[0]);
+        hipLaunchKernelGGL((dc_doff_kernel<3, DcSub>), dim3(grid), dim3(WG), 0, c->stream, d->key_ch, g, S, d->meta, d->wdecoff, d->doff[0]);
         prof_end(c);
     }
     dc_launch_partition<3>(c, d, d->key_ch_s, m, S, 1, 0u);
@@ -1810,29 +1845,8 @@ static int devcoder_pstream_fast(bscgpu_ctx* c, DevCoder* d, const u8* dsym, con
     if (d->hmeta[DM_FAIL] != 0) { dc_note_block(c, d); return BSC_NOT_SUPPORTED; }
     const u32 E = d->hmeta[DM_D0 + 1];
     if (d->hmeta[DM_D0 + 0] != E) return ctx_fail(c, BSC_GPU_ERROR, "device coder (fast): decision counts of stream and chain order differ", hipSuccess);
-    {
-        DcEvalAll A;
-        A.sink = d->sink;
-        A.ev = eval_chunk_events((u64)E);
-        A.wstart[0] = 0; A.cstart[0] = 0;
-        for (int job = 0; job < 4; ++job) {
-            A.job[job].events = d->events[job]; A.job[job].E = job == 1 ? E : 0u; A.job[job].rowstart = d->rowstart + (DC_ROWS + 8) * job;
-            A.job[job].fam = FAM_CHAR;
-            A.V[job] = d->V[job];
-            const u32 nch = (A.job[job].E + A.ev - 1) / A.ev;
-            A.wstart[job + 1] = A.wstart[job] + (nch + 63) / 64;
-            A.cstart[job + 1] = A.cstart[job] + (nch + 63) / 64 * 64;
-        }
-        if (A.cstart[4] > 4 * d->nch_cap) return ctx_fail(c, BSC_GPU_ERROR, "device coder: chunk table too small", hipSuccess);
-        prof_begin(c, BSCGPU_K_DC_EVAL, (u64)E * 6, (u64)E);
-        if (A.wstart[4] > 0) {
-            hipLaunchKernelGGL(dc_mark_rows_kernel, dim3((4 * DC_ROWS + WG - 1) / WG), dim3(WG), 0, c->stream, A);
-            hipLaunchKernelGGL(dc_eval_wave_kernel<false>, dim3((A.wstart[4] + DC_EVAL_WAVES - 1) / DC_EVAL_WAVES), dim3(64 * DC_EVAL_WAVES), DC_EVAL_LDS, c->stream, A, d->mp_fast, d->meta, d->elo, d->ehi, (const u16*)nullptr, d->cnt);
-            hipLaunchKernelGGL(dc_eval_b_kernel, dim3((A.cstart[4] + WG - 1) / WG), dim3(WG), 0, c->stream, A, d->mp_fast, d->meta, d->elo, d->ehi, d->S);
-            hipLaunchKernelGGL(dc_eval_wave_kernel<true>, dim3((A.wstart[4] + DC_EVAL_WAVES - 1) / DC_EVAL_WAVES), dim3(64 * DC_EVAL_WAVES), DC_EVAL_LDS, c->stream, A, d->mp_fast, d->meta, (u16*)nullptr, (u16*)nullptr, d->S, d->cnt + 3 * 4096);
-        }
-        prof_end(c);
-    }
+    rc = dc_eval_fast(c, d, E, false);
+    if (rc < 0) return rc;
     DcGather G;
     G.key_ch = d->key_ch; G.m = m; G.inv_ch = d->inv_ch; G.inv_sr = d->inv_ch; G.inv_sn = d->inv_ch;
     G.doff_sp = d->doff[0]; G.doff_ch = d->doff[1]; G.doff_sr = d->doff[1]; G.doff_sn = d->doff[1];
@@ -1853,6 +1867,81 @@ static int devcoder_pstream_fast(bscgpu_ctx* c, DevCoder* d, const u8* dsym, con
     if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder fast] decisions %u, chunks replayed %u\n", E, d->hmeta[DM_REPLAYS]);
     *D_out = E;
     for (int b = 0; b <= nb; ++b) poff_out[b] = d->hmeta[32 + b];
+    return BSC_NO_ERROR;
+}
+
+// The fast coder's model (-e0) of a whole pass: devcoder_pstream_fast over the table qlfc_front_batch leaves, as devcoder_pstream_batch
+// is devcoder_pstream.  One family: the runs' stream offsets (job 0: counts and scans only), the partition of the symbol-major items
+// (job 1; its scatter writes every event's full sub-block id to esub[1], which dc_mark_chains_kernel folds into the chain-start mark —
+// a fast chain is (sub-block, decision type, symbol)), one evaluation with mp_fast, one stream whose entries are the counter values
+// (dcm::PSF_*).  max_rank is 7 for every sub-block.  No avg_rank flags, no run_hist look-back: FAIL_CAP and FAIL_REPLAY are the only
+// flags that can be raised.  The arena of devcoder_batch_ensure as it is (one esub plane of its four is used).  Two syncs.
+int devcoder_pstream_fast_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out)
+{
+    int rc = devcoder_ensure(c);
+    if (rc < 0) return rc;
+    DevCoder* d = c->dc;
+    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = 0;
+    c->dc_last_fail = m > d->Mcap ? (int)FAIL_CAP : 0;
+    if (m == 0 || m > d->Mcap || nsub < 1 || nsub > FRONT_MAX_SUB || !c->front_tab) return BSC_NOT_SUPPORTED;
+    rc = devcoder_batch_ensure(c, d);
+    if (rc < 0) return rc;
+    const FrontTab T = qlfc_front_tab(c, nsub);
+    const u8* dsym = reinterpret_cast<const u8*>(c->vA); const u8* drank = reinterpret_cast<const u8*>(c->vB); const u32* dstart = c->SA;
+    DcSubTab S; S.nsub = (u32)nsub; S.run = T.sub_run; S.off = T.sub_off; S.base = T.sub_base; S.maxr = d->sub_maxr;
+
+    HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
+    const u32 gm = (m + WG - 1) / WG;
+    const u32 gm8 = (gm + 7u) / 8u * 8u;            // kernels that use dc_virtual_block()
+    prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 14, m);
+    hipLaunchKernelGGL(dc_tab_prep_kernel, dim3(((u32)nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, T.first_run, (u32)nsub, m, 7, d->sub_maxr, T.sub_run);
+    HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));              // no escape coding in this coder
+    hipLaunchKernelGGL(dc_items_kernel<DcSubTab>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, d->ge32, m, 0u, S, d->key_ch);
+    prof_end(c);
+    RadixPass top; top.shift = 56; top.bits = 8;
+    int in_alt = 0;
+    rc = radix_sort_passes(c, d->key_ch, d->key_ch_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_ch);
+    if (rc < 0) return rc;
+    {
+        const DcGeom g = dc_geom(m);
+        const u32 grid = (g.W + WAVES - 1) / WAVES;
+        prof_begin(c, BSCGPU_K_DC_PART, (u64)m * 8, m);
+        hipLaunchKernelGGL((dc_part_count_kernel<3, DcSubTab>), dim3(grid), dim3(WG), 0, c->stream, d->key_ch, g, S, d->rowbins, d->cnt, d->wdec);
+        hipLaunchKernelGGL(dc_scan_rows_kernel, dim3(DC_ROWS), dim3(WG), 0, c->stream, d->cnt, g.W, d->rowtot);
+        hipLaunchKernelGGL(dc_scan_misc_kernel, dim3(1), dim3(WG), 0, c->stream, d->rowtot, d->rowstart, d->wdec, g.W, d->wdecoff, d->meta, 0, (u32)d->Dcap);
+        hipLaunchKernelGGL((dc_doff_kernel<3, DcSubTab>), dim3(grid), dim3(WG), 0, c->stream, d->key_ch, g, S, d->meta, d->wdecoff, d->doff[0]);
+        prof_end(c);
+    }
+    dc_launch_partition<3>(c, d, d->key_ch_s, m, S, 1, 0u);
+    hipLaunchKernelGGL(dc_poff_tab_kernel, dim3(((u32)nsub + 1 + WG - 1) / WG), dim3(WG), 0, c->stream, d->doff[0], S, d->poff_tab);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    prof_collect(c);
+    if (d->hmeta[DM_FAIL] != 0) { dc_note_block(c, d); return BSC_NOT_SUPPORTED; }
+    const u32 E = d->hmeta[DM_D0 + 1];
+    if (d->hmeta[DM_D0 + 0] != E) return ctx_fail(c, BSC_GPU_ERROR, "device coder (fast): decision counts of stream and chain order differ", hipSuccess);
+    rc = dc_eval_fast(c, d, E, true);
+    if (rc < 0) return rc;
+
+    DcGather G;
+    G.key_ch = d->key_ch; G.m = m; G.inv_ch = d->inv_ch; G.inv_sr = d->inv_ch; G.inv_sn = d->inv_ch;
+    G.doff_sp = d->doff[0]; G.doff_ch = d->doff[1]; G.doff_sr = d->doff[1]; G.doff_sn = d->doff[1];
+    G.pos_sp = d->pos[1]; G.pos_ch = d->pos[1]; G.pos_sr = d->pos[1]; G.pos_sn = d->pos[1];
+    G.V_sp = d->V[1]; G.V_ch = d->V[1]; G.V_sr = d->V[1]; G.V_sn = d->V[1];
+    prof_begin(c, BSCGPU_K_DC_PSTREAM, (u64)E * 10, E);
+    if (c->ps_guard[0]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ps_guard[0], 0));     // the buffer's previous copy-out (a single-path block)
+    for (int b = 0; b < 8; ++b) if (c->ps_guard_sig[0][b]) (void)dma_wait(c->ps_guard_sig[0][b]);
+    hipLaunchKernelGGL((dc_pstream_kernel<true, false, DcSubTab>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp_fast, d->meta, d->ps[0], (u16*)nullptr, E, DcP13{});
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    prof_collect(c);
+    dc_note_block(c, d);
+    if (d->hmeta[DM_FAIL] != 0) return BSC_NOT_SUPPORTED;
+    if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder fast batch] sub-blocks %d, decisions %u, chunks replayed %u\n", nsub, E, d->hmeta[DM_REPLAYS]);
+    *D_out = E;
     return BSC_NO_ERROR;
 }
 

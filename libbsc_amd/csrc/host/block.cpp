@@ -1625,7 +1625,7 @@ static int store_from_device(bscgpu_ctx* c, const unsigned char* dIn, unsigned c
 // a model pass's sub-blocks as the device's range coder left them (BSCGPU_OPT_DEVICE_RC; see front_batch_code_rc)
 struct PassCoded { const uint8_t* bytes; const uint32_t* off; const int* res; const int* room; };
 static int front_batch_code_rc(const bscgpu_front_layout* Lo, int block, const uint8_t* bytes, const uint32_t* off, const int* res, const int* room_of,
-                               unsigned char* out, int features);
+                               unsigned char* out, int coder, int features);
 
 // the host tail of bsc_compress (libbsc.cpp:296-336) for one block of a sorted pass; input: host bytes, or dIn in HBM
 // (lay != nullptr: the block is entry li of a pass's front-end layout and is coded from its run arrays; else from its L at Lb)
@@ -1636,9 +1636,11 @@ static int code_sorted_block(bscgpu_ctx* c, const unsigned char* input, const un
 {
     unsigned char* buffer = (unsigned char*)bsc_malloc((size_t)B.lz + 4096);
     if (!buffer) return LIBBSC_NOT_ENOUGH_MEMORY;
-    // (ps: the pass's probability stream from the device model — the static coder's range coder alone)
-    int result = lay ? (pc ? front_batch_code_rc(lay, li, pc->bytes, pc->off, pc->res, pc->room, buffer, features)
-                           : ps ? bscgpu_front_batch_code_ps(lay, li, ps, poff, buffer, features) : bscgpu_front_batch_code(lay, li, buffer, coder, features))
+    // (ps: the pass's probability stream from the device model of this coder, static or fast — the range coder alone)
+    int result = lay ? (pc ? front_batch_code_rc(lay, li, pc->bytes, pc->off, pc->res, pc->room, buffer, coder, features)
+                           : ps ? (coder == LIBBSC_CODER_QLFC_FAST ? bscgpu_front_batch_code_psf(lay, li, ps, poff, buffer, features)
+                                                                   : bscgpu_front_batch_code_ps(lay, li, ps, poff, buffer, features))
+                                : bscgpu_front_batch_code(lay, li, buffer, coder, features))
                      : coder_compress(Lb, buffer, B.lz, coder, features);
     if (result >= LIBBSC_NO_ERROR) memcpy(output + LIBBSC_HEADER_SIZE, buffer, (size_t)result);
     bsc_free(buffer);
@@ -1746,7 +1748,7 @@ struct RunsFetch : RawFetch {                                       // a sub-blo
 };
 }
 
-extern "C" BSCGPU_API int64_t bscgpu_static_pstream_host(const bscgpu_front_layout* Lo, int s, uint16_t* out, int64_t cap)
+static int64_t pstream_host(const bscgpu_front_layout* Lo, int s, uint16_t* out, int64_t cap, int coder)
 {
     if (!Lo || s < 0 || s >= Lo->nsub || cap < 0 || (cap > 0 && !out)) return LIBBSC_BAD_PARAMETER;
     RunView V;
@@ -1755,11 +1757,19 @@ extern "C" BSCGPU_API int64_t bscgpu_static_pstream_host(const bscgpu_front_layo
     V.end = (uint32_t)(Lo->sub_start[s] + Lo->sub_size[s]);
     V.nsym = Lo->nsym[s];
     memcpy(V.first_seen, Lo->first_seen + 256 * (size_t)s, (size_t)V.nsym);
-    return qlfc_static_pstream_runs(V, out, cap);
+    return coder == LIBBSC_CODER_QLFC_FAST ? qlfc_fast_pstream_runs(V, out, cap) : qlfc_static_pstream_runs(V, out, cap);
+}
+extern "C" BSCGPU_API int64_t bscgpu_static_pstream_host(const bscgpu_front_layout* Lo, int s, uint16_t* out, int64_t cap)
+{
+    return pstream_host(Lo, s, out, cap, LIBBSC_CODER_QLFC_STATIC);
+}
+extern "C" BSCGPU_API int64_t bscgpu_fast_pstream_host(const bscgpu_front_layout* Lo, int s, uint16_t* out, int64_t cap)
+{
+    return pstream_host(Lo, s, out, cap, LIBBSC_CODER_QLFC_FAST);
 }
 
-extern "C" BSCGPU_API int bscgpu_front_batch_code_ps(const bscgpu_front_layout* Lo, int block, const uint16_t* ps, const uint32_t* poff,
-                                                     unsigned char* out, int features)
+static int front_batch_code_stream(const bscgpu_front_layout* Lo, int block, const uint16_t* ps, const uint32_t* poff,
+                                   unsigned char* out, int coder, int features)
 {
     if (!Lo || !out || !ps || !poff || block < 0 || block >= Lo->count) return LIBBSC_BAD_PARAMETER;
     const int s0 = Lo->blk_sub[block], nb = Lo->blk_sub[block + 1] - s0;
@@ -1769,22 +1779,33 @@ extern "C" BSCGPU_API int bscgpu_front_batch_code_ps(const bscgpu_front_layout* 
     RunsFetch fetch;
     fetch.views = views; fetch.st = Lo->sub_start + s0; fetch.sz = Lo->sub_size + s0; fetch.nb = nb;
     struct FromStream : SubEncode {                                 // the range coder alone: the model ran on the GPU
-        const bscgpu_front_layout* Lo; int s0; const uint16_t* ps; const uint32_t* poff;
+        const bscgpu_front_layout* Lo; int s0; const uint16_t* ps; const uint32_t* poff; bool fast;
         int operator()(int b, uint8_t* dst, int room) override
         {
             const int s = s0 + b;
-            return qlfc_encode_static_pstream(Lo->first_seen + 256 * (size_t)s, Lo->nsym[s], Lo->sub_size[s], ps + poff[s], (size_t)(poff[s + 1] - poff[s]), dst, room);
+            return (fast ? qlfc_encode_fast_pstream : qlfc_encode_static_pstream)(Lo->first_seen + 256 * (size_t)s, Lo->nsym[s], Lo->sub_size[s], ps + poff[s], (size_t)(poff[s + 1] - poff[s]), dst, room);
         }
     } enc;
-    enc.Lo = Lo; enc.s0 = s0; enc.ps = ps; enc.poff = poff;
-    return coder_compress_views(views, nb, Lo->sub_start + s0, Lo->sub_size + s0, Lo->sizes[block], out, LIBBSC_CODER_QLFC_STATIC, features, fetch, &enc);
+    enc.Lo = Lo; enc.s0 = s0; enc.ps = ps; enc.poff = poff; enc.fast = coder == LIBBSC_CODER_QLFC_FAST;
+    return coder_compress_views(views, nb, Lo->sub_start + s0, Lo->sub_size + s0, Lo->sizes[block], out, coder, features, fetch, &enc);
+}
+extern "C" BSCGPU_API int bscgpu_front_batch_code_ps(const bscgpu_front_layout* Lo, int block, const uint16_t* ps, const uint32_t* poff,
+                                                     unsigned char* out, int features)
+{
+    return front_batch_code_stream(Lo, block, ps, poff, out, LIBBSC_CODER_QLFC_STATIC, features);
+}
+// ... for the fast coder (-e0): the sub-blocks' streams in the BSCGPU_RC_FAST16 form, coded by qlfc_encode_fast_pstream
+extern "C" BSCGPU_API int bscgpu_front_batch_code_psf(const bscgpu_front_layout* Lo, int block, const uint16_t* ps, const uint32_t* poff,
+                                                      unsigned char* out, int features)
+{
+    return front_batch_code_stream(Lo, block, ps, poff, out, LIBBSC_CODER_QLFC_FAST, features);
 }
 
 // bscgpu_front_batch_code_ps with the range coder's work already done on the device: the framing alone.  A sub-block whose budget
 // under the caller's framing rule is not the one the device coded it with (the serial rule behind a sub-block stored raw) goes through
 // the host model from its runs; one that ended LIBBSC_NOT_COMPRESSIBLE is stored raw, rebuilt from its runs.
 static int front_batch_code_rc(const bscgpu_front_layout* Lo, int block, const uint8_t* bytes, const uint32_t* off, const int* res, const int* room_of,
-                               unsigned char* out, int features)
+                               unsigned char* out, int coder, int features)
 {
     const int s0 = Lo->blk_sub[block], nb = Lo->blk_sub[block + 1] - s0;
     if (nb < 1 || nb > 8) return LIBBSC_BAD_PARAMETER;
@@ -1793,17 +1814,17 @@ static int front_batch_code_rc(const bscgpu_front_layout* Lo, int block, const u
     RunsFetch fetch;
     fetch.views = views; fetch.st = Lo->sub_start + s0; fetch.sz = Lo->sub_size + s0; fetch.nb = nb;
     struct Coded : SubEncode {
-        const bscgpu_front_layout* Lo; const RunView* views; int s0; const uint8_t* bytes; const uint32_t* off; const int* res; const int* room_of;
+        const bscgpu_front_layout* Lo; const RunView* views; int s0; const uint8_t* bytes; const uint32_t* off; const int* res; const int* room_of; int coder;
         int operator()(int b, uint8_t* dst, int room) override
         {
             const int s = s0 + b;
-            if (room != room_of[s]) return qlfc_encode_runs(views[b], Lo->sub_size[s], dst, room, LIBBSC_CODER_QLFC_STATIC);
+            if (room != room_of[s]) return qlfc_encode_runs(views[b], Lo->sub_size[s], dst, room, coder);
             if (res[s] >= 0) memcpy(dst, bytes + off[s], (size_t)res[s]);
             return res[s];
         }
     } enc;
-    enc.Lo = Lo; enc.views = views; enc.s0 = s0; enc.bytes = bytes; enc.off = off; enc.res = res; enc.room_of = room_of;
-    return coder_compress_views(views, nb, Lo->sub_start + s0, Lo->sub_size + s0, Lo->sizes[block], out, LIBBSC_CODER_QLFC_STATIC, features, fetch, &enc);
+    enc.Lo = Lo; enc.views = views; enc.s0 = s0; enc.bytes = bytes; enc.off = off; enc.res = res; enc.room_of = room_of; enc.coder = coder;
+    return coder_compress_views(views, nb, Lo->sub_start + s0, Lo->sub_size + s0, Lo->sizes[block], out, coder, features, fetch, &enc);
 }
 
 extern "C" BSCGPU_API int bscgpu_qlfc_front_batch_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out)
@@ -1825,8 +1846,8 @@ extern "C" BSCGPU_API int bscgpu_qlfc_front_batch_device(bscgpu_ctx* c, const vo
     return LIBBSC_NO_ERROR;
 }
 
-extern "C" BSCGPU_API int64_t bscgpu_static_pstream_batch_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out,
-                                                                 uint16_t* ps, int64_t cap, uint32_t* poff)
+static int64_t pstream_batch_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out,
+                                    uint16_t* ps, int64_t cap, uint32_t* poff, int coder)
 {
     if (!c || !poff || cap < 0 || (cap > 0 && !ps)) return LIBBSC_BAD_PARAMETER;
     const int frc = bscgpu_qlfc_front_batch_device(c, dL, sizes, count, out);
@@ -1834,7 +1855,8 @@ extern "C" BSCGPU_API int64_t bscgpu_static_pstream_batch_device(bscgpu_ctx* c, 
     poff[0] = 0;
     if (out->nsub == 0) return 0;
     u32 D = 0;
-    const int rc = devcoder_pstream_batch(c, (u32)out->m, out->nsub, &D);
+    const int rc = coder == LIBBSC_CODER_QLFC_FAST ? devcoder_pstream_fast_batch(c, (u32)out->m, out->nsub, &D)
+                                                   : devcoder_pstream_batch(c, (u32)out->m, out->nsub, &D);
     if (rc == LIBBSC_NOT_SUPPORTED) {
         char buf[96]; snprintf(buf, sizeof buf, "device coder declined the pass (reason mask %d)", c->dc_last_fail);
         c->err = buf;
@@ -1844,6 +1866,16 @@ extern "C" BSCGPU_API int64_t bscgpu_static_pstream_batch_device(bscgpu_ctx* c, 
     if ((int64_t)D <= cap && D > 0 && hipMemcpyAsync(ps, devcoder_pstream_ptr(c, 0), (size_t)D * 2, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return LIBBSC_GPU_ERROR;
     if (ctx_sync(c) != hipSuccess) return LIBBSC_GPU_ERROR;
     return (int64_t)D;
+}
+extern "C" BSCGPU_API int64_t bscgpu_static_pstream_batch_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out,
+                                                                 uint16_t* ps, int64_t cap, uint32_t* poff)
+{
+    return pstream_batch_device(c, dL, sizes, count, out, ps, cap, poff, LIBBSC_CODER_QLFC_STATIC);
+}
+extern "C" BSCGPU_API int64_t bscgpu_fast_pstream_batch_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out,
+                                                               uint16_t* ps, int64_t cap, uint32_t* poff)
+{
+    return pstream_batch_device(c, dL, sizes, count, out, ps, cap, poff, LIBBSC_CODER_QLFC_FAST);
 }
 
 namespace {
@@ -1883,11 +1915,16 @@ int bschost::coder_threads() { return default_coder_threads(); }
 // syncs, the stream's copy) is more than the host spends on the pass's model.  Measured ("The static coder's model of a
 // pass": tools/batch_bench.py --model-sweep): a call of one pass loses up to 8 MiB and wins from 16 MiB.
 // BSC_BATCH_MODEL_MIN_PASS in the environment overrides it (read per call: the sweep and the tests run with 0).
+// The fast coder's route (BSCGPU_OPT_BATCH_MODEL_FAST) has a minimum of its own from its own sweep ("The fast coder's
+// model of a pass"): a call of one pass loses at every swept size, 64 KiB .. 16 MiB, so no swept size qualifies; the minimum is the
+// next power of two above the sweep, below the 64 MiB passes of the several-pass calls that gain.  The environment variable
+// overrides both.
 constexpr int64_t BATCH_MODEL_MIN_PASS_DEFAULT = 16 << 20;
-static int64_t batch_model_min_pass()
+constexpr int64_t BATCH_MODEL_FAST_MIN_PASS_DEFAULT = 32 << 20;
+static int64_t batch_model_min_pass(bool fast)
 {
     const char* e = getenv("BSC_BATCH_MODEL_MIN_PASS");
-    return e ? (int64_t)atoll(e) : BATCH_MODEL_MIN_PASS_DEFAULT;
+    return e ? (int64_t)atoll(e) : fast ? BATCH_MODEL_FAST_MIN_PASS_DEFAULT : BATCH_MODEL_MIN_PASS_DEFAULT;
 }
 
 // BSCGPU_OPT_DEVICE_RC for a model pass: every sub-block stream of the pass through ONE launch of the device's range coder
@@ -1896,7 +1933,7 @@ static int64_t batch_model_min_pass()
 // sorter's first key buffer, dead until the next pass's sort (8 max_n bytes; the regions take n + 128 nsub at most); only the regions
 // and res[] come down.  A sub-block is coded with the budget both framing rules give it when nothing in front of it was stored raw:
 // its size, or n - 1 for a block of one sub-block.
-static int device_rc_pass(bscgpu_ctx* c, PassLayout& PL, uint8_t* host_bytes, size_t host_cap)
+static int device_rc_pass(bscgpu_ctx* c, PassLayout& PL, uint8_t* host_bytes, size_t host_cap, int coder)
 {
     const bscgpu_front_layout& Y = PL.lay;
     const int nsub = Y.nsub;
@@ -1910,7 +1947,7 @@ static int device_rc_pass(bscgpu_ctx* c, PassLayout& PL, uint8_t* host_bytes, si
             qlfc_front_first_seen(PL.first_run + 256 * (size_t)s, Y.first_seen + 256 * (size_t)s, &Y.nsym[s]);
             const size_t at = prefix.size();
             prefix.resize(at + BSCGPU_RC_PREFIX_MAX);
-            const int np = bscgpu_rc_prefix(Y.first_seen + 256 * (size_t)s, Y.nsym[s], Y.sub_size[s], LIBBSC_CODER_QLFC_STATIC, prefix.data() + at, BSCGPU_RC_PREFIX_MAX);
+            const int np = bscgpu_rc_prefix(Y.first_seen + 256 * (size_t)s, Y.nsym[s], Y.sub_size[s], coder, prefix.data() + at, BSCGPU_RC_PREFIX_MAX);
             if (np < 0) return np;
             prefix.resize(at + (size_t)np);
             PL.rc_room[s] = nb == 1 ? Y.sub_size[s] - 1 : Y.sub_size[s];
@@ -1923,7 +1960,7 @@ static int device_rc_pass(bscgpu_ctx* c, PassLayout& PL, uint8_t* host_bytes, si
     }
     if ((size_t)off > (size_t)8 * (size_t)c->max_n || (size_t)off > host_cap) return LIBBSC_NOT_SUPPORTED;
     uint8_t* dOut = reinterpret_cast<uint8_t*>(c->kA);
-    const int rc = rc_encode_device(c, BSCGPU_RC_STATIC16, devcoder_pstream_ptr(c, 0), prefix.data(), (int)prefix.size(), S.data(), nsub, dOut, PL.rc_res.data(), 8);
+    const int rc = rc_encode_device(c, coder == LIBBSC_CODER_QLFC_FAST ? BSCGPU_RC_FAST16 : BSCGPU_RC_STATIC16, devcoder_pstream_ptr(c, 0), prefix.data(), (int)prefix.size(), S.data(), nsub, dOut, PL.rc_res.data(), 8);
     if (rc < 0) return rc;
     if (hipMemcpyAsync(host_bytes, dOut, (size_t)off, hipMemcpyDeviceToHost, c->stream) != hipSuccess || ctx_sync(c) != hipSuccess) return LIBBSC_GPU_ERROR;
     PL.rc_bytes = host_bytes;
@@ -1958,8 +1995,10 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
     const bool front = npass > 0 && c->batch_front != 0 && ctx_ensure_front_host(c) == LIBBSC_NO_ERROR;
     // ... and the static coder's model behind it (BSCGPU_OPT_BATCH_MODEL); its two pinned stream buffers are allocated by the first pass
     // that qualifies, and without them the passes keep the host model
-    const bool model = front && c->batch_model != 0 && coder == LIBBSC_CODER_QLFC_STATIC;
-    const int64_t model_min_pass = batch_model_min_pass();
+    // ... or the fast coder's (BSCGPU_OPT_BATCH_MODEL_FAST: an option and counters of its own); -e2 stays on the host
+    const bool fast_model = front && c->batch_model_fast != 0 && coder == LIBBSC_CODER_QLFC_FAST;
+    const bool model = fast_model || (front && c->batch_model != 0 && coder == LIBBSC_CODER_QLFC_STATIC);
+    const int64_t model_min_pass = batch_model_min_pass(fast_model);
     const size_t frontN = ((size_t)c->max_n + 4096 + 4095) / 4096 * 4096;
     std::vector<PassLayout> lays(2);
     const int threads = default_coder_threads();
@@ -2036,8 +2075,9 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
                     // the model behind the front end, on the same stream, before the next pass's sort; the run arrays came down all the
                     // same: they serve a declined pass, a sub-block stored raw and the <= 28-byte blocks that rode along
                     u32 D = 0;
-                    const int mrc = devcoder_pstream_batch(c, (u32)PL.lay.m, PL.lay.nsub, &D);
-                    if (mrc == LIBBSC_NOT_SUPPORTED) ++c->cnt_model_declined;
+                    const int mrc = fast_model ? devcoder_pstream_fast_batch(c, (u32)PL.lay.m, PL.lay.nsub, &D)
+                                               : devcoder_pstream_batch(c, (u32)PL.lay.m, PL.lay.nsub, &D);
+                    if (mrc == LIBBSC_NOT_SUPPORTED) ++(fast_model ? c->cnt_model_fast_declined : c->cnt_model_declined);
                     else if (mrc < 0) { rc = mrc; break; }
                     else if ((size_t)D <= c->model_host_entries) {
                         PL.poff.resize((size_t)PL.lay.nsub + 1);
@@ -2047,11 +2087,11 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
                             (!drc && D > 0 && hipMemcpyAsync(hps, devcoder_pstream_ptr(c, 0), (size_t)D * 2, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
                             ctx_sync(c) != hipSuccess) { rc = LIBBSC_GPU_ERROR; break; }
                         if (drc) {
-                            rc = device_rc_pass(c, PL, reinterpret_cast<uint8_t*>(hps), c->model_host_entries * 2);
+                            rc = device_rc_pass(c, PL, reinterpret_cast<uint8_t*>(hps), c->model_host_entries * 2, coder);
                             if (rc < 0) break;
                             ++c->cnt_device_rc;
                         } else PL.ps = hps;
-                        ++c->cnt_model_passes;
+                        ++(fast_model ? c->cnt_model_fast_passes : c->cnt_model_passes);
                     }
                 }
             } else {

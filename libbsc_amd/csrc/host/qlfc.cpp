@@ -540,65 +540,111 @@ struct Counters2 {
 };
 template <int R> static inline void nudge(short& p, int target) { p = (short)(p - ((p - target) >> R)); }
 
-static int encode_model2(const RunView& R, uint8_t* out, int in_size, int out_size)
+// The fast coder's walker: every binary decision of a sub-block in stream order, handed to a policy with the counter's value BEFORE
+// the update (the update itself is done here).  pol.code<PREC>(bit, p): PREC = 13 on the rank side of a run, 11 on the run side.
+// One policy codes directly (encode_model2), the other records the stream (qlfc_fast_pstream_runs: the device model's stand-in).
+// Returns false when the policy aborts at a run start.
+template <class Policy>
+static BSC_ALWAYS_INLINE bool walk_model2(const RunView& R, Counters2& K, Policy& pol)
 {
-    std::unique_ptr<Counters2> Cn(new Counters2);
-    fill_shorts(Cn->r_exp, sizeof(Cn->r_exp) + sizeof(Cn->r_mant), 4096);      // qlfc_model.cpp:74
-    fill_shorts(Cn->n_exp, sizeof(Cn->n_exp) + sizeof(Cn->n_mant), 1024);      // qlfc_model.cpp:75
-    Counters2& K = *Cn;
-
-    RangeEncoder rc;
-    rc.init(out, out_size);
-    rc.encode_word((uint32_t)in_size);
-    encode_alphabet(R, [&](unsigned b) { rc.encode<1>(b, 1); });               // qlfc.cpp:1174
-
     const uint32_t m = R.count;
     for (uint32_t j = 0; j < m; ++j) {
-        if (rc.full()) return NOT_COMPRESSIBLE;
+        if (!pol.begin_run()) return false;
         const int c = R.sym[j];
         const unsigned rank = R.rank[j];
         const unsigned run = R.len(j);
         {
             short* e = K.r_exp[c];
-            if (rank == 1) { const int p = e[0]; nudge<4>(e[0], 8016); rc.encode<13>(0, p); }
+            if (rank == 1) { const int p = e[0]; nudge<4>(e[0], 8016); pol.template code<13>(0, p); }
             else {
-                { const int p = e[0]; nudge<4>(e[0], 83); rc.encode<13>(1, p); }
+                { const int p = e[0]; nudge<4>(e[0], 83); pol.template code<13>(1, p); }
                 const int bits = bsr32(rank);
-                for (int b = 1; b < bits; ++b) { const int p = e[b]; nudge<4>(e[b], 122); rc.encode<13>(1, p); }
-                if (bits < 7) { const int p = e[bits]; nudge<4>(e[bits], 8114); rc.encode<13>(0, p); }
+                for (int b = 1; b < bits; ++b) { const int p = e[b]; nudge<4>(e[b], 122); pol.template code<13>(1, p); }
+                if (bits < 7) { const int p = e[bits]; nudge<4>(e[bits], 8114); pol.template code<13>(0, p); }
                 short* mt = K.r_mant[c][bits];
                 for (int ctx = 1, b = bits - 1; b >= 0; --b) {
                     const unsigned v = (rank >> b) & 1u;
-                    const int p = mt[ctx]; nudge<7>(mt[ctx], v ? 235 : 7999); rc.encode<13>(v, p);
+                    const int p = mt[ctx]; nudge<7>(mt[ctx], v ? 235 : 7999); pol.template code<13>(v, p);
                     ctx += ctx + (int)v;
                 }
             }
         }
         {
             short* e = K.n_exp[c];
-            if (run == 1) { const int p = e[0]; nudge<5>(e[0], 2025); rc.encode<11>(0, p); }
+            if (run == 1) { const int p = e[0]; nudge<5>(e[0], 2025); pol.template code<11>(0, p); }
             else {
-                { const int p = e[0]; nudge<5>(e[0], 42); rc.encode<11>(1, p); }
+                { const int p = e[0]; nudge<5>(e[0], 42); pol.template code<11>(1, p); }
                 const int bits = bsr32(run);
-                for (int b = 1; b < bits; ++b) { const int p = e[b]; nudge<4>(e[b], 142); rc.encode<11>(1, p); }
-                { const int p = e[bits]; nudge<4>(e[bits], 1962); rc.encode<11>(0, p); }
+                for (int b = 1; b < bits; ++b) { const int p = e[b]; nudge<4>(e[b], 142); pol.template code<11>(1, p); }
+                { const int p = e[bits]; nudge<4>(e[bits], 1962); pol.template code<11>(0, p); }
                 short* mt = K.n_mant[c][bits];
                 if (bits <= 5) {
                     for (int ctx = 1, b = bits - 1; b >= 0; --b) {
                         const unsigned v = (run >> b) & 1u;
-                        const int p = mt[ctx]; nudge<6>(mt[ctx], v ? 147 : 1951); rc.encode<11>(v, p);
+                        const int p = mt[ctx]; nudge<6>(mt[ctx], v ? 147 : 1951); pol.template code<11>(v, p);
                         ctx += ctx + (int)v;
                     }
                 } else {
                     for (int ctx = 1, b = bits - 1; b >= 0; --b, ++ctx) {
                         const unsigned v = (run >> b) & 1u;
-                        const int p = mt[ctx]; nudge<5>(mt[ctx], v ? 46 : 1987); rc.encode<11>(v, p);
+                        const int p = mt[ctx]; nudge<5>(mt[ctx], v ? 46 : 1987); pol.template code<11>(v, p);
                     }
                 }
             }
         }
     }
+    return true;
+}
+
+static void init_counters2(Counters2& K)
+{
+    fill_shorts(K.r_exp, sizeof(K.r_exp) + sizeof(K.r_mant), 4096);      // qlfc_model.cpp:74
+    fill_shorts(K.n_exp, sizeof(K.n_exp) + sizeof(K.n_mant), 1024);      // qlfc_model.cpp:75
+}
+
+namespace {
+struct DirectPolicy2 {
+    RangeEncoder& rc;
+    BSC_ALWAYS_INLINE bool begin_run() { return !rc.full(); }
+    template <int PREC> BSC_ALWAYS_INLINE void code(unsigned bit, int p) { rc.encode<PREC>(bit, p); }
+};
+// the device model's entries (devcoder_model.h PSF_*): {[12:0] counter value, [13] bit, [14] first decision of a run, [15] run side}
+struct RecordPolicy2 {
+    uint16_t* out; int64_t cap; int64_t n = 0; unsigned first = 0;
+    inline bool begin_run() { first = 1u << 14; return true; }
+    template <int PREC> BSC_ALWAYS_INLINE void code(unsigned bit, int p)
+    {
+        if (n < cap) out[n] = (uint16_t)((unsigned)p | (bit << 13) | first | (PREC == 11 ? 1u << 15 : 0u));
+        ++n; first = 0;
+    }
+};
+}
+
+static int encode_model2(const RunView& R, uint8_t* out, int in_size, int out_size)
+{
+    std::unique_ptr<Counters2> Cn(new Counters2);
+    init_counters2(*Cn);
+
+    RangeEncoder rc;
+    rc.init(out, out_size);
+    rc.encode_word((uint32_t)in_size);
+    encode_alphabet(R, [&](unsigned b) { rc.encode<1>(b, 1); });               // qlfc.cpp:1174
+
+    DirectPolicy2 pol{rc};
+    if (!walk_model2(R, *Cn, pol)) return NOT_COMPRESSIBLE;
     return rc.finish();
+}
+
+// The device fast model's CPU stand-in: the host fast coder's own walk, recording what the range coder would have been given instead
+// of coding it.  Returns the number of decisions; entries past cap are counted, not written.
+int64_t qlfc_fast_pstream_runs(const RunView& R, uint16_t* out, int64_t cap)
+{
+    if (R.nsym <= 0) return BAD_PARAMETER;
+    std::unique_ptr<Counters2> Cn(new Counters2);
+    init_counters2(*Cn);
+    RecordPolicy2 pol{out, cap};
+    (void)walk_model2(R, *Cn, pol);
+    return pol.n;
 }
 
 // ------------------------------------------------------------------------------------------------

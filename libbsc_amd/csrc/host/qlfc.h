@@ -82,6 +82,9 @@ void qlfc_pack_p13(const uint16_t* ps, size_t count, uint8_t* out);
 // The fast coder's back half (-e0, qlfc.cpp:1135-1336) behind the device model: entries {[12:0] probability, [13] bit, [14] first
 // decision of a run, [15] run side = 11-bit precision, else 13} (devcoder_model.h PSF_*); header and alphabet as encode_model2 writes them.
 int qlfc_encode_fast_pstream(const uint8_t* first_seen, int nsym, int in_size, const uint16_t* ps, size_t count, uint8_t* out, int out_size);
+// The fast model's probability stream of one sub-block on the CPU (the device model's stand-in: encode_model2's walk, recording instead
+// of coding): entries as above to out[0 .. cap); returns the number of decisions (those past cap are counted only).
+int64_t qlfc_fast_pstream_runs(const RunView& R, uint16_t* out, int64_t cap);
 void qlfc_encode_fast_pstream_pair(const PstreamJob& A, const PstreamJob& B, int* resA, int* resB);
 bool qlfc_encode_fast_pstream_x8(const PstreamJob* J, int* res);      // eight sub-blocks in SIMD lanes, per-lane precision (as qlfc_encode_static_pstream_x8)
 // Encode one sub-block (what coder.cpp:61 dispatches to).  Returns bytes written or NOT_COMPRESSIBLE.

@@ -276,6 +276,20 @@ class GpuContext:
             raise GpuError(-2, f"{D} decisions exceed the buffer of {cap}")
         return fb, out[:D], poff[:fb.nsub + 1]
 
+    def fast_pstream_batch(self, dL, sizes):
+        """bscgpu_fast_pstream_batch_device: static_pstream_batch for the fast coder (-e0) -> (FrontBatch, entries np.uint16[D] in the
+        RC_FAST16 form, poff np.uint32[nsub + 1]); raises GpuError -4 when the device declines the pass"""
+        fb = FrontBatch(sizes)
+        cap = 4 * int(self.max_n) + 65536                       # the device model's own capacity in decisions
+        out = np.empty(cap, np.uint16)
+        poff = np.zeros(2 * fb.count + 2, np.uint32)
+        D = int(self.L.bscgpu_fast_pstream_batch_device(self.h, _dptr(dL), N.np_ptr(fb.sizes), fb.count, C.byref(fb.lay), N.np_ptr(out), cap,
+                                                        N.np_ptr(poff)))
+        self._check(D)
+        if D > cap:
+            raise GpuError(-2, f"{D} decisions exceed the buffer of {cap}")
+        return fb, out[:D], poff[:fb.nsub + 1]
+
     # ---- batched decompression (one inverse-BWT pass for many blocks, include/bscgpu.h) -------
     def unbwt_batch(self, dL, sizes, primary, dT=None):
         """inverse BWT of every block of a batch laid out back to back in the uint8 device tensor dL (primary: 1-based indexes) ->
@@ -336,6 +350,7 @@ class GpuContext:
     OPT_BATCH_FRONT, CNT_BATCH_FRONT_PASSES, CNT_BATCH_L_PASSES = 9, 10, 11     # the compress-batch passes' route and how many took each
     OPT_DEVICE_RC, CNT_DEVICE_RC_BLOCKS = 12, 13       # a device-model block's streams are range-coded on the GPU (default 0) and how many were
     OPT_BATCH_MODEL, CNT_BATCH_MODEL_PASSES, CNT_BATCH_MODEL_DECLINED = 14, 15, 16    # the static coder's model of a compress-batch pass on the GPU
+    OPT_BATCH_MODEL_FAST, CNT_BATCH_FAST_PASSES, CNT_BATCH_FAST_DECLINED = 17, 18, 19    # ... the fast coder's (-e0), an option of its own
     CNT_DC_REPLAYS, CNT_DC_LAST_FAIL, CNT_DC_AVG_UNDECIDED, CNT_DC_HIST_EXTENDED = 5, 6, 7, 8      # the last device-model block (get only)
     DC_FAIL_AVG, DC_FAIL_HIST, DC_FAIL_CAP, DC_FAIL_REPLAY = 2, 4, 8, 16                          # BSCGPU_DC_FAIL_*
 
@@ -497,6 +512,33 @@ def front_batch_code_ps(fb, block, ps, poff, features=3):
         p = np.zeros(1, np.uint16)
     out = np.empty(int(fb.sizes[block]) + 4096, np.uint8)
     r = int(N.lib().bscgpu_front_batch_code_ps(C.byref(fb.lay), int(block), N.np_ptr(p), N.np_ptr(o), N.np_ptr(out), int(features)))
+    return out[:r].tobytes() if r >= 0 else r
+
+
+def fast_pstream_host(fb, s):
+    """bscgpu_fast_pstream_host: GpuContext.fast_pstream_batch's CPU stand-in for sub-block s of a FrontBatch (no GPU): the host fast
+    coder's own walk, recording {[12:0] counter value, [13] bit, [14] run start, [15] run side} instead of coding -> np.uint16 entries"""
+    cap = 16 * int(fb.sub_size[s]) + 64
+    out = np.empty(cap, np.uint16)
+    n = int(N.lib().bscgpu_fast_pstream_host(C.byref(fb.lay), int(s), N.np_ptr(out), cap))
+    if n < 0:
+        raise GpuError(n, "bscgpu_fast_pstream_host")
+    if n > cap:
+        out = np.empty(n, np.uint16)
+        n = int(N.lib().bscgpu_fast_pstream_host(C.byref(fb.lay), int(s), N.np_ptr(out), n))
+    return out[:n]
+
+
+def front_batch_code_psf(fb, block, ps, poff, features=3):
+    """bscgpu_front_batch_code_psf: FrontBatch.code for the fast coder from the sub-blocks' streams (ps uint16 entries in the RC_FAST16
+    form, sub-block s at poff[s]) -> bytes, or its negative code"""
+    p = np.ascontiguousarray(ps, dtype=np.uint16)
+    o = np.ascontiguousarray(poff, dtype=np.uint32)
+    assert o.size == fb.nsub + 1 and (p.size >= int(o[-1]))
+    if p.size == 0:
+        p = np.zeros(1, np.uint16)
+    out = np.empty(int(fb.sizes[block]) + 4096, np.uint8)
+    r = int(N.lib().bscgpu_front_batch_code_psf(C.byref(fb.lay), int(block), N.np_ptr(p), N.np_ptr(o), N.np_ptr(out), int(features)))
     return out[:r].tobytes() if r >= 0 else r
 
 

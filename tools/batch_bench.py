@@ -47,6 +47,8 @@ bscgpu_static_pstream_batch_device, wall and the HIP-event time per kernel class
 the front end beside them).  The on legs also run with BSCGPU_OPT_DEVICE_RC = 1 (the pass's streams coded by one launch of the
 device's range coder).  --model-sweep: on against off on passes of 64 KiB .. 16 MiB cut from the workload's text — the smallest pass
 the model route wins on (run it with BSC_BATCH_MODEL_MIN_PASS=0 in the environment).  Raw output belongs under profiles/batch_model/.
+With --coder 3 all three drive the fast coder's route instead (BSCGPU_OPT_BATCH_MODEL_FAST, -e0, bscgpu_fast_pstream_batch_device; the
+stage-alone leg adds the pass's decisions per byte from the CPU stand-in); raw output under profiles/batch_fast/.
     python tools/batch_bench.py --model [--model-only | --model-sweep] [--reps 3] [--workloads W1,W2,W3]
 """
 import argparse
@@ -348,9 +350,14 @@ def model_main(args):
     import torch
     from libbsc_amd import GpuContext
     from libbsc_amd.gpu import GpuError, batch_plan
-    coder = 1
+    # --coder 3: the fast coder's route (BSCGPU_OPT_BATCH_MODEL_FAST and its own counters); anything else: the static coder's
+    fast = args.coder == 3
+    coder = 3 if fast else 1
     ctx = GpuContext(0, max_n=(64 << 20) + 4096)
-    OPT = ctx.OPT_BATCH_MODEL
+    OPT = ctx.OPT_BATCH_MODEL_FAST if fast else ctx.OPT_BATCH_MODEL
+    CNT_PASSES = ctx.CNT_BATCH_FAST_PASSES if fast else ctx.CNT_BATCH_MODEL_PASSES
+    CNT_DECLINED = ctx.CNT_BATCH_FAST_DECLINED if fast else ctx.CNT_BATCH_MODEL_DECLINED
+    stage = ctx.fast_pstream_batch if fast else ctx.static_pstream_batch
     pctx = [GpuContext(0, max_n=(1 << 20) + 4096) for _ in range(0 if (args.model_only or args.model_sweep) else args.contexts)]
     pipes = [c.pipe(args.depth) for c in pctx]
     CLASSES = {"contexts": ("dc_ctx",), "sorts": ("radix_scatter", "radix_hist", "radix_scan", "radix_hist_all", "radix_aux"),
@@ -383,12 +390,12 @@ def model_main(args):
                     for _ in range(max(args.reps, 5)):
                         for v in (1, 0):
                             ctx.option_set(OPT, v)
-                            p0 = ctx.option_get(ctx.CNT_BATCH_MODEL_PASSES)
+                            p0 = ctx.option_get(CNT_PASSES)
                             _, wall, _ = timed(lambda: ctx.compress_batch(part, 1, coder))
                             t[v].append(round(wall * 1e3, 3))
                             if v:
-                                kept_n = ctx.option_get(ctx.CNT_BATCH_MODEL_PASSES) - p0
-                    print(json.dumps({"workload": name, "leg": "model_sweep", "pass_bytes": total, "blocks": len(part), "model_passes_per_call": kept_n,
+                                kept_n = ctx.option_get(CNT_PASSES) - p0
+                    print(json.dumps({"workload": name, "leg": "model_sweep", "coder": coder, "pass_bytes": total, "blocks": len(part), "model_passes_per_call": kept_n,
                                       "on_ms": t[1], "off_ms": t[0], "on_median_ms": float(np.median(t[1])), "off_median_ms": float(np.median(t[0]))}), flush=True)
                 continue
             if args.model_only:
@@ -398,9 +405,16 @@ def model_main(args):
                 total = sum(psz)
                 dL = torch.empty(total, dtype=torch.uint8, device="cuda")
                 ctx.bwt_batch(flat[:total], psz, aux=False, dL=dL)
-                rec = {"workload": name, "leg": "model_only", "blocks": cnt, "MB": round(total / 1e6, 2)}
+                rec = {"workload": name, "leg": "model_only", "coder": coder, "blocks": cnt, "MB": round(total / 1e6, 2)}
+                if fast:                                                          # decisions per byte from the CPU stand-in: does the pass fit 4 per byte?
+                    from libbsc_amd import _native as N
+                    from libbsc_amd.gpu import front_batch_host
+                    import ctypes as C
+                    hfb = front_batch_host(dL.cpu().numpy(), psz)
+                    dec = sum(int(N.lib().bscgpu_fast_pstream_host(C.byref(hfb.lay), s, None, 0)) for s in range(hfb.nsub))
+                    rec["decisions_per_byte_stand_in"] = round(dec / total, 3)
                 try:
-                    fb, ps, _ = ctx.static_pstream_batch(dL, psz)                 # warm-up: arenas, tables, first launches
+                    fb, ps, _ = stage(dL, psz)                                    # warm-up: arenas, tables, first launches
                 except GpuError as e:
                     print(json.dumps({**rec, "declined": e.code, "last_fail": ctx.option_get(ctx.CNT_DC_LAST_FAIL)}), flush=True)
                     continue
@@ -409,7 +423,7 @@ def model_main(args):
                 for _ in range(args.reps):
                     ctx.profile_reset()
                     t0 = time.perf_counter()
-                    ctx.static_pstream_batch(dL, psz)
+                    stage(dL, psz)
                     tw.append(round((time.perf_counter() - t0) * 1e3, 2))
                     st = ctx.profile_get()
                     for k, names in CLASSES.items():
@@ -439,10 +453,10 @@ def model_main(args):
                     else:
                         ctx.option_set(OPT, how[0])
                         ctx.option_set(ctx.OPT_DEVICE_RC, how[2])
-                        p0, d0 = ctx.option_get(ctx.CNT_BATCH_MODEL_PASSES), ctx.option_get(ctx.CNT_BATCH_MODEL_DECLINED)
+                        p0, d0 = ctx.option_get(CNT_PASSES), ctx.option_get(CNT_DECLINED)
                         out, wall, cpu = timed((lambda: ctx.compress_batch_device(flat, sizes, 1, coder)) if how[1] else (lambda: ctx.compress_batch(blocks, 1, coder)))
-                        kept[leg] = ctx.option_get(ctx.CNT_BATCH_MODEL_PASSES) - p0
-                        declined[leg] = ctx.option_get(ctx.CNT_BATCH_MODEL_DECLINED) - d0
+                        kept[leg] = ctx.option_get(CNT_PASSES) - p0
+                        declined[leg] = ctx.option_get(CNT_DECLINED) - d0
                     walls[leg].append(wall); cpus[leg].append(cpu)
                     same[leg] = same[leg] and digest(out) == want
             for leg in legs:
@@ -475,7 +489,7 @@ def main():
     ap.add_argument("--profile-pass", action="store_true", help="with --decode: one decompress_batch per workload and config, nothing timed")
     ap.add_argument("--front", action="store_true", help="BSCGPU_OPT_BATCH_FRONT on against off, interleaved (BWT, --coder)")
     ap.add_argument("--front-only", action="store_true", help="with --front: the front-end stage alone against a loop of the single-block front end")
-    ap.add_argument("--model", action="store_true", help="BSCGPU_OPT_BATCH_MODEL on against off, interleaved (BWT, -e1)")
+    ap.add_argument("--model", action="store_true", help="BSCGPU_OPT_BATCH_MODEL on against off, interleaved (BWT, -e1); with --coder 3: BSCGPU_OPT_BATCH_MODEL_FAST (-e0)")
     ap.add_argument("--model-only", action="store_true", help="with --model: the model stage alone on one pass, per kernel class")
     ap.add_argument("--model-sweep", action="store_true", help="with --model: on against off on passes of 64 KiB .. 16 MiB (set BSC_BATCH_MODEL_MIN_PASS=0)")
     args = ap.parse_args()
