@@ -56,6 +56,10 @@ BSCGPU_API int64_t bscgpu_bwt_aux(bscgpu_ctx* ctx, const uint8_t* T, uint8_t* L,
 /* Device-resident variant: dT, dL are device pointers (may alias); I is a HOST array or NULL
  * (r ignored when I is NULL).  Returns the primary index. */
 BSCGPU_API int64_t bscgpu_bwt_device(bscgpu_ctx* ctx, const void* dT, void* dL, int64_t n, int64_t r, uint32_t* I);
+/* The first sort of that transform alone (tests): byte histogram, key packing and the radix sort on the packed prefix keys exactly as
+ * bscgpu_bwt_device runs them for this block, the n sorted (u64 key, u32 value) records copied to d_keys_out / d_vals_out (device
+ * pointers).  Returns 0 or a negative libbsc code. */
+BSCGPU_API int bscgpu_bwt_first_sort_device(bscgpu_ctx* ctx, const void* dT, int64_t n, void* d_keys_out, void* d_vals_out);
 
 /* ---- inverse BWT (libcubwt_unbwt's role, libcubwt.cuh:91-104; reached from bsc_bwt_decode, bwt.cpp:233-281) ---------- */
 /* L[0..n) and the 1-based primary index as bsc_bwt_encode writes them -> T[0..n); host pointers, may alias; synchronous.
@@ -491,13 +495,19 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          Default 0: measured, it gains on calls of several full passes (4 % from host input, 10 % from HBM, a quarter
  *                          less CPU per MB) and loses 9 - 19 % on one-pass calls.
  * BSCGPU_CNT_BATCH_FAST_PASSES, BSCGPU_CNT_BATCH_FAST_DECLINED  (get only) its passes coded from the device's stream, and declined.
+ * BSCGPU_OPT_BWT_FOLD      1 (default; BSC_BWT_FOLD=0 in the environment turns it off): where the first-sort key of a single block leaves
+ *                          1..4 bits over a whole number of bytes (17..64 symbols) and the sort takes the single-read passes, key
+ *                          packing places the records by those bits and counts the byte digits, and the sort is one pass shorter
+ *                          and reads no histogram.  2: packing places the records, rs_hist_all still counts (measurements).  Same output.
+ * BSCGPU_CNT_BWT_FOLDED    (get only) first sorts of this context that took that route.
  * set returns the previous value or a negative libbsc error code; get the value or a negative error code. */
 enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACKED_STREAM = 4,
        BSCGPU_CNT_DC_REPLAYS = 5, BSCGPU_CNT_DC_LAST_FAIL = 6, BSCGPU_CNT_DC_AVG_UNDECIDED = 7, BSCGPU_CNT_DC_HIST_EXTENDED = 8,
        BSCGPU_OPT_BATCH_FRONT = 9, BSCGPU_CNT_BATCH_FRONT_PASSES = 10, BSCGPU_CNT_BATCH_L_PASSES = 11,
        BSCGPU_OPT_DEVICE_RC = 12, BSCGPU_CNT_DEVICE_RC_BLOCKS = 13,
        BSCGPU_OPT_BATCH_MODEL = 14, BSCGPU_CNT_BATCH_MODEL_PASSES = 15, BSCGPU_CNT_BATCH_MODEL_DECLINED = 16,
-       BSCGPU_OPT_BATCH_MODEL_FAST = 17, BSCGPU_CNT_BATCH_FAST_PASSES = 18, BSCGPU_CNT_BATCH_FAST_DECLINED = 19 };
+       BSCGPU_OPT_BATCH_MODEL_FAST = 17, BSCGPU_CNT_BATCH_FAST_PASSES = 18, BSCGPU_CNT_BATCH_FAST_DECLINED = 19,
+       BSCGPU_OPT_BWT_FOLD = 20, BSCGPU_CNT_BWT_FOLDED = 21 };
 /* _FAIL_AVG: undecided avg_rank flags; _FAIL_HIST: a run_hist bracket open after 9216 predecessors; _FAIL_CAP: more runs or decisions
  * than the context's arena holds; _FAIL_REPLAY: a chain whose bracket stayed open over more than 64 evaluation chunks. */
 enum { BSCGPU_DC_FAIL_AVG = 2, BSCGPU_DC_FAIL_HIST = 4, BSCGPU_DC_FAIL_CAP = 8, BSCGPU_DC_FAIL_REPLAY = 16 };

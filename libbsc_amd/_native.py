@@ -61,6 +61,8 @@ def lib():
     L.bscgpu_bwt_aux.restype = C.c_int64
     L.bscgpu_bwt_device.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, u32p]
     L.bscgpu_bwt_device.restype = C.c_int64
+    if hasattr(L, "bscgpu_bwt_first_sort_device"):          # (BSC_LIB_OVERRIDE may name an older build)
+        L.bscgpu_bwt_first_sort_device.argtypes = [vp, vp, C.c_int64, vp, vp]
     L.bscgpu_st_encode.argtypes = [vp, vp, C.c_int, C.c_int]
     L.bscgpu_st_encode_device.argtypes = [vp, vp, vp, C.c_int, C.c_int]
     L.bscgpu_adler32_device.argtypes = [vp, vp, C.c_int64, u32p]

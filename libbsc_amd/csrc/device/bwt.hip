@@ -25,6 +25,7 @@
 //      test (libcubwt does the same, libcubwt.cu:1383).
 //   6. bwt_find / bwt_emit: primary and aux indexes from a scan of SA, L from SA (predecessor codes) or SA/T.
 #include "dev_common.h"
+#include "radix_dev.h"
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -117,6 +118,233 @@ __global__ __launch_bounds__(WG) void bwt_pack_kernel(const u8* __restrict__ T, 
     for (u32 k = 0; k < 4; ++k) {
         const u32 li = k * WG + threadIdx.x, i = b0 + li;
         if (i < n && (u64)i + pp.w <= (u64)n) { keys[i + pp.tc] = skey[li]; vals[i + pp.tc] = sval[li]; }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Folded packing: the key's lowest r = (cb * w) mod 8 bits (1..4 of them, all inside its last character) are sorted HERE, while every
+// record is written anyway, and the digit passes that follow are whole bytes — one pass fewer (bwt_device_once has the plan).
+//   bwt_fold_count_kernel   one read of the text: digit of suffix i = codes[T[i + w - 1]] & (2^r - 1), counted per packing tile
+//                           (FOLD_TILE consecutive suffixes); tails are not counted — their last character is padding, digit 0, and they
+//                           keep their slots [0, tc), the head of bucket 0.
+//   bwt_fold_scan_kernel    per bucket d and scan segment s (64 per bucket): off[d][tile] = records of d in the segment's tiles below,
+//                           segtot[d][s] = all of the segment's.  Packing sums the 1024 totals itself (bucket-major: tails, buckets below,
+//                           segments below), so the tile's first record of digit d has its slot and nothing waits for another workgroup.
+//   bwt_pack_fold_kernel    keys and values exactly as bwt_pack_kernel forms them; the tile's records are ranked inside their digit in
+//                           suffix order (wave-striped, ballot match, per-wave counters, one scan over digit x wave), reordered in LDS so
+//                           that every digit leaves as one run, and written at the scanned offsets.  Stable: bucket order = tile order,
+//                           then suffix order, and bucket 0 starts with the tails — the input order the tails-first rule above needs.
+//                           HIST: also the 256-bin totals of the np byte digits above the folded one, all n keys (tails included), in
+//                           replicated LDS counters that a workgroup — the grid is persistent — adds to the digit passes' tables once.
+// ---------------------------------------------------------------------------------------------
+#ifndef FOLD_REPL_N
+#define FOLD_REPL_N 1           // replicas of the fused digit counters (a power of two; by lane)
+#endif
+#ifndef FOLD_WGS_PER_CU
+#define FOLD_WGS_PER_CU 6       // persistent workgroups per CU: what the LDS of FOLD_REPL_N replicas (and 80 VGPRs) leaves room for
+#endif
+constexpr int FOLD_WAVES = WG / 64, FOLD_TILE = 4 * WG /* 1024 suffixes, four consecutive ones per thread */, FOLD_NB = 16 /* buckets at most */,
+              FOLD_BINS = 32 /* counter stride of a wave */, FOLD_REPL = FOLD_REPL_N, FOLD_MAXP = 7, FOLD_SEGS = 64 /* scan segments of a bucket */;
+static_assert(FOLD_NB * FOLD_SEGS == 4 * WG, "packing scans the segment totals four per thread");
+static_assert(FOLD_NB * FOLD_WAVES == 64, "the tile scan is one wavefront's: a (digit, wave) pair per lane");
+static size_t fold_lds_bytes(u32 np) { return (size_t)FOLD_REPL * np * 256 * 4; }
+
+// one wavefront per tile: a lane reads 16 of its 1024 characters, lane 0 also the w - 1 that follow
+__global__ __launch_bounds__(WG) void bwt_fold_count_kernel(const u8* __restrict__ T, u32 n, u32 w, u32 dmask, const u8* __restrict__ codes,
+                                                            u32 ntiles, u32* __restrict__ cnt /*[FOLD_NB][ntiles]*/)
+{
+    __shared__ u8 lut[256];
+    __shared__ u32 h[FOLD_WAVES][16 * 17];                               // per wave: 16 replicas (by lane), 17 words apart
+    const u32 t = threadIdx.x, wv = t >> 6, lane = t & 63u;
+    const u32 tile = blockIdx.x * (u32)FOLD_WAVES + wv;
+    lut[t] = codes[t] & (u8)dmask;
+    for (u32 i = lane; i < 16 * 17; i += 64) h[wv][i] = 0;
+    __syncthreads();
+    // last characters of the tile's suffixes that are no tails: positions [base + w - 1, base + FOLD_TILE + w - 1) below n
+    const u64 base = (u64)tile * FOLD_TILE, lo = base + w - 1;
+    u64 hi = base + FOLD_TILE + w - 1; if (hi > n) hi = n;
+    u32* hr = h[wv] + (lane & 15u) * 17;
+    if (tile < ntiles) {
+        for (u32 ch = lane; ch < FOLD_TILE / 16 + 1; ch += 64) {
+            const u64 a = base + 16ull * ch;                             // (a < hi <= n: the 16 bytes end inside the text's zero padding)
+            if (a < hi) {
+                const uint4 q = *reinterpret_cast<const uint4*>(T + a);
+                const u32 wd[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                for (u32 x = 0; x < 16; ++x) {
+                    const u64 p = a + x;
+                    if (p >= lo && p < hi) atomicAdd(&hr[lut[(wd[x >> 2] >> (8 * (x & 3))) & 0xffu]], 1u);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (tile < ntiles && lane < (u32)FOLD_NB) {
+        u32 sum = 0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sum += h[wv][r * 17 + lane];
+        cnt[(size_t)lane * ntiles + tile] = sum;
+    }
+}
+
+// one workgroup per digit and segment (FOLD_SEGS segments of seg_tiles tiles): off[d][tile] = records of digit d in the tiles of the
+// segment below this one, segtot[d][s] = all of the segment's
+__global__ __launch_bounds__(WG) void bwt_fold_scan_kernel(const u32* __restrict__ cnt, u32 ntiles, u32 seg_tiles, u32* __restrict__ off, u32* __restrict__ segtot)
+{
+    __shared__ u32 scr[8];
+    const u32 t = threadIdx.x, sg = blockIdx.x, d = blockIdx.y;
+    const u32 s0 = sg * seg_tiles;
+    const u32 s1 = (s0 + seg_tiles < ntiles) ? s0 + seg_tiles : ntiles;           // (s0 may lie past the end: an empty segment)
+    const u32 per = (seg_tiles + WG - 1) / WG;
+    const u32 b = s0 + t * per, e = (b + per < s1) ? b + per : s1;
+    const u32* row = cnt + (size_t)d * ntiles;
+    u32 own = 0;
+    for (u32 i = b; i < e; ++i) own += row[i];
+    u32 tot;
+    u32 run = block_excl_sum(own, scr, &tot);
+    for (u32 i = b; i < e; ++i) { off[(size_t)d * ntiles + i] = run; run += row[i]; }
+    if (t == 0) segtot[d * (u32)FOLD_SEGS + sg] = tot;
+}
+
+template <bool HIST>
+__global__ __launch_bounds__(WG) void bwt_pack_fold_kernel(const u8* __restrict__ T, u32 n, PackParams pp, u32 rbits,
+                                                           const u8* __restrict__ codes, const u32* __restrict__ off, const u32* __restrict__ segtot,
+                                                           u32 ntiles, u32 seg_tiles, u64* __restrict__ keys, u32* __restrict__ vals,
+                                                           u32 np, u32* __restrict__ totals, u32 pass_stride)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char fold_smem[];
+    u32* hh = reinterpret_cast<u32*>(fold_smem);                         // [FOLD_REPL][np][256]
+    __shared__ u64 skey[FOLD_TILE];                                      // the tile in suffix order, then bucket by bucket
+    __shared__ u32 sval[FOLD_TILE];
+    __shared__ u8 lut[256];
+    __shared__ u32 wh[FOLD_WAVES * FOLD_BINS];                           // per wave: digit counters, then the tile-local start of its records of each digit
+    __shared__ u32 sbase[FOLD_NB * FOLD_SEGS];                           // first slot of every (bucket, segment): the tails, the buckets below, the bucket's segments below
+    __shared__ u32 scr[8];
+    __shared__ u32 adj[FOLD_NB];                                         // output slot of tile-local slot q of digit d = adj[d] + q
+    lds_vu32* vwh = (lds_vu32*)wh;
+    const u32 t = threadIdx.x, w = t >> 6, lane = t & 63u;
+    lut[t] = codes[t];
+    {
+        // bucket-major, so one exclusive sum over the table is the layout of the output
+        const uint4 q = *reinterpret_cast<const uint4*>(segtot + 4u * t);
+        u32 tot;
+        const u32 ex = pp.tc + block_excl_sum(q.x + q.y + q.z + q.w, scr, &tot);
+        sbase[4u * t] = ex; sbase[4u * t + 1] = ex + q.x; sbase[4u * t + 2] = ex + q.x + q.y; sbase[4u * t + 3] = ex + q.x + q.y + q.z;
+    }
+    if (HIST) for (u32 i = t; i < (u32)FOLD_REPL * np * 256u; i += WG) hh[i] = 0;
+    __syncthreads();
+    const u32 dmask = (1u << rbits) - 1u;
+    const u32 nt_end = n >= pp.w ? n - pp.w + 1 : 0;                     // suffixes below this index are no tails
+    u32* hr = hh + (lane & (u32)(FOLD_REPL - 1)) * np * 256u;
+    const u64 lt = lanemask_lt();
+
+    for (u32 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const u32 b0 = tile * (u32)FOLD_TILE;                            // first suffix of the tile
+        const u32 i0 = b0 + 4u * t;
+        if (lane < (u32)FOLD_BINS) wh[w * FOLD_BINS + lane] = 0;
+        if (i0 < n) {
+            // bwt_pack_kernel's keys and values.  The kernel is bound by its VALU work, so the four keys are not built character by
+            // character: the first is, and each next one is the one before shifted up by a character (its first character leaves
+            // through the top) with the next character put in at low_shift.
+            const u32* T32 = reinterpret_cast<const u32*>(T + i0);
+            u32 wds[5];
+#pragma unroll
+            for (int x = 0; x < 5; ++x) wds[x] = T32[x];
+            u32 pcode = (pp.pred_shift && i0 > 0) ? (u32)lut[T[i0 - 1]] : 0u;
+            u32 cd[19];                                     // codes of characters i0 .. i0+18 (0 past the end)
+#pragma unroll
+            for (u32 x = 0; x < 19; ++x) {
+                const u32 ch = (wds[x >> 2] >> (8 * (x & 3))) & 0xffu;
+                cd[x] = (i0 + x < n) ? (u32)lut[ch] : 0u;
+            }
+            u64 key = 0;
+            u32 ext = 0;                                    // characters w, w + 1, w + 2, the first of them on top
+#pragma unroll
+            for (u32 x = 0; x < 19; ++x) {
+                if (x < pp.w) { if (x < 16) key |= (u64)cd[x] << (64 - pp.cb * (x + 1)); }
+                else if (x < pp.w + 3) ext |= cd[x] << (pp.cb * (pp.w + 2 - x));
+            }
+            const u32 cmask = (1u << pp.cb) - 1u;
+#pragma unroll
+            for (u32 j = 0; j < 4; ++j) {
+                const u32 i = i0 + j;
+                if (i < n) {
+                    const u32 val = pp.pred_shift ? (i | (pcode << pp.pred_shift)) : i;
+                    if (HIST) {
+                        // (the digits are whole bytes of the key: its top np)
+                        const u32 klo = (u32)key, khi = (u32)(key >> 32);
+#pragma unroll
+                        for (u32 bb = 1; bb < 8; ++bb)
+                            if (bb >= 8u - np) atomicAdd(&hr[(bb - (8u - np)) * 256u + (((bb < 4 ? klo : khi) >> (8 * (bb & 3))) & 0xffu)], 1u);
+                    }
+                    if (i >= nt_end) { keys[n - 1 - i] = key; vals[n - 1 - i] = val; }
+                    else { skey[4u * t + j] = key; sval[4u * t + j] = val; }
+                    pcode = cd[j];
+                }
+                if (j < 3) key = (key << pp.cb) | ((u64)((ext >> (pp.cb * (2 - j))) & cmask) << pp.low_shift);
+            }
+        }
+        __syncthreads();
+        // the tile's records that are no tails are its first nv; a wave ranks 256 consecutive ones, item-major
+        const u32 nv = nt_end > b0 ? ((nt_end - b0 < (u32)FOLD_TILE) ? nt_end - b0 : (u32)FOLD_TILE) : 0u;
+        u64 k[4]; u32 v[4], dg[4], rk[4];
+#pragma unroll
+        for (u32 j = 0; j < 4; ++j) {
+            const u32 q = w * 256u + j * 64u + lane;
+            const bool valid = q < nv;
+            k[j] = valid ? skey[q] : 0ull;
+            v[j] = valid ? sval[q] : 0u;
+            dg[j] = valid ? ((u32)(k[j] >> pp.low_shift) & dmask) : (u32)FOLD_NB;       // slots past the end: a bucket of their own, never written
+        }
+#pragma unroll
+        for (u32 j = 0; j < 4; ++j) {
+            u64 m = ~0ull;
+#pragma unroll
+            for (u32 b = 0; b < 5; ++b) {
+                const bool bit = (dg[j] >> b) & 1u;
+                const u64 bal = __ballot(bit);
+                m &= bit ? bal : ~bal;
+            }
+            const u32 before = vwh[w * FOLD_BINS + dg[j]];
+            const u32 r = (u32)__popcll(m & lt), cnt = (u32)__popcll(m);
+            rk[j] = before + r;
+            if (r == cnt - 1) vwh[w * FOLD_BINS + dg[j]] = before + cnt;                 // highest peer lane publishes
+        }
+        __syncthreads();
+        if (w == 0) {
+            const u32 sd = lane >> 2, sw = lane & 3u;                    // digit-major, then wave: the scan is the tile's bucket layout
+            const u32 c = wh[sw * FOLD_BINS + sd];
+            const u32 ex = wave_incl_sum(c) - c;
+            wh[sw * FOLD_BINS + sd] = ex;
+            if (sw == 0) adj[sd] = sbase[sd * (u32)FOLD_SEGS + tile / seg_tiles] + off[(size_t)sd * ntiles + tile] - ex;
+        }
+        __syncthreads();
+#pragma unroll
+        for (u32 j = 0; j < 4; ++j) {
+            if (dg[j] < (u32)FOLD_NB) {
+                const u32 pos = wh[w * FOLD_BINS + dg[j]] + rk[j];
+                skey[pos] = k[j]; sval[pos] = v[j];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (u32 j = 0; j < 4; ++j) {
+            const u32 q = j * (u32)WG + t;
+            if (q < nv) {
+                const u64 key = skey[q];
+                const u32 o = adj[(u32)(key >> pp.low_shift) & dmask] + q;
+                if (o < n) { keys[o] = key; vals[o] = sval[q]; }         // (always, when the counts are those of this text: the test keeps a store inside the arrays whatever it is given)
+            }
+        }
+        __syncthreads();
+    }
+    if (HIST) {
+        for (u32 i = t; i < np * 256u; i += WG) {
+            u32 sum = 0;
+#pragma unroll
+            for (u32 r = 0; r < (u32)FOLD_REPL; ++r) sum += hh[r * np * 256u + i];
+            if (sum) atomicAdd(&totals[(size_t)(i >> 8) * pass_stride + (i & 255u)], sum);
+        }
     }
 }
 
@@ -1099,14 +1327,12 @@ int bwt_batch_device(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, const int* s
     return rc;
 }
 
-static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_t n64, int64_t r, u32* I_host, int64_t* primary_out, bool reuse_text,
-                           const BwtBatch* bt)
+// The front of a transform: private copy of the text, alphabet, key packing and the first sort (asynchronous behind the alphabet's sync;
+// run_seg checks the sort).  Also what bscgpu_bwt_first_sort_device runs.
+struct FirstSort { PackParams pp; u32 smask, tail_lo; u8* dcodes; u8* ddecode; const u64* ks; const u32* vs; };
+static int bwt_first_sort(bscgpu_ctx* c, const u8* dT_user, u32 n, bool reuse_text, const BwtBatch* bt, FirstSort* fs)
 {
-    if (n64 < 0 || n64 > c->max_n || n64 >= 0x7fffffffll) return BSC_BAD_PARAMETER;
-    if (n64 == 0) { *primary_out = 0; return BSC_NO_ERROR; }
-    const u32 n = (u32)n64;
     int rc;
-
     // private, padded copy of the text (emit may overwrite the user's buffer when dL aliases dT)
     if (!reuse_text) HIP_TRY(c, hipMemcpyAsync(c->dT, dT_user, n, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->dT + n, 0, 32, c->stream));
@@ -1123,7 +1349,7 @@ static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_
     HIP_TRY(c, ctx_sync(c));
     u8 codes[256]; u32 K = 0;
     for (int b = 0; b < 256; ++b) { codes[b] = (u8)K; if (c->hscal[300 + b]) ++K; }
-    PackParams pp;
+    PackParams& pp = fs->pp;
     // a batched pass: codes 1..K (0 = past the block's end) below the block field; no text rounds, no predecessor codes (see bwt_batch_pack_kernel)
     const u32 batch_bb = bt ? (u32)bit_length(bt->count - 1) : 0u;
     pp.cb = 1; while ((1u << pp.cb) < K + (bt ? 1u : 0u)) ++pp.cb;
@@ -1140,14 +1366,63 @@ static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_
     const int idx_bits = bit_length(n - 1);
     static const int pred_on = [] { const char* e = getenv("BSC_BWT_PRED"); return e ? atoi(e) : 1; }();
     pp.pred_shift = (pred_on && !bt && idx_bits >= 1 && idx_bits + (int)pp.cb <= 32) ? (u32)idx_bits : 0u;
-    const u32 smask = pp.pred_shift ? ((1u << pp.pred_shift) - 1u) : 0xffffffffu;
-    const u32 tail_lo = bt ? 0xffffffffu : (n >= pp.w) ? (n - (pp.w - 1)) : 0;
-    u8* dcodes = reinterpret_cast<u8*>(c->dscal + 560);         // 256 bytes of the scalar area
-    u8* ddecode = reinterpret_cast<u8*>(c->dscal + 720);        // 256 bytes: code -> byte (640..703 is the QLFC front end's symbol table)
+    fs->smask = pp.pred_shift ? ((1u << pp.pred_shift) - 1u) : 0xffffffffu;
+    fs->tail_lo = bt ? 0xffffffffu : (n >= pp.w) ? (n - (pp.w - 1)) : 0;
+    u8* dcodes = fs->dcodes = reinterpret_cast<u8*>(c->dscal + 560);         // 256 bytes of the scalar area
+    u8* ddecode = fs->ddecode = reinterpret_cast<u8*>(c->dscal + 720);        // 256 bytes: code -> byte (640..703 is the QLFC front end's symbol table)
     u8 decode[256]; memset(decode, 0, sizeof decode);
     for (int b = 255; b >= 0; --b) if (c->hscal[300 + b]) decode[codes[b]] = (u8)b;
     HIP_TRY(c, hipMemcpyAsync(dcodes, codes, 256, hipMemcpyHostToDevice, c->stream));
     if (pp.pred_shift) HIP_TRY(c, hipMemcpyAsync(ddecode, decode, 256, hipMemcpyHostToDevice, c->stream));
+    // Pass plan.  Digits are 8 bits from low_shift upwards, the topmost with what is left.  Where the key's width leaves r = (cb * w) mod 8
+    // bits over, 1 <= r <= 4 (17..64 symbols: 60 key bits, r = 4), that half digit costs a whole pass over all records; key packing
+    // writes every record once anyway, so it places them by these r bits itself (bwt_pack_fold_kernel; r <= cb: the digit lies inside
+    // the key's last character) and the sort is (cb * w - r) / 8 byte passes from low_shift + r.  A stable LSD sort gives the same
+    // arrays however the bits are cut into digits.  Only single blocks whose sort takes the single-read passes go this way (so not
+    // the retry after a give-up, os_mode == 0); everything else keeps the plan and the kernels it had.
+    const u32 fold_r = (pp.cb * pp.w) & 7u;
+    const int fold_np = (int)((pp.cb * pp.w - fold_r) / 8u);
+    const bool fold = c->bwt_fold != 0 && !bt && fold_r >= 1 && fold_r <= 4 && fold_r <= pp.cb && n >= pp.w &&
+                      radix_onesweep_wanted(c, n, fold_np, true);
+    if (fold) {
+        const bool fused = c->bwt_fold == 1;                // packing counts the byte digits too (else rs_hist_all reads the keys for them)
+        if (!c->fold_lds_set) {
+            HIP_TRY(c, hipFuncSetAttribute((const void*)bwt_pack_fold_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fold_lds_bytes(FOLD_MAXP)));
+            c->fold_lds_set = true;
+        }
+        u32* totals = nullptr; u32 stride = 0;
+        if (fused) { rc = radix_onesweep_prepare(c, n, fold_np, &totals, &stride); if (rc < 0) return rc; }     // (the tables are cleared in front of packing)
+        const u32 ntiles = (n + FOLD_TILE - 1) / FOLD_TILE;
+        u32* fcnt = c->ISA;                                  // [FOLD_NB][ntiles] counts, then as many offsets: ISA is not built before the first seg
+        u32* foff = fcnt + (size_t)FOLD_NB * ntiles;
+        u32* fseg = foff + (((size_t)FOLD_NB * ntiles + 3) & ~(size_t)3);     // [FOLD_NB][FOLD_SEGS] records of a bucket per scan segment
+        const u32 seg_tiles = (ntiles + FOLD_SEGS - 1) / FOLD_SEGS;
+        // an odd number of passes ends in the other pair: the records are packed into the pair from which the sort lands in kA / vA,
+        // so that SA can alias vA and the text rounds keep kB / vB
+        u64* k0 = (fold_np & 1) ? c->kB : c->kA; u64* k1 = (fold_np & 1) ? c->kA : c->kB;
+        u32* v0 = (fold_np & 1) ? c->vB : c->vA; u32* v1 = (fold_np & 1) ? c->vA : c->vB;
+        const u32 resident = (u32)c->num_cus * (u32)FOLD_WGS_PER_CU;
+        const u32 grid = ntiles < resident ? ntiles : resident;
+        prof_begin(c, BSCGPU_K_PACK, (u64)n * 14, n);
+        hipLaunchKernelGGL(bwt_fold_count_kernel, dim3((ntiles + FOLD_WAVES - 1) / FOLD_WAVES), dim3(WG), 0, c->stream,
+                           c->dT, n, pp.w, (1u << fold_r) - 1u, dcodes, ntiles, fcnt);
+        hipLaunchKernelGGL(bwt_fold_scan_kernel, dim3(FOLD_SEGS, FOLD_NB), dim3(WG), 0, c->stream, fcnt, ntiles, seg_tiles, foff, fseg);
+        if (fused)
+            hipLaunchKernelGGL(bwt_pack_fold_kernel<true>, dim3(grid), dim3(WG), fold_lds_bytes((u32)fold_np), c->stream,
+                               c->dT, n, pp, fold_r, dcodes, foff, fseg, ntiles, seg_tiles, k0, v0, (u32)fold_np, totals, stride);
+        else
+            hipLaunchKernelGGL(bwt_pack_fold_kernel<false>, dim3(grid), dim3(WG), 0, c->stream,
+                               c->dT, n, pp, fold_r, dcodes, foff, fseg, ntiles, seg_tiles, k0, v0, 0u, (u32*)nullptr, 0u);
+        prof_end(c);
+        HIP_TRY(c, hipGetLastError());
+        RadixPass fp[FOLD_MAXP];
+        for (int p = 0; p < fold_np; ++p) { fp[p].shift = (int)(pp.low_shift + fold_r) + 8 * p; fp[p].bits = 8; }
+        rc = radix_onesweep_sort(c, k0, k1, v0, v1, n, fp, fold_np, fused);
+        if (rc < 0) return rc;
+        ++c->cnt_bwt_folded;
+        fs->ks = c->kA; fs->vs = c->vA;
+        return BSC_NO_ERROR;
+    }
     prof_begin(c, BSCGPU_K_PACK, (u64)n * 13, n);
     if (bt)
         hipLaunchKernelGGL(bwt_batch_pack_kernel, dim3((n + WG - 1) / WG), dim3(WG), 0, c->stream,
@@ -1163,8 +1438,56 @@ static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_
     int in_alt = 0;
     rc = radix_sort_passes(c, c->kA, c->kB, c->vA, c->vB, n, passes, npass, &in_alt);
     if (rc < 0) return rc;
-    const u64* ks = in_alt ? c->kB : c->kA;
-    const u32* vs = in_alt ? c->vB : c->vA;
+    fs->ks = in_alt ? c->kB : c->kA;
+    fs->vs = in_alt ? c->vB : c->vA;
+    return BSC_NO_ERROR;
+}
+
+// The first sort alone (bscgpu_bwt_first_sort_device): alphabet, packing and the sort as a transform of this block runs them, the sorted
+// (key, value) arrays copied out.  Same retry rule as bwt_device.
+int bwt_first_sort_device(bscgpu_ctx* c, const u8* dT_user, int64_t n64, u64* keys_out, u32* vals_out)
+{
+    if (n64 < 0 || n64 > c->max_n || n64 >= 0x7fffffffll) return BSC_BAD_PARAMETER;
+    if (n64 == 0) return BSC_NO_ERROR;
+    const u32 n = (u32)n64;
+    auto once = [&]() -> int {
+        FirstSort fs;
+        int rc = bwt_first_sort(c, dT_user, n, false, nullptr, &fs);
+        if (rc < 0) return rc;
+        HIP_TRY(c, hipMemcpyAsync(keys_out, fs.ks, (size_t)n * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(vals_out, fs.vs, (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, ctx_sync(c));
+        prof_collect(c);
+        return radix_onesweep_check(c);
+    };
+    c->os_gave_up = false;
+    int rc = once();
+    if (rc == BSC_GPU_ERROR && c->os_gave_up) {
+        const int mode = c->os_mode;
+        c->os_mode = 0; c->os_gave_up = false; ++c->os_retries;
+        rc = once();
+        c->os_mode = mode;
+    }
+    return rc;
+}
+
+static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_t n64, int64_t r, u32* I_host, int64_t* primary_out, bool reuse_text,
+                           const BwtBatch* bt)
+{
+    if (n64 < 0 || n64 > c->max_n || n64 >= 0x7fffffffll) return BSC_BAD_PARAMETER;
+    if (n64 == 0) { *primary_out = 0; return BSC_NO_ERROR; }
+    const u32 n = (u32)n64;
+    int rc;
+
+    FirstSort fs;
+    rc = bwt_first_sort(c, dT_user, n, reuse_text, bt, &fs);
+    if (rc < 0) return rc;
+    const PackParams& pp = fs.pp;
+    const u32 smask = fs.smask, tail_lo = fs.tail_lo;
+    u8* const dcodes = fs.dcodes; u8* const ddecode = fs.ddecode;
+    const u64* ks = fs.ks;
+    const u32* vs = fs.vs;
+    int in_alt = 0;
 
     // Rounds on text keys (bwt_round_textsort_kernel) need a characters + 4 bits in 64: a = w where the first-sort key leaves
     // 4 bits spare, else w - 1.  BSC_BWT_TEXTROUNDS=0 keeps the round-1 flow (ISA built by the first seg, doubling from h = w).

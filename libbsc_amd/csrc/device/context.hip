@@ -198,6 +198,7 @@ extern "C" int bscgpu_create(bscgpu_ctx** out, int device, int64_t max_n)
     c->device = device;
     c->max_n  = max_n;
     { const char* e = getenv("BSC_PS13"); c->dc_p13 = (e && e[0] == '0') ? 0 : 1; }       // BSCGPU_OPT_DC_PACKED_STREAM
+    { const char* e = getenv("BSC_BWT_FOLD"); if (e && e[0] >= '0' && e[0] <= '2' && !e[1]) c->bwt_fold = e[0] - '0'; }       // BSCGPU_OPT_BWT_FOLD
     memset(c->kstat, 0, sizeof c->kstat);
     auto tm_streams = std::make_unique<CtxTimer>("  streams + events");
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return BSC_GPU_ERROR; }
@@ -354,6 +355,7 @@ extern "C" int bscgpu_option_set(bscgpu_ctx* c, int key, int value)
     if (key == BSCGPU_OPT_DEVICE_RC && (value == 0 || value == 1)) { const int old = c->device_rc; c->device_rc = value; return old; }
     if (key == BSCGPU_OPT_BATCH_MODEL && (value == 0 || value == 1)) { const int old = c->batch_model; c->batch_model = value; return old; }
     if (key == BSCGPU_OPT_BATCH_MODEL_FAST && (value == 0 || value == 1)) { const int old = c->batch_model_fast; c->batch_model_fast = value; return old; }
+    if (key == BSCGPU_OPT_BWT_FOLD && value >= 0 && value <= 2) { const int old = c->bwt_fold; c->bwt_fold = value; return old; }
     return BSC_BAD_PARAMETER;
 }
 extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
@@ -377,6 +379,8 @@ extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
     if (key == BSCGPU_OPT_BATCH_MODEL_FAST) return c->batch_model_fast;
     if (key == BSCGPU_CNT_BATCH_FAST_PASSES) return c->cnt_model_fast_passes;
     if (key == BSCGPU_CNT_BATCH_FAST_DECLINED) return c->cnt_model_fast_declined;
+    if (key == BSCGPU_OPT_BWT_FOLD) return c->bwt_fold;
+    if (key == BSCGPU_CNT_BWT_FOLDED) return c->cnt_bwt_folded;
     return BSC_BAD_PARAMETER;
 }
 extern "C" int bscgpu_last_stage_ms(bscgpu_ctx* c, double* out6)
@@ -394,6 +398,13 @@ extern "C" int64_t bscgpu_bwt_device(bscgpu_ctx* c, const void* dT, void* dL, in
     int64_t primary = 0;
     int rc = bwt_device(c, (const u8*)dT, (u8*)dL, n, r, I, &primary);
     return rc < 0 ? rc : primary;
+}
+
+extern "C" int bscgpu_bwt_first_sort_device(bscgpu_ctx* c, const void* dT, int64_t n, void* d_keys_out, void* d_vals_out)
+{
+    if (!c || !dT || !d_keys_out || !d_vals_out) return BSC_BAD_PARAMETER;
+    if (hipSetDevice(c->device) != hipSuccess) return BSC_GPU_ERROR;
+    return bwt_first_sort_device(c, (const u8*)dT, n, (u64*)d_keys_out, (u32*)d_vals_out);
 }
 
 extern "C" int bscgpu_st_encode_device(bscgpu_ctx* c, const void* dT, void* dOut, int n, int k)

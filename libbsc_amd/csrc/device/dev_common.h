@@ -146,6 +146,10 @@ struct bscgpu_ctx {
     int  os_retries = 0;             // transforms redone through the three-kernel passes after a give-up (bscgpu_debug_counter)
     int  dc_p13 = 1;                 // BSCGPU_OPT_DC_PACKED_STREAM: the static coder's p stream leaves as 13 bits per decision (BSC_PS13=0: 16-bit entries)
     bool os_gave_up = false;         // radix_onesweep_check found a give-up: the caller may redo its sorts through the three-kernel passes
+    // BWT first sort: the leftover low digit of the key is sorted by key packing (bwt.hip: bwt_pack_fold_kernel)
+    int  bwt_fold = 1;               // BSCGPU_OPT_BWT_FOLD: 0 off, 1 packing also counts the remaining digits, 2 it leaves that to rs_hist_all
+    int  cnt_bwt_folded = 0;         // BSCGPU_CNT_BWT_FOLDED
+    bool fold_lds_set = false;       // the packing kernels' dynamic-LDS limit has been raised on this context's device
     // pinned host
     u32* hscal  = nullptr;   // 1024 u32 (slot map: the users' comments; OS_ERR_SLOT = 1000)
     u64* hscal64 = nullptr;
@@ -204,12 +208,17 @@ int radix_sort_passes(bscgpu_ctx* c, u64* keys, u64* keys_alt, u32* vals, u32* v
 constexpr int OS_ERR_SLOT = 1000;           // hscal / dscal word: sticky error word of the single-read digit passes (cleared by radix_onesweep_check only)
 int  radix_onesweep_setup(bscgpu_ctx* c);
 bool radix_onesweep_wanted(const bscgpu_ctx* c, u64 n, int npasses, bool has_val);
-int  radix_onesweep_sort(bscgpu_ctx* c, u64* keys, u64* keys_alt, u32* vals, u32* vals_alt, u64 n, const RadixPass* passes, int npasses);
+// totals_ready: radix_onesweep_prepare ran for this sort and the caller has added every digit's totals to the tables it returned (the
+// counters of pass p, digit d at totals[p * stride + d]); the sort then launches its digit passes only.
+int  radix_onesweep_prepare(bscgpu_ctx* c, u64 n, int npasses, u32** totals = nullptr, u32* stride = nullptr);
+int  radix_onesweep_sort(bscgpu_ctx* c, u64* keys, u64* keys_alt, u32* vals, u32* vals_alt, u64 n, const RadixPass* passes, int npasses,
+                         bool totals_ready = false);
 int  radix_onesweep_check(bscgpu_ctx* c);   // after the next stream sync: did a pass of the last such sort give up a wait?
 int radix_engine_setup(bscgpu_ctx* c);     // per-device kernel attributes; bscgpu_create calls it with c->device current
 
 int bwt_device(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_t n, int64_t r, u32* I_host,
                int64_t* primary_out);
+int bwt_first_sort_device(bscgpu_ctx* c, const u8* dT_user, int64_t n, u64* keys_out, u32* vals_out);   // (tests) the sorted arrays of the first sort
 int st_device(bscgpu_ctx* c, const u8* dT_user, u8* dOut_user, int n, int k, int* index_out);
 // Batched BWT pass (bwt.hip): `count` blocks of sizes[b] laid out back to back in dT_user, sum <= max_n, count <= BATCH_MAX_BLOCKS.
 // rates[b] > 0: the block's aux rate, 0: primary index only, < 0: not transformed (L = T).  res[16 b + t] = I[t] of block b as bwt_device

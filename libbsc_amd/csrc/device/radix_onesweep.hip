@@ -4,7 +4,9 @@
 // SORT, then one kernel per digit that reads every record once and writes it once (B_sort = m*kb + P*2*m*(kb+vb)).
 // The three-kernel pass of radix_sort.hip re-reads all keys in rs_hist for every digit (+33 % traffic, 0.13 of 0.47 ms).
 //
-//   rs_hist_all      one streaming read of the keys, the global 256-bin histogram of every digit of the sort (<= 8).
+//   rs_hist_all      one streaming read of the keys, the global 256-bin histogram of every digit of the sort (<= 8).  A caller that
+//                    has every key in registers anyway counts them itself (bwt.hip: bwt_pack_fold_kernel): radix_onesweep_prepare clears
+//                    the tables and hands out the totals' place, radix_onesweep_sort(totals_ready) then launches the passes only.
 //   rs_onesweep      persistent workgroups (one per CU, 16 waves).  FIFTEEN waves stream 7680-record tiles (the tile loop of
 //                    rs_scatter_tiled: wave-striped loads, ballot-match ranking, tile-local reorder through LDS, every digit
 //                    leaves as one run) and publish each tile's digit counts right after the digit scan; the SIXTEENTH wave —
@@ -549,12 +551,10 @@ bool radix_onesweep_wanted(const bscgpu_ctx* c, u64 n, int npasses, bool has_val
     return n >= (u64)(c->os_mode == 2 ? 4 : 512) * OS_TILE;             // mode 2 (tests): every sort of >= 4 tiles; mode 3: large sorts, keys-only too
 }
 
-int radix_onesweep_sort(bscgpu_ctx* c, u64* keys, u64* keys_alt, u32* vals, u32* vals_alt, u64 n,
-                        const RadixPass* passes, int npasses)
+// Tables of one sort: allocated on first use, tickets, digit totals and batch rows of all its passes cleared.
+int radix_onesweep_prepare(bscgpu_ctx* c, u64 n, int npasses, u32** totals, u32* stride)
 {
-    const bool has_val = vals != nullptr;
     const u32 ntiles = (u32)((n + OS_TILE - 1) / OS_TILE);
-    const u32 nbatches = (ntiles + OS_BATCH - 1) / OS_BATCH;
     if (c->os_tiles_cap < ntiles) {
         if (c->os_agg) (void)hipFree(c->os_agg);
         if (c->os_zero) (void)hipFree(c->os_zero);
@@ -575,6 +575,21 @@ int radix_onesweep_sort(bscgpu_ctx* c, u64* keys, u64* keys_alt, u32* vals, u32*
     }
     // per sort: tickets, digit totals and batch rows of all passes start from zero
     HIP_TRY(c, hipMemsetAsync(c->os_zero, 0, (size_t)npasses * c->os_pass_stride * 4, c->stream));
+    if (totals) *totals = c->os_zero + OS_CTL_WORDS;
+    if (stride) *stride = c->os_pass_stride;
+    return BSC_NO_ERROR;
+}
+
+int radix_onesweep_sort(bscgpu_ctx* c, u64* keys, u64* keys_alt, u32* vals, u32* vals_alt, u64 n,
+                        const RadixPass* passes, int npasses, bool totals_ready)
+{
+    const bool has_val = vals != nullptr;
+    const u32 ntiles = (u32)((n + OS_TILE - 1) / OS_TILE);
+    const u32 nbatches = (ntiles + OS_BATCH - 1) / OS_BATCH;
+    if (!totals_ready) {
+        const int prc = radix_onesweep_prepare(c, n, npasses);
+        if (prc < 0) return prc;
+    }
 
     OsPasses P;
     P.np = npasses;
@@ -583,10 +598,12 @@ int radix_onesweep_sort(bscgpu_ctx* c, u64* keys, u64* keys_alt, u32* vals, u32*
         P.mask[p]  = p < npasses ? ((passes[p].bits >= 8) ? 0xffu : ((1u << passes[p].bits) - 1u)) : 0u;
     }
     const u32 grid = ntiles < (u32)c->num_cus ? ntiles : (u32)c->num_cus;
-    prof_begin(c, BSCGPU_K_RADIX_HISTALL, n * 8, n);
-    hipLaunchKernelGGL(rs_hist_all_kernel, dim3(grid), dim3(OS_WG), (size_t)16 * npasses * 256 * 4, c->stream,
-                       keys, (u32)n, P, c->os_zero, c->os_pass_stride);
-    prof_end(c);
+    if (!totals_ready) {
+        prof_begin(c, BSCGPU_K_RADIX_HISTALL, n * 8, n);
+        hipLaunchKernelGGL(rs_hist_all_kernel, dim3(grid), dim3(OS_WG), (size_t)16 * npasses * 256 * 4, c->stream,
+                           keys, (u32)n, P, c->os_zero, c->os_pass_stride);
+        prof_end(c);
+    }
 
     u64 *ksrc = keys, *kdst = keys_alt;
     u32 *vsrc = vals, *vdst = vals_alt;

@@ -96,6 +96,14 @@ class GpuContext:
         rc = self._check(self.L.bscgpu_bwt_device(self.h, _dptr(dT), _dptr(dL), n, 0, None))
         return int(rc), None
 
+    def bwt_first_sort_device(self, dT, n):
+        """bscgpu_bwt_first_sort_device: the first sort of bwt_device's transform of this block alone -> (keys u64[n], vals u32[n])"""
+        import torch
+        keys = torch.empty(n, dtype=torch.int64, device=dT.device)
+        vals = torch.empty(n, dtype=torch.int32, device=dT.device)
+        self._check(self.L.bscgpu_bwt_first_sort_device(self.h, _dptr(dT), n, _dptr(keys), _dptr(vals)))
+        return keys.cpu().numpy().view(np.uint64), vals.cpu().numpy().view(np.uint32)
+
     def st_encode_device(self, dT, dOut, n, k):
         return int(self._check(self.L.bscgpu_st_encode_device(self.h, _dptr(dT), _dptr(dOut), n, k)))
 
@@ -351,6 +359,7 @@ class GpuContext:
     OPT_DEVICE_RC, CNT_DEVICE_RC_BLOCKS = 12, 13       # a device-model block's streams are range-coded on the GPU (default 0) and how many were
     OPT_BATCH_MODEL, CNT_BATCH_MODEL_PASSES, CNT_BATCH_MODEL_DECLINED = 14, 15, 16    # the static coder's model of a compress-batch pass on the GPU
     OPT_BATCH_MODEL_FAST, CNT_BATCH_FAST_PASSES, CNT_BATCH_FAST_DECLINED = 17, 18, 19    # ... the fast coder's (-e0), an option of its own
+    OPT_BWT_FOLD, CNT_BWT_FOLDED = 20, 21              # key packing sorts the first-sort key's leftover low bits (default 1) and how many sorts took that route
     CNT_DC_REPLAYS, CNT_DC_LAST_FAIL, CNT_DC_AVG_UNDECIDED, CNT_DC_HIST_EXTENDED = 5, 6, 7, 8      # the last device-model block (get only)
     DC_FAIL_AVG, DC_FAIL_HIST, DC_FAIL_CAP, DC_FAIL_REPLAY = 2, 4, 8, 16                          # BSCGPU_DC_FAIL_*
 
