@@ -267,6 +267,37 @@ BSCGPU_API int64_t bscgpu_fast_pstream_host(const bscgpu_front_layout* layout, i
 BSCGPU_API int bscgpu_front_batch_code_psf(const bscgpu_front_layout* layout, int block, const uint16_t* ps, const uint32_t* poff,
                                            unsigned char* out, int features);
 
+/* ---- a pass's model in segments ("Model segments") ------------------------------------------------------------------
+ * Sub-blocks are independent chains, so the model of a pass can run over any contiguous range of its sub-blocks and write the same
+ * entries.  A model segment is such a range, made of whole blocks.
+ * bscgpu_model_segment_plan: the rule as a pure function.  sub_dec[s] / sub_und[s]: decisions and undecided avg_rank flags of
+ *   sub-block s; blk_sub[count + 1]: first sub-block of every block (the layout's).  Blocks are taken in order.  A block is excluded
+ *   (seg_of[b] = -1) when one of its sub-blocks has sub_und > 0 or its own decisions exceed dcap; an excluded block ends the current
+ *   segment.  A block without sub-blocks gets -1 and ends nothing.  The others join the current segment while its decisions stay
+ *   <= min(dcap, target) (target <= 0: dcap); a single block above target but <= dcap is a segment of its own.  Returns the number of
+ *   segments, or LIBBSC_BAD_PARAMETER (null pointers with count > 0, count < 0, dcap <= 0, blk_sub not non-decreasing from >= 0) with
+ *   nothing written.
+ * bscgpu_model_segment_facts_device (a stage on its own for tests and tools, as the _pstream_ stages are; no caller needs it to
+ *   compress): front end (as bscgpu_static_pstream_batch_device) and what the plan is made of, for `coder`:
+ *   sub_dec[s] = decisions of sub-block s (what the CPU stand-in of that coder returns for it), sub_und[s] = its undecided avg_rank
+ *   flags (0 for the fast coder); nsub <= 2 count entries each.  Two kernels over the run arrays, before any sort.  Returns 0,
+ *   LIBBSC_NOT_SUPPORTED (an arena did not fit), LIBBSC_BAD_PARAMETER or a GPU error.  Synchronous.
+ * bscgpu_pstream_batch_segments_device: front end (as bscgpu_static_pstream_batch_device) and the model of `coder`
+ *   (LIBBSC_CODER_QLFC_STATIC or _FAST) segment by segment, target decisions per segment.  out[0 .. cap): the kept sub-blocks' entries
+ *   back to back in sub-block order; poff[nsub + 1]: a sub-block that was not modelled has poff[s + 1] == poff[s]; blk_state[count]:
+ *   0 when block b's streams are there, else the mask of BSCGPU_DC_FAIL_* that leaves it to the host model (the layout is always
+ *   filled: bscgpu_front_batch_code codes such a block, bscgpu_front_batch_code_ps / _psf the others from out / poff).  A segment that
+ *   declines while it runs is split at the block boundary nearest half its decisions and both halves run again, at most
+ *   2 ceil(log2(blocks)) + 2 re-runs per pass.  Returns the decisions written (above cap: counted, not copied; poff and blk_state are
+ *   filled all the same); LIBBSC_NOT_SUPPORTED only when an arena did not fit; LIBBSC_BAD_PARAMETER; or a GPU error.  Moves
+ *   BSCGPU_CNT_BATCH_SEGMENTS / _SEG_RERUNS / _SEG_HOST_BLOCKS.  Synchronous.  Memory: as the whole-pass stage, + 100 KB of tables. */
+BSCGPU_API int bscgpu_model_segment_plan(const uint32_t* sub_dec, const uint32_t* sub_und, const int* blk_sub, int count, int64_t dcap,
+                                         int64_t target, int* seg_of);
+BSCGPU_API int bscgpu_model_segment_facts_device(bscgpu_ctx* ctx, const void* dL, const int* sizes, int count, bscgpu_front_layout* layout,
+                                                 int coder, uint32_t* sub_dec, uint32_t* sub_und);
+BSCGPU_API int64_t bscgpu_pstream_batch_segments_device(bscgpu_ctx* ctx, const void* dL, const int* sizes, int count, bscgpu_front_layout* layout,
+                                                        int coder, int64_t target, uint16_t* out, int64_t cap, uint32_t* poff, int* blk_state);
+
 /* ---- batched decompression: one inverse-BWT pass for many blocks -------------
  * bscgpu_unbwt_batch_device: L of `count` blocks back to back in HBM (block b at Σ sizes[0..b), primary[b] its 1-based
  *   primary index) -> T in the same layout; dT may be dL.  Passes of consecutive blocks, at most max_n bytes and
@@ -425,7 +456,8 @@ enum {
     BSCGPU_K_RADIX_HISTALL = 12, /* single-read sorts: the one histogram read per sort (all digits at once) */
     BSCGPU_K_RADIX_AUX     = 13, /* keys-only passes that also emit the permutation (device coder's orders, inverse BWT): not the graded kernel */
     BSCGPU_K_RC            = 14, /* range coder: many probability streams in one launch (rangecoder.hip) */
-    BSCGPU_K_COUNT         = 15
+    BSCGPU_K_DC_FACTS      = 15, /* device coder, a pass in model segments: per-sub-block facts (flags, decision counts) and segment tables */
+    BSCGPU_K_COUNT         = 16
 };
 typedef struct bscgpu_kstat {
     double   ms;        /* accumulated HIP-event time */
@@ -500,6 +532,19 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          packing places the records by those bits and counts the byte digits, and the sort is one pass shorter
  *                          and reads no histogram.  2: packing places the records, rs_hist_all still counts (measurements).  Same output.
  * BSCGPU_CNT_BWT_FOLDED    (get only) first sorts of this context that took that route.
+ * BSCGPU_OPT_BATCH_MODEL_SEGMENTS  0 (default) / 1: with the coder's own model option on (BSCGPU_OPT_BATCH_MODEL for -e1, _FAST for -e0), a
+ *                          pass that takes the model route takes it in model segments (bscgpu_pstream_batch_segments_device's stage):
+ *                          a pass above the arena's capacity in decisions is cut, not declined, and a block the device cannot model
+ *                          takes the host model alone instead of taking its pass with it.  BSC_BATCH_MODEL_SEGMENT in the environment:
+ *                          decisions per segment (default: the capacity).  Not with BSCGPU_OPT_DEVICE_RC: such a pass takes the
+ *                          whole-pass route.  Same output.
+ * BSCGPU_CNT_BATCH_SEGMENTS  (get only) model segments this context modelled and kept.
+ * BSCGPU_CNT_BATCH_SEG_RERUNS  (get only) segments run again as halves of one that declined while it ran.
+ * BSCGPU_CNT_BATCH_SEG_HOST_BLOCKS  (get only) blocks given to the segmented model that ended on the host model.  After a segmented
+ *                          pass BSCGPU_CNT_DC_LAST_FAIL is the OR of those blocks' reasons.
+ *                          (Counted per block of the layout: with HBM input a block that rides along untransformed — stored, or left to
+ *                          the single path — is planned like any other and counts here if the device leaves it out.)
+ * BSCGPU_CNT_DC_DCAP       (get only) decisions the device model's arena holds for this context (a pass or segment above it cannot be modelled).
  * set returns the previous value or a negative libbsc error code; get the value or a negative error code. */
 enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACKED_STREAM = 4,
        BSCGPU_CNT_DC_REPLAYS = 5, BSCGPU_CNT_DC_LAST_FAIL = 6, BSCGPU_CNT_DC_AVG_UNDECIDED = 7, BSCGPU_CNT_DC_HIST_EXTENDED = 8,
@@ -507,7 +552,9 @@ enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACK
        BSCGPU_OPT_DEVICE_RC = 12, BSCGPU_CNT_DEVICE_RC_BLOCKS = 13,
        BSCGPU_OPT_BATCH_MODEL = 14, BSCGPU_CNT_BATCH_MODEL_PASSES = 15, BSCGPU_CNT_BATCH_MODEL_DECLINED = 16,
        BSCGPU_OPT_BATCH_MODEL_FAST = 17, BSCGPU_CNT_BATCH_FAST_PASSES = 18, BSCGPU_CNT_BATCH_FAST_DECLINED = 19,
-       BSCGPU_OPT_BWT_FOLD = 20, BSCGPU_CNT_BWT_FOLDED = 21 };
+       BSCGPU_OPT_BWT_FOLD = 20, BSCGPU_CNT_BWT_FOLDED = 21,
+       BSCGPU_OPT_BATCH_MODEL_SEGMENTS = 22, BSCGPU_CNT_BATCH_SEGMENTS = 23, BSCGPU_CNT_BATCH_SEG_RERUNS = 24,
+       BSCGPU_CNT_BATCH_SEG_HOST_BLOCKS = 25, BSCGPU_CNT_DC_DCAP = 26 };
 /* _FAIL_AVG: undecided avg_rank flags; _FAIL_HIST: a run_hist bracket open after 9216 predecessors; _FAIL_CAP: more runs or decisions
  * than the context's arena holds; _FAIL_REPLAY: a chain whose bracket stayed open over more than 64 evaluation chunks. */
 enum { BSCGPU_DC_FAIL_AVG = 2, BSCGPU_DC_FAIL_HIST = 4, BSCGPU_DC_FAIL_CAP = 8, BSCGPU_DC_FAIL_REPLAY = 16 };

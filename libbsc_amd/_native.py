@@ -13,7 +13,7 @@ i32p = C.POINTER(C.c_int)
 u32p = C.POINTER(C.c_uint32)
 
 K_NAMES = ["radix_scatter", "radix_hist", "radix_scan", "pack", "seg", "gather", "emit", "misc",
-           "dc_ctx", "dc_part", "dc_eval", "dc_pstream", "radix_hist_all", "radix_aux", "rc"]      # order of the BSCGPU_K_* enum (include/bscgpu.h)
+           "dc_ctx", "dc_part", "dc_eval", "dc_pstream", "radix_hist_all", "radix_aux", "rc", "dc_facts"]      # order of the BSCGPU_K_* enum (include/bscgpu.h)
 
 
 class RcStream(C.Structure):
@@ -105,6 +105,10 @@ def lib():
     L.bscgpu_fast_pstream_host.argtypes = [vp, C.c_int, vp, C.c_int64]
     L.bscgpu_fast_pstream_host.restype = C.c_int64
     L.bscgpu_front_batch_code_psf.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int]
+    L.bscgpu_model_segment_plan.argtypes = [vp, vp, vp, C.c_int, C.c_int64, C.c_int64, vp]
+    L.bscgpu_model_segment_facts_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, vp]
+    L.bscgpu_pstream_batch_segments_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int64, vp, C.c_int64, vp, vp]
+    L.bscgpu_pstream_batch_segments_device.restype = C.c_int64
     L.bscgpu_unbwt_batch_plan.argtypes = [vp, C.c_int, C.c_int64, vp]
     L.bscgpu_unbwt_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp]
     L.bscgpu_decompress_batch_sizes.argtypes = [vp, vp, C.c_int, vp]

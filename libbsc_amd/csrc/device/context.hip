@@ -355,6 +355,7 @@ extern "C" int bscgpu_option_set(bscgpu_ctx* c, int key, int value)
     if (key == BSCGPU_OPT_DEVICE_RC && (value == 0 || value == 1)) { const int old = c->device_rc; c->device_rc = value; return old; }
     if (key == BSCGPU_OPT_BATCH_MODEL && (value == 0 || value == 1)) { const int old = c->batch_model; c->batch_model = value; return old; }
     if (key == BSCGPU_OPT_BATCH_MODEL_FAST && (value == 0 || value == 1)) { const int old = c->batch_model_fast; c->batch_model_fast = value; return old; }
+    if (key == BSCGPU_OPT_BATCH_MODEL_SEGMENTS && (value == 0 || value == 1)) { const int old = c->batch_model_segments; c->batch_model_segments = value; return old; }
     if (key == BSCGPU_OPT_BWT_FOLD && value >= 0 && value <= 2) { const int old = c->bwt_fold; c->bwt_fold = value; return old; }
     return BSC_BAD_PARAMETER;
 }
@@ -379,6 +380,11 @@ extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
     if (key == BSCGPU_OPT_BATCH_MODEL_FAST) return c->batch_model_fast;
     if (key == BSCGPU_CNT_BATCH_FAST_PASSES) return c->cnt_model_fast_passes;
     if (key == BSCGPU_CNT_BATCH_FAST_DECLINED) return c->cnt_model_fast_declined;
+    if (key == BSCGPU_OPT_BATCH_MODEL_SEGMENTS) return c->batch_model_segments;
+    if (key == BSCGPU_CNT_BATCH_SEGMENTS) return c->cnt_seg;
+    if (key == BSCGPU_CNT_BATCH_SEG_RERUNS) return c->cnt_seg_reruns;
+    if (key == BSCGPU_CNT_BATCH_SEG_HOST_BLOCKS) return c->cnt_seg_host_blocks;
+    if (key == BSCGPU_CNT_DC_DCAP) { const int64_t v = devcoder_dcap(c); return v > 0x7fffffff ? 0x7fffffff : (int)v; }   // (saturates: max_n above ~512 MiB)
     if (key == BSCGPU_OPT_BWT_FOLD) return c->bwt_fold;
     if (key == BSCGPU_CNT_BWT_FOLDED) return c->cnt_bwt_folded;
     return BSC_BAD_PARAMETER;

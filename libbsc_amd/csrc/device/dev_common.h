@@ -128,6 +128,9 @@ struct bscgpu_ctx {
     // the fast coder's (devcoder.hip: devcoder_pstream_fast_batch); it shares the pinned stream buffers below
     int  batch_model_fast = 0;    // BSCGPU_OPT_BATCH_MODEL_FAST (default 0: DESIGN §2b, "The fast coder's model of a pass")
     int  cnt_model_fast_passes = 0, cnt_model_fast_declined = 0;   // BSCGPU_CNT_BATCH_FAST_PASSES / _DECLINED
+    // model segments (devcoder.hip: devcoder_pstream_segments; DESIGN §2b, "Model segments")
+    int  batch_model_segments = 0;   // BSCGPU_OPT_BATCH_MODEL_SEGMENTS (default 0)
+    int  cnt_seg = 0, cnt_seg_reruns = 0, cnt_seg_host_blocks = 0;   // BSCGPU_CNT_BATCH_SEGMENTS / _SEG_RERUNS / _SEG_HOST_BLOCKS
     u16* model_host[2] = {nullptr, nullptr};   // pinned: a pass's probability stream coming down (two: coding overlaps the next pass), allocated on first use
     size_t model_host_entries = 0;
     bool model_host_failed = false;            // they could not be pinned: the route is off for this context
@@ -279,6 +282,27 @@ int  devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out);
 // FAIL_CAP and FAIL_REPLAY can be raised: this coder has no avg_rank flags and no run_hist look-back)
 int  devcoder_pstream_fast_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out);
 const u32* devcoder_batch_poff_ptr(const bscgpu_ctx* c);
+// ... of a pass in model segments ("Model segments"): the same inputs plus the layout's blk_sub[count + 1] and
+// sub_run[nsub + 1] (host), coder 1 or 3, target decisions per segment (<= 0: the arena's capacity).  out[0 .. cap) (host): the kept
+// sub-blocks' entries back to back in sub-block order, poff[0..nsub] (host; a sub-block that was not modelled is empty), blk_state[b] =
+// 0 or the BSCGPU_DC_FAIL_* mask that leaves block b to the host model.  per_segment_fit: a segment that no longer fits behind the
+// ones before it is left to the host; else a total above cap is counted, not copied.  *D_out: decisions kept.  BSC_NOT_SUPPORTED: an
+// arena did not fit.  Moves the segment counters of the context.  Synchronous.
+// note (or null): told as the pass settles, on the calling thread, so that coding can start before the last segment.  planned(): the
+// plan is known, blk_state holds the excluded blocks.  settled(b0, b1): the blocks of [b0, b1) with a sub-block are final — their
+// entries have landed in out and their poff entries are written, or blk_state gives them to the host.  Every planned block is settled
+// exactly once before a return >= 0; after planned(), blk_state and poff of settled blocks are not written again.
+struct DcSegNote {
+    void (*planned)(void* user);
+    void (*settled)(void* user, int b0, int b1);
+    void* user;
+};
+int  devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub, int count, const u32* sub_run, int coder, int64_t target,
+                               u16* out, int64_t cap, bool per_segment_fit, u32* poff, int* blk_state, int64_t* D_out,
+                               const DcSegNote* note = nullptr);
+// ... the facts the plan is made of alone: dec[s] / und[s] (host, nsub entries each) of the pass qlfc_front_batch just laid out
+int  devcoder_segment_facts(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* dec, u32* und);
+int64_t devcoder_dcap(const bscgpu_ctx* c);             // decisions the device model's arena holds for this context
 int64_t devcoder_batch_bytes(const bscgpu_ctx* c);      // HBM the batch model added on its first use
 void devcoder_destroy(bscgpu_ctx* c);
 // the range coder stage on c->stream (rangecoder.hip): bscgpu_rc_encode_device without the argument check; synchronous

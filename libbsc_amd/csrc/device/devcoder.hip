@@ -38,6 +38,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <vector>
 #include <type_traits>
 
@@ -96,6 +97,10 @@ struct DevCoder {
     char*  batch_arena = nullptr; size_t batch_bytes = 0; bool batch_alloc_failed = false;
     u16 *esub[4] = {nullptr, nullptr, nullptr, nullptr};
     u8  *sub_maxr = nullptr; u32 *poff_tab = nullptr;
+    // model segments (devcoder_pstream_segments): per sub-block the undecided avg_rank flags and the decisions of the coder at hand,
+    // and the run table of the segment being modelled, rebased to its first run
+    u32 *sub_und = nullptr, *sub_dec = nullptr, *seg_run = nullptr;
+    hipEvent_t seg_ev[2] = {nullptr, nullptr};                 // behind the last copy out of ps[0 / 1] on the copy stream
 };
 
 __device__ __forceinline__ u32 dc_sb_of(u32 j, const DcSub& S)
@@ -177,7 +182,8 @@ template <> struct DcForm<DcSubTab> {
 // two-sided bracket [0, 255] started DC_AVG_WARM runs early; the flag of a run is decided when both ends agree.
 // ---------------------------------------------------------------------------------------------------------------------
 template <class SB>
-__global__ __launch_bounds__(WG) void dc_avg_kernel(const u8* __restrict__ rank, u32 m, SB S, u8* __restrict__ ge32, u32* __restrict__ meta)
+__global__ __launch_bounds__(WG) void dc_avg_kernel(const u8* __restrict__ rank, u32 m, SB S, u8* __restrict__ ge32, u32* __restrict__ meta,
+                                                    u32* __restrict__ sub_und /* table only (may be null): undecided flags per sub-block */)
 {
     typedef DcForm<SB> F;
     const u32 c = blockIdx.x * WG + threadIdx.x;
@@ -190,15 +196,19 @@ __global__ __launch_bounds__(WG) void dc_avg_kernel(const u8* __restrict__ rank,
     u32 lo = 0, hi = (w0 == sb_first) ? 0u : F::avg_top(S, sb);
     for (u32 j = w0; j < (u32)j0; ++j) { const u32 r = rank[j]; lo = avg_rank_next(lo, r); hi = avg_rank_next(hi, r); }
     u32 next_first = F::next_first(S, sb);                            // (a chunk of a batched pass can hold dozens of sub-block starts)
-    u32 und = 0;
+    u32 und = 0, und_flushed = 0;                                     // (table: what of und has gone to sub_und)
     for (u32 j = (u32)j0; j < j1; ++j) {
-        if (j == next_first) { lo = hi = 0; ++sb; next_first = F::next_first(S, sb); }
+        if (j == next_first) {
+            if constexpr (F::TAB) { if (sub_und && und != und_flushed) atomicAdd(&sub_und[sb], und - und_flushed); und_flushed = und; }
+            lo = hi = 0; ++sb; next_first = F::next_first(S, sb);
+        }
         const u32 f = lo >= 32u;
         und += (f != (u32)(hi >= 32u));
         ge32[j] = (u8)f;
         const u32 r = rank[j];
         lo = avg_rank_next(lo, r); hi = avg_rank_next(hi, r);
     }
+    if constexpr (F::TAB) { if (sub_und && und != und_flushed) atomicAdd(&sub_und[sb], und - und_flushed); }
     if (und) atomicAdd(&meta[DM_AVG_UND], und);
 }
 
@@ -1324,6 +1334,40 @@ __global__ __launch_bounds__(WG) void dc_tab_prep_kernel(const u32* __restrict__
     if (lane == 63u) maxr[s] = (u8)bsr(cnt - 1u);
 }
 
+// ---- model segments: what the plan needs of every sub-block, before any sort or partition -------------------------------------
+// Decisions of every sub-block of a pass for the coder at hand (maxr: the table's, 7 for the fast coder; ge32: the flags, zero for the
+// fast coder): a run's count is the case analysis the partition walks (count_rank_side / count_run_side of the item the items kernel
+// would pack).  Thread per run.  Runs are in stream order, so the sub-block id is non-decreasing across a wavefront: one inclusive scan
+// of the counts, and the last lane of every sub-block's stretch adds (its prefix - the prefix in front of the stretch's first lane).
+__global__ __launch_bounds__(WG) void dc_sub_dec_kernel(const u8* __restrict__ sym, const u8* __restrict__ rank, const u32* __restrict__ start,
+                                                        const u8* __restrict__ ge32, u32 m, DcSubTab S, u32* __restrict__ sub_dec)
+{
+    typedef DcForm<DcSubTab> F;
+    const u32 j = blockIdx.x * WG + threadIdx.x, lane = threadIdx.x & 63u;
+    u32 nd = 0, sb = 0xffffffffu;                                     // (lanes past the end: a stretch of their own that adds nothing)
+    if (j < m) {
+        const ItemB it = F::unpack(F::item(S, sym, rank, start, ge32, j, m, 0u));
+        sb = it.sb;
+        nd = (u32)(count_rank_side(it, (int)it.maxr) + count_run_side(it));
+    }
+    const u32 incl = wave_incl_sum(nd);
+    const u32 prev_sb = (u32)__shfl_up((int)sb, 1, 64);
+    const u64 heads = __ballot(lane == 0u || prev_sb != sb);          // first lane of every stretch
+    const bool tail = lane == 63u || ((heads >> (lane + 1u)) & 1ull) != 0ull;
+    const u64 upto = heads & (~0ull >> (63u - lane));                 // heads at or below this lane: never empty (lane 0 is one)
+    const u32 first = 63u - (u32)__builtin_clzll(upto);
+    const u32 before = (u32)__shfl((int)(incl - nd), (int)first, 64); // the scan in front of the stretch
+    if (tail && j < m && incl != before) atomicAdd(&sub_dec[sb], incl - before);
+}
+// The rebased run table of the segment [s0, s0 + nsub_seg) whose runs are [r0, r1): to every kernel instantiated for a table the
+// segment then is a small pass of its own (sub_off / sub_base / maxr enter offset by s0, the run arrays and flags offset by r0).
+__global__ __launch_bounds__(WG) void dc_seg_tab_kernel(const u32* __restrict__ sub_run, u32 s0, u32 nsub_seg, u32 r0, u32 r1, u32* __restrict__ seg_run)
+{
+    const u32 i = blockIdx.x * WG + threadIdx.x;
+    if (i < nsub_seg) seg_run[i] = sub_run[s0 + i] - r0;
+    else if (i == nsub_seg) seg_run[i] = r1 - r0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1377,6 +1421,7 @@ void devcoder_destroy(bscgpu_ctx* c)
     if (!d) return;
     if (d->arena) hipFree(d->arena);
     if (d->batch_arena) hipFree(d->batch_arena);
+    for (int k = 0; k < 2; ++k) if (d->seg_ev[k]) hipEventDestroy(d->seg_ev[k]);
     if (d->hmeta) hipHostFree(d->hmeta);
     delete d;
     c->dc = nullptr;
@@ -1407,6 +1452,11 @@ void devcoder_warm_tables()
     static Warm warm;
 }
 
+// the arena's capacity: runs (bytes of max_n, padded) and decisions (four per byte of that)
+static size_t dc_capacity_runs(int64_t max_n) { return ((size_t)max_n + 4096 + 4095) / 4096 * 4096; }
+static size_t dc_capacity_decisions(int64_t max_n) { return 4 * dc_capacity_runs(max_n) + 65536; }
+int64_t devcoder_dcap(const bscgpu_ctx* c) { return (int64_t)dc_capacity_decisions(c->max_n); }
+
 int devcoder_ensure(bscgpu_ctx* c)
 {
     if (c->dc) return BSC_NO_ERROR;
@@ -1416,8 +1466,7 @@ int devcoder_ensure(bscgpu_ctx* c)
     if (getenv("BSC_DEVCODER_FAIL_ALLOC")) { c->dc_alloc_failed = true; return BSC_NOT_SUPPORTED; }      // tests: an arena that does not fit
     CtxTimer tm("devcoder_ensure (arena, tables)");
     DevCoder* d = new DevCoder();
-    const size_t N = ((size_t)c->max_n + 4096 + 4095) / 4096 * 4096;
-    d->Mcap = N; d->Dcap = 4 * N + 65536;
+    d->Mcap = dc_capacity_runs(c->max_n); d->Dcap = dc_capacity_decisions(c->max_n);
     const size_t M = d->Mcap + 64, D = d->Dcap + 64, NCH = d->Dcap / DC_EV + 16;
     struct Carve { void** p; size_t bytes; };
     Carve carve[] = {
@@ -1602,7 +1651,7 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
     bool may_escape = false;
     for (int b = 0; b < nb; ++b) may_escape |= max_rank[b] > 4;
     if (may_escape)
-        hipLaunchKernelGGL(dc_avg_kernel<DcSub>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta);
+        hipLaunchKernelGGL(dc_avg_kernel<DcSub>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta, (u32*)nullptr);
     else
         HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));
     hipLaunchKernelGGL(dc_items_kernel<DcSub>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, d->ge32, m, n, S, d->key_ch);
@@ -1715,6 +1764,8 @@ static int devcoder_batch_ensure(bscgpu_ctx* c, DevCoder* d)
     Carve carve[] = {
         {(void**)&d->esub[0], 2 * D}, {(void**)&d->esub[1], 2 * D}, {(void**)&d->esub[2], 2 * D}, {(void**)&d->esub[3], 2 * D},
         {(void**)&d->sub_maxr, (size_t)FRONT_MAX_SUB + 64}, {(void**)&d->poff_tab, 4 * ((size_t)FRONT_MAX_SUB + 64)},
+        {(void**)&d->sub_und, 4 * ((size_t)FRONT_MAX_SUB + 64)}, {(void**)&d->sub_dec, 4 * ((size_t)FRONT_MAX_SUB + 64)},
+        {(void**)&d->seg_run, 4 * ((size_t)FRONT_MAX_SUB + 64)},
     };
     size_t total = 0;
     for (auto& cv : carve) total += dc_align(cv.bytes);
@@ -1733,33 +1784,23 @@ static int devcoder_batch_ensure(bscgpu_ctx* c, DevCoder* d)
 // poff[0..nsub] in d->poff_tab.  The same four stages, the same kernels, instantiated for the table (DcSubTab); every guarded exit
 // keeps its meaning with the PASS as the unit: a raised flag declines the whole pass (BSC_NOT_SUPPORTED, c->dc_last_fail says why).
 // Two syncs: the families' sizes after the partition, the flags after the stream.
-int devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out)
+//
+// dc_tab_static is the part a whole pass and a model segment share: everything from the items on, over the table S and the run
+// arrays / flags the caller hands in (a segment: its rebased table, the pass's arrays offset to its first run).  The caller has
+// cleared meta and present.  expect >= 0: the decisions the plan counted for these sub-blocks — the families' totals must equal it.
+// poff_host: poff_tab[0..S.nsub] also comes down with the last sync.
+static int dc_tab_static(bscgpu_ctx* c, DevCoder* d, const DcSubTab& S, const u8* dsym, const u8* drank, const u32* dstart, const u8* ge32,
+                         u32 m, int psbuf, int64_t expect, u32* poff_host, u32* D_out)
 {
-    int rc = devcoder_ensure(c);
-    if (rc < 0) return rc;
-    DevCoder* d = c->dc;
-    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = 0;
-    c->dc_last_fail = m > d->Mcap ? (int)FAIL_CAP : 0;
-    if (m == 0 || m > d->Mcap || nsub < 1 || nsub > FRONT_MAX_SUB || !c->front_tab) return BSC_NOT_SUPPORTED;
-    rc = devcoder_batch_ensure(c, d);
-    if (rc < 0) return rc;
-    const FrontTab T = qlfc_front_tab(c, nsub);
-    const u8* dsym = reinterpret_cast<const u8*>(c->vA); const u8* drank = reinterpret_cast<const u8*>(c->vB); const u32* dstart = c->SA;
-    DcSubTab S; S.nsub = (u32)nsub; S.run = T.sub_run; S.off = T.sub_off; S.base = T.sub_base; S.maxr = d->sub_maxr;
-
-    HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
-    HIP_TRY(c, hipMemsetAsync(d->present, 0, (size_t)DC_KIND_WORDS * 4, c->stream));
+    const int nsub = (int)S.nsub;
     const u32 gm = (m + WG - 1) / WG;
     const u32 gm8 = (gm + 7u) / 8u * 8u;            // kernels that use dc_virtual_block()
     prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
-    hipLaunchKernelGGL(dc_tab_prep_kernel, dim3(((u32)nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, T.first_run, (u32)nsub, m, -1, d->sub_maxr, T.sub_run);
-    // (always: which sub-blocks can escape is not known on the host here; one of at most 32 symbols never leaves a flag open — avg_top)
-    hipLaunchKernelGGL(dc_avg_kernel<DcSubTab>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta);
-    hipLaunchKernelGGL(dc_items_kernel<DcSubTab>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, d->ge32, m, 0u, S, d->key_ch);
+    hipLaunchKernelGGL(dc_items_kernel<DcSubTab>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, ge32, m, 0u, S, d->key_ch);
     prof_end(c);
     RadixPass top; top.shift = 56; top.bits = 8;
     int in_alt = 0;
-    rc = radix_sort_passes(c, d->key_ch, d->key_ch_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_ch);
+    int rc = radix_sort_passes(c, d->key_ch, d->key_ch_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_ch);
     if (rc < 0) return rc;
     prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
     hipLaunchKernelGGL(dc_ctx_kernel<DcSubTab>, dim3(gm8), dim3(WG), 0, c->stream, d->key_ch, d->key_ch_s, d->inv_ch, m, S, d->tab_rank, d->tab_run,
@@ -1784,6 +1825,7 @@ int devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out)
     for (int job = 0; job < 4; ++job) E[job] = d->hmeta[DM_D0 + job];
     const u32 Efull = E[0];
     if (Efull != E[1] || Efull != E[2] + E[3]) return ctx_fail(c, BSC_GPU_ERROR, "device coder: decision counts of the families differ", hipSuccess);
+    if (expect >= 0 && (int64_t)Efull != expect) return ctx_fail(c, BSC_GPU_ERROR, "device coder: a segment's decisions differ from the plan's count", hipSuccess);
     rc = dc_eval_static(c, d, E, true);
     if (rc < 0) return rc;
 
@@ -1793,12 +1835,13 @@ int devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out)
     G.pos_sp = d->pos[0]; G.pos_ch = d->pos[1]; G.pos_sr = d->pos[2]; G.pos_sn = d->pos[3];
     G.V_sp = d->V[0]; G.V_ch = d->V[1]; G.V_sr = d->V[2]; G.V_sn = d->V[3];
     prof_begin(c, BSCGPU_K_DC_PSTREAM, (u64)Efull * 26, Efull);
-    if (c->ps_guard[0]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ps_guard[0], 0));     // the buffer's previous copy-out (a single-path block)
-    for (int b = 0; b < 8; ++b) if (c->ps_guard_sig[0][b]) (void)dma_wait(c->ps_guard_sig[0][b]);
-    hipLaunchKernelGGL((dc_pstream_kernel<false, false, DcSubTab>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[0], (u16*)nullptr, Efull, DcP13{});
+    if (c->ps_guard[psbuf & 1]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ps_guard[psbuf & 1], 0));     // the buffer's previous copy-out (a single-path block)
+    for (int b = 0; b < 8; ++b) if (c->ps_guard_sig[psbuf & 1][b]) (void)dma_wait(c->ps_guard_sig[psbuf & 1][b]);
+    hipLaunchKernelGGL((dc_pstream_kernel<false, false, DcSubTab>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], (u16*)nullptr, Efull, DcP13{});
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
+    if (poff_host) HIP_TRY(c, hipMemcpyAsync(poff_host, d->poff_tab, ((size_t)nsub + 1) * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
     prof_collect(c);
     dc_note_block(c, d);
@@ -1806,6 +1849,30 @@ int devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out)
     if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder batch] sub-blocks %d, decisions %u, types %u, chunks replayed %u\n", nsub, Efull, d->hmeta[DM_NTYPES], d->hmeta[DM_REPLAYS]);
     *D_out = Efull;
     return BSC_NO_ERROR;
+}
+
+int devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out)
+{
+    int rc = devcoder_ensure(c);
+    if (rc < 0) return rc;
+    DevCoder* d = c->dc;
+    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = 0;
+    c->dc_last_fail = m > d->Mcap ? (int)FAIL_CAP : 0;
+    if (m == 0 || m > d->Mcap || nsub < 1 || nsub > FRONT_MAX_SUB || !c->front_tab) return BSC_NOT_SUPPORTED;
+    rc = devcoder_batch_ensure(c, d);
+    if (rc < 0) return rc;
+    const FrontTab T = qlfc_front_tab(c, nsub);
+    const u8* dsym = reinterpret_cast<const u8*>(c->vA); const u8* drank = reinterpret_cast<const u8*>(c->vB); const u32* dstart = c->SA;
+    DcSubTab S; S.nsub = (u32)nsub; S.run = T.sub_run; S.off = T.sub_off; S.base = T.sub_base; S.maxr = d->sub_maxr;
+
+    HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d->present, 0, (size_t)DC_KIND_WORDS * 4, c->stream));
+    prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
+    hipLaunchKernelGGL(dc_tab_prep_kernel, dim3(((u32)nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, T.first_run, (u32)nsub, m, -1, d->sub_maxr, T.sub_run);
+    // (always: which sub-blocks can escape is not known on the host here; one of at most 32 symbols never leaves a flag open — avg_top)
+    hipLaunchKernelGGL(dc_avg_kernel<DcSubTab>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta, (u32*)nullptr);
+    prof_end(c);
+    return dc_tab_static(c, d, S, dsym, drank, dstart, d->ge32, m, 0, -1, nullptr, D_out);
 }
 const u32* devcoder_batch_poff_ptr(const bscgpu_ctx* c) { return c->dc ? c->dc->poff_tab : nullptr; }
 
@@ -1876,31 +1943,19 @@ static int devcoder_pstream_fast(bscgpu_ctx* c, DevCoder* d, const u8* dsym, con
 // a fast chain is (sub-block, decision type, symbol)), one evaluation with mp_fast, one stream whose entries are the counter values
 // (dcm::PSF_*).  max_rank is 7 for every sub-block.  No avg_rank flags, no run_hist look-back: FAIL_CAP and FAIL_REPLAY are the only
 // flags that can be raised.  The arena of devcoder_batch_ensure as it is (one esub plane of its four is used).  Two syncs.
-int devcoder_pstream_fast_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out)
+// dc_tab_fast: the part a whole pass and a model segment share (as dc_tab_static; the caller has cleared meta and ge32).
+static int dc_tab_fast(bscgpu_ctx* c, DevCoder* d, const DcSubTab& S, const u8* dsym, const u8* drank, const u32* dstart, const u8* ge32,
+                       u32 m, int psbuf, int64_t expect, u32* poff_host, u32* D_out)
 {
-    int rc = devcoder_ensure(c);
-    if (rc < 0) return rc;
-    DevCoder* d = c->dc;
-    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = 0;
-    c->dc_last_fail = m > d->Mcap ? (int)FAIL_CAP : 0;
-    if (m == 0 || m > d->Mcap || nsub < 1 || nsub > FRONT_MAX_SUB || !c->front_tab) return BSC_NOT_SUPPORTED;
-    rc = devcoder_batch_ensure(c, d);
-    if (rc < 0) return rc;
-    const FrontTab T = qlfc_front_tab(c, nsub);
-    const u8* dsym = reinterpret_cast<const u8*>(c->vA); const u8* drank = reinterpret_cast<const u8*>(c->vB); const u32* dstart = c->SA;
-    DcSubTab S; S.nsub = (u32)nsub; S.run = T.sub_run; S.off = T.sub_off; S.base = T.sub_base; S.maxr = d->sub_maxr;
-
-    HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
+    const int nsub = (int)S.nsub;
     const u32 gm = (m + WG - 1) / WG;
     const u32 gm8 = (gm + 7u) / 8u * 8u;            // kernels that use dc_virtual_block()
     prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 14, m);
-    hipLaunchKernelGGL(dc_tab_prep_kernel, dim3(((u32)nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, T.first_run, (u32)nsub, m, 7, d->sub_maxr, T.sub_run);
-    HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));              // no escape coding in this coder
-    hipLaunchKernelGGL(dc_items_kernel<DcSubTab>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, d->ge32, m, 0u, S, d->key_ch);
+    hipLaunchKernelGGL(dc_items_kernel<DcSubTab>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, ge32, m, 0u, S, d->key_ch);
     prof_end(c);
     RadixPass top; top.shift = 56; top.bits = 8;
     int in_alt = 0;
-    rc = radix_sort_passes(c, d->key_ch, d->key_ch_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_ch);
+    int rc = radix_sort_passes(c, d->key_ch, d->key_ch_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_ch);
     if (rc < 0) return rc;
     {
         const DcGeom g = dc_geom(m);
@@ -1921,6 +1976,7 @@ int devcoder_pstream_fast_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out)
     if (d->hmeta[DM_FAIL] != 0) { dc_note_block(c, d); return BSC_NOT_SUPPORTED; }
     const u32 E = d->hmeta[DM_D0 + 1];
     if (d->hmeta[DM_D0 + 0] != E) return ctx_fail(c, BSC_GPU_ERROR, "device coder (fast): decision counts of stream and chain order differ", hipSuccess);
+    if (expect >= 0 && (int64_t)E != expect) return ctx_fail(c, BSC_GPU_ERROR, "device coder (fast): a segment's decisions differ from the plan's count", hipSuccess);
     rc = dc_eval_fast(c, d, E, true);
     if (rc < 0) return rc;
 
@@ -1930,18 +1986,226 @@ int devcoder_pstream_fast_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out)
     G.pos_sp = d->pos[1]; G.pos_ch = d->pos[1]; G.pos_sr = d->pos[1]; G.pos_sn = d->pos[1];
     G.V_sp = d->V[1]; G.V_ch = d->V[1]; G.V_sr = d->V[1]; G.V_sn = d->V[1];
     prof_begin(c, BSCGPU_K_DC_PSTREAM, (u64)E * 10, E);
-    if (c->ps_guard[0]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ps_guard[0], 0));     // the buffer's previous copy-out (a single-path block)
-    for (int b = 0; b < 8; ++b) if (c->ps_guard_sig[0][b]) (void)dma_wait(c->ps_guard_sig[0][b]);
-    hipLaunchKernelGGL((dc_pstream_kernel<true, false, DcSubTab>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp_fast, d->meta, d->ps[0], (u16*)nullptr, E, DcP13{});
+    if (c->ps_guard[psbuf & 1]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ps_guard[psbuf & 1], 0));     // the buffer's previous copy-out (a single-path block)
+    for (int b = 0; b < 8; ++b) if (c->ps_guard_sig[psbuf & 1][b]) (void)dma_wait(c->ps_guard_sig[psbuf & 1][b]);
+    hipLaunchKernelGGL((dc_pstream_kernel<true, false, DcSubTab>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp_fast, d->meta, d->ps[psbuf & 1], (u16*)nullptr, E, DcP13{});
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
+    if (poff_host) HIP_TRY(c, hipMemcpyAsync(poff_host, d->poff_tab, ((size_t)nsub + 1) * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
     prof_collect(c);
     dc_note_block(c, d);
     if (d->hmeta[DM_FAIL] != 0) return BSC_NOT_SUPPORTED;
     if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder fast batch] sub-blocks %d, decisions %u, chunks replayed %u\n", nsub, E, d->hmeta[DM_REPLAYS]);
     *D_out = E;
+    return BSC_NO_ERROR;
+}
+
+int devcoder_pstream_fast_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out)
+{
+    int rc = devcoder_ensure(c);
+    if (rc < 0) return rc;
+    DevCoder* d = c->dc;
+    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = 0;
+    c->dc_last_fail = m > d->Mcap ? (int)FAIL_CAP : 0;
+    if (m == 0 || m > d->Mcap || nsub < 1 || nsub > FRONT_MAX_SUB || !c->front_tab) return BSC_NOT_SUPPORTED;
+    rc = devcoder_batch_ensure(c, d);
+    if (rc < 0) return rc;
+    const FrontTab T = qlfc_front_tab(c, nsub);
+    const u8* dsym = reinterpret_cast<const u8*>(c->vA); const u8* drank = reinterpret_cast<const u8*>(c->vB); const u32* dstart = c->SA;
+    DcSubTab S; S.nsub = (u32)nsub; S.run = T.sub_run; S.off = T.sub_off; S.base = T.sub_base; S.maxr = d->sub_maxr;
+
+    HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
+    prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 14, m);
+    hipLaunchKernelGGL(dc_tab_prep_kernel, dim3(((u32)nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, T.first_run, (u32)nsub, m, 7, d->sub_maxr, T.sub_run);
+    HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));              // no escape coding in this coder
+    prof_end(c);
+    return dc_tab_fast(c, d, S, dsym, drank, dstart, d->ge32, m, 0, -1, nullptr, D_out);
+}
+
+// ---- a pass in model segments ("Model segments") --------------------------------------------------------------------
+// Sub-blocks are independent chains by construction (the chain identity carries the sub-block), so the model of a pass can run over
+// any contiguous range of its sub-blocks and write the same entries.  Facts first, once per pass and before any sort: every
+// sub-block's undecided avg_rank flags (dc_avg_kernel) and its decisions for this coder (dc_sub_dec_kernel).  The plan
+// (bscgpu_model_segment_plan) excludes a block with an undecided flag or more decisions than the arena holds and cuts the rest into
+// segments of at most min(Dcap, target) decisions; each segment then is a small pass of its own to dc_tab_static / dc_tab_fast (its
+// rebased run table: dc_seg_tab_kernel).  The device stream is double-buffered over ps[0 / 1]: segment k + 1 is modelled while
+// segment k's entries leave on the copy stream.  A segment that declines while it runs (FAIL_HIST, FAIL_REPLAY) is split at the block
+// boundary nearest half its decisions and both halves run again, depth first; a single block that declines is marked with the reason.
+// out / cap: where the kept entries go back to back (host); per_segment_fit: a segment that no longer fits behind the ones before
+// it is left to the host (FAIL_CAP) — else a total above cap is counted, not copied.
+// the facts of a pass (after qlfc_front_batch): dec[s] / und[s] of every sub-block on the host; ge32 and sub_maxr stay for the segments
+static int dc_segment_facts(bscgpu_ctx* c, DevCoder* d, u32 m, int nsub, bool fast, u32* dec, u32* und)
+{
+    const FrontTab T = qlfc_front_tab(c, nsub);
+    const u8* dsym = reinterpret_cast<const u8*>(c->vA); const u8* drank = reinterpret_cast<const u8*>(c->vB); const u32* dstart = c->SA;
+    DcSubTab S; S.nsub = (u32)nsub; S.run = T.sub_run; S.off = T.sub_off; S.base = T.sub_base; S.maxr = d->sub_maxr;
+    HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d->sub_und, 0, (size_t)nsub * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d->sub_dec, 0, (size_t)nsub * 4, c->stream));
+    prof_begin(c, BSCGPU_K_DC_FACTS, (u64)m * 6, m);
+    hipLaunchKernelGGL(dc_tab_prep_kernel, dim3(((u32)nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, T.first_run, (u32)nsub, m, fast ? 7 : -1, d->sub_maxr, T.sub_run);
+    if (fast) HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));
+    else hipLaunchKernelGGL(dc_avg_kernel<DcSubTab>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta, d->sub_und);
+    hipLaunchKernelGGL(dc_sub_dec_kernel, dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, dsym, drank, dstart, d->ge32, m, S, d->sub_dec);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(und, d->sub_und, (size_t)nsub * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dec, d->sub_dec, (size_t)nsub * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    prof_collect(c);
+    return BSC_NO_ERROR;
+}
+int devcoder_segment_facts(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* dec, u32* und)
+{
+    int rc = devcoder_ensure(c);
+    if (rc < 0) return rc;
+    DevCoder* d = c->dc;
+    if (m == 0 || m > d->Mcap || nsub < 1 || nsub > FRONT_MAX_SUB || !c->front_tab) return BSC_NOT_SUPPORTED;
+    rc = devcoder_batch_ensure(c, d);
+    if (rc < 0) return rc;
+    return dc_segment_facts(c, d, m, nsub, coder == 3, dec, und);
+}
+
+int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub, int count, const u32* sub_run, int coder, int64_t target,
+                              u16* out, int64_t cap, bool per_segment_fit, u32* poff, int* blk_state, int64_t* D_out, const DcSegNote* note)
+{
+    int rc = devcoder_ensure(c);
+    if (rc < 0) return rc;
+    DevCoder* d = c->dc;
+    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = 0;
+    c->dc_last_fail = 0;
+    if (m == 0 || m > d->Mcap || nsub < 1 || nsub > FRONT_MAX_SUB || !c->front_tab) return BSC_NOT_SUPPORTED;
+    rc = devcoder_batch_ensure(c, d);
+    if (rc < 0) return rc;
+    for (int k = 0; k < 2; ++k)
+        if (!d->seg_ev[k]) HIP_TRY(c, hipEventCreateWithFlags(&d->seg_ev[k], hipEventDisableTiming));
+    const bool fast = coder == 3;                                      // LIBBSC_CODER_QLFC_FAST
+    const FrontTab T = qlfc_front_tab(c, nsub);
+    const u8* dsym = reinterpret_cast<const u8*>(c->vA); const u8* drank = reinterpret_cast<const u8*>(c->vB); const u32* dstart = c->SA;
+
+    std::vector<u32> und((size_t)nsub), dec((size_t)nsub);
+    rc = dc_segment_facts(c, d, m, nsub, fast, dec.data(), und.data());
+    if (rc < 0) return rc;
+    int64_t und_total = 0;
+    for (int s = 0; s < nsub; ++s) und_total += und[s];
+
+    // the plan
+    std::vector<int> seg_of((size_t)count);
+    const int nseg = bscgpu_model_segment_plan(dec.data(), und.data(), blk_sub, count, (int64_t)d->Dcap, target, seg_of.data());
+    if (nseg < 0) return ctx_fail(c, nseg, "device coder: segment plan", hipSuccess);
+    auto blk_dec = [&](int b) { int64_t t = 0; for (int s = blk_sub[b]; s < blk_sub[b + 1]; ++s) t += dec[s]; return t; };
+    auto blk_und = [&](int b) { for (int s = blk_sub[b]; s < blk_sub[b + 1]; ++s) if (und[s]) return true; return false; };
+    struct Seg { int b0, b1; };
+    std::vector<Seg> todo;                                            // a stack: depth first, in block order
+    int64_t planned = 0;
+    for (int b = count - 1; b >= 0; --b) {
+        blk_state[b] = 0;
+        if (blk_sub[b + 1] == blk_sub[b]) continue;                   // an empty block: nothing to model
+        if (seg_of[b] < 0) { blk_state[b] = blk_und(b) ? (int)FAIL_AVG : (int)FAIL_CAP; continue; }
+        planned += blk_dec(b);
+        if (!todo.empty() && seg_of[todo.back().b0] == seg_of[b]) todo.back().b0 = b; else todo.push_back(Seg{b, b + 1});
+    }
+    // (the ranges were grown from the right: an empty block between two members of a segment lies inside its range, one at its left
+    // edge does not — either way it has no sub-block)
+    const bool copy_all = per_segment_fit || planned <= cap;
+    int nblk = 0; for (int b = 0; b < count; ++b) nblk += blk_sub[b + 1] > blk_sub[b];
+    int lg = 0; while ((1 << lg) < nblk) ++lg;
+    const int rerun_max = 2 * lg + 2;
+    int reruns = 0, kept = 0, launched = 0, replays = 0, hist_ext = 0;
+    std::vector<u32> pseg((size_t)nsub + 1);
+    int64_t base = 0;
+    // poff is written as the segments are kept (they come in block order): everything up to sub-block `filled` is final
+    int filled = 0;
+    poff[0] = 0;
+    auto fill_to = [&](int s) { for (; filled < s; ++filled) poff[filled + 1] = poff[filled]; };
+    // the segments whose copy-out is in flight, oldest first (at most one per ps buffer)
+    struct Pend { int b0, b1, ev; };
+    std::deque<Pend> pend;
+    auto settle = [&](int b0, int b1) { if (note) note->settled(note->user, b0, b1); };
+    // tell what has landed: the copies up to the one out of buffer `upto` (0 / 1) or all of them (2) are waited for, the ones behind
+    // them are told if they are found landed
+    auto landed = [&](int upto) -> hipError_t {
+        int must = 0;                                                  // how many of the oldest to wait for
+        for (size_t k = 0; k < pend.size(); ++k) if (upto == 2 || pend[k].ev == upto) must = (int)k + 1;
+        while (!pend.empty()) {
+            const Pend q = pend.front();
+            if (must <= 0 && hipEventQuery(d->seg_ev[q.ev]) != hipSuccess) break;
+            const hipError_t e = hipEventSynchronize(d->seg_ev[q.ev]);
+            if (e != hipSuccess) return e;
+            pend.pop_front(); --must;
+            settle(q.b0, q.b1);
+        }
+        return hipSuccess;
+    };
+    if (note) note->planned(note->user);
+    auto run = [&]() -> int {
+    while (!todo.empty()) {
+        const Seg g = todo.back(); todo.pop_back();
+        const int s0 = blk_sub[g.b0], s1 = blk_sub[g.b1];
+        const u32 r0 = sub_run[s0], r1 = sub_run[s1];
+        int64_t expect = 0;
+        for (int s = s0; s < s1; ++s) expect += dec[s];
+        auto give_up = [&](int why) { for (int b = g.b0; b < g.b1; ++b) if (blk_sub[b + 1] > blk_sub[b]) blk_state[b] = why; settle(g.b0, g.b1); };
+        if (per_segment_fit && base + expect > cap) { give_up((int)FAIL_CAP); continue; }
+        const int psbuf = launched++ & 1;
+        HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
+        if (!fast) HIP_TRY(c, hipMemsetAsync(d->present, 0, (size_t)DC_KIND_WORDS * 4, c->stream));
+        prof_begin(c, BSCGPU_K_DC_FACTS, (u64)(s1 - s0) * 8, (u64)(s1 - s0));
+        hipLaunchKernelGGL(dc_seg_tab_kernel, dim3(((u32)(s1 - s0) + 1 + WG - 1) / WG), dim3(WG), 0, c->stream, T.sub_run, (u32)s0, (u32)(s1 - s0), r0, r1, d->seg_run);
+        prof_end(c);
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, d->seg_ev[psbuf], 0));          // this buffer's copy-out of two segments ago
+        DcSubTab G; G.nsub = (u32)(s1 - s0); G.run = d->seg_run; G.off = T.sub_off + s0; G.base = T.sub_base + s0; G.maxr = d->sub_maxr + s0;
+        u32 D = 0;
+        rc = fast ? dc_tab_fast(c, d, G, dsym + r0, drank + r0, dstart + r0, d->ge32 + r0, r1 - r0, psbuf, expect, pseg.data(), &D)
+                  : dc_tab_static(c, d, G, dsym + r0, drank + r0, dstart + r0, d->ge32 + r0, r1 - r0, psbuf, expect, pseg.data(), &D);
+        replays += c->dc_replays; hist_ext += c->dc_hist_ext;
+        if (rc == BSC_NOT_SUPPORTED) {
+            const int why = c->dc_last_fail;
+            int members = 0; for (int b = g.b0; b < g.b1; ++b) members += blk_sub[b + 1] > blk_sub[b];
+            if (members < 2 || reruns + 2 > rerun_max) { give_up(why); continue; }
+            // the block boundary nearest half the decisions, with a member on either side
+            int cut = -1; int64_t acc = 0, best = 0;
+            int seen = 0;
+            for (int b = g.b0; b < g.b1; ++b) {
+                if (blk_sub[b + 1] == blk_sub[b]) continue;
+                acc += blk_dec(b); ++seen;
+                if (seen == members) break;
+                const int64_t dist = acc * 2 > expect ? acc * 2 - expect : expect - acc * 2;
+                if (cut < 0 || dist < best) { cut = b + 1; best = dist; }
+            }
+            todo.push_back(Seg{cut, g.b1}); todo.push_back(Seg{g.b0, cut});
+            reruns += 2;
+            continue;
+        }
+        if (rc < 0) return rc;
+        fill_to(s0);
+        for (int s = s0; s < s1; ++s) poff[s + 1] = poff[s0] + (pseg[s - s0 + 1] - pseg[0]);
+        filled = s1;
+        // this buffer's earlier copy-out has landed (the stream kernel waited for it), maybe the other one's too
+        HIP_TRY(c, landed(psbuf));
+        if (copy_all && D > 0) {
+            HIP_TRY(c, hipMemcpyAsync(out + base, d->ps[psbuf], (size_t)D * 2, hipMemcpyDeviceToHost, c->copy_stream));
+            HIP_TRY(c, hipEventRecord(d->seg_ev[psbuf], c->copy_stream));
+            pend.push_back(Pend{g.b0, g.b1, psbuf});
+        } else settle(g.b0, g.b1);
+        base += D; ++kept;
+    }
+    HIP_TRY(c, landed(2));
+    return BSC_NO_ERROR;
+    };
+    rc = run();
+    // (no copy into the caller's buffer may outlive the call, whichever way it ends)
+    if (hipStreamSynchronize(c->copy_stream) != hipSuccess && rc >= 0) rc = ctx_fail(c, BSC_GPU_ERROR, "device coder: segment copy-out", hipSuccess);
+    if (rc < 0) return rc;
+    fill_to(nsub);
+    int fail = 0, host_blocks = 0;
+    for (int b = 0; b < count; ++b) if (blk_state[b]) { fail |= blk_state[b]; ++host_blocks; }
+    c->dc_last_fail = fail; c->dc_replays = replays; c->dc_hist_ext = hist_ext; c->dc_avg_und = (int)und_total;
+    c->cnt_seg += kept; c->cnt_seg_reruns += reruns; c->cnt_seg_host_blocks += host_blocks;
+    if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder segments] sub-blocks %d, planned %d, kept %d, re-runs %d, blocks left to the host %d, decisions %lld\n", nsub, nseg, kept, reruns, host_blocks, (long long)base);
+    *D_out = base;
     return BSC_NO_ERROR;
 }
 

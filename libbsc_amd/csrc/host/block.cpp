@@ -1878,6 +1878,56 @@ extern "C" BSCGPU_API int64_t bscgpu_fast_pstream_batch_device(bscgpu_ctx* c, co
     return pstream_batch_device(c, dL, sizes, count, out, ps, cap, poff, LIBBSC_CODER_QLFC_FAST);
 }
 
+// ---- a pass's model in segments (include/bscgpu.h) ---------------------------------------------------------------------------------
+extern "C" BSCGPU_API int bscgpu_model_segment_plan(const uint32_t* sub_dec, const uint32_t* sub_und, const int* blk_sub, int count, int64_t dcap,
+                                                    int64_t target, int* seg_of)
+{
+    if (count < 0 || dcap <= 0 || (count > 0 && (!sub_dec || !sub_und || !blk_sub || !seg_of))) return LIBBSC_BAD_PARAMETER;
+    if (count > 0 && blk_sub[0] < 0) return LIBBSC_BAD_PARAMETER;
+    for (int b = 0; b < count; ++b) if (blk_sub[b + 1] < blk_sub[b]) return LIBBSC_BAD_PARAMETER;
+    const int64_t limit = target > 0 && target < dcap ? target : dcap;
+    int nseg = 0;
+    bool open = false;              // a segment is being filled
+    int64_t filled = 0;
+    for (int b = 0; b < count; ++b) {
+        if (blk_sub[b + 1] == blk_sub[b]) { seg_of[b] = -1; continue; }      // empty: ends nothing
+        int64_t dec = 0; bool und = false;
+        for (int s = blk_sub[b]; s < blk_sub[b + 1]; ++s) { dec += sub_dec[s]; und = und || sub_und[s] != 0; }
+        if (und || dec > dcap) { seg_of[b] = -1; open = false; continue; }
+        if (!open || filled + dec > limit) { ++nseg; open = true; filled = 0; }
+        filled += dec;
+        seg_of[b] = nseg - 1;
+    }
+    return nseg;
+}
+
+extern "C" BSCGPU_API int bscgpu_model_segment_facts_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out,
+                                                            int coder, uint32_t* sub_dec, uint32_t* sub_und)
+{
+    if (!c || (count > 0 && (!sub_dec || !sub_und))) return LIBBSC_BAD_PARAMETER;
+    if (coder != LIBBSC_CODER_QLFC_STATIC && coder != LIBBSC_CODER_QLFC_FAST) return LIBBSC_BAD_PARAMETER;
+    const int frc = bscgpu_qlfc_front_batch_device(c, dL, sizes, count, out);
+    if (frc < 0 || out->nsub == 0) return frc;
+    return devcoder_segment_facts(c, (u32)out->m, out->nsub, coder, sub_dec, sub_und);
+}
+
+extern "C" BSCGPU_API int64_t bscgpu_pstream_batch_segments_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out,
+                                                                   int coder, int64_t target, uint16_t* ps, int64_t cap, uint32_t* poff, int* blk_state)
+{
+    if (!c || !poff || cap < 0 || (cap > 0 && !ps) || (count > 0 && !blk_state)) return LIBBSC_BAD_PARAMETER;
+    if (coder != LIBBSC_CODER_QLFC_STATIC && coder != LIBBSC_CODER_QLFC_FAST) return LIBBSC_BAD_PARAMETER;
+    const int frc = bscgpu_qlfc_front_batch_device(c, dL, sizes, count, out);
+    if (frc < 0) return frc;
+    poff[0] = 0;
+    for (int b = 0; b < count; ++b) blk_state[b] = 0;
+    if (out->nsub == 0) return 0;
+    int64_t D = 0;
+    const int rc = devcoder_pstream_segments(c, (u32)out->m, out->nsub, out->blk_sub, count, out->sub_run, coder, target, ps, cap, false, poff, blk_state, &D);
+    if (rc == LIBBSC_NOT_SUPPORTED) c->err = "device coder: an arena of the segmented model did not fit";
+    if (rc < 0) return rc;
+    return D;
+}
+
 namespace {
 // a pass's layout inside compress_batch_impl: the small arrays here, sym / rank / start and the first-run table in a pinned buffer
 struct PassLayout {
@@ -1889,6 +1939,7 @@ struct PassLayout {
     bool used = false;
     const uint16_t* ps = nullptr;      // the device model's stream of the pass (BSCGPU_OPT_BATCH_MODEL), sub-block s at poff[s]; null: host model
     std::vector<uint32_t> poff;
+    std::vector<int> blk_state;        // a pass in model segments (BSCGPU_OPT_BATCH_MODEL_SEGMENTS): != 0 where the block takes the host model; else empty
     // ... or, with BSCGPU_OPT_DEVICE_RC, the sub-blocks' coded bytes from the device's range coder: sub-block s's rc_res[s] bytes (or
     // LIBBSC_NOT_COMPRESSIBLE) at rc_bytes + rc_off[s], coded with an output budget of rc_room[s]
     const uint8_t* rc_bytes = nullptr;
@@ -1925,6 +1976,44 @@ static int64_t batch_model_min_pass(bool fast)
 {
     const char* e = getenv("BSC_BATCH_MODEL_MIN_PASS");
     return e ? (int64_t)atoll(e) : fast ? BATCH_MODEL_FAST_MIN_PASS_DEFAULT : BATCH_MODEL_MIN_PASS_DEFAULT;
+}
+
+// A pass in model segments is coded in GROUPS of blocks, queued while its model still runs: first the blocks the device leaves out
+// (their run arrays are down already), then each segment's blocks as its entries land.  One queue per pass slot; the pass's coder
+// thread drains it, one group at a time, after its predecessor's pass is coded (PassOrder, which every pass's coding moves on).
+struct PassGroups {
+    std::mutex mu;
+    std::condition_variable cv;
+    std::deque<std::vector<int>> groups;
+    bool closed = false;
+    void reset() { std::lock_guard<std::mutex> g(mu); groups.clear(); closed = false; }
+    void push(std::vector<int>&& blk) { if (blk.empty()) return; { std::lock_guard<std::mutex> g(mu); groups.push_back(std::move(blk)); } cv.notify_all(); }
+    void close() { { std::lock_guard<std::mutex> g(mu); closed = true; } cv.notify_all(); }
+    bool pop(std::vector<int>& blk)
+    {
+        std::unique_lock<std::mutex> g(mu);
+        cv.wait(g, [&] { return closed || !groups.empty(); });
+        if (groups.empty()) return false;
+        blk = std::move(groups.front()); groups.pop_front();
+        return true;
+    }
+};
+struct PassOrder {
+    std::mutex mu;
+    std::condition_variable cv;
+    int coded = 0;                 // passes of the call that are fully coded (they finish in order)
+    void finish() { { std::lock_guard<std::mutex> g(mu); ++coded; } cv.notify_all(); }
+    void wait_for(int passes) { std::unique_lock<std::mutex> g(mu); cv.wait(g, [&] { return coded >= passes; }); }
+};
+
+// Decisions per model segment (BSCGPU_OPT_BATCH_MODEL_SEGMENTS): the device model's capacity (0).  That is the outcome of the sweep
+// over the capacity / 8 .. the capacity (tools/batch_bench.py --segment-sweep): on W2 with host input no smaller value beats the
+// capacity by more than the legs' own spread ("Model segments").  BSC_BATCH_MODEL_SEGMENT in the environment overrides it.
+constexpr int64_t BATCH_MODEL_SEGMENT_DEFAULT = 0;
+static int64_t batch_model_segment()
+{
+    const char* e = getenv("BSC_BATCH_MODEL_SEGMENT");
+    return e ? (int64_t)atoll(e) : BATCH_MODEL_SEGMENT_DEFAULT;
 }
 
 // BSCGPU_OPT_DEVICE_RC for a model pass: every sub-block stream of the pass through ONE launch of the device's range coder
@@ -1999,12 +2088,18 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
     const bool fast_model = front && c->batch_model_fast != 0 && coder == LIBBSC_CODER_QLFC_FAST;
     const bool model = fast_model || (front && c->batch_model != 0 && coder == LIBBSC_CODER_QLFC_STATIC);
     const int64_t model_min_pass = batch_model_min_pass(fast_model);
+    // ... in model segments (BSCGPU_OPT_BATCH_MODEL_SEGMENTS); with the device's range coder on, a pass takes the whole-pass route
+    const bool segments = model && c->batch_model_segments != 0 && c->device_rc == 0;
+    const int64_t segment_target = segments ? batch_model_segment() : 0;
     const size_t frontN = ((size_t)c->max_n + 4096 + 4095) / 4096 * 4096;
     std::vector<PassLayout> lays(2);
     const int threads = default_coder_threads();
     std::vector<char> single((size_t)count, 0);
     for (int b = 0; b < count; ++b) single[b] = pass_of[b] < 0;
     std::thread coder_thread;                     // codes the previous pass while this one sorts
+    std::thread early_thread;                     // ... this pass's, when it started before the pass's model had finished (model segments)
+    PassGroups groups[2];                         // slot p & 1, free as hb is
+    PassOrder order;
     int rc = LIBBSC_NO_ERROR;
     std::vector<std::vector<BatchBlock>> bufs(2);
     std::vector<uint32_t> res((size_t)BATCH_MAX_BLOCKS * 16), adler((size_t)BATCH_MAX_BLOCKS);
@@ -2057,6 +2152,62 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
             if (B.sorted) { memcpy(hb + pos, B.lzbuf ? B.lzbuf : in_of(B.b), (size_t)B.lz); pos += B.lz; }
             if (B.lzbuf) { bigbuf_put(B.lzbuf); B.lzbuf = nullptr; }
         }
+        // what the coding of the pass is made of: one block; the rest of the pass's bookkeeping; the pass in groups (model segments)
+        auto code_block = [c, &blocks, &PL, hb, at, dev, &in_of, &din_of, &out_of, results, sizes, coder, features](int i) {
+            const BatchBlock& B = blocks[i];
+            if (PL.used && (B.store || B.sorted)) {
+                const bscgpu_front_layout& Y = PL.lay;
+                for (int s = Y.blk_sub[i]; s < Y.blk_sub[i + 1]; ++s)
+                    qlfc_front_first_seen(PL.first_run + 256 * (size_t)s, Y.first_seen + 256 * (size_t)s, &Y.nsym[s]);
+                if (B.store) {                  // <= 28 bytes that rode along (L = T): its bytes are its runs
+                    unsigned char tmp[LIBBSC_HEADER_SIZE + 1];
+                    RunView V[8];
+                    front_views(&Y, i, V);
+                    if (sizes[B.b] > 0) expand_runs(V[0], 0, tmp);
+                    results[B.b] = bsc_store(tmp, out_of(B.b), sizes[B.b], features);
+                } else {
+                    const PassCoded coded{PL.rc_bytes, PL.rc_off.data(), PL.rc_res.data(), PL.rc_room.data()};
+                    results[B.b] = code_sorted_block(c, dev ? nullptr : in_of(B.b), dev ? din_of(B.b) : nullptr, out_of(B.b), sizes[B.b],
+                                                     B, nullptr, coder, features, &Y, i, (!PL.blk_state.empty() && PL.blk_state[i]) ? nullptr : PL.ps, PL.poff.data(),
+                                                     PL.rc_bytes ? &coded : nullptr);
+                }
+                return;
+            }
+            if (B.store) results[B.b] = bsc_store(hb + at[i], out_of(B.b), sizes[B.b], features);
+            else if (B.sorted) results[B.b] = code_sorted_block(c, dev ? nullptr : in_of(B.b), dev ? din_of(B.b) : nullptr, out_of(B.b), sizes[B.b],
+                                                                B, hb + at[i], coder, features);
+        };
+        bool finished = false;
+        auto finish_blocks = [&] {              // the sort's results into the blocks: before the first of them is coded
+            if (finished) return;
+            finished = true;
+            for (int i = 0; i < e - b; ++i) {
+                BatchBlock& B = blocks[i];
+                if (B.single) single[B.b] = 1;
+                if (dev) B.adler = adler[i];
+                if (!B.sorted) continue;
+                if (st) { B.index = stidx[i]; B.num_indexes = 0; continue; }
+                const uint32_t* I = res.data() + 16 * (size_t)i;
+                B.index = (int)I[0];
+                B.num_indexes = (B.lz - 1) / aux_rate(B.lz);
+                for (int t = 0; t < B.num_indexes; ++t) B.indexes[t] = (int)I[t + 1] - 1;
+            }
+        };
+        PassGroups& PG = groups[p & 1];
+        PG.reset();
+        // one coding group at a time per call: the previous pass's coding first, then this pass's groups as they are queued
+        auto code_groups = [code_block, &PG, &order, p, threads] {
+            order.wait_for(p);
+            std::vector<int> g;
+            while (PG.pop(g)) run_bounded((int)g.size(), threads, [&](int k) { code_block(g[k]); });
+            order.finish();
+        };
+        bool grouped = false;
+        auto start_groups = [&] {
+            grouped = true;
+            try { early_thread = std::thread(code_groups); }
+            catch (const std::system_error&) {}           // no thread to be had: the groups are coded here, after the model
+        };
         if (pos > 0) {
             const u8* src = dev ? din_of(b) : c->dL;
             if (!dev && hipMemcpyAsync(c->dL, hb, (size_t)pos, hipMemcpyHostToDevice, c->stream) != hipSuccess) { rc = LIBBSC_GPU_ERROR; break; }
@@ -2070,7 +2221,48 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
                 rc = qlfc_front_batch(c, c->dL, PL.sizes.data(), e - b, &PL.lay, c->front_host[p & 1] + 6 * frontN);
                 if (rc < 0) break;
                 PL.used = true; ++c->cnt_front_passes;
-                PL.ps = nullptr; PL.rc_bytes = nullptr;
+                PL.ps = nullptr; PL.rc_bytes = nullptr; PL.blk_state.clear();
+                if (segments && PL.lay.nsub > 0 && pos >= model_min_pass && ctx_ensure_model_host(c) == LIBBSC_NO_ERROR) {
+                    // the same route segment by segment: the streams of the kept blocks land back to back, a block the device
+                    // leaves out (or whose segment no longer fits the landing buffer) is coded from its run arrays.  Coding starts
+                    // with the plan: the pass's thread takes groups of blocks as they settle (PassGroups)
+                    PL.poff.resize((size_t)PL.lay.nsub + 1);
+                    PL.blk_state.assign((size_t)(e - b), 0);
+                    PL.ps = c->model_host[p & 1];
+                    finish_blocks();
+                    struct Feed {
+                        PassGroups* G; const std::vector<BatchBlock>* blocks; const int* blk_sub; const int* state; std::vector<char> queued;
+                        void take(int b0, int b1, bool planned)
+                        {
+                            std::vector<int> g;
+                            for (int i = b0; i < b1; ++i) {
+                                const BatchBlock& B = (*blocks)[i];
+                                // the first group: what the device's model leaves out, or never sees as a segment's member
+                                const bool member = B.sorted && blk_sub[i + 1] > blk_sub[i];
+                                if (queued[i] || (planned && member && state[i] == 0)) continue;
+                                queued[i] = 1; g.push_back(i);
+                            }
+                            G->push(std::move(g));
+                        }
+                    } feed{&PG, &blocks, PL.lay.blk_sub, PL.blk_state.data(), std::vector<char>((size_t)(e - b), 0)};
+                    DcSegNote note;
+                    note.user = &feed;
+                    note.planned = [](void* u) { Feed* f = static_cast<Feed*>(u); f->take(0, (int)f->blocks->size(), true); };
+                    note.settled = [](void* u, int b0, int b1) { static_cast<Feed*>(u)->take(b0, b1, false); };
+                    start_groups();
+                    int64_t D = 0;
+                    const int mrc = devcoder_pstream_segments(c, (u32)PL.lay.m, PL.lay.nsub, PL.lay.blk_sub, e - b, PL.lay.sub_run, coder, segment_target,
+                                                              c->model_host[p & 1], (int64_t)c->model_host_entries, true, PL.poff.data(), PL.blk_state.data(), &D,
+                                                              &note);
+                    if (mrc < 0 && mrc != LIBBSC_NOT_SUPPORTED) { PG.close(); rc = mrc; break; }
+                    // (an arena did not fit: what is not queued yet takes the host model)
+                    if (mrc < 0) for (int i = 0; i < e - b; ++i) if (!feed.queued[i]) PL.blk_state[i] = BSCGPU_DC_FAIL_CAP;
+                    bool kept = false;
+                    for (int i = 0; i < e - b && mrc >= 0; ++i) kept = kept || (PL.lay.blk_sub[i + 1] > PL.lay.blk_sub[i] && PL.blk_state[i] == 0);
+                    ++(kept ? (fast_model ? c->cnt_model_fast_passes : c->cnt_model_passes) : (fast_model ? c->cnt_model_fast_declined : c->cnt_model_declined));
+                    feed.take(0, e - b, false);         // whatever is left
+                    PG.close();
+                } else
                 if (model && PL.lay.nsub > 0 && pos >= model_min_pass && ctx_ensure_model_host(c) == LIBBSC_NO_ERROR) {
                     // the model behind the front end, on the same stream, before the next pass's sort; the run arrays came down all the
                     // same: they serve a declined pass, a sub-block stored raw and the <= 28-byte blocks that rode along
@@ -2099,41 +2291,15 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
                 ++c->cnt_l_passes;
             }
         }
-        for (int i = 0; i < e - b; ++i) {
-            BatchBlock& B = blocks[i];
-            if (B.single) single[B.b] = 1;
-            if (dev) B.adler = adler[i];
-            if (!B.sorted) continue;
-            if (st) { B.index = stidx[i]; B.num_indexes = 0; continue; }
-            const uint32_t* I = res.data() + 16 * (size_t)i;
-            B.index = (int)I[0];
-            B.num_indexes = (B.lz - 1) / aux_rate(B.lz);
-            for (int t = 0; t < B.num_indexes; ++t) B.indexes[t] = (int)I[t + 1] - 1;
-        }
+        finish_blocks();
         if (coder_thread.joinable()) coder_thread.join();
-        auto code_pass = [c, &blocks, &PL, hb, at, dev, &in_of, &din_of, &out_of, results, sizes, coder, features, threads] {
-            const PassCoded coded{PL.rc_bytes, PL.rc_off.data(), PL.rc_res.data(), PL.rc_room.data()};
-            run_bounded((int)blocks.size(), threads, [&](int i) {
-                const BatchBlock& B = blocks[i];
-                if (PL.used && (B.store || B.sorted)) {
-                    const bscgpu_front_layout& Y = PL.lay;
-                    for (int s = Y.blk_sub[i]; s < Y.blk_sub[i + 1]; ++s)
-                        qlfc_front_first_seen(PL.first_run + 256 * (size_t)s, Y.first_seen + 256 * (size_t)s, &Y.nsym[s]);
-                    if (B.store) {                  // <= 28 bytes that rode along (L = T): its bytes are its runs
-                        unsigned char tmp[LIBBSC_HEADER_SIZE + 1];
-                        RunView V[8];
-                        front_views(&Y, i, V);
-                        if (sizes[B.b] > 0) expand_runs(V[0], 0, tmp);
-                        results[B.b] = bsc_store(tmp, out_of(B.b), sizes[B.b], features);
-                    } else results[B.b] = code_sorted_block(c, dev ? nullptr : in_of(B.b), dev ? din_of(B.b) : nullptr, out_of(B.b), sizes[B.b],
-                                                            B, nullptr, coder, features, &Y, i, PL.ps, PL.poff.data(), PL.rc_bytes ? &coded : nullptr);
-                    return;
-                }
-                if (B.store) results[B.b] = bsc_store(hb + at[i], out_of(B.b), sizes[B.b], features);
-                else if (B.sorted) results[B.b] = code_sorted_block(c, dev ? nullptr : in_of(B.b), dev ? din_of(B.b) : nullptr, out_of(B.b), sizes[B.b],
-                                                                    B, hb + at[i], coder, features);
-            });
-        };
+        if (grouped) {                                    // its coding is under way (or waits here, where no thread was to be had)
+            if (early_thread.joinable()) coder_thread = std::move(early_thread);
+            else { code_groups(); }
+            b = e; ++p;
+            continue;
+        }
+        auto code_pass = [code_block, &order, n = (int)blocks.size(), threads] { run_bounded(n, threads, code_block); order.finish(); };
         try { coder_thread = std::thread(code_pass); }
         catch (const std::system_error&) { code_pass(); }                          // no thread to be had: code the pass here
         b = e; ++p;
@@ -2169,7 +2335,9 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
         for (auto& ft : inflight) results[ft.first] = bscgpu_pipe_wait(pipe, ft.second);
         bscgpu_pipe_destroy(pipe);
     }
+    groups[0].close(); groups[1].close();         // (a pass that ended in an error: its thread codes what it was given and ends)
     if (coder_thread.joinable()) coder_thread.join();
+    if (early_thread.joinable()) early_thread.join();
     return rc;
 }
 

@@ -298,6 +298,32 @@ class GpuContext:
             raise GpuError(-2, f"{D} decisions exceed the buffer of {cap}")
         return fb, out[:D], poff[:fb.nsub + 1]
 
+    def model_segment_facts(self, dL, sizes, coder=1):
+        """bscgpu_model_segment_facts_device: front end of a pass and what the segment plan is made of -> (FrontBatch, sub_dec
+        np.uint32[nsub]: decisions of every sub-block for `coder`, sub_und np.uint32[nsub]: its undecided avg_rank flags)"""
+        fb = FrontBatch(sizes)
+        dec, und = np.zeros(2 * fb.count + 2, np.uint32), np.zeros(2 * fb.count + 2, np.uint32)
+        self._check(self.L.bscgpu_model_segment_facts_device(self.h, _dptr(dL), N.np_ptr(fb.sizes), fb.count, C.byref(fb.lay), int(coder),
+                                                             N.np_ptr(dec), N.np_ptr(und)))
+        return fb, dec[:fb.nsub], und[:fb.nsub]
+
+    def pstream_batch_segments(self, dL, sizes, coder=1, target=0, cap=None):
+        """bscgpu_pstream_batch_segments_device: front end and the model of `coder` (1: -e1, 3: -e0) of a pass in model segments of at
+        most `target` decisions (0: the arena's capacity) -> (FrontBatch, entries np.uint16[D] of the kept sub-blocks back to back,
+        poff np.uint32[nsub + 1], blk_state np.int32[count]: 0 or the DC_FAIL_* mask that leaves the block to the host model)"""
+        fb = FrontBatch(sizes)
+        if cap is None:
+            cap = 16 * int(fb.sizes.sum()) + 4096                  # (a pass may hold more decisions than one segment's capacity)
+        out = np.empty(max(cap, 1), np.uint16)
+        poff = np.zeros(2 * fb.count + 2, np.uint32)
+        state = np.zeros(max(fb.count, 1), np.int32)
+        D = int(self.L.bscgpu_pstream_batch_segments_device(self.h, _dptr(dL), N.np_ptr(fb.sizes), fb.count, C.byref(fb.lay), int(coder), int(target),
+                                                            N.np_ptr(out), cap, N.np_ptr(poff), N.np_ptr(state)))
+        self._check(D)
+        if D > cap:
+            raise GpuError(-2, f"{D} decisions exceed the buffer of {cap}")
+        return fb, out[:D], poff[:fb.nsub + 1], state[:fb.count]
+
     # ---- batched decompression (one inverse-BWT pass for many blocks, include/bscgpu.h) -------
     def unbwt_batch(self, dL, sizes, primary, dT=None):
         """inverse BWT of every block of a batch laid out back to back in the uint8 device tensor dL (primary: 1-based indexes) ->
@@ -360,6 +386,8 @@ class GpuContext:
     OPT_BATCH_MODEL, CNT_BATCH_MODEL_PASSES, CNT_BATCH_MODEL_DECLINED = 14, 15, 16    # the static coder's model of a compress-batch pass on the GPU
     OPT_BATCH_MODEL_FAST, CNT_BATCH_FAST_PASSES, CNT_BATCH_FAST_DECLINED = 17, 18, 19    # ... the fast coder's (-e0), an option of its own
     OPT_BWT_FOLD, CNT_BWT_FOLDED = 20, 21              # key packing sorts the first-sort key's leftover low bits (default 1) and how many sorts took that route
+    # a model pass in segments (default 0), segments kept, halves run again, blocks that ended on the host model; the model's capacity in decisions
+    OPT_BATCH_MODEL_SEGMENTS, CNT_BATCH_SEGMENTS, CNT_BATCH_SEG_RERUNS, CNT_BATCH_SEG_HOST_BLOCKS, CNT_DC_DCAP = 22, 23, 24, 25, 26
     CNT_DC_REPLAYS, CNT_DC_LAST_FAIL, CNT_DC_AVG_UNDECIDED, CNT_DC_HIST_EXTENDED = 5, 6, 7, 8      # the last device-model block (get only)
     DC_FAIL_AVG, DC_FAIL_HIST, DC_FAIL_CAP, DC_FAIL_REPLAY = 2, 4, 8, 16                          # BSCGPU_DC_FAIL_*
 
@@ -568,6 +596,23 @@ def st_batch_plan(sizes, k, cap=64 << 20):
     pass_of = np.full(max(sz.size, 1), -2, np.int32)
     n = N.lib().bscgpu_st_batch_plan(N.np_ptr(sz), sz.size, int(k), int(cap), N.np_ptr(pass_of))
     return int(n), [int(x) for x in pass_of[:sz.size]]
+
+
+def model_segment_plan(sub_dec, sub_und, blk_sub, dcap, target=0):
+    """bscgpu_model_segment_plan: the model segment of every block of a pass, -1 for a block left out -> (segments, list)"""
+    dec = np.ascontiguousarray(np.asarray(sub_dec, dtype=np.uint32))
+    und = np.ascontiguousarray(np.asarray(sub_und, dtype=np.uint32))
+    bs = np.ascontiguousarray(np.asarray(blk_sub, dtype=np.int32))
+    count = bs.size - 1
+    assert count >= 0 and dec.size == und.size and (count == 0 or dec.size >= int(bs[-1]))
+    seg_of = np.full(max(count, 1), -2, np.int32)
+    if dec.size == 0:                                           # (blocks without a sub-block: the arrays are never read)
+        dec = und = np.zeros(1, np.uint32)
+    n = int(N.lib().bscgpu_model_segment_plan(N.np_ptr(dec), N.np_ptr(und), N.np_ptr(bs), count,
+                                              int(dcap), int(target), N.np_ptr(seg_of)))
+    if n < 0:
+        raise GpuError(n, "bscgpu_model_segment_plan")
+    return n, [int(x) for x in seg_of[:count]]
 
 
 def unbwt_batch_plan(sizes, cap=64 << 20):

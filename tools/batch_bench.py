@@ -50,6 +50,13 @@ the model route wins on (run it with BSC_BATCH_MODEL_MIN_PASS=0 in the environme
 With --coder 3 all three drive the fast coder's route instead (BSCGPU_OPT_BATCH_MODEL_FAST, -e0, bscgpu_fast_pstream_batch_device; the
 stage-alone leg adds the pass's decisions per byte from the CPU stand-in); raw output under profiles/batch_fast/.
     python tools/batch_bench.py --model [--model-only | --model-sweep] [--reps 3] [--workloads W1,W2,W3]
+
+--segments (with --model, either coder): the whole-call legs become model off / model on / model + BSCGPU_OPT_BATCH_MODEL_SEGMENTS,
+host and HBM input, interleaved, with the segment counters of every leg; --model-only runs the segmented stage
+(bscgpu_pstream_batch_segments_device) instead of the whole-pass stage, the facts kernels as a class of their own (dc_facts) and the
+copy-out included in the wall time.  --segment-sweep: model + segments on W1 and W2, host input, with BSC_BATCH_MODEL_SEGMENT set to
+the capacity / 8, / 4, / 2 and the capacity, interleaved with model on and off.  Raw output belongs under profiles/batch_segments/.
+    python tools/batch_bench.py --model --segments [--model-only | --segment-sweep] [--coder 3] [--reps 3] [--workloads W1,W2,W3]
 """
 import argparse
 import ctypes as C
@@ -358,9 +365,12 @@ def model_main(args):
     CNT_PASSES = ctx.CNT_BATCH_FAST_PASSES if fast else ctx.CNT_BATCH_MODEL_PASSES
     CNT_DECLINED = ctx.CNT_BATCH_FAST_DECLINED if fast else ctx.CNT_BATCH_MODEL_DECLINED
     stage = ctx.fast_pstream_batch if fast else ctx.static_pstream_batch
-    pctx = [GpuContext(0, max_n=(1 << 20) + 4096) for _ in range(0 if (args.model_only or args.model_sweep) else args.contexts)]
+    if args.segments:                                             # the segmented stage: (layout, entries, poff) as the whole-pass stage returns them
+        stage = lambda dL, psz: ctx.pstream_batch_segments(dL, psz, coder, 0)[:3]
+    SEG_KEYS = (ctx.CNT_BATCH_SEGMENTS, ctx.CNT_BATCH_SEG_RERUNS, ctx.CNT_BATCH_SEG_HOST_BLOCKS)
+    pctx = [GpuContext(0, max_n=(1 << 20) + 4096) for _ in range(0 if (args.model_only or args.model_sweep or args.segment_sweep) else args.contexts)]
     pipes = [c.pipe(args.depth) for c in pctx]
-    CLASSES = {"contexts": ("dc_ctx",), "sorts": ("radix_scatter", "radix_hist", "radix_scan", "radix_hist_all", "radix_aux"),
+    CLASSES = {"facts": ("dc_facts",), "contexts": ("dc_ctx",), "sorts": ("radix_scatter", "radix_hist", "radix_scan", "radix_hist_all", "radix_aux"),
                "partition": ("dc_part",), "evaluation": ("dc_eval",), "p_stream": ("dc_pstream",), "front_end": ("seg", "misc", "gather")}
 
     def digest(out):
@@ -397,6 +407,38 @@ def model_main(args):
                                 kept_n = ctx.option_get(CNT_PASSES) - p0
                     print(json.dumps({"workload": name, "leg": "model_sweep", "coder": coder, "pass_bytes": total, "blocks": len(part), "model_passes_per_call": kept_n,
                                       "on_ms": t[1], "off_ms": t[0], "on_median_ms": float(np.median(t[1])), "off_median_ms": float(np.median(t[0]))}), flush=True)
+                continue
+            if args.segment_sweep:
+                # decisions per segment: the capacity / 8, / 4, / 2 and the capacity, beside model on (whole passes) and off
+                dcap = ctx.option_get(ctx.CNT_DC_DCAP)
+                legs = {"off": (0, 0, None), "on": (1, 0, None)}
+                legs.update({f"segments_{dcap // k}": (1, 1, dcap // k) for k in (8, 4, 2, 1)})
+                for how in legs.values():                          # warm-up: arenas, pinned buffers
+                    ctx.option_set(OPT, how[0]); ctx.option_set(ctx.OPT_BATCH_MODEL_SEGMENTS, how[1])
+                    ctx.compress_batch(blocks[:40], 1, coder)
+                t = {k: [] for k in legs}
+                cnt = {k: None for k in legs}
+                ref = None
+                for _ in range(args.reps):
+                    for leg, how in legs.items():
+                        ctx.option_set(OPT, how[0]); ctx.option_set(ctx.OPT_BATCH_MODEL_SEGMENTS, how[1])
+                        if how[2] is None:
+                            os.environ.pop("BSC_BATCH_MODEL_SEGMENT", None)
+                        else:
+                            os.environ["BSC_BATCH_MODEL_SEGMENT"] = str(how[2])
+                        c0 = [ctx.option_get(k) for k in SEG_KEYS + (CNT_PASSES, CNT_DECLINED)]
+                        out, wall, _ = timed(lambda: ctx.compress_batch(blocks, 1, coder))
+                        cnt[leg] = [ctx.option_get(k) - a for k, a in zip(SEG_KEYS + (CNT_PASSES, CNT_DECLINED), c0)]
+                        t[leg].append(round(wall * 1e3, 1))
+                        ref = ref or digest(out)
+                        assert digest(out) == ref, leg
+                os.environ.pop("BSC_BATCH_MODEL_SEGMENT", None)
+                ctx.option_set(ctx.OPT_BATCH_MODEL_SEGMENTS, 0)
+                for leg in legs:
+                    w = np.array(t[leg])
+                    print(json.dumps({"workload": name, "leg": "segment_sweep_" + leg, "coder": coder, "MB": round(mb, 2), "ms": t[leg],
+                                      "median_MB_s": round(mb / float(np.median(w)) * 1e3, 1), "MB_s_min_max": [round(mb / float(w.max()) * 1e3, 1), round(mb / float(w.min()) * 1e3, 1)],
+                                      "segments_reruns_host_blocks_passes_declined": cnt[leg], "same_output_in_every_leg": True}), flush=True)
                 continue
             if args.model_only:
                 _, pass_of = batch_plan(sizes, 1, ctx.max_n)
@@ -441,6 +483,10 @@ def model_main(args):
                 ctx.compress_batch(blocks[:40], 1, coder)
             legs = {"batch_on": (1, False, 0), "batch_off": (0, False, 0), "batch_on_device_rc": (1, False, 1),
                     "batch_device_on": (1, True, 0), "batch_device_off": (0, True, 0), "batch_device_on_device_rc": (1, True, 1), "pipe": None}
+            if args.segments:                                      # (option, HBM input, device RC, segments)
+                legs = {"batch_off": (0, False, 0, 0), "batch_on": (1, False, 0, 0), "batch_segments": (1, False, 0, 1),
+                        "batch_device_off": (0, True, 0, 0), "batch_device_on": (1, True, 0, 0), "batch_device_segments": (1, True, 0, 1), "pipe": None}
+            segs = {k: None for k in legs}
             walls = {k: [] for k in legs}
             cpus = {k: [] for k in legs}
             same = {k: True for k in legs}
@@ -453,8 +499,11 @@ def model_main(args):
                     else:
                         ctx.option_set(OPT, how[0])
                         ctx.option_set(ctx.OPT_DEVICE_RC, how[2])
+                        ctx.option_set(ctx.OPT_BATCH_MODEL_SEGMENTS, how[3] if len(how) > 3 else 0)
                         p0, d0 = ctx.option_get(CNT_PASSES), ctx.option_get(CNT_DECLINED)
+                        g0 = [ctx.option_get(k) for k in SEG_KEYS]
                         out, wall, cpu = timed((lambda: ctx.compress_batch_device(flat, sizes, 1, coder)) if how[1] else (lambda: ctx.compress_batch(blocks, 1, coder)))
+                        segs[leg] = [ctx.option_get(k) - a for k, a in zip(SEG_KEYS, g0)]
                         kept[leg] = ctx.option_get(CNT_PASSES) - p0
                         declined[leg] = ctx.option_get(CNT_DECLINED) - d0
                     walls[leg].append(wall); cpus[leg].append(cpu)
@@ -465,6 +514,7 @@ def model_main(args):
                                   "ms": [round(x * 1e3, 1) for x in w], "median_MB_s": round(mb / float(np.median(w)), 1),
                                   "MB_s_min_max": [round(mb / float(w.max()), 1), round(mb / float(w.min()), 1)],
                                   "cpu_s_per_MB": round(float(np.mean(cpus[leg])) / mb, 4), "model_passes": kept[leg], "model_declined": declined[leg],
+                                  **({"segments_reruns_host_blocks": segs[leg]} if args.segments else {}),
                                   "sha256_equals_pipe": bool(same[leg])}), flush=True)
             del dblocks
     finally:
@@ -492,8 +542,14 @@ def main():
     ap.add_argument("--model", action="store_true", help="BSCGPU_OPT_BATCH_MODEL on against off, interleaved (BWT, -e1); with --coder 3: BSCGPU_OPT_BATCH_MODEL_FAST (-e0)")
     ap.add_argument("--model-only", action="store_true", help="with --model: the model stage alone on one pass, per kernel class")
     ap.add_argument("--model-sweep", action="store_true", help="with --model: on against off on passes of 64 KiB .. 16 MiB (set BSC_BATCH_MODEL_MIN_PASS=0)")
+    ap.add_argument("--segments", action="store_true", help="implies --model: legs model off / on / on + BSCGPU_OPT_BATCH_MODEL_SEGMENTS; with --model-only: the segmented stage")
+    ap.add_argument("--segment-sweep", action="store_true", help="with --model: BSC_BATCH_MODEL_SEGMENT over the capacity / 8 .. the capacity, host input (set BSC_BATCH_MODEL_MIN_PASS=0 for one-pass workloads of the fast coder)")
     args = ap.parse_args()
-    if args.model or args.model_only or args.model_sweep:
+    if args.segment_sweep:
+        args.workloads = args.workloads or "W1,W2"
+        args.segments = True
+        return model_main(args)
+    if args.model or args.model_only or args.model_sweep or args.segments:        # (--segments is a form of --model)
         args.workloads = args.workloads or "W1,W2,W3"
         return model_main(args)
     if args.front or args.front_only:
