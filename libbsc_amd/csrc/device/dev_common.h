@@ -125,7 +125,7 @@ struct bscgpu_ctx {
     // the static coder's model of a whole pass (devcoder.hip: devcoder_pstream_batch)
     int  batch_model = 0;         // BSCGPU_OPT_BATCH_MODEL (default 0: DESIGN §2b, "The static coder's model of a pass")
     int  cnt_model_passes = 0, cnt_model_declined = 0;   // BSCGPU_CNT_BATCH_MODEL_PASSES / _DECLINED
-    // the fast coder's (devcoder.hip: devcoder_pstream_fast_batch); it shares the pinned stream buffers below
+    // the fast coder's (the same entry with coder 3); it shares the pinned stream buffers below
     int  batch_model_fast = 0;    // BSCGPU_OPT_BATCH_MODEL_FAST (default 0: DESIGN §2b, "The fast coder's model of a pass")
     int  cnt_model_fast_passes = 0, cnt_model_fast_declined = 0;   // BSCGPU_CNT_BATCH_FAST_PASSES / _DECLINED
     // model segments (devcoder.hip: devcoder_pstream_segments; DESIGN §2b, "Model segments")
@@ -268,7 +268,8 @@ int  ctx_ensure_front_host(bscgpu_ctx* c);        // both pinned run buffers of 
 int ctx_ensure_slots(bscgpu_ctx* c, int count);
 int ctx_ensure_pstream_slot(bscgpu_ctx* c, HostSlot& slot, size_t entries);     // pinned landing zone for a block's p stream
 int ctx_ensure_run_slot(bscgpu_ctx* c, HostSlot& slot);                           // pinned landing zone for a block's run arrays
-// device-side model of the static QLFC coder (devcoder.hip): probability stream of a whole block from the front end's run arrays
+// device-side model of the QLFC coders (devcoder.hip: dc_static_run / dc_fast_run): probability stream of a whole block from the front
+// end's run arrays
 int  devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* dstart, u32 m, u32 n, int nb, const u32* run_first,
                       const int* max_rank, u32* D_out, u32* poff_out, u16* dbg, int psbuf = 0, int coder = 1 /* 1 static (-e1), 3 fast (-e0) */,
                       int* packed_out = nullptr /* non-null: the caller takes the 13-bit packed stream (devcoder.hip DcP13); *packed_out = 1 if that is what was written */);
@@ -276,11 +277,9 @@ const u16* devcoder_pstream_ptr(const bscgpu_ctx* c, int psbuf = 0);
 // ... of a whole batched pass ("The static coder's model of a pass"): after qlfc_front_batch, from the run arrays and the
 // table it left in HBM -> *D_out decisions in devcoder_pstream_ptr(c, 0), sub-block s's at [poff[s], poff[s + 1]) with poff[0..nsub] at
 // devcoder_batch_poff_ptr (device).  BSC_NOT_SUPPORTED: the pass is declined (c->dc_last_fail: BSCGPU_DC_FAIL_*; 0: an arena did not
-// fit).  Synchronous.
-int  devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out);
-// ... the fast coder's (-e0) model of the pass: same inputs, same outputs with entries in the dcm::PSF_* form, same exits (only
-// FAIL_CAP and FAIL_REPLAY can be raised: this coder has no avg_rank flags and no run_hist look-back)
-int  devcoder_pstream_fast_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out);
+// fit).  Synchronous.  coder 3: the fast coder's (-e0) model of the pass — same inputs, same outputs with entries in the dcm::PSF_*
+// form, same exits (only FAIL_CAP and FAIL_REPLAY can be raised: this coder has no avg_rank flags and no run_hist look-back)
+int  devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, int coder /* 1 static (-e1), 3 fast (-e0) */, u32* D_out);
 const u32* devcoder_batch_poff_ptr(const bscgpu_ctx* c);
 // ... of a pass in model segments ("Model segments"): the same inputs plus the layout's blk_sub[count + 1] and
 // sub_run[nsub + 1] (host), coder 1 or 3, target decisions per segment (<= 0: the arena's capacity).  out[0 .. cap) (host): the kept

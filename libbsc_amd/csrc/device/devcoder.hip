@@ -29,6 +29,10 @@
 // handles exactly (an avg_rank bracket that does not decide, a run_hist bracket still open after 9216 predecessors, a chain whose
 // bracket stays open over more than 64 evaluation chunks, capacity), a flag is raised and the caller falls back to the host model;
 // nothing approximate is ever emitted.
+//
+// The host side drives the stages from ONE body per coder, a template over the form as the kernels are: dc_static_run (-e1) and
+// dc_fast_run (-e0).  devcoder_pstream (a block), devcoder_pstream_batch (a pass) and devcoder_pstream_segments (a pass cut at
+// capacity) hold what differs in front of a body: the sub-blocks' shape, the avg_rank flags, the table's max_rank, the rebased table.
 #include "dev_common.h"
 #include "dma_copy.h"
 #include <thread>
@@ -1522,7 +1526,9 @@ int devcoder_ensure(bscgpu_ctx* c)
 int64_t devcoder_arena_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)c->dc->arena_bytes : 0; }
 int64_t devcoder_batch_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)c->dc->batch_bytes : 0; }
 
-template <int SIDES, class SB>
+// One partition job: counts, scans, scatter.  SCATTER = false: counts and scans only, then the runs' offsets in the stream
+// (dc_doff_kernel) — all the fast coder needs of job 0, whose events nobody reads.
+template <int SIDES, bool SCATTER = true, class SB>
 static void dc_launch_partition(bscgpu_ctx* c, DevCoder* d, const u64* items, u32 m, const SB& S, int job, u32 ignoreX)
 {
     const DcGeom g = dc_geom(m);
@@ -1532,8 +1538,11 @@ static void dc_launch_partition(bscgpu_ctx* c, DevCoder* d, const u64* items, u3
     hipLaunchKernelGGL((dc_part_count_kernel<SIDES, SB>), dim3(grid), dim3(WG), 0, c->stream, items, g, S, d->rowbins, d->cnt, d->wdec);
     hipLaunchKernelGGL(dc_scan_rows_kernel, dim3(DC_ROWS), dim3(WG), 0, c->stream, d->cnt, g.W, d->rowtot);
     hipLaunchKernelGGL(dc_scan_misc_kernel, dim3(1), dim3(WG), 0, c->stream, d->rowtot, rowstart, d->wdec, g.W, d->wdecoff, d->meta, job, (u32)d->Dcap);
-    hipLaunchKernelGGL((dc_part_scatter_kernel<SIDES, SB>), dim3(grid), dim3(WG), 0, c->stream, items, g, S, d->meta, d->cnt, rowstart,
-                       d->wdecoff, ignoreX, d->events[job], d->pos[job], d->doff[job], d->esub[job]);
+    if constexpr (SCATTER)
+        hipLaunchKernelGGL((dc_part_scatter_kernel<SIDES, SB>), dim3(grid), dim3(WG), 0, c->stream, items, g, S, d->meta, d->cnt, rowstart,
+                           d->wdecoff, ignoreX, d->events[job], d->pos[job], d->doff[job], d->esub[job]);
+    else
+        hipLaunchKernelGGL((dc_doff_kernel<SIDES, SB>), dim3(grid), dim3(WG), 0, c->stream, items, g, S, d->meta, d->wdecoff, d->doff[job]);
     prof_end(c);
 }
 
@@ -1546,8 +1555,48 @@ static void dc_note_block(bscgpu_ctx* c, const DevCoder* d)
     c->dc_hist_ext = (int)d->hmeta[DM_HIST_EXT];
 }
 
-// All chains of a block (or of a batched pass: tab) in one set of launches: E[job] events per family job, values to d->V[job].
-static int dc_eval_static(bscgpu_ctx* c, DevCoder* d, const u32* E, bool tab)
+// One of the bodies' two syncs: meta comes down (and whatever rides with it: DcDown), the finished brackets are folded, the context
+// notes what the flags say.  BSC_NOT_SUPPORTED: a flag is raised — the block (the pass, the segment) is declined.
+struct DcDown { void* dst; const void* src; size_t bytes; };
+static int dc_meta_down(bscgpu_ctx* c, DevCoder* d, const DcDown& also)
+{
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
+    if (also.dst) HIP_TRY(c, hipMemcpyAsync(also.dst, also.src, also.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    prof_collect(c);
+    dc_note_block(c, d);
+    return d->hmeta[DM_FAIL] != 0 ? BSC_NOT_SUPPORTED : BSC_NO_ERROR;
+}
+
+// Before the stream kernel writes ps[psbuf]: the buffer's previous copy-out — an event on the copy stream, or, when it went through the
+// DMA engine directly, the signals of its pieces (two blocks ago: long landed; a piece that FAILED to land ends the call).
+static int dc_ps_wait(bscgpu_ctx* c, int psbuf)
+{
+    if (c->ps_guard[psbuf & 1]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ps_guard[psbuf & 1], 0));
+    for (int b = 0; b < 8; ++b)
+        if (c->ps_guard_sig[psbuf & 1][b] && dma_wait(c->ps_guard_sig[psbuf & 1][b]) != 0)
+            return ctx_fail(c, BSC_GPU_ERROR, "device coder: the stream buffer's previous copy-out failed", hipSuccess);
+    return BSC_NO_ERROR;
+}
+
+// Where the form enters on the host (the kernels: DcForm): the sub-blocks' offsets in the stream, from job 0's doff.  The eight go to
+// d->poff and come down with meta at the FIRST sync (hmeta[32..]: the packed stream's layout is made of them); a table's go to
+// d->poff_tab and come down at the LAST sync, where the caller asks for them (poff_host).
+static void dc_launch_poff(bscgpu_ctx* c, DevCoder* d, const DcSub& S, u32 m)
+{
+    hipLaunchKernelGGL(dc_poff_kernel, dim3(1), dim3(16), 0, c->stream, d->doff[0], S, m, d->poff);
+}
+static void dc_launch_poff(bscgpu_ctx* c, DevCoder* d, const DcSubTab& S, u32)
+{
+    hipLaunchKernelGGL(dc_poff_tab_kernel, dim3((S.nsub + 1 + WG - 1) / WG), dim3(WG), 0, c->stream, d->doff[0], S, d->poff_tab);
+}
+static DcDown dc_poff_down(DevCoder* d, const DcSub&, bool last, u32*) { return last ? DcDown{} : DcDown{d->hmeta + 32, d->poff, 16 * 4}; }
+static DcDown dc_poff_down(DevCoder* d, const DcSubTab& S, bool last, u32* poff_host) { return last ? DcDown{poff_host, d->poff_tab, ((size_t)S.nsub + 1) * 4} : DcDown{}; }
+
+// All chains of a block (or of a batched pass: tab) in one set of launches: E[job] events of family fam[job] per job, values to
+// d->V[job], counters by mp.  The fast coder's one family is job 1 alone: E = {0, E, 0, 0}, mp_fast.
+static int dc_eval(bscgpu_ctx* c, DevCoder* d, const u32 E[4], const int fam[4], const ModelParams* mp, bool tab)
 {
     DcEvalAll A;
     A.wstart[0] = 0; A.cstart[0] = 0; A.sink = d->sink;
@@ -1556,9 +1605,8 @@ static int dc_eval_static(bscgpu_ctx* c, DevCoder* d, const u32* E, bool tab)
     // (what the brackets need to meet) or as many as it takes to stay at <= 1000 wavefronts (+ <= 4 of padding) per launch.
     A.ev = eval_chunk_events((u64)E[0] + E[1] + E[2] + E[3]);
     for (int job = 0; job < 4; ++job) {
-        const int fam = job == 0 ? FAM_STATIC : job == 1 ? FAM_CHAR : FAM_STATE;
         A.job[job].events = d->events[job]; A.job[job].E = E[job]; A.job[job].rowstart = d->rowstart + (DC_ROWS + 8) * job;
-        A.job[job].fam = fam;
+        A.job[job].fam = fam[job];
         A.V[job] = d->V[job];
         const u32 nch = (E[job] + A.ev - 1) / A.ev;
         A.wstart[job + 1] = A.wstart[job] + (nch + 63) / 64;
@@ -1573,98 +1621,44 @@ static int dc_eval_static(bscgpu_ctx* c, DevCoder* d, const u32* E, bool tab)
             for (int job = 0; job < 4; ++job) { K.events[job] = d->events[job]; K.esub[job] = d->esub[job]; K.E[job] = E[job]; if (E[job] > emax) emax = E[job]; }
             hipLaunchKernelGGL(dc_mark_chains_kernel, dim3((emax + 8 * WG - 1) / (8 * WG), 4), dim3(WG), 0, c->stream, K, d->meta);
         }
-        hipLaunchKernelGGL(dc_eval_wave_kernel<false>, dim3((A.wstart[4] + DC_EVAL_WAVES - 1) / DC_EVAL_WAVES), dim3(64 * DC_EVAL_WAVES), DC_EVAL_LDS, c->stream, A, d->mp, d->meta, d->elo, d->ehi, (const u16*)nullptr, d->cnt);
-        hipLaunchKernelGGL(dc_eval_b_kernel, dim3((A.cstart[4] + WG - 1) / WG), dim3(WG), 0, c->stream, A, d->mp, d->meta, d->elo, d->ehi, d->S);
-        hipLaunchKernelGGL(dc_eval_wave_kernel<true>, dim3((A.wstart[4] + DC_EVAL_WAVES - 1) / DC_EVAL_WAVES), dim3(64 * DC_EVAL_WAVES), DC_EVAL_LDS, c->stream, A, d->mp, d->meta, (u16*)nullptr, (u16*)nullptr, d->S, d->cnt + 3 * 4096);
+        hipLaunchKernelGGL(dc_eval_wave_kernel<false>, dim3((A.wstart[4] + DC_EVAL_WAVES - 1) / DC_EVAL_WAVES), dim3(64 * DC_EVAL_WAVES), DC_EVAL_LDS, c->stream, A, mp, d->meta, d->elo, d->ehi, (const u16*)nullptr, d->cnt);
+        hipLaunchKernelGGL(dc_eval_b_kernel, dim3((A.cstart[4] + WG - 1) / WG), dim3(WG), 0, c->stream, A, mp, d->meta, d->elo, d->ehi, d->S);
+        hipLaunchKernelGGL(dc_eval_wave_kernel<true>, dim3((A.wstart[4] + DC_EVAL_WAVES - 1) / DC_EVAL_WAVES), dim3(64 * DC_EVAL_WAVES), DC_EVAL_LDS, c->stream, A, mp, d->meta, (u16*)nullptr, (u16*)nullptr, d->S, d->cnt + 3 * 4096);
     }
     prof_end(c);
     return BSC_NO_ERROR;
 }
 
-// The fast coder's one family (job 1: the char family's chains with shift updates, mp_fast), E events; tab: a batched pass.
-static int dc_eval_fast(bscgpu_ctx* c, DevCoder* d, u32 E, bool tab)
+// ---- the two coders' models, each ONE body for both forms (SB: DcSub, one block's eight sub-blocks; DcSubTab, a pass's or a
+// segment's table) -------------------------------------------------------------------------------------------------------------------
+// Both take the front end's run arrays on the device (sym / rank / start, m runs; n: the block's bytes, 0 for a table, which carries
+// its own ends) with the avg_rank flags and the sub-blocks S, and write *D_out decisions to the device p stream ps[psbuf], the
+// sub-blocks' decision offsets where dc_poff_down says.  The caller has cleared meta (the static coder: present too), and launched
+// what its form needs in front of the items; ctx_open: its contexts bracket is still open and takes the items as well (a single
+// block's flags and items are one bracket).  expect >= 0: the decisions the plan counted for these sub-blocks — the families' totals
+// must equal it.  Every guarded exit declines the whole unit (BSC_NOT_SUPPORTED, c->dc_last_fail says why).  Two syncs: the families'
+// sizes after the partition, the flags after the stream.
+//
+// The static coder (-e1), the four stages of the file header.  dbg: the debug planes; packed_out non-null: the caller can take the
+// stream at 13 bits per decision (DcP13), *packed_out says whether that is what was written.
+template <class SB>
+static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym, const u8* drank, const u32* dstart, const u8* ge32, u32 m, u32 n,
+                         bool ctx_open, int psbuf, int64_t expect, u32* poff_host, u16* dbg, int* packed_out, u32* D_out)
 {
-    DcEvalAll A;
-    A.sink = d->sink;
-    A.ev = eval_chunk_events((u64)E);
-    A.wstart[0] = 0; A.cstart[0] = 0;
-    for (int job = 0; job < 4; ++job) {
-        A.job[job].events = d->events[job]; A.job[job].E = job == 1 ? E : 0u; A.job[job].rowstart = d->rowstart + (DC_ROWS + 8) * job;
-        A.job[job].fam = FAM_CHAR;
-        A.V[job] = d->V[job];
-        const u32 nch = (A.job[job].E + A.ev - 1) / A.ev;
-        A.wstart[job + 1] = A.wstart[job] + (nch + 63) / 64;
-        A.cstart[job + 1] = A.cstart[job] + (nch + 63) / 64 * 64;
-    }
-    if (A.cstart[4] > 4 * d->nch_cap) return ctx_fail(c, BSC_GPU_ERROR, "device coder: chunk table too small", hipSuccess);
-    prof_begin(c, BSCGPU_K_DC_EVAL, (u64)E * 6, (u64)E);
-    if (A.wstart[4] > 0) {
-        hipLaunchKernelGGL(dc_mark_rows_kernel, dim3((4 * DC_ROWS + WG - 1) / WG), dim3(WG), 0, c->stream, A);
-        if (tab) {                                                        // a batched pass: chain starts from the events' full sub-block ids (job 1 alone)
-            DcMarkAll K;
-            for (int job = 0; job < 4; ++job) { K.events[job] = d->events[job]; K.esub[job] = d->esub[job]; K.E[job] = job == 1 ? E : 0u; }
-            hipLaunchKernelGGL(dc_mark_chains_kernel, dim3((E + 8 * WG - 1) / (8 * WG), 4), dim3(WG), 0, c->stream, K, d->meta);
-        }
-        hipLaunchKernelGGL(dc_eval_wave_kernel<false>, dim3((A.wstart[4] + DC_EVAL_WAVES - 1) / DC_EVAL_WAVES), dim3(64 * DC_EVAL_WAVES), DC_EVAL_LDS, c->stream, A, d->mp_fast, d->meta, d->elo, d->ehi, (const u16*)nullptr, d->cnt);
-        hipLaunchKernelGGL(dc_eval_b_kernel, dim3((A.cstart[4] + WG - 1) / WG), dim3(WG), 0, c->stream, A, d->mp_fast, d->meta, d->elo, d->ehi, d->S);
-        hipLaunchKernelGGL(dc_eval_wave_kernel<true>, dim3((A.wstart[4] + DC_EVAL_WAVES - 1) / DC_EVAL_WAVES), dim3(64 * DC_EVAL_WAVES), DC_EVAL_LDS, c->stream, A, d->mp_fast, d->meta, (u16*)nullptr, (u16*)nullptr, d->S, d->cnt + 3 * 4096);
-    }
-    prof_end(c);
-    return BSC_NO_ERROR;
-}
-
-// Probability stream of a whole block.  Inputs: the QLFC front end's run arrays on the device (sym / rank / start, m runs of
-// the n-byte sorted block), the sub-blocks' run ranges and max_rank values.  On success *D_out decisions were written to the
-// device p stream (d->ps) and poff[0..nb] (decision offsets of the sub-blocks) to hmeta[32..]; returns BSC_NOT_SUPPORTED when
-// the block has to go through the host model instead.
-// The fast coder (-e0, qlfc.cpp:1135-1336) on the same machinery: its one counter per decision is indexed by the run's symbol, i.e. its
-// chains ARE the char family's — (sub-block, decision type, symbol) — with shift updates and per-class targets (dcm::model_params_fast),
-// no escape coding and the exponent always closed below 7 bits (max_rank = 7 in the static coder's terms).  So: items, ONE radix pass
-// (symbol-major order), ONE partition job, the stream offsets of the runs, evaluation of that one job, and a p stream whose entries
-// are the counter values themselves.  No contexts, no state tables, no blend: about a third of the static coder's device work.
-static int devcoder_pstream_fast(bscgpu_ctx* c, DevCoder* d, const u8* dsym, const u8* drank, const u32* dstart, u32 m, u32 n, int nb,
-                                 const u32* run_first, u32* D_out, u32* poff_out, int psbuf);
-
-int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* dstart, u32 m, u32 n, int nb, const u32* run_first,
-                     const int* max_rank, u32* D_out, u32* poff_out, u16* dbg, int psbuf, int coder, int* packed_out)
-{
-    if (packed_out) *packed_out = 0;
-    int rc = devcoder_ensure(c);
-    if (rc < 0) return rc;
-    DevCoder* d = c->dc;
-    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = 0;
-    c->dc_last_fail = m > d->Mcap ? (int)FAIL_CAP : 0;                 // (more runs than the arena holds: capacity, as too many decisions are)
-    if (m == 0 || m > d->Mcap || nb < 1 || nb > 8) return BSC_NOT_SUPPORTED;
-    if (coder == 3) return devcoder_pstream_fast(c, d, dsym, drank, dstart, m, n, nb, run_first, D_out, poff_out, psbuf);
-    DcSub S; S.nb = (u32)nb;
-    for (int b = 0; b < 9; ++b) S.first[b] = (b <= nb) ? run_first[b] : m;
-    for (int b = 0; b < 8; ++b) S.maxr[b] = (b < nb) ? (u32)max_rank[b] : 0u;
-
-    HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
-    HIP_TRY(c, hipMemsetAsync(d->present, 0, (size_t)DC_KIND_WORDS * 4, c->stream));
     const u32 gm = (m + WG - 1) / WG;
     const u32 gm8 = (gm + 7u) / 8u * 8u;            // kernels that use dc_virtual_block()
-
-    prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
-    // avg' = (124 avg + 4 rank) >> 7 <= max(avg, rank) and rank < nsym <= 2^(max_rank + 1): with at most 32 symbols in every
-    // sub-block the average never reaches 32 and the escape coding (qlfc.cpp:960) cannot occur
-    bool may_escape = false;
-    for (int b = 0; b < nb; ++b) may_escape |= max_rank[b] > 4;
-    if (may_escape)
-        hipLaunchKernelGGL(dc_avg_kernel<DcSub>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta, (u32*)nullptr);
-    else
-        HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));
-    hipLaunchKernelGGL(dc_items_kernel<DcSub>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, d->ge32, m, n, S, d->key_ch);
+    if (!ctx_open) prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
+    hipLaunchKernelGGL(dc_items_kernel<SB>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, ge32, m, n, S, d->key_ch);
     prof_end(c);
     RadixPass top; top.shift = 56; top.bits = 8;
     int in_alt = 0;
     // one pass: the engine reads `keys` (left intact) and writes the sorted copy to the alt array
-    rc = radix_sort_passes(c, d->key_ch, d->key_ch_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_ch);
+    int rc = radix_sort_passes(c, d->key_ch, d->key_ch_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_ch);
     if (rc < 0) return rc;
     prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
-    hipLaunchKernelGGL(dc_ctx_kernel<DcSub>, dim3(gm8), dim3(WG), 0, c->stream, d->key_ch, d->key_ch_s, d->inv_ch, m, S, d->tab_rank, d->tab_run,
+    hipLaunchKernelGGL(dc_ctx_kernel<SB>, dim3(gm8), dim3(WG), 0, c->stream, d->key_ch, d->key_ch_s, d->inv_ch, m, S, d->tab_rank, d->tab_run,
                        d->key_sr, d->key_sn, d->present, d->meta);
-    hipLaunchKernelGGL(dc_setup_kernel<DcSub>, dim3(1), dim3(WG), 0, c->stream, d->present, S, d->rounds, d->meta);
+    hipLaunchKernelGGL(dc_setup_kernel<SB>, dim3(1), dim3(WG), 0, c->stream, d->present, S, d->rounds, d->meta);
     prof_end(c);
     rc = radix_sort_passes(c, d->key_sr, d->key_sr_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_sr);
     if (rc < 0) return rc;
@@ -1677,21 +1671,16 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
     dc_launch_partition<3>(c, d, d->key_ch_s, m, S, 1, 0u);
     dc_launch_partition<1>(c, d, d->key_sr_s, m, S, 2, 0u);
     dc_launch_partition<2>(c, d, d->key_sn_s, m, S, 3, 0u);
-    // (the sub-blocks' offsets in the stream are known from here on: the packed stream's layout is made of them)
-    hipLaunchKernelGGL(dc_poff_kernel, dim3(1), dim3(16), 0, c->stream, d->doff[0], S, m, d->poff);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d->hmeta + 32, d->poff, 16 * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, ctx_sync(c));
-    prof_collect(c);
-    if (d->hmeta[DM_FAIL] != 0) { dc_note_block(c, d); return BSC_NOT_SUPPORTED; }
-    u32 poff_h[9];
-    for (int b = 0; b <= nb; ++b) poff_h[b] = d->hmeta[32 + b];
+    dc_launch_poff(c, d, S, m);                     // (the sub-blocks' offsets in the stream are known from here on)
+    rc = dc_meta_down(c, d, dc_poff_down(d, S, false, poff_host));
+    if (rc < 0) return rc;
     u32 E[4];
     for (int job = 0; job < 4; ++job) E[job] = d->hmeta[DM_D0 + job];
     const u32 Efull = E[0];                                           // decisions of the block
     if (Efull != E[1] || Efull != E[2] + E[3]) return ctx_fail(c, BSC_GPU_ERROR, "device coder: decision counts of the families differ", hipSuccess);
-    rc = dc_eval_static(c, d, E, false);
+    if (expect >= 0 && (int64_t)Efull != expect) return ctx_fail(c, BSC_GPU_ERROR, "device coder: a segment's decisions differ from the plan's count", hipSuccess);
+    const int fam[4] = {FAM_STATIC, FAM_CHAR, FAM_STATE, FAM_STATE};
+    rc = dc_eval(c, d, E, fam, d->mp, DcForm<SB>::TAB);
     if (rc < 0) return rc;
 
     DcGather G;
@@ -1700,37 +1689,39 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
     G.pos_sp = d->pos[0]; G.pos_ch = d->pos[1]; G.pos_sr = d->pos[2]; G.pos_sn = d->pos[3];
     G.V_sp = d->V[0]; G.V_ch = d->V[1]; G.V_sr = d->V[2]; G.V_sn = d->V[3];
     prof_begin(c, BSCGPU_K_DC_PSTREAM, (u64)Efull * 26, Efull);
-    if (c->ps_guard[psbuf & 1]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ps_guard[psbuf & 1], 0));     // the buffer's previous copy-out
-    for (int b = 0; b < 8; ++b) if (c->ps_guard_sig[psbuf & 1][b]) (void)dma_wait(c->ps_guard_sig[psbuf & 1][b]);   // ... when it went through the DMA engine directly (two blocks ago: long landed)
-    // 13 bits per decision (DcP13) when the caller can take it: not with the debug planes
-    bool packed = packed_out != nullptr && c->dc_p13 != 0 && dbg == nullptr;
+    rc = dc_ps_wait(c, psbuf);
+    if (rc < 0) return rc;
+    bool packed = false;
     DcP13 Q{};
-    if (packed) {
-        u32 pbase = 0;
-        for (int b = 0; b < nb; ++b) { Q.pad[b] = pbase - poff_h[b]; pbase += (poff_h[b + 1] - poff_h[b] + 63u) / 64u * 64u; }
-        Q.out = reinterpret_cast<u8*>(d->ps[psbuf & 1]); Q.frag = d->frag;
-        if ((u64)pbase / 8u * 13u > 2ull * (u64)(d->Dcap + 64)) packed = false;        // (cannot happen: 13 / 8 of D + 8 x 64 decisions of padding against 2 D)
+    if constexpr (!DcForm<SB>::TAB) {               // (the packed stream is laid out by eight sub-blocks: dc_pstream_kernel's static_assert)
+        // 13 bits per decision (DcP13) when the caller can take it: not with the debug planes
+        packed = packed_out != nullptr && c->dc_p13 != 0 && dbg == nullptr;
+        if (packed) {
+            const u32* poff_h = d->hmeta + 32;
+            u32 pbase = 0;
+            for (u32 b = 0; b < S.nb; ++b) { Q.pad[b] = pbase - poff_h[b]; pbase += (poff_h[b + 1] - poff_h[b] + 63u) / 64u * 64u; }
+            Q.out = reinterpret_cast<u8*>(d->ps[psbuf & 1]); Q.frag = d->frag;
+            if ((u64)pbase / 8u * 13u > 2ull * (u64)(d->Dcap + 64)) packed = false;        // (cannot happen: 13 / 8 of D + 8 x 64 decisions of padding against 2 D)
+        }
+        if (packed) {
+            hipLaunchKernelGGL((dc_pstream_kernel<false, true, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
+            hipLaunchKernelGGL(dc_p13_join_kernel, dim3((gm8 * WAVES + WG - 1) / WG), dim3(WG), 0, c->stream, d->frag, gm8 * WAVES, Q.out, d->meta);
+        }
     }
-    if (packed) {
-        hipLaunchKernelGGL((dc_pstream_kernel<false, true, DcSub>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
-        hipLaunchKernelGGL(dc_p13_join_kernel, dim3((gm8 * WAVES + WG - 1) / WG), dim3(WG), 0, c->stream, d->frag, gm8 * WAVES, Q.out, d->meta);
-    } else hipLaunchKernelGGL((dc_pstream_kernel<false, false, DcSub>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
+    if (!packed) hipLaunchKernelGGL((dc_pstream_kernel<false, false, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
     prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, ctx_sync(c));
-    if (d->hmeta[DM_FAIL] != 0) { dc_note_block(c, d); return BSC_NOT_SUPPORTED; }
+    rc = dc_meta_down(c, d, dc_poff_down(d, S, true, poff_host));
+    if (rc < 0) return rc;
     if (packed && d->hmeta[DM_P13_OVER] != 0) {
         // 64 consecutive runs with more decisions than a wavefront's staging buffer holds (runs of thousands): this block's stream in the 2-byte form
         packed = false;
         prof_begin(c, BSCGPU_K_DC_PSTREAM, (u64)Efull * 26, Efull);
-        hipLaunchKernelGGL((dc_pstream_kernel<false, false, DcSub>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
+        hipLaunchKernelGGL((dc_pstream_kernel<false, false, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
         prof_end(c);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, ctx_sync(c));
     }
     if (packed_out) *packed_out = packed ? 1 : 0;
-    dc_note_block(c, d);
 #if DC_EVAL_TIMING
     {
         std::vector<u32> h(6 * 4096);
@@ -1744,8 +1735,95 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
         }
     }
 #endif
-    if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder] decisions %u, types %u, rounds %u, chunks replayed %u\n", Efull, d->hmeta[DM_NTYPES], d->hmeta[DM_NROUNDS], d->hmeta[DM_REPLAYS]);
+    if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder] runs %u, decisions %u, types %u, rounds %u, chunks replayed %u\n", m, Efull, d->hmeta[DM_NTYPES], d->hmeta[DM_NROUNDS], d->hmeta[DM_REPLAYS]);
     *D_out = Efull;
+    return BSC_NO_ERROR;
+}
+
+// The fast coder (-e0, qlfc.cpp:1135-1336) on the same machinery: its one counter per decision is indexed by the run's symbol, i.e. its
+// chains ARE the char family's — (sub-block, decision type, symbol) — with shift updates and per-class targets (dcm::model_params_fast),
+// no escape coding and the exponent always closed below 7 bits (max_rank = 7 in the static coder's terms).  So: items, ONE radix pass
+// (symbol-major order), the stream offsets of the runs (job 0: counts and scans only), ONE partition job (job 1; for a table its
+// scatter writes every event's full sub-block id to esub[1], which dc_mark_chains_kernel folds into the chain-start mark), evaluation
+// of that one job with mp_fast, and a p stream whose entries are the counter values themselves (dcm::PSF_*).  No contexts, no state
+// tables, no blend: about a third of the static coder's device work.  No avg_rank flags, no run_hist look-back: FAIL_CAP and
+// FAIL_REPLAY are the only flags that can be raised.  The caller has cleared ge32 as well.
+template <class SB>
+static int dc_fast_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym, const u8* drank, const u32* dstart, const u8* ge32, u32 m, u32 n,
+                       bool ctx_open, int psbuf, int64_t expect, u32* poff_host, u32* D_out)
+{
+    const u32 gm = (m + WG - 1) / WG;
+    const u32 gm8 = (gm + 7u) / 8u * 8u;            // kernels that use dc_virtual_block()
+    if (!ctx_open) prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 14, m);
+    hipLaunchKernelGGL(dc_items_kernel<SB>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, ge32, m, n, S, d->key_ch);
+    prof_end(c);
+    RadixPass top; top.shift = 56; top.bits = 8;
+    int in_alt = 0;
+    int rc = radix_sort_passes(c, d->key_ch, d->key_ch_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_ch);
+    if (rc < 0) return rc;
+    dc_launch_partition<3, false>(c, d, d->key_ch, m, S, 0, 0u);
+    dc_launch_partition<3>(c, d, d->key_ch_s, m, S, 1, 0u);
+    dc_launch_poff(c, d, S, m);
+    rc = dc_meta_down(c, d, dc_poff_down(d, S, false, poff_host));
+    if (rc < 0) return rc;
+    const u32 E[4] = {0u, d->hmeta[DM_D0 + 1], 0u, 0u};
+    if (d->hmeta[DM_D0 + 0] != E[1]) return ctx_fail(c, BSC_GPU_ERROR, "device coder (fast): decision counts of stream and chain order differ", hipSuccess);
+    if (expect >= 0 && (int64_t)E[1] != expect) return ctx_fail(c, BSC_GPU_ERROR, "device coder (fast): a segment's decisions differ from the plan's count", hipSuccess);
+    const int fam[4] = {FAM_CHAR, FAM_CHAR, FAM_CHAR, FAM_CHAR};
+    rc = dc_eval(c, d, E, fam, d->mp_fast, DcForm<SB>::TAB);
+    if (rc < 0) return rc;
+
+    DcGather G;                                     // (everything is job 1's: the stream kernel reads one value per decision)
+    G.key_ch = d->key_ch; G.m = m; G.inv_ch = d->inv_ch; G.inv_sr = d->inv_ch; G.inv_sn = d->inv_ch;
+    G.doff_sp = d->doff[0]; G.doff_ch = d->doff[1]; G.doff_sr = d->doff[1]; G.doff_sn = d->doff[1];
+    G.pos_sp = d->pos[1]; G.pos_ch = d->pos[1]; G.pos_sr = d->pos[1]; G.pos_sn = d->pos[1];
+    G.V_sp = d->V[1]; G.V_ch = d->V[1]; G.V_sr = d->V[1]; G.V_sn = d->V[1];
+    prof_begin(c, BSCGPU_K_DC_PSTREAM, (u64)E[1] * 10, E[1]);
+    rc = dc_ps_wait(c, psbuf);
+    if (rc < 0) return rc;
+    hipLaunchKernelGGL((dc_pstream_kernel<true, false, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp_fast, d->meta, d->ps[psbuf & 1], (u16*)nullptr, E[1], DcP13{});
+    prof_end(c);
+    rc = dc_meta_down(c, d, dc_poff_down(d, S, true, poff_host));
+    if (rc < 0) return rc;
+    if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder fast] runs %u, decisions %u, chunks replayed %u\n", m, E[1], d->hmeta[DM_REPLAYS]);
+    *D_out = E[1];
+    return BSC_NO_ERROR;
+}
+
+// Probability stream of a whole block.  Inputs: the QLFC front end's run arrays on the device (sym / rank / start, m runs of
+// the n-byte sorted block), the sub-blocks' run ranges and max_rank values; coder 1: dc_static_run, 3: dc_fast_run.  On success
+// *D_out decisions were written to the device p stream (d->ps) and poff[0..nb] (decision offsets of the sub-blocks) to hmeta[32..];
+// returns BSC_NOT_SUPPORTED when the block has to go through the host model instead.
+int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* dstart, u32 m, u32 n, int nb, const u32* run_first,
+                     const int* max_rank, u32* D_out, u32* poff_out, u16* dbg, int psbuf, int coder, int* packed_out)
+{
+    if (packed_out) *packed_out = 0;
+    int rc = devcoder_ensure(c);
+    if (rc < 0) return rc;
+    DevCoder* d = c->dc;
+    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = 0;
+    c->dc_last_fail = m > d->Mcap ? (int)FAIL_CAP : 0;                 // (more runs than the arena holds: capacity, as too many decisions are)
+    if (m == 0 || m > d->Mcap || nb < 1 || nb > 8) return BSC_NOT_SUPPORTED;
+    const bool fast = coder == 3;
+    DcSub S; S.nb = (u32)nb;
+    for (int b = 0; b < 9; ++b) S.first[b] = (b <= nb) ? run_first[b] : m;
+    // (the fast coder: `if (bits < 7)` closes the exponent (qlfc.cpp:1204), whatever the alphabet)
+    for (int b = 0; b < 8; ++b) S.maxr[b] = fast ? 7u : (b < nb) ? (u32)max_rank[b] : 0u;
+
+    HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
+    if (!fast) HIP_TRY(c, hipMemsetAsync(d->present, 0, (size_t)DC_KIND_WORDS * 4, c->stream));
+    prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * (fast ? 14 : 40), m);
+    // avg' = (124 avg + 4 rank) >> 7 <= max(avg, rank) and rank < nsym <= 2^(max_rank + 1): with at most 32 symbols in every
+    // sub-block the average never reaches 32 and the escape coding (qlfc.cpp:960) cannot occur; the fast coder has none
+    bool may_escape = false;
+    for (int b = 0; b < nb && !fast; ++b) may_escape |= max_rank[b] > 4;
+    if (may_escape)
+        hipLaunchKernelGGL(dc_avg_kernel<DcSub>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta, (u32*)nullptr);
+    else
+        HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));
+    rc = fast ? dc_fast_run(c, d, S, dsym, drank, dstart, d->ge32, m, n, true, psbuf, -1, nullptr, D_out)
+              : dc_static_run(c, d, S, dsym, drank, dstart, d->ge32, m, n, true, psbuf, -1, nullptr, dbg, packed_out, D_out);
+    if (rc < 0) return rc;
     for (int b = 0; b <= nb; ++b) poff_out[b] = d->hmeta[32 + b];
     return BSC_NO_ERROR;
 }
@@ -1779,276 +1857,79 @@ static int devcoder_batch_ensure(bscgpu_ctx* c, DevCoder* d)
     return BSC_NO_ERROR;
 }
 
-// Probability stream of a whole pass: the run arrays where qlfc_front_batch leaves them (vA / vB / SA: the buffers the single path
-// reads) and its table in front_tab -> every sub-block's entries back to back in stream order in the device p stream (buffer 0),
-// poff[0..nsub] in d->poff_tab.  The same four stages, the same kernels, instantiated for the table (DcSubTab); every guarded exit
-// keeps its meaning with the PASS as the unit: a raised flag declines the whole pass (BSC_NOT_SUPPORTED, c->dc_last_fail says why).
-// Two syncs: the families' sizes after the partition, the flags after the stream.
-//
-// dc_tab_static is the part a whole pass and a model segment share: everything from the items on, over the table S and the run
-// arrays / flags the caller hands in (a segment: its rebased table, the pass's arrays offset to its first run).  The caller has
-// cleared meta and present.  expect >= 0: the decisions the plan counted for these sub-blocks — the families' totals must equal it.
-// poff_host: poff_tab[0..S.nsub] also comes down with the last sync.
-static int dc_tab_static(bscgpu_ctx* c, DevCoder* d, const DcSubTab& S, const u8* dsym, const u8* drank, const u32* dstart, const u8* ge32,
-                         u32 m, int psbuf, int64_t expect, u32* poff_host, u32* D_out)
-{
-    const int nsub = (int)S.nsub;
-    const u32 gm = (m + WG - 1) / WG;
-    const u32 gm8 = (gm + 7u) / 8u * 8u;            // kernels that use dc_virtual_block()
-    prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
-    hipLaunchKernelGGL(dc_items_kernel<DcSubTab>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, ge32, m, 0u, S, d->key_ch);
-    prof_end(c);
-    RadixPass top; top.shift = 56; top.bits = 8;
-    int in_alt = 0;
-    int rc = radix_sort_passes(c, d->key_ch, d->key_ch_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_ch);
-    if (rc < 0) return rc;
-    prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
-    hipLaunchKernelGGL(dc_ctx_kernel<DcSubTab>, dim3(gm8), dim3(WG), 0, c->stream, d->key_ch, d->key_ch_s, d->inv_ch, m, S, d->tab_rank, d->tab_run,
-                       d->key_sr, d->key_sn, d->present, d->meta);
-    hipLaunchKernelGGL(dc_setup_kernel<DcSubTab>, dim3(1), dim3(WG), 0, c->stream, d->present, S, d->rounds, d->meta);
-    prof_end(c);
-    rc = radix_sort_passes(c, d->key_sr, d->key_sr_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_sr);
-    if (rc < 0) return rc;
-    rc = radix_sort_passes(c, d->key_sn, d->key_sn_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_sn);
-    if (rc < 0) return rc;
-    dc_launch_partition<3>(c, d, d->key_ch, m, S, 0, 1u);
-    dc_launch_partition<3>(c, d, d->key_ch_s, m, S, 1, 0u);
-    dc_launch_partition<1>(c, d, d->key_sr_s, m, S, 2, 0u);
-    dc_launch_partition<2>(c, d, d->key_sn_s, m, S, 3, 0u);
-    hipLaunchKernelGGL(dc_poff_tab_kernel, dim3(((u32)nsub + 1 + WG - 1) / WG), dim3(WG), 0, c->stream, d->doff[0], S, d->poff_tab);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, ctx_sync(c));
-    prof_collect(c);
-    if (d->hmeta[DM_FAIL] != 0) { dc_note_block(c, d); return BSC_NOT_SUPPORTED; }
-    u32 E[4];
-    for (int job = 0; job < 4; ++job) E[job] = d->hmeta[DM_D0 + job];
-    const u32 Efull = E[0];
-    if (Efull != E[1] || Efull != E[2] + E[3]) return ctx_fail(c, BSC_GPU_ERROR, "device coder: decision counts of the families differ", hipSuccess);
-    if (expect >= 0 && (int64_t)Efull != expect) return ctx_fail(c, BSC_GPU_ERROR, "device coder: a segment's decisions differ from the plan's count", hipSuccess);
-    rc = dc_eval_static(c, d, E, true);
-    if (rc < 0) return rc;
-
-    DcGather G;
-    G.key_ch = d->key_ch; G.m = m; G.inv_ch = d->inv_ch; G.inv_sr = d->inv_sr; G.inv_sn = d->inv_sn;
-    G.doff_sp = d->doff[0]; G.doff_ch = d->doff[1]; G.doff_sr = d->doff[2]; G.doff_sn = d->doff[3];
-    G.pos_sp = d->pos[0]; G.pos_ch = d->pos[1]; G.pos_sr = d->pos[2]; G.pos_sn = d->pos[3];
-    G.V_sp = d->V[0]; G.V_ch = d->V[1]; G.V_sr = d->V[2]; G.V_sn = d->V[3];
-    prof_begin(c, BSCGPU_K_DC_PSTREAM, (u64)Efull * 26, Efull);
-    if (c->ps_guard[psbuf & 1]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ps_guard[psbuf & 1], 0));     // the buffer's previous copy-out (a single-path block)
-    for (int b = 0; b < 8; ++b) if (c->ps_guard_sig[psbuf & 1][b]) (void)dma_wait(c->ps_guard_sig[psbuf & 1][b]);
-    hipLaunchKernelGGL((dc_pstream_kernel<false, false, DcSubTab>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], (u16*)nullptr, Efull, DcP13{});
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
-    if (poff_host) HIP_TRY(c, hipMemcpyAsync(poff_host, d->poff_tab, ((size_t)nsub + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, ctx_sync(c));
-    prof_collect(c);
-    dc_note_block(c, d);
-    if (d->hmeta[DM_FAIL] != 0) return BSC_NOT_SUPPORTED;
-    if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder batch] sub-blocks %d, decisions %u, types %u, chunks replayed %u\n", nsub, Efull, d->hmeta[DM_NTYPES], d->hmeta[DM_REPLAYS]);
-    *D_out = Efull;
-    return BSC_NO_ERROR;
-}
-
-int devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out)
+// What the entry points of a pass share: the arenas, the pass as qlfc_front_batch left it — the run arrays (vA / vB / SA: the buffers
+// the single path reads) and its table in front_tab, with max_rank per sub-block where dc_tab_prep_kernel will put it.
+// over_fail >= 0: the call is a model run, which clears what the context says about its last block; over_fail is what dc_last_fail
+// then says about a pass of more runs than the arena holds (a whole pass: FAIL_CAP, as devcoder_pstream; segments: 0).
+struct DcPass { DevCoder* d; FrontTab T; DcSubTab S; const u8 *dsym, *drank; const u32* dstart; };
+static int dc_pass_begin(bscgpu_ctx* c, u32 m, int nsub, int over_fail, DcPass* P)
 {
     int rc = devcoder_ensure(c);
     if (rc < 0) return rc;
     DevCoder* d = c->dc;
-    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = 0;
-    c->dc_last_fail = m > d->Mcap ? (int)FAIL_CAP : 0;
+    if (over_fail >= 0) {
+        c->dc_replays = c->dc_avg_und = c->dc_hist_ext = 0;
+        c->dc_last_fail = m > d->Mcap ? over_fail : 0;
+    }
     if (m == 0 || m > d->Mcap || nsub < 1 || nsub > FRONT_MAX_SUB || !c->front_tab) return BSC_NOT_SUPPORTED;
     rc = devcoder_batch_ensure(c, d);
     if (rc < 0) return rc;
-    const FrontTab T = qlfc_front_tab(c, nsub);
-    const u8* dsym = reinterpret_cast<const u8*>(c->vA); const u8* drank = reinterpret_cast<const u8*>(c->vB); const u32* dstart = c->SA;
-    DcSubTab S; S.nsub = (u32)nsub; S.run = T.sub_run; S.off = T.sub_off; S.base = T.sub_base; S.maxr = d->sub_maxr;
+    P->d = d; P->T = qlfc_front_tab(c, nsub);
+    P->dsym = reinterpret_cast<const u8*>(c->vA); P->drank = reinterpret_cast<const u8*>(c->vB); P->dstart = c->SA;
+    P->S.nsub = (u32)nsub; P->S.run = P->T.sub_run; P->S.off = P->T.sub_off; P->S.base = P->T.sub_base; P->S.maxr = d->sub_maxr;
+    return BSC_NO_ERROR;
+}
 
+// Probability stream of a whole pass, coder 1 (dc_static_run) or 3 (dc_fast_run) -> every sub-block's entries back to back in stream
+// order in the device p stream (buffer 0), poff[0..nsub] in d->poff_tab.  The same stages, the same kernels as a single block's,
+// instantiated for the table (DcSubTab); every guarded exit keeps its meaning with the PASS as the unit: a raised flag declines the
+// whole pass (BSC_NOT_SUPPORTED, c->dc_last_fail says why).  The arena of devcoder_batch_ensure serves both coders (the fast one uses
+// one esub plane of its four, and max_rank 7 for every sub-block).
+int devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* D_out)
+{
+    DcPass P;
+    const int rc = dc_pass_begin(c, m, nsub, (int)FAIL_CAP, &P);
+    if (rc < 0) return rc;
+    DevCoder* d = P.d;
+    const bool fast = coder == 3;                                      // LIBBSC_CODER_QLFC_FAST
     HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
-    HIP_TRY(c, hipMemsetAsync(d->present, 0, (size_t)DC_KIND_WORDS * 4, c->stream));
-    prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
-    hipLaunchKernelGGL(dc_tab_prep_kernel, dim3(((u32)nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, T.first_run, (u32)nsub, m, -1, d->sub_maxr, T.sub_run);
-    // (always: which sub-blocks can escape is not known on the host here; one of at most 32 symbols never leaves a flag open — avg_top)
-    hipLaunchKernelGGL(dc_avg_kernel<DcSubTab>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta, (u32*)nullptr);
+    if (!fast) HIP_TRY(c, hipMemsetAsync(d->present, 0, (size_t)DC_KIND_WORDS * 4, c->stream));
+    prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * (fast ? 14 : 40), m);
+    hipLaunchKernelGGL(dc_tab_prep_kernel, dim3(((u32)nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, P.T.first_run, (u32)nsub, m, fast ? 7 : -1, d->sub_maxr, P.T.sub_run);
+    // (the static coder, always: which sub-blocks can escape is not known on the host here; one of at most 32 symbols never leaves a
+    // flag open — avg_top.  No escape coding in the fast coder)
+    if (fast) HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));
+    else hipLaunchKernelGGL(dc_avg_kernel<DcSubTab>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, P.drank, m, P.S, d->ge32, d->meta, (u32*)nullptr);
     prof_end(c);
-    return dc_tab_static(c, d, S, dsym, drank, dstart, d->ge32, m, 0, -1, nullptr, D_out);
+    return fast ? dc_fast_run(c, d, P.S, P.dsym, P.drank, P.dstart, d->ge32, m, 0u, false, 0, -1, nullptr, D_out)
+                : dc_static_run(c, d, P.S, P.dsym, P.drank, P.dstart, d->ge32, m, 0u, false, 0, -1, nullptr, nullptr, nullptr, D_out);
 }
 const u32* devcoder_batch_poff_ptr(const bscgpu_ctx* c) { return c->dc ? c->dc->poff_tab : nullptr; }
-
-static int devcoder_pstream_fast(bscgpu_ctx* c, DevCoder* d, const u8* dsym, const u8* drank, const u32* dstart, u32 m, u32 n, int nb,
-                                 const u32* run_first, u32* D_out, u32* poff_out, int psbuf)
-{
-    DcSub S; S.nb = (u32)nb;
-    for (int b = 0; b < 9; ++b) S.first[b] = (b <= nb) ? run_first[b] : m;
-    for (int b = 0; b < 8; ++b) S.maxr[b] = 7u;                        // `if (bits < 7)` closes the exponent (qlfc.cpp:1204), whatever the alphabet
-    HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
-    const u32 gm = (m + WG - 1) / WG;
-    const u32 gm8 = (gm + 7u) / 8u * 8u;
-    prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 14, m);
-    HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));              // no escape coding in this coder
-    hipLaunchKernelGGL(dc_items_kernel<DcSub>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, d->ge32, m, n, S, d->key_ch);
-    prof_end(c);
-    RadixPass top; top.shift = 56; top.bits = 8;
-    int in_alt = 0;
-    int rc = radix_sort_passes(c, d->key_ch, d->key_ch_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_ch);
-    if (rc < 0) return rc;
-    // stream offsets of the runs (job 0: counts and scans only), then the one family's chains (job 1, symbol-major items)
-    {
-        const DcGeom g = dc_geom(m);
-        const u32 grid = (g.W + WAVES - 1) / WAVES;
-        prof_begin(c, BSCGPU_K_DC_PART, (u64)m * 8, m);
-        hipLaunchKernelGGL((dc_part_count_kernel<3, DcSub>), dim3(grid), dim3(WG), 0, c->stream, d->key_ch, g, S, d->rowbins, d->cnt, d->wdec);
-        hipLaunchKernelGGL(dc_scan_rows_kernel, dim3(DC_ROWS), dim3(WG), 0, c->stream, d->cnt, g.W, d->rowtot);
-        hipLaunchKernelGGL(dc_scan_misc_kernel, dim3(1), dim3(WG), 0, c->stream, d->rowtot, d->rowstart, d->wdec, g.W, d->wdecoff, d->meta, 0, (u32)d->Dcap);
-        hipLaunchKernelGGL((dc_doff_kernel<3, DcSub>), dim3(grid), dim3(WG), 0, c->stream, d->key_ch, g, S, d->meta, d->wdecoff, d->doff[0]);
-        prof_end(c);
-    }
-    dc_launch_partition<3>(c, d, d->key_ch_s, m, S, 1, 0u);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, ctx_sync(c));
-    prof_collect(c);
-    if (d->hmeta[DM_FAIL] != 0) { dc_note_block(c, d); return BSC_NOT_SUPPORTED; }
-    const u32 E = d->hmeta[DM_D0 + 1];
-    if (d->hmeta[DM_D0 + 0] != E) return ctx_fail(c, BSC_GPU_ERROR, "device coder (fast): decision counts of stream and chain order differ", hipSuccess);
-    rc = dc_eval_fast(c, d, E, false);
-    if (rc < 0) return rc;
-    DcGather G;
-    G.key_ch = d->key_ch; G.m = m; G.inv_ch = d->inv_ch; G.inv_sr = d->inv_ch; G.inv_sn = d->inv_ch;
-    G.doff_sp = d->doff[0]; G.doff_ch = d->doff[1]; G.doff_sr = d->doff[1]; G.doff_sn = d->doff[1];
-    G.pos_sp = d->pos[1]; G.pos_ch = d->pos[1]; G.pos_sr = d->pos[1]; G.pos_sn = d->pos[1];
-    G.V_sp = d->V[1]; G.V_ch = d->V[1]; G.V_sr = d->V[1]; G.V_sn = d->V[1];
-    prof_begin(c, BSCGPU_K_DC_PSTREAM, (u64)E * 10, E);
-    if (c->ps_guard[psbuf & 1]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ps_guard[psbuf & 1], 0));     // the buffer's previous copy-out
-    for (int b = 0; b < 8; ++b) if (c->ps_guard_sig[psbuf & 1][b]) (void)dma_wait(c->ps_guard_sig[psbuf & 1][b]);   // ... when it went through the DMA engine directly (two blocks ago: long landed)
-    hipLaunchKernelGGL((dc_pstream_kernel<true, false, DcSub>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp_fast, d->meta, d->ps[psbuf & 1], (u16*)nullptr, E, DcP13{});
-    hipLaunchKernelGGL(dc_poff_kernel, dim3(1), dim3(16), 0, c->stream, d->doff[0], S, m, d->poff);
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d->hmeta + 32, d->poff, 16 * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, ctx_sync(c));
-    if (d->hmeta[DM_FAIL] != 0) { dc_note_block(c, d); return BSC_NOT_SUPPORTED; }
-    dc_note_block(c, d);
-    if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder fast] decisions %u, chunks replayed %u\n", E, d->hmeta[DM_REPLAYS]);
-    *D_out = E;
-    for (int b = 0; b <= nb; ++b) poff_out[b] = d->hmeta[32 + b];
-    return BSC_NO_ERROR;
-}
-
-// The fast coder's model (-e0) of a whole pass: devcoder_pstream_fast over the table qlfc_front_batch leaves, as devcoder_pstream_batch
-// is devcoder_pstream.  One family: the runs' stream offsets (job 0: counts and scans only), the partition of the symbol-major items
-// (job 1; its scatter writes every event's full sub-block id to esub[1], which dc_mark_chains_kernel folds into the chain-start mark —
-// a fast chain is (sub-block, decision type, symbol)), one evaluation with mp_fast, one stream whose entries are the counter values
-// (dcm::PSF_*).  max_rank is 7 for every sub-block.  No avg_rank flags, no run_hist look-back: FAIL_CAP and FAIL_REPLAY are the only
-// flags that can be raised.  The arena of devcoder_batch_ensure as it is (one esub plane of its four is used).  Two syncs.
-// dc_tab_fast: the part a whole pass and a model segment share (as dc_tab_static; the caller has cleared meta and ge32).
-static int dc_tab_fast(bscgpu_ctx* c, DevCoder* d, const DcSubTab& S, const u8* dsym, const u8* drank, const u32* dstart, const u8* ge32,
-                       u32 m, int psbuf, int64_t expect, u32* poff_host, u32* D_out)
-{
-    const int nsub = (int)S.nsub;
-    const u32 gm = (m + WG - 1) / WG;
-    const u32 gm8 = (gm + 7u) / 8u * 8u;            // kernels that use dc_virtual_block()
-    prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 14, m);
-    hipLaunchKernelGGL(dc_items_kernel<DcSubTab>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, ge32, m, 0u, S, d->key_ch);
-    prof_end(c);
-    RadixPass top; top.shift = 56; top.bits = 8;
-    int in_alt = 0;
-    int rc = radix_sort_passes(c, d->key_ch, d->key_ch_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_ch);
-    if (rc < 0) return rc;
-    {
-        const DcGeom g = dc_geom(m);
-        const u32 grid = (g.W + WAVES - 1) / WAVES;
-        prof_begin(c, BSCGPU_K_DC_PART, (u64)m * 8, m);
-        hipLaunchKernelGGL((dc_part_count_kernel<3, DcSubTab>), dim3(grid), dim3(WG), 0, c->stream, d->key_ch, g, S, d->rowbins, d->cnt, d->wdec);
-        hipLaunchKernelGGL(dc_scan_rows_kernel, dim3(DC_ROWS), dim3(WG), 0, c->stream, d->cnt, g.W, d->rowtot);
-        hipLaunchKernelGGL(dc_scan_misc_kernel, dim3(1), dim3(WG), 0, c->stream, d->rowtot, d->rowstart, d->wdec, g.W, d->wdecoff, d->meta, 0, (u32)d->Dcap);
-        hipLaunchKernelGGL((dc_doff_kernel<3, DcSubTab>), dim3(grid), dim3(WG), 0, c->stream, d->key_ch, g, S, d->meta, d->wdecoff, d->doff[0]);
-        prof_end(c);
-    }
-    dc_launch_partition<3>(c, d, d->key_ch_s, m, S, 1, 0u);
-    hipLaunchKernelGGL(dc_poff_tab_kernel, dim3(((u32)nsub + 1 + WG - 1) / WG), dim3(WG), 0, c->stream, d->doff[0], S, d->poff_tab);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, ctx_sync(c));
-    prof_collect(c);
-    if (d->hmeta[DM_FAIL] != 0) { dc_note_block(c, d); return BSC_NOT_SUPPORTED; }
-    const u32 E = d->hmeta[DM_D0 + 1];
-    if (d->hmeta[DM_D0 + 0] != E) return ctx_fail(c, BSC_GPU_ERROR, "device coder (fast): decision counts of stream and chain order differ", hipSuccess);
-    if (expect >= 0 && (int64_t)E != expect) return ctx_fail(c, BSC_GPU_ERROR, "device coder (fast): a segment's decisions differ from the plan's count", hipSuccess);
-    rc = dc_eval_fast(c, d, E, true);
-    if (rc < 0) return rc;
-
-    DcGather G;
-    G.key_ch = d->key_ch; G.m = m; G.inv_ch = d->inv_ch; G.inv_sr = d->inv_ch; G.inv_sn = d->inv_ch;
-    G.doff_sp = d->doff[0]; G.doff_ch = d->doff[1]; G.doff_sr = d->doff[1]; G.doff_sn = d->doff[1];
-    G.pos_sp = d->pos[1]; G.pos_ch = d->pos[1]; G.pos_sr = d->pos[1]; G.pos_sn = d->pos[1];
-    G.V_sp = d->V[1]; G.V_ch = d->V[1]; G.V_sr = d->V[1]; G.V_sn = d->V[1];
-    prof_begin(c, BSCGPU_K_DC_PSTREAM, (u64)E * 10, E);
-    if (c->ps_guard[psbuf & 1]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ps_guard[psbuf & 1], 0));     // the buffer's previous copy-out (a single-path block)
-    for (int b = 0; b < 8; ++b) if (c->ps_guard_sig[psbuf & 1][b]) (void)dma_wait(c->ps_guard_sig[psbuf & 1][b]);
-    hipLaunchKernelGGL((dc_pstream_kernel<true, false, DcSubTab>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp_fast, d->meta, d->ps[psbuf & 1], (u16*)nullptr, E, DcP13{});
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
-    if (poff_host) HIP_TRY(c, hipMemcpyAsync(poff_host, d->poff_tab, ((size_t)nsub + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, ctx_sync(c));
-    prof_collect(c);
-    dc_note_block(c, d);
-    if (d->hmeta[DM_FAIL] != 0) return BSC_NOT_SUPPORTED;
-    if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder fast batch] sub-blocks %d, decisions %u, chunks replayed %u\n", nsub, E, d->hmeta[DM_REPLAYS]);
-    *D_out = E;
-    return BSC_NO_ERROR;
-}
-
-int devcoder_pstream_fast_batch(bscgpu_ctx* c, u32 m, int nsub, u32* D_out)
-{
-    int rc = devcoder_ensure(c);
-    if (rc < 0) return rc;
-    DevCoder* d = c->dc;
-    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = 0;
-    c->dc_last_fail = m > d->Mcap ? (int)FAIL_CAP : 0;
-    if (m == 0 || m > d->Mcap || nsub < 1 || nsub > FRONT_MAX_SUB || !c->front_tab) return BSC_NOT_SUPPORTED;
-    rc = devcoder_batch_ensure(c, d);
-    if (rc < 0) return rc;
-    const FrontTab T = qlfc_front_tab(c, nsub);
-    const u8* dsym = reinterpret_cast<const u8*>(c->vA); const u8* drank = reinterpret_cast<const u8*>(c->vB); const u32* dstart = c->SA;
-    DcSubTab S; S.nsub = (u32)nsub; S.run = T.sub_run; S.off = T.sub_off; S.base = T.sub_base; S.maxr = d->sub_maxr;
-
-    HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
-    prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 14, m);
-    hipLaunchKernelGGL(dc_tab_prep_kernel, dim3(((u32)nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, T.first_run, (u32)nsub, m, 7, d->sub_maxr, T.sub_run);
-    HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));              // no escape coding in this coder
-    prof_end(c);
-    return dc_tab_fast(c, d, S, dsym, drank, dstart, d->ge32, m, 0, -1, nullptr, D_out);
-}
 
 // ---- a pass in model segments ("Model segments") --------------------------------------------------------------------
 // Sub-blocks are independent chains by construction (the chain identity carries the sub-block), so the model of a pass can run over
 // any contiguous range of its sub-blocks and write the same entries.  Facts first, once per pass and before any sort: every
 // sub-block's undecided avg_rank flags (dc_avg_kernel) and its decisions for this coder (dc_sub_dec_kernel).  The plan
 // (bscgpu_model_segment_plan) excludes a block with an undecided flag or more decisions than the arena holds and cuts the rest into
-// segments of at most min(Dcap, target) decisions; each segment then is a small pass of its own to dc_tab_static / dc_tab_fast (its
+// segments of at most min(Dcap, target) decisions; each segment then is a small pass of its own to dc_static_run / dc_fast_run (its
 // rebased run table: dc_seg_tab_kernel).  The device stream is double-buffered over ps[0 / 1]: segment k + 1 is modelled while
 // segment k's entries leave on the copy stream.  A segment that declines while it runs (FAIL_HIST, FAIL_REPLAY) is split at the block
 // boundary nearest half its decisions and both halves run again, depth first; a single block that declines is marked with the reason.
 // out / cap: where the kept entries go back to back (host); per_segment_fit: a segment that no longer fits behind the ones before
 // it is left to the host (FAIL_CAP) — else a total above cap is counted, not copied.
 // the facts of a pass (after qlfc_front_batch): dec[s] / und[s] of every sub-block on the host; ge32 and sub_maxr stay for the segments
-static int dc_segment_facts(bscgpu_ctx* c, DevCoder* d, u32 m, int nsub, bool fast, u32* dec, u32* und)
+static int dc_segment_facts(bscgpu_ctx* c, const DcPass& P, u32 m, bool fast, u32* dec, u32* und)
 {
-    const FrontTab T = qlfc_front_tab(c, nsub);
-    const u8* dsym = reinterpret_cast<const u8*>(c->vA); const u8* drank = reinterpret_cast<const u8*>(c->vB); const u32* dstart = c->SA;
-    DcSubTab S; S.nsub = (u32)nsub; S.run = T.sub_run; S.off = T.sub_off; S.base = T.sub_base; S.maxr = d->sub_maxr;
+    DevCoder* d = P.d;
+    const int nsub = (int)P.S.nsub;
     HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
     HIP_TRY(c, hipMemsetAsync(d->sub_und, 0, (size_t)nsub * 4, c->stream));
     HIP_TRY(c, hipMemsetAsync(d->sub_dec, 0, (size_t)nsub * 4, c->stream));
     prof_begin(c, BSCGPU_K_DC_FACTS, (u64)m * 6, m);
-    hipLaunchKernelGGL(dc_tab_prep_kernel, dim3(((u32)nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, T.first_run, (u32)nsub, m, fast ? 7 : -1, d->sub_maxr, T.sub_run);
+    hipLaunchKernelGGL(dc_tab_prep_kernel, dim3(((u32)nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, P.T.first_run, (u32)nsub, m, fast ? 7 : -1, d->sub_maxr, P.T.sub_run);
     if (fast) HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));
-    else hipLaunchKernelGGL(dc_avg_kernel<DcSubTab>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta, d->sub_und);
-    hipLaunchKernelGGL(dc_sub_dec_kernel, dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, dsym, drank, dstart, d->ge32, m, S, d->sub_dec);
+    else hipLaunchKernelGGL(dc_avg_kernel<DcSubTab>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, P.drank, m, P.S, d->ge32, d->meta, d->sub_und);
+    hipLaunchKernelGGL(dc_sub_dec_kernel, dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, P.dsym, P.drank, P.dstart, d->ge32, m, P.S, d->sub_dec);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(und, d->sub_und, (size_t)nsub * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2059,34 +1940,25 @@ static int dc_segment_facts(bscgpu_ctx* c, DevCoder* d, u32 m, int nsub, bool fa
 }
 int devcoder_segment_facts(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* dec, u32* und)
 {
-    int rc = devcoder_ensure(c);
+    DcPass P;
+    const int rc = dc_pass_begin(c, m, nsub, -1, &P);
     if (rc < 0) return rc;
-    DevCoder* d = c->dc;
-    if (m == 0 || m > d->Mcap || nsub < 1 || nsub > FRONT_MAX_SUB || !c->front_tab) return BSC_NOT_SUPPORTED;
-    rc = devcoder_batch_ensure(c, d);
-    if (rc < 0) return rc;
-    return dc_segment_facts(c, d, m, nsub, coder == 3, dec, und);
+    return dc_segment_facts(c, P, m, coder == 3, dec, und);
 }
 
 int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub, int count, const u32* sub_run, int coder, int64_t target,
                               u16* out, int64_t cap, bool per_segment_fit, u32* poff, int* blk_state, int64_t* D_out, const DcSegNote* note)
 {
-    int rc = devcoder_ensure(c);
+    DcPass P;
+    int rc = dc_pass_begin(c, m, nsub, 0, &P);
     if (rc < 0) return rc;
-    DevCoder* d = c->dc;
-    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = 0;
-    c->dc_last_fail = 0;
-    if (m == 0 || m > d->Mcap || nsub < 1 || nsub > FRONT_MAX_SUB || !c->front_tab) return BSC_NOT_SUPPORTED;
-    rc = devcoder_batch_ensure(c, d);
-    if (rc < 0) return rc;
+    DevCoder* d = P.d;
     for (int k = 0; k < 2; ++k)
         if (!d->seg_ev[k]) HIP_TRY(c, hipEventCreateWithFlags(&d->seg_ev[k], hipEventDisableTiming));
     const bool fast = coder == 3;                                      // LIBBSC_CODER_QLFC_FAST
-    const FrontTab T = qlfc_front_tab(c, nsub);
-    const u8* dsym = reinterpret_cast<const u8*>(c->vA); const u8* drank = reinterpret_cast<const u8*>(c->vB); const u32* dstart = c->SA;
 
     std::vector<u32> und((size_t)nsub), dec((size_t)nsub);
-    rc = dc_segment_facts(c, d, m, nsub, fast, dec.data(), und.data());
+    rc = dc_segment_facts(c, P, m, fast, dec.data(), und.data());
     if (rc < 0) return rc;
     int64_t und_total = 0;
     for (int s = 0; s < nsub; ++s) und_total += und[s];
@@ -2153,13 +2025,14 @@ int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub
         HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
         if (!fast) HIP_TRY(c, hipMemsetAsync(d->present, 0, (size_t)DC_KIND_WORDS * 4, c->stream));
         prof_begin(c, BSCGPU_K_DC_FACTS, (u64)(s1 - s0) * 8, (u64)(s1 - s0));
-        hipLaunchKernelGGL(dc_seg_tab_kernel, dim3(((u32)(s1 - s0) + 1 + WG - 1) / WG), dim3(WG), 0, c->stream, T.sub_run, (u32)s0, (u32)(s1 - s0), r0, r1, d->seg_run);
+        hipLaunchKernelGGL(dc_seg_tab_kernel, dim3(((u32)(s1 - s0) + 1 + WG - 1) / WG), dim3(WG), 0, c->stream, P.T.sub_run, (u32)s0, (u32)(s1 - s0), r0, r1, d->seg_run);
         prof_end(c);
         HIP_TRY(c, hipStreamWaitEvent(c->stream, d->seg_ev[psbuf], 0));          // this buffer's copy-out of two segments ago
-        DcSubTab G; G.nsub = (u32)(s1 - s0); G.run = d->seg_run; G.off = T.sub_off + s0; G.base = T.sub_base + s0; G.maxr = d->sub_maxr + s0;
+        // (the segment's rebased table, the pass's run arrays and flags offset to its first run)
+        DcSubTab G; G.nsub = (u32)(s1 - s0); G.run = d->seg_run; G.off = P.T.sub_off + s0; G.base = P.T.sub_base + s0; G.maxr = d->sub_maxr + s0;
         u32 D = 0;
-        rc = fast ? dc_tab_fast(c, d, G, dsym + r0, drank + r0, dstart + r0, d->ge32 + r0, r1 - r0, psbuf, expect, pseg.data(), &D)
-                  : dc_tab_static(c, d, G, dsym + r0, drank + r0, dstart + r0, d->ge32 + r0, r1 - r0, psbuf, expect, pseg.data(), &D);
+        rc = fast ? dc_fast_run(c, d, G, P.dsym + r0, P.drank + r0, P.dstart + r0, d->ge32 + r0, r1 - r0, 0u, false, psbuf, expect, pseg.data(), &D)
+                  : dc_static_run(c, d, G, P.dsym + r0, P.drank + r0, P.dstart + r0, d->ge32 + r0, r1 - r0, 0u, false, psbuf, expect, pseg.data(), nullptr, nullptr, &D);
         replays += c->dc_replays; hist_ext += c->dc_hist_ext;
         if (rc == BSC_NOT_SUPPORTED) {
             const int why = c->dc_last_fail;

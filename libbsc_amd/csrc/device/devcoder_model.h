@@ -346,7 +346,7 @@ DC_HD uint32_t run_state_index(uint32_t ctx_rank0, uint32_t ctx_run, uint32_t ra
 #ifndef DC_EV_N
 #define DC_EV_N 8192
 #endif
-constexpr int DC_EV          = DC_EV_N;  // events per evaluation chunk: the minimum (see devcoder_pstream: long enough for the brackets to meet)
+constexpr int DC_EV          = DC_EV_N;  // events per evaluation chunk: the minimum (see dc_eval: long enough for the brackets to meet)
 constexpr int DC_EVAL_WAVES_TARGET = 1000;   // ... or as many as keep a block's evaluation at this many wavefronts of 64 chunks
 constexpr int DC_EB          = 64;       // events per lane per batch of the evaluation walk (chunks are whole batches)
 constexpr int DC_REPLAY_MAX  = 64;       // chunks a serial replay walks back before the block is declined (FAIL_REPLAY)

@@ -476,7 +476,7 @@ static int gpu_stage(BlockJob& J, int blockSorter, bool allow_devcoder = true)
     // (an LZP-preprocessed block — the reference CLI's default, bsc.cpp:73-75 — is just another byte block to the sorter and the model;
     // its LZP output stays alive until the block is done, because a redo on the host model uploads it again)
     // (the fast coder, -e0, runs on the same device machinery: its one counter per decision is the static coder's char family with
-    // other update maps — devcoder.hip: devcoder_pstream_fast; BSC_DEVICE_CODER_FAST=0 keeps it on the host)
+    // other update maps — devcoder.hip: dc_fast_run; BSC_DEVICE_CODER_FAST=0 keeps it on the host)
     static const bool dc_fast = [] { const char* e = getenv("BSC_DEVICE_CODER_FAST"); return e ? atoi(e) != 0 : true; }();
     const bool try_dc = allow_devcoder && devcoder_enabled() && (J.coder == LIBBSC_CODER_QLFC_STATIC || (J.coder == LIBBSC_CODER_QLFC_FAST && dc_fast))
                      && J.nblocks > 1 && n >= devcoder_min_n();
@@ -1855,8 +1855,7 @@ static int64_t pstream_batch_device(bscgpu_ctx* c, const void* dL, const int* si
     poff[0] = 0;
     if (out->nsub == 0) return 0;
     u32 D = 0;
-    const int rc = coder == LIBBSC_CODER_QLFC_FAST ? devcoder_pstream_fast_batch(c, (u32)out->m, out->nsub, &D)
-                                                   : devcoder_pstream_batch(c, (u32)out->m, out->nsub, &D);
+    const int rc = devcoder_pstream_batch(c, (u32)out->m, out->nsub, coder, &D);
     if (rc == LIBBSC_NOT_SUPPORTED) {
         char buf[96]; snprintf(buf, sizeof buf, "device coder declined the pass (reason mask %d)", c->dc_last_fail);
         c->err = buf;
@@ -2267,8 +2266,7 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
                     // the model behind the front end, on the same stream, before the next pass's sort; the run arrays came down all the
                     // same: they serve a declined pass, a sub-block stored raw and the <= 28-byte blocks that rode along
                     u32 D = 0;
-                    const int mrc = fast_model ? devcoder_pstream_fast_batch(c, (u32)PL.lay.m, PL.lay.nsub, &D)
-                                               : devcoder_pstream_batch(c, (u32)PL.lay.m, PL.lay.nsub, &D);
+                    const int mrc = devcoder_pstream_batch(c, (u32)PL.lay.m, PL.lay.nsub, coder, &D);
                     if (mrc == LIBBSC_NOT_SUPPORTED) ++(fast_model ? c->cnt_model_fast_declined : c->cnt_model_declined);
                     else if (mrc < 0) { rc = mrc; break; }
                     else if ((size_t)D <= c->model_host_entries) {

@@ -686,7 +686,7 @@ def test_lzp_blocks_take_the_device_model_and_survive_a_redo(ref, torch_cuda):
 
 def test_fast_coder_on_the_device_model(ref, torch_cuda):
     """-e0 (qlfc.cpp:1135-1336) behind the device model: its one counter per decision is the static coder's char family with shift
-    updates (devcoder.hip: devcoder_pstream_fast; the chain model is pinned on CPU by tools/devcoder_fast_sim.cpp), the host codes the
+    updates (devcoder.hip: dc_fast_run; the chain model is pinned on CPU by tools/devcoder_fast_sim.cpp), the host codes the
     13- / 11-bit entries (qlfc_encode_fast_pstream).  Text with 2, 4 and 8 sub-blocks, 256-symbol data (all 7-bit rank exponents), long
     runs (run-length mantissas of more than 5 bits: the second rate class), a block with a raw sub-block (redo on the host model) and an
     LZP block; synchronous and pipelined, both framings; bytes = the reference's, and the counters say the device model ran."""
