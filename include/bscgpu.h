@@ -106,7 +106,7 @@ BSCGPU_API int64_t bscgpu_qlfc_static_pstream_packed(bscgpu_ctx* ctx, const uint
  * the host coders of the same form (rangecoder.h:38-271: 32-bit range, 64-bit low with the carry in bit 32, 16-bit little-endian
  * units, finish = one conditional and three unconditional shifts).
  *   prefix entry (u32)   [15:0] multiplier p, [20:16] precision, [24] coded bit: range' = (range >> precision) * p for a 0 bit
- *   bscgpu_rc_prefix     pure function: the decisions qlfc_encode_static_pstream / _p13 (coder 1) or qlfc_encode_fast_pstream (coder 3)
+ *   bscgpu_rc_prefix     pure function: the decisions qlfc_encode_pstream (the static forms for coder 1, the fast form for coder 3)
  *                        issue before the body — EncodeWord(in_size) at precision 12, p 2048, then the alphabet (csrc/host/qlfc.cpp: encode_alphabet) at
  *                        precision 12, p 2048 (static) or precision 1, p 1 (fast).  Returns the count (at most BSCGPU_RC_PREFIX_MAX; entries
  *                        may be NULL to ask for it) or LIBBSC_BAD_PARAMETER (cap too small included).

@@ -355,8 +355,8 @@ struct BlockJob {
     int  ps_g = 2;                 // device-model sub-blocks per coder task (ps_group), fixed when the block's host work starts
     bool use_ps = false; const uint16_t* ps = nullptr; u32 poff[9]; u32 ndec = 0; int sorter = 0;
     bool ps_packed = false; u32 pbase[9];          // the stream is the 13-bit packed form (devcoder.hip DcP13): sub-block b's starts at decision pbase[b] of the packed space (a multiple of 64)
-    // sub-block b's stream as the coders take it: 16-bit entries, or the packed bytes behind the same pointer type
-    const uint16_t* ps_of(int b) const { return ps_packed ? reinterpret_cast<const uint16_t*>(reinterpret_cast<const uint8_t*>(ps) + (size_t)pbase[b] / 8u * 13u) : ps + poff[b]; }
+    // sub-block b's stream as the coders take it: 16-bit entries, or the packed bytes
+    const void* ps_of(int b) const { return ps_packed ? static_cast<const void*>(reinterpret_cast<const uint8_t*>(ps) + (size_t)pbase[b] / 8u * 13u) : ps + poff[b]; }
     hipEvent_t ps_ready = nullptr;   // the p stream's copy to the host (copy stream), all of it
     hipEvent_t ps_part[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // ... up to and including sub-block b: what a coder task waits on
     bool ps_dma = false; uint64_t ps_sig[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the pieces went through the DMA engine directly (dma_copy.h): signals instead of events
@@ -382,6 +382,28 @@ static bool devcoder_enabled() { static const int v = [] { const char* e = geten
 static int  devcoder_min_n() { static const int v = [] { const char* e = getenv("BSC_DEVICE_CODER_MIN_N"); return e ? atoi(e) : (1 << 20); }(); return v; }
 
 static std::atomic<uint64_t> g_count_devmodel{0}, g_count_redo{0}, g_count_devmodel_lzp{0};     // bscgpu_process_counter
+
+// the entry form of a device-model block's probability stream (include/bscgpu.h)
+static int ps_form(const BlockJob& J) { return J.ps_packed ? BSCGPU_RC_STATIC13 : J.coder == LIBBSC_CODER_QLFC_FAST ? BSCGPU_RC_FAST16 : BSCGPU_RC_STATIC16; }
+// sub-block q's buffer for its coded bytes
+static void sub_scratch(BlockJob& J, int q)
+{
+    const size_t need = (size_t)J.size[q] + 64;
+    if (J.scratch_cap[q] < need) { J.scratch[q].reset(new uint8_t[need + need / 8]); J.scratch_cap[q] = need + need / 8; }
+}
+// sub-block q of a device-model block as the stream coders take it (qlfc.h); parallel framing semantics (coder.cpp:159-240): every
+// sub-block is coded with outputSize = its own size
+static PstreamJob ps_job(BlockJob& J, int q)
+{
+    sub_scratch(J, q);
+    return PstreamJob{J.views[q].first_seen, J.views[q].nsym, J.size[q], J.ps_of(q), (size_t)(J.poff[q + 1] - J.poff[q]), J.scratch[q].get(), J.size[q]};
+}
+// ... and what its coder returned: a sub-block that did not compress would be stored raw, which needs the run arrays — the block is redone
+static void ps_record(BlockJob& J, int q, int r)
+{
+    if (r < 0) J.redo.store(true, std::memory_order_relaxed);
+    J.sub_res[q] = r < 0 ? J.size[q] : r;
+}
 
 // BSCGPU_OPT_DEVICE_RC: the sub-block streams of a device-model block through the device's range coder (rangecoder.hip), one launch on
 // the context's stream straight from the device's p stream; only the coded bytes come down, into the sub-blocks' scratch buffers, and
@@ -412,15 +434,13 @@ static int device_rc_block(BlockJob& J, int psbuf)
     }
     if ((size_t)off > (size_t)8 * (size_t)c->max_n) return LIBBSC_NOT_SUPPORTED;
     uint8_t* dOut = reinterpret_cast<uint8_t*>(c->kA);
-    const int form = J.ps_packed ? BSCGPU_RC_STATIC13 : J.coder == LIBBSC_CODER_QLFC_FAST ? BSCGPU_RC_FAST16 : BSCGPU_RC_STATIC16;
     // (one stream per wavefront: with a block's 2 .. 8 streams the wave-uniform chain is the fastest shape measured)
-    int rc = rc_encode_device(c, form, devcoder_pstream_ptr(c, psbuf), prefix.data(), (int)prefix.size(), S, nb, dOut, res, 1);
+    int rc = rc_encode_device(c, ps_form(J), devcoder_pstream_ptr(c, psbuf), prefix.data(), (int)prefix.size(), S, nb, dOut, res, 1);
     if (rc < 0) return rc;
     for (int b = 0; b < nb; ++b) {
-        const size_t need = (size_t)J.size[b] + 64;
-        if (J.scratch_cap[b] < need) { J.scratch[b].reset(new uint8_t[need + need / 8]); J.scratch_cap[b] = need + need / 8; }
-        if (res[b] < 0) { J.redo.store(true, std::memory_order_relaxed); J.sub_res[b] = J.size[b]; continue; }      // would be stored raw: that needs the run arrays
-        J.sub_res[b] = res[b];
+        sub_scratch(J, b);
+        ps_record(J, b, res[b]);
+        if (res[b] < 0) continue;
         if (hipMemcpyAsync(J.scratch[b].get(), dOut + S[b].out_off, (size_t)res[b], hipMemcpyDeviceToHost, c->stream) != hipSuccess) return LIBBSC_GPU_ERROR;
     }
     if (ctx_sync(c) != hipSuccess) return LIBBSC_GPU_ERROR;
@@ -597,24 +617,19 @@ static void expand_runs(const RunView& V, int sub_start, uint8_t* dst)
     for (uint32_t j = 0; j < V.count; ++j) memset(dst + (V.start[j] - (uint32_t)sub_start), V.sym[j], V.len(j));
 }
 
-// parallel framing semantics (coder.cpp:159-240): every sub-block is coded with outputSize = its own size
+// One sub-block, from its run arrays or — a device-model block — from its probability stream.  A stream coder's task waits for the
+// arrival of its last sub-block's piece of the stream; if that did not land the block is redone on the host model.
 static void host_encode_sub(BlockJob& J, int b)
 {
-    const size_t need = (size_t)J.size[b] + 64;
-    if (J.scratch_cap[b] < need) { J.scratch[b].reset(new uint8_t[need + need / 8]); J.scratch_cap[b] = need + need / 8; }
-    if (J.use_ps) {
-        if (J.rc_done) return;
-        if (!J.ps_landed(b)) { J.redo.store(true, std::memory_order_relaxed); J.sub_res[b] = J.size[b]; return; }
-        const int r = J.ps_packed ? qlfc_encode_static_p13(J.views[b].first_seen, J.views[b].nsym, J.size[b], reinterpret_cast<const uint8_t*>(J.ps_of(b)),
-                                                           (size_t)(J.poff[b + 1] - J.poff[b]), J.scratch[b].get(), J.size[b])
-                    : (J.coder == LIBBSC_CODER_QLFC_FAST ? qlfc_encode_fast_pstream : qlfc_encode_static_pstream)(
-                          J.views[b].first_seen, J.views[b].nsym, J.size[b], J.ps + J.poff[b], (size_t)(J.poff[b + 1] - J.poff[b]), J.scratch[b].get(), J.size[b]);
-        if (r < 0) J.redo.store(true, std::memory_order_relaxed);      // would be stored raw: that needs the run arrays
+    if (!J.use_ps) {
+        sub_scratch(J, b);
+        const int r = qlfc_encode_runs(J.views[b], J.size[b], J.scratch[b].get(), J.size[b], J.coder);      // outputSize = its own size, as in ps_job
         J.sub_res[b] = (r < 0) ? J.size[b] : r;
         return;
     }
-    const int r = qlfc_encode_runs(J.views[b], J.size[b], J.scratch[b].get(), J.size[b], J.coder);
-    J.sub_res[b] = (r < 0) ? J.size[b] : r;
+    const PstreamJob P = ps_job(J, b);
+    if (J.rc_done) return;
+    ps_record(J, b, J.ps_landed(b) ? qlfc_encode_pstream(ps_form(J), P) : LIBBSC_NOT_COMPRESSIBLE);
 }
 
 // two sub-blocks of a device-model block in one interleaved range-coder loop (b even)
@@ -622,26 +637,15 @@ static void host_encode_pair(BlockJob& J, int b)
 {
     if (!J.use_ps || b + 1 >= J.nblocks) { host_encode_sub(J, b); if (b + 1 < J.nblocks) host_encode_sub(J, b + 1); return; }
     if (J.rc_done) return;
-    PstreamJob P[2];
-    for (int k = 0; k < 2; ++k) {
-        const int q = b + k;
-        const size_t need = (size_t)J.size[q] + 64;
-        if (J.scratch_cap[q] < need) { J.scratch[q].reset(new uint8_t[need + need / 8]); J.scratch_cap[q] = need + need / 8; }
-        P[k] = PstreamJob{J.views[q].first_seen, J.views[q].nsym, J.size[q], J.ps_of(q), (size_t)(J.poff[q + 1] - J.poff[q]), J.scratch[q].get(), J.size[q]};
-    }
-    if (!J.ps_landed(b + 1)) { J.redo.store(true, std::memory_order_relaxed); J.sub_res[b] = J.size[b]; J.sub_res[b + 1] = J.size[b + 1]; return; }
-    int r0, r1;
-    if (J.ps_packed) qlfc_encode_static_p13_pair(P[0], P[1], &r0, &r1);
-    else if (J.coder == LIBBSC_CODER_QLFC_FAST) qlfc_encode_fast_pstream_pair(P[0], P[1], &r0, &r1);
-    else qlfc_encode_static_pstream_pair(P[0], P[1], &r0, &r1);
-    if (r0 < 0 || r1 < 0) J.redo.store(true, std::memory_order_relaxed);
-    J.sub_res[b] = r0 < 0 ? J.size[b] : r0;
-    J.sub_res[b + 1] = r1 < 0 ? J.size[b + 1] : r1;
+    const PstreamJob P[2] = {ps_job(J, b), ps_job(J, b + 1)};
+    int r[2] = {LIBBSC_NOT_COMPRESSIBLE, LIBBSC_NOT_COMPRESSIBLE};
+    if (J.ps_landed(b + 1)) qlfc_encode_pstream_pair(ps_form(J), P[0], P[1], &r[0], &r[1]);
+    ps_record(J, b, r[0]); ps_record(J, b + 1, r[1]);
 }
 
 // How the eight sub-blocks of a device-model block are coded on the host (EPYC 9575F, the coding loops alone on one quiet thread, per 64 MiB
 // bench block: tools/rc_host_bench.cpp, profiles/r05/host_coder_on_box_cpu.txt; round 4's figures in brackets):
-//   8  all eight in the lanes of one SIMD range-coder loop (qlfc_encode_static_pstream_x8): one task of 96 ms [104] with AVX-512VL (126 with AVX2)
+//   8  all eight in the lanes of one SIMD range-coder loop (qlfc_encode_pstream_x8): one task of 96 ms [104] with AVX-512VL (126 with AVX2)
 //   2  four tasks of two interleaved scalar coders: 48 ms each [54], 0.19 CPU-s
 //   1  eight tasks of one scalar coder: 35 ms each [46], 0.28 CPU-s [0.37]
 // bscgpu_coder_task_shape is the rule (a pure function, unit-tested on CPU); ps_group feeds it.  BSC_RC_SIMD=8 / 0 forces eight lanes /
@@ -720,22 +724,14 @@ static void host_encode_group(BlockJob& J, int b)
     if (g == 2) { host_encode_pair(J, b); return; }
     if (g == 1) { host_encode_sub(J, b); return; }
     PstreamJob P[8];
-    for (int k = 0; k < g; ++k) {
-        const int q = b + k;
-        const size_t need = (size_t)J.size[q] + 64;
-        if (J.scratch_cap[q] < need) { J.scratch[q].reset(new uint8_t[need + need / 8]); J.scratch_cap[q] = need + need / 8; }
-        P[k] = PstreamJob{J.views[q].first_seen, J.views[q].nsym, J.size[q], J.ps_of(q), (size_t)(J.poff[q + 1] - J.poff[q]), J.scratch[q].get(), J.size[q]};
-    }
-    if (!J.ps_landed(b + g - 1)) { J.redo.store(true, std::memory_order_relaxed); for (int k = 0; k < g; ++k) J.sub_res[b + k] = J.size[b + k]; return; }
+    for (int k = 0; k < g; ++k) P[k] = ps_job(J, b + k);
     int r[8];
-    if (!(J.ps_packed ? qlfc_encode_static_p13_x8(P, r) : J.coder == LIBBSC_CODER_QLFC_FAST ? qlfc_encode_fast_pstream_x8(P, r) : qlfc_encode_static_pstream_x8(P, r))) {
+    if (!J.ps_landed(b + g - 1)) std::fill(r, r + g, (int)LIBBSC_NOT_COMPRESSIBLE);
+    else if (!qlfc_encode_pstream_x8(ps_form(J), P, r)) {
         for (int k = 0; k < g; k += 2) host_encode_pair(J, b + k);      // a stream near its budget: the exact scalar coders
         return;
     }
-    for (int k = 0; k < g; ++k) {
-        if (r[k] < 0) J.redo.store(true, std::memory_order_relaxed);
-        J.sub_res[b + k] = r[k] < 0 ? J.size[b + k] : r[k];
-    }
+    for (int k = 0; k < g; ++k) ps_record(J, b + k, r[k]);
 }
 
 static void write_stored(BlockJob& J)
@@ -1779,14 +1775,14 @@ static int front_batch_code_stream(const bscgpu_front_layout* Lo, int block, con
     RunsFetch fetch;
     fetch.views = views; fetch.st = Lo->sub_start + s0; fetch.sz = Lo->sub_size + s0; fetch.nb = nb;
     struct FromStream : SubEncode {                                 // the range coder alone: the model ran on the GPU
-        const bscgpu_front_layout* Lo; int s0; const uint16_t* ps; const uint32_t* poff; bool fast;
+        const bscgpu_front_layout* Lo; int s0; const uint16_t* ps; const uint32_t* poff; int form;
         int operator()(int b, uint8_t* dst, int room) override
         {
             const int s = s0 + b;
-            return (fast ? qlfc_encode_fast_pstream : qlfc_encode_static_pstream)(Lo->first_seen + 256 * (size_t)s, Lo->nsym[s], Lo->sub_size[s], ps + poff[s], (size_t)(poff[s + 1] - poff[s]), dst, room);
+            return qlfc_encode_pstream(form, PstreamJob{Lo->first_seen + 256 * (size_t)s, Lo->nsym[s], Lo->sub_size[s], ps + poff[s], (size_t)(poff[s + 1] - poff[s]), dst, room});
         }
     } enc;
-    enc.Lo = Lo; enc.s0 = s0; enc.ps = ps; enc.poff = poff; enc.fast = coder == LIBBSC_CODER_QLFC_FAST;
+    enc.Lo = Lo; enc.s0 = s0; enc.ps = ps; enc.poff = poff; enc.form = coder == LIBBSC_CODER_QLFC_FAST ? BSCGPU_RC_FAST16 : BSCGPU_RC_STATIC16;
     return coder_compress_views(views, nb, Lo->sub_start + s0, Lo->sub_size + s0, Lo->sizes[block], out, coder, features, fetch, &enc);
 }
 extern "C" BSCGPU_API int bscgpu_front_batch_code_ps(const bscgpu_front_layout* Lo, int block, const uint16_t* ps, const uint32_t* poff,
@@ -1794,7 +1790,7 @@ extern "C" BSCGPU_API int bscgpu_front_batch_code_ps(const bscgpu_front_layout* 
 {
     return front_batch_code_stream(Lo, block, ps, poff, out, LIBBSC_CODER_QLFC_STATIC, features);
 }
-// ... for the fast coder (-e0): the sub-blocks' streams in the BSCGPU_RC_FAST16 form, coded by qlfc_encode_fast_pstream
+// ... for the fast coder (-e0): the sub-blocks' streams in the BSCGPU_RC_FAST16 form
 extern "C" BSCGPU_API int bscgpu_front_batch_code_psf(const bscgpu_front_layout* Lo, int block, const uint16_t* ps, const uint32_t* poff,
                                                       unsigned char* out, int features)
 {

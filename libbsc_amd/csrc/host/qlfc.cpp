@@ -142,16 +142,6 @@ public:
         L.low  += (uint64_t)(r & m);
         L.range = next_range(L.range, r, bit);
     }
-    // the same, keeping `is_full` (= full(), which only changes inside shift()) in a caller's register: the run-start budget test of
-    // the p-stream coders costs three loads and a compare per decision otherwise
-    template <int P> __attribute__((always_inline)) inline void encode_live_f(Live& L, unsigned bit, int p, unsigned& is_full)
-    {
-        if (__builtin_expect(L.range < 0x10000u, 0)) { low_ = L.low; shift(); L.low = low_; L.range <<= 16; is_full = (unsigned)full(); }
-        const uint32_t r = (L.range >> P) * (uint32_t)p;
-        const uint32_t m = 0u - bit;
-        L.low  += (uint64_t)(r & m);
-        L.range = next_range(L.range, r, bit);
-    }
     template <int P> __attribute__((always_inline)) inline void encode(unsigned bit, int p)
     {
         if (__builtin_expect(range_ < 0x10000u, 0)) { shift(); range_ <<= 16; }
@@ -160,7 +150,9 @@ public:
         low_  += (uint64_t)(r & m);
         range_ = next_range(range_, r, bit);
     }
-    // precision picked per decision (the fast coder behind the device model: 13 bits on the rank side, 11 on the run side)
+    // encode_live with the precision picked per decision (the fast coder behind the device model: 13 bits on the rank side, 11 on the
+    // run side; a constant for the static coder's streams), keeping `is_full` (= full(), which only changes inside shift()) in a
+    // caller's register: the run-start budget test of the p-stream coders costs three loads and a compare per decision otherwise
     __attribute__((always_inline)) inline void encode_live_var(Live& L, unsigned bit, unsigned p, unsigned prec, unsigned& is_full)
     {
         if (__builtin_expect(L.range < 0x10000u, 0)) { low_ = L.low; shift(); L.low = low_; L.range <<= 16; is_full = (unsigned)full(); }
@@ -172,7 +164,7 @@ public:
     inline void encode_half(unsigned bit) { encode<12>(bit, 2048); }     // rangecoder.h:179-182
     void encode_word(uint32_t w) { for (int b = 31; b >= 0; --b) encode_half((w >> b) & 1u); }
 
-    // the output half of shift() for a coder whose low word lives elsewhere (qlfc_encode_static_pstream_x8):
+    // the output half of shift() for a coder whose low word lives elsewhere (encode_pstream_x8):
     // top16 = bits 16..31 of low, carry = bit 32
     inline void emit_unit(uint32_t top16, uint32_t carry)
     {
@@ -899,29 +891,6 @@ int qlfc_decode_block_bounded(const uint8_t* in, long long in_size, uint8_t* out
 // the reference's entry point carries no input size (qlfc.h:58): the caller vouches for the stream
 int qlfc_decode_block(const uint8_t* in, uint8_t* out, int coder) { return qlfc_decode_block_bounded(in, UNBOUNDED_INPUT, out, coder, 0x7fffffff); }
 
-// The static coder's back half alone: the probabilities come from the GPU (devcoder.hip), in stream order, with the first
-// decision of every run marked so that the output-budget test sits where the reference has it (qlfc.cpp:894).
-int qlfc_encode_static_pstream(const uint8_t* first_seen, int nsym, int in_size, const uint16_t* ps, size_t count, uint8_t* out, int out_size)
-{
-    if (in_size <= 0 || nsym <= 0) return BAD_PARAMETER;
-    RunView H; H.nsym = nsym; memcpy(H.first_seen, first_seen, (size_t)nsym);
-    RangeEncoder rc;
-    rc.init(out, out_size);
-    rc.encode_word((uint32_t)in_size);
-    (void)encode_alphabet(H, [&](unsigned b) { rc.encode_half(b); });
-    RangeEncoder::Live L = rc.enter();
-    unsigned is_full = (unsigned)rc.full();                             // full() looks at the output cursor only: kept current by encode_live_f
-    for (size_t i = 0; i < count; ++i) {
-        const unsigned x = ps[i];
-        // one test that practically never fires instead of a branch on the run-start mark itself (which is set on every third or fourth
-        // decision, irregularly: mispredicted, it cost this loop more than its arithmetic)
-        if (__builtin_expect(((x >> 13) & is_full) != 0u, 0)) return NOT_COMPRESSIBLE;
-        rc.encode_live_f<12>(L, (x >> 12) & 1u, (int)(x & 0xfffu), is_full);
-    }
-    rc.leave(L);
-    return rc.finish();
-}
-
 // The device model's CPU stand-in: the host model's own walk with a policy that records what the range coder would have been given —
 // {[11:0] p, [12] bit, [13] first decision of a run}, the entries devcoder.hip writes — instead of coding it.  Returns the number of
 // decisions; entries past cap are counted, not written.
@@ -951,53 +920,163 @@ int64_t qlfc_static_pstream_runs(const RunView& R, uint16_t* out, int64_t cap)
     return pol.n;
 }
 
-void qlfc_encode_static_pstream_pair(const PstreamJob& A, const PstreamJob& B, int* resA, int* resB)
+// ------------------------------------------------------------------------------------------------
+// The back half alone, behind the device model: the probabilities come from the GPU (devcoder.hip) as a stream of entries in stream
+// order, one per decision; the host writes the header and the alphabet and range-codes the entries.  Three entry forms
+// (include/bscgpu.h BSCGPU_RC_*), three task shapes (one stream, two interleaved, eight SIMD lanes); every loop below is written once
+// and instantiated per form.
+//
+// PsForm<FORM> is the only place that knows an entry's bit layout (a contract with devcoder.hip / devcoder_model.h):
+//   STATIC16  {[11:0] probability, [12] coded bit, [13] first decision of a run}: the static coder (-e1).  The run-start mark puts the
+//             output-budget test where the reference has it (qlfc.cpp:894).
+//   STATIC13  the same packed (devcoder.hip DcP13): field i at bits [13 i, 13 i + 13) of the sub-block's stream, little endian,
+//             {probability[11:0], coded bit}, eight decisions in 13 bytes.  There is no run-start mark: a stream whose budget is reached
+//             at ANY decision gives up (NOT_COMPRESSIBLE), and the caller redoes the block on the host model from the run arrays — which
+//             is what it does for every sub-block that does not compress, and which reproduces the reference's decision exactly.
+//   FAST16    {[12:0] probability, [13] coded bit, [14] first decision of a run, [15] run side}: the fast coder (-e0).  One counter per
+//             decision, so an entry IS the probability; its precision follows the side of the run the decision belongs to (13 bits, on the
+//             run side 11), and the alphabet header's bits go out at precision 1 (qlfc.cpp:1174).  The budget test sits on the run-start
+//             mark as in encode_model2 (qlfc.cpp:1191).
+// Members: at(body, first) the stream that begins at decision `first` of a body; get(ps, i) entry i (the packed form reads 4 bytes: up
+// to 3 past the stream, the landing zones have that slack) and get_exact, which reads no byte the stream does not own; mark(x) whose
+// bit 0 says that the budget is tested in front of x (the bits above it mean nothing); bit(x), prob(x), prec(x) the decision as
+// RangeEncoder::encode_live_var takes it (decoded where the step is called, not in a member that wraps the step: behind a wrapper the
+// compiler moved the precision's arithmetic behind the renormalisation test and into byte registers, 1.6 % on the fast form's loops);
+// header_bit(...) a bit of the alphabet header.
+// ------------------------------------------------------------------------------------------------
+template <int FORM> struct PsForm;
+struct PsEntries16 {                                                 // 16-bit entries: a load
+    static BSC_ALWAYS_INLINE const void* at(const void* body, int64_t first) { return static_cast<const uint16_t*>(body) + first; }
+    static BSC_ALWAYS_INLINE unsigned get(const void* ps, size_t i) { return static_cast<const uint16_t*>(ps)[i]; }
+    static BSC_ALWAYS_INLINE unsigned get_exact(const void* ps, size_t i) { return get(ps, i); }
+};
+struct PsStaticEntry {                                              // the static coder's decision, either width: 12-bit probability, the bit above it
+    static BSC_ALWAYS_INLINE unsigned bit(unsigned x) { return (x >> 12) & 1u; }
+    static BSC_ALWAYS_INLINE unsigned prob(unsigned x) { return x & 0xfffu; }
+    static BSC_ALWAYS_INLINE unsigned prec(unsigned) { return 12u; }
+    static BSC_ALWAYS_INLINE void header_bit(RangeEncoder& rc, unsigned b) { rc.encode_half(b); }
+};
+template <> struct PsForm<BSCGPU_RC_STATIC16> : PsEntries16, PsStaticEntry {
+    static constexpr bool fast = false, packed = false;
+    static BSC_ALWAYS_INLINE unsigned mark(unsigned x) { return x >> 13; }
+};
+template <> struct PsForm<BSCGPU_RC_STATIC13> : PsStaticEntry {
+    static constexpr bool fast = false, packed = true;
+    static BSC_ALWAYS_INLINE const void* at(const void* body, int64_t first) { return static_cast<const uint8_t*>(body) + first / 8 * 13; }      // first: a multiple of 8
+    static BSC_ALWAYS_INLINE unsigned get(const void* ps, size_t i)
+    {
+        const size_t bit = i * 13u;
+        uint32_t w; memcpy(&w, static_cast<const uint8_t*>(ps) + (bit >> 3), 4);
+        return (w >> (bit & 7u)) & 0x1fffu;
+    }
+    static BSC_ALWAYS_INLINE unsigned get_exact(const void* ps, size_t i)
+    {
+        const uint8_t* b = static_cast<const uint8_t*>(ps);
+        const size_t bit = i * 13u, at = bit >> 3;
+        const unsigned sh = (unsigned)(bit & 7u);
+        uint32_t w = (uint32_t)b[at] | ((uint32_t)b[at + 1] << 8);
+        if (sh + 13u > 16u) w |= (uint32_t)b[at + 2] << 16;
+        return (w >> sh) & 0x1fffu;
+    }
+    static BSC_ALWAYS_INLINE unsigned mark(unsigned) { return 1u; }                   // no mark: tested at every decision
+};
+template <> struct PsForm<BSCGPU_RC_FAST16> : PsEntries16 {
+    static constexpr bool fast = true, packed = false;
+    static BSC_ALWAYS_INLINE unsigned mark(unsigned x) { return x >> 14; }
+    static BSC_ALWAYS_INLINE unsigned bit(unsigned x) { return (x >> 13) & 1u; }
+    static BSC_ALWAYS_INLINE unsigned prob(unsigned x) { return x & 0x1fffu; }
+    static BSC_ALWAYS_INLINE unsigned prec(unsigned x) { return 13u - ((x >> 15) << 1); }
+    static BSC_ALWAYS_INLINE void header_bit(RangeEncoder& rc, unsigned b) { rc.encode<1>(b, 1); }
+};
+
+// a stream's prologue: the header word and the alphabet
+template <int FORM>
+static void ps_begin(RangeEncoder& rc, const PstreamJob& J)
 {
-    RunView HA, HB;
-    HA.nsym = A.nsym; memcpy(HA.first_seen, A.first_seen, (size_t)A.nsym);
-    HB.nsym = B.nsym; memcpy(HB.first_seen, B.first_seen, (size_t)B.nsym);
+    RunView H; H.nsym = J.nsym; memcpy(H.first_seen, J.first_seen, (size_t)J.nsym);
+    rc.init(J.out, J.out_size);
+    rc.encode_word((uint32_t)J.in_size);
+    (void)encode_alphabet(H, [&](unsigned b) { PsForm<FORM>::header_bit(rc, b); });
+}
+
+// Entries [from, count) of one stream; false: the stream stopped at its output budget (NOT_COMPRESSIBLE).  is_full = rc.full(), which
+// looks at the output cursor only: kept current by the encoder steps.
+template <int FORM>
+static BSC_ALWAYS_INLINE bool ps_code(RangeEncoder& rc, RangeEncoder::Live& L, unsigned& is_full, const void* ps, size_t from, size_t count)
+{
+    using F = PsForm<FORM>;
+    for (size_t i = from; i < count; ++i) {
+        const unsigned x = F::get(ps, i);
+        // one test that practically never fires instead of a branch on the run-start mark itself (which is set on every third or fourth
+        // decision, irregularly: mispredicted, it cost this loop more than its arithmetic)
+        if (__builtin_expect((F::mark(x) & is_full) != 0u, 0)) return false;
+        rc.encode_live_var(L, F::bit(x), F::prob(x), F::prec(x), is_full);
+    }
+    return true;
+}
+
+// (not inlined into the entry points' switches: a loop keeps the registers of a function of its own)
+template <int FORM>
+static __attribute__((noinline)) int encode_pstream(const PstreamJob& J)
+{
+    if (J.in_size <= 0 || J.nsym <= 0) return BAD_PARAMETER;
+    RangeEncoder rc;
+    ps_begin<FORM>(rc, J);
+    RangeEncoder::Live L = rc.enter();
+    unsigned is_full = (unsigned)rc.full();
+    if (!ps_code<FORM>(rc, L, is_full, J.ps, 0, J.count)) return NOT_COMPRESSIBLE;
+    rc.leave(L);
+    return rc.finish();
+}
+
+// Two independent streams in one loop (the recurrence range -> shift -> multiply -> select is latency bound: two chains in flight).
+template <int FORM>
+static __attribute__((noinline)) void encode_pstream_pair(const PstreamJob& A, const PstreamJob& B, int* resA, int* resB)
+{
+    using F = PsForm<FORM>;
     RangeEncoder ra, rb;
-    ra.init(A.out, A.out_size); rb.init(B.out, B.out_size);
-    ra.encode_word((uint32_t)A.in_size); rb.encode_word((uint32_t)B.in_size);
-    (void)encode_alphabet(HA, [&](unsigned b) { ra.encode_half(b); });
-    (void)encode_alphabet(HB, [&](unsigned b) { rb.encode_half(b); });
+    ps_begin<FORM>(ra, A); ps_begin<FORM>(rb, B);
     RangeEncoder::Live La = ra.enter(), Lb = rb.enter();
-    const uint16_t* pa = A.ps; const uint16_t* pb = B.ps;
+    const void* const pa = A.ps; const void* const pb = B.ps;
     const size_t both = A.count < B.count ? A.count : B.count;
     size_t i = 0;
     bool fa = false, fb = false;                              // a stream ran out of budget (reference: NOT_COMPRESSIBLE at a run start)
-    unsigned fulla = (unsigned)ra.full(), fullb = (unsigned)rb.full();     // kept current by encode_live_f
+    unsigned fulla = (unsigned)ra.full(), fullb = (unsigned)rb.full();
     for (; i < both; ++i) {
-        const unsigned x = pa[i], y = pb[i];
-        // branch-free test (the budget check belongs to run starts only, qlfc.cpp:894; it practically never fires)
-        const unsigned stop = ((x >> 13) & fulla) | ((y >> 13) & fullb);
-        if (__builtin_expect(stop != 0, 0)) {
-            if ((x & 0x2000u) && fulla) { fa = true; break; }
-            fb = true; break;
-        }
-        ra.encode_live_f<12>(La, (x >> 12) & 1u, (int)(x & 0xfffu), fulla);
-        rb.encode_live_f<12>(Lb, (y >> 12) & 1u, (int)(y & 0xfffu), fullb);
+        const unsigned x = F::get(pa, i), y = F::get(pb, i);
+        // branch-free test, as in ps_code
+        const unsigned stopa = F::mark(x) & fulla, stopb = F::mark(y) & fullb;
+        if (__builtin_expect((stopa | stopb) != 0u, 0)) { if (stopa) fa = true; else fb = true; break; }
+        ra.encode_live_var(La, F::bit(x), F::prob(x), F::prec(x), fulla);
+        rb.encode_live_var(Lb, F::bit(y), F::prob(y), F::prec(y), fullb);
     }
     // what is left of either stream, singly
-    if (!fa) for (size_t k = i; k < A.count; ++k) { const unsigned x = pa[k]; if ((x & 0x2000u) && fulla) { fa = true; break; } ra.encode_live_f<12>(La, (x >> 12) & 1u, (int)(x & 0xfffu), fulla); }
-    if (!fb) for (size_t k = i; k < B.count; ++k) { const unsigned y = pb[k]; if ((y & 0x2000u) && fullb) { fb = true; break; } rb.encode_live_f<12>(Lb, (y >> 12) & 1u, (int)(y & 0xfffu), fullb); }
+    if (!fa) fa = !ps_code<FORM>(ra, La, fulla, pa, i, A.count);
+    if (!fb) fb = !ps_code<FORM>(rb, Lb, fullb, pb, i, B.count);
     ra.leave(La); rb.leave(Lb);
     *resA = fa ? NOT_COMPRESSIBLE : ra.finish();
     *resB = fb ? NOT_COMPRESSIBLE : rb.finish();
 }
 
-// ---- the packed stream (round 6; devcoder.hip DcP13): 13 bits per decision, eight decisions in 13 bytes -------------------------------
-// field i at bits [13 i, 13 i + 13) of the sub-block's stream, little endian: {probability[11:0], coded bit}.  There is no run-start mark:
-// the reference tests its output budget at run starts only (qlfc.cpp:894), here a stream whose budget is reached at ANY decision gives up
-// (NOT_COMPRESSIBLE), and the caller redoes the block on the host model from the run arrays — which is what it does for every sub-block that
-// does not compress, and which reproduces the reference's decision exactly.  (A 4-byte read at the last field reaches 3 bytes past the
-// stream: the landing zones have that slack.)
-static inline unsigned p13_get(const uint8_t* b, size_t i)
+int qlfc_encode_pstream(int form, const PstreamJob& J)
 {
-    const size_t bit = i * 13u;
-    uint32_t w; memcpy(&w, b + (bit >> 3), 4);
-    return (w >> (bit & 7u)) & 0x1fffu;
+    switch (form) {
+        case BSCGPU_RC_STATIC16: return encode_pstream<BSCGPU_RC_STATIC16>(J);
+        case BSCGPU_RC_STATIC13: return encode_pstream<BSCGPU_RC_STATIC13>(J);
+        case BSCGPU_RC_FAST16:   return encode_pstream<BSCGPU_RC_FAST16>(J);
+    }
+    return BAD_PARAMETER;
 }
+void qlfc_encode_pstream_pair(int form, const PstreamJob& A, const PstreamJob& B, int* resA, int* resB)
+{
+    switch (form) {
+        case BSCGPU_RC_STATIC16: return encode_pstream_pair<BSCGPU_RC_STATIC16>(A, B, resA, resB);
+        case BSCGPU_RC_STATIC13: return encode_pstream_pair<BSCGPU_RC_STATIC13>(A, B, resA, resB);
+        case BSCGPU_RC_FAST16:   return encode_pstream_pair<BSCGPU_RC_FAST16>(A, B, resA, resB);
+    }
+    *resA = *resB = BAD_PARAMETER;
+}
+
 void qlfc_pack_p13(const uint16_t* ps, size_t count, uint8_t* out)
 {
     const size_t bytes = (count + 7) / 8 * 13;
@@ -1007,108 +1086,6 @@ void qlfc_pack_p13(const uint16_t* ps, size_t count, uint8_t* out)
         const uint32_t f = ((uint32_t)ps[i] & 0x1fffu) << (bit & 7u);
         out[bit >> 3] |= (uint8_t)f; out[(bit >> 3) + 1] |= (uint8_t)(f >> 8); if (f >> 16) out[(bit >> 3) + 2] |= (uint8_t)(f >> 16);
     }
-}
-int qlfc_encode_static_p13(const uint8_t* first_seen, int nsym, int in_size, const uint8_t* ps, size_t count, uint8_t* out, int out_size)
-{
-    if (in_size <= 0 || nsym <= 0) return BAD_PARAMETER;
-    RunView H; H.nsym = nsym; memcpy(H.first_seen, first_seen, (size_t)nsym);
-    RangeEncoder rc;
-    rc.init(out, out_size);
-    rc.encode_word((uint32_t)in_size);
-    (void)encode_alphabet(H, [&](unsigned b) { rc.encode_half(b); });
-    RangeEncoder::Live L = rc.enter();
-    unsigned is_full = (unsigned)rc.full();
-    for (size_t i = 0; i < count; ++i) {
-        if (__builtin_expect(is_full != 0u, 0)) return NOT_COMPRESSIBLE;
-        const unsigned x = p13_get(ps, i);
-        rc.encode_live_f<12>(L, x >> 12, (int)(x & 0xfffu), is_full);
-    }
-    rc.leave(L);
-    return rc.finish();
-}
-void qlfc_encode_static_p13_pair(const PstreamJob& A, const PstreamJob& B, int* resA, int* resB)
-{
-    RunView HA, HB;
-    HA.nsym = A.nsym; memcpy(HA.first_seen, A.first_seen, (size_t)A.nsym);
-    HB.nsym = B.nsym; memcpy(HB.first_seen, B.first_seen, (size_t)B.nsym);
-    RangeEncoder ra, rb;
-    ra.init(A.out, A.out_size); rb.init(B.out, B.out_size);
-    ra.encode_word((uint32_t)A.in_size); rb.encode_word((uint32_t)B.in_size);
-    (void)encode_alphabet(HA, [&](unsigned b) { ra.encode_half(b); });
-    (void)encode_alphabet(HB, [&](unsigned b) { rb.encode_half(b); });
-    RangeEncoder::Live La = ra.enter(), Lb = rb.enter();
-    const uint8_t* pa = (const uint8_t*)A.ps; const uint8_t* pb = (const uint8_t*)B.ps;
-    const size_t both = A.count < B.count ? A.count : B.count;
-    size_t i = 0;
-    bool fa = false, fb = false;
-    unsigned fulla = (unsigned)ra.full(), fullb = (unsigned)rb.full();
-    for (; i < both; ++i) {
-        if (__builtin_expect((fulla | fullb) != 0u, 0)) { if (fulla) fa = true; else fb = true; break; }
-        const unsigned x = p13_get(pa, i), y = p13_get(pb, i);
-        ra.encode_live_f<12>(La, x >> 12, (int)(x & 0xfffu), fulla);
-        rb.encode_live_f<12>(Lb, y >> 12, (int)(y & 0xfffu), fullb);
-    }
-    if (!fa) for (size_t k = i; k < A.count; ++k) { if (fulla) { fa = true; break; } const unsigned x = p13_get(pa, k); ra.encode_live_f<12>(La, x >> 12, (int)(x & 0xfffu), fulla); }
-    if (!fb) for (size_t k = i; k < B.count; ++k) { if (fullb) { fb = true; break; } const unsigned y = p13_get(pb, k); rb.encode_live_f<12>(Lb, y >> 12, (int)(y & 0xfffu), fullb); }
-    ra.leave(La); rb.leave(Lb);
-    *resA = fa ? NOT_COMPRESSIBLE : ra.finish();
-    *resB = fb ? NOT_COMPRESSIBLE : rb.finish();
-}
-
-// The fast coder (-e0) behind the device model: one counter per decision, so an entry IS the probability; what differs from the
-// static coder's stream is the precision, which follows the side of the run the decision belongs to (bit 15), and the alphabet header,
-// whose bits go out at precision 1 (qlfc.cpp:1174).  The budget test sits on the run-start mark as in encode_model2 (qlfc.cpp:1191).
-static inline unsigned psf_prec(unsigned x) { return 13u - ((x >> 15) << 1); }
-int qlfc_encode_fast_pstream(const uint8_t* first_seen, int nsym, int in_size, const uint16_t* ps, size_t count, uint8_t* out, int out_size)
-{
-    if (in_size <= 0 || nsym <= 0) return BAD_PARAMETER;
-    RunView H; H.nsym = nsym; memcpy(H.first_seen, first_seen, (size_t)nsym);
-    RangeEncoder rc;
-    rc.init(out, out_size);
-    rc.encode_word((uint32_t)in_size);
-    (void)encode_alphabet(H, [&](unsigned b) { rc.encode<1>(b, 1); });
-    RangeEncoder::Live L = rc.enter();
-    unsigned is_full = (unsigned)rc.full();
-    for (size_t i = 0; i < count; ++i) {
-        const unsigned x = ps[i];
-        if (__builtin_expect(((x >> 14) & is_full) != 0u, 0)) return NOT_COMPRESSIBLE;
-        rc.encode_live_var(L, (x >> 13) & 1u, x & 0x1fffu, psf_prec(x), is_full);
-    }
-    rc.leave(L);
-    return rc.finish();
-}
-
-void qlfc_encode_fast_pstream_pair(const PstreamJob& A, const PstreamJob& B, int* resA, int* resB)
-{
-    RunView HA, HB;
-    HA.nsym = A.nsym; memcpy(HA.first_seen, A.first_seen, (size_t)A.nsym);
-    HB.nsym = B.nsym; memcpy(HB.first_seen, B.first_seen, (size_t)B.nsym);
-    RangeEncoder ra, rb;
-    ra.init(A.out, A.out_size); rb.init(B.out, B.out_size);
-    ra.encode_word((uint32_t)A.in_size); rb.encode_word((uint32_t)B.in_size);
-    (void)encode_alphabet(HA, [&](unsigned b) { ra.encode<1>(b, 1); });
-    (void)encode_alphabet(HB, [&](unsigned b) { rb.encode<1>(b, 1); });
-    RangeEncoder::Live La = ra.enter(), Lb = rb.enter();
-    const uint16_t* pa = A.ps; const uint16_t* pb = B.ps;
-    const size_t both = A.count < B.count ? A.count : B.count;
-    size_t i = 0;
-    bool fa = false, fb = false;
-    unsigned fulla = (unsigned)ra.full(), fullb = (unsigned)rb.full();
-    for (; i < both; ++i) {
-        const unsigned x = pa[i], y = pb[i];
-        const unsigned stop = ((x >> 14) & fulla) | ((y >> 14) & fullb);
-        if (__builtin_expect((stop & 1u) != 0, 0)) {
-            if ((x & 0x4000u) && fulla) { fa = true; break; }
-            fb = true; break;
-        }
-        ra.encode_live_var(La, (x >> 13) & 1u, x & 0x1fffu, psf_prec(x), fulla);
-        rb.encode_live_var(Lb, (y >> 13) & 1u, y & 0x1fffu, psf_prec(y), fullb);
-    }
-    if (!fa) for (size_t k = i; k < A.count; ++k) { const unsigned x = pa[k]; if ((x & 0x4000u) && fulla) { fa = true; break; } ra.encode_live_var(La, (x >> 13) & 1u, x & 0x1fffu, psf_prec(x), fulla); }
-    if (!fb) for (size_t k = i; k < B.count; ++k) { const unsigned y = pb[k]; if ((y & 0x4000u) && fullb) { fb = true; break; } rb.encode_live_var(Lb, (y >> 13) & 1u, y & 0x1fffu, psf_prec(y), fullb); }
-    ra.leave(La); rb.leave(Lb);
-    *resA = fa ? NOT_COMPRESSIBLE : ra.finish();
-    *resB = fb ? NOT_COMPRESSIBLE : rb.finish();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1406,36 +1383,42 @@ static int x8_prefetch_entries()
     static const int env = [] { const char* e = getenv("BSC_RC_PREFETCH"); return e ? atoi(e) : 256; }();      // 512 bytes ahead: -2 % (104 -> 102 -> 96 ms per block with the new step)
     return g_x8_prefetch_override >= 0 ? g_x8_prefetch_override : env;
 }
-template <bool FAST, bool P13 = false>
-static bool encode_pstream_x8(const PstreamJob* J, int* res)
-{
 #if defined(__AVX2__)
-    RunView H;
-    RangeEncoder rc[8];
-    size_t common = ~(size_t)0;
-    for (int l = 0; l < 8; ++l) {
-        H.nsym = J[l].nsym; memcpy(H.first_seen, J[l].first_seen, (size_t)J[l].nsym);
-        rc[l].init(J[l].out, J[l].out_size);
-        rc[l].encode_word((uint32_t)J[l].in_size);
-        if (FAST) (void)encode_alphabet(H, [&](unsigned b) { rc[l].template encode<1>(b, 1); });
-        else      (void)encode_alphabet(H, [&](unsigned b) { rc[l].encode_half(b); });
-        if (J[l].count < common) common = J[l].count;
-    }
-    X8State S;
-    for (int l = 0; l < 8; ++l) { const RangeEncoder::Live L = rc[l].enter(); S.R[l] = L.range; S.LO[l] = (uint32_t)L.low; S.CY[l] = (uint32_t)(L.low >> 32); }
-    static const bool use512 = [] {
+static bool x8_use_avx512()                                          // BSC_RC_AVX512=0: the AVX2 step
+{
+    static const bool use = [] {
         if (const char* e = getenv("BSC_RC_AVX512")) return atoi(e) != 0 && __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512vl");
         return __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512vl");
     }();
-
-    // The VBMI form of the packed stream's unpacking: on by default on AMD hosts that have it (EPYC 9575F: the eight-lane task 101.6 -> 96.0 ms
-    // per block, against 94.3 on 16-bit entries); off by default elsewhere — on the Xeon of the build container the 512-bit permutes
-    // among 256-bit steps cost 40 % (1.03 -> 1.46 ns per decision).  BSC_RC_VBMI=1 / 0 overrides.
-    static const bool use_vbmi = [] {
+    return use;
+}
+// The VBMI form of the packed stream's unpacking: on by default on AMD hosts that have it (EPYC 9575F: the eight-lane task 101.6 -> 96.0 ms
+// per block, against 94.3 on 16-bit entries); off by default elsewhere — on the Xeon of the build container the 512-bit permutes
+// among 256-bit steps cost 40 % (1.03 -> 1.46 ns per decision).  BSC_RC_VBMI=1 / 0 overrides.
+static bool x8_use_vbmi()
+{
+    static const bool use = [] {
         const bool have = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512vl") && __builtin_cpu_supports("avx512bw") && __builtin_cpu_supports("avx512vbmi");
         if (const char* e = getenv("BSC_RC_VBMI")) return atoi(e) != 0 && have;
         return have && __builtin_cpu_is("amd");
     }();
+    return use;
+}
+#endif
+template <int FORM>
+static bool encode_pstream_x8(const PstreamJob* J, int* res)
+{
+#if defined(__AVX2__)
+    constexpr bool FAST = PsForm<FORM>::fast, P13 = PsForm<FORM>::packed;
+    RangeEncoder rc[8];
+    size_t common = ~(size_t)0;
+    for (int l = 0; l < 8; ++l) {
+        ps_begin<FORM>(rc[l], J[l]);
+        if (J[l].count < common) common = J[l].count;
+    }
+    X8State S;
+    for (int l = 0; l < 8; ++l) { const RangeEncoder::Live L = rc[l].enter(); S.R[l] = L.range; S.LO[l] = (uint32_t)L.low; S.CY[l] = (uint32_t)(L.low >> 32); }
+    const bool use512 = x8_use_avx512(), use_vbmi = P13 && x8_use_vbmi();
     const size_t pf = (size_t)x8_prefetch_entries();
     const int vsel = x8_vector_select();
     constexpr size_t CHUNK = 32768;                                  // steps between two replays of the log (1 MiB of records at most)
@@ -1443,14 +1426,14 @@ static bool encode_pstream_x8(const PstreamJob* J, int* res)
     if (!log_mem) log_mem.reset(new uint32_t[CHUNK * 8 + 16]);
     uint32_t* const log0 = log_mem.get();
 
-    const uint16_t* ps[8];
-    for (int l = 0; l < 8; ++l) ps[l] = J[l].ps;
+    const uint16_t* ps[8];                                           // (the vector steps take either form behind this type)
+    for (int l = 0; l < 8; ++l) ps[l] = static_cast<const uint16_t*>(J[l].ps);
     size_t i = 0;
     while (i + 8 <= common) {
         size_t end = i + CHUNK; if (end > common) end = common;
         end = i + ((end - i) & ~(size_t)7);
         uint32_t* const logp = !use512 ? x8_steps_avx2<FAST, P13>(S, ps, i, end, log0, pf)
-                             : (P13 && use_vbmi) ? (vsel != 0 ? x8_steps_avx512_vbmi<2>(S, ps, i, end, log0, pf) : x8_steps_avx512_vbmi<0>(S, ps, i, end, log0, pf))
+                             : use_vbmi ? (vsel != 0 ? x8_steps_avx512_vbmi<2>(S, ps, i, end, log0, pf) : x8_steps_avx512_vbmi<0>(S, ps, i, end, log0, pf))
                              : vsel != 0 ? x8_steps_avx512<FAST, 2, P13>(S, ps, i, end, log0, pf) : x8_steps_avx512<FAST, 0, P13>(S, ps, i, end, log0, pf);
         i = end;
         for (const uint32_t* q = log0; q < logp; ++q) {              // replay: the only code that touches the outputs
@@ -1461,31 +1444,13 @@ static bool encode_pstream_x8(const PstreamJob* J, int* res)
         }
     }
     for (int l = 0; l < 8; ++l) if (rc[l].full()) return false;
-    // the rest of every stream on its own (they differ in length by a few per cent), with the run-start test of the scalar coder
+    // the rest of every stream on its own (they differ in length by a few per cent), with the budget test of the scalar coder
     for (int l = 0; l < 8; ++l) {
         RangeEncoder::Live L{(uint64_t)S.LO[l] | ((uint64_t)S.CY[l] << 32), S.R[l]};
-        bool failed = false;
-        const uint16_t* q = ps[l];
         unsigned is_full = (unsigned)rc[l].full();
-        if (P13) {
-            for (size_t k = i; k < J[l].count; ++k) {
-                if (__builtin_expect(is_full != 0u, 0)) { failed = true; break; }
-                const unsigned x = p13_get((const uint8_t*)q, k);
-                rc[l].template encode_live_f<12>(L, x >> 12, (int)(x & 0xfffu), is_full);
-            }
-        } else
-        for (size_t k = i; k < J[l].count; ++k) {
-            const unsigned x = q[k];
-            if (FAST) {
-                if (__builtin_expect(((x >> 14) & is_full) != 0u, 0)) { failed = true; break; }
-                rc[l].encode_live_var(L, (x >> 13) & 1u, x & 0x1fffu, psf_prec(x), is_full);
-            } else {
-                if (__builtin_expect(((x >> 13) & is_full) != 0u, 0)) { failed = true; break; }
-                rc[l].template encode_live_f<12>(L, (x >> 12) & 1u, (int)(x & 0xfffu), is_full);
-            }
-        }
+        const bool fits = ps_code<FORM>(rc[l], L, is_full, J[l].ps, i, J[l].count);
         rc[l].leave(L);
-        res[l] = failed ? NOT_COMPRESSIBLE : rc[l].finish();
+        res[l] = fits ? rc[l].finish() : NOT_COMPRESSIBLE;
     }
     return true;
 #else
@@ -1493,9 +1458,15 @@ static bool encode_pstream_x8(const PstreamJob* J, int* res)
     return false;
 #endif
 }
-bool qlfc_encode_static_pstream_x8(const PstreamJob* J, int* res) { return encode_pstream_x8<false>(J, res); }
-bool qlfc_encode_static_p13_x8(const PstreamJob* J, int* res) { return encode_pstream_x8<false, true>(J, res); }
-bool qlfc_encode_fast_pstream_x8(const PstreamJob* J, int* res) { return encode_pstream_x8<true>(J, res); }
+bool qlfc_encode_pstream_x8(int form, const PstreamJob* J, int* res)
+{
+    switch (form) {
+        case BSCGPU_RC_STATIC16: return encode_pstream_x8<BSCGPU_RC_STATIC16>(J, res);
+        case BSCGPU_RC_STATIC13: return encode_pstream_x8<BSCGPU_RC_STATIC13>(J, res);
+        case BSCGPU_RC_FAST16:   return encode_pstream_x8<BSCGPU_RC_FAST16>(J, res);
+    }
+    return false;
+}
 
 int qlfc_encode_runs(const RunView& R, int in_size, uint8_t* out, int out_size, int coder)
 {
@@ -1518,13 +1489,18 @@ int qlfc_encode_block(const uint8_t* in, uint8_t* out, int in_size, int out_size
 
 // ---- the range coder as a stage: many streams of plain entries (include/bscgpu.h) ----------------------------------------
 // CPU stand-in of csrc/device/rangecoder.hip: the same streams through the RangeEncoder above, one after the other.
-static inline unsigned p13_get_exact(const uint8_t* b, size_t i)      // p13_get without the read past the field's last byte
+// A stream's entries with the stage's own bound `no_room` in front of each; false: the stream ended at a bound.
+template <int FORM, class NoRoom>
+static BSC_ALWAYS_INLINE bool rc_stream_entries(RangeEncoder& rc, RangeEncoder::Live& L, unsigned& is_full, NoRoom&& no_room, const void* body, const bscgpu_rc_stream& S)
 {
-    const size_t bit = i * 13u, at = bit >> 3;
-    const unsigned sh = (unsigned)(bit & 7u);
-    uint32_t w = (uint32_t)b[at] | ((uint32_t)b[at + 1] << 8);
-    if (sh + 13u > 16u) w |= (uint32_t)b[at + 2] << 16;
-    return (w >> sh) & 0x1fffu;
+    using F = PsForm<FORM>;
+    const void* ps = F::at(body, S.body);
+    for (uint32_t i = 0; i < S.count; ++i) {
+        const unsigned x = F::get_exact(ps, i);
+        if ((F::mark(x) & is_full) || no_room()) return false;
+        rc.encode_live_var(L, F::bit(x), F::prob(x), F::prec(x), is_full);
+    }
+    return true;
 }
 
 static int rc_stream_host(int form, const void* body, const uint32_t* prefix, const bscgpu_rc_stream& S, uint8_t* out)
@@ -1541,23 +1517,13 @@ static int rc_stream_host(int form, const void* body, const uint32_t* prefix, co
         if (no_room()) return NOT_COMPRESSIBLE;
         rc.encode_live_var(L, (e >> 24) & 1u, e & 0xffffu, (e >> 16) & 31u, is_full);
     }
-    if (form == BSCGPU_RC_STATIC13) {
-        const uint8_t* ps = static_cast<const uint8_t*>(body) + S.body / 8 * 13;
-        for (uint32_t i = 0; i < S.count; ++i) {
-            if (is_full || no_room()) return NOT_COMPRESSIBLE;
-            const unsigned x = p13_get_exact(ps, i);
-            rc.encode_live_f<12>(L, x >> 12, (int)(x & 0xfffu), is_full);
-        }
-    } else {
-        const uint16_t* ps = static_cast<const uint16_t*>(body) + S.body;
-        const bool fast = form == BSCGPU_RC_FAST16;
-        for (uint32_t i = 0; i < S.count; ++i) {
-            const unsigned x = ps[i];
-            if ((((x >> (fast ? 14 : 13)) & 1u) & is_full) || no_room()) return NOT_COMPRESSIBLE;
-            if (fast) rc.encode_live_var(L, (x >> 13) & 1u, x & 0x1fffu, psf_prec(x), is_full);
-            else      rc.encode_live_f<12>(L, (x >> 12) & 1u, (int)(x & 0xfffu), is_full);
-        }
+    bool fits = false;
+    switch (form) {
+        case BSCGPU_RC_STATIC16: fits = rc_stream_entries<BSCGPU_RC_STATIC16>(rc, L, is_full, no_room, body, S); break;
+        case BSCGPU_RC_STATIC13: fits = rc_stream_entries<BSCGPU_RC_STATIC13>(rc, L, is_full, no_room, body, S); break;
+        case BSCGPU_RC_FAST16:   fits = rc_stream_entries<BSCGPU_RC_FAST16>(rc, L, is_full, no_room, body, S); break;
     }
+    if (!fits) return NOT_COMPRESSIBLE;
     rc.leave(L);
     if (rc.committed() + 8 > region) return NOT_COMPRESSIBLE;
     return rc.finish();
@@ -1573,7 +1539,7 @@ extern "C" BSCGPU_API int bscgpu_rc_prefix(const unsigned char* first_seen, int 
     int n = 0;
     auto put = [&](unsigned bit, unsigned prec, unsigned p) { if (entries && n < cap) entries[n] = p | (prec << 16) | (bit << 24); ++n; };
     for (int b = 31; b >= 0; --b) put(((uint32_t)in_size >> b) & 1u, 12, 2048);                 // RangeEncoder::encode_word
-    if (coder == CODER_FAST) (void)encode_alphabet(H, [&](unsigned b) { put(b, 1, 1); });       // encode<1>(b, 1): qlfc_encode_fast_pstream
+    if (coder == CODER_FAST) (void)encode_alphabet(H, [&](unsigned b) { put(b, 1, 1); });       // encode<1>(b, 1): PsForm<BSCGPU_RC_FAST16>::header_bit
     else                     (void)encode_alphabet(H, [&](unsigned b) { put(b, 12, 2048); });   // encode_half
     return (entries && n > cap) ? BAD_PARAMETER : n;
 }

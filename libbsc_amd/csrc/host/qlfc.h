@@ -59,34 +59,28 @@ void qlfc_runs(const uint8_t* in, int n, QlfcRuns& out);
 
 // Encode one sub-block from its run arrays.  Returns bytes written or NOT_COMPRESSIBLE.
 int qlfc_encode_runs(const RunView& R, int in_size, uint8_t* out, int out_size, int coder);
-// Static coder (-e1) from a precomputed probability stream (devcoder_model.h: [11:0] p, [12] bit, [13] run start): header,
-// alphabet and range coding only — the model ran on the GPU.  Returns bytes written or NOT_COMPRESSIBLE.
-int qlfc_encode_static_pstream(const uint8_t* first_seen, int nsym, int in_size, const uint16_t* ps, size_t count, uint8_t* out, int out_size);
-// The static model's probability stream of one sub-block on the CPU (the device model's stand-in: the host model's walk, recording
-// instead of coding): entries as above to out[0 .. cap); returns the number of decisions (those past cap are counted only).
-int64_t qlfc_static_pstream_runs(const RunView& R, uint16_t* out, int64_t cap);
+// The coders' back half behind the device model: header, alphabet and range coding only, from a stream of entries (one per decision)
+// that the GPU computed.  `form` is the entry form, BSCGPU_RC_STATIC16 / _STATIC13 / _FAST16 (include/bscgpu.h; the bit layouts are at
+// qlfc.cpp PsForm): the static coder's (-e1) 16-bit entries, the same packed into 13 bits (eight decisions in 13 bytes, no run-start mark:
+// a stream that reaches its budget anywhere returns NOT_COMPRESSIBLE / false and the block is redone on the host model), and the fast
+// coder's (-e0, qlfc.cpp:1135-1336) 16-bit entries with per-entry precision; header and alphabet as the respective host coder writes them.
+// ps points at the sub-block's first entry (packed form: at its bytes).
+struct PstreamJob { const uint8_t* first_seen; int nsym; int in_size; const void* ps; size_t count; uint8_t* out; int out_size; };
+// One stream.  Returns bytes written or NOT_COMPRESSIBLE.
+int  qlfc_encode_pstream(int form, const PstreamJob& J);
 // Two independent sub-blocks coded in one loop: the range coder's recurrence (range -> shift -> multiply -> select) is latency
-// bound, two chains in flight nearly double a core's rate (1.9 -> 1.1 ns per decision on an EPYC 9575F).  res[k] as above.
-struct PstreamJob { const uint8_t* first_seen; int nsym; int in_size; const uint16_t* ps; size_t count; uint8_t* out; int out_size; };
-void qlfc_encode_static_pstream_pair(const PstreamJob& A, const PstreamJob& B, int* resA, int* resB);
-// Eight sub-blocks, one per AVX2 lane (J[8], res[8]).  false = not done (a stream reached its output budget, or no AVX2):
-// the caller codes the sub-blocks with the functions above.
-bool qlfc_encode_static_pstream_x8(const PstreamJob* J, int* res);
-// The packed stream (devcoder.hip DcP13): 13 bits per decision {probability[11:0], coded bit}, eight decisions in 13 bytes, no run-start
-// mark (a stream that reaches its budget anywhere returns NOT_COMPRESSIBLE / false and the block is redone on the host model).  PstreamJob::ps
-// then points at the packed bytes.  qlfc_pack_p13 makes the packed form of a 16-bit stream (tests, tools): out has (count + 7) / 8 * 13 bytes.
-int  qlfc_encode_static_p13(const uint8_t* first_seen, int nsym, int in_size, const uint8_t* ps, size_t count, uint8_t* out, int out_size);
-void qlfc_encode_static_p13_pair(const PstreamJob& A, const PstreamJob& B, int* resA, int* resB);
-bool qlfc_encode_static_p13_x8(const PstreamJob* J, int* res);
+// bound, two chains in flight nearly double a core's rate (1.9 -> 1.1 ns per decision on an EPYC 9575F).  *resA, *resB as above.
+void qlfc_encode_pstream_pair(int form, const PstreamJob& A, const PstreamJob& B, int* resA, int* resB);
+// Eight sub-blocks, one per AVX2 lane (J[8], res[8]; the fast form with per-lane precision).  false = not done (a stream reached its
+// output budget, or no AVX2): the caller codes the sub-blocks with the functions above.
+bool qlfc_encode_pstream_x8(int form, const PstreamJob* J, int* res);
+// qlfc_pack_p13 makes the packed form of a 16-bit stream (tests, tools): out has (count + 7) / 8 * 13 bytes.
 void qlfc_pack_p13(const uint16_t* ps, size_t count, uint8_t* out);
-// The fast coder's back half (-e0, qlfc.cpp:1135-1336) behind the device model: entries {[12:0] probability, [13] bit, [14] first
-// decision of a run, [15] run side = 11-bit precision, else 13} (devcoder_model.h PSF_*); header and alphabet as encode_model2 writes them.
-int qlfc_encode_fast_pstream(const uint8_t* first_seen, int nsym, int in_size, const uint16_t* ps, size_t count, uint8_t* out, int out_size);
-// The fast model's probability stream of one sub-block on the CPU (the device model's stand-in: encode_model2's walk, recording instead
-// of coding): entries as above to out[0 .. cap); returns the number of decisions (those past cap are counted only).
+// The static / fast model's probability stream of one sub-block on the CPU (the device model's stand-in: the host model's walk /
+// encode_model2's walk, recording instead of coding): 16-bit entries to out[0 .. cap); returns the number of decisions (those past
+// cap are counted only).
+int64_t qlfc_static_pstream_runs(const RunView& R, uint16_t* out, int64_t cap);
 int64_t qlfc_fast_pstream_runs(const RunView& R, uint16_t* out, int64_t cap);
-void qlfc_encode_fast_pstream_pair(const PstreamJob& A, const PstreamJob& B, int* resA, int* resB);
-bool qlfc_encode_fast_pstream_x8(const PstreamJob* J, int* res);      // eight sub-blocks in SIMD lanes, per-lane precision (as qlfc_encode_static_pstream_x8)
 // Encode one sub-block (what coder.cpp:61 dispatches to).  Returns bytes written or NOT_COMPRESSIBLE.
 int qlfc_encode_block(const uint8_t* in, uint8_t* out, int in_size, int out_size, int coder);
 // Decode one sub-block; returns the decoded size or an error.

@@ -527,7 +527,7 @@ def _rerun_with_env(selection, **env):
 
 
 def test_simd_range_coder_mode(torch_cuda):
-    """The opt-in eight-lane range coder (qlfc_encode_static_pstream_x8) end to end: eight-sub-block inputs, the 64 MiB golden
+    """The opt-in eight-lane range coder (qlfc_encode_pstream_x8) end to end: eight-sub-block inputs, the 64 MiB golden
     block and the pipelined path, in a child process with BSC_RC_SIMD=8."""
     _rerun_with_env("eight_sub_block_inputs or full_size_64m_block_golden or pipe_matches_sync_path", BSC_RC_SIMD="8")
 
@@ -687,7 +687,7 @@ def test_lzp_blocks_take_the_device_model_and_survive_a_redo(ref, torch_cuda):
 def test_fast_coder_on_the_device_model(ref, torch_cuda):
     """-e0 (qlfc.cpp:1135-1336) behind the device model: its one counter per decision is the static coder's char family with shift
     updates (devcoder.hip: dc_fast_run; the chain model is pinned on CPU by tools/devcoder_fast_sim.cpp), the host codes the
-    13- / 11-bit entries (qlfc_encode_fast_pstream).  Text with 2, 4 and 8 sub-blocks, 256-symbol data (all 7-bit rank exponents), long
+    13- / 11-bit entries (qlfc_encode_pstream, BSCGPU_RC_FAST16).  Text with 2, 4 and 8 sub-blocks, 256-symbol data (all 7-bit rank exponents), long
     runs (run-length mantissas of more than 5 bits: the second rate class), a block with a raw sub-block (redo on the host model) and an
     LZP block; synchronous and pipelined, both framings; bytes = the reference's, and the counters say the device model ran."""
     import ctypes as C

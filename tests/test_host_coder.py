@@ -123,11 +123,12 @@ def test_native_library_exports_every_declared_symbol():
 
 
 def test_avx2_eight_lane_range_coder_matches_scalar(tmp_path):
-    """qlfc_encode_static_pstream_x8 / qlfc_encode_fast_pstream_x8 (eight sub-block streams in SIMD lanes, renormalisation log) against
+    """qlfc_encode_pstream_x8 in its three entry forms (eight sub-block streams in SIMD lanes, renormalisation log) against
     the scalar coders fed by the same probability streams: byte-identical outputs, and it must give up (never mis-code) when a stream
     reaches its output budget.  Every step the product can run is covered — round 5's AVX-512VL step, round 4's (BSC_RC_VSEL=0), the AVX2
     step (BSC_RC_AVX512=0) where the CPU has them — at stream lengths below one step, around it and across the replay chunk, built with
     g++ and with the product's own host compiler (the select in RangeEncoder::next_range is compiler-specific).
+    The two-stream coder with one output too small must report, for either stream and in every form, what the single-stream coder does.
     tools/rc_x8_check.cpp compiles the host coder directly (no test hook in the product library)."""
     import os
     import subprocess
@@ -148,6 +149,7 @@ def test_avx2_eight_lane_range_coder_matches_scalar(tmp_path):
                 assert "packed stream: equal" in r.stdout, (cxx, extra, size, r.stdout + r.stderr)       # round 6: 13 bits per decision (single, pair, eight lanes)
                 if size == "400000":
                     assert "gave up" in r.stdout            # the budget case bails out to the scalar coders
+                    assert "pair, one output too small (three forms): equal" in r.stdout, (cxx, extra, size, r.stdout + r.stderr)
 
 
 @pytest.mark.parametrize("nphys", [1, 2, 4, 8])
@@ -226,7 +228,7 @@ def test_coder_task_shape_rule():
 
 def test_fast_coder_chain_model_matches_the_host_coder(tmp_path):
     """The fast coder (-e0) as the device runs it — chains (decision type, symbol) with the shift updates of dcm::model_params_fast,
-    entries of 13 / 11 bits, qlfc_encode_fast_pstream and its pair version — walked serially on the CPU: the bytes must be those of
+    entries of 13 / 11 bits, qlfc_encode_pstream in the fast form and its pair version — walked serially on the CPU: the bytes must be those of
     the host's own fast coder, which the tests above pin to the reference (tools/devcoder_fast_sim.cpp; random bytes, long runs,
     text-like and one-symbol data, with room and at the format's budget out_size = in_size)."""
     import os

@@ -3,7 +3,7 @@
 // The device runs the fast coder as chains (sub-block, decision type, symbol) with the update maps of dcm::model_params_fast and hands
 // the host 16-bit entries (devcoder_model.h PSF_*).  Here the same chains are walked serially: decisions by dcm::enumerate with
 // max_rank 7, counters in a table indexed by (type, symbol) starting from ModelParams::init, dcm::step as the update, the entry
-// stream coded by qlfc_encode_fast_pstream (and the pair coder) — and the bytes must be those of the host's own fast coder
+// stream coded by qlfc_encode_pstream in the fast form (and the pair coder) — and the bytes must be those of the host's own fast coder
 // (encode_model2, which the CPU tests pin to the reference).  Also checks nth_decision against enumerate at max_rank 7.
 //   fast_sim --trace IN OUT   writes the entry stream of the sub-block in file IN (uint16, little endian) to OUT and nothing else: the fast
 //                             coder's trace on the CPU, for tests of the range coder stage (tests/test_rc_streams_host.py)
@@ -83,18 +83,18 @@ int main(int argc, char** argv)
             const int osz = budget_mode ? (int)in.size() : (int)want.size() - 64;                               // the format's budget: out_size = in_size
             const int rw = qlfc_encode_runs(R.view, (int)in.size(), want.data(), osz, CODER_FAST);
             const std::vector<uint16_t> ps = chain_stream(R.view, M, &bad);
-            const int rg = qlfc_encode_fast_pstream(R.view.first_seen, R.view.nsym, (int)in.size(), ps.data(), ps.size(), got.data(), osz);
+            const int rg = qlfc_encode_pstream(BSCGPU_RC_FAST16, PstreamJob{R.view.first_seen, R.view.nsym, (int)in.size(), ps.data(), ps.size(), got.data(), osz});
             PstreamJob A{R.view.first_seen, R.view.nsym, (int)in.size(), ps.data(), ps.size(), got2.data(), osz};
             PstreamJob B{R.view.first_seen, R.view.nsym, (int)in.size(), ps.data(), ps.size() / 2, got.data() + 0, osz};   // (B's output is not looked at)
             std::vector<uint8_t> scratchB(want.size()); B.out = scratchB.data();
             int r2 = 0, r3 = 0;
-            qlfc_encode_fast_pstream_pair(A, B, &r2, &r3);
+            qlfc_encode_pstream_pair(BSCGPU_RC_FAST16, A, B, &r2, &r3);
             ++cases;
             if (rw != rg || (rw > 0 && memcmp(want.data(), got.data(), (size_t)rw) != 0)) { ++bad; printf("MISMATCH n %zu budget %d: host %d chains %d\n", in.size(), budget_mode, rw, rg); }
             if (rw != r2 || (rw > 0 && memcmp(want.data(), got2.data(), (size_t)rw) != 0)) { ++bad; printf("PAIR MISMATCH n %zu budget %d: host %d pair %d\n", in.size(), budget_mode, rw, r2); }
         }
     }
-    {   // eight streams in SIMD lanes (qlfc_encode_fast_pstream_x8) against eight single coders; then with one output too small: it must give up
+    {   // eight streams in SIMD lanes (qlfc_encode_pstream_x8) against eight single coders; then with one output too small: it must give up
         std::vector<std::vector<uint16_t>> ps(8); std::vector<QlfcRuns> R(8);
         const size_t pick[8] = {2, 5, 8, 11, 1, 4, 7, 10};
         for (int l = 0; l < 8; ++l) { qlfc_runs(inputs[pick[l]].data(), (int)inputs[pick[l]].size(), R[l]); ps[l] = chain_stream(R[l].view, M, &bad); }
@@ -104,10 +104,10 @@ int main(int argc, char** argv)
                 const size_t n = inputs[pick[l]].size();
                 const int osz = (mode == 1 && l == 0) ? 4096 : (int)n * 2 + 4096;      // lane 0 = 600 000 random bytes: far beyond 4 KB
                 oa[l].assign((size_t)osz + 64, 0); ob[l].assign((size_t)osz + 64, 0);
-                ra[l] = qlfc_encode_fast_pstream(R[l].view.first_seen, R[l].view.nsym, (int)n, ps[l].data(), ps[l].size(), oa[l].data(), osz);
+                ra[l] = qlfc_encode_pstream(BSCGPU_RC_FAST16, PstreamJob{R[l].view.first_seen, R[l].view.nsym, (int)n, ps[l].data(), ps[l].size(), oa[l].data(), osz});
                 J[l] = PstreamJob{R[l].view.first_seen, R[l].view.nsym, (int)n, ps[l].data(), ps[l].size(), ob[l].data(), osz};
             }
-            const bool ok = qlfc_encode_fast_pstream_x8(J, rb);
+            const bool ok = qlfc_encode_pstream_x8(BSCGPU_RC_FAST16, J, rb);
             ++cases;
             if (mode == 1) { if (ra[0] >= 0 || (ok && rb[0] >= 0)) { ++bad; printf("x8: a stream past its budget was not noticed (%d, %d)\n", ra[0], rb[0]); } else printf("x8 budget case: %s\n", ok ? "coded, lane 0 NOT_COMPRESSIBLE" : "gave up"); continue; }
             if (!ok) { ++bad; printf("x8 gave up with roomy outputs\n"); continue; }

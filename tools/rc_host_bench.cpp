@@ -61,7 +61,7 @@ int main(int argc, char** argv)
         else { volatile unsigned long long sink = 0; for (size_t i = 0; i < evict.size(); i += 64) sink = sink + evict[i]; }
     };
     int refres[8];
-    { PstreamJob J[8]; jobs(plain.data(), J, ref); for (int b = 0; b < 8; ++b) refres[b] = qlfc_encode_static_pstream(J[b].first_seen, J[b].nsym, J[b].in_size, J[b].ps, J[b].count, J[b].out, J[b].out_size); }
+    { PstreamJob J[8]; jobs(plain.data(), J, ref); for (int b = 0; b < 8; ++b) refres[b] = qlfc_encode_pstream(BSCGPU_RC_STATIC16, J[b]); }
     long long total = 0; for (int b = 0; b < 8; ++b) total += refres[b] > 0 ? refres[b] : 0;
     printf("coded: %lld bytes over eight sub-blocks\n", total);
     int bad = 0;
@@ -79,7 +79,7 @@ int main(int argc, char** argv)
                 make_cold(pin != 0);
                 g_x8_prefetch_override = 256; g_x8_vsel_override = vsel;
                 const double t0 = now_ms();
-                const bool ok = qlfc_encode_static_pstream_x8(J, r);
+                const bool ok = qlfc_encode_pstream_x8(BSCGPU_RC_STATIC16, J, r);
                 const double ms = now_ms() - t0;
                 if (!ok) { printf("x8 gave up\n"); ++bad; break; }
                 if (rep == 0) check("x8", r);
@@ -101,7 +101,7 @@ int main(int argc, char** argv)
                 make_cold(pin != 0);
                 g_x8_prefetch_override = pf;
                 const double t0 = now_ms();
-                const bool ok = qlfc_encode_static_pstream_x8(J, r);
+                const bool ok = qlfc_encode_pstream_x8(BSCGPU_RC_STATIC16, J, r);
                 const double ms = now_ms() - t0;
                 if (!ok) { printf("x8 gave up\n"); ++bad; break; }
                 if (rep == 0) check("x8", r);
@@ -115,7 +115,7 @@ int main(int argc, char** argv)
                 PstreamJob J[8]; jobs(base, J, out); int r[8];
                 make_cold(pin != 0);
                 const double t0 = now_ms();
-                for (int b = 0; b < 8; b += 2) qlfc_encode_static_pstream_pair(J[b], J[b + 1], &r[b], &r[b + 1]);
+                for (int b = 0; b < 8; b += 2) qlfc_encode_pstream_pair(BSCGPU_RC_STATIC16, J[b], J[b + 1], &r[b], &r[b + 1]);
                 const double ms = now_ms() - t0;
                 if (rep == 0) check("pairs", r);
                 if (ms < best) best = ms;
@@ -128,7 +128,7 @@ int main(int argc, char** argv)
                 PstreamJob J[8]; jobs(base, J, out); int r[8];
                 make_cold(pin != 0);
                 const double t0 = now_ms();
-                for (int b = 0; b < 8; ++b) r[b] = qlfc_encode_static_pstream(J[b].first_seen, J[b].nsym, J[b].in_size, J[b].ps, J[b].count, J[b].out, J[b].out_size);
+                for (int b = 0; b < 8; ++b) r[b] = qlfc_encode_pstream(BSCGPU_RC_STATIC16, J[b]);
                 const double ms = now_ms() - t0;
                 if (rep == 0) check("singles", r);
                 if (ms < best) best = ms;
@@ -150,7 +150,7 @@ int main(int argc, char** argv)
         if (hipMalloc((void**)&d13, bytes13) != hipSuccess || hipMemcpy(d13, pin13, bytes13, hipMemcpyHostToDevice) != hipSuccess) return 1;
         printf("== packed stream (13 bits per decision): %zu bytes against %lld as 16-bit entries; pinned landing zone, written by DMA before every run\n", bytes13, (long long)D * 2);
         auto jobs13 = [&](PstreamJob* J, std::vector<uint8_t>* o) {
-            for (int b = 0; b < 8; ++b) J[b] = PstreamJob{first_seen, 96, sub_size[b], reinterpret_cast<const uint16_t*>(pin13 + (size_t)pbase[b] / 8 * 13), (size_t)(poff[b + 1] - poff[b]), o[b].data(), sub_size[b]};
+            for (int b = 0; b < 8; ++b) J[b] = PstreamJob{first_seen, 96, sub_size[b], pin13 + (size_t)pbase[b] / 8 * 13, (size_t)(poff[b + 1] - poff[b]), o[b].data(), sub_size[b]};
         };
         auto cold13 = [&] { if (hipMemcpy(pin13, d13, bytes13, hipMemcpyDeviceToHost) != hipSuccess) exit(1); };
         for (int shape = 8; shape >= 1; shape = shape == 8 ? 2 : shape == 2 ? 1 : 0) {
@@ -160,9 +160,9 @@ int main(int argc, char** argv)
                 cold13();
                 g_x8_prefetch_override = 256; g_x8_vsel_override = -1;
                 const double t0 = now_ms();
-                if (shape == 8) { if (!qlfc_encode_static_p13_x8(J, r)) { printf("packed x8 gave up\n"); ++bad; break; } }
-                else if (shape == 2) for (int b = 0; b < 8; b += 2) qlfc_encode_static_p13_pair(J[b], J[b + 1], &r[b], &r[b + 1]);
-                else for (int b = 0; b < 8; ++b) r[b] = qlfc_encode_static_p13(J[b].first_seen, J[b].nsym, J[b].in_size, reinterpret_cast<const uint8_t*>(J[b].ps), J[b].count, J[b].out, J[b].out_size);
+                if (shape == 8) { if (!qlfc_encode_pstream_x8(BSCGPU_RC_STATIC13, J, r)) { printf("packed x8 gave up\n"); ++bad; break; } }
+                else if (shape == 2) for (int b = 0; b < 8; b += 2) qlfc_encode_pstream_pair(BSCGPU_RC_STATIC13, J[b], J[b + 1], &r[b], &r[b + 1]);
+                else for (int b = 0; b < 8; ++b) r[b] = qlfc_encode_pstream(BSCGPU_RC_STATIC13, J[b]);
                 const double ms = now_ms() - t0;
                 if (rep == 0) check(shape == 8 ? "packed x8" : shape == 2 ? "packed pairs" : "packed singles", r);
                 if (ms < best) best = ms;
@@ -198,7 +198,7 @@ int main(int argc, char** argv)
                         PstreamJob J[8]; int r[8];
                         for (int b = 0; b < 8; ++b) J[b] = PstreamJob{first_seen, 96, sub_size[b], zone[t] + poff[b], (size_t)(poff[b + 1] - poff[b]), o[(size_t)t * 8 + b].data(), sub_size[b]};
                         const double t0 = now_ms();
-                        okk[t] = qlfc_encode_static_pstream_x8(J, r);
+                        okk[t] = qlfc_encode_pstream_x8(BSCGPU_RC_STATIC16, J, r);
                         ms[t] = now_ms() - t0;
                         for (int b = 0; b < 8; ++b) if (r[b] != refres[b]) okk[t] = false;
                     });
