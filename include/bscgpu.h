@@ -298,6 +298,42 @@ BSCGPU_API int bscgpu_model_segment_facts_device(bscgpu_ctx* ctx, const void* dL
 BSCGPU_API int64_t bscgpu_pstream_batch_segments_device(bscgpu_ctx* ctx, const void* dL, const int* sizes, int count, bscgpu_front_layout* layout,
                                                         int coder, int64_t target, uint16_t* out, int64_t cap, uint32_t* poff, int* blk_state);
 
+/* ---- the packed 13-bit stream of a pass (-e1; DESIGN §2b, "The packed stream of a pass") ------------------------------------------
+ * The static coder's stream of a pass in the form bscgpu_qlfc_static_pstream_packed writes for a block, over up to 8192 sub-blocks:
+ * 13 bits per decision, {[11:0] probability, [12] coded bit}, eight decisions in 13 bytes (field e of a group at bits
+ * [13 e, 13 e + 13), little endian).  Sub-block s starts at decision pbase[s] of the packed space: pbase[0] = 0, pbase[s + 1] =
+ * pbase[s] + (poff[s + 1] - poff[s] rounded up to a multiple of 64), i.e. at byte pbase[s] / 8 * 13; behind a sub-block's last
+ * decision its extent is zero.  The stream is pbase[nsub] / 8 * 13 bytes, every one of them written.  A sub-block is a
+ * BSCGPU_RC_STATIC13 body at pbase[s] (bscgpu_rc_stream::body) for every range coder of this library.
+ * bscgpu_static_pstream_batch_packed_device: bscgpu_static_pstream_batch_device with the stream in this form.  out[0 .. cap_bytes);
+ *   poff[nsub + 1] as there, pbase[nsub + 1].  Returns the number of decisions; nothing is copied when pbase[nsub] / 8 * 13 >
+ *   cap_bytes (poff and pbase are filled all the same).  LIBBSC_NOT_SUPPORTED when the device declines the pass
+ *   (BSCGPU_CNT_DC_LAST_FAIL says why) and also, with BSCGPU_CNT_DC_LAST_FAIL = 0, when the packed form was void: 64 consecutive runs
+ *   with more decisions than a wavefront stages (runs of thousands) — the 16-bit stage still serves such a pass.  Synchronous.
+ *   Memory: as the 16-bit stage, + 66 KB of tables.
+ * bscgpu_pstream_pack13_host: the CPU stand-in for the layout, a pure function: packs 16-bit static entries (ps, sub-block s's at
+ *   [poff[s], poff[s + 1])) into out and fills pbase[nsub + 1].  Returns the byte count pbase[nsub] / 8 * 13; above cap_bytes nothing
+ *   is written but pbase.  LIBBSC_BAD_PARAMETER: null pointers, nsub < 0, poff not non-decreasing.
+ * bscgpu_front_batch_code_ps13: bscgpu_front_batch_code_ps reading BSCGPU_RC_STATIC13 bodies (packed / poff / pbase as above).  One
+ *   difference: the packed coder gives up at ANY decision once its output is full, the reference at a run start, so a sub-block
+ *   whose packed stream ends LIBBSC_NOT_COMPRESSIBLE is coded again by the host model from its runs, and the reference's own answer
+ *   decides between "compressed" and "stored raw" — never the packed coder's word alone.  Output byte-equal to
+ *   bscgpu_front_batch_code.  Thread-safe for different blocks of one layout.
+ * bscgpu_pstream_batch_segments_packed_device: bscgpu_pstream_batch_segments_device for -e1 in this form (any other coder:
+ *   LIBBSC_BAD_PARAMETER).  out[0 .. cap_bytes): the kept segments' packed streams back to back; pbase runs on across segments in
+ *   kept order and a sub-block that was not modelled has pbase[s + 1] == pbase[s] (and poff[s + 1] == poff[s]).  Above cap_bytes:
+ *   counted, not copied.  A segment whose packed form is void is re-run in the 16-bit form internally and packed into place on the
+ *   host (bscgpu_pstream_pack13_host): the caller sees one form, the blocks keep the device's model, BSCGPU_CNT_BATCH_PACKED_VOID
+ *   counts it.  Returns the decisions written.  Everything else as the 16-bit stage. */
+BSCGPU_API int64_t bscgpu_static_pstream_batch_packed_device(bscgpu_ctx* ctx, const void* dL, const int* sizes, int count, bscgpu_front_layout* layout,
+                                                             uint8_t* out, int64_t cap_bytes, uint32_t* poff, int64_t* pbase);
+BSCGPU_API int64_t bscgpu_pstream_pack13_host(const uint16_t* ps, const uint32_t* poff, int nsub, uint8_t* out, int64_t cap_bytes, int64_t* pbase);
+BSCGPU_API int bscgpu_front_batch_code_ps13(const bscgpu_front_layout* layout, int block, const uint8_t* packed, const uint32_t* poff,
+                                            const int64_t* pbase, unsigned char* out, int features);
+BSCGPU_API int64_t bscgpu_pstream_batch_segments_packed_device(bscgpu_ctx* ctx, const void* dL, const int* sizes, int count, bscgpu_front_layout* layout,
+                                                               int coder, int64_t target, uint8_t* out, int64_t cap_bytes, uint32_t* poff,
+                                                               int64_t* pbase, int* blk_state);
+
 /* ---- batched decompression: one inverse-BWT pass for many blocks -------------
  * bscgpu_unbwt_batch_device: L of `count` blocks back to back in HBM (block b at Σ sizes[0..b), primary[b] its 1-based
  *   primary index) -> T in the same layout; dT may be dL.  Passes of consecutive blocks, at most max_n bytes and
@@ -545,6 +581,13 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          (Counted per block of the layout: with HBM input a block that rides along untransformed — stored, or left to
  *                          the single path — is planned like any other and counts here if the device leaves it out.)
  * BSCGPU_CNT_DC_DCAP       (get only) decisions the device model's arena holds for this context (a pass or segment above it cannot be modelled).
+ * BSCGPU_OPT_BATCH_MODEL_PACKED  0 (default) / 1: with BSCGPU_OPT_BATCH_MODEL on (with or without _SEGMENTS) and -e1, a pass's or a
+ *                          segment's stream is written and brought down in the packed 13-bit form (13 bytes per eight decisions instead
+ *                          of 16: the pinned landing buffers hold 16 / 13 as many decisions) and coded by bscgpu_front_batch_code_ps13;
+ *                          with BSCGPU_OPT_DEVICE_RC the device's range coder reads it as BSCGPU_RC_STATIC13.  A pass whose packed form
+ *                          is void goes down as 16-bit entries.  -e0, -e2, the L route and single blocks are not affected.  Same output.
+ * BSCGPU_CNT_BATCH_PACKED_PASSES, BSCGPU_CNT_BATCH_PACKED_VOID  (get only) passes or segments of this context that went down packed, and
+ *                          those whose packed form was void and went down as 16-bit entries.
  * set returns the previous value or a negative libbsc error code; get the value or a negative error code. */
 enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACKED_STREAM = 4,
        BSCGPU_CNT_DC_REPLAYS = 5, BSCGPU_CNT_DC_LAST_FAIL = 6, BSCGPU_CNT_DC_AVG_UNDECIDED = 7, BSCGPU_CNT_DC_HIST_EXTENDED = 8,
@@ -554,7 +597,8 @@ enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACK
        BSCGPU_OPT_BATCH_MODEL_FAST = 17, BSCGPU_CNT_BATCH_FAST_PASSES = 18, BSCGPU_CNT_BATCH_FAST_DECLINED = 19,
        BSCGPU_OPT_BWT_FOLD = 20, BSCGPU_CNT_BWT_FOLDED = 21,
        BSCGPU_OPT_BATCH_MODEL_SEGMENTS = 22, BSCGPU_CNT_BATCH_SEGMENTS = 23, BSCGPU_CNT_BATCH_SEG_RERUNS = 24,
-       BSCGPU_CNT_BATCH_SEG_HOST_BLOCKS = 25, BSCGPU_CNT_DC_DCAP = 26 };
+       BSCGPU_CNT_BATCH_SEG_HOST_BLOCKS = 25, BSCGPU_CNT_DC_DCAP = 26,
+       BSCGPU_OPT_BATCH_MODEL_PACKED = 27, BSCGPU_CNT_BATCH_PACKED_PASSES = 28, BSCGPU_CNT_BATCH_PACKED_VOID = 29 };
 /* _FAIL_AVG: undecided avg_rank flags; _FAIL_HIST: a run_hist bracket open after 9216 predecessors; _FAIL_CAP: more runs or decisions
  * than the context's arena holds; _FAIL_REPLAY: a chain whose bracket stayed open over more than 64 evaluation chunks. */
 enum { BSCGPU_DC_FAIL_AVG = 2, BSCGPU_DC_FAIL_HIST = 4, BSCGPU_DC_FAIL_CAP = 8, BSCGPU_DC_FAIL_REPLAY = 16 };

@@ -109,6 +109,13 @@ def lib():
     L.bscgpu_model_segment_facts_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, vp]
     L.bscgpu_pstream_batch_segments_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int64, vp, C.c_int64, vp, vp]
     L.bscgpu_pstream_batch_segments_device.restype = C.c_int64
+    L.bscgpu_static_pstream_batch_packed_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int64, vp, vp]
+    L.bscgpu_static_pstream_batch_packed_device.restype = C.c_int64
+    L.bscgpu_pstream_pack13_host.argtypes = [vp, vp, C.c_int, vp, C.c_int64, vp]
+    L.bscgpu_pstream_pack13_host.restype = C.c_int64
+    L.bscgpu_front_batch_code_ps13.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int]
+    L.bscgpu_pstream_batch_segments_packed_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int64, vp, C.c_int64, vp, vp, vp]
+    L.bscgpu_pstream_batch_segments_packed_device.restype = C.c_int64
     L.bscgpu_unbwt_batch_plan.argtypes = [vp, C.c_int, C.c_int64, vp]
     L.bscgpu_unbwt_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp]
     L.bscgpu_decompress_batch_sizes.argtypes = [vp, vp, C.c_int, vp]

@@ -356,6 +356,7 @@ extern "C" int bscgpu_option_set(bscgpu_ctx* c, int key, int value)
     if (key == BSCGPU_OPT_BATCH_MODEL && (value == 0 || value == 1)) { const int old = c->batch_model; c->batch_model = value; return old; }
     if (key == BSCGPU_OPT_BATCH_MODEL_FAST && (value == 0 || value == 1)) { const int old = c->batch_model_fast; c->batch_model_fast = value; return old; }
     if (key == BSCGPU_OPT_BATCH_MODEL_SEGMENTS && (value == 0 || value == 1)) { const int old = c->batch_model_segments; c->batch_model_segments = value; return old; }
+    if (key == BSCGPU_OPT_BATCH_MODEL_PACKED && (value == 0 || value == 1)) { const int old = c->batch_model_packed; c->batch_model_packed = value; return old; }
     if (key == BSCGPU_OPT_BWT_FOLD && value >= 0 && value <= 2) { const int old = c->bwt_fold; c->bwt_fold = value; return old; }
     return BSC_BAD_PARAMETER;
 }
@@ -385,6 +386,9 @@ extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
     if (key == BSCGPU_CNT_BATCH_SEG_RERUNS) return c->cnt_seg_reruns;
     if (key == BSCGPU_CNT_BATCH_SEG_HOST_BLOCKS) return c->cnt_seg_host_blocks;
     if (key == BSCGPU_CNT_DC_DCAP) { const int64_t v = devcoder_dcap(c); return v > 0x7fffffff ? 0x7fffffff : (int)v; }   // (saturates: max_n above ~512 MiB)
+    if (key == BSCGPU_OPT_BATCH_MODEL_PACKED) return c->batch_model_packed;
+    if (key == BSCGPU_CNT_BATCH_PACKED_PASSES) return c->cnt_packed_passes;
+    if (key == BSCGPU_CNT_BATCH_PACKED_VOID) return c->cnt_packed_void;
     if (key == BSCGPU_OPT_BWT_FOLD) return c->bwt_fold;
     if (key == BSCGPU_CNT_BWT_FOLDED) return c->cnt_bwt_folded;
     return BSC_BAD_PARAMETER;

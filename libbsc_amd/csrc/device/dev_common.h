@@ -131,6 +131,9 @@ struct bscgpu_ctx {
     // model segments (devcoder.hip: devcoder_pstream_segments; DESIGN §2b, "Model segments")
     int  batch_model_segments = 0;   // BSCGPU_OPT_BATCH_MODEL_SEGMENTS (default 0)
     int  cnt_seg = 0, cnt_seg_reruns = 0, cnt_seg_host_blocks = 0;   // BSCGPU_CNT_BATCH_SEGMENTS / _SEG_RERUNS / _SEG_HOST_BLOCKS
+    // the packed 13-bit stream of a pass ("The packed stream of a pass")
+    int  batch_model_packed = 0;     // BSCGPU_OPT_BATCH_MODEL_PACKED (default 0)
+    int  cnt_packed_passes = 0, cnt_packed_void = 0;                 // BSCGPU_CNT_BATCH_PACKED_PASSES / _VOID
     u16* model_host[2] = {nullptr, nullptr};   // pinned: a pass's probability stream coming down (two: coding overlaps the next pass), allocated on first use
     size_t model_host_entries = 0;
     bool model_host_failed = false;            // they could not be pinned: the route is off for this context
@@ -279,8 +282,13 @@ const u16* devcoder_pstream_ptr(const bscgpu_ctx* c, int psbuf = 0);
 // devcoder_batch_poff_ptr (device).  BSC_NOT_SUPPORTED: the pass is declined (c->dc_last_fail: BSCGPU_DC_FAIL_*; 0: an arena did not
 // fit).  Synchronous.  coder 3: the fast coder's (-e0) model of the pass — same inputs, same outputs with entries in the dcm::PSF_*
 // form, same exits (only FAIL_CAP and FAIL_REPLAY can be raised: this coder has no avg_rank flags and no run_hist look-back)
-int  devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, int coder /* 1 static (-e1), 3 fast (-e0) */, u32* D_out);
+// packed_out non-null (coder 1): the stream may be left in the packed 13-bit form of a pass ("The packed stream of a pass");
+// *packed_out = 1: it was — pbase[0..nsub] at devcoder_batch_pbase_ptr (device), *pbytes_out = pbase[nsub] / 8 * 13 bytes in the
+// stream buffer; 0: the packed form was void and the 2-byte entries are there instead
+int  devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, int coder /* 1 static (-e1), 3 fast (-e0) */, u32* D_out,
+                            int* packed_out = nullptr, int64_t* pbytes_out = nullptr);
 const u32* devcoder_batch_poff_ptr(const bscgpu_ctx* c);
+const u32* devcoder_batch_pbase_ptr(const bscgpu_ctx* c);
 // ... of a pass in model segments ("Model segments"): the same inputs plus the layout's blk_sub[count + 1] and
 // sub_run[nsub + 1] (host), coder 1 or 3, target decisions per segment (<= 0: the arena's capacity).  out[0 .. cap) (host): the kept
 // sub-blocks' entries back to back in sub-block order, poff[0..nsub] (host; a sub-block that was not modelled is empty), blk_state[b] =
@@ -297,8 +305,8 @@ struct DcSegNote {
     void* user;
 };
 int  devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub, int count, const u32* sub_run, int coder, int64_t target,
-                               u16* out, int64_t cap, bool per_segment_fit, u32* poff, int* blk_state, int64_t* D_out,
-                               const DcSegNote* note = nullptr);
+                               void* out, int64_t cap, bool per_segment_fit, u32* poff, int* blk_state, int64_t* D_out,
+                               const DcSegNote* note = nullptr, int64_t* pbase = nullptr /* non-null: the packed form, out / cap in bytes */);
 // ... the facts the plan is made of alone: dec[s] / und[s] (host, nsub entries each) of the pass qlfc_front_batch just laid out
 int  devcoder_segment_facts(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* dec, u32* und);
 int64_t devcoder_dcap(const bscgpu_ctx* c);             // decisions the device model's arena holds for this context

@@ -104,6 +104,8 @@ struct DevCoder {
     // model segments (devcoder_pstream_segments): per sub-block the undecided avg_rank flags and the decisions of the coder at hand,
     // and the run table of the segment being modelled, rebased to its first run
     u32 *sub_und = nullptr, *sub_dec = nullptr, *seg_run = nullptr;
+    // the packed stream of a pass or a segment (DcP13Tab): pad[s] and pbase[0 .. nsub] of the table at hand (dc_pbase_tab_kernel)
+    u32 *pad_tab = nullptr, *pbase_tab = nullptr;
     hipEvent_t seg_ev[2] = {nullptr, nullptr};                 // behind the last copy out of ps[0 / 1] on the copy stream
 };
 
@@ -1100,6 +1102,12 @@ typedef __attribute__((address_space(3))) volatile u16 dc_lds_vu16;
 // the tail record of the one and the head record of the other — no atomics, no zeroed buffer.
 struct DcFrag { u32 gidx; u32 slot_count; u16 e[8]; };               // group index (decisions / 8), first slot | count << 8 (count 0: none), the entries
 struct DcP13 { u32 pad[8]; u8* out; DcFrag* frag; };                 // pad[sb]: packed index of a decision = its index in the block's stream + pad[its sub-block]
+// ... of a batched pass or a segment: up to FRONT_MAX_SUB offsets, a table in HBM indexed by the table's sub-block id (dc_pbase_tab_kernel
+// writes it from poff, no host round trip); the index is wave-uniform wherever it is read, so the read is a scalar load
+struct DcP13Tab { const u32* pad; u8* out; DcFrag* frag; };
+template <class SB> struct DcP13Of;
+template <> struct DcP13Of<DcSub> { typedef DcP13 T; };
+template <> struct DcP13Of<DcSubTab> { typedef DcP13Tab T; };
 struct __attribute__((packed)) DcGroup13 { u32 a, b, c; u8 d; };
 __device__ __forceinline__ DcGroup13 dc_pack13(const u32 (&f)[8])
 {
@@ -1109,9 +1117,18 @@ __device__ __forceinline__ DcGroup13 dc_pack13(const u32 (&f)[8])
     return g;
 }
 // The wavefront's staged entries sg[0 .. wtotal) are the decisions wbase .. of the block's stream; loc / nd / sb / valid: this lane's run.
-__device__ __forceinline__ void dc_flush13(dc_lds_vu16* sg, const u32 wbase, const u32 lane, const u32 loc, const u32 nd, const u32 sb, const bool valid,
-                                           const DcP13& Q, const u32 wave_global)
+// The same walk serves a table (P13Q = DcP13Tab), where a wavefront of 64 runs can hold dozens of whole sub-blocks (blocks of a handful
+// of runs): every sub-block has at least one run, so the s2 loop trips once per sub-block present, each trip a piece that starts on its
+// sub-block's first decision — a multiple of 64 in the packed space — except the first.  Hence only the first piece can leave a head
+// record and only the last a tail record; every piece in between ends its sub-block and writes its own zero-padded last group.  The
+// whole zero groups behind a short sub-block's last group (its extent is padded to 64 decisions) are nobody's piece: dc_p13_fill_tab_kernel.
+// run_end: the run index behind the wavefront's last valid lane; sub_end(s): the run index behind sub-block s's last run.
+// Returns false where the piece cannot be recorded (below): the caller voids the packed stream.
+template <class P13Q, class SubEnd>
+__device__ __forceinline__ bool dc_flush13(dc_lds_vu16* sg, const u32 wbase, const u32 lane, const u32 loc, const u32 nd, const u32 sb, const bool valid,
+                                           const P13Q& Q, const u32 wave_global, const u32 run_end, SubEnd sub_end)
 {
+    bool ok = true;
     const u64 vmask = __ballot(valid);
     DcFrag head, tail; head.slot_count = 0; tail.slot_count = 0; head.gidx = 0; tail.gidx = 0;
 #pragma unroll
@@ -1142,6 +1159,11 @@ __device__ __forceinline__ void dc_flush13(dc_lds_vu16* sg, const u32 wbase, con
                 head.gidx = P0 >> 3; head.slot_count = (P0 & 7u) | (hcount << 8);
 #pragma unroll
                 for (int x = 0; x < 8; ++x) head.e[x] = (u32)x < hcount ? (u16)(sg[k0 + (u32)x] & 0x1fffu) : (u16)0;
+                // A head-only piece: the whole piece lies inside one group and does not reach its end.  The join writes a group from ONE
+                // tail and ONE head, so unless the sub-block ends here (the group's rest is padding) the next wavefront's head belongs to
+                // the same group and two threads of the join would write it, each without the other's entries.  Not reachable while every
+                // wavefront but a sub-block's last holds 64 runs of at least one decision each (8 < 64); kept so that it can never be silent.
+                if (hcount == len && ((P0 + len) & 7u) != 0u && s2 == sb_last && run_end != sub_end(s2)) ok = false;
             }
             // the fragment behind the last one: the next wavefront completes it — unless the sub-block ends here, then it is a whole (padded) group
             if (((P0 + len) & 7u) != 0u && (g_full1 << 3) >= P0) {
@@ -1167,6 +1189,7 @@ __device__ __forceinline__ void dc_flush13(dc_lds_vu16* sg, const u32 wbase, con
                     : q == 4u ? ((u32)r.e[4] | ((u32)r.e[5] << 16)) : ((u32)r.e[6] | ((u32)r.e[7] << 16));
         reinterpret_cast<u32*>(Q.frag + 2u * wave_global)[lane] = w;
     }
+    return ok;
 }
 // thread w: the group between wavefront w and w + 1 (tail of w, head of w + 1), and a head nobody's tail belongs to (never on blocks whose
 // wavefronts hold 64 runs; written for completeness)
@@ -1204,10 +1227,10 @@ __global__ __launch_bounds__(WG) void dc_p13_join_kernel(const DcFrag* __restric
 #endif
 template <bool FAST, bool P13, class SB>
 __global__ __launch_bounds__(WG, DC_PS_MINW) void dc_pstream_kernel(DcGather G, SB S, const ModelParams* __restrict__ mp,
-                                                        u32* __restrict__ meta, u16* __restrict__ out, u16* __restrict__ dbg /*[3][D] or null*/, u32 dbgD, DcP13 Q)
+                                                        u32* __restrict__ meta, u16* __restrict__ out, u16* __restrict__ dbg /*[3][D] or null*/, u32 dbgD,
+                                                        typename DcP13Of<SB>::T Q)
 {
     typedef DcForm<SB> F;
-    static_assert(!(P13 && F::TAB), "the packed stream is laid out by eight sub-blocks");
     const u32 mrp = F::maxr_word(S);                                  // max_rank of the eight sub-blocks, one scalar word
     __shared__ u16 stage[WAVES][DC_PS_STAGE];
     __shared__ short s_lr[NUM_CLS][4];                                // blend weights per class: an LDS read per decision instead of global loads at a per-lane address
@@ -1296,7 +1319,12 @@ __global__ __launch_bounds__(WG, DC_PS_MINW) void dc_pstream_kernel(DcGather G, 
         // (a piece that does not fit the staging buffer voids the packed stream: the host launches the 2-byte form for this block)
         if (!staged) { if (lane == 0u) atomicOr(&meta[DM_P13_OVER], 1u); }
         __builtin_amdgcn_wave_barrier();
-        if (staged) dc_flush13(sg, wbase, lane, loc, (u32)nd, (u32)it.sb, valid, Q, j >> 6);
+        if (staged) {
+            const u32 j0 = j - lane, run_end = j0 + 64u < G.m ? j0 + 64u : G.m;
+            const bool ok = dc_flush13(sg, wbase, lane, loc, (u32)nd, (u32)it.sb, valid, Q, j >> 6, run_end,
+                                       [&](u32 s2) { const u32 nf = F::next_first(S, s2); return nf == 0xffffffffu ? G.m : nf; });
+            if (!ok && lane == 0u) atomicOr(&meta[DM_P13_OVER], 1u);
+        }
         else if (lane < 12u) reinterpret_cast<u32*>(Q.frag + 2u * (j >> 6))[lane] = 0u;
     } else if (staged) {
         // the wavefront's piece [wbase, wbase + wtotal) of the stream: 4-byte stores from the first even entry on, the odd ends singly
@@ -1321,6 +1349,41 @@ __global__ __launch_bounds__(WG) void dc_poff_tab_kernel(const u32* __restrict__
 {
     const u32 b = blockIdx.x * WG + threadIdx.x;
     if (b <= S.nsub) poff[b] = doff_sp[S.run[b]];
+}
+// ... and, for the packed stream of a pass (DcP13Tab), where every sub-block starts in the packed space: pbase[0] = 0, pbase[s + 1] =
+// pbase[s] + (poff[s + 1] - poff[s] rounded up to 64), pad[s] = pbase[s] - poff[s].  One workgroup scans the at most FRONT_MAX_SUB + 1
+// entries (a stretch per thread, the stretches' sums through LDS); behind dc_poff_tab_kernel on the stream, no host round trip.
+__global__ __launch_bounds__(WG) void dc_pbase_tab_kernel(const u32* __restrict__ poff, u32 nsub, u32* __restrict__ pad, u32* __restrict__ pbase)
+{
+    __shared__ u32 s_sum[WG];
+    const u32 t = threadIdx.x, per = (nsub + WG - 1) / WG;
+    const u32 s0 = t * per, s1 = s0 + per < nsub ? s0 + per : nsub;
+    u32 sum = 0;
+    for (u32 s = s0; s < s1; ++s) sum += (poff[s + 1] - poff[s] + 63u) & ~63u;
+    s_sum[t] = sum;
+    __syncthreads();
+    for (u32 d = 1; d < (u32)WG; d <<= 1) {
+        const u32 v = t >= d ? s_sum[t - d] : 0u;
+        __syncthreads();
+        s_sum[t] += v;
+        __syncthreads();
+    }
+    u32 base = s_sum[t] - sum;
+    for (u32 s = s0; s < s1; ++s) { pbase[s] = base; pad[s] = base - poff[s]; base += (poff[s + 1] - poff[s] + 63u) & ~63u; }
+    if (t == (u32)WG - 1u) pbase[nsub] = s_sum[t];
+}
+// The whole zero groups of a pass's packed stream: behind sub-block s's last (padded) group, up to its extent's end at pbase[s + 1] — at
+// most seven groups, where the sub-block's decisions leave 57 .. 63 modulo 64 or fewer than 8 of them are there at all.  Thread per
+// sub-block; with the stream kernel and the join every byte of [0, pbase[nsub] / 8 * 13) is written, the buffer is not cleared first.
+__global__ __launch_bounds__(WG) void dc_p13_fill_tab_kernel(const u32* __restrict__ poff, const u32* __restrict__ pbase, u32 nsub, u8* __restrict__ out,
+                                                             const u32* __restrict__ meta)
+{
+    if (meta[DM_FAIL] != 0u) return;
+    const u32 s = blockIdx.x * WG + threadIdx.x;
+    if (s >= nsub) return;
+    const u32 g0 = (pbase[s] + (poff[s + 1] - poff[s]) + 7u) >> 3, g1 = pbase[s + 1] >> 3;
+    DcGroup13 z; z.a = 0; z.b = 0; z.c = 0; z.d = 0;
+    for (u32 g = g0; g < g1; ++g) *reinterpret_cast<DcGroup13*>(out + (size_t)g * 13u) = z;
 }
 // max_rank of every sub-block of a pass from its first-run table: bsr(nsym - 1), nsym = symbols with a first run.  One wavefront per
 // sub-block.  Also closes the run table: run[nsub] = m.  fixed >= 0: that value for every sub-block instead (the fast coder closes
@@ -1643,8 +1706,9 @@ static int dc_eval(bscgpu_ctx* c, DevCoder* d, const u32 E[4], const int fam[4],
 // stream at 13 bits per decision (DcP13), *packed_out says whether that is what was written.
 template <class SB>
 static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym, const u8* drank, const u32* dstart, const u8* ge32, u32 m, u32 n,
-                         bool ctx_open, int psbuf, int64_t expect, u32* poff_host, u16* dbg, int* packed_out, u32* D_out)
+                         bool ctx_open, int psbuf, int64_t expect, u32* poff_host, u16* dbg, int* packed_out, u32* D_out, u32* pbase_host = nullptr)
 {
+    constexpr bool TAB = DcForm<SB>::TAB;
     const u32 gm = (m + WG - 1) / WG;
     const u32 gm8 = (gm + 7u) / 8u * 8u;            // kernels that use dc_virtual_block()
     if (!ctx_open) prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
@@ -1672,6 +1736,9 @@ static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym
     dc_launch_partition<1>(c, d, d->key_sr_s, m, S, 2, 0u);
     dc_launch_partition<2>(c, d, d->key_sn_s, m, S, 3, 0u);
     dc_launch_poff(c, d, S, m);                     // (the sub-blocks' offsets in the stream are known from here on)
+    if constexpr (TAB) {                            // ... and where they start in the packed space, if that is what the caller takes
+        if (packed_out) hipLaunchKernelGGL(dc_pbase_tab_kernel, dim3(1), dim3(WG), 0, c->stream, d->poff_tab, S.nsub, d->pad_tab, d->pbase_tab);
+    }
     rc = dc_meta_down(c, d, dc_poff_down(d, S, false, poff_host));
     if (rc < 0) return rc;
     u32 E[4];
@@ -1692,8 +1759,14 @@ static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym
     rc = dc_ps_wait(c, psbuf);
     if (rc < 0) return rc;
     bool packed = false;
-    DcP13 Q{};
-    if constexpr (!DcForm<SB>::TAB) {               // (the packed stream is laid out by eight sub-blocks: dc_pstream_kernel's static_assert)
+    typename DcP13Of<SB>::T Q{};
+    if constexpr (TAB) {
+        // a pass's or a segment's: the offsets are on the device (dc_pbase_tab_kernel), the host knows only their bound — every sub-block
+        // pads by at most 63 decisions.  13 / 8 of that against the 2 Dcap bytes of the buffer: fits whenever Dcap >= 2.2 M decisions
+        // (contexts from ~0.5 MiB up), whatever the pass; a pass that does not takes the 2-byte form like a void one
+        packed = packed_out != nullptr && ((u64)Efull + 63ull * S.nsub + 7ull) / 8ull * 13ull <= 2ull * (u64)(d->Dcap + 64);
+        if (packed) { Q.pad = d->pad_tab; Q.out = reinterpret_cast<u8*>(d->ps[psbuf & 1]); Q.frag = d->frag; }
+    } else {
         // 13 bits per decision (DcP13) when the caller can take it: not with the debug planes
         packed = packed_out != nullptr && c->dc_p13 != 0 && dbg == nullptr;
         if (packed) {
@@ -1703,9 +1776,16 @@ static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym
             Q.out = reinterpret_cast<u8*>(d->ps[psbuf & 1]); Q.frag = d->frag;
             if ((u64)pbase / 8u * 13u > 2ull * (u64)(d->Dcap + 64)) packed = false;        // (cannot happen: 13 / 8 of D + 8 x 64 decisions of padding against 2 D)
         }
-        if (packed) {
-            hipLaunchKernelGGL((dc_pstream_kernel<false, true, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
-            hipLaunchKernelGGL(dc_p13_join_kernel, dim3((gm8 * WAVES + WG - 1) / WG), dim3(WG), 0, c->stream, d->frag, gm8 * WAVES, Q.out, d->meta);
+    }
+    if (packed) {
+        // (d->frag holds two records for each of the gm8 * WAVES <= m / 64 + 32 wavefronts: (Mcap + 64) / 64 + 64 pairs, m <= Mcap)
+        hipLaunchKernelGGL((dc_pstream_kernel<false, true, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
+        hipLaunchKernelGGL(dc_p13_join_kernel, dim3((gm8 * WAVES + WG - 1) / WG), dim3(WG), 0, c->stream, d->frag, gm8 * WAVES, Q.out, d->meta);
+        if constexpr (TAB) {
+            hipLaunchKernelGGL(dc_p13_fill_tab_kernel, dim3((S.nsub + WG - 1) / WG), dim3(WG), 0, c->stream, d->poff_tab, d->pbase_tab, S.nsub, Q.out, d->meta);
+            // the layout comes down with the flags: its end for every caller (hmeta[48]), all of it where the caller keeps the offsets
+            HIP_TRY(c, hipMemcpyAsync(d->hmeta + 48, d->pbase_tab + S.nsub, 4, hipMemcpyDeviceToHost, c->stream));
+            if (pbase_host) HIP_TRY(c, hipMemcpyAsync(pbase_host, d->pbase_tab, ((size_t)S.nsub + 1) * 4, hipMemcpyDeviceToHost, c->stream));
         }
     }
     if (!packed) hipLaunchKernelGGL((dc_pstream_kernel<false, false, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
@@ -1713,7 +1793,8 @@ static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym
     rc = dc_meta_down(c, d, dc_poff_down(d, S, true, poff_host));
     if (rc < 0) return rc;
     if (packed && d->hmeta[DM_P13_OVER] != 0) {
-        // 64 consecutive runs with more decisions than a wavefront's staging buffer holds (runs of thousands): this block's stream in the 2-byte form
+        // 64 consecutive runs with more decisions than a wavefront's staging buffer holds (runs of thousands): this block's (pass's,
+        // segment's) stream in the 2-byte form
         packed = false;
         prof_begin(c, BSCGPU_K_DC_PSTREAM, (u64)Efull * 26, Efull);
         hipLaunchKernelGGL((dc_pstream_kernel<false, false, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
@@ -1781,7 +1862,7 @@ static int dc_fast_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym, 
     prof_begin(c, BSCGPU_K_DC_PSTREAM, (u64)E[1] * 10, E[1]);
     rc = dc_ps_wait(c, psbuf);
     if (rc < 0) return rc;
-    hipLaunchKernelGGL((dc_pstream_kernel<true, false, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp_fast, d->meta, d->ps[psbuf & 1], (u16*)nullptr, E[1], DcP13{});
+    hipLaunchKernelGGL((dc_pstream_kernel<true, false, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp_fast, d->meta, d->ps[psbuf & 1], (u16*)nullptr, E[1], typename DcP13Of<SB>::T{});
     prof_end(c);
     rc = dc_meta_down(c, d, dc_poff_down(d, S, true, poff_host));
     if (rc < 0) return rc;
@@ -1844,6 +1925,7 @@ static int devcoder_batch_ensure(bscgpu_ctx* c, DevCoder* d)
         {(void**)&d->sub_maxr, (size_t)FRONT_MAX_SUB + 64}, {(void**)&d->poff_tab, 4 * ((size_t)FRONT_MAX_SUB + 64)},
         {(void**)&d->sub_und, 4 * ((size_t)FRONT_MAX_SUB + 64)}, {(void**)&d->sub_dec, 4 * ((size_t)FRONT_MAX_SUB + 64)},
         {(void**)&d->seg_run, 4 * ((size_t)FRONT_MAX_SUB + 64)},
+        {(void**)&d->pad_tab, 4 * ((size_t)FRONT_MAX_SUB + 64)}, {(void**)&d->pbase_tab, 4 * ((size_t)FRONT_MAX_SUB + 64)},
     };
     size_t total = 0;
     for (auto& cv : carve) total += dc_align(cv.bytes);
@@ -1885,8 +1967,11 @@ static int dc_pass_begin(bscgpu_ctx* c, u32 m, int nsub, int over_fail, DcPass* 
 // instantiated for the table (DcSubTab); every guarded exit keeps its meaning with the PASS as the unit: a raised flag declines the
 // whole pass (BSC_NOT_SUPPORTED, c->dc_last_fail says why).  The arena of devcoder_batch_ensure serves both coders (the fast one uses
 // one esub plane of its four, and max_rank 7 for every sub-block).
-int devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* D_out)
+// packed_out non-null (coder 1 only): the caller can take the stream at 13 bits per decision (DcP13Tab); *packed_out says whether that
+// is what lies in the buffer — pbase[0..nsub] in d->pbase_tab, its end in *pbytes_out as bytes — or the 2-byte form after all (void).
+int devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* D_out, int* packed_out, int64_t* pbytes_out)
 {
+    if (packed_out) *packed_out = 0;
     DcPass P;
     const int rc = dc_pass_begin(c, m, nsub, (int)FAIL_CAP, &P);
     if (rc < 0) return rc;
@@ -1901,10 +1986,13 @@ int devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* D_out
     if (fast) HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));
     else hipLaunchKernelGGL(dc_avg_kernel<DcSubTab>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, P.drank, m, P.S, d->ge32, d->meta, (u32*)nullptr);
     prof_end(c);
-    return fast ? dc_fast_run(c, d, P.S, P.dsym, P.drank, P.dstart, d->ge32, m, 0u, false, 0, -1, nullptr, D_out)
-                : dc_static_run(c, d, P.S, P.dsym, P.drank, P.dstart, d->ge32, m, 0u, false, 0, -1, nullptr, nullptr, nullptr, D_out);
+    if (fast) return dc_fast_run(c, d, P.S, P.dsym, P.drank, P.dstart, d->ge32, m, 0u, false, 0, -1, nullptr, D_out);
+    const int src = dc_static_run(c, d, P.S, P.dsym, P.drank, P.dstart, d->ge32, m, 0u, false, 0, -1, nullptr, nullptr, packed_out, D_out);
+    if (src >= 0 && packed_out && *packed_out && pbytes_out) *pbytes_out = (int64_t)d->hmeta[48] / 8 * 13;
+    return src;
 }
 const u32* devcoder_batch_poff_ptr(const bscgpu_ctx* c) { return c->dc ? c->dc->poff_tab : nullptr; }
+const u32* devcoder_batch_pbase_ptr(const bscgpu_ctx* c) { return c->dc ? c->dc->pbase_tab : nullptr; }
 
 // ---- a pass in model segments ("Model segments") --------------------------------------------------------------------
 // Sub-blocks are independent chains by construction (the chain identity carries the sub-block), so the model of a pass can run over
@@ -1917,6 +2005,12 @@ const u32* devcoder_batch_poff_ptr(const bscgpu_ctx* c) { return c->dc ? c->dc->
 // boundary nearest half its decisions and both halves run again, depth first; a single block that declines is marked with the reason.
 // out / cap: where the kept entries go back to back (host); per_segment_fit: a segment that no longer fits behind the ones before
 // it is left to the host (FAIL_CAP) — else a total above cap is counted, not copied.
+// pbase non-null (coder 1 only): the packed form (DcP13Tab).  out / cap are BYTES then; every kept segment's packed stream lands behind
+// the one before it (a segment's bytes are a whole number of 104-byte sub-block extents), pbase[0..nsub] runs on across the segments in
+// kept order and a sub-block that was not modelled has pbase[s + 1] == pbase[s].  A segment's bytes are known with the plan
+// (sub_dec rounded up to 64 per sub-block), so "fits" is tested before it runs.  A segment whose packed form is void (DM_P13_OVER)
+// has been re-launched in the 2-byte form by dc_static_run: its entries come down to a scratch vector and bscgpu_pstream_pack13_host
+// packs them into place — the caller sees one form, the blocks keep the device's model; counted in cnt_packed_void.
 // the facts of a pass (after qlfc_front_batch): dec[s] / und[s] of every sub-block on the host; ge32 and sub_maxr stay for the segments
 static int dc_segment_facts(bscgpu_ctx* c, const DcPass& P, u32 m, bool fast, u32* dec, u32* und)
 {
@@ -1947,8 +2041,13 @@ int devcoder_segment_facts(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* dec, 
 }
 
 int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub, int count, const u32* sub_run, int coder, int64_t target,
-                              u16* out, int64_t cap, bool per_segment_fit, u32* poff, int* blk_state, int64_t* D_out, const DcSegNote* note)
+                              void* out_any, int64_t cap, bool per_segment_fit, u32* poff, int* blk_state, int64_t* D_out, const DcSegNote* note,
+                              int64_t* pbase)
 {
+    const bool pk = pbase != nullptr;
+    if (pk && coder != 1) return BSC_BAD_PARAMETER;
+    u16* out = static_cast<u16*>(out_any);
+    u8* out8 = static_cast<u8*>(out_any);
     DcPass P;
     int rc = dc_pass_begin(c, m, nsub, 0, &P);
     if (rc < 0) return rc;
@@ -1968,6 +2067,8 @@ int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub
     const int nseg = bscgpu_model_segment_plan(dec.data(), und.data(), blk_sub, count, (int64_t)d->Dcap, target, seg_of.data());
     if (nseg < 0) return ctx_fail(c, nseg, "device coder: segment plan", hipSuccess);
     auto blk_dec = [&](int b) { int64_t t = 0; for (int s = blk_sub[b]; s < blk_sub[b + 1]; ++s) t += dec[s]; return t; };
+    // what sub-blocks [s0, s1) take of the landing buffer, in its units: entries, or bytes of the packed form
+    auto span_need = [&](int s0, int s1) { int64_t t = 0; for (int s = s0; s < s1; ++s) t += pk ? ((int64_t)dec[s] + 63) / 64 * 104 : (int64_t)dec[s]; return t; };
     auto blk_und = [&](int b) { for (int s = blk_sub[b]; s < blk_sub[b + 1]; ++s) if (und[s]) return true; return false; };
     struct Seg { int b0, b1; };
     std::vector<Seg> todo;                                            // a stack: depth first, in block order
@@ -1976,7 +2077,7 @@ int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub
         blk_state[b] = 0;
         if (blk_sub[b + 1] == blk_sub[b]) continue;                   // an empty block: nothing to model
         if (seg_of[b] < 0) { blk_state[b] = blk_und(b) ? (int)FAIL_AVG : (int)FAIL_CAP; continue; }
-        planned += blk_dec(b);
+        planned += span_need(blk_sub[b], blk_sub[b + 1]);
         if (!todo.empty() && seg_of[todo.back().b0] == seg_of[b]) todo.back().b0 = b; else todo.push_back(Seg{b, b + 1});
     }
     // (the ranges were grown from the right: an empty block between two members of a segment lies inside its range, one at its left
@@ -1986,12 +2087,15 @@ int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub
     int lg = 0; while ((1 << lg) < nblk) ++lg;
     const int rerun_max = 2 * lg + 2;
     int reruns = 0, kept = 0, launched = 0, replays = 0, hist_ext = 0;
-    std::vector<u32> pseg((size_t)nsub + 1);
-    int64_t base = 0;
+    std::vector<u32> pseg((size_t)nsub + 1), pbseg(pk ? (size_t)nsub + 1 : 0);
+    std::vector<u16> void_entries;                                    // (packed: the 2-byte entries of a void segment on their way to the host's packer)
+    int64_t base = 0, base_dec = 0;                                   // where the next segment lands (entries, or bytes), decisions kept
+    int kept_packed = 0, kept_void = 0;
     // poff is written as the segments are kept (they come in block order): everything up to sub-block `filled` is final
     int filled = 0;
     poff[0] = 0;
-    auto fill_to = [&](int s) { for (; filled < s; ++filled) poff[filled + 1] = poff[filled]; };
+    if (pk) pbase[0] = 0;
+    auto fill_to = [&](int s) { for (; filled < s; ++filled) { poff[filled + 1] = poff[filled]; if (pk) pbase[filled + 1] = pbase[filled]; } };
     // the segments whose copy-out is in flight, oldest first (at most one per ps buffer)
     struct Pend { int b0, b1, ev; };
     std::deque<Pend> pend;
@@ -2020,7 +2124,8 @@ int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub
         int64_t expect = 0;
         for (int s = s0; s < s1; ++s) expect += dec[s];
         auto give_up = [&](int why) { for (int b = g.b0; b < g.b1; ++b) if (blk_sub[b + 1] > blk_sub[b]) blk_state[b] = why; settle(g.b0, g.b1); };
-        if (per_segment_fit && base + expect > cap) { give_up((int)FAIL_CAP); continue; }
+        const int64_t need = span_need(s0, s1);
+        if (per_segment_fit && base + need > cap) { give_up((int)FAIL_CAP); continue; }
         const int psbuf = launched++ & 1;
         HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
         if (!fast) HIP_TRY(c, hipMemsetAsync(d->present, 0, (size_t)DC_KIND_WORDS * 4, c->stream));
@@ -2031,8 +2136,10 @@ int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub
         // (the segment's rebased table, the pass's run arrays and flags offset to its first run)
         DcSubTab G; G.nsub = (u32)(s1 - s0); G.run = d->seg_run; G.off = P.T.sub_off + s0; G.base = P.T.sub_base + s0; G.maxr = d->sub_maxr + s0;
         u32 D = 0;
+        int packed = 0;
         rc = fast ? dc_fast_run(c, d, G, P.dsym + r0, P.drank + r0, P.dstart + r0, d->ge32 + r0, r1 - r0, 0u, false, psbuf, expect, pseg.data(), &D)
-                  : dc_static_run(c, d, G, P.dsym + r0, P.drank + r0, P.dstart + r0, d->ge32 + r0, r1 - r0, 0u, false, psbuf, expect, pseg.data(), nullptr, nullptr, &D);
+                  : dc_static_run(c, d, G, P.dsym + r0, P.drank + r0, P.dstart + r0, d->ge32 + r0, r1 - r0, 0u, false, psbuf, expect, pseg.data(), nullptr,
+                                  pk ? &packed : nullptr, &D, pk ? pbseg.data() : nullptr);
         replays += c->dc_replays; hist_ext += c->dc_hist_ext;
         if (rc == BSC_NOT_SUPPORTED) {
             const int why = c->dc_last_fail;
@@ -2058,12 +2165,29 @@ int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub
         filled = s1;
         // this buffer's earlier copy-out has landed (the stream kernel waited for it), maybe the other one's too
         HIP_TRY(c, landed(psbuf));
-        if (copy_all && D > 0) {
-            HIP_TRY(c, hipMemcpyAsync(out + base, d->ps[psbuf], (size_t)D * 2, hipMemcpyDeviceToHost, c->copy_stream));
+        if (pk) {
+            // the layout the plan counted on: the packed extents of this segment's sub-blocks, from its decisions per sub-block
+            if (!packed) { pbseg[0] = 0; for (int s = s0; s < s1; ++s) pbseg[s - s0 + 1] = pbseg[s - s0] + ((pseg[s - s0 + 1] - pseg[s - s0] + 63u) & ~63u); }
+            if ((int64_t)pbseg[s1 - s0] / 8 * 13 != need) return ctx_fail(c, BSC_GPU_ERROR, "device coder: a segment's packed layout differs from the plan's", hipSuccess);
+            for (int s = s0; s < s1; ++s) pbase[s + 1] = pbase[s0] + (int64_t)pbseg[s - s0 + 1];
+        }
+        if (pk && !packed && copy_all && D > 0) {
+            // void: the 2-byte form lies in ps[psbuf] (dc_static_run re-launched it); down, and packed into place on the host
+            void_entries.resize((size_t)D);
+            HIP_TRY(c, hipMemcpyAsync(void_entries.data(), d->ps[psbuf], (size_t)D * 2, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, ctx_sync(c));
+            std::vector<int64_t> pb((size_t)(s1 - s0) + 1);
+            if (bscgpu_pstream_pack13_host(void_entries.data(), pseg.data(), s1 - s0, out8 + base, need, pb.data()) != need)
+                return ctx_fail(c, BSC_GPU_ERROR, "device coder: packing a void segment", hipSuccess);
+            settle(g.b0, g.b1);
+        } else if (copy_all && D > 0) {
+            if (pk) HIP_TRY(c, hipMemcpyAsync(out8 + base, d->ps[psbuf], (size_t)need, hipMemcpyDeviceToHost, c->copy_stream));
+            else HIP_TRY(c, hipMemcpyAsync(out + base, d->ps[psbuf], (size_t)D * 2, hipMemcpyDeviceToHost, c->copy_stream));
             HIP_TRY(c, hipEventRecord(d->seg_ev[psbuf], c->copy_stream));
             pend.push_back(Pend{g.b0, g.b1, psbuf});
         } else settle(g.b0, g.b1);
-        base += D; ++kept;
+        if (pk) ++(packed ? kept_packed : kept_void);
+        base += pk ? need : (int64_t)D; base_dec += D; ++kept;
     }
     HIP_TRY(c, landed(2));
     return BSC_NO_ERROR;
@@ -2077,8 +2201,9 @@ int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub
     for (int b = 0; b < count; ++b) if (blk_state[b]) { fail |= blk_state[b]; ++host_blocks; }
     c->dc_last_fail = fail; c->dc_replays = replays; c->dc_hist_ext = hist_ext; c->dc_avg_und = (int)und_total;
     c->cnt_seg += kept; c->cnt_seg_reruns += reruns; c->cnt_seg_host_blocks += host_blocks;
-    if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder segments] sub-blocks %d, planned %d, kept %d, re-runs %d, blocks left to the host %d, decisions %lld\n", nsub, nseg, kept, reruns, host_blocks, (long long)base);
-    *D_out = base;
+    c->cnt_packed_passes += kept_packed; c->cnt_packed_void += kept_void;
+    if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder segments] sub-blocks %d, planned %d, kept %d, re-runs %d, blocks left to the host %d, decisions %lld\n", nsub, nseg, kept, reruns, host_blocks, (long long)base_dec);
+    *D_out = base_dec;
     return BSC_NO_ERROR;
 }
 

@@ -1619,23 +1619,25 @@ static int store_from_device(bscgpu_ctx* c, const unsigned char* dIn, unsigned c
 }
 
 // a model pass's sub-blocks as the device's range coder left them (BSCGPU_OPT_DEVICE_RC; see front_batch_code_rc)
-struct PassCoded { const uint8_t* bytes; const uint32_t* off; const int* res; const int* room; };
+// (packed: the streams were BSCGPU_RC_STATIC13 bodies, whose LIBBSC_NOT_COMPRESSIBLE is not the reference's: see front_batch_code_rc)
+struct PassCoded { const uint8_t* bytes; const uint32_t* off; const int* res; const int* room; bool packed; };
 static int front_batch_code_rc(const bscgpu_front_layout* Lo, int block, const uint8_t* bytes, const uint32_t* off, const int* res, const int* room_of,
-                               unsigned char* out, int coder, int features);
+                               unsigned char* out, int coder, int features, bool packed);
 
 // the host tail of bsc_compress (libbsc.cpp:296-336) for one block of a sorted pass; input: host bytes, or dIn in HBM
 // (lay != nullptr: the block is entry li of a pass's front-end layout and is coded from its run arrays; else from its L at Lb)
 static int code_sorted_block(bscgpu_ctx* c, const unsigned char* input, const unsigned char* dIn, unsigned char* output, int n,
                              const BatchBlock& B, const unsigned char* Lb, int coder, int features,
                              const bscgpu_front_layout* lay = nullptr, int li = 0, const uint16_t* ps = nullptr, const uint32_t* poff = nullptr,
-                             const struct PassCoded* pc = nullptr)
+                             const struct PassCoded* pc = nullptr, const int64_t* pbase = nullptr /* non-null: ps is the pass's packed stream */)
 {
     unsigned char* buffer = (unsigned char*)bsc_malloc((size_t)B.lz + 4096);
     if (!buffer) return LIBBSC_NOT_ENOUGH_MEMORY;
     // (ps: the pass's probability stream from the device model of this coder, static or fast — the range coder alone)
-    int result = lay ? (pc ? front_batch_code_rc(lay, li, pc->bytes, pc->off, pc->res, pc->room, buffer, coder, features)
+    int result = lay ? (pc ? front_batch_code_rc(lay, li, pc->bytes, pc->off, pc->res, pc->room, buffer, coder, features, pc->packed)
                            : ps ? (coder == LIBBSC_CODER_QLFC_FAST ? bscgpu_front_batch_code_psf(lay, li, ps, poff, buffer, features)
-                                                                   : bscgpu_front_batch_code_ps(lay, li, ps, poff, buffer, features))
+                                   : pbase ? bscgpu_front_batch_code_ps13(lay, li, reinterpret_cast<const uint8_t*>(ps), poff, pbase, buffer, features)
+                                           : bscgpu_front_batch_code_ps(lay, li, ps, poff, buffer, features))
                                 : bscgpu_front_batch_code(lay, li, buffer, coder, features))
                      : coder_compress(Lb, buffer, B.lz, coder, features);
     if (result >= LIBBSC_NO_ERROR) memcpy(output + LIBBSC_HEADER_SIZE, buffer, (size_t)result);
@@ -1797,11 +1799,72 @@ extern "C" BSCGPU_API int bscgpu_front_batch_code_psf(const bscgpu_front_layout*
     return front_batch_code_stream(Lo, block, ps, poff, out, LIBBSC_CODER_QLFC_FAST, features);
 }
 
+// ... from the packed 13-bit stream of a pass (BSCGPU_RC_STATIC13 bodies at pbase[s]).  That form has no run-start mark: its coder gives
+// up at ANY decision once the output is full, the reference at a run start.  So LIBBSC_NOT_COMPRESSIBLE from the packed coder is not an
+// answer: the sub-block is coded again by the host model from its runs, whose result — bytes or LIBBSC_NOT_COMPRESSIBLE, then stored
+// raw — is the reference's own (what the large-block path does: "redone from the run arrays").
+extern "C" BSCGPU_API int bscgpu_front_batch_code_ps13(const bscgpu_front_layout* Lo, int block, const uint8_t* packed, const uint32_t* poff,
+                                                       const int64_t* pbase, unsigned char* out, int features)
+{
+    if (!Lo || !out || !packed || !poff || !pbase || block < 0 || block >= Lo->count) return LIBBSC_BAD_PARAMETER;
+    const int s0 = Lo->blk_sub[block], nb = Lo->blk_sub[block + 1] - s0;
+    if (nb < 1 || nb > 8) return LIBBSC_BAD_PARAMETER;
+    for (int s = s0; s < s0 + nb; ++s) if (pbase[s] < 0 || (pbase[s] & 7) != 0) return LIBBSC_BAD_PARAMETER;      // a body starts on a group
+    RunView views[8];
+    front_views(Lo, block, views);
+    RunsFetch fetch;
+    fetch.views = views; fetch.st = Lo->sub_start + s0; fetch.sz = Lo->sub_size + s0; fetch.nb = nb;
+    struct FromPacked : SubEncode {
+        const bscgpu_front_layout* Lo; const RunView* views; int s0; const uint8_t* packed; const uint32_t* poff; const int64_t* pbase;
+        int operator()(int b, uint8_t* dst, int room) override
+        {
+            const int s = s0 + b;
+            const int r = qlfc_encode_pstream(BSCGPU_RC_STATIC13, PstreamJob{Lo->first_seen + 256 * (size_t)s, Lo->nsym[s], Lo->sub_size[s], packed + pbase[s] / 8 * 13,
+                                                                             (size_t)(poff[s + 1] - poff[s]), dst, room});
+            return r == LIBBSC_NOT_COMPRESSIBLE ? qlfc_encode_runs(views[b], Lo->sub_size[s], dst, room, LIBBSC_CODER_QLFC_STATIC) : r;
+        }
+    } enc;
+    enc.Lo = Lo; enc.views = views; enc.s0 = s0; enc.packed = packed; enc.poff = poff; enc.pbase = pbase;
+    return coder_compress_views(views, nb, Lo->sub_start + s0, Lo->sub_size + s0, Lo->sizes[block], out, LIBBSC_CODER_QLFC_STATIC, features, fetch, &enc);
+}
+
+// the CPU stand-in for the packed layout of a pass (include/bscgpu.h): a pure function
+extern "C" BSCGPU_API int64_t bscgpu_pstream_pack13_host(const uint16_t* ps, const uint32_t* poff, int nsub, uint8_t* out, int64_t cap_bytes, int64_t* pbase)
+{
+    if (nsub < 0 || !poff || !pbase || cap_bytes < 0) return LIBBSC_BAD_PARAMETER;
+    pbase[0] = 0;
+    for (int s = 0; s < nsub; ++s) {
+        if (poff[s + 1] < poff[s]) return LIBBSC_BAD_PARAMETER;
+        pbase[s + 1] = pbase[s] + ((int64_t)(poff[s + 1] - poff[s]) + 63) / 64 * 64;
+    }
+    const int64_t bytes = pbase[nsub] / 8 * 13;
+    if (bytes > cap_bytes || bytes == 0) return bytes;
+    if (!out || !ps) return LIBBSC_BAD_PARAMETER;
+    for (int s = 0; s < nsub; ++s) {
+        const uint16_t* e = ps + poff[s];
+        const int64_t len = (int64_t)(poff[s + 1] - poff[s]);
+        uint8_t* g = out + pbase[s] / 8 * 13;
+        for (int64_t k = 0; k < pbase[s + 1] - pbase[s]; k += 8, g += 13) {
+            uint64_t lo = 0, hi = 0;                                   // fields 0..4 (the fifth's low 12 bits) | its top bit, fields 5..7
+            for (int x = 0; x < 8; ++x) {
+                const uint64_t f = k + x < len ? (uint64_t)(e[k + x] & 0x1fffu) : 0u;
+                if (x < 4) lo |= f << (13 * x);
+                else if (x == 4) { lo |= f << 52; hi |= f >> 12; }
+                else hi |= f << (13 * (x - 5) + 1);
+            }
+            for (int i = 0; i < 8; ++i) g[i] = (uint8_t)(lo >> (8 * i));
+            for (int i = 0; i < 5; ++i) g[8 + i] = (uint8_t)(hi >> (8 * i));
+        }
+    }
+    return bytes;
+}
+
 // bscgpu_front_batch_code_ps with the range coder's work already done on the device: the framing alone.  A sub-block whose budget
 // under the caller's framing rule is not the one the device coded it with (the serial rule behind a sub-block stored raw) goes through
-// the host model from its runs; one that ended LIBBSC_NOT_COMPRESSIBLE is stored raw, rebuilt from its runs.
+// the host model from its runs; one that ended LIBBSC_NOT_COMPRESSIBLE is stored raw, rebuilt from its runs — unless the streams were
+// packed (BSCGPU_RC_STATIC13 gives up at any decision, not at a run start): then the host model codes it again and its answer decides.
 static int front_batch_code_rc(const bscgpu_front_layout* Lo, int block, const uint8_t* bytes, const uint32_t* off, const int* res, const int* room_of,
-                               unsigned char* out, int coder, int features)
+                               unsigned char* out, int coder, int features, bool packed)
 {
     const int s0 = Lo->blk_sub[block], nb = Lo->blk_sub[block + 1] - s0;
     if (nb < 1 || nb > 8) return LIBBSC_BAD_PARAMETER;
@@ -1810,16 +1873,16 @@ static int front_batch_code_rc(const bscgpu_front_layout* Lo, int block, const u
     RunsFetch fetch;
     fetch.views = views; fetch.st = Lo->sub_start + s0; fetch.sz = Lo->sub_size + s0; fetch.nb = nb;
     struct Coded : SubEncode {
-        const bscgpu_front_layout* Lo; const RunView* views; int s0; const uint8_t* bytes; const uint32_t* off; const int* res; const int* room_of; int coder;
+        const bscgpu_front_layout* Lo; const RunView* views; int s0; const uint8_t* bytes; const uint32_t* off; const int* res; const int* room_of; int coder; bool packed;
         int operator()(int b, uint8_t* dst, int room) override
         {
             const int s = s0 + b;
-            if (room != room_of[s]) return qlfc_encode_runs(views[b], Lo->sub_size[s], dst, room, coder);
+            if (room != room_of[s] || (packed && res[s] == LIBBSC_NOT_COMPRESSIBLE)) return qlfc_encode_runs(views[b], Lo->sub_size[s], dst, room, coder);
             if (res[s] >= 0) memcpy(dst, bytes + off[s], (size_t)res[s]);
             return res[s];
         }
     } enc;
-    enc.Lo = Lo; enc.views = views; enc.s0 = s0; enc.bytes = bytes; enc.off = off; enc.res = res; enc.room_of = room_of; enc.coder = coder;
+    enc.Lo = Lo; enc.views = views; enc.s0 = s0; enc.bytes = bytes; enc.off = off; enc.res = res; enc.room_of = room_of; enc.coder = coder; enc.packed = packed;
     return coder_compress_views(views, nb, Lo->sub_start + s0, Lo->sub_size + s0, Lo->sizes[block], out, coder, features, fetch, &enc);
 }
 
@@ -1873,6 +1936,32 @@ extern "C" BSCGPU_API int64_t bscgpu_fast_pstream_batch_device(bscgpu_ctx* c, co
     return pstream_batch_device(c, dL, sizes, count, out, ps, cap, poff, LIBBSC_CODER_QLFC_FAST);
 }
 
+extern "C" BSCGPU_API int64_t bscgpu_static_pstream_batch_packed_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out,
+                                                                        uint8_t* packed, int64_t cap_bytes, uint32_t* poff, int64_t* pbase)
+{
+    if (!c || !poff || !pbase || cap_bytes < 0 || (cap_bytes > 0 && !packed)) return LIBBSC_BAD_PARAMETER;
+    const int frc = bscgpu_qlfc_front_batch_device(c, dL, sizes, count, out);
+    if (frc < 0) return frc;
+    poff[0] = 0; pbase[0] = 0;
+    if (out->nsub == 0) return 0;
+    u32 D = 0;
+    int pk = 0; int64_t bytes = 0;
+    int rc = devcoder_pstream_batch(c, (u32)out->m, out->nsub, LIBBSC_CODER_QLFC_STATIC, &D, &pk, &bytes);
+    if (rc == LIBBSC_NOT_SUPPORTED) {
+        char buf[96]; snprintf(buf, sizeof buf, "device coder declined the pass (reason mask %d)", c->dc_last_fail);
+        c->err = buf;
+    }
+    if (rc < 0) return rc;
+    if (!pk) { c->err = "the packed stream of the pass was void (a wavefront's piece beyond the staging buffer)"; return LIBBSC_NOT_SUPPORTED; }
+    std::vector<uint32_t> pb((size_t)out->nsub + 1);
+    if (hipMemcpyAsync(poff, devcoder_batch_poff_ptr(c), ((size_t)out->nsub + 1) * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return LIBBSC_GPU_ERROR;
+    if (hipMemcpyAsync(pb.data(), devcoder_batch_pbase_ptr(c), ((size_t)out->nsub + 1) * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return LIBBSC_GPU_ERROR;
+    if (bytes <= cap_bytes && bytes > 0 && hipMemcpyAsync(packed, devcoder_pstream_ptr(c, 0), (size_t)bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return LIBBSC_GPU_ERROR;
+    if (ctx_sync(c) != hipSuccess) return LIBBSC_GPU_ERROR;
+    for (int s = 0; s <= out->nsub; ++s) pbase[s] = (int64_t)pb[s];
+    return (int64_t)D;
+}
+
 // ---- a pass's model in segments (include/bscgpu.h) ---------------------------------------------------------------------------------
 extern "C" BSCGPU_API int bscgpu_model_segment_plan(const uint32_t* sub_dec, const uint32_t* sub_und, const int* blk_sub, int count, int64_t dcap,
                                                     int64_t target, int* seg_of)
@@ -1923,6 +2012,25 @@ extern "C" BSCGPU_API int64_t bscgpu_pstream_batch_segments_device(bscgpu_ctx* c
     return D;
 }
 
+extern "C" BSCGPU_API int64_t bscgpu_pstream_batch_segments_packed_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out,
+                                                                          int coder, int64_t target, uint8_t* packed, int64_t cap_bytes, uint32_t* poff,
+                                                                          int64_t* pbase, int* blk_state)
+{
+    if (!c || !poff || !pbase || cap_bytes < 0 || (cap_bytes > 0 && !packed) || (count > 0 && !blk_state)) return LIBBSC_BAD_PARAMETER;
+    if (coder != LIBBSC_CODER_QLFC_STATIC) return LIBBSC_BAD_PARAMETER;
+    const int frc = bscgpu_qlfc_front_batch_device(c, dL, sizes, count, out);
+    if (frc < 0) return frc;
+    poff[0] = 0; pbase[0] = 0;
+    for (int b = 0; b < count; ++b) blk_state[b] = 0;
+    if (out->nsub == 0) return 0;
+    int64_t D = 0;
+    const int rc = devcoder_pstream_segments(c, (u32)out->m, out->nsub, out->blk_sub, count, out->sub_run, coder, target, packed, cap_bytes, false, poff, blk_state, &D,
+                                             nullptr, pbase);
+    if (rc == LIBBSC_NOT_SUPPORTED) c->err = "device coder: an arena of the segmented model did not fit";
+    if (rc < 0) return rc;
+    return D;
+}
+
 namespace {
 // a pass's layout inside compress_batch_impl: the small arrays here, sym / rank / start and the first-run table in a pinned buffer
 struct PassLayout {
@@ -1934,6 +2042,7 @@ struct PassLayout {
     bool used = false;
     const uint16_t* ps = nullptr;      // the device model's stream of the pass (BSCGPU_OPT_BATCH_MODEL), sub-block s at poff[s]; null: host model
     std::vector<uint32_t> poff;
+    std::vector<int64_t> pbase;        // BSCGPU_OPT_BATCH_MODEL_PACKED: non-empty where ps (or the device's stream) is the packed 13-bit form, sub-block s at pbase[s]
     std::vector<int> blk_state;        // a pass in model segments (BSCGPU_OPT_BATCH_MODEL_SEGMENTS): != 0 where the block takes the host model; else empty
     // ... or, with BSCGPU_OPT_DEVICE_RC, the sub-blocks' coded bytes from the device's range coder: sub-block s's rc_res[s] bytes (or
     // LIBBSC_NOT_COMPRESSIBLE) at rc_bytes + rc_off[s], coded with an output budget of rc_room[s]
@@ -2035,7 +2144,7 @@ static int device_rc_pass(bscgpu_ctx* c, PassLayout& PL, uint8_t* host_bytes, si
             if (np < 0) return np;
             prefix.resize(at + (size_t)np);
             PL.rc_room[s] = nb == 1 ? Y.sub_size[s] - 1 : Y.sub_size[s];
-            S[s].body = (int64_t)PL.poff[s]; S[s].count = PL.poff[s + 1] - PL.poff[s];
+            S[s].body = PL.pbase.empty() ? (int64_t)PL.poff[s] : PL.pbase[s]; S[s].count = PL.poff[s + 1] - PL.poff[s];
             S[s].prefix = (uint32_t)at; S[s].nprefix = (uint32_t)np;
             S[s].out_off = off; S[s].out_size = (uint32_t)PL.rc_room[s];
             PL.rc_off[s] = off;
@@ -2044,7 +2153,7 @@ static int device_rc_pass(bscgpu_ctx* c, PassLayout& PL, uint8_t* host_bytes, si
     }
     if ((size_t)off > (size_t)8 * (size_t)c->max_n || (size_t)off > host_cap) return LIBBSC_NOT_SUPPORTED;
     uint8_t* dOut = reinterpret_cast<uint8_t*>(c->kA);
-    const int rc = rc_encode_device(c, coder == LIBBSC_CODER_QLFC_FAST ? BSCGPU_RC_FAST16 : BSCGPU_RC_STATIC16, devcoder_pstream_ptr(c, 0), prefix.data(), (int)prefix.size(), S.data(), nsub, dOut, PL.rc_res.data(), 8);
+    const int rc = rc_encode_device(c, coder == LIBBSC_CODER_QLFC_FAST ? BSCGPU_RC_FAST16 : !PL.pbase.empty() ? BSCGPU_RC_STATIC13 : BSCGPU_RC_STATIC16, devcoder_pstream_ptr(c, 0), prefix.data(), (int)prefix.size(), S.data(), nsub, dOut, PL.rc_res.data(), 8);
     if (rc < 0) return rc;
     if (hipMemcpyAsync(host_bytes, dOut, (size_t)off, hipMemcpyDeviceToHost, c->stream) != hipSuccess || ctx_sync(c) != hipSuccess) return LIBBSC_GPU_ERROR;
     PL.rc_bytes = host_bytes;
@@ -2086,6 +2195,8 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
     // ... in model segments (BSCGPU_OPT_BATCH_MODEL_SEGMENTS); with the device's range coder on, a pass takes the whole-pass route
     const bool segments = model && c->batch_model_segments != 0 && c->device_rc == 0;
     const int64_t segment_target = segments ? batch_model_segment() : 0;
+    // ... with the stream in the packed 13-bit form (BSCGPU_OPT_BATCH_MODEL_PACKED): -e1 only, whole passes and segments alike
+    const bool packed_route = model && !fast_model && c->batch_model_packed != 0;
     const size_t frontN = ((size_t)c->max_n + 4096 + 4095) / 4096 * 4096;
     std::vector<PassLayout> lays(2);
     const int threads = default_coder_threads();
@@ -2161,10 +2272,10 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
                     if (sizes[B.b] > 0) expand_runs(V[0], 0, tmp);
                     results[B.b] = bsc_store(tmp, out_of(B.b), sizes[B.b], features);
                 } else {
-                    const PassCoded coded{PL.rc_bytes, PL.rc_off.data(), PL.rc_res.data(), PL.rc_room.data()};
+                    const PassCoded coded{PL.rc_bytes, PL.rc_off.data(), PL.rc_res.data(), PL.rc_room.data(), !PL.pbase.empty()};
                     results[B.b] = code_sorted_block(c, dev ? nullptr : in_of(B.b), dev ? din_of(B.b) : nullptr, out_of(B.b), sizes[B.b],
                                                      B, nullptr, coder, features, &Y, i, (!PL.blk_state.empty() && PL.blk_state[i]) ? nullptr : PL.ps, PL.poff.data(),
-                                                     PL.rc_bytes ? &coded : nullptr);
+                                                     PL.rc_bytes ? &coded : nullptr, PL.pbase.empty() ? nullptr : PL.pbase.data());
                 }
                 return;
             }
@@ -2216,7 +2327,7 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
                 rc = qlfc_front_batch(c, c->dL, PL.sizes.data(), e - b, &PL.lay, c->front_host[p & 1] + 6 * frontN);
                 if (rc < 0) break;
                 PL.used = true; ++c->cnt_front_passes;
-                PL.ps = nullptr; PL.rc_bytes = nullptr; PL.blk_state.clear();
+                PL.ps = nullptr; PL.rc_bytes = nullptr; PL.blk_state.clear(); PL.pbase.clear();
                 if (segments && PL.lay.nsub > 0 && pos >= model_min_pass && ctx_ensure_model_host(c) == LIBBSC_NO_ERROR) {
                     // the same route segment by segment: the streams of the kept blocks land back to back, a block the device
                     // leaves out (or whose segment no longer fits the landing buffer) is coded from its run arrays.  Coding starts
@@ -2224,6 +2335,8 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
                     PL.poff.resize((size_t)PL.lay.nsub + 1);
                     PL.blk_state.assign((size_t)(e - b), 0);
                     PL.ps = c->model_host[p & 1];
+                    // (packed: the landing buffer in bytes, less the few a packed entry's 4-byte read may reach past a stream)
+                    if (packed_route) PL.pbase.assign((size_t)PL.lay.nsub + 1, 0);
                     finish_blocks();
                     struct Feed {
                         PassGroups* G; const std::vector<BatchBlock>* blocks; const int* blk_sub; const int* state; std::vector<char> queued;
@@ -2247,8 +2360,8 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
                     start_groups();
                     int64_t D = 0;
                     const int mrc = devcoder_pstream_segments(c, (u32)PL.lay.m, PL.lay.nsub, PL.lay.blk_sub, e - b, PL.lay.sub_run, coder, segment_target,
-                                                              c->model_host[p & 1], (int64_t)c->model_host_entries, true, PL.poff.data(), PL.blk_state.data(), &D,
-                                                              &note);
+                                                              c->model_host[p & 1], packed_route ? (int64_t)c->model_host_entries * 2 - 8 : (int64_t)c->model_host_entries,
+                                                              true, PL.poff.data(), PL.blk_state.data(), &D, &note, packed_route ? PL.pbase.data() : nullptr);
                     if (mrc < 0 && mrc != LIBBSC_NOT_SUPPORTED) { PG.close(); rc = mrc; break; }
                     // (an arena did not fit: what is not queued yet takes the host model)
                     if (mrc < 0) for (int i = 0; i < e - b; ++i) if (!feed.queued[i]) PL.blk_state[i] = BSCGPU_DC_FAIL_CAP;
@@ -2262,16 +2375,22 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
                     // the model behind the front end, on the same stream, before the next pass's sort; the run arrays came down all the
                     // same: they serve a declined pass, a sub-block stored raw and the <= 28-byte blocks that rode along
                     u32 D = 0;
-                    const int mrc = devcoder_pstream_batch(c, (u32)PL.lay.m, PL.lay.nsub, coder, &D);
+                    int pk = 0; int64_t pbytes = 0;          // packed: what the device left is the 13-bit form, pbytes of it; void: 16-bit entries as ever
+                    const int mrc = devcoder_pstream_batch(c, (u32)PL.lay.m, PL.lay.nsub, coder, &D, packed_route ? &pk : nullptr, &pbytes);
                     if (mrc == LIBBSC_NOT_SUPPORTED) ++(fast_model ? c->cnt_model_fast_declined : c->cnt_model_declined);
                     else if (mrc < 0) { rc = mrc; break; }
-                    else if ((size_t)D <= c->model_host_entries) {
+                    else if (pk ? (size_t)pbytes + 8 <= c->model_host_entries * 2 : (size_t)D <= c->model_host_entries) {
                         PL.poff.resize((size_t)PL.lay.nsub + 1);
                         u16* hps = c->model_host[p & 1];     // free: as hb is
                         const bool drc = c->device_rc != 0;  // the streams stay in HBM: one launch of the device's range coder codes them
+                        const size_t down = pk ? (size_t)pbytes : (size_t)D * 2;
+                        std::vector<uint32_t> pb(pk ? PL.poff.size() : 0);
                         if (hipMemcpyAsync(PL.poff.data(), devcoder_batch_poff_ptr(c), PL.poff.size() * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                            (!drc && D > 0 && hipMemcpyAsync(hps, devcoder_pstream_ptr(c, 0), (size_t)D * 2, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+                            (pk && hipMemcpyAsync(pb.data(), devcoder_batch_pbase_ptr(c), pb.size() * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+                            (!drc && down > 0 && hipMemcpyAsync(hps, devcoder_pstream_ptr(c, 0), down, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
                             ctx_sync(c) != hipSuccess) { rc = LIBBSC_GPU_ERROR; break; }
+                        if (pk) PL.pbase.assign(pb.begin(), pb.end());
+                        if (packed_route) ++(pk ? c->cnt_packed_passes : c->cnt_packed_void);
                         if (drc) {
                             rc = device_rc_pass(c, PL, reinterpret_cast<uint8_t*>(hps), c->model_host_entries * 2, coder);
                             if (rc < 0) break;

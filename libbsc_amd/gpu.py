@@ -688,3 +688,85 @@ class Pipe:
             self.close()
         except Exception:
             pass
+
+
+# ---- the packed 13-bit stream of a pass (include/bscgpu.h, "the packed 13-bit stream of a pass") -----------------------------------
+P13_SLACK = 8                                       # bytes behind a packed stream that a coder's 4-byte entry read may touch
+
+
+def pstream_pack13_host(ps, poff):
+    """bscgpu_pstream_pack13_host: the CPU stand-in for the packed layout of a pass: 16-bit static entries (sub-block s at
+    [poff[s], poff[s + 1])) -> (bytes np.uint8[pbase[nsub] / 8 * 13], pbase np.int64[nsub + 1])"""
+    p = np.ascontiguousarray(ps, dtype=np.uint16)
+    o = np.ascontiguousarray(poff, dtype=np.uint32)
+    nsub = int(o.size) - 1
+    assert nsub >= 0 and p.size >= int(o[-1])
+    if p.size == 0:
+        p = np.zeros(1, np.uint16)
+    pbase = np.zeros(nsub + 1, np.int64)
+    n = int(N.lib().bscgpu_pstream_pack13_host(N.np_ptr(p), N.np_ptr(o), nsub, None, 0, N.np_ptr(pbase)))
+    if n < 0:
+        raise GpuError(n, "bscgpu_pstream_pack13_host")
+    out = np.full(n + P13_SLACK, 0xa5, np.uint8)     # (not zero: the call has to write every byte of the layout itself)
+    n2 = int(N.lib().bscgpu_pstream_pack13_host(N.np_ptr(p), N.np_ptr(o), nsub, N.np_ptr(out), n, N.np_ptr(pbase)))
+    if n2 != n:
+        raise GpuError(n2, "bscgpu_pstream_pack13_host")
+    return out[:n], pbase
+
+
+def front_batch_code_ps13(fb, block, packed, poff, pbase, features=3):
+    """bscgpu_front_batch_code_ps13: FrontBatch.code for the static coder from the pass's packed stream (sub-block s's RC_STATIC13
+    body at decision pbase[s]) -> bytes, or its negative code"""
+    o = np.ascontiguousarray(poff, dtype=np.uint32)
+    pb = np.ascontiguousarray(pbase, dtype=np.int64)
+    assert o.size == fb.nsub + 1 and pb.size == fb.nsub + 1
+    b = np.zeros(int(pb[-1]) // 8 * 13 + P13_SLACK, np.uint8)
+    src = np.ascontiguousarray(packed, dtype=np.uint8)
+    assert src.size >= b.size - P13_SLACK
+    b[:b.size - P13_SLACK] = src[:b.size - P13_SLACK]
+    out = np.empty(int(fb.sizes[block]) + 4096, np.uint8)
+    r = int(N.lib().bscgpu_front_batch_code_ps13(C.byref(fb.lay), int(block), N.np_ptr(b), N.np_ptr(o), N.np_ptr(pb), N.np_ptr(out), int(features)))
+    return out[:r].tobytes() if r >= 0 else r
+
+
+def _static_pstream_batch_packed(self, dL, sizes, cap_bytes=None):
+    """bscgpu_static_pstream_batch_packed_device: static_pstream_batch with the stream in the packed 13-bit form -> (FrontBatch, bytes
+    np.uint8[pbase[nsub] / 8 * 13], poff np.uint32[nsub + 1], pbase np.int64[nsub + 1]); raises GpuError -4 when the device declines
+    the pass or (option_get(CNT_DC_LAST_FAIL) == 0) the packed form was void"""
+    fb = FrontBatch(sizes)
+    if cap_bytes is None:
+        cap_bytes = 2 * (4 * int(self.max_n) + 65536)           # the device's stream buffer
+    out = np.full(cap_bytes + P13_SLACK, 0xa5, np.uint8)
+    poff = np.zeros(2 * fb.count + 2, np.uint32)
+    pbase = np.zeros(2 * fb.count + 2, np.int64)
+    D = int(self.L.bscgpu_static_pstream_batch_packed_device(self.h, _dptr(dL), N.np_ptr(fb.sizes), fb.count, C.byref(fb.lay), N.np_ptr(out),
+                                                             cap_bytes, N.np_ptr(poff), N.np_ptr(pbase)))
+    self._check(D)
+    n = int(pbase[fb.nsub]) // 8 * 13
+    if n > cap_bytes:
+        raise GpuError(-2, f"{n} bytes exceed the buffer of {cap_bytes}")
+    return fb, out[:n], poff[:fb.nsub + 1], pbase[:fb.nsub + 1]
+
+
+def _pstream_batch_segments_packed(self, dL, sizes, coder=1, target=0, cap_bytes=None):
+    """bscgpu_pstream_batch_segments_packed_device: pstream_batch_segments for -e1 with the kept segments' streams in the packed 13-bit
+    form -> (FrontBatch, bytes np.uint8[pbase[nsub] / 8 * 13], poff np.uint32[nsub + 1], pbase np.int64[nsub + 1], blk_state
+    np.int32[count]); above cap_bytes the bytes are counted, not copied (the returned array is then empty)"""
+    fb = FrontBatch(sizes)
+    if cap_bytes is None:
+        cap_bytes = 26 * int(fb.sizes.sum()) + 104 * 2 * fb.count + 4096
+    out = np.full(max(cap_bytes, 0) + P13_SLACK, 0xa5, np.uint8)
+    poff = np.zeros(2 * fb.count + 2, np.uint32)
+    pbase = np.zeros(2 * fb.count + 2, np.int64)
+    state = np.zeros(max(fb.count, 1), np.int32)
+    D = int(self.L.bscgpu_pstream_batch_segments_packed_device(self.h, _dptr(dL), N.np_ptr(fb.sizes), fb.count, C.byref(fb.lay), int(coder), int(target),
+                                                               N.np_ptr(out), int(cap_bytes), N.np_ptr(poff), N.np_ptr(pbase), N.np_ptr(state)))
+    self._check(D)
+    n = int(pbase[fb.nsub]) // 8 * 13
+    return fb, (out[:n] if n <= cap_bytes else out[:0]), poff[:fb.nsub + 1], pbase[:fb.nsub + 1], state[:fb.count]
+
+
+GpuContext.static_pstream_batch_packed = _static_pstream_batch_packed
+GpuContext.pstream_batch_segments_packed = _pstream_batch_segments_packed
+# the packed 13-bit stream for the static coder's batch model (default 0); passes / segments that went down packed, and as 16-bit entries after all
+GpuContext.OPT_BATCH_MODEL_PACKED, GpuContext.CNT_BATCH_PACKED_PASSES, GpuContext.CNT_BATCH_PACKED_VOID = 27, 28, 29

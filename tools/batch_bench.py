@@ -54,7 +54,10 @@ stage-alone leg adds the pass's decisions per byte from the CPU stand-in); raw o
 --segments (with --model, either coder): the whole-call legs become model off / model on / model + BSCGPU_OPT_BATCH_MODEL_SEGMENTS,
 host and HBM input, interleaved, with the segment counters of every leg; --model-only runs the segmented stage
 (bscgpu_pstream_batch_segments_device) instead of the whole-pass stage, the facts kernels as a class of their own (dc_facts) and the
-copy-out included in the wall time.  --segment-sweep: model + segments on W1 and W2, host input, with BSC_BATCH_MODEL_SEGMENT set to
+copy-out included in the wall time.  --packed (with --model, -e1): the whole-call legs become model off / model on / model on +
+BSCGPU_OPT_BATCH_MODEL_PACKED for either input kind (with --segments: both model legs segmented), with the packed counters and the
+assertion that W1's segmented pass leaves no block to the host for landing space; with --model-only the stage in the packed form beside
+the 16-bit one, with the assertion bytes = pbase[nsub] / 8 * 13.  Raw output belongs under profiles/batch_packed/.  --segment-sweep: model + segments on W1 and W2, host input, with BSC_BATCH_MODEL_SEGMENT set to
 the capacity / 8, / 4, / 2 and the capacity, interleaved with model on and off.  Raw output belongs under profiles/batch_segments/.
     python tools/batch_bench.py --model --segments [--model-only | --segment-sweep] [--coder 3] [--reps 3] [--workloads W1,W2,W3]
 """
@@ -367,6 +370,11 @@ def model_main(args):
     stage = ctx.fast_pstream_batch if fast else ctx.static_pstream_batch
     if args.segments:                                             # the segmented stage: (layout, entries, poff) as the whole-pass stage returns them
         stage = lambda dL, psz: ctx.pstream_batch_segments(dL, psz, coder, 0)[:3]
+    if args.packed and fast:
+        raise SystemExit("--packed is the static coder's (-e1): the fast coder's entries use all 16 bits")
+    # --packed --model-only: the stage in the packed 13-bit form beside the 16-bit one, same session, interleaved
+    stage13 = (lambda dL, psz: ctx.pstream_batch_segments_packed(dL, psz, coder, 0)[:4]) if args.segments else ctx.static_pstream_batch_packed
+    PACKED_KEYS = (ctx.CNT_BATCH_PACKED_PASSES, ctx.CNT_BATCH_PACKED_VOID)
     SEG_KEYS = (ctx.CNT_BATCH_SEGMENTS, ctx.CNT_BATCH_SEG_RERUNS, ctx.CNT_BATCH_SEG_HOST_BLOCKS)
     pctx = [GpuContext(0, max_n=(1 << 20) + 4096) for _ in range(0 if (args.model_only or args.model_sweep or args.segment_sweep) else args.contexts)]
     pipes = [c.pipe(args.depth) for c in pctx]
@@ -460,17 +468,32 @@ def model_main(args):
                 except GpuError as e:
                     print(json.dumps({**rec, "declined": e.code, "last_fail": ctx.option_get(ctx.CNT_DC_LAST_FAIL)}), flush=True)
                     continue
+                if args.packed:                                                   # the layout's deterministic check, and the warm-up of the packed launches
+                    try:
+                        _, pk, poff13, pbase13 = stage13(dL, psz)
+                    except GpuError as e:
+                        print(json.dumps({**rec, "packed_declined_or_void": e.code, "last_fail": ctx.option_get(ctx.CNT_DC_LAST_FAIL)}), flush=True)
+                        continue
+                    assert int(pk.size) == int(pbase13[-1]) // 8 * 13, "bytes copied per pass = pbase[nsub] / 8 * 13"
+                    rec.update({"packed_bytes": int(pk.size), "bytes_16_bit": 2 * int(ps.size), "pbase_end": int(pbase13[-1])})
                 ctx.profile(True)
                 tw, per = [], {k: [] for k in CLASSES}
+                tw13, per13 = [], {k: [] for k in CLASSES}
                 for _ in range(args.reps):
-                    ctx.profile_reset()
-                    t0 = time.perf_counter()
-                    stage(dL, psz)
-                    tw.append(round((time.perf_counter() - t0) * 1e3, 2))
-                    st = ctx.profile_get()
-                    for k, names in CLASSES.items():
-                        per[k].append(round(sum(st[n]["ms"] for n in names), 3))
+                    for run, walls, classes in ((stage, tw, per),) + (((stage13, tw13, per13),) if args.packed else ()):
+                        ctx.profile_reset()
+                        t0 = time.perf_counter()
+                        run(dL, psz)
+                        walls.append(round((time.perf_counter() - t0) * 1e3, 2))
+                        st = ctx.profile_get()
+                        for k, names in CLASSES.items():
+                            classes[k].append(round(sum(st[n]["ms"] for n in names), 3))
                 ctx.profile(False)
+                if args.packed:
+                    rec.update({"packed_wall_ms_with_front_end_and_copy_out": tw13, "packed_kernel_ms": per13,
+                                "p_stream_ms_median_16_bit_vs_packed": [float(np.median(per["p_stream"])), float(np.median(per13["p_stream"]))],
+                                "p_stream_ms_min_max_16_bit": [min(per["p_stream"]), max(per["p_stream"])],
+                                "p_stream_ms_min_max_packed": [min(per13["p_stream"]), max(per13["p_stream"])]})
                 print(json.dumps({**rec, "runs": fb.m, "sub_blocks": fb.nsub, "decisions": int(ps.size), "replays": ctx.option_get(ctx.CNT_DC_REPLAYS),
                                   "wall_ms_with_front_end_and_copy_out": tw, "kernel_ms": per,
                                   "model_kernel_ms_median": round(float(sum(np.median(v) for k, v in per.items() if k != "front_end")), 3)}), flush=True)
@@ -486,6 +509,11 @@ def model_main(args):
             if args.segments:                                      # (option, HBM input, device RC, segments)
                 legs = {"batch_off": (0, False, 0, 0), "batch_on": (1, False, 0, 0), "batch_segments": (1, False, 0, 1),
                         "batch_device_off": (0, True, 0, 0), "batch_device_on": (1, True, 0, 0), "batch_device_segments": (1, True, 0, 1), "pipe": None}
+            if args.packed:                                        # (..., packed): packed on / packed off / model off, interleaved, either input kind
+                sg = 1 if args.segments else 0
+                legs = {"batch_off": (0, False, 0, 0, 0), "batch_on": (1, False, 0, sg, 0), "batch_on_packed": (1, False, 0, sg, 1),
+                        "batch_device_off": (0, True, 0, 0, 0), "batch_device_on": (1, True, 0, sg, 0), "batch_device_on_packed": (1, True, 0, sg, 1), "pipe": None}
+            packed_cnt = {k: None for k in legs}
             segs = {k: None for k in legs}
             walls = {k: [] for k in legs}
             cpus = {k: [] for k in legs}
@@ -500,10 +528,15 @@ def model_main(args):
                         ctx.option_set(OPT, how[0])
                         ctx.option_set(ctx.OPT_DEVICE_RC, how[2])
                         ctx.option_set(ctx.OPT_BATCH_MODEL_SEGMENTS, how[3] if len(how) > 3 else 0)
+                        ctx.option_set(ctx.OPT_BATCH_MODEL_PACKED, how[4] if len(how) > 4 else 0)
                         p0, d0 = ctx.option_get(CNT_PASSES), ctx.option_get(CNT_DECLINED)
                         g0 = [ctx.option_get(k) for k in SEG_KEYS]
+                        k0 = [ctx.option_get(k) for k in PACKED_KEYS]
                         out, wall, cpu = timed((lambda: ctx.compress_batch_device(flat, sizes, 1, coder)) if how[1] else (lambda: ctx.compress_batch(blocks, 1, coder)))
                         segs[leg] = [ctx.option_get(k) - a for k, a in zip(SEG_KEYS, g0)]
+                        packed_cnt[leg] = [ctx.option_get(k) - a for k, a in zip(PACKED_KEYS, k0)]
+                        if leg == "batch_on_packed":
+                            packed_fail = ctx.option_get(ctx.CNT_DC_LAST_FAIL)
                         kept[leg] = ctx.option_get(CNT_PASSES) - p0
                         declined[leg] = ctx.option_get(CNT_DECLINED) - d0
                     walls[leg].append(wall); cpus[leg].append(cpu)
@@ -514,8 +547,17 @@ def model_main(args):
                                   "ms": [round(x * 1e3, 1) for x in w], "median_MB_s": round(mb / float(np.median(w)), 1),
                                   "MB_s_min_max": [round(mb / float(w.max()), 1), round(mb / float(w.min()), 1)],
                                   "cpu_s_per_MB": round(float(np.mean(cpus[leg])) / mb, 4), "model_passes": kept[leg], "model_declined": declined[leg],
-                                  **({"segments_reruns_host_blocks": segs[leg]} if args.segments else {}),
+                                  **({"segments_reruns_host_blocks": segs[leg]} if args.segments or args.packed else {}),
+                                  **({"packed_passes_void": packed_cnt[leg]} if args.packed else {}),
                                   "sha256_equals_pipe": bool(same[leg])}), flush=True)
+            if args.packed and args.segments and name == "W1":
+                # derived, not measured: W1's -e1 pass exceeds the pinned landing buffer as 16-bit entries and fits it packed.  What the
+                # packed leg still leaves to the host was excluded for another reason (an undecided avg_rank flag, a rare exit), which its
+                # reason mask names; BSCGPU_DC_FAIL_CAP (8) may not be among them
+                h16, h13 = segs["batch_on"][2], segs["batch_on_packed"][2]
+                print(json.dumps({"workload": name, "check": "segment host blocks through landing space", "16_bit": h16, "packed": h13,
+                                  "reason_mask_of_the_packed_leg": packed_fail}), flush=True)
+                assert h13 <= h16 and (h13 == 0 or (packed_fail & ctx.DC_FAIL_CAP) == 0), "a block of W1 left out for landing space in the packed leg"
             del dblocks
     finally:
         for p in pipes:
@@ -543,6 +585,7 @@ def main():
     ap.add_argument("--model-only", action="store_true", help="with --model: the model stage alone on one pass, per kernel class")
     ap.add_argument("--model-sweep", action="store_true", help="with --model: on against off on passes of 64 KiB .. 16 MiB (set BSC_BATCH_MODEL_MIN_PASS=0)")
     ap.add_argument("--segments", action="store_true", help="implies --model: legs model off / on / on + BSCGPU_OPT_BATCH_MODEL_SEGMENTS; with --model-only: the segmented stage")
+    ap.add_argument("--packed", action="store_true", help="with --model (and --segments, --model-only): BSCGPU_OPT_BATCH_MODEL_PACKED on / off / model off, interleaved (-e1)")
     ap.add_argument("--segment-sweep", action="store_true", help="with --model: BSC_BATCH_MODEL_SEGMENT over the capacity / 8 .. the capacity, host input (set BSC_BATCH_MODEL_MIN_PASS=0 for one-pass workloads of the fast coder)")
     args = ap.parse_args()
     if args.segment_sweep:
