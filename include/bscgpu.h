@@ -529,9 +529,17 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          stayed there or was declined (the block is then coded through the host model, same bytes):
  *     _REPLAYS             evaluation chunks whose start value had to be replayed serially (the predecessor's bracket had not met)
  *     _LAST_FAIL           why the block was declined: a mask of BSCGPU_DC_FAIL_*, 0 when it stayed on the device
- *     _AVG_UNDECIDED       runs whose avg_rank >= 32 flag the warmed-up bracket left open (any such run declines: _FAIL_AVG)
+ *     _AVG_UNDECIDED       runs whose avg_rank >= 32 flag the warmed-up bracket left open (any such run declines: _FAIL_AVG — unless BSCGPU_OPT_DC_AVG_EXACT settles it)
+ *     _AVG_RESOLVED        of those, the runs whose flag the exact resolve then settled (BSCGPU_OPT_DC_AVG_EXACT; 0 with the option off)
  *     _HIST_EXTENDED       runs whose run_hist bracket was still open after nine predecessors of their symbol and went on to the
  *                          extended look-back (36 .. 9216 predecessors; still open after that: _FAIL_HIST)
+ * BSCGPU_OPT_DC_AVG_EXACT  0 (default; BSC_DC_AVG_EXACT=1 in the environment turns it on for contexts created after that) / 1: the
+ *                          avg_rank flags the bracket leaves open are computed exactly on the device — every chunk of runs is walked
+ *                          from each of the at most 33 values its start can have, the chunks' maps are chained, the open chunks walked
+ *                          again from their exact start; no sync, nothing approximate — so such a block, pass or segment is not declined
+ *                          for them: _FAIL_AVG is raised only where a start bracket is 64 values wide or more, which the contraction
+ *                          of avg_rank rules out.  Batched passes in model segments: no block is excluded for its avg flags.  -e0 has
+ *                          no such flags and is not affected.  Same output.
  * BSCGPU_OPT_BATCH_FRONT    1: the passes of bscgpu_compress_batch / _batch_device run the QLFC front end of the whole pass on the GPU and
  *                          bring down its run arrays (sym, rank, start) instead of L; 0: L comes down and every block goes through
  *                          bsc_coder_compress on the host.  Same output.  Default 1 (measured: DESIGN §2b).
@@ -598,7 +606,8 @@ enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACK
        BSCGPU_OPT_BWT_FOLD = 20, BSCGPU_CNT_BWT_FOLDED = 21,
        BSCGPU_OPT_BATCH_MODEL_SEGMENTS = 22, BSCGPU_CNT_BATCH_SEGMENTS = 23, BSCGPU_CNT_BATCH_SEG_RERUNS = 24,
        BSCGPU_CNT_BATCH_SEG_HOST_BLOCKS = 25, BSCGPU_CNT_DC_DCAP = 26,
-       BSCGPU_OPT_BATCH_MODEL_PACKED = 27, BSCGPU_CNT_BATCH_PACKED_PASSES = 28, BSCGPU_CNT_BATCH_PACKED_VOID = 29 };
+       BSCGPU_OPT_BATCH_MODEL_PACKED = 27, BSCGPU_CNT_BATCH_PACKED_PASSES = 28, BSCGPU_CNT_BATCH_PACKED_VOID = 29,
+       BSCGPU_OPT_DC_AVG_EXACT = 30, BSCGPU_CNT_DC_AVG_RESOLVED = 31 };
 /* _FAIL_AVG: undecided avg_rank flags; _FAIL_HIST: a run_hist bracket open after 9216 predecessors; _FAIL_CAP: more runs or decisions
  * than the context's arena holds; _FAIL_REPLAY: a chain whose bracket stayed open over more than 64 evaluation chunks. */
 enum { BSCGPU_DC_FAIL_AVG = 2, BSCGPU_DC_FAIL_HIST = 4, BSCGPU_DC_FAIL_CAP = 8, BSCGPU_DC_FAIL_REPLAY = 16 };

@@ -26,7 +26,8 @@
 //                    emit 16 bits per decision: probability, coded bit, start-of-run mark.
 //
 // The host (qlfc.cpp: encode_from_pstream) then runs only the range coder.  Whenever something is outside what this path
-// handles exactly (an avg_rank bracket that does not decide, a run_hist bracket still open after 9216 predecessors, a chain whose
+// handles exactly (an avg_rank bracket that does not decide — unless BSCGPU_OPT_DC_AVG_EXACT has the open flags computed exactly,
+// 1a' —, a run_hist bracket still open after 9216 predecessors, a chain whose
 // bracket stays open over more than 64 evaluation chunks, capacity), a flag is raised and the caller falls back to the host model;
 // nothing approximate is ever emitted.
 //
@@ -67,12 +68,24 @@ constexpr u32 DC_SIGMASK  = 0x7ffu;    // event = X | sub-block << 8 | bit << 11
 constexpr int DC_ROWS     = 1088;      // rows of the chain-major layout = decision types (NUM_TAU = 1080), padded to whole wavefronts
 
 // meta scalars (device u32 array)
-enum { DM_FAIL = 0, DM_NTYPES, DM_NROUNDS, DM_AVG_UND, DM_REPLAYS, DM_D0, DM_D1, DM_D2, DM_D3, DM_HIST_EXT /* runs that entered the extended run_hist look-back */, DM_P13_OVER /* a wavefront's piece did not fit the staging buffer: the packed stream is void */, DM_COUNT = 16 };
+enum { DM_FAIL = 0, DM_NTYPES, DM_NROUNDS, DM_AVG_UND, DM_REPLAYS, DM_D0, DM_D1, DM_D2, DM_D3, DM_HIST_EXT /* runs that entered the extended run_hist look-back */, DM_P13_OVER /* a wavefront's piece did not fit the staging buffer: the packed stream is void */,
+       DM_AVG_RESOLVED /* exact resolve: flags the bracket left open and the resolve settled */, DM_AVG_LEFT /* ... and did not (the guard) */, DM_COUNT = 16 };
 // (bit 0 is not in use: every decision type has a row of its own, DC_ROWS >= NUM_TAU, so no number of types is too many)
 enum { FAIL_AVG = BSCGPU_DC_FAIL_AVG, FAIL_HIST = BSCGPU_DC_FAIL_HIST, FAIL_CAP = BSCGPU_DC_FAIL_CAP, FAIL_REPLAY = BSCGPU_DC_FAIL_REPLAY };
 
 struct DcSub { u32 nb; u32 first[9]; u32 maxr[8]; };           // run index range (first[nb] = m) and max_rank of each sub-block
 struct DcRowBins { u16 lo1, hi1, lo2, hi2; };                   // counting pass: count(row) = P[hi1] - P[lo1] + P[hi2] - P[lo2] over bin prefix sums
+
+// what the exact resolve of open avg_rank flags keeps per chunk of DC_AVG_CH runs and per group of DC_AVG_GROUP chunks (1a')
+struct DcAvgRec {
+    u16* brk;       // per chunk: lo0 | hi0 << 8, the bracket at the chunk's first run (equal where the warm-up reached the sub-block's first run)
+    u16* und;       // per chunk: runs whose flag the bracket left open
+    u8*  st;        // per chunk: DC_AVG_ST_*
+    u16* ex;        // per chunk: the exact avg_rank at its first run, or DC_AVG_UNKNOWN
+    u8*  map;       // per chunk, DC_AVG_CAND bytes: map[v] = avg_rank at the next chunk's first run, had this one started at lo0 + v
+    u16* gmap;      // per group of DC_AVG_GROUP chunks, DC_AVG_CAND entries: the same across the group, from its first chunk's candidates
+    u16* gstart;    // per group: the exact start of its first chunk
+};
 
 struct DevCoder {
     size_t Mcap = 0, Dcap = 0;
@@ -107,6 +120,10 @@ struct DevCoder {
     // the packed stream of a pass or a segment (DcP13Tab): pad[s] and pbase[0 .. nsub] of the table at hand (dc_pbase_tab_kernel)
     u32 *pad_tab = nullptr, *pbase_tab = nullptr;
     hipEvent_t seg_ev[2] = {nullptr, nullptr};                 // behind the last copy out of ps[0 / 1] on the copy stream
+    // the exact resolve of open avg_rank flags (BSCGPU_OPT_DC_AVG_EXACT), allocated on its first use: 71 bytes per chunk of DC_AVG_CH
+    // runs, 130 per group of DC_AVG_GROUP chunks — under 0.1 byte per byte of max_n
+    char* avg_arena = nullptr; size_t avg_bytes = 0; bool avg_alloc_failed = false;
+    DcAvgRec avg = {};
 };
 
 __device__ __forceinline__ u32 dc_sb_of(u32 j, const DcSub& S)
@@ -187,9 +204,15 @@ template <> struct DcForm<DcSubTab> {
 // 1a. avg_rank >= 32 (qlfc.cpp:903 / :978): avg' = (avg * 124 + rank * 4) >> 7, reset per sub-block.  One lane per chunk,
 // two-sided bracket [0, 255] started DC_AVG_WARM runs early; the flag of a run is decided when both ends agree.
 // ---------------------------------------------------------------------------------------------------------------------
-template <class SB>
+// REC (the exact resolve, 1a'): the lane also leaves what the kernels behind it start from (DcAvgRec) — its bracket at j0, its undecided
+// count, whether a sub-block starts inside its chunk and whether the bracket is too wide to walk.  Off: the empty DcAvgNoRec, the
+// kernel as it was.
+struct DcAvgNoRec {};
+enum : u32 { DC_AVG_ST_START = 1 /* a sub-block starts inside the chunk: whatever it started from, it ends the same */, DC_AVG_ST_WIDE = 2 /* DC_AVG_CAND values or more */ };
+template <class SB, bool REC = false>
 __global__ __launch_bounds__(WG) void dc_avg_kernel(const u8* __restrict__ rank, u32 m, SB S, u8* __restrict__ ge32, u32* __restrict__ meta,
-                                                    u32* __restrict__ sub_und /* table only (may be null): undecided flags per sub-block */)
+                                                    u32* __restrict__ sub_und /* table only (may be null): undecided flags per sub-block */,
+                                                    typename std::conditional<REC, DcAvgRec, DcAvgNoRec>::type R)
 {
     typedef DcForm<SB> F;
     const u32 c = blockIdx.x * WG + threadIdx.x;
@@ -203,10 +226,13 @@ __global__ __launch_bounds__(WG) void dc_avg_kernel(const u8* __restrict__ rank,
     for (u32 j = w0; j < (u32)j0; ++j) { const u32 r = rank[j]; lo = avg_rank_next(lo, r); hi = avg_rank_next(hi, r); }
     u32 next_first = F::next_first(S, sb);                            // (a chunk of a batched pass can hold dozens of sub-block starts)
     u32 und = 0, und_flushed = 0;                                     // (table: what of und has gone to sub_und)
+    u32 st = 0;
+    if constexpr (REC) { R.brk[c] = (u16)(lo | hi << 8); if (hi - lo >= (u32)DC_AVG_CAND) st = DC_AVG_ST_WIDE; }
     for (u32 j = (u32)j0; j < j1; ++j) {
         if (j == next_first) {
             if constexpr (F::TAB) { if (sub_und && und != und_flushed) atomicAdd(&sub_und[sb], und - und_flushed); und_flushed = und; }
             lo = hi = 0; ++sb; next_first = F::next_first(S, sb);
+            if constexpr (REC) st |= DC_AVG_ST_START;
         }
         const u32 f = lo >= 32u;
         und += (f != (u32)(hi >= 32u));
@@ -216,6 +242,226 @@ __global__ __launch_bounds__(WG) void dc_avg_kernel(const u8* __restrict__ rank,
     }
     if constexpr (F::TAB) { if (sub_und && und != und_flushed) atomicAdd(&sub_und[sb], und - und_flushed); }
     if (und) atomicAdd(&meta[DM_AVG_UND], und);
+    if constexpr (REC) { R.und[c] = (u16)und; R.st[c] = (u8)st; }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// 1a'. the open flags resolved exactly (BSCGPU_OPT_DC_AVG_EXACT; devcoder_model.h: avg_resolve_host restates these kernels).
+// avg' is monotone in avg, so the exact value at a lane's first run lies in its bracket [lo0, hi0], and the bracket's width d obeys
+// d' <= floor(124 d / 128) + 1: from 255 it is at most 32 after 128 runs, so behind DC_AVG_WARM runs a lane has at most 33 candidates.
+// dc_avg_map_kernel walks a chunk once per candidate — its transfer map —, dc_avg_chain_kernel composes the maps of DC_AVG_GROUP
+// chunks, dc_avg_groups_kernel chains the groups, dc_avg_chain_kernel<true> hands every chunk its exact start and dc_avg_fix_kernel
+// walks the chunks with open flags again from theirs, one wavefront each.  All of them leave at once where nothing is open.
+// ---------------------------------------------------------------------------------------------------------------------
+// one wavefront per chunk whose successor starts open; lane v walks from lo0 + v.  The chunk has a successor, so it is whole:
+// DC_AVG_CH runs, 16 rank bytes per lane, handed round the wavefront as scalars (every lane walks the same runs)
+template <class SB>
+__global__ __launch_bounds__(WG) void dc_avg_map_kernel(const u8* __restrict__ rank, u32 m, SB S, DcAvgRec R)
+{
+    typedef DcForm<SB> F;
+    static_assert(DC_AVG_CAND == 64 && DC_AVG_CH == 64 * 16, "one candidate and 16 runs per lane");
+    const u32 c = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * WAVES + (threadIdx.x >> 6)));
+    const u32 lane = threadIdx.x & 63u;
+    const u32 nch = (m + DC_AVG_CH - 1) / DC_AVG_CH;
+    if (c + 1 >= nch) return;
+    const u32 bn = R.brk[c + 1];
+    if ((bn & 255u) == (bn >> 8)) return;                              // the successor starts exact: nobody reads this map
+    const u32 b = R.brk[c], lo0 = b & 255u, w = (b >> 8) - lo0;
+    if (w >= (u32)DC_AVG_CAND) return;                                 // the guard: not walked (DC_AVG_ST_WIDE says so to the chain)
+    const u32 j0 = c * DC_AVG_CH;
+    const u8* p = rank + j0 + 16u * lane;
+    u32 q[4];
+    if ((reinterpret_cast<uintptr_t>(rank) & 15u) == 0) {
+        const uint4 t = *reinterpret_cast<const uint4*>(p);
+        q[0] = t.x; q[1] = t.y; q[2] = t.z; q[3] = t.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = (u32)p[4 * k] | (u32)p[4 * k + 1] << 8 | (u32)p[4 * k + 2] << 16 | (u32)p[4 * k + 3] << 24;
+    }
+    u32 x = lo0 + (lane <= w ? lane : 0u);
+    u32 sb = 0, next_first = 0xffffffffu;
+    if (R.st[c] & DC_AVG_ST_START) { sb = dc_sb_of(j0, S); next_first = F::next_first(S, sb); }
+    for (u32 l = 0; l < 64u; ++l) {
+        u32 r[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[k] = (u32)__builtin_amdgcn_readlane((int)q[k], (int)l);
+        const u32 jb = j0 + 16u * l;
+        if (next_first - jb < 16u) {                                   // a sub-block starts in these 16 runs (maybe several)
+#pragma unroll
+            for (u32 k = 0; k < 16u; ++k) {
+                if (jb + k == next_first) { x = 0; ++sb; next_first = F::next_first(S, sb); }
+                x = avg_rank_next(x, (r[k >> 2] >> (8u * (k & 3u))) & 255u);
+            }
+        } else {
+#pragma unroll
+            for (u32 k = 0; k < 16u; ++k) x = avg_rank_next(x, (r[k >> 2] >> (8u * (k & 3u))) & 255u);
+        }
+    }
+    if (lane <= w) R.map[(size_t)c * DC_AVG_CAND + lane] = (u8)x;
+}
+
+// the exact start of chunk c + 1 from the exact start x of chunk c; brk1 / brk0 / st0: of chunk c + 1 / c / c, map0: chunk c's map
+__device__ __forceinline__ u32 dc_avg_step(u32 x, u32 brk1, u32 brk0, u32 st0, const u8* map0)
+{
+    if ((brk1 & 255u) == (brk1 >> 8)) return brk1 & 255u;             // a closed bracket restarts the chain
+    if (st0 & DC_AVG_ST_WIDE) return DC_AVG_UNKNOWN;
+    if (st0 & DC_AVG_ST_START) return map0[0];                         // ... and so does a sub-block start inside the chunk
+    return x == DC_AVG_UNKNOWN ? DC_AVG_UNKNOWN : (u32)map0[x - (brk0 & 255u)];
+}
+// One wavefront per group of DC_AVG_GROUP chunks, their maps in LDS.  HAND = false: lane v follows candidate v of the group's first
+// chunk through the group -> gmap[g][v], the start of the next group's first chunk (only where that one starts open).  HAND = true:
+// every lane follows the group's exact start (gstart[g]) and lane k keeps what chunk k starts from -> ex.
+template <bool HAND>
+__global__ __launch_bounds__(64) void dc_avg_chain_kernel(u32 m, DcAvgRec R)
+{
+    static_assert(DC_AVG_GROUP == 64 && DC_AVG_CAND == 64, "one chunk and one candidate per lane");
+    __shared__ u32 brk_s[DC_AVG_GROUP + 1], st_s[DC_AVG_GROUP];
+    __shared__ uint4 map_s[DC_AVG_GROUP * DC_AVG_CAND / 16];
+    const u32 g = blockIdx.x, lane = threadIdx.x, c0 = g * DC_AVG_GROUP;
+    const u32 nch = (m + DC_AVG_CH - 1) / DC_AVG_CH;
+    const u32 cnt = nch - c0 < (u32)DC_AVG_GROUP ? nch - c0 : (u32)DC_AVG_GROUP;      // chunks of this group
+    const u32 mine = lane < cnt ? (u32)R.brk[c0 + lane] : 0u;
+    if constexpr (HAND) {
+        if (__ballot(lane < cnt && (mine & 255u) != (mine >> 8)) == 0ull) {         // every chunk starts exact
+            if (lane < cnt) R.ex[c0 + lane] = (u16)(mine & 255u);
+            return;
+        }
+    } else {
+        if (c0 + DC_AVG_GROUP >= nch) return;
+        const u32 bn = R.brk[c0 + DC_AVG_GROUP];
+        if ((bn & 255u) == (bn >> 8)) return;
+    }
+    brk_s[lane] = mine; st_s[lane] = lane < cnt ? (u32)R.st[c0 + lane] : 0u;
+    if (lane == 0) brk_s[DC_AVG_GROUP] = c0 + DC_AVG_GROUP < nch ? (u32)R.brk[c0 + DC_AVG_GROUP] : 0u;
+    const uint4* src = reinterpret_cast<const uint4*>(R.map + (size_t)c0 * DC_AVG_CAND);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) map_s[k * 64 + lane] = src[k * 64 + lane];            // (the arrays are padded to whole groups)
+    __syncthreads();
+    const u8* maps = reinterpret_cast<const u8*>(map_s);
+    u32 x, keep = 0;
+    if constexpr (HAND) x = R.gstart[g];
+    else x = (!(st_s[0] & DC_AVG_ST_WIDE) && lane <= (brk_s[0] >> 8) - (brk_s[0] & 255u)) ? (brk_s[0] & 255u) + lane : DC_AVG_UNKNOWN;
+    for (u32 k = 0; k < cnt; ++k) {
+        if (HAND && lane == k) keep = x;
+        if (c0 + k + 1 >= nch) break;
+        x = dc_avg_step(x, brk_s[k + 1], brk_s[k], st_s[k], maps + k * DC_AVG_CAND);
+    }
+    if constexpr (HAND) { if (lane < cnt) R.ex[c0 + lane] = (u16)keep; }
+    else R.gmap[(size_t)g * DC_AVG_CAND + lane] = (u16)x;
+}
+// the groups chained: one wavefront, 64 groups' maps at a time in LDS, the walk itself on one value
+__global__ __launch_bounds__(64) void dc_avg_groups_kernel(u32 m, DcAvgRec R)
+{
+    __shared__ u32 first_s[65], wide_s[64];
+    __shared__ uint4 gmap_s[64 * DC_AVG_CAND * 2 / 16];
+    const u32 lane = threadIdx.x;
+    const u32 nch = (m + DC_AVG_CH - 1) / DC_AVG_CH, ngr = (nch + DC_AVG_GROUP - 1) / DC_AVG_GROUP;
+    u32 x = (u32)R.brk[0] & 255u;                                      // (chunk 0 starts a sub-block)
+    for (u32 g0 = 0; g0 < ngr; g0 += 64u) {
+        const u32 cnt = ngr - g0 < 64u ? ngr - g0 : 64u;
+        // lane i: group g0 + i, and the first chunk of the group behind it
+        const u32 nf = g0 + lane + 1 < ngr ? (u32)R.brk[(g0 + lane + 1) * DC_AVG_GROUP] : 0u;
+        const bool any_open = __ballot((nf & 255u) != (nf >> 8)) != 0ull;
+        __syncthreads();
+        first_s[lane + 1] = nf;
+        if (any_open) {
+            if (lane == 0) first_s[0] = (u32)R.brk[g0 * DC_AVG_GROUP];
+            wide_s[lane] = lane < cnt ? (u32)R.st[(g0 + lane) * DC_AVG_GROUP] & DC_AVG_ST_WIDE : 0u;
+            const uint4* src = reinterpret_cast<const uint4*>(R.gmap + (size_t)g0 * DC_AVG_CAND);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) gmap_s[k * 64 + lane] = src[k * 64 + lane];    // (padded to 64 groups)
+        }
+        __syncthreads();
+        if (!any_open) {                                               // every group of the tile starts exact
+            if (lane == 0) R.gstart[g0] = (u16)x;
+            if (lane + 1 < cnt) R.gstart[g0 + lane + 1] = (u16)(nf & 255u);
+            x = first_s[cnt] & 255u;                                   // (the tile behind starts from its own first chunk's bracket, if there is one)
+            continue;
+        }
+        const u16* gm = reinterpret_cast<const u16*>(gmap_s);
+        u32 keep = 0;
+        for (u32 k = 0; k < cnt; ++k) {
+            if (lane == k) keep = x;
+            if (g0 + k + 1 >= ngr) break;
+            const u32 b1 = first_s[k + 1], b0 = first_s[k];
+            if ((b1 & 255u) == (b1 >> 8)) x = b1 & 255u;
+            else x = (x == DC_AVG_UNKNOWN || wide_s[k]) ? DC_AVG_UNKNOWN : (u32)gm[k * DC_AVG_CAND + (x - (b0 & 255u))];
+        }
+        if (lane < cnt) R.gstart[g0 + lane] = (u16)keep;
+    }
+}
+// one wavefront per chunk with open flags: again from its exact start, the ranks handed round as in dc_avg_map_kernel (a lane that
+// walked alone would wait for every byte: 0.40 ms where every chunk of an 8 MiB block is open, against 0.18), every lane on the same values and lane l
+// keeping the flags of runs 16 l ..  An unknown start (the guard) leaves the flags as they are and counts them: DM_AVG_LEFT, and per
+// sub-block where the table form asks
+template <class SB>
+__global__ __launch_bounds__(WG) void dc_avg_fix_kernel(const u8* __restrict__ rank, u32 m, SB S, u8* __restrict__ ge32, u32* __restrict__ meta,
+                                                        u32* __restrict__ sub_und, DcAvgRec R)
+{
+    typedef DcForm<SB> F;
+    const u32 c = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * WAVES + (threadIdx.x >> 6)));
+    const u32 lane = threadIdx.x & 63u;
+    const u32 nch = (m + DC_AVG_CH - 1) / DC_AVG_CH;
+    if (c >= nch) return;
+    const u32 und = R.und[c];
+    if (und == 0) return;
+    const u32 j0 = c * DC_AVG_CH, j1 = (m - j0 > (u32)DC_AVG_CH) ? j0 + DC_AVG_CH : m;
+    const u32 b = R.brk[c], e = R.ex[c];
+    const bool known = e != DC_AVG_UNKNOWN;
+    u32 lo = b & 255u, hi = b >> 8, x = known ? e : lo;
+    const u32 at = j0 + 16u * lane;                                    // this lane's 16 runs (the last chunk may end inside or in front of them)
+    u32 q[4];
+    if (at + 16u <= j1 && (reinterpret_cast<uintptr_t>(rank) & 15u) == 0) {
+        const uint4 t = *reinterpret_cast<const uint4*>(rank + at);
+        q[0] = t.x; q[1] = t.y; q[2] = t.z; q[3] = t.w;
+    } else {
+#pragma unroll
+        for (u32 k = 0; k < 4u; ++k) {
+            q[k] = 0;
+#pragma unroll
+            for (u32 i = 0; i < 4u; ++i) if (at + 4u * k + i < j1) q[k] |= (u32)rank[at + 4u * k + i] << (8u * i);
+        }
+    }
+    u32 sb = dc_sb_of(j0, S);
+    u32 next_first = F::next_first(S, sb);
+    u32 left = 0, mine = 0;
+    const u32 pieces = (j1 - j0 + 15u) / 16u;
+    for (u32 l = 0; l < pieces; ++l) {
+        u32 r[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[k] = (u32)__builtin_amdgcn_readlane((int)q[k], (int)l);
+        const u32 jb = j0 + 16u * l;
+        u32 bits = 0;
+#pragma unroll
+        for (u32 k = 0; k < 16u; ++k) {
+            if (jb + k < j1) {
+                if (jb + k == next_first) {
+                    if constexpr (F::TAB) { if (sub_und && left && lane == 0) atomicAdd(&sub_und[sb], left); }
+                    left = 0; lo = hi = x = 0; ++sb; next_first = F::next_first(S, sb);
+                }
+                left += (u32)(!known && (lo >= 32u) != (hi >= 32u));
+                bits |= (u32)(x >= 32u) << k;
+                const u32 rk = (r[k >> 2] >> (8u * (k & 3u))) & 255u;
+                lo = avg_rank_next(lo, rk); hi = avg_rank_next(hi, rk); x = avg_rank_next(x, rk);
+            }
+        }
+        if (lane == l) mine = bits;
+    }
+    if (lane == 0) {
+        if constexpr (F::TAB) { if (sub_und && left) atomicAdd(&sub_und[sb], left); }
+        atomicAdd(&meta[known ? DM_AVG_RESOLVED : DM_AVG_LEFT], und);
+    }
+    if (!known) return;
+    if (at + 16u <= j1 && (reinterpret_cast<uintptr_t>(ge32) & 15u) == 0) {
+        uint4 t;
+        t.x = (mine & 1u) | (mine & 2u) << 7 | (mine & 4u) << 14 | (mine & 8u) << 21;
+        t.y = (mine >> 4 & 1u) | (mine >> 4 & 2u) << 7 | (mine >> 4 & 4u) << 14 | (mine >> 4 & 8u) << 21;
+        t.z = (mine >> 8 & 1u) | (mine >> 8 & 2u) << 7 | (mine >> 8 & 4u) << 14 | (mine >> 8 & 8u) << 21;
+        t.w = (mine >> 12 & 1u) | (mine >> 12 & 2u) << 7 | (mine >> 12 & 4u) << 14 | (mine >> 12 & 8u) << 21;
+        *reinterpret_cast<uint4*>(ge32 + at) = t;
+    } else {
+        for (u32 k = 0; k < 16u; ++k) if (at + k < j1) ge32[at + k] = (u8)(mine >> k & 1u);
+    }
 }
 
 // 1b. packed items in stream order: X = symbol (the char family's sort digit; the static family ignores it)
@@ -339,7 +585,8 @@ __global__ __launch_bounds__(WG) void dc_ctx_kernel(const u64* __restrict__ key_
 
 // 1d. the canonical rounds that occur (and how many decision types: diagnostics).  One workgroup.
 template <class SB>
-__global__ __launch_bounds__(WG) void dc_setup_kernel(const u32* __restrict__ kinds, SB S, u8* __restrict__ rounds, u32* __restrict__ meta)
+__global__ __launch_bounds__(WG) void dc_setup_kernel(const u32* __restrict__ kinds, SB S, u8* __restrict__ rounds, u32* __restrict__ meta,
+                                                      u32 avg_word /* DM_AVG_UND, or DM_AVG_LEFT behind the exact resolve */)
 {
     typedef DcForm<SB> F;
     const u32 mrp = F::maxr_word(S);                                  // max_rank of the eight sub-blocks, one scalar word
@@ -391,7 +638,7 @@ __global__ __launch_bounds__(WG) void dc_setup_kernel(const u32* __restrict__ ki
         u32 nr = 0;
         for (int r = 0; r < NUM_ROUNDS; ++r) if (rbits[r >> 5] & (1u << (r & 31))) rounds[nr++] = (u8)r;
         meta[DM_NTYPES] = ntypes; meta[DM_NROUNDS] = nr;
-        if (meta[DM_AVG_UND] != 0u) atomicOr(&meta[DM_FAIL], (u32)FAIL_AVG);
+        if (meta[avg_word] != 0u) atomicOr(&meta[DM_FAIL], (u32)FAIL_AVG);
     }
 }
 
@@ -1488,6 +1735,7 @@ void devcoder_destroy(bscgpu_ctx* c)
     if (!d) return;
     if (d->arena) hipFree(d->arena);
     if (d->batch_arena) hipFree(d->batch_arena);
+    if (d->avg_arena) hipFree(d->avg_arena);
     for (int k = 0; k < 2; ++k) if (d->seg_ev[k]) hipEventDestroy(d->seg_ev[k]);
     if (d->hmeta) hipHostFree(d->hmeta);
     delete d;
@@ -1587,7 +1835,7 @@ int devcoder_ensure(bscgpu_ctx* c)
 }
 
 int64_t devcoder_arena_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)c->dc->arena_bytes : 0; }
-int64_t devcoder_batch_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)c->dc->batch_bytes : 0; }
+int64_t devcoder_batch_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)(c->dc->batch_bytes + c->dc->avg_bytes) : 0; }
 
 // One partition job: counts, scans, scatter.  SCATTER = false: counts and scans only, then the runs' offsets in the stream
 // (dc_doff_kernel) — all the fast coder needs of job 0, whose events nobody reads.
@@ -1616,6 +1864,51 @@ static void dc_note_block(bscgpu_ctx* c, const DevCoder* d)
     c->dc_replays = (int)d->hmeta[DM_REPLAYS];
     c->dc_avg_und = (int)d->hmeta[DM_AVG_UND];
     c->dc_hist_ext = (int)d->hmeta[DM_HIST_EXT];
+    c->dc_avg_resolved = (int)d->hmeta[DM_AVG_RESOLVED];
+}
+
+// ---- the avg_rank flags of m runs (1a), and with BSCGPU_OPT_DC_AVG_EXACT the exact resolve behind them (1a') ---------------------------
+// The resolve's buffers, on the first call that asks for it.  Do not fit: the unit is declined, as for the batch arena.
+static int devcoder_avg_ensure(DevCoder* d)
+{
+    if (d->avg_arena) return BSC_NO_ERROR;
+    if (d->avg_alloc_failed) return BSC_NOT_SUPPORTED;
+    // chunks padded to whole groups, groups to the 64 that dc_avg_groups_kernel loads at a time
+    const size_t NC = (d->Mcap / DC_AVG_CH + 1 + DC_AVG_GROUP) / DC_AVG_GROUP * DC_AVG_GROUP + DC_AVG_GROUP, NG = (NC / DC_AVG_GROUP + 64) / 64 * 64 + 64;
+    struct Carve { void** p; size_t bytes; };
+    Carve carve[] = {
+        {(void**)&d->avg.brk, 2 * NC}, {(void**)&d->avg.und, 2 * NC}, {(void**)&d->avg.st, NC}, {(void**)&d->avg.ex, 2 * NC},
+        {(void**)&d->avg.map, (size_t)DC_AVG_CAND * NC}, {(void**)&d->avg.gmap, 2 * (size_t)DC_AVG_CAND * NG}, {(void**)&d->avg.gstart, 2 * NG},
+    };
+    size_t total = 0;
+    for (auto& cv : carve) total += dc_align(cv.bytes);
+    if (hipMalloc((void**)&d->avg_arena, total) != hipSuccess) {
+        (void)hipGetLastError(); d->avg_arena = nullptr; d->avg_alloc_failed = true;
+        return BSC_NOT_SUPPORTED;
+    }
+    d->avg_bytes = total;
+    size_t off = 0;
+    for (auto& cv : carve) { *cv.p = d->avg_arena + off; off += dc_align(cv.bytes); }
+    return BSC_NO_ERROR;
+}
+// No sync: the resolve's kernels are launched whether or not a flag is open, and leave at once where none is.
+template <class SB>
+static int dc_launch_avg(bscgpu_ctx* c, DevCoder* d, const u8* drank, u32 m, const SB& S, u32* sub_und)
+{
+    const u32 nch = (m + DC_AVG_CH - 1) / DC_AVG_CH, ngr = (nch + DC_AVG_GROUP - 1) / DC_AVG_GROUP;
+    if (!c->dc_avg_exact) {
+        hipLaunchKernelGGL(dc_avg_kernel<SB>, dim3((nch + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta, sub_und, DcAvgNoRec{});
+        return BSC_NO_ERROR;
+    }
+    const int rc = devcoder_avg_ensure(d);
+    if (rc < 0) return rc;
+    hipLaunchKernelGGL((dc_avg_kernel<SB, true>), dim3((nch + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta, (u32*)nullptr, d->avg);
+    if (nch > 1) hipLaunchKernelGGL(dc_avg_map_kernel<SB>, dim3((nch - 1 + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, drank, m, S, d->avg);
+    if (ngr > 1) hipLaunchKernelGGL(dc_avg_chain_kernel<false>, dim3(ngr - 1), dim3(64), 0, c->stream, m, d->avg);
+    hipLaunchKernelGGL(dc_avg_groups_kernel, dim3(1), dim3(64), 0, c->stream, m, d->avg);
+    hipLaunchKernelGGL(dc_avg_chain_kernel<true>, dim3(ngr), dim3(64), 0, c->stream, m, d->avg);
+    hipLaunchKernelGGL(dc_avg_fix_kernel<SB>, dim3((nch + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta, sub_und, d->avg);
+    return BSC_NO_ERROR;
 }
 
 // One of the bodies' two syncs: meta comes down (and whatever rides with it: DcDown), the finished brackets are folded, the context
@@ -1722,7 +2015,8 @@ static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym
     prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
     hipLaunchKernelGGL(dc_ctx_kernel<SB>, dim3(gm8), dim3(WG), 0, c->stream, d->key_ch, d->key_ch_s, d->inv_ch, m, S, d->tab_rank, d->tab_run,
                        d->key_sr, d->key_sn, d->present, d->meta);
-    hipLaunchKernelGGL(dc_setup_kernel<SB>, dim3(1), dim3(WG), 0, c->stream, d->present, S, d->rounds, d->meta);
+    hipLaunchKernelGGL(dc_setup_kernel<SB>, dim3(1), dim3(WG), 0, c->stream, d->present, S, d->rounds, d->meta,
+                       (u32)(c->dc_avg_exact ? DM_AVG_LEFT : DM_AVG_UND));
     prof_end(c);
     rc = radix_sort_passes(c, d->key_sr, d->key_sr_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_sr);
     if (rc < 0) return rc;
@@ -1882,7 +2176,7 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
     int rc = devcoder_ensure(c);
     if (rc < 0) return rc;
     DevCoder* d = c->dc;
-    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = 0;
+    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = c->dc_avg_resolved = 0;
     c->dc_last_fail = m > d->Mcap ? (int)FAIL_CAP : 0;                 // (more runs than the arena holds: capacity, as too many decisions are)
     if (m == 0 || m > d->Mcap || nb < 1 || nb > 8) return BSC_NOT_SUPPORTED;
     const bool fast = coder == 3;
@@ -1898,9 +2192,10 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
     // sub-block the average never reaches 32 and the escape coding (qlfc.cpp:960) cannot occur; the fast coder has none
     bool may_escape = false;
     for (int b = 0; b < nb && !fast; ++b) may_escape |= max_rank[b] > 4;
-    if (may_escape)
-        hipLaunchKernelGGL(dc_avg_kernel<DcSub>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta, (u32*)nullptr);
-    else
+    if (may_escape) {
+        rc = dc_launch_avg(c, d, drank, m, S, (u32*)nullptr);
+        if (rc < 0) { prof_end(c); return rc; }
+    } else
         HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));
     rc = fast ? dc_fast_run(c, d, S, dsym, drank, dstart, d->ge32, m, n, true, psbuf, -1, nullptr, D_out)
               : dc_static_run(c, d, S, dsym, drank, dstart, d->ge32, m, n, true, psbuf, -1, nullptr, dbg, packed_out, D_out);
@@ -1950,7 +2245,7 @@ static int dc_pass_begin(bscgpu_ctx* c, u32 m, int nsub, int over_fail, DcPass* 
     if (rc < 0) return rc;
     DevCoder* d = c->dc;
     if (over_fail >= 0) {
-        c->dc_replays = c->dc_avg_und = c->dc_hist_ext = 0;
+        c->dc_replays = c->dc_avg_und = c->dc_hist_ext = c->dc_avg_resolved = 0;
         c->dc_last_fail = m > d->Mcap ? over_fail : 0;
     }
     if (m == 0 || m > d->Mcap || nsub < 1 || nsub > FRONT_MAX_SUB || !c->front_tab) return BSC_NOT_SUPPORTED;
@@ -1984,7 +2279,10 @@ int devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* D_out
     // (the static coder, always: which sub-blocks can escape is not known on the host here; one of at most 32 symbols never leaves a
     // flag open — avg_top.  No escape coding in the fast coder)
     if (fast) HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));
-    else hipLaunchKernelGGL(dc_avg_kernel<DcSubTab>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, P.drank, m, P.S, d->ge32, d->meta, (u32*)nullptr);
+    else {
+        const int arc = dc_launch_avg(c, d, P.drank, m, P.S, (u32*)nullptr);
+        if (arc < 0) { prof_end(c); return arc; }
+    }
     prof_end(c);
     if (fast) return dc_fast_run(c, d, P.S, P.dsym, P.drank, P.dstart, d->ge32, m, 0u, false, 0, -1, nullptr, D_out);
     const int src = dc_static_run(c, d, P.S, P.dsym, P.drank, P.dstart, d->ge32, m, 0u, false, 0, -1, nullptr, nullptr, packed_out, D_out);
@@ -2012,7 +2310,7 @@ const u32* devcoder_batch_pbase_ptr(const bscgpu_ctx* c) { return c->dc ? c->dc-
 // has been re-launched in the 2-byte form by dc_static_run: its entries come down to a scratch vector and bscgpu_pstream_pack13_host
 // packs them into place — the caller sees one form, the blocks keep the device's model; counted in cnt_packed_void.
 // the facts of a pass (after qlfc_front_batch): dec[s] / und[s] of every sub-block on the host; ge32 and sub_maxr stay for the segments
-static int dc_segment_facts(bscgpu_ctx* c, const DcPass& P, u32 m, bool fast, u32* dec, u32* und)
+static int dc_segment_facts(bscgpu_ctx* c, const DcPass& P, u32 m, bool fast, u32* dec, u32* und, u32* avg_open = nullptr, u32* avg_resolved = nullptr)
 {
     DevCoder* d = P.d;
     const int nsub = (int)P.S.nsub;
@@ -2022,14 +2320,20 @@ static int dc_segment_facts(bscgpu_ctx* c, const DcPass& P, u32 m, bool fast, u3
     prof_begin(c, BSCGPU_K_DC_FACTS, (u64)m * 6, m);
     hipLaunchKernelGGL(dc_tab_prep_kernel, dim3(((u32)nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, P.T.first_run, (u32)nsub, m, fast ? 7 : -1, d->sub_maxr, P.T.sub_run);
     if (fast) HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));
-    else hipLaunchKernelGGL(dc_avg_kernel<DcSubTab>, dim3(((m + DC_AVG_CH - 1) / DC_AVG_CH + WG - 1) / WG), dim3(WG), 0, c->stream, P.drank, m, P.S, d->ge32, d->meta, d->sub_und);
+    else {
+        const int arc = dc_launch_avg(c, d, P.drank, m, P.S, d->sub_und);      // (with the exact resolve: what is left behind it)
+        if (arc < 0) { prof_end(c); return arc; }
+    }
     hipLaunchKernelGGL(dc_sub_dec_kernel, dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, P.dsym, P.drank, P.dstart, d->ge32, m, P.S, d->sub_dec);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(und, d->sub_und, (size_t)nsub * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(dec, d->sub_dec, (size_t)nsub * 4, hipMemcpyDeviceToHost, c->stream));
+    // (behind the exact resolve und[] is what it left: what the bracket had left open, and what was settled, are meta words)
+    if (c->dc_avg_exact && avg_open) HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
     prof_collect(c);
+    if (c->dc_avg_exact && avg_open) { *avg_open = d->hmeta[DM_AVG_UND]; *avg_resolved = d->hmeta[DM_AVG_RESOLVED]; }
     return BSC_NO_ERROR;
 }
 int devcoder_segment_facts(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* dec, u32* und)
@@ -2057,10 +2361,12 @@ int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub
     const bool fast = coder == 3;                                      // LIBBSC_CODER_QLFC_FAST
 
     std::vector<u32> und((size_t)nsub), dec((size_t)nsub);
-    rc = dc_segment_facts(c, P, m, fast, dec.data(), und.data());
+    u32 avg_open = 0, avg_resolved = 0;
+    rc = dc_segment_facts(c, P, m, fast, dec.data(), und.data(), &avg_open, &avg_resolved);
     if (rc < 0) return rc;
     int64_t und_total = 0;
     for (int s = 0; s < nsub; ++s) und_total += und[s];
+    if (c->dc_avg_exact) und_total = avg_open;
 
     // the plan
     std::vector<int> seg_of((size_t)count);
@@ -2199,7 +2505,7 @@ int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub
     fill_to(nsub);
     int fail = 0, host_blocks = 0;
     for (int b = 0; b < count; ++b) if (blk_state[b]) { fail |= blk_state[b]; ++host_blocks; }
-    c->dc_last_fail = fail; c->dc_replays = replays; c->dc_hist_ext = hist_ext; c->dc_avg_und = (int)und_total;
+    c->dc_last_fail = fail; c->dc_replays = replays; c->dc_hist_ext = hist_ext; c->dc_avg_und = (int)und_total; c->dc_avg_resolved = (int)avg_resolved;
     c->cnt_seg += kept; c->cnt_seg_reruns += reruns; c->cnt_seg_host_blocks += host_blocks;
     c->cnt_packed_passes += kept_packed; c->cnt_packed_void += kept_void;
     if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder segments] sub-blocks %d, planned %d, kept %d, re-runs %d, blocks left to the host %d, decisions %lld\n", nsub, nseg, kept, reruns, host_blocks, (long long)base_dec);

@@ -21,6 +21,7 @@
 // wavefront emit the decisions of 64 runs round by round and rank them stably with ballots.
 #pragma once
 #include <stdint.h>
+#include <vector>
 
 #if defined(__HIPCC__)
 #define DC_HD __host__ __device__ __forceinline__
@@ -352,6 +353,10 @@ constexpr int DC_EB          = 64;       // events per lane per batch of the eva
 constexpr int DC_REPLAY_MAX  = 64;       // chunks a serial replay walks back before the block is declined (FAIL_REPLAY)
 constexpr int DC_AVG_CH      = 1024;     // runs per avg_rank lane
 constexpr int DC_AVG_WARM    = 768;      // warm-up runs in front of an avg_rank chunk
+constexpr int DC_AVG_CAND    = 64;       // exact resolve: start values a lane's chunk is walked from, one per lane of a wavefront (the bracket
+                                         // behind DC_AVG_WARM runs is at most 32 wide: 33 candidates; a wider one is not resolved)
+constexpr int DC_AVG_GROUP   = 64;       // exact resolve: consecutive chunks whose transfer maps one wavefront composes
+constexpr uint32_t DC_AVG_UNKNOWN = 0xffffu;   // exact resolve: a chunk's start value behind a bracket too wide to walk (the guard)
 constexpr int DC_HIST_NP     = 9;        // predecessors of a run's symbol that the run_hist bracket always walks
 constexpr int DC_HIST_KMAX   = 4096;     // the extended look-back quadruples from 4 DC_HIST_NP and gives up (FAIL_HIST) at the first K >= this
 // events per evaluation chunk of a block with Etot events over all jobs
@@ -360,6 +365,115 @@ inline uint32_t eval_chunk_events(uint64_t Etot)
     uint64_t ev = (Etot + 64ull * DC_EVAL_WAVES_TARGET - 1) / (64ull * DC_EVAL_WAVES_TARGET);
     ev = (ev + DC_EB - 1) / DC_EB * DC_EB;
     return ev < (uint64_t)DC_EV ? (uint32_t)DC_EV : (uint32_t)ev;
+}
+
+// ---- avg_rank flags resolved exactly (devcoder.hip 1a': dc_avg_map_kernel .. dc_avg_fix_kernel), restated for the host -------------------
+// rank[0 .. m): the ranks of the runs; first_run[0 .. nsub]: first run of every sub-block (strictly increasing, first_run[nsub] = m);
+// top[s]: upper end a bracket inside sub-block s starts from (255, or 2^(max_rank + 1) - 1 for a table).  The same steps in the same
+// order as the kernels: (1) every chunk of DC_AVG_CH runs walks its bracket from DC_AVG_WARM runs early, notes the bracket at its first
+// run (lo0, hi0), writes the lower end's flags and counts the runs whose ends disagree; (2) a chunk whose successor starts open is
+// walked from every value of its own start bracket: its transfer map; (3) the maps of DC_AVG_GROUP chunks are composed, the groups
+// chained, every chunk handed its exact start (a closed bracket and a sub-block start inside a chunk restart the chain); (4) a chunk
+// with open flags is walked again from its exact start.  A bracket of DC_AVG_CAND values or more is not walked: what follows it stays
+// DC_AVG_UNKNOWN until the chain restarts, and the open flags of such chunks are `left`.
+struct AvgResolve {
+    uint64_t und = 0, resolved = 0, left = 0;      // flags the bracket left open; of those: settled exactly, not settled (the guard)
+    uint32_t max_width = 0;                        // widest start bracket (hi0 - lo0) of any chunk
+    uint32_t chain_steps = 0;                      // longest dependent path: steps inside a group + groups chained + steps inside a group
+    std::vector<uint16_t> lo0, hi0, exact;         // per chunk
+    std::vector<uint32_t> sub_left;                // per sub-block: flags left open
+};
+inline void avg_resolve_host(const uint8_t* rank, uint32_t m, const uint32_t* first_run, uint32_t nsub, const uint32_t* top, uint8_t* ge32, AvgResolve& R)
+{
+    const uint32_t nch = (m + DC_AVG_CH - 1) / DC_AVG_CH, ngr = (nch + DC_AVG_GROUP - 1) / DC_AVG_GROUP;
+    R = AvgResolve();
+    R.lo0.assign(nch, 0); R.hi0.assign(nch, 0); R.exact.assign(nch, 0); R.sub_left.assign(nsub, 0);
+    std::vector<uint16_t> und(nch, 0);
+    std::vector<uint8_t> has_start(nch, 0), map((size_t)nch * DC_AVG_CAND, 0);
+    auto sb_of = [&](uint32_t j) { uint32_t s = 0; while (s + 1 < nsub && j >= first_run[s + 1]) ++s; return s; };
+    auto open = [&](uint32_t c) { return R.lo0[c] != R.hi0[c]; };
+    auto wide = [&](uint32_t c) { return (uint32_t)(R.hi0[c] - R.lo0[c]) >= (uint32_t)DC_AVG_CAND; };
+    // (1) dc_avg_kernel
+    for (uint32_t c = 0; c < nch; ++c) {
+        const uint32_t j0 = c * DC_AVG_CH, j1 = j0 + DC_AVG_CH < m ? j0 + DC_AVG_CH : m;
+        uint32_t sb = sb_of(j0);
+        const uint32_t w0 = j0 > first_run[sb] + DC_AVG_WARM ? j0 - DC_AVG_WARM : first_run[sb];
+        uint32_t lo = 0, hi = w0 == first_run[sb] ? 0u : top[sb];
+        for (uint32_t j = w0; j < j0; ++j) { lo = avg_rank_next(lo, rank[j]); hi = avg_rank_next(hi, rank[j]); }
+        R.lo0[c] = (uint16_t)lo; R.hi0[c] = (uint16_t)hi;
+        if (hi - lo > R.max_width) R.max_width = hi - lo;
+        for (uint32_t j = j0; j < j1; ++j) {
+            if (sb + 1 < nsub && j == first_run[sb + 1]) { lo = hi = 0; ++sb; has_start[c] = 1; }
+            und[c] += (lo >= 32u) != (hi >= 32u);
+            ge32[j] = (uint8_t)(lo >= 32u);
+            lo = avg_rank_next(lo, rank[j]); hi = avg_rank_next(hi, rank[j]);
+        }
+        R.und += und[c];
+    }
+    // (2) dc_avg_map_kernel
+    for (uint32_t c = 0; c + 1 < nch; ++c) {
+        if (!open(c + 1) || wide(c)) continue;
+        const uint32_t j0 = c * DC_AVG_CH;
+        for (uint32_t v = 0; v <= (uint32_t)(R.hi0[c] - R.lo0[c]); ++v) {
+            uint32_t x = R.lo0[c] + v, sb = sb_of(j0);
+            for (uint32_t j = j0; j < j0 + DC_AVG_CH; ++j) {
+                if (sb + 1 < nsub && j == first_run[sb + 1]) { x = 0; ++sb; }
+                x = avg_rank_next(x, rank[j]);
+            }
+            map[(size_t)c * DC_AVG_CAND + v] = (uint8_t)x;
+        }
+    }
+    // the exact start of chunk c + 1 from that of chunk c (dc_avg_step)
+    auto step = [&](uint32_t c, uint32_t x) -> uint32_t {
+        if (!open(c + 1)) return R.lo0[c + 1];
+        if (wide(c)) return DC_AVG_UNKNOWN;
+        if (has_start[c]) return map[(size_t)c * DC_AVG_CAND];
+        return x == DC_AVG_UNKNOWN ? DC_AVG_UNKNOWN : map[(size_t)c * DC_AVG_CAND + (x - R.lo0[c])];
+    };
+    // (3) dc_avg_chain_kernel<false>, dc_avg_groups_kernel, dc_avg_chain_kernel<true>
+    std::vector<uint16_t> gmap((size_t)ngr * DC_AVG_CAND, 0), gstart(ngr, 0);
+    uint32_t in_group = 0, across = 0, across_now = 0;
+    for (uint32_t g = 0; g + 1 < ngr; ++g) {
+        const uint32_t c0 = g * DC_AVG_GROUP;
+        if (!open(c0 + DC_AVG_GROUP)) continue;
+        for (uint32_t v = 0; v < (uint32_t)DC_AVG_CAND; ++v) {
+            uint32_t x = (!wide(c0) && v <= (uint32_t)(R.hi0[c0] - R.lo0[c0])) ? R.lo0[c0] + v : DC_AVG_UNKNOWN;
+            for (uint32_t c = c0; c < c0 + DC_AVG_GROUP; ++c) x = step(c, x);
+            gmap[(size_t)g * DC_AVG_CAND + v] = (uint16_t)x;
+        }
+        in_group = DC_AVG_GROUP;
+    }
+    if (ngr) gstart[0] = R.lo0[0];
+    for (uint32_t g = 0; g + 1 < ngr; ++g) {
+        const uint32_t c0 = g * DC_AVG_GROUP, x = gstart[g];
+        if (!open(c0 + DC_AVG_GROUP)) { gstart[g + 1] = R.lo0[c0 + DC_AVG_GROUP]; across_now = 0; continue; }
+        gstart[g + 1] = (x == DC_AVG_UNKNOWN || wide(c0)) ? (uint16_t)DC_AVG_UNKNOWN : gmap[(size_t)g * DC_AVG_CAND + (x - R.lo0[c0])];
+        if (++across_now > across) across = across_now;
+    }
+    for (uint32_t g = 0; g < ngr; ++g) {
+        uint32_t x = gstart[g];
+        for (uint32_t c = g * DC_AVG_GROUP; c < nch && c < (g + 1) * DC_AVG_GROUP; ++c) {
+            R.exact[c] = (uint16_t)x;
+            if (c + 1 == nch) break;
+            if (open(c + 1) && c % DC_AVG_GROUP + 1 > in_group) in_group = c % DC_AVG_GROUP + 1;
+            x = step(c, x);
+        }
+    }
+    R.chain_steps = across ? 2 * DC_AVG_GROUP + across : in_group;
+    // (4) dc_avg_fix_kernel
+    for (uint32_t c = 0; c < nch; ++c) {
+        if (!und[c]) continue;
+        const uint32_t j0 = c * DC_AVG_CH, j1 = j0 + DC_AVG_CH < m ? j0 + DC_AVG_CH : m;
+        const bool known = R.exact[c] != DC_AVG_UNKNOWN;
+        uint32_t lo = R.lo0[c], hi = R.hi0[c], x = known ? R.exact[c] : lo, sb = sb_of(j0);
+        for (uint32_t j = j0; j < j1; ++j) {
+            if (sb + 1 < nsub && j == first_run[sb + 1]) { lo = hi = x = 0; ++sb; }
+            if (!known && (lo >= 32u) != (hi >= 32u)) ++R.sub_left[sb];
+            ge32[j] = (uint8_t)(x >= 32u);
+            lo = avg_rank_next(lo, rank[j]); hi = avg_rank_next(hi, rank[j]); x = avg_rank_next(x, rank[j]);
+        }
+        (known ? R.resolved : R.left) += und[c];
+    }
 }
 
 // p-stream entry handed to the range coder: [11:0] probability, [12] bit, [13] first decision of a run
