@@ -63,7 +63,11 @@ BSCGPU_API int bscgpu_bwt_first_sort_device(bscgpu_ctx* ctx, const void* dT, int
 
 /* ---- inverse BWT (libcubwt_unbwt's role, libcubwt.cuh:91-104; reached from bsc_bwt_decode, bwt.cpp:233-281) ---------- */
 /* L[0..n) and the 1-based primary index as bsc_bwt_encode writes them -> T[0..n); host pointers, may alias; synchronous.
- * Returns 0, LIBBSC_DATA_CORRUPT (-6) when the rows do not form one cycle through the sentinel row, or another libbsc code. */
+ * Returns 0, LIBBSC_DATA_CORRUPT (-6) when the rows 0..n do not form one cycle through the sentinel row (T is then not written; the
+ * same verdict, and on 0 the same text, as bsc_bwt_decode's host walk), LIBBSC_NOT_SUPPORTED (-4) when a piece of the cycle between two
+ * marked rows is longer than the step cap (T not written: use the host walk), or another libbsc code.
+ * BSC_UNBWT_STEP_CAP in the environment (read when a context is created; values below 16 are ignored): the step cap, 1 << 22 by
+ * default.  A test knob: no constructible input reaches the default, so a small cap is what drives the LIBBSC_NOT_SUPPORTED exits. */
 BSCGPU_API int bscgpu_unbwt(bscgpu_ctx* ctx, const uint8_t* L, uint8_t* T, int64_t n, int64_t index);
 
 /* ---- Sort Transform (order k = 3..8) ----------------------------------------------------- */
@@ -344,9 +348,9 @@ BSCGPU_API int64_t bscgpu_pstream_batch_segments_packed_device(bscgpu_ctx* ctx, 
  *   read; returns the decoded total (Σ data_sizes) or LIBBSC_BAD_PARAMETER.
  * bscgpu_decompress_batch: compressed blocks back to back in host memory (block b: in_sizes[b] bytes).  Block b decodes to
  *   output + Σ data_sizes[0..b) (the layout bscgpu_compress_batch took its input in); out_cap must hold the total.
- *   results[b] = what bsc_decompress(block b, in_sizes[b], ..., dataSize, features) returns, error codes included — with one
- *   caveat: a forged block with valid checksums but inconsistent aux indexes may decode here where bsc_decompress's host walk
- *   rejects it (bsc_decompress itself decodes such blocks from BSC_GPU_UNBWT_MIN_N on: the GPU walk ignores aux indexes).
+ *   results[b] = what bsc_decompress(block b, in_sizes[b], ..., dataSize, features) returns, error codes included.  (Aux indexes
+ *   are a shortcut, not data: the GPU walk never reads them, and bsc_decompress falls back to the single walk from row 0 where
+ *   they are inconsistent, so a block with valid checksums and damaged aux indexes decodes on both routes.)
  *   BWT blocks of 2 .. max_n bytes share one GPU inverse BWT per pass (QLFC decoding on the host threads, pass k + 1's
  *   overlapping pass k's GPU work; Adler-32 of the output on the GPU); stored, ST3..ST8, larger and damaged blocks go
  *   through bsc_decompress itself.  input and output must not overlap.
@@ -596,6 +600,8 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          is void goes down as 16-bit entries.  -e0, -e2, the L route and single blocks are not affected.  Same output.
  * BSCGPU_CNT_BATCH_PACKED_PASSES, BSCGPU_CNT_BATCH_PACKED_VOID  (get only) passes or segments of this context that went down packed, and
  *                          those whose packed form was void and went down as 16-bit entries.
+ * Environment only, no option key: BSC_UNBWT_STEP_CAP (read when a context is created, like BSC_PS13; values below 16 are ignored) is the
+ *                          inverse BWT's step cap, 1 << 22 by default — a test knob for the LIBBSC_NOT_SUPPORTED exits (see bscgpu_unbwt).
  * set returns the previous value or a negative libbsc error code; get the value or a negative error code. */
 enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACKED_STREAM = 4,
        BSCGPU_CNT_DC_REPLAYS = 5, BSCGPU_CNT_DC_LAST_FAIL = 6, BSCGPU_CNT_DC_AVG_UNDECIDED = 7, BSCGPU_CNT_DC_HIST_EXTENDED = 8,

@@ -200,6 +200,7 @@ extern "C" int bscgpu_create(bscgpu_ctx** out, int device, int64_t max_n)
     { const char* e = getenv("BSC_PS13"); c->dc_p13 = (e && e[0] == '0') ? 0 : 1; }       // BSCGPU_OPT_DC_PACKED_STREAM
     { const char* e = getenv("BSC_DC_AVG_EXACT"); c->dc_avg_exact = (e && e[0] == '1') ? 1 : 0; }      // BSCGPU_OPT_DC_AVG_EXACT
     { const char* e = getenv("BSC_BWT_FOLD"); if (e && e[0] >= '0' && e[0] <= '2' && !e[1]) c->bwt_fold = e[0] - '0'; }       // BSCGPU_OPT_BWT_FOLD
+    { const char* e = getenv("BSC_UNBWT_STEP_CAP"); const long long v = e ? atoll(e) : 0; if (v >= 16 && v <= 0xffffffffll) c->ub_step_cap = (u32)v; }   // unbwt.hip
     memset(c->kstat, 0, sizeof c->kstat);
     auto tm_streams = std::make_unique<CtxTimer>("  streams + events");
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return BSC_GPU_ERROR; }

@@ -75,6 +75,8 @@ constexpr int MAX_SLOTS = 8;
 
 struct DevCoder;                  // device-side static coder state (devcoder.hip), created on first use
 
+constexpr u32 UB_STEP_CAP = 1u << 22;       // unbwt.hip: steps a walk may take between two marked rows (bscgpu_ctx::ub_step_cap)
+
 struct bscgpu_ctx {
     int          device      = 0;
     hipStream_t  stream      = nullptr;
@@ -157,6 +159,7 @@ struct bscgpu_ctx {
     int  bwt_fold = 1;               // BSCGPU_OPT_BWT_FOLD: 0 off, 1 packing also counts the remaining digits, 2 it leaves that to rs_hist_all
     int  cnt_bwt_folded = 0;         // BSCGPU_CNT_BWT_FOLDED
     bool fold_lds_set = false;       // the packing kernels' dynamic-LDS limit has been raised on this context's device
+    u32  ub_step_cap = UB_STEP_CAP;  // inverse BWT: a walk longer than this between two marked rows is declined (BSC_UNBWT_STEP_CAP, a test knob)
     // pinned host
     u32* hscal  = nullptr;   // 1024 u32 (slot map: the users' comments; OS_ERR_SLOT = 1000)
     u64* hscal64 = nullptr;

@@ -24,8 +24,10 @@
 
 constexpr u64 UB_MARK = 1ull << 63;
 constexpr u32 UB_END  = 0xffffffffu;            // successor of the segment that runs into the sentinel row (as a start: not walked)
-constexpr u32 UB_CAP  = 0xfffffffeu;            // successor of a segment whose walk hit UB_STEP_CAP
-constexpr u32 UB_STEP_CAP = 1u << 22;           // a walk longer than this is a cycle without marks: corrupt input
+constexpr u32 UB_CAP  = 0xfffffffeu;            // successor of a segment whose walk hit the step cap
+// The step cap (bscgpu_ctx::ub_step_cap: UB_STEP_CAP, dev_common.h, unless BSC_UNBWT_STEP_CAP says otherwise): a walk longer than
+// this is declined.  ub_walk_kernel takes it as an argument; with the default it is compiled in (ARG_CAP = false), because the
+// compiler unrolls the decode walk four times only when it knows the bound (the argument form measured 2 % slower on a whole call).
 
 struct UbSeg { u64 orig; u32 row; u32 pad; };   // original P entry of the marked row, and the row
 
@@ -71,10 +73,11 @@ __global__ __launch_bounds__(WG) void ub_mark_kernel(u64* __restrict__ P, u32 S,
 }
 
 // one lane per segment: DECODE = false: length + successor; true: bytes to out[k], k descending from `start`
-template <bool DECODE>
+template <bool DECODE, bool ARG_CAP>
 __global__ __launch_bounds__(WG) void ub_walk_kernel(const u64* __restrict__ P, const UbSeg* __restrict__ seg, u32 S,
                                                      u32* __restrict__ seg_len, u32* __restrict__ seg_next,
-                                                     const u32* __restrict__ seg_start, u8* __restrict__ out, u32* __restrict__ bad)
+                                                     const u32* __restrict__ seg_start, u8* __restrict__ out, u32* __restrict__ bad,
+                                                     u32 step_cap)
 {
     const u32 s = blockIdx.x * WG + threadIdx.x;
     if (s >= S) return;
@@ -86,15 +89,26 @@ __global__ __launch_bounds__(WG) void ub_walk_kernel(const u64* __restrict__ P, 
     if (DECODE && seg_start[s] == UB_END) return;                     // a batched pass's block that failed its chain check
     long long k = DECODE ? (long long)seg_start[s] : 0;
     u32 len = 0, nxt = UB_END;
+    const u32 cap = ARG_CAP ? step_cap : UB_STEP_CAP;
     for (;;) {
         if (DECODE) { if (k < 0) { atomicOr(bad, 1u); break; } out[k--] = (u8)(p >> 32); }
         ++len;
         const u64 q = P[(u32)p];
         if (q & UB_MARK) { nxt = (u32)q; break; }
         p = q;
-        if (len >= UB_STEP_CAP) { atomicOr(bad, 2u); nxt = UB_CAP; break; }
+        if (len >= cap) { atomicOr(bad, 2u); nxt = UB_CAP; break; }
     }
     if (!DECODE) { seg_len[s] = len; seg_next[s] = nxt; }
+}
+
+template <bool DECODE>
+static void ub_launch_walk(bscgpu_ctx* c, const u64* P, const UbSeg* seg, u32 S, u32* seg_len, u32* seg_next, const u32* seg_start, u8* out)
+{
+    const dim3 grid((S + WG - 1) / WG), block(WG);
+    if (c->ub_step_cap == UB_STEP_CAP)
+        hipLaunchKernelGGL((ub_walk_kernel<DECODE, false>), grid, block, 0, c->stream, P, seg, S, seg_len, seg_next, seg_start, out, c->dscal + 4, UB_STEP_CAP);
+    else
+        hipLaunchKernelGGL((ub_walk_kernel<DECODE, true>), grid, block, 0, c->stream, P, seg, S, seg_len, seg_next, seg_start, out, c->dscal + 4, c->ub_step_cap);
 }
 
 // Host-pointer entry: L (n bytes) -> T (n bytes), both host memory; returns BSC_NO_ERROR, a libbsc error code,
@@ -129,8 +143,7 @@ extern "C" int bscgpu_unbwt(bscgpu_ctx* c, const uint8_t* L, uint8_t* T, int64_t
     hipLaunchKernelGGL(ub_mark_kernel, dim3((S + WG - 1) / WG), dim3(WG), 0, c->stream, P, S, rows, seg);
     prof_end(c);
     prof_begin(c, BSCGPU_K_GATHER, (u64)n * 8, n);
-    hipLaunchKernelGGL(ub_walk_kernel<false>, dim3((S + WG - 1) / WG), dim3(WG), 0, c->stream, P, seg, S, seg_len, seg_next,
-                       (const u32*)nullptr, (u8*)nullptr, c->dscal + 4);
+    ub_launch_walk<false>(c, P, seg, S, seg_len, seg_next, nullptr, nullptr);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     std::vector<u32> hlen(S), hnext(S), hstart(S, 0u);
@@ -139,7 +152,7 @@ extern "C" int bscgpu_unbwt(bscgpu_ctx* c, const uint8_t* L, uint8_t* T, int64_t
     HIP_TRY(c, hipMemcpyAsync(c->hscal + 4, c->dscal + 4, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
     prof_collect(c);
-    // A walk longer than UB_STEP_CAP is not proof of corruption — the marked rows are a fixed hash of the row number, and a valid
+    // A walk longer than the step cap is not proof of corruption — the marked rows are a fixed hash of the row number, and a valid
     // but adversarial block can put more than the cap between two of them —, so it is "not handled here" (the caller's host walk
     // decides, T is still untouched); LIBBSC_DATA_CORRUPT is reserved for the chain-closure checks below.
     if (c->hscal[4] & 2u) return BSC_NOT_SUPPORTED;
@@ -165,8 +178,7 @@ extern "C" int bscgpu_unbwt(bscgpu_ctx* c, const uint8_t* L, uint8_t* T, int64_t
     }
     HIP_TRY(c, hipMemcpyAsync(seg_start, hstart.data(), (size_t)S * 4, hipMemcpyHostToDevice, c->stream));
     prof_begin(c, BSCGPU_K_GATHER, (u64)n * 9, n);
-    hipLaunchKernelGGL(ub_walk_kernel<true>, dim3((S + WG - 1) / WG), dim3(WG), 0, c->stream, P, seg, S, (u32*)nullptr, (u32*)nullptr,
-                       seg_start, c->dL, c->dscal + 4);
+    ub_launch_walk<true>(c, P, seg, S, nullptr, nullptr, seg_start, c->dL);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(T, c->dL, n, hipMemcpyDeviceToHost, c->stream));
@@ -351,8 +363,7 @@ int unbwt_batch_pass(bscgpu_ctx* c, const u8* dL, u8* out, const int* sizes, con
     hipLaunchKernelGGL(ub_mark_batch_kernel, dim3((nseg + WG - 1) / WG), dim3(WG), 0, c->stream, P, doff, dsoff, (u32)count, nseg, seg);
     prof_end(c);
     prof_begin(c, BSCGPU_K_GATHER, (u64)n * 8, n);
-    hipLaunchKernelGGL(ub_walk_kernel<false>, dim3((nseg + WG - 1) / WG), dim3(WG), 0, c->stream, P, seg, nseg, seg_len, seg_next,
-                       (const u32*)nullptr, (u8*)nullptr, c->dscal + 4);
+    ub_launch_walk<false>(c, P, seg, nseg, seg_len, seg_next, nullptr, nullptr);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     std::vector<u32> hlen(nseg), hnext(nseg), hstart(nseg, 0u);
@@ -386,8 +397,7 @@ int unbwt_batch_pass(bscgpu_ctx* c, const u8* dL, u8* out, const int* sizes, con
     HIP_TRY(c, hipMemcpyAsync(seg_start, hstart.data(), (size_t)nseg * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->dscal + 4, 0, 4, c->stream));
     prof_begin(c, BSCGPU_K_GATHER, (u64)n * 9, n);
-    hipLaunchKernelGGL(ub_walk_kernel<true>, dim3((nseg + WG - 1) / WG), dim3(WG), 0, c->stream, P, seg, nseg, (u32*)nullptr, (u32*)nullptr,
-                       seg_start, out, c->dscal + 4);
+    ub_launch_walk<true>(c, P, seg, nseg, nullptr, nullptr, seg_start, out);
     prof_end(c);
     if (adler) {
         launch_adler_batch(c, out, dtab + A_PAIR, (u32)count, dtab + A_ADLER, 2);

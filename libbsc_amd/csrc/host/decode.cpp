@@ -115,7 +115,7 @@ int bsc_bwt_decode(unsigned char* T, int n, int index, unsigned char num_indexes
     const size_t N = (size_t)n;
     // 8 bytes per row, written once below: no zero fill
     struct FreeRaw { void operator()(void* q) const { free(q); } };
-    std::unique_ptr<void, FreeRaw> pown(malloc((N + 1) * sizeof(uint64_t)));
+    std::unique_ptr<void, FreeRaw> pown(malloc((N + 2) * sizeof(uint64_t)));
     if (!pown) return LIBBSC_NOT_ENOUGH_MEMORY;
     uint64_t* const P = static_cast<uint64_t*>(pown.get());
     {
@@ -125,7 +125,10 @@ int bsc_bwt_decode(unsigned char* T, int n, int index, unsigned char num_indexes
         for (int c = 0; c < 256; ++c) { base[c] = sum; sum += cnt[c]; }
         const size_t idx = (size_t)index;
         for (size_t i = 0; i < idx; ++i) { const unsigned char c = T[i]; P[i] = (uint64_t)base[c]++ | ((uint64_t)c << 32); }
-        P[idx] = 0;
+        // the sentinel row leads to a trap: P[N + 1] is its own successor, so a chain that reaches the sentinel row before its last
+        // step ends on N + 1 and never on its `expect` (a row <= N).  The walk is valid iff the rows 0..n are ONE cycle.
+        P[idx] = (uint64_t)(N + 1);
+        P[N + 1] = (uint64_t)(N + 1);
         for (size_t i = idx + 1; i <= N; ++i) { const unsigned char c = T[i - 1]; P[i] = (uint64_t)base[c]++ | ((uint64_t)c << 32); }
     }
 
@@ -268,6 +271,10 @@ int bsc_decompress(const unsigned char* input, int inputSize, unsigned char* out
     if (lzSize < LIBBSC_NO_ERROR) return lzSize;
     int rc = (sorter == LIBBSC_BLOCKSORTER_BWT) ? bsc_bwt_decode(output, lzSize, index, (unsigned char)num_indexes, indexes, features)
                                                 : bsc_st_decode(output, lzSize, sorter, index, features);
+    // aux indexes are a shortcut, not part of the data: where they are inconsistent the single walk from row 0 decides (it leaves
+    // `output` untouched when it fails too), as the GPU routes, which never read them, already do.  The checksum below has the last word.
+    if (rc == LIBBSC_DATA_CORRUPT && sorter == LIBBSC_BLOCKSORTER_BWT && num_indexes > 0)
+        rc = bsc_bwt_decode(output, lzSize, index, 0, nullptr, features);
     if (rc < LIBBSC_NO_ERROR) return rc;
     if (lzpHashSize != 0 || lzpMinLen != 0) {                  // undo LZP (libbsc.cpp:594-609); encoding it is not built (f3)
         std::unique_ptr<unsigned char, void (*)(void*)> tmp((unsigned char*)bschost::bigbuf_get((size_t)lzSize + 1), bschost::bigbuf_put);   // (par.h: kept buffers)

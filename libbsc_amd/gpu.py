@@ -71,10 +71,13 @@ class GpuContext:
         rc = self._check(self.L.bscgpu_bwt(self.h, N.np_ptr(T), N.np_ptr(Lout), n))
         return Lout[:n], int(rc), None
 
-    def unbwt(self, L, index):
-        """bscgpu_unbwt: inverse BWT of L (np.uint8) with the 1-based primary index -> (text np.uint8, rc)"""
+    def unbwt(self, L, index, out=None):
+        """bscgpu_unbwt: inverse BWT of L (np.uint8) with the 1-based primary index -> (text np.uint8, rc); out: the caller's
+        buffer (contiguous uint8, at least len(L) bytes), left as it is where rc is not 0"""
         a = np.ascontiguousarray(L, dtype=np.uint8)
-        out = np.empty(max(a.size, 1), np.uint8)
+        if out is None:
+            out = np.empty(max(a.size, 1), np.uint8)
+        assert out.dtype == np.uint8 and out.flags.c_contiguous and out.size >= a.size
         f = self.L.bscgpu_unbwt
         f.restype = C.c_int
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]

@@ -53,6 +53,7 @@ def test_unbwt_batch_matches_reference(dctx, ref):
 def test_unbwt_batch_isolates_bad_blocks(dctx, ref):
     import torch
     from libbsc_amd.synth import synth_text_v1
+    from unbwt_inputs import lf_verdict
     texts = [synth_text_v1(50 + i, n) for i, n in enumerate([3000, 70000, 400000, 65536, 129, 250000, 17])]
     enc = [ref.bwt_encode(T, aux=False) for T in texts]
     Ls = [np.asarray(e[0][:t.size], np.uint8).copy() for e, t in zip(enc, texts)]
@@ -69,7 +70,8 @@ def test_unbwt_batch_isolates_bad_blocks(dctx, ref):
     for b, T in enumerate(texts):
         got = Th[offs[b]:offs[b + 1]]
         if b in (bad_prim, bad_col):
-            assert res[b] == -6 or (res[b] == 0 and not np.array_equal(got, T)), (b, res[b])
+            want_rc, want = lf_verdict(Ls[b], prim[b])             # the plain LF walk's verdict (tests/unbwt_inputs.py)
+            assert res[b] == want_rc and (res[b] != 0 or np.array_equal(got, want)), (b, res[b])
             if res[b] == -6:
                 assert (got == 0xAB).all(), f"block {b} failed but wrote its range"
         else:
@@ -143,6 +145,82 @@ def test_damaged_blocks_get_their_own_error(dctx, ref):
     _, _, res = dctx.decompress_batch_device(blocks)
     assert [r for b, r in enumerate(res) if b in (1, 3, 4)] == [api.bsc_decompress(blocks[b]) for b in (1, 3, 4)]
     assert [r for b, r in enumerate(res) if b not in (1, 3, 4)] == [0, 0, 0]
+
+
+def _seal(b, size=True):
+    import struct
+    from libbsc_amd import api
+    if size:
+        b[0:4] = struct.pack("<i", len(b))
+    b[20:24] = struct.pack("<I", api.bsc_adler32(np.frombuffer(bytes(b[28:]), np.uint8)))
+    b[24:28] = struct.pack("<I", api.bsc_adler32(np.frombuffer(bytes(b[:24]), np.uint8)))
+    return bytes(b)
+
+
+def test_sealed_damage_reaches_the_batched_route(dctx, ref):
+    """Damaged blocks whose checksums were repaired (the recipe of test_decompress_survives_corrupt_streams, plus directed edits of the
+    primary index and the aux-index count) pass every check in front of the GPU pass: garbage reaches the QLFC decoders and the
+    batched inverse BWT.  Interleaved with clean blocks in one call, every block must come back exactly as bsc_decompress returns it
+    alone — the error code or the bytes.  (The reference's decoder is not asked: it has no chain check.)  Random edits start at
+    offset 8: blockSize is rewritten anyway, and dataSize only decides how much the caller allocates."""
+    import struct
+    from libbsc_amd import api
+    from libbsc_amd.synth import synth_text_v1
+    rng = np.random.default_rng(78)
+    src = []
+    for i, (coder, lzp, n) in enumerate([(1, (0, 0), 2000), (2, (0, 0), 70_000), (3, (0, 0), 9001), (1, (15, 128), 40_000),
+                                         (2, (15, 128), 5000), (3, (15, 128), 23_456)]):
+        T = synth_text_v1(400 + i, n)
+        if lzp[0]:
+            T = np.concatenate([T, T[:n // 2], T[n // 3:]])[:70_000]       # something for LZP to find
+        src.append((T, ref.compress(T, 1, coder, lzp[0], lzp[1])))
+        assert isinstance(src[-1][1], bytes) and api.bsc_decompress(src[-1][1]) == T.tobytes()
+    damaged = []
+    for it in range(114):
+        b = bytearray(src[it % len(src)][1])
+        for _ in range(int(rng.integers(1, 4))):
+            mode = int(rng.integers(0, 4)); pos = int(rng.integers(8, len(b)))
+            if mode == 0: b[pos] ^= 1 << int(rng.integers(0, 8))
+            elif mode == 1: b[pos] = int(rng.integers(0, 256))
+            elif mode == 2 and len(b) > 40: del b[pos]
+            else: b.insert(pos, int(rng.integers(0, 256)))
+        damaged.append(_seal(b, size=bool(rng.integers(0, 4))))
+    for T, blk in src:                                                    # directed header edits
+        index = struct.unpack("<i", blk[12:16])[0]
+        for value in (0, T.size + 1, -1, index - 1, index + 1):
+            b = bytearray(blk)
+            b[12:16] = struct.pack("<i", value)
+            damaged.append(_seal(b))
+        b = bytearray(blk)
+        b[-1] = min(b[-1] + 1 + int(rng.integers(0, 4)), 255)             # more aux indexes than the block has
+        damaged.append(_seal(b))
+        if blk[-1] > 0:                                                   # (blocks from 64 KiB on carry aux indexes)
+            b = bytearray(blk)                                            # an aux index moved: a shortcut, not data — the block still decodes
+            b[-5:-1] = struct.pack("<i", struct.unpack("<i", blk[-5:-1])[0] ^ 1)
+            damaged.append(_seal(b))
+            assert api.bsc_decompress(damaged[-1]) == T.tobytes()
+    assert len(damaged) == 152
+    blocks, clean_of = [], {}
+    for i, d in enumerate(damaged):                                       # damaged and clean blocks alternate
+        blocks.append(d)
+        clean_of[len(blocks)] = src[i % len(src)][0]
+        blocks.append(src[i % len(src)][1])
+    want = [api.bsc_decompress(blk) for blk in blocks]
+    codes = sorted({w for w in want if isinstance(w, int)})
+    decoded = sum(1 for b, w in enumerate(want) if b not in clean_of and not isinstance(w, int))
+    print("error codes met:", codes, "damaged blocks that decode:", decoded)
+    assert any(isinstance(w, int) for w in want)
+    got = dctx.decompress_batch(blocks)
+    for b, (g, w) in enumerate(zip(got, want)):
+        assert g == w, (b, g if isinstance(g, int) else "bytes", w if isinstance(w, int) else "bytes")
+        if b in clean_of:
+            assert g == clean_of[b].tobytes(), b
+    T, offs, res = dctx.decompress_batch_device(blocks)
+    assert res == [w if isinstance(w, int) else 0 for w in want]
+    Th = T.cpu().numpy()
+    for b, w in enumerate(want):
+        if not isinstance(w, int):
+            assert Th[offs[b]:offs[b + 1]].tobytes() == w, f"device output, block {b}"
 
 
 def test_many_passes_and_the_single_block_path(ref):

@@ -592,6 +592,7 @@ def test_gpu_inverse_bwt(ctx, ref):
     and walked in parallel.  Against the texts the reference's forward BWT came from; wrong primary indexes and damaged columns
     must come back as DATA_CORRUPT or as a different text, never hang."""
     from libbsc_amd.synth import synth_text_v1, synth_repeat_v1
+    from unbwt_inputs import lf_verdict
     rng = np.random.default_rng(3)
     cases = [synth_text_v1(7, n) for n in (1, 2, 3, 17, 127, 128, 129, 1000, 65536, 300_000, (1 << 20) + 17, 5 << 20)]
     cases += [rng.integers(0, 256, 200_000, dtype=np.uint8), np.zeros(70_000, np.uint8), (np.arange(100_000) % 2).astype(np.uint8),
@@ -606,7 +607,9 @@ def test_gpu_inverse_bwt(ctx, ref):
         if bad == idx or bad < 1 or bad > T.size:
             continue
         back, rc = ctx.unbwt(L, bad)
-        assert rc == -6 or (rc == 0 and not np.array_equal(back, T)), bad
+        want_rc, want = lf_verdict(L, bad)                      # the plain LF walk's verdict (tests/unbwt_inputs.py)
+        assert rc == want_rc and (rc != 0 or np.array_equal(back, want)), bad
     L2 = L.copy(); L2[1000:1100] = L2[5000:5100]                # damaged column: symbol counts change, cycles break
     back, rc = ctx.unbwt(L2, idx)
-    assert rc == -6 or (rc == 0 and not np.array_equal(back, T))
+    want_rc, want = lf_verdict(L2, idx)
+    assert rc == want_rc and (rc != 0 or np.array_equal(back, want))
