@@ -1232,7 +1232,20 @@ void launch_seg_scan(bscgpu_ctx* c, u32 num_chunks)
 }
 
 // ---------------------------------------------------------------------------------------------
-static int bit_length(u64 x) { int b = 0; while (x) { ++b; x >>= 1; } return b; }
+// The driver.  What it decides — key layout, digit passes, the kind of every round — is bwt_plan.h's arithmetic; here are the launches.
+// ---------------------------------------------------------------------------------------------
+// The driver's environment switches, read once per process (bwt_plan.h: BwtSwitches says what each does).
+static const BwtSwitches& bwt_switches()
+{
+    static const BwtSwitches sw = [] {
+        auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+        return BwtSwitches{env("BSC_BWT_W", 0), env("BSC_BWT_TEXTROUNDS", 1), env("BSC_BWT_HYBRID", 1), env("BSC_BWT_HYBRID_PCT", 100), env("BSC_BWT_ISASKIP", 1)};
+    }();
+    return sw;
+}
+
+// workgroups of a grid-stride kernel over x items
+static inline u32 capped_grid(u32 x, u32 cap = 8192) { const u32 blocks = (x + WG - 1) / WG; return blocks > cap ? cap : blocks; }
 
 template <bool INITIAL, bool WRITE_ISA>
 static int run_seg(bscgpu_ctx* c, const u64* keys, const u32* sa_sorted, const u32* cpos_in, u32 m, u32 tail_lo, u32 smask,
@@ -1259,26 +1272,13 @@ static int run_seg(bscgpu_ctx* c, const u64* keys, const u32* sa_sorted, const u
     return radix_onesweep_check(c);            // the sort in front of this seg, if it used the single-read passes
 }
 
-static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_t n64, int64_t r, u32* I_host, int64_t* primary_out, bool reuse_text,
+static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_t n64, int64_t r, u32* I_host, int64_t* primary_out,
                            const BwtBatch* bt = nullptr);
 
-// A single-read digit pass that gave up a wait (radix_onesweep.hip: bounded polls; pre-emption, a debugger, a hogged CU) fails the
-// sort, not the block: the transform is redone once with the three-kernel passes, which have no cross-workgroup protocol at all.
-// Every sort is checked (run_seg) before anything is written to the caller's buffer; the private copy of the text is NOT relied on
-// for the second attempt (it may have been clobbered by kernels that ran behind the failed sort): the text is copied again.
+// Retry rule: with_onesweep_retry (dev_common.h); the second attempt copies the text again, as the first.
 int bwt_device(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_t n64, int64_t r, u32* I_host, int64_t* primary_out)
 {
-    c->os_gave_up = false;
-    int rc = bwt_device_once(c, dT_user, dL_user, n64, r, I_host, primary_out, false);
-    if (rc == BSC_GPU_ERROR && c->os_gave_up) {
-        const int mode = c->os_mode;
-        c->os_mode = 0; c->os_gave_up = false; ++c->os_retries;
-        // (the text is copied again: the caller's buffer is untouched until the last kernel of a transform, while the private copy may
-        // not be — kernels that consume a failed sort's output run before the check, on stale keys and values: see seg_apply_kernel)
-        rc = bwt_device_once(c, dT_user, dL_user, n64, r, I_host, primary_out, false);
-        c->os_mode = mode;
-    }
-    return rc;
+    return with_onesweep_retry(c, [&](bool) { return bwt_device_once(c, dT_user, dL_user, n64, r, I_host, primary_out); });
 }
 
 // One batched pass (see bwt_batch_pack_kernel): the block table goes up, one transform of the whole pass runs, the per-block indexes come
@@ -1294,47 +1294,46 @@ int batch_tab_ensure(bscgpu_ctx* c)
     return BSC_NO_ERROR;
 }
 
-int bwt_batch_device(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, const int* sizes, int count, const int* rates, u32* res, u32* adler_host)
+int batch_pass_setup(bscgpu_ctx* c, const u8* dT_user, const int* sizes, int count, const int* rates, int* index_out, u32* adler_host, BatchTab* bt)
 {
     if (count <= 0 || count > BATCH_MAX_BLOCKS) return BSC_BAD_PARAMETER;
-    const int trc = batch_tab_ensure(c);
-    if (trc < 0) return trc;
-    std::vector<u32> tab((size_t)2 * count + 1);
+    RC_TRY(batch_tab_ensure(c));
+    std::vector<u32> tab((size_t)2 * count + 1, 0u);
     u64 total = 0;
-    for (int b = 0; b < count; ++b) { tab[b] = (u32)total; total += (u64)sizes[b]; }
+    for (int b = 0; b < count; ++b) { tab[b] = (u32)total; total += (u64)sizes[b]; if (index_out) index_out[b] = 0; }
     tab[count] = (u32)total;
-    memcpy(&tab[count + 1], rates, (size_t)count * 4);
+    if (rates) memcpy(&tab[count + 1], rates, (size_t)count * 4);
+    bt->total = 0;
     if (total == 0) return BSC_NO_ERROR;
     if (total > (u64)c->max_n || total >= 0x7fffffffull) return BSC_BAD_PARAMETER;
-    BwtBatch bt;
-    bt.count = (u32)count; bt.off = c->batch_tab; bt.rate = reinterpret_cast<const int*>(c->batch_tab + count + 1);
-    bt.res = c->batch_tab + 2 * BATCH_MAX_BLOCKS + 1; bt.res_host = res;
+    bt->total = (u32)total; bt->off = c->batch_tab; bt->rate = reinterpret_cast<const int*>(c->batch_tab + count + 1);
+    bt->res = c->batch_tab + 2 * BATCH_MAX_BLOCKS + 1;
     HIP_TRY(c, hipMemcpyAsync(c->batch_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
     if (adler_host) {                           // (reads the caller's text before the transform may overwrite it; the transform's last sync covers the copy)
         u32* dadler = c->batch_tab + 18 * BATCH_MAX_BLOCKS + 1;
         launch_adler_batch(c, dT_user, c->batch_tab, (u32)count, dadler);
         HIP_TRY(c, hipMemcpyAsync(adler_host, dadler, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
     }
+    return BSC_NO_ERROR;
+}
+
+int bwt_batch_device(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, const int* sizes, int count, const int* rates, u32* res, u32* adler_host)
+{
+    BatchTab tab;
+    const int src = batch_pass_setup(c, dT_user, sizes, count, rates, nullptr, adler_host, &tab);
+    if (src < 0 || tab.total == 0) return src;
+    const BwtBatch bt = {(u32)count, tab.off, tab.rate, tab.res, res};
     int64_t unused = 0;
-    c->os_gave_up = false;
-    int rc = bwt_device_once(c, dT_user, dL_user, (int64_t)total, 0, nullptr, &unused, false, &bt);
-    if (rc == BSC_GPU_ERROR && c->os_gave_up) {
-        const int mode = c->os_mode;
-        c->os_mode = 0; c->os_gave_up = false; ++c->os_retries;
-        rc = bwt_device_once(c, dT_user, dL_user, (int64_t)total, 0, nullptr, &unused, false, &bt);
-        c->os_mode = mode;
-    }
-    return rc;
+    return with_onesweep_retry(c, [&](bool) { return bwt_device_once(c, dT_user, dL_user, (int64_t)tab.total, 0, nullptr, &unused, &bt); });
 }
 
 // The front of a transform: private copy of the text, alphabet, key packing and the first sort (asynchronous behind the alphabet's sync;
 // run_seg checks the sort).  Also what bscgpu_bwt_first_sort_device runs.
-struct FirstSort { PackParams pp; u32 smask, tail_lo; u8* dcodes; u8* ddecode; const u64* ks; const u32* vs; };
-static int bwt_first_sort(bscgpu_ctx* c, const u8* dT_user, u32 n, bool reuse_text, const BwtBatch* bt, FirstSort* fs)
+struct FirstSort { BwtKeyPlan kp; PackParams pp; u8* dcodes; u8* ddecode; const u64* ks; const u32* vs; };
+static int bwt_first_sort(bscgpu_ctx* c, const u8* dT_user, u32 n, const BwtBatch* bt, FirstSort* fs)
 {
-    int rc;
     // private, padded copy of the text (emit may overwrite the user's buffer when dL aliases dT)
-    if (!reuse_text) HIP_TRY(c, hipMemcpyAsync(c->dT, dT_user, n, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->dT, dT_user, n, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->dT + n, 0, 32, c->stream));
 
     // alphabet: byte histogram -> dense order-preserving codes
@@ -1349,49 +1348,27 @@ static int bwt_first_sort(bscgpu_ctx* c, const u8* dT_user, u32 n, bool reuse_te
     HIP_TRY(c, ctx_sync(c));
     u8 codes[256]; u32 K = 0;
     for (int b = 0; b < 256; ++b) { codes[b] = (u8)K; if (c->hscal[300 + b]) ++K; }
+    // key layout and pass plan (bwt_plan.h); the single-read passes are asked about the fold's pass count, which does not depend on the answer
+    const u32 count = bt ? bt->count : 0u;
+    const int wmax = bwt_switches().wmax, fold_np = bwt_key_plan(K, n, count, wmax, false).fold_np;
+    const BwtKeyPlan& kp = fs->kp = bwt_key_plan(K, n, count, wmax, c->bwt_fold != 0 && radix_onesweep_wanted(c, n, fold_np, true));
     PackParams& pp = fs->pp;
-    // a batched pass: codes 1..K (0 = past the block's end) below the block field; no text rounds, no predecessor codes (see bwt_batch_pack_kernel)
-    const u32 batch_bb = bt ? (u32)bit_length(bt->count - 1) : 0u;
-    pp.cb = 1; while ((1u << pp.cb) < K + (bt ? 1u : 0u)) ++pp.cb;
-    if (pp.cb < 4) pp.cb = 4;                                   // at most 16 characters per key
-    pp.w = 64 / pp.cb;
-    if (bt) { pp.w = (64 - batch_bb) / pp.cb; if (pp.w > 16) pp.w = 16; }
-    else { static const int wmax = [] { const char* e = getenv("BSC_BWT_W"); return e ? atoi(e) : 0; }(); if (wmax >= 2 && (u32)wmax < pp.w) pp.w = (u32)wmax; }   // experiment: shorter first-sort keys
-    // (Base-K keys — the w characters as one base-K number, 13 instead of 12 characters for 28 symbols — were measured and removed: fewer
-    // unsorted suffixes after the first sort, but slower digit passes on their uniform bytes; profiles/r06/first_sort_keys.txt.)
-    pp.tc = n < pp.w - 1 ? n : pp.w - 1;
-    pp.low_shift = 64 - pp.cb * pp.w - batch_bb;
-    // The sort's values have spare high bits when the block is not huge: carry the code of the character in FRONT of the
-    // suffix there, so that the final L = T[SA - 1] needs no random gather from the text (BSC_BWT_PRED=0 keeps the gather)
-    const int idx_bits = bit_length(n - 1);
-    static const int pred_on = [] { const char* e = getenv("BSC_BWT_PRED"); return e ? atoi(e) : 1; }();
-    pp.pred_shift = (pred_on && !bt && idx_bits >= 1 && idx_bits + (int)pp.cb <= 32) ? (u32)idx_bits : 0u;
-    fs->smask = pp.pred_shift ? ((1u << pp.pred_shift) - 1u) : 0xffffffffu;
-    fs->tail_lo = bt ? 0xffffffffu : (n >= pp.w) ? (n - (pp.w - 1)) : 0;
+    pp.cb = kp.cb; pp.w = kp.w; pp.tc = kp.tc; pp.low_shift = kp.low_shift; pp.pred_shift = kp.pred_shift;
     u8* dcodes = fs->dcodes = reinterpret_cast<u8*>(c->dscal + 560);         // 256 bytes of the scalar area
     u8* ddecode = fs->ddecode = reinterpret_cast<u8*>(c->dscal + 720);        // 256 bytes: code -> byte (640..703 is the QLFC front end's symbol table)
     u8 decode[256]; memset(decode, 0, sizeof decode);
     for (int b = 255; b >= 0; --b) if (c->hscal[300 + b]) decode[codes[b]] = (u8)b;
     HIP_TRY(c, hipMemcpyAsync(dcodes, codes, 256, hipMemcpyHostToDevice, c->stream));
     if (pp.pred_shift) HIP_TRY(c, hipMemcpyAsync(ddecode, decode, 256, hipMemcpyHostToDevice, c->stream));
-    // Pass plan.  Digits are 8 bits from low_shift upwards, the topmost with what is left.  Where the key's width leaves r = (cb * w) mod 8
-    // bits over, 1 <= r <= 4 (17..64 symbols: 60 key bits, r = 4), that half digit costs a whole pass over all records; key packing
-    // writes every record once anyway, so it places them by these r bits itself (bwt_pack_fold_kernel; r <= cb: the digit lies inside
-    // the key's last character) and the sort is (cb * w - r) / 8 byte passes from low_shift + r.  A stable LSD sort gives the same
-    // arrays however the bits are cut into digits.  Only single blocks whose sort takes the single-read passes go this way (so not
-    // the retry after a give-up, os_mode == 0); everything else keeps the plan and the kernels it had.
-    const u32 fold_r = (pp.cb * pp.w) & 7u;
-    const int fold_np = (int)((pp.cb * pp.w - fold_r) / 8u);
-    const bool fold = c->bwt_fold != 0 && !bt && fold_r >= 1 && fold_r <= 4 && fold_r <= pp.cb && n >= pp.w &&
-                      radix_onesweep_wanted(c, n, fold_np, true);
-    if (fold) {
+    if (kp.fold) {
+        const u32 fold_r = kp.fold_r;
         const bool fused = c->bwt_fold == 1;                // packing counts the byte digits too (else rs_hist_all reads the keys for them)
         if (!c->fold_lds_set) {
             HIP_TRY(c, hipFuncSetAttribute((const void*)bwt_pack_fold_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fold_lds_bytes(FOLD_MAXP)));
             c->fold_lds_set = true;
         }
         u32* totals = nullptr; u32 stride = 0;
-        if (fused) { rc = radix_onesweep_prepare(c, n, fold_np, &totals, &stride); if (rc < 0) return rc; }     // (the tables are cleared in front of packing)
+        if (fused) RC_TRY(radix_onesweep_prepare(c, n, fold_np, &totals, &stride));     // (the tables are cleared in front of packing)
         const u32 ntiles = (n + FOLD_TILE - 1) / FOLD_TILE;
         u32* fcnt = c->ISA;                                  // [FOLD_NB][ntiles] counts, then as many offsets: ISA is not built before the first seg
         u32* foff = fcnt + (size_t)FOLD_NB * ntiles;
@@ -1415,10 +1392,7 @@ static int bwt_first_sort(bscgpu_ctx* c, const u8* dT_user, u32 n, bool reuse_te
                                c->dT, n, pp, fold_r, dcodes, foff, fseg, ntiles, seg_tiles, k0, v0, 0u, (u32*)nullptr, 0u);
         prof_end(c);
         HIP_TRY(c, hipGetLastError());
-        RadixPass fp[FOLD_MAXP];
-        for (int p = 0; p < fold_np; ++p) { fp[p].shift = (int)(pp.low_shift + fold_r) + 8 * p; fp[p].bits = 8; }
-        rc = radix_onesweep_sort(c, k0, k1, v0, v1, n, fp, fold_np, fused);
-        if (rc < 0) return rc;
+        RC_TRY(radix_onesweep_sort(c, k0, k1, v0, v1, n, kp.passes, kp.npass, fused));
         ++c->cnt_bwt_folded;
         fs->ks = c->kA; fs->vs = c->vA;
         return BSC_NO_ERROR;
@@ -1426,18 +1400,14 @@ static int bwt_first_sort(bscgpu_ctx* c, const u8* dT_user, u32 n, bool reuse_te
     prof_begin(c, BSCGPU_K_PACK, (u64)n * 13, n);
     if (bt)
         hipLaunchKernelGGL(bwt_batch_pack_kernel, dim3((n + WG - 1) / WG), dim3(WG), 0, c->stream,
-                           c->dT, n, bt->off, bt->count, batch_bb, pp.cb, pp.w, dcodes, c->kA, c->vA);
+                           c->dT, n, bt->off, bt->count, kp.batch_bb, pp.cb, pp.w, dcodes, c->kA, c->vA);
     else
         hipLaunchKernelGGL(bwt_pack_kernel, dim3((n + 4 * WG - 1) / (4 * WG)), dim3(WG), 0, c->stream,
                            c->dT, n, pp, dcodes, c->kA, c->vA);
     prof_end(c);
 
-    RadixPass passes[16]; int npass = 0;
-    constexpr int dbits = 8;    // measured: 7- / 6-bit digits raise per-pass bandwidth (3.5 -> 3.8 / 4.0 TB/s) but the extra passes lose overall
-    for (u32 sft = pp.low_shift; sft < 64; sft += dbits) { passes[npass].shift = (int)sft; passes[npass].bits = (64 - sft < (u32)dbits) ? (int)(64 - sft) : dbits; ++npass; }
     int in_alt = 0;
-    rc = radix_sort_passes(c, c->kA, c->kB, c->vA, c->vB, n, passes, npass, &in_alt);
-    if (rc < 0) return rc;
+    RC_TRY(radix_sort_passes(c, c->kA, c->kB, c->vA, c->vB, n, kp.passes, kp.npass, &in_alt));
     fs->ks = in_alt ? c->kB : c->kA;
     fs->vs = in_alt ? c->vB : c->vA;
     return BSC_NO_ERROR;
@@ -1450,261 +1420,260 @@ int bwt_first_sort_device(bscgpu_ctx* c, const u8* dT_user, int64_t n64, u64* ke
     if (n64 < 0 || n64 > c->max_n || n64 >= 0x7fffffffll) return BSC_BAD_PARAMETER;
     if (n64 == 0) return BSC_NO_ERROR;
     const u32 n = (u32)n64;
-    auto once = [&]() -> int {
+    return with_onesweep_retry(c, [&](bool) -> int {
         FirstSort fs;
-        int rc = bwt_first_sort(c, dT_user, n, false, nullptr, &fs);
-        if (rc < 0) return rc;
+        RC_TRY(bwt_first_sort(c, dT_user, n, nullptr, &fs));
         HIP_TRY(c, hipMemcpyAsync(keys_out, fs.ks, (size_t)n * 8, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(vals_out, fs.vs, (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(c, ctx_sync(c));
         prof_collect(c);
         return radix_onesweep_check(c);
-    };
-    c->os_gave_up = false;
-    int rc = once();
-    if (rc == BSC_GPU_ERROR && c->os_gave_up) {
-        const int mode = c->os_mode;
-        c->os_mode = 0; c->os_gave_up = false; ++c->os_retries;
-        rc = once();
-        c->os_mode = mode;
-    }
-    return rc;
+    });
 }
 
-static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_t n64, int64_t r, u32* I_host, int64_t* primary_out, bool reuse_text,
-                           const BwtBatch* bt)
+// ---------------------------------------------------------------------------------------------
+// The refinement rounds.  What they share:
+struct BwtRounds {
+    // fixed for the transform
+    u32 n; PackParams pp; u32 smask, ta; u8* dcodes;
+    int lo_bits;                // next-rank field: values 0 .. n
+    // moved by the rounds
+    int cur;                    // the half of cpos / csa / cgrp that holds the unsorted set
+    u32 U;                      // its records
+    u64 h;                      // characters the groups are sorted by
+    u32* SA;                    // the sort's value array itself when the rounds do not write to it (they put their output into kB / vB), else a copy
+    bool isa_valid;             // ISA exists: the rounds double; else they are rounds on text keys
+    bool first_flags;           // c->flags still holds the first seg's flags, indexed by SA slot (bit 1: the slot's suffix is unsorted)
+    const u64* ks; const u32* vs; int in_alt;       // where the last sort left its records
+    int rounds, text_rounds;
+    // debug trace only: wall time of a round (every round ends in a sync)
+    bool dbg; double t_round;
+};
+
+static double bwt_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+static double bwt_lap(BwtRounds& s) { const double t = bwt_now_ms(), d = t - s.t_round; s.t_round = t; return d; }
+
+// A round's sort gives up when a group does not fit a workgroup: the word is cleared in front of the launches, read behind them
+static int bwt_giveup_clear(bscgpu_ctx* c) { HIP_TRY(c, hipMemsetAsync(c->dscal + 2, 0, 4, c->stream)); return BSC_NO_ERROR; }
+static int bwt_giveup_read(bscgpu_ctx* c, bool* sorted)
 {
-    if (n64 < 0 || n64 > c->max_n || n64 >= 0x7fffffffll) return BSC_BAD_PARAMETER;
-    if (n64 == 0) { *primary_out = 0; return BSC_NO_ERROR; }
-    const u32 n = (u32)n64;
-    int rc;
+    HIP_TRY(c, hipMemcpyAsync(c->hscal + 2, c->dscal + 2, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    prof_collect(c);
+    *sorted = c->hscal[2] == 0;
+    return BSC_NO_ERROR;
+}
 
-    FirstSort fs;
-    rc = bwt_first_sort(c, dT_user, n, reuse_text, bt, &fs);
-    if (rc < 0) return rc;
-    const PackParams& pp = fs.pp;
-    const u32 smask = fs.smask, tail_lo = fs.tail_lo;
-    u8* const dcodes = fs.dcodes; u8* const ddecode = fs.ddecode;
-    const u64* ks = fs.ks;
-    const u32* vs = fs.vs;
-    int in_alt = 0;
-
-    // Rounds on text keys (bwt_round_textsort_kernel) need a characters + 4 bits in 64: a = w where the first-sort key leaves
-    // 4 bits spare, else w - 1.  BSC_BWT_TEXTROUNDS=0 keeps the round-1 flow (ISA built by the first seg, doubling from h = w).
-    static const int text_on = [] { const char* e = getenv("BSC_BWT_TEXTROUNDS"); return e ? atoi(e) : 1; }();
-    const u32 ta = (pp.cb * pp.w + 4 <= 64) ? pp.w : pp.w - 1;
-    bool isa_valid = bt != nullptr || !(text_on && ta >= 2 && ta <= 15);       // (text rounds read the text past a suffix: not across block ends)
-    int cur = 0;
-    u32 U = 0;
-    // SA: the sort's value array itself when the rounds do not write to it (they put their output into kB / vB), else a copy
-    u32* SA = (vs == c->vA) ? c->vA : c->SA;
-    if (isa_valid) rc = run_seg<true, true >(c, ks, vs, nullptr, n, tail_lo, smask, c->cpos[cur], c->csa[cur], c->cgrp[cur], &U, SA);
-    else           rc = run_seg<true, false>(c, ks, vs, nullptr, n, tail_lo, smask, c->cpos[cur], c->csa[cur], c->cgrp[cur], &U, SA);
-    if (rc < 0) return rc;
-
-    bool first_flags = true;                    // c->flags still holds the first seg's flags, indexed by SA slot (bit 1: the slot's suffix is unsorted)
-    const int lo_bits = bit_length(n);          // next-rank field: values 0 .. n
-    const int hi_bits = bit_length(n - 1);      // group rank field: values 0 .. n-1
-    u64 h = pp.w;
-    int rounds = 0, text_rounds = 0;
-    const bool dbg = getenv("BSCGPU_DEBUG") != nullptr;
-    if (dbg) fprintf(stderr, "[bwt] n=%u initial unsorted=%u\n", n, U);
-    auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t_round = dbg ? now_ms() : 0.0;                       // debug trace only: wall time of a round (every round ends in a sync)
-    auto lap = [&] { const double t = now_ms(), d = t - t_round; t_round = t; return d; };
-    while (U > 0) {
-        if (++rounds > 60) return ctx_fail(c, BSC_GPU_ERROR, "prefix doubling did not converge", hipSuccess);
-        // what the seg that produced this unsorted set counted (seg_apply): groups no segmented sort of this round can take
-        const u32 n_long = c->hscal[DS_NLONG], n_long_rec = c->hscal[DS_EXCESS] + c->hscal[DS_NLONG] * (u32)RS_G;
-        const u32 n_mid = c->hscal[DS_NMID], n_mid_rec = c->hscal[DS_MIDEXCESS] + c->hscal[DS_NMID] * (u32)HY_G;      // groups of > HY_G records (hybrid rounds)
-        if (!isa_valid) {
-            // a round on text keys; it hands over to doubling when a group does not fit a workgroup or the round did not pay
-            static const int long_split_on = [] { const char* e = getenv("BSC_BWT_LONGSPLIT"); return e ? atoi(e) : 1; }();
-            bool round_done = false;
-            if (n_long == 0) {
-                HIP_TRY(c, hipMemsetAsync(c->dscal + 2, 0, 4, c->stream));
-                prof_begin(c, BSCGPU_K_GATHER, (u64)U * (4 + 4 + 16 + 8 + 4), U);
-                hipLaunchKernelGGL(bwt_round_textsort_kernel, dim3((U + RS_T - 1) / RS_T), dim3(WG), 0, c->stream,
-                                   c->dT, dcodes, c->csa[cur], c->cgrp[cur], U, h, n, smask, pp.cb, ta, c->kB, c->vB, c->dscal + 2);
-                prof_end(c);
-                HIP_TRY(c, hipMemcpyAsync(c->hscal + 2, c->dscal + 2, 4, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(c, ctx_sync(c));
-                prof_collect(c);
-                round_done = c->hscal[2] == 0;
-            } else {
-                // Groups too long for one workgroup.  While they hold a small part of the round's records they — and only they — are
-                // split by the top bits of this round's key and the segmented sort runs with the bucket starts as extra boundaries;
-                // otherwise (long repeats: most unsorted suffixes sit in a few huge groups, and their records would all go through
-                // global atomics — python sources, 64 MiB: 127 ms against 44 ms) the round is handed over to prefix doubling at once,
-                // without first running a sort that gives up (9.5 ms on that block).
-                // (tables in an allocation of their own, made when a block first needs them — 16.8 MB per context; round 3 carved them
-                // out of kA on the strength of a comment.  Group ids go to ISA, which does not exist yet on this path — isa_valid is
-                // false, it is built at the hand-over —, sub-group heads to flags, which only the seg kernels behind the round rewrite;
-                // the permuted suffixes to csa[cur ^ 1], the half the next seg writes.)
-                constexpr size_t LT_BYTES = (size_t)(64 + LG_MAX + (size_t)LG_MAX * LG_BUCKETS) * 4;
-                bool fits = n_long <= LG_MAX && n_long_rec <= U / 8u && long_split_on;
-                if (fits && !c->long_tables) {
-                    if (hipMalloc((void**)&c->long_tables, LT_BYTES) != hipSuccess) { (void)hipGetLastError(); c->long_tables = nullptr; fits = false; }
-                }
-                LongTables LT;
-                LT.nlong = c->long_tables; LT.khead = LT.nlong + 64; LT.cnt = LT.khead + LG_MAX;
-                const bool pays = fits;
-                if (pays) {
-                    u8* subhead = c->flags;
-                    first_flags = false;
-                    HIP_TRY(c, hipMemsetAsync(LT.nlong, 0, LT_BYTES, c->stream));
-                    HIP_TRY(c, hipMemsetAsync(subhead, 0, (size_t)U + 1, c->stream));
-                    HIP_TRY(c, hipMemsetAsync(c->dscal + 2, 0, 4, c->stream));
-                    u32 blocks = (U + WG - 1) / WG; if (blocks > 4096) blocks = 4096;
-                    prof_begin(c, BSCGPU_K_GATHER, (u64)U * (8 + (8 + 4 + 16 + 4) * 2), U);
-                    hipLaunchKernelGGL(bwt_long_heads_kernel, dim3(blocks), dim3(WG), 0, c->stream, c->cpos[cur], c->cgrp[cur], U, LT, c->ISA);
-                    hipLaunchKernelGGL(bwt_long_count_kernel, dim3(blocks), dim3(WG), 0, c->stream, c->dT, dcodes, c->csa[cur], c->cpos[cur], c->cgrp[cur],
-                                       U, h, n, smask, pp.cb, ta, LT, c->ISA);
-                    hipLaunchKernelGGL(bwt_long_scan_kernel, dim3(n_long), dim3(WG), 0, c->stream, LT, U, subhead);
-                    hipLaunchKernelGGL(bwt_long_scatter_kernel, dim3(blocks), dim3(WG), 0, c->stream, c->dT, dcodes, c->csa[cur], c->cpos[cur], c->cgrp[cur],
-                                       U, h, n, smask, pp.cb, ta, LT, c->ISA, c->csa[cur ^ 1]);
-                    hipLaunchKernelGGL(bwt_round_textsort_kernel, dim3((U + RS_T - 1) / RS_T), dim3(WG), 0, c->stream,
-                                       c->dT, dcodes, c->csa[cur ^ 1], c->cgrp[cur], U, h, n, smask, pp.cb, ta, c->kB, c->vB, c->dscal + 2, subhead);
-                    prof_end(c);
-                    HIP_TRY(c, hipMemcpyAsync(c->hscal + 2, c->dscal + 2, 4, hipMemcpyDeviceToHost, c->stream));
-                    HIP_TRY(c, ctx_sync(c));
-                    prof_collect(c);
-                    round_done = c->hscal[2] == 0;
-                }
-                if (dbg) fprintf(stderr, "[bwt] text round %d: %u long group(s) with %u of %u records: %s\n", rounds, n_long, n_long_rec, U,
-                                 !pays ? "not split (too many / too large)" : round_done ? "split by the top key bits -> sorted" : "split, but a bucket is still too long");
-            }
-            if (round_done) {
-                u32 U2 = 0;
-                first_flags = false;
-                rc = run_seg<false, false>(c, c->kB, c->vB, c->cpos[cur], U, 0, smask, c->cpos[cur ^ 1], c->csa[cur ^ 1], c->cgrp[cur ^ 1], &U2, SA, c->cgrp[cur]);
-                if (rc < 0) return rc;
-                cur ^= 1;
-                ++text_rounds;
-                h += ta;
-                if (dbg) fprintf(stderr, "[bwt] text round %d depth %llu U %u -> %u  (%.2f ms)\n", rounds, (unsigned long long)h, U, U2, lap());
-                const bool pays = U2 < 65536u || U2 <= U / 4;
-                U = U2;
-                if (U == 0 || (pays && text_rounds < 8)) continue;
-            } else if (dbg) fprintf(stderr, "[bwt] text round %d: group too long, handing over\n", rounds);
-            // hand over: ISA from the current order
-            u32 blocks = (n + WG - 1) / WG; if (blocks > 8192) blocks = 8192;
-            prof_begin(c, BSCGPU_K_SEG, (u64)n * 8, n);
-            hipLaunchKernelGGL(bwt_isa_fill_kernel, dim3(blocks), dim3(WG), 0, c->stream, SA, n, smask, c->ISA, first_flags ? c->flags : (const u8*)nullptr);
-            prof_end(c);
-            u32 fb = (U + WG - 1) / WG; if (fb > 8192) fb = 8192;
-            prof_begin(c, BSCGPU_K_SEG, (u64)U * 12, U);
-            hipLaunchKernelGGL(bwt_isa_fix_kernel, dim3(fb), dim3(WG), 0, c->stream, c->csa[cur], c->cgrp[cur], U, smask, c->ISA);
-            prof_end(c);
-            isa_valid = true;
-            if (round_done) continue;                // the round itself was done; the next one doubles
-        }
-        // segmented sort of the grouped records (falls back to the radix engine when a group is too long for one workgroup)
-        static const int segsort_on = [] { const char* e = getenv("BSC_BWT_SEGSORT"); return e ? atoi(e) : 1; }();
-        bool sorted = false;
-        // A round with a group of > RS_G records is a hybrid round.  BSC_BWT_HYBRID=0: never (the whole round through the radix engine, as in
-        // round 3); BSC_BWT_HYBRID_PCT=<p>: only while the groups of > HY_G records hold at most p % of the round's records (shared objects, first
-        // rounds: 48 of 57 M records are extracted; same box, 64 MiB: 40.4 ms without, 36.3 at 50 %, 34.8 at 100 % = the default).
-        static const int hybrid_on = [] { const char* e = getenv("BSC_BWT_HYBRID"); return e ? atoi(e) : 1; }();
-        static const int hybrid_pct = [] { const char* e = getenv("BSC_BWT_HYBRID_PCT"); return e ? atoi(e) : 100; }();
-        const bool hybrid = segsort_on && hybrid_on && n_long != 0 && n_mid != 0 && (u64)n_mid_rec * 100ull <= (u64)U * (u64)hybrid_pct;
-        if (segsort_on && n_long == 0 && !hybrid) {        // (with a group of > RS_G records the kernel would only find out and give up)
-            HIP_TRY(c, hipMemsetAsync(c->dscal + 2, 0, 4, c->stream));
-            prof_begin(c, BSCGPU_K_GATHER, (u64)U * (4 + 4 + 4 + 8 + 4), U);
-            hipLaunchKernelGGL(bwt_round_segsort_kernel, dim3((U + RS_T - 1) / RS_T), dim3(WG), 0, c->stream,
-                               c->csa[cur], c->cgrp[cur], c->ISA, U, h, (u64)n, lo_bits, smask, c->kB, c->vB, c->dscal + 2);
-            prof_end(c);
-            HIP_TRY(c, hipMemcpyAsync(c->hscal + 2, c->dscal + 2, 4, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, ctx_sync(c));
-            prof_collect(c);
-            sorted = (c->hscal[2] == 0);
-            ks = c->kB; vs = c->vB;
-        }
-        int np = 0;
-        if (!sorted && hybrid) {
-            // hybrid round: the long groups' records through the radix engine, the rest through the segmented sort (see bwt_longrec_kernel)
-            const u32 UL = n_mid_rec;                               // every record of a group of > HY_G records (seg_apply counted them)
-            if (SA == c->vA) {
-                HIP_TRY(c, hipMemcpyAsync(c->SA, c->vA, (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));
-                SA = c->SA;
-            }
-            const Chunking lc = make_chunking(U, LR_TILE);
-            u32* lidx = c->cpos[cur ^ 1];                          // the half the seg behind this round writes: free until then
-            prof_begin(c, BSCGPU_K_GATHER, (u64)U * 16 + (u64)UL * (4 + 4 + 4 + 8 + 4), U);
-            hipLaunchKernelGGL(bwt_longrec_kernel<false>, dim3(lc.num_chunks), dim3(WG), 0, c->stream, c->cpos[cur], c->csa[cur], c->cgrp[cur], c->ISA,
-                               U, h, (u64)n, lo_bits, smask, lc.chunk_tiles, lc.num_tiles, c->segsum, lidx, c->kA, c->vA);
-            hipLaunchKernelGGL(bwt_longrec_scan_kernel, dim3(1), dim3(WG), 0, c->stream, c->segsum, lc.num_chunks, c->segoff, c->dscal + DS_LRTOTAL);
-            hipLaunchKernelGGL(bwt_longrec_kernel<true>, dim3(lc.num_chunks), dim3(WG), 0, c->stream, c->cpos[cur], c->csa[cur], c->cgrp[cur], c->ISA,
-                               U, h, (u64)n, lo_bits, smask, lc.chunk_tiles, lc.num_tiles, c->segoff, lidx, c->kA, c->vA);
-            prof_end(c);
-            RadixPass rp[8];
-            const int kbits = lo_bits + bit_length((u64)(U - 1) >> LR_HEAD_SHIFT);      // 27 + 18 at 64 M unsorted records: 6 passes
-            for (int s = 0; s < kbits; s += 8) { rp[np].shift = s; rp[np].bits = (kbits - s < 8) ? kbits - s : 8; ++np; }
-            rc = radix_sort_passes(c, c->kA, c->kB, c->vA, c->vB, UL, rp, np, &in_alt);
-            if (rc < 0) return rc;
-            const u64* lks = in_alt ? c->kB : c->kA;
-            const u32* lvs = in_alt ? c->vB : c->vA;
-            u64* ko = in_alt ? c->kA : c->kB;                       // the pair the sorted long records are NOT in takes the round's output
-            u32* vo = in_alt ? c->vA : c->vB;
-            prof_begin(c, BSCGPU_K_GATHER, (u64)U * (4 + 4 + 4 + 8 + 4) + (u64)UL * (8 + 4 + 4 + 4 + 8 + 4), U);
-            hipLaunchKernelGGL(bwt_round_segsort_kernel, dim3((U + RS_T - 1) / RS_T), dim3(WG), 0, c->stream,
-                               c->csa[cur], c->cgrp[cur], c->ISA, U, h, (u64)n, lo_bits, smask, ko, vo, c->dscal + 2, 1u);
-            u32 pb = (UL + WG - 1) / WG; if (pb > 8192) pb = 8192;
-            hipLaunchKernelGGL(bwt_longrec_place_kernel, dim3(pb), dim3(WG), 0, c->stream, lks, lvs, lidx, c->cgrp[cur], UL, lo_bits, ko, vo);
-            prof_end(c);
-            HIP_TRY(c, hipGetLastError());
-            ks = ko; vs = vo;
-            sorted = true;
-            if (dbg) fprintf(stderr, "[bwt] round %d: hybrid, %u of %u records in %u group(s) of > 256\n", rounds, UL, U, n_mid);
-        }
-        if (!sorted) {
-            if (SA == c->vA) {                       // the radix engine is about to use vA: SA moves to its own buffer
-                HIP_TRY(c, hipMemcpyAsync(c->SA, c->vA, (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));
-                SA = c->SA;
-            }
-            u32 blocks = (U + WG - 1) / WG; if (blocks > 8192) blocks = 8192;
-            prof_begin(c, BSCGPU_K_GATHER, (u64)U * (4 + 4 + 4 + 8 + 4), U);
-            hipLaunchKernelGGL(bwt_gather_kernel, dim3(blocks), dim3(WG), 0, c->stream,
-                               c->csa[cur], c->cgrp[cur], c->ISA, U, h, (u64)n, lo_bits, smask, c->kA, c->vA);
-            prof_end(c);
-
-            RadixPass rp[8];
-            const int kbits = lo_bits + hi_bits;            // key = (group rank << lo_bits) | next rank : 53 bits at n = 2^26 -> 7 passes
-            for (int s = 0; s < kbits; s += 8) { rp[np].shift = s; rp[np].bits = (kbits - s < 8) ? kbits - s : 8; ++np; }
-            rc = radix_sort_passes(c, c->kA, c->kB, c->vA, c->vB, U, rp, np, &in_alt);
-            if (rc < 0) return rc;
-            ks = in_alt ? c->kB : c->kA;
-            vs = in_alt ? c->vB : c->vA;
-        }
-
-        u32 U2 = 0;
-        // (the keys' group field starts at lo_bits: a new group that begins where an old one did keeps its rank, its ISA stores are skipped)
-        static const int isa_skip = [] { const char* e = getenv("BSC_BWT_ISASKIP"); return e ? atoi(e) : 1; }();
-        rc = run_seg<false, true>(c, ks, vs, c->cpos[cur], U, 0, smask, c->cpos[cur ^ 1], c->csa[cur ^ 1], c->cgrp[cur ^ 1], &U2, SA, nullptr, isa_skip ? lo_bits : 0);
-        if (rc < 0) return rc;
-        if (hybrid && c->hscal[DS_LRTOTAL] != n_mid_rec) return ctx_fail(c, BSC_GPU_ERROR, "hybrid round: extracted records differ from the counted ones", hipSuccess);
-        cur ^= 1;
-        if (dbg) fprintf(stderr, "[bwt] round %d h=%llu U %u -> %u (passes %d)  (%.2f ms)\n", rounds, (unsigned long long)h, U, U2, np, lap());
-        U = U2;
-        h <<= 1;
+// The radix engine is about to use vA: SA moves to its own buffer
+static int bwt_sa_to_own_buffer(bscgpu_ctx* c, BwtRounds& s)
+{
+    if (s.SA == c->vA) {
+        const u32 n = s.n;
+        HIP_TRY(c, hipMemcpyAsync(c->SA, c->vA, (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));
+        s.SA = c->SA;
     }
-    c->stage_ms[5] = rounds;
+    return BSC_NO_ERROR;
+}
 
-    if (bt) {
-        // every block's indexes from the final ISA, every block's L in place; one copy of the results, one sync for the pass
-        prof_begin(c, BSCGPU_K_EMIT, (u64)n * 10, n);
-        HIP_TRY(c, hipMemsetAsync(bt->res, 0, (size_t)bt->count * 16 * 4, c->stream));
-        hipLaunchKernelGGL(bwt_batch_find_kernel, dim3((bt->count + WG - 1) / WG), dim3(WG), 0, c->stream, c->ISA, n, bt->off, bt->rate, bt->count, bt->res);
-        hipLaunchKernelGGL(bwt_batch_emit_kernel, dim3((n + WG - 1) / WG), dim3(WG), 0, c->stream, c->dT, SA, c->ISA, n, bt->off, bt->rate, bt->count, dL_user);
-        prof_end(c);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(bt->res_host, bt->res, (size_t)bt->count * 16 * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, ctx_sync(c));
-        prof_collect(c);
-        *primary_out = 0;
-        return BSC_NO_ERROR;
+// The sort of a round on text keys and its verdict, output in kB / vB.  csa: the round's suffixes; subhead: extra group boundaries or
+// null.  The caller has cleared the give-up word and opened the profile bracket.
+static int bwt_textsort(bscgpu_ctx* c, BwtRounds& s, const u32* csa, const u8* subhead, bool* sorted)
+{
+    hipLaunchKernelGGL(bwt_round_textsort_kernel, dim3((s.U + RS_T - 1) / RS_T), dim3(WG), 0, c->stream,
+                       c->dT, s.dcodes, csa, c->cgrp[s.cur], s.U, s.h, s.n, s.smask, s.pp.cb, s.ta, c->kB, c->vB, c->dscal + 2, subhead);
+    prof_end(c);
+    return bwt_giveup_read(c, sorted);
+}
+
+static int bwt_round_text(bscgpu_ctx* c, BwtRounds& s, bool* sorted)
+{
+    const u32 U = s.U;
+    RC_TRY(bwt_giveup_clear(c));
+    prof_begin(c, BSCGPU_K_GATHER, (u64)U * (4 + 4 + 16 + 8 + 4), U);
+    return bwt_textsort(c, s, c->csa[s.cur], nullptr, sorted);
+}
+
+// The long groups' tables in an allocation of their own, made when a block first needs them — 16.8 MB per context; round 3 carved them
+// out of kA on the strength of a comment.  false: not to be had (the round is handed over)
+constexpr size_t LT_BYTES = (size_t)(64 + LG_MAX + (size_t)LG_MAX * LG_BUCKETS) * 4;
+static bool bwt_long_tables_ensure(bscgpu_ctx* c)
+{
+    if (!c->long_tables && hipMalloc((void**)&c->long_tables, LT_BYTES) != hipSuccess) { (void)hipGetLastError(); c->long_tables = nullptr; }
+    return c->long_tables != nullptr;
+}
+
+// ... with the n_long groups too long for one workgroup split by the top bits of the round's key first.  Group ids go to ISA, which
+// does not exist yet on this path — isa_valid is false, it is built at the hand-over —, sub-group heads to flags, which only the
+// seg kernels behind the round rewrite; the permuted suffixes to csa[cur ^ 1], the half the next seg writes.
+static int bwt_round_text_split(bscgpu_ctx* c, BwtRounds& s, u32 n_long, bool* sorted)
+{
+    const u32 U = s.U, n = s.n, smask = s.smask, ta = s.ta; const u64 h = s.h; const int cur = s.cur; const PackParams& pp = s.pp; u8* const dcodes = s.dcodes;
+    LongTables LT;
+    LT.nlong = c->long_tables; LT.khead = LT.nlong + 64; LT.cnt = LT.khead + LG_MAX;
+    u8* subhead = c->flags;
+    s.first_flags = false;
+    HIP_TRY(c, hipMemsetAsync(LT.nlong, 0, LT_BYTES, c->stream));
+    HIP_TRY(c, hipMemsetAsync(subhead, 0, (size_t)U + 1, c->stream));
+    RC_TRY(bwt_giveup_clear(c));
+    const u32 blocks = capped_grid(U, 4096);
+    prof_begin(c, BSCGPU_K_GATHER, (u64)U * (8 + (8 + 4 + 16 + 4) * 2), U);
+    hipLaunchKernelGGL(bwt_long_heads_kernel, dim3(blocks), dim3(WG), 0, c->stream, c->cpos[cur], c->cgrp[cur], U, LT, c->ISA);
+    hipLaunchKernelGGL(bwt_long_count_kernel, dim3(blocks), dim3(WG), 0, c->stream, c->dT, dcodes, c->csa[cur], c->cpos[cur], c->cgrp[cur],
+                       U, h, n, smask, pp.cb, ta, LT, c->ISA);
+    hipLaunchKernelGGL(bwt_long_scan_kernel, dim3(n_long), dim3(WG), 0, c->stream, LT, U, subhead);
+    hipLaunchKernelGGL(bwt_long_scatter_kernel, dim3(blocks), dim3(WG), 0, c->stream, c->dT, dcodes, c->csa[cur], c->cpos[cur], c->cgrp[cur],
+                       U, h, n, smask, pp.cb, ta, LT, c->ISA, c->csa[cur ^ 1]);
+    return bwt_textsort(c, s, c->csa[cur ^ 1], subhead, sorted);
+}
+
+// The seg behind a round on text keys that sorted its records.  *more: the next round is one on text keys too
+static int bwt_text_advance(bscgpu_ctx* c, BwtRounds& s, bool* more)
+{
+    const int cur = s.cur;
+    u32 U2 = 0;
+    s.first_flags = false;
+    RC_TRY((run_seg<false, false>(c, c->kB, c->vB, c->cpos[cur], s.U, 0, s.smask, c->cpos[cur ^ 1], c->csa[cur ^ 1], c->cgrp[cur ^ 1], &U2, s.SA, c->cgrp[cur])));
+    s.cur ^= 1;
+    ++s.text_rounds;
+    s.h += s.ta;
+    if (s.dbg) fprintf(stderr, "[bwt] text round %d depth %llu U %u -> %u  (%.2f ms)\n", s.rounds, (unsigned long long)s.h, s.U, U2, bwt_lap(s));
+    *more = U2 == 0 || bwt_text_round_pays(s.U, U2, s.text_rounds);
+    s.U = U2;
+    return BSC_NO_ERROR;
+}
+
+// hand over to prefix doubling: ISA from the current order
+static int bwt_hand_over(bscgpu_ctx* c, BwtRounds& s)
+{
+    const u32 n = s.n, U = s.U;
+    prof_begin(c, BSCGPU_K_SEG, (u64)n * 8, n);
+    hipLaunchKernelGGL(bwt_isa_fill_kernel, dim3(capped_grid(n)), dim3(WG), 0, c->stream, s.SA, n, s.smask, c->ISA, s.first_flags ? c->flags : (const u8*)nullptr);
+    prof_end(c);
+    prof_begin(c, BSCGPU_K_SEG, (u64)U * 12, U);
+    hipLaunchKernelGGL(bwt_isa_fix_kernel, dim3(capped_grid(U)), dim3(WG), 0, c->stream, c->csa[s.cur], c->cgrp[s.cur], U, s.smask, c->ISA);
+    prof_end(c);
+    s.isa_valid = true;
+    return BSC_NO_ERROR;
+}
+
+// segmented sort of the grouped records (gives up when a group is too long for one workgroup: the radix engine then takes the round)
+static int bwt_round_segsort(bscgpu_ctx* c, BwtRounds& s, bool* sorted)
+{
+    const u32 U = s.U;
+    RC_TRY(bwt_giveup_clear(c));
+    prof_begin(c, BSCGPU_K_GATHER, (u64)U * (4 + 4 + 4 + 8 + 4), U);
+    hipLaunchKernelGGL(bwt_round_segsort_kernel, dim3((U + RS_T - 1) / RS_T), dim3(WG), 0, c->stream,
+                       c->csa[s.cur], c->cgrp[s.cur], c->ISA, U, s.h, (u64)s.n, s.lo_bits, s.smask, c->kB, c->vB, c->dscal + 2);
+    prof_end(c);
+    s.ks = c->kB; s.vs = c->vB;
+    return bwt_giveup_read(c, sorted);
+}
+
+// hybrid round: the long groups' records through the radix engine, the rest through the segmented sort (see bwt_longrec_kernel)
+static int bwt_round_hybrid(bscgpu_ctx* c, BwtRounds& s, const BwtRoundCounts& g, int* np)
+{
+    const u32 U = s.U, n = s.n, smask = s.smask; const u64 h = s.h; const int cur = s.cur, lo_bits = s.lo_bits;
+    const u32 UL = g.n_mid_rec;                             // every record of a group of > HY_G records (seg_apply counted them)
+    RC_TRY(bwt_sa_to_own_buffer(c, s));
+    const Chunking lc = make_chunking(U, LR_TILE);
+    u32* lidx = c->cpos[cur ^ 1];                          // the half the seg behind this round writes: free until then
+    prof_begin(c, BSCGPU_K_GATHER, (u64)U * 16 + (u64)UL * (4 + 4 + 4 + 8 + 4), U);
+    hipLaunchKernelGGL(bwt_longrec_kernel<false>, dim3(lc.num_chunks), dim3(WG), 0, c->stream, c->cpos[cur], c->csa[cur], c->cgrp[cur], c->ISA,
+                       U, h, (u64)n, lo_bits, smask, lc.chunk_tiles, lc.num_tiles, c->segsum, lidx, c->kA, c->vA);
+    hipLaunchKernelGGL(bwt_longrec_scan_kernel, dim3(1), dim3(WG), 0, c->stream, c->segsum, lc.num_chunks, c->segoff, c->dscal + DS_LRTOTAL);
+    hipLaunchKernelGGL(bwt_longrec_kernel<true>, dim3(lc.num_chunks), dim3(WG), 0, c->stream, c->cpos[cur], c->csa[cur], c->cgrp[cur], c->ISA,
+                       U, h, (u64)n, lo_bits, smask, lc.chunk_tiles, lc.num_tiles, c->segoff, lidx, c->kA, c->vA);
+    prof_end(c);
+    RadixPass rp[8];
+    *np = bwt_cut_passes(rp, 0, lo_bits + bwt_bit_length((u64)(U - 1) >> LR_HEAD_SHIFT));      // 27 + 18 at 64 M unsorted records: 6 passes
+    RC_TRY(radix_sort_passes(c, c->kA, c->kB, c->vA, c->vB, UL, rp, *np, &s.in_alt));
+    const u64* lks = s.in_alt ? c->kB : c->kA;
+    const u32* lvs = s.in_alt ? c->vB : c->vA;
+    u64* ko = s.in_alt ? c->kA : c->kB;                     // the pair the sorted long records are NOT in takes the round's output
+    u32* vo = s.in_alt ? c->vA : c->vB;
+    prof_begin(c, BSCGPU_K_GATHER, (u64)U * (4 + 4 + 4 + 8 + 4) + (u64)UL * (8 + 4 + 4 + 4 + 8 + 4), U);
+    hipLaunchKernelGGL(bwt_round_segsort_kernel, dim3((U + RS_T - 1) / RS_T), dim3(WG), 0, c->stream,
+                       c->csa[cur], c->cgrp[cur], c->ISA, U, h, (u64)n, lo_bits, smask, ko, vo, c->dscal + 2, 1u);
+    hipLaunchKernelGGL(bwt_longrec_place_kernel, dim3(capped_grid(UL)), dim3(WG), 0, c->stream, lks, lvs, lidx, c->cgrp[cur], UL, lo_bits, ko, vo);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    s.ks = ko; s.vs = vo;
+    if (s.dbg) fprintf(stderr, "[bwt] round %d: hybrid, %u of %u records in %u group(s) of > 256\n", s.rounds, UL, U, g.n_mid);
+    return BSC_NO_ERROR;
+}
+
+// the whole round through the radix engine
+static int bwt_round_radix(bscgpu_ctx* c, BwtRounds& s, int* np)
+{
+    const u32 U = s.U, n = s.n;
+    RC_TRY(bwt_sa_to_own_buffer(c, s));
+    prof_begin(c, BSCGPU_K_GATHER, (u64)U * (4 + 4 + 4 + 8 + 4), U);
+    hipLaunchKernelGGL(bwt_gather_kernel, dim3(capped_grid(U)), dim3(WG), 0, c->stream,
+                       c->csa[s.cur], c->cgrp[s.cur], c->ISA, U, s.h, (u64)n, s.lo_bits, s.smask, c->kA, c->vA);
+    prof_end(c);
+
+    RadixPass rp[8];
+    *np = bwt_cut_passes(rp, 0, s.lo_bits + bwt_bit_length(n - 1));     // key = (group rank << lo_bits) | next rank : 53 bits at n = 2^26 -> 7 passes
+    RC_TRY(radix_sort_passes(c, c->kA, c->kB, c->vA, c->vB, U, rp, *np, &s.in_alt));
+    s.ks = s.in_alt ? c->kB : c->kA;
+    s.vs = s.in_alt ? c->vB : c->vA;
+    return BSC_NO_ERROR;
+}
+
+// Runs the sort of one round.  *sorted: a text round's or a segmented sort's verdict; *np: digit passes of the radix engine
+static int bwt_run_round(bscgpu_ctx* c, BwtRounds& s, BwtRound kind, const BwtRoundCounts& g, bool* sorted, int* np)
+{
+    switch (kind) {
+    case BWT_ROUND_TEXT:       return bwt_round_text(c, s, sorted);
+    case BWT_ROUND_TEXT_SPLIT: return bwt_round_text_split(c, s, g.n_long, sorted);
+    case BWT_ROUND_HAND_OVER:  return BSC_NO_ERROR;                 // (no sort: the caller hands over)
+    case BWT_ROUND_HYBRID:     return bwt_round_hybrid(c, s, g, np);
+    case BWT_ROUND_RADIX:      return bwt_round_radix(c, s, np);
+    case BWT_ROUND_SEGSORT: {
+        const int rc = bwt_round_segsort(c, s, sorted);
+        return (rc < 0 || *sorted) ? rc : bwt_round_radix(c, s, np);
     }
-    // primary index and aux indexes from SA, then the last column
+    }
+    return BSC_BAD_PARAMETER;
+}
+
+// The seg behind a doubling round: the new unsorted set, ISA of the suffixes it settled
+static int bwt_doubling_advance(bscgpu_ctx* c, BwtRounds& s, BwtRound kind, const BwtRoundCounts& g, int np)
+{
+    const int cur = s.cur;
+    u32 U2 = 0;
+    // (the keys' group field starts at lo_bits: a new group that begins where an old one did keeps its rank, its ISA stores are skipped)
+    RC_TRY((run_seg<false, true>(c, s.ks, s.vs, c->cpos[cur], s.U, 0, s.smask, c->cpos[cur ^ 1], c->csa[cur ^ 1], c->cgrp[cur ^ 1], &U2, s.SA, nullptr,
+                                 bwt_switches().isa_skip ? s.lo_bits : 0)));
+    if (kind == BWT_ROUND_HYBRID && c->hscal[DS_LRTOTAL] != g.n_mid_rec) return ctx_fail(c, BSC_GPU_ERROR, "hybrid round: extracted records differ from the counted ones", hipSuccess);
+    s.cur ^= 1;
+    if (s.dbg) fprintf(stderr, "[bwt] round %d h=%llu U %u -> %u (passes %d)  (%.2f ms)\n", s.rounds, (unsigned long long)s.h, s.U, U2, np, bwt_lap(s));
+    s.U = U2;
+    s.h <<= 1;
+    return BSC_NO_ERROR;
+}
+
+// The ending of a batched pass: every block's indexes from the final ISA, every block's L in place; one copy of the results, one sync for the pass
+static int bwt_emit_batch(bscgpu_ctx* c, const BwtRounds& s, const BwtBatch* bt, u8* dL_user, int64_t* primary_out)
+{
+    const u32 n = s.n;
+    prof_begin(c, BSCGPU_K_EMIT, (u64)n * 10, n);
+    HIP_TRY(c, hipMemsetAsync(bt->res, 0, (size_t)bt->count * 16 * 4, c->stream));
+    hipLaunchKernelGGL(bwt_batch_find_kernel, dim3((bt->count + WG - 1) / WG), dim3(WG), 0, c->stream, c->ISA, n, bt->off, bt->rate, bt->count, bt->res);
+    hipLaunchKernelGGL(bwt_batch_emit_kernel, dim3((n + WG - 1) / WG), dim3(WG), 0, c->stream, c->dT, s.SA, c->ISA, n, bt->off, bt->rate, bt->count, dL_user);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(bt->res_host, bt->res, (size_t)bt->count * 16 * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    prof_collect(c);
+    *primary_out = 0;
+    return BSC_NO_ERROR;
+}
+
+// The ending of a single block: primary index and aux indexes from SA, then the last column
+static int bwt_emit_single(bscgpu_ctx* c, const BwtRounds& s, const u8* ddecode, u8* dL_user, int64_t n64, int64_t r, u32* I_host, int64_t* primary_out)
+{
+    const u32 n = s.n;
     u32 cnt = 0, rshift = 0;
     if (I_host != nullptr) {
         if (r <= 0 || (r & (r - 1)) != 0) return BSC_BAD_PARAMETER;
@@ -1714,15 +1683,15 @@ static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_
     }
     prof_begin(c, BSCGPU_K_EMIT, (u64)n * 4, n);
     hipLaunchKernelGGL(bwt_find_kernel, dim3((n + 4 * WG - 1) / (4 * WG)), dim3(WG), 0, c->stream,
-                       SA, n, smask, cnt ? (u32)(r - 1) : 0u, rshift, cnt, c->dscal);
+                       s.SA, n, s.smask, cnt ? (u32)(r - 1) : 0u, rshift, cnt, c->dscal);
     prof_end(c);
     prof_begin(c, BSCGPU_K_EMIT, (u64)n * 6, n);
-    if (pp.pred_shift)
+    if (s.pp.pred_shift)
         hipLaunchKernelGGL(bwt_emit_pred_kernel, dim3((n + 4 * WG - 1) / (4 * WG)), dim3(WG), 0, c->stream,
-                           c->dT, SA, n, pp.pred_shift, ddecode, dL_user, c->dscal);
+                           c->dT, s.SA, n, s.pp.pred_shift, ddecode, dL_user, c->dscal);
     else
         hipLaunchKernelGGL(bwt_emit_kernel, dim3((n + 4 * WG - 1) / (4 * WG)), dim3(WG), 0, c->stream,
-                           c->dT, SA, n, dL_user, c->dscal);
+                           c->dT, s.SA, n, dL_user, c->dscal);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(c->hscal, c->dscal, (8 + 256) * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1731,4 +1700,59 @@ static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_
     *primary_out = c->hscal[1];
     for (u32 t = 0; t < cnt; ++t) I_host[t] = c->hscal[8 + t];
     return BSC_NO_ERROR;
+}
+
+// One transform: first sort, first seg, and while suffixes are unsorted: decide the round (bwt_plan.h), run it, seg, advance; then emit.
+static int bwt_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_t n64, int64_t r, u32* I_host, int64_t* primary_out,
+                           const BwtBatch* bt)
+{
+    if (n64 < 0 || n64 > c->max_n || n64 >= 0x7fffffffll) return BSC_BAD_PARAMETER;
+    if (n64 == 0) { *primary_out = 0; return BSC_NO_ERROR; }
+    const u32 n = (u32)n64;
+    const BwtSwitches& sw = bwt_switches();
+
+    FirstSort fs;
+    RC_TRY(bwt_first_sort(c, dT_user, n, bt, &fs));
+    BwtRounds s;
+    s.n = n; s.pp = fs.pp; s.smask = fs.kp.smask; s.ta = fs.kp.ta; s.dcodes = fs.dcodes; s.lo_bits = bwt_bit_length(n);
+    s.cur = 0; s.U = 0; s.h = fs.pp.w; s.ks = fs.ks; s.vs = fs.vs; s.in_alt = 0; s.rounds = 0; s.text_rounds = 0; s.first_flags = true;
+    // text rounds read the text past a suffix: not across block ends; their keys hold 2 .. 15 characters
+    s.isa_valid = bt != nullptr || !(sw.text_rounds && s.ta >= 2 && s.ta <= 15);
+    s.SA = (s.vs == c->vA) ? c->vA : c->SA;
+    if (s.isa_valid) RC_TRY((run_seg<true, true >(c, s.ks, s.vs, nullptr, n, fs.kp.tail_lo, s.smask, c->cpos[0], c->csa[0], c->cgrp[0], &s.U, s.SA)));
+    else             RC_TRY((run_seg<true, false>(c, s.ks, s.vs, nullptr, n, fs.kp.tail_lo, s.smask, c->cpos[0], c->csa[0], c->cgrp[0], &s.U, s.SA)));
+
+    s.dbg = getenv("BSCGPU_DEBUG") != nullptr;
+    if (s.dbg) fprintf(stderr, "[bwt] n=%u initial unsorted=%u\n", n, s.U);
+    s.t_round = s.dbg ? bwt_now_ms() : 0.0;
+    while (s.U > 0) {
+        if (++s.rounds > 60) return ctx_fail(c, BSC_GPU_ERROR, "prefix doubling did not converge", hipSuccess);
+        // what the seg that produced this unsorted set counted (seg_apply): groups of > RS_G records, which no segmented sort of this
+        // round can take, and groups of > HY_G records (hybrid rounds), each with their records
+        const BwtRoundCounts g = {s.U, c->hscal[DS_NLONG], c->hscal[DS_EXCESS] + c->hscal[DS_NLONG] * (u32)RS_G,
+                                  c->hscal[DS_NMID], c->hscal[DS_MIDEXCESS] + c->hscal[DS_NMID] * (u32)HY_G};
+        BwtRound kind = bwt_round_kind(s.isa_valid, g, sw, LG_MAX);
+        if (kind == BWT_ROUND_TEXT_SPLIT && !bwt_long_tables_ensure(c)) kind = BWT_ROUND_HAND_OVER;
+        bool sorted = false;
+        int np = 0;
+        if (!s.isa_valid) {
+            // a round on text keys; it hands over to doubling when a group does not fit a workgroup or the round did not pay
+            RC_TRY(bwt_run_round(c, s, kind, g, &sorted, &np));
+            if (s.dbg && kind != BWT_ROUND_TEXT)
+                fprintf(stderr, "[bwt] text round %d: %u long group(s) with %u of %u records: %s\n", s.rounds, g.n_long, g.n_long_rec, s.U,
+                        kind == BWT_ROUND_HAND_OVER ? "not split (too many / too large)" : sorted ? "split by the top key bits -> sorted" : "split, but a bucket is still too long");
+            if (sorted) {
+                bool more = false;
+                RC_TRY(bwt_text_advance(c, s, &more));
+                if (more) continue;
+            } else if (s.dbg) fprintf(stderr, "[bwt] text round %d: group too long, handing over\n", s.rounds);
+            RC_TRY(bwt_hand_over(c, s));
+            if (sorted) continue;                    // the round itself was done; the next one doubles
+            kind = bwt_round_kind(true, g, sw, LG_MAX);     // this round doubles
+        }
+        RC_TRY(bwt_run_round(c, s, kind, g, &sorted, &np));
+        RC_TRY(bwt_doubling_advance(c, s, kind, g, np));
+    }
+    c->stage_ms[5] = s.rounds;
+    return bt ? bwt_emit_batch(c, s, bt, dL_user, primary_out) : bwt_emit_single(c, s, fs.ddecode, dL_user, n64, r, I_host, primary_out);
 }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../../include/bscgpu.h"
+#include "bwt_plan.h"      // RadixPass; the BWT driver's plan (host arithmetic, no HIP)
 
 typedef unsigned long long u64;
 typedef unsigned int       u32;
@@ -202,6 +203,7 @@ hipError_t ctx_sync(bscgpu_ctx* c);   // wait for everything queued on c->stream
     do { hipError_t _e = (expr);                                                   \
          if (_e != hipSuccess) return ctx_fail((ctx), BSC_GPU_ERROR, #expr, _e);   \
     } while (0)
+#define RC_TRY(expr) do { const int _rc = (expr); if (_rc < 0) return _rc; } while (0)     // an internal call's error code goes up as it is
 
 // profiling brackets: PROF_BEGIN/END record events on ctx->stream around a launch.
 void prof_begin(bscgpu_ctx* c, int kind, u64 bytes, u64 records);
@@ -209,7 +211,6 @@ void prof_end(bscgpu_ctx* c);
 void prof_collect(bscgpu_ctx* c);   // after a stream sync: fold pending events into kstat
 
 // ---- internal device-layer entry points (all asynchronous on ctx->stream) ---------------------
-struct RadixPass { int shift; int bits; };
 // Sort n records; passes applied in order (LSD).  Result lands in (keys, vals) if the number of
 // passes is even, else in (keys_alt, vals_alt); *in_alt tells which.
 // emit_pos (optional; one keys-only pass): emit_pos[i] = index in the output of input record i.
@@ -225,6 +226,26 @@ int  radix_onesweep_prepare(bscgpu_ctx* c, u64 n, int npasses, u32** totals = nu
 int  radix_onesweep_sort(bscgpu_ctx* c, u64* keys, u64* keys_alt, u32* vals, u32* vals_alt, u64 n, const RadixPass* passes, int npasses,
                          bool totals_ready = false);
 int  radix_onesweep_check(bscgpu_ctx* c);   // after the next stream sync: did a pass of the last such sort give up a wait?
+// A single-read digit pass that gave up a wait (radix_onesweep.hip: bounded polls; pre-emption, a debugger, a hogged CU) fails the
+// sort, not the block: the transform is redone once with the three-kernel passes, which have no cross-workgroup protocol at all.
+// once(second_attempt) runs the transform; every sort in it is checked (radix_onesweep_check) before anything is written to the
+// caller's buffer.  The BWT does NOT rely on its private copy of the text for the second attempt (it may have been clobbered by
+// kernels that ran behind the failed sort — kernels that consume a failed sort's output run before the check, on stale keys and
+// values: see seg_apply_kernel — while the caller's buffer is untouched until the last kernel of a transform): it copies the text
+// again.  The ST's caller's buffer may already hold the failed attempt's bytes when it is also the output: it reuses its copy.
+template <class Once>
+static inline int with_onesweep_retry(bscgpu_ctx* c, Once once)
+{
+    c->os_gave_up = false;
+    int rc = once(false);
+    if (rc == BSC_GPU_ERROR && c->os_gave_up) {
+        const int mode = c->os_mode;
+        c->os_mode = 0; c->os_gave_up = false; ++c->os_retries;
+        rc = once(true);
+        c->os_mode = mode;
+    }
+    return rc;
+}
 int radix_engine_setup(bscgpu_ctx* c);     // per-device kernel attributes; bscgpu_create calls it with c->device current
 
 int bwt_device(bscgpu_ctx* c, const u8* dT_user, u8* dL_user, int64_t n, int64_t r, u32* I_host,
@@ -245,6 +266,10 @@ int st_batch_device(bscgpu_ctx* c, const u8* dT_user, u8* dOut_user, const int* 
 // (stride 2: doff holds a (start, end) pair per block, blocks anywhere in d)
 void launch_adler_batch(bscgpu_ctx* c, const u8* d, const u32* doff, u32 count, u32* dout, u32 stride = 1);     // st.hip (asynchronous)
 int batch_tab_ensure(bscgpu_ctx* c);       // bwt.hip: batch_tab on first use
+// The set-up of a batched BWT / ST pass (bwt.hip): count and total checked, the block table built and uploaded, every block's Adler-32
+// launched where asked for.  total == 0: nothing to do.  index_out (ST only): zeroed, and rates may then be null (all blocks transformed).
+struct BatchTab { u32 total; const u32* off; const int* rate; u32* res; };      // device: offsets [count + 1], rates [count], results
+int batch_pass_setup(bscgpu_ctx* c, const u8* dT_user, const int* sizes, int count, const int* rates, int* index_out, u32* adler_host, BatchTab* bt);
 // Batched inverse-BWT pass (unbwt.hip): `count` <= unbwt_batch_max_blocks(max_n) blocks, L of sizes[b] bytes back to back at
 // dL (sum <= max_n); idx[b] = the block's primary index (1..n_b), 0 = not decoded (nothing written).  Block b's T goes to out + dst[b]
 // (dst[b] + n_b < 2^32; out may be dL).  res[b] = 0, LIBBSC_DATA_CORRUPT or LIBBSC_NOT_SUPPORTED (0 for a block not decoded).

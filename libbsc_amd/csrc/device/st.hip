@@ -83,15 +83,7 @@ static int st_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dOut_user, int n
 // the private copy of the text (the caller's buffer may already hold the failed attempt's bytes when it is also the output)
 int st_device(bscgpu_ctx* c, const u8* dT_user, u8* dOut_user, int n_, int k, int* index_out)
 {
-    c->os_gave_up = false;
-    int rc = st_device_once(c, dT_user, dOut_user, n_, k, index_out, false);
-    if (rc == BSC_GPU_ERROR && c->os_gave_up) {
-        const int mode = c->os_mode;
-        c->os_mode = 0; c->os_gave_up = false; ++c->os_retries;
-        rc = st_device_once(c, dT_user, dOut_user, n_, k, index_out, true);
-        c->os_mode = mode;
-    }
-    return rc;
+    return with_onesweep_retry(c, [&](bool reuse_text) { return st_device_once(c, dT_user, dOut_user, n_, k, index_out, reuse_text); });
 }
 
 static int st_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dOut_user, int n_, int k, int* index_out, bool reuse_text)
@@ -116,7 +108,7 @@ static int st_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dOut_user, int n
         prof_begin(c, BSCGPU_K_PACK, (u64)n * 9, n);
         hipLaunchKernelGGL(st_pack_kernel<false>, grid, dim3(WG), 0, c->stream, c->dT, n, c->kA, (u32*)nullptr, c->dscal64);
         prof_end(c);
-        for (int p = 0; p < k; ++p) { passes[p].shift = (7 - k) * 8 + 8 * p; passes[p].bits = 8; }
+        bwt_cut_passes(passes, (7 - k) * 8, 8 * k);
         rc = radix_sort_passes(c, c->kA, c->kB, nullptr, nullptr, n, passes, k, &in_alt);
         if (rc < 0) return rc;
         prof_begin(c, BSCGPU_K_EMIT, (u64)n * 9, n);
@@ -127,7 +119,7 @@ static int st_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dOut_user, int n
         prof_begin(c, BSCGPU_K_PACK, (u64)n * 13, n);
         hipLaunchKernelGGL(st_pack_kernel<true>, grid, dim3(WG), 0, c->stream, c->dT, n, c->kA, c->vA, c->dscal64);
         prof_end(c);
-        for (int p = 0; p < 8; ++p) { passes[p].shift = 8 * p; passes[p].bits = 8; }
+        bwt_cut_passes(passes, 0, 64);
         rc = radix_sort_passes(c, c->kA, c->kB, c->vA, c->vB, n, passes, 8, &in_alt);
         if (rc < 0) return rc;
         prof_begin(c, BSCGPU_K_EMIT, (u64)n * 5, n);
@@ -265,7 +257,7 @@ static int st_batch_once(bscgpu_ctx* c, const u8* dT_user, u8* dOut_user, u32 N,
     if (kv) hipLaunchKernelGGL(st_batch_pack_kernel<true>, grid, dim3(WG), 0, c->stream, c->dT, N, doff, drate, count, kcur, vcur);
     else hipLaunchKernelGGL(st_batch_pack_kernel<false>, grid, dim3(WG), 0, c->stream, c->dT, N, doff, drate, count, kcur, vcur);
     prof_end(c);
-    for (int p = 0; p < k; ++p) { passes[np].shift = (kv ? 8 * (8 - k) : (int)STB_CTX_SHIFT + 8 * (5 - k)) + 8 * p; passes[np++].bits = 8; }
+    np = bwt_cut_passes(passes, kv ? 8 * (8 - k) : (int)STB_CTX_SHIFT + 8 * (5 - k), 8 * k);
     const int block_shift = kv ? 0 : (int)STB_BLOCK_SHIFT;
     if (kv && bb > 0) {
         rc = radix_sort_passes(c, kcur, kalt, vcur, valt, N, passes, np, &in_alt);
@@ -276,8 +268,7 @@ static int st_batch_once(bscgpu_ctx* c, const u8* dT_user, u8* dOut_user, u32 N,
         prof_end(c);
         np = 0;
     }
-    if (bb > 0) { passes[np].shift = block_shift; passes[np++].bits = bb < 8 ? bb : 8; }
-    if (bb > 8) { passes[np].shift = block_shift + 8; passes[np++].bits = bb - 8; }
+    np += bwt_cut_passes(passes + np, block_shift, bb);
     rc = radix_sort_passes(c, kcur, kalt, vcur, valt, N, passes, np, &in_alt);
     if (rc < 0) return rc;
     if (in_alt) { u64* tk = kcur; kcur = kalt; kalt = tk; u32* tv = vcur; vcur = valt; valt = tv; }
@@ -299,34 +290,13 @@ static int st_batch_once(bscgpu_ctx* c, const u8* dT_user, u8* dOut_user, u32 N,
 int st_batch_device(bscgpu_ctx* c, const u8* dT_user, u8* dOut_user, const int* sizes, int count, int k, const int* rates, int* index_out,
                     u32* adler_host)
 {
-    if (count <= 0 || count > BATCH_MAX_BLOCKS || k < 3 || k > 8) return BSC_BAD_PARAMETER;
-    const int trc = batch_tab_ensure(c);
-    if (trc < 0) return trc;
-    std::vector<u32> tab((size_t)2 * count + 1, 0u);
-    u64 total = 0;
-    for (int b = 0; b < count; ++b) { tab[b] = (u32)total; total += (u64)sizes[b]; index_out[b] = 0; }
-    tab[count] = (u32)total;
-    if (rates) memcpy(&tab[count + 1], rates, (size_t)count * 4);
-    if (total == 0) return BSC_NO_ERROR;
-    if (total > (u64)c->max_n || total >= 0x7fffffffull) return BSC_BAD_PARAMETER;
-    const u32* doff = c->batch_tab;
-    const int* drate = reinterpret_cast<const int*>(c->batch_tab + count + 1);
-    u32* dindex = c->batch_tab + 2 * BATCH_MAX_BLOCKS + 1;
-    HIP_TRY(c, hipMemcpyAsync(c->batch_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
-    if (adler_host) {                           // (reads the caller's text before the post kernel may overwrite it; the pass's last sync covers the copy)
-        u32* dadler = c->batch_tab + 18 * BATCH_MAX_BLOCKS + 1;
-        launch_adler_batch(c, dT_user, c->batch_tab, (u32)count, dadler);
-        HIP_TRY(c, hipMemcpyAsync(adler_host, dadler, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    c->os_gave_up = false;
-    int rc = st_batch_once(c, dT_user, dOut_user, (u32)total, (u32)count, k, doff, drate, dindex, index_out, false);
-    if (rc == BSC_GPU_ERROR && c->os_gave_up) {
-        const int mode = c->os_mode;
-        c->os_mode = 0; c->os_gave_up = false; ++c->os_retries;
-        rc = st_batch_once(c, dT_user, dOut_user, (u32)total, (u32)count, k, doff, drate, dindex, index_out, true);
-        c->os_mode = mode;
-    }
-    return rc;
+    if (k < 3 || k > 8) return BSC_BAD_PARAMETER;
+    BatchTab tab;                               // (the Adler launch reads the caller's text before the post kernel may overwrite it; the pass's last sync covers the copy)
+    const int src = batch_pass_setup(c, dT_user, sizes, count, rates, index_out, adler_host, &tab);
+    if (src < 0 || tab.total == 0) return src;
+    return with_onesweep_retry(c, [&](bool reuse_text) {
+        return st_batch_once(c, dT_user, dOut_user, tab.total, (u32)count, k, tab.off, tab.rate, tab.res, index_out, reuse_text);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------

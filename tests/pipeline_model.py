@@ -62,7 +62,7 @@ def bit_length(x):
 
 
 def key_geometry(K, n, batch_count=0):
-    """The first sort's key layout as bwt_device_once derives it from the alphabet size K of the text (of the whole pass for a batch), the
+    """The first sort's key layout as bwt_key_plan (libbsc_amd/csrc/device/bwt_plan.h; test_bwt_plan_host.py holds the two together) derives it from the alphabet size K of the text (of the whole pass for a batch), the
     length n and the number of blocks of a batched pass (0: a single block):
       cb          bits per character: the smallest with 2^cb >= K, at least 4; a batch codes 1..K (0 = past the block's end): K + 1
       w           characters per key: 64 / cb; a batch keeps batch_bb bits for the block field on top, at most 16 characters

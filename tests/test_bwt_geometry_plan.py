@@ -1,5 +1,5 @@
-"""What the BWT key-geometry sweep covers (no GPU): pipeline_model.key_geometry restates how bwt_device_once lays out the first sort's keys
-from the alphabet size, the block length and the block count of a batched pass; the case list of bwt_geometry_cases.py must reach every
+"""What the BWT key-geometry sweep covers (no GPU): pipeline_model.key_geometry restates how bwt_key_plan (libbsc_amd/csrc/device/bwt_plan.h;
+test_bwt_plan_host.py compares the two field by field) lays out the first sort's keys from the alphabet size, the block length and the block count of a batched pass; the case list of bwt_geometry_cases.py must reach every
 layout the rules can produce — character widths, key lengths, digit passes, the text rounds' key lengths, values with and without the
 predecessor's code, every width of the block field — with the alphabet each case is meant to have."""
 import numpy as np

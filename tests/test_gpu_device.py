@@ -345,23 +345,22 @@ def test_bwt_long_groups_with_default_keys(torch_cuda):
     code = r"""
 import sys
 sys.path.insert(0, %r)
+sys.path.insert(0, %r)
 import numpy as np
-from libbsc_amd import GpuContext, api
+from libbsc_amd import GpuContext
 from oracle.refbind import Ref
+from bwt_inputs import planted_phrase
 ref = Ref()
 n = 6 << 20
 ctx = GpuContext(0, max_n=n + 4096)
 rng = np.random.default_rng(4)
 for plen in (13, 40):
-    T = api.synth_text_v1(31, n).copy()
-    phrase = np.frombuffer(b"qzjxvkwpyfgmbqzjxvkwpyfgmbqzjxvkwpyfgmbhh"[:plen], np.uint8)
-    for p in rng.choice((n - 64) // 64, 3000, replace=False) * 64:
-        T[p:p + plen] = phrase
+    T = planted_phrase(rng, n, plen)
     L, idx, _ = ctx.bwt(T)
     wL, widx, _ = ref.bwt_encode(T, aux=False)
     assert idx == widx and np.array_equal(L, wL), plen
     print("planted phrase of", plen, "ok", flush=True)
-""" % root
+""" % (root, os.path.join(root, "tests"))
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, BSCGPU_DEBUG="1"), cwd=root)
     log = r.stdout + r.stderr
     assert r.returncode == 0 and "planted phrase of 40 ok" in log, log[-3000:]
@@ -384,32 +383,17 @@ def test_bwt_hybrid_doubling_rounds(torch_cuda, env):
     code = r"""
 import sys
 sys.path.insert(0, %r)
+sys.path.insert(0, %r)
 import numpy as np
 from libbsc_amd import GpuContext, api
 from libbsc_amd.synth import image_corpus
 from oracle.refbind import Ref
+from bwt_inputs import source_like, object_like
 ref = Ref()
 n = 6 << 20
 ctx = GpuContext(0, max_n=n + 4096)
 rng = np.random.default_rng(11)
-def source_like(n):
-    T = api.synth_text_v1(5, n).copy()
-    T[rng.integers(0, n, n // 300)] = rng.integers(128, 256, n // 300).astype(np.uint8)      # > 128 symbols: 8-bit codes, 8-character keys
-    for p in rng.integers(0, n - 64, n // 40):                                                # indentation: runs of 4 .. 40 spaces
-        T[p:p + int(rng.integers(4, 41))] = 32
-    for _ in range(40):                                                                       # duplicated passages (LCPs up to 60 000)
-        L = int(rng.integers(2000, 60000)); a, b = (int(x) for x in rng.integers(0, n - L, 2))
-        T[b:b + L] = T[a:a + L]
-    return T
-def object_like(n):
-    T = rng.integers(0, 256, n).astype(np.uint8)
-    for p in rng.integers(0, n - 5000, n // 2000):                                            # zero runs of 16 .. 4096 bytes
-        T[p:p + int(rng.integers(16, 4097))] = 0
-    tab = rng.integers(0, 256, 4096).astype(np.uint8)
-    for p in rng.integers(0, n - 4096, 300):                                                  # the same table many times
-        T[p:p + 4096] = tab
-    return T
-cases = [("source-like", source_like(n)), ("object-like", object_like(n))]
+cases = [("source-like", source_like(rng, n)), ("object-like", object_like(rng, n))]
 for kind in ("python-source", "binary"):
     T = image_corpus(kind, n)
     if T is not None: cases.append((kind, T))
@@ -418,7 +402,7 @@ for name, T in cases:
     wL, widx, _ = ref.bwt_encode(T, aux=False)
     assert idx == widx and np.array_equal(L, wL), name
     print(name, "ok", flush=True)
-""" % root
+""" % (root, os.path.join(root, "tests"))
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, BSCGPU_DEBUG="1", **env), cwd=root)
     log = r.stdout + r.stderr
     assert r.returncode == 0 and "source-like ok" in log and "object-like ok" in log, log[-3000:]
