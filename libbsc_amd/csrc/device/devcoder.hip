@@ -39,6 +39,7 @@
 #include <thread>
 #include <system_error>
 #include "devcoder_model.h"
+#include "dc_segment_plan.h"
 #include "../host/qlfc.h"
 #include <cstdio>
 #include <cstdlib>
@@ -2165,6 +2166,15 @@ static int dc_fast_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym, 
     return BSC_NO_ERROR;
 }
 
+// What every unit of model work (a block, a pass, a pass's facts, a segment) starts from: the meta words cleared and, where the static
+// coder's model follows, the context kinds it has seen.
+static int dc_unit_clear(bscgpu_ctx* c, DevCoder* d, bool kinds_seen)
+{
+    HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
+    if (kinds_seen) HIP_TRY(c, hipMemsetAsync(d->present, 0, (size_t)DC_KIND_WORDS * 4, c->stream));
+    return BSC_NO_ERROR;
+}
+
 // Probability stream of a whole block.  Inputs: the QLFC front end's run arrays on the device (sym / rank / start, m runs of
 // the n-byte sorted block), the sub-blocks' run ranges and max_rank values; coder 1: dc_static_run, 3: dc_fast_run.  On success
 // *D_out decisions were written to the device p stream (d->ps) and poff[0..nb] (decision offsets of the sub-blocks) to hmeta[32..];
@@ -2185,8 +2195,8 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
     // (the fast coder: `if (bits < 7)` closes the exponent (qlfc.cpp:1204), whatever the alphabet)
     for (int b = 0; b < 8; ++b) S.maxr[b] = fast ? 7u : (b < nb) ? (u32)max_rank[b] : 0u;
 
-    HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
-    if (!fast) HIP_TRY(c, hipMemsetAsync(d->present, 0, (size_t)DC_KIND_WORDS * 4, c->stream));
+    rc = dc_unit_clear(c, d, !fast);
+    if (rc < 0) return rc;
     prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * (fast ? 14 : 40), m);
     // avg' = (124 avg + 4 rank) >> 7 <= max(avg, rank) and rank < nsym <= 2^(max_rank + 1): with at most 32 symbols in every
     // sub-block the average never reaches 32 and the escape coding (qlfc.cpp:960) cannot occur; the fast coder has none
@@ -2256,6 +2266,18 @@ static int dc_pass_begin(bscgpu_ctx* c, u32 m, int nsub, int over_fail, DcPass* 
     P->S.nsub = (u32)nsub; P->S.run = P->T.sub_run; P->S.off = P->T.sub_off; P->S.base = P->T.sub_base; P->S.maxr = d->sub_maxr;
     return BSC_NO_ERROR;
 }
+// ... and what every model of the pass reads: max_rank per sub-block and the rebased run table, then the avg_rank >= 32 flags.  The
+// static coder walks them always (which sub-blocks can escape is not known on the host here; one of at most 32 symbols never leaves a
+// flag open — avg_top), sub_und non-null: with the flags left open counted per sub-block; the fast coder has no escape coding.
+// Inside the caller's profile bracket.
+static int dc_pass_tables(bscgpu_ctx* c, const DcPass& P, u32 m, bool fast, u32* sub_und)
+{
+    DevCoder* d = P.d;
+    hipLaunchKernelGGL(dc_tab_prep_kernel, dim3((P.S.nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, P.T.first_run, P.S.nsub, m, fast ? 7 : -1, d->sub_maxr, P.T.sub_run);
+    if (!fast) return dc_launch_avg(c, d, P.drank, m, P.S, sub_und);
+    HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));
+    return BSC_NO_ERROR;
+}
 
 // Probability stream of a whole pass, coder 1 (dc_static_run) or 3 (dc_fast_run) -> every sub-block's entries back to back in stream
 // order in the device p stream (buffer 0), poff[0..nsub] in d->poff_tab.  The same stages, the same kernels as a single block's,
@@ -2268,22 +2290,16 @@ int devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* D_out
 {
     if (packed_out) *packed_out = 0;
     DcPass P;
-    const int rc = dc_pass_begin(c, m, nsub, (int)FAIL_CAP, &P);
+    int rc = dc_pass_begin(c, m, nsub, (int)FAIL_CAP, &P);
     if (rc < 0) return rc;
     DevCoder* d = P.d;
     const bool fast = coder == 3;                                      // LIBBSC_CODER_QLFC_FAST
-    HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
-    if (!fast) HIP_TRY(c, hipMemsetAsync(d->present, 0, (size_t)DC_KIND_WORDS * 4, c->stream));
+    rc = dc_unit_clear(c, d, !fast);
+    if (rc < 0) return rc;
     prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * (fast ? 14 : 40), m);
-    hipLaunchKernelGGL(dc_tab_prep_kernel, dim3(((u32)nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, P.T.first_run, (u32)nsub, m, fast ? 7 : -1, d->sub_maxr, P.T.sub_run);
-    // (the static coder, always: which sub-blocks can escape is not known on the host here; one of at most 32 symbols never leaves a
-    // flag open — avg_top.  No escape coding in the fast coder)
-    if (fast) HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));
-    else {
-        const int arc = dc_launch_avg(c, d, P.drank, m, P.S, (u32*)nullptr);
-        if (arc < 0) { prof_end(c); return arc; }
-    }
+    rc = dc_pass_tables(c, P, m, fast, nullptr);
     prof_end(c);
+    if (rc < 0) return rc;
     if (fast) return dc_fast_run(c, d, P.S, P.dsym, P.drank, P.dstart, d->ge32, m, 0u, false, 0, -1, nullptr, D_out);
     const int src = dc_static_run(c, d, P.S, P.dsym, P.drank, P.dstart, d->ge32, m, 0u, false, 0, -1, nullptr, nullptr, packed_out, D_out);
     if (src >= 0 && packed_out && *packed_out && pbytes_out) *pbytes_out = (int64_t)d->hmeta[48] / 8 * 13;
@@ -2296,7 +2312,7 @@ const u32* devcoder_batch_pbase_ptr(const bscgpu_ctx* c) { return c->dc ? c->dc-
 // Sub-blocks are independent chains by construction (the chain identity carries the sub-block), so the model of a pass can run over
 // any contiguous range of its sub-blocks and write the same entries.  Facts first, once per pass and before any sort: every
 // sub-block's undecided avg_rank flags (dc_avg_kernel) and its decisions for this coder (dc_sub_dec_kernel).  The plan
-// (bscgpu_model_segment_plan) excludes a block with an undecided flag or more decisions than the arena holds and cuts the rest into
+// (dc_segment_plan.h: dc_segment_plan) excludes a block with an undecided flag or more decisions than the arena holds and cuts the rest into
 // segments of at most min(Dcap, target) decisions; each segment then is a small pass of its own to dc_static_run / dc_fast_run (its
 // rebased run table: dc_seg_tab_kernel).  The device stream is double-buffered over ps[0 / 1]: segment k + 1 is modelled while
 // segment k's entries leave on the copy stream.  A segment that declines while it runs (FAIL_HIST, FAIL_REPLAY) is split at the block
@@ -2307,23 +2323,22 @@ const u32* devcoder_batch_pbase_ptr(const bscgpu_ctx* c) { return c->dc ? c->dc-
 // the one before it (a segment's bytes are a whole number of 104-byte sub-block extents), pbase[0..nsub] runs on across the segments in
 // kept order and a sub-block that was not modelled has pbase[s + 1] == pbase[s].  A segment's bytes are known with the plan
 // (sub_dec rounded up to 64 per sub-block), so "fits" is tested before it runs.  A segment whose packed form is void (DM_P13_OVER)
-// has been re-launched in the 2-byte form by dc_static_run: its entries come down to a scratch vector and bscgpu_pstream_pack13_host
+// has been re-launched in the 2-byte form by dc_static_run: its entries come down to a scratch vector and dc_pack13_host
 // packs them into place — the caller sees one form, the blocks keep the device's model; counted in cnt_packed_void.
+// Every decision of the above that is arithmetic — what runs next, whether it fits, where a declined range is cut and when it is
+// given up, where kept entries land, poff / pbase — is DcSegSchedule's (dc_segment_plan.h); the driver below launches, copies and tells.
 // the facts of a pass (after qlfc_front_batch): dec[s] / und[s] of every sub-block on the host; ge32 and sub_maxr stay for the segments
 static int dc_segment_facts(bscgpu_ctx* c, const DcPass& P, u32 m, bool fast, u32* dec, u32* und, u32* avg_open = nullptr, u32* avg_resolved = nullptr)
 {
     DevCoder* d = P.d;
     const int nsub = (int)P.S.nsub;
-    HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
+    const int crc = dc_unit_clear(c, d, /* kinds_seen: no model runs here */ false);
+    if (crc < 0) return crc;
     HIP_TRY(c, hipMemsetAsync(d->sub_und, 0, (size_t)nsub * 4, c->stream));
     HIP_TRY(c, hipMemsetAsync(d->sub_dec, 0, (size_t)nsub * 4, c->stream));
     prof_begin(c, BSCGPU_K_DC_FACTS, (u64)m * 6, m);
-    hipLaunchKernelGGL(dc_tab_prep_kernel, dim3(((u32)nsub + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, P.T.first_run, (u32)nsub, m, fast ? 7 : -1, d->sub_maxr, P.T.sub_run);
-    if (fast) HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));
-    else {
-        const int arc = dc_launch_avg(c, d, P.drank, m, P.S, d->sub_und);      // (with the exact resolve: what is left behind it)
-        if (arc < 0) { prof_end(c); return arc; }
-    }
+    const int arc = dc_pass_tables(c, P, m, fast, d->sub_und);             // (with the exact resolve: what is left behind it)
+    if (arc < 0) { prof_end(c); return arc; }
     hipLaunchKernelGGL(dc_sub_dec_kernel, dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, P.dsym, P.drank, P.dstart, d->ge32, m, P.S, d->sub_dec);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
@@ -2344,14 +2359,97 @@ int devcoder_segment_facts(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* dec, 
     return dc_segment_facts(c, P, m, coder == 3, dec, und);
 }
 
+// The copy-outs of kept segments in flight on the copy stream, oldest first: at most one per ps buffer, its end marked by seg_ev[k].
+struct DcCopyRing {
+    hipEvent_t* ev; hipStream_t copy_stream; const DcSegNote* note;
+    struct Pend { int b0, b1, k; };
+    std::deque<Pend> pend;
+    void settle(const DcSegRange& g) const { if (note) note->settled(note->user, g.b0, g.b1); }
+    // a copy out of ps[k] with the entries of range g has been queued on the copy stream
+    hipError_t started(int k, const DcSegRange& g)
+    {
+        const hipError_t e = hipEventRecord(ev[k], copy_stream);
+        if (e == hipSuccess) pend.push_back(Pend{g.b0, g.b1, k});
+        return e;
+    }
+    // tell what has landed: the copies up to the one out of buffer `upto` (0 / 1) or all of them (2) are waited for, the ones behind
+    // them are told if they are found landed; nothing is told out of order
+    hipError_t landed(int upto)
+    {
+        int must = 0;                                                  // how many of the oldest to wait for
+        for (size_t k = 0; k < pend.size(); ++k) if (upto == 2 || pend[k].k == upto) must = (int)k + 1;
+        while (!pend.empty()) {
+            const Pend q = pend.front();
+            if (must <= 0 && hipEventQuery(ev[q.k]) != hipSuccess) break;
+            const hipError_t e = hipEventSynchronize(ev[q.k]);
+            if (e != hipSuccess) return e;
+            pend.pop_front(); --must;
+            if (note) note->settled(note->user, q.b0, q.b1);
+        }
+        return hipSuccess;
+    }
+};
+
+// The ranges of the schedule one after the other, launch by launch; out: the landing buffer (host), 2-byte entries or the packed
+// form's bytes (pk).  *replays / *hist_ext: what the kept and the declined runs counted together.
+static int dc_segments_loop(bscgpu_ctx* c, const DcPass& P, bool fast, bool pk, const u32* sub_run, DcSegSchedule& sch, DcCopyRing& ring, u8* out,
+                            int* replays, int* hist_ext)
+{
+    DevCoder* d = P.d;
+    std::vector<u32> pseg((size_t)P.S.nsub + 1), pbseg(pk ? (size_t)P.S.nsub + 1 : 0);
+    std::vector<u16> void_entries;                                    // (packed: the 2-byte entries of a void segment on their way to the host's packer)
+    std::vector<int64_t> void_pbase;
+    int launched = 0;
+    DcSegRange g;
+    for (DcSegNext nx; (nx = sch.next(&g)) != DC_SEG_DONE; ) {
+        if (nx == DC_SEG_GIVEN_UP) { ring.settle(g); continue; }
+        const int s0 = g.s0, s1 = g.s1;
+        const u32 r0 = sub_run[s0], r1 = sub_run[s1];
+        const int psbuf = launched++ & 1;
+        int rc = dc_unit_clear(c, d, !fast);
+        if (rc < 0) return rc;
+        prof_begin(c, BSCGPU_K_DC_FACTS, (u64)(s1 - s0) * 8, (u64)(s1 - s0));
+        hipLaunchKernelGGL(dc_seg_tab_kernel, dim3(((u32)(s1 - s0) + 1 + WG - 1) / WG), dim3(WG), 0, c->stream, P.T.sub_run, (u32)s0, (u32)(s1 - s0), r0, r1, d->seg_run);
+        prof_end(c);
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, d->seg_ev[psbuf], 0));          // this buffer's copy-out of two segments ago
+        // (the segment's rebased table, the pass's run arrays and flags offset to its first run)
+        DcSubTab G; G.nsub = (u32)(s1 - s0); G.run = d->seg_run; G.off = P.T.sub_off + s0; G.base = P.T.sub_base + s0; G.maxr = d->sub_maxr + s0;
+        u32 D = 0;
+        int packed = 0;
+        rc = fast ? dc_fast_run(c, d, G, P.dsym + r0, P.drank + r0, P.dstart + r0, d->ge32 + r0, r1 - r0, 0u, false, psbuf, g.expect, pseg.data(), &D)
+                  : dc_static_run(c, d, G, P.dsym + r0, P.drank + r0, P.dstart + r0, d->ge32 + r0, r1 - r0, 0u, false, psbuf, g.expect, pseg.data(), nullptr,
+                                  pk ? &packed : nullptr, &D, pk ? pbseg.data() : nullptr);
+        *replays += c->dc_replays; *hist_ext += c->dc_hist_ext;
+        if (rc == BSC_NOT_SUPPORTED) { if (sch.declined(g, c->dc_last_fail)) ring.settle(g); continue; }
+        if (rc < 0) return rc;
+        // this buffer's earlier copy-out has landed (the stream kernel waited for it), maybe the other one's too
+        HIP_TRY(c, ring.landed(psbuf));
+        const int64_t at = sch.kept(g, D, pseg.data(), packed ? pbseg.data() : nullptr, packed != 0);
+        if (at < 0) return ctx_fail(c, BSC_GPU_ERROR, "device coder: a segment's packed layout differs from the plan's", hipSuccess);
+        if (!sch.copy_all() || D == 0) ring.settle(g);
+        else if (pk && !packed) {
+            // void: the 2-byte form lies in ps[psbuf] (dc_static_run re-launched it); down, and packed into place on the host
+            void_entries.resize((size_t)D); void_pbase.resize((size_t)(s1 - s0) + 1);
+            HIP_TRY(c, hipMemcpyAsync(void_entries.data(), d->ps[psbuf], (size_t)D * 2, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, ctx_sync(c));
+            if (dc_pack13_host(void_entries.data(), pseg.data(), s1 - s0, out + at, g.need, void_pbase.data()) != g.need)
+                return ctx_fail(c, BSC_GPU_ERROR, "device coder: packing a void segment", hipSuccess);
+            ring.settle(g);
+        } else {
+            HIP_TRY(c, hipMemcpyAsync(out + (pk ? at : 2 * at), d->ps[psbuf], pk ? (size_t)g.need : (size_t)D * 2, hipMemcpyDeviceToHost, c->copy_stream));
+            HIP_TRY(c, ring.started(psbuf, g));
+        }
+    }
+    HIP_TRY(c, ring.landed(2));
+    return BSC_NO_ERROR;
+}
+
 int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub, int count, const u32* sub_run, int coder, int64_t target,
-                              void* out_any, int64_t cap, bool per_segment_fit, u32* poff, int* blk_state, int64_t* D_out, const DcSegNote* note,
+                              void* out, int64_t cap, bool per_segment_fit, u32* poff, int* blk_state, int64_t* D_out, const DcSegNote* note,
                               int64_t* pbase)
 {
     const bool pk = pbase != nullptr;
     if (pk && coder != 1) return BSC_BAD_PARAMETER;
-    u16* out = static_cast<u16*>(out_any);
-    u8* out8 = static_cast<u8*>(out_any);
     DcPass P;
     int rc = dc_pass_begin(c, m, nsub, 0, &P);
     if (rc < 0) return rc;
@@ -2368,148 +2466,20 @@ int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub
     for (int s = 0; s < nsub; ++s) und_total += und[s];
     if (c->dc_avg_exact) und_total = avg_open;
 
-    // the plan
-    std::vector<int> seg_of((size_t)count);
-    const int nseg = bscgpu_model_segment_plan(dec.data(), und.data(), blk_sub, count, (int64_t)d->Dcap, target, seg_of.data());
-    if (nseg < 0) return ctx_fail(c, nseg, "device coder: segment plan", hipSuccess);
-    auto blk_dec = [&](int b) { int64_t t = 0; for (int s = blk_sub[b]; s < blk_sub[b + 1]; ++s) t += dec[s]; return t; };
-    // what sub-blocks [s0, s1) take of the landing buffer, in its units: entries, or bytes of the packed form
-    auto span_need = [&](int s0, int s1) { int64_t t = 0; for (int s = s0; s < s1; ++s) t += pk ? ((int64_t)dec[s] + 63) / 64 * 104 : (int64_t)dec[s]; return t; };
-    auto blk_und = [&](int b) { for (int s = blk_sub[b]; s < blk_sub[b + 1]; ++s) if (und[s]) return true; return false; };
-    struct Seg { int b0, b1; };
-    std::vector<Seg> todo;                                            // a stack: depth first, in block order
-    int64_t planned = 0;
-    for (int b = count - 1; b >= 0; --b) {
-        blk_state[b] = 0;
-        if (blk_sub[b + 1] == blk_sub[b]) continue;                   // an empty block: nothing to model
-        if (seg_of[b] < 0) { blk_state[b] = blk_und(b) ? (int)FAIL_AVG : (int)FAIL_CAP; continue; }
-        planned += span_need(blk_sub[b], blk_sub[b + 1]);
-        if (!todo.empty() && seg_of[todo.back().b0] == seg_of[b]) todo.back().b0 = b; else todo.push_back(Seg{b, b + 1});
-    }
-    // (the ranges were grown from the right: an empty block between two members of a segment lies inside its range, one at its left
-    // edge does not — either way it has no sub-block)
-    const bool copy_all = per_segment_fit || planned <= cap;
-    int nblk = 0; for (int b = 0; b < count; ++b) nblk += blk_sub[b + 1] > blk_sub[b];
-    int lg = 0; while ((1 << lg) < nblk) ++lg;
-    const int rerun_max = 2 * lg + 2;
-    int reruns = 0, kept = 0, launched = 0, replays = 0, hist_ext = 0;
-    std::vector<u32> pseg((size_t)nsub + 1), pbseg(pk ? (size_t)nsub + 1 : 0);
-    std::vector<u16> void_entries;                                    // (packed: the 2-byte entries of a void segment on their way to the host's packer)
-    int64_t base = 0, base_dec = 0;                                   // where the next segment lands (entries, or bytes), decisions kept
-    int kept_packed = 0, kept_void = 0;
-    // poff is written as the segments are kept (they come in block order): everything up to sub-block `filled` is final
-    int filled = 0;
-    poff[0] = 0;
-    if (pk) pbase[0] = 0;
-    auto fill_to = [&](int s) { for (; filled < s; ++filled) { poff[filled + 1] = poff[filled]; if (pk) pbase[filled + 1] = pbase[filled]; } };
-    // the segments whose copy-out is in flight, oldest first (at most one per ps buffer)
-    struct Pend { int b0, b1, ev; };
-    std::deque<Pend> pend;
-    auto settle = [&](int b0, int b1) { if (note) note->settled(note->user, b0, b1); };
-    // tell what has landed: the copies up to the one out of buffer `upto` (0 / 1) or all of them (2) are waited for, the ones behind
-    // them are told if they are found landed
-    auto landed = [&](int upto) -> hipError_t {
-        int must = 0;                                                  // how many of the oldest to wait for
-        for (size_t k = 0; k < pend.size(); ++k) if (upto == 2 || pend[k].ev == upto) must = (int)k + 1;
-        while (!pend.empty()) {
-            const Pend q = pend.front();
-            if (must <= 0 && hipEventQuery(d->seg_ev[q.ev]) != hipSuccess) break;
-            const hipError_t e = hipEventSynchronize(d->seg_ev[q.ev]);
-            if (e != hipSuccess) return e;
-            pend.pop_front(); --must;
-            settle(q.b0, q.b1);
-        }
-        return hipSuccess;
-    };
+    DcSegSchedule sch(dec.data(), und.data(), blk_sub, count, nsub, (int64_t)d->Dcap, target, cap, per_segment_fit, (int)FAIL_AVG, (int)FAIL_CAP, poff, pbase, blk_state);
     if (note) note->planned(note->user);
-    auto run = [&]() -> int {
-    while (!todo.empty()) {
-        const Seg g = todo.back(); todo.pop_back();
-        const int s0 = blk_sub[g.b0], s1 = blk_sub[g.b1];
-        const u32 r0 = sub_run[s0], r1 = sub_run[s1];
-        int64_t expect = 0;
-        for (int s = s0; s < s1; ++s) expect += dec[s];
-        auto give_up = [&](int why) { for (int b = g.b0; b < g.b1; ++b) if (blk_sub[b + 1] > blk_sub[b]) blk_state[b] = why; settle(g.b0, g.b1); };
-        const int64_t need = span_need(s0, s1);
-        if (per_segment_fit && base + need > cap) { give_up((int)FAIL_CAP); continue; }
-        const int psbuf = launched++ & 1;
-        HIP_TRY(c, hipMemsetAsync(d->meta, 0, DM_COUNT * 4, c->stream));
-        if (!fast) HIP_TRY(c, hipMemsetAsync(d->present, 0, (size_t)DC_KIND_WORDS * 4, c->stream));
-        prof_begin(c, BSCGPU_K_DC_FACTS, (u64)(s1 - s0) * 8, (u64)(s1 - s0));
-        hipLaunchKernelGGL(dc_seg_tab_kernel, dim3(((u32)(s1 - s0) + 1 + WG - 1) / WG), dim3(WG), 0, c->stream, P.T.sub_run, (u32)s0, (u32)(s1 - s0), r0, r1, d->seg_run);
-        prof_end(c);
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, d->seg_ev[psbuf], 0));          // this buffer's copy-out of two segments ago
-        // (the segment's rebased table, the pass's run arrays and flags offset to its first run)
-        DcSubTab G; G.nsub = (u32)(s1 - s0); G.run = d->seg_run; G.off = P.T.sub_off + s0; G.base = P.T.sub_base + s0; G.maxr = d->sub_maxr + s0;
-        u32 D = 0;
-        int packed = 0;
-        rc = fast ? dc_fast_run(c, d, G, P.dsym + r0, P.drank + r0, P.dstart + r0, d->ge32 + r0, r1 - r0, 0u, false, psbuf, expect, pseg.data(), &D)
-                  : dc_static_run(c, d, G, P.dsym + r0, P.drank + r0, P.dstart + r0, d->ge32 + r0, r1 - r0, 0u, false, psbuf, expect, pseg.data(), nullptr,
-                                  pk ? &packed : nullptr, &D, pk ? pbseg.data() : nullptr);
-        replays += c->dc_replays; hist_ext += c->dc_hist_ext;
-        if (rc == BSC_NOT_SUPPORTED) {
-            const int why = c->dc_last_fail;
-            int members = 0; for (int b = g.b0; b < g.b1; ++b) members += blk_sub[b + 1] > blk_sub[b];
-            if (members < 2 || reruns + 2 > rerun_max) { give_up(why); continue; }
-            // the block boundary nearest half the decisions, with a member on either side
-            int cut = -1; int64_t acc = 0, best = 0;
-            int seen = 0;
-            for (int b = g.b0; b < g.b1; ++b) {
-                if (blk_sub[b + 1] == blk_sub[b]) continue;
-                acc += blk_dec(b); ++seen;
-                if (seen == members) break;
-                const int64_t dist = acc * 2 > expect ? acc * 2 - expect : expect - acc * 2;
-                if (cut < 0 || dist < best) { cut = b + 1; best = dist; }
-            }
-            todo.push_back(Seg{cut, g.b1}); todo.push_back(Seg{g.b0, cut});
-            reruns += 2;
-            continue;
-        }
-        if (rc < 0) return rc;
-        fill_to(s0);
-        for (int s = s0; s < s1; ++s) poff[s + 1] = poff[s0] + (pseg[s - s0 + 1] - pseg[0]);
-        filled = s1;
-        // this buffer's earlier copy-out has landed (the stream kernel waited for it), maybe the other one's too
-        HIP_TRY(c, landed(psbuf));
-        if (pk) {
-            // the layout the plan counted on: the packed extents of this segment's sub-blocks, from its decisions per sub-block
-            if (!packed) { pbseg[0] = 0; for (int s = s0; s < s1; ++s) pbseg[s - s0 + 1] = pbseg[s - s0] + ((pseg[s - s0 + 1] - pseg[s - s0] + 63u) & ~63u); }
-            if ((int64_t)pbseg[s1 - s0] / 8 * 13 != need) return ctx_fail(c, BSC_GPU_ERROR, "device coder: a segment's packed layout differs from the plan's", hipSuccess);
-            for (int s = s0; s < s1; ++s) pbase[s + 1] = pbase[s0] + (int64_t)pbseg[s - s0 + 1];
-        }
-        if (pk && !packed && copy_all && D > 0) {
-            // void: the 2-byte form lies in ps[psbuf] (dc_static_run re-launched it); down, and packed into place on the host
-            void_entries.resize((size_t)D);
-            HIP_TRY(c, hipMemcpyAsync(void_entries.data(), d->ps[psbuf], (size_t)D * 2, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, ctx_sync(c));
-            std::vector<int64_t> pb((size_t)(s1 - s0) + 1);
-            if (bscgpu_pstream_pack13_host(void_entries.data(), pseg.data(), s1 - s0, out8 + base, need, pb.data()) != need)
-                return ctx_fail(c, BSC_GPU_ERROR, "device coder: packing a void segment", hipSuccess);
-            settle(g.b0, g.b1);
-        } else if (copy_all && D > 0) {
-            if (pk) HIP_TRY(c, hipMemcpyAsync(out8 + base, d->ps[psbuf], (size_t)need, hipMemcpyDeviceToHost, c->copy_stream));
-            else HIP_TRY(c, hipMemcpyAsync(out + base, d->ps[psbuf], (size_t)D * 2, hipMemcpyDeviceToHost, c->copy_stream));
-            HIP_TRY(c, hipEventRecord(d->seg_ev[psbuf], c->copy_stream));
-            pend.push_back(Pend{g.b0, g.b1, psbuf});
-        } else settle(g.b0, g.b1);
-        if (pk) ++(packed ? kept_packed : kept_void);
-        base += pk ? need : (int64_t)D; base_dec += D; ++kept;
-    }
-    HIP_TRY(c, landed(2));
-    return BSC_NO_ERROR;
-    };
-    rc = run();
+    DcCopyRing ring{d->seg_ev, c->copy_stream, note, {}};
+    int replays = 0, hist_ext = 0;
+    rc = dc_segments_loop(c, P, fast, pk, sub_run, sch, ring, static_cast<u8*>(out), &replays, &hist_ext);
     // (no copy into the caller's buffer may outlive the call, whichever way it ends)
     if (hipStreamSynchronize(c->copy_stream) != hipSuccess && rc >= 0) rc = ctx_fail(c, BSC_GPU_ERROR, "device coder: segment copy-out", hipSuccess);
     if (rc < 0) return rc;
-    fill_to(nsub);
-    int fail = 0, host_blocks = 0;
-    for (int b = 0; b < count; ++b) if (blk_state[b]) { fail |= blk_state[b]; ++host_blocks; }
-    c->dc_last_fail = fail; c->dc_replays = replays; c->dc_hist_ext = hist_ext; c->dc_avg_und = (int)und_total; c->dc_avg_resolved = (int)avg_resolved;
-    c->cnt_seg += kept; c->cnt_seg_reruns += reruns; c->cnt_seg_host_blocks += host_blocks;
-    c->cnt_packed_passes += kept_packed; c->cnt_packed_void += kept_void;
-    if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder segments] sub-blocks %d, planned %d, kept %d, re-runs %d, blocks left to the host %d, decisions %lld\n", nsub, nseg, kept, reruns, host_blocks, (long long)base_dec);
-    *D_out = base_dec;
+    const DcSegTotals T = sch.finish();
+    c->dc_last_fail = T.fail; c->dc_replays = replays; c->dc_hist_ext = hist_ext; c->dc_avg_und = (int)und_total; c->dc_avg_resolved = (int)avg_resolved;
+    c->cnt_seg += T.kept; c->cnt_seg_reruns += T.reruns; c->cnt_seg_host_blocks += T.host_blocks;
+    c->cnt_packed_passes += T.kept_packed; c->cnt_packed_void += T.kept_void;
+    if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder segments] sub-blocks %d, planned %d, kept %d, re-runs %d, blocks left to the host %d, decisions %lld\n", nsub, T.planned, T.kept, T.reruns, T.host_blocks, (long long)T.decisions);
+    *D_out = T.decisions;
     return BSC_NO_ERROR;
 }
 

@@ -25,6 +25,7 @@
 #include "../../../include/bscgpu.h"
 #include "../device/dev_common.h"
 #include "../device/dma_copy.h"
+#include "../device/dc_segment_plan.h"
 #include "qlfc.h"
 #include "lzp.h"
 #include "par.h"
@@ -1832,31 +1833,8 @@ extern "C" BSCGPU_API int bscgpu_front_batch_code_ps13(const bscgpu_front_layout
 extern "C" BSCGPU_API int64_t bscgpu_pstream_pack13_host(const uint16_t* ps, const uint32_t* poff, int nsub, uint8_t* out, int64_t cap_bytes, int64_t* pbase)
 {
     if (nsub < 0 || !poff || !pbase || cap_bytes < 0) return LIBBSC_BAD_PARAMETER;
-    pbase[0] = 0;
-    for (int s = 0; s < nsub; ++s) {
-        if (poff[s + 1] < poff[s]) return LIBBSC_BAD_PARAMETER;
-        pbase[s + 1] = pbase[s] + ((int64_t)(poff[s + 1] - poff[s]) + 63) / 64 * 64;
-    }
-    const int64_t bytes = pbase[nsub] / 8 * 13;
-    if (bytes > cap_bytes || bytes == 0) return bytes;
-    if (!out || !ps) return LIBBSC_BAD_PARAMETER;
-    for (int s = 0; s < nsub; ++s) {
-        const uint16_t* e = ps + poff[s];
-        const int64_t len = (int64_t)(poff[s + 1] - poff[s]);
-        uint8_t* g = out + pbase[s] / 8 * 13;
-        for (int64_t k = 0; k < pbase[s + 1] - pbase[s]; k += 8, g += 13) {
-            uint64_t lo = 0, hi = 0;                                   // fields 0..4 (the fifth's low 12 bits) | its top bit, fields 5..7
-            for (int x = 0; x < 8; ++x) {
-                const uint64_t f = k + x < len ? (uint64_t)(e[k + x] & 0x1fffu) : 0u;
-                if (x < 4) lo |= f << (13 * x);
-                else if (x == 4) { lo |= f << 52; hi |= f >> 12; }
-                else hi |= f << (13 * (x - 5) + 1);
-            }
-            for (int i = 0; i < 8; ++i) g[i] = (uint8_t)(lo >> (8 * i));
-            for (int i = 0; i < 5; ++i) g[8 + i] = (uint8_t)(hi >> (8 * i));
-        }
-    }
-    return bytes;
+    const int64_t bytes = dc_pack13_host(ps, poff, nsub, out, cap_bytes, pbase);
+    return bytes < 0 ? LIBBSC_BAD_PARAMETER : bytes;
 }
 
 // bscgpu_front_batch_code_ps with the range coder's work already done on the device: the framing alone.  A sub-block whose budget
@@ -1969,20 +1947,7 @@ extern "C" BSCGPU_API int bscgpu_model_segment_plan(const uint32_t* sub_dec, con
     if (count < 0 || dcap <= 0 || (count > 0 && (!sub_dec || !sub_und || !blk_sub || !seg_of))) return LIBBSC_BAD_PARAMETER;
     if (count > 0 && blk_sub[0] < 0) return LIBBSC_BAD_PARAMETER;
     for (int b = 0; b < count; ++b) if (blk_sub[b + 1] < blk_sub[b]) return LIBBSC_BAD_PARAMETER;
-    const int64_t limit = target > 0 && target < dcap ? target : dcap;
-    int nseg = 0;
-    bool open = false;              // a segment is being filled
-    int64_t filled = 0;
-    for (int b = 0; b < count; ++b) {
-        if (blk_sub[b + 1] == blk_sub[b]) { seg_of[b] = -1; continue; }      // empty: ends nothing
-        int64_t dec = 0; bool und = false;
-        for (int s = blk_sub[b]; s < blk_sub[b + 1]; ++s) { dec += sub_dec[s]; und = und || sub_und[s] != 0; }
-        if (und || dec > dcap) { seg_of[b] = -1; open = false; continue; }
-        if (!open || filled + dec > limit) { ++nseg; open = true; filled = 0; }
-        filled += dec;
-        seg_of[b] = nseg - 1;
-    }
-    return nseg;
+    return dc_segment_plan(sub_dec, sub_und, blk_sub, count, dcap, target, seg_of);
 }
 
 extern "C" BSCGPU_API int bscgpu_model_segment_facts_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out,
@@ -1995,21 +1960,29 @@ extern "C" BSCGPU_API int bscgpu_model_segment_facts_device(bscgpu_ctx* c, const
     return devcoder_segment_facts(c, (u32)out->m, out->nsub, coder, sub_dec, sub_und);
 }
 
+// the stage in either form: pbase non-null is the packed one (out / cap in bytes); the callers have checked their own arguments
+static int64_t pstream_batch_segments(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out, int coder, int64_t target,
+                                      void* ps, int64_t cap, uint32_t* poff, int64_t* pbase, int* blk_state)
+{
+    const int frc = bscgpu_qlfc_front_batch_device(c, dL, sizes, count, out);
+    if (frc < 0) return frc;
+    poff[0] = 0;
+    if (pbase) pbase[0] = 0;
+    for (int b = 0; b < count; ++b) blk_state[b] = 0;
+    if (out->nsub == 0) return 0;
+    int64_t D = 0;
+    const int rc = devcoder_pstream_segments(c, (u32)out->m, out->nsub, out->blk_sub, count, out->sub_run, coder, target, ps, cap, false, poff, blk_state, &D, nullptr, pbase);
+    if (rc == LIBBSC_NOT_SUPPORTED) c->err = "device coder: an arena of the segmented model did not fit";
+    if (rc < 0) return rc;
+    return D;
+}
+
 extern "C" BSCGPU_API int64_t bscgpu_pstream_batch_segments_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out,
                                                                    int coder, int64_t target, uint16_t* ps, int64_t cap, uint32_t* poff, int* blk_state)
 {
     if (!c || !poff || cap < 0 || (cap > 0 && !ps) || (count > 0 && !blk_state)) return LIBBSC_BAD_PARAMETER;
     if (coder != LIBBSC_CODER_QLFC_STATIC && coder != LIBBSC_CODER_QLFC_FAST) return LIBBSC_BAD_PARAMETER;
-    const int frc = bscgpu_qlfc_front_batch_device(c, dL, sizes, count, out);
-    if (frc < 0) return frc;
-    poff[0] = 0;
-    for (int b = 0; b < count; ++b) blk_state[b] = 0;
-    if (out->nsub == 0) return 0;
-    int64_t D = 0;
-    const int rc = devcoder_pstream_segments(c, (u32)out->m, out->nsub, out->blk_sub, count, out->sub_run, coder, target, ps, cap, false, poff, blk_state, &D);
-    if (rc == LIBBSC_NOT_SUPPORTED) c->err = "device coder: an arena of the segmented model did not fit";
-    if (rc < 0) return rc;
-    return D;
+    return pstream_batch_segments(c, dL, sizes, count, out, coder, target, ps, cap, poff, nullptr, blk_state);
 }
 
 extern "C" BSCGPU_API int64_t bscgpu_pstream_batch_segments_packed_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out,
@@ -2018,17 +1991,7 @@ extern "C" BSCGPU_API int64_t bscgpu_pstream_batch_segments_packed_device(bscgpu
 {
     if (!c || !poff || !pbase || cap_bytes < 0 || (cap_bytes > 0 && !packed) || (count > 0 && !blk_state)) return LIBBSC_BAD_PARAMETER;
     if (coder != LIBBSC_CODER_QLFC_STATIC) return LIBBSC_BAD_PARAMETER;
-    const int frc = bscgpu_qlfc_front_batch_device(c, dL, sizes, count, out);
-    if (frc < 0) return frc;
-    poff[0] = 0; pbase[0] = 0;
-    for (int b = 0; b < count; ++b) blk_state[b] = 0;
-    if (out->nsub == 0) return 0;
-    int64_t D = 0;
-    const int rc = devcoder_pstream_segments(c, (u32)out->m, out->nsub, out->blk_sub, count, out->sub_run, coder, target, packed, cap_bytes, false, poff, blk_state, &D,
-                                             nullptr, pbase);
-    if (rc == LIBBSC_NOT_SUPPORTED) c->err = "device coder: an arena of the segmented model did not fit";
-    if (rc < 0) return rc;
-    return D;
+    return pstream_batch_segments(c, dL, sizes, count, out, coder, target, packed, cap_bytes, poff, pbase, blk_state);
 }
 
 namespace {

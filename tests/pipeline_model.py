@@ -145,3 +145,141 @@ def st_model(T, k):
         out = (vs & 0xff).astype(np.uint8)
         index = int(np.flatnonzero(vs & 0x100)[0])
     return out, index
+
+
+# ---- a pass in model segments (devcoder.hip: devcoder_pstream_segments) --------------------------------------------------------------
+FAIL_AVG, FAIL_CAP = 2, 8                                       # include/bscgpu.h: BSCGPU_DC_FAIL_*
+
+
+def segment_plan(dec, und, blk_sub, dcap, target):
+    """bscgpu_model_segment_plan -> (segments, the segment of every block or -1)"""
+    limit = target if 0 < target < dcap else dcap
+    nseg, is_open, filled, seg_of = 0, False, 0, []
+    for b in range(len(blk_sub) - 1):
+        s0, s1 = blk_sub[b], blk_sub[b + 1]
+        if s0 == s1:
+            seg_of.append(-1)
+            continue
+        d = sum(dec[s0:s1])
+        if any(und[s0:s1]) or d > dcap:
+            seg_of.append(-1)
+            is_open = False
+            continue
+        if not is_open or filled + d > limit:
+            nseg, is_open, filled = nseg + 1, True, 0
+        filled += d
+        seg_of.append(nseg - 1)
+    return nseg, seg_of
+
+
+def segment_schedule(dec, und, blk_sub, dcap, target, cap, per_segment_fit, packed, model=lambda b0, b1: (0, False, False)):
+    """What the host side of a pass in model segments does, written down from the driver as it stood when the whole of it was one
+    function (the work stack, the room rule, the cut, the re-run budget, poff / pbase) — the reference tools/dc_segment_probe.cpp's
+    output is held against.  dec / und: decisions and undecided flags per sub-block; model(b0, b1) stands for the device:
+    -> (reason mask the range declines with or 0, its packed form is void, its packed layout is 64 fields longer than the plan's).
+    -> dict with the probe's keys."""
+    count, nsub = len(blk_sub) - 1, len(dec)
+    member = lambda b: blk_sub[b + 1] > blk_sub[b]
+    blk_dec = lambda b: sum(dec[blk_sub[b]:blk_sub[b + 1]])
+    span_need = lambda s0, s1: sum((d + 63) // 64 * 104 if packed else d for d in dec[s0:s1])
+    nseg, seg_of = segment_plan(dec, und, blk_sub, dcap, target)
+    state, todo, planned = [0] * count, [], 0
+    for b in range(count - 1, -1, -1):
+        if not member(b):
+            continue
+        if seg_of[b] < 0:
+            state[b] = FAIL_AVG if any(und[blk_sub[b]:blk_sub[b + 1]]) else FAIL_CAP
+            continue
+        planned += span_need(blk_sub[b], blk_sub[b + 1])
+        if todo and seg_of[todo[-1][0]] == seg_of[b]:
+            todo[-1][0] = b
+        else:
+            todo.append([b, b + 1])
+    copy_all = per_segment_fit or planned <= cap
+    nblk = sum(member(b) for b in range(count))
+    lg = 0
+    while (1 << lg) < nblk:
+        lg += 1
+    rerun_max = 2 * lg + 2
+    out = dict(need=planned, copy_all=copy_all, excluded=list(state), ranges=[], error=False)
+    reruns = kept = kept_packed = kept_void = base = base_dec = filled = 0
+    poff, pbase = [0] * (nsub + 1), [0] * (nsub + 1)
+
+    def fill_to(s):
+        nonlocal filled
+        while filled < s:
+            poff[filled + 1], pbase[filled + 1] = poff[filled], pbase[filled]
+            filled += 1
+
+    def give_up(b0, b1, why):
+        for b in range(b0, b1):
+            if member(b):
+                state[b] = why
+
+    while todo:
+        b0, b1 = todo.pop()
+        s0, s1 = blk_sub[b0], blk_sub[b1]
+        expect, need = sum(dec[s0:s1]), span_need(s0, s1)
+        row = [b0, b1, s0, s1, expect, need]
+        if per_segment_fit and base + need > cap:
+            give_up(b0, b1, FAIL_CAP)
+            out["ranges"].append(row + ["nofit", FAIL_CAP])
+            continue
+        why, void, skew = model(b0, b1)
+        if why:
+            members = sum(member(b) for b in range(b0, b1))
+            if members < 2 or reruns + 2 > rerun_max:
+                give_up(b0, b1, why)
+                out["ranges"].append(row + ["gave_up", why])
+                continue
+            cut, acc, best, seen = -1, 0, 0, 0
+            for b in range(b0, b1):
+                if not member(b):
+                    continue
+                acc += blk_dec(b)
+                seen += 1
+                if seen == members:
+                    break
+                dist = abs(acc * 2 - expect)
+                if cut < 0 or dist < best:
+                    cut, best = b + 1, dist
+            todo.append([cut, b1])
+            todo.append([b0, cut])
+            reruns += 2
+            out["ranges"].append(row + ["split", why])
+            continue
+        D = expect
+        fill_to(s0)
+        for s in range(s0, s1):
+            poff[s + 1] = poff[s] + dec[s]
+        filled = s1
+        is_packed = packed and not void
+        if packed:
+            for s in range(s0, s1):
+                pbase[s + 1] = pbase[s] + (dec[s] + 63) // 64 * 64
+            if is_packed and skew:
+                pbase[s1] += 64
+            if (pbase[s1] - pbase[s0]) // 8 * 13 != need:
+                out["ranges"].append(row + ["layout", -1])
+                out["error"] = True
+                return out
+            kept_packed, kept_void = kept_packed + is_packed, kept_void + (not is_packed)
+        out["ranges"].append(row + ["void" if packed and not is_packed else "kept", base])
+        base += need if packed else D
+        base_dec += D
+        kept += 1
+    fill_to(nsub)
+    out.update(blk_state=state, poff=poff, planned=nseg, kept=kept, reruns=reruns, host_blocks=sum(x != 0 for x in state), packed=kept_packed,
+               void=kept_void, fail=int(np.bitwise_or.reduce(np.array(state + [0]))), decisions=base_dec)
+    if packed:
+        out["pbase"] = pbase
+    return out
+
+
+def segment_counters(dec, blk_sub, dcap, target=0, decline=(), why=4, und=None):
+    """(segments kept, re-runs, blocks left to the host) of a 16-bit pass whose landing buffer holds everything, when exactly the ranges
+    that hold a block of `decline` decline (reason mask `why`)"""
+    dec, blk_sub = [int(x) for x in dec], [int(x) for x in blk_sub]
+    r = segment_schedule(dec, [0] * len(dec) if und is None else [int(x) for x in und], blk_sub, dcap, target, sum(dec), False, False,
+                         lambda b0, b1: (why if any(b0 <= b < b1 for b in decline) else 0, False, False))
+    return r["kept"], r["reruns"], r["host_blocks"]
