@@ -497,7 +497,8 @@ enum {
     BSCGPU_K_RADIX_AUX     = 13, /* keys-only passes that also emit the permutation (device coder's orders, inverse BWT): not the graded kernel */
     BSCGPU_K_RC            = 14, /* range coder: many probability streams in one launch (rangecoder.hip) */
     BSCGPU_K_DC_FACTS      = 15, /* device coder, a pass in model segments: per-sub-block facts (flags, decision counts) and segment tables */
-    BSCGPU_K_COUNT         = 16
+    BSCGPU_K_DC_REPLAY     = 16, /* device coder: open chunk starts resolved exactly (BSCGPU_OPT_DC_REPLAY_EXACT): candidate walks and chaining */
+    BSCGPU_K_COUNT         = 17
 };
 typedef struct bscgpu_kstat {
     double   ms;        /* accumulated HIP-event time */
@@ -531,7 +532,9 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          either way.  Same output.
  * BSCGPU_CNT_DC_*          (get only) the last block this context gave to the device model of the static / fast coder, whether it
  *                          stayed there or was declined (the block is then coded through the host model, same bytes):
- *     _REPLAYS             evaluation chunks whose start value had to be replayed serially (the predecessor's bracket had not met)
+ *     _REPLAYS             evaluation chunks whose start value had to be replayed serially (the predecessor's bracket had not met);
+ *                          0 where BSCGPU_OPT_DC_REPLAY_EXACT settled every such start
+ *     _REPLAY_RESOLVED     evaluation chunks whose start value the exact resolve settled (BSCGPU_OPT_DC_REPLAY_EXACT; 0 with the option off)
  *     _LAST_FAIL           why the block was declined: a mask of BSCGPU_DC_FAIL_*, 0 when it stayed on the device
  *     _AVG_UNDECIDED       runs whose avg_rank >= 32 flag the warmed-up bracket left open (any such run declines: _FAIL_AVG — unless BSCGPU_OPT_DC_AVG_EXACT settles it)
  *     _AVG_RESOLVED        of those, the runs whose flag the exact resolve then settled (BSCGPU_OPT_DC_AVG_EXACT; 0 with the option off)
@@ -544,6 +547,16 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          for them: _FAIL_AVG is raised only where a start bracket is 64 values wide or more, which the contraction
  *                          of avg_rank rules out.  Batched passes in model segments: no block is excluded for its avg flags.  -e0 has
  *                          no such flags and is not affected.  Same output.
+ * BSCGPU_OPT_DC_REPLAY_EXACT  0 (default; BSC_DC_REPLAY_EXACT=1 in the environment turns it on for contexts created after that) / 1:
+ *                          an evaluation chunk that starts inside a counter chain whose bracket has not met (periodic ranks or run
+ *                          lengths: tables, records, bitmaps) gets its start value exactly and in parallel — the chunk before it is
+ *                          walked from every value of its own start bracket (at most 373 for -e1, 128 for -e0; up to six per lane of
+ *                          one wavefront), the chunks' maps are followed from the last known start — instead of one lane replaying up to
+ *                          64 chunks serially; such a block, pass or segment is then not declined for it: _FAIL_REPLAY is raised only
+ *                          behind a start bracket of more than 384 values, which the contraction of the counter maps rules out
+ *                          (BSC_DC_REPLAY_CAND in the environment, read when a context is created: a lower cap, a test knob).  Both
+ *                          coders, single blocks, passes and model segments.  Buffers on first use (1.5 bytes per byte of max_n, counted
+ *                          by bscgpu_arena_bytes from then on); if they do not fit the option has no effect.  Same output.
  * BSCGPU_OPT_BATCH_FRONT    1: the passes of bscgpu_compress_batch / _batch_device run the QLFC front end of the whole pass on the GPU and
  *                          bring down its run arrays (sym, rank, start) instead of L; 0: L comes down and every block goes through
  *                          bsc_coder_compress on the host.  Same output.  Default 1 (measured: DESIGN §2b).
@@ -613,9 +626,11 @@ enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACK
        BSCGPU_OPT_BATCH_MODEL_SEGMENTS = 22, BSCGPU_CNT_BATCH_SEGMENTS = 23, BSCGPU_CNT_BATCH_SEG_RERUNS = 24,
        BSCGPU_CNT_BATCH_SEG_HOST_BLOCKS = 25, BSCGPU_CNT_DC_DCAP = 26,
        BSCGPU_OPT_BATCH_MODEL_PACKED = 27, BSCGPU_CNT_BATCH_PACKED_PASSES = 28, BSCGPU_CNT_BATCH_PACKED_VOID = 29,
-       BSCGPU_OPT_DC_AVG_EXACT = 30, BSCGPU_CNT_DC_AVG_RESOLVED = 31 };
+       BSCGPU_OPT_DC_AVG_EXACT = 30, BSCGPU_CNT_DC_AVG_RESOLVED = 31,
+       BSCGPU_OPT_DC_REPLAY_EXACT = 32, BSCGPU_CNT_DC_REPLAY_RESOLVED = 33 };
 /* _FAIL_AVG: undecided avg_rank flags; _FAIL_HIST: a run_hist bracket open after 9216 predecessors; _FAIL_CAP: more runs or decisions
- * than the context's arena holds; _FAIL_REPLAY: a chain whose bracket stayed open over more than 64 evaluation chunks. */
+ * than the context's arena holds; _FAIL_REPLAY: a chain whose bracket stayed open over more than 64 evaluation chunks (with
+ * BSCGPU_OPT_DC_REPLAY_EXACT: only behind the resolve's guard). */
 enum { BSCGPU_DC_FAIL_AVG = 2, BSCGPU_DC_FAIL_HIST = 4, BSCGPU_DC_FAIL_CAP = 8, BSCGPU_DC_FAIL_REPLAY = 16 };
 BSCGPU_API int bscgpu_option_set(bscgpu_ctx* ctx, int key, int value);
 BSCGPU_API int bscgpu_option_get(bscgpu_ctx* ctx, int key);

@@ -28,7 +28,8 @@
 // The host (qlfc.cpp: encode_from_pstream) then runs only the range coder.  Whenever something is outside what this path
 // handles exactly (an avg_rank bracket that does not decide — unless BSCGPU_OPT_DC_AVG_EXACT has the open flags computed exactly,
 // 1a' —, a run_hist bracket still open after 9216 predecessors, a chain whose
-// bracket stays open over more than 64 evaluation chunks, capacity), a flag is raised and the caller falls back to the host model;
+// bracket stays open over more than 64 evaluation chunks — unless BSCGPU_OPT_DC_REPLAY_EXACT has the open chunk starts computed
+// exactly, 3' —, capacity), a flag is raised and the caller falls back to the host model;
 // nothing approximate is ever emitted.
 //
 // The host side drives the stages from ONE body per coder, a template over the form as the kernels are: dc_static_run (-e1) and
@@ -64,13 +65,13 @@ __device__ __forceinline__ u32 dc_virtual_block() {
 }
 
 constexpr int DC_WCH_MAX  = 4096;      // wave-chunks of a partition job (one wavefront walks one chunk of runs)
-// (DC_EV, DC_AVG_CH, DC_AVG_WARM, DC_HIST_NP, DC_HIST_KMAX, DC_REPLAY_MAX: devcoder_model.h — the CPU probe of the exits shares them)
-constexpr u32 DC_SIGMASK  = 0x7ffu;    // event = X | sub-block << 8 | bit << 11
-constexpr int DC_ROWS     = 1088;      // rows of the chain-major layout = decision types (NUM_TAU = 1080), padded to whole wavefronts
+// (DC_EV, DC_AVG_CH, DC_AVG_WARM, DC_HIST_NP, DC_HIST_KMAX, DC_REPLAY_MAX: devcoder_model.h — the CPU probe of the exits shares them; so
+// are DC_SIGMASK (event = X | sub-block << 8 | bit << 11), DC_ROWMARK and DC_ROWS, which the host restatement of the evaluation reads)
 
 // meta scalars (device u32 array)
 enum { DM_FAIL = 0, DM_NTYPES, DM_NROUNDS, DM_AVG_UND, DM_REPLAYS, DM_D0, DM_D1, DM_D2, DM_D3, DM_HIST_EXT /* runs that entered the extended run_hist look-back */, DM_P13_OVER /* a wavefront's piece did not fit the staging buffer: the packed stream is void */,
-       DM_AVG_RESOLVED /* exact resolve: flags the bracket left open and the resolve settled */, DM_AVG_LEFT /* ... and did not (the guard) */, DM_COUNT = 16 };
+       DM_AVG_RESOLVED /* exact resolve: flags the bracket left open and the resolve settled */, DM_AVG_LEFT /* ... and did not (the guard) */,
+       DM_REPLAY_RESOLVED /* open chunk starts the exact resolve settled (3') */, DM_COUNT = 16 };
 // (bit 0 is not in use: every decision type has a row of its own, DC_ROWS >= NUM_TAU, so no number of types is too many)
 enum { FAIL_AVG = BSCGPU_DC_FAIL_AVG, FAIL_HIST = BSCGPU_DC_FAIL_HIST, FAIL_CAP = BSCGPU_DC_FAIL_CAP, FAIL_REPLAY = BSCGPU_DC_FAIL_REPLAY };
 
@@ -125,6 +126,10 @@ struct DevCoder {
     // runs, 130 per group of DC_AVG_GROUP chunks — under 0.1 byte per byte of max_n
     char* avg_arena = nullptr; size_t avg_bytes = 0; bool avg_alloc_failed = false;
     DcAvgRec avg = {};
+    // the exact resolve of open chunk starts (BSCGPU_OPT_DC_REPLAY_EXACT), allocated on its first use: per chunk slot (4 nch_cap of them)
+    // 2 DC_RP_CAND bytes of map, the head's end and a state byte — 771 bytes per slot, 1.5 bytes per byte of max_n (101 MB for 64 MiB)
+    char* rp_arena = nullptr; size_t rp_bytes = 0; bool rp_alloc_failed = false;
+    struct DcRpRec* rp = nullptr;
 };
 
 __device__ __forceinline__ u32 dc_sb_of(u32 j, const DcSub& S)
@@ -1044,8 +1049,7 @@ constexpr int DC_EROW = DC_EB * 2 + 16;         // LDS row pitch in bytes (padde
 struct DcEvalAll { DcEvalJob job[4]; u32 wstart[5]; u32 cstart[5]; u16* V[4]; u16* sink; u32 ev; };   // first wavefront / first chunk of each job; events per chunk
 
 // First event of every non-empty row gets DC_ROWMARK: inside the rows of one class (same update rates) a walk then needs no row
-// bookkeeping at all — a chain ends where the signature changes or a marked event begins.
-constexpr u32 DC_ROWMARK = 0x1000u;
+// bookkeeping at all — a chain ends where the signature changes or a marked event begins.  (DC_ROWMARK: devcoder_model.h)
 __global__ __launch_bounds__(WG) void dc_mark_rows_kernel(DcEvalAll A)
 {
     const u32 g = blockIdx.x * WG + threadIdx.x;
@@ -1257,6 +1261,137 @@ __device__ __forceinline__ bool dc_chunk_continues(const DcEvalJob& J, u32 c, u3
     // (a marked event starts a chain: a row — tested above — or, in a batched pass, another sub-block with the same signature)
     const u32 e1 = J.events[k0];
     return ((((u32)J.events[k0 - 1] ^ e1) & DC_SIGMASK) | (e1 & DC_ROWMARK)) == 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// 3'. open chunk starts resolved exactly (BSCGPU_OPT_DC_REPLAY_EXACT; devcoder_model.h: replay_resolve_host restates these kernels).
+// Chunk c is OPEN iff it continues a chain and the bracket of chunk c - 1 has not met; today one lane of dc_eval_b_kernel then walks back
+// to the nearest known start and replays everything in between, and gives the unit up (FAIL_REPLAY) behind DC_REPLAY_MAX chunks.  The
+// maps are monotone, so the exact start of an open chunk lies inside the bracket in front of it, and a chunk can be walked from every
+// value of that bracket at once: dc_rp_map_kernel, one wavefront per chunk whose successor is open — the head of a stretch (its own
+// start is known) from that one value, every other chunk from all w = ehi - elo + 1 values of its start bracket, ceil(w / 64) per lane —,
+// then dc_rp_chain_kernel, one lane per stretch, follows the maps from the head and CLOSES the brackets (elo = ehi = exact start of the
+// next chunk), so that dc_eval_b_kernel, unchanged, finds nothing to replay.  A chunk whose end bracket is open holds no chain boundary
+// (a boundary resets both ends to the same value) and is a full chunk (it has a successor): one row, one set of rates, a bare loop.
+// The guard: a start bracket of more than `cand` values (DC_RP_CAND, which the contraction of the maps rules out — tools/
+// replay_resolve_probe.cpp bound —, or what BSC_DC_REPLAY_CAND lowers it to) is not walked; the chain stops there and what lies behind
+// it in the stretch is left to dc_eval_b_kernel's replay.
+// ---------------------------------------------------------------------------------------------------------------------
+struct DcRpRec {
+    u16* map;       // per chunk slot, DC_RP_CAND entries: map[v] = (value at the chunk's end, had it started at elo[p - 1] + v) - elo[p]
+    u16* head;      // per chunk slot: the exact end of a stretch's head
+    u8*  st;        // per chunk slot: DC_RP_*
+    u32  cand;      // widest start bracket that is walked (values)
+};
+static_assert(DC_RP_CAND % 64 == 0 && DC_RP_CAND / 64 == 6, "dc_rp_map_kernel: candidates per lane");
+
+// N chains over the same nq x 8 events, interleaved (their dependent steps fill each other's issue gaps); the events 16 bytes per load
+// with four loads in flight, as the replay loop of dc_eval_b_kernel; the step in the form of dc_eval_wave_kernel (c = t a + r per bit)
+template <int N>
+__device__ __forceinline__ void dc_rp_walk(const uint4* __restrict__ ev, u32 nq, const Rates& R, int (&v)[N])
+{
+    const int c0 = R.t0 * R.a0 + R.r0, c1 = R.t1 * R.a1 + R.r1;
+    uint4 qb[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) qb[i] = ev[(u32)i < nq ? (u32)i : 0u];
+    for (u32 i = 0; i < nq; ++i) {
+        const uint4 q = qb[0];
+        qb[0] = qb[1]; qb[1] = qb[2]; qb[2] = qb[3];
+        qb[3] = ev[i + 4u < nq ? i + 4u : i];
+        const u32 wds[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int x = 0; x < 8; ++x) {
+            const bool b1 = ((wds[x >> 1] >> (16 * (x & 1) + 11)) & 1u) != 0u;
+            const int Cc = b1 ? c1 : c0, Aa = b1 ? R.a1 : R.a0;
+#pragma unroll
+            for (int k = 0; k < N; ++k) v[k] += (Cc - __mul24(v[k], Aa)) >> 12;
+        }
+    }
+}
+
+// the candidates lane + 64 k of a start bracket of w values from lo0 (a lane past the bracket walks its last value again and stores nothing)
+template <int N>
+__device__ __forceinline__ void dc_rp_candidates(const uint4* __restrict__ ev, u32 nq, const Rates& R, u32 lane, u32 lo0, u32 w, u32 base, u16* __restrict__ map)
+{
+    int v[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) { const u32 cv = lane + 64u * (u32)k; v[k] = (int)(lo0 + (cv < w ? cv : w - 1u)); }
+    dc_rp_walk<N>(ev, nq, R, v);
+#pragma unroll
+    for (int k = 0; k < N; ++k) { const u32 cv = lane + 64u * (u32)k; if (cv < w) map[cv] = (u16)((u32)v[k] - base); }
+}
+
+// one wavefront per chunk slot (all jobs in one launch); nearly all leave behind two loads: their bracket has met
+__global__ __launch_bounds__(WG) void dc_rp_map_kernel(DcEvalAll A, const ModelParams* __restrict__ mp, const u32* __restrict__ meta,
+                                                       const u16* __restrict__ elo_all, const u16* __restrict__ ehi_all, DcRpRec Q)
+{
+    if (meta[DM_FAIL] != 0u) return;
+    const u32 lane = threadIdx.x & 63u;
+    const u32 g = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * WAVES + (threadIdx.x >> 6)));
+    if (g >= A.cstart[4]) return;
+    int jb = 0;
+#pragma unroll
+    for (int q = 1; q < 4; ++q) if (g >= A.cstart[q]) jb = q;
+    const DcEvalJob J = A.job[jb];
+    const u16* elo = elo_all + A.cstart[jb]; const u16* ehi = ehi_all + A.cstart[jb];
+    const u32 p = g - A.cstart[jb], EV = A.ev;
+    u32 state = DC_RP_NONE;
+    // (elo / ehi of a slot past the job's last chunk are not written: the test on E comes first)
+    if ((u64)(p + 1u) * EV < J.E && elo[p] != ehi[p] && dc_chunk_continues(J, p + 1u, EV)) {
+        const int cls = tau_class((int)dc_find_row(J.rowstart, p * EV));
+        const Rates R = mp->rates[cls][J.fam];
+        const uint4* ev = reinterpret_cast<const uint4*>(J.events + (size_t)p * EV);
+        const u32 nq = EV / 8u;
+        const bool cont = dc_chunk_continues(J, p, EV);
+        // (!cont cannot be: a chunk that starts a chain resets both ends at its first event, so its end bracket would have met.  The arm
+        // stays so that no index rests on that argument: p - 1 is read only where the chunk continues, i.e. p > 0.)
+        if (!cont || elo[p - 1u] == ehi[p - 1u]) {
+            int v[1] = {cont ? (int)elo[p - 1u] : (int)mp->init[cls]};
+            dc_rp_walk<1>(ev, nq, R, v);
+            if (lane == 0) Q.head[g] = (u16)v[0];
+            state = DC_RP_HEAD;
+        } else {
+            const u32 lo0 = elo[p - 1u], w = (u32)ehi[p - 1u] - lo0 + 1u, base = elo[p];
+            u16* map = Q.map + (size_t)g * DC_RP_CAND;
+            if (w > Q.cand) state = DC_RP_WIDE;
+            else {
+                if (w <= 64u) dc_rp_candidates<1>(ev, nq, R, lane, lo0, w, base, map);
+                else if (w <= 128u) dc_rp_candidates<2>(ev, nq, R, lane, lo0, w, base, map);
+                else if (w <= 256u) dc_rp_candidates<4>(ev, nq, R, lane, lo0, w, base, map);
+                else dc_rp_candidates<6>(ev, nq, R, lane, lo0, w, base, map);
+                state = DC_RP_MAP;
+            }
+        }
+    }
+    if (lane == 0) Q.st[g] = (u8)state;
+}
+
+// One lane per stretch: from the head's exact end through the maps, closing every bracket on the way.  Stretches are disjoint, so
+// the lane is the only writer of its entries; a bracket's lower end is read (the base of the next chunk's candidates) before it is
+// overwritten.  One dependent load per chunk (the map entry; the next chunk's state and lower end are requested with it).
+__global__ __launch_bounds__(WG) void dc_rp_chain_kernel(DcEvalAll A, u32* __restrict__ meta, u16* elo_all, u16* ehi_all, DcRpRec Q)
+{
+    if (meta[DM_FAIL] != 0u) return;
+    const u32 g = blockIdx.x * WG + threadIdx.x;
+    if (g >= A.cstart[4] || Q.st[g] != DC_RP_HEAD) return;
+    u32 gend = A.cstart[4];
+#pragma unroll
+    for (int q = 3; q >= 1; --q) if (g < A.cstart[q]) gend = A.cstart[q];
+    u32 x = Q.head[g], base = elo_all[g];
+    elo_all[g] = (u16)x; ehi_all[g] = (u16)x;
+    u32 n = 1, p = g + 1u;
+    u32 st_n = p < gend ? (u32)Q.st[p] : (u32)DC_RP_NONE, lo_n = p < gend ? (u32)elo_all[p] : 0u;
+    while (st_n == (u32)DC_RP_MAP) {
+        const u32 lo = lo_n, idx = x - base;
+        if (idx >= (u32)DC_RP_CAND) break;                              // (monotone maps: never; what follows then takes the serial replay)
+        const u32 mv = Q.map[(size_t)p * DC_RP_CAND + idx];
+        const u32 pn = p + 1u;
+        st_n = pn < gend ? (u32)Q.st[pn] : (u32)DC_RP_NONE; lo_n = pn < gend ? (u32)elo_all[pn] : 0u;
+        x = lo + mv; base = lo;
+        elo_all[p] = (u16)x; ehi_all[p] = (u16)x;
+        ++n; p = pn;
+    }
+    atomicAdd(&meta[DM_REPLAY_RESOLVED], n);
 }
 
 // exact value at the start of every chunk that begins inside a chain (all jobs in one launch; thread per chunk)
@@ -1737,6 +1872,8 @@ void devcoder_destroy(bscgpu_ctx* c)
     if (d->arena) hipFree(d->arena);
     if (d->batch_arena) hipFree(d->batch_arena);
     if (d->avg_arena) hipFree(d->avg_arena);
+    if (d->rp_arena) hipFree(d->rp_arena);
+    delete d->rp;
     for (int k = 0; k < 2; ++k) if (d->seg_ev[k]) hipEventDestroy(d->seg_ev[k]);
     if (d->hmeta) hipHostFree(d->hmeta);
     delete d;
@@ -1836,7 +1973,7 @@ int devcoder_ensure(bscgpu_ctx* c)
 }
 
 int64_t devcoder_arena_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)c->dc->arena_bytes : 0; }
-int64_t devcoder_batch_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)(c->dc->batch_bytes + c->dc->avg_bytes) : 0; }
+int64_t devcoder_batch_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)(c->dc->batch_bytes + c->dc->avg_bytes + c->dc->rp_bytes) : 0; }
 
 // One partition job: counts, scans, scatter.  SCATTER = false: counts and scans only, then the runs' offsets in the stream
 // (dc_doff_kernel) — all the fast coder needs of job 0, whose events nobody reads.
@@ -1866,6 +2003,7 @@ static void dc_note_block(bscgpu_ctx* c, const DevCoder* d)
     c->dc_avg_und = (int)d->hmeta[DM_AVG_UND];
     c->dc_hist_ext = (int)d->hmeta[DM_HIST_EXT];
     c->dc_avg_resolved = (int)d->hmeta[DM_AVG_RESOLVED];
+    c->dc_replay_resolved = (int)d->hmeta[DM_REPLAY_RESOLVED];
 }
 
 // ---- the avg_rank flags of m runs (1a), and with BSCGPU_OPT_DC_AVG_EXACT the exact resolve behind them (1a') ---------------------------
@@ -1951,6 +2089,27 @@ static void dc_launch_poff(bscgpu_ctx* c, DevCoder* d, const DcSubTab& S, u32)
 static DcDown dc_poff_down(DevCoder* d, const DcSub&, bool last, u32*) { return last ? DcDown{} : DcDown{d->hmeta + 32, d->poff, 16 * 4}; }
 static DcDown dc_poff_down(DevCoder* d, const DcSubTab& S, bool last, u32* poff_host) { return last ? DcDown{poff_host, d->poff_tab, ((size_t)S.nsub + 1) * 4} : DcDown{}; }
 
+// The buffers of the exact resolve of open chunk starts (3'), on the first evaluation that asks for it.  Do not fit: the option stays
+// without effect (the evaluation is what it is with the option off) — not an error, and not retried.
+static bool devcoder_rp_ensure(bscgpu_ctx* c, DevCoder* d)
+{
+    if (d->rp_arena) return true;
+    if (d->rp_alloc_failed) return false;
+    const size_t slots = 4 * d->nch_cap;
+    const size_t b_map = dc_align(2 * (size_t)DC_RP_CAND * slots), b_head = dc_align(2 * slots), b_st = dc_align(slots);
+    // (BSC_DC_REPLAY_FAIL_ALLOC in the environment: buffers that do not fit, for the test of this exit — what BSC_DEVCODER_FAIL_ALLOC is to the arena)
+    if (getenv("BSC_DC_REPLAY_FAIL_ALLOC") || hipMalloc((void**)&d->rp_arena, b_map + b_head + b_st) != hipSuccess) {
+        (void)hipGetLastError(); d->rp_arena = nullptr; d->rp_alloc_failed = true;
+        return false;
+    }
+    d->rp_bytes = b_map + b_head + b_st;
+    d->rp = new DcRpRec();
+    d->rp->map = reinterpret_cast<u16*>(d->rp_arena); d->rp->head = reinterpret_cast<u16*>(d->rp_arena + b_map); d->rp->st = reinterpret_cast<u8*>(d->rp_arena + b_map + b_head);
+    // (a lane of dc_rp_map_kernel holds at most DC_RP_CAND / 64 candidates and a slot's map DC_RP_CAND entries: the cap can only be lowered)
+    d->rp->cand = (c->dc_replay_cand == 0 || c->dc_replay_cand > (u32)DC_RP_CAND) ? (u32)DC_RP_CAND : c->dc_replay_cand;
+    return true;
+}
+
 // All chains of a block (or of a batched pass: tab) in one set of launches: E[job] events of family fam[job] per job, values to
 // d->V[job], counters by mp.  The fast coder's one family is job 1 alone: E = {0, E, 0, 0}, mp_fast.
 static int dc_eval(bscgpu_ctx* c, DevCoder* d, const u32 E[4], const int fam[4], const ModelParams* mp, bool tab)
@@ -1970,6 +2129,7 @@ static int dc_eval(bscgpu_ctx* c, DevCoder* d, const u32 E[4], const int fam[4],
         A.cstart[job + 1] = A.cstart[job] + (nch + 63) / 64 * 64;           // chunk slots padded to whole wavefronts
     }
     if (A.cstart[4] > 4 * d->nch_cap) return ctx_fail(c, BSC_GPU_ERROR, "device coder: chunk table too small", hipSuccess);
+    const bool resolve = c->dc_replay_exact && A.wstart[4] > 0 && devcoder_rp_ensure(c, d);
     prof_begin(c, BSCGPU_K_DC_EVAL, (u64)(E[0] + E[1] + E[2] + E[3]) * 6, (u64)E[0] + E[1] + E[2] + E[3]);
     if (A.wstart[4] > 0) {
         hipLaunchKernelGGL(dc_mark_rows_kernel, dim3((4 * DC_ROWS + WG - 1) / WG), dim3(WG), 0, c->stream, A);
@@ -1979,6 +2139,14 @@ static int dc_eval(bscgpu_ctx* c, DevCoder* d, const u32 E[4], const int fam[4],
             hipLaunchKernelGGL(dc_mark_chains_kernel, dim3((emax + 8 * WG - 1) / (8 * WG), 4), dim3(WG), 0, c->stream, K, d->meta);
         }
         hipLaunchKernelGGL(dc_eval_wave_kernel<false>, dim3((A.wstart[4] + DC_EVAL_WAVES - 1) / DC_EVAL_WAVES), dim3(64 * DC_EVAL_WAVES), DC_EVAL_LDS, c->stream, A, mp, d->meta, d->elo, d->ehi, (const u16*)nullptr, d->cnt);
+        if (resolve) {                                                    // 3': a class of its own in the profile
+            prof_end(c);
+            prof_begin(c, BSCGPU_K_DC_REPLAY, (u64)A.cstart[4] * 5, A.cstart[4]);
+            hipLaunchKernelGGL(dc_rp_map_kernel, dim3((A.cstart[4] + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, A, mp, d->meta, d->elo, d->ehi, *d->rp);
+            hipLaunchKernelGGL(dc_rp_chain_kernel, dim3((A.cstart[4] + WG - 1) / WG), dim3(WG), 0, c->stream, A, d->meta, d->elo, d->ehi, *d->rp);
+            prof_end(c);
+            prof_begin(c, BSCGPU_K_DC_EVAL, 0, 0);
+        }
         hipLaunchKernelGGL(dc_eval_b_kernel, dim3((A.cstart[4] + WG - 1) / WG), dim3(WG), 0, c->stream, A, mp, d->meta, d->elo, d->ehi, d->S);
         hipLaunchKernelGGL(dc_eval_wave_kernel<true>, dim3((A.wstart[4] + DC_EVAL_WAVES - 1) / DC_EVAL_WAVES), dim3(64 * DC_EVAL_WAVES), DC_EVAL_LDS, c->stream, A, mp, d->meta, (u16*)nullptr, (u16*)nullptr, d->S, d->cnt + 3 * 4096);
     }
@@ -2186,7 +2354,7 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
     int rc = devcoder_ensure(c);
     if (rc < 0) return rc;
     DevCoder* d = c->dc;
-    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = c->dc_avg_resolved = 0;
+    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = c->dc_avg_resolved = c->dc_replay_resolved = 0;
     c->dc_last_fail = m > d->Mcap ? (int)FAIL_CAP : 0;                 // (more runs than the arena holds: capacity, as too many decisions are)
     if (m == 0 || m > d->Mcap || nb < 1 || nb > 8) return BSC_NOT_SUPPORTED;
     const bool fast = coder == 3;
@@ -2255,7 +2423,7 @@ static int dc_pass_begin(bscgpu_ctx* c, u32 m, int nsub, int over_fail, DcPass* 
     if (rc < 0) return rc;
     DevCoder* d = c->dc;
     if (over_fail >= 0) {
-        c->dc_replays = c->dc_avg_und = c->dc_hist_ext = c->dc_avg_resolved = 0;
+        c->dc_replays = c->dc_avg_und = c->dc_hist_ext = c->dc_avg_resolved = c->dc_replay_resolved = 0;
         c->dc_last_fail = m > d->Mcap ? over_fail : 0;
     }
     if (m == 0 || m > d->Mcap || nsub < 1 || nsub > FRONT_MAX_SUB || !c->front_tab) return BSC_NOT_SUPPORTED;
@@ -2393,7 +2561,7 @@ struct DcCopyRing {
 // The ranges of the schedule one after the other, launch by launch; out: the landing buffer (host), 2-byte entries or the packed
 // form's bytes (pk).  *replays / *hist_ext: what the kept and the declined runs counted together.
 static int dc_segments_loop(bscgpu_ctx* c, const DcPass& P, bool fast, bool pk, const u32* sub_run, DcSegSchedule& sch, DcCopyRing& ring, u8* out,
-                            int* replays, int* hist_ext)
+                            int* replays, int* hist_ext, int* replay_resolved)
 {
     DevCoder* d = P.d;
     std::vector<u32> pseg((size_t)P.S.nsub + 1), pbseg(pk ? (size_t)P.S.nsub + 1 : 0);
@@ -2419,7 +2587,7 @@ static int dc_segments_loop(bscgpu_ctx* c, const DcPass& P, bool fast, bool pk, 
         rc = fast ? dc_fast_run(c, d, G, P.dsym + r0, P.drank + r0, P.dstart + r0, d->ge32 + r0, r1 - r0, 0u, false, psbuf, g.expect, pseg.data(), &D)
                   : dc_static_run(c, d, G, P.dsym + r0, P.drank + r0, P.dstart + r0, d->ge32 + r0, r1 - r0, 0u, false, psbuf, g.expect, pseg.data(), nullptr,
                                   pk ? &packed : nullptr, &D, pk ? pbseg.data() : nullptr);
-        *replays += c->dc_replays; *hist_ext += c->dc_hist_ext;
+        *replays += c->dc_replays; *hist_ext += c->dc_hist_ext; *replay_resolved += c->dc_replay_resolved;
         if (rc == BSC_NOT_SUPPORTED) { if (sch.declined(g, c->dc_last_fail)) ring.settle(g); continue; }
         if (rc < 0) return rc;
         // this buffer's earlier copy-out has landed (the stream kernel waited for it), maybe the other one's too
@@ -2469,13 +2637,13 @@ int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub
     DcSegSchedule sch(dec.data(), und.data(), blk_sub, count, nsub, (int64_t)d->Dcap, target, cap, per_segment_fit, (int)FAIL_AVG, (int)FAIL_CAP, poff, pbase, blk_state);
     if (note) note->planned(note->user);
     DcCopyRing ring{d->seg_ev, c->copy_stream, note, {}};
-    int replays = 0, hist_ext = 0;
-    rc = dc_segments_loop(c, P, fast, pk, sub_run, sch, ring, static_cast<u8*>(out), &replays, &hist_ext);
+    int replays = 0, hist_ext = 0, replay_resolved = 0;
+    rc = dc_segments_loop(c, P, fast, pk, sub_run, sch, ring, static_cast<u8*>(out), &replays, &hist_ext, &replay_resolved);
     // (no copy into the caller's buffer may outlive the call, whichever way it ends)
     if (hipStreamSynchronize(c->copy_stream) != hipSuccess && rc >= 0) rc = ctx_fail(c, BSC_GPU_ERROR, "device coder: segment copy-out", hipSuccess);
     if (rc < 0) return rc;
     const DcSegTotals T = sch.finish();
-    c->dc_last_fail = T.fail; c->dc_replays = replays; c->dc_hist_ext = hist_ext; c->dc_avg_und = (int)und_total; c->dc_avg_resolved = (int)avg_resolved;
+    c->dc_last_fail = T.fail; c->dc_replays = replays; c->dc_hist_ext = hist_ext; c->dc_avg_und = (int)und_total; c->dc_avg_resolved = (int)avg_resolved; c->dc_replay_resolved = replay_resolved;
     c->cnt_seg += T.kept; c->cnt_seg_reruns += T.reruns; c->cnt_seg_host_blocks += T.host_blocks;
     c->cnt_packed_passes += T.kept_packed; c->cnt_packed_void += T.kept_void;
     if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder segments] sub-blocks %d, planned %d, kept %d, re-runs %d, blocks left to the host %d, decisions %lld\n", nsub, T.planned, T.kept, T.reruns, T.host_blocks, (long long)T.decisions);

@@ -351,6 +351,12 @@ constexpr int DC_EV          = DC_EV_N;  // events per evaluation chunk: the min
 constexpr int DC_EVAL_WAVES_TARGET = 1000;   // ... or as many as keep a block's evaluation at this many wavefronts of 64 chunks
 constexpr int DC_EB          = 64;       // events per lane per batch of the evaluation walk (chunks are whole batches)
 constexpr int DC_REPLAY_MAX  = 64;       // chunks a serial replay walks back before the block is declined (FAIL_REPLAY)
+constexpr int DC_RP_CAND     = 384;      // exact resolve of open chunk starts: start values a chunk is walked from, six per lane of a wavefront (the
+                                         // bracket behind DC_EV events is at most 373 wide for the static coder's slowest rate, 11 / 4096, and 128 for
+                                         // the fast coder's: tools/replay_resolve_probe.cpp bound; a wider one is not walked)
+constexpr uint32_t DC_SIGMASK = 0x7ffu;  // chain-major event = X | sub-block << 8 | bit << 11: the bits that name the chain inside a row
+constexpr uint32_t DC_ROWMARK = 0x1000u; // ... and the mark of an event that starts a chain whatever its signature (dc_mark_rows_kernel, dc_mark_chains_kernel)
+constexpr int DC_ROWS        = 1088;     // rows of the chain-major layout = decision types (NUM_TAU = 1080), padded to whole wavefronts
 constexpr int DC_AVG_CH      = 1024;     // runs per avg_rank lane
 constexpr int DC_AVG_WARM    = 768;      // warm-up runs in front of an avg_rank chunk
 constexpr int DC_AVG_CAND    = 64;       // exact resolve: start values a lane's chunk is walked from, one per lane of a wavefront (the bracket
@@ -473,6 +479,149 @@ inline void avg_resolve_host(const uint8_t* rank, uint32_t m, const uint32_t* fi
             lo = avg_rank_next(lo, rank[j]); hi = avg_rank_next(hi, rank[j]); x = avg_rank_next(x, rank[j]);
         }
         (known ? R.resolved : R.left) += und[c];
+    }
+}
+
+// ---- open chunk starts resolved exactly (devcoder.hip 3': dc_rp_map_kernel, dc_rp_chain_kernel), restated for the host -------------------
+// The evaluation of one unit as dc_eval has it: up to four jobs of chain-major events (row = decision type, rowstart[0 .. DC_ROWS]; the
+// first event of every non-empty row and every other chain start the signature does not show carry DC_ROWMARK already), EV events per
+// chunk, the chunks of job q in slots cstart[q] .. (padded to whole wavefronts, as on the device).  The same steps in the same order as
+// the kernels: (1) dc_eval_wave_kernel<false>: every chunk walks the bracket [vmin, vmax] of its first row's class to its end
+// (elo, ehi), both ends reset wherever a chain starts; (2) chunk c is OPEN iff it continues the chain of the event before it and the
+// bracket of chunk c - 1 has not met; a STRETCH is a maximal run of open chunks c0 + 1 .. ck + 1, its HEAD c0 starts from a known value;
+// (3) dc_rp_map_kernel: a chunk whose successor is open is walked — the head from its one start (head end), every other one from
+// every value elo[p - 1] + v of its start bracket: map[p][v] = end - elo[p] — unless that bracket has more than `cand` values (the
+// guard: state WIDE); (4) dc_rp_chain_kernel: per stretch the exact starts follow from the maps in order and close the brackets
+// (elo[p] = ehi[p] = exact start of p + 1), up to the first WIDE chunk; (5) dc_eval_b_kernel: the start of every chunk — the chain's
+// initial value, the closed bracket in front of it, or a serial replay from the nearest known start (`replays` chunks walked; more than
+// DC_REPLAY_MAX back: fail_replay).  resolve false: steps 3 and 4 are left out — today's path.
+enum : uint8_t { DC_RP_NONE = 0, DC_RP_HEAD = 1, DC_RP_MAP = 2, DC_RP_WIDE = 3 };      // per chunk: what dc_rp_map_kernel left for the chain
+struct ReplayJob { const uint16_t* events; uint32_t E; const uint32_t* rowstart; int fam; };
+struct ReplayResolve {
+    uint32_t ev = 0, cstart[5] = {0, 0, 0, 0, 0};
+    uint32_t open = 0;                             // chunks that start inside a chain behind a bracket that has not met
+    uint32_t resolved = 0;                         // of those: start settled by the resolve (DM_REPLAY_RESOLVED)
+    uint32_t replays = 0;                          // chunks walked again serially (DM_REPLAYS)
+    bool     fail_replay = false;
+    uint32_t stretches = 0, longest = 0;           // stretches, and the open chunks of the longest
+    uint32_t max_width = 0;                        // widest start bracket (values) of an open chunk
+    uint32_t wide = 0;                             // chunks the guard left unwalked
+    std::vector<uint16_t> elo, ehi, start;         // per chunk slot: the bracket at its end (after step 4), the start value dc_eval_b_kernel hands it
+    std::vector<uint8_t> known;                    // per chunk slot: start[] is set (a chunk behind a declined replay is not)
+};
+inline int class_first_row(int cls)
+{
+    return cls == CLS_RF ? TAU_RF : cls == CLS_RE ? TAU_RE : cls == CLS_RM ? TAU_RM : cls == CLS_RP ? TAU_RP : cls == CLS_NF ? TAU_NF
+         : cls == CLS_NE ? TAU_NE : cls == CLS_NM ? TAU_NM : cls == CLS_NM2 ? TAU_NM2 : DC_ROWS;
+}
+inline uint32_t replay_find_row(const uint32_t* rowstart, uint32_t k)
+{
+    uint32_t lo = 0, hi = DC_ROWS;                                     // largest row with rowstart[row] <= k (dc_find_row)
+    while (lo + 1 < hi) { const uint32_t mid = (lo + hi) >> 1; if (rowstart[mid] <= k) lo = mid; else hi = mid; }
+    return lo;
+}
+inline bool replay_chunk_continues(const ReplayJob& J, uint32_t c, uint32_t EV)
+{
+    if (c == 0) return false;
+    const uint32_t k0 = c * EV;
+    if (J.rowstart[replay_find_row(J.rowstart, k0)] == k0) return false;
+    const uint32_t e1 = J.events[k0];
+    return ((((uint32_t)J.events[k0 - 1] ^ e1) & DC_SIGMASK) | (e1 & DC_ROWMARK)) == 0;
+}
+inline void replay_resolve_host(const ReplayJob* jobs /* [4] */, uint32_t EV, const ModelParams& M, uint32_t cand, bool resolve, ReplayResolve& R)
+{
+    R = ReplayResolve();
+    R.ev = EV;
+    for (int q = 0; q < 4; ++q) R.cstart[q + 1] = R.cstart[q] + ((jobs[q].E + EV - 1) / EV + 63) / 64 * 64;
+    const uint32_t slots = R.cstart[4];
+    R.elo.assign(slots, 0); R.ehi.assign(slots, 0); R.start.assign(slots, 0); R.known.assign(slots, 0);
+    std::vector<uint8_t> st(slots, DC_RP_NONE);
+    std::vector<uint16_t> head(slots, 0), map(resolve ? (size_t)slots * DC_RP_CAND : 0, 0);
+    if (cand > (uint32_t)DC_RP_CAND) cand = DC_RP_CAND;
+    for (int q = 0; q < 4; ++q) {
+        const ReplayJob& J = jobs[q];
+        if (J.E == 0) continue;
+        const uint32_t nch = (J.E + EV - 1) / EV, s0 = R.cstart[q];
+        uint16_t* elo = R.elo.data() + s0; uint16_t* ehi = R.ehi.data() + s0;
+        auto cls_of = [&](uint32_t k) { return tau_class((int)replay_find_row(J.rowstart, k)); };
+        auto is_open = [&](uint32_t c) { return c < nch && replay_chunk_continues(J, c, EV) && elo[c - 1] != ehi[c - 1]; };
+        // a bare walk of n events from k: one chain, one set of rates (what the map kernel and the replay loop do)
+        auto bare = [&](uint32_t k, uint32_t n, int v, const Rates& Rt) { for (uint32_t i = 0; i < n; ++i) v = step(v, ((uint32_t)J.events[k + i] >> 11) & 1u, Rt); return v; };
+        // (1) dc_eval_wave_kernel<false>
+        for (uint32_t c = 0; c < nch; ++c) {
+            const uint32_t k0 = c * EV, k1 = k0 + EV < J.E ? k0 + EV : J.E;
+            int cls = 0;
+            while (cls + 1 < NUM_CLS && J.rowstart[class_first_row(cls + 1)] <= k0) ++cls;
+            uint32_t clsend = J.rowstart[class_first_row(cls + 1)];
+            uint32_t prev = k0 > 0 ? ((uint32_t)J.events[k0 - 1] & DC_SIGMASK) : 0xffffu;
+            int lo = M.vmin[cls][J.fam], hi = M.vmax[cls][J.fam];
+            for (uint32_t k = k0; k < k1; ++k) {
+                while (k >= clsend && cls + 1 < NUM_CLS) { ++cls; clsend = J.rowstart[class_first_row(cls + 1)]; }
+                const uint32_t e = J.events[k];
+                if ((e & (DC_SIGMASK | DC_ROWMARK)) != prev) lo = hi = M.init[cls];
+                prev = e & DC_SIGMASK;
+                lo = step(lo, (e >> 11) & 1u, M.rates[cls][J.fam]); hi = step(hi, (e >> 11) & 1u, M.rates[cls][J.fam]);
+            }
+            elo[c] = (uint16_t)lo; ehi[c] = (uint16_t)hi;
+        }
+        // (2) the open chunks and their stretches
+        for (uint32_t c = 1, run = 0; c <= nch; ++c) {
+            if (is_open(c)) {
+                ++R.open; ++run;
+                const uint32_t w = (uint32_t)(ehi[c - 1] - elo[c - 1]) + 1u;
+                if (w > R.max_width) R.max_width = w;
+                if (run == 1) ++R.stretches;
+                if (run > R.longest) R.longest = run;
+            } else run = 0;
+        }
+        if (resolve) {
+            // (3) dc_rp_map_kernel
+            for (uint32_t p = 0; p + 1 < nch; ++p) {
+                if (!is_open(p + 1)) continue;
+                const Rates& Rt = M.rates[cls_of(p * EV)][J.fam];
+                if (!is_open(p)) {                                     // (a head always continues a chain behind a closed bracket: see dc_rp_map_kernel)
+                    const int s = replay_chunk_continues(J, p, EV) ? (int)elo[p - 1] : (int)M.init[cls_of(p * EV)];
+                    head[s0 + p] = (uint16_t)bare(p * EV, EV, s, Rt);
+                    st[s0 + p] = DC_RP_HEAD;
+                    continue;
+                }
+                const uint32_t w = (uint32_t)(ehi[p - 1] - elo[p - 1]) + 1u;
+                if (w > cand) { st[s0 + p] = DC_RP_WIDE; ++R.wide; continue; }
+                for (uint32_t v = 0; v < w; ++v) map[(size_t)(s0 + p) * DC_RP_CAND + v] = (uint16_t)(bare(p * EV, EV, (int)elo[p - 1] + (int)v, Rt) - (int)elo[p]);
+                st[s0 + p] = DC_RP_MAP;
+            }
+            // (4) dc_rp_chain_kernel: one walk per stretch, from its head
+            for (uint32_t p0 = 0; p0 < nch; ++p0) {
+                if (st[s0 + p0] != DC_RP_HEAD) continue;
+                uint32_t x = head[s0 + p0], base = elo[p0];
+                elo[p0] = ehi[p0] = (uint16_t)x; ++R.resolved;
+                for (uint32_t p = p0 + 1; p < nch && st[s0 + p] == DC_RP_MAP; ++p) {
+                    const uint32_t y = (uint32_t)elo[p] + map[(size_t)(s0 + p) * DC_RP_CAND + (x - base)];
+                    base = elo[p];
+                    elo[p] = ehi[p] = (uint16_t)y; ++R.resolved;
+                    x = y;
+                }
+            }
+        }
+        // (5) dc_eval_b_kernel
+        for (uint32_t c = 0; c < nch; ++c) {
+            const int init_c = M.init[cls_of(c * EV)];
+            R.known[s0 + c] = 1;
+            if (!replay_chunk_continues(J, c, EV)) { R.start[s0 + c] = (uint16_t)init_c; continue; }
+            if (elo[c - 1] == ehi[c - 1]) { R.start[s0 + c] = elo[c - 1]; continue; }
+            uint32_t j = c - 1, depth = 1;
+            int s = init_c;
+            bool failed = false;
+            for (;;) {
+                if (!replay_chunk_continues(J, j, EV)) { s = init_c; break; }
+                if (elo[j - 1] == ehi[j - 1]) { s = elo[j - 1]; break; }
+                --j; ++depth;
+                if (depth > (uint32_t)DC_REPLAY_MAX) { failed = true; break; }
+            }
+            if (failed) { R.fail_replay = true; R.known[s0 + c] = 0; continue; }
+            R.replays += depth;
+            R.start[s0 + c] = (uint16_t)bare(j * EV, (c - j) * EV, s, M.rates[cls_of(j * EV)][J.fam]);
+        }
     }
 }
 

@@ -392,6 +392,7 @@ class GpuContext:
     # a model pass in segments (default 0), segments kept, halves run again, blocks that ended on the host model; the model's capacity in decisions
     OPT_BATCH_MODEL_SEGMENTS, CNT_BATCH_SEGMENTS, CNT_BATCH_SEG_RERUNS, CNT_BATCH_SEG_HOST_BLOCKS, CNT_DC_DCAP = 22, 23, 24, 25, 26
     CNT_DC_REPLAYS, CNT_DC_LAST_FAIL, CNT_DC_AVG_UNDECIDED, CNT_DC_HIST_EXTENDED = 5, 6, 7, 8      # the last device-model block (get only)
+    OPT_DC_REPLAY_EXACT, CNT_DC_REPLAY_RESOLVED = 32, 33    # open chunk starts of the evaluation resolved exactly; chunks that settled (get only)
     OPT_DC_AVG_EXACT, CNT_DC_AVG_RESOLVED = 30, 31      # open avg_rank flags resolved exactly on the device; what that settled (get only)
     DC_FAIL_AVG, DC_FAIL_HIST, DC_FAIL_CAP, DC_FAIL_REPLAY = 2, 4, 8, 16                          # BSCGPU_DC_FAIL_*
 

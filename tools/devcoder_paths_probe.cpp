@@ -4,6 +4,10 @@
 //   g++ -O2 -std=c++17 -march=x86-64-v3 -I libbsc_amd/csrc/host -I libbsc_amd/csrc/device -I include tools/devcoder_paths_probe.cpp \
 //       libbsc_amd/csrc/host/coder.cpp -o probe -lpthread
 //   probe L.bin      -> one JSON object on stdout
+//   probe L.bin replay_exact   the same with BSCGPU_OPT_DC_REPLAY_EXACT on: open chunk starts are resolved exactly whatever the length of
+//                    the stretch (no bracket exceeds the resolve's cap: tools/replay_resolve_probe.cpp bound), so no chunk is replayed and
+//                    FAIL_REPLAY is not among the exits; the object gains "replay_exact": true.  How many chunks the resolve settles
+//                    depends on the chain-major layout: replay_resolve_probe block L.bin.
 //
 // What is computed, per block (sub-block split and run / rank front end as the stage function has them):
 //   avg_und      runs whose avg_rank >= 32 flag stays undecided under dc_avg_kernel's rule: chunks of DC_AVG_CH runs of the block's run
@@ -84,7 +88,8 @@ struct CountPolicy {                       // decisions of a sub-block (the chun
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s L.bin\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s L.bin [replay_exact]\n", argv[0]); return 2; }
+    const bool replay_exact = argc > 2 && !strcmp(argv[2], "replay_exact");
     FILE* f = fopen(argv[1], "rb");
     if (!f) { perror(argv[1]); return 2; }
     fseek(f, 0, SEEK_END); const long n = ftell(f); fseek(f, 0, SEEK_SET);
@@ -182,8 +187,8 @@ int main(int argc, char** argv)
     if (avg_und) mask |= 2;
     if (hist_fail) mask |= 4;
     // (an earlier exit stops the evaluation: a block declined for its contexts is never replayed)
-    const bool fail_replay = mask == 0 && stretch > fail_min;
-    const bool no_fail_replay = mask != 0 || risk <= keep_max;
+    const bool fail_replay = mask == 0 && stretch > fail_min && !replay_exact;
+    const bool no_fail_replay = mask != 0 || risk <= keep_max || replay_exact;
     if (fail_replay) mask |= 16;
 
     printf("{\"n\": %ld, \"nb\": %d, \"runs\": %u, \"decisions\": %llu, \"ev\": %u,\n", n, nb, m, (unsigned long long)D, EV);
@@ -206,7 +211,9 @@ int main(int argc, char** argv)
     printf("},\n");
     printf(" \"replay_min\": %llu, \"fail_min\": %llu, \"keep_max\": %llu,\n", (unsigned long long)replay_min, (unsigned long long)fail_min, (unsigned long long)keep_max);
     // fail_mask: the reason mask the stage must return (0: none of the exits judged here is certain); the three booleans say what is CERTAIN
+    if (replay_exact) printf(" \"replay_exact\": true,\n");
     printf(" \"fail_mask\": %d, \"replay_certain\": %s, \"no_replay_certain\": %s, \"no_fail_replay_certain\": %s}\n", mask,
-           (mask == 0 || fail_replay) && stretch >= replay_min ? "true" : "false", (mask & ~16) != 0 || risk == 0 ? "true" : "false", no_fail_replay ? "true" : "false");
+           (mask == 0 || fail_replay) && stretch >= replay_min && !replay_exact ? "true" : "false", (mask & ~16) != 0 || risk == 0 || replay_exact ? "true" : "false",
+           no_fail_replay ? "true" : "false");
     return 0;
 }
