@@ -26,6 +26,7 @@
 #include "../device/dev_common.h"
 #include "../device/dma_copy.h"
 #include "../device/dc_segment_plan.h"
+#include "batch_pass_plan.h"
 #include "qlfc.h"
 #include "lzp.h"
 #include "par.h"
@@ -182,13 +183,6 @@ struct DefaultGpuUser {                         // RAII around acquire / release
 
 static inline void put_i32(unsigned char* p, int v) { memcpy(p, &v, 4); }
 static inline int  get_i32(const unsigned char* p) { int v; memcpy(&v, p, 4); return v; }
-
-static int aux_rate(int n)          // largest power of two <= n / 8 (>= 1), bwt.cpp:192-197
-{
-    int mod = n / 8;
-    mod |= mod >> 1; mod |= mod >> 2; mod |= mod >> 4; mod |= mod >> 8; mod |= mod >> 16; mod >>= 1;
-    return mod + 1;
-}
 
 extern "C" {
 
@@ -1434,22 +1428,7 @@ int bsc_synth_text_v1(unsigned long long seed, unsigned char* out, long long n)
 extern "C" BSCGPU_API int bscgpu_batch_plan(const int* sizes, int count, int blockSorter, int64_t cap, int* pass_of)
 {
     if (count < 0 || (count > 0 && (!sizes || !pass_of))) return LIBBSC_BAD_PARAMETER;
-    int passes = 0, cur = -1, span = 0;
-    int64_t bytes = 0;
-    for (int b = 0; b < count; ++b) {
-        const int n = sizes[b];
-        if (n < 0) return LIBBSC_BAD_PARAMETER;
-        const bool batched = blockSorter == LIBBSC_BLOCKSORTER_BWT && n > 0 && n < BSCGPU_BATCH_MAX_N && (int64_t)n <= cap;
-        if (!batched) {
-            pass_of[b] = -1;
-            if (n > 0) cur = -1;                     // a pass is one contiguous range of the input: a block of its own ends it
-            else if (cur >= 0) ++span;               // (an empty block inside a pass is an empty entry of its table)
-            continue;
-        }
-        if (cur < 0 || bytes + n > cap || span + 1 > BATCH_MAX_BLOCKS) { cur = passes++; bytes = 0; span = 0; }
-        pass_of[b] = cur; bytes += n; ++span;
-    }
-    return passes;
+    return batch_pass_plan_bwt(sizes, count, blockSorter, cap, pass_of);
 }
 
 // The same rule for the sort transform: blocks of 1 .. BSCGPU_ST_BATCH_MAX_N - 1 bytes ride in passes (a block of one byte too: its
@@ -1458,20 +1437,7 @@ extern "C" BSCGPU_API int bscgpu_st_batch_plan(const int* sizes, int count, int 
 {
     if (count < 0 || (count > 0 && (!sizes || !pass_of)) || k < LIBBSC_BLOCKSORTER_ST3 || k > LIBBSC_BLOCKSORTER_ST8) return LIBBSC_BAD_PARAMETER;
     for (int b = 0; b < count; ++b) if (sizes[b] < 0) return LIBBSC_BAD_PARAMETER;
-    int passes = 0, cur = -1, span = 0;
-    int64_t bytes = 0;
-    for (int b = 0; b < count; ++b) {
-        const int n = sizes[b];
-        if (n == 0 || n >= BSCGPU_ST_BATCH_MAX_N || (int64_t)n > cap) {
-            pass_of[b] = -1;
-            if (n > 0) cur = -1;
-            else if (cur >= 0) ++span;
-            continue;
-        }
-        if (cur < 0 || bytes + n > cap || span + 1 > BSCGPU_ST_BATCH_MAX_BLOCKS) { cur = passes++; bytes = 0; span = 0; }
-        pass_of[b] = cur; bytes += n; ++span;
-    }
-    return passes;
+    return batch_pass_plan_st(sizes, count, cap, pass_of);
 }
 
 static int plan_for(const int* sizes, int count, int blockSorter, int64_t cap, int* pass_of)
@@ -1501,8 +1467,7 @@ extern "C" BSCGPU_API int bscgpu_st_batch_device(bscgpu_ctx* c, const void* dT, 
             ++b;
             continue;
         }
-        int e = b;
-        for (int q = b; q < count && (pass_of[q] == pass_of[b] || (pass_of[q] < 0 && sizes[q] == 0)); ++q) if (pass_of[q] == pass_of[b]) e = q + 1;
+        const int e = batch_pass_end(pass_of.data(), sizes, count, b);
         const int rc = st_batch_device(c, T + off[b], O + off[b], sizes + b, e - b, k, nullptr, index + b);
         if (rc < 0) return rc;
         b = e;
@@ -1557,9 +1522,7 @@ extern "C" BSCGPU_API int bscgpu_bwt_batch_device(bscgpu_ctx* c, const void* dT,
             ++b;
             continue;
         }
-        // the pass: its members and the empty blocks between them, one contiguous range
-        int e = b;
-        for (int q = b; q < count && (pass_of[q] == pass_of[b] || (pass_of[q] < 0 && sizes[q] == 0)); ++q) if (pass_of[q] == pass_of[b]) e = q + 1;
+        const int e = batch_pass_end(pass_of.data(), sizes, count, b);      // the pass: one contiguous range
         const int rc = bwt_batch_device(c, T + off[b], L + off[b], sizes + b, e - b, rate.data() + b, res.data());
         if (rc < 0) return rc;
         for (int q = b; q < e; ++q) if (rate[q] >= 0 && sizes[q] > 0) put(q, res.data() + 16 * (size_t)(q - b));
@@ -1596,15 +1559,28 @@ static int compress_one_on_ctx(bscgpu_ctx* c, const unsigned char* input, unsign
     return J->result;
 }
 
+static_assert(BATCH_PASS_MAX_BLOCKS == BATCH_MAX_BLOCKS, "batch_pass_plan.h plans passes of as many blocks as the sorters take");
+
 namespace {
 struct BatchBlock {
     int b = 0, lz = 0, mode = 0, index = 0, num_indexes = 0;
     int indexes[16];
     unsigned adler = 0;                          // Adler-32 of the block's input (device input: from the pass's segmented kernel)
-    bool sorted = false;                         // in the pass's sort (else result already set, or left to the single path)
-    bool single = false;                         // after LZP: the single-block path decides (a sorter input too short for the aux indexes)
-    bool store = false;                          // device input of <= 28 bytes: stored from its copy in the pass's L buffer (L = T there)
+    BatchClass cls = BATCH_EMPTY;                // what became of it in the pass's preparation (batch_pass_plan.h)
     unsigned char* lzbuf = nullptr;
+};
+
+// What a block of a sorted pass is coded from (batch_pass_plan.h: batch_block_source): its L, or entry li of the pass's front-end layout
+// with its run arrays, the pass's probability stream from the device model of this coder (ps, sub-block s at poff[s]; packed: the
+// BSCGPU_RC_STATIC13 bodies at pbase[s]) or the sub-blocks as the device's range coder left them (BSCGPU_OPT_DEVICE_RC: rc_res[s] bytes,
+// or LIBBSC_NOT_COMPRESSIBLE, at rc_bytes + rc_off[s], coded with a budget of rc_room[s]; see front_batch_code_rc)
+struct PassSource {
+    BatchSource kind;
+    const unsigned char* L;
+    const bscgpu_front_layout* lay; int li;
+    const uint16_t* ps; const uint32_t* poff; const int64_t* pbase;
+    const uint8_t* rc_bytes; const uint32_t* rc_off; const int* rc_res; const int* rc_room;
+    bool packed;         // (the coded streams were BSCGPU_RC_STATIC13 bodies, whose LIBBSC_NOT_COMPRESSIBLE is not the reference's)
 };
 }
 
@@ -1619,28 +1595,30 @@ static int store_from_device(bscgpu_ctx* c, const unsigned char* dIn, unsigned c
     return n + LIBBSC_HEADER_SIZE;
 }
 
-// a model pass's sub-blocks as the device's range coder left them (BSCGPU_OPT_DEVICE_RC; see front_batch_code_rc)
-// (packed: the streams were BSCGPU_RC_STATIC13 bodies, whose LIBBSC_NOT_COMPRESSIBLE is not the reference's: see front_batch_code_rc)
-struct PassCoded { const uint8_t* bytes; const uint32_t* off; const int* res; const int* room; bool packed; };
 static int front_batch_code_rc(const bscgpu_front_layout* Lo, int block, const uint8_t* bytes, const uint32_t* off, const int* res, const int* room_of,
                                unsigned char* out, int coder, int features, bool packed);
 
+// the coder's part of it -> the bytes in out, or a negative code
+static int code_from_source(const PassSource& S, int lz, unsigned char* out, int coder, int features)
+{
+    switch (S.kind) {
+    case BATCH_FROM_L:         return coder_compress(S.L, out, lz, coder, features);
+    case BATCH_FROM_RUNS:      return bscgpu_front_batch_code(S.lay, S.li, out, coder, features);
+    case BATCH_FROM_PS16:      return bscgpu_front_batch_code_ps(S.lay, S.li, S.ps, S.poff, out, features);
+    case BATCH_FROM_PS13:      return bscgpu_front_batch_code_ps13(S.lay, S.li, reinterpret_cast<const uint8_t*>(S.ps), S.poff, S.pbase, out, features);
+    case BATCH_FROM_FAST:      return bscgpu_front_batch_code_psf(S.lay, S.li, S.ps, S.poff, out, features);
+    case BATCH_FROM_DEVICE_RC: return front_batch_code_rc(S.lay, S.li, S.rc_bytes, S.rc_off, S.rc_res, S.rc_room, out, coder, features, S.packed);
+    }
+    return LIBBSC_BAD_PARAMETER;
+}
+
 // the host tail of bsc_compress (libbsc.cpp:296-336) for one block of a sorted pass; input: host bytes, or dIn in HBM
-// (lay != nullptr: the block is entry li of a pass's front-end layout and is coded from its run arrays; else from its L at Lb)
 static int code_sorted_block(bscgpu_ctx* c, const unsigned char* input, const unsigned char* dIn, unsigned char* output, int n,
-                             const BatchBlock& B, const unsigned char* Lb, int coder, int features,
-                             const bscgpu_front_layout* lay = nullptr, int li = 0, const uint16_t* ps = nullptr, const uint32_t* poff = nullptr,
-                             const struct PassCoded* pc = nullptr, const int64_t* pbase = nullptr /* non-null: ps is the pass's packed stream */)
+                             const BatchBlock& B, int coder, int features, const PassSource* src)
 {
     unsigned char* buffer = (unsigned char*)bsc_malloc((size_t)B.lz + 4096);
     if (!buffer) return LIBBSC_NOT_ENOUGH_MEMORY;
-    // (ps: the pass's probability stream from the device model of this coder, static or fast — the range coder alone)
-    int result = lay ? (pc ? front_batch_code_rc(lay, li, pc->bytes, pc->off, pc->res, pc->room, buffer, coder, features, pc->packed)
-                           : ps ? (coder == LIBBSC_CODER_QLFC_FAST ? bscgpu_front_batch_code_psf(lay, li, ps, poff, buffer, features)
-                                   : pbase ? bscgpu_front_batch_code_ps13(lay, li, reinterpret_cast<const uint8_t*>(ps), poff, pbase, buffer, features)
-                                           : bscgpu_front_batch_code_ps(lay, li, ps, poff, buffer, features))
-                                : bscgpu_front_batch_code(lay, li, buffer, coder, features))
-                     : coder_compress(Lb, buffer, B.lz, coder, features);
+    int result = code_from_source(*src, B.lz, buffer, coder, features);
     if (result >= LIBBSC_NO_ERROR) memcpy(output + LIBBSC_HEADER_SIZE, buffer, (size_t)result);
     bsc_free(buffer);
     const int num = n < 64 * 1024 ? 0 : B.num_indexes;
@@ -1995,7 +1973,7 @@ extern "C" BSCGPU_API int64_t bscgpu_pstream_batch_segments_packed_device(bscgpu
 }
 
 namespace {
-// a pass's layout inside compress_batch_impl: the small arrays here, sym / rank / start and the first-run table in a pinned buffer
+// a pass's front-end layout (BatchPass): the small arrays here, sym / rank / start and the first-run table in a pinned buffer
 struct PassLayout {
     bscgpu_front_layout lay;
     std::vector<int> sizes, blk_sub, sub_start, sub_size, nsym;
@@ -2065,6 +2043,24 @@ struct PassGroups {
         return true;
     }
 };
+// what fills a segmented pass's queue: the segment driver's notes (DcSegNote), each block queued once
+struct PassFeed {
+    PassGroups* G; const std::vector<BatchBlock>* blocks; const int* blk_sub; const int* state; std::vector<char> queued;
+    void take(int b0, int b1, bool planned)
+    {
+        std::vector<int> g;
+        for (int i = b0; i < b1; ++i) {
+            const BatchBlock& B = (*blocks)[i];
+            // the first group: what the device's model leaves out, or never sees as a segment's member
+            const bool member = B.cls == BATCH_SORTED && blk_sub[i + 1] > blk_sub[i];
+            if (queued[i] || (planned && member && state[i] == 0)) continue;
+            queued[i] = 1; g.push_back(i);
+        }
+        G->push(std::move(g));
+    }
+    static void planned(void* u) { PassFeed* f = static_cast<PassFeed*>(u); f->take(0, (int)f->blocks->size(), true); }
+    static void settled(void* u, int b0, int b1) { static_cast<PassFeed*>(u)->take(b0, b1, false); }
+};
 struct PassOrder {
     std::mutex mu;
     std::condition_variable cv;
@@ -2123,299 +2119,437 @@ static int device_rc_pass(bscgpu_ctx* c, PassLayout& PL, uint8_t* host_bytes, si
     return LIBBSC_NO_ERROR;
 }
 
-// One implementation for both entry points: host input (`input`, LZP per block) or input in HBM (`dInput`, no LZP).
-static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const unsigned char* dInput, const int* sizes, int count,
-                               unsigned char* output, int* results, int lzpHashSize, int lzpMinLen, int blockSorter, int coder, int features)
+// ---- the driver of a batched-compress call: what batch_pass_plan.h decides, done in named steps ------------------------------------
+namespace {
+// What every step of a call works on.  One implementation for both entry points: host input (`input`, LZP per block) or input in HBM
+// (`dInput`, no LZP).
+struct BatchCall {
+    bscgpu_ctx* c;
+    const unsigned char* input; const unsigned char* dInput; const int* sizes; int count; unsigned char* output; int* results;
+    int lzpHashSize, lzpMinLen, blockSorter, coder, features;
+    int mode;
+    bool dev, st;                                 // input in HBM; (make_mode: BWT or ST3..ST8) the pass is one sort transform, no aux indexes
+    std::vector<int> pass_of;
+    std::vector<int64_t> in_off;
+    BatchRoute route;
+    size_t frontN;
+    int threads;
+    std::vector<char> single;                     // blocks that are not coded with a pass: batch_leftovers
+    std::vector<uint32_t> res, adler;             // what the sort of a pass leaves, until finish_blocks (one pass sorts at a time)
+    std::vector<int> stidx;
+
+    const unsigned char* in_of(int b) const { return input + in_off[b]; }
+    const unsigned char* din_of(int b) const { return dInput + in_off[b]; }
+    unsigned char* out_of(int b) const { return output + in_off[b] + (int64_t)LIBBSC_HEADER_SIZE * b; }
+    bool lzp() const { return mode != (mode & 0xff); }
+    int alone(int b) const                        // a block by the single-block path on the call's context
+    {
+        return dev ? bscgpu_compress_device(c, din_of(b), out_of(b), sizes[b], blockSorter, coder, features)
+                   : compress_one_on_ctx(c, in_of(b), out_of(b), sizes[b], lzpHashSize, lzpMinLen, blockSorter, coder, features);
+    }
+};
+
+class PassHandOff;
+
+// A pass of a call, in one of the call's two slots (p & 1; PassHandOff says why the slot is free): its blocks [b, e) of the input, where
+// they lie in the pass, its front-end layout and the queue its coding is fed from when the model runs in segments.
+struct BatchPass {
+    BatchCall* K = nullptr;
+    int p = 0, b = 0, e = 0;
+    std::vector<BatchBlock> blocks;
+    BatchGeometry G;                              // (G.at[i]: where block b + i's L lies in hb)
+    u8* hb = nullptr;
+    PassLayout PL;
+    PassGroups groups;
+    bool finished = false, grouped = false;
+
+    void prepare(BatchCall* call, int pass, int b0, int e0);
+    void prep_block(int i);
+    int  stage();
+    int  sort();
+    int  l_down();
+    int  front();
+    BatchModelStep model_step();
+    int  model_whole();
+    int  land_whole(u32 D, int pk, int64_t pbytes);
+    int  model_segments(PassHandOff& hand);
+    void finish_blocks();
+    // what the coding of the pass is made of: one block; the whole pass; the pass in groups (model segments)
+    PassSource source_of(int i) const;
+    void code_block(int i);
+    void code_pass(PassOrder& order);
+    void code_groups(PassOrder& order);
+};
+
+// The threads of a call.  One coder thread per pass codes pass p while pass p + 1 sorts; the thread of a pass in model segments starts
+// early, beside the pass's model, and becomes its coder thread when the pass is handed over; PassOrder makes the passes finish in order.
+// The buffer-lifetime rule: what pass p writes — its BatchPass slot and the context's batch_host, front_host and model_host of the same
+// index p & 1 — is free because the coder thread of pass p - 2 was joined (in take() of pass p - 1) before pass p - 1's coding started.
+class PassHandOff {
+public:
+    PassOrder order;
+    // a pass in model segments: its groups are coded as they are queued, from now on
+    void start_early(BatchPass& P)
+    {
+        P.grouped = true;
+        try { early_thread = std::thread([&P, this] { P.code_groups(order); }); }
+        catch (const std::system_error&) {}           // no thread to be had: the groups are coded in take(), after the model
+    }
+    // the pass is sorted and its blocks are finished: the previous pass's coding ends here, this pass's runs beside the next pass's sort
+    void take(BatchPass& P)
+    {
+        if (coder_thread.joinable()) coder_thread.join();
+        if (P.grouped) {                              // its coding is under way (or waits here, where no thread was to be had)
+            if (early_thread.joinable()) coder_thread = std::move(early_thread);
+            else P.code_groups(order);
+            return;
+        }
+        try { coder_thread = std::thread([&P, this] { P.code_pass(order); }); }
+        catch (const std::system_error&) { P.code_pass(order); }                   // no thread to be had: code the pass here
+    }
+    // the end of the call (a pass that ended in an error: its thread codes what it was given and ends)
+    void finish(BatchPass* slots)
+    {
+        slots[0].groups.close(); slots[1].groups.close();
+        if (coder_thread.joinable()) coder_thread.join();
+        if (early_thread.joinable()) early_thread.join();
+    }
+private:
+    std::thread coder_thread;                     // codes the previous pass while this one sorts
+    std::thread early_thread;                     // ... this pass's, when it started before the pass's model had finished (model segments)
+};
+
+void ctx_count(bscgpu_ctx* c, const BatchCounters& d)
 {
-    int mode = 0;
-    const int mrc = make_mode(blockSorter, coder, lzpHashSize, lzpMinLen, &mode);
-    if (mrc != LIBBSC_NO_ERROR) { for (int b = 0; b < count; ++b) results[b] = mrc; return LIBBSC_NO_ERROR; }
-    if (hipSetDevice(c->device) != hipSuccess) return LIBBSC_GPU_ERROR;
-    const bool dev = dInput != nullptr;
-    std::vector<int> pass_of((size_t)count);
-    const bool st = blockSorter != LIBBSC_BLOCKSORTER_BWT;                  // (make_mode: BWT or ST3..ST8) the pass is one sort transform, no aux indexes
-    const int npass = plan_for(sizes, count, blockSorter, c->max_n, pass_of.data());
+    c->cnt_front_passes += d.front_passes; c->cnt_l_passes += d.l_passes;
+    c->cnt_model_passes += d.model_passes; c->cnt_model_declined += d.model_declined;
+    c->cnt_model_fast_passes += d.fast_passes; c->cnt_model_fast_declined += d.fast_declined;
+    c->cnt_packed_passes += d.packed_passes; c->cnt_packed_void += d.packed_void; c->cnt_device_rc += d.device_rc;
+}
+
+// 1. prepare: the pass takes its slot; LZP of every member (libbsc.cpp:263-281) and its class
+void BatchPass::prepare(BatchCall* call, int pass, int b0, int e0)
+{
+    K = call; p = pass; b = b0; e = e0;
+    blocks.assign((size_t)(e - b), BatchBlock());
+    finished = grouped = false;
+    PL.used = false;
+    groups.reset();
+    hb = K->c->batch_host[p & 1];
+    // in parallel; without LZP there is nothing to spread over threads
+    if (K->lzp()) run_bounded(e - b, K->threads, [this](int i) { prep_block(i); });
+    else for (int i = 0; i < e - b; ++i) prep_block(i);
+}
+
+void BatchPass::prep_block(int i)
+{
+    BatchBlock& B = blocks[i];
+    const int q = b + i, n = K->sizes[q];
+    B.b = q; B.mode = K->mode; B.lz = n;
+    B.cls = batch_block_class(n, n, K->st, K->dev, K->pass_of[q] >= 0);            // (before LZP: n stands for what it leaves)
+    if (B.cls == BATCH_STORED) K->results[q] = bsc_store(K->in_of(q), K->out_of(q), n, K->features);
+    if (B.cls != BATCH_SORTED || !K->lzp()) return;
+    B.lzbuf = (unsigned char*)bigbuf_get((size_t)n);
+    const int r = B.lzbuf ? lzp_compress(K->in_of(q), B.lzbuf, n, K->lzpHashSize, K->lzpMinLen, K->features) : LIBBSC_NOT_ENOUGH_MEMORY;
+    if (r < LIBBSC_NO_ERROR) { B.mode &= 0xff; bigbuf_put(B.lzbuf); B.lzbuf = nullptr; }
+    else B.lz = r;
+    B.cls = batch_block_class(n, B.lz, K->st, K->dev, true);
+    if (B.cls == BATCH_SINGLE) { bigbuf_put(B.lzbuf); B.lzbuf = nullptr; }
+}
+
+// 2. stage: where every block lies in the pass; host input goes into hb and up to the device
+int BatchPass::stage()
+{
+    const int cnt = e - b;
+    std::vector<BatchClass> cls((size_t)cnt);
+    std::vector<int> lz((size_t)cnt);
+    for (int i = 0; i < cnt; ++i) { cls[i] = blocks[i].cls; lz[i] = blocks[i].lz; }
+    batch_pass_geometry(cls.data(), K->sizes + b, lz.data(), cnt, K->st, K->dev, &G);
+    if (K->dev) return LIBBSC_NO_ERROR;                                          // the pass is the caller's own range of HBM
+    for (int i = 0; i < cnt; ++i) {
+        BatchBlock& B = blocks[i];
+        if (B.cls == BATCH_SORTED) memcpy(hb + G.at[i], B.lzbuf ? B.lzbuf : K->in_of(B.b), (size_t)B.lz);
+        if (B.lzbuf) { bigbuf_put(B.lzbuf); B.lzbuf = nullptr; }
+    }
+    if (G.pos > 0 && hipMemcpyAsync(K->c->dL, hb, (size_t)G.pos, hipMemcpyHostToDevice, K->c->stream) != hipSuccess) return LIBBSC_GPU_ERROR;
+    return LIBBSC_NO_ERROR;
+}
+
+// 3. sort: one suffix sort or one sort transform for the pass
+int BatchPass::sort()
+{
+    bscgpu_ctx* c = K->c;
+    const u8* src = K->dev ? K->din_of(b) : c->dL;
+    u32* adler = K->dev ? K->adler.data() : nullptr;
+    return K->st ? st_batch_device(c, src, c->dL, G.psz.data(), e - b, K->blockSorter, G.prate.data(), K->stidx.data(), adler)
+                 : bwt_batch_device(c, src, c->dL, G.psz.data(), e - b, G.prate.data(), K->res.data(), adler);
+}
+
+// 5c. L down: the pass's L comes back in one copy
+int BatchPass::l_down()
+{
+    bscgpu_ctx* c = K->c;
+    if (hipMemcpyAsync(hb, c->dL, (size_t)G.pos, hipMemcpyDeviceToHost, c->stream) != hipSuccess || ctx_sync(c) != hipSuccess) return LIBBSC_GPU_ERROR;
+    ++c->cnt_l_passes;
+    return LIBBSC_NO_ERROR;
+}
+
+// 4. front: the pass's run arrays come down instead of its L
+int BatchPass::front()
+{
+    bscgpu_ctx* c = K->c;
+    // (the front end covers the whole range of the pass: with HBM input that includes members the layout is never read
+    // for — a block left to the single path rides along untransformed; correct, a little wasted work)
+    PL.bind(G.psz, c->front_host[p & 1], K->frontN);
+    const int rc = qlfc_front_batch(c, c->dL, PL.sizes.data(), e - b, &PL.lay, c->front_host[p & 1] + 6 * K->frontN);
+    if (rc < 0) return rc;
+    PL.used = true; ++c->cnt_front_passes;
+    PL.ps = nullptr; PL.rc_bytes = nullptr; PL.blk_state.clear(); PL.pbase.clear();
+    return rc;
+}
+
+// ... and which model step follows it; the two pinned stream buffers are allocated by the first pass that qualifies
+BatchModelStep BatchPass::model_step()
+{
+    BatchModelStep step = batch_model_step(K->route, PL.lay.nsub, G.pos, true);
+    if (step != BATCH_MODEL_NONE && ctx_ensure_model_host(K->c) != LIBBSC_NO_ERROR) step = batch_model_step(K->route, PL.lay.nsub, G.pos, false);
+    return step;
+}
+
+// 5a. model whole: the model behind the front end, on the same stream, before the next pass's sort; the run arrays came down all the
+// same: they serve a declined pass, a sub-block stored raw and the <= 28-byte blocks that rode along
+int BatchPass::model_whole()
+{
+    bscgpu_ctx* c = K->c;
+    u32 D = 0;
+    int pk = 0; int64_t pbytes = 0;          // packed: what the device left is the 13-bit form, pbytes of it; void: 16-bit entries as ever
+    const int mrc = devcoder_pstream_batch(c, (u32)PL.lay.m, PL.lay.nsub, K->coder, &D, K->route.packed ? &pk : nullptr, &pbytes);
+    const BatchVerdict v = batch_whole_verdict(mrc, D, pk, pbytes, c->model_host_entries);
+    if (v == BATCH_PASS_ERROR) return mrc;
+    if (v == BATCH_PASS_KEPT) {
+        const int rc = land_whole(D, pk, pbytes);
+        if (rc < 0) return rc;
+    }
+    ctx_count(c, batch_model_counters(K->route, BATCH_MODEL_WHOLE, v, pk));
+    return LIBBSC_NO_ERROR;
+}
+
+// the kept stream of a whole pass comes down — or stays in HBM, where one launch of the device's range coder codes it
+int BatchPass::land_whole(u32 D, int pk, int64_t pbytes)
+{
+    bscgpu_ctx* c = K->c;
+    PL.poff.resize((size_t)PL.lay.nsub + 1);
+    u16* hps = c->model_host[p & 1];
+    const bool drc = K->route.device_rc;
+    const size_t down = pk ? (size_t)pbytes : (size_t)D * 2;
+    std::vector<uint32_t> pb(pk ? PL.poff.size() : 0);
+    if (hipMemcpyAsync(PL.poff.data(), devcoder_batch_poff_ptr(c), PL.poff.size() * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        (pk && hipMemcpyAsync(pb.data(), devcoder_batch_pbase_ptr(c), pb.size() * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+        (!drc && down > 0 && hipMemcpyAsync(hps, devcoder_pstream_ptr(c, 0), down, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+        ctx_sync(c) != hipSuccess) return LIBBSC_GPU_ERROR;
+    if (pk) PL.pbase.assign(pb.begin(), pb.end());
+    if (drc) return device_rc_pass(c, PL, reinterpret_cast<uint8_t*>(hps), c->model_host_entries * 2, K->coder);
+    PL.ps = hps;
+    return LIBBSC_NO_ERROR;
+}
+
+// 5b. model segments: the same route segment by segment: the streams of the kept blocks land back to back, a block the device leaves
+// out (or whose segment no longer fits the landing buffer) is coded from its run arrays.  Coding starts with the plan: the pass's
+// thread takes groups of blocks as they settle (PassGroups)
+int BatchPass::model_segments(PassHandOff& hand)
+{
+    bscgpu_ctx* c = K->c;
+    const bool packed = K->route.packed;
+    const int cnt = e - b;
+    PL.poff.resize((size_t)PL.lay.nsub + 1);
+    PL.blk_state.assign((size_t)cnt, 0);
+    PL.ps = c->model_host[p & 1];
+    if (packed) PL.pbase.assign((size_t)PL.lay.nsub + 1, 0);
+    finish_blocks();
+    PassFeed feed{&groups, &blocks, PL.lay.blk_sub, PL.blk_state.data(), std::vector<char>((size_t)cnt, 0)};
+    DcSegNote note{PassFeed::planned, PassFeed::settled, &feed};
+    hand.start_early(*this);
+    int64_t D = 0;
+    // (packed: the landing buffer in bytes, less the few a packed entry's 4-byte read may reach past a stream)
+    const int mrc = devcoder_pstream_segments(c, (u32)PL.lay.m, PL.lay.nsub, PL.lay.blk_sub, cnt, PL.lay.sub_run, K->coder, K->route.segment_target,
+                                              c->model_host[p & 1], packed ? (int64_t)c->model_host_entries * 2 - 8 : (int64_t)c->model_host_entries,
+                                              true, PL.poff.data(), PL.blk_state.data(), &D, &note, packed ? PL.pbase.data() : nullptr);
+    const BatchVerdict v = batch_segments_verdict(mrc, PL.lay.blk_sub, PL.blk_state.data(), cnt);
+    if (v == BATCH_PASS_ERROR) { groups.close(); return mrc; }
+    // (an arena did not fit: what is not queued yet takes the host model)
+    if (mrc < 0) for (int i = 0; i < cnt; ++i) if (!feed.queued[i]) PL.blk_state[i] = BSCGPU_DC_FAIL_CAP;
+    ctx_count(c, batch_model_counters(K->route, BATCH_MODEL_SEGMENTS, v, 0));
+    feed.take(0, cnt, false);               // whatever is left
+    groups.close();
+    return LIBBSC_NO_ERROR;
+}
+
+// 6. finish blocks: the sort's results into the blocks, before the first of them is coded
+void BatchPass::finish_blocks()
+{
+    if (finished) return;
+    finished = true;
+    for (int i = 0; i < e - b; ++i) {
+        BatchBlock& B = blocks[i];
+        if (B.cls == BATCH_SINGLE) K->single[B.b] = 1;
+        if (K->dev) B.adler = K->adler[i];
+        if (B.cls != BATCH_SORTED) continue;
+        if (K->st) { B.index = K->stidx[i]; B.num_indexes = 0; continue; }
+        const uint32_t* I = K->res.data() + 16 * (size_t)i;
+        B.index = (int)I[0];
+        B.num_indexes = (B.lz - 1) / aux_rate(B.lz);
+        for (int t = 0; t < B.num_indexes; ++t) B.indexes[t] = (int)I[t + 1] - 1;
+    }
+}
+
+// (the per-block test "this block keeps the host model" is settled here)
+PassSource BatchPass::source_of(int i) const
+{
+    const bool host_block = !PL.blk_state.empty() && PL.blk_state[i] != 0, packed = !PL.pbase.empty();
+    PassSource S = {};
+    S.kind = batch_block_source(PL.used, PL.ps != nullptr, PL.rc_bytes != nullptr, host_block, K->coder == LIBBSC_CODER_QLFC_FAST, packed);
+    S.L = hb + G.at[i];
+    S.lay = &PL.lay; S.li = i;
+    S.ps = PL.ps; S.poff = PL.poff.data(); S.pbase = PL.pbase.data();
+    S.rc_bytes = PL.rc_bytes; S.rc_off = PL.rc_off.data(); S.rc_res = PL.rc_res.data(); S.rc_room = PL.rc_room.data();
+    S.packed = packed;
+    return S;
+}
+
+void BatchPass::code_block(int i)
+{
+    const BatchBlock& B = blocks[i];
+    if (B.cls != BATCH_RIDES && B.cls != BATCH_SORTED) return;
+    const int n = K->sizes[B.b];
+    const bscgpu_front_layout& Y = PL.lay;
+    if (PL.used)
+        for (int s = Y.blk_sub[i]; s < Y.blk_sub[i + 1]; ++s)
+            qlfc_front_first_seen(PL.first_run + 256 * (size_t)s, Y.first_seen + 256 * (size_t)s, &Y.nsym[s]);
+    if (B.cls == BATCH_RIDES) {             // <= 28 bytes that rode along (L = T): in the pass's L, or — its bytes are its runs — in its layout
+        unsigned char tmp[LIBBSC_HEADER_SIZE + 1];
+        RunView V[8];
+        if (PL.used) { front_views(&Y, i, V); expand_runs(V[0], 0, tmp); }
+        K->results[B.b] = bsc_store(PL.used ? tmp : hb + G.at[i], K->out_of(B.b), n, K->features);
+        return;
+    }
+    const PassSource S = source_of(i);
+    K->results[B.b] = code_sorted_block(K->c, K->dev ? nullptr : K->in_of(B.b), K->dev ? K->din_of(B.b) : nullptr, K->out_of(B.b), n, B, K->coder, K->features, &S);
+}
+
+void BatchPass::code_pass(PassOrder& order)
+{
+    run_bounded((int)blocks.size(), K->threads, [this](int i) { code_block(i); });
+    order.finish();
+}
+
+// one coding group at a time per call: the previous pass's coding first, then this pass's groups as they are queued
+void BatchPass::code_groups(PassOrder& order)
+{
+    order.wait_for(p);
+    std::vector<int> g;
+    while (groups.pop(g)) run_bounded((int)g.size(), K->threads, [&](int k) { code_block(g[k]); });
+    order.finish();
+}
+
+// the call's route: the context's options and the coder, with the environment's values read per call
+BatchRoute call_route(bscgpu_ctx* c, int npass, int coder)
+{
+    const BatchOptions o = {c->batch_front, c->batch_model, c->batch_model_fast, c->batch_model_segments, c->batch_model_packed, c->device_rc};
+    // the front end needs the two pinned run buffers; without them today's route
+    const bool front_host = batch_wants_front(npass, o) && ctx_ensure_front_host(c) == LIBBSC_NO_ERROR;
+    return batch_route(npass, o, coder, front_host, batch_model_min_pass(false), batch_model_min_pass(true), batch_model_segment());
+}
+
+// the plan of the call, its offsets, buffers and route -> the number of passes, or a negative code
+int batch_call_begin(BatchCall& K)
+{
+    bscgpu_ctx* c = K.c;
+    K.pass_of.resize((size_t)K.count);
+    const int npass = plan_for(K.sizes, K.count, K.blockSorter, c->max_n, K.pass_of.data());
     if (npass < 0) return npass;
-    std::vector<int64_t> in_off((size_t)count + 1, 0);
-    for (int b = 0; b < count; ++b) in_off[b + 1] = in_off[b] + sizes[b];
-    auto in_of = [&](int b) { return input + in_off[b]; };
-    auto din_of = [&](int b) { return dInput + in_off[b]; };
-    auto out_of = [&](int b) { return output + in_off[b] + (int64_t)LIBBSC_HEADER_SIZE * b; };
+    K.in_off.assign((size_t)K.count + 1, 0);
+    for (int b = 0; b < K.count; ++b) K.in_off[b + 1] = K.in_off[b] + K.sizes[b];
     if (npass > 0)
         for (int k = 0; k < 2; ++k)
             if (!c->batch_host[k] && hipHostMalloc((void**)&c->batch_host[k], (size_t)c->max_n + 64, hipHostMallocDefault) != hipSuccess) {
                 c->batch_host[k] = nullptr;
                 return ctx_fail(c, LIBBSC_GPU_NOT_ENOUGH_MEMORY, "batched compression: pinned pass buffers", hipSuccess);
             }
-    // the front end of every pass on the GPU (BSCGPU_OPT_BATCH_FRONT): needs the two pinned run buffers; without them today's route
-    const bool front = npass > 0 && c->batch_front != 0 && ctx_ensure_front_host(c) == LIBBSC_NO_ERROR;
-    // ... and the static coder's model behind it (BSCGPU_OPT_BATCH_MODEL); its two pinned stream buffers are allocated by the first pass
-    // that qualifies, and without them the passes keep the host model
-    // ... or the fast coder's (BSCGPU_OPT_BATCH_MODEL_FAST: an option and counters of its own); -e2 stays on the host
-    const bool fast_model = front && c->batch_model_fast != 0 && coder == LIBBSC_CODER_QLFC_FAST;
-    const bool model = fast_model || (front && c->batch_model != 0 && coder == LIBBSC_CODER_QLFC_STATIC);
-    const int64_t model_min_pass = batch_model_min_pass(fast_model);
-    // ... in model segments (BSCGPU_OPT_BATCH_MODEL_SEGMENTS); with the device's range coder on, a pass takes the whole-pass route
-    const bool segments = model && c->batch_model_segments != 0 && c->device_rc == 0;
-    const int64_t segment_target = segments ? batch_model_segment() : 0;
-    // ... with the stream in the packed 13-bit form (BSCGPU_OPT_BATCH_MODEL_PACKED): -e1 only, whole passes and segments alike
-    const bool packed_route = model && !fast_model && c->batch_model_packed != 0;
-    const size_t frontN = ((size_t)c->max_n + 4096 + 4095) / 4096 * 4096;
-    std::vector<PassLayout> lays(2);
-    const int threads = default_coder_threads();
-    std::vector<char> single((size_t)count, 0);
-    for (int b = 0; b < count; ++b) single[b] = pass_of[b] < 0;
-    std::thread coder_thread;                     // codes the previous pass while this one sorts
-    std::thread early_thread;                     // ... this pass's, when it started before the pass's model had finished (model segments)
-    PassGroups groups[2];                         // slot p & 1, free as hb is
-    PassOrder order;
-    int rc = LIBBSC_NO_ERROR;
-    std::vector<std::vector<BatchBlock>> bufs(2);
-    std::vector<uint32_t> res((size_t)BATCH_MAX_BLOCKS * 16), adler((size_t)BATCH_MAX_BLOCKS);
-    std::vector<int> stidx((size_t)BATCH_MAX_BLOCKS);
-    for (int b = 0, p = 0; b < count && rc >= 0;) {
-        if (pass_of[b] < 0) { ++b; continue; }
-        int e = b;          // the pass: its members and the empty blocks between them, one contiguous range of the input
-        for (int q = b; q < count && (pass_of[q] == pass_of[b] || (pass_of[q] < 0 && sizes[q] == 0)); ++q) if (pass_of[q] == pass_of[b]) e = q + 1;
-        std::vector<BatchBlock>& blocks = bufs[p & 1];
-        blocks.assign((size_t)(e - b), BatchBlock());
-        // LZP of every member (libbsc.cpp:263-281), in parallel; without LZP there is nothing to spread over threads
-        auto prep = [&](int i) {
-            BatchBlock& B = blocks[i];
-            const int q = b + i, n = sizes[q];
-            B.b = q; B.mode = mode; B.lz = n;
-            if (pass_of[q] < 0) return;                                          // an empty block between members
-            if (n <= LIBBSC_HEADER_SIZE) {
-                if (dev) B.store = true;                                         // its bytes come back with the pass (rate -1: L = T)
-                else results[q] = bsc_store(in_of(q), out_of(q), n, features);
-                return;
-            }
-            if (mode != (mode & 0xff)) {
-                B.lzbuf = (unsigned char*)bigbuf_get((size_t)n);
-                const int r = B.lzbuf ? lzp_compress(in_of(q), B.lzbuf, n, lzpHashSize, lzpMinLen, features) : LIBBSC_NOT_ENOUGH_MEMORY;
-                if (r < LIBBSC_NO_ERROR) { B.mode &= 0xff; bigbuf_put(B.lzbuf); B.lzbuf = nullptr; }
-                else B.lz = r;
-            }
-            if (!st && aux_rate(B.lz) < 2) { B.single = true; bigbuf_put(B.lzbuf); B.lzbuf = nullptr; return; }
-            B.sorted = true;
-        };
-        if (mode != (mode & 0xff)) run_bounded(e - b, threads, prep);
-        else for (int i = 0; i < e - b; ++i) prep(i);
-        PassLayout& PL = lays[p & 1];      // (free, as hb is)
-        PL.used = false;
-        u8* hb = c->batch_host[p & 1];     // free: the coder thread of the pass before last was joined before the previous pass's started
-        std::vector<int> psz((size_t)(e - b)), prate((size_t)(e - b));
-        std::vector<int64_t> at((size_t)(e - b) + 1, 0);                         // where block b + i's L lies in hb
-        int64_t pos = 0;
-        for (int i = 0; i < e - b; ++i) {
-            BatchBlock& B = blocks[i];
-            at[i] = pos;
-            if (dev) {                                                           // the pass is the caller's own range of HBM
-                psz[i] = sizes[b + i];
-                prate[i] = B.sorted ? (st ? 0 : aux_rate(B.lz)) : -1;
-                pos += sizes[b + i];
-                continue;
-            }
-            psz[i] = B.sorted ? B.lz : 0;
-            prate[i] = B.sorted ? (st ? 0 : aux_rate(B.lz)) : -1;
-            if (B.sorted) { memcpy(hb + pos, B.lzbuf ? B.lzbuf : in_of(B.b), (size_t)B.lz); pos += B.lz; }
-            if (B.lzbuf) { bigbuf_put(B.lzbuf); B.lzbuf = nullptr; }
-        }
-        // what the coding of the pass is made of: one block; the rest of the pass's bookkeeping; the pass in groups (model segments)
-        auto code_block = [c, &blocks, &PL, hb, at, dev, &in_of, &din_of, &out_of, results, sizes, coder, features](int i) {
-            const BatchBlock& B = blocks[i];
-            if (PL.used && (B.store || B.sorted)) {
-                const bscgpu_front_layout& Y = PL.lay;
-                for (int s = Y.blk_sub[i]; s < Y.blk_sub[i + 1]; ++s)
-                    qlfc_front_first_seen(PL.first_run + 256 * (size_t)s, Y.first_seen + 256 * (size_t)s, &Y.nsym[s]);
-                if (B.store) {                  // <= 28 bytes that rode along (L = T): its bytes are its runs
-                    unsigned char tmp[LIBBSC_HEADER_SIZE + 1];
-                    RunView V[8];
-                    front_views(&Y, i, V);
-                    if (sizes[B.b] > 0) expand_runs(V[0], 0, tmp);
-                    results[B.b] = bsc_store(tmp, out_of(B.b), sizes[B.b], features);
-                } else {
-                    const PassCoded coded{PL.rc_bytes, PL.rc_off.data(), PL.rc_res.data(), PL.rc_room.data(), !PL.pbase.empty()};
-                    results[B.b] = code_sorted_block(c, dev ? nullptr : in_of(B.b), dev ? din_of(B.b) : nullptr, out_of(B.b), sizes[B.b],
-                                                     B, nullptr, coder, features, &Y, i, (!PL.blk_state.empty() && PL.blk_state[i]) ? nullptr : PL.ps, PL.poff.data(),
-                                                     PL.rc_bytes ? &coded : nullptr, PL.pbase.empty() ? nullptr : PL.pbase.data());
-                }
-                return;
-            }
-            if (B.store) results[B.b] = bsc_store(hb + at[i], out_of(B.b), sizes[B.b], features);
-            else if (B.sorted) results[B.b] = code_sorted_block(c, dev ? nullptr : in_of(B.b), dev ? din_of(B.b) : nullptr, out_of(B.b), sizes[B.b],
-                                                                B, hb + at[i], coder, features);
-        };
-        bool finished = false;
-        auto finish_blocks = [&] {              // the sort's results into the blocks: before the first of them is coded
-            if (finished) return;
-            finished = true;
-            for (int i = 0; i < e - b; ++i) {
-                BatchBlock& B = blocks[i];
-                if (B.single) single[B.b] = 1;
-                if (dev) B.adler = adler[i];
-                if (!B.sorted) continue;
-                if (st) { B.index = stidx[i]; B.num_indexes = 0; continue; }
-                const uint32_t* I = res.data() + 16 * (size_t)i;
-                B.index = (int)I[0];
-                B.num_indexes = (B.lz - 1) / aux_rate(B.lz);
-                for (int t = 0; t < B.num_indexes; ++t) B.indexes[t] = (int)I[t + 1] - 1;
-            }
-        };
-        PassGroups& PG = groups[p & 1];
-        PG.reset();
-        // one coding group at a time per call: the previous pass's coding first, then this pass's groups as they are queued
-        auto code_groups = [code_block, &PG, &order, p, threads] {
-            order.wait_for(p);
-            std::vector<int> g;
-            while (PG.pop(g)) run_bounded((int)g.size(), threads, [&](int k) { code_block(g[k]); });
-            order.finish();
-        };
-        bool grouped = false;
-        auto start_groups = [&] {
-            grouped = true;
-            try { early_thread = std::thread(code_groups); }
-            catch (const std::system_error&) {}           // no thread to be had: the groups are coded here, after the model
-        };
-        if (pos > 0) {
-            const u8* src = dev ? din_of(b) : c->dL;
-            if (!dev && hipMemcpyAsync(c->dL, hb, (size_t)pos, hipMemcpyHostToDevice, c->stream) != hipSuccess) { rc = LIBBSC_GPU_ERROR; break; }
-            rc = st ? st_batch_device(c, src, c->dL, psz.data(), e - b, blockSorter, prate.data(), stidx.data(), dev ? adler.data() : nullptr)
-                    : bwt_batch_device(c, src, c->dL, psz.data(), e - b, prate.data(), res.data(), dev ? adler.data() : nullptr);
-            if (rc < 0) break;
-            if (front) {                            // the pass's run arrays come down instead of its L
-                // (the front end covers the whole range of the pass: with HBM input that includes members the layout is never read
-                // for — a block left to the single path rides along untransformed; correct, a little wasted work)
-                PL.bind(psz, c->front_host[p & 1], frontN);
-                rc = qlfc_front_batch(c, c->dL, PL.sizes.data(), e - b, &PL.lay, c->front_host[p & 1] + 6 * frontN);
-                if (rc < 0) break;
-                PL.used = true; ++c->cnt_front_passes;
-                PL.ps = nullptr; PL.rc_bytes = nullptr; PL.blk_state.clear(); PL.pbase.clear();
-                if (segments && PL.lay.nsub > 0 && pos >= model_min_pass && ctx_ensure_model_host(c) == LIBBSC_NO_ERROR) {
-                    // the same route segment by segment: the streams of the kept blocks land back to back, a block the device
-                    // leaves out (or whose segment no longer fits the landing buffer) is coded from its run arrays.  Coding starts
-                    // with the plan: the pass's thread takes groups of blocks as they settle (PassGroups)
-                    PL.poff.resize((size_t)PL.lay.nsub + 1);
-                    PL.blk_state.assign((size_t)(e - b), 0);
-                    PL.ps = c->model_host[p & 1];
-                    // (packed: the landing buffer in bytes, less the few a packed entry's 4-byte read may reach past a stream)
-                    if (packed_route) PL.pbase.assign((size_t)PL.lay.nsub + 1, 0);
-                    finish_blocks();
-                    struct Feed {
-                        PassGroups* G; const std::vector<BatchBlock>* blocks; const int* blk_sub; const int* state; std::vector<char> queued;
-                        void take(int b0, int b1, bool planned)
-                        {
-                            std::vector<int> g;
-                            for (int i = b0; i < b1; ++i) {
-                                const BatchBlock& B = (*blocks)[i];
-                                // the first group: what the device's model leaves out, or never sees as a segment's member
-                                const bool member = B.sorted && blk_sub[i + 1] > blk_sub[i];
-                                if (queued[i] || (planned && member && state[i] == 0)) continue;
-                                queued[i] = 1; g.push_back(i);
-                            }
-                            G->push(std::move(g));
-                        }
-                    } feed{&PG, &blocks, PL.lay.blk_sub, PL.blk_state.data(), std::vector<char>((size_t)(e - b), 0)};
-                    DcSegNote note;
-                    note.user = &feed;
-                    note.planned = [](void* u) { Feed* f = static_cast<Feed*>(u); f->take(0, (int)f->blocks->size(), true); };
-                    note.settled = [](void* u, int b0, int b1) { static_cast<Feed*>(u)->take(b0, b1, false); };
-                    start_groups();
-                    int64_t D = 0;
-                    const int mrc = devcoder_pstream_segments(c, (u32)PL.lay.m, PL.lay.nsub, PL.lay.blk_sub, e - b, PL.lay.sub_run, coder, segment_target,
-                                                              c->model_host[p & 1], packed_route ? (int64_t)c->model_host_entries * 2 - 8 : (int64_t)c->model_host_entries,
-                                                              true, PL.poff.data(), PL.blk_state.data(), &D, &note, packed_route ? PL.pbase.data() : nullptr);
-                    if (mrc < 0 && mrc != LIBBSC_NOT_SUPPORTED) { PG.close(); rc = mrc; break; }
-                    // (an arena did not fit: what is not queued yet takes the host model)
-                    if (mrc < 0) for (int i = 0; i < e - b; ++i) if (!feed.queued[i]) PL.blk_state[i] = BSCGPU_DC_FAIL_CAP;
-                    bool kept = false;
-                    for (int i = 0; i < e - b && mrc >= 0; ++i) kept = kept || (PL.lay.blk_sub[i + 1] > PL.lay.blk_sub[i] && PL.blk_state[i] == 0);
-                    ++(kept ? (fast_model ? c->cnt_model_fast_passes : c->cnt_model_passes) : (fast_model ? c->cnt_model_fast_declined : c->cnt_model_declined));
-                    feed.take(0, e - b, false);         // whatever is left
-                    PG.close();
-                } else
-                if (model && PL.lay.nsub > 0 && pos >= model_min_pass && ctx_ensure_model_host(c) == LIBBSC_NO_ERROR) {
-                    // the model behind the front end, on the same stream, before the next pass's sort; the run arrays came down all the
-                    // same: they serve a declined pass, a sub-block stored raw and the <= 28-byte blocks that rode along
-                    u32 D = 0;
-                    int pk = 0; int64_t pbytes = 0;          // packed: what the device left is the 13-bit form, pbytes of it; void: 16-bit entries as ever
-                    const int mrc = devcoder_pstream_batch(c, (u32)PL.lay.m, PL.lay.nsub, coder, &D, packed_route ? &pk : nullptr, &pbytes);
-                    if (mrc == LIBBSC_NOT_SUPPORTED) ++(fast_model ? c->cnt_model_fast_declined : c->cnt_model_declined);
-                    else if (mrc < 0) { rc = mrc; break; }
-                    else if (pk ? (size_t)pbytes + 8 <= c->model_host_entries * 2 : (size_t)D <= c->model_host_entries) {
-                        PL.poff.resize((size_t)PL.lay.nsub + 1);
-                        u16* hps = c->model_host[p & 1];     // free: as hb is
-                        const bool drc = c->device_rc != 0;  // the streams stay in HBM: one launch of the device's range coder codes them
-                        const size_t down = pk ? (size_t)pbytes : (size_t)D * 2;
-                        std::vector<uint32_t> pb(pk ? PL.poff.size() : 0);
-                        if (hipMemcpyAsync(PL.poff.data(), devcoder_batch_poff_ptr(c), PL.poff.size() * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                            (pk && hipMemcpyAsync(pb.data(), devcoder_batch_pbase_ptr(c), pb.size() * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-                            (!drc && down > 0 && hipMemcpyAsync(hps, devcoder_pstream_ptr(c, 0), down, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-                            ctx_sync(c) != hipSuccess) { rc = LIBBSC_GPU_ERROR; break; }
-                        if (pk) PL.pbase.assign(pb.begin(), pb.end());
-                        if (packed_route) ++(pk ? c->cnt_packed_passes : c->cnt_packed_void);
-                        if (drc) {
-                            rc = device_rc_pass(c, PL, reinterpret_cast<uint8_t*>(hps), c->model_host_entries * 2, coder);
-                            if (rc < 0) break;
-                            ++c->cnt_device_rc;
-                        } else PL.ps = hps;
-                        ++(fast_model ? c->cnt_model_fast_passes : c->cnt_model_passes);
-                    }
-                }
-            } else {
-                if (hipMemcpyAsync(hb, c->dL, (size_t)pos, hipMemcpyDeviceToHost, c->stream) != hipSuccess || ctx_sync(c) != hipSuccess) { rc = LIBBSC_GPU_ERROR; break; }
-                ++c->cnt_l_passes;
-            }
-        }
-        finish_blocks();
-        if (coder_thread.joinable()) coder_thread.join();
-        if (grouped) {                                    // its coding is under way (or waits here, where no thread was to be had)
-            if (early_thread.joinable()) coder_thread = std::move(early_thread);
-            else { code_groups(); }
-            b = e; ++p;
-            continue;
-        }
-        auto code_pass = [code_block, &order, n = (int)blocks.size(), threads] { run_bounded(n, threads, code_block); order.finish(); };
-        try { coder_thread = std::thread(code_pass); }
-        catch (const std::system_error&) { code_pass(); }                          // no thread to be had: code the pass here
-        b = e; ++p;
-    }
-    // the blocks of their own, beside the last pass's coding: through a pipe on this context (the GPU stage of one overlaps the host
-    // coding of the ones before it); the few it does not take (larger than the context, a too short sorter input) first, one by one
-    // (both use the context's pinned slots: never at the same time)
-    auto piped = [&](int b) { return pass_of[b] < 0 && sizes[b] <= c->max_n && (dev || sizes[b] > LIBBSC_HEADER_SIZE); };
-    for (int b = 0; b < count && rc >= 0; ++b)
-        if (single[b] && !piped(b))
-            results[b] = dev ? bscgpu_compress_device(c, din_of(b), out_of(b), sizes[b], blockSorter, coder, features)
-                             : compress_one_on_ctx(c, in_of(b), out_of(b), sizes[b], lzpHashSize, lzpMinLen, blockSorter, coder, features);
+    K.route = call_route(c, npass, K.coder);
+    K.frontN = ((size_t)c->max_n + 4096 + 4095) / 4096 * 4096;
+    K.threads = default_coder_threads();
+    K.single.assign((size_t)K.count, 0);
+    for (int b = 0; b < K.count; ++b) K.single[b] = K.pass_of[b] < 0;
+    K.res.resize((size_t)BATCH_MAX_BLOCKS * 16); K.adler.resize((size_t)BATCH_MAX_BLOCKS); K.stidx.resize((size_t)BATCH_MAX_BLOCKS);
+    return npass;
+}
+
+// The blocks of their own, beside the last pass's coding: through a pipe on this context (the GPU stage of one overlaps the host
+// coding of the ones before it); the few it does not take (larger than the context, a too short sorter input) first, one by one
+// (both use the context's pinned slots: never at the same time)
+void batch_leftovers(BatchCall& K)
+{
+    auto kind = [&](int b) { return batch_leftover(K.single[b] != 0, K.pass_of[b] >= 0, K.sizes[b], K.c->max_n, K.dev); };
+    auto one_by_one = [&](BatchLeftover k) { for (int b = 0; b < K.count; ++b) if (kind(b) == k) K.results[b] = K.alone(b); };
+    one_by_one(BATCH_LEFT_ONE_BY_ONE);
+    bool any = false;
+    for (int b = 0; b < K.count; ++b) any = any || kind(b) == BATCH_LEFT_PIPE;
+    if (!any) return;
     bscgpu_pipe* pipe = nullptr;
     constexpr int PIPE_DEPTH = 4;
-    bool any = false;
-    for (int b = 0; b < count; ++b) any = any || (single[b] && piped(b));
-    if (any && rc >= 0 && bscgpu_pipe_create(c, PIPE_DEPTH, &pipe) < 0) {
-        pipe = nullptr;                                   // no pipe: one by one
-        for (int b = 0; b < count; ++b)
-            if (single[b] && piped(b))
-                results[b] = dev ? bscgpu_compress_device(c, din_of(b), out_of(b), sizes[b], blockSorter, coder, features)
-                                 : compress_one_on_ctx(c, in_of(b), out_of(b), sizes[b], lzpHashSize, lzpMinLen, blockSorter, coder, features);
+    if (bscgpu_pipe_create(K.c, PIPE_DEPTH, &pipe) < 0) { one_by_one(BATCH_LEFT_PIPE); return; }        // no pipe: one by one
+    std::deque<std::pair<int, int>> inflight;         // (block, ticket)
+    for (int b = 0; b < K.count; ++b) {
+        if (kind(b) != BATCH_LEFT_PIPE) continue;
+        if ((int)inflight.size() >= PIPE_DEPTH) { K.results[inflight.front().first] = bscgpu_pipe_wait(pipe, inflight.front().second); inflight.pop_front(); }
+        const int t = K.dev ? bscgpu_pipe_submit(pipe, K.din_of(b), K.out_of(b), K.sizes[b], K.blockSorter, K.coder, K.features)
+                            : bscgpu_pipe_submit_host(pipe, K.in_of(b), K.out_of(b), K.sizes[b], K.lzpHashSize, K.lzpMinLen, K.blockSorter, K.coder, K.features);
+        if (t < 0) K.results[b] = t; else inflight.push_back({b, t});
     }
-    if (pipe) {
-        std::deque<std::pair<int, int>> inflight;         // (block, ticket)
-        for (int b = 0; b < count; ++b) {
-            if (!single[b] || !piped(b)) continue;
-            if ((int)inflight.size() >= PIPE_DEPTH) { results[inflight.front().first] = bscgpu_pipe_wait(pipe, inflight.front().second); inflight.pop_front(); }
-            const int t = dev ? bscgpu_pipe_submit(pipe, din_of(b), out_of(b), sizes[b], blockSorter, coder, features)
-                              : bscgpu_pipe_submit_host(pipe, in_of(b), out_of(b), sizes[b], lzpHashSize, lzpMinLen, blockSorter, coder, features);
-            if (t < 0) results[b] = t; else inflight.push_back({b, t});
-        }
-        for (auto& ft : inflight) results[ft.first] = bscgpu_pipe_wait(pipe, ft.second);
-        bscgpu_pipe_destroy(pipe);
+    for (auto& ft : inflight) K.results[ft.first] = bscgpu_pipe_wait(pipe, ft.second);
+    bscgpu_pipe_destroy(pipe);
+}
+}  // namespace
+
+static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const unsigned char* dInput, const int* sizes, int count,
+                               unsigned char* output, int* results, int lzpHashSize, int lzpMinLen, int blockSorter, int coder, int features)
+{
+    BatchCall K = {c, input, dInput, sizes, count, output, results, lzpHashSize, lzpMinLen, blockSorter, coder, features, 0,
+                   dInput != nullptr, blockSorter != LIBBSC_BLOCKSORTER_BWT, {}, {}, {}, 0, 0, {}, {}, {}, {}};
+    const int mrc = make_mode(blockSorter, coder, lzpHashSize, lzpMinLen, &K.mode);
+    if (mrc != LIBBSC_NO_ERROR) { for (int b = 0; b < count; ++b) results[b] = mrc; return LIBBSC_NO_ERROR; }
+    if (hipSetDevice(c->device) != hipSuccess) return LIBBSC_GPU_ERROR;
+    const int npass = batch_call_begin(K);
+    if (npass < 0) return npass;
+    BatchPass slots[2];
+    PassHandOff hand;
+    int rc = LIBBSC_NO_ERROR;
+    // (a negative rc ends the passes: the threads that were started code what they were given, blocks already coded keep their results)
+    for (int b = 0, p = 0; b < count && rc >= 0;) {
+        if (K.pass_of[b] < 0) { ++b; continue; }
+        const int e = batch_pass_end(K.pass_of.data(), sizes, count, b);
+        BatchPass& P = slots[p & 1];
+        P.prepare(&K, p, b, e);
+        rc = P.stage();
+        const bool sorts = rc >= 0 && P.G.pos > 0;                                 // (host input of stored blocks only: nothing to sort)
+        if (sorts) rc = P.sort();
+        if (sorts && rc >= 0) rc = K.route.front ? P.front() : P.l_down();
+        if (sorts && rc >= 0 && K.route.front)
+            switch (P.model_step()) {
+            case BATCH_MODEL_WHOLE:    rc = P.model_whole(); break;
+            case BATCH_MODEL_SEGMENTS: rc = P.model_segments(hand); break;
+            case BATCH_MODEL_NONE:     break;
+            }
+        if (rc < 0) break;
+        P.finish_blocks();
+        hand.take(P);
+        b = e; ++p;
     }
-    groups[0].close(); groups[1].close();         // (a pass that ended in an error: its thread codes what it was given and ends)
-    if (coder_thread.joinable()) coder_thread.join();
-    if (early_thread.joinable()) early_thread.join();
+    if (rc >= 0) batch_leftovers(K);
+    hand.finish(slots);
     return rc;
 }
+
 
 static int batch_args(bscgpu_ctx* c, const void* in, const int* sizes, int count, unsigned char* output, int* results)
 {

@@ -283,3 +283,145 @@ def segment_counters(dec, blk_sub, dcap, target=0, decline=(), why=4, und=None):
     r = segment_schedule(dec, [0] * len(dec) if und is None else [int(x) for x in und], blk_sub, dcap, target, sum(dec), False, False,
                          lambda b0, b1: (why if any(b0 <= b < b1 for b in decline) else 0, False, False))
     return r["kept"], r["reruns"], r["host_blocks"]
+
+
+# ---- the batched-compress driver (block.cpp: compress_batch_impl) ---------------------------------------------------------------------
+BATCH_MAX_N, BATCH_MAX_BLOCKS, HEADER_SIZE, NOT_SUPPORTED = 1 << 20, 4096, 28, -4      # include/bscgpu.h, include/libbsc.h
+BATCH_MIN_PASS, BATCH_FAST_MIN_PASS = 16 << 20, 32 << 20                               # block.cpp: BATCH_MODEL_*MIN_PASS_DEFAULT
+CODER_STATIC, CODER_FAST = 1, 3
+
+
+def aux_rate(n):
+    """the largest power of two <= n / 8, at least 1 (block.cpp: aux_rate)"""
+    m = n // 8
+    return 1 << (m.bit_length() - 1) if m > 0 else 1
+
+
+def batch_plan(sizes, sorter, cap):
+    """bscgpu_batch_plan / bscgpu_st_batch_plan (sorter 1: BWT, 3..8: ST) -> (passes, pass_of)"""
+    passes, cur, span, filled, pass_of = 0, -1, 0, 0, []
+    for n in sizes:
+        if not (sorter in (1, 3, 4, 5, 6, 7, 8) and 0 < n < BATCH_MAX_N and n <= cap):
+            pass_of.append(-1)
+            if n > 0:
+                cur = -1
+            elif cur >= 0:
+                span += 1
+            continue
+        if cur < 0 or filled + n > cap or span + 1 > BATCH_MAX_BLOCKS:
+            cur, filled, span = passes, 0, 0
+            passes += 1
+        pass_of.append(cur)
+        filled += n
+        span += 1
+    return passes, pass_of
+
+
+def batch_call(sizes, sorter, coder, cap, dev, lz, opts, facts, entries, min_pass=None, target=0, front_host=True, model_host=True):
+    """What compress_batch_impl decides for one call, written down from the function as it stood when all of it was one body — the
+    reference tools/batch_pass_probe.cpp's output is held against.
+      sizes, sorter, coder, cap (the context's max_n), dev (input in HBM); lz[b]: what LZP left of block b (its size where LZP is off
+      or gave up); opts: the context's option values front, model, fast, segments, packed, device_rc; min_pass: the environment's
+      override of the smallest modelled pass or None; target: the segment target; front_host / model_host: the pinned buffers are to
+      be had; entries: 16-bit entries a pinned stream buffer holds
+      facts[p]: what the device says of pass p (a pass that never asks takes defaults): nsub, mrc, D, pk, pbytes, blk_state
+    -> dict with the probe's keys."""
+    st = sorter != 1
+    npass, pass_of = batch_plan(sizes, sorter, cap)
+    front = npass > 0 and opts["front"] != 0 and front_host
+    fast_model = front and opts["fast"] != 0 and coder == CODER_FAST
+    model = fast_model or (front and opts["model"] != 0 and coder == CODER_STATIC)
+    model_min_pass = min_pass if min_pass is not None else BATCH_FAST_MIN_PASS if fast_model else BATCH_MIN_PASS
+    segments = model and opts["segments"] != 0 and opts["device_rc"] == 0
+    segment_target = target if segments else 0
+    packed_route = model and not fast_model and opts["packed"] != 0
+    out = dict(npass=npass, pass_of=pass_of, route=[int(front), int(model), int(fast_model), int(segments), int(packed_route),
+                                                     int(model and opts["device_rc"] != 0)],
+               min_pass=model_min_pass, target=segment_target, passes=[], error=0)
+    single = [int(p < 0) for p in pass_of]
+    count, b, p = len(sizes), 0, 0
+    while b < count:
+        if pass_of[b] < 0:
+            b += 1
+            continue
+        e = b
+        for q in range(b, count):
+            if not (pass_of[q] == pass_of[b] or (pass_of[q] < 0 and sizes[q] == 0)):
+                break
+            if pass_of[q] == pass_of[b]:
+                e = q + 1
+        cls = []
+        for q in range(b, e):
+            n = sizes[q]
+            if pass_of[q] < 0:
+                cls.append("empty")
+            elif n <= HEADER_SIZE:
+                cls.append("rides" if dev else "stored")
+            elif not st and aux_rate(lz[q]) < 2:
+                cls.append("single")
+            else:
+                cls.append("sorted")
+        psz, prate, at, pos = [], [], [], 0
+        for i, q in enumerate(range(b, e)):
+            srt = cls[i] == "sorted"
+            at.append(pos)
+            prate.append((0 if st else aux_rate(lz[q])) if srt else -1)
+            if dev:
+                psz.append(sizes[q])
+                pos += sizes[q]
+            else:
+                psz.append(lz[q] if srt else 0)
+                pos += lz[q] if srt else 0
+        cnt = dict(front=0, l=0, model=0, declined=0, fast=0, fast_declined=0, packed=0, void=0, device_rc=0)
+        row = dict(b=b, e=e, classes=cls, psz=psz, prate=prate, at=at, pos=pos, step="none", kept=0, counters=cnt)
+        out["passes"].append(row)
+        f = facts.get(p, {})
+        nsub, mrc = f.get("nsub", 0), f.get("mrc", 0)
+        ok, no = ("fast", "fast_declined") if fast_model else ("model", "declined")
+        error = 0
+        if pos > 0 and not front:
+            row["step"] = "l_down"
+            cnt["l"] += 1
+        elif pos > 0:
+            cnt["front"] += 1
+            if segments and nsub > 0 and pos >= model_min_pass and model_host:
+                row["step"] = "segments"
+                if mrc < 0 and mrc != NOT_SUPPORTED:
+                    error = mrc
+                else:
+                    state = f.get("blk_state", [0] * (e - b))
+                    kept = mrc >= 0 and any(psz[i] > 0 and state[i] == 0 for i in range(e - b))
+                    row["kept"] = int(kept)
+                    cnt[ok if kept else no] += 1
+            elif model and nsub > 0 and pos >= model_min_pass and model_host:
+                row["step"] = "whole"
+                pk = f.get("pk", 0) if packed_route else 0
+                if mrc == NOT_SUPPORTED:
+                    cnt[no] += 1
+                elif mrc < 0:
+                    error = mrc
+                elif (f.get("pbytes", 0) + 8 <= entries * 2) if pk else (f.get("D", 0) <= entries):
+                    row["kept"] = 1
+                    if packed_route:
+                        cnt["packed" if pk else "void"] += 1
+                    if opts["device_rc"] != 0:
+                        cnt["device_rc"] += 1
+                    cnt[ok] += 1
+        if error:
+            out["error"] = error
+            break
+        # what every sorted block is coded from (code_sorted_block's arguments as code_block chose them)
+        state = f.get("blk_state", [0] * (e - b)) if row["step"] == "segments" else [0] * (e - b)
+        pk = f.get("pk", 0) if packed_route else 0
+        coded = row["step"] == "whole" and row["kept"] and opts["device_rc"] != 0
+        stream = row["step"] == "segments" or (row["step"] == "whole" and row["kept"] and not coded)
+        is_packed = packed_route if row["step"] == "segments" else bool(row["kept"] and pk)
+        row["sources"] = ["" if cls[i] != "sorted" else "l" if not front else "device_rc" if coded else "runs" if not stream or state[i]
+                          else "fast" if coder == CODER_FAST else "ps13" if is_packed else "ps16" for i in range(e - b)]
+        for i, q in enumerate(range(b, e)):
+            if cls[i] == "single":
+                single[q] = 1
+        b, p = e, p + 1
+    piped = lambda q: pass_of[q] < 0 and sizes[q] <= cap and (dev or sizes[q] > HEADER_SIZE)
+    out["leftover"] = [] if out["error"] else ["none" if not single[q] else "pipe" if piped(q) else "one_by_one" for q in range(count)]
+    return out
