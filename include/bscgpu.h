@@ -539,7 +539,9 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *     _AVG_UNDECIDED       runs whose avg_rank >= 32 flag the warmed-up bracket left open (any such run declines: _FAIL_AVG — unless BSCGPU_OPT_DC_AVG_EXACT settles it)
  *     _AVG_RESOLVED        of those, the runs whose flag the exact resolve then settled (BSCGPU_OPT_DC_AVG_EXACT; 0 with the option off)
  *     _HIST_EXTENDED       runs whose run_hist bracket was still open after nine predecessors of their symbol and went on to the
- *                          extended look-back (36 .. 9216 predecessors; still open after that: _FAIL_HIST)
+ *                          extended look-back (36 .. 9216 predecessors; still open after that: _FAIL_HIST) — or, with
+ *                          BSCGPU_OPT_DC_HIST_EXACT, to the exact resolve (the same runs are counted in both modes)
+ *     _HIST_RESOLVED       of those, the runs whose run_hist the exact resolve settled (BSCGPU_OPT_DC_HIST_EXACT: all of them; 0 with the option off)
  * BSCGPU_OPT_DC_AVG_EXACT  0 (default; BSC_DC_AVG_EXACT=1 in the environment turns it on for contexts created after that) / 1: the
  *                          avg_rank flags the bracket leaves open are computed exactly on the device — every chunk of runs is walked
  *                          from each of the at most 33 values its start can have, the chunks' maps are chained, the open chunks walked
@@ -557,6 +559,15 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          (BSC_DC_REPLAY_CAND in the environment, read when a context is created: a lower cap, a test knob).  Both
  *                          coders, single blocks, passes and model segments.  Buffers on first use (1.5 bytes per byte of max_n, counted
  *                          by bscgpu_arena_bytes from then on); if they do not fit the option has no effect.  Same output.
+ * BSCGPU_OPT_DC_HIST_EXACT  0 (default; BSC_DC_HIST_EXACT=1 in the environment turns it on for contexts created after that) / 1:
+ *                          a run whose run_hist bracket is still open after nine predecessors of its symbol (a symbol whose runs stay
+ *                          in one length class of 2 to 127 bytes: tables, records, bitmaps, padding) gets its value exactly and in
+ *                          parallel instead of looking back over up to 9216 predecessors in its own lane — every chunk of 1024 runs
+ *                          in symbol-major order is walked from all 64 values run_hist can have, one per lane of a wavefront, the
+ *                          chunks' maps are chained as the avg_rank resolve's are, the chunks with open runs walked again from their
+ *                          exact start; no sync, nothing approximate, and no guard: _FAIL_HIST is never raised.  -e1 single blocks,
+ *                          passes and model segments; -e0 has no run_hist and is not affected.  Buffers on first use (0.2 byte per byte
+ *                          of max_n, counted by bscgpu_arena_bytes from then on); if they do not fit the option has no effect.  Same output.
  * BSCGPU_OPT_BATCH_FRONT    1: the passes of bscgpu_compress_batch / _batch_device run the QLFC front end of the whole pass on the GPU and
  *                          bring down its run arrays (sym, rank, start) instead of L; 0: L comes down and every block goes through
  *                          bsc_coder_compress on the host.  Same output.  Default 1 (measured: DESIGN §2b).
@@ -627,8 +638,10 @@ enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACK
        BSCGPU_CNT_BATCH_SEG_HOST_BLOCKS = 25, BSCGPU_CNT_DC_DCAP = 26,
        BSCGPU_OPT_BATCH_MODEL_PACKED = 27, BSCGPU_CNT_BATCH_PACKED_PASSES = 28, BSCGPU_CNT_BATCH_PACKED_VOID = 29,
        BSCGPU_OPT_DC_AVG_EXACT = 30, BSCGPU_CNT_DC_AVG_RESOLVED = 31,
-       BSCGPU_OPT_DC_REPLAY_EXACT = 32, BSCGPU_CNT_DC_REPLAY_RESOLVED = 33 };
-/* _FAIL_AVG: undecided avg_rank flags; _FAIL_HIST: a run_hist bracket open after 9216 predecessors; _FAIL_CAP: more runs or decisions
+       BSCGPU_OPT_DC_REPLAY_EXACT = 32, BSCGPU_CNT_DC_REPLAY_RESOLVED = 33,
+       BSCGPU_OPT_DC_HIST_EXACT = 34, BSCGPU_CNT_DC_HIST_RESOLVED = 35 };
+/* _FAIL_AVG: undecided avg_rank flags; _FAIL_HIST: a run_hist bracket open after 9216 predecessors (never with
+ * BSCGPU_OPT_DC_HIST_EXACT); _FAIL_CAP: more runs or decisions
  * than the context's arena holds; _FAIL_REPLAY: a chain whose bracket stayed open over more than 64 evaluation chunks (with
  * BSCGPU_OPT_DC_REPLAY_EXACT: only behind the resolve's guard). */
 enum { BSCGPU_DC_FAIL_AVG = 2, BSCGPU_DC_FAIL_HIST = 4, BSCGPU_DC_FAIL_CAP = 8, BSCGPU_DC_FAIL_REPLAY = 16 };

@@ -200,6 +200,7 @@ extern "C" int bscgpu_create(bscgpu_ctx** out, int device, int64_t max_n)
     { const char* e = getenv("BSC_PS13"); c->dc_p13 = (e && e[0] == '0') ? 0 : 1; }       // BSCGPU_OPT_DC_PACKED_STREAM
     { const char* e = getenv("BSC_DC_AVG_EXACT"); c->dc_avg_exact = (e && e[0] == '1') ? 1 : 0; }      // BSCGPU_OPT_DC_AVG_EXACT
     { const char* e = getenv("BSC_DC_REPLAY_EXACT"); c->dc_replay_exact = (e && e[0] == '1') ? 1 : 0; }      // BSCGPU_OPT_DC_REPLAY_EXACT
+    { const char* e = getenv("BSC_DC_HIST_EXACT"); c->dc_hist_exact = (e && e[0] == '1') ? 1 : 0; }      // BSCGPU_OPT_DC_HIST_EXACT
     { const char* e = getenv("BSC_DC_REPLAY_CAND"); const long long v = e ? atoll(e) : 0; if (v >= 1 && v <= 0xffffffffll) c->dc_replay_cand = (u32)v; }   // devcoder.hip 3': the guard
     { const char* e = getenv("BSC_BWT_FOLD"); if (e && e[0] >= '0' && e[0] <= '2' && !e[1]) c->bwt_fold = e[0] - '0'; }       // BSCGPU_OPT_BWT_FOLD
     { const char* e = getenv("BSC_UNBWT_STEP_CAP"); const long long v = e ? atoll(e) : 0; if (v >= 16 && v <= 0xffffffffll) c->ub_step_cap = (u32)v; }   // unbwt.hip
@@ -357,6 +358,7 @@ extern "C" int bscgpu_option_set(bscgpu_ctx* c, int key, int value)
     if (key == BSCGPU_OPT_DC_PACKED_STREAM && (value == 0 || value == 1)) { const int old = c->dc_p13; c->dc_p13 = value; return old; }
     if (key == BSCGPU_OPT_DC_AVG_EXACT && (value == 0 || value == 1)) { const int old = c->dc_avg_exact; c->dc_avg_exact = value; return old; }
     if (key == BSCGPU_OPT_DC_REPLAY_EXACT && (value == 0 || value == 1)) { const int old = c->dc_replay_exact; c->dc_replay_exact = value; return old; }
+    if (key == BSCGPU_OPT_DC_HIST_EXACT && (value == 0 || value == 1)) { const int old = c->dc_hist_exact; c->dc_hist_exact = value; return old; }
     if (key == BSCGPU_OPT_BATCH_FRONT && (value == 0 || value == 1)) { const int old = c->batch_front; c->batch_front = value; return old; }
     if (key == BSCGPU_OPT_DEVICE_RC && (value == 0 || value == 1)) { const int old = c->device_rc; c->device_rc = value; return old; }
     if (key == BSCGPU_OPT_BATCH_MODEL && (value == 0 || value == 1)) { const int old = c->batch_model; c->batch_model = value; return old; }
@@ -380,6 +382,8 @@ extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
     if (key == BSCGPU_CNT_DC_AVG_RESOLVED) return c->dc_avg_resolved;
     if (key == BSCGPU_OPT_DC_REPLAY_EXACT) return c->dc_replay_exact;
     if (key == BSCGPU_CNT_DC_REPLAY_RESOLVED) return c->dc_replay_resolved;
+    if (key == BSCGPU_OPT_DC_HIST_EXACT) return c->dc_hist_exact;
+    if (key == BSCGPU_CNT_DC_HIST_RESOLVED) return c->dc_hist_resolved;
     if (key == BSCGPU_OPT_BATCH_FRONT) return c->batch_front;
     if (key == BSCGPU_CNT_BATCH_FRONT_PASSES) return c->cnt_front_passes;
     if (key == BSCGPU_CNT_BATCH_L_PASSES) return c->cnt_l_passes;

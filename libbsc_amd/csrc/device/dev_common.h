@@ -155,7 +155,8 @@ struct bscgpu_ctx {
     int  os_retries = 0;             // transforms redone through the three-kernel passes after a give-up (bscgpu_debug_counter)
     int  dc_avg_exact = 0;           // BSCGPU_OPT_DC_AVG_EXACT: open avg_rank flags are resolved exactly on the device (BSC_DC_AVG_EXACT=1)
     int  dc_replay_exact = 0;        // BSCGPU_OPT_DC_REPLAY_EXACT: open chunk starts of the evaluation are resolved exactly (BSC_DC_REPLAY_EXACT=1)
-    u32  dc_replay_cand = 0;         // ... the widest start bracket that resolve walks, if BSC_DC_REPLAY_CAND sets one (a test knob); 0: DC_RP_CAND.  devcoder_rp_ensure clamps it to DC_RP_CAND
+    int  dc_hist_exact = 0;          // BSCGPU_OPT_DC_HIST_EXACT: open run_hist brackets are resolved exactly on the device (BSC_DC_HIST_EXACT=1)
+    u32  dc_replay_cand = 0;        // ... the widest start bracket that resolve walks, if BSC_DC_REPLAY_CAND sets one (a test knob); 0: DC_RP_CAND.  devcoder_rp_ensure clamps it to DC_RP_CAND
     int  dc_p13 = 1;                 // BSCGPU_OPT_DC_PACKED_STREAM: the static coder's p stream leaves as 13 bits per decision (BSC_PS13=0: 16-bit entries)
     bool os_gave_up = false;         // radix_onesweep_check found a give-up: the caller may redo its sorts through the three-kernel passes
     // BWT first sort: the leftover low digit of the key is sorted by key packing (bwt.hip: bwt_pack_fold_kernel)
@@ -179,6 +180,7 @@ struct bscgpu_ctx {
     int      dc_avg_resolved = 0; // ... of those, the runs the exact resolve settled (BSCGPU_OPT_DC_AVG_EXACT)
     int      dc_replay_resolved = 0; // chunks whose start the exact resolve settled (BSCGPU_OPT_DC_REPLAY_EXACT)
     int      dc_hist_ext = 0;    // runs whose run_hist bracket was still open after nine predecessors (the extended look-back)
+    int      dc_hist_resolved = 0; // ... of those, the runs the exact resolve settled (BSCGPU_OPT_DC_HIST_EXACT)
 
     // profiling
     bool         prof        = false;

@@ -10,7 +10,8 @@
 //
 //   1. contexts      avg_rank >= 32 flags (two-sided bracket walk with warm-up), per-run packed items; a stable 8-bit
 //                    radix pass by symbol gives the symbol-major order in which "previous run of the same symbol"
-//                    (rank_hist / run_hist, qlfc.cpp:900, :981-987) is the neighbouring element; context states from the
+//                    (rank_hist / run_hist, qlfc.cpp:900, :981-987) is the neighbouring element (run_hist: a bracket over the
+//                    nine nearest such runs, then a longer look-back or, with BSCGPU_OPT_DC_HIST_EXACT, the exact resolve 1c'); context states from the
 //                    reference's two state tables; two more radix passes order the runs by rank-state and by run-state.
 //   2. partition     for each family (static: stream order; char: symbol-major; state: state-major) the decisions of the
 //                    runs, generated on the fly round by round (64 runs per wavefront, ballot-match ranking, no atomics on
@@ -27,7 +28,8 @@
 //
 // The host (qlfc.cpp: encode_from_pstream) then runs only the range coder.  Whenever something is outside what this path
 // handles exactly (an avg_rank bracket that does not decide — unless BSCGPU_OPT_DC_AVG_EXACT has the open flags computed exactly,
-// 1a' —, a run_hist bracket still open after 9216 predecessors, a chain whose
+// 1a' —, a run_hist bracket still open after 9216 predecessors — unless BSCGPU_OPT_DC_HIST_EXACT has the open brackets computed
+// exactly, 1c', which leaves none —, a chain whose
 // bracket stays open over more than 64 evaluation chunks — unless BSCGPU_OPT_DC_REPLAY_EXACT has the open chunk starts computed
 // exactly, 3' —, capacity), a flag is raised and the caller falls back to the host model;
 // nothing approximate is ever emitted.
@@ -71,7 +73,8 @@ constexpr int DC_WCH_MAX  = 4096;      // wave-chunks of a partition job (one wa
 // meta scalars (device u32 array)
 enum { DM_FAIL = 0, DM_NTYPES, DM_NROUNDS, DM_AVG_UND, DM_REPLAYS, DM_D0, DM_D1, DM_D2, DM_D3, DM_HIST_EXT /* runs that entered the extended run_hist look-back */, DM_P13_OVER /* a wavefront's piece did not fit the staging buffer: the packed stream is void */,
        DM_AVG_RESOLVED /* exact resolve: flags the bracket left open and the resolve settled */, DM_AVG_LEFT /* ... and did not (the guard) */,
-       DM_REPLAY_RESOLVED /* open chunk starts the exact resolve settled (3') */, DM_COUNT = 16 };
+       DM_REPLAY_RESOLVED /* open chunk starts the exact resolve settled (3') */,
+       DM_HIST_RESOLVED /* runs whose open run_hist bracket the exact resolve settled (1c') */, DM_COUNT = 16 };
 // (bit 0 is not in use: every decision type has a row of its own, DC_ROWS >= NUM_TAU, so no number of types is too many)
 enum { FAIL_AVG = BSCGPU_DC_FAIL_AVG, FAIL_HIST = BSCGPU_DC_FAIL_HIST, FAIL_CAP = BSCGPU_DC_FAIL_CAP, FAIL_REPLAY = BSCGPU_DC_FAIL_REPLAY };
 
@@ -86,6 +89,20 @@ struct DcAvgRec {
     u16* ex;        // per chunk: the exact avg_rank at its first run, or DC_AVG_UNKNOWN
     u8*  map;       // per chunk, DC_AVG_CAND bytes: map[v] = avg_rank at the next chunk's first run, had this one started at lo0 + v
     u16* gmap;      // per group of DC_AVG_GROUP chunks, DC_AVG_CAND entries: the same across the group, from its first chunk's candidates
+    u16* gstart;    // per group: the exact start of its first chunk
+};
+
+// what the exact resolve of open run_hist brackets keeps (1c'): per symbol-major element, per chunk of DC_HIST_CH elements and per group
+// of DC_HIST_GROUP chunks; map, gmap, gstart and ex in the avg_rank resolve's format, whose chain and groups kernels walk them
+struct DcHistRec {
+    const u32* ext; // DM_HIST_EXT: runs the nine predecessors left open — zero: every kernel behind dc_ctx_kernel leaves at once
+    u32* bits;      // per element: a bit, set where the run is open
+    u8*  flag;      // per chunk: it holds an open run
+    u64* scr;       // per open element: its run j << 13 | run_state_index with run_hist 0 (key_sn_s, which nobody writes before the
+                    // run-state radix pass behind this stage)
+    u16* ex;        // per chunk: run_hist in front of its first element
+    u8*  map;       // per chunk, DC_HIST_CAND bytes: map[v] = run_hist in front of the next chunk's first element, had this one started at v
+    u16* gmap;      // per group, DC_HIST_CAND entries: the same across the group
     u16* gstart;    // per group: the exact start of its first chunk
 };
 
@@ -130,6 +147,10 @@ struct DevCoder {
     // 2 DC_RP_CAND bytes of map, the head's end and a state byte — 771 bytes per slot, 1.5 bytes per byte of max_n (101 MB for 64 MiB)
     char* rp_arena = nullptr; size_t rp_bytes = 0; bool rp_alloc_failed = false;
     struct DcRpRec* rp = nullptr;
+    // the exact resolve of open run_hist brackets (BSCGPU_OPT_DC_HIST_EXACT), allocated on its first use: a bit per run, 67 bytes per chunk
+    // of DC_HIST_CH runs, 130 per group of DC_HIST_GROUP chunks — 0.2 byte per byte of max_n
+    char* hist_arena = nullptr; size_t hist_bytes = 0; bool hist_alloc_failed = false;
+    DcHistRec hist = {};
 };
 
 __device__ __forceinline__ u32 dc_sb_of(u32 j, const DcSub& S)
@@ -306,6 +327,14 @@ __global__ __launch_bounds__(WG) void dc_avg_map_kernel(const u8* __restrict__ r
     if (lane <= w) R.map[(size_t)c * DC_AVG_CAND + lane] = (u8)x;
 }
 
+// what the chain and groups kernels below read of a chunk, for the two resolves that share them: its start bracket (lo0 | hi0 << 8), its
+// state, and whether there is anything to do at all
+__device__ __forceinline__ u32 dc_rs_brk(const DcAvgRec& R, u32 c) { return R.brk[c]; }
+__device__ __forceinline__ u32 dc_rs_st(const DcAvgRec& R, u32 c) { return R.st[c]; }
+__device__ __forceinline__ bool dc_rs_idle(const DcAvgRec&) { return false; }
+__device__ __forceinline__ u32 dc_rs_brk(const DcHistRec&, u32) { return (u32)(DC_HIST_CAND - 1) << 8; }      // [0, 63] everywhere: nothing restarts the chain but the maps
+__device__ __forceinline__ u32 dc_rs_st(const DcHistRec&, u32) { return 0u; }
+__device__ __forceinline__ bool dc_rs_idle(const DcHistRec& R) { return *R.ext == 0u; }
 // the exact start of chunk c + 1 from the exact start x of chunk c; brk1 / brk0 / st0: of chunk c + 1 / c / c, map0: chunk c's map
 __device__ __forceinline__ u32 dc_avg_step(u32 x, u32 brk1, u32 brk0, u32 st0, const u8* map0)
 {
@@ -317,16 +346,19 @@ __device__ __forceinline__ u32 dc_avg_step(u32 x, u32 brk1, u32 brk0, u32 st0, c
 // One wavefront per group of DC_AVG_GROUP chunks, their maps in LDS.  HAND = false: lane v follows candidate v of the group's first
 // chunk through the group -> gmap[g][v], the start of the next group's first chunk (only where that one starts open).  HAND = true:
 // every lane follows the group's exact start (gstart[g]) and lane k keeps what chunk k starts from -> ex.
-template <bool HAND>
-__global__ __launch_bounds__(64) void dc_avg_chain_kernel(u32 m, DcAvgRec R)
+// REC: whose maps they are.  DcAvgRec: the avg_rank resolve's; DcHistRec: the run_hist resolve's (1c') — the same map format, 64 byte
+// entries from base 0, every chunk open over the whole range, no state, and nothing to do where no run is open (dc_rs_*)
+template <bool HAND, class REC = DcAvgRec>
+__global__ __launch_bounds__(64) void dc_avg_chain_kernel(u32 m, REC R)
 {
     static_assert(DC_AVG_GROUP == 64 && DC_AVG_CAND == 64, "one chunk and one candidate per lane");
     __shared__ u32 brk_s[DC_AVG_GROUP + 1], st_s[DC_AVG_GROUP];
     __shared__ uint4 map_s[DC_AVG_GROUP * DC_AVG_CAND / 16];
+    if (dc_rs_idle(R)) return;
     const u32 g = blockIdx.x, lane = threadIdx.x, c0 = g * DC_AVG_GROUP;
     const u32 nch = (m + DC_AVG_CH - 1) / DC_AVG_CH;
     const u32 cnt = nch - c0 < (u32)DC_AVG_GROUP ? nch - c0 : (u32)DC_AVG_GROUP;      // chunks of this group
-    const u32 mine = lane < cnt ? (u32)R.brk[c0 + lane] : 0u;
+    const u32 mine = lane < cnt ? dc_rs_brk(R, c0 + lane) : 0u;
     if constexpr (HAND) {
         if (__ballot(lane < cnt && (mine & 255u) != (mine >> 8)) == 0ull) {         // every chunk starts exact
             if (lane < cnt) R.ex[c0 + lane] = (u16)(mine & 255u);
@@ -334,11 +366,11 @@ __global__ __launch_bounds__(64) void dc_avg_chain_kernel(u32 m, DcAvgRec R)
         }
     } else {
         if (c0 + DC_AVG_GROUP >= nch) return;
-        const u32 bn = R.brk[c0 + DC_AVG_GROUP];
+        const u32 bn = dc_rs_brk(R, c0 + DC_AVG_GROUP);
         if ((bn & 255u) == (bn >> 8)) return;
     }
-    brk_s[lane] = mine; st_s[lane] = lane < cnt ? (u32)R.st[c0 + lane] : 0u;
-    if (lane == 0) brk_s[DC_AVG_GROUP] = c0 + DC_AVG_GROUP < nch ? (u32)R.brk[c0 + DC_AVG_GROUP] : 0u;
+    brk_s[lane] = mine; st_s[lane] = lane < cnt ? dc_rs_st(R, c0 + lane) : 0u;
+    if (lane == 0) brk_s[DC_AVG_GROUP] = c0 + DC_AVG_GROUP < nch ? dc_rs_brk(R, c0 + DC_AVG_GROUP) : 0u;
     const uint4* src = reinterpret_cast<const uint4*>(R.map + (size_t)c0 * DC_AVG_CAND);
 #pragma unroll
     for (int k = 0; k < 4; ++k) map_s[k * 64 + lane] = src[k * 64 + lane];            // (the arrays are padded to whole groups)
@@ -356,23 +388,25 @@ __global__ __launch_bounds__(64) void dc_avg_chain_kernel(u32 m, DcAvgRec R)
     else R.gmap[(size_t)g * DC_AVG_CAND + lane] = (u16)x;
 }
 // the groups chained: one wavefront, 64 groups' maps at a time in LDS, the walk itself on one value
-__global__ __launch_bounds__(64) void dc_avg_groups_kernel(u32 m, DcAvgRec R)
+template <class REC = DcAvgRec>
+__global__ __launch_bounds__(64) void dc_avg_groups_kernel(u32 m, REC R)
 {
     __shared__ u32 first_s[65], wide_s[64];
     __shared__ uint4 gmap_s[64 * DC_AVG_CAND * 2 / 16];
+    if (dc_rs_idle(R)) return;
     const u32 lane = threadIdx.x;
     const u32 nch = (m + DC_AVG_CH - 1) / DC_AVG_CH, ngr = (nch + DC_AVG_GROUP - 1) / DC_AVG_GROUP;
-    u32 x = (u32)R.brk[0] & 255u;                                      // (chunk 0 starts a sub-block)
+    u32 x = dc_rs_brk(R, 0) & 255u;                                    // (chunk 0 starts a sub-block)
     for (u32 g0 = 0; g0 < ngr; g0 += 64u) {
         const u32 cnt = ngr - g0 < 64u ? ngr - g0 : 64u;
         // lane i: group g0 + i, and the first chunk of the group behind it
-        const u32 nf = g0 + lane + 1 < ngr ? (u32)R.brk[(g0 + lane + 1) * DC_AVG_GROUP] : 0u;
+        const u32 nf = g0 + lane + 1 < ngr ? dc_rs_brk(R, (g0 + lane + 1) * DC_AVG_GROUP) : 0u;
         const bool any_open = __ballot((nf & 255u) != (nf >> 8)) != 0ull;
         __syncthreads();
         first_s[lane + 1] = nf;
         if (any_open) {
-            if (lane == 0) first_s[0] = (u32)R.brk[g0 * DC_AVG_GROUP];
-            wide_s[lane] = lane < cnt ? (u32)R.st[(g0 + lane) * DC_AVG_GROUP] & DC_AVG_ST_WIDE : 0u;
+            if (lane == 0) first_s[0] = dc_rs_brk(R, g0 * DC_AVG_GROUP);
+            wide_s[lane] = lane < cnt ? dc_rs_st(R, (g0 + lane) * DC_AVG_GROUP) & DC_AVG_ST_WIDE : 0u;
             const uint4* src = reinterpret_cast<const uint4*>(R.gmap + (size_t)g0 * DC_AVG_CAND);
 #pragma unroll
             for (int k = 0; k < 8; ++k) gmap_s[k * 64 + lane] = src[k * 64 + lane];    // (padded to 64 groups)
@@ -484,10 +518,15 @@ __global__ __launch_bounds__(WG) void dc_items_kernel(const u8* __restrict__ sym
 constexpr u32 DC_KIND_RUN = 8 * 512, DC_KIND_WORDS = (DC_KIND_RUN + 96 + 31) / 32;
 
 // 1c. context states + the state family's items + which kinds of run occur.  Thread per run (stream order).
-template <class SB>
+// REC (the exact resolve of open run_hist brackets, 1c'): a run whose bracket the nine predecessors leave open does not look further
+// back — it keeps the lower end for now and leaves what dc_hist_fix_kernel rewrites its run-state from (DcHistRec).  Off: the empty
+// DcHistNoRec, the kernel as it was.
+struct DcHistNoRec {};
+template <class SB, bool REC = false>
 __global__ __launch_bounds__(WG) void dc_ctx_kernel(const u64* __restrict__ key_ch, const u64* __restrict__ key_ch_s, const u32* __restrict__ inv_ch,
                                                     u32 m, SB S, const u8* __restrict__ tab_rank, const u8* __restrict__ tab_run,
-                                                    u64* __restrict__ key_sr, u64* __restrict__ key_sn, u32* __restrict__ present, u32* __restrict__ meta)
+                                                    u64* __restrict__ key_sr, u64* __restrict__ key_sn, u32* __restrict__ present, u32* __restrict__ meta,
+                                                    typename std::conditional<REC, DcHistRec, DcHistNoRec>::type R)
 {
     __shared__ u32 bits[DC_KIND_WORDS];
     for (u32 i = threadIdx.x; i < DC_KIND_WORDS; i += WG) bits[i] = 0;
@@ -548,7 +587,14 @@ __global__ __launch_bounds__(WG) void dc_ctx_kernel(const u64* __restrict__ key_
 #pragma unroll
             for (int t = NP; t >= 1; --t) if (t <= np) { lo = run_hist_next(lo, prun[t - 1]); hi = run_hist_next(hi, prun[t - 1]); }
             u32 cl = lo < 7u ? lo : 7u, ch = hi < 7u ? hi : 7u;
-            if (cl != ch) {
+            if constexpr (REC) {
+                if (cl != ch) {                                       // open: the lower end for now, the rest is dc_hist_fix_kernel's
+                    atomicAdd(&meta[DM_HIST_EXT], 1u);
+                    R.scr[q] = (u64)j << 13 | run_state_index(ctx_rank0, ctx_run, it.rank, 0u);
+                    atomicOr(&R.bits[q >> 5], 1u << (q & 31u));
+                    R.flag[q / (u32)DC_HIST_CH] = 1;
+                }
+            } else if (cl != ch) {
                 // rare: look further back (quadrupling) until the clamped values agree or the chain starts
                 atomicAdd(&meta[DM_HIST_EXT], 1u);
                 u32 K = 4 * NP;
@@ -587,6 +633,108 @@ __global__ __launch_bounds__(WG) void dc_ctx_kernel(const u64* __restrict__ key_
         const u32 mine = bits[i];
         if (mine) { const u32 need = mine & ~__builtin_nontemporal_load(&present[i]); if (need) atomicOr(&present[i], need); }
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// 1c'. the open run_hist brackets resolved exactly (BSCGPU_OPT_DC_HIST_EXACT; devcoder_model.h: hist_resolve_host restates these
+// kernels).  h' = (h + inc) >> 2 is monotone in h and contracts by four — for a <= b the images are at most floor((b - a + 3) / 4)
+// apart, so a bracket's width goes 63 -> 16 -> 4 -> 1 and stays at 1 wherever the class of the runs has two fixed points (runs of 2 to
+// 127 bytes) — and [0, 63] is invariant: (63 + 93) >> 2 = 39.  So one wavefront walks a chunk of the symbol-major array from ALL 64
+// values, one per lane: dc_hist_map_kernel.  The maps have the avg_rank resolve's format and are composed, chained and handed out by
+// its kernels (dc_avg_chain_kernel<false>, dc_avg_groups_kernel, dc_avg_chain_kernel<true>, over DcHistRec); dc_hist_fix_kernel walks
+// the chunks that hold an open run again from their exact start.  No guard: 64 candidates are the whole range, FAIL_HIST is never raised.
+// All of them leave at once where no run is open.
+// ---------------------------------------------------------------------------------------------------------------------
+// a lane's 16 elements from `at` on, a byte each: the increment (at most 3 * 30 + 3) | 128 where the element starts a chain
+template <class F>
+__device__ __forceinline__ void dc_hist_load(const u64* __restrict__ key_ch_s, u32 at, u32 m, u32 q[4])
+{
+    u64 prev = (at > 0u && at <= m) ? key_ch_s[at - 1u] : 0ull;
+#pragma unroll
+    for (u32 k = 0; k < 4u; ++k) {
+        q[k] = 0;
+#pragma unroll
+        for (u32 i = 0; i < 4u; ++i) {
+            const u32 p = at + 4u * k + i;
+            if (p < m) {
+                const u64 key = key_ch_s[p];
+                const u32 b = run_hist_inc(F::unpack(key).run) | ((p == 0u || (key >> F::CHAIN_SHIFT) != (prev >> F::CHAIN_SHIFT)) ? 128u : 0u);
+                q[k] |= b << (8u * i);
+                prev = key;
+            }
+        }
+    }
+}
+__device__ __forceinline__ u32 dc_hist_step(u32 x, u32 b) { return (((b & 128u) ? 0u : x) + (b & 127u)) >> 2; }
+// one wavefront per whole chunk (the last chunk has no successor); lane v walks from v.  The bytes are handed round the wavefront as
+// scalars: every lane walks the same elements
+template <class SB>
+__global__ __launch_bounds__(WG) void dc_hist_map_kernel(const u64* __restrict__ key_ch_s, u32 m, DcHistRec R)
+{
+    static_assert(DC_HIST_CAND == 64 && DC_HIST_CH == 64 * 16, "one candidate and 16 elements per lane");
+    if (*R.ext == 0u) return;
+    const u32 c = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * WAVES + (threadIdx.x >> 6)));
+    const u32 lane = threadIdx.x & 63u;
+    const u32 nch = (m + DC_HIST_CH - 1) / DC_HIST_CH;
+    if (c + 1 >= nch) return;
+    u32 q[4];
+    dc_hist_load<DcForm<SB>>(key_ch_s, c * DC_HIST_CH + 16u * lane, m, q);
+    u32 x = lane;
+    for (u32 l = 0; l < 64u; ++l) {
+        u32 r[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[k] = (u32)__builtin_amdgcn_readlane((int)q[k], (int)l);
+#pragma unroll
+        for (u32 k = 0; k < 16u; ++k) x = dc_hist_step(x, (r[k >> 2] >> (8u * (k & 3u))) & 255u);
+    }
+    R.map[(size_t)c * DC_HIST_CAND + lane] = (u8)x;
+}
+// one wavefront per chunk that holds an open run: again from its exact start, every lane on the same values, lane l keeping min(h, 7)
+// of elements 16 l ..; then every lane rewrites the run-state of its open elements (the state byte of key_sn[j]; key_sr does not
+// depend on run_hist)
+template <class SB>
+__global__ __launch_bounds__(WG) void dc_hist_fix_kernel(const u64* __restrict__ key_ch_s, u32 m, const u8* __restrict__ tab_run, u64* __restrict__ key_sn,
+                                                         u32* __restrict__ meta, DcHistRec R)
+{
+    if (*R.ext == 0u) return;
+    const u32 c = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * WAVES + (threadIdx.x >> 6)));
+    const u32 lane = threadIdx.x & 63u;
+    const u32 nch = (m + DC_HIST_CH - 1) / DC_HIST_CH;
+    if (c >= nch || R.flag[c] == 0) return;
+    const u32 at = c * DC_HIST_CH + 16u * lane;                        // (the last chunk may end inside or in front of these: bytes of 0)
+    u32 q[4];
+    dc_hist_load<DcForm<SB>>(key_ch_s, at, m, q);
+    u32 x = R.ex[c];
+    u32 mine[2] = {0u, 0u};                                           // four bits per element
+    for (u32 l = 0; l < 64u; ++l) {
+        u32 r[4], v[2] = {0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[k] = (u32)__builtin_amdgcn_readlane((int)q[k], (int)l);
+#pragma unroll
+        for (u32 k = 0; k < 16u; ++k) {
+            const u32 b = (r[k >> 2] >> (8u * (k & 3u))) & 255u;
+            if (b & 128u) x = 0;
+            v[k >> 3] |= (x < 7u ? x : 7u) << (4u * (k & 7u));
+            x = (x + (b & 127u)) >> 2;
+        }
+        if (lane == l) { mine[0] = v[0]; mine[1] = v[1]; }
+    }
+    const u32 open = (R.bits[at >> 5] >> (at & 31u)) & 0xffffu;        // (16 elements: half a word; no bit is set at or behind m)
+    u32 n = 0;
+#pragma unroll
+    for (u32 k = 0; k < 16u; ++k) {
+        bool done = false;
+        if (open >> k & 1u) {
+            const u64 s = R.scr[at + k];
+            const u32 j = (u32)(s >> 13);
+            if (j < m) {
+                reinterpret_cast<u8*>(key_sn + j)[7] = tab_run[((u32)s & 8191u) | ((mine[k >> 3] >> (4u * (k & 7u))) & 7u)];
+                done = true;
+            }
+        }
+        n += (u32)__popcll(__ballot(done));
+    }
+    if (lane == 0 && n) atomicAdd(&meta[DM_HIST_RESOLVED], n);
 }
 
 // 1d. the canonical rounds that occur (and how many decision types: diagnostics).  One workgroup.
@@ -1874,6 +2022,7 @@ void devcoder_destroy(bscgpu_ctx* c)
     if (d->avg_arena) hipFree(d->avg_arena);
     if (d->rp_arena) hipFree(d->rp_arena);
     delete d->rp;
+    if (d->hist_arena) hipFree(d->hist_arena);
     for (int k = 0; k < 2; ++k) if (d->seg_ev[k]) hipEventDestroy(d->seg_ev[k]);
     if (d->hmeta) hipHostFree(d->hmeta);
     delete d;
@@ -1973,7 +2122,7 @@ int devcoder_ensure(bscgpu_ctx* c)
 }
 
 int64_t devcoder_arena_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)c->dc->arena_bytes : 0; }
-int64_t devcoder_batch_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)(c->dc->batch_bytes + c->dc->avg_bytes + c->dc->rp_bytes) : 0; }
+int64_t devcoder_batch_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)(c->dc->batch_bytes + c->dc->avg_bytes + c->dc->rp_bytes + c->dc->hist_bytes) : 0; }
 
 // One partition job: counts, scans, scatter.  SCATTER = false: counts and scans only, then the runs' offsets in the stream
 // (dc_doff_kernel) — all the fast coder needs of job 0, whose events nobody reads.
@@ -2004,6 +2153,7 @@ static void dc_note_block(bscgpu_ctx* c, const DevCoder* d)
     c->dc_hist_ext = (int)d->hmeta[DM_HIST_EXT];
     c->dc_avg_resolved = (int)d->hmeta[DM_AVG_RESOLVED];
     c->dc_replay_resolved = (int)d->hmeta[DM_REPLAY_RESOLVED];
+    c->dc_hist_resolved = (int)d->hmeta[DM_HIST_RESOLVED];
 }
 
 // ---- the avg_rank flags of m runs (1a), and with BSCGPU_OPT_DC_AVG_EXACT the exact resolve behind them (1a') ---------------------------
@@ -2044,9 +2194,59 @@ static int dc_launch_avg(bscgpu_ctx* c, DevCoder* d, const u8* drank, u32 m, con
     hipLaunchKernelGGL((dc_avg_kernel<SB, true>), dim3((nch + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta, (u32*)nullptr, d->avg);
     if (nch > 1) hipLaunchKernelGGL(dc_avg_map_kernel<SB>, dim3((nch - 1 + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, drank, m, S, d->avg);
     if (ngr > 1) hipLaunchKernelGGL(dc_avg_chain_kernel<false>, dim3(ngr - 1), dim3(64), 0, c->stream, m, d->avg);
-    hipLaunchKernelGGL(dc_avg_groups_kernel, dim3(1), dim3(64), 0, c->stream, m, d->avg);
+    hipLaunchKernelGGL(dc_avg_groups_kernel<>, dim3(1), dim3(64), 0, c->stream, m, d->avg);
     hipLaunchKernelGGL(dc_avg_chain_kernel<true>, dim3(ngr), dim3(64), 0, c->stream, m, d->avg);
     hipLaunchKernelGGL(dc_avg_fix_kernel<SB>, dim3((nch + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta, sub_und, d->avg);
+    return BSC_NO_ERROR;
+}
+
+// ---- the exact resolve of open run_hist brackets (1c') ---------------------------------------------------------------------------------
+// Its buffers, on the first static model that asks for it.  Do not fit: the option stays without effect (dc_ctx_kernel<SB> with its
+// look-back, as with the option off) — not an error, and not retried.
+static bool devcoder_hist_ensure(DevCoder* d)
+{
+    if (d->hist_arena) return true;
+    if (d->hist_alloc_failed) return false;
+    // chunks padded to whole groups, groups to the 64 that dc_avg_groups_kernel loads at a time; a bit per element of the padded chunks
+    const size_t NC = (d->Mcap / DC_HIST_CH + 1 + DC_HIST_GROUP) / DC_HIST_GROUP * DC_HIST_GROUP + DC_HIST_GROUP, NG = (NC / DC_HIST_GROUP + 64) / 64 * 64 + 64;
+    struct Carve { void** p; size_t bytes; };
+    Carve carve[] = {
+        {(void**)&d->hist.bits, NC * DC_HIST_CH / 8}, {(void**)&d->hist.flag, NC}, {(void**)&d->hist.ex, 2 * NC},
+        {(void**)&d->hist.map, (size_t)DC_HIST_CAND * NC}, {(void**)&d->hist.gmap, 2 * (size_t)DC_HIST_CAND * NG}, {(void**)&d->hist.gstart, 2 * NG},
+    };
+    size_t total = 0;
+    for (auto& cv : carve) total += dc_align(cv.bytes);
+    if (hipMalloc((void**)&d->hist_arena, total) != hipSuccess) {
+        (void)hipGetLastError(); d->hist_arena = nullptr; d->hist_alloc_failed = true;
+        return false;
+    }
+    d->hist_bytes = total;
+    size_t off = 0;
+    for (auto& cv : carve) { *cv.p = d->hist_arena + off; off += dc_align(cv.bytes); }
+    d->hist.ext = d->meta + DM_HIST_EXT; d->hist.scr = d->key_sn_s;
+    return true;
+}
+// The context states of m runs (1c), and with the resolve behind them (1c').  No sync: the resolve's kernels are launched whether or
+// not a run is open, and leave at once where none is.
+template <class SB>
+static int dc_launch_ctx(bscgpu_ctx* c, DevCoder* d, u32 m, const SB& S)
+{
+    const u32 gm8 = ((m + WG - 1) / WG + 7u) / 8u * 8u;                // (dc_virtual_block())
+    if (!(c->dc_hist_exact && devcoder_hist_ensure(d))) {
+        hipLaunchKernelGGL(dc_ctx_kernel<SB>, dim3(gm8), dim3(WG), 0, c->stream, d->key_ch, d->key_ch_s, d->inv_ch, m, S, d->tab_rank, d->tab_run,
+                           d->key_sr, d->key_sn, d->present, d->meta, DcHistNoRec{});
+        return BSC_NO_ERROR;
+    }
+    const u32 nch = (m + DC_HIST_CH - 1) / DC_HIST_CH, ngr = (nch + DC_HIST_GROUP - 1) / DC_HIST_GROUP;
+    HIP_TRY(c, hipMemsetAsync(d->hist.bits, 0, (size_t)nch * DC_HIST_CH / 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d->hist.flag, 0, nch, c->stream));
+    hipLaunchKernelGGL((dc_ctx_kernel<SB, true>), dim3(gm8), dim3(WG), 0, c->stream, d->key_ch, d->key_ch_s, d->inv_ch, m, S, d->tab_rank, d->tab_run,
+                       d->key_sr, d->key_sn, d->present, d->meta, d->hist);
+    if (nch > 1) hipLaunchKernelGGL(dc_hist_map_kernel<SB>, dim3((nch - 1 + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, d->key_ch_s, m, d->hist);
+    if (ngr > 1) hipLaunchKernelGGL((dc_avg_chain_kernel<false, DcHistRec>), dim3(ngr - 1), dim3(64), 0, c->stream, m, d->hist);
+    hipLaunchKernelGGL(dc_avg_groups_kernel<DcHistRec>, dim3(1), dim3(64), 0, c->stream, m, d->hist);
+    hipLaunchKernelGGL((dc_avg_chain_kernel<true, DcHistRec>), dim3(ngr), dim3(64), 0, c->stream, m, d->hist);
+    hipLaunchKernelGGL(dc_hist_fix_kernel<SB>, dim3((nch + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, d->key_ch_s, m, d->tab_run, d->key_sn, d->meta, d->hist);
     return BSC_NO_ERROR;
 }
 
@@ -2182,8 +2382,8 @@ static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym
     int rc = radix_sort_passes(c, d->key_ch, d->key_ch_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_ch);
     if (rc < 0) return rc;
     prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
-    hipLaunchKernelGGL(dc_ctx_kernel<SB>, dim3(gm8), dim3(WG), 0, c->stream, d->key_ch, d->key_ch_s, d->inv_ch, m, S, d->tab_rank, d->tab_run,
-                       d->key_sr, d->key_sn, d->present, d->meta);
+    rc = dc_launch_ctx(c, d, m, S);                 // (with BSCGPU_OPT_DC_HIST_EXACT: and the resolve of the open run_hist brackets, 1c')
+    if (rc < 0) { prof_end(c); return rc; }
     hipLaunchKernelGGL(dc_setup_kernel<SB>, dim3(1), dim3(WG), 0, c->stream, d->present, S, d->rounds, d->meta,
                        (u32)(c->dc_avg_exact ? DM_AVG_LEFT : DM_AVG_UND));
     prof_end(c);
@@ -2354,7 +2554,7 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
     int rc = devcoder_ensure(c);
     if (rc < 0) return rc;
     DevCoder* d = c->dc;
-    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = c->dc_avg_resolved = c->dc_replay_resolved = 0;
+    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = c->dc_avg_resolved = c->dc_replay_resolved = c->dc_hist_resolved = 0;
     c->dc_last_fail = m > d->Mcap ? (int)FAIL_CAP : 0;                 // (more runs than the arena holds: capacity, as too many decisions are)
     if (m == 0 || m > d->Mcap || nb < 1 || nb > 8) return BSC_NOT_SUPPORTED;
     const bool fast = coder == 3;
@@ -2423,7 +2623,7 @@ static int dc_pass_begin(bscgpu_ctx* c, u32 m, int nsub, int over_fail, DcPass* 
     if (rc < 0) return rc;
     DevCoder* d = c->dc;
     if (over_fail >= 0) {
-        c->dc_replays = c->dc_avg_und = c->dc_hist_ext = c->dc_avg_resolved = c->dc_replay_resolved = 0;
+        c->dc_replays = c->dc_avg_und = c->dc_hist_ext = c->dc_avg_resolved = c->dc_replay_resolved = c->dc_hist_resolved = 0;
         c->dc_last_fail = m > d->Mcap ? over_fail : 0;
     }
     if (m == 0 || m > d->Mcap || nsub < 1 || nsub > FRONT_MAX_SUB || !c->front_tab) return BSC_NOT_SUPPORTED;
@@ -2561,7 +2761,7 @@ struct DcCopyRing {
 // The ranges of the schedule one after the other, launch by launch; out: the landing buffer (host), 2-byte entries or the packed
 // form's bytes (pk).  *replays / *hist_ext: what the kept and the declined runs counted together.
 static int dc_segments_loop(bscgpu_ctx* c, const DcPass& P, bool fast, bool pk, const u32* sub_run, DcSegSchedule& sch, DcCopyRing& ring, u8* out,
-                            int* replays, int* hist_ext, int* replay_resolved)
+                            int* replays, int* hist_ext, int* replay_resolved, int* hist_resolved)
 {
     DevCoder* d = P.d;
     std::vector<u32> pseg((size_t)P.S.nsub + 1), pbseg(pk ? (size_t)P.S.nsub + 1 : 0);
@@ -2587,7 +2787,7 @@ static int dc_segments_loop(bscgpu_ctx* c, const DcPass& P, bool fast, bool pk, 
         rc = fast ? dc_fast_run(c, d, G, P.dsym + r0, P.drank + r0, P.dstart + r0, d->ge32 + r0, r1 - r0, 0u, false, psbuf, g.expect, pseg.data(), &D)
                   : dc_static_run(c, d, G, P.dsym + r0, P.drank + r0, P.dstart + r0, d->ge32 + r0, r1 - r0, 0u, false, psbuf, g.expect, pseg.data(), nullptr,
                                   pk ? &packed : nullptr, &D, pk ? pbseg.data() : nullptr);
-        *replays += c->dc_replays; *hist_ext += c->dc_hist_ext; *replay_resolved += c->dc_replay_resolved;
+        *replays += c->dc_replays; *hist_ext += c->dc_hist_ext; *replay_resolved += c->dc_replay_resolved; *hist_resolved += c->dc_hist_resolved;
         if (rc == BSC_NOT_SUPPORTED) { if (sch.declined(g, c->dc_last_fail)) ring.settle(g); continue; }
         if (rc < 0) return rc;
         // this buffer's earlier copy-out has landed (the stream kernel waited for it), maybe the other one's too
@@ -2637,13 +2837,13 @@ int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub
     DcSegSchedule sch(dec.data(), und.data(), blk_sub, count, nsub, (int64_t)d->Dcap, target, cap, per_segment_fit, (int)FAIL_AVG, (int)FAIL_CAP, poff, pbase, blk_state);
     if (note) note->planned(note->user);
     DcCopyRing ring{d->seg_ev, c->copy_stream, note, {}};
-    int replays = 0, hist_ext = 0, replay_resolved = 0;
-    rc = dc_segments_loop(c, P, fast, pk, sub_run, sch, ring, static_cast<u8*>(out), &replays, &hist_ext, &replay_resolved);
+    int replays = 0, hist_ext = 0, replay_resolved = 0, hist_resolved = 0;
+    rc = dc_segments_loop(c, P, fast, pk, sub_run, sch, ring, static_cast<u8*>(out), &replays, &hist_ext, &replay_resolved, &hist_resolved);
     // (no copy into the caller's buffer may outlive the call, whichever way it ends)
     if (hipStreamSynchronize(c->copy_stream) != hipSuccess && rc >= 0) rc = ctx_fail(c, BSC_GPU_ERROR, "device coder: segment copy-out", hipSuccess);
     if (rc < 0) return rc;
     const DcSegTotals T = sch.finish();
-    c->dc_last_fail = T.fail; c->dc_replays = replays; c->dc_hist_ext = hist_ext; c->dc_avg_und = (int)und_total; c->dc_avg_resolved = (int)avg_resolved; c->dc_replay_resolved = replay_resolved;
+    c->dc_last_fail = T.fail; c->dc_replays = replays; c->dc_hist_ext = hist_ext; c->dc_avg_und = (int)und_total; c->dc_avg_resolved = (int)avg_resolved; c->dc_replay_resolved = replay_resolved; c->dc_hist_resolved = hist_resolved;
     c->cnt_seg += T.kept; c->cnt_seg_reruns += T.reruns; c->cnt_seg_host_blocks += T.host_blocks;
     c->cnt_packed_passes += T.kept_packed; c->cnt_packed_void += T.kept_void;
     if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder segments] sub-blocks %d, planned %d, kept %d, re-runs %d, blocks left to the host %d, decisions %lld\n", nsub, T.planned, T.kept, T.reruns, T.host_blocks, (long long)T.decisions);

@@ -482,6 +482,81 @@ inline void avg_resolve_host(const uint8_t* rank, uint32_t m, const uint32_t* fi
     }
 }
 
+// ---- open run_hist brackets resolved exactly (devcoder.hip 1c': dc_ctx_kernel<SB, true>, dc_hist_map_kernel .. dc_hist_fix_kernel), restated
+// for the host ----------------------------------------------------------------------------------------------------------------------
+// The runs in symbol-major order, as the stable sort by symbol leaves them: chain[q] names the chain of element q (symbol and sub-block:
+// the elements of one chain are consecutive), run[q] is its length.  run_hist of element q is h over the chain's elements in front of
+// it, h' = (h + run_hist_inc(run)) >> 2 from 0.  h -> h' is monotone and [0, 63] is invariant (the largest increment, 3 * 29 + 3 for a
+// run of 2^30 bytes, gives (63 + 90) >> 2 = 38), so 64 start values cover whatever a chunk can start from and nothing needs a guard.  The
+// same steps in the same order as the kernels: (1) every run walks the bracket [0, 63] over its DC_HIST_NP nearest predecessors (from 0
+// where the chain starts among them); its clamped ends differ: the run is OPEN and keeps the lower end for now; (2) if anything is open,
+// every whole chunk of DC_HIST_CH elements is walked from each of the 64 values, reset to 0 at every chain start: its transfer map;
+// (3) the maps of DC_HIST_GROUP chunks are composed, the groups chained from 0, every chunk handed its exact start; (4) a chunk that
+// holds an open run is walked again from its exact start and every open run takes its min(h, 7).
+constexpr int DC_HIST_CH     = 1024;     // exact resolve: symbol-major elements per chunk — 16 per lane of the wavefront that walks it
+constexpr int DC_HIST_CAND   = 64;       // ... start values a chunk is walked from, one per lane: all of [0, 63]
+constexpr int DC_HIST_GROUP  = 64;       // ... consecutive chunks whose transfer maps one wavefront composes
+static_assert(DC_HIST_CH == DC_AVG_CH && DC_HIST_CAND == DC_AVG_CAND && DC_HIST_GROUP == DC_AVG_GROUP, "the two resolves share their chain and groups kernels");
+DC_HD uint32_t run_hist_inc(uint32_t run) { return run == 1u ? 2u : 3u * (uint32_t)bsr(run) + 3u; }      // run_hist_next(h, run) = (h + run_hist_inc(run)) >> 2
+struct HistResolve {
+    uint64_t ext = 0, resolved = 0;                // runs whose bracket the nine predecessors left open; of those: settled by the resolve
+    uint32_t chunks = 0, groups = 0;               // chunks that hold an open run; groups of chunks in the launch
+    uint32_t chain_steps = 0;                      // longest dependent path: steps inside a group + groups chained + steps inside a group
+    std::vector<uint8_t> hist, open;               // per element: min(run_hist, 7) as the stage leaves it; whether (1) left it open
+};
+inline void hist_resolve_host(const uint64_t* chain, const uint32_t* run, uint32_t m, HistResolve& R)
+{
+    const uint32_t nch = (m + DC_HIST_CH - 1) / DC_HIST_CH, ngr = (nch + DC_HIST_GROUP - 1) / DC_HIST_GROUP;
+    R = HistResolve();
+    R.hist.assign(m, 0); R.open.assign(m, 0); R.groups = ngr;
+    std::vector<uint8_t> flag(nch, 0);
+    auto starts = [&](uint32_t q) { return q == 0 || chain[q] != chain[q - 1]; };
+    // (1) dc_ctx_kernel<SB, true>
+    for (uint32_t q = 0; q < m; ++q) {
+        uint32_t np = 0;
+        while (np < (uint32_t)DC_HIST_NP && q > np && chain[q - np - 1] == chain[q]) ++np;
+        uint32_t lo = 0, hi = np < (uint32_t)DC_HIST_NP ? 0u : 63u;
+        for (uint32_t t = np; t >= 1; --t) { lo = run_hist_next(lo, run[q - t]); hi = run_hist_next(hi, run[q - t]); }
+        const uint32_t cl = lo < 7u ? lo : 7u, ch = hi < 7u ? hi : 7u;
+        R.hist[q] = (uint8_t)cl;
+        if (cl != ch) { ++R.ext; R.open[q] = 1; flag[q / DC_HIST_CH] = 1; }
+    }
+    if (R.ext == 0) return;                                           // (every kernel behind the first leaves at once)
+    // (2) dc_hist_map_kernel: whole chunks only — the last chunk has no successor
+    std::vector<uint8_t> map((size_t)nch * DC_HIST_CAND, 0);
+    for (uint32_t c = 0; c + 1 < nch; ++c)
+        for (uint32_t v = 0; v < (uint32_t)DC_HIST_CAND; ++v) {
+            uint32_t x = v;
+            for (uint32_t q = c * DC_HIST_CH; q < (c + 1) * DC_HIST_CH; ++q) { if (starts(q)) x = 0; x = (x + run_hist_inc(run[q])) >> 2; }
+            map[(size_t)c * DC_HIST_CAND + v] = (uint8_t)x;
+        }
+    // (3) dc_avg_chain_kernel<false, DcHistRec>, dc_avg_groups_kernel<DcHistRec>, dc_avg_chain_kernel<true, DcHistRec>
+    std::vector<uint8_t> gmap((size_t)ngr * DC_HIST_CAND, 0), gstart(ngr, 0), ex(nch, 0);
+    for (uint32_t g = 0; g + 1 < ngr; ++g)
+        for (uint32_t v = 0; v < (uint32_t)DC_HIST_CAND; ++v) {
+            uint32_t x = v;
+            for (uint32_t c = g * DC_HIST_GROUP; c < (g + 1) * DC_HIST_GROUP; ++c) x = map[(size_t)c * DC_HIST_CAND + x];
+            gmap[(size_t)g * DC_HIST_CAND + v] = (uint8_t)x;
+        }
+    for (uint32_t g = 0; g + 1 < ngr; ++g) gstart[g + 1] = gmap[(size_t)g * DC_HIST_CAND + gstart[g]];      // (element 0 starts a chain: from 0)
+    for (uint32_t g = 0; g < ngr; ++g) {
+        uint32_t x = gstart[g];
+        for (uint32_t c = g * DC_HIST_GROUP; c < nch && c < (g + 1) * DC_HIST_GROUP; ++c) { ex[c] = (uint8_t)x; x = map[(size_t)c * DC_HIST_CAND + x]; }
+    }
+    R.chain_steps = ngr > 1 ? 2 * DC_HIST_GROUP + (ngr - 1) : nch - 1;
+    // (4) dc_hist_fix_kernel
+    for (uint32_t c = 0; c < nch; ++c) {
+        if (!flag[c]) continue;
+        ++R.chunks;
+        uint32_t x = ex[c];
+        for (uint32_t q = c * DC_HIST_CH; q < m && q < (c + 1) * DC_HIST_CH; ++q) {
+            if (starts(q)) x = 0;
+            if (R.open[q]) { R.hist[q] = (uint8_t)(x < 7u ? x : 7u); ++R.resolved; }
+            x = (x + run_hist_inc(run[q])) >> 2;
+        }
+    }
+}
+
 // ---- open chunk starts resolved exactly (devcoder.hip 3': dc_rp_map_kernel, dc_rp_chain_kernel), restated for the host -------------------
 // The evaluation of one unit as dc_eval has it: up to four jobs of chain-major events (row = decision type, rowstart[0 .. DC_ROWS]; the
 // first event of every non-empty row and every other chain start the signature does not show carry DC_ROWMARK already), EV events per

@@ -394,7 +394,8 @@ class GpuContext:
     CNT_DC_REPLAYS, CNT_DC_LAST_FAIL, CNT_DC_AVG_UNDECIDED, CNT_DC_HIST_EXTENDED = 5, 6, 7, 8      # the last device-model block (get only)
     OPT_DC_REPLAY_EXACT, CNT_DC_REPLAY_RESOLVED = 32, 33    # open chunk starts of the evaluation resolved exactly; chunks that settled (get only)
     OPT_DC_AVG_EXACT, CNT_DC_AVG_RESOLVED = 30, 31      # open avg_rank flags resolved exactly on the device; what that settled (get only)
-    DC_FAIL_AVG, DC_FAIL_HIST, DC_FAIL_CAP, DC_FAIL_REPLAY = 2, 4, 8, 16                          # BSCGPU_DC_FAIL_*
+    OPT_DC_HIST_EXACT, CNT_DC_HIST_RESOLVED = 34, 35    # open run_hist brackets resolved exactly on the device; runs that settled (get only)
+    DC_FAIL_AVG, DC_FAIL_HIST, DC_FAIL_CAP, DC_FAIL_REPLAY = 2, 4, 8, 16                         # BSCGPU_DC_FAIL_*
 
     def option_set(self, key, value):
         return self._check(self.L.bscgpu_option_set(self.h, key, value))
