@@ -228,14 +228,18 @@ def build_probe(dirname):
     return exe
 
 
-def run_probe(exe, L, dirname):
-    """the probe's verdict on the sorted block L (a dict: tools/devcoder_paths_probe.cpp)"""
+PROBE_OPTIONS = ("avg_exact", "hist_exact", "replay_exact")       # the probe's option words: BSCGPU_OPT_DC_{AVG,HIST,REPLAY}_EXACT on
+
+
+def run_probe(exe, L, dirname, options=()):
+    """the probe's verdict on the sorted block L (a dict: tools/devcoder_paths_probe.cpp); options: the words of PROBE_OPTIONS that are on"""
     import json
     import os
     import subprocess
+    assert all(o in PROBE_OPTIONS for o in options), options
     path = os.path.join(str(dirname), "probe_input.bin")
     np.ascontiguousarray(L, dtype=np.uint8).tofile(path)
-    r = subprocess.run([exe, path], capture_output=True, text=True)
+    r = subprocess.run([exe, path, *options], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     return json.loads(r.stdout)
 

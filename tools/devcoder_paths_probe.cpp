@@ -8,6 +8,13 @@
 //                    the stretch (no bracket exceeds the resolve's cap: tools/replay_resolve_probe.cpp bound), so no chunk is replayed and
 //                    FAIL_REPLAY is not among the exits; the object gains "replay_exact": true.  How many chunks the resolve settles
 //                    depends on the chain-major layout: replay_resolve_probe block L.bin.
+//   probe L.bin [avg_exact] [hist_exact] [replay_exact]   any of the three option words, in any order: the mask the stage must return
+//                    under that option set.  With R the block's reasons among AVG and HIST and O the options that are on: if R \ O is
+//                    not empty the mask is exactly R \ O (both exits are judged at the first sync, the evaluation never runs: REPLAY is
+//                    never beside them); else 16 if a stretch exceeds fail_min and replay_exact is off; else 0.  The counts (avg_und,
+//                    hist_ext, hist_fail, the stretches) do not depend on the options; every option word that is on is echoed as true.
+//   probe L.bin option_sets [...]   also "fail_mask_by_option_set": the masks of all eight option sets from the one walk, indexed by
+//                    avg_exact + 2 hist_exact + 4 replay_exact.
 //
 // What is computed, per block (sub-block split and run / rank front end as the stage function has them):
 //   avg_und      runs whose avg_rank >= 32 flag stays undecided under dc_avg_kernel's rule: chunks of DC_AVG_CH runs of the block's run
@@ -88,8 +95,15 @@ struct CountPolicy {                       // decisions of a sub-block (the chun
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s L.bin [replay_exact]\n", argv[0]); return 2; }
-    const bool replay_exact = argc > 2 && !strcmp(argv[2], "replay_exact");
+    if (argc < 2) { fprintf(stderr, "usage: %s L.bin [avg_exact] [hist_exact] [replay_exact]\n", argv[0]); return 2; }
+    bool avg_exact = false, hist_exact = false, replay_exact = false, option_sets = false;
+    for (int a = 2; a < argc; ++a) {
+        if (!strcmp(argv[a], "avg_exact")) avg_exact = true;
+        else if (!strcmp(argv[a], "hist_exact")) hist_exact = true;
+        else if (!strcmp(argv[a], "replay_exact")) replay_exact = true;
+        else if (!strcmp(argv[a], "option_sets")) option_sets = true;
+        else { fprintf(stderr, "%s: unknown option word %s\n", argv[0], argv[a]); return 2; }
+    }
     FILE* f = fopen(argv[1], "rb");
     if (!f) { perror(argv[1]); return 2; }
     fseek(f, 0, SEEK_END); const long n = ftell(f); fseek(f, 0, SEEK_SET);
@@ -183,10 +197,13 @@ int main(int argc, char** argv)
     const uint64_t replay_min = 3ull * EV, fail_min = (uint64_t)(dcm::DC_REPLAY_MAX + 2) * EV, keep_max = (uint64_t)dcm::DC_REPLAY_MAX * EV;
     uint32_t stretch = 0; uint64_t risk = 0;
     for (int fam = 0; fam < 3; ++fam) { if (F[fam].stretch > stretch) stretch = F[fam].stretch; if (F[fam].risk > risk) risk = F[fam].risk; }
-    int mask = 0;                                                   // include/bscgpu.h: BSCGPU_DC_FAIL_*
-    if (avg_und) mask |= 2;
-    if (hist_fail) mask |= 4;
-    // (an earlier exit stops the evaluation: a block declined for its contexts is never replayed)
+    // include/bscgpu.h: BSCGPU_DC_FAIL_*.  (With an option on every open flag is resolved: avg_resolve_probe; every open bracket:
+    // hist_resolve_probe.  An earlier exit stops the evaluation: a block declined for its contexts is never replayed)
+    auto mask_under = [&](bool avg_on, bool hist_on, bool replay_on) {
+        const int first_sync = (avg_und && !avg_on ? 2 : 0) | (hist_fail && !hist_on ? 4 : 0);
+        return first_sync ? first_sync : stretch > fail_min && !replay_on ? 16 : 0;
+    };
+    int mask = mask_under(avg_exact, hist_exact, true);
     const bool fail_replay = mask == 0 && stretch > fail_min && !replay_exact;
     const bool no_fail_replay = mask != 0 || risk <= keep_max || replay_exact;
     if (fail_replay) mask |= 16;
@@ -211,6 +228,13 @@ int main(int argc, char** argv)
     printf("},\n");
     printf(" \"replay_min\": %llu, \"fail_min\": %llu, \"keep_max\": %llu,\n", (unsigned long long)replay_min, (unsigned long long)fail_min, (unsigned long long)keep_max);
     // fail_mask: the reason mask the stage must return (0: none of the exits judged here is certain); the three booleans say what is CERTAIN
+    if (option_sets) {
+        printf(" \"fail_mask_by_option_set\": [");
+        for (int o = 0; o < 8; ++o) printf("%s%d", o ? ", " : "", mask_under(o & 1, o & 2, o & 4));
+        printf("],\n");
+    }
+    if (avg_exact) printf(" \"avg_exact\": true,\n");
+    if (hist_exact) printf(" \"hist_exact\": true,\n");
     if (replay_exact) printf(" \"replay_exact\": true,\n");
     printf(" \"fail_mask\": %d, \"replay_certain\": %s, \"no_replay_certain\": %s, \"no_fail_replay_certain\": %s}\n", mask,
            (mask == 0 || fail_replay) && stretch >= replay_min && !replay_exact ? "true" : "false", (mask & ~16) != 0 || risk == 0 || replay_exact ? "true" : "false",
