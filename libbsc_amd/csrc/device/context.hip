@@ -374,16 +374,16 @@ extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
     if (key == BSCGPU_OPT_RS_ONESWEEP) return c->os_mode;
     if (key == BSCGPU_CNT_OS_RETRIES) return c->os_retries;
     if (key == BSCGPU_OPT_DC_PACKED_STREAM) return c->dc_p13;
-    if (key == BSCGPU_CNT_DC_REPLAYS) return c->dc_replays;
-    if (key == BSCGPU_CNT_DC_LAST_FAIL) return c->dc_last_fail;
-    if (key == BSCGPU_CNT_DC_AVG_UNDECIDED) return c->dc_avg_und;
-    if (key == BSCGPU_CNT_DC_HIST_EXTENDED) return c->dc_hist_ext;
+    if (key == BSCGPU_CNT_DC_REPLAYS) return c->dc_note.replays;
+    if (key == BSCGPU_CNT_DC_LAST_FAIL) return c->dc_note.fail;
+    if (key == BSCGPU_CNT_DC_AVG_UNDECIDED) return c->dc_note.avg_und;
+    if (key == BSCGPU_CNT_DC_HIST_EXTENDED) return c->dc_note.hist_ext;
     if (key == BSCGPU_OPT_DC_AVG_EXACT) return c->dc_avg_exact;
-    if (key == BSCGPU_CNT_DC_AVG_RESOLVED) return c->dc_avg_resolved;
+    if (key == BSCGPU_CNT_DC_AVG_RESOLVED) return c->dc_note.avg_resolved;
     if (key == BSCGPU_OPT_DC_REPLAY_EXACT) return c->dc_replay_exact;
-    if (key == BSCGPU_CNT_DC_REPLAY_RESOLVED) return c->dc_replay_resolved;
+    if (key == BSCGPU_CNT_DC_REPLAY_RESOLVED) return c->dc_note.replay_resolved;
     if (key == BSCGPU_OPT_DC_HIST_EXACT) return c->dc_hist_exact;
-    if (key == BSCGPU_CNT_DC_HIST_RESOLVED) return c->dc_hist_resolved;
+    if (key == BSCGPU_CNT_DC_HIST_RESOLVED) return c->dc_note.hist_resolved;
     if (key == BSCGPU_OPT_BATCH_FRONT) return c->batch_front;
     if (key == BSCGPU_CNT_BATCH_FRONT_PASSES) return c->cnt_front_passes;
     if (key == BSCGPU_CNT_BATCH_L_PASSES) return c->cnt_l_passes;

@@ -75,6 +75,17 @@ struct HostSlot {
 constexpr int MAX_SLOTS = 8;
 
 struct DevCoder;                  // device-side static coder state (devcoder.hip), created on first use
+// What a unit of the device coder's model work (a block, a pass, a pass in segments) says about itself (bscgpu_option_get: BSCGPU_CNT_DC_*)
+struct DcNote {
+    int fail = 0;            // why it left the device coder (bit mask, devcoder.hip FAIL_* = BSCGPU_DC_FAIL_*), 0 = it did not
+    int replays = 0;         // evaluation chunks replayed serially
+    int avg_und = 0;         // runs whose avg_rank >= 32 flag the two-sided bracket left undecided (any: FAIL_AVG)
+    int avg_resolved = 0;    // ... of those, the runs the exact resolve settled (BSCGPU_OPT_DC_AVG_EXACT)
+    int replay_resolved = 0; // chunks whose start the exact resolve settled (BSCGPU_OPT_DC_REPLAY_EXACT)
+    int hist_ext = 0;        // runs whose run_hist bracket was still open after nine predecessors (the extended look-back)
+    int hist_resolved = 0;   // ... of those, the runs the exact resolve settled (BSCGPU_OPT_DC_HIST_EXACT)
+    void clear(int why = 0) { *this = DcNote(); fail = why; }
+};
 
 constexpr u32 UB_STEP_CAP = 1u << 22;       // unbwt.hip: steps a walk may take between two marked rows (bscgpu_ctx::ub_step_cap)
 
@@ -173,14 +184,7 @@ struct bscgpu_ctx {
     int      nslots = 0;
     DevCoder* dc = nullptr;
     bool     dc_alloc_failed = false;   // the device coder's arena did not fit: this context keeps the host model (not retried per block)
-    // the last block that went to the device coder (bscgpu_option_get: BSCGPU_CNT_DC_*), set whether the block stayed there or not
-    int      dc_last_fail = 0;   // why it left the device coder (bit mask, devcoder.hip FAIL_* = BSCGPU_DC_FAIL_*), 0 = it did not
-    int      dc_replays = 0;     // evaluation chunks replayed serially
-    int      dc_avg_und = 0;     // runs whose avg_rank >= 32 flag the two-sided bracket left undecided (any: FAIL_AVG)
-    int      dc_avg_resolved = 0; // ... of those, the runs the exact resolve settled (BSCGPU_OPT_DC_AVG_EXACT)
-    int      dc_replay_resolved = 0; // chunks whose start the exact resolve settled (BSCGPU_OPT_DC_REPLAY_EXACT)
-    int      dc_hist_ext = 0;    // runs whose run_hist bracket was still open after nine predecessors (the extended look-back)
-    int      dc_hist_resolved = 0; // ... of those, the runs the exact resolve settled (BSCGPU_OPT_DC_HIST_EXACT)
+    DcNote   dc_note;            // the last block (pass) that went to the device coder, set whether it stayed there or not
 
     // profiling
     bool         prof        = false;
@@ -314,7 +318,7 @@ int  devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32*
 const u16* devcoder_pstream_ptr(const bscgpu_ctx* c, int psbuf = 0);
 // ... of a whole batched pass ("The static coder's model of a pass"): after qlfc_front_batch, from the run arrays and the
 // table it left in HBM -> *D_out decisions in devcoder_pstream_ptr(c, 0), sub-block s's at [poff[s], poff[s + 1]) with poff[0..nsub] at
-// devcoder_batch_poff_ptr (device).  BSC_NOT_SUPPORTED: the pass is declined (c->dc_last_fail: BSCGPU_DC_FAIL_*; 0: an arena did not
+// devcoder_batch_poff_ptr (device).  BSC_NOT_SUPPORTED: the pass is declined (c->dc_note.fail: BSCGPU_DC_FAIL_*; 0: an arena did not
 // fit).  Synchronous.  coder 3: the fast coder's (-e0) model of the pass — same inputs, same outputs with entries in the dcm::PSF_*
 // form, same exits (only FAIL_CAP and FAIL_REPLAY can be raised: this coder has no avg_rank flags and no run_hist look-back)
 // packed_out non-null (coder 1): the stream may be left in the packed 13-bit form of a pass ("The packed stream of a pass");

@@ -77,6 +77,9 @@ enum { DM_FAIL = 0, DM_NTYPES, DM_NROUNDS, DM_AVG_UND, DM_REPLAYS, DM_D0, DM_D1,
        DM_HIST_RESOLVED /* runs whose open run_hist bracket the exact resolve settled (1c') */, DM_COUNT = 16 };
 // (bit 0 is not in use: every decision type has a row of its own, DC_ROWS >= NUM_TAU, so no number of types is too many)
 enum { FAIL_AVG = BSCGPU_DC_FAIL_AVG, FAIL_HIST = BSCGPU_DC_FAIL_HIST, FAIL_CAP = BSCGPU_DC_FAIL_CAP, FAIL_REPLAY = BSCGPU_DC_FAIL_REPLAY };
+// the pinned host copy (DevCoder::hmeta, HM_WORDS words): the meta words in front, then what comes down beside them
+enum { HM_POFF = 32 /* a block's poff[0..nb], 16 words */, HM_PBASE_END = 48 /* a table's pbase[nsub], the end of its packed layout */, HM_WORDS = 64 };
+static_assert(DM_COUNT <= HM_POFF, "hmeta: the meta words end where the offsets begin");
 
 struct DcSub { u32 nb; u32 first[9]; u32 maxr[8]; };           // run index range (first[nb] = m) and max_rank of each sub-block
 struct DcRowBins { u16 lo1, hi1, lo2, hi2; };                   // counting pass: count(row) = P[hi1] - P[lo1] + P[hi2] - P[lo2] over bin prefix sums
@@ -106,9 +109,21 @@ struct DcHistRec {
     u16* gstart;    // per group: the exact start of its first chunk
 };
 
+// what the exact resolve of open chunk starts keeps per chunk slot of the evaluation (3', in front of dc_rp_walk)
+struct DcRpRec {
+    u16* map;       // per chunk slot, DC_RP_CAND entries: map[v] = (value at the chunk's end, had it started at elo[p - 1] + v) - elo[p]
+    u16* head;      // per chunk slot: the exact end of a stretch's head
+    u8*  st;        // per chunk slot: DC_RP_*
+    u32  cand;      // widest start bracket that is walked (values)
+};
+
+// One hipMalloc carved into 256-byte aligned pieces (dc_arena_alloc), made on the first use of what it serves.  failed: it did not
+// fit, and is not tried again — what that means is its user's: see the five ensures.
+struct DcArena { char* base = nullptr; size_t bytes = 0; bool failed = false; };
+
 struct DevCoder {
     size_t Mcap = 0, Dcap = 0;
-    char*  arena = nullptr; size_t arena_bytes = 0;
+    DcArena arena;
     u64 *key_ch = nullptr, *key_ch_s = nullptr, *key_sr = nullptr, *key_sr_s = nullptr, *key_sn = nullptr, *key_sn_s = nullptr;
     u32 *inv_ch = nullptr, *inv_sr = nullptr, *inv_sn = nullptr;
     u8  *ge32 = nullptr;
@@ -127,10 +142,10 @@ struct DevCoder {
     ModelParams* mp = nullptr;                                 // device copy (static coder)
     ModelParams* mp_fast = nullptr;                            // device copy (fast coder: dcm::model_params_fast)
     struct DcFrag* frag = nullptr;                              // packed stream: two fragment records per wavefront of dc_pstream (DcP13)
-    u32 *hmeta = nullptr;                                      // pinned: meta + poff
+    u32 *hmeta = nullptr;                                      // pinned, HM_WORDS: meta, poff (HM_POFF), the packed layout's end (HM_PBASE_END)
     // the model of a batched pass (devcoder_pstream_batch), allocated on its first use: the wider chain identity — every event's full
     // sub-block id, 2 bytes per decision and family (8 Dcap bytes) —, max_rank and stream offset of every sub-block
-    char*  batch_arena = nullptr; size_t batch_bytes = 0; bool batch_alloc_failed = false;
+    DcArena batch_arena;
     u16 *esub[4] = {nullptr, nullptr, nullptr, nullptr};
     u8  *sub_maxr = nullptr; u32 *poff_tab = nullptr;
     // model segments (devcoder_pstream_segments): per sub-block the undecided avg_rank flags and the decisions of the coder at hand,
@@ -141,15 +156,15 @@ struct DevCoder {
     hipEvent_t seg_ev[2] = {nullptr, nullptr};                 // behind the last copy out of ps[0 / 1] on the copy stream
     // the exact resolve of open avg_rank flags (BSCGPU_OPT_DC_AVG_EXACT), allocated on its first use: 71 bytes per chunk of DC_AVG_CH
     // runs, 130 per group of DC_AVG_GROUP chunks — under 0.1 byte per byte of max_n
-    char* avg_arena = nullptr; size_t avg_bytes = 0; bool avg_alloc_failed = false;
+    DcArena avg_arena;
     DcAvgRec avg = {};
     // the exact resolve of open chunk starts (BSCGPU_OPT_DC_REPLAY_EXACT), allocated on its first use: per chunk slot (4 nch_cap of them)
     // 2 DC_RP_CAND bytes of map, the head's end and a state byte — 771 bytes per slot, 1.5 bytes per byte of max_n (101 MB for 64 MiB)
-    char* rp_arena = nullptr; size_t rp_bytes = 0; bool rp_alloc_failed = false;
-    struct DcRpRec* rp = nullptr;
+    DcArena rp_arena;
+    DcRpRec rp = {};
     // the exact resolve of open run_hist brackets (BSCGPU_OPT_DC_HIST_EXACT), allocated on its first use: a bit per run, 67 bytes per chunk
     // of DC_HIST_CH runs, 130 per group of DC_HIST_GROUP chunks — 0.2 byte per byte of max_n
-    char* hist_arena = nullptr; size_t hist_bytes = 0; bool hist_alloc_failed = false;
+    DcArena hist_arena;
     DcHistRec hist = {};
 };
 
@@ -1425,12 +1440,6 @@ __device__ __forceinline__ bool dc_chunk_continues(const DcEvalJob& J, u32 c, u3
 // replay_resolve_probe.cpp bound —, or what BSC_DC_REPLAY_CAND lowers it to) is not walked; the chain stops there and what lies behind
 // it in the stretch is left to dc_eval_b_kernel's replay.
 // ---------------------------------------------------------------------------------------------------------------------
-struct DcRpRec {
-    u16* map;       // per chunk slot, DC_RP_CAND entries: map[v] = (value at the chunk's end, had it started at elo[p - 1] + v) - elo[p]
-    u16* head;      // per chunk slot: the exact end of a stretch's head
-    u8*  st;        // per chunk slot: DC_RP_*
-    u32  cand;      // widest start bracket that is walked (values)
-};
 static_assert(DC_RP_CAND % 64 == 0 && DC_RP_CAND / 64 == 6, "dc_rp_map_kernel: candidates per lane");
 
 // N chains over the same nq x 8 events, interleaved (their dependent steps fill each other's issue gaps); the events 16 bytes per load
@@ -2013,19 +2022,35 @@ static bool dc_build_rowbins(DcRowBins* T)
 
 static size_t dc_align(size_t x) { return (x + 255) / 256 * 256; }
 
+// The arena's one allocation, and the pointers of the carve table into it.  false: it does not fit — or fail_env (may be null) is set
+// in the environment, the tests' way to that exit —; the HIP error is cleared and the arena marked, so that nobody allocates again.
+struct Carve { void** p; size_t bytes; };
+template <size_t N>
+static bool dc_arena_alloc(DcArena& a, const Carve (&carve)[N], const char* fail_env)
+{
+    size_t total = 0;
+    for (const Carve& cv : carve) total += dc_align(cv.bytes);
+    if ((fail_env && getenv(fail_env)) || hipMalloc((void**)&a.base, total) != hipSuccess) {
+        (void)hipGetLastError(); a.base = nullptr; a.failed = true;
+        return false;
+    }
+    a.bytes = total;
+    size_t off = 0;
+    for (const Carve& cv : carve) { *cv.p = a.base + off; off += dc_align(cv.bytes); }
+    return true;
+}
+
+// Everything a DevCoder owns, whether it is the context's or one whose set-up did not get that far.
+static void dc_free(DevCoder* d)
+{
+    for (DcArena* a : {&d->arena, &d->batch_arena, &d->avg_arena, &d->rp_arena, &d->hist_arena}) if (a->base) (void)hipFree(a->base);
+    for (int k = 0; k < 2; ++k) if (d->seg_ev[k]) (void)hipEventDestroy(d->seg_ev[k]);
+    if (d->hmeta) (void)hipHostFree(d->hmeta);
+    delete d;
+}
 void devcoder_destroy(bscgpu_ctx* c)
 {
-    DevCoder* d = c->dc;
-    if (!d) return;
-    if (d->arena) hipFree(d->arena);
-    if (d->batch_arena) hipFree(d->batch_arena);
-    if (d->avg_arena) hipFree(d->avg_arena);
-    if (d->rp_arena) hipFree(d->rp_arena);
-    delete d->rp;
-    if (d->hist_arena) hipFree(d->hist_arena);
-    for (int k = 0; k < 2; ++k) if (d->seg_ev[k]) hipEventDestroy(d->seg_ev[k]);
-    if (d->hmeta) hipHostFree(d->hmeta);
-    delete d;
+    if (c->dc) dc_free(c->dc);
     c->dc = nullptr;
 }
 
@@ -2065,13 +2090,11 @@ int devcoder_ensure(bscgpu_ctx* c)
     // An arena that does not fit (~220 bytes per block byte on top of the sorter's ~60) is a reason to DECLINE, not an error: the
     // block takes the host model, as it did before the device model existed, and the allocation is not retried for every block.
     if (c->dc_alloc_failed) return BSC_NOT_SUPPORTED;
-    if (getenv("BSC_DEVCODER_FAIL_ALLOC")) { c->dc_alloc_failed = true; return BSC_NOT_SUPPORTED; }      // tests: an arena that does not fit
     CtxTimer tm("devcoder_ensure (arena, tables)");
     DevCoder* d = new DevCoder();
     d->Mcap = dc_capacity_runs(c->max_n); d->Dcap = dc_capacity_decisions(c->max_n);
     const size_t M = d->Mcap + 64, D = d->Dcap + 64, NCH = d->Dcap / DC_EV + 16;
-    struct Carve { void** p; size_t bytes; };
-    Carve carve[] = {
+    const Carve carve[] = {
         {(void**)&d->key_ch, 8 * M}, {(void**)&d->key_ch_s, 8 * M}, {(void**)&d->key_sr, 8 * M}, {(void**)&d->key_sr_s, 8 * M},
         {(void**)&d->key_sn, 8 * M}, {(void**)&d->key_sn_s, 8 * M},
         {(void**)&d->inv_ch, 4 * M}, {(void**)&d->inv_sr, 4 * M}, {(void**)&d->inv_sn, 4 * M}, {(void**)&d->ge32, M},
@@ -2088,13 +2111,12 @@ int devcoder_ensure(bscgpu_ctx* c)
         {(void**)&d->tab_rank, 32768}, {(void**)&d->tab_run, 8192}, {(void**)&d->mp, sizeof(ModelParams)}, {(void**)&d->mp_fast, sizeof(ModelParams)},
         {(void**)&d->rowbins, DC_ROWS * sizeof(DcRowBins)}, {(void**)&d->sink, 4096},
     };
-    size_t total = 0;
-    for (auto& cv : carve) total += dc_align(cv.bytes);
-    if (hipMalloc((void**)&d->arena, total) != hipSuccess) { (void)hipGetLastError(); delete d; c->dc_alloc_failed = true; return BSC_NOT_SUPPORTED; }
-    d->arena_bytes = total; d->nch_cap = NCH;
-    size_t off = 0;
-    for (auto& cv : carve) { *cv.p = d->arena + off; off += dc_align(cv.bytes); }
-    if (hipHostMalloc((void**)&d->hmeta, 64 * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); hipFree(d->arena); delete d; c->dc_alloc_failed = true; return BSC_NOT_SUPPORTED; }
+    d->nch_cap = NCH;
+    if (!dc_arena_alloc(d->arena, carve, "BSC_DEVCODER_FAIL_ALLOC") || hipHostMalloc((void**)&d->hmeta, HM_WORDS * 4, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError(); d->hmeta = nullptr; dc_free(d);
+        c->dc_alloc_failed = true;                                       // the policy above: the context keeps the host model
+        return BSC_NOT_SUPPORTED;
+    }
     // (once per process: the attainable-range closures behind the brackets take ~60 ms to compute, and every context needs the same tables;
     // devcoder_warm_tables starts them on a thread of their own while the first context is still being created)
     const ModelParams& mp = dc_model_static();
@@ -2102,12 +2124,12 @@ int devcoder_ensure(bscgpu_ctx* c)
     // more than 64 KB of dynamic LDS is a per-device attribute of the function: set for every context's device
     if (hipFuncSetAttribute((const void*)dc_eval_wave_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, DC_EVAL_LDS) != hipSuccess ||
         hipFuncSetAttribute((const void*)dc_eval_wave_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, DC_EVAL_LDS) != hipSuccess) {
-        (void)hipFree(d->arena); (void)hipHostFree(d->hmeta); delete d;
+        dc_free(d);
         return ctx_fail(c, BSC_GPU_ERROR, "device coder: LDS attribute", hipSuccess);
     }
     static DcRowBins rowbins[DC_ROWS];
     static const bool rowbins_ok = dc_build_rowbins(rowbins);
-    if (!rowbins_ok) { (void)hipFree(d->arena); (void)hipHostFree(d->hmeta); delete d; return ctx_fail(c, BSC_GPU_ERROR, "device coder: bin layout", hipSuccess); }
+    if (!rowbins_ok) { dc_free(d); return ctx_fail(c, BSC_GPU_ERROR, "device coder: bin layout", hipSuccess); }
     const bschost::QlfcTables& QT = bschost::qlfc_tables();
     const uint8_t *rs = QT.rank_state, *ns = QT.run_state;
     const bool ok = hipMemcpyAsync(d->mp, &mp, sizeof mp, hipMemcpyHostToDevice, c->stream) == hipSuccess
@@ -2116,13 +2138,13 @@ int devcoder_ensure(bscgpu_ctx* c)
                  && hipMemcpyAsync(d->tab_run, ns, 8192, hipMemcpyHostToDevice, c->stream) == hipSuccess
                  && hipMemcpyAsync(d->rowbins, rowbins, sizeof rowbins, hipMemcpyHostToDevice, c->stream) == hipSuccess
                  && ctx_sync(c) == hipSuccess;                      // mp is a stack object: the copies must have finished
-    if (!ok) { hipFree(d->arena); hipHostFree(d->hmeta); delete d; return ctx_fail(c, BSC_GPU_ERROR, "device coder tables", hipSuccess); }
+    if (!ok) { dc_free(d); return ctx_fail(c, BSC_GPU_ERROR, "device coder tables", hipSuccess); }
     c->dc = d;
     return BSC_NO_ERROR;
 }
 
-int64_t devcoder_arena_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)c->dc->arena_bytes : 0; }
-int64_t devcoder_batch_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)(c->dc->batch_bytes + c->dc->avg_bytes + c->dc->rp_bytes + c->dc->hist_bytes) : 0; }
+int64_t devcoder_arena_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)c->dc->arena.bytes : 0; }
+int64_t devcoder_batch_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)(c->dc->batch_arena.bytes + c->dc->avg_arena.bytes + c->dc->rp_arena.bytes + c->dc->hist_arena.bytes) : 0; }
 
 // One partition job: counts, scans, scatter.  SCATTER = false: counts and scans only, then the runs' offsets in the stream
 // (dc_doff_kernel) — all the fast coder needs of job 0, whose events nobody reads.
@@ -2145,40 +2167,24 @@ static void dc_launch_partition(bscgpu_ctx* c, DevCoder* d, const u64* items, u3
 }
 
 // what bscgpu_option_get reports about the context's last block, from the meta words just read back (declined or not)
-static void dc_note_block(bscgpu_ctx* c, const DevCoder* d)
+static DcNote dc_note_from(const u32* hmeta)
 {
-    c->dc_last_fail = (int)d->hmeta[DM_FAIL];
-    c->dc_replays = (int)d->hmeta[DM_REPLAYS];
-    c->dc_avg_und = (int)d->hmeta[DM_AVG_UND];
-    c->dc_hist_ext = (int)d->hmeta[DM_HIST_EXT];
-    c->dc_avg_resolved = (int)d->hmeta[DM_AVG_RESOLVED];
-    c->dc_replay_resolved = (int)d->hmeta[DM_REPLAY_RESOLVED];
-    c->dc_hist_resolved = (int)d->hmeta[DM_HIST_RESOLVED];
+    return DcNote{(int)hmeta[DM_FAIL], (int)hmeta[DM_REPLAYS], (int)hmeta[DM_AVG_UND], (int)hmeta[DM_AVG_RESOLVED], (int)hmeta[DM_REPLAY_RESOLVED],
+                  (int)hmeta[DM_HIST_EXT], (int)hmeta[DM_HIST_RESOLVED]};
 }
 
 // ---- the avg_rank flags of m runs (1a), and with BSCGPU_OPT_DC_AVG_EXACT the exact resolve behind them (1a') ---------------------------
-// The resolve's buffers, on the first call that asks for it.  Do not fit: the unit is declined, as for the batch arena.
-static int devcoder_avg_ensure(DevCoder* d)
+// The resolve's buffers, on the first call that asks for it; false: they do not fit.
+static bool devcoder_avg_ensure(DevCoder* d)
 {
-    if (d->avg_arena) return BSC_NO_ERROR;
-    if (d->avg_alloc_failed) return BSC_NOT_SUPPORTED;
+    if (d->avg_arena.base || d->avg_arena.failed) return !d->avg_arena.failed;
     // chunks padded to whole groups, groups to the 64 that dc_avg_groups_kernel loads at a time
     const size_t NC = (d->Mcap / DC_AVG_CH + 1 + DC_AVG_GROUP) / DC_AVG_GROUP * DC_AVG_GROUP + DC_AVG_GROUP, NG = (NC / DC_AVG_GROUP + 64) / 64 * 64 + 64;
-    struct Carve { void** p; size_t bytes; };
-    Carve carve[] = {
+    const Carve carve[] = {
         {(void**)&d->avg.brk, 2 * NC}, {(void**)&d->avg.und, 2 * NC}, {(void**)&d->avg.st, NC}, {(void**)&d->avg.ex, 2 * NC},
         {(void**)&d->avg.map, (size_t)DC_AVG_CAND * NC}, {(void**)&d->avg.gmap, 2 * (size_t)DC_AVG_CAND * NG}, {(void**)&d->avg.gstart, 2 * NG},
     };
-    size_t total = 0;
-    for (auto& cv : carve) total += dc_align(cv.bytes);
-    if (hipMalloc((void**)&d->avg_arena, total) != hipSuccess) {
-        (void)hipGetLastError(); d->avg_arena = nullptr; d->avg_alloc_failed = true;
-        return BSC_NOT_SUPPORTED;
-    }
-    d->avg_bytes = total;
-    size_t off = 0;
-    for (auto& cv : carve) { *cv.p = d->avg_arena + off; off += dc_align(cv.bytes); }
-    return BSC_NO_ERROR;
+    return dc_arena_alloc(d->avg_arena, carve, "BSC_DC_AVG_FAIL_ALLOC");
 }
 // No sync: the resolve's kernels are launched whether or not a flag is open, and leave at once where none is.
 template <class SB>
@@ -2189,8 +2195,7 @@ static int dc_launch_avg(bscgpu_ctx* c, DevCoder* d, const u8* drank, u32 m, con
         hipLaunchKernelGGL(dc_avg_kernel<SB>, dim3((nch + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta, sub_und, DcAvgNoRec{});
         return BSC_NO_ERROR;
     }
-    const int rc = devcoder_avg_ensure(d);
-    if (rc < 0) return rc;
+    if (!devcoder_avg_ensure(d)) return BSC_NOT_SUPPORTED;             // do not fit: the unit is declined, as for the batch arena (no reason bit)
     hipLaunchKernelGGL((dc_avg_kernel<SB, true>), dim3((nch + WG - 1) / WG), dim3(WG), 0, c->stream, drank, m, S, d->ge32, d->meta, (u32*)nullptr, d->avg);
     if (nch > 1) hipLaunchKernelGGL(dc_avg_map_kernel<SB>, dim3((nch - 1 + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, drank, m, S, d->avg);
     if (ngr > 1) hipLaunchKernelGGL(dc_avg_chain_kernel<false>, dim3(ngr - 1), dim3(64), 0, c->stream, m, d->avg);
@@ -2201,28 +2206,17 @@ static int dc_launch_avg(bscgpu_ctx* c, DevCoder* d, const u8* drank, u32 m, con
 }
 
 // ---- the exact resolve of open run_hist brackets (1c') ---------------------------------------------------------------------------------
-// Its buffers, on the first static model that asks for it.  Do not fit: the option stays without effect (dc_ctx_kernel<SB> with its
-// look-back, as with the option off) — not an error, and not retried.
+// Its buffers, on the first static model that asks for it; false: they do not fit.
 static bool devcoder_hist_ensure(DevCoder* d)
 {
-    if (d->hist_arena) return true;
-    if (d->hist_alloc_failed) return false;
+    if (d->hist_arena.base || d->hist_arena.failed) return !d->hist_arena.failed;
     // chunks padded to whole groups, groups to the 64 that dc_avg_groups_kernel loads at a time; a bit per element of the padded chunks
     const size_t NC = (d->Mcap / DC_HIST_CH + 1 + DC_HIST_GROUP) / DC_HIST_GROUP * DC_HIST_GROUP + DC_HIST_GROUP, NG = (NC / DC_HIST_GROUP + 64) / 64 * 64 + 64;
-    struct Carve { void** p; size_t bytes; };
-    Carve carve[] = {
+    const Carve carve[] = {
         {(void**)&d->hist.bits, NC * DC_HIST_CH / 8}, {(void**)&d->hist.flag, NC}, {(void**)&d->hist.ex, 2 * NC},
         {(void**)&d->hist.map, (size_t)DC_HIST_CAND * NC}, {(void**)&d->hist.gmap, 2 * (size_t)DC_HIST_CAND * NG}, {(void**)&d->hist.gstart, 2 * NG},
     };
-    size_t total = 0;
-    for (auto& cv : carve) total += dc_align(cv.bytes);
-    if (hipMalloc((void**)&d->hist_arena, total) != hipSuccess) {
-        (void)hipGetLastError(); d->hist_arena = nullptr; d->hist_alloc_failed = true;
-        return false;
-    }
-    d->hist_bytes = total;
-    size_t off = 0;
-    for (auto& cv : carve) { *cv.p = d->hist_arena + off; off += dc_align(cv.bytes); }
+    if (!dc_arena_alloc(d->hist_arena, carve, "BSC_DC_HIST_FAIL_ALLOC")) return false;
     d->hist.ext = d->meta + DM_HIST_EXT; d->hist.scr = d->key_sn_s;
     return true;
 }
@@ -2232,6 +2226,7 @@ template <class SB>
 static int dc_launch_ctx(bscgpu_ctx* c, DevCoder* d, u32 m, const SB& S)
 {
     const u32 gm8 = ((m + WG - 1) / WG + 7u) / 8u * 8u;                // (dc_virtual_block())
+    // (buffers that do not fit: the option stays without effect — dc_ctx_kernel<SB> with its look-back, as with the option off; not an error)
     if (!(c->dc_hist_exact && devcoder_hist_ensure(d))) {
         hipLaunchKernelGGL(dc_ctx_kernel<SB>, dim3(gm8), dim3(WG), 0, c->stream, d->key_ch, d->key_ch_s, d->inv_ch, m, S, d->tab_rank, d->tab_run,
                            d->key_sr, d->key_sn, d->present, d->meta, DcHistNoRec{});
@@ -2260,7 +2255,7 @@ static int dc_meta_down(bscgpu_ctx* c, DevCoder* d, const DcDown& also)
     if (also.dst) HIP_TRY(c, hipMemcpyAsync(also.dst, also.src, also.bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
     prof_collect(c);
-    dc_note_block(c, d);
+    c->dc_note = dc_note_from(d->hmeta);
     return d->hmeta[DM_FAIL] != 0 ? BSC_NOT_SUPPORTED : BSC_NO_ERROR;
 }
 
@@ -2276,7 +2271,7 @@ static int dc_ps_wait(bscgpu_ctx* c, int psbuf)
 }
 
 // Where the form enters on the host (the kernels: DcForm): the sub-blocks' offsets in the stream, from job 0's doff.  The eight go to
-// d->poff and come down with meta at the FIRST sync (hmeta[32..]: the packed stream's layout is made of them); a table's go to
+// d->poff and come down with meta at the FIRST sync (hmeta[HM_POFF..]: the packed stream's layout is made of them); a table's go to
 // d->poff_tab and come down at the LAST sync, where the caller asks for them (poff_host).
 static void dc_launch_poff(bscgpu_ctx* c, DevCoder* d, const DcSub& S, u32 m)
 {
@@ -2286,27 +2281,18 @@ static void dc_launch_poff(bscgpu_ctx* c, DevCoder* d, const DcSubTab& S, u32)
 {
     hipLaunchKernelGGL(dc_poff_tab_kernel, dim3((S.nsub + 1 + WG - 1) / WG), dim3(WG), 0, c->stream, d->doff[0], S, d->poff_tab);
 }
-static DcDown dc_poff_down(DevCoder* d, const DcSub&, bool last, u32*) { return last ? DcDown{} : DcDown{d->hmeta + 32, d->poff, 16 * 4}; }
+static DcDown dc_poff_down(DevCoder* d, const DcSub&, bool last, u32*) { return last ? DcDown{} : DcDown{d->hmeta + HM_POFF, d->poff, 16 * 4}; }
 static DcDown dc_poff_down(DevCoder* d, const DcSubTab& S, bool last, u32* poff_host) { return last ? DcDown{poff_host, d->poff_tab, ((size_t)S.nsub + 1) * 4} : DcDown{}; }
 
-// The buffers of the exact resolve of open chunk starts (3'), on the first evaluation that asks for it.  Do not fit: the option stays
-// without effect (the evaluation is what it is with the option off) — not an error, and not retried.
+// The buffers of the exact resolve of open chunk starts (3'), on the first evaluation that asks for it; false: they do not fit.
 static bool devcoder_rp_ensure(bscgpu_ctx* c, DevCoder* d)
 {
-    if (d->rp_arena) return true;
-    if (d->rp_alloc_failed) return false;
+    if (d->rp_arena.base || d->rp_arena.failed) return !d->rp_arena.failed;
     const size_t slots = 4 * d->nch_cap;
-    const size_t b_map = dc_align(2 * (size_t)DC_RP_CAND * slots), b_head = dc_align(2 * slots), b_st = dc_align(slots);
-    // (BSC_DC_REPLAY_FAIL_ALLOC in the environment: buffers that do not fit, for the test of this exit — what BSC_DEVCODER_FAIL_ALLOC is to the arena)
-    if (getenv("BSC_DC_REPLAY_FAIL_ALLOC") || hipMalloc((void**)&d->rp_arena, b_map + b_head + b_st) != hipSuccess) {
-        (void)hipGetLastError(); d->rp_arena = nullptr; d->rp_alloc_failed = true;
-        return false;
-    }
-    d->rp_bytes = b_map + b_head + b_st;
-    d->rp = new DcRpRec();
-    d->rp->map = reinterpret_cast<u16*>(d->rp_arena); d->rp->head = reinterpret_cast<u16*>(d->rp_arena + b_map); d->rp->st = reinterpret_cast<u8*>(d->rp_arena + b_map + b_head);
+    const Carve carve[] = {{(void**)&d->rp.map, 2 * (size_t)DC_RP_CAND * slots}, {(void**)&d->rp.head, 2 * slots}, {(void**)&d->rp.st, slots}};
+    if (!dc_arena_alloc(d->rp_arena, carve, "BSC_DC_REPLAY_FAIL_ALLOC")) return false;
     // (a lane of dc_rp_map_kernel holds at most DC_RP_CAND / 64 candidates and a slot's map DC_RP_CAND entries: the cap can only be lowered)
-    d->rp->cand = (c->dc_replay_cand == 0 || c->dc_replay_cand > (u32)DC_RP_CAND) ? (u32)DC_RP_CAND : c->dc_replay_cand;
+    d->rp.cand = (c->dc_replay_cand == 0 || c->dc_replay_cand > (u32)DC_RP_CAND) ? (u32)DC_RP_CAND : c->dc_replay_cand;
     return true;
 }
 
@@ -2329,6 +2315,7 @@ static int dc_eval(bscgpu_ctx* c, DevCoder* d, const u32 E[4], const int fam[4],
         A.cstart[job + 1] = A.cstart[job] + (nch + 63) / 64 * 64;           // chunk slots padded to whole wavefronts
     }
     if (A.cstart[4] > 4 * d->nch_cap) return ctx_fail(c, BSC_GPU_ERROR, "device coder: chunk table too small", hipSuccess);
+    // (buffers that do not fit: the option stays without effect — the evaluation is what it is with the option off; not an error)
     const bool resolve = c->dc_replay_exact && A.wstart[4] > 0 && devcoder_rp_ensure(c, d);
     prof_begin(c, BSCGPU_K_DC_EVAL, (u64)(E[0] + E[1] + E[2] + E[3]) * 6, (u64)E[0] + E[1] + E[2] + E[3]);
     if (A.wstart[4] > 0) {
@@ -2342,8 +2329,8 @@ static int dc_eval(bscgpu_ctx* c, DevCoder* d, const u32 E[4], const int fam[4],
         if (resolve) {                                                    // 3': a class of its own in the profile
             prof_end(c);
             prof_begin(c, BSCGPU_K_DC_REPLAY, (u64)A.cstart[4] * 5, A.cstart[4]);
-            hipLaunchKernelGGL(dc_rp_map_kernel, dim3((A.cstart[4] + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, A, mp, d->meta, d->elo, d->ehi, *d->rp);
-            hipLaunchKernelGGL(dc_rp_chain_kernel, dim3((A.cstart[4] + WG - 1) / WG), dim3(WG), 0, c->stream, A, d->meta, d->elo, d->ehi, *d->rp);
+            hipLaunchKernelGGL(dc_rp_map_kernel, dim3((A.cstart[4] + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, A, mp, d->meta, d->elo, d->ehi, d->rp);
+            hipLaunchKernelGGL(dc_rp_chain_kernel, dim3((A.cstart[4] + WG - 1) / WG), dim3(WG), 0, c->stream, A, d->meta, d->elo, d->ehi, d->rp);
             prof_end(c);
             prof_begin(c, BSCGPU_K_DC_EVAL, 0, 0);
         }
@@ -2354,27 +2341,58 @@ static int dc_eval(bscgpu_ctx* c, DevCoder* d, const u32 E[4], const int fam[4],
     return BSC_NO_ERROR;
 }
 
+#if DC_EVAL_TIMING
+// the per-wavefront timing words dc_eval_wave_kernel left in d->cnt (both of its passes), one line per wavefront on stderr
+static void dc_eval_timing_dump(const DevCoder* d)
+{
+    std::vector<u32> h(6 * 4096);
+    (void)hipMemcpy(h.data(), d->cnt, h.size() * 4, hipMemcpyDeviceToHost);
+    const u32 nw = 1100;
+    for (int pass = 0; pass < 2; ++pass) {
+        const u32* t = h.data() + pass * 3 * 4096;
+        u32 t0 = 0xffffffffu; for (u32 i = 0; i < nw && i < 4096; ++i) if (t[3 * i + 1] && t[3 * i] < t0) t0 = t[3 * i];
+        fprintf(stderr, "[eval timing pass %d] wave: start(us) dur(us) maxslowbatches job\n", pass);
+        for (u32 i = 0; i < nw && i < 4096; ++i) if (t[3 * i + 1]) fprintf(stderr, "  %u %.1f %.1f %u %u\n", i, (t[3 * i] - t0) / 100.0, t[3 * i + 1] / 100.0, t[3 * i + 2] & 0xffff, t[3 * i + 2] >> 16);
+    }
+}
+#endif
+
 // ---- the two coders' models, each ONE body for both forms (SB: DcSub, one block's eight sub-blocks; DcSubTab, a pass's or a
 // segment's table) -------------------------------------------------------------------------------------------------------------------
-// Both take the front end's run arrays on the device (sym / rank / start, m runs; n: the block's bytes, 0 for a table, which carries
-// its own ends) with the avg_rank flags and the sub-blocks S, and write *D_out decisions to the device p stream ps[psbuf], the
-// sub-blocks' decision offsets where dc_poff_down says.  The caller has cleared meta (the static coder: present too), and launched
-// what its form needs in front of the items; ctx_open: its contexts bracket is still open and takes the items as well (a single
-// block's flags and items are one bracket).  expect >= 0: the decisions the plan counted for these sub-blocks — the families' totals
-// must equal it.  Every guarded exit declines the whole unit (BSC_NOT_SUPPORTED, c->dc_last_fail says why).  Two syncs: the families'
-// sizes after the partition, the flags after the stream.
+// Both take a unit (DcUnit) with its sub-blocks S and write O.D decisions to the device p stream ps[U.psbuf], the sub-blocks' decision
+// offsets where dc_poff_down says.  The caller has cleared meta (the static coder: present too), and launched what its form needs in
+// front of the items.  Every guarded exit declines the whole unit (BSC_NOT_SUPPORTED, c->dc_note.fail says why).  Two syncs: the
+// families' sizes after the partition, the flags after the stream.
 //
-// The static coder (-e1), the four stages of the file header.  dbg: the debug planes; packed_out non-null: the caller can take the
-// stream at 13 bits per decision (DcP13), *packed_out says whether that is what was written.
+// The unit: the front end's run arrays on the device with the avg_rank flags, and how it runs.
+struct DcUnit {
+    const u8 *sym, *rank; const u32* start; const u8* ge32;      // m runs
+    u32 m, n;                   // n: the block's bytes, 0 for a table, which carries its own ends
+    int psbuf;                  // the device p stream written: ps[psbuf & 1]
+    int64_t expect;             // >= 0: the decisions the plan counted for these sub-blocks — the families' totals must equal it
+    bool ctx_open;              // the caller's contexts bracket of the profile is still open and takes the items as well (a single block)
+};
+// What comes back, and where what comes down to the host goes.  Written on success only.
+struct DcOut {
+    u32  D = 0;                 // decisions written
+    bool take_packed = false;   // in (static coder): the caller can take the stream at 13 bits per decision (DcP13 / DcP13Tab) ...
+    bool packed = false;        // ... and that is what was written
+    u32* poff_host = nullptr;   // a table: poff[0..nsub] (the eight of a block: hmeta[HM_POFF..])
+    u32* pbase_host = nullptr;  // a table, packed: pbase[0..nsub], where the caller keeps the offsets (its end: hmeta[HM_PBASE_END], always)
+    u16* dbg = nullptr;         // the static coder's debug planes (device)
+};
+
+// The static coder (-e1), the four stages of the file header.
 template <class SB>
-static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym, const u8* drank, const u32* dstart, const u8* ge32, u32 m, u32 n,
-                         bool ctx_open, int psbuf, int64_t expect, u32* poff_host, u16* dbg, int* packed_out, u32* D_out, u32* pbase_host = nullptr)
+static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const DcUnit& U, DcOut& O)
 {
     constexpr bool TAB = DcForm<SB>::TAB;
+    const u32 m = U.m;
+    const int psbuf = U.psbuf; u16* const dbg = O.dbg;
     const u32 gm = (m + WG - 1) / WG;
     const u32 gm8 = (gm + 7u) / 8u * 8u;            // kernels that use dc_virtual_block()
-    if (!ctx_open) prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
-    hipLaunchKernelGGL(dc_items_kernel<SB>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, ge32, m, n, S, d->key_ch);
+    if (!U.ctx_open) prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
+    hipLaunchKernelGGL(dc_items_kernel<SB>, dim3(gm), dim3(WG), 0, c->stream, U.sym, U.rank, U.start, U.ge32, m, U.n, S, d->key_ch);
     prof_end(c);
     RadixPass top; top.shift = 56; top.bits = 8;
     int in_alt = 0;
@@ -2400,15 +2418,15 @@ static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym
     dc_launch_partition<2>(c, d, d->key_sn_s, m, S, 3, 0u);
     dc_launch_poff(c, d, S, m);                     // (the sub-blocks' offsets in the stream are known from here on)
     if constexpr (TAB) {                            // ... and where they start in the packed space, if that is what the caller takes
-        if (packed_out) hipLaunchKernelGGL(dc_pbase_tab_kernel, dim3(1), dim3(WG), 0, c->stream, d->poff_tab, S.nsub, d->pad_tab, d->pbase_tab);
+        if (O.take_packed) hipLaunchKernelGGL(dc_pbase_tab_kernel, dim3(1), dim3(WG), 0, c->stream, d->poff_tab, S.nsub, d->pad_tab, d->pbase_tab);
     }
-    rc = dc_meta_down(c, d, dc_poff_down(d, S, false, poff_host));
+    rc = dc_meta_down(c, d, dc_poff_down(d, S, false, O.poff_host));
     if (rc < 0) return rc;
     u32 E[4];
     for (int job = 0; job < 4; ++job) E[job] = d->hmeta[DM_D0 + job];
     const u32 Efull = E[0];                                           // decisions of the block
     if (Efull != E[1] || Efull != E[2] + E[3]) return ctx_fail(c, BSC_GPU_ERROR, "device coder: decision counts of the families differ", hipSuccess);
-    if (expect >= 0 && (int64_t)Efull != expect) return ctx_fail(c, BSC_GPU_ERROR, "device coder: a segment's decisions differ from the plan's count", hipSuccess);
+    if (U.expect >= 0 && (int64_t)Efull != U.expect) return ctx_fail(c, BSC_GPU_ERROR, "device coder: a segment's decisions differ from the plan's count", hipSuccess);
     const int fam[4] = {FAM_STATIC, FAM_CHAR, FAM_STATE, FAM_STATE};
     rc = dc_eval(c, d, E, fam, d->mp, DcForm<SB>::TAB);
     if (rc < 0) return rc;
@@ -2427,13 +2445,13 @@ static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym
         // a pass's or a segment's: the offsets are on the device (dc_pbase_tab_kernel), the host knows only their bound — every sub-block
         // pads by at most 63 decisions.  13 / 8 of that against the 2 Dcap bytes of the buffer: fits whenever Dcap >= 2.2 M decisions
         // (contexts from ~0.5 MiB up), whatever the pass; a pass that does not takes the 2-byte form like a void one
-        packed = packed_out != nullptr && ((u64)Efull + 63ull * S.nsub + 7ull) / 8ull * 13ull <= 2ull * (u64)(d->Dcap + 64);
+        packed = O.take_packed && ((u64)Efull + 63ull * S.nsub + 7ull) / 8ull * 13ull <= 2ull * (u64)(d->Dcap + 64);
         if (packed) { Q.pad = d->pad_tab; Q.out = reinterpret_cast<u8*>(d->ps[psbuf & 1]); Q.frag = d->frag; }
     } else {
         // 13 bits per decision (DcP13) when the caller can take it: not with the debug planes
-        packed = packed_out != nullptr && c->dc_p13 != 0 && dbg == nullptr;
+        packed = O.take_packed && c->dc_p13 != 0 && dbg == nullptr;
         if (packed) {
-            const u32* poff_h = d->hmeta + 32;
+            const u32* poff_h = d->hmeta + HM_POFF;
             u32 pbase = 0;
             for (u32 b = 0; b < S.nb; ++b) { Q.pad[b] = pbase - poff_h[b]; pbase += (poff_h[b + 1] - poff_h[b] + 63u) / 64u * 64u; }
             Q.out = reinterpret_cast<u8*>(d->ps[psbuf & 1]); Q.frag = d->frag;
@@ -2446,14 +2464,14 @@ static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym
         hipLaunchKernelGGL(dc_p13_join_kernel, dim3((gm8 * WAVES + WG - 1) / WG), dim3(WG), 0, c->stream, d->frag, gm8 * WAVES, Q.out, d->meta);
         if constexpr (TAB) {
             hipLaunchKernelGGL(dc_p13_fill_tab_kernel, dim3((S.nsub + WG - 1) / WG), dim3(WG), 0, c->stream, d->poff_tab, d->pbase_tab, S.nsub, Q.out, d->meta);
-            // the layout comes down with the flags: its end for every caller (hmeta[48]), all of it where the caller keeps the offsets
-            HIP_TRY(c, hipMemcpyAsync(d->hmeta + 48, d->pbase_tab + S.nsub, 4, hipMemcpyDeviceToHost, c->stream));
-            if (pbase_host) HIP_TRY(c, hipMemcpyAsync(pbase_host, d->pbase_tab, ((size_t)S.nsub + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+            // the layout comes down with the flags: its end for every caller (hmeta[HM_PBASE_END]), all of it where the caller keeps the offsets
+            HIP_TRY(c, hipMemcpyAsync(d->hmeta + HM_PBASE_END, d->pbase_tab + S.nsub, 4, hipMemcpyDeviceToHost, c->stream));
+            if (O.pbase_host) HIP_TRY(c, hipMemcpyAsync(O.pbase_host, d->pbase_tab, ((size_t)S.nsub + 1) * 4, hipMemcpyDeviceToHost, c->stream));
         }
     }
     if (!packed) hipLaunchKernelGGL((dc_pstream_kernel<false, false, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
     prof_end(c);
-    rc = dc_meta_down(c, d, dc_poff_down(d, S, true, poff_host));
+    rc = dc_meta_down(c, d, dc_poff_down(d, S, true, O.poff_host));
     if (rc < 0) return rc;
     if (packed && d->hmeta[DM_P13_OVER] != 0) {
         // 64 consecutive runs with more decisions than a wavefront's staging buffer holds (runs of thousands): this block's (pass's,
@@ -2465,22 +2483,11 @@ static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, ctx_sync(c));
     }
-    if (packed_out) *packed_out = packed ? 1 : 0;
 #if DC_EVAL_TIMING
-    {
-        std::vector<u32> h(6 * 4096);
-        (void)hipMemcpy(h.data(), d->cnt, h.size() * 4, hipMemcpyDeviceToHost);
-        const u32 nw = 1100;
-        for (int pass = 0; pass < 2; ++pass) {
-            const u32* t = h.data() + pass * 3 * 4096;
-            u32 t0 = 0xffffffffu; for (u32 i = 0; i < nw && i < 4096; ++i) if (t[3 * i + 1] && t[3 * i] < t0) t0 = t[3 * i];
-            fprintf(stderr, "[eval timing pass %d] wave: start(us) dur(us) maxslowbatches job\n", pass);
-            for (u32 i = 0; i < nw && i < 4096; ++i) if (t[3 * i + 1]) fprintf(stderr, "  %u %.1f %.1f %u %u\n", i, (t[3 * i] - t0) / 100.0, t[3 * i + 1] / 100.0, t[3 * i + 2] & 0xffff, t[3 * i + 2] >> 16);
-        }
-    }
+    dc_eval_timing_dump(d);
 #endif
     if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder] runs %u, decisions %u, types %u, rounds %u, chunks replayed %u\n", m, Efull, d->hmeta[DM_NTYPES], d->hmeta[DM_NROUNDS], d->hmeta[DM_REPLAYS]);
-    *D_out = Efull;
+    O.D = Efull; O.packed = packed;
     return BSC_NO_ERROR;
 }
 
@@ -2493,13 +2500,13 @@ static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym
 // tables, no blend: about a third of the static coder's device work.  No avg_rank flags, no run_hist look-back: FAIL_CAP and
 // FAIL_REPLAY are the only flags that can be raised.  The caller has cleared ge32 as well.
 template <class SB>
-static int dc_fast_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym, const u8* drank, const u32* dstart, const u8* ge32, u32 m, u32 n,
-                       bool ctx_open, int psbuf, int64_t expect, u32* poff_host, u32* D_out)
+static int dc_fast_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const DcUnit& U, DcOut& O)
 {
+    const u32 m = U.m;
     const u32 gm = (m + WG - 1) / WG;
     const u32 gm8 = (gm + 7u) / 8u * 8u;            // kernels that use dc_virtual_block()
-    if (!ctx_open) prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 14, m);
-    hipLaunchKernelGGL(dc_items_kernel<SB>, dim3(gm), dim3(WG), 0, c->stream, dsym, drank, dstart, ge32, m, n, S, d->key_ch);
+    if (!U.ctx_open) prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 14, m);
+    hipLaunchKernelGGL(dc_items_kernel<SB>, dim3(gm), dim3(WG), 0, c->stream, U.sym, U.rank, U.start, U.ge32, m, U.n, S, d->key_ch);
     prof_end(c);
     RadixPass top; top.shift = 56; top.bits = 8;
     int in_alt = 0;
@@ -2508,11 +2515,11 @@ static int dc_fast_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym, 
     dc_launch_partition<3, false>(c, d, d->key_ch, m, S, 0, 0u);
     dc_launch_partition<3>(c, d, d->key_ch_s, m, S, 1, 0u);
     dc_launch_poff(c, d, S, m);
-    rc = dc_meta_down(c, d, dc_poff_down(d, S, false, poff_host));
+    rc = dc_meta_down(c, d, dc_poff_down(d, S, false, O.poff_host));
     if (rc < 0) return rc;
     const u32 E[4] = {0u, d->hmeta[DM_D0 + 1], 0u, 0u};
     if (d->hmeta[DM_D0 + 0] != E[1]) return ctx_fail(c, BSC_GPU_ERROR, "device coder (fast): decision counts of stream and chain order differ", hipSuccess);
-    if (expect >= 0 && (int64_t)E[1] != expect) return ctx_fail(c, BSC_GPU_ERROR, "device coder (fast): a segment's decisions differ from the plan's count", hipSuccess);
+    if (U.expect >= 0 && (int64_t)E[1] != U.expect) return ctx_fail(c, BSC_GPU_ERROR, "device coder (fast): a segment's decisions differ from the plan's count", hipSuccess);
     const int fam[4] = {FAM_CHAR, FAM_CHAR, FAM_CHAR, FAM_CHAR};
     rc = dc_eval(c, d, E, fam, d->mp_fast, DcForm<SB>::TAB);
     if (rc < 0) return rc;
@@ -2523,14 +2530,14 @@ static int dc_fast_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const u8* dsym, 
     G.pos_sp = d->pos[1]; G.pos_ch = d->pos[1]; G.pos_sr = d->pos[1]; G.pos_sn = d->pos[1];
     G.V_sp = d->V[1]; G.V_ch = d->V[1]; G.V_sr = d->V[1]; G.V_sn = d->V[1];
     prof_begin(c, BSCGPU_K_DC_PSTREAM, (u64)E[1] * 10, E[1]);
-    rc = dc_ps_wait(c, psbuf);
+    rc = dc_ps_wait(c, U.psbuf);
     if (rc < 0) return rc;
-    hipLaunchKernelGGL((dc_pstream_kernel<true, false, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp_fast, d->meta, d->ps[psbuf & 1], (u16*)nullptr, E[1], typename DcP13Of<SB>::T{});
+    hipLaunchKernelGGL((dc_pstream_kernel<true, false, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp_fast, d->meta, d->ps[U.psbuf & 1], (u16*)nullptr, E[1], typename DcP13Of<SB>::T{});
     prof_end(c);
-    rc = dc_meta_down(c, d, dc_poff_down(d, S, true, poff_host));
+    rc = dc_meta_down(c, d, dc_poff_down(d, S, true, O.poff_host));
     if (rc < 0) return rc;
     if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder fast] runs %u, decisions %u, chunks replayed %u\n", m, E[1], d->hmeta[DM_REPLAYS]);
-    *D_out = E[1];
+    O.D = E[1];
     return BSC_NO_ERROR;
 }
 
@@ -2545,7 +2552,7 @@ static int dc_unit_clear(bscgpu_ctx* c, DevCoder* d, bool kinds_seen)
 
 // Probability stream of a whole block.  Inputs: the QLFC front end's run arrays on the device (sym / rank / start, m runs of
 // the n-byte sorted block), the sub-blocks' run ranges and max_rank values; coder 1: dc_static_run, 3: dc_fast_run.  On success
-// *D_out decisions were written to the device p stream (d->ps) and poff[0..nb] (decision offsets of the sub-blocks) to hmeta[32..];
+// *D_out decisions were written to the device p stream (d->ps) and poff[0..nb] (decision offsets of the sub-blocks) to hmeta[HM_POFF..];
 // returns BSC_NOT_SUPPORTED when the block has to go through the host model instead.
 int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* dstart, u32 m, u32 n, int nb, const u32* run_first,
                      const int* max_rank, u32* D_out, u32* poff_out, u16* dbg, int psbuf, int coder, int* packed_out)
@@ -2554,8 +2561,7 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
     int rc = devcoder_ensure(c);
     if (rc < 0) return rc;
     DevCoder* d = c->dc;
-    c->dc_replays = c->dc_avg_und = c->dc_hist_ext = c->dc_avg_resolved = c->dc_replay_resolved = c->dc_hist_resolved = 0;
-    c->dc_last_fail = m > d->Mcap ? (int)FAIL_CAP : 0;                 // (more runs than the arena holds: capacity, as too many decisions are)
+    c->dc_note.clear(m > d->Mcap ? (int)FAIL_CAP : 0);                 // (more runs than the arena holds: capacity, as too many decisions are)
     if (m == 0 || m > d->Mcap || nb < 1 || nb > 8) return BSC_NOT_SUPPORTED;
     const bool fast = coder == 3;
     DcSub S; S.nb = (u32)nb;
@@ -2575,46 +2581,41 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
         if (rc < 0) { prof_end(c); return rc; }
     } else
         HIP_TRY(c, hipMemsetAsync(d->ge32, 0, m, c->stream));
-    rc = fast ? dc_fast_run(c, d, S, dsym, drank, dstart, d->ge32, m, n, true, psbuf, -1, nullptr, D_out)
-              : dc_static_run(c, d, S, dsym, drank, dstart, d->ge32, m, n, true, psbuf, -1, nullptr, dbg, packed_out, D_out);
+    DcUnit U;
+    U.sym = dsym; U.rank = drank; U.start = dstart; U.ge32 = d->ge32; U.m = m; U.n = n;
+    U.psbuf = psbuf; U.expect = -1; U.ctx_open = true;
+    DcOut O;
+    O.take_packed = packed_out != nullptr; O.dbg = dbg;
+    rc = fast ? dc_fast_run(c, d, S, U, O) : dc_static_run(c, d, S, U, O);
     if (rc < 0) return rc;
-    for (int b = 0; b <= nb; ++b) poff_out[b] = d->hmeta[32 + b];
+    *D_out = O.D;
+    if (packed_out) *packed_out = O.packed ? 1 : 0;
+    for (int b = 0; b <= nb; ++b) poff_out[b] = d->hmeta[HM_POFF + b];
     return BSC_NO_ERROR;
 }
 
 // ---- the model of a whole batched pass ------------------------------------------------------------------------------
 // What the wider chain identity needs on top of the arena, on the first pass that takes this route: every event's full sub-block
 // id (2 bytes per decision and family = 8 Dcap bytes, ~32 bytes per byte of max_n), max_rank and stream offset per sub-block.
-// Does not fit: the pass is declined (its blocks take the host model), not an error, and not retried per pass.
-static int devcoder_batch_ensure(bscgpu_ctx* c, DevCoder* d)
+// false: it does not fit.
+static bool devcoder_batch_ensure(DevCoder* d)
 {
-    if (d->batch_arena) return BSC_NO_ERROR;
-    if (d->batch_alloc_failed) return BSC_NOT_SUPPORTED;
+    if (d->batch_arena.base || d->batch_arena.failed) return !d->batch_arena.failed;
     CtxTimer tm("devcoder_batch_ensure (sub-block ids of the events)");
     const size_t D = d->Dcap + 64;
-    struct Carve { void** p; size_t bytes; };
-    Carve carve[] = {
+    const Carve carve[] = {
         {(void**)&d->esub[0], 2 * D}, {(void**)&d->esub[1], 2 * D}, {(void**)&d->esub[2], 2 * D}, {(void**)&d->esub[3], 2 * D},
         {(void**)&d->sub_maxr, (size_t)FRONT_MAX_SUB + 64}, {(void**)&d->poff_tab, 4 * ((size_t)FRONT_MAX_SUB + 64)},
         {(void**)&d->sub_und, 4 * ((size_t)FRONT_MAX_SUB + 64)}, {(void**)&d->sub_dec, 4 * ((size_t)FRONT_MAX_SUB + 64)},
         {(void**)&d->seg_run, 4 * ((size_t)FRONT_MAX_SUB + 64)},
         {(void**)&d->pad_tab, 4 * ((size_t)FRONT_MAX_SUB + 64)}, {(void**)&d->pbase_tab, 4 * ((size_t)FRONT_MAX_SUB + 64)},
     };
-    size_t total = 0;
-    for (auto& cv : carve) total += dc_align(cv.bytes);
-    if (hipMalloc((void**)&d->batch_arena, total) != hipSuccess) {
-        (void)hipGetLastError(); d->batch_arena = nullptr; d->batch_alloc_failed = true;
-        return BSC_NOT_SUPPORTED;
-    }
-    d->batch_bytes = total;
-    size_t off = 0;
-    for (auto& cv : carve) { *cv.p = d->batch_arena + off; off += dc_align(cv.bytes); }
-    return BSC_NO_ERROR;
+    return dc_arena_alloc(d->batch_arena, carve, nullptr);
 }
 
 // What the entry points of a pass share: the arenas, the pass as qlfc_front_batch left it — the run arrays (vA / vB / SA: the buffers
 // the single path reads) and its table in front_tab, with max_rank per sub-block where dc_tab_prep_kernel will put it.
-// over_fail >= 0: the call is a model run, which clears what the context says about its last block; over_fail is what dc_last_fail
+// over_fail >= 0: the call is a model run, which clears what the context says about its last block; over_fail is what dc_note.fail
 // then says about a pass of more runs than the arena holds (a whole pass: FAIL_CAP, as devcoder_pstream; segments: 0).
 struct DcPass { DevCoder* d; FrontTab T; DcSubTab S; const u8 *dsym, *drank; const u32* dstart; };
 static int dc_pass_begin(bscgpu_ctx* c, u32 m, int nsub, int over_fail, DcPass* P)
@@ -2622,17 +2623,21 @@ static int dc_pass_begin(bscgpu_ctx* c, u32 m, int nsub, int over_fail, DcPass* 
     int rc = devcoder_ensure(c);
     if (rc < 0) return rc;
     DevCoder* d = c->dc;
-    if (over_fail >= 0) {
-        c->dc_replays = c->dc_avg_und = c->dc_hist_ext = c->dc_avg_resolved = c->dc_replay_resolved = c->dc_hist_resolved = 0;
-        c->dc_last_fail = m > d->Mcap ? over_fail : 0;
-    }
+    if (over_fail >= 0) c->dc_note.clear(m > d->Mcap ? over_fail : 0);
     if (m == 0 || m > d->Mcap || nsub < 1 || nsub > FRONT_MAX_SUB || !c->front_tab) return BSC_NOT_SUPPORTED;
-    rc = devcoder_batch_ensure(c, d);
-    if (rc < 0) return rc;
+    if (!devcoder_batch_ensure(d)) return BSC_NOT_SUPPORTED;             // does not fit: the pass is declined (its blocks take the host model), not an error
     P->d = d; P->T = qlfc_front_tab(c, nsub);
     P->dsym = reinterpret_cast<const u8*>(c->vA); P->drank = reinterpret_cast<const u8*>(c->vB); P->dstart = c->SA;
     P->S.nsub = (u32)nsub; P->S.run = P->T.sub_run; P->S.off = P->T.sub_off; P->S.base = P->T.sub_base; P->S.maxr = d->sub_maxr;
     return BSC_NO_ERROR;
+}
+// Runs [r0, r1) of the pass as a unit of their own (all of it: [0, m)): the run arrays and the flags offset to its first run
+static DcUnit dc_pass_range(const DcPass& P, u32 r0, u32 r1, int psbuf, int64_t expect)
+{
+    DcUnit U;
+    U.sym = P.dsym + r0; U.rank = P.drank + r0; U.start = P.dstart + r0; U.ge32 = P.d->ge32 + r0; U.m = r1 - r0; U.n = 0u;
+    U.psbuf = psbuf; U.expect = expect; U.ctx_open = false;
+    return U;
 }
 // ... and what every model of the pass reads: max_rank per sub-block and the rebased run table, then the avg_rank >= 32 flags.  The
 // static coder walks them always (which sub-blocks can escape is not known on the host here; one of at most 32 symbols never leaves a
@@ -2650,7 +2655,7 @@ static int dc_pass_tables(bscgpu_ctx* c, const DcPass& P, u32 m, bool fast, u32*
 // Probability stream of a whole pass, coder 1 (dc_static_run) or 3 (dc_fast_run) -> every sub-block's entries back to back in stream
 // order in the device p stream (buffer 0), poff[0..nsub] in d->poff_tab.  The same stages, the same kernels as a single block's,
 // instantiated for the table (DcSubTab); every guarded exit keeps its meaning with the PASS as the unit: a raised flag declines the
-// whole pass (BSC_NOT_SUPPORTED, c->dc_last_fail says why).  The arena of devcoder_batch_ensure serves both coders (the fast one uses
+// whole pass (BSC_NOT_SUPPORTED, c->dc_note.fail says why).  The arena of devcoder_batch_ensure serves both coders (the fast one uses
 // one esub plane of its four, and max_rank 7 for every sub-block).
 // packed_out non-null (coder 1 only): the caller can take the stream at 13 bits per decision (DcP13Tab); *packed_out says whether that
 // is what lies in the buffer — pbase[0..nsub] in d->pbase_tab, its end in *pbytes_out as bytes — or the 2-byte form after all (void).
@@ -2668,10 +2673,15 @@ int devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* D_out
     rc = dc_pass_tables(c, P, m, fast, nullptr);
     prof_end(c);
     if (rc < 0) return rc;
-    if (fast) return dc_fast_run(c, d, P.S, P.dsym, P.drank, P.dstart, d->ge32, m, 0u, false, 0, -1, nullptr, D_out);
-    const int src = dc_static_run(c, d, P.S, P.dsym, P.drank, P.dstart, d->ge32, m, 0u, false, 0, -1, nullptr, nullptr, packed_out, D_out);
-    if (src >= 0 && packed_out && *packed_out && pbytes_out) *pbytes_out = (int64_t)d->hmeta[48] / 8 * 13;
-    return src;
+    const DcUnit U = dc_pass_range(P, 0u, m, 0, -1);
+    DcOut O;
+    O.take_packed = !fast && packed_out != nullptr;
+    rc = fast ? dc_fast_run(c, d, P.S, U, O) : dc_static_run(c, d, P.S, U, O);
+    if (rc < 0) return rc;
+    *D_out = O.D;
+    if (packed_out) *packed_out = O.packed ? 1 : 0;
+    if (O.packed && pbytes_out) *pbytes_out = (int64_t)d->hmeta[HM_PBASE_END] / 8 * 13;
+    return rc;
 }
 const u32* devcoder_batch_poff_ptr(const bscgpu_ctx* c) { return c->dc ? c->dc->poff_tab : nullptr; }
 const u32* devcoder_batch_pbase_ptr(const bscgpu_ctx* c) { return c->dc ? c->dc->pbase_tab : nullptr; }
@@ -2696,7 +2706,8 @@ const u32* devcoder_batch_pbase_ptr(const bscgpu_ctx* c) { return c->dc ? c->dc-
 // Every decision of the above that is arithmetic — what runs next, whether it fits, where a declined range is cut and when it is
 // given up, where kept entries land, poff / pbase — is DcSegSchedule's (dc_segment_plan.h); the driver below launches, copies and tells.
 // the facts of a pass (after qlfc_front_batch): dec[s] / und[s] of every sub-block on the host; ge32 and sub_maxr stay for the segments
-static int dc_segment_facts(bscgpu_ctx* c, const DcPass& P, u32 m, bool fast, u32* dec, u32* und, u32* avg_open = nullptr, u32* avg_resolved = nullptr)
+// note non-null: its avg_und and avg_resolved are the pass's — the flags the bracket left open, and what the exact resolve settled of them
+static int dc_segment_facts(bscgpu_ctx* c, const DcPass& P, u32 m, bool fast, u32* dec, u32* und, DcNote* note = nullptr)
 {
     DevCoder* d = P.d;
     const int nsub = (int)P.S.nsub;
@@ -2713,10 +2724,15 @@ static int dc_segment_facts(bscgpu_ctx* c, const DcPass& P, u32 m, bool fast, u3
     HIP_TRY(c, hipMemcpyAsync(und, d->sub_und, (size_t)nsub * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(dec, d->sub_dec, (size_t)nsub * 4, hipMemcpyDeviceToHost, c->stream));
     // (behind the exact resolve und[] is what it left: what the bracket had left open, and what was settled, are meta words)
-    if (c->dc_avg_exact && avg_open) HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
+    if (c->dc_avg_exact && note) HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
     prof_collect(c);
-    if (c->dc_avg_exact && avg_open) { *avg_open = d->hmeta[DM_AVG_UND]; *avg_resolved = d->hmeta[DM_AVG_RESOLVED]; }
+    if (note && c->dc_avg_exact) { note->avg_und = (int)d->hmeta[DM_AVG_UND]; note->avg_resolved = (int)d->hmeta[DM_AVG_RESOLVED]; }
+    else if (note) {
+        int64_t und_total = 0;
+        for (int s = 0; s < nsub; ++s) und_total += und[s];
+        note->avg_und = (int)und_total; note->avg_resolved = 0;
+    }
     return BSC_NO_ERROR;
 }
 int devcoder_segment_facts(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* dec, u32* und)
@@ -2759,9 +2775,9 @@ struct DcCopyRing {
 };
 
 // The ranges of the schedule one after the other, launch by launch; out: the landing buffer (host), 2-byte entries or the packed
-// form's bytes (pk).  *replays / *hist_ext: what the kept and the declined runs counted together.
+// form's bytes (pk).  sum: what the kept and the declined runs counted together (replays, hist_ext and what the two resolves settled).
 static int dc_segments_loop(bscgpu_ctx* c, const DcPass& P, bool fast, bool pk, const u32* sub_run, DcSegSchedule& sch, DcCopyRing& ring, u8* out,
-                            int* replays, int* hist_ext, int* replay_resolved, int* hist_resolved)
+                            DcNote& sum)
 {
     DevCoder* d = P.d;
     std::vector<u32> pseg((size_t)P.S.nsub + 1), pbseg(pk ? (size_t)P.S.nsub + 1 : 0);
@@ -2780,22 +2796,23 @@ static int dc_segments_loop(bscgpu_ctx* c, const DcPass& P, bool fast, bool pk, 
         hipLaunchKernelGGL(dc_seg_tab_kernel, dim3(((u32)(s1 - s0) + 1 + WG - 1) / WG), dim3(WG), 0, c->stream, P.T.sub_run, (u32)s0, (u32)(s1 - s0), r0, r1, d->seg_run);
         prof_end(c);
         HIP_TRY(c, hipStreamWaitEvent(c->stream, d->seg_ev[psbuf], 0));          // this buffer's copy-out of two segments ago
-        // (the segment's rebased table, the pass's run arrays and flags offset to its first run)
+        // (the segment's rebased table; its runs as a unit)
         DcSubTab G; G.nsub = (u32)(s1 - s0); G.run = d->seg_run; G.off = P.T.sub_off + s0; G.base = P.T.sub_base + s0; G.maxr = d->sub_maxr + s0;
-        u32 D = 0;
-        int packed = 0;
-        rc = fast ? dc_fast_run(c, d, G, P.dsym + r0, P.drank + r0, P.dstart + r0, d->ge32 + r0, r1 - r0, 0u, false, psbuf, g.expect, pseg.data(), &D)
-                  : dc_static_run(c, d, G, P.dsym + r0, P.drank + r0, P.dstart + r0, d->ge32 + r0, r1 - r0, 0u, false, psbuf, g.expect, pseg.data(), nullptr,
-                                  pk ? &packed : nullptr, &D, pk ? pbseg.data() : nullptr);
-        *replays += c->dc_replays; *hist_ext += c->dc_hist_ext; *replay_resolved += c->dc_replay_resolved; *hist_resolved += c->dc_hist_resolved;
-        if (rc == BSC_NOT_SUPPORTED) { if (sch.declined(g, c->dc_last_fail)) ring.settle(g); continue; }
+        const DcUnit U = dc_pass_range(P, r0, r1, psbuf, g.expect);
+        DcOut O;
+        O.take_packed = pk; O.poff_host = pseg.data(); O.pbase_host = pk ? pbseg.data() : nullptr;
+        rc = fast ? dc_fast_run(c, d, G, U, O) : dc_static_run(c, d, G, U, O);
+        const DcNote& run = c->dc_note;
+        sum.replays += run.replays; sum.hist_ext += run.hist_ext; sum.replay_resolved += run.replay_resolved; sum.hist_resolved += run.hist_resolved;
+        if (rc == BSC_NOT_SUPPORTED) { if (sch.declined(g, run.fail)) ring.settle(g); continue; }
         if (rc < 0) return rc;
+        const u32 D = O.D;
         // this buffer's earlier copy-out has landed (the stream kernel waited for it), maybe the other one's too
         HIP_TRY(c, ring.landed(psbuf));
-        const int64_t at = sch.kept(g, D, pseg.data(), packed ? pbseg.data() : nullptr, packed != 0);
+        const int64_t at = sch.kept(g, D, pseg.data(), O.packed ? pbseg.data() : nullptr, O.packed);
         if (at < 0) return ctx_fail(c, BSC_GPU_ERROR, "device coder: a segment's packed layout differs from the plan's", hipSuccess);
         if (!sch.copy_all() || D == 0) ring.settle(g);
-        else if (pk && !packed) {
+        else if (pk && !O.packed) {
             // void: the 2-byte form lies in ps[psbuf] (dc_static_run re-launched it); down, and packed into place on the host
             void_entries.resize((size_t)D); void_pbase.resize((size_t)(s1 - s0) + 1);
             HIP_TRY(c, hipMemcpyAsync(void_entries.data(), d->ps[psbuf], (size_t)D * 2, hipMemcpyDeviceToHost, c->stream));
@@ -2827,23 +2844,20 @@ int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub
     const bool fast = coder == 3;                                      // LIBBSC_CODER_QLFC_FAST
 
     std::vector<u32> und((size_t)nsub), dec((size_t)nsub);
-    u32 avg_open = 0, avg_resolved = 0;
-    rc = dc_segment_facts(c, P, m, fast, dec.data(), und.data(), &avg_open, &avg_resolved);
+    DcNote sum;                                                        // the pass's: avg values from the facts, the rest summed over its segments
+    rc = dc_segment_facts(c, P, m, fast, dec.data(), und.data(), &sum);
     if (rc < 0) return rc;
-    int64_t und_total = 0;
-    for (int s = 0; s < nsub; ++s) und_total += und[s];
-    if (c->dc_avg_exact) und_total = avg_open;
 
     DcSegSchedule sch(dec.data(), und.data(), blk_sub, count, nsub, (int64_t)d->Dcap, target, cap, per_segment_fit, (int)FAIL_AVG, (int)FAIL_CAP, poff, pbase, blk_state);
     if (note) note->planned(note->user);
     DcCopyRing ring{d->seg_ev, c->copy_stream, note, {}};
-    int replays = 0, hist_ext = 0, replay_resolved = 0, hist_resolved = 0;
-    rc = dc_segments_loop(c, P, fast, pk, sub_run, sch, ring, static_cast<u8*>(out), &replays, &hist_ext, &replay_resolved, &hist_resolved);
+    rc = dc_segments_loop(c, P, fast, pk, sub_run, sch, ring, static_cast<u8*>(out), sum);
     // (no copy into the caller's buffer may outlive the call, whichever way it ends)
     if (hipStreamSynchronize(c->copy_stream) != hipSuccess && rc >= 0) rc = ctx_fail(c, BSC_GPU_ERROR, "device coder: segment copy-out", hipSuccess);
     if (rc < 0) return rc;
     const DcSegTotals T = sch.finish();
-    c->dc_last_fail = T.fail; c->dc_replays = replays; c->dc_hist_ext = hist_ext; c->dc_avg_und = (int)und_total; c->dc_avg_resolved = (int)avg_resolved; c->dc_replay_resolved = replay_resolved; c->dc_hist_resolved = hist_resolved;
+    sum.fail = T.fail;
+    c->dc_note = sum;
     c->cnt_seg += T.kept; c->cnt_seg_reruns += T.reruns; c->cnt_seg_host_blocks += T.host_blocks;
     c->cnt_packed_passes += T.kept_packed; c->cnt_packed_void += T.kept_void;
     if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder segments] sub-blocks %d, planned %d, kept %d, re-runs %d, blocks left to the host %d, decisions %lld\n", nsub, T.planned, T.kept, T.reruns, T.host_blocks, (long long)T.decisions);
@@ -2887,7 +2901,7 @@ static int64_t qlfc_static_pstream_stage(bscgpu_ctx* c, const uint8_t* L, int n,
                           want_packed ? &packed : nullptr);
     if (rc == BSC_NO_ERROR && want_packed && !packed) { c->err = "the packed stream was not produced (option off, or a wavefront's piece beyond the staging buffer)"; rc = BSC_NOT_SUPPORTED; }
     else if (rc == BSC_NOT_SUPPORTED) {
-        char buf[96]; snprintf(buf, sizeof buf, "device coder declined the block (reason mask %d)", c->dc_last_fail);
+        char buf[96]; snprintf(buf, sizeof buf, "device coder declined the block (reason mask %d)", c->dc_note.fail);
         c->err = buf;
     }
     if (rc < 0) { if (ddbg) hipFree(ddbg); return rc; }

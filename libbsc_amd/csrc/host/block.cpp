@@ -1872,7 +1872,7 @@ static int64_t pstream_batch_device(bscgpu_ctx* c, const void* dL, const int* si
     u32 D = 0;
     const int rc = devcoder_pstream_batch(c, (u32)out->m, out->nsub, coder, &D);
     if (rc == LIBBSC_NOT_SUPPORTED) {
-        char buf[96]; snprintf(buf, sizeof buf, "device coder declined the pass (reason mask %d)", c->dc_last_fail);
+        char buf[96]; snprintf(buf, sizeof buf, "device coder declined the pass (reason mask %d)", c->dc_note.fail);
         c->err = buf;
     }
     if (rc < 0) return rc;
@@ -1904,7 +1904,7 @@ extern "C" BSCGPU_API int64_t bscgpu_static_pstream_batch_packed_device(bscgpu_c
     int pk = 0; int64_t bytes = 0;
     int rc = devcoder_pstream_batch(c, (u32)out->m, out->nsub, LIBBSC_CODER_QLFC_STATIC, &D, &pk, &bytes);
     if (rc == LIBBSC_NOT_SUPPORTED) {
-        char buf[96]; snprintf(buf, sizeof buf, "device coder declined the pass (reason mask %d)", c->dc_last_fail);
+        char buf[96]; snprintf(buf, sizeof buf, "device coder declined the pass (reason mask %d)", c->dc_note.fail);
         c->err = buf;
     }
     if (rc < 0) return rc;

@@ -277,3 +277,32 @@ def test_option_keys_and_environment(ctx, monkeypatch):
     finally:
         c.close()
     assert ctx.arena_bytes == a0
+
+
+def test_buffers_that_do_not_fit_decline_the_unit(monkeypatch):
+    """BSC_DC_AVG_FAIL_ALLOC: the resolve's buffers do not fit.  A block that leaves flags open is declined with no reason bit (an arena
+    did not fit), nothing is allocated, now or at the next call; with the option off the same context declines it with FAIL_AVG"""
+    from libbsc_amd import GpuContext
+    from libbsc_amd.gpu import GpuError
+    L = GENERATOR_BLOCKS[ar.FAIL_AVG_GENERATORS[0]]()
+    monkeypatch.setenv("BSC_DC_AVG_FAIL_ALLOC", "1")
+    c = GpuContext(0, max_n=1 << 20)
+    try:
+        c.option_set(c.OPT_DC_AVG_EXACT, 1)
+        c.qlfc_static_pstream((np.arange(50_000) % 3).astype(np.uint8))      # (no sub-block can escape: the flags are not walked)
+        a1 = c.arena_bytes
+        for call in range(2):
+            with pytest.raises(GpuError) as e:
+                c.qlfc_static_pstream(L)
+            got = _avg_counters(c)
+            print(f"call {call}: code {e.value.code}, gpu {got}, arena bytes {c.arena_bytes} (before: {a1})")
+            assert e.value.code == NOT_SUPPORTED and got["fail"] == 0 and got["resolved"] == 0
+            assert c.arena_bytes == a1, "no buffers, and no second attempt"
+        c.option_set(c.OPT_DC_AVG_EXACT, 0)
+        with pytest.raises(GpuError) as e:
+            c.qlfc_static_pstream(L)
+        got = _avg_counters(c)
+        assert e.value.code == NOT_SUPPORTED and got["fail"] == c.DC_FAIL_AVG and got["und"] > 0 and got["resolved"] == 0, got
+        assert c.arena_bytes == a1
+    finally:
+        c.close()

@@ -290,3 +290,28 @@ def test_option_keys_and_environment(ctx, monkeypatch):
     finally:
         c.close()
     assert ctx.arena_bytes == a0
+
+
+def test_buffers_that_do_not_fit_leave_the_option_without_effect(monkeypatch):
+    """BSC_DC_HIST_FAIL_ALLOC: the resolve's buffers do not fit.  A block whose brackets the nine predecessors leave open comes out as
+    from a context with the option off: the same entries, the same seven counters, the same bytes of arena"""
+    from libbsc_amd import GpuContext
+    L = di.GENERATORS["hist_q9216"][2]()
+    monkeypatch.setenv("BSC_DC_HIST_FAIL_ALLOC", "1")
+    seen = []
+    for option in (0, 1):
+        c = GpuContext(0, max_n=1 << 20)
+        try:
+            c.option_set(c.OPT_DC_HIST_EXACT, option)
+            ps, st, sz, poff, _ = c.qlfc_static_pstream(L)
+            keys = (c.CNT_DC_LAST_FAIL, c.CNT_DC_REPLAYS, c.CNT_DC_AVG_UNDECIDED, c.CNT_DC_AVG_RESOLVED, c.CNT_DC_REPLAY_RESOLVED,
+                    c.CNT_DC_HIST_EXTENDED, c.CNT_DC_HIST_RESOLVED)
+            seen.append((ps, list(st), list(sz), list(poff), [c.option_get(k) for k in keys], c.arena_bytes))
+        finally:
+            c.close()
+    off, on_ = seen
+    print(f"counters: option off {off[4]}, option on {on_[4]}; arena bytes {off[5]} / {on_[5]}")
+    assert off[4][0] == 0 and off[4][5] > 0, "the input: kept, with open brackets"
+    assert on_[4] == off[4] and on_[4][6] == 0
+    assert np.array_equal(on_[0], off[0]) and on_[1:4] == off[1:4]
+    assert on_[5] == off[5]
