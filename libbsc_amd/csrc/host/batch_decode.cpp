@@ -17,11 +17,10 @@
 #include "../device/dev_common.h"
 #include "qlfc.h"
 #include "lzp.h"
+#include "container.h"
 #include "par.h"
 
 using namespace bschost;
-
-static inline int rd32(const unsigned char* p) { int v; memcpy(&v, p, 4); return v; }
 
 extern "C" BSCGPU_API int bscgpu_unbwt_batch_plan(const int* sizes, int count, int64_t cap, int* pass_of)
 {
@@ -83,13 +82,14 @@ static int decompress_batch_impl(bscgpu_ctx* c, const unsigned char* input, cons
     const bool dev = dOut != nullptr;
     std::vector<int64_t> in_off((size_t)count + 1, 0), out_off((size_t)count + 1, 0);
     std::vector<int> bound((size_t)count, -1), pass_of((size_t)count);
+    std::vector<BlockFields> hdr((size_t)count);                    // of the blocks with a bound
     for (int b = 0; b < count; ++b) {
         in_off[b + 1] = in_off[b] + in_sizes[b];
         out_off[b + 1] = out_off[b] + ds[b];
         const unsigned char* in = input + in_off[b];
         int bs = 0, d = 0;
         if (in_sizes[b] >= LIBBSC_HEADER_SIZE && bsc_block_info(in, in_sizes[b], &bs, &d, features) == LIBBSC_NO_ERROR
-            && in_sizes[b] >= bs && bs >= LIBBSC_HEADER_SIZE + 2 && (rd32(in + 8) & 0x1f) == LIBBSC_BLOCKSORTER_BWT)
+            && in_sizes[b] >= bs && block_header_read(in, &hdr[b]) && block_holds_payload(hdr[b]) && block_mode_unpack(hdr[b].mode).sorter == LIBBSC_BLOCKSORTER_BWT)
             bound[b] = d;                                        // the QLFC decoders write at most dataSize bytes (bsc_decompress's bound)
     }
     const int npass = bscgpu_unbwt_batch_plan(bound.data(), count, c->max_n, pass_of.data());
@@ -121,14 +121,10 @@ static int decompress_batch_impl(bscgpu_ctx* c, const unsigned char* input, cons
         const int qf = k < threads ? features : features & ~LIBBSC_FEATURE_MULTITHREADING;
         run_bounded(k, threads, [&](int i) {
             const int b = P.m[i];
-            const unsigned char* in = input + in_off[b];
-            const int bs = rd32(in);
-            if ((unsigned)rd32(in + 20) != adler32(in + LIBBSC_HEADER_SIZE, (size_t)(bs - LIBBSC_HEADER_SIZE))) return;
-            const int num_indexes = in[bs - 1];
-            const long long payload = (long long)bs - LIBBSC_HEADER_SIZE - 1 - 4LL * num_indexes;
-            if (payload < 1) return;
-            const int lz = coder_decompress_bounded(in + LIBBSC_HEADER_SIZE, payload, hb + P.at[i], (rd32(in + 8) >> 5) & 0x7, qf, bound[b]);
-            const int index = rd32(in + 12);
+            CodedPayload pay;
+            if (block_coded_payload(input + in_off[b], hdr[b], &pay) != LIBBSC_NO_ERROR) return;
+            const int lz = coder_decompress_bounded(pay.data, pay.size, hb + P.at[i], block_mode_unpack(hdr[b].mode).coder, qf, bound[b]);
+            const int index = hdr[b].index;
             if (lz < 2 || index <= 0 || index > lz) return;
             P.lz[i] = lz; P.idx[i] = index;
         });
@@ -168,7 +164,7 @@ static int decompress_batch_impl(bscgpu_ctx* c, const unsigned char* input, cons
         for (int j = 0; j < k; ++j) {
             const int i = g[j], b = P.m[i];
             if (res[j] != LIBBSC_NO_ERROR) continue;
-            const bool lzp = (rd32(input + in_off[b] + 8) >> 8) != 0;
+            const bool lzp = block_mode_has_lzp(hdr[b].mode);
             hipError_t e = hipSuccess;
             if (dev && lzp) e = hipMemcpyAsync(hb + P.at[i], out + dst[j], (size_t)P.lz[i], hipMemcpyDeviceToHost, c->stream);
             else if (dev && !direct) e = hipMemcpyAsync(dOut + out_off[b], out + dst[j], (size_t)P.lz[i], hipMemcpyDeviceToDevice, c->stream);
@@ -180,9 +176,9 @@ static int decompress_batch_impl(bscgpu_ctx* c, const unsigned char* input, cons
         run_bounded(k, threads, [&](int j) {
             const int i = g[j], b = P.m[i];
             if (res[j] != LIBBSC_NO_ERROR) { own[b] = 1; return; }   // DATA_CORRUPT / NOT_SUPPORTED: bsc_decompress decides
-            const unsigned char* in = input + in_off[b];
-            const int mode = rd32(in + 8), lzpHashSize = (mode >> 16) & 0xff, lzpMinLen = (mode >> 8) & 0xff, n = ds[b];
-            const unsigned adler_data = (unsigned)rd32(in + 16);
+            const BlockMode m = block_mode_unpack(hdr[b].mode);
+            const int lzpHashSize = m.lzp_hash, lzpMinLen = m.lzp_min, n = ds[b];
+            const unsigned adler_data = hdr[b].adler_data;
             if (lzpHashSize == 0 && lzpMinLen == 0) {
                 if (P.lz[i] != n) { results[b] = LIBBSC_DATA_CORRUPT; return; }
                 if (!dev) memcpy(output + out_off[b], hb + P.at[i], (size_t)n);

@@ -11,15 +11,9 @@
 
 #include "../../../include/libbsc.h"
 #include "../../../include/bscgpu.h"
+#include "container.h"          // aux_rate
 
 constexpr int BATCH_PASS_MAX_BLOCKS = BSCGPU_ST_BATCH_MAX_BLOCKS;      // blocks of a pass, empty ones included: BWT and ST alike
-
-static inline int aux_rate(int n)          // largest power of two <= n / 8 (>= 1), bwt.cpp:192-197
-{
-    int mod = n / 8;
-    mod |= mod >> 1; mod |= mod >> 2; mod |= mod >> 4; mod |= mod >> 8; mod |= mod >> 16; mod >>= 1;
-    return mod + 1;
-}
 
 // ---- pass membership and ranges ---------------------------------------------------------------------------------------------------
 // Consecutive members (member(n): a block of n > 0 bytes that the pass's sorter takes) fill passes of at most cap bytes and

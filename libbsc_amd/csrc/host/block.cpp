@@ -27,6 +27,7 @@
 #include "../device/dma_copy.h"
 #include "../device/dc_segment_plan.h"
 #include "batch_pass_plan.h"
+#include "container.h"
 #include "qlfc.h"
 #include "lzp.h"
 #include "par.h"
@@ -181,9 +182,6 @@ struct DefaultGpuUser {                         // RAII around acquire / release
     ~DefaultGpuUser() { if (rc == LIBBSC_NO_ERROR) default_gpu_release(dev, slot); }
 };
 
-static inline void put_i32(unsigned char* p, int v) { memcpy(p, &v, 4); }
-static inline int  get_i32(const unsigned char* p) { int v; memcpy(&v, p, 4); return v; }
-
 extern "C" {
 
 int bsc_init_full(int features, void* (*malloc_fn)(size_t), void* (*zero_malloc_fn)(size_t), void (*free_fn)(void*))
@@ -271,51 +269,46 @@ int bsc_st_encode(unsigned char* T, int n, int k, int features)
 int bsc_store(const unsigned char* input, unsigned char* output, int n, int)
 {
     const unsigned a = adler32(input, (size_t)n);
-    memmove(output + LIBBSC_HEADER_SIZE, input, (size_t)n);
-    put_i32(output + 0, n + LIBBSC_HEADER_SIZE);
-    put_i32(output + 4, n);
-    put_i32(output + 8, 0);
-    put_i32(output + 12, 0);
-    put_i32(output + 16, (int)a);
-    put_i32(output + 20, (int)a);
-    put_i32(output + 24, (int)adler32(output, 24));
-    return n + LIBBSC_HEADER_SIZE;
+    memmove(block_body(output), input, (size_t)n);
+    return block_finish_stored(output, n, a);
+}
+
+// the stored rule (libbsc.cpp:188) for a block whose input is in HBM: one copy of it straight into the output region
+static int store_from_device(bscgpu_ctx* c, const void* dIn, unsigned char* output, int n, unsigned adler)
+{
+    if (hipSetDevice(c->device) != hipSuccess || hipMemcpy(block_body(output), dIn, (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+        return LIBBSC_GPU_ERROR;
+    return block_finish_stored(output, n, adler);
 }
 
 static int make_mode(int sorter, int coder, int lzpHashSize, int lzpMinLen, int* mode_out)
 {
-    int mode;
-    if (sorter == LIBBSC_BLOCKSORTER_BWT || (sorter >= LIBBSC_BLOCKSORTER_ST3 && sorter <= LIBBSC_BLOCKSORTER_ST8)) mode = sorter;
-    else return LIBBSC_BAD_PARAMETER;
+    if (sorter != LIBBSC_BLOCKSORTER_BWT && (sorter < LIBBSC_BLOCKSORTER_ST3 || sorter > LIBBSC_BLOCKSORTER_ST8)) return LIBBSC_BAD_PARAMETER;
     if (coder < LIBBSC_CODER_QLFC_STATIC || coder > LIBBSC_CODER_QLFC_FAST) return LIBBSC_BAD_PARAMETER;
-    mode += coder << 5;
     if (lzpMinLen != 0 || lzpHashSize != 0) {
         if (lzpMinLen < 4 || lzpMinLen > 255) return LIBBSC_BAD_PARAMETER;
         if (lzpHashSize < 10 || lzpHashSize > 28) return LIBBSC_BAD_PARAMETER;
-        mode += (lzpMinLen << 8) + (lzpHashSize << 16);
     }
-    *mode_out = mode;
+    *mode_out = block_mode_pack(BlockMode{sorter, coder, lzpHashSize, lzpMinLen});
     return LIBBSC_NO_ERROR;
 }
 
 int bsc_block_info(const unsigned char* hdr, int headerSize, int* pBlockSize, int* pDataSize, int)
 {
     if (headerSize < LIBBSC_HEADER_SIZE) return LIBBSC_UNEXPECTED_EOB;
-    if ((unsigned)get_i32(hdr + 24) != adler32(hdr, 24)) return LIBBSC_DATA_CORRUPT;
-    const int blockSize = get_i32(hdr + 0), dataSize = get_i32(hdr + 4), mode = get_i32(hdr + 8), index = get_i32(hdr + 12);
-    const int lzpHashSize = (mode >> 16) & 0xff, lzpMinLen = (mode >> 8) & 0xff, coder = (mode >> 5) & 0x7, sorter = mode & 0x1f;
+    BlockFields h;
+    if (!block_header_read(hdr, &h)) return LIBBSC_DATA_CORRUPT;
+    const int blockSize = h.block_size, dataSize = h.data_size, index = h.index;
+    const BlockMode m = block_mode_unpack(h.mode);
 
-    int test = 0;
-    if (sorter == LIBBSC_BLOCKSORTER_BWT || (sorter >= LIBBSC_BLOCKSORTER_ST3 && sorter <= LIBBSC_BLOCKSORTER_ST8)) test = sorter;
-    else if (sorter > 0) return LIBBSC_DATA_CORRUPT;
-    if (coder >= LIBBSC_CODER_QLFC_STATIC && coder <= LIBBSC_CODER_QLFC_FAST) test += coder << 5;
-    else if (coder > 0) return LIBBSC_DATA_CORRUPT;
-    if (lzpMinLen != 0 || lzpHashSize != 0) {
-        if (lzpMinLen < 4 || lzpMinLen > 255) return LIBBSC_DATA_CORRUPT;
-        if (lzpHashSize < 10 || lzpHashSize > 28) return LIBBSC_DATA_CORRUPT;
-        test += (lzpMinLen << 8) + (lzpHashSize << 16);
+    // every field a value the format knows (0: a stored block has neither sorter nor coder), and no bit of the mode word outside them
+    if (m.sorter != 0 && m.sorter != LIBBSC_BLOCKSORTER_BWT && (m.sorter < LIBBSC_BLOCKSORTER_ST3 || m.sorter > LIBBSC_BLOCKSORTER_ST8)) return LIBBSC_DATA_CORRUPT;
+    if (m.coder != 0 && (m.coder < LIBBSC_CODER_QLFC_STATIC || m.coder > LIBBSC_CODER_QLFC_FAST)) return LIBBSC_DATA_CORRUPT;
+    if (m.lzp_min != 0 || m.lzp_hash != 0) {
+        if (m.lzp_min < 4 || m.lzp_min > 255) return LIBBSC_DATA_CORRUPT;
+        if (m.lzp_hash < 10 || m.lzp_hash > 28) return LIBBSC_DATA_CORRUPT;
     }
-    if (test != mode) return LIBBSC_DATA_CORRUPT;
+    if (block_mode_pack(m) != h.mode) return LIBBSC_DATA_CORRUPT;
     if (blockSize < LIBBSC_HEADER_SIZE || blockSize > LIBBSC_HEADER_SIZE + dataSize) return LIBBSC_DATA_CORRUPT;
     if (index < 0 || index > dataSize) return LIBBSC_DATA_CORRUPT;
     if (pBlockSize) *pBlockSize = blockSize;
@@ -731,52 +724,41 @@ static void host_encode_group(BlockJob& J, int b)
 
 static void write_stored(BlockJob& J)
 {
-    uint8_t* output = J.output; const int n = J.n_orig;
-    if (J.hInput) { J.result = J.inplace ? LIBBSC_NOT_COMPRESSIBLE : bsc_store(J.hInput, output, n, J.features); return; }   // libbsc.cpp:188, :315
-    if (hipSetDevice(J.c->device) != hipSuccess ||
-        hipMemcpy(output + LIBBSC_HEADER_SIZE, J.dInput, (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) { J.result = LIBBSC_GPU_ERROR; return; }
-    put_i32(output + 0, n + LIBBSC_HEADER_SIZE); put_i32(output + 4, n); put_i32(output + 8, 0); put_i32(output + 12, 0);
-    put_i32(output + 16, (int)J.adler_data); put_i32(output + 20, (int)J.adler_data);
-    put_i32(output + 24, (int)adler32(output, 24));
-    J.result = n + LIBBSC_HEADER_SIZE;
+    if (J.hInput) { J.result = J.inplace ? LIBBSC_NOT_COMPRESSIBLE : bsc_store(J.hInput, J.output, J.n_orig, J.features); return; }   // libbsc.cpp:188, :315
+    J.result = store_from_device(J.c, J.dInput, J.output, J.n_orig, J.adler_data);
 }
 
+// result: the payload's bytes at block_body(J.output), or the coder's negative code
 static void write_header_and_trailer(BlockJob& J, int result)
 {
-    uint8_t* output = J.output; const int n = J.n_orig;
-    if (result < LIBBSC_NO_ERROR || result + 1 + 4 * J.num_indexes >= n) { write_stored(J); return; }      // libbsc.cpp:315-318
-    if (J.num_indexes > 0) memcpy(output + LIBBSC_HEADER_SIZE + result, J.indexes, (size_t)4 * J.num_indexes);
-    output[LIBBSC_HEADER_SIZE + result + 4 * J.num_indexes] = (unsigned char)J.num_indexes;
-    result += 1 + 4 * J.num_indexes;
-    put_i32(output + 0, result + LIBBSC_HEADER_SIZE);
-    put_i32(output + 4, n);
-    put_i32(output + 8, J.mode);
-    put_i32(output + 12, J.index);
-    put_i32(output + 16, (int)J.adler_data);
-    put_i32(output + 20, (int)adler32(output + LIBBSC_HEADER_SIZE, (size_t)result));
-    put_i32(output + 24, (int)adler32(output, 24));
-    J.result = result + LIBBSC_HEADER_SIZE;
+    J.result = block_finish_coded(J.output, J.n_orig, result, J.mode, J.index, J.indexes, J.num_indexes, J.adler_data);
+    if (J.result == LIBBSC_NOT_COMPRESSIBLE) write_stored(J);
+}
+
+namespace {
+struct RunsFetch : RawFetch {                                       // a sub-block stored raw is rebuilt from its runs
+    const RunView* views; const int* st; const int* sz; int nb;
+    RunsFetch(const RunView* views_, const int* st_, const int* sz_, int nb_) : views(views_), st(st_), sz(sz_), nb(nb_) {}
+    int operator()(int start, int size, uint8_t* dst) override
+    {
+        for (int q = 0; q < nb; ++q) if (st[q] == start && sz[q] == size) { expand_runs(views[q], start, dst); return 0; }
+        return LIBBSC_BAD_PARAMETER;
+    }
+};
+}
+
+// sub-block b of a block whose sub-blocks were coded on their own: once from its scratch buffer, or, kept raw, expanded from its runs
+static int put_coded_sub(const BlockJob& J, int b, uint8_t* dst)
+{
+    if (J.sub_res[b] != J.size[b]) memcpy(dst, J.scratch[b].get(), (size_t)J.sub_res[b]);
+    else expand_runs(J.views[b], J.start[b], dst);
+    return 0;
 }
 
 // frame the independently coded sub-blocks (nblocks > 1, MULTITHREADING semantics)
 static void host_finalize_parallel(BlockJob& J)
 {
-    uint8_t* out = J.output + LIBBSC_HEADER_SIZE; const int n = J.n, nb = J.nblocks;
-    int total = 1 + 8 * nb;
-    for (int b = 0; b < nb; ++b) total += J.sub_res[b];
-    if (total >= n) { write_header_and_trailer(J, LIBBSC_NOT_COMPRESSIBLE); }
-    else {
-        out[0] = (uint8_t)nb;
-        int optr = 1 + 8 * nb;
-        for (int b = 0; b < nb; ++b) {
-            put_i32(out + 1 + 8 * b, J.size[b]);
-            put_i32(out + 1 + 8 * b + 4, J.sub_res[b]);
-            if (J.sub_res[b] != J.size[b]) memcpy(out + optr, J.scratch[b].get(), (size_t)J.sub_res[b]);
-            else expand_runs(J.views[b], J.start[b], out + optr);
-            optr += J.sub_res[b];
-        }
-        write_header_and_trailer(J, total);
-    }
+    write_header_and_trailer(J, frame_parallel(block_body(J.output), J.n, J.nblocks, J.size, J.sub_res, [&J](int b, uint8_t* dst) { return put_coded_sub(J, b, dst); }));
 }
 
 // every block with more than one sub-block is coded as independent per-sub-block tasks, whatever the caller's
@@ -787,49 +769,30 @@ static bool job_uses_tasks(const BlockJob& J) { return !J.stored_small && J.nblo
 // the block's sub-blocks through the strictly serial coder (coder.cpp:111-155) on this thread
 static void host_code_serially(BlockJob& J)
 {
-    struct Fetch : RawFetch {
-        const BlockJob* J;
-        int operator()(int st, int sz, uint8_t* dst) override
-        {
-            for (int b = 0; b < J->nblocks; ++b) if (J->start[b] == st && J->size[b] == sz) { expand_runs(J->views[b], st, dst); return 0; }
-            return LIBBSC_BAD_PARAMETER;
-        }
-    } fetch; fetch.J = &J;
+    RunsFetch fetch(J.views, J.start, J.size, J.nblocks);
     unsigned char* buffer = (unsigned char*)bsc_malloc((size_t)J.n + 4096);
     if (!buffer) { J.result = LIBBSC_NOT_ENOUGH_MEMORY; return; }
     const int result = coder_compress_views(J.views, J.nblocks, J.start, J.size, J.n, buffer, J.coder, J.features & ~LIBBSC_FEATURE_MULTITHREADING, fetch);
-    if (result >= 0) memcpy(J.output + LIBBSC_HEADER_SIZE, buffer, (size_t)result);
+    if (result >= 0) memcpy(block_body(J.output), buffer, (size_t)result);
     bsc_free(buffer);
     write_header_and_trailer(J, result);
 }
 
 // Serial framing rules (coder.cpp:111-155) applied to sub-blocks that were coded independently, each with an output
-// budget of its own size.  The serial coder gives sub-block b the budget min(size_b, n - bytes written so far); when that
-// is size_b for every b — always, unless the block is close to incompressible — its result is exactly what the
-// independent run produced.  Otherwise the block is simply coded again serially.
+// budget of its own size: where serial_verdict (container.h) says that this is what the serial coder would have produced —
+// always, unless the block is close to incompressible — they are framed as they are.  Otherwise the block is simply coded
+// again serially.
 static void host_finalize_serial(BlockJob& J)
 {
-    uint8_t* out = J.output + LIBBSC_HEADER_SIZE; const int n = J.n, nb = J.nblocks;
-    int optr = 1 + 8 * nb;
-    bool exact = true, incompressible = false;
-    for (int b = 0; b < nb && exact && !incompressible; ++b) {
-        if (n - optr < J.size[b]) { exact = false; break; }
-        if (J.sub_res[b] == J.size[b] && optr + J.size[b] >= n) { incompressible = true; break; }       // coder.cpp:131-134
-        optr += J.sub_res[b];
-    }
-    if (!exact) { if (J.use_ps) { J.redo.store(true, std::memory_order_relaxed); return; } host_code_serially(J); return; }
-    if (incompressible) write_header_and_trailer(J, LIBBSC_NOT_COMPRESSIBLE);
-    else {
-        out[0] = (uint8_t)nb;
-        optr = 1 + 8 * nb;
-        for (int b = 0; b < nb; ++b) {
-            put_i32(out + 1 + 8 * b, J.size[b]);
-            put_i32(out + 1 + 8 * b + 4, J.sub_res[b]);
-            if (J.sub_res[b] != J.size[b]) memcpy(out + optr, J.scratch[b].get(), (size_t)J.sub_res[b]);
-            else expand_runs(J.views[b], J.start[b], out + optr);
-            optr += J.sub_res[b];
-        }
-        write_header_and_trailer(J, optr);
+    switch (serial_verdict(J.n, J.nblocks, J.size, J.sub_res)) {
+    case SERIAL_NOT_EXACT:
+        if (J.use_ps) J.redo.store(true, std::memory_order_relaxed); else host_code_serially(J);
+        return;
+    case SERIAL_INCOMPRESSIBLE:
+        write_header_and_trailer(J, LIBBSC_NOT_COMPRESSIBLE);
+        return;
+    case SERIAL_EXACT:
+        write_header_and_trailer(J, subtable_write(block_body(J.output), J.nblocks, J.size, J.sub_res, [&J](int b, uint8_t* dst) { return put_coded_sub(J, b, dst); }));
     }
 }
 
@@ -861,14 +824,14 @@ static int stage_host_lzp(BlockJob& J, const unsigned char* input, unsigned char
 {
     int lzSize = n;
     J.lz.reset();
-    if (mode != (mode & 0xff)) {
+    if (block_mode_has_lzp(mode)) {
         J.lz = std::unique_ptr<unsigned char, void (*)(void*)>((unsigned char*)bigbuf_get((size_t)n), bigbuf_put);   // (par.h: a few block-sized buffers are kept)
         if (!J.lz) return LIBBSC_NOT_ENOUGH_MEMORY;
         const int r = lzp_compress(input, J.lz.get(), n, lzpHashSize, lzpMinLen, features);
-        if (r < LIBBSC_NO_ERROR) { mode &= 0xff; J.lz.reset(); }            // libbsc.cpp:266-269: the block goes on without LZP
+        if (r < LIBBSC_NO_ERROR) { mode = block_mode_without_lzp(mode); J.lz.reset(); }            // libbsc.cpp:266-269: the block goes on without LZP
         else lzSize = r;
     }
-    if (lzSize <= LIBBSC_HEADER_SIZE) { *sorter = LIBBSC_BLOCKSORTER_BWT; mode = (mode & ~0x1f) | LIBBSC_BLOCKSORTER_BWT; }
+    if (lzSize <= LIBBSC_HEADER_SIZE) { *sorter = LIBBSC_BLOCKSORTER_BWT; mode = block_mode_with_sorter(mode, LIBBSC_BLOCKSORTER_BWT); }
     J.hInput = input; J.output = output; J.n = lzSize; J.n_orig = n; J.inplace = (input == output);
     J.coder = coder; J.features = features; J.mode = mode; J.stored_small = false; J.result = 0; J.have_adler = false;
     if (J.lz) { J.adler_data = adler32(input, (size_t)n); J.have_adler = true; }
@@ -1584,17 +1547,6 @@ struct PassSource {
 };
 }
 
-// the stored rule (libbsc.cpp:188) for a block whose input is in HBM: one copy of it straight into the output region
-static int store_from_device(bscgpu_ctx* c, const unsigned char* dIn, unsigned char* output, int n, unsigned adler)
-{
-    if (hipSetDevice(c->device) != hipSuccess || hipMemcpy(output + LIBBSC_HEADER_SIZE, dIn, (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
-        return LIBBSC_GPU_ERROR;
-    put_i32(output + 0, n + LIBBSC_HEADER_SIZE); put_i32(output + 4, n); put_i32(output + 8, 0); put_i32(output + 12, 0);
-    put_i32(output + 16, (int)adler); put_i32(output + 20, (int)adler);
-    put_i32(output + 24, (int)adler32(output, 24));
-    return n + LIBBSC_HEADER_SIZE;
-}
-
 static int front_batch_code_rc(const bscgpu_front_layout* Lo, int block, const uint8_t* bytes, const uint32_t* off, const int* res, const int* room_of,
                                unsigned char* out, int coder, int features, bool packed);
 
@@ -1619,22 +1571,15 @@ static int code_sorted_block(bscgpu_ctx* c, const unsigned char* input, const un
     unsigned char* buffer = (unsigned char*)bsc_malloc((size_t)B.lz + 4096);
     if (!buffer) return LIBBSC_NOT_ENOUGH_MEMORY;
     int result = code_from_source(*src, B.lz, buffer, coder, features);
-    if (result >= LIBBSC_NO_ERROR) memcpy(output + LIBBSC_HEADER_SIZE, buffer, (size_t)result);
+    if (result >= LIBBSC_NO_ERROR) memcpy(block_body(output), buffer, (size_t)result);
     bsc_free(buffer);
     const int num = n < 64 * 1024 ? 0 : B.num_indexes;
-    if (result < LIBBSC_NO_ERROR || result + 1 + 4 * num >= n)
-        return input ? bsc_store(input, output, n, features) : store_from_device(c, dIn, output, n, B.adler);
-    if (num > 0) memcpy(output + LIBBSC_HEADER_SIZE + result, B.indexes, (size_t)4 * num);
-    output[LIBBSC_HEADER_SIZE + result + 4 * num] = (unsigned char)num;
-    result += 1 + 4 * num;
-    put_i32(output + 0, result + LIBBSC_HEADER_SIZE);
-    put_i32(output + 4, n);
-    put_i32(output + 8, B.mode);
-    put_i32(output + 12, B.index);
-    put_i32(output + 16, (int)(input ? adler32(input, (size_t)n) : B.adler));
-    put_i32(output + 20, (int)adler32(output + LIBBSC_HEADER_SIZE, (size_t)result));
-    put_i32(output + 24, (int)adler32(output, 24));
-    return result + LIBBSC_HEADER_SIZE;
+    const unsigned adler = input ? adler32(input, (size_t)n) : B.adler;
+    const int size = block_finish_coded(output, n, result, B.mode, B.index, B.indexes, num, adler);
+    if (size != LIBBSC_NOT_COMPRESSIBLE) return size;
+    if (!input) return store_from_device(c, dIn, output, n, adler);
+    memmove(block_body(output), input, (size_t)n);         // (bsc_store, without a second pass for the checksum)
+    return block_finish_stored(output, n, adler);
 }
 
 // ---- the QLFC front end of a whole pass: layout on the host, coding of one block from a layout (include/bscgpu.h) ----------------
@@ -1680,19 +1625,21 @@ extern "C" BSCGPU_API int bscgpu_front_batch_host(const unsigned char* L, const 
     return LIBBSC_NO_ERROR;
 }
 
+// the run arrays of sub-block s of a layout
+static RunView front_view(const bscgpu_front_layout* Lo, int s)
+{
+    RunView V;
+    V.sym = Lo->sym + Lo->sub_run[s]; V.rank = Lo->rank + Lo->sub_run[s]; V.start = Lo->start + Lo->sub_run[s];
+    V.count = Lo->sub_run[s + 1] - Lo->sub_run[s];
+    V.end = (uint32_t)(Lo->sub_start[s] + Lo->sub_size[s]);
+    V.nsym = Lo->nsym[s];
+    memcpy(V.first_seen, Lo->first_seen + 256 * (size_t)s, (size_t)V.nsym);
+    return V;
+}
 static void front_views(const bscgpu_front_layout* Lo, int block, RunView* views)
 {
     const int s0 = Lo->blk_sub[block], nb = Lo->blk_sub[block + 1] - s0;
-    for (int q = 0; q < nb; ++q) {
-        const int s = s0 + q;
-        RunView& V = views[q];
-        V = RunView();
-        V.sym = Lo->sym + Lo->sub_run[s]; V.rank = Lo->rank + Lo->sub_run[s]; V.start = Lo->start + Lo->sub_run[s];
-        V.count = Lo->sub_run[s + 1] - Lo->sub_run[s];
-        V.end = (uint32_t)(Lo->sub_start[s] + Lo->sub_size[s]);
-        V.nsym = Lo->nsym[s];
-        memcpy(V.first_seen, Lo->first_seen + 256 * (size_t)s, (size_t)V.nsym);
-    }
+    for (int q = 0; q < nb; ++q) views[q] = front_view(Lo, s0 + q);
 }
 
 extern "C" BSCGPU_API int bscgpu_front_batch_code(const bscgpu_front_layout* Lo, int block, unsigned char* out, int coder, int features)
@@ -1702,38 +1649,14 @@ extern "C" BSCGPU_API int bscgpu_front_batch_code(const bscgpu_front_layout* Lo,
     if (nb < 1 || nb > 8) return LIBBSC_BAD_PARAMETER;             // (an empty block: what bsc_coder_compress says to n = 0)
     RunView views[8];
     front_views(Lo, block, views);
-    struct Fetch : RawFetch {                                       // a sub-block stored raw is rebuilt from its runs
-        const RunView* views; const int* st; const int* sz; int nb;
-        int operator()(int start, int size, uint8_t* dst) override
-        {
-            for (int q = 0; q < nb; ++q) if (st[q] == start && sz[q] == size) { expand_runs(views[q], start, dst); return 0; }
-            return LIBBSC_BAD_PARAMETER;
-        }
-    } fetch;
-    fetch.views = views; fetch.st = Lo->sub_start + s0; fetch.sz = Lo->sub_size + s0; fetch.nb = nb;
+    RunsFetch fetch(views, Lo->sub_start + s0, Lo->sub_size + s0, nb);
     return coder_compress_views(views, nb, Lo->sub_start + s0, Lo->sub_size + s0, Lo->sizes[block], out, coder, features, fetch);
-}
-
-namespace {
-struct RunsFetch : RawFetch {                                       // a sub-block stored raw is rebuilt from its runs
-    const RunView* views; const int* st; const int* sz; int nb;
-    int operator()(int start, int size, uint8_t* dst) override
-    {
-        for (int q = 0; q < nb; ++q) if (st[q] == start && sz[q] == size) { expand_runs(views[q], start, dst); return 0; }
-        return LIBBSC_BAD_PARAMETER;
-    }
-};
 }
 
 static int64_t pstream_host(const bscgpu_front_layout* Lo, int s, uint16_t* out, int64_t cap, int coder)
 {
     if (!Lo || s < 0 || s >= Lo->nsub || cap < 0 || (cap > 0 && !out)) return LIBBSC_BAD_PARAMETER;
-    RunView V;
-    V.sym = Lo->sym + Lo->sub_run[s]; V.rank = Lo->rank + Lo->sub_run[s]; V.start = Lo->start + Lo->sub_run[s];
-    V.count = Lo->sub_run[s + 1] - Lo->sub_run[s];
-    V.end = (uint32_t)(Lo->sub_start[s] + Lo->sub_size[s]);
-    V.nsym = Lo->nsym[s];
-    memcpy(V.first_seen, Lo->first_seen + 256 * (size_t)s, (size_t)V.nsym);
+    const RunView V = front_view(Lo, s);
     return coder == LIBBSC_CODER_QLFC_FAST ? qlfc_fast_pstream_runs(V, out, cap) : qlfc_static_pstream_runs(V, out, cap);
 }
 extern "C" BSCGPU_API int64_t bscgpu_static_pstream_host(const bscgpu_front_layout* Lo, int s, uint16_t* out, int64_t cap)
@@ -1753,8 +1676,7 @@ static int front_batch_code_stream(const bscgpu_front_layout* Lo, int block, con
     if (nb < 1 || nb > 8) return LIBBSC_BAD_PARAMETER;
     RunView views[8];
     front_views(Lo, block, views);
-    RunsFetch fetch;
-    fetch.views = views; fetch.st = Lo->sub_start + s0; fetch.sz = Lo->sub_size + s0; fetch.nb = nb;
+    RunsFetch fetch(views, Lo->sub_start + s0, Lo->sub_size + s0, nb);
     struct FromStream : SubEncode {                                 // the range coder alone: the model ran on the GPU
         const bscgpu_front_layout* Lo; int s0; const uint16_t* ps; const uint32_t* poff; int form;
         int operator()(int b, uint8_t* dst, int room) override
@@ -1791,8 +1713,7 @@ extern "C" BSCGPU_API int bscgpu_front_batch_code_ps13(const bscgpu_front_layout
     for (int s = s0; s < s0 + nb; ++s) if (pbase[s] < 0 || (pbase[s] & 7) != 0) return LIBBSC_BAD_PARAMETER;      // a body starts on a group
     RunView views[8];
     front_views(Lo, block, views);
-    RunsFetch fetch;
-    fetch.views = views; fetch.st = Lo->sub_start + s0; fetch.sz = Lo->sub_size + s0; fetch.nb = nb;
+    RunsFetch fetch(views, Lo->sub_start + s0, Lo->sub_size + s0, nb);
     struct FromPacked : SubEncode {
         const bscgpu_front_layout* Lo; const RunView* views; int s0; const uint8_t* packed; const uint32_t* poff; const int64_t* pbase;
         int operator()(int b, uint8_t* dst, int room) override
@@ -1826,8 +1747,7 @@ static int front_batch_code_rc(const bscgpu_front_layout* Lo, int block, const u
     if (nb < 1 || nb > 8) return LIBBSC_BAD_PARAMETER;
     RunView views[8];
     front_views(Lo, block, views);
-    RunsFetch fetch;
-    fetch.views = views; fetch.st = Lo->sub_start + s0; fetch.sz = Lo->sub_size + s0; fetch.nb = nb;
+    RunsFetch fetch(views, Lo->sub_start + s0, Lo->sub_size + s0, nb);
     struct Coded : SubEncode {
         const bscgpu_front_layout* Lo; const RunView* views; int s0; const uint8_t* bytes; const uint32_t* off; const int* res; const int* room_of; int coder; bool packed;
         int operator()(int b, uint8_t* dst, int room) override
@@ -2141,7 +2061,7 @@ struct BatchCall {
     const unsigned char* in_of(int b) const { return input + in_off[b]; }
     const unsigned char* din_of(int b) const { return dInput + in_off[b]; }
     unsigned char* out_of(int b) const { return output + in_off[b] + (int64_t)LIBBSC_HEADER_SIZE * b; }
-    bool lzp() const { return mode != (mode & 0xff); }
+    bool lzp() const { return block_mode_has_lzp(mode); }
     int alone(int b) const                        // a block by the single-block path on the call's context
     {
         return dev ? bscgpu_compress_device(c, din_of(b), out_of(b), sizes[b], blockSorter, coder, features)
@@ -2251,7 +2171,7 @@ void BatchPass::prep_block(int i)
     if (B.cls != BATCH_SORTED || !K->lzp()) return;
     B.lzbuf = (unsigned char*)bigbuf_get((size_t)n);
     const int r = B.lzbuf ? lzp_compress(K->in_of(q), B.lzbuf, n, K->lzpHashSize, K->lzpMinLen, K->features) : LIBBSC_NOT_ENOUGH_MEMORY;
-    if (r < LIBBSC_NO_ERROR) { B.mode &= 0xff; bigbuf_put(B.lzbuf); B.lzbuf = nullptr; }
+    if (r < LIBBSC_NO_ERROR) { B.mode = block_mode_without_lzp(B.mode); bigbuf_put(B.lzbuf); B.lzbuf = nullptr; }
     else B.lz = r;
     B.cls = batch_block_class(n, B.lz, K->st, K->dev, true);
     if (B.cls == BATCH_SINGLE) { bigbuf_put(B.lzbuf); B.lzbuf = nullptr; }

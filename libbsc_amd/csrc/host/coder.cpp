@@ -2,6 +2,7 @@
 // independently (one host thread per sub-block), frame them.  Wire format and split rule are the
 // reference's (coder.cpp:52-59 counts, :70-109 split, :111-155 serial framing, :159-240 parallel framing).
 #include "qlfc.h"
+#include "container.h"
 
 #include <cstring>
 #include <immintrin.h>
@@ -53,9 +54,6 @@ void coder_split_blocks(const uint8_t* in, int n, int nblocks, int* start, int* 
     }
 }
 
-static inline void put_i32(uint8_t* p, int v) { memcpy(p, &v, 4); }
-static inline int  get_i32(const uint8_t* p) { int v; memcpy(&v, p, 4); return v; }
-
 static int compress_serial(const uint8_t* in, uint8_t* out, int n, int coder)
 {
     const int nblocks = coder_num_blocks(n);
@@ -67,22 +65,9 @@ static int compress_serial(const uint8_t* in, uint8_t* out, int n, int coder)
     }
     int start[8], size[8];
     coder_split_blocks(in, n, nblocks, start, size);
-    out[0] = (uint8_t)nblocks;
-    int optr = 1 + 8 * nblocks;
-    for (int b = 0; b < nblocks; ++b) {
-        int room = size[b];
-        if (room > n - optr) room = n - optr;
-        int r = qlfc_encode_block(in + start[b], out + optr, size[b], room, coder);
-        if (r < 0) {                                         // stored raw (coder.cpp:136-140)
-            if (optr + size[b] >= n) return NOT_COMPRESSIBLE;
-            r = size[b];
-            memcpy(out + optr, in + start[b], (size_t)size[b]);
-        }
-        put_i32(out + 1 + 8 * b, size[b]);
-        put_i32(out + 1 + 8 * b + 4, r);
-        optr += r;
-    }
-    return optr;
+    return frame_serial(out, n, nblocks, size,
+        [&](int b, uint8_t* dst, int room) { return qlfc_encode_block(in + start[b], dst, size[b], room, coder); },
+        [&](int b, uint8_t* dst) { memcpy(dst, in + start[b], (size_t)size[b]); return 0; });       // stored raw (coder.cpp:136-140)
 }
 
 static int compress_parallel(const uint8_t* in, uint8_t* out, int n, int coder)
@@ -97,19 +82,8 @@ static int compress_parallel(const uint8_t* in, uint8_t* out, int n, int coder)
         int r = qlfc_encode_block(in + start[b], scratch + start[b], size[b], size[b], coder);
         res[b] = (r < 0) ? size[b] : r;                     // failed sub-block is stored raw (coder.cpp:194)
     });
-    int total = 1 + 8 * nblocks;
-    for (int b = 0; b < nblocks; ++b) total += res[b];
-    if (total >= n) return NOT_COMPRESSIBLE;
-
-    out[0] = (uint8_t)nblocks;
-    int optr = 1 + 8 * nblocks;
-    for (int b = 0; b < nblocks; ++b) {
-        put_i32(out + 1 + 8 * b, size[b]);
-        put_i32(out + 1 + 8 * b + 4, res[b]);
-        memcpy(out + optr, (res[b] != size[b] ? scratch : in) + start[b], (size_t)res[b]);
-        optr += res[b];
-    }
-    return total;
+    return frame_parallel(out, n, nblocks, size, res,
+        [&](int b, uint8_t* dst) { memcpy(dst, (res[b] != size[b] ? scratch : in) + start[b], (size_t)res[b]); return 0; });
 }
 
 int coder_compress_views(const RunView* views, int nblocks, const int* start, const int* size, int n,
@@ -125,7 +99,7 @@ int coder_compress_views(const RunView* views, int nblocks, const int* start, co
         out[0] = 1;
         return r + 1;
     }
-    out[0] = (uint8_t)nblocks;
+    auto raw = [&](int b, uint8_t* dst) { return fetch_raw(start[b], size[b], dst); };
     if (features & FEATURE_MULTITHREADING) {               // coder.cpp:159-240
         std::vector<std::unique_ptr<uint8_t[]>> scratch((size_t)nblocks);
         int res[8];
@@ -138,34 +112,14 @@ int coder_compress_views(const RunView* views, int nblocks, const int* start, co
             tms[b] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         });
         if (getenv("BSCGPU_DEBUG")) { fprintf(stderr, "[coder] sub-block ms:"); for (int b = 0; b < nblocks; ++b) fprintf(stderr, " %.1f", tms[b]); fprintf(stderr, "\n"); }
-        int total = 1 + 8 * nblocks;
-        for (int b = 0; b < nblocks; ++b) total += res[b];
-        if (total >= n) return NOT_COMPRESSIBLE;
-        int optr = 1 + 8 * nblocks;
-        for (int b = 0; b < nblocks; ++b) {
-            put_i32(out + 1 + 8 * b, size[b]);
-            put_i32(out + 1 + 8 * b + 4, res[b]);
-            if (res[b] != size[b]) memcpy(out + optr, scratch[(size_t)b].get(), (size_t)res[b]);
-            else { int rc = fetch_raw(start[b], size[b], out + optr); if (rc < 0) return rc; }
-            optr += res[b];
-        }
-        return total;
+        return frame_parallel(out, n, nblocks, size, res, [&](int b, uint8_t* dst) {
+            if (res[b] == size[b]) return raw(b, dst);
+            memcpy(dst, scratch[(size_t)b].get(), (size_t)res[b]);
+            return 0;
+        });
     }
-    int optr = 1 + 8 * nblocks;                            // coder.cpp:111-155
-    for (int b = 0; b < nblocks; ++b) {
-        int room = size[b];
-        if (room > n - optr) room = n - optr;
-        int r = encode(b, size[b], out + optr, room);
-        if (r < 0) {
-            if (optr + size[b] >= n) return NOT_COMPRESSIBLE;
-            r = size[b];
-            int rc = fetch_raw(start[b], size[b], out + optr); if (rc < 0) return rc;
-        }
-        put_i32(out + 1 + 8 * b, size[b]);
-        put_i32(out + 1 + 8 * b + 4, r);
-        optr += r;
-    }
-    return optr;
+    return frame_serial(out, n, nblocks, size,             // coder.cpp:111-155
+        [&](int b, uint8_t* dst, int room) { return encode(b, size[b], dst, room); }, raw);
 }
 
 int coder_compress(const uint8_t* in, uint8_t* out, int n, int coder, int features)
@@ -178,21 +132,17 @@ int coder_compress(const uint8_t* in, uint8_t* out, int n, int coder, int featur
 int coder_decompress_bounded(const uint8_t* in, long long in_size, uint8_t* out, int coder, int features, int max_out)
 {
     if (coder != CODER_STATIC && coder != CODER_ADAPTIVE && coder != CODER_FAST) return BAD_PARAMETER;
-    if (in_size < 1) return DATA_CORRUPT;
-    const int nblocks = in[0];
+    SubTableReader table;
+    const int nblocks = subtable_open(&table, in, in_size, max_out);
+    if (nblocks < 0) return nblocks;
     if (nblocks == 1) return qlfc_decode_block_bounded(in + 1, in_size - 1, out, coder, max_out);
-    if (nblocks < 1 || nblocks > 8) return DATA_CORRUPT;   // the format never writes more than 8 (coder.cpp:52-59)
-    if (in_size < 1 + 8 * nblocks) return DATA_CORRUPT;    // the frame table itself must lie inside the payload
 
-    int res[8], iptr[8], optr[8], isz[8], osz[8];
-    long long ip = 1 + 8 * nblocks, op = 0;
+    int res[8], isz[8], osz[8];
+    long long iptr[8], optr[8];
     for (int b = 0; b < nblocks; ++b) {
-        osz[b] = get_i32(in + 1 + 8 * b);
-        isz[b] = get_i32(in + 1 + 8 * b + 4);
-        if (osz[b] < 0 || isz[b] < 0 || op + osz[b] > max_out) return DATA_CORRUPT;
-        if (ip + isz[b] > in_size) return DATA_CORRUPT;    // a sub-block may not extend past the payload (checksum-valid corrupt tables)
-        iptr[b] = (int)ip; optr[b] = (int)op;
-        ip += isz[b]; op += osz[b];
+        SubBlock s;
+        if (subtable_next(&table, &s) < 0) return DATA_CORRUPT;
+        isz[b] = s.isz; osz[b] = s.osz; iptr[b] = s.iptr; optr[b] = s.optr;
     }
     auto one = [&](int b) {
         if (isz[b] != osz[b]) { res[b] = qlfc_decode_block_bounded(in + iptr[b], isz[b], out + optr[b], coder, osz[b]); if (res[b] >= 0 && res[b] != osz[b]) res[b] = DATA_CORRUPT; }

@@ -15,10 +15,9 @@
 #include "../../../include/libbsc.h"
 #include "qlfc.h"
 #include "lzp.h"
+#include "container.h"
 
 using namespace bschost;
-
-static inline int get_i32(const unsigned char* p) { int v; memcpy(&v, p, 4); return v; }
 
 // ---- LZP decoding (lzp.cpp:564-676 block decoder, :813-885 framing) -------------------------------------------
 // The stream is literal bytes; wherever the 4-byte context has been seen before (hash table of last positions), an
@@ -64,22 +63,20 @@ static int lzp_decode_block(const unsigned char* in, const unsigned char* in_end
 namespace bschost {
 int lzp_decompress(const uint8_t* in, uint8_t* out, int n, int out_cap, int hashSize, int minLen)
 {
-    if (n < 1) return LIBBSC_DATA_CORRUPT;
-    const int nblocks = in[0];
+    SubTableReader table;
+    const int nblocks = subtable_open(&table, in, n, out_cap);
+    if (nblocks < 0) return nblocks;
     if (nblocks == 1) return lzp_decode_block(in + 1, in + n, out, out_cap, hashSize, minLen);
-    if (nblocks < 1 || nblocks > 8 || n < 1 + 8 * nblocks) return LIBBSC_DATA_CORRUPT;
-    long long ip = 1 + 8 * nblocks, op = 0;
     for (int b = 0; b < nblocks; ++b) {
-        const int osz = get_i32(in + 1 + 8 * b), isz = get_i32(in + 1 + 8 * b + 4);
-        if (osz < 0 || isz < 0 || ip + isz > n || op + osz > out_cap) return LIBBSC_DATA_CORRUPT;
+        SubBlock s;
+        if (subtable_next(&table, &s) < 0) return LIBBSC_DATA_CORRUPT;
         int r;
-        if (isz != osz) r = lzp_decode_block(in + ip, in + ip + isz, out + op, osz, hashSize, minLen);
-        else { r = isz; memcpy(out + op, in + ip, (size_t)isz); }
+        if (s.isz != s.osz) r = lzp_decode_block(in + s.iptr, in + s.iptr + s.isz, out + s.optr, s.osz, hashSize, minLen);
+        else { r = s.isz; memcpy(out + s.optr, in + s.iptr, (size_t)s.isz); }
         if (r < 0) return r;
-        if (r != osz) return LIBBSC_DATA_CORRUPT;
-        ip += isz; op += osz;
+        if (r != s.osz) return LIBBSC_DATA_CORRUPT;
     }
-    return (int)op;
+    return (int)table.op;
 }
 }  // namespace bschost
 
@@ -92,13 +89,6 @@ extern "C" {
 // independent backward walks; they run interleaved (several cache misses in flight per core) and, with
 // LIBBSC_FEATURE_MULTITHREADING, on several threads.  The reference reaches the same result through
 // libsais_unbwt_aux (bwt.cpp:283-334).
-static int aux_rate_of(int n)          // largest power of two <= n / 8 (>= 1), bwt.cpp:192-197
-{
-    int mod = n / 8;
-    mod |= mod >> 1; mod |= mod >> 2; mod |= mod >> 4; mod |= mod >> 8; mod |= mod >> 16; mod >>= 1;
-    return mod + 1;
-}
-
 int bsc_bwt_decode_gpu(unsigned char* T, int n, int index);            // block.cpp: the default GPU context's bscgpu_unbwt
 
 int bsc_bwt_decode(unsigned char* T, int n, int index, unsigned char num_indexes, int* indexes, int features)
@@ -134,7 +124,7 @@ int bsc_bwt_decode(unsigned char* T, int n, int index, unsigned char num_indexes
 
     // walks: chain s rebuilds text positions [s * r, min((s + 1) * r, n)) backwards from the row of its end position
     int chains = 1;
-    const int r = aux_rate_of(n);
+    const int r = aux_rate(n);
     if (num_indexes > 0 && indexes != nullptr && (int)num_indexes == (n - 1) / r) {
         chains = (int)num_indexes + 1;
         for (int t = 0; t < (int)num_indexes; ++t) if (indexes[t] < 0 || indexes[t] >= n) return LIBBSC_DATA_CORRUPT;
@@ -247,27 +237,27 @@ int bsc_decompress(const unsigned char* input, int inputSize, unsigned char* out
     int info = bsc_block_info(input, inputSize, &blockSize, &dataSize, features);
     if (info != LIBBSC_NO_ERROR) return info;
     if (inputSize < blockSize || outputSize < dataSize) return LIBBSC_UNEXPECTED_EOB;
-    if ((unsigned)get_i32(input + 20) != adler32(input + LIBBSC_HEADER_SIZE, (size_t)(blockSize - LIBBSC_HEADER_SIZE))) return LIBBSC_DATA_CORRUPT;
-    const int mode = get_i32(input + 8);
-    if (mode == 0) { memmove(output, input + LIBBSC_HEADER_SIZE, (size_t)dataSize); return LIBBSC_NO_ERROR; }
-
-    const int index = get_i32(input + 12);
-    const unsigned adler_data = (unsigned)get_i32(input + 16);
-    const int lzpHashSize = (mode >> 16) & 0xff, lzpMinLen = (mode >> 8) & 0xff, coder = (mode >> 5) & 0x7, sorter = mode & 0x1f;
+    BlockFields h;
+    block_header_read(input, &h);                              // (bsc_block_info has checked it)
+    if (h.mode == 0) {
+        if (!block_body_ok(input, h)) return LIBBSC_DATA_CORRUPT;
+        memmove(output, block_body(input), (size_t)dataSize);
+        return LIBBSC_NO_ERROR;
+    }
+    CodedPayload pay;
+    if (block_coded_payload(input, h, &pay) != LIBBSC_NO_ERROR) return LIBBSC_DATA_CORRUPT;
+    const int index = h.index, num_indexes = pay.num_indexes;
+    const unsigned adler_data = h.adler_data;
+    const BlockMode m = block_mode_unpack(h.mode);
+    const int lzpHashSize = m.lzp_hash, lzpMinLen = m.lzp_min, coder = m.coder, sorter = m.sorter;
+    int indexes[256];
+    if (num_indexes > 0) memcpy(indexes, pay.indexes, (size_t)4 * num_indexes);
 
     // the coder writes dataSize bytes; decode through a scratch buffer when decompressing in place
-    const bool inplace = (input == output);
     std::vector<unsigned char> copy;
-    const unsigned char* src = input;
-    if (inplace) { copy.assign(input, input + blockSize); src = copy.data(); }
-    if (blockSize < LIBBSC_HEADER_SIZE + 2) return LIBBSC_DATA_CORRUPT;      // a coded block holds at least one payload byte and the index count
-    int num_indexes = src[blockSize - 1];
-    int indexes[256];
-    const long long payload = (long long)blockSize - LIBBSC_HEADER_SIZE - 1 - 4LL * num_indexes;     // what the coder may read
-    if (payload < 1) return LIBBSC_DATA_CORRUPT;
-    if (num_indexes > 0) memcpy(indexes, src + blockSize - 1 - 4 * num_indexes, (size_t)4 * num_indexes);
+    if (input == output) { copy.assign(input, input + blockSize); pay.data = block_body(copy.data()); }
     // guard the decoder's input and output before it reads / writes: the stream announces its own lengths
-    int lzSize = coder_decompress_bounded(src + LIBBSC_HEADER_SIZE, payload, output, coder, features, dataSize);
+    int lzSize = coder_decompress_bounded(pay.data, pay.size, output, coder, features, dataSize);
     if (lzSize < LIBBSC_NO_ERROR) return lzSize;
     int rc = (sorter == LIBBSC_BLOCKSORTER_BWT) ? bsc_bwt_decode(output, lzSize, index, (unsigned char)num_indexes, indexes, features)
                                                 : bsc_st_decode(output, lzSize, sorter, index, features);

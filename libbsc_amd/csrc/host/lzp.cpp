@@ -24,6 +24,7 @@
 
 #include "qlfc.h"
 #include "lzp.h"
+#include "container.h"
 
 namespace bschost {
 
@@ -263,10 +264,8 @@ int lzp_encode_chunk(const uint8_t* in, int n, uint8_t* out, int out_cap, int ha
     return r;
 }
 
-static inline void put_le32(uint8_t* p, int v) { memcpy(p, &v, 4); }
-
-// Block framing (lzp.cpp:687-811): [nChunks] then, for more than one chunk, {i32 rawSize, i32 codedSize} per chunk and
-// the chunk payloads; a chunk that does not shrink is kept raw (codedSize == rawSize).
+// Block framing (lzp.cpp:687-811): [nChunks] then, for more than one chunk, the sub-block table of container.h and the chunk
+// payloads; a chunk that does not shrink is kept raw.
 int lzp_compress(const uint8_t* in, uint8_t* out, int n, int hashSize, int minLen, int features)
 {
     const int nc = lzp_num_chunks(n);
@@ -276,7 +275,8 @@ int lzp_compress(const uint8_t* in, uint8_t* out, int n, int hashSize, int minLe
         out[0] = 1;
         return r + 1;
     }
-    const int chunk = n / nc;
+    int start[8], size[8];
+    for (int b = 0; b < nc; ++b) { start[b] = b * (n / nc); size[b] = (b != nc - 1) ? n / nc : n - start[b]; }
     if (features & 2 /* LIBBSC_FEATURE_MULTITHREADING */) {
         // concurrent chunks, each with a budget of its own size (lzp.cpp:736-790)
         std::unique_ptr<uint8_t, void (*)(void*)> tmp_buf((uint8_t*)bigbuf_get((size_t)n), bigbuf_put);   // (not a zeroed vector, not a fresh mapping per block)
@@ -284,38 +284,16 @@ int lzp_compress(const uint8_t* in, uint8_t* out, int n, int hashSize, int minLe
         uint8_t* const tmp = tmp_buf.get();
         int res[8];
         run_tasks(nc, [&](int b) {
-            const int st = b * chunk, sz = (b != nc - 1) ? chunk : n - st;
-            const int r = lzp_encode_chunk(in + st, sz, tmp + st, sz, hashSize, minLen);
-            res[b] = (r < 0) ? sz : r;
+            const int r = lzp_encode_chunk(in + start[b], size[b], tmp + start[b], size[b], hashSize, minLen);
+            res[b] = (r < 0) ? size[b] : r;
         });
-        int64_t total = 1 + 8 * nc;
-        for (int b = 0; b < nc; ++b) total += res[b];
-        if (total >= n) return NOT_COMPRESSIBLE;
-        out[0] = (uint8_t)nc;
-        int optr = 1 + 8 * nc;
-        for (int b = 0; b < nc; ++b) {
-            const int st = b * chunk, sz = (b != nc - 1) ? chunk : n - st;
-            put_le32(out + 1 + 8 * b, sz); put_le32(out + 1 + 8 * b + 4, res[b]);
-            memcpy(out + optr, (res[b] != sz) ? tmp + st : in + st, (size_t)res[b]);
-            optr += res[b];
-        }
-        return optr;
+        return frame_parallel(out, n, nc, size, res,
+            [&](int b, uint8_t* dst) { memcpy(dst, (res[b] != size[b] ? tmp : in) + start[b], (size_t)res[b]); return 0; });
     }
     // one chunk after the other, each limited by what is left of the n-byte output (lzp.cpp:697-731)
-    out[0] = (uint8_t)nc;
-    int optr = 1 + 8 * nc;
-    for (int b = 0; b < nc; ++b) {
-        const int st = b * chunk, sz = (b != nc - 1) ? chunk : n - st;
-        int cap = sz; if (cap > n - optr) cap = n - optr;
-        int r = lzp_encode_chunk(in + st, sz, out + optr, cap, hashSize, minLen);
-        if (r < 0) {
-            if (optr + sz >= n) return NOT_COMPRESSIBLE;
-            r = sz; memcpy(out + optr, in + st, (size_t)sz);
-        }
-        put_le32(out + 1 + 8 * b, sz); put_le32(out + 1 + 8 * b + 4, r);
-        optr += r;
-    }
-    return optr;
+    return frame_serial(out, n, nc, size,
+        [&](int b, uint8_t* dst, int room) { return lzp_encode_chunk(in + start[b], size[b], dst, room, hashSize, minLen); },
+        [&](int b, uint8_t* dst) { memcpy(dst, in + start[b], (size_t)size[b]); return 0; });
 }
 
 }  // namespace bschost

@@ -425,3 +425,121 @@ def batch_call(sizes, sorter, coder, cap, dev, lz, opts, facts, entries, min_pas
     piped = lambda q: pass_of[q] < 0 and sizes[q] <= cap and (dev or sizes[q] > HEADER_SIZE)
     out["leftover"] = [] if out["error"] else ["none" if not single[q] else "pipe" if piped(q) else "one_by_one" for q in range(count)]
     return out
+
+
+# ---- the block format (libbsc_amd/csrc/host/container.h), restated from the reference's layout --------------------------------------
+# A block is a 28-byte header (seven little-endian words, the last the Adler-32 of the six before it) and a body: the data itself
+# (mode 0), or the coder's payload, the aux indexes and their count byte.  A payload of more than one sub-block is a count byte, a
+# table of {raw size, coded size} and the sub-blocks back to back (coded size == raw size: kept raw).
+NOT_COMPRESSIBLE, DATA_CORRUPT = -3, -6
+
+
+def _adler(b):
+    import zlib
+    return zlib.adler32(bytes(b)) & 0xffffffff
+
+
+def _words(*v):
+    import struct
+    return b"".join(struct.pack("<I", x & 0xffffffff) for x in v)
+
+
+def mode_pack(sorter, coder, lzp_hash, lzp_min):
+    return sorter | coder << 5 | lzp_min << 8 | lzp_hash << 16
+
+
+def mode_unpack(mode):
+    """-> [sorter, coder, lzp_hash, lzp_min]"""
+    return [mode & 31, mode >> 5 & 7, mode >> 16 & 255, mode >> 8 & 255]
+
+
+def block_header(block_size, data_size, mode, index, adler_data, adler_body):
+    six = _words(block_size, data_size, mode, index, adler_data, adler_body)
+    return six + _words(_adler(six))
+
+
+def stored_block(data):
+    return block_header(len(data) + HEADER_SIZE, len(data), 0, 0, _adler(data), _adler(data)) + bytes(data)
+
+
+def coded_block(n_orig, payload, mode, index, indexes, adler_data, coded=None):
+    """coded: what the coder returned where that is not len(payload) (a negative code) -> the block, or NOT_COMPRESSIBLE: store it"""
+    coded = len(payload) if coded is None else coded
+    if coded < 0 or coded + 1 + 4 * len(indexes) >= n_orig:
+        return NOT_COMPRESSIBLE
+    body = bytes(payload[:coded]) + _words(*indexes) + bytes([len(indexes)])
+    return block_header(len(body) + HEADER_SIZE, n_orig, mode, index, adler_data, _adler(body)) + body
+
+
+def coded_payload(block):
+    """the decoders' view of a coded block whose header has passed -> dict(num, size, data, indexes: offsets) or DATA_CORRUPT"""
+    import struct
+    bs, adler_body = struct.unpack_from("<i", block, 0)[0], struct.unpack_from("<I", block, 20)[0]
+    if bs < HEADER_SIZE + 2 or _adler(block[HEADER_SIZE:bs]) != adler_body:
+        return DATA_CORRUPT
+    num = block[bs - 1]
+    size = bs - HEADER_SIZE - 1 - 4 * num
+    return DATA_CORRUPT if size < 1 else dict(num=num, size=size, data=HEADER_SIZE, indexes=HEADER_SIZE + size)
+
+
+def _sub_bytes(b, raw, k):
+    return bytes([(0xA0 if raw else 0xC0) + b]) * k        # what tools/container_probe.cpp's stand-in coder writes
+
+
+def frame_parallel(n, size, res):
+    """every sub-block coded on its own with a budget of its own size (res[b] == size[b]: kept raw) -> the payload or NOT_COMPRESSIBLE"""
+    if 1 + 8 * len(size) + sum(res) >= n:
+        return NOT_COMPRESSIBLE
+    table = b"".join(_words(s, r) for s, r in zip(size, res))
+    return bytes([len(size)]) + table + b"".join(_sub_bytes(b, r == s, r) for b, (s, r) in enumerate(zip(size, res)))
+
+
+def frame_serial(n, size, c):
+    """one sub-block after the other with the budget min(size[b], n - bytes so far); the stand-in coder needs c[b] bytes and gives up
+    without room for them or where c[b] >= size[b] -> (the payload or NOT_COMPRESSIBLE, the budgets handed out)"""
+    optr, table, subs, rooms = 1 + 8 * len(size), b"", b"", []
+    for b, (s, k) in enumerate(zip(size, c)):
+        room = min(s, n - optr)
+        rooms.append(room)
+        raw = k >= s or k > room
+        if raw:
+            if optr + s >= n:
+                return NOT_COMPRESSIBLE, rooms
+            k = s
+        table += _words(s, k)
+        subs += _sub_bytes(b, raw, k)
+        optr += k
+    return bytes([len(size)]) + table + subs, rooms
+
+
+def serial_verdict(n, size, res):
+    """sub-blocks coded on their own, under the serial rule: 'exact' (the serial coder's payload is frame_parallel's table and
+    sub-blocks, whatever their total), 'incompressible' (its answer is NOT_COMPRESSIBLE), 'not_exact' (a budget was smaller: unknown)"""
+    optr = 1 + 8 * len(size)
+    for s, r in zip(size, res):
+        if n - optr < s:
+            return "not_exact"
+        if r == s and optr + s >= n:
+            return "incompressible"
+        optr += r
+    return "exact"
+
+
+def subtable_parse(data, in_size, max_out):
+    """-> (nb or DATA_CORRUPT, [[isz, osz, iptr, optr] of the sub-blocks up to the first bad one], 0 or DATA_CORRUPT); nb == 1 has no table"""
+    import struct
+    if in_size < 1:
+        return DATA_CORRUPT, [], DATA_CORRUPT
+    nb = data[0]
+    if nb == 1:
+        return 1, [], 0
+    if nb < 1 or nb > 8 or in_size < 1 + 8 * nb:
+        return DATA_CORRUPT, [], DATA_CORRUPT
+    ip, op, subs = 1 + 8 * nb, 0, []
+    for b in range(nb):
+        osz, isz = struct.unpack_from("<ii", data, 1 + 8 * b)
+        if osz < 0 or isz < 0 or ip + isz > in_size or op + osz > max_out:
+            return nb, subs, DATA_CORRUPT
+        subs.append([isz, osz, ip, op])
+        ip, op = ip + isz, op + osz
+    return nb, subs, 0

@@ -25,6 +25,26 @@ def _texts():
     return out
 
 
+def _raw_sub_block_cases():
+    """coder inputs (given to it as they are: a BWT in front would mix the halves) of more than one sub-block, some of which do not
+    compress: a raw sub-block comes last or first, or the whole payload does not pay"""
+    from libbsc_amd.synth import synth_text_v1
+    rng = np.random.default_rng(20261020)
+    noise = lambda n: rng.integers(0, 256, n, dtype=np.uint8)
+    return [("noise300k", noise(300_000)),
+            ("text+noise", np.concatenate([synth_text_v1(9, 200_000), noise(200_000)])),
+            ("noise+text", np.concatenate([noise(200_000), synth_text_v1(9, 200_000)])),
+            ("lowent600k", rng.integers(0, 200, 600_000, dtype=np.uint8)),
+            ("text4m+noise1m", np.concatenate([synth_text_v1(4, 4 << 20), noise(1 << 20)]))]
+
+
+def _raw_flags(payload):
+    """per sub-block of a coder payload: is it kept raw"""
+    import struct
+    nb = payload[0]
+    return [False] if nb == 1 else [struct.unpack_from("<ii", payload, 1 + 8 * b)[0] == struct.unpack_from("<ii", payload, 1 + 8 * b)[1] for b in range(nb)]
+
+
 def test_synth_generators_agree_and_match_survey_md5():
     from libbsc_amd.synth import synth_text_v1
     a = synth_text_v1(1, 1 << 20)
@@ -69,11 +89,18 @@ def test_qlfc_encode_block_matches_reference(ref, coder):
 def test_coder_compress_matches_reference(ref, coder, features):
     from libbsc_amd.synth import synth_text_v1
     cases = _texts() + [("text5m", synth_text_v1(4, 5 << 20))]        # 4 sub-blocks
-    for name, T in cases:
-        L, _, _ = ref.bwt_encode(T, aux=False)
+    cases = [(name, ref.bwt_encode(T, aux=False)[0]) for name, T in cases] + _raw_sub_block_cases()
+    shapes = {}
+    for name, L in cases:
         want = ref.coder_compress(L, coder, features=features)
         got = api.bsc_coder_compress(L, coder, features=features)
         assert got == want, (name, coder, features)
+        shapes[name] = want if isinstance(want, int) else _raw_flags(want)
+    # what the added inputs are there for (coder 2 may frame them otherwise: held to the reference above, not to these shapes)
+    if coder != 2:
+        assert shapes["noise300k"] == api.NOT_COMPRESSIBLE
+        assert (shapes["text+noise"], shapes["noise+text"]) == ([False, True], [True, False])
+        assert (shapes["lowent600k"], shapes["text4m+noise1m"]) == ([False] * 2, [False] * 4)
 
 
 def test_store_and_block_info_match_reference(ref):

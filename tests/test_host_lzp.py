@@ -40,6 +40,12 @@ def test_lzp_stage_matches_reference(ref, features):
                 if not isinstance(got, int):
                     assert api.bsc_lzp_decompress(got, T.size, h, m) == T.tobytes(), (name, h, m)
                     assert ref.lzp_decompress(got, T.size, h, m) == T.tobytes(), (name, h, m)
+    # two chunks, the first kept raw: 299 000 random bytes, then zeros
+    T = np.concatenate([np.random.default_rng(6).integers(0, 256, 299_000, dtype=np.uint8), np.zeros(1000, np.uint8)])
+    want = ref.lzp_compress(T, 15, 32, features=features)
+    got = api.bsc_lzp_compress(T, 15, 32, features=features)
+    assert not isinstance(want, int) and want[0] == 2 and want[1:5] == want[5:9] and want[9:13] != want[13:17]
+    assert got == want and api.bsc_lzp_decompress(got, T.size, 15, 32) == T.tobytes()
 
 
 def test_lzp_tiny_and_boundary_sizes(ref):
