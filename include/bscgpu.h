@@ -46,6 +46,9 @@ BSCGPU_API void bscgpu_destroy(bscgpu_ctx* ctx);
 
 /* Bytes of device memory held by the context's arena. */
 BSCGPU_API int64_t bscgpu_arena_bytes(const bscgpu_ctx* ctx);
+/* Bytes of the device model's own arena (carved on the first -e1 / -e0 block or pass that takes the device model, for
+ * ceil(max_n / BSCGPU_OPT_DC_ARENA_DIV); 0 before that).  bscgpu_arena_bytes does not count it. */
+BSCGPU_API int64_t bscgpu_model_arena_bytes(const bscgpu_ctx* ctx);
 
 /* ---- forward BWT ------------------------------------------------------------------------- */
 /* L may alias T.  Returns the primary index (1..n) like libcubwt_bwt, or a negative error. */
@@ -616,7 +619,8 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          pass BSCGPU_CNT_DC_LAST_FAIL is the OR of those blocks' reasons.
  *                          (Counted per block of the layout: with HBM input a block that rides along untransformed — stored, or left to
  *                          the single path — is planned like any other and counts here if the device leaves it out.)
- * BSCGPU_CNT_DC_DCAP       (get only) decisions the device model's arena holds for this context (a pass or segment above it cannot be modelled).
+ * BSCGPU_CNT_DC_DCAP       (get only) decisions the device model's arena holds for this context (a pass or segment above it cannot be modelled):
+ *                          4 Mcap + 65536, where Mcap — the runs it holds — is ceil(max_n / BSCGPU_OPT_DC_ARENA_DIV) + 4096 rounded up to 4096.
  * BSCGPU_OPT_BATCH_MODEL_PACKED  0 (default) / 1: with BSCGPU_OPT_BATCH_MODEL on (with or without _SEGMENTS) and -e1, a pass's or a
  *                          segment's stream is written and brought down in the packed 13-bit form (13 bytes per eight decisions instead
  *                          of 16: the pinned landing buffers hold 16 / 13 as many decisions) and coded by bscgpu_front_batch_code_ps13;
@@ -624,6 +628,21 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          is void goes down as 16-bit entries.  -e0, -e2, the L route and single blocks are not affected.  Same output.
  * BSCGPU_CNT_BATCH_PACKED_PASSES, BSCGPU_CNT_BATCH_PACKED_VOID  (get only) passes or segments of this context that went down packed, and
  *                          those whose packed form was void and went down as 16-bit entries.
+ * BSCGPU_OPT_DC_ARENA_DIV  1 (default) / 2 / 4 / 8 (BSC_DC_ARENA_DIV in the environment, read when a context is created, sets the same): the
+ *                          device model's arena is carved for the runs and decisions of ceil(max_n / k) bytes instead of max_n — about
+ *                          221 / k + 1 bytes per byte of max_n (the avg_rank flags keep their byte per run of the whole block).  A single
+ *                          -e1 / -e0 block above that capacity is modelled in segments of whole sub-blocks, one after the other through
+ *                          the same two stream buffers, each segment's pieces landing where the whole block's would
+ *                          (bscgpu_block_segment_plan cuts; DESIGN §3.6, "A block in sub-block segments"); a block one of whose
+ *                          sub-blocks alone exceeds the capacity takes the host model (BSCGPU_DC_FAIL_CAP).  Not combined with
+ *                          BSCGPU_OPT_DEVICE_RC: the stream of a block in more than one segment goes down and the host codes it.  Batched
+ *                          passes see the smaller capacity (BSCGPU_CNT_DC_DCAP): the segments route cuts finer, a whole-pass model above it
+ *                          declines with BSCGPU_DC_FAIL_CAP.  Set while the context's arena exists with another value:
+ *                          LIBBSC_NOT_SUPPORTED, nothing changes; other values: LIBBSC_BAD_PARAMETER.  Same output.
+ * BSCGPU_CNT_DC_BLOCK_SEGMENTS  (get only) segments the last single block given to the device model of a context with a divided arena ran
+ *                          in: 1 = whole, 0 = declined before any ran (or the arena is not divided: such a block takes the whole-block
+ *                          route without the plan's facts).  Segments of a packed block count in BSCGPU_CNT_BATCH_PACKED_PASSES, one
+ *                          whose packed form was void — re-run as 16-bit entries and packed into place by the host — in _PACKED_VOID.
  * Environment only, no option key: BSC_UNBWT_STEP_CAP (read when a context is created, like BSC_PS13; values below 16 are ignored) is the
  *                          inverse BWT's step cap, 1 << 22 by default — a test knob for the LIBBSC_NOT_SUPPORTED exits (see bscgpu_unbwt).
  * set returns the previous value or a negative libbsc error code; get the value or a negative error code. */
@@ -639,13 +658,25 @@ enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACK
        BSCGPU_OPT_BATCH_MODEL_PACKED = 27, BSCGPU_CNT_BATCH_PACKED_PASSES = 28, BSCGPU_CNT_BATCH_PACKED_VOID = 29,
        BSCGPU_OPT_DC_AVG_EXACT = 30, BSCGPU_CNT_DC_AVG_RESOLVED = 31,
        BSCGPU_OPT_DC_REPLAY_EXACT = 32, BSCGPU_CNT_DC_REPLAY_RESOLVED = 33,
-       BSCGPU_OPT_DC_HIST_EXACT = 34, BSCGPU_CNT_DC_HIST_RESOLVED = 35 };
+       BSCGPU_OPT_DC_HIST_EXACT = 34, BSCGPU_CNT_DC_HIST_RESOLVED = 35,
+       BSCGPU_OPT_DC_ARENA_DIV = 36, BSCGPU_CNT_DC_BLOCK_SEGMENTS = 37 };
 /* _FAIL_AVG: undecided avg_rank flags; _FAIL_HIST: a run_hist bracket open after 9216 predecessors (never with
  * BSCGPU_OPT_DC_HIST_EXACT); _FAIL_CAP: more runs or decisions
  * than the context's arena holds; _FAIL_REPLAY: a chain whose bracket stayed open over more than 64 evaluation chunks (with
  * BSCGPU_OPT_DC_REPLAY_EXACT: only behind the resolve's guard). */
 enum { BSCGPU_DC_FAIL_AVG = 2, BSCGPU_DC_FAIL_HIST = 4, BSCGPU_DC_FAIL_CAP = 8, BSCGPU_DC_FAIL_REPLAY = 16 };
 BSCGPU_API int bscgpu_option_set(bscgpu_ctx* ctx, int key, int value);
+/* Where a single block is cut when the device model's arena holds less than the block (BSCGPU_OPT_DC_ARENA_DIV): pure host arithmetic,
+ * no GPU needed.  Sub-blocks in order (nsub in 1..8), sub_runs[s] runs and sub_dec[s] decisions each; consecutive sub-blocks join a
+ * segment while the runs stay within mcap and the decisions within dcap (greedy: the fewest contiguous segments).  seg_of[s]: the
+ * segment of sub-block s.  Returns the number of segments; LIBBSC_NOT_SUPPORTED when one sub-block alone exceeds a capacity,
+ * LIBBSC_BAD_PARAMETER for null pointers, nsub outside 1..8 or a capacity <= 0 — nothing is written then. */
+BSCGPU_API int bscgpu_block_segment_plan(const uint32_t* sub_runs, const uint32_t* sub_dec, int nsub, int64_t mcap, int64_t dcap, int* seg_of);
+/* The facts that plan is made of, as a stage on its own (tests, tools; like bscgpu_model_segment_facts_device for a pass): the sorted
+ * block L[0..n) through the sub-block split and the run / rank front end, then per sub-block its runs, its decisions for `coder`
+ * (1: -e1, 3: -e0) and the avg_rank flags the bracket (with BSCGPU_OPT_DC_AVG_EXACT: the resolve) left open (-e0: none).  Arrays of 8. */
+BSCGPU_API int bscgpu_qlfc_pstream_facts(bscgpu_ctx* ctx, const uint8_t* L, int n, int coder, int* nblocks, int* sub_start, int* sub_size,
+                                         uint32_t* sub_runs, uint32_t* sub_dec, uint32_t* sub_und);
 BSCGPU_API int bscgpu_option_get(bscgpu_ctx* ctx, int key);
 /* Process-wide counts since start (tests, reports): blocks whose static model ran on the GPU, how many of those were LZP-preprocessed,
  * and blocks that took the device model first and were redone with the model on the host (a sub-block that does not compress has to

@@ -198,6 +198,7 @@ extern "C" int bscgpu_create(bscgpu_ctx** out, int device, int64_t max_n)
     c->device = device;
     c->max_n  = max_n;
     { const char* e = getenv("BSC_PS13"); c->dc_p13 = (e && e[0] == '0') ? 0 : 1; }       // BSCGPU_OPT_DC_PACKED_STREAM
+    { const char* e = getenv("BSC_DC_ARENA_DIV"); const int k = e ? atoi(e) : 1; c->dc_arena_div = (k == 2 || k == 4 || k == 8) ? k : 1; }   // BSCGPU_OPT_DC_ARENA_DIV
     { const char* e = getenv("BSC_DC_AVG_EXACT"); c->dc_avg_exact = (e && e[0] == '1') ? 1 : 0; }      // BSCGPU_OPT_DC_AVG_EXACT
     { const char* e = getenv("BSC_DC_REPLAY_EXACT"); c->dc_replay_exact = (e && e[0] == '1') ? 1 : 0; }      // BSCGPU_OPT_DC_REPLAY_EXACT
     { const char* e = getenv("BSC_DC_HIST_EXACT"); c->dc_hist_exact = (e && e[0] == '1') ? 1 : 0; }      // BSCGPU_OPT_DC_HIST_EXACT
@@ -293,6 +294,7 @@ extern "C" void bscgpu_destroy(bscgpu_ctx* c)
 }
 
 extern "C" int64_t bscgpu_arena_bytes(const bscgpu_ctx* c) { return c ? (int64_t)(c->arena_bytes + c->batch_bytes + c->front_bytes + c->rc_tab_bytes) + devcoder_batch_bytes(c) : 0; }
+extern "C" int64_t bscgpu_model_arena_bytes(const bscgpu_ctx* c) { return c ? devcoder_arena_bytes(c) : 0; }
 extern "C" const char* bscgpu_last_error(const bscgpu_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 // ---- profiling --------------------------------------------------------------------------------
@@ -366,6 +368,7 @@ extern "C" int bscgpu_option_set(bscgpu_ctx* c, int key, int value)
     if (key == BSCGPU_OPT_BATCH_MODEL_SEGMENTS && (value == 0 || value == 1)) { const int old = c->batch_model_segments; c->batch_model_segments = value; return old; }
     if (key == BSCGPU_OPT_BATCH_MODEL_PACKED && (value == 0 || value == 1)) { const int old = c->batch_model_packed; c->batch_model_packed = value; return old; }
     if (key == BSCGPU_OPT_BWT_FOLD && value >= 0 && value <= 2) { const int old = c->bwt_fold; c->bwt_fold = value; return old; }
+    if (key == BSCGPU_OPT_DC_ARENA_DIV) return devcoder_arena_div_set(c, value);
     return BSC_BAD_PARAMETER;
 }
 extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
@@ -405,6 +408,8 @@ extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
     if (key == BSCGPU_CNT_BATCH_PACKED_VOID) return c->cnt_packed_void;
     if (key == BSCGPU_OPT_BWT_FOLD) return c->bwt_fold;
     if (key == BSCGPU_CNT_BWT_FOLDED) return c->cnt_bwt_folded;
+    if (key == BSCGPU_OPT_DC_ARENA_DIV) return c->dc_arena_div;
+    if (key == BSCGPU_CNT_DC_BLOCK_SEGMENTS) return c->cnt_block_segments;
     return BSC_BAD_PARAMETER;
 }
 extern "C" int bscgpu_last_stage_ms(bscgpu_ctx* c, double* out6)

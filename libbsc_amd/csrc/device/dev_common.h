@@ -8,6 +8,7 @@
 
 #include "../../../include/bscgpu.h"
 #include "bwt_plan.h"      // RadixPass; the BWT driver's plan (host arithmetic, no HIP)
+#include "dc_block_plan.h" // DcBlockSchedule: a single block in sub-block segments (host arithmetic, no HIP)
 
 typedef unsigned long long u64;
 typedef unsigned int       u32;
@@ -168,6 +169,8 @@ struct bscgpu_ctx {
     int  dc_replay_exact = 0;        // BSCGPU_OPT_DC_REPLAY_EXACT: open chunk starts of the evaluation are resolved exactly (BSC_DC_REPLAY_EXACT=1)
     int  dc_hist_exact = 0;          // BSCGPU_OPT_DC_HIST_EXACT: open run_hist brackets are resolved exactly on the device (BSC_DC_HIST_EXACT=1)
     u32  dc_replay_cand = 0;        // ... the widest start bracket that resolve walks, if BSC_DC_REPLAY_CAND sets one (a test knob); 0: DC_RP_CAND.  devcoder_rp_ensure clamps it to DC_RP_CAND
+    int  dc_arena_div = 1;           // BSCGPU_OPT_DC_ARENA_DIV: the device coder's arena holds ceil(max_n / this) bytes' worth of runs and decisions (BSC_DC_ARENA_DIV)
+    int  cnt_block_segments = 0;     // BSCGPU_CNT_DC_BLOCK_SEGMENTS: segments the last single block given to the device model ran in
     int  dc_p13 = 1;                 // BSCGPU_OPT_DC_PACKED_STREAM: the static coder's p stream leaves as 13 bits per decision (BSC_PS13=0: 16-bit entries)
     bool os_gave_up = false;         // radix_onesweep_check found a give-up: the caller may redo its sorts through the three-kernel passes
     // BWT first sort: the leftover low digit of the key is sorted by key packing (bwt.hip: bwt_pack_fold_kernel)
@@ -316,6 +319,29 @@ int  devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32*
                       const int* max_rank, u32* D_out, u32* poff_out, u16* dbg, int psbuf = 0, int coder = 1 /* 1 static (-e1), 3 fast (-e0) */,
                       int* packed_out = nullptr /* non-null: the caller takes the 13-bit packed stream (devcoder.hip DcP13); *packed_out = 1 if that is what was written */);
 const u16* devcoder_pstream_ptr(const bscgpu_ctx* c, int psbuf = 0);
+// ... of a block in segments of whole sub-blocks ("A block in sub-block segments"), for a context whose arena is divided
+// (BSCGPU_OPT_DC_ARENA_DIV > 1).  devcoder_block_begin: the facts of the block — the avg_rank flags of all its runs, every sub-block's
+// decisions and undecided flags, one sync — and the plan made of them (B->plan, dc_block_plan.h); take_packed: the block's stream is
+// the 13-bit form (coder 1 with BSCGPU_OPT_DC_PACKED_STREAM), else 16-bit entries.  BSC_NOT_SUPPORTED: the block is declined before any
+// segment ran (c->dc_note.fail: FAIL_AVG an open flag, FAIL_CAP a sub-block alone above the capacity, 0 an arena did not fit).
+// devcoder_block_segment: the model of segment g of the plan into the device p stream psbuf, laid out as g says; *host_packed: its
+// packed form was void, the 16-bit entries lie there instead and the caller packs them into place (dc_pack13_host).
+// BSC_NOT_SUPPORTED: the segment, and with it the block, is declined.  Either way c->dc_note is the sum over the segments run so far
+// and BSCGPU_CNT_DC_BLOCK_SEGMENTS counts the ones that stayed.
+struct DcBlock {
+    const u8 *sym = nullptr, *rank = nullptr; const u32* start = nullptr; u32 m = 0, n = 0; int nb = 0; bool fast = false, packed = false;
+    u32 maxr[8] = {}, end[8] = {} /* the byte behind each sub-block */, dec[8] = {}, und[8] = {};
+    DcBlockSchedule plan;
+    DcNote sum;
+};
+int  devcoder_block_begin(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* dstart, u32 m, u32 n, int nb, const int* sub_start,
+                          const int* sub_size, const u32* run_first, const int* max_rank, int coder, bool take_packed, DcBlock* B);
+// ... the facts alone (bscgpu_qlfc_pstream_facts): B->dec / B->und, whatever the divisor; no plan, nothing declined for an open flag
+int  devcoder_block_facts(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* dstart, u32 m, u32 n, int nb, const int* sub_start,
+                          const int* sub_size, const u32* run_first, const int* max_rank, int coder, DcBlock* B);
+int  devcoder_block_segment(bscgpu_ctx* c, DcBlock* B, const DcBlockSeg& g, int psbuf, bool* host_packed);
+int  devcoder_arena_div_set(bscgpu_ctx* c, int value);     // BSCGPU_OPT_DC_ARENA_DIV: the previous value, or a negative libbsc code
+int64_t devcoder_mcap(const bscgpu_ctx* c);             // runs the device model's arena holds for this context
 // ... of a whole batched pass ("The static coder's model of a pass"): after qlfc_front_batch, from the run arrays and the
 // table it left in HBM -> *D_out decisions in devcoder_pstream_ptr(c, 0), sub-block s's at [poff[s], poff[s + 1]) with poff[0..nsub] at
 // devcoder_batch_poff_ptr (device).  BSC_NOT_SUPPORTED: the pass is declined (c->dc_note.fail: BSCGPU_DC_FAIL_*; 0: an arena did not

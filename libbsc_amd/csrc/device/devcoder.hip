@@ -122,7 +122,8 @@ struct DcRpRec {
 struct DcArena { char* base = nullptr; size_t bytes = 0; bool failed = false; };
 
 struct DevCoder {
-    size_t Mcap = 0, Dcap = 0;
+    size_t Mcap = 0, Dcap = 0;                                 // runs and decisions a unit of model work may have (of max_n / BSCGPU_OPT_DC_ARENA_DIV)
+    size_t Gcap = 0;                                           // runs of a whole block (of max_n): what ge32 holds
     DcArena arena;
     u64 *key_ch = nullptr, *key_ch_s = nullptr, *key_sr = nullptr, *key_sr_s = nullptr, *key_sn = nullptr, *key_sn_s = nullptr;
     u32 *inv_ch = nullptr, *inv_sr = nullptr, *inv_sn = nullptr;
@@ -166,6 +167,9 @@ struct DevCoder {
     // of DC_HIST_CH runs, 130 per group of DC_HIST_GROUP chunks — 0.2 byte per byte of max_n
     DcArena hist_arena;
     DcHistRec hist = {};
+    // a block in sub-block segments (devcoder_block_begin), allocated on its first use: decisions and undecided flags of its eight sub-blocks
+    DcArena blk_arena;
+    u32 *blk_dec = nullptr, *blk_und = nullptr;
 };
 
 __device__ __forceinline__ u32 dc_sb_of(u32 j, const DcSub& S)
@@ -202,6 +206,7 @@ __device__ __forceinline__ u32 dc_sb_of(u32 j, const DcSubTab& S) { return batch
 template <class SB> struct DcForm;
 template <> struct DcForm<DcSub> {
     static constexpr bool TAB = false;
+    static constexpr bool SUB_UND = false;                            // the avg_rank kernels count open flags for the block only
     static constexpr int CHAIN_SHIFT = ITEM_CHAIN_SHIFT;
     typedef Item It;
     static __device__ __forceinline__ It unpack(u64 k) { return item_unpack(k); }
@@ -219,6 +224,7 @@ template <> struct DcForm<DcSub> {
 };
 template <> struct DcForm<DcSubTab> {
     static constexpr bool TAB = true;
+    static constexpr bool SUB_UND = true;                             // ... and per sub-block (sub_und)
     static constexpr int CHAIN_SHIFT = ITEMB_CHAIN_SHIFT;
     typedef ItemB It;
     static __device__ __forceinline__ It unpack(u64 k) { return item_unpack_b(k); }
@@ -241,6 +247,10 @@ template <> struct DcForm<DcSubTab> {
         return item_pack_b(sym[j], sb, ge32[j], rank[j], S.maxr[sb], end - start[j]);
     }
 };
+// The eight-entry form where the facts of a block in segments are taken (dc_block_facts): DcSub in everything, but the avg_rank kernels
+// count the flags they leave open per sub-block as they do for a table.  A form of its own, so that the kernels of DcSub stay as they are.
+struct DcSubU : DcSub {};
+template <> struct DcForm<DcSubU> : DcForm<DcSub> { static constexpr bool SUB_UND = true; };
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 1a. avg_rank >= 32 (qlfc.cpp:903 / :978): avg' = (avg * 124 + rank * 4) >> 7, reset per sub-block.  One lane per chunk,
@@ -253,7 +263,7 @@ struct DcAvgNoRec {};
 enum : u32 { DC_AVG_ST_START = 1 /* a sub-block starts inside the chunk: whatever it started from, it ends the same */, DC_AVG_ST_WIDE = 2 /* DC_AVG_CAND values or more */ };
 template <class SB, bool REC = false>
 __global__ __launch_bounds__(WG) void dc_avg_kernel(const u8* __restrict__ rank, u32 m, SB S, u8* __restrict__ ge32, u32* __restrict__ meta,
-                                                    u32* __restrict__ sub_und /* table only (may be null): undecided flags per sub-block */,
+                                                    u32* __restrict__ sub_und /* forms with SUB_UND only (may be null): undecided flags per sub-block */,
                                                     typename std::conditional<REC, DcAvgRec, DcAvgNoRec>::type R)
 {
     typedef DcForm<SB> F;
@@ -272,7 +282,7 @@ __global__ __launch_bounds__(WG) void dc_avg_kernel(const u8* __restrict__ rank,
     if constexpr (REC) { R.brk[c] = (u16)(lo | hi << 8); if (hi - lo >= (u32)DC_AVG_CAND) st = DC_AVG_ST_WIDE; }
     for (u32 j = (u32)j0; j < j1; ++j) {
         if (j == next_first) {
-            if constexpr (F::TAB) { if (sub_und && und != und_flushed) atomicAdd(&sub_und[sb], und - und_flushed); und_flushed = und; }
+            if constexpr (F::SUB_UND) { if (sub_und && und != und_flushed) atomicAdd(&sub_und[sb], und - und_flushed); und_flushed = und; }
             lo = hi = 0; ++sb; next_first = F::next_first(S, sb);
             if constexpr (REC) st |= DC_AVG_ST_START;
         }
@@ -282,7 +292,7 @@ __global__ __launch_bounds__(WG) void dc_avg_kernel(const u8* __restrict__ rank,
         const u32 r = rank[j];
         lo = avg_rank_next(lo, r); hi = avg_rank_next(hi, r);
     }
-    if constexpr (F::TAB) { if (sub_und && und != und_flushed) atomicAdd(&sub_und[sb], und - und_flushed); }
+    if constexpr (F::SUB_UND) { if (sub_und && und != und_flushed) atomicAdd(&sub_und[sb], und - und_flushed); }
     if (und) atomicAdd(&meta[DM_AVG_UND], und);
     if constexpr (REC) { R.und[c] = (u16)und; R.st[c] = (u8)st; }
 }
@@ -491,7 +501,7 @@ __global__ __launch_bounds__(WG) void dc_avg_fix_kernel(const u8* __restrict__ r
         for (u32 k = 0; k < 16u; ++k) {
             if (jb + k < j1) {
                 if (jb + k == next_first) {
-                    if constexpr (F::TAB) { if (sub_und && left && lane == 0) atomicAdd(&sub_und[sb], left); }
+                    if constexpr (F::SUB_UND) { if (sub_und && left && lane == 0) atomicAdd(&sub_und[sb], left); }
                     left = 0; lo = hi = x = 0; ++sb; next_first = F::next_first(S, sb);
                 }
                 left += (u32)(!known && (lo >= 32u) != (hi >= 32u));
@@ -503,7 +513,7 @@ __global__ __launch_bounds__(WG) void dc_avg_fix_kernel(const u8* __restrict__ r
         if (lane == l) mine = bits;
     }
     if (lane == 0) {
-        if constexpr (F::TAB) { if (sub_und && left) atomicAdd(&sub_und[sb], left); }
+        if constexpr (F::SUB_UND) { if (sub_und && left) atomicAdd(&sub_und[sb], left); }
         atomicAdd(&meta[known ? DM_AVG_RESOLVED : DM_AVG_LEFT], und);
     }
     if (!known) return;
@@ -1966,6 +1976,45 @@ __global__ __launch_bounds__(WG) void dc_sub_dec_kernel(const u8* __restrict__ s
     const u32 before = (u32)__shfl((int)(incl - nd), (int)first, 64); // the scan in front of the stretch
     if (tail && j < m && incl != before) atomicAdd(&sub_dec[sb], incl - before);
 }
+// ... of a single block (a block in sub-block segments, dc_block_facts): the eight-entry twin — Item, run lengths up to 2^31 (n: the
+// block's bytes, the end of its last run), max_rank from the packed word.  A block has tens of millions of runs and eight counters: one
+// atomic per wavefront of 64 runs (the table's way, where thousands of sub-blocks share them) would queue half a million atomics on
+// eight addresses — 5 ms for the bench block.  So a wavefront walks tiles of 64 runs at the grid's stride and keeps the counts in
+// registers, lane b the one of sub-block b (the sum of every stretch is handed to its lane: one or two stretches a tile), and adds them
+// at the end: at most eight atomics per wavefront, a few thousand a block.
+constexpr u32 DC_SUB_DEC8_GRID = 2048;
+__global__ __launch_bounds__(WG) void dc_sub_dec8_kernel(const u8* __restrict__ sym, const u8* __restrict__ rank, const u32* __restrict__ start,
+                                                         const u8* __restrict__ ge32, u32 m, u32 n, DcSub S, u32* __restrict__ sub_dec /*[8]*/)
+{
+    typedef DcForm<DcSub> F;
+    const u32 maxr_w = F::maxr_word(S);
+    const u32 lane = threadIdx.x & 63u;
+    const u32 wave = blockIdx.x * WAVES + (threadIdx.x >> 6), nwaves = gridDim.x * WAVES;
+    const u32 tiles = (m + 63u) / 64u;
+    u32 acc = 0;                                                      // lane b < 8: decisions of sub-block b in this wavefront's tiles
+    for (u32 t = wave; t < tiles; t += nwaves) {
+        const u32 j = t * 64u + lane;
+        u32 nd = 0, sb = 8u;                                          // (lanes past the end: a stretch of their own that no lane owns)
+        if (j < m) {
+            const Item it = F::unpack(F::item(S, sym, rank, start, ge32, j, m, n));
+            sb = it.sb;
+            nd = (u32)(count_rank_side(it, F::maxr(it, maxr_w)) + count_run_side(it));
+        }
+        const u32 incl = wave_incl_sum(nd);
+        const u32 prev_sb = (u32)__shfl_up((int)sb, 1, 64);
+        // runs are in stream order, so the sub-block id does not decrease across the tile: at most nine stretches, one loop trip each
+        for (u64 h = __ballot(lane == 0u || prev_sb != sb); h != 0ull; h &= h - 1ull) {
+            const u32 first = (u32)__builtin_ctzll(h);
+            const u64 rest = h & (h - 1ull);
+            const u32 last = rest ? (u32)__builtin_ctzll(rest) - 1u : 63u;
+            const u32 before = first ? (u32)__shfl((int)incl, (int)first - 1, 64) : 0u;
+            const u32 sum = (u32)__shfl((int)incl, (int)last, 64) - before;
+            const u32 owner = (u32)__shfl((int)sb, (int)first, 64);
+            if (lane == owner) acc += sum;
+        }
+    }
+    if (lane < 8u && acc != 0u) atomicAdd(&sub_dec[lane], acc);
+}
 // The rebased run table of the segment [s0, s0 + nsub_seg) whose runs are [r0, r1): to every kernel instantiated for a table the
 // segment then is a small pass of its own (sub_off / sub_base / maxr enter offset by s0, the run arrays and flags offset by r0).
 __global__ __launch_bounds__(WG) void dc_seg_tab_kernel(const u32* __restrict__ sub_run, u32 s0, u32 nsub_seg, u32 r0, u32 r1, u32* __restrict__ seg_run)
@@ -2043,7 +2092,7 @@ static bool dc_arena_alloc(DcArena& a, const Carve (&carve)[N], const char* fail
 // Everything a DevCoder owns, whether it is the context's or one whose set-up did not get that far.
 static void dc_free(DevCoder* d)
 {
-    for (DcArena* a : {&d->arena, &d->batch_arena, &d->avg_arena, &d->rp_arena, &d->hist_arena}) if (a->base) (void)hipFree(a->base);
+    for (DcArena* a : {&d->arena, &d->batch_arena, &d->avg_arena, &d->rp_arena, &d->hist_arena, &d->blk_arena}) if (a->base) (void)hipFree(a->base);
     for (int k = 0; k < 2; ++k) if (d->seg_ev[k]) (void)hipEventDestroy(d->seg_ev[k]);
     if (d->hmeta) (void)hipHostFree(d->hmeta);
     delete d;
@@ -2082,7 +2131,19 @@ void devcoder_warm_tables()
 // the arena's capacity: runs (bytes of max_n, padded) and decisions (four per byte of that)
 static size_t dc_capacity_runs(int64_t max_n) { return ((size_t)max_n + 4096 + 4095) / 4096 * 4096; }
 static size_t dc_capacity_decisions(int64_t max_n) { return 4 * dc_capacity_runs(max_n) + 65536; }
-int64_t devcoder_dcap(const bscgpu_ctx* c) { return (int64_t)dc_capacity_decisions(c->max_n); }
+// ... of ceil(max_n / k) for the context's arena divisor k (BSCGPU_OPT_DC_ARENA_DIV; 1: max_n itself)
+static int64_t dc_capacity_n(const bscgpu_ctx* c) { return (c->max_n + c->dc_arena_div - 1) / c->dc_arena_div; }
+int64_t devcoder_dcap(const bscgpu_ctx* c) { return (int64_t)dc_capacity_decisions(dc_capacity_n(c)); }
+int64_t devcoder_mcap(const bscgpu_ctx* c) { return (int64_t)dc_capacity_runs(dc_capacity_n(c)); }
+// The divisor can change only while no arena was carved by another one.
+int devcoder_arena_div_set(bscgpu_ctx* c, int value)
+{
+    if (value != 1 && value != 2 && value != 4 && value != 8) return BSC_BAD_PARAMETER;
+    if (c->dc && value != c->dc_arena_div) return BSC_NOT_SUPPORTED;
+    const int old = c->dc_arena_div;
+    c->dc_arena_div = value;
+    return old;
+}
 
 int devcoder_ensure(bscgpu_ctx* c)
 {
@@ -2092,12 +2153,16 @@ int devcoder_ensure(bscgpu_ctx* c)
     if (c->dc_alloc_failed) return BSC_NOT_SUPPORTED;
     CtxTimer tm("devcoder_ensure (arena, tables)");
     DevCoder* d = new DevCoder();
-    d->Mcap = dc_capacity_runs(c->max_n); d->Dcap = dc_capacity_decisions(c->max_n);
-    const size_t M = d->Mcap + 64, D = d->Dcap + 64, NCH = d->Dcap / DC_EV + 16;
+    // (BSCGPU_OPT_DC_ARENA_DIV: the capacity of 1 / k of max_n; a block above it is modelled in sub-block segments.  ge32 alone keeps a
+    // byte per run of the whole block: the facts the plan is made of are taken over all of it, once — k = 1: G == M, the carve as ever)
+    const int64_t cap_n = dc_capacity_n(c);
+    d->Mcap = dc_capacity_runs(cap_n); d->Dcap = dc_capacity_decisions(cap_n);
+    const size_t M = d->Mcap + 64, D = d->Dcap + 64, NCH = d->Dcap / DC_EV + 16, G = dc_capacity_runs(c->max_n) + 64;
+    d->Gcap = G - 64;
     const Carve carve[] = {
         {(void**)&d->key_ch, 8 * M}, {(void**)&d->key_ch_s, 8 * M}, {(void**)&d->key_sr, 8 * M}, {(void**)&d->key_sr_s, 8 * M},
         {(void**)&d->key_sn, 8 * M}, {(void**)&d->key_sn_s, 8 * M},
-        {(void**)&d->inv_ch, 4 * M}, {(void**)&d->inv_sr, 4 * M}, {(void**)&d->inv_sn, 4 * M}, {(void**)&d->ge32, M},
+        {(void**)&d->inv_ch, 4 * M}, {(void**)&d->inv_sr, 4 * M}, {(void**)&d->inv_sn, 4 * M}, {(void**)&d->ge32, G},
         {(void**)&d->doff[0], 4 * M}, {(void**)&d->doff[1], 4 * M}, {(void**)&d->doff[2], 4 * M}, {(void**)&d->doff[3], 4 * M},
         {(void**)&d->events[0], 2 * D}, {(void**)&d->events[1], 2 * D}, {(void**)&d->events[2], 2 * D}, {(void**)&d->events[3], 2 * D},
         {(void**)&d->pos[0], 4 * D}, {(void**)&d->pos[1], 4 * D}, {(void**)&d->pos[2], 4 * D}, {(void**)&d->pos[3], 4 * D},
@@ -2144,7 +2209,7 @@ int devcoder_ensure(bscgpu_ctx* c)
 }
 
 int64_t devcoder_arena_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)c->dc->arena.bytes : 0; }
-int64_t devcoder_batch_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)(c->dc->batch_arena.bytes + c->dc->avg_arena.bytes + c->dc->rp_arena.bytes + c->dc->hist_arena.bytes) : 0; }
+int64_t devcoder_batch_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)(c->dc->batch_arena.bytes + c->dc->avg_arena.bytes + c->dc->rp_arena.bytes + c->dc->hist_arena.bytes + c->dc->blk_arena.bytes) : 0; }
 
 // One partition job: counts, scans, scatter.  SCATTER = false: counts and scans only, then the runs' offsets in the stream
 // (dc_doff_kernel) — all the fast coder needs of job 0, whose events nobody reads.
@@ -2178,8 +2243,9 @@ static DcNote dc_note_from(const u32* hmeta)
 static bool devcoder_avg_ensure(DevCoder* d)
 {
     if (d->avg_arena.base || d->avg_arena.failed) return !d->avg_arena.failed;
-    // chunks padded to whole groups, groups to the 64 that dc_avg_groups_kernel loads at a time
-    const size_t NC = (d->Mcap / DC_AVG_CH + 1 + DC_AVG_GROUP) / DC_AVG_GROUP * DC_AVG_GROUP + DC_AVG_GROUP, NG = (NC / DC_AVG_GROUP + 64) / 64 * 64 + 64;
+    // chunks padded to whole groups, groups to the 64 that dc_avg_groups_kernel loads at a time (of Gcap: the facts of a block in
+    // sub-block segments walk the flags of the whole block, whatever the arena's divisor; Gcap == Mcap without one)
+    const size_t NC = (d->Gcap / DC_AVG_CH + 1 + DC_AVG_GROUP) / DC_AVG_GROUP * DC_AVG_GROUP + DC_AVG_GROUP, NG = (NC / DC_AVG_GROUP + 64) / 64 * 64 + 64;
     const Carve carve[] = {
         {(void**)&d->avg.brk, 2 * NC}, {(void**)&d->avg.und, 2 * NC}, {(void**)&d->avg.st, NC}, {(void**)&d->avg.ex, 2 * NC},
         {(void**)&d->avg.map, (size_t)DC_AVG_CAND * NC}, {(void**)&d->avg.gmap, 2 * (size_t)DC_AVG_CAND * NG}, {(void**)&d->avg.gstart, 2 * NG},
@@ -2594,6 +2660,124 @@ int devcoder_pstream(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* 
     return BSC_NO_ERROR;
 }
 
+// ---- a block in sub-block segments ("A block in sub-block segments") ----------------------------------------------------
+// Sub-blocks are independent chains, so the model can run over any contiguous range of a block's sub-blocks and write the same entries
+// — what the batched path does with a pass (below), here in the eight-entry form, which takes run lengths up to 2^31: to every kernel
+// the range is a block of its own (S.first rebased to its first run, the run arrays and the flags offset by it, n = the end of its last
+// sub-block).  What is needed of the whole block comes first, once: the avg_rank flags of all its runs (ge32 holds a byte per run of
+// max_n) and, for the plan (dc_block_plan.h), every sub-block's decisions and the flags left open.
+static bool devcoder_block_ensure(DevCoder* d)
+{
+    if (d->blk_arena.base || d->blk_arena.failed) return !d->blk_arena.failed;
+    const Carve carve[] = {{(void**)&d->blk_dec, 8 * 4}, {(void**)&d->blk_und, 8 * 4}};
+    return dc_arena_alloc(d->blk_arena, carve, nullptr);
+}
+static DcSub dc_block_sub(int nb, const u32* first, const u32* maxr, u32 m)
+{
+    DcSub S; S.nb = (u32)nb;
+    for (int b = 0; b < 9; ++b) S.first[b] = (b <= nb) ? first[b] : m;
+    for (int b = 0; b < 8; ++b) S.maxr[b] = (b < nb) ? maxr[b] : 0u;
+    return S;
+}
+// The facts: flags behind dc_launch_avg over the whole block (the fast coder and a block that cannot escape: zero, as devcoder_pstream),
+// then dc_sub_dec8_kernel.  One sync.  B->sum: the avg values of the block, as a pass's in segments.
+static int dc_block_facts(bscgpu_ctx* c, DevCoder* d, DcBlock* B, const u32* run_first)
+{
+    u32 first[9];
+    for (int b = 0; b < 9; ++b) first[b] = b <= B->nb ? run_first[b] : B->m;
+    DcSubU S; static_cast<DcSub&>(S) = dc_block_sub(B->nb, first, B->maxr, B->m);
+    int rc = dc_unit_clear(c, d, /* kinds_seen: no model runs here */ false);
+    if (rc < 0) return rc;
+    HIP_TRY(c, hipMemsetAsync(d->blk_dec, 0, 8 * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d->blk_und, 0, 8 * 4, c->stream));
+    prof_begin(c, BSCGPU_K_DC_FACTS, (u64)B->m * 6, B->m);
+    bool may_escape = false;
+    for (int b = 0; b < B->nb && !B->fast; ++b) may_escape |= B->maxr[b] > 4u;
+    if (may_escape) {
+        rc = dc_launch_avg(c, d, B->rank, B->m, S, d->blk_und);
+        if (rc < 0) { prof_end(c); return rc; }
+    } else
+        HIP_TRY(c, hipMemsetAsync(d->ge32, 0, B->m, c->stream));
+    const u32 dec_grid = ((B->m + 63u) / 64u + WAVES - 1) / WAVES;
+    hipLaunchKernelGGL(dc_sub_dec8_kernel, dim3(dec_grid < DC_SUB_DEC8_GRID ? dec_grid : DC_SUB_DEC8_GRID), dim3(WG), 0, c->stream, B->sym, B->rank, B->start, d->ge32, B->m, B->n,
+                       static_cast<const DcSub&>(S), d->blk_dec);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(d->hmeta, d->meta, DM_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d->hmeta + HM_POFF, d->blk_dec, 8 * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d->hmeta + HM_POFF + 8, d->blk_und, 8 * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    prof_collect(c);
+    for (int b = 0; b < 8; ++b) { B->dec[b] = b < B->nb ? d->hmeta[HM_POFF + b] : 0u; B->und[b] = b < B->nb ? d->hmeta[HM_POFF + 8 + b] : 0u; }
+    B->sum.avg_und = (int)d->hmeta[DM_AVG_UND]; B->sum.avg_resolved = (int)d->hmeta[DM_AVG_RESOLVED];
+    return BSC_NO_ERROR;
+}
+static int dc_block_open(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* dstart, u32 m, u32 n, int nb, const int* sub_start,
+                         const int* sub_size, const int* max_rank, int coder, DcBlock* B)
+{
+    int rc = devcoder_ensure(c);
+    if (rc < 0) return rc;
+    DevCoder* d = c->dc;
+    c->cnt_block_segments = 0;
+    c->dc_note.clear(m > d->Gcap ? (int)FAIL_CAP : 0);
+    if (m == 0 || m > d->Gcap || nb < 1 || nb > 8) return BSC_NOT_SUPPORTED;
+    if (!devcoder_block_ensure(d)) return BSC_NOT_SUPPORTED;            // does not fit: declined, no reason bit (as the batch arena)
+    *B = DcBlock();
+    B->sym = dsym; B->rank = drank; B->start = dstart; B->m = m; B->n = n; B->nb = nb; B->fast = coder == 3;
+    // (the fast coder: `if (bits < 7)` closes the exponent (qlfc.cpp:1204), whatever the alphabet)
+    for (int b = 0; b < nb; ++b) { B->maxr[b] = B->fast ? 7u : (u32)max_rank[b]; B->end[b] = (u32)(sub_start[b] + sub_size[b]); }
+    return BSC_NO_ERROR;
+}
+int devcoder_block_begin(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* dstart, u32 m, u32 n, int nb, const int* sub_start,
+                         const int* sub_size, const u32* run_first, const int* max_rank, int coder, bool take_packed, DcBlock* B)
+{
+    int rc = dc_block_open(c, dsym, drank, dstart, m, n, nb, sub_start, sub_size, max_rank, coder, B);
+    if (rc < 0) return rc;
+    DevCoder* d = c->dc;
+    rc = dc_block_facts(c, d, B, run_first);
+    if (rc < 0) return rc;
+    c->dc_note = B->sum;
+    int64_t open = 0;
+    for (int b = 0; b < nb; ++b) open += B->und[b];
+    if (open) { c->dc_note.fail = (int)FAIL_AVG; return BSC_NOT_SUPPORTED; }       // (what dc_setup_kernel raises for a block run whole)
+    B->packed = take_packed && !B->fast && c->dc_p13 != 0;
+    B->plan = DcBlockSchedule(run_first, B->dec, nb, (int64_t)d->Mcap, (int64_t)d->Dcap, B->packed);
+    if (B->plan.segments() == DC_BLOCK_NOT_SUPPORTED) { c->dc_note.fail = (int)FAIL_CAP; return BSC_NOT_SUPPORTED; }
+    if (B->plan.segments() < 0) return ctx_fail(c, BSC_GPU_ERROR, "device coder: no plan for the block's segments", hipSuccess);
+    return BSC_NO_ERROR;
+}
+int devcoder_block_facts(bscgpu_ctx* c, const u8* dsym, const u8* drank, const u32* dstart, u32 m, u32 n, int nb, const int* sub_start,
+                         const int* sub_size, const u32* run_first, const int* max_rank, int coder, DcBlock* B)
+{
+    const int rc = dc_block_open(c, dsym, drank, dstart, m, n, nb, sub_start, sub_size, max_rank, coder, B);
+    return rc < 0 ? rc : dc_block_facts(c, c->dc, B, run_first);
+}
+int devcoder_block_segment(bscgpu_ctx* c, DcBlock* B, const DcBlockSeg& g, int psbuf, bool* host_packed)
+{
+    DevCoder* d = c->dc;
+    *host_packed = false;
+    int rc = dc_unit_clear(c, d, !B->fast);
+    if (rc < 0) return rc;
+    const DcSub S = dc_block_sub(g.s1 - g.s0, g.first, B->maxr + g.s0, g.r1 - g.r0);
+    DcUnit U;
+    U.sym = B->sym + g.r0; U.rank = B->rank + g.r0; U.start = B->start + g.r0; U.ge32 = d->ge32 + g.r0; U.m = g.r1 - g.r0;
+    U.n = B->end[g.s1 - 1];                                            // (the last run of the range ends with its sub-block)
+    U.psbuf = psbuf; U.expect = g.expect; U.ctx_open = false;
+    DcOut O;
+    O.take_packed = B->packed;
+    rc = B->fast ? dc_fast_run(c, d, S, U, O) : dc_static_run(c, d, S, U, O);
+    const DcNote& run = c->dc_note;
+    B->sum.fail |= run.fail; B->sum.replays += run.replays; B->sum.hist_ext += run.hist_ext;
+    B->sum.replay_resolved += run.replay_resolved; B->sum.hist_resolved += run.hist_resolved;
+    c->dc_note = B->sum;
+    if (rc < 0) return rc;
+    if (!B->plan.agrees(g, d->hmeta + HM_POFF)) return ctx_fail(c, BSC_GPU_ERROR, "device coder: a segment's sub-block offsets differ from the plan's", hipSuccess);
+    *host_packed = B->packed && !O.packed;
+    ++c->cnt_block_segments;
+    if (B->packed) ++(O.packed ? c->cnt_packed_passes : c->cnt_packed_void);
+    return BSC_NO_ERROR;
+}
+
 // ---- the model of a whole batched pass ------------------------------------------------------------------------------
 // What the wider chain identity needs on top of the arena, on the first pass that takes this route: every event's full sub-block
 // id (2 bytes per decision and family = 8 Dcap bytes, ~32 bytes per byte of max_n), max_rank and stream offset per sub-block.
@@ -2872,6 +3056,47 @@ const u16* devcoder_pstream_ptr(const bscgpu_ctx* c, int psbuf) { return c->dc ?
 // oracle's trace of the reference model: sub-block split (coder.cpp:70-109), run / rank front end and the model on the GPU.
 // Returns the number of decisions (their 16-bit entries are in out[0..)), BSC_NOT_SUPPORTED when the block needs the host
 // model (bscgpu_last_error tells why), or another negative libbsc code.
+// ... of a context with a divided arena (BSCGPU_OPT_DC_ARENA_DIV > 1): facts, plan, and the segments one after the other, each one's
+// pieces copied to where the plan puts them in out — the same out, poff and pbase as the whole block's (the bytes between a sub-block's
+// last group of eight and its padded extent are nobody's in either; a void segment is packed into place, where the whole block would
+// have been void).  The debug planes are the whole block's only.
+static int64_t qlfc_static_pstream_segments(bscgpu_ctx* c, int n, int nb, const int* sub_start, const int* sub_size, u32 m, const u32* run_first,
+                                            const int* max_rank, uint16_t* out, int64_t cap, int* nblocks_out, int64_t* poff_out, bool dbg,
+                                            bool want_packed, int64_t* pbase_out)
+{
+    if (dbg) { c->err = "the debug planes need the whole block in the arena (BSCGPU_OPT_DC_ARENA_DIV 1)"; return BSC_NOT_SUPPORTED; }
+    DcBlock B;
+    int rc = devcoder_block_begin(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, m, (u32)n, nb, sub_start, sub_size,
+                                  run_first, max_rank, 1, want_packed, &B);
+    if (rc == BSC_NO_ERROR && want_packed && !B.packed) { c->err = "the packed stream was not produced (option off)"; return BSC_NOT_SUPPORTED; }
+    std::vector<u16> void_entries;
+    const bool fits = B.plan.segments() > 0 && B.plan.zone_bytes() <= (want_packed ? cap : 2 * cap);
+    for (int i = 0; rc == BSC_NO_ERROR && i < B.plan.segments(); ++i) {
+        const DcBlockSeg g = B.plan.segment(i);
+        bool host_packed = false;
+        rc = devcoder_block_segment(c, &B, g, i & 1, &host_packed);
+        if (rc < 0 || !fits) continue;
+        const u8* dps = reinterpret_cast<const u8*>(devcoder_pstream_ptr(c, i & 1));
+        if (host_packed) {
+            void_entries.resize((size_t)g.expect);
+            HIP_TRY(c, hipMemcpyAsync(void_entries.data(), dps, (size_t)g.expect * 2, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, ctx_sync(c));
+            if (!B.plan.pack_void(g, void_entries.data(), reinterpret_cast<u8*>(out))) return ctx_fail(c, BSC_GPU_ERROR, "device coder: packing a void segment", hipSuccess);
+        } else
+            for (int k = 0; k < g.s1 - g.s0; ++k)
+                if (g.len[k]) HIP_TRY(c, hipMemcpyAsync(reinterpret_cast<u8*>(out) + g.dst[k], dps + g.src[k], (size_t)g.len[k], hipMemcpyDeviceToHost, c->stream));
+    }
+    if (rc == BSC_NOT_SUPPORTED) {
+        char buf[96]; snprintf(buf, sizeof buf, "device coder declined the block (reason mask %d)", c->dc_note.fail);
+        c->err = buf;
+    }
+    HIP_TRY(c, ctx_sync(c));                                           // (no copy into the caller's buffer outlives the call)
+    prof_collect(c);
+    if (rc < 0) return rc;
+    *nblocks_out = nb;
+    for (int b = 0; b <= nb; ++b) { poff_out[b] = B.plan.poff_of(b); if (want_packed) pbase_out[b] = B.plan.pbase_of(b); }
+    return B.plan.decisions();
+}
 static int64_t qlfc_static_pstream_stage(bscgpu_ctx* c, const uint8_t* L, int n, uint16_t* out, int64_t cap, int* nblocks_out,
                                          int* sub_start /*[8]*/, int* sub_size /*[8]*/, int64_t* poff_out /*[9]*/, uint16_t* dbg_out /*[3][cap] or NULL*/,
                                          bool want_packed, int64_t* pbase_out /*[9], packed only*/)
@@ -2893,6 +3118,8 @@ static int64_t qlfc_static_pstream_stage(bscgpu_ctx* c, const uint8_t* L, int n,
         for (int s = 0; s < 256; ++s) nsym += first_run[b * 256 + s] != 0xffffffffu;
         max_rank[b] = bsr((uint32_t)(nsym - 1));
     }
+    if (c->dc_arena_div > 1)
+        return qlfc_static_pstream_segments(c, n, nb, sub_start, sub_size, m, run_first, max_rank, out, cap, nblocks_out, poff_out, dbg_out != nullptr, want_packed, pbase_out);
     u16* ddbg = nullptr;
     if (dbg_out) { rc = devcoder_ensure(c); if (rc < 0) return rc; if (hipMalloc((void**)&ddbg, (size_t)c->dc->Dcap * 6) != hipSuccess) return BSC_GPU_NOT_ENOUGH_MEMORY; }
     u32 D = 0, poff[9];
@@ -2936,4 +3163,35 @@ extern "C" int64_t bscgpu_qlfc_static_pstream_packed(bscgpu_ctx* c, const uint8_
 {
     if (!pbase_out) return BSC_BAD_PARAMETER;
     return qlfc_static_pstream_stage(c, L, n, reinterpret_cast<uint16_t*>(out), cap_bytes, nblocks_out, sub_start, sub_size, poff_out, nullptr, true, pbase_out);
+}
+
+// The facts of a block alone (include/bscgpu.h): the front end as above, then the flags, every sub-block's runs, its decisions for the
+// coder at hand and the flags left open.
+extern "C" int bscgpu_qlfc_pstream_facts(bscgpu_ctx* c, const uint8_t* L, int n, int coder, int* nblocks_out, int* sub_start /*[8]*/, int* sub_size /*[8]*/,
+                                         uint32_t* sub_runs /*[8]*/, uint32_t* sub_dec /*[8]*/, uint32_t* sub_und /*[8]*/)
+{
+    if (!c || !L || n <= 0 || (coder != 1 && coder != 3) || !nblocks_out || !sub_start || !sub_size || !sub_runs || !sub_dec || !sub_und) return BSC_BAD_PARAMETER;
+    if (n > c->max_n) return BSC_GPU_NOT_ENOUGH_MEMORY;
+    if (hipSetDevice(c->device) != hipSuccess) return BSC_GPU_ERROR;
+    HIP_TRY(c, hipMemcpyAsync(c->dL, L, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    const int nb = bschost::coder_num_blocks(n);
+    int rc = qlfc_front_split(c, c->dL, (u32)n, nb, sub_start, sub_size);
+    if (rc < 0) return rc;
+    u32 m = 0, run_first[9];
+    static thread_local u32 first_run[8 * 256];
+    rc = qlfc_front_runs(c, c->dL, (u32)n, nb, sub_start, &m, run_first, first_run, c->slots[0]);
+    if (rc < 0) return rc;
+    int max_rank[8];
+    for (int b = 0; b < nb; ++b) {
+        int nsym = 0;
+        for (int s = 0; s < 256; ++s) nsym += first_run[b * 256 + s] != 0xffffffffu;
+        max_rank[b] = bsr((uint32_t)(nsym - 1));
+    }
+    DcBlock B;
+    rc = devcoder_block_facts(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, m, (u32)n, nb, sub_start, sub_size, run_first,
+                              max_rank, coder, &B);
+    if (rc < 0) return rc;
+    *nblocks_out = nb;
+    for (int b = 0; b < nb; ++b) { sub_runs[b] = run_first[b + 1] - run_first[b]; sub_dec[b] = B.dec[b]; sub_und[b] = B.und[b]; }
+    return BSC_NO_ERROR;
 }

@@ -349,7 +349,8 @@ struct BlockJob {
     hipEvent_t ps_part[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // ... up to and including sub-block b: what a coder task waits on
     bool ps_dma = false; uint64_t ps_sig[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the pieces went through the DMA engine directly (dma_copy.h): signals instead of events
     bool rc_done = false;            // BSCGPU_OPT_DEVICE_RC: the GPU stage has range-coded the sub-blocks as well (scratch / sub_res are final, nothing crossed PCIe but them)
-    bool ps_landed(int b) const { return ps_dma ? dma_wait(ps_sig[b]) == 0 : hipEventSynchronize(ps_part[b]) == hipSuccess; }
+    // (a signal of 0: the piece was put into the landing zone by the host itself — a void segment of a block in sub-block segments)
+    bool ps_landed(int b) const { return ps_dma ? ps_sig[b] == 0 || dma_wait(ps_sig[b]) == 0 : hipEventSynchronize(ps_part[b]) == hipSuccess; }
     std::atomic<bool> redo{false};   // a sub-block did not compress: the block goes through the host model again (raw sub-blocks need the run arrays)
     bool stored_small = false;       // n <= header size: finished in the GPU stage
     int  result = 0;
@@ -435,6 +436,92 @@ static int device_rc_block(BlockJob& J, int psbuf)
     return LIBBSC_NO_ERROR;
 }
 
+// The device model of a block on a context whose arena is divided (BSCGPU_OPT_DC_ARENA_DIV > 1; DESIGN §3.6, "A block in sub-block
+// segments"): facts, plan, then the segments in order, segment i into the device stream buffer ps_toggle names behind that buffer's
+// guard, its sub-blocks' pieces on their way to the block's one landing zone — at the offsets the plan gives, a signal or an event per
+// sub-block as for a whole block — while the next segment's kernels run.  Returns what devcoder_pstream returns; J.poff / J.pbase /
+// J.ps_packed / *ndec are the block's.  *sent = false: the plan is one segment, which lies in ps[ps_toggle] as devcoder_pstream leaves a
+// block (a void packed form: 16-bit entries), and the caller goes on as ever.  *sent = true: several segments, all pieces issued.
+// A segment that declines declines the block (what is in flight lands first); one whose packed form is void comes down as 16-bit
+// entries and is packed into place by the host (dc_pack13_host) — the block stays in one form.
+static int devcoder_block_in_segments(BlockJob& J, u32 m, const int* maxr, u32* ndec, bool* sent)
+{
+    bscgpu_ctx* c = J.c;
+    const int nb = J.nblocks;
+    *sent = false;
+    DcBlock B;
+    int rc = devcoder_block_begin(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, m, (u32)J.n, nb, J.start, J.size,
+                                  J.run_first, maxr, J.coder, true, &B);
+    if (rc < 0) return rc;
+    const DcBlockSchedule& plan = B.plan;
+    *ndec = (u32)plan.decisions();
+    for (int b = 0; b <= nb; ++b) { J.poff[b] = (u32)plan.poff_of(b); J.pbase[b] = (u32)plan.pbase_of(b); }
+    if (plan.segments() == 1) {
+        bool host_packed = false;
+        rc = devcoder_block_segment(c, &B, plan.segment(0), c->ps_toggle, &host_packed);
+        J.ps_packed = B.packed && !host_packed;
+        return rc;
+    }
+    J.ps_packed = B.packed;
+    const size_t zone_entries = ((size_t)plan.zone_bytes() + 1u) / 2u + 64;
+    if (ctx_ensure_pstream_slot(c, *J.slot, zone_entries) != LIBBSC_NO_ERROR) return LIBBSC_NOT_SUPPORTED;    // (as an arena that does not fit)
+    bool dma = dma_available() && J.slot->hps_dev != nullptr;
+    for (int b = 0; b < 8 && dma; ++b) dma = J.slot->part_sig[b] != 0;
+    J.ps_dma = dma;
+    uint8_t* const zone = reinterpret_cast<uint8_t*>(J.slot->hps);
+    std::vector<uint16_t> void_entries;
+    int issued = 0;                                                  // sub-blocks whose piece is in flight or has landed
+    // everything queued so far has landed (before the host writes a piece itself, and before the block is given up)
+    auto settle = [&]() {
+        if (!dma) return hipStreamSynchronize(c->copy_stream) == hipSuccess;
+        bool ok = true;
+        for (int b = 0; b < issued; ++b) ok = (J.ps_sig[b] == 0 || dma_wait(J.ps_sig[b]) == 0) && ok;
+        return ok;
+    };
+    for (int i = 0; i < plan.segments(); ++i) {
+        const int pb = c->ps_toggle;
+        const DcBlockSeg g = plan.segment(i);
+        bool host_packed = false;
+        rc = devcoder_block_segment(c, &B, g, pb, &host_packed);
+        if (rc < 0) { (void)settle(); return rc; }
+        // the stream has been synchronised behind the segment's last kernel
+        const uint8_t* dps = reinterpret_cast<const uint8_t*>(devcoder_pstream_ptr(c, pb));
+        c->ps_guard[pb] = nullptr;
+        for (int b = 0; b < 8; ++b) c->ps_guard_sig[pb][b] = 0;
+        if (host_packed) {
+            void_entries.resize((size_t)g.expect);
+            if (hipMemcpyAsync(void_entries.data(), dps, (size_t)g.expect * 2, hipMemcpyDeviceToHost, c->stream) != hipSuccess || ctx_sync(c) != hipSuccess || !settle())
+                return LIBBSC_GPU_ERROR;
+            if (!plan.pack_void(g, void_entries.data(), zone)) return LIBBSC_GPU_ERROR;
+        }
+        for (int s = g.s0; s < g.s1; ++s, ++issued) {
+            const int k = s - g.s0;
+            const size_t src = (size_t)g.src[k], dst = (size_t)g.dst[k], len = (size_t)g.len[k];
+            if (dma) {
+                J.ps_sig[s] = 0;
+                if (host_packed || len == 0) continue;
+                if (dma_d2h((uint8_t*)J.slot->hps_dev + dst, dps + src, len, J.slot->part_sig[s]) == 0) {
+                    J.ps_sig[s] = c->ps_guard_sig[pb][s] = J.slot->part_sig[s];
+                } else if (!settle() || hipMemcpyAsync(zone + dst, dps + src, len, hipMemcpyDeviceToHost, c->stream) != hipSuccess || ctx_sync(c) != hipSuccess)
+                    return LIBBSC_GPU_ERROR;                         // (the engine took no more: this piece through HIP, waited for)
+            } else {
+                if ((!host_packed && len > 0 && hipMemcpyAsync(zone + dst, dps + src, len, hipMemcpyDeviceToHost, c->copy_stream) != hipSuccess) ||
+                    hipEventRecord(J.slot->part_ev[s], c->copy_stream) != hipSuccess) return LIBBSC_GPU_ERROR;
+                J.ps_part[s] = J.slot->part_ev[s];
+                c->ps_guard[pb] = J.slot->part_ev[s];                // (the segment's last piece: behind it the buffer is free)
+            }
+        }
+        c->ps_toggle = pb ^ 1;
+    }
+    J.ps_ready = nullptr;
+    if (!dma) {
+        if (hipEventRecord(J.slot->copy_ev, c->copy_stream) != hipSuccess) return LIBBSC_GPU_ERROR;
+        J.ps_ready = J.slot->copy_ev;
+    }
+    *sent = true;
+    return LIBBSC_NO_ERROR;
+}
+
 static int gpu_stage(BlockJob& J, int blockSorter, bool allow_devcoder = true)
 {
     CtxTimer tm_stage("gpu_stage of one block");
@@ -503,12 +590,20 @@ static int gpu_stage(BlockJob& J, int blockSorter, bool allow_devcoder = true)
             u32 ndec = 0;
             const int pb = c->ps_toggle;
             int packed = 0;
-            const int r2 = devcoder_pstream(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, m, (u32)n, J.nblocks,
+            bool sent = false;                                       // a block in several sub-block segments: its pieces are on their way already
+            const int r2 = c->dc_arena_div > 1 ? devcoder_block_in_segments(J, m, maxr, &ndec, &sent)
+                         : devcoder_pstream(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, m, (u32)n, J.nblocks,
                                             J.run_first, maxr, &ndec, J.poff, nullptr, pb, J.coder, &packed);
             // byte range of every sub-block's piece in the device buffer = in the landing zone (the same layout on both sides)
             size_t piece_lo[8], piece_hi[8], zone_entries = (size_t)ndec + 64;
-            J.ps_packed = packed != 0;
-            if (r2 == LIBBSC_NO_ERROR) {
+            if (c->dc_arena_div == 1) J.ps_packed = packed != 0;
+            const bool whole = r2 == LIBBSC_NO_ERROR && !sent;      // the block's stream lies in ps[pb]
+            if (r2 == LIBBSC_NO_ERROR && sent) {
+                J.use_ps = true; J.ps = J.slot->hps; J.ndec = ndec; ok = true;
+                g_count_devmodel.fetch_add(1, std::memory_order_relaxed);
+                if (J.lz) g_count_devmodel_lzp.fetch_add(1, std::memory_order_relaxed);
+            }
+            if (whole) {
                 u32 pb13 = 0;
                 for (int b = 0; b < J.nblocks; ++b) {
                     const u32 cnt = J.poff[b + 1] - J.poff[b];
@@ -519,7 +614,7 @@ static int gpu_stage(BlockJob& J, int blockSorter, bool allow_devcoder = true)
                 J.pbase[J.nblocks] = pb13;
                 if (J.ps_packed) zone_entries = ((size_t)pb13 / 8u * 13u + 1u) / 2u + 64;
             }
-            if (r2 == LIBBSC_NO_ERROR && c->device_rc) {
+            if (whole && c->device_rc) {
                 // the range coder runs here as well: the stream stays in HBM (its buffer is free again when this returns: no guard, no toggle)
                 rc = device_rc_block(J, pb);
                 if (rc < 0) return rc;
@@ -529,7 +624,7 @@ static int gpu_stage(BlockJob& J, int blockSorter, bool allow_devcoder = true)
                 if (J.lz) g_count_devmodel_lzp.fetch_add(1, std::memory_order_relaxed);
             } else
             // (a pinned landing zone that cannot be had is a reason to take the host model, like an arena that does not fit)
-            if (r2 == LIBBSC_NO_ERROR && ctx_ensure_pstream_slot(c, *J.slot, zone_entries) == LIBBSC_NO_ERROR) {
+            if (whole && ctx_ensure_pstream_slot(c, *J.slot, zone_entries) == LIBBSC_NO_ERROR) {
                 // the stream has been synchronised behind the last kernel; the copy goes to the copy stream and is NOT waited for
                 // here: the next block's sort overlaps it, the coder tasks wait on the event
                 // (sub-block by sub-block, an event behind each piece: the task that codes sub-blocks b.. starts when ITS entries have landed —
@@ -1836,6 +1931,12 @@ extern "C" BSCGPU_API int64_t bscgpu_static_pstream_batch_packed_device(bscgpu_c
     if (ctx_sync(c) != hipSuccess) return LIBBSC_GPU_ERROR;
     for (int s = 0; s <= out->nsub; ++s) pbase[s] = (int64_t)pb[s];
     return (int64_t)D;
+}
+
+// ---- a single block in sub-block segments: the plan as a pure function (include/bscgpu.h) ------------------------------------------
+extern "C" BSCGPU_API int bscgpu_block_segment_plan(const uint32_t* sub_runs, const uint32_t* sub_dec, int nsub, int64_t mcap, int64_t dcap, int* seg_of)
+{
+    return dc_block_segment_plan(sub_runs, sub_dec, nsub, mcap, dcap, seg_of);
 }
 
 // ---- a pass's model in segments (include/bscgpu.h) ---------------------------------------------------------------------------------

@@ -56,6 +56,14 @@ class GpuContext:
     def arena_bytes(self):
         return int(self.L.bscgpu_arena_bytes(self.h))
 
+    @property
+    def model_arena_bytes(self):
+        """bscgpu_model_arena_bytes: the device model's own arena (0 before the first block or pass that takes the device model)"""
+        f = self.L.bscgpu_model_arena_bytes
+        f.restype = C.c_int64
+        f.argtypes = [C.c_void_p]
+        return int(f(self.h))
+
     # ---- host-pointer entry points (shape of the reference hooks) -----------------------------
     def bwt(self, data, aux_rate=None):
         """-> (L np.uint8[n], primary index, I list or None).  libcubwt_bwt / libcubwt_bwt_aux."""
@@ -169,6 +177,19 @@ class GpuContext:
             w = out[byte].astype(np.uint32) | (out[byte + 1].astype(np.uint32) << 8) | (out[byte + 2].astype(np.uint32) << 16)
             fields[po[b]:po[b + 1]] = ((w >> (bit & 7).astype(np.uint32)) & 0x1fff).astype(np.uint16)
         return fields, list(st[:k]), list(sz[:k]), po, pb, out[:nbytes]
+
+    def qlfc_pstream_facts(self, L, coder=1):
+        """bscgpu_qlfc_pstream_facts: what the plan of a block in sub-block segments is made of -> (sub_start, sub_size, sub_runs,
+        sub_dec: decisions of every sub-block for `coder` (1: -e1, 3: -e0), sub_und: its avg_rank flags left open), lists of nb"""
+        a = np.ascontiguousarray(L, dtype=np.uint8)
+        nb = C.c_int(0); st = (C.c_int * 8)(); sz = (C.c_int * 8)()
+        runs, dec, und = (C.c_uint32 * 8)(), (C.c_uint32 * 8)(), (C.c_uint32 * 8)()
+        f = self.L.bscgpu_qlfc_pstream_facts
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(f(self.h, N.np_ptr(a), a.size, int(coder), C.byref(nb), st, sz, runs, dec, und))
+        k = nb.value
+        return list(st[:k]), list(sz[:k]), list(runs[:k]), list(dec[:k]), list(und[:k])
 
     # ---- the range coder as a stage: many probability streams in one launch (include/bscgpu.h, DESIGN §3.8) ----
     def rc_encode(self, form, body, prefix, streams, streams_per_wave=64, out=None):
@@ -395,6 +416,8 @@ class GpuContext:
     OPT_DC_REPLAY_EXACT, CNT_DC_REPLAY_RESOLVED = 32, 33    # open chunk starts of the evaluation resolved exactly; chunks that settled (get only)
     OPT_DC_AVG_EXACT, CNT_DC_AVG_RESOLVED = 30, 31      # open avg_rank flags resolved exactly on the device; what that settled (get only)
     OPT_DC_HIST_EXACT, CNT_DC_HIST_RESOLVED = 34, 35    # open run_hist brackets resolved exactly on the device; runs that settled (get only)
+    # the device model's arena carved for max_n / k (1, 2, 4, 8; a block above it runs in sub-block segments); segments of the last block (get only)
+    OPT_DC_ARENA_DIV, CNT_DC_BLOCK_SEGMENTS = 36, 37
     DC_FAIL_AVG, DC_FAIL_HIST, DC_FAIL_CAP, DC_FAIL_REPLAY = 2, 4, 8, 16                         # BSCGPU_DC_FAIL_*
 
     def option_set(self, key, value):
@@ -619,6 +642,22 @@ def model_segment_plan(sub_dec, sub_und, blk_sub, dcap, target=0):
     if n < 0:
         raise GpuError(n, "bscgpu_model_segment_plan")
     return n, [int(x) for x in seg_of[:count]]
+
+
+def block_segment_plan(sub_runs, sub_dec, mcap, dcap):
+    """bscgpu_block_segment_plan: where a single block is cut for an arena of mcap runs and dcap decisions -> (segments, segment of
+    every sub-block); raises GpuError -4 when a sub-block alone exceeds a capacity, -1 for bad arguments"""
+    runs = np.ascontiguousarray(np.asarray(sub_runs, dtype=np.uint32))
+    dec = np.ascontiguousarray(np.asarray(sub_dec, dtype=np.uint32))
+    assert runs.size == dec.size
+    seg_of = np.full(8, -2, np.int32)
+    f = N.lib().bscgpu_block_segment_plan
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p]
+    n = int(f(N.np_ptr(runs) if runs.size else None, N.np_ptr(dec) if dec.size else None, runs.size, int(mcap), int(dcap), N.np_ptr(seg_of)))
+    if n < 0:
+        raise GpuError(n, "bscgpu_block_segment_plan")
+    return n, [int(x) for x in seg_of[:runs.size]]
 
 
 def unbwt_batch_plan(sizes, cap=64 << 20):

@@ -119,7 +119,7 @@ int main(int argc, char** argv)
     std::vector<QlfcRuns> R((size_t)nb);
     int max_rank[8]; uint32_t first[9]; first[0] = 0;
     std::unique_ptr<Counters1> K(new_counters());
-    uint64_t D = 0;
+    uint64_t D = 0, sub_dec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     bool may_escape = false;
     for (int sb = 0; sb < nb; ++sb) {
         qlfc_runs(L.data() + start[sb], size[sb], R[sb]);
@@ -127,7 +127,7 @@ int main(int argc, char** argv)
         may_escape |= max_rank[sb] > 4;
         first[sb + 1] = first[sb] + R[sb].view.count;
         CountPolicy cp; walk_model1<false>(R[sb].view, T, max_rank[sb], *K, nullptr, cp);
-        D += cp.decisions;
+        D += cp.decisions; sub_dec[sb] = cp.decisions;
     }
     const uint32_t m = first[nb];
     const uint32_t EV = dcm::eval_chunk_events(3 * D);           // jobs: static + char + (state: rank side + run side)
@@ -212,6 +212,7 @@ int main(int argc, char** argv)
     printf(" \"constants\": {\"DC_EV\": %d, \"DC_REPLAY_MAX\": %d, \"DC_AVG_CH\": %d, \"DC_AVG_WARM\": %d, \"DC_HIST_NP\": %d, \"DC_HIST_KMAX\": %d},\n",
            dcm::DC_EV, dcm::DC_REPLAY_MAX, dcm::DC_AVG_CH, dcm::DC_AVG_WARM, dcm::DC_HIST_NP, dcm::DC_HIST_KMAX);
     printf(" \"sub_runs\": ["); for (int sb = 0; sb < nb; ++sb) printf("%s%u", sb ? ", " : "", first[sb + 1] - first[sb]); printf("],\n");
+    printf(" \"sub_decisions\": ["); for (int sb = 0; sb < nb; ++sb) printf("%s%llu", sb ? ", " : "", (unsigned long long)sub_dec[sb]); printf("],\n");
     printf(" \"max_rank\": ["); for (int sb = 0; sb < nb; ++sb) printf("%s%d", sb ? ", " : "", max_rank[sb]); printf("],\n");
     printf(" \"avg_launched\": %s, \"avg_und\": %llu, \"avg_und_sb\": [", may_escape ? "true" : "false", (unsigned long long)avg_und);
     for (int sb = 0; sb < nb; ++sb) printf("%s%llu", sb ? ", " : "", (unsigned long long)avg_und_sb[sb]); printf("],\n");
