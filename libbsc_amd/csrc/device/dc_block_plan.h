@@ -1,8 +1,11 @@
-// dc_block_plan.h — a single block modelled in segments of whole sub-blocks (devcoder.hip: devcoder_block_begin / _segment; DESIGN
-// §3.6, "A block in sub-block segments"), as plain host arithmetic without any HIP in it: where the block is cut so that every
-// segment fits the arena's capacity in runs and in decisions, the eight-entry run table of a segment rebased to its first run, and
-// where the pieces of a segment's stream lie in the device buffer and land in the block's one landing zone.  The driver launches by
-// DcBlockSchedule; tools/block_plan_probe.cpp reads the same from stdin, for tests/test_block_segment_plan_host.py.
+// dc_block_plan.h — the device model of a single block as plain host arithmetic without any HIP in it.  A block modelled in segments of
+// whole sub-blocks (devcoder.hip: devcoder_block_begin / _segment; DESIGN §3.6, "A block in sub-block segments"): where the block is cut
+// so that every segment fits the arena's capacity in runs and in decisions, the eight-entry run table of a segment rebased to its first
+// run.  Where a sub-block's piece of the probability stream lies in the device buffer and lands in the block's one landing zone — of a
+// block in segments and of one modelled in one go (DcBlockSchedule::whole) alike: block.cpp's sender copies by it and fills the job's
+// poff / pbase from it, the stage functions of devcoder.hip lay their output out by it.  max_rank of a sub-block from its symbol count,
+// and what the driver of one block (block.cpp: gpu_stage) decides.  tools/block_plan_probe.cpp reads the same from stdin, for
+// tests/test_block_segment_plan_host.py.
 #pragma once
 #include <stdint.h>
 #include "dc_segment_plan.h"                                            // the packed layout: dc_pack13_fields / dc_pack13_bytes
@@ -63,6 +66,14 @@ public:
         }
         first[nsub] = run_first[nsub];
     }
+    // A block that was modelled in one go, from the poff[0..nsub] the model returned: one segment with src == dst, capacities no question
+    // (its run fields are zero: nothing launches by it).
+    static DcBlockSchedule whole(const uint32_t* poff, int nsub, bool packed)
+    {
+        uint32_t no_runs[DC_BLOCK_MAX_SUB + 1] = {}, dec[DC_BLOCK_MAX_SUB] = {};
+        for (int s = 0; poff && s < nsub && s < DC_BLOCK_MAX_SUB; ++s) dec[s] = poff[s + 1] - poff[s];
+        return DcBlockSchedule(poff ? no_runs : nullptr, dec, nsub, INT64_MAX, INT64_MAX, packed);
+    }
 
     // the number of segments, or why there is no plan (DC_BLOCK_NOT_SUPPORTED, DC_BLOCK_BAD_PARAMETER)
     int segments() const { return nseg; }
@@ -115,3 +126,47 @@ private:
     uint32_t first[DC_BLOCK_MAX_SUB + 1] = {}, sub_dec[DC_BLOCK_MAX_SUB] = {};
     int64_t poff[DC_BLOCK_MAX_SUB + 1] = {}, pbase[DC_BLOCK_MAX_SUB + 1] = {};
 };
+
+// ---- max_rank ------------------------------------------------------------------------------------------------------------------------
+// ... of a sub-block with nsym symbols: bsr(nsym - 1), 0 for nsym <= 2 (qlfc.cpp:888, encode_alphabet)
+static inline int dc_max_rank(int nsym)
+{
+    int k = 0;
+    for (int v = nsym - 1; v > 1; v >>= 1) ++k;
+    return k;
+}
+// ... of sub-blocks 0 .. nb - 1 from the front end's table: first_run[256 b + c] = the first run of symbol c in sub-block b, 0xffffffff: none
+static inline void dc_max_rank_table(const uint32_t* first_run, int nb, int* max_rank)
+{
+    for (int b = 0; b < nb; ++b) {
+        int nsym = 0;
+        for (int c = 0; c < 256; ++c) nsym += first_run[b * 256 + c] != 0xffffffffu;
+        max_rank[b] = dc_max_rank(nsym);
+    }
+}
+
+// ---- what the driver of one block decides ------------------------------------------------------------------------------------------
+// Plain functions of integers and flags; the driver (block.cpp: gpu_stage) reads the environment and the context and asks.
+// Whether the block tries the device model: the caller allows it (a redo does not), BSC_DEVICE_CODER, the static coder or the fast one
+// with BSC_DEVICE_CODER_FAST, several sub-blocks, and at least BSC_DEVICE_CODER_MIN_N bytes.
+static inline bool dc_block_tries_model(bool allowed, bool enabled, bool coder_static, bool coder_fast_enabled, int nsub, int64_t n, int64_t min_n)
+{
+    return allowed && enabled && (coder_static || coder_fast_enabled) && nsub > 1 && n >= min_n;
+}
+// Whether its m runs are too dense to bother: nearly one run per byte, the sub-blocks will be stored raw anyway
+static inline bool dc_block_runs_too_dense(uint32_t m, int n) { return !((double)m <= 0.70 * (double)n); }
+// What becomes of the block after the model returned code (a libbsc code).  sent: a block in several segments has issued its pieces;
+// else NO_ERROR says that the whole stream lies in the device buffer — device_rc: the context codes it there (BSCGPU_OPT_DEVICE_RC);
+// zone: the pinned landing zone could be had (not asked where device_rc is on).
+enum DcBlockVerdict {
+    DC_BLOCK_SENT,              // the pieces are on their way to the landing zone: the host codes from the stream
+    DC_BLOCK_DEVICE_RC,         // range-coded on the device
+    DC_BLOCK_LANDED,            // the whole stream goes down to the landing zone: the host codes from it
+    DC_BLOCK_HOST_MODEL,        // declined, or no landing zone: the run arrays go down and the host models
+    DC_BLOCK_ERROR              // code is the call's result
+};
+static inline DcBlockVerdict dc_block_verdict(int code, bool sent, bool device_rc, bool zone)
+{
+    if (code == 0 /* LIBBSC_NO_ERROR */) return sent ? DC_BLOCK_SENT : device_rc ? DC_BLOCK_DEVICE_RC : zone ? DC_BLOCK_LANDED : DC_BLOCK_HOST_MODEL;
+    return code == DC_BLOCK_NOT_SUPPORTED ? DC_BLOCK_HOST_MODEL : DC_BLOCK_ERROR;
+}

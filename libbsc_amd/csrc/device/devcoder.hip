@@ -3097,34 +3097,40 @@ static int64_t qlfc_static_pstream_segments(bscgpu_ctx* c, int n, int nb, const 
     for (int b = 0; b <= nb; ++b) { poff_out[b] = B.plan.poff_of(b); if (want_packed) pbase_out[b] = B.plan.pbase_of(b); }
     return B.plan.decisions();
 }
+// What the stage functions below start with: the arguments they share checked, the block up into dL, its sub-block split and runs
+// (qlfc_front.hip; the run arrays stay in HBM) and every sub-block's max_rank.
+struct StageFront { int nb = 0; u32 m = 0, run_first[9] = {}; int max_rank[8] = {}; };
+static int qlfc_stage_front(bscgpu_ctx* c, const uint8_t* L, int n, int* nblocks_out, int* sub_start /*[8]*/, int* sub_size /*[8]*/, StageFront* F)
+{
+    if (!c || !L || n <= 0 || !nblocks_out || !sub_start || !sub_size) return BSC_BAD_PARAMETER;
+    if (n > c->max_n) return BSC_GPU_NOT_ENOUGH_MEMORY;
+    if (hipSetDevice(c->device) != hipSuccess) return BSC_GPU_ERROR;
+    HIP_TRY(c, hipMemcpyAsync(c->dL, L, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    F->nb = bschost::coder_num_blocks(n);
+    int rc = qlfc_front_split(c, c->dL, (u32)n, F->nb, sub_start, sub_size);
+    if (rc < 0) return rc;
+    static thread_local u32 first_run[8 * 256];
+    rc = qlfc_front_runs(c, c->dL, (u32)n, F->nb, sub_start, &F->m, F->run_first, first_run, c->slots[0]);
+    if (rc < 0) return rc;
+    dc_max_rank_table(first_run, F->nb, F->max_rank);
+    return BSC_NO_ERROR;
+}
 static int64_t qlfc_static_pstream_stage(bscgpu_ctx* c, const uint8_t* L, int n, uint16_t* out, int64_t cap, int* nblocks_out,
                                          int* sub_start /*[8]*/, int* sub_size /*[8]*/, int64_t* poff_out /*[9]*/, uint16_t* dbg_out /*[3][cap] or NULL*/,
                                          bool want_packed, int64_t* pbase_out /*[9], packed only*/)
 {
-    if (!c || !L || !out || n <= 0 || !nblocks_out || !sub_start || !sub_size || !poff_out) return BSC_BAD_PARAMETER;
-    if (n > c->max_n) return BSC_GPU_NOT_ENOUGH_MEMORY;
-    if (hipSetDevice(c->device) != hipSuccess) return BSC_GPU_ERROR;
-    HIP_TRY(c, hipMemcpyAsync(c->dL, L, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    const int nb = bschost::coder_num_blocks(n);
-    int rc = qlfc_front_split(c, c->dL, (u32)n, nb, sub_start, sub_size);
+    if (!out || !poff_out) return BSC_BAD_PARAMETER;
+    StageFront F;
+    int rc = qlfc_stage_front(c, L, n, nblocks_out, sub_start, sub_size, &F);
     if (rc < 0) return rc;
-    u32 m = 0, run_first[9];
-    static thread_local u32 first_run[8 * 256];
-    rc = qlfc_front_runs(c, c->dL, (u32)n, nb, sub_start, &m, run_first, first_run, c->slots[0]);
-    if (rc < 0) return rc;
-    int max_rank[8];
-    for (int b = 0; b < nb; ++b) {
-        int nsym = 0;
-        for (int s = 0; s < 256; ++s) nsym += first_run[b * 256 + s] != 0xffffffffu;
-        max_rank[b] = bsr((uint32_t)(nsym - 1));
-    }
+    const int nb = F.nb;
     if (c->dc_arena_div > 1)
-        return qlfc_static_pstream_segments(c, n, nb, sub_start, sub_size, m, run_first, max_rank, out, cap, nblocks_out, poff_out, dbg_out != nullptr, want_packed, pbase_out);
+        return qlfc_static_pstream_segments(c, n, nb, sub_start, sub_size, F.m, F.run_first, F.max_rank, out, cap, nblocks_out, poff_out, dbg_out != nullptr, want_packed, pbase_out);
     u16* ddbg = nullptr;
     if (dbg_out) { rc = devcoder_ensure(c); if (rc < 0) return rc; if (hipMalloc((void**)&ddbg, (size_t)c->dc->Dcap * 6) != hipSuccess) return BSC_GPU_NOT_ENOUGH_MEMORY; }
     u32 D = 0, poff[9];
     int packed = 0;
-    rc = devcoder_pstream(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, m, (u32)n, nb, run_first, max_rank, &D, poff, ddbg, 0, 1,
+    rc = devcoder_pstream(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, F.m, (u32)n, nb, F.run_first, F.max_rank, &D, poff, ddbg, 0, 1,
                           want_packed ? &packed : nullptr);
     if (rc == BSC_NO_ERROR && want_packed && !packed) { c->err = "the packed stream was not produced (option off, or a wavefront's piece beyond the staging buffer)"; rc = BSC_NOT_SUPPORTED; }
     else if (rc == BSC_NOT_SUPPORTED) {
@@ -3133,13 +3139,10 @@ static int64_t qlfc_static_pstream_stage(bscgpu_ctx* c, const uint8_t* L, int n,
     }
     if (rc < 0) { if (ddbg) hipFree(ddbg); return rc; }
     *nblocks_out = nb;
-    for (int b = 0; b <= nb; ++b) poff_out[b] = poff[b];
+    const DcBlockSchedule lay = DcBlockSchedule::whole(poff, nb, want_packed);
+    for (int b = 0; b <= nb; ++b) { poff_out[b] = lay.poff_of(b); if (want_packed) pbase_out[b] = lay.pbase_of(b); }
     if (want_packed) {
-        int64_t pb = 0;
-        for (int b = 0; b < nb; ++b) { pbase_out[b] = pb; pb += ((int64_t)(poff[b + 1] - poff[b]) + 63) / 64 * 64; }
-        pbase_out[nb] = pb;
-        const int64_t bytes = pb / 8 * 13;
-        if (bytes <= cap) { HIP_TRY(c, hipMemcpyAsync(out, devcoder_pstream_ptr(c), (size_t)bytes, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(c, ctx_sync(c)); }
+        if (lay.zone_bytes() <= cap) { HIP_TRY(c, hipMemcpyAsync(out, devcoder_pstream_ptr(c), (size_t)lay.zone_bytes(), hipMemcpyDeviceToHost, c->stream)); HIP_TRY(c, ctx_sync(c)); }
     } else if ((int64_t)D <= cap) {
         HIP_TRY(c, hipMemcpyAsync(out, devcoder_pstream_ptr(c), (size_t)D * 2, hipMemcpyDeviceToHost, c->stream));
         if (dbg_out) for (int f = 0; f < 3; ++f) HIP_TRY(c, hipMemcpyAsync(dbg_out + (size_t)f * cap, ddbg + (size_t)f * D, (size_t)D * 2, hipMemcpyDeviceToHost, c->stream));
@@ -3170,28 +3173,15 @@ extern "C" int64_t bscgpu_qlfc_static_pstream_packed(bscgpu_ctx* c, const uint8_
 extern "C" int bscgpu_qlfc_pstream_facts(bscgpu_ctx* c, const uint8_t* L, int n, int coder, int* nblocks_out, int* sub_start /*[8]*/, int* sub_size /*[8]*/,
                                          uint32_t* sub_runs /*[8]*/, uint32_t* sub_dec /*[8]*/, uint32_t* sub_und /*[8]*/)
 {
-    if (!c || !L || n <= 0 || (coder != 1 && coder != 3) || !nblocks_out || !sub_start || !sub_size || !sub_runs || !sub_dec || !sub_und) return BSC_BAD_PARAMETER;
-    if (n > c->max_n) return BSC_GPU_NOT_ENOUGH_MEMORY;
-    if (hipSetDevice(c->device) != hipSuccess) return BSC_GPU_ERROR;
-    HIP_TRY(c, hipMemcpyAsync(c->dL, L, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    const int nb = bschost::coder_num_blocks(n);
-    int rc = qlfc_front_split(c, c->dL, (u32)n, nb, sub_start, sub_size);
+    if ((coder != 1 && coder != 3) || !sub_runs || !sub_dec || !sub_und) return BSC_BAD_PARAMETER;
+    StageFront F;
+    int rc = qlfc_stage_front(c, L, n, nblocks_out, sub_start, sub_size, &F);
     if (rc < 0) return rc;
-    u32 m = 0, run_first[9];
-    static thread_local u32 first_run[8 * 256];
-    rc = qlfc_front_runs(c, c->dL, (u32)n, nb, sub_start, &m, run_first, first_run, c->slots[0]);
-    if (rc < 0) return rc;
-    int max_rank[8];
-    for (int b = 0; b < nb; ++b) {
-        int nsym = 0;
-        for (int s = 0; s < 256; ++s) nsym += first_run[b * 256 + s] != 0xffffffffu;
-        max_rank[b] = bsr((uint32_t)(nsym - 1));
-    }
     DcBlock B;
-    rc = devcoder_block_facts(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, m, (u32)n, nb, sub_start, sub_size, run_first,
-                              max_rank, coder, &B);
+    rc = devcoder_block_facts(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, F.m, (u32)n, F.nb, sub_start, sub_size, F.run_first,
+                              F.max_rank, coder, &B);
     if (rc < 0) return rc;
-    *nblocks_out = nb;
-    for (int b = 0; b < nb; ++b) { sub_runs[b] = run_first[b + 1] - run_first[b]; sub_dec[b] = B.dec[b]; sub_und[b] = B.und[b]; }
+    *nblocks_out = F.nb;
+    for (int b = 0; b < F.nb; ++b) { sub_runs[b] = F.run_first[b + 1] - F.run_first[b]; sub_dec[b] = B.dec[b]; sub_und[b] = B.und[b]; }
     return BSC_NO_ERROR;
 }

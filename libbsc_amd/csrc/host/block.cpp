@@ -436,26 +436,94 @@ static int device_rc_block(BlockJob& J, int psbuf)
     return LIBBSC_NO_ERROR;
 }
 
+// ---- the stream of a device-model block on its way to the host ---------------------------------------------------------------------
+// Where sub-block b's piece lies is DcBlockSchedule's (dc_block_plan.h), for a block in segments and for one modelled in one go alike:
+// the job's poff / pbase are the schedule's -> the entries the landing zone must hold
+static size_t ps_layout(BlockJob& J, const DcBlockSchedule& plan)
+{
+    for (int b = 0; b <= J.nblocks; ++b) { J.poff[b] = (u32)plan.poff_of(b); J.pbase[b] = (u32)plan.pbase_of(b); }
+    return ((size_t)plan.zone_bytes() + 1u) / 2u + 64;
+}
+
+// The one sender of pieces from a device stream buffer (ps[pb], synchronised behind the last kernel that wrote it) to the slot's landing
+// zone, which exists (ctx_ensure_pstream_slot).  A piece is NOT waited for here: the next segment's kernels and the next block's sort
+// overlap it, the coder task of sub-blocks b.. waits for ITS pieces (J.ps_landed; 366 MB take 7-14 ms over PCIe).
+// Which engine moves them is decided once per block: hipMemcpyAsync is a DMA-engine copy on the system's HIP runtime but a 256-workgroup
+// copy KERNEL on the runtime a torch process carries (dma_copy.h), so the pieces go to the HSA runtime's DMA copy directly and complete
+// HSA signals; hipMemcpyAsync on the copy stream + an event per piece remain where that is not possible (or BSC_D2H_DMA=0).  Either way
+// the buffer's guard (c->ps_guard_sig / c->ps_guard: the next model run into it waits) is what its pieces complete: their signals, or
+// the event of the last piece issued from it.  finish() records the slot's copy_ev directly behind that event with nothing between
+// them, so for the block's last buffer a wait on either is the same wait.
+// The engine refusing a piece (its queue is full): that piece alone goes through HIP behind everything queued so far, is waited for and
+// counts as landed by the host (ps_sig 0), for a whole block as for a segment.  (Until this sender a whole block sent its whole stream
+// again through HIP instead: other copies, the same bytes.  No test reaches this exit without exhausting the engine's queue on purpose.)
+struct PsSender {
+    BlockJob& J; bscgpu_ctx* c; bool dma; int issued = 0;             // issued: sub-blocks whose piece is in flight or has landed
+    PsSender(BlockJob& job, bscgpu_ctx* ctx) : J(job), c(ctx), dma(dma_available() && job.slot->hps_dev != nullptr)
+    {
+        for (int b = 0; b < 8 && dma; ++b) dma = J.slot->part_sig[b] != 0;
+        J.ps_dma = dma; J.ps_ready = nullptr;
+    }
+    // buffer pb is about to send: its guards are the pieces issued from here on
+    void begin(int pb) { c->ps_guard[pb] = nullptr; for (int b = 0; b < 8; ++b) c->ps_guard_sig[pb][b] = 0; }
+    // sub-block s's piece: len bytes at src (device, in ps[pb]) to byte dst of the zone; len 0: nothing to copy (the host put it there)
+    int piece(int s, int pb, const uint8_t* src, size_t dst, size_t len)
+    {
+        uint8_t* const zone = reinterpret_cast<uint8_t*>(J.slot->hps);
+        issued = s + 1;
+        if (dma) {
+            J.ps_sig[s] = 0;
+            if (len == 0) return LIBBSC_NO_ERROR;
+            if (dma_d2h((uint8_t*)J.slot->hps_dev + dst, src, len, J.slot->part_sig[s]) == 0) { J.ps_sig[s] = c->ps_guard_sig[pb][s] = J.slot->part_sig[s]; return LIBBSC_NO_ERROR; }
+            return settle() && hipMemcpyAsync(zone + dst, src, len, hipMemcpyDeviceToHost, c->stream) == hipSuccess && ctx_sync(c) == hipSuccess ? LIBBSC_NO_ERROR : LIBBSC_GPU_ERROR;
+        }
+        if ((len > 0 && hipMemcpyAsync(zone + dst, src, len, hipMemcpyDeviceToHost, c->copy_stream) != hipSuccess) ||
+            hipEventRecord(J.slot->part_ev[s], c->copy_stream) != hipSuccess) return LIBBSC_GPU_ERROR;
+        J.ps_part[s] = c->ps_guard[pb] = J.slot->part_ev[s];
+        return LIBBSC_NO_ERROR;
+    }
+    // every piece of segment g, which lies in ps[pb]; host_put: the host has packed the segment into the zone itself
+    int segment(const DcBlockSeg& g, int pb, bool host_put = false)
+    {
+        const uint8_t* dps = reinterpret_cast<const uint8_t*>(devcoder_pstream_ptr(c, pb));
+        int rc = LIBBSC_NO_ERROR;
+        begin(pb);
+        for (int s = g.s0, k = 0; s < g.s1 && rc >= 0; ++s, ++k) rc = piece(s, pb, dps + g.src[k], (size_t)g.dst[k], host_put ? 0 : (size_t)g.len[k]);
+        return rc;
+    }
+    // everything issued so far has landed (before the host writes a piece itself, and before the block is given up)
+    bool settle()
+    {
+        bool ok = dma || hipStreamSynchronize(c->copy_stream) == hipSuccess;
+        for (int b = 0; dma && b < issued; ++b) ok = (J.ps_sig[b] == 0 || dma_wait(J.ps_sig[b]) == 0) && ok;
+        return ok;
+    }
+    // the block's last piece has been issued
+    int finish()
+    {
+        if (!dma && hipEventRecord(J.slot->copy_ev, c->copy_stream) != hipSuccess) return LIBBSC_GPU_ERROR;
+        if (!dma) J.ps_ready = J.slot->copy_ev;
+        return LIBBSC_NO_ERROR;
+    }
+};
+
 // The device model of a block on a context whose arena is divided (BSCGPU_OPT_DC_ARENA_DIV > 1; DESIGN §3.6, "A block in sub-block
 // segments"): facts, plan, then the segments in order, segment i into the device stream buffer ps_toggle names behind that buffer's
-// guard, its sub-blocks' pieces on their way to the block's one landing zone — at the offsets the plan gives, a signal or an event per
-// sub-block as for a whole block — while the next segment's kernels run.  Returns what devcoder_pstream returns; J.poff / J.pbase /
-// J.ps_packed / *ndec are the block's.  *sent = false: the plan is one segment, which lies in ps[ps_toggle] as devcoder_pstream leaves a
-// block (a void packed form: 16-bit entries), and the caller goes on as ever.  *sent = true: several segments, all pieces issued.
-// A segment that declines declines the block (what is in flight lands first); one whose packed form is void comes down as 16-bit
-// entries and is packed into place by the host (dc_pack13_host) — the block stays in one form.
+// guard, its pieces through the sender to the block's one landing zone while the next segment's kernels run.  Returns what
+// devcoder_pstream returns; J.poff / J.pbase / J.ps_packed / *ndec are the block's.  *sent = false: the plan is one segment, which lies
+// in ps[ps_toggle] as devcoder_pstream leaves a block (a void packed form: 16-bit entries), and the caller goes on as ever.  *sent =
+// true: several segments, all pieces issued.  A segment that declines declines the block (what is in flight lands first); one whose
+// packed form is void comes down as 16-bit entries and is packed into place by the host (dc_pack13_host): the block stays in one form.
 static int devcoder_block_in_segments(BlockJob& J, u32 m, const int* maxr, u32* ndec, bool* sent)
 {
     bscgpu_ctx* c = J.c;
-    const int nb = J.nblocks;
-    *sent = false;
     DcBlock B;
-    int rc = devcoder_block_begin(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, m, (u32)J.n, nb, J.start, J.size,
+    int rc = devcoder_block_begin(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, m, (u32)J.n, J.nblocks, J.start, J.size,
                                   J.run_first, maxr, J.coder, true, &B);
     if (rc < 0) return rc;
     const DcBlockSchedule& plan = B.plan;
     *ndec = (u32)plan.decisions();
-    for (int b = 0; b <= nb; ++b) { J.poff[b] = (u32)plan.poff_of(b); J.pbase[b] = (u32)plan.pbase_of(b); }
+    const size_t zone_entries = ps_layout(J, plan);
     if (plan.segments() == 1) {
         bool host_packed = false;
         rc = devcoder_block_segment(c, &B, plan.segment(0), c->ps_toggle, &host_packed);
@@ -463,65 +531,114 @@ static int devcoder_block_in_segments(BlockJob& J, u32 m, const int* maxr, u32* 
         return rc;
     }
     J.ps_packed = B.packed;
-    const size_t zone_entries = ((size_t)plan.zone_bytes() + 1u) / 2u + 64;
     if (ctx_ensure_pstream_slot(c, *J.slot, zone_entries) != LIBBSC_NO_ERROR) return LIBBSC_NOT_SUPPORTED;    // (as an arena that does not fit)
-    bool dma = dma_available() && J.slot->hps_dev != nullptr;
-    for (int b = 0; b < 8 && dma; ++b) dma = J.slot->part_sig[b] != 0;
-    J.ps_dma = dma;
-    uint8_t* const zone = reinterpret_cast<uint8_t*>(J.slot->hps);
+    PsSender send(J, c);
     std::vector<uint16_t> void_entries;
-    int issued = 0;                                                  // sub-blocks whose piece is in flight or has landed
-    // everything queued so far has landed (before the host writes a piece itself, and before the block is given up)
-    auto settle = [&]() {
-        if (!dma) return hipStreamSynchronize(c->copy_stream) == hipSuccess;
-        bool ok = true;
-        for (int b = 0; b < issued; ++b) ok = (J.ps_sig[b] == 0 || dma_wait(J.ps_sig[b]) == 0) && ok;
-        return ok;
-    };
     for (int i = 0; i < plan.segments(); ++i) {
         const int pb = c->ps_toggle;
         const DcBlockSeg g = plan.segment(i);
         bool host_packed = false;
         rc = devcoder_block_segment(c, &B, g, pb, &host_packed);
-        if (rc < 0) { (void)settle(); return rc; }
-        // the stream has been synchronised behind the segment's last kernel
-        const uint8_t* dps = reinterpret_cast<const uint8_t*>(devcoder_pstream_ptr(c, pb));
-        c->ps_guard[pb] = nullptr;
-        for (int b = 0; b < 8; ++b) c->ps_guard_sig[pb][b] = 0;
+        if (rc < 0) { (void)send.settle(); return rc; }
         if (host_packed) {
             void_entries.resize((size_t)g.expect);
-            if (hipMemcpyAsync(void_entries.data(), dps, (size_t)g.expect * 2, hipMemcpyDeviceToHost, c->stream) != hipSuccess || ctx_sync(c) != hipSuccess || !settle())
-                return LIBBSC_GPU_ERROR;
-            if (!plan.pack_void(g, void_entries.data(), zone)) return LIBBSC_GPU_ERROR;
+            if (hipMemcpyAsync(void_entries.data(), devcoder_pstream_ptr(c, pb), (size_t)g.expect * 2, hipMemcpyDeviceToHost, c->stream) != hipSuccess || ctx_sync(c) != hipSuccess ||
+                !send.settle() || !plan.pack_void(g, void_entries.data(), reinterpret_cast<uint8_t*>(J.slot->hps))) return LIBBSC_GPU_ERROR;
         }
-        for (int s = g.s0; s < g.s1; ++s, ++issued) {
-            const int k = s - g.s0;
-            const size_t src = (size_t)g.src[k], dst = (size_t)g.dst[k], len = (size_t)g.len[k];
-            if (dma) {
-                J.ps_sig[s] = 0;
-                if (host_packed || len == 0) continue;
-                if (dma_d2h((uint8_t*)J.slot->hps_dev + dst, dps + src, len, J.slot->part_sig[s]) == 0) {
-                    J.ps_sig[s] = c->ps_guard_sig[pb][s] = J.slot->part_sig[s];
-                } else if (!settle() || hipMemcpyAsync(zone + dst, dps + src, len, hipMemcpyDeviceToHost, c->stream) != hipSuccess || ctx_sync(c) != hipSuccess)
-                    return LIBBSC_GPU_ERROR;                         // (the engine took no more: this piece through HIP, waited for)
-            } else {
-                if ((!host_packed && len > 0 && hipMemcpyAsync(zone + dst, dps + src, len, hipMemcpyDeviceToHost, c->copy_stream) != hipSuccess) ||
-                    hipEventRecord(J.slot->part_ev[s], c->copy_stream) != hipSuccess) return LIBBSC_GPU_ERROR;
-                J.ps_part[s] = J.slot->part_ev[s];
-                c->ps_guard[pb] = J.slot->part_ev[s];                // (the segment's last piece: behind it the buffer is free)
-            }
-        }
+        rc = send.segment(g, pb, host_packed);
+        if (rc < 0) return rc;
         c->ps_toggle = pb ^ 1;
     }
-    J.ps_ready = nullptr;
-    if (!dma) {
-        if (hipEventRecord(J.slot->copy_ev, c->copy_stream) != hipSuccess) return LIBBSC_GPU_ERROR;
-        J.ps_ready = J.slot->copy_ev;
-    }
     *sent = true;
+    return send.finish();
+}
+
+// ---- the GPU stage of one block: its steps (the decisions among them: dc_block_plan.h) ---------------------------------------------
+// sort: the BWT with its secondary indexes, or a sort transform, into c->dL
+static int stage_sort(BlockJob& J, int blockSorter)
+{
+    bscgpu_ctx* c = J.c;
+    const int n = J.n;
+    J.num_indexes = 0;
+    if (blockSorter == LIBBSC_BLOCKSORTER_BWT) {
+        const int r = aux_rate(n);
+        uint32_t I[256];
+        int64_t primary = 0;
+        const int rc = bwt_device(c, (const u8*)J.dInput, c->dL, n, r, I, &primary);
+        if (rc < 0) return rc;
+        J.index = (int)primary;
+        J.num_indexes = (n - 1) / r;
+        for (int t = 0; t < J.num_indexes; ++t) J.indexes[t] = (int)I[t + 1] - 1;
+    } else {
+        const int rc = st_device(c, (const u8*)J.dInput, c->dL, n, blockSorter, &J.index);
+        if (rc < 0) return rc;
+    }
+    if (J.n_orig < 64 * 1024) J.num_indexes = 0;              // libbsc.cpp:290 (the original size decides)
     return LIBBSC_NO_ERROR;
 }
 
+// model, decide: static coder on a block with several sub-blocks: the adaptive model runs on the GPU too (devcoder.hip) and only the
+// probability stream crosses PCIe; anything that path declines falls back to the run arrays + host model
+// (an LZP-preprocessed block — the reference CLI's default, bsc.cpp:73-75 — is just another byte block to the sorter and the model;
+// its LZP output stays alive until the block is done, because a redo on the host model uploads it again)
+// (the fast coder, -e0, runs on the same device machinery: its one counter per decision is the static coder's char family with
+// other update maps — devcoder.hip: dc_fast_run; BSC_DEVICE_CODER_FAST=0 keeps it on the host)
+static bool model_tries(const BlockJob& J, bool allow_devcoder)
+{
+    static const bool dc_fast = [] { const char* e = getenv("BSC_DEVICE_CODER_FAST"); return e ? atoi(e) != 0 : true; }();
+    return dc_block_tries_model(allow_devcoder, devcoder_enabled(), J.coder == LIBBSC_CODER_QLFC_STATIC, J.coder == LIBBSC_CODER_QLFC_FAST && dc_fast,
+                                J.nblocks, J.n, devcoder_min_n());
+}
+// model, run and land -> < 0, or *took: the block is the device model's (else its run arrays are still to go down)
+static int stage_model(BlockJob& J, u32 m, bool* took)
+{
+    bscgpu_ctx* c = J.c;
+    *took = false;
+    if (dc_block_runs_too_dense(m, J.n)) return LIBBSC_NO_ERROR;
+    // run: whole into ps[pb], or in segments (sent: its pieces are on their way already)
+    int maxr[8], packed = 0;
+    dc_max_rank_table(J.first_run, J.nblocks, maxr);
+    u32 ndec = 0;
+    const int pb = c->ps_toggle;
+    bool sent = false;
+    const int mrc = c->dc_arena_div > 1 ? devcoder_block_in_segments(J, m, maxr, &ndec, &sent)
+                  : devcoder_pstream(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, m, (u32)J.n, J.nblocks,
+                                     J.run_first, maxr, &ndec, J.poff, nullptr, pb, J.coder, &packed);
+    if (c->dc_arena_div == 1) J.ps_packed = packed != 0;
+    // the whole stream lies in ps[pb]: its layout there = in the landing zone
+    const bool whole = mrc == LIBBSC_NO_ERROR && !sent;
+    const DcBlockSchedule lay = whole ? DcBlockSchedule::whole(J.poff, J.nblocks, J.ps_packed) : DcBlockSchedule();
+    const size_t zone_entries = whole ? ps_layout(J, lay) : 0;
+    // (a pinned landing zone that cannot be had is a reason to take the host model, like an arena that does not fit)
+    const bool zone = whole && !c->device_rc && ctx_ensure_pstream_slot(c, *J.slot, zone_entries) == LIBBSC_NO_ERROR;
+    int rc = LIBBSC_NO_ERROR;
+    switch (dc_block_verdict(mrc, sent, c->device_rc != 0, zone)) {
+    case DC_BLOCK_HOST_MODEL: return LIBBSC_NO_ERROR;
+    case DC_BLOCK_ERROR: return mrc;
+    case DC_BLOCK_SENT: break;
+    case DC_BLOCK_DEVICE_RC:
+        // the range coder runs here as well: the stream stays in HBM (its buffer is free again when this returns: no guard, no toggle)
+        rc = device_rc_block(J, pb);
+        if (rc < 0) return rc;
+        J.rc_done = true; ++c->cnt_device_rc;
+        break;
+    case DC_BLOCK_LANDED: {
+        // one segment through the sender: one copy per sub-block, none waited for
+        PsSender send(J, c);
+        rc = send.segment(lay.segment(0), pb);
+        if (rc >= 0) rc = send.finish();
+        if (rc < 0) return rc;
+        c->ps_toggle = pb ^ 1;
+        break; }
+    }
+    // the block is the device model's: the host codes from the landing zone, or has nothing left to code
+    *took = J.use_ps = true; J.ps = J.rc_done ? nullptr : J.slot->hps; J.ndec = ndec;
+    g_count_devmodel.fetch_add(1, std::memory_order_relaxed);
+    if (J.lz) g_count_devmodel_lzp.fetch_add(1, std::memory_order_relaxed);
+    return LIBBSC_NO_ERROR;
+}
+
+// small block stored | adler | sort | front (split and runs) | model | the run arrays down if the model did not take the block
 static int gpu_stage(BlockJob& J, int blockSorter, bool allow_devcoder = true)
 {
     CtxTimer tm_stage("gpu_stage of one block");
@@ -542,136 +659,23 @@ static int gpu_stage(BlockJob& J, int blockSorter, bool allow_devcoder = true)
     c->stage_ms[0] = ms_since(t0);
 
     t0 = clk::now();
-    J.num_indexes = 0;
-    if (blockSorter == LIBBSC_BLOCKSORTER_BWT) {
-        const int r = aux_rate(n);
-        uint32_t I[256];
-        int64_t primary = 0;
-        rc = bwt_device(c, (const u8*)J.dInput, c->dL, n, r, I, &primary);
-        if (rc < 0) return rc;
-        J.index = (int)primary;
-        J.num_indexes = (n - 1) / r;
-        for (int t = 0; t < J.num_indexes; ++t) J.indexes[t] = (int)I[t + 1] - 1;
-    } else {
-        rc = st_device(c, (const u8*)J.dInput, c->dL, n, blockSorter, &J.index);
-        if (rc < 0) return rc;
-    }
-    if (J.n_orig < 64 * 1024) J.num_indexes = 0;              // libbsc.cpp:290 (the original size decides)
+    rc = stage_sort(J, blockSorter);
+    if (rc < 0) return rc;
     c->stage_ms[1] = ms_since(t0);
 
-    // QLFC front half on the GPU (sub-block split, runs, ranks); only the run arrays (+ L for the rare raw
-    // sub-block) cross PCIe, into this job's pinned slot.
+    // QLFC front half on the GPU (sub-block split, runs, ranks); only the run arrays (+ L for the rare raw sub-block) cross PCIe, into
+    // this job's pinned slot: at once where the block does not try the device model, after it where the model did not take the block
     t0 = clk::now();
     J.nblocks = coder_num_blocks(n);
     rc = qlfc_front_split(c, c->dL, (u32)n, J.nblocks, J.start, J.size);
     if (rc < 0) return rc;
     u32 m = 0;
-    // static coder on a block with several sub-blocks: the adaptive model runs on the GPU too (devcoder.hip) and only the
-    // probability stream crosses PCIe; anything that path declines falls back to the run arrays + host model
-    // (an LZP-preprocessed block — the reference CLI's default, bsc.cpp:73-75 — is just another byte block to the sorter and the model;
-    // its LZP output stays alive until the block is done, because a redo on the host model uploads it again)
-    // (the fast coder, -e0, runs on the same device machinery: its one counter per decision is the static coder's char family with
-    // other update maps — devcoder.hip: dc_fast_run; BSC_DEVICE_CODER_FAST=0 keeps it on the host)
-    static const bool dc_fast = [] { const char* e = getenv("BSC_DEVICE_CODER_FAST"); return e ? atoi(e) != 0 : true; }();
-    const bool try_dc = allow_devcoder && devcoder_enabled() && (J.coder == LIBBSC_CODER_QLFC_STATIC || (J.coder == LIBBSC_CODER_QLFC_FAST && dc_fast))
-                     && J.nblocks > 1 && n >= devcoder_min_n();
+    const bool try_dc = model_tries(J, allow_devcoder);
+    bool took = false;
     rc = qlfc_front_runs(c, c->dL, (u32)n, J.nblocks, J.start, &m, J.run_first, J.first_run, *J.slot, !try_dc);
+    if (rc >= 0 && try_dc) rc = stage_model(J, m, &took);
+    if (rc >= 0 && try_dc && !took) rc = qlfc_front_copy_runs(c, m, *J.slot);
     if (rc < 0) return rc;
-    if (try_dc) {
-        bool ok = false;
-        if ((double)m <= 0.70 * (double)n) {                        // nearly one run per byte: the sub-blocks will be stored raw anyway
-            int maxr[8];
-            for (int b = 0; b < J.nblocks; ++b) {
-                int nsym = 0;
-                for (int sy = 0; sy < 256; ++sy) nsym += J.first_run[b * 256 + sy] != 0xffffffffu;
-                int k = 0; while ((2 << k) <= nsym - 1) ++k;           // bsr(nsym - 1), 0 for nsym <= 2 (qlfc.cpp:888)
-                maxr[b] = nsym >= 2 ? k : 0;
-            }
-            u32 ndec = 0;
-            const int pb = c->ps_toggle;
-            int packed = 0;
-            bool sent = false;                                       // a block in several sub-block segments: its pieces are on their way already
-            const int r2 = c->dc_arena_div > 1 ? devcoder_block_in_segments(J, m, maxr, &ndec, &sent)
-                         : devcoder_pstream(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, m, (u32)n, J.nblocks,
-                                            J.run_first, maxr, &ndec, J.poff, nullptr, pb, J.coder, &packed);
-            // byte range of every sub-block's piece in the device buffer = in the landing zone (the same layout on both sides)
-            size_t piece_lo[8], piece_hi[8], zone_entries = (size_t)ndec + 64;
-            if (c->dc_arena_div == 1) J.ps_packed = packed != 0;
-            const bool whole = r2 == LIBBSC_NO_ERROR && !sent;      // the block's stream lies in ps[pb]
-            if (r2 == LIBBSC_NO_ERROR && sent) {
-                J.use_ps = true; J.ps = J.slot->hps; J.ndec = ndec; ok = true;
-                g_count_devmodel.fetch_add(1, std::memory_order_relaxed);
-                if (J.lz) g_count_devmodel_lzp.fetch_add(1, std::memory_order_relaxed);
-            }
-            if (whole) {
-                u32 pb13 = 0;
-                for (int b = 0; b < J.nblocks; ++b) {
-                    const u32 cnt = J.poff[b + 1] - J.poff[b];
-                    J.pbase[b] = pb13;
-                    if (J.ps_packed) { piece_lo[b] = (size_t)pb13 / 8u * 13u; piece_hi[b] = piece_lo[b] + ((size_t)cnt + 7u) / 8u * 13u; pb13 += (cnt + 63u) / 64u * 64u; }
-                    else             { piece_lo[b] = (size_t)J.poff[b] * 2u; piece_hi[b] = (size_t)J.poff[b + 1] * 2u; }
-                }
-                J.pbase[J.nblocks] = pb13;
-                if (J.ps_packed) zone_entries = ((size_t)pb13 / 8u * 13u + 1u) / 2u + 64;
-            }
-            if (whole && c->device_rc) {
-                // the range coder runs here as well: the stream stays in HBM (its buffer is free again when this returns: no guard, no toggle)
-                rc = device_rc_block(J, pb);
-                if (rc < 0) return rc;
-                J.use_ps = true; J.rc_done = true; J.ps = nullptr; J.ndec = ndec; ok = true;
-                ++c->cnt_device_rc;
-                g_count_devmodel.fetch_add(1, std::memory_order_relaxed);
-                if (J.lz) g_count_devmodel_lzp.fetch_add(1, std::memory_order_relaxed);
-            } else
-            // (a pinned landing zone that cannot be had is a reason to take the host model, like an arena that does not fit)
-            if (whole && ctx_ensure_pstream_slot(c, *J.slot, zone_entries) == LIBBSC_NO_ERROR) {
-                // the stream has been synchronised behind the last kernel; the copy goes to the copy stream and is NOT waited for
-                // here: the next block's sort overlaps it, the coder tasks wait on the event
-                // (sub-block by sub-block, an event behind each piece: the task that codes sub-blocks b.. starts when ITS entries have landed —
-                // 366 MB take 7-14 ms over PCIe, which the last block of a job and every synchronous call used to wait out in full)
-                // Which engine moves them: hipMemcpyAsync is a DMA-engine copy on the system's HIP runtime but a 256-workgroup copy KERNEL on
-                // the runtime a torch process carries (dma_copy.h), so the pieces are handed to the HSA runtime's DMA copy directly and
-                // complete HSA signals; hipMemcpyAsync + events remain for a process where that is not possible (or BSC_D2H_DMA=0).
-                bool dma = dma_available() && J.slot->hps_dev != nullptr;
-                for (int b = 0; b < 8 && dma; ++b) dma = J.slot->part_sig[b] != 0;
-                J.ps_dma = false;
-                if (dma) {
-                    const uint8_t* dps = reinterpret_cast<const uint8_t*>(devcoder_pstream_ptr(c, pb));
-                    uint8_t* hdev = (uint8_t*)J.slot->hps_dev;
-                    int issued = 0;
-                    for (; issued < J.nblocks; ++issued) {
-                        const size_t lo = piece_lo[issued], hi = piece_hi[issued];
-                        if (dma_d2h(hdev + lo, dps + lo, hi - lo, J.slot->part_sig[issued]) != 0) break;
-                        J.ps_sig[issued] = J.slot->part_sig[issued];
-                    }
-                    if (issued == J.nblocks) {
-                        J.ps_dma = true;
-                        for (int b = 0; b < 8; ++b) c->ps_guard_sig[pb][b] = b < J.nblocks ? J.slot->part_sig[b] : 0;
-                        c->ps_guard[pb] = nullptr; J.ps_ready = nullptr;
-                    } else {
-                        for (int b = 0; b < issued; ++b) (void)dma_wait(J.slot->part_sig[b]);       // what was queued lands first; then the whole stream again through HIP
-                    }
-                }
-                if (!J.ps_dma) {
-                    const uint8_t* dps = reinterpret_cast<const uint8_t*>(devcoder_pstream_ptr(c, pb));
-                    for (int b = 0; b < J.nblocks; ++b) {
-                        const size_t lo = piece_lo[b], hi = piece_hi[b];
-                        if ((hi > lo && hipMemcpyAsync((uint8_t*)J.slot->hps + lo, dps + lo, hi - lo, hipMemcpyDeviceToHost, c->copy_stream) != hipSuccess) ||
-                            hipEventRecord(J.slot->part_ev[b], c->copy_stream) != hipSuccess) return LIBBSC_GPU_ERROR;
-                        J.ps_part[b] = J.slot->part_ev[b];
-                    }
-                    if (hipEventRecord(J.slot->copy_ev, c->copy_stream) != hipSuccess) return LIBBSC_GPU_ERROR;
-                    c->ps_guard[pb] = J.slot->copy_ev; J.ps_ready = J.slot->copy_ev;
-                    for (int b = 0; b < 8; ++b) c->ps_guard_sig[pb][b] = 0;
-                }
-                c->ps_toggle = pb ^ 1;
-                J.use_ps = true; J.ps = J.slot->hps; J.ndec = ndec; ok = true;
-                g_count_devmodel.fetch_add(1, std::memory_order_relaxed);
-                if (J.lz) g_count_devmodel_lzp.fetch_add(1, std::memory_order_relaxed);
-            } else if (r2 != LIBBSC_NOT_SUPPORTED && r2 != LIBBSC_NO_ERROR) return r2;
-        }
-        if (!ok) { rc = qlfc_front_copy_runs(c, m, *J.slot); if (rc < 0) return rc; }
-    }
     c->stage_ms[2] = ms_since(t0);
     return LIBBSC_NO_ERROR;
 }

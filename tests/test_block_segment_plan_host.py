@@ -1,7 +1,10 @@
-"""The plan of a single block in sub-block segments (libbsc_amd/csrc/device/dc_block_plan.h — what devcoder_block_begin cuts by and
-what gpu_stage copies by) judged on the CPU through tools/block_plan_probe.cpp: against a Python restatement over a fixed-seed sweep of
-random tables, against brute force over all cut sets, at its edges, and its joining of the segments' streams against the layout of
-bscgpu_pstream_pack13_host.  The probe is also built with AddressSanitizer and UBSan and run, as that program, on the same sweep."""
+"""The host arithmetic of a single block's device model (libbsc_amd/csrc/device/dc_block_plan.h) judged on the CPU through
+tools/block_plan_probe.cpp.  The plan of a block in sub-block segments — what devcoder_block_begin cuts by and block.cpp's sender copies
+by: against a Python restatement over a fixed-seed sweep of random tables, against brute force over all cut sets, at its edges, and its
+joining of the segments' streams against the layout of bscgpu_pstream_pack13_host.  The schedule of a block modelled in one go — what
+gpu_stage lands a whole stream by and the stage functions lay their output out by: against the arithmetic gpu_stage had of its own.
+max_rank of a sub-block, and the three decisions of the driver of one block, every combination against the conditions they replace.
+The probe is also built with AddressSanitizer and UBSan and run, as that program, on the same inputs."""
 import itertools
 import json
 import os
@@ -24,7 +27,7 @@ def _build(tmp_path_factory, name, extra):
 
 
 def _ask(exe, scenarios, env=None):
-    text = "\n".join(_line(**sc) for sc in scenarios) + "\n"
+    text = "\n".join(sc if isinstance(sc, str) else _line(**sc) for sc in scenarios) + "\n"
     r = subprocess.run([exe], input=text, capture_output=True, text=True, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     out = [json.loads(l) for l in r.stdout.splitlines()]
@@ -214,11 +217,144 @@ def test_exported_plan_is_the_headers():
             assert block_segment_plan(sc["runs"], sc["dec"], sc["mcap"], sc["dcap"]) == (rc, seg_of)
 
 
+# ---- a block modelled in one go --------------------------------------------------------------------------------------------------------
+def _whole_sweep():
+    rng = random.Random(20261021)
+    special = [0, 1, 7, 8, 63, 64, 65]
+    out = [(n, packed, [d] * n) for n in range(1, 9) for packed in (0, 1) for d in special]
+    for i in range(600):
+        n = rng.randint(1, 8)
+        out.append((n, i & 1, [rng.choice(special) if rng.random() < 0.5 else rng.randint(0, 50000) for _ in range(n)]))
+    return out
+
+
+def _gpu_stage_had(dec, packed):
+    """the layout of a whole block's stream as gpu_stage wrote it out by hand before DcBlockSchedule::whole:
+    -> poff, pbase (the packed form's; it left zeros otherwise, which nothing read), piece_lo, piece_hi, zone_entries"""
+    poff = [0]
+    for d in dec:
+        poff.append(poff[-1] + d)
+    ndec = poff[-1]
+    piece_lo, piece_hi, pbase, pb13 = [], [], [], 0
+    zone_entries = ndec + 64
+    for b in range(len(dec)):
+        cnt = poff[b + 1] - poff[b]
+        pbase.append(pb13)
+        if packed:
+            piece_lo.append(pb13 // 8 * 13)
+            piece_hi.append(piece_lo[b] + (cnt + 7) // 8 * 13)
+            pb13 += (cnt + 63) // 64 * 64
+        else:
+            piece_lo.append(poff[b] * 2)
+            piece_hi.append(poff[b + 1] * 2)
+    pbase.append(pb13)
+    if packed:
+        zone_entries = (pb13 // 8 * 13 + 1) // 2 + 64
+    return poff, pbase, piece_lo, piece_hi, zone_entries
+
+
+def _judge_whole(cases, results):
+    for (n, packed, dec), got in zip(cases, results):
+        poff, pbase, lo, hi, zone_entries = _gpu_stage_had(dec, packed)
+        assert got["segments"] == 1 == len(got["segs"]) and got["decisions"] == poff[-1], (n, packed, dec)
+        g = got["segs"][0]
+        assert (g["s0"], g["s1"], g["expect"]) == (0, n, poff[-1])
+        assert g["src"] == g["dst"] == lo and g["len"] == [h - l for l, h in zip(lo, hi)], (n, packed, dec)
+        assert got["poff"] == poff
+        assert (got["zone"] + 1) // 2 + 64 == zone_entries and got["zone"] == (pbase[-1] // 8 * 13 if packed else 2 * poff[-1])
+        if packed:
+            assert got["pbase"] == pbase, (n, dec)
+        else:
+            assert got["pbase"] == _gpu_stage_had(dec, 1)[1], "the packed space's, whichever form the block is in"
+
+
+def _whole_line(case):
+    n, packed, dec = case
+    return " ".join(str(x) for x in ["whole", n, packed] + dec)
+
+
+def test_whole_block_schedule(probe):
+    cases = _whole_sweep()
+    _judge_whole(cases, probe([_whole_line(c) for c in cases]))
+    for n, packed, dec in cases[::40]:
+        if packed:
+            packed_bytes, pbase = _pack13_layout(dec)
+            got, = probe([_whole_line((n, packed, dec))])
+            assert got["pbase"] == [int(x) for x in pbase] and got["zone"] == len(packed_bytes)
+    for bad in ("whole 0 0", "whole 9 1 1 1 1 1 1 1 1 1 1"):
+        assert probe([bad])[0]["segments"] == BAD_PARAMETER
+
+
+# ---- max_rank ----------------------------------------------------------------------------------------------------------------------------
+MAX_RANK_LINES = ["maxrank 8 1 2 3 4 5 33 255 256", "maxrank 3 17 16 0", "maxrank 0"]
+
+
+def _judge_max_rank(lines, results):
+    for line, got in zip(lines, results):
+        nsym = [int(x) for x in line.split()[2:]]
+        assert got["max_rank"] == [max(0, (k - 1).bit_length() - 1) for k in range(1, 257)]
+        assert got["table"] == [max(0, (k - 1).bit_length() - 1) for k in nsym] + UNTOUCHED[len(nsym):]
+
+
+def test_max_rank(probe):
+    _judge_max_rank(MAX_RANK_LINES, probe(MAX_RANK_LINES))
+
+
+# ---- what the driver of one block decides ----------------------------------------------------------------------------------------------
+SENT, DEVICE_RC, LANDED, HOST_MODEL, ERROR = range(5)
+
+
+def _decision_lines():
+    tries = [f"tries {a} {e} {st} {fa} {nsub} {n} {min_n}" for a, e, st, fa in itertools.product((0, 1), repeat=4) for nsub in (0, 1, 2, 8)
+             for n, min_n in ((1 << 20, 1 << 20), ((1 << 20) - 1, 1 << 20), (5, 0), (2147483647, 1 << 20))]
+    dense = [f"dense {m} {n}" for n in (10, 7, 1 << 20, 1000003, 2147483647, 3) for m in
+             sorted({0, n, *(max(0, int(0.70 * n) + d) for d in (-2, -1, 0, 1, 2))})]
+    verdict = [f"verdict {code} {s} {rc} {z}" for code in (0, -4, -1, -2, -3, -5, -9, -10, 1) for s, rc, z in itertools.product((0, 1), repeat=3)]
+    return tries + dense + verdict
+
+
+def _decided_before(line):
+    """the conditions of gpu_stage that the three functions replace"""
+    kind, *v = line.split()
+    v = [int(x) for x in v]
+    if kind == "tries":
+        allow_devcoder, enabled, coder_static, coder_fast_and_enabled, nblocks, n, min_n = v
+        return {"tries": int(bool(allow_devcoder and enabled and (coder_static or coder_fast_and_enabled) and nblocks > 1 and n >= min_n))}
+    if kind == "dense":
+        m, n = v
+        return {"dense": int(not float(m) <= 0.70 * float(n))}
+    r2, sent, device_rc, zone_had = v
+    whole = r2 == 0 and not sent
+    if r2 == 0 and sent:
+        return {"verdict": SENT}
+    if whole and device_rc:
+        return {"verdict": DEVICE_RC}
+    if whole and zone_had:
+        return {"verdict": LANDED}
+    if r2 != NOT_SUPPORTED and r2 != 0:
+        return {"verdict": ERROR}
+    return {"verdict": HOST_MODEL}
+
+
+def test_decisions_of_one_block(probe):
+    lines = _decision_lines()
+    results = probe(lines)
+    assert results == [_decided_before(l) for l in lines]
+    verdicts = [r["verdict"] for r in results if "verdict" in r]
+    assert set(verdicts) == {SENT, DEVICE_RC, LANDED, HOST_MODEL, ERROR}, "every result is reached, every combination has exactly one"
+    assert {r["dense"] for r in results if "dense" in r} == {0, 1} and {r["tries"] for r in results if "tries" in r} == {0, 1}
+
+
 def test_sanitizer_build_runs_clean(tmp_path_factory):
-    """the probe as a stand-alone program under AddressSanitizer and UBSan, on the sweep and the edges: same answers, nothing reported"""
+    """the probe as a stand-alone program under AddressSanitizer and UBSan, on the sweeps and the edges: same answers, nothing reported"""
     exe = _build(tmp_path_factory, "block_plan_probe_san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"])
     scenarios = _sweep() + [_scenario([1, 2], [3, 4], 10, 40, nullmask=7), _scenario([1] * 9, [1] * 9, 10, 40), _scenario([1], [1], 10, 40, nsub=0)]
+    whole, decisions = _whole_sweep(), _decision_lines()
     env = {k: v for k, v in os.environ.items() if k != "LD_PRELOAD"}
-    results, stderr = _ask(exe, scenarios, env=env)
+    results, stderr = _ask(exe, scenarios + [_whole_line(c) for c in whole] + MAX_RANK_LINES + decisions, env=env)
     assert "ERROR" not in stderr and "runtime error" not in stderr, stderr[-2000:]
-    _judge(scenarios, results)
+    _judge(scenarios, results[:len(scenarios)])
+    rest = results[len(scenarios):]
+    _judge_whole(whole, rest[:len(whole)])
+    _judge_max_rank(MAX_RANK_LINES, rest[len(whole):len(whole) + len(MAX_RANK_LINES)])
+    assert rest[len(whole) + len(MAX_RANK_LINES):] == [_decided_before(l) for l in decisions]

@@ -1,9 +1,12 @@
 """A single block modelled in sub-block segments on a context whose device-model arena is divided (BSCGPU_OPT_DC_ARENA_DIV; DESIGN §3.6,
 "A block in sub-block segments"): the facts the plan is made of, the stream of every divisor against the undivided context's — both
-forms, the void packed segment, the three exact resolves on —, whole blocks against the compiled reference, a pipe, the capacity exit,
-the arena's size and the option's semantics.  Segment counts are computed from the facts by bscgpu_block_segment_plan, never written down."""
+forms, the void packed segment, the three exact resolves on —, whole blocks against the compiled reference, a pipe, the same through
+the sender's events route (BSC_D2H_DMA=0, a child process), the capacity exit, the arena's size and the option's semantics.  Segment counts are computed from the facts by bscgpu_block_segment_plan, never written down."""
 import ctypes as C
 import functools
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -295,6 +298,31 @@ def test_pipe_of_depth_3(torch_cuda):
             c.close()
         out[k] = res
     assert out[4] == out[1]
+
+
+def test_two_sub_blocks_at_divisor_2(ref, torch_cuda):
+    """the smallest block in segments: two sub-blocks, one segment each"""
+    name = "1m+1"
+    T = bs.text(name)
+    c = _ctx(T.size, 2)
+    try:
+        got = c.compress_device(torch_cuda.from_numpy(T).cuda(), T.size, 1, 1).tobytes()
+        assert c.option_get(c.CNT_DC_BLOCK_SEGMENTS) == 2 and c.option_get(c.CNT_DC_LAST_FAIL) == 0
+    finally:
+        c.close()
+    assert got == _reference(ref, name, 1, 1)
+
+
+def test_events_route_of_the_sender(torch_cuda):
+    """BSC_D2H_DMA=0 keeps hipMemcpyAsync on the copy stream and an event per piece (block.cpp: PsSender), for a block in segments as for a
+    whole one: several segments at divisor 4, two at divisor 2, and the pipe, where a stream buffer is reused behind an event guard —
+    in a child process, the switch being read once"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    selection = "(whole_blocks_match_the_reference and 4m) or pipe_of_depth_3 or two_sub_blocks_at_divisor_2"
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_block_segments.py"), "-q", "-x", "-k", selection],
+                       capture_output=True, text=True, env=dict(os.environ, BSC_D2H_DMA="0"), cwd=root)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "6 passed" in r.stdout, r.stdout[-2000:]
 
 
 # ---- the capacity exit -----------------------------------------------------------------------------------------------------------------

@@ -11,8 +11,14 @@
 // rc > 0 the schedule — poff, pbase, the zone's bytes, every segment — and "join": the segments' streams, each laid out on its own the
 // way the device lays out a block of those sub-blocks, copied piece by piece (or packed into place: void_seg) into one zone, give the
 // whole block's stream where it holds decisions.
+// A line that begins with a word asks something else of the header:
+//   whole nsub packed dec[nsub]      DcBlockSchedule::whole of the poff these counts sum to: the same keys, one segment
+//   maxrank nb nsym[nb]              dc_max_rank of 1..256, and dc_max_rank_table of a first-run table with nsym[b] symbols in sub-block b
+//   tries allowed enabled coder_static coder_fast nsub n min_n | dense m n | verdict code sent device_rc zone
+//                                    what the driver of one block decides
 #include "dc_block_plan.h"
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -38,11 +44,87 @@ static std::vector<uint8_t> unit_stream(const std::vector<uint16_t>& e, const st
     return out;
 }
 
+static void print_segment(const DcBlockSeg& g, bool first)
+{
+    const int ns = g.s1 - g.s0;
+    printf("%s{\"s0\":%d,\"s1\":%d,\"r0\":%u,\"r1\":%u,\"expect\":%lld", first ? "" : ",", g.s0, g.s1, g.r0, g.r1, (long long)g.expect);
+    print_list("first", g.first, DC_BLOCK_MAX_SUB + 1);
+    print_list("src", g.src, ns); print_list("dst", g.dst, ns); print_list("len", g.len, ns);
+    printf("}");
+}
+
+// a line that began with a word -> false: not understood
+static bool asked(const char* word)
+{
+    if (!strcmp(word, "whole")) {
+        int nsub, packed;
+        if (scanf("%d %d", &nsub, &packed) != 2 || nsub < 0 || nsub > 64) return false;
+        std::vector<uint32_t> poff((size_t)nsub + 1, 0u);
+        for (int s = 0; s < nsub; ++s) { long long v; if (scanf("%lld", &v) != 1) return false; poff[(size_t)s + 1] = poff[(size_t)s] + (uint32_t)v; }
+        const DcBlockSchedule sch = DcBlockSchedule::whole(poff.data(), nsub, packed != 0);
+        printf("{\"segments\":%d", sch.segments());
+        if (sch.segments() > 0) {
+            std::vector<int64_t> po, pb;
+            for (int s = 0; s <= nsub; ++s) { po.push_back(sch.poff_of(s)); pb.push_back(sch.pbase_of(s)); }
+            printf(",\"zone\":%lld,\"decisions\":%lld", (long long)sch.zone_bytes(), (long long)sch.decisions());
+            print_list("poff", po.data(), nsub + 1);
+            print_list("pbase", pb.data(), nsub + 1);
+            printf(",\"segs\":[");
+            for (int i = 0; i < sch.segments(); ++i) print_segment(sch.segment(i), i == 0);
+            printf("]");
+        }
+        printf("}\n");
+        return true;
+    }
+    if (!strcmp(word, "maxrank")) {
+        int nb;
+        if (scanf("%d", &nb) != 1 || nb < 0 || nb > DC_BLOCK_MAX_SUB) return false;
+        std::vector<uint32_t> first_run((size_t)DC_BLOCK_MAX_SUB * 256, 0xffffffffu);
+        for (int b = 0; b < nb; ++b) {
+            int nsym;
+            if (scanf("%d", &nsym) != 1 || nsym < 0 || nsym > 256) return false;
+            for (int k = 0; k < nsym; ++k) first_run[(size_t)b * 256 + (size_t)((k * 7 + b * 31) & 255)] = (uint32_t)k;       // (k -> 7 k + c is a permutation of 0..255)
+        }
+        int of_count[256], table[DC_BLOCK_MAX_SUB];
+        for (int nsym = 1; nsym <= 256; ++nsym) of_count[nsym - 1] = dc_max_rank(nsym);
+        for (int& t : table) t = -7;
+        dc_max_rank_table(first_run.data(), nb, table);
+        printf("{\"rc\":0");
+        print_list("max_rank", of_count, 256);
+        print_list("table", table, DC_BLOCK_MAX_SUB);
+        printf("}\n");
+        return true;
+    }
+    if (!strcmp(word, "tries")) {
+        int allowed, enabled, coder_static, coder_fast, nsub; long long n, min_n;
+        if (scanf("%d %d %d %d %d %lld %lld", &allowed, &enabled, &coder_static, &coder_fast, &nsub, &n, &min_n) != 7) return false;
+        printf("{\"tries\":%d}\n", dc_block_tries_model(allowed != 0, enabled != 0, coder_static != 0, coder_fast != 0, nsub, n, min_n) ? 1 : 0);
+        return true;
+    }
+    if (!strcmp(word, "dense")) {
+        long long m, n;
+        if (scanf("%lld %lld", &m, &n) != 2) return false;
+        printf("{\"dense\":%d}\n", dc_block_runs_too_dense((uint32_t)m, (int)n) ? 1 : 0);
+        return true;
+    }
+    if (!strcmp(word, "verdict")) {
+        int code, sent, device_rc, zone;
+        if (scanf("%d %d %d %d", &code, &sent, &device_rc, &zone) != 4) return false;
+        printf("{\"verdict\":%d}\n", (int)dc_block_verdict(code, sent != 0, device_rc != 0, zone != 0));
+        return true;
+    }
+    return false;
+}
+
 int main()
 {
     int nsub, count, packed, nullmask, void_seg;
     long long mcap, dcap;
-    while (scanf("%d %d %lld %lld %d %d %d", &nsub, &count, &mcap, &dcap, &packed, &nullmask, &void_seg) == 7) {
+    char word[24];
+    while (scanf("%23s", word) == 1) {
+        if (word[0] != '-' && (word[0] < '0' || word[0] > '9')) { if (!asked(word)) return 1; continue; }
+        nsub = atoi(word);
+        if (scanf("%d %lld %lld %d %d %d", &count, &mcap, &dcap, &packed, &nullmask, &void_seg) != 6) return 1;
         if (count < 0 || count > 64) return 1;
         std::vector<uint32_t> runs((size_t)count), dec((size_t)count);
         for (int pass = 0; pass < 2; ++pass)
@@ -70,10 +152,7 @@ int main()
             for (int i = 0; i < sch.segments(); ++i) {
                 const DcBlockSeg g = sch.segment(i);
                 const int ns = g.s1 - g.s0;
-                printf("%s{\"s0\":%d,\"s1\":%d,\"r0\":%u,\"r1\":%u,\"expect\":%lld", i ? "," : "", g.s0, g.s1, g.r0, g.r1, (long long)g.expect);
-                print_list("first", g.first, DC_BLOCK_MAX_SUB + 1);
-                print_list("src", g.src, ns); print_list("dst", g.dst, ns); print_list("len", g.len, ns);
-                printf("}");
+                print_segment(g, i == 0);
                 uint32_t rel[DC_BLOCK_MAX_SUB + 1];
                 for (int s = g.s0; s <= g.s1; ++s) rel[s - g.s0] = (uint32_t)(poff[(size_t)s] - poff[(size_t)g.s0]);
                 join = join && sch.agrees(g, rel);
