@@ -450,16 +450,15 @@ __global__ __launch_bounds__(WG) void seg_reduce_kernel(const u64* __restrict__ 
 // the groups whose head lies in its tile of RS_T records and sees RS_G records past the tile, so a group of up to RS_G + 1 records always
 // fits; seg_apply counts the groups that do not (see there).
 constexpr int RS_T = 2048, RS_G = 1024, RS_E = RS_T + RS_G;       // 24 KB of LDS per workgroup: 6 workgroups per CU hide the ISA gather
-constexpr int DS_NLONG = 5, DS_EXCESS = 6;                        // dscal slots: groups of > RS_G records in the new unsorted set, their records past the first RS_G
-// The same two counts for groups of more than HY_G records (hybrid doubling rounds, bwt_longrec_kernel): the segmented sort ranks a record by
-// counting inside its group — s comparisons per record of a group of s —, the radix engine costs ~50 ps per record whatever the group.
-constexpr int HY_G = 256, DS_NMID = 3, DS_MIDEXCESS = 4;
-constexpr int DS_LRTOTAL = 7;                                     // what a hybrid round's extraction really found (must equal the host's count)
+// seg_apply counts the groups of > RS_G records in the new unsorted set and their records past the first RS_G (dev_common.h: DS_NLONG, DS_EXCESS),
+// and the same for groups of more than HY_G records (DS_NMID, DS_MIDEXCESS; hybrid doubling rounds, bwt_longrec_kernel): the segmented sort ranks a
+// record by counting inside its group — s comparisons per record of a group of s —, the radix engine costs ~50 ps per record whatever the group.
+constexpr int HY_G = 256;
 
 // seg phase B: one workgroup scans the <= 1024 chunk summaries.
 //   segoff[c]            = exclusive sum of unsorted counts
 //   segoff[MAX_CHUNKS+c] = max(last head + 1) over chunks < c
-//   dscal[0]             = total unsorted
+//   dscal[DS_TOTAL]      = total unsorted
 __global__ __launch_bounds__(WG) void seg_scan_kernel(const u32* __restrict__ segsum, u32 num_chunks,
                                                       u32* __restrict__ segoff, u32* __restrict__ dscal)
 {
@@ -485,7 +484,7 @@ __global__ __launch_bounds__(WG) void seg_scan_kernel(const u32* __restrict__ se
         carrymax = (carrymax > totmax) ? carrymax : totmax;
         __syncthreads();
     }
-    if (threadIdx.x == 0) { dscal[0] = carry; dscal[DS_NLONG] = 0; dscal[DS_EXCESS] = 0; dscal[DS_NMID] = 0; dscal[DS_MIDEXCESS] = 0; }   // (seg_apply, the next launch, adds to the counters)
+    if (threadIdx.x == 0) { dscal[DS_TOTAL] = carry; dscal[DS_NLONG] = 0; dscal[DS_EXCESS] = 0; dscal[DS_NMID] = 0; dscal[DS_MIDEXCESS] = 0; }   // (seg_apply, the next launch, adds to the counters)
 }
 
 // seg phase C: ranks (position of the group head), SA / ISA write-back, compaction of unsorted records.
@@ -1088,8 +1087,8 @@ __global__ __launch_bounds__(WG) void bwt_isa_fix_kernel(const u32* __restrict__
     for (u32 k = blockIdx.x * WG + threadIdx.x; k < U; k += stride) ISA[csa[k] & smask] = cgrp[k];
 }
 
-// Primary index and aux indexes straight from SA (no ISA needed): dscal[1] = j + 1 where SA[j] = 0,
-// dscal[8 + t] = j + 1 where SA[j] = t * r (libsais_bwt_aux semantics: I[t] = ISA[t * r] + 1).
+// Primary index and aux indexes straight from SA (no ISA needed): dscal[DS_PRIMARY] = j + 1 where SA[j] = 0,
+// dscal[DS_AUX + t] = j + 1 where SA[j] = t * r (libsais_bwt_aux semantics: I[t] = ISA[t * r] + 1).
 __global__ __launch_bounds__(WG) void bwt_find_kernel(const u32* __restrict__ SA, u32 n, u32 smask, u32 rmask, u32 rshift, u32 cnt, u32* __restrict__ dscal)
 {
     const u32 j0 = 4u * (blockIdx.x * WG + threadIdx.x);
@@ -1101,8 +1100,8 @@ __global__ __launch_bounds__(WG) void bwt_find_kernel(const u32* __restrict__ SA
     for (u32 q = 0; q < 4; ++q) {
         if (j0 + q >= n) continue;
         const u32 sfx = sv[q] & smask;
-        if (sfx == 0) dscal[1] = j0 + q + 1;
-        if (cnt != 0 && (sfx & rmask) == 0 && (sfx >> rshift) < cnt) dscal[8 + (sfx >> rshift)] = j0 + q + 1;
+        if (sfx == 0) dscal[DS_PRIMARY] = j0 + q + 1;
+        if (cnt != 0 && (sfx & rmask) == 0 && (sfx >> rshift) < cnt) dscal[DS_AUX + (sfx >> rshift)] = j0 + q + 1;
     }
 }
 
@@ -1114,7 +1113,7 @@ __global__ __launch_bounds__(WG) void bwt_emit_kernel(const u8* __restrict__ T, 
 {
     const u32 o0 = 4u * (blockIdx.x * WG + threadIdx.x);
     if (o0 >= n) return;
-    const u32 p = dscal[1] - 1;                  // ISA[0], from bwt_find_kernel
+    const u32 p = dscal[DS_PRIMARY] - 1;                  // ISA[0], from bwt_find_kernel
     u32 word = 0;
 #pragma unroll
     for (u32 q = 0; q < 4; ++q) {
@@ -1143,7 +1142,7 @@ __global__ __launch_bounds__(WG) void bwt_emit_pred_kernel(const u8* __restrict_
     __syncthreads();
     const u32 o0 = 4u * (blockIdx.x * WG + threadIdx.x);
     if (o0 >= n) return;
-    const u32 p = dscal[1] - 1;                  // ISA[0], from bwt_find_kernel
+    const u32 p = dscal[DS_PRIMARY] - 1;                  // ISA[0], from bwt_find_kernel
     u32 word = 0;
 #pragma unroll
     for (u32 q = 0; q < 4; ++q) {
@@ -1265,10 +1264,10 @@ static int run_seg(bscgpu_ctx* c, const u64* keys, const u32* sa_sorted, const u
                        SA, c->ISA, cpos_out, csa_out, cgrp_out, c->dscal);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->hscal, c->dscal, (DS_LRTOTAL + 1) * 4, hipMemcpyDeviceToHost, c->stream));  // U, (slots of other kernels), group counts, a hybrid round's extracted records
+    HIP_TRY(c, hipMemcpyAsync(c->hscal, c->dscal, DS_ROUND_WORDS * 4, hipMemcpyDeviceToHost, c->stream));  // U, (slots of other kernels), group counts, a hybrid round's extracted records
     HIP_TRY(c, ctx_sync(c));
     prof_collect(c);
-    *U_out = c->hscal[0];
+    *U_out = c->hscal[DS_TOTAL];
     return radix_onesweep_check(c);            // the sort in front of this seg, if it used the single-read passes
 }
 
@@ -1337,27 +1336,27 @@ static int bwt_first_sort(bscgpu_ctx* c, const u8* dT_user, u32 n, const BwtBatc
     HIP_TRY(c, hipMemsetAsync(c->dT + n, 0, 32, c->stream));
 
     // alphabet: byte histogram -> dense order-preserving codes
-    HIP_TRY(c, hipMemsetAsync(c->dscal + 300, 0, 256 * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->dscal + DS_BYTEHIST, 0, DS_BYTEHIST_LEN * 4, c->stream));
     {
         const Chunking hc = make_chunking(n, 16 * WG * 16);
         prof_begin(c, BSCGPU_K_MISC, n, 0);
-        hipLaunchKernelGGL(bwt_bytehist_kernel, dim3(hc.num_chunks), dim3(WG), 0, c->stream, c->dT, n, hc.chunk_tiles * 16u * WG * 16u, c->dscal + 300);
+        hipLaunchKernelGGL(bwt_bytehist_kernel, dim3(hc.num_chunks), dim3(WG), 0, c->stream, c->dT, n, hc.chunk_tiles * 16u * WG * 16u, c->dscal + DS_BYTEHIST);
         prof_end(c);
     }
-    HIP_TRY(c, hipMemcpyAsync(c->hscal + 300, c->dscal + 300, 256 * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->hscal + DS_BYTEHIST, c->dscal + DS_BYTEHIST, DS_BYTEHIST_LEN * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
     u8 codes[256]; u32 K = 0;
-    for (int b = 0; b < 256; ++b) { codes[b] = (u8)K; if (c->hscal[300 + b]) ++K; }
+    for (int b = 0; b < 256; ++b) { codes[b] = (u8)K; if (c->hscal[DS_BYTEHIST + b]) ++K; }
     // key layout and pass plan (bwt_plan.h); the single-read passes are asked about the fold's pass count, which does not depend on the answer
     const u32 count = bt ? bt->count : 0u;
     const int wmax = bwt_switches().wmax, fold_np = bwt_key_plan(K, n, count, wmax, false).fold_np;
     const BwtKeyPlan& kp = fs->kp = bwt_key_plan(K, n, count, wmax, c->bwt_fold != 0 && radix_onesweep_wanted(c, n, fold_np, true));
     PackParams& pp = fs->pp;
     pp.cb = kp.cb; pp.w = kp.w; pp.tc = kp.tc; pp.low_shift = kp.low_shift; pp.pred_shift = kp.pred_shift;
-    u8* dcodes = fs->dcodes = reinterpret_cast<u8*>(c->dscal + 560);         // 256 bytes of the scalar area
-    u8* ddecode = fs->ddecode = reinterpret_cast<u8*>(c->dscal + 720);        // 256 bytes: code -> byte (640..703 is the QLFC front end's symbol table)
+    u8* dcodes = fs->dcodes = reinterpret_cast<u8*>(c->dscal + DS_CODES);
+    u8* ddecode = fs->ddecode = reinterpret_cast<u8*>(c->dscal + DS_DECODE);
     u8 decode[256]; memset(decode, 0, sizeof decode);
-    for (int b = 255; b >= 0; --b) if (c->hscal[300 + b]) decode[codes[b]] = (u8)b;
+    for (int b = 255; b >= 0; --b) if (c->hscal[DS_BYTEHIST + b]) decode[codes[b]] = (u8)b;
     HIP_TRY(c, hipMemcpyAsync(dcodes, codes, 256, hipMemcpyHostToDevice, c->stream));
     if (pp.pred_shift) HIP_TRY(c, hipMemcpyAsync(ddecode, decode, 256, hipMemcpyHostToDevice, c->stream));
     if (kp.fold) {
@@ -1454,13 +1453,13 @@ static double bwt_now_ms() { return std::chrono::duration<double, std::milli>(st
 static double bwt_lap(BwtRounds& s) { const double t = bwt_now_ms(), d = t - s.t_round; s.t_round = t; return d; }
 
 // A round's sort gives up when a group does not fit a workgroup: the word is cleared in front of the launches, read behind them
-static int bwt_giveup_clear(bscgpu_ctx* c) { HIP_TRY(c, hipMemsetAsync(c->dscal + 2, 0, 4, c->stream)); return BSC_NO_ERROR; }
+static int bwt_giveup_clear(bscgpu_ctx* c) { HIP_TRY(c, hipMemsetAsync(c->dscal + DS_GIVEUP, 0, 4, c->stream)); return BSC_NO_ERROR; }
 static int bwt_giveup_read(bscgpu_ctx* c, bool* sorted)
 {
-    HIP_TRY(c, hipMemcpyAsync(c->hscal + 2, c->dscal + 2, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->hscal + DS_GIVEUP, c->dscal + DS_GIVEUP, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
     prof_collect(c);
-    *sorted = c->hscal[2] == 0;
+    *sorted = c->hscal[DS_GIVEUP] == 0;
     return BSC_NO_ERROR;
 }
 
@@ -1480,7 +1479,7 @@ static int bwt_sa_to_own_buffer(bscgpu_ctx* c, BwtRounds& s)
 static int bwt_textsort(bscgpu_ctx* c, BwtRounds& s, const u32* csa, const u8* subhead, bool* sorted)
 {
     hipLaunchKernelGGL(bwt_round_textsort_kernel, dim3((s.U + RS_T - 1) / RS_T), dim3(WG), 0, c->stream,
-                       c->dT, s.dcodes, csa, c->cgrp[s.cur], s.U, s.h, s.n, s.smask, s.pp.cb, s.ta, c->kB, c->vB, c->dscal + 2, subhead);
+                       c->dT, s.dcodes, csa, c->cgrp[s.cur], s.U, s.h, s.n, s.smask, s.pp.cb, s.ta, c->kB, c->vB, c->dscal + DS_GIVEUP, subhead);
     prof_end(c);
     return bwt_giveup_read(c, sorted);
 }
@@ -1563,7 +1562,7 @@ static int bwt_round_segsort(bscgpu_ctx* c, BwtRounds& s, bool* sorted)
     RC_TRY(bwt_giveup_clear(c));
     prof_begin(c, BSCGPU_K_GATHER, (u64)U * (4 + 4 + 4 + 8 + 4), U);
     hipLaunchKernelGGL(bwt_round_segsort_kernel, dim3((U + RS_T - 1) / RS_T), dim3(WG), 0, c->stream,
-                       c->csa[s.cur], c->cgrp[s.cur], c->ISA, U, s.h, (u64)s.n, s.lo_bits, s.smask, c->kB, c->vB, c->dscal + 2);
+                       c->csa[s.cur], c->cgrp[s.cur], c->ISA, U, s.h, (u64)s.n, s.lo_bits, s.smask, c->kB, c->vB, c->dscal + DS_GIVEUP);
     prof_end(c);
     s.ks = c->kB; s.vs = c->vB;
     return bwt_giveup_read(c, sorted);
@@ -1593,7 +1592,7 @@ static int bwt_round_hybrid(bscgpu_ctx* c, BwtRounds& s, const BwtRoundCounts& g
     u32* vo = s.in_alt ? c->vA : c->vB;
     prof_begin(c, BSCGPU_K_GATHER, (u64)U * (4 + 4 + 4 + 8 + 4) + (u64)UL * (8 + 4 + 4 + 4 + 8 + 4), U);
     hipLaunchKernelGGL(bwt_round_segsort_kernel, dim3((U + RS_T - 1) / RS_T), dim3(WG), 0, c->stream,
-                       c->csa[cur], c->cgrp[cur], c->ISA, U, h, (u64)n, lo_bits, smask, ko, vo, c->dscal + 2, 1u);
+                       c->csa[cur], c->cgrp[cur], c->ISA, U, h, (u64)n, lo_bits, smask, ko, vo, c->dscal + DS_GIVEUP, 1u);
     hipLaunchKernelGGL(bwt_longrec_place_kernel, dim3(capped_grid(UL)), dim3(WG), 0, c->stream, lks, lvs, lidx, c->cgrp[cur], UL, lo_bits, ko, vo);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
@@ -1694,11 +1693,11 @@ static int bwt_emit_single(bscgpu_ctx* c, const BwtRounds& s, const u8* ddecode,
                            c->dT, s.SA, n, dL_user, c->dscal);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->hscal, c->dscal, (8 + 256) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->hscal, c->dscal, (DS_AUX + DS_AUX_LEN) * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
     prof_collect(c);
-    *primary_out = c->hscal[1];
-    for (u32 t = 0; t < cnt; ++t) I_host[t] = c->hscal[8 + t];
+    *primary_out = c->hscal[DS_PRIMARY];
+    for (u32 t = 0; t < cnt; ++t) I_host[t] = c->hscal[DS_AUX + t];
     return BSC_NO_ERROR;
 }
 

@@ -228,8 +228,8 @@ extern "C" int bscgpu_create(bscgpu_ctx** out, int device, int64_t max_n)
         {(void**)&c->rowtot,  256 * 4, 0},
         {(void**)&c->segsum,  2 * MAX_CHUNKS * 4, 0},
         {(void**)&c->segoff,  2 * MAX_CHUNKS * 4, 0},
-        {(void**)&c->dscal,   1024 * 4, 0},
-        {(void**)&c->dscal64, 16 * 8, 0},
+        {(void**)&c->dscal,   SCAL_WORDS * 4, 0},
+        {(void**)&c->dscal64, SCAL64_WORDS * 8, 0},
         {(void**)&c->adler_part, (size_t)MAX_CHUNKS * 16, 0},
         {(void**)&c->wc_sink, (size_t)512 * 1024 * 8, 0},
     };
@@ -243,8 +243,7 @@ extern "C" int bscgpu_create(bscgpu_ctx** out, int device, int64_t max_n)
     for (auto& cv : carve) { *cv.p = c->arena + off + cv.lead; off += align_up(cv.bytes, ARENA_ALIGN); }
     if (hipMemsetAsync(c->arena, 0, total, c->stream) != hipSuccess) { bscgpu_destroy(c); return BSC_GPU_ERROR; }
 
-    bool ok = hipHostMalloc((void**)&c->hscal, 1024 * 4, hipHostMallocDefault) == hipSuccess
-           && hipHostMalloc((void**)&c->hscal64, 16 * 8, hipHostMallocDefault) == hipSuccess
+    bool ok = hipHostMalloc((void**)&c->hscal, SCAL_WORDS * 4, hipHostMallocDefault) == hipSuccess
            && hipHostMalloc((void**)&c->hadler, (size_t)MAX_CHUNKS * 16, hipHostMallocDefault) == hipSuccess
            && hipHostMalloc((void**)&c->hsplit, N / 256 + 64, hipHostMallocDefault) == hipSuccess
            && ctx_ensure_slots(c, 1) == BSC_NO_ERROR;
@@ -274,7 +273,6 @@ extern "C" void bscgpu_destroy(bscgpu_ctx* c)
     for (auto& p : c->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto& e : c->event_pool) hipEventDestroy(e);
     if (c->hscal) hipHostFree(c->hscal);
-    if (c->hscal64) hipHostFree(c->hscal64);
     if (c->hadler) hipHostFree(c->hadler);
     if (c->hsplit) hipHostFree(c->hsplit);
     for (int i = 0; i < MAX_SLOTS; ++i) {

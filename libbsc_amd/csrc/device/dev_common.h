@@ -9,6 +9,7 @@
 #include "../../../include/bscgpu.h"
 #include "bwt_plan.h"      // RadixPass; the BWT driver's plan (host arithmetic, no HIP)
 #include "dc_block_plan.h" // DcBlockSchedule: a single block in sub-block segments (host arithmetic, no HIP)
+#include "qlfc_front_plan.h" // the QLFC front end's cuts, alphabets, pass plan and table layout (host arithmetic, no HIP)
 
 typedef unsigned long long u64;
 typedef unsigned int       u32;
@@ -52,6 +53,44 @@ static inline Chunking make_chunking(u64 n, u32 tile) {
     c.num_chunks  = (c.num_tiles + c.chunk_tiles - 1) / c.chunk_tiles;
     return c;
 }
+
+// ---------------------------------------------------------------------------------------------
+// The scalar area of a context: dscal (HBM) and hscal (pinned), SCAL_WORDS u32 each, hscal[i] mirroring dscal[i]; dscal64, SCAL64_WORDS
+// u64 in HBM.  This is the one map of both: every user indexes them by these names.  A context runs one call at a time, so words of
+// stages that never run inside one another may coincide; those are the aliases below, each written as one.  Ranges that can be live
+// together are held apart by the static_asserts.
+// ---------------------------------------------------------------------------------------------
+constexpr int SCAL_WORDS = 1024, SCAL64_WORDS = 16;
+constexpr int DS_TOTAL     = 0;     // seg_scan_kernel's total: the unsorted records of a BWT round
+constexpr int DS_PRIMARY   = 1;     // bwt_find_kernel: the primary index (the emit kernels read it)
+constexpr int DS_GIVEUP    = 2;     // a BWT round's segmented sort met a group it could not hold
+constexpr int DS_NMID      = 3;     // seg_apply: groups of more than HY_G records in the new unsorted set (hybrid doubling rounds) ...
+constexpr int DS_MIDEXCESS = 4;     // ... and their records past the first HY_G
+constexpr int DS_NLONG     = 5;     // the same two counts for groups of more than RS_G records
+constexpr int DS_EXCESS    = 6;
+constexpr int DS_LRTOTAL   = 7;     // what a hybrid round's extraction really found (must equal the host's count)
+constexpr int DS_ROUND_WORDS = DS_LRTOTAL + 1;      // a BWT round reads words [0, DS_ROUND_WORDS) back in one copy
+constexpr int DS_AUX       = 8,   DS_AUX_LEN = 256;        // bwt_find_kernel: aux index t at DS_AUX + t; bwt_finish reads [0, DS_AUX + DS_AUX_LEN) back
+constexpr int DS_BYTEHIST  = 300, DS_BYTEHIST_LEN = 256;   // BWT first sort: the text's byte histogram
+constexpr int DS_CODES     = 560, DS_CODES_LEN = 64;       // ... its code table, byte -> code (256 bytes)
+constexpr int DS_FRONT_LUT = 640, DS_FRONT_LUT_LEN = 64;   // QLFC front end: the alphabet's renumbering (256 bytes), up from hscal
+constexpr int DS_DECODE    = 720, DS_DECODE_LEN = 64;      // BWT first sort: code -> byte (256 bytes), read by the emit kernel
+constexpr int OS_ERR_SLOT  = 1000;  // sticky error word of the single-read digit passes (cleared by radix_onesweep_check only)
+// Aliases: a word one stage leaves free, taken by a stage that never runs inside it.
+constexpr int DS_FRONT_RUNS = DS_TOTAL;       // the front end scans its run heads with seg_scan_kernel after the sort: the total is its run count m
+constexpr int DS_ST_INDEX   = DS_GIVEUP;      // a sort transform's index; a context sorts a block by BWT or by ST
+constexpr int DS_ST_WORDS   = 4;              // ... st_device reads words [0, DS_ST_WORDS) back for it
+constexpr int DS_UB_GUARD   = DS_MIDEXCESS;   // the inverse BWT's guard word: decoding runs no BWT round
+constexpr int DS64_ST_KEY0  = 0;              // dscal64: the sort transform's key of position 0
+
+static_assert(DS_ROUND_WORDS <= DS_AUX && DS_AUX + DS_AUX_LEN <= DS_BYTEHIST && DS_BYTEHIST + DS_BYTEHIST_LEN <= DS_CODES
+              && DS_CODES + DS_CODES_LEN <= DS_FRONT_LUT && DS_FRONT_LUT + DS_FRONT_LUT_LEN <= DS_DECODE && DS_DECODE + DS_DECODE_LEN <= OS_ERR_SLOT
+              && OS_ERR_SLOT + 1 <= SCAL_WORDS, "the ranges of the scalar area lie in this order, apart, inside it");
+static_assert(DS_TOTAL < DS_PRIMARY && DS_PRIMARY < DS_GIVEUP && DS_GIVEUP < DS_NMID && DS_NMID < DS_MIDEXCESS && DS_MIDEXCESS < DS_NLONG
+              && DS_NLONG < DS_EXCESS && DS_EXCESS < DS_LRTOTAL, "the words of a BWT round are distinct");
+static_assert(DS_ST_INDEX < DS_ST_WORDS && DS_ST_WORDS <= DS_AUX && DS64_ST_KEY0 < SCAL64_WORDS, "the sort transform's words");
+static_assert(DS_FRONT_RUNS < DS_ROUND_WORDS && DS_ST_INDEX < DS_ROUND_WORDS && DS_UB_GUARD < DS_ROUND_WORDS,
+              "every alias names a word of a BWT round: none reaches a table, the histogram or the sticky error word");
 
 // ---------------------------------------------------------------------------------------------
 // Context
@@ -117,8 +156,8 @@ struct bscgpu_ctx {
     u32* rowtot = nullptr;   // [256]
     u32* segsum = nullptr;   // [2][MAX_CHUNKS] per-chunk (unsorted count, last head+1)
     u32* segoff = nullptr;   // [2][MAX_CHUNKS] scanned
-    u32* dscal  = nullptr;   // small device scalars (1024 u32, mirrored slot by slot in hscal)
-    u64* dscal64 = nullptr;  // small device u64 scalars (16)
+    u32* dscal  = nullptr;   // small device scalars (SCAL_WORDS u32, mirrored slot by slot in hscal; the slot map is above)
+    u64* dscal64 = nullptr;  // small device u64 scalars (SCAL64_WORDS)
     u64* adler_part = nullptr; // [MAX_CHUNKS][2]
     u32* tile_counts = nullptr; size_t tile_counts_cap = 0;   // [256][tiles of 8192 records]: rs_scatter_tiled's offsets, allocated on first use
     u32* long_tables = nullptr;   // BWT text rounds: counting-sort tables of the long-group split (bwt.hip LongTables), allocated on first use
@@ -179,8 +218,7 @@ struct bscgpu_ctx {
     bool fold_lds_set = false;       // the packing kernels' dynamic-LDS limit has been raised on this context's device
     u32  ub_step_cap = UB_STEP_CAP;  // inverse BWT: a walk longer than this between two marked rows is declined (BSC_UNBWT_STEP_CAP, a test knob)
     // pinned host
-    u32* hscal  = nullptr;   // 1024 u32 (slot map: the users' comments; OS_ERR_SLOT = 1000)
-    u64* hscal64 = nullptr;
+    u32* hscal  = nullptr;   // SCAL_WORDS u32 (the slot map is above)
     u64* hadler = nullptr;
     u64* hsplit = nullptr;   // pinned: split-flag words (max_n / 256 + 64 bytes)
     HostSlot slots[MAX_SLOTS];   // pinned landing zones for the QLFC front end; >1 when blocks are pipelined
@@ -229,7 +267,6 @@ void prof_collect(bscgpu_ctx* c);   // after a stream sync: fold pending events 
 int radix_sort_passes(bscgpu_ctx* c, u64* keys, u64* keys_alt, u32* vals, u32* vals_alt, u64 n,
                       const RadixPass* passes, int npasses, int* in_alt, u32* emit_pos = nullptr);
 
-constexpr int OS_ERR_SLOT = 1000;           // hscal / dscal word: sticky error word of the single-read digit passes (cleared by radix_onesweep_check only)
 int  radix_onesweep_setup(bscgpu_ctx* c);
 bool radix_onesweep_wanted(const bscgpu_ctx* c, u64 n, int npasses, bool has_val);
 // totals_ready: radix_onesweep_prepare ran for this sort and the caller has added every digit's totals to the tables it returned (the
@@ -292,6 +329,22 @@ int unbwt_batch_pass(bscgpu_ctx* c, const u8* dL, u8* out, const int* sizes, con
                      u32* adler, u8* t_host);
 int adler32_device(bscgpu_ctx* c, const u8* d, int64_t n, u32* out);
 void launch_seg_scan(bscgpu_ctx* c, u32 num_chunks);
+// The QLFC front end's view of the sort buffers (qlfc_front.hip).  Once a block's (a pass's) L has been emitted nothing of the sorter
+// is live until the next sorter starts, and the front end and whoever reads its run arrays — the copy down, the device model — take
+// these roles from here:
+struct FrontBufs {
+    u8*  sym;        // vA: symbol of every run (m <= n bytes of 4 n; the sort values were last read when SA was made)
+    u8*  rank;       // vB: QLFC rank of every run (the values' other half)
+    u32* start;      // SA: start of every run (L has been emitted from it)
+    u32* first;      // ISA: a single block's first-run rows [8][256] (a pass keeps its rows in front_tab)
+    u64* mask;       // kB: the symbol set of every 256 runs (the sort keys went with the values)
+    u64* super;      // cpos[0]: ... of every 65536 runs (the BWT rounds' positions)
+    u64* flags;      // kA: the split-flag words, read back before the run arrays are made
+};
+static inline FrontBufs front_bufs(const bscgpu_ctx* c)
+{
+    return {reinterpret_cast<u8*>(c->vA), reinterpret_cast<u8*>(c->vB), c->SA, c->ISA, c->kB, reinterpret_cast<u64*>(c->cpos[0]), c->kA};
+}
 int qlfc_front_split(bscgpu_ctx* c, const u8* dL, u32 n, int nblocks, int* start, int* size);
 int qlfc_front_runs(bscgpu_ctx* c, const u8* dL, u32 n, int nblocks, const int* start, u32* m_out, u32* run_first, u32* first_run_host,
                     HostSlot& slot, bool copy_runs = true);
@@ -300,14 +353,11 @@ int qlfc_front_copy_runs(bscgpu_ctx* c, u32 m, HostSlot& slot);
 // below 1 MiB) -> the layout of include/bscgpu.h, without nsym / first_seen: first_run_host[256 s + c] = first run of symbol c in
 // sub-block s (0xffffffff: none), which qlfc_front_first_seen turns into a sub-block's alphabet.  scratch_host: front_scratch_bytes()
 // bytes, the split-flag words land there and then the first-run table (first_run_host may point into it).  Synchronous.
-constexpr int FRONT_MAX_SUB = 2 * BATCH_MAX_BLOCKS;
-size_t front_scratch_bytes(int64_t max_n);
+static_assert(FRONT_MAX_BLOCKS == BATCH_MAX_BLOCKS, "qlfc_front_plan.h plans passes of as many blocks as the sorters take");
 int  qlfc_front_batch(bscgpu_ctx* c, const u8* dL, const int* sizes, int count, bscgpu_front_layout* out, void* scratch_host);
-void qlfc_front_first_seen(const u32* first_run /*[256]*/, u8* first_seen /*[256]*/, int* nsym);
-// the table qlfc_front_batch left in HBM for its last pass of nsub sub-blocks (qlfc_front.hip: front_tab words)
+// the table qlfc_front_batch left in HBM for its last pass of nsub sub-blocks (qlfc_front_plan.h: the FT_* words)
 struct FrontTab { const u32* sub_off; const u32* sub_base; u32* sub_run; const u32* first_run; };
 FrontTab qlfc_front_tab(const bscgpu_ctx* c, int nsub);
-void qlfc_pick_cuts(const u64* w, u32 nwords, u32 n, int nblocks, int* start, int* size);   // coder.cpp:70-109 from the sampled flag words
 int  ctx_ensure_model_host(bscgpu_ctx* c);        // both pinned stream buffers of the batch model; < 0: not to be had (the pass takes the host model)
 int  ctx_ensure_front_host(bscgpu_ctx* c);        // both pinned run buffers of the batch front end; < 0: not to be had (the pass takes the L route)
 int ctx_ensure_slots(bscgpu_ctx* c, int count);

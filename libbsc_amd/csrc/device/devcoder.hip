@@ -2797,7 +2797,7 @@ static bool devcoder_batch_ensure(DevCoder* d)
     return dc_arena_alloc(d->batch_arena, carve, nullptr);
 }
 
-// What the entry points of a pass share: the arenas, the pass as qlfc_front_batch left it — the run arrays (vA / vB / SA: the buffers
+// What the entry points of a pass share: the arenas, the pass as qlfc_front_batch left it — the run arrays (FrontBufs: the buffers
 // the single path reads) and its table in front_tab, with max_rank per sub-block where dc_tab_prep_kernel will put it.
 // over_fail >= 0: the call is a model run, which clears what the context says about its last block; over_fail is what dc_note.fail
 // then says about a pass of more runs than the arena holds (a whole pass: FAIL_CAP, as devcoder_pstream; segments: 0).
@@ -2811,7 +2811,7 @@ static int dc_pass_begin(bscgpu_ctx* c, u32 m, int nsub, int over_fail, DcPass* 
     if (m == 0 || m > d->Mcap || nsub < 1 || nsub > FRONT_MAX_SUB || !c->front_tab) return BSC_NOT_SUPPORTED;
     if (!devcoder_batch_ensure(d)) return BSC_NOT_SUPPORTED;             // does not fit: the pass is declined (its blocks take the host model), not an error
     P->d = d; P->T = qlfc_front_tab(c, nsub);
-    P->dsym = reinterpret_cast<const u8*>(c->vA); P->drank = reinterpret_cast<const u8*>(c->vB); P->dstart = c->SA;
+    { const FrontBufs fb = front_bufs(c); P->dsym = fb.sym; P->drank = fb.rank; P->dstart = fb.start; }
     P->S.nsub = (u32)nsub; P->S.run = P->T.sub_run; P->S.off = P->T.sub_off; P->S.base = P->T.sub_base; P->S.maxr = d->sub_maxr;
     return BSC_NO_ERROR;
 }
@@ -3066,7 +3066,8 @@ static int64_t qlfc_static_pstream_segments(bscgpu_ctx* c, int n, int nb, const 
 {
     if (dbg) { c->err = "the debug planes need the whole block in the arena (BSCGPU_OPT_DC_ARENA_DIV 1)"; return BSC_NOT_SUPPORTED; }
     DcBlock B;
-    int rc = devcoder_block_begin(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, m, (u32)n, nb, sub_start, sub_size,
+    const FrontBufs fb = front_bufs(c);
+    int rc = devcoder_block_begin(c, fb.sym, fb.rank, fb.start, m, (u32)n, nb, sub_start, sub_size,
                                   run_first, max_rank, 1, want_packed, &B);
     if (rc == BSC_NO_ERROR && want_packed && !B.packed) { c->err = "the packed stream was not produced (option off)"; return BSC_NOT_SUPPORTED; }
     std::vector<u16> void_entries;
@@ -3130,7 +3131,8 @@ static int64_t qlfc_static_pstream_stage(bscgpu_ctx* c, const uint8_t* L, int n,
     if (dbg_out) { rc = devcoder_ensure(c); if (rc < 0) return rc; if (hipMalloc((void**)&ddbg, (size_t)c->dc->Dcap * 6) != hipSuccess) return BSC_GPU_NOT_ENOUGH_MEMORY; }
     u32 D = 0, poff[9];
     int packed = 0;
-    rc = devcoder_pstream(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, F.m, (u32)n, nb, F.run_first, F.max_rank, &D, poff, ddbg, 0, 1,
+    const FrontBufs fb = front_bufs(c);
+    rc = devcoder_pstream(c, fb.sym, fb.rank, fb.start, F.m, (u32)n, nb, F.run_first, F.max_rank, &D, poff, ddbg, 0, 1,
                           want_packed ? &packed : nullptr);
     if (rc == BSC_NO_ERROR && want_packed && !packed) { c->err = "the packed stream was not produced (option off, or a wavefront's piece beyond the staging buffer)"; rc = BSC_NOT_SUPPORTED; }
     else if (rc == BSC_NOT_SUPPORTED) {
@@ -3178,7 +3180,8 @@ extern "C" int bscgpu_qlfc_pstream_facts(bscgpu_ctx* c, const uint8_t* L, int n,
     int rc = qlfc_stage_front(c, L, n, nblocks_out, sub_start, sub_size, &F);
     if (rc < 0) return rc;
     DcBlock B;
-    rc = devcoder_block_facts(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, F.m, (u32)n, F.nb, sub_start, sub_size, F.run_first,
+    const FrontBufs fb = front_bufs(c);
+    rc = devcoder_block_facts(c, fb.sym, fb.rank, fb.start, F.m, (u32)n, F.nb, sub_start, sub_size, F.run_first,
                               F.max_rank, coder, &B);
     if (rc < 0) return rc;
     *nblocks_out = F.nb;

@@ -16,13 +16,30 @@
 //
 // The host coder then consumes (sym, rank, start) directly; L itself never crosses PCIe unless a sub-block turns
 // out incompressible and must be stored raw.
+//
+// Two forms share these steps, the kernels where a kernel can be one body, and the host driver below:
+//   a block   qlfc_front_split + qlfc_front_runs: at most eight sub-blocks, their boundaries passed to the kernels by value (QfSplit for
+//             the bytes, QfRuns for the runs), the first-run rows [8][256] in ISA
+//   a pass    qlfc_front_batch: L of up to 4096 blocks back to back, up to 8192 sub-blocks, their boundaries a table in HBM
+//             (QfbTab for the bytes, QfRunTab for the runs; front_tab, laid out by qlfc_front_plan.h), run starts relative to the block
+// Reduce and rank are one kernel template over the form; the apply kernels differ in substance (eight LDS rows against one row that is flushed
+// when the sub-block changes) and stay two.  All host arithmetic — cuts, alphabets, the plan of a pass — is qlfc_front_plan.h; where the
+// arrays live is FrontBufs (dev_common.h).
 #include "dev_common.h"
 #include <type_traits>
 
 constexpr int QF_BYTES = 16;                 // bytes per thread per tile
 constexpr int QF_TILE  = WG * QF_BYTES;      // 4096 bytes per tile
 
-struct QfSplit { u32 nblocks; u32 start[9]; };     // start[nblocks] = n
+// Where sub-blocks start in the bytes, for the two forms.  QfSplit: one block's cuts, by value; start[nblocks] = n.  QfbTab: a pass's
+// table in HBM —
+//   sub_off[s]   first byte of sub-block s in the pass (strictly increasing: empty blocks have no sub-block), sub_off[nsub] = N
+//   sub_base[s]  first byte of the BLOCK that holds sub-block s (run starts are relative to it, as RunView expects)
+// — looked up per tile: the sub-blocks of a tile's first and last byte come from two binary searches on workgroup-uniform values (scalar
+// loads, once per tile; QfbTile); a lane searches only in a tile that holds a boundary, and only between those two sub-blocks.
+struct QfSplit { u32 nblocks; u32 start[9]; };
+struct QfbTab { const u32* sub_off; const u32* sub_base; u32 nsub; };
+struct QfbTile { u32 lo, hi; bool cut; };       // sub-blocks of the tile's first and last byte; cut: a sub-block starts inside the tile
 
 __global__ __launch_bounds__(WG) void qf_split_flags_kernel(const u8* __restrict__ L, u32 n, u32 nq, u64* __restrict__ words)
 {
@@ -33,8 +50,8 @@ __global__ __launch_bounds__(WG) void qf_split_flags_kernel(const u8* __restrict
     if ((threadIdx.x & 63) == 0 && (q >> 6) < ((nq + 63) >> 6)) words[q >> 6] = b;
 }
 
-// (the block-table front end's half of qf_heads16 below) 16-bit mask of the positions i0 .. i0 + 15 whose byte differs from the one
-// before it (position 0 included); the caller adds the table's forced heads and clips the mask to n
+// 16-bit mask of the positions i0 .. i0 + 15 whose byte differs from the one before it (position 0 included); the caller adds the forced
+// heads at its sub-block starts and clips the mask to n
 __device__ __forceinline__ u32 qf_heads16_raw(const u8* __restrict__ L, u32 i0, u32 n, uint4& bytes)
 {
     bytes = make_uint4(0, 0, 0, 0);
@@ -53,9 +70,12 @@ __device__ __forceinline__ u32 qf_heads16_raw(const u8* __restrict__ L, u32 i0, 
     return mask;
 }
 
+// The head mask of a block with its cuts: bit p set iff position i0 + p starts a run (and i0 + p < n).  Its first fifteen lines ARE
+// qf_heads16_raw.  Written as a call of it the function is simplified in two steps instead of one before it is inlined, and both of its
+// kernels come out with other instructions (the first compare merged with the i0 == 0 test, other registers): the copy keeps them as
+// they are (profiles/front_end/README.md).  A change to either copy goes into both.
 __device__ __forceinline__ u32 qf_heads16(const u8* __restrict__ L, u32 i0, u32 n, const QfSplit& sp, uint4& bytes)
 {
-    // returns a 16-bit mask: bit p set iff position i0+p starts a run (and i0+p < n)
     bytes = make_uint4(0, 0, 0, 0);
     if (i0 + 16 <= n) bytes = *reinterpret_cast<const uint4*>(L + i0);
     else { u8 tmp[16]; for (int p = 0; p < 16; ++p) tmp[p] = (i0 + p < n) ? L[i0 + p] : 0; bytes = *reinterpret_cast<uint4*>(tmp); }
@@ -77,18 +97,61 @@ __device__ __forceinline__ u32 qf_heads16(const u8* __restrict__ L, u32 i0, u32 
     return mask;
 }
 
-__global__ __launch_bounds__(WG) void qf_reduce_kernel(const u8* __restrict__ L, u32 n, QfSplit sp, u32 chunk_tiles, u32 num_tiles,
+// what the table form looks up once per tile, before its lanes look at bytes ...
+__device__ __forceinline__ QfbTile qfb_tile(const QfbTab& tb, u32 tile, u32 n)
+{
+    const u32 t0 = tile * QF_TILE;
+    const u32 t1 = (t0 + QF_TILE < n ? t0 + QF_TILE : n) - 1u;
+    QfbTile r;
+    r.lo = batch_block_of(tb.sub_off, 0u, tb.nsub, t0);
+    r.hi = batch_block_of(tb.sub_off, r.lo, tb.nsub, t1);
+    r.cut = r.hi != r.lo || tb.sub_off[r.lo] == t0;
+    return r;
+}
+// ... and the head mask of bytes i0 .. i0 + 15 with the table's forced heads; s = sub-block of byte i0
+__device__ __forceinline__ u32 qfb_heads16(const u8* __restrict__ L, u32 i0, u32 n, const QfbTab& tb, const QfbTile& tl, uint4& bytes, u32& s)
+{
+    u32 mask = qf_heads16_raw(L, i0, n, bytes);
+    s = tl.lo;
+    if (tl.cut) {
+        s = batch_block_of(tb.sub_off, tl.lo, tl.hi + 1u, i0);
+        if (tb.sub_off[s] == i0) mask |= 1u;
+        for (u32 t = s + 1u; t <= tl.hi; ++t) {               // (sub-blocks are not empty: at most fifteen steps)
+            const u32 o = tb.sub_off[t];
+            if (o >= i0 + 16u) break;
+            mask |= 1u << (o - i0);
+        }
+    }
+    if (i0 + 16 > n) mask &= (n > i0) ? ((1u << (n - i0)) - 1u) : 0u;
+    return mask;
+}
+
+// Run heads per chunk, one kernel over the form (TB: QfSplit or QfbTab).  The frame is shared; what a tile does is spelled out per form,
+// each in the parent kernel's own order: hoisting the two lines they share, or hiding the table's tile look-up behind an overload that
+// is empty for a block, moved the compiler's registers or the loop's exit test.
+template <class TB>
+__global__ __launch_bounds__(WG) void qf_reduce_kernel(const u8* __restrict__ L, u32 n, TB tb, u32 chunk_tiles, u32 num_tiles,
                                                        u32* __restrict__ segsum)
 {
+    constexpr bool TABLE = std::is_same<TB, QfbTab>::value;
     __shared__ u32 scr[8];
     const u32 tile0 = blockIdx.x * chunk_tiles;
     u32 tile1 = tile0 + chunk_tiles; if (tile1 > num_tiles) tile1 = num_tiles;
     u32 cnt = 0;
     for (u32 tile = tile0; tile < tile1; ++tile) {
-        const u32 i0 = tile * QF_TILE + threadIdx.x * QF_BYTES;
-        if (i0 >= n) continue;
-        uint4 bytes;
-        cnt += __popc(qf_heads16(L, i0, n, sp, bytes));
+        if constexpr (TABLE) {
+            if (tile * QF_TILE >= n) break;
+            const QfbTile tl = qfb_tile(tb, tile, n);
+            const u32 i0 = tile * QF_TILE + threadIdx.x * QF_BYTES;
+            if (i0 >= n) continue;
+            uint4 bytes; u32 s;
+            cnt += __popc(qfb_heads16(L, i0, n, tb, tl, bytes, s));
+        } else {
+            const u32 i0 = tile * QF_TILE + threadIdx.x * QF_BYTES;
+            if (i0 >= n) continue;
+            uint4 bytes;
+            cnt += __popc(qf_heads16(L, i0, n, tb, bytes));
+        }
     }
     u32 tot;
     block_excl_sum(cnt, scr, &tot);
@@ -421,154 +484,7 @@ __global__ __launch_bounds__(WG) void qf_rank_kernel(const u8* __restrict__ sym,
     rank[j] = (u8)set.count();
 }
 
-// -------------------------------------------------------------------------------------------------
-// host side of the front end
-// -------------------------------------------------------------------------------------------------
-int qlfc_front_split(bscgpu_ctx* c, const u8* dL, u32 n, int nblocks, int* start, int* size)
-{
-    // coder.cpp:70-109
-    if (nblocks == 1) { start[0] = 0; size[0] = (int)n; return BSC_NO_ERROR; }
-    const u32 nq = (n >= 2) ? (n - 1 + 31) / 32 : 0;
-    const u32 nwords = (nq + 63) / 64;
-    u64* dwords = reinterpret_cast<u64*>(c->kA);          // scratch: the sort buffers are free after the BWT
-    prof_begin(c, BSCGPU_K_MISC, nq * 2, 0);
-    hipLaunchKernelGGL(qf_split_flags_kernel, dim3((nq + WG - 1) / WG), dim3(WG), 0, c->stream, dL, n, nq, dwords);
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->hsplit, dwords, (size_t)nwords * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, ctx_sync(c));
-    qlfc_pick_cuts(c->hsplit, nwords, n, nblocks, start, size);
-    return BSC_NO_ERROR;
-}
-
-void qlfc_pick_cuts(const u64* w, u32 nwords, u32 n, int nblocks, int* start, int* size)
-{
-    u64 changes = 0;
-    for (u32 k = 0; k < nwords; ++k) changes += (u64)__builtin_popcountll(w[k]);
-    if (changes > (u64)nblocks) {
-        const u64 per = changes / (u64)nblocks;
-        int id = 0; u64 seen = 0;
-        start[0] = 0;
-        for (u32 k = 0; k < nwords && id < nblocks - 1; ++k) {
-            u64 bits = w[k];
-            const u64 pc = (u64)__builtin_popcountll(bits);
-            if (seen + pc < per) { seen += pc; continue; }
-            while (bits && id < nblocks - 1) {
-                const int b = __builtin_ctzll(bits); bits &= bits - 1;
-                if (++seen == per) {
-                    seen = 0;
-                    const int i = 1 + 32 * (int)(k * 64 + (u32)b);
-                    size[id] = i - start[id];
-                    start[++id] = i;
-                }
-            }
-        }
-        size[nblocks - 1] = (int)n - start[nblocks - 1];
-    } else {
-        const int each = (int)n / nblocks;
-        for (int p = 0; p < nblocks; ++p) { start[p] = each * p; size[p] = (p != nblocks - 1) ? each : (int)n - each * (nblocks - 1); }
-    }
-}
-
-// Runs + ranks of all sub-blocks of dL.  Results in pinned host memory: c->hsym / c->hrank / c->hstart (m entries),
-// run_first[0..nblocks] (run index range per sub-block) and first_run[8][256].
-int qlfc_front_copy_runs(bscgpu_ctx* c, u32 m, HostSlot& slot)
-{
-    // the run arrays of the block whose front end ran last (they live in the sort buffers until the next block's sorter starts)
-    { const int rc = ctx_ensure_run_slot(c, slot); if (rc < 0) return ctx_fail(c, rc, "pinned host memory for the run arrays", hipSuccess); }
-    HIP_TRY(c, hipMemcpyAsync(slot.hsym, reinterpret_cast<u8*>(c->vA), m, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(slot.hrank, reinterpret_cast<u8*>(c->vB), m, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(slot.hstart, c->SA, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, ctx_sync(c));
-    prof_collect(c);
-    return BSC_NO_ERROR;
-}
-
-int qlfc_front_runs(bscgpu_ctx* c, const u8* dL, u32 n, int nblocks, const int* start, u32* m_out, u32* run_first /*[9]*/,
-                    u32* first_run_host /*[8*256]*/, HostSlot& slot, bool copy_runs)
-{
-    QfSplit sp; sp.nblocks = (u32)nblocks;
-    for (int b = 0; b < 9; ++b) sp.start[b] = (b < nblocks) ? (u32)start[b] : n;
-    u8*  dsym   = reinterpret_cast<u8*>(c->vA);
-    u8*  drank  = reinterpret_cast<u8*>(c->vB);
-    u32* dstart = c->SA;                                   // SA / ISA are dead once L has been emitted
-    u32* dfirst = c->ISA;
-    u64* dmask  = c->kB;                                   // m / 8 bytes
-    u64* dsuper = reinterpret_cast<u64*>(c->cpos[0]);
-
-    const Chunking ch = make_chunking(n, QF_TILE);
-    HIP_TRY(c, hipMemsetAsync(dfirst, 0xff, 8 * 256 * 4, c->stream));
-    prof_begin(c, BSCGPU_K_SEG, n, 0);
-    hipLaunchKernelGGL(qf_reduce_kernel, dim3(ch.num_chunks), dim3(WG), 0, c->stream, dL, n, sp, ch.chunk_tiles, ch.num_tiles, c->segsum);
-    prof_end(c);
-    launch_seg_scan(c, ch.num_chunks);
-    prof_begin(c, BSCGPU_K_SEG, n, 0);
-    hipLaunchKernelGGL(qf_apply_kernel, dim3(ch.num_chunks), dim3(WG), 0, c->stream, dL, n, sp, ch.chunk_tiles, ch.num_tiles,
-                       c->segoff, dsym, dstart, dfirst);
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->hscal, c->dscal, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(first_run_host, dfirst, 8 * 256 * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, ctx_sync(c));
-    const u32 m = c->hscal[0];
-    *m_out = m;
-
-    // run index range of every sub-block = smallest first_run of its symbols
-    QfRuns rb; rb.nblocks = (u32)nblocks;
-    for (int b = 0; b < nblocks; ++b) {
-        u32 lo = 0xffffffffu;
-        for (int s = 0; s < 256; ++s) if (first_run_host[b * 256 + s] < lo) lo = first_run_host[b * 256 + s];
-        rb.first[b] = lo;
-    }
-    for (int b = nblocks; b < 9; ++b) rb.first[b] = m;
-    for (int b = 0; b <= nblocks; ++b) run_first[b] = rb.first[b];
-
-    // alphabet of the block = symbols that start a run somewhere; <= 64 of them -> one-word symbol sets
-    u8* hlut = reinterpret_cast<u8*>(c->hscal + 640);      // pinned; the copy below is consumed before the next block
-    u8* dlut = reinterpret_cast<u8*>(c->dscal + 640);
-    u32 K = 0;
-    for (int s = 0; s < 256; ++s) {
-        bool present = false;
-        for (int b = 0; b < nblocks; ++b) present |= (first_run_host[b * 256 + s] != 0xffffffffu);
-        hlut[s] = (u8)(present ? (K < 255 ? K : 255) : 0);
-        K += present;
-    }
-    const bool dense = K <= 64;
-    if (dense) HIP_TRY(c, hipMemcpyAsync(dlut, hlut, 256, hipMemcpyHostToDevice, c->stream));
-
-    const u32 ntiles = (m + 255) / 256, nsuper = (ntiles + 255) / 256;
-    prof_begin(c, BSCGPU_K_MISC, m, 0);
-    if (dense) {
-        hipLaunchKernelGGL(qf_tile_masks_kernel<true>, dim3((ntiles + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, dsym, m, dlut, dmask);
-        hipLaunchKernelGGL(qf_super_masks_kernel<true>, dim3(nsuper), dim3(WG), 0, c->stream, dmask, ntiles, dsuper);
-    } else {
-        hipLaunchKernelGGL(qf_tile_masks_kernel<false>, dim3((ntiles + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, dsym, m, dlut, dmask);
-        hipLaunchKernelGGL(qf_super_masks_kernel<false>, dim3(nsuper), dim3(WG), 0, c->stream, dmask, ntiles, dsuper);
-    }
-    prof_end(c);
-    prof_begin(c, BSCGPU_K_GATHER, (u64)m * 2, m);
-    if (dense && K <= 32) hipLaunchKernelGGL((qf_rank_kernel<true, true, QfRuns>), dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, dsym, m, rb, dlut, dmask, dsuper, drank);
-    else if (dense)       hipLaunchKernelGGL((qf_rank_kernel<true, false, QfRuns>), dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, dsym, m, rb, dlut, dmask, dsuper, drank);
-    else                  hipLaunchKernelGGL((qf_rank_kernel<false, false, QfRuns>), dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, dsym, m, rb, dlut, dmask, dsuper, drank);
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    (void)dstart;
-    if (copy_runs) return qlfc_front_copy_runs(c, m, slot);
-    return BSC_NO_ERROR;           // the caller feeds the device coder from the arrays in HBM (and may still ask for the copy)
-}
-
-// -------------------------------------------------------------------------------------------------
-// The front end of a whole PASS: L of up to 4096 blocks back to back, up to 8192 sub-blocks.  The boundaries that the
-// kernels above take as by-value structs of eight entries are a table in HBM here:
-//   sub_off[s]   first byte of sub-block s in the pass (strictly increasing: empty blocks have no sub-block), sub_off[nsub] = N
-//   sub_base[s]  first byte of the BLOCK that holds sub-block s (run starts are relative to it, as RunView expects)
-//   sub_run[s]   first run of sub-block s — written by the apply kernel (the forced head at sub_off[s]), read by the rank kernel
-//   first_run[s][256]  first run of every symbol per sub-block
-// Table lookup: the sub-blocks of a tile's first and last byte come from two binary searches on workgroup-uniform values (scalar
-// loads, once per tile); a lane searches only in a tile that holds a boundary, and only between those two sub-blocks.
-// -------------------------------------------------------------------------------------------------
-struct QfbTab { const u32* sub_off; const u32* sub_base; u32 nsub; };
-
+// ---- a pass: the kernels that are its own ------------------------------------------------------------------------------------------
 // one grid row per block with two sub-blocks; ftab[3 y ..] = {first byte of the block in the pass, its length, its first flag word}
 __global__ __launch_bounds__(WG) void qfb_split_flags_kernel(const u8* __restrict__ L, const u32* __restrict__ ftab, u64* __restrict__ words)
 {
@@ -580,55 +496,6 @@ __global__ __launch_bounds__(WG) void qfb_split_flags_kernel(const u8* __restric
     if (q < nq) { const u32 i = at + 1u + 32u * q; f = L[i] != L[i - 1u]; }      // sampled relative to the block's own start
     const u64 b = __ballot(f);
     if ((threadIdx.x & 63) == 0 && (q >> 6) < ((nq + 63u) >> 6)) words[wb + (q >> 6)] = b;
-}
-
-struct QfbTile { u32 lo, hi; bool cut; };       // sub-blocks of the tile's first and last byte; cut: a sub-block starts inside the tile
-__device__ __forceinline__ QfbTile qfb_tile(const QfbTab& tb, u32 tile, u32 n)
-{
-    const u32 t0 = tile * QF_TILE;
-    const u32 t1 = (t0 + QF_TILE < n ? t0 + QF_TILE : n) - 1u;
-    QfbTile r;
-    r.lo = batch_block_of(tb.sub_off, 0u, tb.nsub, t0);
-    r.hi = batch_block_of(tb.sub_off, r.lo, tb.nsub, t1);
-    r.cut = r.hi != r.lo || tb.sub_off[r.lo] == t0;
-    return r;
-}
-// the head mask of bytes i0 .. i0 + 15 with the table's forced heads; s = sub-block of byte i0
-__device__ __forceinline__ u32 qfb_heads16(const u8* __restrict__ L, u32 i0, u32 n, const QfbTab& tb, const QfbTile& tl, uint4& bytes, u32& s)
-{
-    u32 mask = qf_heads16_raw(L, i0, n, bytes);
-    s = tl.lo;
-    if (tl.cut) {
-        s = batch_block_of(tb.sub_off, tl.lo, tl.hi + 1u, i0);
-        if (tb.sub_off[s] == i0) mask |= 1u;
-        for (u32 t = s + 1u; t <= tl.hi; ++t) {               // (sub-blocks are not empty: at most fifteen steps)
-            const u32 o = tb.sub_off[t];
-            if (o >= i0 + 16u) break;
-            mask |= 1u << (o - i0);
-        }
-    }
-    if (i0 + 16 > n) mask &= (n > i0) ? ((1u << (n - i0)) - 1u) : 0u;
-    return mask;
-}
-
-__global__ __launch_bounds__(WG) void qfb_reduce_kernel(const u8* __restrict__ L, u32 n, QfbTab tb, u32 chunk_tiles, u32 num_tiles,
-                                                        u32* __restrict__ segsum)
-{
-    __shared__ u32 scr[8];
-    const u32 tile0 = blockIdx.x * chunk_tiles;
-    u32 tile1 = tile0 + chunk_tiles; if (tile1 > num_tiles) tile1 = num_tiles;
-    u32 cnt = 0;
-    for (u32 tile = tile0; tile < tile1; ++tile) {
-        if (tile * QF_TILE >= n) break;
-        const QfbTile tl = qfb_tile(tb, tile, n);
-        const u32 i0 = tile * QF_TILE + threadIdx.x * QF_BYTES;
-        if (i0 >= n) continue;
-        uint4 bytes; u32 s;
-        cnt += __popc(qfb_heads16(L, i0, n, tb, tl, bytes, s));
-    }
-    u32 tot;
-    block_excl_sum(cnt, scr, &tot);
-    if (threadIdx.x == 0) { segsum[blockIdx.x] = tot; segsum[MAX_CHUNKS + blockIdx.x] = 0; }
 }
 
 __global__ __launch_bounds__(WG) void qfb_apply_kernel(const u8* __restrict__ L, u32 n, QfbTab tb, u32 chunk_tiles, u32 num_tiles,
@@ -689,173 +556,192 @@ __global__ __launch_bounds__(WG) void qfb_apply_kernel(const u8* __restrict__ L,
     }
 }
 
-// front_tab words: sub_off [nsub + 1] with sub_base [nsub] right behind it (one copy up; 2 FRONT_MAX_SUB + 1 words reserved),
-// sub_run [FRONT_MAX_SUB + 1], split-flag table [3 BATCH_MAX_BLOCKS], first_run [FRONT_MAX_SUB][256]
-constexpr size_t FT_OFF = 0, FT_RUN = FT_OFF + 2 * (size_t)FRONT_MAX_SUB + 1, FT_FLAG = FT_RUN + FRONT_MAX_SUB + 1,
-                 FT_FIRST = (FT_FLAG + 3 * (size_t)BATCH_MAX_BLOCKS + 63) / 64 * 64, FT_WORDS = FT_FIRST + (size_t)FRONT_MAX_SUB * 256;
-
-size_t front_scratch_bytes(int64_t max_n)
+// -------------------------------------------------------------------------------------------------
+// host side of the front end
+// -------------------------------------------------------------------------------------------------
+int qlfc_front_split(bscgpu_ctx* c, const u8* dL, u32 n, int nblocks, int* start, int* size)
 {
-    // the larger of: the flag words of every block (n_b / 256 + 8 bytes each), the first-run table and sub_run
-    const size_t flags = (size_t)max_n / 256 + 8 * (size_t)BATCH_MAX_BLOCKS + 64, table = (size_t)FRONT_MAX_SUB * 1024 + 4 * (size_t)(FRONT_MAX_SUB + 1);
-    return (flags > table ? flags : table) + 4096;
+    // coder.cpp:70-109
+    if (nblocks == 1) { start[0] = 0; size[0] = (int)n; return BSC_NO_ERROR; }
+    const u32 nq = qlfc_split_samples(n), nwords = qlfc_split_words(n);
+    u64* dwords = front_bufs(c).flags;
+    prof_begin(c, BSCGPU_K_MISC, nq * 2, 0);
+    hipLaunchKernelGGL(qf_split_flags_kernel, dim3((nq + WG - 1) / WG), dim3(WG), 0, c->stream, dL, n, nq, dwords);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->hsplit, dwords, (size_t)nwords * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    qlfc_pick_cuts(c->hsplit, nwords, n, nblocks, start, size);
+    return BSC_NO_ERROR;
 }
 
+// ---- the two steps both forms take --------------------------------------------------------------------------------------------------
+// Run heads of L under the form's boundaries tb: heads per chunk, their scan (seg_scan_kernel: the total is the run count), then the
+// compaction to fb.sym / fb.start with the first run of every symbol per sub-block — `rows` rows of 256 at dfirst, cleared here; they
+// come down to first_host with the run count, one sync.  A pass's apply kernel also notes the first run of every sub-block (the forced
+// head at sub_off[s]) at dsub_run, which the rank kernel reads; its `rows` entries come down to sub_run_host with the same sync.
+template <class TB>
+static int qf_run_heads(bscgpu_ctx* c, const u8* dL, u32 n, const TB& tb, const FrontBufs& fb, u32* dfirst, u32 rows, u32* first_host,
+                        u32* dsub_run, u32* sub_run_host, u32* m_out)
+{
+    const Chunking ch = make_chunking(n, QF_TILE);
+    HIP_TRY(c, hipMemsetAsync(dfirst, 0xff, (size_t)rows * 1024, c->stream));
+    prof_begin(c, BSCGPU_K_SEG, n, 0);
+    hipLaunchKernelGGL(qf_reduce_kernel<TB>, dim3(ch.num_chunks), dim3(WG), 0, c->stream, dL, n, tb, ch.chunk_tiles, ch.num_tiles, c->segsum);
+    prof_end(c);
+    launch_seg_scan(c, ch.num_chunks);
+    prof_begin(c, BSCGPU_K_SEG, n, 0);
+    if constexpr (std::is_same<TB, QfSplit>::value)
+        hipLaunchKernelGGL(qf_apply_kernel, dim3(ch.num_chunks), dim3(WG), 0, c->stream, dL, n, tb, ch.chunk_tiles, ch.num_tiles,
+                           c->segoff, fb.sym, fb.start, dfirst);
+    else
+        hipLaunchKernelGGL(qfb_apply_kernel, dim3(ch.num_chunks), dim3(WG), 0, c->stream, dL, n, tb, ch.chunk_tiles, ch.num_tiles,
+                           c->segoff, fb.sym, fb.start, dfirst, dsub_run);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->hscal + DS_FRONT_RUNS, c->dscal + DS_FRONT_RUNS, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(first_host, dfirst, (size_t)rows * 1024, hipMemcpyDeviceToHost, c->stream));
+    if (sub_run_host) HIP_TRY(c, hipMemcpyAsync(sub_run_host, dsub_run, (size_t)rows * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    *m_out = c->hscal[DS_FRONT_RUNS];
+    return BSC_NO_ERROR;
+}
+
+// Ranks of the m runs at fb.sym into fb.rank, sub-blocks ending where rb says.  The union alphabet of the first-run rows picks how a set
+// of symbols is held (qlfc_front_plan.h); its renumbering goes up for the two dense layouts (through pinned hscal: the copy is consumed
+// before the next block), then the sets of every 256 and every 65536 runs, then one lane per run.  Asynchronous.
+template <bool DENSE, bool NARROW, class RB>
+static void qf_launch_ranks(bscgpu_ctx* c, const FrontBufs& fb, u32 m, const RB& rb, const u8* dlut)
+{
+    const u32 ntiles = (m + 255) / 256, nsuper = (ntiles + 255) / 256;
+    prof_begin(c, BSCGPU_K_MISC, m, 0);
+    hipLaunchKernelGGL(qf_tile_masks_kernel<DENSE>, dim3((ntiles + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, fb.sym, m, dlut, fb.mask);
+    hipLaunchKernelGGL(qf_super_masks_kernel<DENSE>, dim3(nsuper), dim3(WG), 0, c->stream, fb.mask, ntiles, fb.super);
+    prof_end(c);
+    prof_begin(c, BSCGPU_K_GATHER, (u64)m * 2, m);
+    hipLaunchKernelGGL((qf_rank_kernel<DENSE, NARROW, RB>), dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, fb.sym, m, rb, dlut, fb.mask, fb.super, fb.rank);
+    prof_end(c);
+}
+template <class RB>
+static int qf_ranks(bscgpu_ctx* c, const FrontBufs& fb, u32 m, const RB& rb, const u32* first_host, u32 rows)
+{
+    u8* hlut = reinterpret_cast<u8*>(c->hscal + DS_FRONT_LUT);
+    u8* dlut = reinterpret_cast<u8*>(c->dscal + DS_FRONT_LUT);
+    const QfRankPath path = qlfc_front_rank_path(qlfc_front_alphabet(first_host, rows, hlut));
+    if (path != QF_RANK_WIDE) HIP_TRY(c, hipMemcpyAsync(dlut, hlut, 256, hipMemcpyHostToDevice, c->stream));
+    if (path == QF_RANK_NARROW)     qf_launch_ranks<true, true>(c, fb, m, rb, dlut);
+    else if (path == QF_RANK_DENSE) qf_launch_ranks<true, false>(c, fb, m, rb, dlut);
+    else                            qf_launch_ranks<false, false>(c, fb, m, rb, dlut);
+    HIP_TRY(c, hipGetLastError());
+    return BSC_NO_ERROR;
+}
+
+// ---- a block ------------------------------------------------------------------------------------------------------------------------
+// the run arrays of the block whose front end ran last (they stay where FrontBufs says until the next block's sorter starts) into the
+// slot's pinned memory: hsym / hrank / hstart, m entries each
+int qlfc_front_copy_runs(bscgpu_ctx* c, u32 m, HostSlot& slot)
+{
+    { const int rc = ctx_ensure_run_slot(c, slot); if (rc < 0) return ctx_fail(c, rc, "pinned host memory for the run arrays", hipSuccess); }
+    const FrontBufs fb = front_bufs(c);
+    HIP_TRY(c, hipMemcpyAsync(slot.hsym, fb.sym, m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(slot.hrank, fb.rank, m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(slot.hstart, fb.start, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    prof_collect(c);
+    return BSC_NO_ERROR;
+}
+
+// Runs + ranks of all sub-blocks of dL: *m_out runs, run_first[0..nblocks] (run index range per sub-block) and first_run_host[8][256];
+// copy_runs: the arrays also come down into the slot.
+int qlfc_front_runs(bscgpu_ctx* c, const u8* dL, u32 n, int nblocks, const int* start, u32* m_out, u32* run_first /*[9]*/,
+                    u32* first_run_host /*[8*256]*/, HostSlot& slot, bool copy_runs)
+{
+    QfSplit sp; sp.nblocks = (u32)nblocks;
+    for (int b = 0; b < 9; ++b) sp.start[b] = (b < nblocks) ? (u32)start[b] : n;
+    const FrontBufs fb = front_bufs(c);
+    u32 m = 0;
+    RC_TRY(qf_run_heads(c, dL, n, sp, fb, fb.first, 8, first_run_host, nullptr, nullptr, &m));
+    *m_out = m;
+    QfRuns rb; rb.nblocks = (u32)nblocks;
+    for (int b = 0; b < 9; ++b) rb.first[b] = (b < nblocks) ? qlfc_front_row_first(first_run_host + 256 * b) : m;
+    for (int b = 0; b <= nblocks; ++b) run_first[b] = rb.first[b];
+    RC_TRY(qf_ranks(c, fb, m, rb, first_run_host, (u32)nblocks));
+    if (copy_runs) return qlfc_front_copy_runs(c, m, slot);
+    return BSC_NO_ERROR;           // the caller feeds the device coder from the arrays in HBM (and may still ask for the copy)
+}
+
+// ---- a pass -------------------------------------------------------------------------------------------------------------------------
 FrontTab qlfc_front_tab(const bscgpu_ctx* c, int nsub)
 {
     FrontTab t;
     t.sub_off = c->front_tab + FT_OFF; t.sub_base = c->front_tab + FT_OFF + nsub + 1; t.sub_run = c->front_tab + FT_RUN; t.first_run = c->front_tab + FT_FIRST;
     return t;
 }
-
-void qlfc_front_first_seen(const u32* first_run, u8* first_seen, int* nsym)
+// table memory: front_tab on first use
+static int front_tab_ensure(bscgpu_ctx* c)
 {
-    // alphabet in order of first appearance = symbols sorted by the index of their first run (as block.cpp: host_prepare)
-    u64 order[256]; int k = 0;
-    for (u32 s = 0; s < 256; ++s) if (first_run[s] != 0xffffffffu) order[k++] = ((u64)first_run[s] << 8) | s;
-    for (int i = 1; i < k; ++i) { const u64 v = order[i]; int j = i; while (j > 0 && order[j - 1] > v) { order[j] = order[j - 1]; --j; } order[j] = v; }
-    for (int i = 0; i < k; ++i) first_seen[i] = (u8)(order[i] & 0xffu);
-    *nsym = k;
+    if (c->front_tab) return BSC_NO_ERROR;
+    if (hipMalloc((void**)&c->front_tab, FT_WORDS * 4) != hipSuccess) {
+        (void)hipGetLastError(); c->front_tab = nullptr;
+        return ctx_fail(c, BSC_GPU_NOT_ENOUGH_MEMORY, "batched front end: sub-block table", hipSuccess);
+    }
+    c->front_bytes = FT_WORDS * 4;
+    return BSC_NO_ERROR;
+}
+// flags: the sampled blocks' flag words into words_host; no such block: no launch, no sync
+static int front_batch_flags(bscgpu_ctx* c, const u8* dL, const QfPassFlags& F, void* words_host)
+{
+    if (F.sampled() == 0) return BSC_NO_ERROR;
+    u32* const dflag = c->front_tab + FT_FLAG;
+    u64* const dwords = front_bufs(c).flags;
+    HIP_TRY(c, hipMemcpyAsync(dflag, F.tab.data(), F.tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    prof_begin(c, BSCGPU_K_MISC, (u64)F.nwords * 128, 0);
+    hipLaunchKernelGGL(qfb_split_flags_kernel, dim3((F.maxq + WG - 1) / WG, (u32)F.sampled()), dim3(WG), 0, c->stream, dL, dflag, dwords);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(words_host, dwords, (size_t)F.nwords * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    return BSC_NO_ERROR;
 }
 
 int qlfc_front_batch(bscgpu_ctx* c, const u8* dL, const int* sizes, int count, bscgpu_front_layout* out, void* scratch_host)
 {
-    if (count < 0 || count > BATCH_MAX_BLOCKS || ((uintptr_t)dL & 15u)) return BSC_BAD_PARAMETER;
-    u64 total = 0;
-    int nbig = 0;
-    for (int b = 0; b < count; ++b) {
-        if (sizes[b] < 0 || sizes[b] >= BSCGPU_BATCH_MAX_N) return BSC_BAD_PARAMETER;
-        total += (u64)sizes[b]; nbig += sizes[b] >= 256 * 1024;
-    }
-    if (total > (u64)c->max_n) return BSC_BAD_PARAMETER;
+    // arguments
+    if ((uintptr_t)dL & 15u) return BSC_BAD_PARAMETER;
+    const int64_t total = qlfc_pass_total(sizes, count, BSCGPU_BATCH_MAX_N, c->max_n);
+    if (total < 0) return BSC_BAD_PARAMETER;
     out->count = count; out->sizes = sizes; out->nsub = 0; out->m = 0;
     for (int b = 0; b <= count; ++b) out->blk_sub[b] = 0;
     out->sub_run[0] = 0;
     if (total == 0) return BSC_NO_ERROR;
     const u32 n = (u32)total;
-    if (!c->front_tab) {
-        if (hipMalloc((void**)&c->front_tab, FT_WORDS * 4) != hipSuccess) {
-            (void)hipGetLastError(); c->front_tab = nullptr;
-            return ctx_fail(c, BSC_GPU_NOT_ENOUGH_MEMORY, "batched front end: sub-block table", hipSuccess);
-        }
-        c->front_bytes = FT_WORDS * 4;
-    }
-    u32* const dtab = c->front_tab;
-    u8*  dsym   = reinterpret_cast<u8*>(c->vA);           // the sort buffers are dead once the pass's L has been emitted
-    u8*  drank  = reinterpret_cast<u8*>(c->vB);
-    u32* dstart = c->SA;
-    u64* dmask  = c->kB;
-    u64* dsuper = reinterpret_cast<u64*>(c->cpos[0]);
-    u64* dwords = c->kA;
-
-    // 1. split flags of the blocks with two sub-blocks, cuts on the host (coder.cpp:70-109); no such block: no launch, no sync
-    std::vector<u32> ftab((size_t)3 * nbig);
-    u32 nwords = 0, maxq = 0;
-    {
-        u64 at = 0; int k = 0;
-        for (int b = 0; b < count; ++b) {
-            if (sizes[b] >= 256 * 1024) {
-                const u32 nq = ((u32)sizes[b] - 1 + 31) / 32;
-                ftab[3 * k] = (u32)at; ftab[3 * k + 1] = (u32)sizes[b]; ftab[3 * k + 2] = nwords; ++k;
-                nwords += (nq + 63) / 64; if (nq > maxq) maxq = nq;
-            }
-            at += (u64)sizes[b];
-        }
-    }
-    const u64* hwords = reinterpret_cast<const u64*>(scratch_host);
-    if (nbig > 0) {
-        HIP_TRY(c, hipMemcpyAsync(dtab + FT_FLAG, ftab.data(), ftab.size() * 4, hipMemcpyHostToDevice, c->stream));
-        prof_begin(c, BSCGPU_K_MISC, (u64)nwords * 128, 0);
-        hipLaunchKernelGGL(qfb_split_flags_kernel, dim3((maxq + WG - 1) / WG, (u32)nbig), dim3(WG), 0, c->stream, dL, dtab + FT_FLAG, dwords);
-        prof_end(c);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(scratch_host, dwords, (size_t)nwords * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, ctx_sync(c));
-    }
-    // 2. the sub-block table
-    std::vector<u32> tab;
-    tab.reserve((size_t)4 * count + 2);
-    std::vector<u32> sbase;
-    int nsub = 0;
-    {
-        u64 at = 0; int k = 0;
-        for (int b = 0; b < count; ++b) {
-            out->blk_sub[b] = nsub;
-            const int nb_ = sizes[b] == 0 ? 0 : (sizes[b] >= 256 * 1024 ? 2 : 1);
-            if (nb_ == 1) { out->sub_start[nsub] = 0; out->sub_size[nsub] = sizes[b]; }
-            if (nb_ == 2) {
-                const u32 nq = ((u32)sizes[b] - 1 + 31) / 32;
-                qlfc_pick_cuts(hwords + ftab[3 * k + 2], (nq + 63) / 64, (u32)sizes[b], 2, out->sub_start + nsub, out->sub_size + nsub);
-                ++k;
-            }
-            for (int q = 0; q < nb_; ++q) { tab.push_back((u32)at + (u32)out->sub_start[nsub + q]); sbase.push_back((u32)at); }
-            nsub += nb_;
-            at += (u64)sizes[b];
-        }
-        out->blk_sub[count] = nsub;
-    }
+    // table memory
+    RC_TRY(front_tab_ensure(c));
+    // flags and cuts (coder.cpp:70-109), the sub-block table
+    const QfPassFlags F = qlfc_pass_flags(sizes, count);
+    RC_TRY(front_batch_flags(c, dL, F, scratch_host));
+    QfPassTable T;
+    const int nsub = qlfc_pass_table(sizes, count, F, reinterpret_cast<const u64*>(scratch_host), out->blk_sub, out->sub_start, out->sub_size, &T);
+    if (nsub < 0) return BSC_BAD_PARAMETER;
     out->nsub = nsub;
-    tab.push_back(n);
-    tab.insert(tab.end(), sbase.begin(), sbase.end());
-    u32* const doff = dtab + FT_OFF;
-    u32* const dbase = dtab + FT_OFF + nsub + 1;              // (behind the offsets: one copy for both)
-    u32* const drun = dtab + FT_RUN;
-    u32* const dfirst = dtab + FT_FIRST;
-    if (2 * (size_t)nsub + 1 > FT_RUN - FT_OFF) return BSC_BAD_PARAMETER;      // (count <= BATCH_MAX_BLOCKS, two sub-blocks each at most: cannot happen)
-    HIP_TRY(c, hipMemcpyAsync(doff, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(dfirst, 0xff, (size_t)nsub * 1024, c->stream));
-    QfbTab tb; tb.sub_off = doff; tb.sub_base = dbase; tb.nsub = (u32)nsub;
-
-    // 3. run heads, compaction, first runs
-    const Chunking ch = make_chunking(n, QF_TILE);
-    prof_begin(c, BSCGPU_K_SEG, n, 0);
-    hipLaunchKernelGGL(qfb_reduce_kernel, dim3(ch.num_chunks), dim3(WG), 0, c->stream, dL, n, tb, ch.chunk_tiles, ch.num_tiles, c->segsum);
-    prof_end(c);
-    launch_seg_scan(c, ch.num_chunks);
-    prof_begin(c, BSCGPU_K_SEG, n, 0);
-    hipLaunchKernelGGL(qfb_apply_kernel, dim3(ch.num_chunks), dim3(WG), 0, c->stream, dL, n, tb, ch.chunk_tiles, ch.num_tiles,
-                       c->segoff, dsym, dstart, dfirst, drun);
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
+    // table up
+    const FrontTab ft = qlfc_front_tab(c, nsub);
+    HIP_TRY(c, hipMemcpyAsync(c->front_tab + FT_OFF, T.words.data(), T.words.size() * 4, hipMemcpyHostToDevice, c->stream));
+    const QfbTab tb = {ft.sub_off, ft.sub_base, (u32)nsub};
+    // run heads, compaction, first runs (the rows land where the flag words were)
+    const FrontBufs fb = front_bufs(c);
     u32* const first_run_host = reinterpret_cast<u32*>(scratch_host);
-    HIP_TRY(c, hipMemcpyAsync(c->hscal, c->dscal, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(first_run_host, dfirst, (size_t)nsub * 1024, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(out->sub_run, drun, (size_t)nsub * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, ctx_sync(c));
-    const u32 m = c->hscal[0];
+    u32 m = 0;
+    RC_TRY(qf_run_heads(c, dL, n, tb, fb, c->front_tab + FT_FIRST, (u32)nsub, first_run_host, ft.sub_run, out->sub_run, &m));
     if (m == 0 || m > n) return ctx_fail(c, BSC_GPU_ERROR, "batched front end: run count", hipSuccess);
     out->m = m; out->sub_run[nsub] = m;
-
-    // 4. symbol sets from the pass's union alphabet, ranks
-    u8* hlut = reinterpret_cast<u8*>(c->hscal + 640);
-    u8* dlut = reinterpret_cast<u8*>(c->dscal + 640);
-    bool present[256] = {};
-    for (size_t i = 0; i < (size_t)nsub * 256; ++i) if (first_run_host[i] != 0xffffffffu) present[i & 255u] = true;
-    u32 K = 0;
-    for (int s = 0; s < 256; ++s) { hlut[s] = (u8)(present[s] ? (K < 255 ? K : 255) : 0); K += present[s]; }
-    const bool dense = K <= 64;
-    if (dense) HIP_TRY(c, hipMemcpyAsync(dlut, hlut, 256, hipMemcpyHostToDevice, c->stream));
-    const u32 ntiles = (m + 255) / 256, nsuper = (ntiles + 255) / 256;
-    prof_begin(c, BSCGPU_K_MISC, m, 0);
-    if (dense) {
-        hipLaunchKernelGGL(qf_tile_masks_kernel<true>, dim3((ntiles + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, dsym, m, dlut, dmask);
-        hipLaunchKernelGGL(qf_super_masks_kernel<true>, dim3(nsuper), dim3(WG), 0, c->stream, dmask, ntiles, dsuper);
-    } else {
-        hipLaunchKernelGGL(qf_tile_masks_kernel<false>, dim3((ntiles + WAVES - 1) / WAVES), dim3(WG), 0, c->stream, dsym, m, dlut, dmask);
-        hipLaunchKernelGGL(qf_super_masks_kernel<false>, dim3(nsuper), dim3(WG), 0, c->stream, dmask, ntiles, dsuper);
-    }
-    prof_end(c);
-    QfRunTab rt; rt.first = drun; rt.nsub = (u32)nsub;
-    prof_begin(c, BSCGPU_K_GATHER, (u64)m * 2, m);
-    if (dense && K <= 32) hipLaunchKernelGGL((qf_rank_kernel<true, true, QfRunTab>), dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, dsym, m, rt, dlut, dmask, dsuper, drank);
-    else if (dense)       hipLaunchKernelGGL((qf_rank_kernel<true, false, QfRunTab>), dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, dsym, m, rt, dlut, dmask, dsuper, drank);
-    else                  hipLaunchKernelGGL((qf_rank_kernel<false, false, QfRunTab>), dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, dsym, m, rt, dlut, dmask, dsuper, drank);
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    // 5. the run arrays
-    HIP_TRY(c, hipMemcpyAsync(out->sym, dsym, m, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(out->rank, drank, m, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(out->start, dstart, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
+    // ranks, from the pass's union alphabet
+    const QfRunTab rt = {ft.sub_run, (u32)nsub};
+    RC_TRY(qf_ranks(c, fb, m, rt, first_run_host, (u32)nsub));
+    // arrays down
+    HIP_TRY(c, hipMemcpyAsync(out->sym, fb.sym, m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out->rank, fb.rank, m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out->start, fb.start, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
     prof_collect(c);
     return BSC_NO_ERROR;

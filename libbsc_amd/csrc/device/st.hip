@@ -99,39 +99,39 @@ static int st_device_once(bscgpu_ctx* c, const u8* dT_user, u8* dOut_user, int n
     }
     if (!reuse_text) HIP_TRY(c, hipMemcpyAsync(c->dT, dT_user, n, hipMemcpyDeviceToDevice, c->stream));
     hipLaunchKernelGGL(st_pad_kernel, dim3(1), dim3(64), 0, c->stream, c->dT, n);
-    HIP_TRY(c, hipMemsetAsync(c->dscal + 2, 0xff, 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->dscal + DS_ST_INDEX, 0xff, 4, c->stream));
 
     const dim3 grid((n + 4 * WG - 1) / (4 * WG));
     int in_alt = 0, rc;
     RadixPass passes[8];
     if (k < 8) {
         prof_begin(c, BSCGPU_K_PACK, (u64)n * 9, n);
-        hipLaunchKernelGGL(st_pack_kernel<false>, grid, dim3(WG), 0, c->stream, c->dT, n, c->kA, (u32*)nullptr, c->dscal64);
+        hipLaunchKernelGGL(st_pack_kernel<false>, grid, dim3(WG), 0, c->stream, c->dT, n, c->kA, (u32*)nullptr, c->dscal64 + DS64_ST_KEY0);
         prof_end(c);
         bwt_cut_passes(passes, (7 - k) * 8, 8 * k);
         rc = radix_sort_passes(c, c->kA, c->kB, nullptr, nullptr, n, passes, k, &in_alt);
         if (rc < 0) return rc;
         prof_begin(c, BSCGPU_K_EMIT, (u64)n * 9, n);
         hipLaunchKernelGGL(st_post_kernel<false>, grid, dim3(WG), 0, c->stream, in_alt ? c->kB : c->kA, (const u32*)nullptr,
-                           n, c->dscal64, dOut_user, c->dscal + 2);
+                           n, c->dscal64 + DS64_ST_KEY0, dOut_user, c->dscal + DS_ST_INDEX);
         prof_end(c);
     } else {
         prof_begin(c, BSCGPU_K_PACK, (u64)n * 13, n);
-        hipLaunchKernelGGL(st_pack_kernel<true>, grid, dim3(WG), 0, c->stream, c->dT, n, c->kA, c->vA, c->dscal64);
+        hipLaunchKernelGGL(st_pack_kernel<true>, grid, dim3(WG), 0, c->stream, c->dT, n, c->kA, c->vA, c->dscal64 + DS64_ST_KEY0);
         prof_end(c);
         bwt_cut_passes(passes, 0, 64);
         rc = radix_sort_passes(c, c->kA, c->kB, c->vA, c->vB, n, passes, 8, &in_alt);
         if (rc < 0) return rc;
         prof_begin(c, BSCGPU_K_EMIT, (u64)n * 5, n);
         hipLaunchKernelGGL(st_post_kernel<true>, grid, dim3(WG), 0, c->stream, in_alt ? c->kB : c->kA, in_alt ? c->vB : c->vA,
-                           n, c->dscal64, dOut_user, c->dscal + 2);
+                           n, c->dscal64 + DS64_ST_KEY0, dOut_user, c->dscal + DS_ST_INDEX);
         prof_end(c);
     }
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->hscal, c->dscal, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->hscal, c->dscal, DS_ST_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
     prof_collect(c);
-    *index_out = (int)c->hscal[2];
+    *index_out = (int)c->hscal[DS_ST_INDEX];
     return radix_onesweep_check(c);
 }
 

@@ -106,9 +106,9 @@ static void ub_launch_walk(bscgpu_ctx* c, const u64* P, const UbSeg* seg, u32 S,
 {
     const dim3 grid((S + WG - 1) / WG), block(WG);
     if (c->ub_step_cap == UB_STEP_CAP)
-        hipLaunchKernelGGL((ub_walk_kernel<DECODE, false>), grid, block, 0, c->stream, P, seg, S, seg_len, seg_next, seg_start, out, c->dscal + 4, UB_STEP_CAP);
+        hipLaunchKernelGGL((ub_walk_kernel<DECODE, false>), grid, block, 0, c->stream, P, seg, S, seg_len, seg_next, seg_start, out, c->dscal + DS_UB_GUARD, UB_STEP_CAP);
     else
-        hipLaunchKernelGGL((ub_walk_kernel<DECODE, true>), grid, block, 0, c->stream, P, seg, S, seg_len, seg_next, seg_start, out, c->dscal + 4, c->ub_step_cap);
+        hipLaunchKernelGGL((ub_walk_kernel<DECODE, true>), grid, block, 0, c->stream, P, seg, S, seg_len, seg_next, seg_start, out, c->dscal + DS_UB_GUARD, c->ub_step_cap);
 }
 
 // Host-pointer entry: L (n bytes) -> T (n bytes), both host memory; returns BSC_NO_ERROR, a libbsc error code,
@@ -130,7 +130,7 @@ extern "C" int bscgpu_unbwt(bscgpu_ctx* c, const uint8_t* L, uint8_t* T, int64_t
     if ((size_t)S * 16 > (size_t)c->max_n * 4 + 4096 * 4) { S = (u32)(((size_t)c->max_n * 4) / 16); if (S < 1) S = 1; }
 
     HIP_TRY(c, hipMemcpyAsync(dL, L, n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->dscal + 4, 0, 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->dscal + DS_UB_GUARD, 0, 4, c->stream));
     prof_begin(c, BSCGPU_K_PACK, (u64)n * 9, n);
     hipLaunchKernelGGL(ub_keys_kernel, dim3((n + WG - 1) / WG), dim3(WG), 0, c->stream, dL, n, keys);
     prof_end(c);
@@ -149,14 +149,14 @@ extern "C" int bscgpu_unbwt(bscgpu_ctx* c, const uint8_t* L, uint8_t* T, int64_t
     std::vector<u32> hlen(S), hnext(S), hstart(S, 0u);
     HIP_TRY(c, hipMemcpyAsync(hlen.data(), seg_len, (size_t)S * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(hnext.data(), seg_next, (size_t)S * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->hscal + 4, c->dscal + 4, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->hscal + DS_UB_GUARD, c->dscal + DS_UB_GUARD, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
     prof_collect(c);
     // A walk longer than the step cap is not proof of corruption — the marked rows are a fixed hash of the row number, and a valid
     // but adversarial block can put more than the cap between two of them —, so it is "not handled here" (the caller's host walk
     // decides, T is still untouched); LIBBSC_DATA_CORRUPT is reserved for the chain-closure checks below.
-    if (c->hscal[4] & 2u) return BSC_NOT_SUPPORTED;
-    if (c->hscal[4] != 0) return -6;
+    if (c->hscal[DS_UB_GUARD] & 2u) return BSC_NOT_SUPPORTED;
+    if (c->hscal[DS_UB_GUARD] != 0) return -6;
     // order of the segments: from segment 0 (row 0 = the text's end) along the successor links; every non-empty segment must
     // be met exactly once, the lengths must add up to n and the last link must be the sentinel row
     {
@@ -182,10 +182,10 @@ extern "C" int bscgpu_unbwt(bscgpu_ctx* c, const uint8_t* L, uint8_t* T, int64_t
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(T, c->dL, n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->hscal + 4, c->dscal + 4, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->hscal + DS_UB_GUARD, c->dscal + DS_UB_GUARD, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
     prof_collect(c);
-    return c->hscal[4] != 0 ? -6 : BSC_NO_ERROR;
+    return c->hscal[DS_UB_GUARD] != 0 ? -6 : BSC_NO_ERROR;
 }
 
 // ---- batched passes (bscgpu_unbwt_batch_device; the decompress batch, batch_decode.cpp) ------------------------------
@@ -348,7 +348,7 @@ int unbwt_batch_pass(bscgpu_ctx* c, const u8* dL, u8* out, const int* sizes, con
 
     HIP_TRY(c, hipMemcpyAsync(dtab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(H, 0, (size_t)count * 256 * 4, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->dscal + 4, 0, 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->dscal + DS_UB_GUARD, 0, 4, c->stream));
     prof_begin(c, BSCGPU_K_PACK, (u64)n * 9, n);
     if (n > 0) hipLaunchKernelGGL(ub_keys_batch_kernel, dim3((n + UB_TILE - 1) / UB_TILE), dim3(WG), 0, c->stream, dL, n, doff, (u32)count, keys, H);
     prof_end(c);
@@ -395,7 +395,7 @@ int unbwt_batch_pass(bscgpu_ctx* c, const u8* dL, u8* out, const int* sizes, con
         if (r != BSC_NO_ERROR) { res[b] = r; for (u32 s = s0; s < s1; ++s) hstart[s] = UB_END; }     // its segments are not walked
     }
     HIP_TRY(c, hipMemcpyAsync(seg_start, hstart.data(), (size_t)nseg * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->dscal + 4, 0, 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->dscal + DS_UB_GUARD, 0, 4, c->stream));
     prof_begin(c, BSCGPU_K_GATHER, (u64)n * 9, n);
     ub_launch_walk<true>(c, P, seg, nseg, nullptr, nullptr, seg_start, out);
     prof_end(c);
@@ -405,10 +405,10 @@ int unbwt_batch_pass(bscgpu_ctx* c, const u8* dL, u8* out, const int* sizes, con
     }
     HIP_TRY(c, hipGetLastError());
     if (t_host && span > 0) HIP_TRY(c, hipMemcpyAsync(t_host, out, (size_t)span, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->hscal + 4, c->dscal + 4, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->hscal + DS_UB_GUARD, c->dscal + DS_UB_GUARD, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
     prof_collect(c);
-    if (c->hscal[4] != 0)                       // a guard of the decode walk fired (the chain checks rule it out): trust no block of the pass
+    if (c->hscal[DS_UB_GUARD] != 0)                       // a guard of the decode walk fired (the chain checks rule it out): trust no block of the pass
         for (int b = 0; b < count; ++b) if (idx[b] && res[b] == BSC_NO_ERROR) res[b] = BSC_DATA_CORRUPT;
     return BSC_NO_ERROR;
 }

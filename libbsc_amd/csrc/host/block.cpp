@@ -518,7 +518,8 @@ static int devcoder_block_in_segments(BlockJob& J, u32 m, const int* maxr, u32* 
 {
     bscgpu_ctx* c = J.c;
     DcBlock B;
-    int rc = devcoder_block_begin(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, m, (u32)J.n, J.nblocks, J.start, J.size,
+    const FrontBufs fb = front_bufs(c);
+    int rc = devcoder_block_begin(c, fb.sym, fb.rank, fb.start, m, (u32)J.n, J.nblocks, J.start, J.size,
                                   J.run_first, maxr, J.coder, true, &B);
     if (rc < 0) return rc;
     const DcBlockSchedule& plan = B.plan;
@@ -601,8 +602,9 @@ static int stage_model(BlockJob& J, u32 m, bool* took)
     u32 ndec = 0;
     const int pb = c->ps_toggle;
     bool sent = false;
+    const FrontBufs fb = front_bufs(c);
     const int mrc = c->dc_arena_div > 1 ? devcoder_block_in_segments(J, m, maxr, &ndec, &sent)
-                  : devcoder_pstream(c, reinterpret_cast<const u8*>(c->vA), reinterpret_cast<const u8*>(c->vB), c->SA, m, (u32)J.n, J.nblocks,
+                  : devcoder_pstream(c, fb.sym, fb.rank, fb.start, m, (u32)J.n, J.nblocks,
                                      J.run_first, maxr, &ndec, J.poff, nullptr, pb, J.coder, &packed);
     if (c->dc_arena_div == 1) J.ps_packed = packed != 0;
     // the whole stream lies in ps[pb]: its layout there = in the landing zone

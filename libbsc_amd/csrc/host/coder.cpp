@@ -18,14 +18,6 @@ namespace bschost {
 
 enum { FEATURE_MULTITHREADING = 2 };
 
-int coder_num_blocks(int n)
-{
-    if (n < 256 * 1024)       return 1;
-    if (n < 4 * 1024 * 1024)  return 2;
-    if (n < 16 * 1024 * 1024) return 4;
-    return 8;
-}
-
 // Sub-block boundaries: sample every 32nd position (1, 33, 65, ...), count the sampled positions that
 // start a run, cut whenever the running count reaches total / nblocks, at that sampled position.
 void coder_split_blocks(const uint8_t* in, int n, int nblocks, int* start, int* size)

@@ -94,7 +94,14 @@ int coder_decompress(const uint8_t* in, uint8_t* out, int coder, int features);
 constexpr long long UNBOUNDED_INPUT = (long long)1 << 62;
 int coder_decompress_bounded(const uint8_t* in, long long in_size, uint8_t* out, int coder, int features, int max_out);
 int qlfc_decode_block_bounded(const uint8_t* in, long long in_size, uint8_t* out, int coder, int max_out);
-int coder_num_blocks(int n);
+// sub-blocks of a block of n bytes (coder.cpp:52-59); inline: the front end's plan (device/qlfc_front_plan.h) counts by it too
+inline int coder_num_blocks(int n)
+{
+    if (n < 256 * 1024)       return 1;
+    if (n < 4 * 1024 * 1024)  return 2;
+    if (n < 16 * 1024 * 1024) return 4;
+    return 8;
+}
 // Same framing, but the sub-blocks arrive as run arrays (GPU front end).  fetch_raw(start, size, dst) supplies the
 // original bytes of a sub-block that has to be stored raw.
 struct RawFetch { virtual int operator()(int start, int size, uint8_t* dst) = 0; virtual ~RawFetch() {} };
