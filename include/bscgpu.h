@@ -274,6 +274,30 @@ BSCGPU_API int64_t bscgpu_fast_pstream_host(const bscgpu_front_layout* layout, i
 BSCGPU_API int bscgpu_front_batch_code_psf(const bscgpu_front_layout* layout, int block, const uint16_t* ps, const uint32_t* poff,
                                            unsigned char* out, int features);
 
+/* ---- the adaptive coder's model (-e2) of a whole pass ("The adaptive coder's model of a pass") ----------------------
+ * The adaptive coder's decisions, contexts and counters are the static coder's with other rates; its probability comes from one of
+ * 1896 mixer instances per sub-block instead of a fixed blend.  The stage runs the static coder's device model with the adaptive
+ * rates, then walks every mixer chain (sub-block, mixer id) of the pass, one lane per chain.  Entries are in the static coder's
+ * 16-bit form, {[11:0] probability, [12] coded bit, [13] first decision of a run}: an -e2 sub-block stream is a BSCGPU_RC_STATIC16
+ * body behind the prefix that bscgpu_rc_prefix returns for coder 1 (header word, alphabet and stop rule are the static coder's;
+ * bscgpu_rc_prefix itself keeps refusing coder 2).  There is no block coder of its own: bscgpu_front_batch_code_ps codes a block
+ * from -e2 streams, bscgpu_rc_encode_host / _device take a sub-block's stream unchanged.
+ * bscgpu_adaptive_pstream_batch_device: limits, return values, "counted, not copied" above cap and "a declined pass still fills
+ *   the layout" are bscgpu_static_pstream_batch_device's word for word.  dbg (optional, [4][cap] uint16): the state-, char- and
+ *   position-indexed counter values before their update and the mixer id behind every decision, to localise a mismatch.  Declines:
+ *   those of the static model (the run_hist resolve always runs, so never BSCGPU_DC_FAIL_HIST), and BSCGPU_DC_FAIL_MIX when the
+ *   longest mixer chain of the pass exceeds the step cap (BSC_DC_MIX_CHAIN_CAP in the environment, read when a context is created;
+ *   values below 16 are ignored; default 1 << 18: the steps the walk does in the time the host coder takes for a 64 MiB pass on 16
+ *   threads, measured).  Memory: the first call adds 24 bytes per decision of capacity (96 bytes per byte of max_n) to
+ *   the device model's arena, on top of the batch model's 8, counted by bscgpu_arena_bytes from then on; where that does not fit
+ *   the pass is declined with BSCGPU_CNT_DC_LAST_FAIL = 0.
+ * bscgpu_adaptive_pstream_host: the CPU stand-in (no GPU, no context): the host model's own walk over sub-block s of a layout with
+ *   the mixer step the device uses, recording instead of coding; dbg as above.  Returns the sub-block's number of decisions; entries
+ *   past cap are counted, not written. */
+BSCGPU_API int64_t bscgpu_adaptive_pstream_batch_device(bscgpu_ctx* ctx, const void* dL, const int* sizes, int count, bscgpu_front_layout* layout,
+                                                        uint16_t* out, int64_t cap, uint32_t* poff, uint16_t* dbg);
+BSCGPU_API int64_t bscgpu_adaptive_pstream_host(const bscgpu_front_layout* layout, int s, uint16_t* out, int64_t cap, uint16_t* dbg);
+
 /* ---- a pass's model in segments ("Model segments") ------------------------------------------------------------------
  * Sub-blocks are independent chains, so the model of a pass can run over any contiguous range of its sub-blocks and write the same
  * entries.  A model segment is such a range, made of whole blocks.
@@ -602,6 +626,19 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          Default 0: measured, it gains on calls of several full passes (4 % from host input, 10 % from HBM, a quarter
  *                          less CPU per MB) and loses 9 - 19 % on one-pass calls.
  * BSCGPU_CNT_BATCH_FAST_PASSES, BSCGPU_CNT_BATCH_FAST_DECLINED  (get only) its passes coded from the device's stream, and declined.
+ * BSCGPU_OPT_BATCH_MODEL_ADAPTIVE  1: the same for the adaptive coder (-e2), an option of its own: a pass of the compress-batch calls that
+ *                          takes the front-end route with -e2 also runs the adaptive coder's model on the GPU
+ *                          (bscgpu_adaptive_pstream_batch_device's stage); the 16-bit stream comes down and the coder threads run the
+ *                          range coder only (bscgpu_front_batch_code_ps).  A pass the device declines (the static model's reasons, or
+ *                          BSCGPU_DC_FAIL_MIX) and a pass below BSC_BATCH_MODEL_MIN_PASS (default 16 MiB, -e1's, until measured) take
+ *                          the host model.  Segments, the packed form and BSCGPU_OPT_DEVICE_RC do not apply to -e2: with them on such a
+ *                          pass takes the whole-pass 16-bit host-coded route.  -e1 and -e0 and their counters are not affected.  Same
+ *                          output.  Default 0 (DESIGN §2b has the stage's and the whole calls' figures).
+ * BSCGPU_CNT_BATCH_ADAPTIVE_PASSES, BSCGPU_CNT_BATCH_ADAPTIVE_DECLINED  (get only) its passes coded from the device's stream, and declined.
+ * BSCGPU_CNT_DC_MIX_CHAINS, BSCGPU_CNT_DC_MIX_LONGEST  (get only) mixer chains of the last -e2 pass given to the device model, and the
+ *                          steps of the longest (what BSC_DC_MIX_CHAIN_CAP is compared with).
+ * BSCGPU_CNT_DC_MIX_WALK_US  (get only) the host's wall time, in microseconds, of that pass's walk (chain placement and walk kernels up to
+ *                          their sync): divided by the longest chain, the walk's time per dependent step (tools/batch_bench.py).
  * BSCGPU_OPT_BWT_FOLD      1 (default; BSC_BWT_FOLD=0 in the environment turns it off): where the first-sort key of a single block leaves
  *                          1..4 bits over a whole number of bytes (17..64 symbols) and the sort takes the single-read passes, key
  *                          packing places the records by those bits and counts the byte digits, and the sort is one pass shorter
@@ -659,12 +696,15 @@ enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACK
        BSCGPU_OPT_DC_AVG_EXACT = 30, BSCGPU_CNT_DC_AVG_RESOLVED = 31,
        BSCGPU_OPT_DC_REPLAY_EXACT = 32, BSCGPU_CNT_DC_REPLAY_RESOLVED = 33,
        BSCGPU_OPT_DC_HIST_EXACT = 34, BSCGPU_CNT_DC_HIST_RESOLVED = 35,
-       BSCGPU_OPT_DC_ARENA_DIV = 36, BSCGPU_CNT_DC_BLOCK_SEGMENTS = 37 };
+       BSCGPU_OPT_DC_ARENA_DIV = 36, BSCGPU_CNT_DC_BLOCK_SEGMENTS = 37,
+       BSCGPU_OPT_BATCH_MODEL_ADAPTIVE = 38, BSCGPU_CNT_BATCH_ADAPTIVE_PASSES = 39, BSCGPU_CNT_BATCH_ADAPTIVE_DECLINED = 40,
+       BSCGPU_CNT_DC_MIX_CHAINS = 41, BSCGPU_CNT_DC_MIX_LONGEST = 42, BSCGPU_CNT_DC_MIX_WALK_US = 43 };
 /* _FAIL_AVG: undecided avg_rank flags; _FAIL_HIST: a run_hist bracket open after 9216 predecessors (never with
  * BSCGPU_OPT_DC_HIST_EXACT); _FAIL_CAP: more runs or decisions
  * than the context's arena holds; _FAIL_REPLAY: a chain whose bracket stayed open over more than 64 evaluation chunks (with
- * BSCGPU_OPT_DC_REPLAY_EXACT: only behind the resolve's guard). */
-enum { BSCGPU_DC_FAIL_AVG = 2, BSCGPU_DC_FAIL_HIST = 4, BSCGPU_DC_FAIL_CAP = 8, BSCGPU_DC_FAIL_REPLAY = 16 };
+ * BSCGPU_OPT_DC_REPLAY_EXACT: only behind the resolve's guard); _FAIL_MIX (the adaptive coder's model of a pass only): the longest
+ * mixer chain exceeds the step cap. */
+enum { BSCGPU_DC_FAIL_AVG = 2, BSCGPU_DC_FAIL_HIST = 4, BSCGPU_DC_FAIL_CAP = 8, BSCGPU_DC_FAIL_REPLAY = 16, BSCGPU_DC_FAIL_MIX = 32 };
 BSCGPU_API int bscgpu_option_set(bscgpu_ctx* ctx, int key, int value);
 /* Where a single block is cut when the device model's arena holds less than the block (BSCGPU_OPT_DC_ARENA_DIV): pure host arithmetic,
  * no GPU needed.  Sub-blocks in order (nsub in 1..8), sub_runs[s] runs and sub_dec[s] decisions each; consecutive sub-blocks join a

@@ -104,6 +104,10 @@ def lib():
     L.bscgpu_fast_pstream_batch_device.restype = C.c_int64
     L.bscgpu_fast_pstream_host.argtypes = [vp, C.c_int, vp, C.c_int64]
     L.bscgpu_fast_pstream_host.restype = C.c_int64
+    L.bscgpu_adaptive_pstream_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int64, vp, vp]
+    L.bscgpu_adaptive_pstream_batch_device.restype = C.c_int64
+    L.bscgpu_adaptive_pstream_host.argtypes = [vp, C.c_int, vp, C.c_int64, vp]
+    L.bscgpu_adaptive_pstream_host.restype = C.c_int64
     L.bscgpu_front_batch_code_psf.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int]
     L.bscgpu_model_segment_plan.argtypes = [vp, vp, vp, C.c_int, C.c_int64, C.c_int64, vp]
     L.bscgpu_model_segment_facts_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, vp]

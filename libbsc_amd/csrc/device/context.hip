@@ -204,6 +204,7 @@ extern "C" int bscgpu_create(bscgpu_ctx** out, int device, int64_t max_n)
     { const char* e = getenv("BSC_DC_HIST_EXACT"); c->dc_hist_exact = (e && e[0] == '1') ? 1 : 0; }      // BSCGPU_OPT_DC_HIST_EXACT
     { const char* e = getenv("BSC_DC_REPLAY_CAND"); const long long v = e ? atoll(e) : 0; if (v >= 1 && v <= 0xffffffffll) c->dc_replay_cand = (u32)v; }   // devcoder.hip 3': the guard
     { const char* e = getenv("BSC_BWT_FOLD"); if (e && e[0] >= '0' && e[0] <= '2' && !e[1]) c->bwt_fold = e[0] - '0'; }       // BSCGPU_OPT_BWT_FOLD
+    { const char* e = getenv("BSC_DC_MIX_CHAIN_CAP"); const long long v = e ? atoll(e) : 0; if (v >= 16 && v <= 0xffffffffll) c->dc_mix_cap = (u32)v; }   // devcoder.hip: FAIL_MIX
     { const char* e = getenv("BSC_UNBWT_STEP_CAP"); const long long v = e ? atoll(e) : 0; if (v >= 16 && v <= 0xffffffffll) c->ub_step_cap = (u32)v; }   // unbwt.hip
     memset(c->kstat, 0, sizeof c->kstat);
     auto tm_streams = std::make_unique<CtxTimer>("  streams + events");
@@ -363,6 +364,7 @@ extern "C" int bscgpu_option_set(bscgpu_ctx* c, int key, int value)
     if (key == BSCGPU_OPT_DEVICE_RC && (value == 0 || value == 1)) { const int old = c->device_rc; c->device_rc = value; return old; }
     if (key == BSCGPU_OPT_BATCH_MODEL && (value == 0 || value == 1)) { const int old = c->batch_model; c->batch_model = value; return old; }
     if (key == BSCGPU_OPT_BATCH_MODEL_FAST && (value == 0 || value == 1)) { const int old = c->batch_model_fast; c->batch_model_fast = value; return old; }
+    if (key == BSCGPU_OPT_BATCH_MODEL_ADAPTIVE && (value == 0 || value == 1)) { const int old = c->batch_model_adaptive; c->batch_model_adaptive = value; return old; }
     if (key == BSCGPU_OPT_BATCH_MODEL_SEGMENTS && (value == 0 || value == 1)) { const int old = c->batch_model_segments; c->batch_model_segments = value; return old; }
     if (key == BSCGPU_OPT_BATCH_MODEL_PACKED && (value == 0 || value == 1)) { const int old = c->batch_model_packed; c->batch_model_packed = value; return old; }
     if (key == BSCGPU_OPT_BWT_FOLD && value >= 0 && value <= 2) { const int old = c->bwt_fold; c->bwt_fold = value; return old; }
@@ -396,6 +398,12 @@ extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
     if (key == BSCGPU_OPT_BATCH_MODEL_FAST) return c->batch_model_fast;
     if (key == BSCGPU_CNT_BATCH_FAST_PASSES) return c->cnt_model_fast_passes;
     if (key == BSCGPU_CNT_BATCH_FAST_DECLINED) return c->cnt_model_fast_declined;
+    if (key == BSCGPU_OPT_BATCH_MODEL_ADAPTIVE) return c->batch_model_adaptive;
+    if (key == BSCGPU_CNT_BATCH_ADAPTIVE_PASSES) return c->cnt_model_adaptive_passes;
+    if (key == BSCGPU_CNT_BATCH_ADAPTIVE_DECLINED) return c->cnt_model_adaptive_declined;
+    if (key == BSCGPU_CNT_DC_MIX_CHAINS) return (int)c->dc_mix_chains;
+    if (key == BSCGPU_CNT_DC_MIX_LONGEST) return (int)c->dc_mix_longest;
+    if (key == BSCGPU_CNT_DC_MIX_WALK_US) return (int)c->dc_mix_walk_us;
     if (key == BSCGPU_OPT_BATCH_MODEL_SEGMENTS) return c->batch_model_segments;
     if (key == BSCGPU_CNT_BATCH_SEGMENTS) return c->cnt_seg;
     if (key == BSCGPU_CNT_BATCH_SEG_RERUNS) return c->cnt_seg_reruns;

@@ -127,6 +127,9 @@ struct DcNote {
     void clear(int why = 0) { *this = DcNote(); fail = why; }
 };
 
+constexpr u32 DC_MIX_CHAIN_CAP = 1u << 18;  // devcoder.hip: steps of the longest mixer chain of an -e2 pass (bscgpu_ctx::dc_mix_cap).  Measured (DESIGN §2b,
+                                            // "The adaptive coder's model of a pass"): the walk takes 274 - 293 ns per step of the longest chain, the host
+                                            // coder 108 - 122 ms for a 64 MiB pass on 16 threads: 371 - 423 thousand steps, rounded down to a power of two
 constexpr u32 UB_STEP_CAP = 1u << 22;       // unbwt.hip: steps a walk may take between two marked rows (bscgpu_ctx::ub_step_cap)
 
 struct bscgpu_ctx {
@@ -182,6 +185,12 @@ struct bscgpu_ctx {
     // the fast coder's (the same entry with coder 3); it shares the pinned stream buffers below
     int  batch_model_fast = 0;    // BSCGPU_OPT_BATCH_MODEL_FAST (default 0: DESIGN §2b, "The fast coder's model of a pass")
     int  cnt_model_fast_passes = 0, cnt_model_fast_declined = 0;   // BSCGPU_CNT_BATCH_FAST_PASSES / _DECLINED
+    // the adaptive coder's (coder 2: the static model with the adaptive rates, then the mixer chains)
+    int  batch_model_adaptive = 0;   // BSCGPU_OPT_BATCH_MODEL_ADAPTIVE (default 0: DESIGN §2b, "The adaptive coder's model of a pass")
+    int  cnt_model_adaptive_passes = 0, cnt_model_adaptive_declined = 0;   // BSCGPU_CNT_BATCH_ADAPTIVE_PASSES / _DECLINED
+    u32  dc_mix_cap = DC_MIX_CHAIN_CAP;   // steps the longest mixer chain of a pass may have (BSC_DC_MIX_CHAIN_CAP, a test knob): above it FAIL_MIX
+    u32  dc_mix_chains = 0, dc_mix_longest = 0;   // BSCGPU_CNT_DC_MIX_CHAINS / _LONGEST: the last -e2 pass given to the device model
+    u32  dc_mix_walk_us = 0;                      // BSCGPU_CNT_DC_MIX_WALK_US: ... and the host's wall time of its walk (placement and walk kernels, one sync)
     // model segments (devcoder.hip: devcoder_pstream_segments; DESIGN §2b, "Model segments")
     int  batch_model_segments = 0;   // BSCGPU_OPT_BATCH_MODEL_SEGMENTS (default 0)
     int  cnt_seg = 0, cnt_seg_reruns = 0, cnt_seg_host_blocks = 0;   // BSCGPU_CNT_BATCH_SEGMENTS / _SEG_RERUNS / _SEG_HOST_BLOCKS
@@ -265,7 +274,7 @@ void prof_collect(bscgpu_ctx* c);   // after a stream sync: fold pending events 
 // passes is even, else in (keys_alt, vals_alt); *in_alt tells which.
 // emit_pos (optional; one keys-only pass): emit_pos[i] = index in the output of input record i.
 int radix_sort_passes(bscgpu_ctx* c, u64* keys, u64* keys_alt, u32* vals, u32* vals_alt, u64 n,
-                      const RadixPass* passes, int npasses, int* in_alt, u32* emit_pos = nullptr);
+                      const RadixPass* passes, int npasses, int* in_alt, u32* emit_pos = nullptr, bool aux = false);
 
 int  radix_onesweep_setup(bscgpu_ctx* c);
 bool radix_onesweep_wanted(const bscgpu_ctx* c, u64 n, int npasses, bool has_val);
@@ -400,8 +409,12 @@ int64_t devcoder_mcap(const bscgpu_ctx* c);             // runs the device model
 // packed_out non-null (coder 1): the stream may be left in the packed 13-bit form of a pass ("The packed stream of a pass");
 // *packed_out = 1: it was — pbase[0..nsub] at devcoder_batch_pbase_ptr (device), *pbytes_out = pbase[nsub] / 8 * 13 bytes in the
 // stream buffer; 0: the packed form was void and the 2-byte entries are there instead
-int  devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, int coder /* 1 static (-e1), 3 fast (-e0) */, u32* D_out,
+// coder 2: the adaptive coder's (-e2) — the static model with the adaptive rates (the run_hist resolve always on: never FAIL_HIST),
+// then one walk per mixer chain; entries in the static coder's form; FAIL_MIX when the longest chain exceeds c->dc_mix_cap; the four
+// debug planes [4][*D_out] (state / char / static counter values, mixer id) stay at devcoder_mix_dbg_ptr (device)
+int  devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, int coder /* 1 static (-e1), 2 adaptive (-e2), 3 fast (-e0) */, u32* D_out,
                             int* packed_out = nullptr, int64_t* pbytes_out = nullptr);
+const u16* devcoder_mix_dbg_ptr(const bscgpu_ctx* c);
 const u32* devcoder_batch_poff_ptr(const bscgpu_ctx* c);
 const u32* devcoder_batch_pbase_ptr(const bscgpu_ctx* c);
 // ... of a pass in model segments ("Model segments"): the same inputs plus the layout's blk_sub[count + 1] and

@@ -37,6 +37,7 @@
 // The host side drives the stages from ONE body per coder, a template over the form as the kernels are: dc_static_run (-e1) and
 // dc_fast_run (-e0).  devcoder_pstream (a block), devcoder_pstream_batch (a pass) and devcoder_pstream_segments (a pass cut at
 // capacity) hold what differs in front of a body: the sub-blocks' shape, the avg_rank flags, the table's max_rank, the rebased table.
+// The adaptive coder (-e2) of a whole pass is dc_static_run with its own rates and, behind it, one walk per mixer chain (dc_mix_run).
 #include "dev_common.h"
 #include "dma_copy.h"
 #include <thread>
@@ -76,9 +77,10 @@ enum { DM_FAIL = 0, DM_NTYPES, DM_NROUNDS, DM_AVG_UND, DM_REPLAYS, DM_D0, DM_D1,
        DM_REPLAY_RESOLVED /* open chunk starts the exact resolve settled (3') */,
        DM_HIST_RESOLVED /* runs whose open run_hist bracket the exact resolve settled (1c') */, DM_COUNT = 16 };
 // (bit 0 is not in use: every decision type has a row of its own, DC_ROWS >= NUM_TAU, so no number of types is too many)
-enum { FAIL_AVG = BSCGPU_DC_FAIL_AVG, FAIL_HIST = BSCGPU_DC_FAIL_HIST, FAIL_CAP = BSCGPU_DC_FAIL_CAP, FAIL_REPLAY = BSCGPU_DC_FAIL_REPLAY };
+enum { FAIL_AVG = BSCGPU_DC_FAIL_AVG, FAIL_HIST = BSCGPU_DC_FAIL_HIST, FAIL_CAP = BSCGPU_DC_FAIL_CAP, FAIL_REPLAY = BSCGPU_DC_FAIL_REPLAY, FAIL_MIX = BSCGPU_DC_FAIL_MIX };
 // the pinned host copy (DevCoder::hmeta, HM_WORDS words): the meta words in front, then what comes down beside them
-enum { HM_POFF = 32 /* a block's poff[0..nb], 16 words */, HM_PBASE_END = 48 /* a table's pbase[nsub], the end of its packed layout */, HM_WORDS = 64 };
+enum { HM_POFF = 32 /* a block's poff[0..nb], 16 words */, HM_PBASE_END = 48 /* a table's pbase[nsub], the end of its packed layout */,
+       HM_MIX = 50 /* the adaptive model's chains and the longest of them, 2 words */, HM_WORDS = 64 };
 static_assert(DM_COUNT <= HM_POFF, "hmeta: the meta words end where the offsets begin");
 
 struct DcSub { u32 nb; u32 first[9]; u32 maxr[8]; };           // run index range (first[nb] = m) and max_rank of each sub-block
@@ -170,6 +172,17 @@ struct DevCoder {
     // a block in sub-block segments (devcoder_block_begin), allocated on its first use: decisions and undecided flags of its eight sub-blocks
     DcArena blk_arena;
     u32 *blk_dec = nullptr, *blk_und = nullptr;
+    // the adaptive coder's model of a pass (devcoder_adaptive_batch), allocated on its first use: two key buffers of the chain-major
+    // sort (8 bytes per decision each) and the four debug planes (8) — 24 bytes per decision, 96 per byte of max_n — plus the tables
+    // (stretch, squash, the mixers' parameters, the adaptive rates).  Everything else the stage needs lives in arrays of the main
+    // arena that are dead behind the static model's stream kernel (pos[0..3], inv_sr).
+    DcArena mix_arena;
+    u64 *mix_key[2] = {nullptr, nullptr};
+    u16 *mix_dbg = nullptr;                                    // [4][D]: state, char, static counter values, mixer id
+    u32 *mix_meta = nullptr;                                   // MX_*
+    short *mix_tab = nullptr;                                  // stretch[MX_TAB], squash[MX_TAB]
+    MixParams *mix_mp = nullptr;                               // [NUM_CLS]
+    ModelParams *mp_adapt = nullptr;                           // device copy (adaptive coder's counters)
 };
 
 __device__ __forceinline__ u32 dc_sb_of(u32 j, const DcSub& S)
@@ -2092,7 +2105,7 @@ static bool dc_arena_alloc(DcArena& a, const Carve (&carve)[N], const char* fail
 // Everything a DevCoder owns, whether it is the context's or one whose set-up did not get that far.
 static void dc_free(DevCoder* d)
 {
-    for (DcArena* a : {&d->arena, &d->batch_arena, &d->avg_arena, &d->rp_arena, &d->hist_arena, &d->blk_arena}) if (a->base) (void)hipFree(a->base);
+    for (DcArena* a : {&d->arena, &d->batch_arena, &d->avg_arena, &d->rp_arena, &d->hist_arena, &d->blk_arena, &d->mix_arena}) if (a->base) (void)hipFree(a->base);
     for (int k = 0; k < 2; ++k) if (d->seg_ev[k]) (void)hipEventDestroy(d->seg_ev[k]);
     if (d->hmeta) (void)hipHostFree(d->hmeta);
     delete d;
@@ -2209,7 +2222,7 @@ int devcoder_ensure(bscgpu_ctx* c)
 }
 
 int64_t devcoder_arena_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)c->dc->arena.bytes : 0; }
-int64_t devcoder_batch_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)(c->dc->batch_arena.bytes + c->dc->avg_arena.bytes + c->dc->rp_arena.bytes + c->dc->hist_arena.bytes + c->dc->blk_arena.bytes) : 0; }
+int64_t devcoder_batch_bytes(const bscgpu_ctx* c) { return c->dc ? (int64_t)(c->dc->batch_arena.bytes + c->dc->avg_arena.bytes + c->dc->rp_arena.bytes + c->dc->hist_arena.bytes + c->dc->blk_arena.bytes + c->dc->mix_arena.bytes) : 0; }
 
 // One partition job: counts, scans, scatter.  SCATTER = false: counts and scans only, then the runs' offsets in the stream
 // (dc_doff_kernel) — all the fast coder needs of job 0, whose events nobody reads.
@@ -2289,11 +2302,11 @@ static bool devcoder_hist_ensure(DevCoder* d)
 // The context states of m runs (1c), and with the resolve behind them (1c').  No sync: the resolve's kernels are launched whether or
 // not a run is open, and leave at once where none is.
 template <class SB>
-static int dc_launch_ctx(bscgpu_ctx* c, DevCoder* d, u32 m, const SB& S)
+static int dc_launch_ctx(bscgpu_ctx* c, DevCoder* d, u32 m, const SB& S, bool always_exact = false)
 {
     const u32 gm8 = ((m + WG - 1) / WG + 7u) / 8u * 8u;                // (dc_virtual_block())
     // (buffers that do not fit: the option stays without effect — dc_ctx_kernel<SB> with its look-back, as with the option off; not an error)
-    if (!(c->dc_hist_exact && devcoder_hist_ensure(d))) {
+    if (!((c->dc_hist_exact || always_exact) && devcoder_hist_ensure(d))) {
         hipLaunchKernelGGL(dc_ctx_kernel<SB>, dim3(gm8), dim3(WG), 0, c->stream, d->key_ch, d->key_ch_s, d->inv_ch, m, S, d->tab_rank, d->tab_run,
                            d->key_sr, d->key_sn, d->present, d->meta, DcHistNoRec{});
         return BSC_NO_ERROR;
@@ -2437,6 +2450,7 @@ struct DcUnit {
     int psbuf;                  // the device p stream written: ps[psbuf & 1]
     int64_t expect;             // >= 0: the decisions the plan counted for these sub-blocks — the families' totals must equal it
     bool ctx_open;              // the caller's contexts bracket of the profile is still open and takes the items as well (a single block)
+    const ModelParams* mp = nullptr;   // the adaptive coder's counters (device copy): dc_static_run with these rates, the run_hist resolve always on
 };
 // What comes back, and where what comes down to the host goes.  Written on success only.
 struct DcOut {
@@ -2455,6 +2469,7 @@ static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const DcUnit& 
     constexpr bool TAB = DcForm<SB>::TAB;
     const u32 m = U.m;
     const int psbuf = U.psbuf; u16* const dbg = O.dbg;
+    const ModelParams* const mp = U.mp ? U.mp : d->mp;
     const u32 gm = (m + WG - 1) / WG;
     const u32 gm8 = (gm + 7u) / 8u * 8u;            // kernels that use dc_virtual_block()
     if (!U.ctx_open) prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
@@ -2466,7 +2481,7 @@ static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const DcUnit& 
     int rc = radix_sort_passes(c, d->key_ch, d->key_ch_s, nullptr, nullptr, m, &top, 1, &in_alt, d->inv_ch);
     if (rc < 0) return rc;
     prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * 40, m);
-    rc = dc_launch_ctx(c, d, m, S);                 // (with BSCGPU_OPT_DC_HIST_EXACT: and the resolve of the open run_hist brackets, 1c')
+    rc = dc_launch_ctx(c, d, m, S, U.mp != nullptr);   // (with BSCGPU_OPT_DC_HIST_EXACT: and the resolve of the open run_hist brackets, 1c')
     if (rc < 0) { prof_end(c); return rc; }
     hipLaunchKernelGGL(dc_setup_kernel<SB>, dim3(1), dim3(WG), 0, c->stream, d->present, S, d->rounds, d->meta,
                        (u32)(c->dc_avg_exact ? DM_AVG_LEFT : DM_AVG_UND));
@@ -2494,7 +2509,7 @@ static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const DcUnit& 
     if (Efull != E[1] || Efull != E[2] + E[3]) return ctx_fail(c, BSC_GPU_ERROR, "device coder: decision counts of the families differ", hipSuccess);
     if (U.expect >= 0 && (int64_t)Efull != U.expect) return ctx_fail(c, BSC_GPU_ERROR, "device coder: a segment's decisions differ from the plan's count", hipSuccess);
     const int fam[4] = {FAM_STATIC, FAM_CHAR, FAM_STATE, FAM_STATE};
-    rc = dc_eval(c, d, E, fam, d->mp, DcForm<SB>::TAB);
+    rc = dc_eval(c, d, E, fam, mp, DcForm<SB>::TAB);
     if (rc < 0) return rc;
 
     DcGather G;
@@ -2526,7 +2541,7 @@ static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const DcUnit& 
     }
     if (packed) {
         // (d->frag holds two records for each of the gm8 * WAVES <= m / 64 + 32 wavefronts: (Mcap + 64) / 64 + 64 pairs, m <= Mcap)
-        hipLaunchKernelGGL((dc_pstream_kernel<false, true, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
+        hipLaunchKernelGGL((dc_pstream_kernel<false, true, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
         hipLaunchKernelGGL(dc_p13_join_kernel, dim3((gm8 * WAVES + WG - 1) / WG), dim3(WG), 0, c->stream, d->frag, gm8 * WAVES, Q.out, d->meta);
         if constexpr (TAB) {
             hipLaunchKernelGGL(dc_p13_fill_tab_kernel, dim3((S.nsub + WG - 1) / WG), dim3(WG), 0, c->stream, d->poff_tab, d->pbase_tab, S.nsub, Q.out, d->meta);
@@ -2535,7 +2550,7 @@ static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const DcUnit& 
             if (O.pbase_host) HIP_TRY(c, hipMemcpyAsync(O.pbase_host, d->pbase_tab, ((size_t)S.nsub + 1) * 4, hipMemcpyDeviceToHost, c->stream));
         }
     }
-    if (!packed) hipLaunchKernelGGL((dc_pstream_kernel<false, false, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
+    if (!packed) hipLaunchKernelGGL((dc_pstream_kernel<false, false, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
     prof_end(c);
     rc = dc_meta_down(c, d, dc_poff_down(d, S, true, O.poff_host));
     if (rc < 0) return rc;
@@ -2544,7 +2559,7 @@ static int dc_static_run(bscgpu_ctx* c, DevCoder* d, const SB& S, const DcUnit& 
         // segment's) stream in the 2-byte form
         packed = false;
         prof_begin(c, BSCGPU_K_DC_PSTREAM, (u64)Efull * 26, Efull);
-        hipLaunchKernelGGL((dc_pstream_kernel<false, false, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, d->mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
+        hipLaunchKernelGGL((dc_pstream_kernel<false, false, SB>), dim3(gm8), dim3(WG), 0, c->stream, G, S, mp, d->meta, d->ps[psbuf & 1], dbg, Efull, Q);
         prof_end(c);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, ctx_sync(c));
@@ -2836,7 +2851,254 @@ static int dc_pass_tables(bscgpu_ctx* c, const DcPass& P, u32 m, bool fast, u32*
     return BSC_NO_ERROR;
 }
 
-// Probability stream of a whole pass, coder 1 (dc_static_run) or 3 (dc_fast_run) -> every sub-block's entries back to back in stream
+// ---- the adaptive coder's model of a pass (-e2; DESIGN §2b, "The adaptive coder's model of a pass") -------------------------------
+// dc_static_run with the adaptive rates leaves, per decision in stream order, the three counter values (the debug planes) and the
+// coded bit with the run-start mark (the stream's entries; their blended probability is not used).  What is left is the mixer: one of
+// NUM_MIX instances per sub-block picks the probability, and an instance only ever sees its own decisions — a chain (sub-block,
+// mixer id).  A pass of small blocks has ~10^5 such chains, the longest a few 10^4 steps:
+//   (a) dc_mix_hist_kernel   rank_hist and the UNCLAMPED run_hist of every run (run_exp is indexed by the full value; the static
+//                            model's contexts keep min(run_hist, 7)): a workgroup per sub-block, a thread per symbol, the sub-block's
+//                            runs through LDS — exact by construction, no bracket
+//       dc_mix_key_kernel    thread per run: key = (sub-block << 11 | mixer id) << 32 | stream position of every decision
+//   (b) radix passes         stable, keys only, on the 11 + log2(nsub) key bits above bit 32: chain-major order, the permutation in the
+//                            keys' low words
+//   (c) dc_mix_gather_kernel thread per decision in chain-major order: its 8-byte record (counter values, bit, run-start mark) next
+//                            to its key; the last decision of a chain finds the chain's first by bisection and notes (start, length)
+//       dc_mix_place_kernel  the chains by descending bsr(length), so that the 64 lanes of a wavefront walk chains of similar length
+//   (d) dc_mix_walk_kernel   one lane per chain: weights in registers, the 17-cell map in an LDS row of its own, stretch / squash
+//                            shared in LDS; the probabilities in chain-major order
+//       dc_mix_scatter_kernel  thread per decision: the entry {p, bit, run start} to the decision's stream position
+// Guard: the longest chain above the context's step cap (BSC_DC_MIX_CHAIN_CAP) declines the pass, FAIL_MIX.
+enum { MX_CNT = 0 /* chains per bsr(length), 32 */, MX_OFF = 32 /* first slot of each, 32 */, MX_FILL = 64 /* 32 */, MX_CHAINS = 96, MX_LONGEST = 97, MX_WORDS = 128 };
+constexpr int MX_TAB = 4104;                                          // shorts per table (4097, padded to 16 bytes)
+constexpr int MX_MAP_STRIDE = 18;                                     // shorts per lane's map row: 9 words, odd against bank conflicts
+
+__global__ __launch_bounds__(WG) void dc_mix_hist_kernel(const u64* __restrict__ key_ch, DcSubTab S, u16* __restrict__ hist)
+{
+    static_assert(WG == 256, "a thread per symbol");
+    __shared__ u32 s_it[WG], s_run[WG];
+    const u32 s = blockIdx.x, t = threadIdx.x;
+    const u32 r0 = S.run[s], r1 = S.run[s + 1];
+    u32 rh = 0, nh = 0;
+    for (u32 base = r0; base < r1; base += WG) {
+        const u32 n = r1 - base < (u32)WG ? r1 - base : (u32)WG;
+        if (t < n) {
+            const u64 k = key_ch[base + t];
+            const ItemB it = item_unpack_b(k);
+            s_it[t] = item_X(k) | (u32)bsr(it.rank) << 8; s_run[t] = it.run;
+        }
+        __syncthreads();
+        for (u32 i = 0; i < n; ++i) {
+            const u32 v = s_it[i];
+            if ((v & 0xffu) == t) { hist[base + i] = (u16)(rh | nh << 8); rh = v >> 8; nh = run_hist_next(nh, s_run[i]); }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(WG) void dc_mix_key_kernel(const u64* __restrict__ key_ch, const u32* __restrict__ doff_sp, const u16* __restrict__ hist,
+                                                        u32 m, u32 D, u64* __restrict__ key, u16* __restrict__ dbg_id)
+{
+    const u32 j = blockIdx.x * WG + threadIdx.x;
+    if (j >= m) return;
+    const u64 k = key_ch[j];
+    const ItemB it = item_unpack_b(k);
+    const int maxr = (int)it.maxr, c = (int)item_X(k);
+    const int n_rank = count_rank_side(it, maxr), nd = n_rank + count_run_side(it);
+    const u32 b = doff_sp[j], h = hist[j];
+    if ((u64)b + (u32)nd > (u64)D) return;                            // (never: the offsets are sums of the same counts)
+    for (int q = 0; q < nd; ++q) {
+        const u32 id = (u32)nth_mixer(it, maxr, n_rank, q, c, (int)(h & 0xffu), (int)(h >> 8));
+        key[b + q] = (u64)(it.sb << MIX_BITS | id) << 32 | (u64)(b + (u32)q);
+        dbg_id[b + q] = (u16)id;
+    }
+}
+
+// record of a decision in chain-major order: [12:0] state, [25:13] char, [38:26] static counter value, [39] coded bit, [40] run start
+constexpr int MX_PF = 8;                                              // records a lane has in flight ahead of the step that uses them
+__global__ __launch_bounds__(WG) void dc_mix_gather_kernel(const u64* __restrict__ key, u32 D, const u16* __restrict__ dbg, const u16* __restrict__ ps,
+                                                           u64* __restrict__ rec, u32* __restrict__ tmp_start, u32* __restrict__ tmp_len, u32* __restrict__ meta)
+{
+    const u32 i = blockIdx.x * WG + threadIdx.x;
+    if (i >= D) return;
+    const u64 k = key[i];
+    const u32 ck = (u32)(k >> 32), pos = (u32)k < D ? (u32)k : 0u;     // (never clipped: the keys are a permutation of [0, D))
+    const u32 e = ps[pos];
+    rec[i] = (u64)(dbg[pos] & 0x1fffu) | (u64)(dbg[(size_t)D + pos] & 0x1fffu) << 13 | (u64)(dbg[2 * (size_t)D + pos] & 0x1fffu) << 26
+           | (u64)((e >> 12) & 3u) << 39;
+    if (i + 1 < D && (u32)(key[i + 1] >> 32) == ck) return;
+    u32 lo = 0, hi = i;                                               // the first decision of the chain that ends here
+    while (lo < hi) { const u32 mid = (lo + hi) >> 1; if ((u32)(key[mid] >> 32) < ck) lo = mid + 1; else hi = mid; }
+    const u32 len = i + 1 - lo;
+    const u32 slot = atomicAdd(&meta[MX_CHAINS], 1u);
+    tmp_start[slot] = lo; tmp_len[slot] = len;
+    atomicAdd(&meta[MX_CNT + bsr(len)], 1u);
+    atomicMax(&meta[MX_LONGEST], len);
+}
+__global__ void dc_mix_offsets_kernel(u32* __restrict__ meta)
+{
+    if (threadIdx.x != 0) return;
+    u32 off = 0;
+    for (int b = 31; b >= 0; --b) { meta[MX_OFF + b] = off; off += meta[MX_CNT + b]; }
+}
+__global__ __launch_bounds__(WG) void dc_mix_place_kernel(const u32* __restrict__ tmp_start, const u32* __restrict__ tmp_len, u32 nchains, u32* __restrict__ meta,
+                                                          u32* __restrict__ chain_start, u32* __restrict__ chain_len)
+{
+    const u32 q = blockIdx.x * WG + threadIdx.x;
+    if (q >= nchains) return;
+    const u32 len = tmp_len[q], b = (u32)bsr(len);
+    const u32 slot = meta[MX_OFF + b] + atomicAdd(&meta[MX_FILL + b], 1u);
+    if (slot >= nchains) return;                                      // (never: the offsets are sums of the same counts)
+    chain_start[slot] = tmp_start[q]; chain_len[slot] = len;
+}
+
+// A lane's step waits for nothing but its own previous step, and a wavefront's memory instructions touch 64 lines each (every lane is in
+// a chain of its own), so they are kept few: the records of the next MX_PF steps are requested before the current MX_PF are walked, two
+// records per load, and the probabilities of MX_PF steps leave as two 16-byte stores in chain-major order (pout, 4 bytes per decision);
+// dc_mix_scatter_kernel, a thread per decision, then puts every entry at its stream position.  (One step ahead with a store per step,
+// the walk ran at about 1.3 us per step, a load's latency; with eight steps ahead but two loads and a store per step, at 0.7 - 0.9 us.)
+struct __attribute__((packed, aligned(4))) DcMixRec2 { u64 a, b; };
+struct __attribute__((packed, aligned(4))) DcMixOut4 { u32 a, b, c, d; };
+__global__ __launch_bounds__(WG) void dc_mix_walk_kernel(const u64* __restrict__ key, const u64* __restrict__ rec, u32 D,
+                                                         const u32* __restrict__ chain_start, const u32* __restrict__ chain_len, u32 nchains,
+                                                         const short* __restrict__ tab, const MixParams* __restrict__ mixp, u32* __restrict__ pout)
+{
+    static_assert(MX_PF == 8, "two records per load, four probabilities per store");
+    __shared__ short s_stretch[MX_TAB], s_squash[MX_TAB];
+    __shared__ short s_map[WG * MX_MAP_STRIDE];
+    for (u32 x = threadIdx.x; x < (u32)MX_TAB; x += WG) { s_stretch[x] = tab[x]; s_squash[x] = tab[MX_TAB + x]; }
+    __syncthreads();
+    const u32 q = blockIdx.x * WG + threadIdx.x;
+    if (q >= nchains) return;
+    const u32 lo = chain_start[q];
+    u32 len = chain_len[q];
+    if (lo >= D || len == 0u) return;
+    if (len > D - lo) len = D - lo;                                   // (never: a chain lies inside the pass)
+    // (records are read up to 2 MX_PF - 1 past the chain's last, inside the buffer's slack behind D, and not used)
+    u64 rc[MX_PF], rn[MX_PF];
+    auto fetch = [&](u32 at, u64* r) {
+#pragma unroll
+        for (int x = 0; x < MX_PF; x += 2) { const DcMixRec2 v = *reinterpret_cast<const DcMixRec2*>(rec + at + x); r[x] = v.a; r[x + 1] = v.b; }
+    };
+    fetch(lo, rc);
+    const MixParams P = mixp[mixer_class((int)((u32)(key[lo] >> 32) & ((1u << MIX_BITS) - 1u)))];
+    short* map = s_map + threadIdx.x * MX_MAP_STRIDE;
+    int32_t w0 = 2048 << 5, w1 = 2048 << 5, w2 = 0;
+    for (int p = 0; p < 17; ++p) map[p] = s_squash[2048 + (p - 8) * 256];
+    for (u32 i = 0; i < len; i += MX_PF) {
+        fetch(lo + i + MX_PF, rn);
+        u32 out[MX_PF];
+#pragma unroll
+        for (int x = 0; x < MX_PF; ++x) {
+            const u64 r = rc[x];
+            out[x] = 0;
+            if (i + (u32)x < len)
+                out[x] = (u32)mixer_step_on(w0, w1, w2, map, P, (const short*)s_stretch, (const short*)s_squash, (int)((u32)(r >> 13) & 0x1fffu), (int)((u32)r & 0x1fffu),
+                                            (int)((u32)(r >> 26) & 0x1fffu), (u32)(r >> 39) & 1u);
+        }
+        u32* o = pout + lo + i;
+        if (i + MX_PF <= len) {
+            *reinterpret_cast<DcMixOut4*>(o) = DcMixOut4{out[0], out[1], out[2], out[3]};
+            *reinterpret_cast<DcMixOut4*>(o + 4) = DcMixOut4{out[4], out[5], out[6], out[7]};
+        } else {
+#pragma unroll
+            for (int x = 0; x < MX_PF; ++x) if (i + (u32)x < len) o[x] = out[x];
+        }
+#pragma unroll
+        for (int x = 0; x < MX_PF; ++x) rc[x] = rn[x];
+    }
+}
+// thread per decision in chain-major order: the mixed probability with the record's bit and run-start mark, to its stream position
+__global__ __launch_bounds__(WG) void dc_mix_scatter_kernel(const u64* __restrict__ key, const u64* __restrict__ rec, const u32* __restrict__ pout, u32 D, u16* __restrict__ ps)
+{
+    const u32 i = blockIdx.x * WG + threadIdx.x;
+    if (i >= D) return;
+    const u32 pos = (u32)key[i];
+    if (pos < D) ps[pos] = (u16)((pout[i] & 0xfffu) | ((u32)(rec[i] >> 39) & 3u) << 12);
+}
+
+// The adaptive stage's buffers and tables, on the first -e2 pass; false: they do not fit (the pass is declined, reason 0).
+static bool devcoder_mix_ensure(bscgpu_ctx* c, DevCoder* d)
+{
+    if (d->mix_arena.base || d->mix_arena.failed) return !d->mix_arena.failed;
+    CtxTimer tm("devcoder_mix_ensure (adaptive model: keys, planes, tables)");
+    const size_t D = d->Dcap + 64;
+    const Carve carve[] = {
+        {(void**)&d->mix_key[0], 8 * D + 65536}, {(void**)&d->mix_key[1], 8 * D + 65536}, {(void**)&d->mix_dbg, 8 * D},
+        {(void**)&d->mix_meta, MX_WORDS * 4}, {(void**)&d->mix_tab, 2 * MX_TAB * sizeof(short)}, {(void**)&d->mix_mp, NUM_CLS * sizeof(MixParams)},
+        {(void**)&d->mp_adapt, sizeof(ModelParams)},
+    };
+    if (!dc_arena_alloc(d->mix_arena, carve, "BSC_DC_MIX_FAIL_ALLOC")) return false;
+    static const ModelParams mpa = [] { ModelParams m; model_params_adaptive(bschost::qlfc_adaptive_params(), m); return m; }();
+    const bschost::QlfcTables& QT = bschost::qlfc_tables();
+    std::vector<short> tab(2 * MX_TAB, 0);
+    memcpy(tab.data(), QT.stretch, sizeof QT.stretch); memcpy(tab.data() + MX_TAB, QT.squash, sizeof QT.squash);
+    MixParams mixp[NUM_CLS];
+    mix_params_from_table(bschost::qlfc_adaptive_params(), mixp);
+    const bool ok = hipMemcpyAsync(d->mp_adapt, &mpa, sizeof mpa, hipMemcpyHostToDevice, c->stream) == hipSuccess
+                 && hipMemcpyAsync(d->mix_tab, tab.data(), tab.size() * sizeof(short), hipMemcpyHostToDevice, c->stream) == hipSuccess
+                 && hipMemcpyAsync(d->mix_mp, mixp, sizeof mixp, hipMemcpyHostToDevice, c->stream) == hipSuccess
+                 && ctx_sync(c) == hipSuccess;                        // (stack objects: the copies must have finished)
+    if (!ok) { (void)hipGetLastError(); (void)hipFree(d->mix_arena.base); d->mix_arena.base = nullptr; d->mix_arena.bytes = 0; d->mix_arena.failed = true; }
+    return ok;
+}
+
+// Behind dc_static_run with the adaptive rates and the debug planes (D decisions in ps[0], their counter values in mix_dbg): the
+// mixers.  One sync of its own: the chains' number and the longest of them.
+static int dc_mix_run(bscgpu_ctx* c, DevCoder* d, const DcSubTab& S, u32 m, u32 D)
+{
+    static_assert(HM_MIX + 2 <= HM_WORDS && sizeof(short) == 2, "hmeta holds the two words");
+    if (D == 0) return BSC_NO_ERROR;
+    u16* const hist = reinterpret_cast<u16*>(d->inv_sr);              // dead behind the stream kernel, as pos[0..3] below
+    u32 *tmp_start = d->pos[0], *tmp_len = d->pos[1], *chain_start = d->pos[2], *chain_len = d->pos[3];
+    u32* pout = d->pos[0];                                            // (the walk's output, behind the placement's last read of tmp_start)
+    HIP_TRY(c, hipMemsetAsync(d->mix_meta, 0, MX_WORDS * 4, c->stream));
+    prof_begin(c, BSCGPU_K_DC_EVAL, (u64)m * 10 + (u64)D * 10, D);
+    hipLaunchKernelGGL(dc_mix_hist_kernel, dim3(S.nsub), dim3(WG), 0, c->stream, d->key_ch, S, hist);
+    hipLaunchKernelGGL(dc_mix_key_kernel, dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, d->key_ch, d->doff[0], hist, m, D, d->mix_key[0], d->mix_dbg + 3 * (size_t)D);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    // (b) the sub-block bits that are set at all and the mixer id: two or three 8-bit passes
+    int sbits = 0;
+    while ((1u << sbits) < S.nsub) ++sbits;
+    const int kbits = MIX_BITS + sbits, npass = (kbits + 7) / 8;
+    RadixPass passes[3];
+    for (int p = 0; p < npass; ++p) { passes[p].shift = 32 + 8 * p; passes[p].bits = kbits - 8 * p < 8 ? kbits - 8 * p : 8; }
+    int in_alt = 0;
+    int rc = radix_sort_passes(c, d->mix_key[0], d->mix_key[1], nullptr, nullptr, D, passes, npass, &in_alt, nullptr, /* aux */ true);
+    if (rc < 0) return rc;
+    const u64* key = d->mix_key[in_alt];
+    u64* rec = d->mix_key[in_alt ^ 1];                                // (the sort's other buffer: dead behind its last pass)
+    prof_begin(c, BSCGPU_K_DC_EVAL, (u64)D * 26, D);
+    hipLaunchKernelGGL(dc_mix_gather_kernel, dim3((D + WG - 1) / WG), dim3(WG), 0, c->stream, key, D, d->mix_dbg, d->ps[0], rec, tmp_start, tmp_len, d->mix_meta);
+    hipLaunchKernelGGL(dc_mix_offsets_kernel, dim3(1), dim3(64), 0, c->stream, d->mix_meta);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(d->hmeta + HM_MIX, d->mix_meta + MX_CHAINS, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    prof_collect(c);
+    const u32 nchains = d->hmeta[HM_MIX], longest = d->hmeta[HM_MIX + 1];
+    c->dc_mix_chains = nchains; c->dc_mix_longest = longest;
+    if (nchains == 0 || nchains > D) return ctx_fail(c, BSC_GPU_ERROR, "device coder (adaptive): chain table", hipSuccess);
+    if (longest > c->dc_mix_cap) { c->dc_note.fail |= (int)FAIL_MIX; return BSC_NOT_SUPPORTED; }
+    const auto walk_t0 = std::chrono::steady_clock::now();             // (the stream is idle: the sync above)
+    prof_begin(c, BSCGPU_K_DC_EVAL, (u64)D * 18, D);
+    hipLaunchKernelGGL(dc_mix_place_kernel, dim3((nchains + WG - 1) / WG), dim3(WG), 0, c->stream, tmp_start, tmp_len, nchains, d->mix_meta, chain_start, chain_len);
+    hipLaunchKernelGGL(dc_mix_walk_kernel, dim3((nchains + WG - 1) / WG), dim3(WG), 0, c->stream, key, rec, D, chain_start, chain_len, nchains,
+                       d->mix_tab, d->mix_mp, pout);
+    hipLaunchKernelGGL(dc_mix_scatter_kernel, dim3((D + WG - 1) / WG), dim3(WG), 0, c->stream, key, rec, pout, D, d->ps[0]);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, ctx_sync(c));
+    c->dc_mix_walk_us = (u32)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - walk_t0).count();
+    prof_collect(c);
+    if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder adaptive] decisions %u, chains %u, longest %u\n", D, nchains, longest);
+    return BSC_NO_ERROR;
+}
+const u16* devcoder_mix_dbg_ptr(const bscgpu_ctx* c) { return c->dc ? c->dc->mix_dbg : nullptr; }
+
+// Probability stream of a whole pass, coder 1 (dc_static_run), 2 (dc_static_run with the adaptive rates, then dc_mix_run) or 3
+// (dc_fast_run) -> every sub-block's entries back to back in stream
 // order in the device p stream (buffer 0), poff[0..nsub] in d->poff_tab.  The same stages, the same kernels as a single block's,
 // instantiated for the table (DcSubTab); every guarded exit keeps its meaning with the PASS as the unit: a raised flag declines the
 // whole pass (BSC_NOT_SUPPORTED, c->dc_note.fail says why).  The arena of devcoder_batch_ensure serves both coders (the fast one uses
@@ -2851,17 +3113,24 @@ int devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* D_out
     if (rc < 0) return rc;
     DevCoder* d = P.d;
     const bool fast = coder == 3;                                      // LIBBSC_CODER_QLFC_FAST
+    const bool adaptive = coder == 2;                                  // LIBBSC_CODER_QLFC_ADAPTIVE
+    if (adaptive && !devcoder_mix_ensure(c, d)) return BSC_NOT_SUPPORTED;   // does not fit: declined, no reason bit (as the batch arena)
     rc = dc_unit_clear(c, d, !fast);
     if (rc < 0) return rc;
     prof_begin(c, BSCGPU_K_DC_CTX, (u64)m * (fast ? 14 : 40), m);
     rc = dc_pass_tables(c, P, m, fast, nullptr);
     prof_end(c);
     if (rc < 0) return rc;
-    const DcUnit U = dc_pass_range(P, 0u, m, 0, -1);
+    DcUnit U = dc_pass_range(P, 0u, m, 0, -1);
     DcOut O;
-    O.take_packed = !fast && packed_out != nullptr;
+    O.take_packed = coder == 1 && packed_out != nullptr;
+    if (adaptive) { U.mp = d->mp_adapt; O.dbg = d->mix_dbg; }
     rc = fast ? dc_fast_run(c, d, P.S, U, O) : dc_static_run(c, d, P.S, U, O);
     if (rc < 0) return rc;
+    if (adaptive) {
+        rc = dc_mix_run(c, d, P.S, m, O.D);
+        if (rc < 0) return rc;
+    }
     *D_out = O.D;
     if (packed_out) *packed_out = O.packed ? 1 : 0;
     if (O.packed && pbytes_out) *pbytes_out = (int64_t)d->hmeta[HM_PBASE_END] / 8 * 13;

@@ -322,6 +322,105 @@ inline void model_params_fast(ModelParams& M)
         }
     }
 }
+// ---- the adaptive coder (-e2, qlfc.cpp:583-819) ------------------------------------------------------------------------------------
+// Its decisions, contexts and three counter families are the static coder's, decision for decision, with the rates of kAdaptiveParams
+// (same 19-column rows: model_params_from_table reads either table).  What differs is the probability: not a fixed blend of the three
+// counter values but the output of a ProbabilityMixer (predictor.h:74-213), one of 1896 instances per sub-block.  Counters never depend
+// on a mixer's output, so a mixer instance is one more independent chain, (sub-block, mixer id), over its decisions in stream order.
+// (columns 16..18 of this table are the mixer's learning rates, not blend weights: the blend is left at zero, so that the static model's
+// stream kernel writes the coded bit and the run-start mark of every decision around an empty probability field)
+inline void model_params_adaptive(const short (*P)[19], ModelParams& M)
+{
+    model_params_from_table(P, M);
+    for (int c = 0; c < NUM_CLS; ++c) M.lr[c][0] = M.lr[c][1] = M.lr[c][2] = 0;
+}
+
+// mixer ids in the order of the reference's member arrays (qlfc_model.h): which instance a decision uses is a pure function of the run
+//   RF  rank[c]                              c: the run's symbol
+//   RE  rank_exp[max(hist, b)][b]            b: 1-based position, hist: rank_hist[c] before this run (0..7)
+//   RM  rank_mant[B]                         B = bsr(rank): one mixer for all nodes of the tree
+//   RP  rank_esc[ctx]                        the tree node
+//   NF  run[c]
+//   NE  run_exp[max(hist, b)][b]             hist: run_hist[c] before this run, NOT clamped to 7 (0..31)
+//   NM  run_mant[bits]                       bits = bsr(run)
+constexpr int MIX_RF = 0, MIX_RE = 256, MIX_RM = 320, MIX_RP = 328, MIX_NF = 584, MIX_NE = 840, MIX_NM = 1864, NUM_MIX = 1896;
+constexpr int MIX_BITS = 11;
+static_assert(NUM_MIX <= (1 << MIX_BITS), "a mixer id fits 11 bits");
+DC_HD int mix_re(int hist, int b) { return MIX_RE + ((hist > b ? hist : b) & 7) * 8 + b; }
+DC_HD int mix_ne(int hist, int b) { return MIX_NE + ((hist > b ? hist : b) & 31) * 32 + b; }
+DC_HD int mixer_class(int id)
+{
+    return id < MIX_RE ? CLS_RF : id < MIX_RM ? CLS_RE : id < MIX_RP ? CLS_RM : id < MIX_NF ? CLS_RP : id < MIX_NE ? CLS_NF : id < MIX_NM ? CLS_NE : CLS_NM;
+}
+// The mixer id of a run's k-th decision (the case analysis of nth_class): c the run's symbol, rank_hist / run_hist the symbol's
+// histories in front of this run (run_hist unclamped).
+DC_HD int nth_mixer(const Item& it, int max_rank, int n_rank, int k, int c, int rank_hist, int run_hist)
+{
+    if (k < n_rank) {
+        const uint32_t rank = it.rank;
+        if (it.ge32) return MIX_RP + (int)((1u << k) | ((rank >> (max_rank + 1 - k)) & ((1u << k) - 1u)));
+        if (k == 0) return MIX_RF + c;
+        const int B = bsr(rank);
+        const int e = (B - 1) + (B < max_rank ? 1 : 0);
+        return k <= e ? mix_re(rank_hist, k) : MIX_RM + B;
+    }
+    const int kk = k - n_rank;
+    if (kk == 0) return MIX_NF + c;
+    const int nb = bsr(it.run);
+    return kk <= nb ? mix_ne(run_hist, kk) : MIX_NM + nb;
+}
+
+// One mixer instance and its step (predictor.h:121-183).  The reference's `int` arithmetic overflows on some inputs; what its binary
+// computes is the two's-complement wrap, so the weighted sum and the weight updates are spelled in uint32_t with the same casts.
+// P: the class's row of kAdaptiveParams — MixParams keeps its columns 12..18.
+struct MixParams { short th0, ar0, th1, ar1, lr0, lr1, lr2, pad; };
+inline void mix_params_from_table(const short (*P)[19], MixParams* out /* [NUM_CLS] */)
+{
+    for (int c = 0; c < NUM_CLS; ++c) {
+        const short* r = P[c == CLS_NM2 ? CLS_NM : c];
+        out[c] = MixParams{r[12], r[13], r[14], r[15], r[16], r[17], r[18], 0};
+    }
+}
+struct MixerState { int32_t w0, w1, w2; short map[17]; };
+DC_HD void mixer_init(MixerState& M, const short* squash)
+{
+    M.w0 = M.w1 = 2048 << 5; M.w2 = 0;
+    for (int p = 0; p < 17; ++p) M.map[p] = squash[2048 + (p - 8) * 256];
+}
+DC_HD int mix_wmul(int a, int b) { return (int)((uint32_t)a * (uint32_t)b); }
+DC_HD short mix_bump(short p, uint32_t bit, const MixParams& P)
+{
+    const int up = ((4096 - P.th0 - p) * P.ar0) >> 12, down = ((p - P.th1) * P.ar1) >> 12;
+    return (short)(p + (bit ? -down : up));
+}
+// the stretched sum, clamped: the index of the squash table and of the interpolated map
+DC_HD int mixer_dot(int s0, int s1, int s2, int w0, int w1, int w2)
+{
+    int d = (short)((int)((uint32_t)mix_wmul(s0, w0) + (uint32_t)mix_wmul(s1, w1) + (uint32_t)mix_wmul(s2, w2)) >> 17);
+    return d < -2047 ? -2047 : d > 2047 ? 2047 : d;
+}
+// p_ch / p_st / p_sp: the char-, state- and position-indexed counter values BEFORE their update; returns the 12-bit probability.
+// The weights and the 17-cell map wherever the caller keeps them (MixerState on the host, registers and an LDS row on the device).
+template <class MapP, class TabP>
+DC_HD int mixer_step_on(int32_t& w0, int32_t& w1, int32_t& w2, MapP map, const MixParams& P, TabP stretch, TabP squash, int p_ch, int p_st, int p_sp, uint32_t bit)
+{
+    const int s0 = stretch[p_ch], s1 = stretch[p_st], s2 = stretch[p_sp];
+    const int d = mixer_dot(s0, s1, s2, w0, w1, w2);
+    const int frac = d & 255, idx = (d + 2048) >> 8;
+    const int m0 = map[idx], m1 = map[idx + 1];
+    const int p = (3 * squash[2048 + d] + m0 + (((m1 - m0) * frac) >> 8)) >> 2;
+    map[idx] = mix_bump((short)m0, bit, P); map[idx + 1] = mix_bump((short)m1, bit, P);
+    const int eps = p - (bit ? 1 : 4095);
+    w0 = (int32_t)((uint32_t)w0 - (uint32_t)(mix_wmul(mix_wmul(P.lr0, eps), s0) >> 16));
+    w1 = (int32_t)((uint32_t)w1 - (uint32_t)(mix_wmul(mix_wmul(P.lr1, eps), s1) >> 16));
+    w2 = (int32_t)((uint32_t)w2 - (uint32_t)(mix_wmul(mix_wmul(P.lr2, eps), s2) >> 16));
+    return p;
+}
+DC_HD int mixer_step(MixerState& M, const MixParams& P, const short* stretch, const short* squash, int p_ch, int p_st, int p_sp, uint32_t bit)
+{
+    return mixer_step_on(M.w0, M.w1, M.w2, (short*)M.map, P, stretch, squash, p_ch, p_st, p_sp, bit);
+}
+
 DC_HD int blend(int v_char, int v_state, int v_static, const short* lr)
 {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -454,7 +454,7 @@ int radix_engine_setup(bscgpu_ctx* c)
 }
 
 int radix_sort_passes(bscgpu_ctx* c, u64* keys, u64* keys_alt, u32* vals, u32* vals_alt, u64 n,
-                      const RadixPass* passes, int npasses, int* in_alt, u32* emit_pos)
+                      const RadixPass* passes, int npasses, int* in_alt, u32* emit_pos, bool aux)
 {
     if (emit_pos != nullptr && (npasses != 1 || vals != nullptr)) return BSC_BAD_PARAMETER;     // inverse of ONE keys-only pass
     *in_alt = 0;
@@ -465,7 +465,7 @@ int radix_sort_passes(bscgpu_ctx* c, u64* keys, u64* keys_alt, u32* vals, u32* v
     const Chunking ch = rs_chunking(n);
     const bool has_val = (vals != nullptr);
     // large (key, value) sorts: one histogram read per sort + single-read digit passes (radix_onesweep.hip; BSC_RS_ONESWEEP)
-    if (emit_pos == nullptr && radix_onesweep_wanted(c, n, npasses, has_val)) {
+    if (emit_pos == nullptr && !aux && radix_onesweep_wanted(c, n, npasses, has_val)) {
         const int rc = radix_onesweep_sort(c, keys, keys_alt, vals, vals_alt, n, passes, npasses);
         if (rc == BSC_NO_ERROR) *in_alt = (npasses & 1);
         return rc;
@@ -487,8 +487,10 @@ int radix_sort_passes(bscgpu_ctx* c, u64* keys, u64* keys_alt, u32* vals, u32* v
     }
 
     // passes that also emit the permutation serve the device coder / the inverse BWT: booked apart from the graded digit passes
-    const int kind_hist = emit_pos ? BSCGPU_K_RADIX_AUX : BSCGPU_K_RADIX_HIST, kind_scan = emit_pos ? BSCGPU_K_RADIX_AUX : BSCGPU_K_RADIX_SCAN,
-              kind_scatter = emit_pos ? BSCGPU_K_RADIX_AUX : BSCGPU_K_RADIX_SCATTER;
+    // (aux: keys-only passes of the device coder that carry their permutation in the key's low bits)
+    const bool book_aux = emit_pos != nullptr || aux;
+    const int kind_hist = book_aux ? BSCGPU_K_RADIX_AUX : BSCGPU_K_RADIX_HIST, kind_scan = book_aux ? BSCGPU_K_RADIX_AUX : BSCGPU_K_RADIX_SCAN,
+              kind_scatter = book_aux ? BSCGPU_K_RADIX_AUX : BSCGPU_K_RADIX_SCATTER;
     for (int p = 0; p < npasses; ++p) {
         const int shift = passes[p].shift;
         const u32 mask  = (passes[p].bits >= 8) ? 0xffu : ((1u << passes[p].bits) - 1u);

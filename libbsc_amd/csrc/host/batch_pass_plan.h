@@ -57,17 +57,19 @@ static inline int batch_pass_end(const int* pass_of, const int* sizes, int count
 }
 
 // ---- the call's route --------------------------------------------------------------------------------------------------------------
-struct BatchOptions { int front, model, model_fast, segments, packed, device_rc; };      // the context's BSCGPU_OPT_* values
+struct BatchOptions { int front, model, model_fast, segments, packed, device_rc, model_adaptive; };      // the context's BSCGPU_OPT_* values
 
 struct BatchRoute {
     bool front;          // the front end of every pass on the GPU (BSCGPU_OPT_BATCH_FRONT): its run arrays come down instead of its L
     bool model;          // ... and the coder's model behind it: the static coder's (BSCGPU_OPT_BATCH_MODEL) or the fast coder's
-    bool fast_model;     // (BSCGPU_OPT_BATCH_MODEL_FAST: an option and counters of its own); -e2 stays on the host
+    bool fast_model;     // (BSCGPU_OPT_BATCH_MODEL_FAST: an option and counters of its own) or the adaptive coder's (adaptive_model, below)
     bool segments;       // ... in model segments (BSCGPU_OPT_BATCH_MODEL_SEGMENTS); with the device's range coder on, a pass takes the whole-pass route
     bool packed;         // ... with the stream in the packed 13-bit form (BSCGPU_OPT_BATCH_MODEL_PACKED): -e1 only, whole passes and segments alike
     bool device_rc;      // a whole pass's streams stay in HBM: one launch of the device's range coder codes them (BSCGPU_OPT_DEVICE_RC)
     int64_t min_pass;    // smallest pass (bytes of L) that is given to the device model
     int64_t segment_target;
+    bool adaptive_model; // the model is the adaptive coder's (BSCGPU_OPT_BATCH_MODEL_ADAPTIVE, -e2: an option and counters of its own): whole passes of
+                         // 16-bit entries that the host codes — no segments, no packed form, no device range coder, whatever those options say
 };
 
 // the front end needs its two pinned run buffers: they are asked for (front_host) only where this holds
@@ -80,12 +82,13 @@ static inline BatchRoute batch_route(int npass, const BatchOptions& o, int coder
     BatchRoute R;
     R.front = batch_wants_front(npass, o) && front_host;
     R.fast_model = R.front && o.model_fast != 0 && coder == LIBBSC_CODER_QLFC_FAST;
-    R.model = R.fast_model || (R.front && o.model != 0 && coder == LIBBSC_CODER_QLFC_STATIC);
-    R.min_pass = R.fast_model ? min_pass_fast : min_pass_static;
-    R.segments = R.model && o.segments != 0 && o.device_rc == 0;
+    R.adaptive_model = R.front && o.model_adaptive != 0 && coder == LIBBSC_CODER_QLFC_ADAPTIVE;
+    R.model = R.fast_model || R.adaptive_model || (R.front && o.model != 0 && coder == LIBBSC_CODER_QLFC_STATIC);
+    R.min_pass = R.fast_model ? min_pass_fast : min_pass_static;         // (-e2: the static coder's until its own sweep is measured)
+    R.segments = R.model && !R.adaptive_model && o.segments != 0 && o.device_rc == 0;
     R.segment_target = R.segments ? segment_target : 0;
-    R.packed = R.model && !R.fast_model && o.packed != 0;
-    R.device_rc = R.model && o.device_rc != 0;
+    R.packed = R.model && !R.fast_model && !R.adaptive_model && o.packed != 0;
+    R.device_rc = R.model && !R.adaptive_model && o.device_rc != 0;
     return R;
 }
 
@@ -136,7 +139,8 @@ static inline BatchModelStep batch_model_step(const BatchRoute& R, int nsub, int
 }
 
 // what a pass adds to the context's counters (BSCGPU_CNT_BATCH_*, BSCGPU_CNT_DEVICE_RC_BLOCKS; the segments' own are the model's)
-struct BatchCounters { int front_passes, l_passes, model_passes, model_declined, fast_passes, fast_declined, packed_passes, packed_void, device_rc; };
+struct BatchCounters { int front_passes, l_passes, model_passes, model_declined, fast_passes, fast_declined, packed_passes, packed_void, device_rc,
+                       adaptive_passes, adaptive_declined; };
 
 enum BatchVerdict { BATCH_PASS_KEPT, BATCH_PASS_HOST, BATCH_PASS_DECLINED, BATCH_PASS_ERROR };
 // A whole-pass model returned mrc with D decisions; pk: what it left is the packed 13-bit form, pbytes of it (else 16-bit entries);
@@ -161,11 +165,11 @@ static inline BatchCounters batch_model_counters(const BatchRoute& R, BatchModel
 {
     BatchCounters d = {};
     if (v == BATCH_PASS_KEPT) {
-        ++(R.fast_model ? d.fast_passes : d.model_passes);
+        ++(R.fast_model ? d.fast_passes : R.adaptive_model ? d.adaptive_passes : d.model_passes);
         if (step == BATCH_MODEL_WHOLE && R.packed) ++(pk ? d.packed_passes : d.packed_void);
         if (step == BATCH_MODEL_WHOLE && R.device_rc) ++d.device_rc;
     }
-    if (v == BATCH_PASS_DECLINED) ++(R.fast_model ? d.fast_declined : d.model_declined);
+    if (v == BATCH_PASS_DECLINED) ++(R.fast_model ? d.fast_declined : R.adaptive_model ? d.adaptive_declined : d.model_declined);
     return d;
 }
 
@@ -173,7 +177,7 @@ static inline BatchCounters batch_model_counters(const BatchRoute& R, BatchModel
 enum BatchSource {
     BATCH_FROM_L,        // its L, by the host coder
     BATCH_FROM_RUNS,     // its run arrays in the pass's layout, by the host model
-    BATCH_FROM_PS16,     // the device model's 16-bit stream of the static coder: the range coder alone
+    BATCH_FROM_PS16,     // the device model's 16-bit stream of the static coder, or the adaptive coder's in the same form: the range coder alone
     BATCH_FROM_PS13,     // ... in the packed 13-bit form
     BATCH_FROM_FAST,     // the fast coder's stream
     BATCH_FROM_DEVICE_RC // the bytes the device's range coder left

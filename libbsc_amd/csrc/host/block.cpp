@@ -1768,6 +1768,12 @@ extern "C" BSCGPU_API int64_t bscgpu_fast_pstream_host(const bscgpu_front_layout
 {
     return pstream_host(Lo, s, out, cap, LIBBSC_CODER_QLFC_FAST);
 }
+// ... for the adaptive coder (-e2): entries in the static coder's form, dbg (optional) [4][cap]
+extern "C" BSCGPU_API int64_t bscgpu_adaptive_pstream_host(const bscgpu_front_layout* Lo, int s, uint16_t* out, int64_t cap, uint16_t* dbg)
+{
+    if (!Lo || s < 0 || s >= Lo->nsub || cap < 0 || (cap > 0 && !out)) return LIBBSC_BAD_PARAMETER;
+    return qlfc_adaptive_pstream_runs(front_view(Lo, s), out, cap, dbg);
+}
 
 static int front_batch_code_stream(const bscgpu_front_layout* Lo, int block, const uint16_t* ps, const uint32_t* poff,
                                    unsigned char* out, int coder, int features)
@@ -1911,6 +1917,17 @@ extern "C" BSCGPU_API int64_t bscgpu_fast_pstream_batch_device(bscgpu_ctx* c, co
                                                                uint16_t* ps, int64_t cap, uint32_t* poff)
 {
     return pstream_batch_device(c, dL, sizes, count, out, ps, cap, poff, LIBBSC_CODER_QLFC_FAST);
+}
+extern "C" BSCGPU_API int64_t bscgpu_adaptive_pstream_batch_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out,
+                                                                   uint16_t* ps, int64_t cap, uint32_t* poff, uint16_t* dbg)
+{
+    const int64_t D = pstream_batch_device(c, dL, sizes, count, out, ps, cap, poff, LIBBSC_CODER_QLFC_ADAPTIVE);
+    if (D <= 0 || D > cap || !dbg) return D;
+    for (int p = 0; p < 4; ++p)                                      // the device's planes are [4][D], the caller's [4][cap]
+        if (hipMemcpyAsync(dbg + (size_t)p * (size_t)cap, devcoder_mix_dbg_ptr(c) + (size_t)p * (size_t)D, (size_t)D * 2, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+            return LIBBSC_GPU_ERROR;
+    if (ctx_sync(c) != hipSuccess) return LIBBSC_GPU_ERROR;
+    return D;
 }
 
 extern "C" BSCGPU_API int64_t bscgpu_static_pstream_batch_packed_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out,
@@ -2251,6 +2268,7 @@ void ctx_count(bscgpu_ctx* c, const BatchCounters& d)
     c->cnt_front_passes += d.front_passes; c->cnt_l_passes += d.l_passes;
     c->cnt_model_passes += d.model_passes; c->cnt_model_declined += d.model_declined;
     c->cnt_model_fast_passes += d.fast_passes; c->cnt_model_fast_declined += d.fast_declined;
+    c->cnt_model_adaptive_passes += d.adaptive_passes; c->cnt_model_adaptive_declined += d.adaptive_declined;
     c->cnt_packed_passes += d.packed_passes; c->cnt_packed_void += d.packed_void; c->cnt_device_rc += d.device_rc;
 }
 
@@ -2481,7 +2499,7 @@ void BatchPass::code_groups(PassOrder& order)
 // the call's route: the context's options and the coder, with the environment's values read per call
 BatchRoute call_route(bscgpu_ctx* c, int npass, int coder)
 {
-    const BatchOptions o = {c->batch_front, c->batch_model, c->batch_model_fast, c->batch_model_segments, c->batch_model_packed, c->device_rc};
+    const BatchOptions o = {c->batch_front, c->batch_model, c->batch_model_fast, c->batch_model_segments, c->batch_model_packed, c->device_rc, c->batch_model_adaptive};
     // the front end needs the two pinned run buffers; without them today's route
     const bool front_host = batch_wants_front(npass, o) && ctx_ensure_front_host(c) == LIBBSC_NO_ERROR;
     return batch_route(npass, o, coder, front_host, batch_model_min_pass(false), batch_model_min_pass(true), batch_model_segment());

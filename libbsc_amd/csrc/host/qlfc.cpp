@@ -17,6 +17,7 @@
 #include <tmmintrin.h>
 
 #include "qlfc_data.inc"
+#include "../device/devcoder_model.h"
 
 namespace bschost {
 
@@ -41,6 +42,7 @@ const QlfcTables& qlfc_tables()
 }
 
 const short (*qlfc_static_params())[19] { return kStaticParams; }
+const short (*qlfc_adaptive_params())[19] { return kAdaptiveParams; }
 
 static inline int bsr32(unsigned x) { return x ? 31 - __builtin_clz(x) : 0; }
 
@@ -917,6 +919,50 @@ int64_t qlfc_static_pstream_runs(const RunView& R, uint16_t* out, int64_t cap)
     const int max_rank = encode_alphabet(R, [](unsigned) {});
     RecordPolicy pol{out, cap};
     (void)walk_model1<false>(R, T, max_rank, *Cn, nullptr, pol);
+    return pol.n;
+}
+
+// The adaptive model's stand-in (-e2): the same walk with the adaptive counters; the probability of a decision comes from the mixer
+// step that the device shares (devcoder_model.h: mixer_step), the instance from the walker's own Mixer slot — Mixers1 lists its members
+// in mixer-id order, so the slot's index IS the id.  Entries in the static coder's 16-bit form; dbg (optional, [4][cap]): the state-,
+// char- and position-indexed counter values before their update, and the mixer id, behind every decision.
+namespace {
+struct RecordPolicyAdaptive {
+    uint16_t* out; int64_t cap; uint16_t* dbg; const QlfcTables& T; const Mixer* base; dcm::MixerState* mix; const dcm::MixParams* mp;
+    int64_t n = 0; unsigned first = 0;
+    struct Live {};
+    inline bool begin_run() { first = 1u << 13; return true; }
+    inline Live enter() { return Live(); }
+    inline void leave(const Live&) {}
+    template <int CLS> BSC_ALWAYS_INLINE void decide(Live&, unsigned bit, short& st, short& ch, short& sp, Mixer* mx)
+    {
+        const int p_ch = ch, p_st = st, p_sp = sp;
+        (void)static_step<CLS, true>(bit, st, ch, sp);
+        const int id = (int)(mx - base);
+        const int p = dcm::mixer_step(mix[id], mp[CLS], T.stretch, T.squash, p_ch, p_st, p_sp, bit);
+        if (n < cap) {
+            out[n] = (uint16_t)((unsigned)p | (bit << 12) | first);
+            if (dbg) { dbg[n] = (uint16_t)p_st; dbg[cap + n] = (uint16_t)p_ch; dbg[2 * cap + n] = (uint16_t)p_sp; dbg[3 * cap + n] = (uint16_t)id; }
+        }
+        ++n; first = 0;
+    }
+};
+static_assert(sizeof(Mixers1) == dcm::NUM_MIX * sizeof(Mixer), "Mixers1 is the mixer-id space");
+}
+int64_t qlfc_adaptive_pstream_runs(const RunView& R, uint16_t* out, int64_t cap, uint16_t* dbg)
+{
+    if (R.nsym <= 0) return BAD_PARAMETER;
+    const QlfcTables& T = qlfc_tables();
+    Counters1* Cn = tl_counters();
+    static const Mixers1 slots{};                            // never read: the walker only forms addresses inside it
+    static dcm::MixParams mp[dcm::NUM_CLS];
+    static const bool mp_ok = (dcm::mix_params_from_table(kAdaptiveParams, mp), true);
+    (void)mp_ok;
+    std::unique_ptr<dcm::MixerState[]> mix(new dcm::MixerState[dcm::NUM_MIX]);
+    for (int i = 0; i < dcm::NUM_MIX; ++i) dcm::mixer_init(mix[i], T.squash);
+    const int max_rank = encode_alphabet(R, [](unsigned) {});
+    RecordPolicyAdaptive pol{out, cap, dbg, T, reinterpret_cast<const Mixer*>(&slots), mix.get(), mp};
+    (void)walk_model1<true>(R, T, max_rank, *Cn, const_cast<Mixers1*>(&slots), pol);
     return pol.n;
 }
 

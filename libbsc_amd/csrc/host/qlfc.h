@@ -32,6 +32,8 @@ struct QlfcTables {
 const QlfcTables& qlfc_tables();
 // tuned constants of the static model, one row per decision class (layout: tools/gen_qlfc_data.py)
 const short (*qlfc_static_params())[19];
+// ... and of the adaptive model (same layout; columns 12..18 are its mixer's map rates and learning rates)
+const short (*qlfc_adaptive_params())[19];
 
 // Run decomposition of a sub-block + QLFC ranks, as flat arrays (the layout the GPU front end produces):
 //   sym[j], start[j] : symbol and start position of the j-th maximal run (length = start[j+1] - start[j], the
@@ -81,6 +83,9 @@ void qlfc_pack_p13(const uint16_t* ps, size_t count, uint8_t* out);
 // cap are counted only).
 int64_t qlfc_static_pstream_runs(const RunView& R, uint16_t* out, int64_t cap);
 int64_t qlfc_fast_pstream_runs(const RunView& R, uint16_t* out, int64_t cap);
+// ... of the adaptive model (-e2), in the static coder's entry form; dbg (optional, [4][cap]): the state / char / static counter values
+// and the mixer id behind every decision
+int64_t qlfc_adaptive_pstream_runs(const RunView& R, uint16_t* out, int64_t cap, uint16_t* dbg);
 // Encode one sub-block (what coder.cpp:61 dispatches to).  Returns bytes written or NOT_COMPRESSIBLE.
 int qlfc_encode_block(const uint8_t* in, uint8_t* out, int in_size, int out_size, int coder);
 // Decode one sub-block; returns the decoded size or an error.

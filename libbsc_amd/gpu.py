@@ -322,6 +322,22 @@ class GpuContext:
             raise GpuError(-2, f"{D} decisions exceed the buffer of {cap}")
         return fb, out[:D], poff[:fb.nsub + 1]
 
+    def adaptive_pstream_batch(self, dL, sizes, dbg=False):
+        """bscgpu_adaptive_pstream_batch_device: static_pstream_batch for the adaptive coder (-e2) -> (FrontBatch, entries np.uint16[D]
+        in the static coder's form, poff np.uint32[nsub + 1]); dbg=True: a fourth item, planes np.uint16[4][D] (state / char / static
+        counter values and the mixer id per decision); raises GpuError -4 when the device declines the pass"""
+        fb = FrontBatch(sizes)
+        cap = 4 * int(self.max_n) + 65536                       # the device model's own capacity in decisions
+        out = np.empty(cap, np.uint16)
+        planes = np.zeros((4, cap), np.uint16) if dbg else None
+        poff = np.zeros(2 * fb.count + 2, np.uint32)
+        D = int(self.L.bscgpu_adaptive_pstream_batch_device(self.h, _dptr(dL), N.np_ptr(fb.sizes), fb.count, C.byref(fb.lay), N.np_ptr(out), cap,
+                                                            N.np_ptr(poff), N.np_ptr(planes) if dbg else None))
+        self._check(D)
+        if D > cap:
+            raise GpuError(-2, f"{D} decisions exceed the buffer of {cap}")
+        return (fb, out[:D], poff[:fb.nsub + 1]) + ((planes[:, :D],) if dbg else ())
+
     def model_segment_facts(self, dL, sizes, coder=1):
         """bscgpu_model_segment_facts_device: front end of a pass and what the segment plan is made of -> (FrontBatch, sub_dec
         np.uint32[nsub]: decisions of every sub-block for `coder`, sub_und np.uint32[nsub]: its undecided avg_rank flags)"""
@@ -409,7 +425,9 @@ class GpuContext:
     OPT_DEVICE_RC, CNT_DEVICE_RC_BLOCKS = 12, 13       # a device-model block's streams are range-coded on the GPU (default 0) and how many were
     OPT_BATCH_MODEL, CNT_BATCH_MODEL_PASSES, CNT_BATCH_MODEL_DECLINED = 14, 15, 16    # the static coder's model of a compress-batch pass on the GPU
     OPT_BATCH_MODEL_FAST, CNT_BATCH_FAST_PASSES, CNT_BATCH_FAST_DECLINED = 17, 18, 19    # ... the fast coder's (-e0), an option of its own
-    OPT_BWT_FOLD, CNT_BWT_FOLDED = 20, 21              # key packing sorts the first-sort key's leftover low bits (default 1) and how many sorts took that route
+    OPT_BATCH_MODEL_ADAPTIVE, CNT_BATCH_ADAPTIVE_PASSES, CNT_BATCH_ADAPTIVE_DECLINED = 38, 39, 40    # ... the adaptive coder's (-e2), an option of its own
+    CNT_DC_MIX_CHAINS, CNT_DC_MIX_LONGEST, CNT_DC_MIX_WALK_US = 41, 42, 43     # mixer chains of the last -e2 pass on the device model, the steps of the longest, its walk's wall time (get only)
+    OPT_BWT_FOLD, CNT_BWT_FOLDED = 20, 21            # key packing sorts the first-sort key's leftover low bits (default 1) and how many sorts took that route
     # a model pass in segments (default 0), segments kept, halves run again, blocks that ended on the host model; the model's capacity in decisions
     OPT_BATCH_MODEL_SEGMENTS, CNT_BATCH_SEGMENTS, CNT_BATCH_SEG_RERUNS, CNT_BATCH_SEG_HOST_BLOCKS, CNT_DC_DCAP = 22, 23, 24, 25, 26
     CNT_DC_REPLAYS, CNT_DC_LAST_FAIL, CNT_DC_AVG_UNDECIDED, CNT_DC_HIST_EXTENDED = 5, 6, 7, 8      # the last device-model block (get only)
@@ -418,7 +436,7 @@ class GpuContext:
     OPT_DC_HIST_EXACT, CNT_DC_HIST_RESOLVED = 34, 35    # open run_hist brackets resolved exactly on the device; runs that settled (get only)
     # the device model's arena carved for max_n / k (1, 2, 4, 8; a block above it runs in sub-block segments); segments of the last block (get only)
     OPT_DC_ARENA_DIV, CNT_DC_BLOCK_SEGMENTS = 36, 37
-    DC_FAIL_AVG, DC_FAIL_HIST, DC_FAIL_CAP, DC_FAIL_REPLAY = 2, 4, 8, 16                         # BSCGPU_DC_FAIL_*
+    DC_FAIL_AVG, DC_FAIL_HIST, DC_FAIL_CAP, DC_FAIL_REPLAY, DC_FAIL_MIX = 2, 4, 8, 16, 32          # BSCGPU_DC_FAIL_*
 
     def option_set(self, key, value):
         return self._check(self.L.bscgpu_option_set(self.h, key, value))
@@ -593,6 +611,21 @@ def fast_pstream_host(fb, s):
         out = np.empty(n, np.uint16)
         n = int(N.lib().bscgpu_fast_pstream_host(C.byref(fb.lay), int(s), N.np_ptr(out), n))
     return out[:n]
+
+
+def adaptive_pstream_host(fb, s, dbg=False):
+    """bscgpu_adaptive_pstream_host: GpuContext.adaptive_pstream_batch's CPU stand-in for sub-block s of a FrontBatch (no GPU): the host
+    model's walk with the adaptive counters and the mixer step the device uses, recording {[11:0] p, [12] bit, [13] run start} ->
+    np.uint16 entries; dbg=True: (entries, planes np.uint16[4][n]: state / char / static counter values and the mixer id per decision)"""
+    f = N.lib().bscgpu_adaptive_pstream_host
+    n = int(f(C.byref(fb.lay), int(s), None, 0, None))
+    if n < 0:
+        raise GpuError(n, "bscgpu_adaptive_pstream_host")
+    out = np.empty(max(n, 1), np.uint16)
+    planes = np.zeros((4, max(n, 1)), np.uint16) if dbg else None
+    n2 = int(f(C.byref(fb.lay), int(s), N.np_ptr(out), max(n, 1), N.np_ptr(planes) if dbg else None))
+    assert n2 == n
+    return (out[:n], planes[:, :n]) if dbg else out[:n]
 
 
 def front_batch_code_psf(fb, block, ps, poff, features=3):

@@ -47,6 +47,10 @@ bscgpu_static_pstream_batch_device, wall and the HIP-event time per kernel class
 the front end beside them).  The on legs also run with BSCGPU_OPT_DEVICE_RC = 1 (the pass's streams coded by one launch of the
 device's range coder).  --model-sweep: on against off on passes of 64 KiB .. 16 MiB cut from the workload's text — the smallest pass
 the model route wins on (run it with BSC_BATCH_MODEL_MIN_PASS=0 in the environment).  Raw output belongs under profiles/batch_model/.
+With --coder 2 --model and --model-only drive the adaptive coder's route (BSCGPU_OPT_BATCH_MODEL_ADAPTIVE, -e2,
+bscgpu_adaptive_pstream_batch_device; no device range coder, segments or packed form there); --model-only then also prints the pass's
+mixer chains, the longest chain, the walk's wall time and ns per dependent step, the host coder's wall time for the same pass on 16
+threads, and the chain cap those two give (the steps the walk does in the host's time, rounded down to a power of two).
 With --coder 3 all three drive the fast coder's route instead (BSCGPU_OPT_BATCH_MODEL_FAST, -e0, bscgpu_fast_pstream_batch_device; the
 stage-alone leg adds the pass's decisions per byte from the CPU stand-in); raw output under profiles/batch_fast/.
     python tools/batch_bench.py --model [--model-only | --model-sweep] [--reps 3] [--workloads W1,W2,W3]
@@ -362,12 +366,15 @@ def model_main(args):
     from libbsc_amd.gpu import GpuError, batch_plan
     # --coder 3: the fast coder's route (BSCGPU_OPT_BATCH_MODEL_FAST and its own counters); anything else: the static coder's
     fast = args.coder == 3
-    coder = 3 if fast else 1
+    adaptive = args.coder == 2                                    # the adaptive coder's route: whole passes of 16-bit entries, host-coded
+    coder = 3 if fast else 2 if adaptive else 1
     ctx = GpuContext(0, max_n=(64 << 20) + 4096)
-    OPT = ctx.OPT_BATCH_MODEL_FAST if fast else ctx.OPT_BATCH_MODEL
-    CNT_PASSES = ctx.CNT_BATCH_FAST_PASSES if fast else ctx.CNT_BATCH_MODEL_PASSES
-    CNT_DECLINED = ctx.CNT_BATCH_FAST_DECLINED if fast else ctx.CNT_BATCH_MODEL_DECLINED
-    stage = ctx.fast_pstream_batch if fast else ctx.static_pstream_batch
+    OPT = ctx.OPT_BATCH_MODEL_FAST if fast else ctx.OPT_BATCH_MODEL_ADAPTIVE if adaptive else ctx.OPT_BATCH_MODEL
+    CNT_PASSES = ctx.CNT_BATCH_FAST_PASSES if fast else ctx.CNT_BATCH_ADAPTIVE_PASSES if adaptive else ctx.CNT_BATCH_MODEL_PASSES
+    CNT_DECLINED = ctx.CNT_BATCH_FAST_DECLINED if fast else ctx.CNT_BATCH_ADAPTIVE_DECLINED if adaptive else ctx.CNT_BATCH_MODEL_DECLINED
+    stage = ctx.fast_pstream_batch if fast else ctx.adaptive_pstream_batch if adaptive else ctx.static_pstream_batch
+    if adaptive and (args.segments or args.packed or args.segment_sweep):
+        raise SystemExit("--segments and --packed are not the adaptive coder's (-e2): its passes take the whole-pass 16-bit route")
     if args.segments:                                             # the segmented stage: (layout, entries, poff) as the whole-pass stage returns them
         stage = lambda dL, psz: ctx.pstream_batch_segments(dL, psz, coder, 0)[:3]
     if args.packed and fast:
@@ -494,6 +501,24 @@ def model_main(args):
                                 "p_stream_ms_median_16_bit_vs_packed": [float(np.median(per["p_stream"])), float(np.median(per13["p_stream"]))],
                                 "p_stream_ms_min_max_16_bit": [min(per["p_stream"]), max(per["p_stream"])],
                                 "p_stream_ms_min_max_packed": [min(per13["p_stream"]), max(per13["p_stream"])]})
+                if adaptive:
+                    # what the chain cap's default is derived from: the walk's time per dependent step (its wall time over the longest
+                    # chain) against the host coder's wall time for the same pass, every block from its runs on 16 threads
+                    chains, longest = ctx.option_get(ctx.CNT_DC_MIX_CHAINS), ctx.option_get(ctx.CNT_DC_MIX_LONGEST)
+                    walk_us = []
+                    for _ in range(args.reps):
+                        stage(dL, psz)
+                        walk_us.append(ctx.option_get(ctx.CNT_DC_MIX_WALK_US))
+                    host_ms = []
+                    for _ in range(args.reps):
+                        t0 = time.perf_counter()
+                        run_16(list(range(cnt)), lambda b: fb.code(b, 2, 1))
+                        host_ms.append(round((time.perf_counter() - t0) * 1e3, 1))
+                    ns_step = float(np.median(walk_us)) * 1e3 / max(longest, 1)
+                    steps = float(np.median(host_ms)) * 1e6 / ns_step
+                    rec.update({"mixer_chains": chains, "longest_chain": longest, "walk_us": walk_us, "walk_ns_per_step_of_the_longest_chain": round(ns_step, 1),
+                                "host_coder_ms_16_threads": host_ms, "steps_the_walk_does_in_the_host_time": int(steps),
+                                "chain_cap_power_of_two": 1 << (int(steps).bit_length() - 1)})
                 print(json.dumps({**rec, "runs": fb.m, "sub_blocks": fb.nsub, "decisions": int(ps.size), "replays": ctx.option_get(ctx.CNT_DC_REPLAYS),
                                   "wall_ms_with_front_end_and_copy_out": tw, "kernel_ms": per,
                                   "model_kernel_ms_median": round(float(sum(np.median(v) for k, v in per.items() if k != "front_end")), 3)}), flush=True)
@@ -506,6 +531,8 @@ def model_main(args):
                 ctx.compress_batch(blocks[:40], 1, coder)
             legs = {"batch_on": (1, False, 0), "batch_off": (0, False, 0), "batch_on_device_rc": (1, False, 1),
                     "batch_device_on": (1, True, 0), "batch_device_off": (0, True, 0), "batch_device_on_device_rc": (1, True, 1), "pipe": None}
+            if adaptive:                                           # (the device's range coder does not take this coder's passes)
+                legs = {k: v for k, v in legs.items() if not k.endswith("device_rc")}
             if args.segments:                                      # (option, HBM input, device RC, segments)
                 legs = {"batch_off": (0, False, 0, 0), "batch_on": (1, False, 0, 0), "batch_segments": (1, False, 0, 1),
                         "batch_device_off": (0, True, 0, 0), "batch_device_on": (1, True, 0, 0), "batch_device_segments": (1, True, 0, 1), "pipe": None}
@@ -581,7 +608,7 @@ def main():
     ap.add_argument("--profile-pass", action="store_true", help="with --decode: one decompress_batch per workload and config, nothing timed")
     ap.add_argument("--front", action="store_true", help="BSCGPU_OPT_BATCH_FRONT on against off, interleaved (BWT, --coder)")
     ap.add_argument("--front-only", action="store_true", help="with --front: the front-end stage alone against a loop of the single-block front end")
-    ap.add_argument("--model", action="store_true", help="BSCGPU_OPT_BATCH_MODEL on against off, interleaved (BWT, -e1); with --coder 3: BSCGPU_OPT_BATCH_MODEL_FAST (-e0)")
+    ap.add_argument("--model", action="store_true", help="BSCGPU_OPT_BATCH_MODEL on against off, interleaved (BWT, -e1); with --coder 3: BSCGPU_OPT_BATCH_MODEL_FAST (-e0); with --coder 2: BSCGPU_OPT_BATCH_MODEL_ADAPTIVE (-e2)")
     ap.add_argument("--model-only", action="store_true", help="with --model: the model stage alone on one pass, per kernel class")
     ap.add_argument("--model-sweep", action="store_true", help="with --model: on against off on passes of 64 KiB .. 16 MiB (set BSC_BATCH_MODEL_MIN_PASS=0)")
     ap.add_argument("--segments", action="store_true", help="implies --model: legs model off / on / on + BSCGPU_OPT_BATCH_MODEL_SEGMENTS; with --model-only: the segmented stage")
