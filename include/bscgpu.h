@@ -297,6 +297,9 @@ BSCGPU_API int bscgpu_front_batch_code_psf(const bscgpu_front_layout* layout, in
 BSCGPU_API int64_t bscgpu_adaptive_pstream_batch_device(bscgpu_ctx* ctx, const void* dL, const int* sizes, int count, bscgpu_front_layout* layout,
                                                         uint16_t* out, int64_t cap, uint32_t* poff, uint16_t* dbg);
 BSCGPU_API int64_t bscgpu_adaptive_pstream_host(const bscgpu_front_layout* layout, int s, uint16_t* out, int64_t cap, uint16_t* dbg);
+/* bscgpu_adaptive_longest_chain_host: the same walk, counting: the decisions of every mixer of sub-block s (per_mixer, optional, 1896
+ *   entries) — a sub-block's mixer chains — and, returned, the longest of them.  LIBBSC_BAD_PARAMETER as above. */
+BSCGPU_API int64_t bscgpu_adaptive_longest_chain_host(const bscgpu_front_layout* layout, int s, uint32_t* per_mixer);
 
 /* ---- a pass's model in segments ("Model segments") ------------------------------------------------------------------
  * Sub-blocks are independent chains, so the model of a pass can run over any contiguous range of its sub-blocks and write the same
@@ -328,6 +331,22 @@ BSCGPU_API int bscgpu_model_segment_facts_device(bscgpu_ctx* ctx, const void* dL
                                                  int coder, uint32_t* sub_dec, uint32_t* sub_und);
 BSCGPU_API int64_t bscgpu_pstream_batch_segments_device(bscgpu_ctx* ctx, const void* dL, const int* sizes, int count, bscgpu_front_layout* layout,
                                                         int coder, int64_t target, uint16_t* out, int64_t cap, uint32_t* poff, int* blk_state);
+/* ... for the adaptive coder (-e2; DESIGN §2b, "The adaptive coder's model in segments"); the two above keep refusing coder 2.
+ * bscgpu_adaptive_segment_facts_device: sub_dec and sub_und are the static coder's (same decisions, same flags); sub_mix[s] = the
+ *   longest mixer chain of sub-block s (what bscgpu_adaptive_longest_chain_host returns for it), exact, from one more kernel over the
+ *   run arrays; it means something only where sub_und[s] == 0.  Returns as bscgpu_model_segment_facts_device.
+ * bscgpu_adaptive_pstream_batch_segments_device: bscgpu_pstream_batch_segments_device with the adaptive coder's model: every segment is
+ *   the static model with the adaptive rates and then the mixers' walk over the segment's chains.  The plan has a third rule: a block
+ *   with a sub-block whose longest chain exceeds the step cap (BSC_DC_MIX_CHAIN_CAP) is excluded with BSCGPU_DC_FAIL_MIX and ends the
+ *   segment before it — the cap reads per BLOCK here, per pass in bscgpu_adaptive_pstream_batch_device.  Entries are the 16-bit static
+ *   form; out, poff, blk_state, the re-runs (BSCGPU_DC_FAIL_REPLAY only), the return values and the segment counters are the above's.
+ *   A segment whose chain table disagrees with its sub_mix is LIBBSC_GPU_ERROR.  BSCGPU_CNT_DC_MIX_CHAINS / _LONGEST / _WALK_US then say
+ *   sum / maximum / sum over the pass's kept segments.  Memory: as bscgpu_adaptive_pstream_batch_device; where the mixers' arena does not
+ *   fit, LIBBSC_NOT_SUPPORTED with BSCGPU_CNT_DC_LAST_FAIL = 0. */
+BSCGPU_API int bscgpu_adaptive_segment_facts_device(bscgpu_ctx* ctx, const void* dL, const int* sizes, int count, bscgpu_front_layout* layout,
+                                                    uint32_t* sub_dec, uint32_t* sub_und, uint32_t* sub_mix);
+BSCGPU_API int64_t bscgpu_adaptive_pstream_batch_segments_device(bscgpu_ctx* ctx, const void* dL, const int* sizes, int count, bscgpu_front_layout* layout,
+                                                                 int64_t target, uint16_t* out, int64_t cap, uint32_t* poff, int* blk_state);
 
 /* ---- the packed 13-bit stream of a pass (-e1; DESIGN §2b, "The packed stream of a pass") ------------------------------------------
  * The static coder's stream of a pass in the form bscgpu_qlfc_static_pstream_packed writes for a block, over up to 8192 sub-blocks:
@@ -631,14 +650,23 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          (bscgpu_adaptive_pstream_batch_device's stage); the 16-bit stream comes down and the coder threads run the
  *                          range coder only (bscgpu_front_batch_code_ps).  A pass the device declines (the static model's reasons, or
  *                          BSCGPU_DC_FAIL_MIX) and a pass below BSC_BATCH_MODEL_MIN_PASS (default 16 MiB, -e1's, until measured) take
- *                          the host model.  Segments, the packed form and BSCGPU_OPT_DEVICE_RC do not apply to -e2: with them on such a
- *                          pass takes the whole-pass 16-bit host-coded route.  -e1 and -e0 and their counters are not affected.  Same
+ *                          the host model.  BSCGPU_OPT_BATCH_MODEL_SEGMENTS, the packed form and BSCGPU_OPT_DEVICE_RC do not apply to -e2:
+ *                          with them on such a pass takes the whole-pass 16-bit host-coded route (segments for -e2 have an option of
+ *                          their own, BSCGPU_OPT_BATCH_ADAPTIVE_SEGMENTS).  -e1 and -e0 and their counters are not affected.  Same
  *                          output.  Default 0 (DESIGN §2b has the stage's and the whole calls' figures).
  * BSCGPU_CNT_BATCH_ADAPTIVE_PASSES, BSCGPU_CNT_BATCH_ADAPTIVE_DECLINED  (get only) its passes coded from the device's stream, and declined.
  * BSCGPU_CNT_DC_MIX_CHAINS, BSCGPU_CNT_DC_MIX_LONGEST  (get only) mixer chains of the last -e2 pass given to the device model, and the
- *                          steps of the longest (what BSC_DC_MIX_CHAIN_CAP is compared with).
+ *                          steps of the longest (what BSC_DC_MIX_CHAIN_CAP is compared with); a pass in segments: the sum and the
+ *                          maximum over its kept segments (and _WALK_US below their sum).
  * BSCGPU_CNT_DC_MIX_WALK_US  (get only) the host's wall time, in microseconds, of that pass's walk (chain placement and walk kernels up to
  *                          their sync): divided by the longest chain, the walk's time per dependent step (tools/batch_bench.py).
+ * BSCGPU_OPT_BATCH_ADAPTIVE_SEGMENTS  0 (default) / 1: with BSCGPU_OPT_BATCH_MODEL_ADAPTIVE on and -e2, a pass that takes the model route
+ *                          takes it in model segments (bscgpu_adaptive_pstream_batch_segments_device's stage): a pass above the arena's
+ *                          capacity is cut, not declined, and a block with a mixer chain above the step cap (BSCGPU_DC_FAIL_MIX, per
+ *                          block here) or another of the model's reasons takes the host model alone.  Moves
+ *                          BSCGPU_CNT_BATCH_ADAPTIVE_PASSES / _DECLINED (kept: the device's stream serves any block) and
+ *                          BSCGPU_CNT_BATCH_SEGMENTS / _SEG_RERUNS / _SEG_HOST_BLOCKS.  BSC_BATCH_MODEL_SEGMENT applies.  -e1 and -e0 are
+ *                          not affected, nor is -e2 without BSCGPU_OPT_BATCH_MODEL_ADAPTIVE.  Same output.
  * BSCGPU_OPT_BWT_FOLD      1 (default; BSC_BWT_FOLD=0 in the environment turns it off): where the first-sort key of a single block leaves
  *                          1..4 bits over a whole number of bytes (17..64 symbols) and the sort takes the single-read passes, key
  *                          packing places the records by those bits and counts the byte digits, and the sort is one pass shorter
@@ -698,7 +726,8 @@ enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACK
        BSCGPU_OPT_DC_HIST_EXACT = 34, BSCGPU_CNT_DC_HIST_RESOLVED = 35,
        BSCGPU_OPT_DC_ARENA_DIV = 36, BSCGPU_CNT_DC_BLOCK_SEGMENTS = 37,
        BSCGPU_OPT_BATCH_MODEL_ADAPTIVE = 38, BSCGPU_CNT_BATCH_ADAPTIVE_PASSES = 39, BSCGPU_CNT_BATCH_ADAPTIVE_DECLINED = 40,
-       BSCGPU_CNT_DC_MIX_CHAINS = 41, BSCGPU_CNT_DC_MIX_LONGEST = 42, BSCGPU_CNT_DC_MIX_WALK_US = 43 };
+       BSCGPU_CNT_DC_MIX_CHAINS = 41, BSCGPU_CNT_DC_MIX_LONGEST = 42, BSCGPU_CNT_DC_MIX_WALK_US = 43,
+       BSCGPU_OPT_BATCH_ADAPTIVE_SEGMENTS = 44 };
 /* _FAIL_AVG: undecided avg_rank flags; _FAIL_HIST: a run_hist bracket open after 9216 predecessors (never with
  * BSCGPU_OPT_DC_HIST_EXACT); _FAIL_CAP: more runs or decisions
  * than the context's arena holds; _FAIL_REPLAY: a chain whose bracket stayed open over more than 64 evaluation chunks (with

@@ -108,11 +108,16 @@ def lib():
     L.bscgpu_adaptive_pstream_batch_device.restype = C.c_int64
     L.bscgpu_adaptive_pstream_host.argtypes = [vp, C.c_int, vp, C.c_int64, vp]
     L.bscgpu_adaptive_pstream_host.restype = C.c_int64
+    L.bscgpu_adaptive_longest_chain_host.argtypes = [vp, C.c_int, vp]
+    L.bscgpu_adaptive_longest_chain_host.restype = C.c_int64
     L.bscgpu_front_batch_code_psf.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int]
     L.bscgpu_model_segment_plan.argtypes = [vp, vp, vp, C.c_int, C.c_int64, C.c_int64, vp]
     L.bscgpu_model_segment_facts_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, vp]
     L.bscgpu_pstream_batch_segments_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int64, vp, C.c_int64, vp, vp]
     L.bscgpu_pstream_batch_segments_device.restype = C.c_int64
+    L.bscgpu_adaptive_segment_facts_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    L.bscgpu_adaptive_pstream_batch_segments_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, vp]
+    L.bscgpu_adaptive_pstream_batch_segments_device.restype = C.c_int64
     L.bscgpu_static_pstream_batch_packed_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int64, vp, vp]
     L.bscgpu_static_pstream_batch_packed_device.restype = C.c_int64
     L.bscgpu_pstream_pack13_host.argtypes = [vp, vp, C.c_int, vp, C.c_int64, vp]

@@ -365,6 +365,7 @@ extern "C" int bscgpu_option_set(bscgpu_ctx* c, int key, int value)
     if (key == BSCGPU_OPT_BATCH_MODEL && (value == 0 || value == 1)) { const int old = c->batch_model; c->batch_model = value; return old; }
     if (key == BSCGPU_OPT_BATCH_MODEL_FAST && (value == 0 || value == 1)) { const int old = c->batch_model_fast; c->batch_model_fast = value; return old; }
     if (key == BSCGPU_OPT_BATCH_MODEL_ADAPTIVE && (value == 0 || value == 1)) { const int old = c->batch_model_adaptive; c->batch_model_adaptive = value; return old; }
+    if (key == BSCGPU_OPT_BATCH_ADAPTIVE_SEGMENTS && (value == 0 || value == 1)) { const int old = c->batch_adaptive_segments; c->batch_adaptive_segments = value; return old; }
     if (key == BSCGPU_OPT_BATCH_MODEL_SEGMENTS && (value == 0 || value == 1)) { const int old = c->batch_model_segments; c->batch_model_segments = value; return old; }
     if (key == BSCGPU_OPT_BATCH_MODEL_PACKED && (value == 0 || value == 1)) { const int old = c->batch_model_packed; c->batch_model_packed = value; return old; }
     if (key == BSCGPU_OPT_BWT_FOLD && value >= 0 && value <= 2) { const int old = c->bwt_fold; c->bwt_fold = value; return old; }
@@ -404,6 +405,7 @@ extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
     if (key == BSCGPU_CNT_DC_MIX_CHAINS) return (int)c->dc_mix_chains;
     if (key == BSCGPU_CNT_DC_MIX_LONGEST) return (int)c->dc_mix_longest;
     if (key == BSCGPU_CNT_DC_MIX_WALK_US) return (int)c->dc_mix_walk_us;
+    if (key == BSCGPU_OPT_BATCH_ADAPTIVE_SEGMENTS) return c->batch_adaptive_segments;
     if (key == BSCGPU_OPT_BATCH_MODEL_SEGMENTS) return c->batch_model_segments;
     if (key == BSCGPU_CNT_BATCH_SEGMENTS) return c->cnt_seg;
     if (key == BSCGPU_CNT_BATCH_SEG_RERUNS) return c->cnt_seg_reruns;

@@ -50,7 +50,16 @@ static inline int64_t dc_pack13_host(const uint16_t* ps, const uint32_t* poff, i
 // [blk_sub[b], blk_sub[b + 1]).  A block with an undecided flag or more than dcap decisions is left out (seg_of[b] = -1) and ends the
 // segment before it; an empty block is in no segment and ends nothing; the others fill segments of at most min(dcap, target)
 // decisions (target <= 0: dcap).  -> the number of segments.  blk_sub must not decrease (the exported wrapper checks).
-static inline int dc_segment_plan(const uint32_t* sub_dec, const uint32_t* sub_und, const int* blk_sub, int count, int64_t dcap, int64_t target, int* seg_of)
+// sub_mix (optional, the adaptive coder's third fact): the longest mixer chain of every sub-block, read only where sub_und[s] == 0; a
+// block with a sub-block whose chain exceeds mix_cap is left out like an undecided one.  Null: no such rule.
+static inline bool dc_segment_mix_barred(const uint32_t* sub_und, const uint32_t* sub_mix, int64_t mix_cap, int s0, int s1)
+{
+    if (!sub_mix) return false;
+    for (int s = s0; s < s1; ++s) if (sub_und[s] == 0 && (int64_t)sub_mix[s] > mix_cap) return true;
+    return false;
+}
+static inline int dc_segment_plan(const uint32_t* sub_dec, const uint32_t* sub_und, const int* blk_sub, int count, int64_t dcap, int64_t target, int* seg_of,
+                                  const uint32_t* sub_mix = nullptr, int64_t mix_cap = 0)
 {
     const int64_t limit = target > 0 && target < dcap ? target : dcap;
     int nseg = 0;
@@ -60,7 +69,7 @@ static inline int dc_segment_plan(const uint32_t* sub_dec, const uint32_t* sub_u
         if (blk_sub[b + 1] == blk_sub[b]) { seg_of[b] = -1; continue; }      // empty: ends nothing
         int64_t dec = 0; bool und = false;
         for (int s = blk_sub[b]; s < blk_sub[b + 1]; ++s) { dec += sub_dec[s]; und = und || sub_und[s] != 0; }
-        if (und || dec > dcap) { seg_of[b] = -1; open = false; continue; }
+        if (und || dec > dcap || dc_segment_mix_barred(sub_und, sub_mix, mix_cap, blk_sub[b], blk_sub[b + 1])) { seg_of[b] = -1; open = false; continue; }
         if (!open || filled + dec > limit) { ++nseg; open = true; filled = 0; }
         filled += dec;
         seg_of[b] = nseg - 1;
@@ -83,16 +92,18 @@ struct DcSegTotals { int planned, kept, reruns, host_blocks, kept_packed, kept_v
 
 // Constructed from the facts of a pass; the caller's poff[0..nsub], pbase[0..nsub] (non-null: the packed form, cap and every need in
 // bytes) and blk_state[0..count) are written as the pass goes.  After construction blk_state holds the blocks the plan left out
-// (fail_avg where a sub-block has an undecided flag, else fail_cap: BSCGPU_DC_FAIL_*), planned_need() and copy_all() are known.  Every
-// range with a member ends in exactly one of: next() -> DC_SEG_GIVEN_UP, declined() -> true, kept().
+// (fail_avg where a sub-block has an undecided flag, else fail_cap where its decisions exceed dcap, else fail_mix — mix non-null only: a
+// mixer chain above mix_cap; BSCGPU_DC_FAIL_*), planned_need() and copy_all() are known.  Every range with a member ends in exactly one
+// of: next() -> DC_SEG_GIVEN_UP, declined() -> true, kept().
 class DcSegSchedule {
 public:
     DcSegSchedule(const uint32_t* dec, const uint32_t* und, const int* blk_sub, int count, int nsub, int64_t dcap, int64_t target, int64_t cap,
-                  bool per_segment_fit, int fail_avg, int fail_cap, uint32_t* poff, int64_t* pbase, int* blk_state)
+                  bool per_segment_fit, int fail_avg, int fail_cap, uint32_t* poff, int64_t* pbase, int* blk_state,
+                  const uint32_t* mix = nullptr, int64_t mix_cap = 0, int fail_mix = 0)
         : dec(dec), blk_sub(blk_sub), count(count), nsub(nsub), cap(cap), per_segment_fit(per_segment_fit), fail_cap(fail_cap), poff(poff), pbase(pbase), blk_state(blk_state)
     {
         std::vector<int> seg_of((size_t)count);
-        T.planned = dc_segment_plan(dec, und, blk_sub, count, dcap, target, seg_of.data());
+        T.planned = dc_segment_plan(dec, und, blk_sub, count, dcap, target, seg_of.data(), mix, mix_cap);
         int nblk = 0;
         // the ranges are grown from the right (the stack then yields them in block order): an empty block between two members of a
         // segment lies inside its range, one at its left edge does not — either way it has no sub-block
@@ -101,9 +112,9 @@ public:
             if (!member(b)) continue;                                  // an empty block: nothing to model
             ++nblk;
             if (seg_of[b] < 0) {
-                bool open = false;
-                for (int s = blk_sub[b]; s < blk_sub[b + 1]; ++s) open = open || und[s] != 0;
-                blk_state[b] = open ? fail_avg : fail_cap;
+                bool open = false; int64_t own = 0;
+                for (int s = blk_sub[b]; s < blk_sub[b + 1]; ++s) { open = open || und[s] != 0; own += dec[s]; }
+                blk_state[b] = open ? fail_avg : own > dcap || !mix ? fail_cap : fail_mix;
                 continue;
             }
             need_all += span_need(blk_sub[b], blk_sub[b + 1]);

@@ -187,6 +187,7 @@ struct bscgpu_ctx {
     int  cnt_model_fast_passes = 0, cnt_model_fast_declined = 0;   // BSCGPU_CNT_BATCH_FAST_PASSES / _DECLINED
     // the adaptive coder's (coder 2: the static model with the adaptive rates, then the mixer chains)
     int  batch_model_adaptive = 0;   // BSCGPU_OPT_BATCH_MODEL_ADAPTIVE (default 0: DESIGN §2b, "The adaptive coder's model of a pass")
+    int  batch_adaptive_segments = 0;   // BSCGPU_OPT_BATCH_ADAPTIVE_SEGMENTS (default 0: DESIGN §2b, "The adaptive coder's model in segments")
     int  cnt_model_adaptive_passes = 0, cnt_model_adaptive_declined = 0;   // BSCGPU_CNT_BATCH_ADAPTIVE_PASSES / _DECLINED
     u32  dc_mix_cap = DC_MIX_CHAIN_CAP;   // steps the longest mixer chain of a pass may have (BSC_DC_MIX_CHAIN_CAP, a test knob): above it FAIL_MIX
     u32  dc_mix_chains = 0, dc_mix_longest = 0;   // BSCGPU_CNT_DC_MIX_CHAINS / _LONGEST: the last -e2 pass given to the device model
@@ -418,11 +419,13 @@ const u16* devcoder_mix_dbg_ptr(const bscgpu_ctx* c);
 const u32* devcoder_batch_poff_ptr(const bscgpu_ctx* c);
 const u32* devcoder_batch_pbase_ptr(const bscgpu_ctx* c);
 // ... of a pass in model segments ("Model segments"): the same inputs plus the layout's blk_sub[count + 1] and
-// sub_run[nsub + 1] (host), coder 1 or 3, target decisions per segment (<= 0: the arena's capacity).  out[0 .. cap) (host): the kept
+// sub_run[nsub + 1] (host), coder 1, 2 or 3, target decisions per segment (<= 0: the arena's capacity).  out[0 .. cap) (host): the kept
 // sub-blocks' entries back to back in sub-block order, poff[0..nsub] (host; a sub-block that was not modelled is empty), blk_state[b] =
 // 0 or the BSCGPU_DC_FAIL_* mask that leaves block b to the host model.  per_segment_fit: a segment that no longer fits behind the
 // ones before it is left to the host; else a total above cap is counted, not copied.  *D_out: decisions kept.  BSC_NOT_SUPPORTED: an
 // arena did not fit.  Moves the segment counters of the context.  Synchronous.
+// coder 2: every segment is the static model with the adaptive rates and then the mixers' walk; a block with a mixer chain above
+// c->dc_mix_cap is left out by the plan (FAIL_MIX per BLOCK), c->dc_mix_chains / _longest / _walk_us say sum / maximum / sum of the kept segments.
 // note (or null): told as the pass settles, on the calling thread, so that coding can start before the last segment.  planned(): the
 // plan is known, blk_state holds the excluded blocks.  settled(b0, b1): the blocks of [b0, b1) with a sub-block are final — their
 // entries have landed in out and their poff entries are written, or blk_state gives them to the host.  Every planned block is settled
@@ -436,7 +439,7 @@ int  devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_su
                                void* out, int64_t cap, bool per_segment_fit, u32* poff, int* blk_state, int64_t* D_out,
                                const DcSegNote* note = nullptr, int64_t* pbase = nullptr /* non-null: the packed form, out / cap in bytes */);
 // ... the facts the plan is made of alone: dec[s] / und[s] (host, nsub entries each) of the pass qlfc_front_batch just laid out
-int  devcoder_segment_facts(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* dec, u32* und);
+int  devcoder_segment_facts(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* dec, u32* und, u32* mix = nullptr);   // (mix: coder 2, and only then)
 int64_t devcoder_dcap(const bscgpu_ctx* c);             // decisions the device model's arena holds for this context
 int64_t devcoder_batch_bytes(const bscgpu_ctx* c);      // HBM the batch model added on its first use
 void devcoder_destroy(bscgpu_ctx* c);

@@ -37,7 +37,8 @@
 // The host side drives the stages from ONE body per coder, a template over the form as the kernels are: dc_static_run (-e1) and
 // dc_fast_run (-e0).  devcoder_pstream (a block), devcoder_pstream_batch (a pass) and devcoder_pstream_segments (a pass cut at
 // capacity) hold what differs in front of a body: the sub-blocks' shape, the avg_rank flags, the table's max_rank, the rebased table.
-// The adaptive coder (-e2) of a whole pass is dc_static_run with its own rates and, behind it, one walk per mixer chain (dc_mix_run).
+// The adaptive coder (-e2) of a whole pass, or of a model segment of one, is dc_static_run with its own rates and, behind it, one walk
+// per mixer chain (dc_mix_run); the segment plan of such a pass has a third fact, every sub-block's longest chain (dc_mix_facts_kernel).
 #include "dev_common.h"
 #include "dma_copy.h"
 #include <thread>
@@ -153,7 +154,7 @@ struct DevCoder {
     u8  *sub_maxr = nullptr; u32 *poff_tab = nullptr;
     // model segments (devcoder_pstream_segments): per sub-block the undecided avg_rank flags and the decisions of the coder at hand,
     // and the run table of the segment being modelled, rebased to its first run
-    u32 *sub_und = nullptr, *sub_dec = nullptr, *seg_run = nullptr;
+    u32 *sub_und = nullptr, *sub_dec = nullptr, *seg_run = nullptr, *sub_mix = nullptr;   // (sub_mix: the adaptive coder's third fact, dc_mix_facts_kernel)
     // the packed stream of a pass or a segment (DcP13Tab): pad[s] and pbase[0 .. nsub] of the table at hand (dc_pbase_tab_kernel)
     u32 *pad_tab = nullptr, *pbase_tab = nullptr;
     hipEvent_t seg_ev[2] = {nullptr, nullptr};                 // behind the last copy out of ps[0 / 1] on the copy stream
@@ -2806,7 +2807,7 @@ static bool devcoder_batch_ensure(DevCoder* d)
         {(void**)&d->esub[0], 2 * D}, {(void**)&d->esub[1], 2 * D}, {(void**)&d->esub[2], 2 * D}, {(void**)&d->esub[3], 2 * D},
         {(void**)&d->sub_maxr, (size_t)FRONT_MAX_SUB + 64}, {(void**)&d->poff_tab, 4 * ((size_t)FRONT_MAX_SUB + 64)},
         {(void**)&d->sub_und, 4 * ((size_t)FRONT_MAX_SUB + 64)}, {(void**)&d->sub_dec, 4 * ((size_t)FRONT_MAX_SUB + 64)},
-        {(void**)&d->seg_run, 4 * ((size_t)FRONT_MAX_SUB + 64)},
+        {(void**)&d->seg_run, 4 * ((size_t)FRONT_MAX_SUB + 64)}, {(void**)&d->sub_mix, 4 * ((size_t)FRONT_MAX_SUB + 64)},
         {(void**)&d->pad_tab, 4 * ((size_t)FRONT_MAX_SUB + 64)}, {(void**)&d->pbase_tab, 4 * ((size_t)FRONT_MAX_SUB + 64)},
     };
     return dc_arena_alloc(d->batch_arena, carve, nullptr);
@@ -2894,6 +2895,58 @@ __global__ __launch_bounds__(WG) void dc_mix_hist_kernel(const u64* __restrict__
         }
         __syncthreads();
     }
+}
+
+// The adaptive coder's fact for the segment plan (dc_segment_plan.h): the longest mixer chain of every sub-block, exactly, before any
+// sort or partition — the chains of a sub-block are its decisions by mixer id, so the longest is the maximum of their histogram.
+// dc_mix_hist_kernel's shape: a workgroup per sub-block, its runs through LDS in tiles of WG; the thread that owns a run's symbol carries
+// rank_hist and the unclamped run_hist and leaves them beside the run, then the thread that owns the run builds the item
+// dc_sub_dec_kernel builds (ge32: behind dc_avg_kernel, and behind the exact resolve where that is on) and counts the mixer id of each
+// of its decisions in an LDS histogram.  No global atomics, no scratch.  sub_mix[s] means something only where sub_und[s] == 0.
+constexpr int MX_HIST = 1 << MIX_BITS;                                // counters of the histogram (NUM_MIX of them used): 8 KB
+__global__ __launch_bounds__(WG) void dc_mix_facts_kernel(const u8* __restrict__ sym, const u8* __restrict__ rank, const u32* __restrict__ start,
+                                                          const u8* __restrict__ ge32, u32 m, DcSubTab S, u32* __restrict__ sub_mix)
+{
+    typedef DcForm<DcSubTab> F;
+    static_assert(WG == 256 && NUM_MIX <= MX_HIST, "a thread per symbol");
+    __shared__ u32 s_it[WG], s_run[WG], s_hist[WG], s_cnt[MX_HIST], s_max[WAVES];
+    const u32 s = blockIdx.x, t = threadIdx.x;
+    for (u32 x = t; x < (u32)MX_HIST; x += WG) s_cnt[x] = 0u;
+    const u32 r0 = S.run[s], r1 = S.run[s + 1] < m ? S.run[s + 1] : m;
+    u32 rh = 0, nh = 0;
+    for (u32 base = r0; base < r1; base += WG) {
+        const u32 n = r1 - base < (u32)WG ? r1 - base : (u32)WG;
+        u64 k = 0;
+        if (t < n) {
+            k = F::item(S, sym, rank, start, ge32, base + t, m, 0u);
+            const ItemB it = item_unpack_b(k);
+            s_it[t] = item_X(k) | (u32)bsr(it.rank) << 8; s_run[t] = it.run;
+        }
+        __syncthreads();
+        for (u32 i = 0; i < n; ++i) {
+            const u32 v = s_it[i];
+            if ((v & 0xffu) == t) { s_hist[i] = rh | nh << 8; rh = v >> 8; nh = run_hist_next(nh, s_run[i]); }
+        }
+        __syncthreads();
+        if (t < n) {
+            const ItemB it = item_unpack_b(k);
+            const int maxr = (int)it.maxr, c = (int)item_X(k);
+            const int n_rank = count_rank_side(it, maxr), nd = n_rank + count_run_side(it);
+            const u32 h = s_hist[t];
+            for (int q = 0; q < nd; ++q) {
+                const u32 id = (u32)nth_mixer(it, maxr, n_rank, q, c, (int)(h & 0xffu), (int)(h >> 8));
+                atomicAdd(&s_cnt[id & (u32)(MX_HIST - 1)], 1u);
+            }
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+    u32 mx = 0;
+    for (u32 x = t; x < (u32)MX_HIST; x += WG) mx = s_cnt[x] > mx ? s_cnt[x] : mx;
+    for (int o = 32; o > 0; o >>= 1) { const u32 y = (u32)__shfl_xor((int)mx, o, 64); mx = y > mx ? y : mx; }
+    if ((t & 63u) == 0u) s_max[t >> 6] = mx;
+    __syncthreads();
+    if (t == 0) { for (u32 w = 1; w < (u32)WAVES; ++w) mx = s_max[w] > mx ? s_max[w] : mx; sub_mix[s] = mx; }
 }
 
 __global__ __launch_bounds__(WG) void dc_mix_key_kernel(const u64* __restrict__ key_ch, const u32* __restrict__ doff_sp, const u16* __restrict__ hist,
@@ -3043,9 +3096,10 @@ static bool devcoder_mix_ensure(bscgpu_ctx* c, DevCoder* d)
     return ok;
 }
 
-// Behind dc_static_run with the adaptive rates and the debug planes (D decisions in ps[0], their counter values in mix_dbg): the
-// mixers.  One sync of its own: the chains' number and the longest of them.
-static int dc_mix_run(bscgpu_ctx* c, DevCoder* d, const DcSubTab& S, u32 m, u32 D)
+// Behind dc_static_run with the adaptive rates and the debug planes (D decisions in ps, their counter values in mix_dbg): the
+// mixers.  One sync of its own: the chains' number and the longest of them.  expect_longest >= 0 (a segment): what the plan's facts
+// say the longest chain is — the chain table must agree, as the families' totals must with the plan's decisions.
+static int dc_mix_run(bscgpu_ctx* c, DevCoder* d, const DcSubTab& S, u32 m, u32 D, u16* ps, int64_t expect_longest = -1)
 {
     static_assert(HM_MIX + 2 <= HM_WORDS && sizeof(short) == 2, "hmeta holds the two words");
     if (D == 0) return BSC_NO_ERROR;
@@ -3070,7 +3124,7 @@ static int dc_mix_run(bscgpu_ctx* c, DevCoder* d, const DcSubTab& S, u32 m, u32 
     const u64* key = d->mix_key[in_alt];
     u64* rec = d->mix_key[in_alt ^ 1];                                // (the sort's other buffer: dead behind its last pass)
     prof_begin(c, BSCGPU_K_DC_EVAL, (u64)D * 26, D);
-    hipLaunchKernelGGL(dc_mix_gather_kernel, dim3((D + WG - 1) / WG), dim3(WG), 0, c->stream, key, D, d->mix_dbg, d->ps[0], rec, tmp_start, tmp_len, d->mix_meta);
+    hipLaunchKernelGGL(dc_mix_gather_kernel, dim3((D + WG - 1) / WG), dim3(WG), 0, c->stream, key, D, d->mix_dbg, ps, rec, tmp_start, tmp_len, d->mix_meta);
     hipLaunchKernelGGL(dc_mix_offsets_kernel, dim3(1), dim3(64), 0, c->stream, d->mix_meta);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
@@ -3080,13 +3134,15 @@ static int dc_mix_run(bscgpu_ctx* c, DevCoder* d, const DcSubTab& S, u32 m, u32 
     const u32 nchains = d->hmeta[HM_MIX], longest = d->hmeta[HM_MIX + 1];
     c->dc_mix_chains = nchains; c->dc_mix_longest = longest;
     if (nchains == 0 || nchains > D) return ctx_fail(c, BSC_GPU_ERROR, "device coder (adaptive): chain table", hipSuccess);
+    if (expect_longest >= 0 && (int64_t)longest != expect_longest)
+        return ctx_fail(c, BSC_GPU_ERROR, "device coder (adaptive): a segment's longest chain differs from the plan's", hipSuccess);
     if (longest > c->dc_mix_cap) { c->dc_note.fail |= (int)FAIL_MIX; return BSC_NOT_SUPPORTED; }
     const auto walk_t0 = std::chrono::steady_clock::now();             // (the stream is idle: the sync above)
     prof_begin(c, BSCGPU_K_DC_EVAL, (u64)D * 18, D);
     hipLaunchKernelGGL(dc_mix_place_kernel, dim3((nchains + WG - 1) / WG), dim3(WG), 0, c->stream, tmp_start, tmp_len, nchains, d->mix_meta, chain_start, chain_len);
     hipLaunchKernelGGL(dc_mix_walk_kernel, dim3((nchains + WG - 1) / WG), dim3(WG), 0, c->stream, key, rec, D, chain_start, chain_len, nchains,
                        d->mix_tab, d->mix_mp, pout);
-    hipLaunchKernelGGL(dc_mix_scatter_kernel, dim3((D + WG - 1) / WG), dim3(WG), 0, c->stream, key, rec, pout, D, d->ps[0]);
+    hipLaunchKernelGGL(dc_mix_scatter_kernel, dim3((D + WG - 1) / WG), dim3(WG), 0, c->stream, key, rec, pout, D, ps);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, ctx_sync(c));
@@ -3128,7 +3184,7 @@ int devcoder_pstream_batch(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* D_out
     rc = fast ? dc_fast_run(c, d, P.S, U, O) : dc_static_run(c, d, P.S, U, O);
     if (rc < 0) return rc;
     if (adaptive) {
-        rc = dc_mix_run(c, d, P.S, m, O.D);
+        rc = dc_mix_run(c, d, P.S, m, O.D, d->ps[0]);
         if (rc < 0) return rc;
     }
     *D_out = O.D;
@@ -3150,6 +3206,10 @@ const u32* devcoder_batch_pbase_ptr(const bscgpu_ctx* c) { return c->dc ? c->dc-
 // boundary nearest half its decisions and both halves run again, depth first; a single block that declines is marked with the reason.
 // out / cap: where the kept entries go back to back (host); per_segment_fit: a segment that no longer fits behind the ones before
 // it is left to the host (FAIL_CAP) — else a total above cap is counted, not copied.
+// coder 2 (the adaptive coder): a third fact, the longest mixer chain of every sub-block (dc_mix_facts_kernel), lets the plan leave out
+// a block whose chain exceeds the context's step cap (FAIL_MIX, per BLOCK on this route) before anything runs; every segment is
+// dc_static_run with the adaptive rates and dc_mix_run over the same rebased table, into the segment's ps buffer.  A segment's chain
+// table must report the longest chain its facts promise (BSC_GPU_ERROR otherwise), so FAIL_MIX cannot arise while a segment runs.
 // pbase non-null (coder 1 only): the packed form (DcP13Tab).  out / cap are BYTES then; every kept segment's packed stream lands behind
 // the one before it (a segment's bytes are a whole number of 104-byte sub-block extents), pbase[0..nsub] runs on across the segments in
 // kept order and a sub-block that was not modelled has pbase[s + 1] == pbase[s].  A segment's bytes are known with the plan
@@ -3160,7 +3220,9 @@ const u32* devcoder_batch_pbase_ptr(const bscgpu_ctx* c) { return c->dc ? c->dc-
 // given up, where kept entries land, poff / pbase — is DcSegSchedule's (dc_segment_plan.h); the driver below launches, copies and tells.
 // the facts of a pass (after qlfc_front_batch): dec[s] / und[s] of every sub-block on the host; ge32 and sub_maxr stay for the segments
 // note non-null: its avg_und and avg_resolved are the pass's — the flags the bracket left open, and what the exact resolve settled of them
-static int dc_segment_facts(bscgpu_ctx* c, const DcPass& P, u32 m, bool fast, u32* dec, u32* und, DcNote* note = nullptr)
+// mix non-null (the adaptive coder; dec and und are the static coder's: same decisions, same flags): the longest mixer chain of every
+// sub-block (dc_mix_facts_kernel), down in the same sync
+static int dc_segment_facts(bscgpu_ctx* c, const DcPass& P, u32 m, bool fast, u32* dec, u32* und, DcNote* note = nullptr, u32* mix = nullptr)
 {
     DevCoder* d = P.d;
     const int nsub = (int)P.S.nsub;
@@ -3173,6 +3235,12 @@ static int dc_segment_facts(bscgpu_ctx* c, const DcPass& P, u32 m, bool fast, u3
     if (arc < 0) { prof_end(c); return arc; }
     hipLaunchKernelGGL(dc_sub_dec_kernel, dim3((m + WG - 1) / WG), dim3(WG), 0, c->stream, P.dsym, P.drank, P.dstart, d->ge32, m, P.S, d->sub_dec);
     prof_end(c);
+    if (mix) {
+        prof_begin(c, BSCGPU_K_DC_FACTS, (u64)m * 10, m);
+        hipLaunchKernelGGL(dc_mix_facts_kernel, dim3((u32)nsub), dim3(WG), 0, c->stream, P.dsym, P.drank, P.dstart, d->ge32, m, P.S, d->sub_mix);
+        prof_end(c);
+        HIP_TRY(c, hipMemcpyAsync(mix, d->sub_mix, (size_t)nsub * 4, hipMemcpyDeviceToHost, c->stream));
+    }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(und, d->sub_und, (size_t)nsub * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(dec, d->sub_dec, (size_t)nsub * 4, hipMemcpyDeviceToHost, c->stream));
@@ -3188,12 +3256,13 @@ static int dc_segment_facts(bscgpu_ctx* c, const DcPass& P, u32 m, bool fast, u3
     }
     return BSC_NO_ERROR;
 }
-int devcoder_segment_facts(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* dec, u32* und)
+int devcoder_segment_facts(bscgpu_ctx* c, u32 m, int nsub, int coder, u32* dec, u32* und, u32* mix)
 {
+    if ((coder == 2) != (mix != nullptr)) return BSC_BAD_PARAMETER;
     DcPass P;
     const int rc = dc_pass_begin(c, m, nsub, -1, &P);
     if (rc < 0) return rc;
-    return dc_segment_facts(c, P, m, coder == 3, dec, und);
+    return dc_segment_facts(c, P, m, coder == 3, dec, und, nullptr, mix);
 }
 
 // The copy-outs of kept segments in flight on the copy stream, oldest first: at most one per ps buffer, its end marked by seg_ev[k].
@@ -3229,8 +3298,12 @@ struct DcCopyRing {
 
 // The ranges of the schedule one after the other, launch by launch; out: the landing buffer (host), 2-byte entries or the packed
 // form's bytes (pk).  sum: what the kept and the declined runs counted together (replays, hist_ext and what the two resolves settled).
+// sub_mix non-null: the adaptive coder — dc_static_run with its rates and the debug planes, then the mixers over the same table (the
+// sub-block ids in the mixer key are the segment's own: chains never cross a segment, which is made of whole sub-blocks); mixsum: the
+// chains (sum), the longest (maximum) and the walk's microseconds (sum) of the kept segments.
+struct DcMixSum { u64 chains = 0; u32 longest = 0; u64 walk_us = 0; };
 static int dc_segments_loop(bscgpu_ctx* c, const DcPass& P, bool fast, bool pk, const u32* sub_run, DcSegSchedule& sch, DcCopyRing& ring, u8* out,
-                            DcNote& sum)
+                            DcNote& sum, const u32* sub_mix = nullptr, DcMixSum* mixsum = nullptr)
 {
     DevCoder* d = P.d;
     std::vector<u32> pseg((size_t)P.S.nsub + 1), pbseg(pk ? (size_t)P.S.nsub + 1 : 0);
@@ -3251,10 +3324,17 @@ static int dc_segments_loop(bscgpu_ctx* c, const DcPass& P, bool fast, bool pk, 
         HIP_TRY(c, hipStreamWaitEvent(c->stream, d->seg_ev[psbuf], 0));          // this buffer's copy-out of two segments ago
         // (the segment's rebased table; its runs as a unit)
         DcSubTab G; G.nsub = (u32)(s1 - s0); G.run = d->seg_run; G.off = P.T.sub_off + s0; G.base = P.T.sub_base + s0; G.maxr = d->sub_maxr + s0;
-        const DcUnit U = dc_pass_range(P, r0, r1, psbuf, g.expect);
+        DcUnit U = dc_pass_range(P, r0, r1, psbuf, g.expect);
         DcOut O;
         O.take_packed = pk; O.poff_host = pseg.data(); O.pbase_host = pk ? pbseg.data() : nullptr;
+        if (sub_mix) { U.mp = d->mp_adapt; O.dbg = d->mix_dbg; }
         rc = fast ? dc_fast_run(c, d, G, U, O) : dc_static_run(c, d, G, U, O);
+        if (sub_mix && rc >= 0) {
+            u32 longest = 0;
+            for (int s = s0; s < s1; ++s) longest = sub_mix[s] > longest ? sub_mix[s] : longest;
+            rc = dc_mix_run(c, d, G, r1 - r0, O.D, d->ps[psbuf & 1], (int64_t)longest);
+            if (rc >= 0 && mixsum && O.D > 0) { mixsum->chains += c->dc_mix_chains; mixsum->longest = c->dc_mix_longest > mixsum->longest ? c->dc_mix_longest : mixsum->longest; mixsum->walk_us += c->dc_mix_walk_us; }
+        }
         const DcNote& run = c->dc_note;
         sum.replays += run.replays; sum.hist_ext += run.hist_ext; sum.replay_resolved += run.replay_resolved; sum.hist_resolved += run.hist_resolved;
         if (rc == BSC_NOT_SUPPORTED) { if (sch.declined(g, run.fail)) ring.settle(g); continue; }
@@ -3295,22 +3375,28 @@ int devcoder_pstream_segments(bscgpu_ctx* c, u32 m, int nsub, const int* blk_sub
     for (int k = 0; k < 2; ++k)
         if (!d->seg_ev[k]) HIP_TRY(c, hipEventCreateWithFlags(&d->seg_ev[k], hipEventDisableTiming));
     const bool fast = coder == 3;                                      // LIBBSC_CODER_QLFC_FAST
+    const bool adaptive = coder == 2;                                  // LIBBSC_CODER_QLFC_ADAPTIVE
+    if (adaptive && !devcoder_mix_ensure(c, d)) return BSC_NOT_SUPPORTED;   // does not fit: declined, no reason bit (as the whole-pass stage)
 
-    std::vector<u32> und((size_t)nsub), dec((size_t)nsub);
+    std::vector<u32> und((size_t)nsub), dec((size_t)nsub), mix(adaptive ? (size_t)nsub : 0);
     DcNote sum;                                                        // the pass's: avg values from the facts, the rest summed over its segments
-    rc = dc_segment_facts(c, P, m, fast, dec.data(), und.data(), &sum);
+    rc = dc_segment_facts(c, P, m, fast, dec.data(), und.data(), &sum, adaptive ? mix.data() : nullptr);
     if (rc < 0) return rc;
 
-    DcSegSchedule sch(dec.data(), und.data(), blk_sub, count, nsub, (int64_t)d->Dcap, target, cap, per_segment_fit, (int)FAIL_AVG, (int)FAIL_CAP, poff, pbase, blk_state);
+    // (the adaptive coder: the step cap reads per BLOCK here — a block with a chain above it is left out, FAIL_MIX, before anything runs)
+    DcSegSchedule sch(dec.data(), und.data(), blk_sub, count, nsub, (int64_t)d->Dcap, target, cap, per_segment_fit, (int)FAIL_AVG, (int)FAIL_CAP, poff, pbase, blk_state,
+                      adaptive ? mix.data() : nullptr, (int64_t)c->dc_mix_cap, (int)FAIL_MIX);
     if (note) note->planned(note->user);
     DcCopyRing ring{d->seg_ev, c->copy_stream, note, {}};
-    rc = dc_segments_loop(c, P, fast, pk, sub_run, sch, ring, static_cast<u8*>(out), sum);
+    DcMixSum mixsum;
+    rc = dc_segments_loop(c, P, fast, pk, sub_run, sch, ring, static_cast<u8*>(out), sum, adaptive ? mix.data() : nullptr, &mixsum);
     // (no copy into the caller's buffer may outlive the call, whichever way it ends)
     if (hipStreamSynchronize(c->copy_stream) != hipSuccess && rc >= 0) rc = ctx_fail(c, BSC_GPU_ERROR, "device coder: segment copy-out", hipSuccess);
     if (rc < 0) return rc;
     const DcSegTotals T = sch.finish();
     sum.fail = T.fail;
     c->dc_note = sum;
+    if (adaptive) { c->dc_mix_chains = (u32)mixsum.chains; c->dc_mix_longest = mixsum.longest; c->dc_mix_walk_us = (u32)mixsum.walk_us; }
     c->cnt_seg += T.kept; c->cnt_seg_reruns += T.reruns; c->cnt_seg_host_blocks += T.host_blocks;
     c->cnt_packed_passes += T.kept_packed; c->cnt_packed_void += T.kept_void;
     if (getenv("BSCGPU_DEBUG")) fprintf(stderr, "[devcoder segments] sub-blocks %d, planned %d, kept %d, re-runs %d, blocks left to the host %d, decisions %lld\n", nsub, T.planned, T.kept, T.reruns, T.host_blocks, (long long)T.decisions);

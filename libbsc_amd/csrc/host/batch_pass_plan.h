@@ -57,19 +57,21 @@ static inline int batch_pass_end(const int* pass_of, const int* sizes, int count
 }
 
 // ---- the call's route --------------------------------------------------------------------------------------------------------------
-struct BatchOptions { int front, model, model_fast, segments, packed, device_rc, model_adaptive; };      // the context's BSCGPU_OPT_* values
+struct BatchOptions { int front, model, model_fast, segments, packed, device_rc, model_adaptive, adaptive_segments; };      // the context's BSCGPU_OPT_* values
 
 struct BatchRoute {
     bool front;          // the front end of every pass on the GPU (BSCGPU_OPT_BATCH_FRONT): its run arrays come down instead of its L
     bool model;          // ... and the coder's model behind it: the static coder's (BSCGPU_OPT_BATCH_MODEL) or the fast coder's
     bool fast_model;     // (BSCGPU_OPT_BATCH_MODEL_FAST: an option and counters of its own) or the adaptive coder's (adaptive_model, below)
-    bool segments;       // ... in model segments (BSCGPU_OPT_BATCH_MODEL_SEGMENTS); with the device's range coder on, a pass takes the whole-pass route
+    bool segments;       // ... in model segments (BSCGPU_OPT_BATCH_MODEL_SEGMENTS; the adaptive coder's: BSCGPU_OPT_BATCH_ADAPTIVE_SEGMENTS alone); with the
+                         // device's range coder on, a pass of -e1 / -e0 takes the whole-pass route
     bool packed;         // ... with the stream in the packed 13-bit form (BSCGPU_OPT_BATCH_MODEL_PACKED): -e1 only, whole passes and segments alike
     bool device_rc;      // a whole pass's streams stay in HBM: one launch of the device's range coder codes them (BSCGPU_OPT_DEVICE_RC)
     int64_t min_pass;    // smallest pass (bytes of L) that is given to the device model
     int64_t segment_target;
     bool adaptive_model; // the model is the adaptive coder's (BSCGPU_OPT_BATCH_MODEL_ADAPTIVE, -e2: an option and counters of its own): whole passes of
-                         // 16-bit entries that the host codes — no segments, no packed form, no device range coder, whatever those options say
+                         // 16-bit entries that the host codes — no packed form, no device range coder, and segments only by its own option
+                         // (BSCGPU_OPT_BATCH_ADAPTIVE_SEGMENTS), whatever the other coders' options say
 };
 
 // the front end needs its two pinned run buffers: they are asked for (front_host) only where this holds
@@ -85,7 +87,7 @@ static inline BatchRoute batch_route(int npass, const BatchOptions& o, int coder
     R.adaptive_model = R.front && o.model_adaptive != 0 && coder == LIBBSC_CODER_QLFC_ADAPTIVE;
     R.model = R.fast_model || R.adaptive_model || (R.front && o.model != 0 && coder == LIBBSC_CODER_QLFC_STATIC);
     R.min_pass = R.fast_model ? min_pass_fast : min_pass_static;         // (-e2: the static coder's until its own sweep is measured)
-    R.segments = R.model && !R.adaptive_model && o.segments != 0 && o.device_rc == 0;
+    R.segments = R.adaptive_model ? o.adaptive_segments != 0 : R.model && o.segments != 0 && o.device_rc == 0;
     R.segment_target = R.segments ? segment_target : 0;
     R.packed = R.model && !R.fast_model && !R.adaptive_model && o.packed != 0;
     R.device_rc = R.model && !R.adaptive_model && o.device_rc != 0;

@@ -1775,6 +1775,13 @@ extern "C" BSCGPU_API int64_t bscgpu_adaptive_pstream_host(const bscgpu_front_la
     return qlfc_adaptive_pstream_runs(front_view(Lo, s), out, cap, dbg);
 }
 
+// ... and the longest mixer chain of sub-block s, per_mixer (optional, [1896]) every mixer's decisions: the host walker's own count
+extern "C" BSCGPU_API int64_t bscgpu_adaptive_longest_chain_host(const bscgpu_front_layout* Lo, int s, uint32_t* per_mixer)
+{
+    if (!Lo || s < 0 || s >= Lo->nsub) return LIBBSC_BAD_PARAMETER;
+    return qlfc_adaptive_longest_chain_runs(front_view(Lo, s), per_mixer);
+}
+
 static int front_batch_code_stream(const bscgpu_front_layout* Lo, int block, const uint16_t* ps, const uint32_t* poff,
                                    unsigned char* out, int coder, int features)
 {
@@ -1982,6 +1989,16 @@ extern "C" BSCGPU_API int bscgpu_model_segment_facts_device(bscgpu_ctx* c, const
     return devcoder_segment_facts(c, (u32)out->m, out->nsub, coder, sub_dec, sub_und);
 }
 
+// ... for the adaptive coder (-e2): the third fact beside the static coder's two
+extern "C" BSCGPU_API int bscgpu_adaptive_segment_facts_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out,
+                                                               uint32_t* sub_dec, uint32_t* sub_und, uint32_t* sub_mix)
+{
+    if (!c || (count > 0 && (!sub_dec || !sub_und || !sub_mix))) return LIBBSC_BAD_PARAMETER;
+    const int frc = bscgpu_qlfc_front_batch_device(c, dL, sizes, count, out);
+    if (frc < 0 || out->nsub == 0) return frc;
+    return devcoder_segment_facts(c, (u32)out->m, out->nsub, LIBBSC_CODER_QLFC_ADAPTIVE, sub_dec, sub_und, sub_mix);
+}
+
 // the stage in either form: pbase non-null is the packed one (out / cap in bytes); the callers have checked their own arguments
 static int64_t pstream_batch_segments(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out, int coder, int64_t target,
                                       void* ps, int64_t cap, uint32_t* poff, int64_t* pbase, int* blk_state)
@@ -2005,6 +2022,13 @@ extern "C" BSCGPU_API int64_t bscgpu_pstream_batch_segments_device(bscgpu_ctx* c
     if (!c || !poff || cap < 0 || (cap > 0 && !ps) || (count > 0 && !blk_state)) return LIBBSC_BAD_PARAMETER;
     if (coder != LIBBSC_CODER_QLFC_STATIC && coder != LIBBSC_CODER_QLFC_FAST) return LIBBSC_BAD_PARAMETER;
     return pstream_batch_segments(c, dL, sizes, count, out, coder, target, ps, cap, poff, nullptr, blk_state);
+}
+
+extern "C" BSCGPU_API int64_t bscgpu_adaptive_pstream_batch_segments_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out,
+                                                                            int64_t target, uint16_t* ps, int64_t cap, uint32_t* poff, int* blk_state)
+{
+    if (!c || !poff || cap < 0 || (cap > 0 && !ps) || (count > 0 && !blk_state)) return LIBBSC_BAD_PARAMETER;
+    return pstream_batch_segments(c, dL, sizes, count, out, LIBBSC_CODER_QLFC_ADAPTIVE, target, ps, cap, poff, nullptr, blk_state);
 }
 
 extern "C" BSCGPU_API int64_t bscgpu_pstream_batch_segments_packed_device(bscgpu_ctx* c, const void* dL, const int* sizes, int count, bscgpu_front_layout* out,
@@ -2499,7 +2523,8 @@ void BatchPass::code_groups(PassOrder& order)
 // the call's route: the context's options and the coder, with the environment's values read per call
 BatchRoute call_route(bscgpu_ctx* c, int npass, int coder)
 {
-    const BatchOptions o = {c->batch_front, c->batch_model, c->batch_model_fast, c->batch_model_segments, c->batch_model_packed, c->device_rc, c->batch_model_adaptive};
+    const BatchOptions o = {c->batch_front, c->batch_model, c->batch_model_fast, c->batch_model_segments, c->batch_model_packed, c->device_rc, c->batch_model_adaptive,
+                            c->batch_adaptive_segments};
     // the front end needs the two pinned run buffers; without them today's route
     const bool front_host = batch_wants_front(npass, o) && ctx_ensure_front_host(c) == LIBBSC_NO_ERROR;
     return batch_route(npass, o, coder, front_host, batch_model_min_pass(false), batch_model_min_pass(true), batch_model_segment());

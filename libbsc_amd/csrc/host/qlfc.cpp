@@ -966,6 +966,35 @@ int64_t qlfc_adaptive_pstream_runs(const RunView& R, uint16_t* out, int64_t cap,
     return pol.n;
 }
 
+// ... and the walker's own count of every mixer's decisions: the chains of a sub-block (what dc_mix_facts_kernel counts on the device).
+// per_mixer (optional, [dcm::NUM_MIX]); -> the longest chain, or BAD_PARAMETER
+namespace {
+struct CountPolicyAdaptive {
+    uint32_t* cnt; const Mixer* base;
+    struct Live {};
+    inline bool begin_run() { return true; }
+    inline Live enter() { return Live(); }
+    inline void leave(const Live&) {}
+    template <int CLS> BSC_ALWAYS_INLINE void decide(Live&, unsigned, short&, short&, short&, Mixer* mx) { ++cnt[mx - base]; }
+};
+}
+int64_t qlfc_adaptive_longest_chain_runs(const RunView& R, uint32_t* per_mixer)
+{
+    if (R.nsym <= 0) return BAD_PARAMETER;
+    const QlfcTables& T = qlfc_tables();
+    Counters1* Cn = tl_counters();
+    static const Mixers1 slots{};                            // never read: the walker only forms addresses inside it
+    std::vector<uint32_t> own(per_mixer ? 0 : (size_t)dcm::NUM_MIX);
+    uint32_t* cnt = per_mixer ? per_mixer : own.data();
+    memset(cnt, 0, sizeof(uint32_t) * dcm::NUM_MIX);
+    const int max_rank = encode_alphabet(R, [](unsigned) {});
+    CountPolicyAdaptive pol{cnt, reinterpret_cast<const Mixer*>(&slots)};
+    (void)walk_model1<true>(R, T, max_rank, *Cn, const_cast<Mixers1*>(&slots), pol);
+    uint32_t longest = 0;
+    for (int i = 0; i < dcm::NUM_MIX; ++i) longest = cnt[i] > longest ? cnt[i] : longest;
+    return (int64_t)longest;
+}
+
 // ------------------------------------------------------------------------------------------------
 // The back half alone, behind the device model: the probabilities come from the GPU (devcoder.hip) as a stream of entries in stream
 // order, one per decision; the host writes the header and the alphabet and range-codes the entries.  Three entry forms

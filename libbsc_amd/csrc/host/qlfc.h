@@ -86,6 +86,7 @@ int64_t qlfc_fast_pstream_runs(const RunView& R, uint16_t* out, int64_t cap);
 // ... of the adaptive model (-e2), in the static coder's entry form; dbg (optional, [4][cap]): the state / char / static counter values
 // and the mixer id behind every decision
 int64_t qlfc_adaptive_pstream_runs(const RunView& R, uint16_t* out, int64_t cap, uint16_t* dbg);
+int64_t qlfc_adaptive_longest_chain_runs(const RunView& R, uint32_t* per_mixer /* [1896] or null */);
 // Encode one sub-block (what coder.cpp:61 dispatches to).  Returns bytes written or NOT_COMPRESSIBLE.
 int qlfc_encode_block(const uint8_t* in, uint8_t* out, int in_size, int out_size, int coder);
 // Decode one sub-block; returns the decoded size or an error.

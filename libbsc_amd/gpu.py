@@ -364,6 +364,31 @@ class GpuContext:
             raise GpuError(-2, f"{D} decisions exceed the buffer of {cap}")
         return fb, out[:D], poff[:fb.nsub + 1], state[:fb.count]
 
+    def adaptive_segment_facts(self, dL, sizes):
+        """bscgpu_adaptive_segment_facts_device: model_segment_facts for the adaptive coder (-e2) -> (FrontBatch, sub_dec, sub_und,
+        sub_mix np.uint32[nsub]: the longest mixer chain of every sub-block, meaningful where sub_und is 0)"""
+        fb = FrontBatch(sizes)
+        dec, und, mix = (np.zeros(2 * fb.count + 2, np.uint32) for _ in range(3))
+        self._check(self.L.bscgpu_adaptive_segment_facts_device(self.h, _dptr(dL), N.np_ptr(fb.sizes), fb.count, C.byref(fb.lay),
+                                                                N.np_ptr(dec), N.np_ptr(und), N.np_ptr(mix)))
+        return fb, dec[:fb.nsub], und[:fb.nsub], mix[:fb.nsub]
+
+    def adaptive_pstream_batch_segments(self, dL, sizes, target=0, cap=None):
+        """bscgpu_adaptive_pstream_batch_segments_device: pstream_batch_segments for the adaptive coder (-e2): entries in the static
+        coder's 16-bit form; blk_state may hold DC_FAIL_MIX (a block with a mixer chain above the step cap)"""
+        fb = FrontBatch(sizes)
+        if cap is None:
+            cap = 16 * int(fb.sizes.sum()) + 4096
+        out = np.empty(max(cap, 1), np.uint16)
+        poff = np.zeros(2 * fb.count + 2, np.uint32)
+        state = np.zeros(max(fb.count, 1), np.int32)
+        D = int(self.L.bscgpu_adaptive_pstream_batch_segments_device(self.h, _dptr(dL), N.np_ptr(fb.sizes), fb.count, C.byref(fb.lay), int(target),
+                                                                     N.np_ptr(out), cap, N.np_ptr(poff), N.np_ptr(state)))
+        self._check(D)
+        if D > cap:
+            raise GpuError(-2, f"{D} decisions exceed the buffer of {cap}")
+        return fb, out[:D], poff[:fb.nsub + 1], state[:fb.count]
+
     # ---- batched decompression (one inverse-BWT pass for many blocks, include/bscgpu.h) -------
     def unbwt_batch(self, dL, sizes, primary, dT=None):
         """inverse BWT of every block of a batch laid out back to back in the uint8 device tensor dL (primary: 1-based indexes) ->
@@ -426,6 +451,7 @@ class GpuContext:
     OPT_BATCH_MODEL, CNT_BATCH_MODEL_PASSES, CNT_BATCH_MODEL_DECLINED = 14, 15, 16    # the static coder's model of a compress-batch pass on the GPU
     OPT_BATCH_MODEL_FAST, CNT_BATCH_FAST_PASSES, CNT_BATCH_FAST_DECLINED = 17, 18, 19    # ... the fast coder's (-e0), an option of its own
     OPT_BATCH_MODEL_ADAPTIVE, CNT_BATCH_ADAPTIVE_PASSES, CNT_BATCH_ADAPTIVE_DECLINED = 38, 39, 40    # ... the adaptive coder's (-e2), an option of its own
+    OPT_BATCH_ADAPTIVE_SEGMENTS = 44                 # ... in model segments (default 0; with OPT_BATCH_MODEL_ADAPTIVE and -e2 only)
     CNT_DC_MIX_CHAINS, CNT_DC_MIX_LONGEST, CNT_DC_MIX_WALK_US = 41, 42, 43     # mixer chains of the last -e2 pass on the device model, the steps of the longest, its walk's wall time (get only)
     OPT_BWT_FOLD, CNT_BWT_FOLDED = 20, 21            # key packing sorts the first-sort key's leftover low bits (default 1) and how many sorts took that route
     # a model pass in segments (default 0), segments kept, halves run again, blocks that ended on the host model; the model's capacity in decisions
@@ -626,6 +652,16 @@ def adaptive_pstream_host(fb, s, dbg=False):
     n2 = int(f(C.byref(fb.lay), int(s), N.np_ptr(out), max(n, 1), N.np_ptr(planes) if dbg else None))
     assert n2 == n
     return (out[:n], planes[:, :n]) if dbg else out[:n]
+
+
+def adaptive_longest_chain_host(fb, s, per_mixer=False):
+    """bscgpu_adaptive_longest_chain_host: the longest mixer chain of sub-block s of a FrontBatch, the host walker's own count (no GPU)
+    -> int; per_mixer=True: (int, np.uint32[1896] decisions of every mixer)"""
+    cnt = np.zeros(1896, np.uint32) if per_mixer else None
+    n = int(N.lib().bscgpu_adaptive_longest_chain_host(C.byref(fb.lay), int(s), N.np_ptr(cnt) if per_mixer else None))
+    if n < 0:
+        raise GpuError(n, "bscgpu_adaptive_longest_chain_host")
+    return (n, cnt) if per_mixer else n
 
 
 def front_batch_code_psf(fb, block, ps, poff, features=3):

@@ -48,7 +48,8 @@ the front end beside them).  The on legs also run with BSCGPU_OPT_DEVICE_RC = 1 
 device's range coder).  --model-sweep: on against off on passes of 64 KiB .. 16 MiB cut from the workload's text — the smallest pass
 the model route wins on (run it with BSC_BATCH_MODEL_MIN_PASS=0 in the environment).  Raw output belongs under profiles/batch_model/.
 With --coder 2 --model and --model-only drive the adaptive coder's route (BSCGPU_OPT_BATCH_MODEL_ADAPTIVE, -e2,
-bscgpu_adaptive_pstream_batch_device; no device range coder, segments or packed form there); --model-only then also prints the pass's
+bscgpu_adaptive_pstream_batch_device; no device range coder or packed form there; --segments drives its own segments option, below);
+--model-only then also prints the pass's
 mixer chains, the longest chain, the walk's wall time and ns per dependent step, the host coder's wall time for the same pass on 16
 threads, and the chain cap those two give (the steps the walk does in the host's time, rounded down to a power of two).
 With --coder 3 all three drive the fast coder's route instead (BSCGPU_OPT_BATCH_MODEL_FAST, -e0, bscgpu_fast_pstream_batch_device; the
@@ -63,7 +64,11 @@ BSCGPU_OPT_BATCH_MODEL_PACKED for either input kind (with --segments: both model
 assertion that W1's segmented pass leaves no block to the host for landing space; with --model-only the stage in the packed form beside
 the 16-bit one, with the assertion bytes = pbase[nsub] / 8 * 13.  Raw output belongs under profiles/batch_packed/.  --segment-sweep: model + segments on W1 and W2, host input, with BSC_BATCH_MODEL_SEGMENT set to
 the capacity / 8, / 4, / 2 and the capacity, interleaved with model on and off.  Raw output belongs under profiles/batch_segments/.
-    python tools/batch_bench.py --model --segments [--model-only | --segment-sweep] [--coder 3] [--reps 3] [--workloads W1,W2,W3]
+With --coder 2 the segments are the adaptive coder's (BSCGPU_OPT_BATCH_ADAPTIVE_SEGMENTS, bscgpu_adaptive_pstream_batch_segments_device):
+the same legs and the same sweep; --model-only adds the third fact's kernel on a line of its own (the -e2 facts stage less the -e1
+facts stage), the longest chain the facts report, and the chains, longest chain and walk time summed over the pass's segments.  Raw
+output belongs under profiles/batch_adaptive_segments/.
+    python tools/batch_bench.py --model --segments [--model-only | --segment-sweep] [--coder 3 | --coder 2] [--reps 3] [--workloads W1,W2,W3]
 """
 import argparse
 import ctypes as C
@@ -373,10 +378,12 @@ def model_main(args):
     CNT_PASSES = ctx.CNT_BATCH_FAST_PASSES if fast else ctx.CNT_BATCH_ADAPTIVE_PASSES if adaptive else ctx.CNT_BATCH_MODEL_PASSES
     CNT_DECLINED = ctx.CNT_BATCH_FAST_DECLINED if fast else ctx.CNT_BATCH_ADAPTIVE_DECLINED if adaptive else ctx.CNT_BATCH_MODEL_DECLINED
     stage = ctx.fast_pstream_batch if fast else ctx.adaptive_pstream_batch if adaptive else ctx.static_pstream_batch
-    if adaptive and (args.segments or args.packed or args.segment_sweep):
-        raise SystemExit("--segments and --packed are not the adaptive coder's (-e2): its passes take the whole-pass 16-bit route")
+    if adaptive and args.packed:
+        raise SystemExit("--packed is not the adaptive coder's (-e2): its passes and segments are 16-bit entries")
+    # the option that puts a model pass into segments: the adaptive coder has one of its own
+    SEG_OPT = ctx.OPT_BATCH_ADAPTIVE_SEGMENTS if adaptive else ctx.OPT_BATCH_MODEL_SEGMENTS
     if args.segments:                                             # the segmented stage: (layout, entries, poff) as the whole-pass stage returns them
-        stage = lambda dL, psz: ctx.pstream_batch_segments(dL, psz, coder, 0)[:3]
+        stage = (lambda dL, psz: ctx.adaptive_pstream_batch_segments(dL, psz, 0)[:3]) if adaptive else (lambda dL, psz: ctx.pstream_batch_segments(dL, psz, coder, 0)[:3])
     if args.packed and fast:
         raise SystemExit("--packed is the static coder's (-e1): the fast coder's entries use all 16 bits")
     # --packed --model-only: the stage in the packed 13-bit form beside the 16-bit one, same session, interleaved
@@ -429,14 +436,14 @@ def model_main(args):
                 legs = {"off": (0, 0, None), "on": (1, 0, None)}
                 legs.update({f"segments_{dcap // k}": (1, 1, dcap // k) for k in (8, 4, 2, 1)})
                 for how in legs.values():                          # warm-up: arenas, pinned buffers
-                    ctx.option_set(OPT, how[0]); ctx.option_set(ctx.OPT_BATCH_MODEL_SEGMENTS, how[1])
+                    ctx.option_set(OPT, how[0]); ctx.option_set(SEG_OPT, how[1])
                     ctx.compress_batch(blocks[:40], 1, coder)
                 t = {k: [] for k in legs}
                 cnt = {k: None for k in legs}
                 ref = None
                 for _ in range(args.reps):
                     for leg, how in legs.items():
-                        ctx.option_set(OPT, how[0]); ctx.option_set(ctx.OPT_BATCH_MODEL_SEGMENTS, how[1])
+                        ctx.option_set(OPT, how[0]); ctx.option_set(SEG_OPT, how[1])
                         if how[2] is None:
                             os.environ.pop("BSC_BATCH_MODEL_SEGMENT", None)
                         else:
@@ -448,7 +455,7 @@ def model_main(args):
                         ref = ref or digest(out)
                         assert digest(out) == ref, leg
                 os.environ.pop("BSC_BATCH_MODEL_SEGMENT", None)
-                ctx.option_set(ctx.OPT_BATCH_MODEL_SEGMENTS, 0)
+                ctx.option_set(SEG_OPT, 0)
                 for leg in legs:
                     w = np.array(t[leg])
                     print(json.dumps({"workload": name, "leg": "segment_sweep_" + leg, "coder": coder, "MB": round(mb, 2), "ms": t[leg],
@@ -496,11 +503,28 @@ def model_main(args):
                         for k, names in CLASSES.items():
                             classes[k].append(round(sum(st[n]["ms"] for n in names), 3))
                 ctx.profile(False)
+                g0 = [ctx.option_get(k) for k in SEG_KEYS]
+                stage(dL, psz)
+                seg_moved = [ctx.option_get(k) - a for k, a in zip(SEG_KEYS, g0)]
                 if args.packed:
                     rec.update({"packed_wall_ms_with_front_end_and_copy_out": tw13, "packed_kernel_ms": per13,
                                 "p_stream_ms_median_16_bit_vs_packed": [float(np.median(per["p_stream"])), float(np.median(per13["p_stream"]))],
                                 "p_stream_ms_min_max_16_bit": [min(per["p_stream"]), max(per["p_stream"])],
                                 "p_stream_ms_min_max_packed": [min(per13["p_stream"]), max(per13["p_stream"])]})
+                if adaptive and args.segments:
+                    # the third fact's kernel on its own line: the facts stage of -e2 (dc_avg, dc_sub_dec, dc_mix_facts) less the facts
+                    # stage of -e1 (the first two), HIP-event time of the dc_facts class, interleaved
+                    ctx.profile(True)
+                    f2, f1 = [], []
+                    for _ in range(args.reps):
+                        for run, acc in ((lambda: ctx.adaptive_segment_facts(dL, psz), f2), (lambda: ctx.model_segment_facts(dL, psz, 1), f1)):
+                            ctx.profile_reset()
+                            run()
+                            acc.append(round(ctx.profile_get()["dc_facts"]["ms"], 3))
+                    ctx.profile(False)
+                    sub_mix = ctx.adaptive_segment_facts(dL, psz)[3]
+                    rec.update({"facts_stage_ms_e2": f2, "facts_stage_ms_e1": f1, "mix_facts_kernel_ms_median": round(float(np.median(f2) - np.median(f1)), 3),
+                                "longest_chain_by_the_facts": int(sub_mix.max()), "segments_reruns_host_blocks_of_a_run": seg_moved})
                 if adaptive:
                     # what the chain cap's default is derived from: the walk's time per dependent step (its wall time over the longest
                     # chain) against the host coder's wall time for the same pass, every block from its runs on 16 threads
@@ -554,7 +578,7 @@ def model_main(args):
                     else:
                         ctx.option_set(OPT, how[0])
                         ctx.option_set(ctx.OPT_DEVICE_RC, how[2])
-                        ctx.option_set(ctx.OPT_BATCH_MODEL_SEGMENTS, how[3] if len(how) > 3 else 0)
+                        ctx.option_set(SEG_OPT, how[3] if len(how) > 3 else 0)
                         ctx.option_set(ctx.OPT_BATCH_MODEL_PACKED, how[4] if len(how) > 4 else 0)
                         p0, d0 = ctx.option_get(CNT_PASSES), ctx.option_get(CNT_DECLINED)
                         g0 = [ctx.option_get(k) for k in SEG_KEYS]

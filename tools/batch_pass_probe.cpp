@@ -5,19 +5,39 @@
 // One call per line on stdin, numbers separated by blanks:
 //   count sorter coder cap dev  front model fast segments packed device_rc (the option values)
 //   min_pass_static min_pass_fast target front_host model_host entries  sizes[count]  lz[count]
-//   nfacts (pass nsub mrc D pk pbytes nstate blk_state[nstate])*
-// A pass without facts has nsub = 0; a pass whose facts have no blk_state has all zeros.  One JSON object per line on stdout.
+//   nfacts (pass nsub mrc D pk pbytes nstate blk_state[nstate])*  [adaptive_segments [model_adaptive]]
+// A pass without facts has nsub = 0; a pass whose facts have no blk_state has all zeros.  The optional trailing fields are the values of
+// BSCGPU_OPT_BATCH_ADAPTIVE_SEGMENTS and BSCGPU_OPT_BATCH_MODEL_ADAPTIVE; a line without them means 0, and only a line with them
+// gets the adaptive route's keys ("adaptive_model" of the call, "adaptive": [passes, declined] of a pass) in its answer.
+// One JSON object per line on stdout.
 #include "batch_pass_plan.h"
 #include <cstdio>
+#include <cstdlib>
 #include <map>
+#include <string>
 #include <vector>
 
 struct Facts { int nsub = 0, mrc = 0; long long D = 0; int pk = 0; long long pbytes = 0; std::vector<int> state; };
 
+// the numbers of the current line, taken in order
+static std::vector<long long> line;
+static size_t line_at;
+static bool next_line()
+{
+    std::string text;
+    int ch;
+    while ((ch = getchar()) != EOF && ch != '\n') text.push_back((char)ch);
+    if (ch == EOF && text.empty()) return false;
+    line.clear(); line_at = 0;
+    const char* p = text.c_str();
+    for (char* end; ; p = end) { const long long v = strtoll(p, &end, 10); if (end == p) break; line.push_back(v); }
+    return true;
+}
 static bool read_ints(std::vector<long long>& v, long long n)
 {
-    v.resize((size_t)n);
-    for (long long i = 0; i < n; ++i) if (scanf("%lld", &v[(size_t)i]) != 1) return false;
+    if (n < 0 || line_at + (size_t)n > line.size()) return false;
+    v.assign(line.begin() + (long)line_at, line.begin() + (long)(line_at + (size_t)n));
+    line_at += (size_t)n;
     return true;
 }
 
@@ -40,24 +60,36 @@ int main()
     static const char* const STEP[] = {"none", "whole", "segments"};
     static const char* const SOURCE[] = {"l", "runs", "ps16", "ps13", "fast", "device_rc"};
     static const char* const LEFT[] = {"none", "one_by_one", "pipe"};
-    int count, sorter, coder, dev, front_host, model_host;
-    long long cap, min_static, min_fast, target, entries;
-    BatchOptions o;
-    while (scanf("%d %d %d %lld %d %d %d %d %d %d %d %lld %lld %lld %d %d %lld", &count, &sorter, &coder, &cap, &dev, &o.front, &o.model, &o.model_fast,
-                 &o.segments, &o.packed, &o.device_rc, &min_static, &min_fast, &target, &front_host, &model_host, &entries) == 17) {
+    while (next_line()) {
+        if (line.empty()) continue;
         std::vector<long long> t;
+        if (!read_ints(t, 17)) return 1;
+        const int count = (int)t[0], sorter = (int)t[1], coder = (int)t[2], dev = (int)t[4], front_host = (int)t[14], model_host = (int)t[15];
+        const long long cap = t[3], min_static = t[11], min_fast = t[12], target = t[13], entries = t[16];
+        BatchOptions o = {};
+        o.front = (int)t[5]; o.model = (int)t[6]; o.model_fast = (int)t[7]; o.segments = (int)t[8]; o.packed = (int)t[9]; o.device_rc = (int)t[10];
         if (!read_ints(t, count)) return 1;
         const std::vector<int> sizes(t.begin(), t.end());
         if (!read_ints(t, count)) return 1;
         const std::vector<int> lz(t.begin(), t.end());
         std::map<int, Facts> facts;
-        int nf;
-        if (scanf("%d", &nf) != 1) return 1;
+        if (!read_ints(t, 1)) return 1;
+        const int nf = (int)t[0];
         for (int k = 0; k < nf; ++k) {
-            int p, ns; Facts f;
-            if (scanf("%d %d %d %lld %d %lld %d", &p, &f.nsub, &f.mrc, &f.D, &f.pk, &f.pbytes, &ns) != 7 || !read_ints(t, ns)) return 1;
+            Facts f;
+            if (!read_ints(t, 7)) return 1;
+            const int p = (int)t[0], ns = (int)t[6];
+            f.nsub = (int)t[1]; f.mrc = (int)t[2]; f.D = t[3]; f.pk = (int)t[4]; f.pbytes = t[5];
+            if (!read_ints(t, ns)) return 1;
             f.state.assign(t.begin(), t.end());
             facts[p] = f;
+        }
+        const bool with_adaptive = line_at < line.size();
+        if (with_adaptive) {
+            if (!read_ints(t, 1)) return 1;
+            o.adaptive_segments = (int)t[0];
+            if (line_at < line.size()) { if (!read_ints(t, 1)) return 1; o.model_adaptive = (int)t[0]; }
+            if (line_at != line.size()) return 1;
         }
 
         const bool st = sorter != LIBBSC_BLOCKSORTER_BWT;
@@ -66,8 +98,10 @@ int main()
         const BatchRoute R = batch_route(npass, o, coder, batch_wants_front(npass, o) && front_host != 0, min_static, min_fast, target);
         printf("{\"npass\":%d,", npass);
         print_list("pass_of", pass_of);
-        printf(",\"route\":[%d,%d,%d,%d,%d,%d],\"min_pass\":%lld,\"target\":%lld,\"passes\":[", R.front, R.model, R.fast_model, R.segments, R.packed, R.device_rc,
+        printf(",\"route\":[%d,%d,%d,%d,%d,%d],\"min_pass\":%lld,\"target\":%lld,", R.front, R.model, R.fast_model, R.segments, R.packed, R.device_rc,
                (long long)R.min_pass, (long long)R.segment_target);
+        if (with_adaptive) printf("\"adaptive_model\":%d,", R.adaptive_model);
+        printf("\"passes\":[");
         std::vector<char> single((size_t)count);
         for (int b = 0; b < count; ++b) single[(size_t)b] = pass_of[(size_t)b] < 0;
         int error = 0;
@@ -102,6 +136,7 @@ int main()
                     const BatchCounters m = batch_model_counters(R, step, v, pk);
                     d.model_passes = m.model_passes; d.model_declined = m.model_declined; d.fast_passes = m.fast_passes; d.fast_declined = m.fast_declined;
                     d.packed_passes = m.packed_passes; d.packed_void = m.packed_void; d.device_rc = m.device_rc;
+                    d.adaptive_passes = m.adaptive_passes; d.adaptive_declined = m.adaptive_declined;
                 }
                 if (v == BATCH_PASS_ERROR) error = f.mrc;
             }
@@ -114,6 +149,7 @@ int main()
             printf(",\"pos\":%lld,\"step\":\"%s\",\"kept\":%d,\"counters\":{\"front\":%d,\"l\":%d,\"model\":%d,\"declined\":%d,\"fast\":%d,\"fast_declined\":%d,"
                    "\"packed\":%d,\"void\":%d,\"device_rc\":%d}", (long long)G.pos, G.pos > 0 && !R.front ? "l_down" : STEP[step], kept, d.front_passes, d.l_passes,
                    d.model_passes, d.model_declined, d.fast_passes, d.fast_declined, d.packed_passes, d.packed_void, d.device_rc);
+            if (with_adaptive) printf(",\"adaptive\":[%d,%d]", d.adaptive_passes, d.adaptive_declined);
             if (!error) {
                 const bool coded = step == BATCH_MODEL_WHOLE && kept && R.device_rc;
                 const bool stream = step == BATCH_MODEL_SEGMENTS || (step == BATCH_MODEL_WHOLE && kept && !coded);
