@@ -156,6 +156,26 @@ BSCGPU_API int bscgpu_rc_check(int form, int nprefix_total, const bscgpu_rc_stre
 BSCGPU_API int bscgpu_compress_device(bscgpu_ctx* ctx, const void* dInput, uint8_t* output, int n,
                            int blockSorter, int coder, int features);
 
+/* bscgpu_compress_device with the LZP stage in front (bsc_compress's full parameter list for input in HBM): the Adler-32 of the original
+ * comes from the device kernel, bscgpu_lzp_compress_device's stage writes the sorter's input.  A chunk-level or block-level
+ * LIBBSC_NOT_COMPRESSIBLE lets the block go on without LZP (libbsc.cpp:266-269); LIBBSC_NOT_SUPPORTED where the stage declines
+ * (lzpHashSize >= 16).  lzpHashSize == 0 and lzpMinLen == 0: bscgpu_compress_device.  Same bytes as bsc_compress of the same input. */
+BSCGPU_API int bscgpu_compress_device_lzp(bscgpu_ctx* ctx, const void* dInput, uint8_t* output, int n, int lzpHashSize, int lzpMinLen,
+                           int blockSorter, int coder, int features);
+
+/* ---- the LZP encoder stage on the GPU ------------------------------------------
+ * bscgpu_lzp_compress_device: what bsc_lzp_compress returns for the n bytes at dIn (HBM), with the same bytes in dOut (HBM, n bytes; may
+ *   be dIn) — or LIBBSC_NOT_SUPPORTED, before anything is launched, for hashSize >= 16: the stage holds a chunk's table in LDS and covers
+ *   the narrow scanners only.  Both framings (features & LIBBSC_FEATURE_MULTITHREADING) are exact.  BSCGPU_CNT_LZP_MATCHES.. say which
+ *   paths the block took.  n <= the context's max_n.
+ * bscgpu_lzp_compress: the same with host pointers (out: n bytes).
+ * bscgpu_lzp_staged_host: the CPU stand-in — the stage's three steps (links, flags, the sweep with its dirty marks and the real table:
+ *   written for every visited position, read by dirty positions only) as the device runs them, on the calling thread; no GPU, no context.  counters (or NULL): five values in the order of
+ *   BSCGPU_CNT_LZP_MATCHES .. _RAW_CHUNKS. */
+BSCGPU_API int bscgpu_lzp_compress_device(bscgpu_ctx* ctx, const void* dIn, void* dOut, int n, int hashSize, int minLen, int features);
+BSCGPU_API int bscgpu_lzp_compress(bscgpu_ctx* ctx, const uint8_t* in, uint8_t* out, int n, int hashSize, int minLen, int features);
+BSCGPU_API int bscgpu_lzp_staged_host(const uint8_t* in, uint8_t* out, int n, int hashSize, int minLen, int features, int64_t* counters);
+
 /* ---- batches of small blocks: one suffix sort for many blocks ------------------------------
  * Blocks are laid out back to back: block b starts at off_b = sizes[0] + ... + sizes[b-1].  Blocks below
  * BSCGPU_BATCH_MAX_N that the BWT sorts share one suffix sort per pass (at most max_n bytes and 4096 blocks,
@@ -544,7 +564,8 @@ enum {
     BSCGPU_K_RC            = 14, /* range coder: many probability streams in one launch (rangecoder.hip) */
     BSCGPU_K_DC_FACTS      = 15, /* device coder, a pass in model segments: per-sub-block facts (flags, decision counts) and segment tables */
     BSCGPU_K_DC_REPLAY     = 16, /* device coder: open chunk starts resolved exactly (BSCGPU_OPT_DC_REPLAY_EXACT): candidate walks and chaining */
-    BSCGPU_K_COUNT         = 17
+    BSCGPU_K_LZP           = 17, /* LZP encoder stage (lzp.hip): keys, links, flags, the sweep; its sort passes are booked under _RADIX_AUX */
+    BSCGPU_K_COUNT         = 18
 };
 typedef struct bscgpu_kstat {
     double   ms;        /* accumulated HIP-event time */
@@ -708,6 +729,20 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          in: 1 = whole, 0 = declined before any ran (or the arena is not divided: such a block takes the whole-block
  *                          route without the plan's facts).  Segments of a packed block count in BSCGPU_CNT_BATCH_PACKED_PASSES, one
  *                          whose packed form was void — re-run as 16-bit entries and packed into place by the host — in _PACKED_VOID.
+ * BSCGPU_OPT_DEVICE_LZP    0 (default) / 1 (BSC_DEVICE_LZP=1 in the environment, read when a context is created, sets the same): in
+ *                          bscgpu_pipe_submit_host (and so the job driver's blocks) and in the single-block path of bscgpu_compress_batch a
+ *                          host block with LZP whose parameters the device stage takes (hashSize 10..15) goes up raw and
+ *                          is preprocessed by bscgpu_lzp_compress_device's stage in front of the sorter, instead of by lzp_compress on the
+ *                          submitting thread.  A block the stage declines takes the host route.  Same output.  The batched passes of
+ *                          bscgpu_compress_batch keep host LZP.  bsc_compress runs on default contexts that no caller can set options on and
+ *                          decides, before it has one, whether LZP runs on the host: it takes the route from BSC_DEVICE_LZP=1 in the
+ *                          environment AS IT STANDS AT THE CALL, not from the option of the context it then gets.
+ * BSCGPU_CNT_LZP_BLOCKS    (get only) blocks that route gave to the stage; _LZP_DECLINED: blocks with LZP it left to the host because the
+ *                          stage does not take their parameters.
+ * BSCGPU_CNT_LZP_MATCHES   (get only, as the four that follow: of the LAST block given to the stage, by the route or by bscgpu_lzp_compress*,
+ *                          summed over its chunks, saturating) matches taken; _LZP_DIRTY: positions visited whose predecessor a match had
+ *                          skipped (they read the real table); _LZP_SERIAL_ZONES: failed verifies (minLen > 16), each followed by a stretch
+ *                          run group by group; _LZP_ESCAPES: escaped literals (0xF2 0xFF); _LZP_RAW_CHUNKS: chunks kept raw by the framing.
  * Environment only, no option key: BSC_UNBWT_STEP_CAP (read when a context is created, like BSC_PS13; values below 16 are ignored) is the
  *                          inverse BWT's step cap, 1 << 22 by default — a test knob for the LIBBSC_NOT_SUPPORTED exits (see bscgpu_unbwt).
  * set returns the previous value or a negative libbsc error code; get the value or a negative error code. */
@@ -727,7 +762,10 @@ enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACK
        BSCGPU_OPT_DC_ARENA_DIV = 36, BSCGPU_CNT_DC_BLOCK_SEGMENTS = 37,
        BSCGPU_OPT_BATCH_MODEL_ADAPTIVE = 38, BSCGPU_CNT_BATCH_ADAPTIVE_PASSES = 39, BSCGPU_CNT_BATCH_ADAPTIVE_DECLINED = 40,
        BSCGPU_CNT_DC_MIX_CHAINS = 41, BSCGPU_CNT_DC_MIX_LONGEST = 42, BSCGPU_CNT_DC_MIX_WALK_US = 43,
-       BSCGPU_OPT_BATCH_ADAPTIVE_SEGMENTS = 44 };
+       BSCGPU_OPT_BATCH_ADAPTIVE_SEGMENTS = 44,
+       BSCGPU_OPT_DEVICE_LZP = 45, BSCGPU_CNT_LZP_BLOCKS = 46, BSCGPU_CNT_LZP_DECLINED = 47,
+       BSCGPU_CNT_LZP_MATCHES = 48, BSCGPU_CNT_LZP_DIRTY = 49, BSCGPU_CNT_LZP_SERIAL_ZONES = 50, BSCGPU_CNT_LZP_ESCAPES = 51,
+       BSCGPU_CNT_LZP_RAW_CHUNKS = 52 };
 /* _FAIL_AVG: undecided avg_rank flags; _FAIL_HIST: a run_hist bracket open after 9216 predecessors (never with
  * BSCGPU_OPT_DC_HIST_EXACT); _FAIL_CAP: more runs or decisions
  * than the context's arena holds; _FAIL_REPLAY: a chain whose bracket stayed open over more than 64 evaluation chunks (with
@@ -749,8 +787,10 @@ BSCGPU_API int bscgpu_qlfc_pstream_facts(bscgpu_ctx* ctx, const uint8_t* L, int 
 BSCGPU_API int bscgpu_option_get(bscgpu_ctx* ctx, int key);
 /* Process-wide counts since start (tests, reports): blocks whose static model ran on the GPU, how many of those were LZP-preprocessed,
  * and blocks that took the device model first and were redone with the model on the host (a sub-block that does not compress has to
- * be stored raw from the run arrays, which the device path never copies). */
-enum { BSCGPU_PCNT_DEVICE_MODEL_BLOCKS = 1, BSCGPU_PCNT_REDONE_ON_HOST_MODEL = 2, BSCGPU_PCNT_DEVICE_MODEL_LZP_BLOCKS = 3 };
+ * be stored raw from the run arrays, which the device path never copies); _DEVICE_LZP_BLOCKS: runs of the device's LZP stage in front
+ * of a sorter (BSCGPU_OPT_DEVICE_LZP, BSC_DEVICE_LZP=1 for bsc_compress, bscgpu_compress_device_lzp), a redo's second run included. */
+enum { BSCGPU_PCNT_DEVICE_MODEL_BLOCKS = 1, BSCGPU_PCNT_REDONE_ON_HOST_MODEL = 2, BSCGPU_PCNT_DEVICE_MODEL_LZP_BLOCKS = 3,
+       BSCGPU_PCNT_DEVICE_LZP_BLOCKS = 4 };
 BSCGPU_API long long bscgpu_process_counter(int key);
 
 /* ---- how the libbsc.h entry points spread concurrent callers over the GPUs of a node (pure functions, no GPU needed) -------------

@@ -13,7 +13,7 @@ i32p = C.POINTER(C.c_int)
 u32p = C.POINTER(C.c_uint32)
 
 K_NAMES = ["radix_scatter", "radix_hist", "radix_scan", "pack", "seg", "gather", "emit", "misc",
-           "dc_ctx", "dc_part", "dc_eval", "dc_pstream", "radix_hist_all", "radix_aux", "rc", "dc_facts", "dc_replay"]      # order of the BSCGPU_K_* enum (include/bscgpu.h)
+           "dc_ctx", "dc_part", "dc_eval", "dc_pstream", "radix_hist_all", "radix_aux", "rc", "dc_facts", "dc_replay", "lzp"]      # order of the BSCGPU_K_* enum (include/bscgpu.h)
 
 
 class RcStream(C.Structure):
@@ -138,6 +138,11 @@ def lib():
     L.bscgpu_rc_encode.argtypes = [vp, C.c_int, vp, C.c_int64, vp, C.c_int, vp, C.c_int, vp, C.c_int64, vp, C.c_int]
     if hasattr(L, "bscgpu_compress_device"):
         L.bscgpu_compress_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    if hasattr(L, "bscgpu_lzp_staged_host"):
+        L.bscgpu_lzp_staged_host.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+        L.bscgpu_lzp_compress.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.bscgpu_lzp_compress_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.bscgpu_compress_device_lzp.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     _lib = L
     return L
 

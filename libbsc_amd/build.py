@@ -113,7 +113,8 @@ def _command(src, obj, asan=False):
 
 
 def _compile(src, force, asan=False):
-    name = os.path.splitext(os.path.basename(src))[0]
+    # device/lzp.hip and host/lzp.cpp are two translation units: the object carries its directory's name
+    name = os.path.basename(os.path.dirname(src)) + "_" + os.path.splitext(os.path.basename(src))[0]
     obj = os.path.join(ASAN_OBJ if asan else OBJ, name + ".o")
     stamp = obj + ".sha1"
     want = _deps_hash(src, asan)
@@ -137,6 +138,13 @@ def build(force=False, verbose=True, asan=False):
         res = list(ex.map(lambda s: _compile(s, force, asan), srcs))
     objs = [o for o, _ in res]
     changed = any(c for _, c in res)
+    # objects of sources that are gone or were named otherwise (an incrementally built tree): whoever links `obj/*.o` must not find them
+    objdir = ASAN_OBJ if asan else OBJ
+    for f in os.listdir(objdir):
+        if f.endswith(".o") and os.path.join(objdir, f) not in objs:
+            for stale in (f, f + ".sha1"):
+                if os.path.exists(os.path.join(objdir, stale)):
+                    os.remove(os.path.join(objdir, stale))
     if changed or force or not os.path.exists(LIB):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB] + objs + ["-lpthread", "-Wl,-Bsymbolic"]
 

@@ -200,6 +200,7 @@ extern "C" int bscgpu_create(bscgpu_ctx** out, int device, int64_t max_n)
     { const char* e = getenv("BSC_PS13"); c->dc_p13 = (e && e[0] == '0') ? 0 : 1; }       // BSCGPU_OPT_DC_PACKED_STREAM
     { const char* e = getenv("BSC_DC_ARENA_DIV"); const int k = e ? atoi(e) : 1; c->dc_arena_div = (k == 2 || k == 4 || k == 8) ? k : 1; }   // BSCGPU_OPT_DC_ARENA_DIV
     { const char* e = getenv("BSC_DC_AVG_EXACT"); c->dc_avg_exact = (e && e[0] == '1') ? 1 : 0; }      // BSCGPU_OPT_DC_AVG_EXACT
+    { const char* e = getenv("BSC_DEVICE_LZP"); c->device_lzp = (e && e[0] == '1') ? 1 : 0; }      // BSCGPU_OPT_DEVICE_LZP
     { const char* e = getenv("BSC_DC_REPLAY_EXACT"); c->dc_replay_exact = (e && e[0] == '1') ? 1 : 0; }      // BSCGPU_OPT_DC_REPLAY_EXACT
     { const char* e = getenv("BSC_DC_HIST_EXACT"); c->dc_hist_exact = (e && e[0] == '1') ? 1 : 0; }      // BSCGPU_OPT_DC_HIST_EXACT
     { const char* e = getenv("BSC_DC_REPLAY_CAND"); const long long v = e ? atoll(e) : 0; if (v >= 1 && v <= 0xffffffffll) c->dc_replay_cand = (u32)v; }   // devcoder.hip 3': the guard
@@ -358,6 +359,7 @@ extern "C" int bscgpu_option_set(bscgpu_ctx* c, int key, int value)
     if (key == BSCGPU_OPT_RS_ONESWEEP && value >= 0 && value <= 3 && (value == 0 || c->os_available)) { const int old = c->os_mode; c->os_mode = value; return old; }
     if (key == BSCGPU_OPT_DC_PACKED_STREAM && (value == 0 || value == 1)) { const int old = c->dc_p13; c->dc_p13 = value; return old; }
     if (key == BSCGPU_OPT_DC_AVG_EXACT && (value == 0 || value == 1)) { const int old = c->dc_avg_exact; c->dc_avg_exact = value; return old; }
+    if (key == BSCGPU_OPT_DEVICE_LZP && (value == 0 || value == 1)) { const int old = c->device_lzp; c->device_lzp = value; return old; }
     if (key == BSCGPU_OPT_DC_REPLAY_EXACT && (value == 0 || value == 1)) { const int old = c->dc_replay_exact; c->dc_replay_exact = value; return old; }
     if (key == BSCGPU_OPT_DC_HIST_EXACT && (value == 0 || value == 1)) { const int old = c->dc_hist_exact; c->dc_hist_exact = value; return old; }
     if (key == BSCGPU_OPT_BATCH_FRONT && (value == 0 || value == 1)) { const int old = c->batch_front; c->batch_front = value; return old; }
@@ -417,6 +419,13 @@ extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
     if (key == BSCGPU_OPT_BWT_FOLD) return c->bwt_fold;
     if (key == BSCGPU_CNT_BWT_FOLDED) return c->cnt_bwt_folded;
     if (key == BSCGPU_OPT_DC_ARENA_DIV) return c->dc_arena_div;
+    if (key == BSCGPU_OPT_DEVICE_LZP) return c->device_lzp;
+    if (key == BSCGPU_CNT_LZP_BLOCKS) return c->cnt_lzp_blocks;
+    if (key == BSCGPU_CNT_LZP_DECLINED) return c->cnt_lzp_declined;
+    if (key >= BSCGPU_CNT_LZP_MATCHES && key <= BSCGPU_CNT_LZP_RAW_CHUNKS) {      // (in the order of lzp_staged.h's CNT_*)
+        const int64_t v = c->lzp_last[key - BSCGPU_CNT_LZP_MATCHES];
+        return v > 0x7fffffff ? 0x7fffffff : (int)v;
+    }
     if (key == BSCGPU_CNT_DC_BLOCK_SEGMENTS) return c->cnt_block_segments;
     return BSC_BAD_PARAMETER;
 }

@@ -226,6 +226,11 @@ struct bscgpu_ctx {
     int  bwt_fold = 1;               // BSCGPU_OPT_BWT_FOLD: 0 off, 1 packing also counts the remaining digits, 2 it leaves that to rs_hist_all
     int  cnt_bwt_folded = 0;         // BSCGPU_CNT_BWT_FOLDED
     bool fold_lds_set = false;       // the packing kernels' dynamic-LDS limit has been raised on this context's device
+    // the LZP stage (lzp.hip)
+    int  device_lzp = 0;             // BSCGPU_OPT_DEVICE_LZP: a host block with LZP goes up raw and is preprocessed on the device (BSC_DEVICE_LZP=1)
+    int  cnt_lzp_blocks = 0, cnt_lzp_declined = 0;   // BSCGPU_CNT_LZP_BLOCKS / _DECLINED: blocks the route gave to the stage / that it declined
+    int64_t lzp_last[5] = {0, 0, 0, 0, 0};           // BSCGPU_CNT_LZP_MATCHES .. _RAW_CHUNKS of the last block given to the stage (lzp_staged.h: CNT_*)
+    int  lzp_lds_set = 0;            // sweep variants whose dynamic-LDS limit has been raised on this context's device (bit mask)
     u32  ub_step_cap = UB_STEP_CAP;  // inverse BWT: a walk longer than this between two marked rows is declined (BSC_UNBWT_STEP_CAP, a test knob)
     // pinned host
     u32* hscal  = nullptr;   // SCAL_WORDS u32 (the slot map is above)
@@ -338,6 +343,10 @@ int unbwt_batch_max_blocks(int64_t cap);
 int unbwt_batch_pass(bscgpu_ctx* c, const u8* dL, u8* out, const int* sizes, const int* idx, int count, const u32* dst, int* res,
                      u32* adler, u8* t_host);
 int adler32_device(bscgpu_ctx* c, const u8* d, int64_t n, u32* out);
+// The LZP encoder stage (lzp.hip): dIn (HBM, n bytes; may be c->dT or dOut) -> what lzp_compress returns, with the same
+// bytes in dOut (HBM, n bytes; may be c->dL); hashSize 10..15, else BSC_NOT_SUPPORTED before anything is launched.  One sync; the
+// frame's copies into dOut are queued behind it, final_sync waits for them too.  c->lzp_last: the paths taken.
+int lzp_device(bscgpu_ctx* c, const u8* dIn, u8* dOut, int n, int hashSize, int minLen, int features, bool final_sync);
 void launch_seg_scan(bscgpu_ctx* c, u32 num_chunks);
 // The QLFC front end's view of the sort buffers (qlfc_front.hip).  Once a block's (a pass's) L has been emitted nothing of the sorter
 // is live until the next sorter starts, and the front end and whoever reads its run arrays — the copy down, the device model — take

@@ -30,6 +30,7 @@
 #include "container.h"
 #include "qlfc.h"
 #include "lzp.h"
+#include "lzp_staged.h"
 #include "par.h"
 
 using namespace bschost;
@@ -326,6 +327,9 @@ struct BlockJob {
     int n_orig = 0;                  // size of the original block; n below is what the sorter sees (LZP output or the same)
     bool have_adler = false, inplace = false;
     std::unique_ptr<unsigned char, void (*)(void*)> lz{nullptr, nullptr};   // LZP output while the block is in flight
+    // BSCGPU_OPT_DEVICE_LZP: the block goes up raw and the device stage (lzp.hip) writes the sorter's input; lz is not made
+    bool dev_lzp = false; int lzp_hash = 0, lzp_min = 0, mode_with_lzp = 0;
+    const void* dRaw = nullptr;      // ... the raw block in HBM where the caller's input is there (bscgpu_compress_device_lzp); null: it is uploaded from hInput
     int n = 0, coder = 0, features = 0, mode = 0, index = 0, num_indexes = 0, nblocks = 0;
     int indexes[256];
     uint32_t adler_data = 0;
@@ -370,7 +374,7 @@ static double ms_since(clk::time_point t0) { return std::chrono::duration<double
 static bool devcoder_enabled() { static const int v = [] { const char* e = getenv("BSC_DEVICE_CODER"); return e ? atoi(e) : 1; }(); return v != 0; }
 static int  devcoder_min_n() { static const int v = [] { const char* e = getenv("BSC_DEVICE_CODER_MIN_N"); return e ? atoi(e) : (1 << 20); }(); return v; }
 
-static std::atomic<uint64_t> g_count_devmodel{0}, g_count_redo{0}, g_count_devmodel_lzp{0};     // bscgpu_process_counter
+static std::atomic<uint64_t> g_count_devmodel{0}, g_count_redo{0}, g_count_devmodel_lzp{0}, g_count_device_lzp{0};     // bscgpu_process_counter
 
 // the entry form of a device-model block's probability stream (include/bscgpu.h)
 static int ps_form(const BlockJob& J) { return J.ps_packed ? BSCGPU_RC_STATIC13 : J.coder == LIBBSC_CODER_QLFC_FAST ? BSCGPU_RC_FAST16 : BSCGPU_RC_STATIC16; }
@@ -636,7 +640,7 @@ static int stage_model(BlockJob& J, u32 m, bool* took)
     // the block is the device model's: the host codes from the landing zone, or has nothing left to code
     *took = J.use_ps = true; J.ps = J.rc_done ? nullptr : J.slot->hps; J.ndec = ndec;
     g_count_devmodel.fetch_add(1, std::memory_order_relaxed);
-    if (J.lz) g_count_devmodel_lzp.fetch_add(1, std::memory_order_relaxed);
+    if (J.lz || (J.dev_lzp && block_mode_has_lzp(J.mode))) g_count_devmodel_lzp.fetch_add(1, std::memory_order_relaxed);
     return LIBBSC_NO_ERROR;
 }
 
@@ -826,7 +830,7 @@ static void host_encode_group(BlockJob& J, int b)
 static void write_stored(BlockJob& J)
 {
     if (J.hInput) { J.result = J.inplace ? LIBBSC_NOT_COMPRESSIBLE : bsc_store(J.hInput, J.output, J.n_orig, J.features); return; }   // libbsc.cpp:188, :315
-    J.result = store_from_device(J.c, J.dInput, J.output, J.n_orig, J.adler_data);
+    J.result = store_from_device(J.c, J.dRaw ? J.dRaw : J.dInput, J.output, J.n_orig, J.adler_data);
 }
 
 // result: the payload's bytes at block_body(J.output), or the coder's negative code
@@ -920,12 +924,20 @@ static void host_stage(BlockJob& J)
 
 // Host-resident block -> job, part 1 (no GPU involved): optional LZP on the host (lzp.cpp:798 semantics).  `sorter` may be
 // changed (a tiny LZP output is always BWT-sorted, libbsc.cpp:277-281).
+// device_lzp (BSCGPU_OPT_DEVICE_LZP): a block with LZP whose parameters the device stage takes is left raw here — stage_host_h2d
+// uploads it and runs the stage (stage_device_lzp); *declined says that the block has LZP and the stage does not take it.
+static bool device_lzp_takes(int lzpHashSize) { return lzpHashSize >= 10 && lzpHashSize <= lzp::STAGED_MAX_HASH; }
 static int stage_host_lzp(BlockJob& J, const unsigned char* input, unsigned char* output, int n,
-                          int lzpHashSize, int lzpMinLen, int* sorter, int coder, int features, int mode)
+                          int lzpHashSize, int lzpMinLen, int* sorter, int coder, int features, int mode,
+                          bool device_lzp = false, bool* declined = nullptr)
 {
     int lzSize = n;
     J.lz.reset();
-    if (block_mode_has_lzp(mode)) {
+    J.dev_lzp = false; J.dRaw = nullptr;
+    if (declined) *declined = device_lzp && block_mode_has_lzp(mode) && !device_lzp_takes(lzpHashSize);
+    if (device_lzp && block_mode_has_lzp(mode) && device_lzp_takes(lzpHashSize)) {
+        J.dev_lzp = true; J.lzp_hash = lzpHashSize; J.lzp_min = lzpMinLen; J.mode_with_lzp = mode;
+    } else if (block_mode_has_lzp(mode)) {
         J.lz = std::unique_ptr<unsigned char, void (*)(void*)>((unsigned char*)bigbuf_get((size_t)n), bigbuf_put);   // (par.h: a few block-sized buffers are kept)
         if (!J.lz) return LIBBSC_NOT_ENOUGH_MEMORY;
         const int r = lzp_compress(input, J.lz.get(), n, lzpHashSize, lzpMinLen, features);
@@ -938,11 +950,36 @@ static int stage_host_lzp(BlockJob& J, const unsigned char* input, unsigned char
     if (J.lz) { J.adler_data = adler32(input, (size_t)n); J.have_adler = true; }
     return LIBBSC_NO_ERROR;
 }
+// The LZP stage of a raw block in HBM (c->dT after an upload, or J.dRaw): Adler-32 of the original, then the sorter's input into c->dL.
+// A block the stage finds not compressible goes on without LZP (libbsc.cpp:266-269).  Repeatable: a redo runs it again.
+static int stage_device_lzp(BlockJob& J, bscgpu_ctx* c)
+{
+    const u8* raw = J.dRaw ? (const u8*)J.dRaw : c->dT;
+    int rc = adler32_device(c, raw, J.n_orig, &J.adler_data);
+    if (rc < 0) return rc;
+    J.have_adler = true;
+    const int r = lzp_device(c, raw, c->dL, J.n_orig, J.lzp_hash, J.lzp_min, J.features, false);
+    ++c->cnt_lzp_blocks;
+    g_count_device_lzp.fetch_add(1, std::memory_order_relaxed);
+    if (r < 0 && r != LIBBSC_NOT_COMPRESSIBLE) return r;
+    // (a coded block is 1 + 4 + the tail behind `limit`, 36 bytes and more: never as small as a header, so the sorter stays the caller's)
+    if (r >= 0 && r <= LIBBSC_HEADER_SIZE) return LIBBSC_GPU_ERROR;
+    if (r < 0 && hipMemcpyAsync(c->dL, raw, (size_t)J.n_orig, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return LIBBSC_GPU_ERROR;
+    J.n = r < 0 ? J.n_orig : r;
+    J.mode = r < 0 ? block_mode_without_lzp(J.mode_with_lzp) : J.mode_with_lzp;
+    J.dInput = c->dL;
+    return LIBBSC_NO_ERROR;
+}
+
 // part 2: one H2D copy of what the sorter will see into the context's text buffer
 static int stage_host_h2d(BlockJob& J, bscgpu_ctx* c)
 {
     J.c = c; J.dInput = c->dL;
     if (hipSetDevice(c->device) != hipSuccess) return LIBBSC_GPU_ERROR;
+    if (J.dev_lzp) {                                            // the raw block goes up; the stage makes the sorter's input of it
+        if (hipMemcpyAsync(c->dT, J.hInput, (size_t)J.n_orig, hipMemcpyHostToDevice, c->stream) != hipSuccess) return LIBBSC_GPU_ERROR;
+        return stage_device_lzp(J, c);
+    }
     const unsigned char* data = J.lz ? J.lz.get() : J.hInput;
     if (hipMemcpyAsync(c->dL, data, (size_t)J.n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return LIBBSC_GPU_ERROR;
     return LIBBSC_NO_ERROR;
@@ -954,6 +991,7 @@ extern "C" BSCGPU_API long long bscgpu_process_counter(int key)
         case BSCGPU_PCNT_DEVICE_MODEL_BLOCKS:     return (long long)g_count_devmodel.load(std::memory_order_relaxed);
         case BSCGPU_PCNT_REDONE_ON_HOST_MODEL:    return (long long)g_count_redo.load(std::memory_order_relaxed);
         case BSCGPU_PCNT_DEVICE_MODEL_LZP_BLOCKS: return (long long)g_count_devmodel_lzp.load(std::memory_order_relaxed);
+        case BSCGPU_PCNT_DEVICE_LZP_BLOCKS:       return (long long)g_count_device_lzp.load(std::memory_order_relaxed);
     }
     return LIBBSC_BAD_PARAMETER;
 }
@@ -967,7 +1005,8 @@ static int redo_on_host_model(BlockJob& J)
     g_count_redo.fetch_add(1, std::memory_order_relaxed);
     J.redo.store(false, std::memory_order_relaxed);
     int rc = LIBBSC_NO_ERROR;
-    if (J.hInput) rc = stage_host_h2d(J, J.c);
+    if (J.hInput) rc = stage_host_h2d(J, J.c);                 // (with the device's LZP stage: upload and stage again — deterministic)
+    else if (J.dev_lzp) rc = stage_device_lzp(J, J.c);
     if (rc >= 0) rc = gpu_stage(J, J.sorter, false);
     J.lz.reset();
     if (rc < 0) { J.result = rc; return rc; }
@@ -993,7 +1032,10 @@ int bsc_compress(const unsigned char* input, unsigned char* output, int n, int l
     if (n <= LIBBSC_HEADER_SIZE) return bsc_store(input, output, n, features);
 
     std::unique_ptr<BlockJob> J(new BlockJob);
-    rc = stage_host_lzp(*J, input, output, n, lzpHashSize, lzpMinLen, &blockSorter, coder, features, mode);
+    // (the default contexts are not the caller's to set options on: BSC_DEVICE_LZP as it stands at the call decides)
+    const char* const dl_env = getenv("BSC_DEVICE_LZP");
+    bool declined = false;
+    rc = stage_host_lzp(*J, input, output, n, lzpHashSize, lzpMinLen, &blockSorter, coder, features, mode, dl_env && dl_env[0] == '1', &declined);
     if (rc < 0) return rc;
     DefaultGpuUser user(J->n, true);
     if (user.rc != LIBBSC_NO_ERROR) return user.rc;
@@ -1001,6 +1043,7 @@ int bsc_compress(const unsigned char* input, unsigned char* output, int n, int l
     {
         std::lock_guard<std::mutex> g(user.dev->gpu_lock);      // GPU stage; concurrent callers on this device queue here
         if (hipSetDevice(c->device) != hipSuccess) return LIBBSC_GPU_ERROR;
+        if (declined) ++c->cnt_lzp_declined;
         rc = ctx_ensure_slots(c, user.slot + 1);
         if (rc < 0) return rc;
         J->slot = &c->slots[user.slot];
@@ -1039,6 +1082,7 @@ static int prepare_job(BlockJob& J, bscgpu_ctx* c, const void* dInput, uint8_t* 
     if (n < 0 || n > c->max_n) return LIBBSC_BAD_PARAMETER;
     J.c = c; J.dInput = dInput; J.output = output; J.n = n; J.n_orig = n; J.coder = coder; J.features = features;
     J.hInput = nullptr; J.have_adler = false; J.inplace = false; J.lz.reset();
+    J.dev_lzp = false; J.dRaw = nullptr;
     J.stored_small = false; J.result = 0;
     return LIBBSC_NO_ERROR;
 }
@@ -1050,6 +1094,34 @@ int bscgpu_compress_device(bscgpu_ctx* c, const void* dInput, uint8_t* output, i
     int rc = prepare_job(*J, c, dInput, output, n, blockSorter, coder, features);
     if (rc < 0) return rc;
     J->slot = &c->slots[0];
+    rc = gpu_stage(*J, blockSorter);
+    if (rc < 0) return rc;
+    const auto t0 = clk::now();
+    host_stage(*J);
+    if (J->redo.load(std::memory_order_relaxed)) redo_on_host_model(*J);
+    c->stage_ms[3] = ms_since(t0);
+    c->stage_ms[4] = ms_since(t_all);
+    return J->result;
+}
+
+int bscgpu_compress_device_lzp(bscgpu_ctx* c, const void* dInput, uint8_t* output, int n, int lzpHashSize, int lzpMinLen,
+                               int blockSorter, int coder, int features)
+{
+    if (lzpHashSize == 0 && lzpMinLen == 0) return bscgpu_compress_device(c, dInput, output, n, blockSorter, coder, features);
+    const auto t_all = clk::now();
+    std::unique_ptr<BlockJob> J(new BlockJob);
+    int rc = prepare_job(*J, c, dInput, output, n, blockSorter, coder, features);
+    if (rc < 0) return rc;
+    rc = make_mode(blockSorter, coder, lzpHashSize, lzpMinLen, &J->mode);
+    if (rc != LIBBSC_NO_ERROR) return rc;
+    if (!device_lzp_takes(lzpHashSize)) return LIBBSC_NOT_SUPPORTED;
+    J->slot = &c->slots[0];
+    if (n > LIBBSC_HEADER_SIZE) {                               // (a block as small as a header is stored, LZP or not)
+        if (hipSetDevice(c->device) != hipSuccess) return LIBBSC_GPU_ERROR;
+        J->dev_lzp = true; J->dRaw = dInput; J->lzp_hash = lzpHashSize; J->lzp_min = lzpMinLen; J->mode_with_lzp = J->mode;
+        rc = stage_device_lzp(*J, c);
+        if (rc < 0) return rc;
+    }
     rc = gpu_stage(*J, blockSorter);
     if (rc < 0) return rc;
     const auto t0 = clk::now();
@@ -1419,8 +1491,10 @@ int bscgpu_pipe_submit_host(bscgpu_pipe* p, const uint8_t* input, uint8_t* outpu
         J.stored_small = true;
         return pipe_enqueue(p, L, ticket);
     }
-    rc = stage_host_lzp(J, input, output, n, lzpHashSize, lzpMinLen, &blockSorter, coder, features, mode);
+    bool declined = false;
+    rc = stage_host_lzp(J, input, output, n, lzpHashSize, lzpMinLen, &blockSorter, coder, features, mode, p->c->device_lzp != 0, &declined);
     if (rc < 0) return rc;
+    if (declined) ++p->c->cnt_lzp_declined;
     rc = stage_host_h2d(J, p->c);
     if (rc < 0) return rc;
     rc = gpu_stage(J, blockSorter);
@@ -1606,8 +1680,10 @@ static int compress_one_on_ctx(bscgpu_ctx* c, const unsigned char* input, unsign
     if (n <= LIBBSC_HEADER_SIZE) return bsc_store(input, output, n, features);
     if (n > c->max_n) return LIBBSC_GPU_NOT_ENOUGH_MEMORY;        // (the call's context is not resized: bscgpu.h)
     std::unique_ptr<BlockJob> J(new BlockJob);
-    rc = stage_host_lzp(*J, input, output, n, lzpHashSize, lzpMinLen, &blockSorter, coder, features, mode);
+    bool declined = false;
+    rc = stage_host_lzp(*J, input, output, n, lzpHashSize, lzpMinLen, &blockSorter, coder, features, mode, c->device_lzp != 0, &declined);
     if (rc < 0) return rc;
+    if (declined) ++c->cnt_lzp_declined;
     if (J->n > c->max_n) return LIBBSC_GPU_NOT_ENOUGH_MEMORY;
     if (hipSetDevice(c->device) != hipSuccess) return LIBBSC_GPU_ERROR;
     rc = ctx_ensure_slots(c, 1);

@@ -1,5 +1,8 @@
-// lzp.cpp — LZP preprocessor, encoder side.  Host code: the predictor is one sequential hash chain per
-// chunk, at most 8 chunks per block, so there is nothing here for the GPU.
+// lzp.cpp — LZP preprocessor, encoder side, on the host.  The scanner below walks one hash table per chunk, at most 8
+// chunks per block, position by position; that walk is sequential, the work is not: device/lzp.hip computes the same stream for the
+// narrow tables (hashSize <= 15) from links and flags made in parallel and a sweep that asks a real table only behind a match
+// (lzp_staged.cpp is that algorithm on the CPU).  This file stays the definition both are held to, and the route every
+// block takes unless BSCGPU_OPT_DEVICE_LZP is set.
 //
 // Stream format and match decisions are fixed by the reference (libbsc/lzp/lzp.cpp): the decoder mirrors the
 // encoder's hash table, so *which* positions become matches is part of the format in practice — a different but valid
@@ -24,18 +27,20 @@
 
 #include "qlfc.h"
 #include "lzp.h"
+#include "lzp_staged.h"
 #include "container.h"
 
 namespace bschost {
 
 namespace {
 
-constexpr uint8_t FLAG = 0xF2;
+using lzp::FLAG;
+using lzp::slot_of;
+using lzp::narrow_guard;
 
 inline uint32_t ld32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }
 inline uint64_t ld64(const uint8_t* p) { uint64_t v; memcpy(&v, p, 8); return v; }
 inline uint32_t ctx_at(const uint8_t* p) { return __builtin_bswap32(ld32(p - 4)); }        // previous four bytes, newest lowest
-inline uint32_t slot_of(uint32_t c, uint32_t mask) { return ((c >> 15) ^ c ^ (c >> 3)) & mask; }
 
 // Match length counted in 8-byte strides from `len` on, while the compared window starts before `limit`
 // (lzp.cpp:103-110): a stride that starts before the limit is compared in full.
@@ -174,15 +179,6 @@ int scan_wide(const uint8_t* in, const uint8_t* end, uint8_t* out, uint8_t* out_
     return finish_tail(base, p, end, out, o, eob, table, mask);
 }
 
-// Where the main phase of the narrow scanner stops, in bytes before the end of the chunk (lzp.cpp:56, :166, :276, :330).
-int narrow_guard(int minLen)
-{
-    if (minLen == 4) return 4 + 32;
-    if (minLen <= 8) return 8 + 32;
-    if (minLen <= 16) return 16 + 32;
-    return minLen + 32;
-}
-
 }  // namespace
 
 // ---- bigbuf: see par.h ----------------------------------------------------------------------------------------------------------------
@@ -236,13 +232,7 @@ void bigbuf_put(void* p)
     free(p);                                                            // (also: a small request that never entered the cache)
 }
 
-int lzp_num_chunks(int n)                                   // lzp.cpp:44-51
-{
-    if (n < 256 * 1024) return 1;
-    if (n < 4 * 1024 * 1024) return 2;
-    if (n < 16 * 1024 * 1024) return 4;
-    return 8;
-}
+int lzp_num_chunks(int n) { return lzp::num_chunks(n); }
 
 int lzp_encode_chunk(const uint8_t* in, int n, uint8_t* out, int out_cap, int hashSize, int minLen)   // lzp.cpp:529
 {

@@ -211,10 +211,36 @@ class GpuContext:
                                                    _dptr(dOut), N.np_ptr(res), int(streams_per_wave)))
         return [int(x) for x in res[:len(st)]]
 
-    def compress_device(self, dInput, n, sorter=1, coder=1, features=3):
+    def compress_device(self, dInput, n, sorter=1, coder=1, features=3, lzp_hash=0, lzp_min=0):
+        """bsc_compress of n bytes in HBM -> the block (np.uint8).  lzp_hash / lzp_min: with the LZP stage in front
+        (bscgpu_compress_device_lzp; lzp_hash 10..15, else the stage declines: GpuError LIBBSC_NOT_SUPPORTED)"""
         out = np.empty(n + 28, np.uint8)
-        rc = self._check(self.L.bscgpu_compress_device(self.h, _dptr(dInput), N.np_ptr(out), n, sorter, coder, features))
+        if lzp_hash or lzp_min:
+            rc = self._check(self.L.bscgpu_compress_device_lzp(self.h, _dptr(dInput), N.np_ptr(out), n, lzp_hash, lzp_min, sorter, coder, features))
+        else:
+            rc = self._check(self.L.bscgpu_compress_device(self.h, _dptr(dInput), N.np_ptr(out), n, sorter, coder, features))
         return out[:rc]
+
+    # ---- the LZP encoder stage (include/bscgpu.h; DESIGN §3.9) --------------------------------
+    def lzp_compress(self, data, hash_size, min_len, features=3, device=False):
+        """bscgpu_lzp_compress: bsc_lzp_compress on the GPU -> bytes, or the negative libbsc code (LIBBSC_NOT_COMPRESSIBLE,
+        LIBBSC_NOT_SUPPORTED for hash_size >= 16).  device=True: `data` is a uint8 device tensor and the stage runs from HBM to HBM
+        (bscgpu_lzp_compress_device).  lzp_counters() says which paths the block took."""
+        if device:
+            import torch
+            n = int(data.numel())
+            dout = torch.empty(max(n, 1), dtype=torch.uint8, device=data.device)
+            r = self.L.bscgpu_lzp_compress_device(self.h, _dptr(data), _dptr(dout), n, hash_size, min_len, features)
+            return dout[:r].cpu().numpy().tobytes() if r >= 0 else r
+        a = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8)
+        inp = a if a.size else np.zeros(1, np.uint8)
+        out = np.empty(a.size + 64, np.uint8)
+        r = self.L.bscgpu_lzp_compress(self.h, N.np_ptr(inp), N.np_ptr(out), a.size, hash_size, min_len, features)
+        return out[:r].tobytes() if r >= 0 else r
+
+    def lzp_counters(self):
+        """the last block given to the LZP stage: dict(matches, dirty, serial_zones, escapes, raw_chunks)"""
+        return {k: self.option_get(self.CNT_LZP_MATCHES + i) for i, k in enumerate(LZP_COUNTERS)}
 
     # ---- batches of small blocks (one suffix sort per pass, include/bscgpu.h) ----------------
     def bwt_batch(self, dT, sizes, aux=True, dL=None):
@@ -462,6 +488,10 @@ class GpuContext:
     OPT_DC_HIST_EXACT, CNT_DC_HIST_RESOLVED = 34, 35    # open run_hist brackets resolved exactly on the device; runs that settled (get only)
     # the device model's arena carved for max_n / k (1, 2, 4, 8; a block above it runs in sub-block segments); segments of the last block (get only)
     OPT_DC_ARENA_DIV, CNT_DC_BLOCK_SEGMENTS = 36, 37
+    # host blocks with LZP are preprocessed on the device (default 0); blocks that took that route / that the stage declined; the paths of
+    # the last block given to the stage (get only): matches, dirty look-ups, failed verifies, escaped literals, chunks kept raw
+    OPT_DEVICE_LZP, CNT_LZP_BLOCKS, CNT_LZP_DECLINED = 45, 46, 47
+    CNT_LZP_MATCHES, CNT_LZP_DIRTY, CNT_LZP_SERIAL_ZONES, CNT_LZP_ESCAPES, CNT_LZP_RAW_CHUNKS = 48, 49, 50, 51, 52
     DC_FAIL_AVG, DC_FAIL_HIST, DC_FAIL_CAP, DC_FAIL_REPLAY, DC_FAIL_MIX = 2, 4, 8, 16, 32          # BSCGPU_DC_FAIL_*
 
     def option_set(self, key, value):
@@ -499,6 +529,19 @@ RC_STATIC16, RC_STATIC13, RC_FAST16 = 0, 1, 2      # BSCGPU_RC_*: the form of a 
 RC_REFILL = 128                                    # BSCGPU_RC_REFILL: decisions a wavefront stages per stream and refill
 RC_PREFIX_MAX = 32 + 256 * 8                       # BSCGPU_RC_PREFIX_MAX
 NOT_COMPRESSIBLE = -3                              # LIBBSC_NOT_COMPRESSIBLE
+NOT_SUPPORTED = -4                                 # LIBBSC_NOT_SUPPORTED
+LZP_COUNTERS = ("matches", "dirty", "serial_zones", "escapes", "raw_chunks")     # BSCGPU_CNT_LZP_MATCHES .. _RAW_CHUNKS
+
+
+def lzp_staged_host(data, hash_size, min_len, features=3):
+    """bscgpu_lzp_staged_host: the LZP stage's algorithm on the CPU (no GPU, no context) -> (bytes or the negative libbsc code,
+    dict of the path counters in the order of LZP_COUNTERS)"""
+    a = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8)
+    inp = a if a.size else np.zeros(1, np.uint8)
+    out = np.empty(a.size + 64, np.uint8)
+    cnt = np.zeros(len(LZP_COUNTERS), np.int64)
+    r = N.lib().bscgpu_lzp_staged_host(N.np_ptr(inp), N.np_ptr(out), a.size, hash_size, min_len, features, N.np_ptr(cnt))
+    return (out[:r].tobytes() if r >= 0 else r), dict(zip(LZP_COUNTERS, (int(x) for x in cnt)))
 
 
 def rc_streams(streams):
