@@ -176,6 +176,35 @@ BSCGPU_API int bscgpu_lzp_compress_device(bscgpu_ctx* ctx, const void* dIn, void
 BSCGPU_API int bscgpu_lzp_compress(bscgpu_ctx* ctx, const uint8_t* in, uint8_t* out, int n, int hashSize, int minLen, int features);
 BSCGPU_API int bscgpu_lzp_staged_host(const uint8_t* in, uint8_t* out, int n, int hashSize, int minLen, int features, int64_t* counters);
 
+/* ---- the LZP stage for all blocks of a pass ("A pass of small blocks") ----------
+ * bscgpu_lzp_batch_device: `count` blocks back to back at dIn (HBM), as in the other batch calls.  results[b] = what
+ *   bsc_lzp_compress(block b, hashSize, minLen, features) returns, a size or LIBBSC_NOT_COMPRESSIBLE; where it is a size the same bytes
+ *   lie in dOut (HBM, dIn's layout, sizes[b] bytes per block) at the block's own offset.  One key kernel, one sort, one link and one
+ *   flag kernel and one sweep with a workgroup per chunk for the whole pass; one copy of the chunks' results down, one sync, one gather
+ *   kernel for all frames.  dIn and dOut must not overlap; dIn is not modified.  Limits: count <= BSCGPU_ST_BATCH_MAX_BLOCKS, every
+ *   sizes[b] < BSCGPU_BATCH_MAX_N, the sum <= the context's max_n, hashSize 10..15 — hashSize >= 16: LIBBSC_NOT_SUPPORTED before
+ *   anything is launched; every other violation: LIBBSC_BAD_PARAMETER, nothing written.  Returns 0 or such a batch-level error.
+ *   BSCGPU_CNT_LZP_MATCHES .. _RAW_CHUNKS are the sums over the call's blocks.  Memory: on first use a context allocates the stage's
+ *   tables (709 KB of HBM, counted by bscgpu_arena_bytes from then on, and as much pinned host memory).
+ * bscgpu_lzp_batch_plan: the chunk table of such a pass as a pure function, one entry per chunk in pass order (arrays of 8192): its
+ *   block, its first byte in the pass, its size, and the bytes its sweep may write (sizes[b] - 2 for a block that is one chunk).  An
+ *   empty block, or one the encoder refuses by size (n - minLen < 32 or n - 2 < 16), owns no chunk.  Returns the number of chunks, or
+ *   LIBBSC_BAD_PARAMETER (count above 4096, a size negative or not below BSCGPU_BATCH_MAX_N, a sum of 2^31 - 1 or more, minLen outside
+ *   4..255) with nothing written.
+ * bscgpu_lzp_batch_frame: the frames of the pass from its chunks' own results own[k] (chunk k of the plan: its sweep's size or a
+ *   negative code), both framings: results[b] as above, and the list of pieces one gather kernel moves (arrays of 3 * 4096): source
+ *   (0 the sweep's staging area, 1 the raw input, 2 the table bytes), offset in the source (staging and input: in the pass), offset in
+ *   the output, length.  table: count * 17 bytes, the blocks' tables one behind the other.  raw_chunks (or NULL): chunks kept raw.
+ *   Returns the number of pieces.
+ * bscgpu_lzp_chunk_staged_host: the CPU stand-in's sweep of ONE chunk of n bytes under a budget of cap bytes -> its size (the bytes in
+ *   out, n bytes) or LIBBSC_NOT_COMPRESSIBLE: own[k] of the two calls above.  counters as bscgpu_lzp_staged_host's. */
+BSCGPU_API int bscgpu_lzp_batch_device(bscgpu_ctx* ctx, const void* dIn, void* dOut, const int* sizes, int count, int hashSize, int minLen,
+                                       int features, int* results);
+BSCGPU_API int bscgpu_lzp_batch_plan(const int* sizes, int count, int minLen, int* chunk_block, int* chunk_start, int* chunk_size, int* chunk_cap);
+BSCGPU_API int bscgpu_lzp_batch_frame(const int* sizes, int count, int minLen, int features, const int* own, int* results, int* piece_src,
+                                      int* piece_src_off, int* piece_dst_off, int* piece_len, unsigned char* table, int64_t* raw_chunks);
+BSCGPU_API int bscgpu_lzp_chunk_staged_host(const uint8_t* in, uint8_t* out, int n, int cap, int hashSize, int minLen, int64_t* counters);
+
 /* ---- batches of small blocks: one suffix sort for many blocks ------------------------------
  * Blocks are laid out back to back: block b starts at off_b = sizes[0] + ... + sizes[b-1].  Blocks below
  * BSCGPU_BATCH_MAX_N that the BWT sorts share one suffix sort per pass (at most max_n bytes and 4096 blocks,
@@ -193,6 +222,11 @@ BSCGPU_API int bscgpu_lzp_staged_host(const uint8_t* in, uint8_t* out, int n, in
  * bscgpu_compress_batch_device: the same for input in HBM, without LZP, results as bscgpu_compress_device's (a block
  *   larger than max_n: LIBBSC_BAD_PARAMETER).  Passes are sorted straight from dInput; checksums come from one
  *   segmented Adler-32 launch per pass; only L (and a stored block's own bytes) crosses PCIe.
+ * bscgpu_compress_batch_device_lzp: the same with bsc_compress's full parameter list.  Per pass one run of bscgpu_lzp_batch_device's
+ *   stage writes the sorter's input, the blocks' LZP streams back to back as the host route lays them out; a block the
+ *   stage finds not compressible goes on without LZP (libbsc.cpp:266-269); blocks outside a pass go one by one through
+ *   bscgpu_compress_device_lzp.  lzpHashSize == 0 and lzpMinLen == 0: bscgpu_compress_batch_device.  lzpHashSize >= 16:
+ *   LIBBSC_NOT_SUPPORTED at batch level, nothing written.  Same bytes as bsc_compress of every block.
  * Memory: on first use a context allocates the batch table (311 KB of HBM, counted by bscgpu_arena_bytes from then
  *   on) and two pinned host buffers of max_n bytes each (not HBM; kept until bscgpu_destroy).
  * bscgpu_batch_plan: the routing rule as a pure function: pass_of[b] = the pass of block b, or -1 for the
@@ -218,6 +252,8 @@ BSCGPU_API int bscgpu_compress_batch(bscgpu_ctx* ctx, const unsigned char* input
                                      int* results, int lzpHashSize, int lzpMinLen, int blockSorter, int coder, int features);
 BSCGPU_API int bscgpu_compress_batch_device(bscgpu_ctx* ctx, const void* dInput, const int* sizes, int count, unsigned char* output,
                                             int* results, int blockSorter, int coder, int features);
+BSCGPU_API int bscgpu_compress_batch_device_lzp(bscgpu_ctx* ctx, const void* dInput, const int* sizes, int count, unsigned char* output,
+                                                int* results, int lzpHashSize, int lzpMinLen, int blockSorter, int coder, int features);
 
 /* ---- the QLFC front end of a whole pass ---------------------------------------
  * What bsc_coder_compress does to a sorted block before any entropy coding — the sub-block split (coder.cpp:70-109), the run scan
@@ -734,13 +770,20 @@ BSCGPU_API const char* bscgpu_last_error(const bscgpu_ctx* ctx);
  *                          host block with LZP whose parameters the device stage takes (hashSize 10..15) goes up raw and
  *                          is preprocessed by bscgpu_lzp_compress_device's stage in front of the sorter, instead of by lzp_compress on the
  *                          submitting thread.  A block the stage declines takes the host route.  Same output.  The batched passes of
- *                          bscgpu_compress_batch keep host LZP.  bsc_compress runs on default contexts that no caller can set options on and
+ *                          bscgpu_compress_batch have an option of their own (BSCGPU_OPT_BATCH_DEVICE_LZP).  bsc_compress runs on default contexts that no caller can set options on and
  *                          decides, before it has one, whether LZP runs on the host: it takes the route from BSC_DEVICE_LZP=1 in the
  *                          environment AS IT STANDS AT THE CALL, not from the option of the context it then gets.
  * BSCGPU_CNT_LZP_BLOCKS    (get only) blocks that route gave to the stage; _LZP_DECLINED: blocks with LZP it left to the host because the
  *                          stage does not take their parameters.
- * BSCGPU_CNT_LZP_MATCHES   (get only, as the four that follow: of the LAST block given to the stage, by the route or by bscgpu_lzp_compress*,
- *                          summed over its chunks, saturating) matches taken; _LZP_DIRTY: positions visited whose predecessor a match had
+ * BSCGPU_OPT_BATCH_DEVICE_LZP  0 (default) / 1 (BSC_BATCH_DEVICE_LZP=1 in the environment, read when a context is created, sets the same): in
+ *                          bscgpu_compress_batch the members of a pass with LZP whose parameters the device stage takes (hashSize 10..15) go
+ *                          up raw, and one run of bscgpu_lzp_batch_device's stage per pass makes the sorter's input of them, as
+ *                          bscgpu_compress_batch_device_lzp does for input in HBM.  With hashSize >= 16 the pass keeps host LZP and
+ *                          BSCGPU_CNT_LZP_DECLINED counts it.  Same output.
+ * BSCGPU_CNT_BATCH_LZP_PASSES  (get only) passes, of either call, whose LZP ran as one stage on the device; _BATCH_LZP_BLOCKS: the blocks of
+ *                          those passes that went to the sorter.
+ * BSCGPU_CNT_LZP_MATCHES   (get only, as the four that follow: of the LAST block — or the last pass — given to the stage, by a route or by
+ *                          bscgpu_lzp_compress* / bscgpu_lzp_batch_device, summed over its chunks, saturating) matches taken; _LZP_DIRTY: positions visited whose predecessor a match had
  *                          skipped (they read the real table); _LZP_SERIAL_ZONES: failed verifies (minLen > 16), each followed by a stretch
  *                          run group by group; _LZP_ESCAPES: escaped literals (0xF2 0xFF); _LZP_RAW_CHUNKS: chunks kept raw by the framing.
  * Environment only, no option key: BSC_UNBWT_STEP_CAP (read when a context is created, like BSC_PS13; values below 16 are ignored) is the
@@ -765,7 +808,8 @@ enum { BSCGPU_OPT_RS_ONESWEEP = 1, BSCGPU_CNT_OS_RETRIES = 2, BSCGPU_OPT_DC_PACK
        BSCGPU_OPT_BATCH_ADAPTIVE_SEGMENTS = 44,
        BSCGPU_OPT_DEVICE_LZP = 45, BSCGPU_CNT_LZP_BLOCKS = 46, BSCGPU_CNT_LZP_DECLINED = 47,
        BSCGPU_CNT_LZP_MATCHES = 48, BSCGPU_CNT_LZP_DIRTY = 49, BSCGPU_CNT_LZP_SERIAL_ZONES = 50, BSCGPU_CNT_LZP_ESCAPES = 51,
-       BSCGPU_CNT_LZP_RAW_CHUNKS = 52 };
+       BSCGPU_CNT_LZP_RAW_CHUNKS = 52,
+       BSCGPU_OPT_BATCH_DEVICE_LZP = 53, BSCGPU_CNT_BATCH_LZP_PASSES = 54, BSCGPU_CNT_BATCH_LZP_BLOCKS = 55 };
 /* _FAIL_AVG: undecided avg_rank flags; _FAIL_HIST: a run_hist bracket open after 9216 predecessors (never with
  * BSCGPU_OPT_DC_HIST_EXACT); _FAIL_CAP: more runs or decisions
  * than the context's arena holds; _FAIL_REPLAY: a chain whose bracket stayed open over more than 64 evaluation chunks (with

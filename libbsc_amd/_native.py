@@ -143,6 +143,12 @@ def lib():
         L.bscgpu_lzp_compress.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]
         L.bscgpu_lzp_compress_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]
         L.bscgpu_compress_device_lzp.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    if hasattr(L, "bscgpu_lzp_batch_device"):
+        L.bscgpu_compress_batch_device_lzp.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.bscgpu_lzp_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+        L.bscgpu_lzp_batch_plan.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
+        L.bscgpu_lzp_batch_frame.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.bscgpu_lzp_chunk_staged_host.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     _lib = L
     return L
 

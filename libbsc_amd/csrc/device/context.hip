@@ -201,6 +201,7 @@ extern "C" int bscgpu_create(bscgpu_ctx** out, int device, int64_t max_n)
     { const char* e = getenv("BSC_DC_ARENA_DIV"); const int k = e ? atoi(e) : 1; c->dc_arena_div = (k == 2 || k == 4 || k == 8) ? k : 1; }   // BSCGPU_OPT_DC_ARENA_DIV
     { const char* e = getenv("BSC_DC_AVG_EXACT"); c->dc_avg_exact = (e && e[0] == '1') ? 1 : 0; }      // BSCGPU_OPT_DC_AVG_EXACT
     { const char* e = getenv("BSC_DEVICE_LZP"); c->device_lzp = (e && e[0] == '1') ? 1 : 0; }      // BSCGPU_OPT_DEVICE_LZP
+    { const char* e = getenv("BSC_BATCH_DEVICE_LZP"); c->batch_device_lzp = (e && e[0] == '1') ? 1 : 0; }      // BSCGPU_OPT_BATCH_DEVICE_LZP
     { const char* e = getenv("BSC_DC_REPLAY_EXACT"); c->dc_replay_exact = (e && e[0] == '1') ? 1 : 0; }      // BSCGPU_OPT_DC_REPLAY_EXACT
     { const char* e = getenv("BSC_DC_HIST_EXACT"); c->dc_hist_exact = (e && e[0] == '1') ? 1 : 0; }      // BSCGPU_OPT_DC_HIST_EXACT
     { const char* e = getenv("BSC_DC_REPLAY_CAND"); const long long v = e ? atoll(e) : 0; if (v >= 1 && v <= 0xffffffffll) c->dc_replay_cand = (u32)v; }   // devcoder.hip 3': the guard
@@ -268,6 +269,8 @@ extern "C" void bscgpu_destroy(bscgpu_ctx* c)
     if (c->batch_tab) { (void)hipFree(c->batch_tab); c->batch_tab = nullptr; c->batch_bytes = 0; }
     for (auto& hb : c->batch_host) if (hb) { (void)hipHostFree(hb); hb = nullptr; }
     if (c->rc_tab) { (void)hipFree(c->rc_tab); c->rc_tab = nullptr; c->rc_tab_bytes = 0; }
+    if (c->lzp_tab) { (void)hipFree(c->lzp_tab); c->lzp_tab = nullptr; c->lzp_tab_bytes = 0; }
+    if (c->lzp_tab_host) { (void)hipHostFree(c->lzp_tab_host); c->lzp_tab_host = nullptr; }
     if (c->front_tab) { (void)hipFree(c->front_tab); c->front_tab = nullptr; c->front_bytes = 0; }
     for (auto& hb : c->front_host) if (hb) { pinned_free(hb, c->front_host_bytes); hb = nullptr; }
     for (auto& hb : c->model_host) if (hb) { pinned_free(hb, c->model_host_entries * 2); hb = nullptr; }
@@ -293,7 +296,7 @@ extern "C" void bscgpu_destroy(bscgpu_ctx* c)
     delete c;
 }
 
-extern "C" int64_t bscgpu_arena_bytes(const bscgpu_ctx* c) { return c ? (int64_t)(c->arena_bytes + c->batch_bytes + c->front_bytes + c->rc_tab_bytes) + devcoder_batch_bytes(c) : 0; }
+extern "C" int64_t bscgpu_arena_bytes(const bscgpu_ctx* c) { return c ? (int64_t)(c->arena_bytes + c->batch_bytes + c->front_bytes + c->rc_tab_bytes + c->lzp_tab_bytes) + devcoder_batch_bytes(c) : 0; }
 extern "C" int64_t bscgpu_model_arena_bytes(const bscgpu_ctx* c) { return c ? devcoder_arena_bytes(c) : 0; }
 extern "C" const char* bscgpu_last_error(const bscgpu_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
@@ -360,6 +363,7 @@ extern "C" int bscgpu_option_set(bscgpu_ctx* c, int key, int value)
     if (key == BSCGPU_OPT_DC_PACKED_STREAM && (value == 0 || value == 1)) { const int old = c->dc_p13; c->dc_p13 = value; return old; }
     if (key == BSCGPU_OPT_DC_AVG_EXACT && (value == 0 || value == 1)) { const int old = c->dc_avg_exact; c->dc_avg_exact = value; return old; }
     if (key == BSCGPU_OPT_DEVICE_LZP && (value == 0 || value == 1)) { const int old = c->device_lzp; c->device_lzp = value; return old; }
+    if (key == BSCGPU_OPT_BATCH_DEVICE_LZP && (value == 0 || value == 1)) { const int old = c->batch_device_lzp; c->batch_device_lzp = value; return old; }
     if (key == BSCGPU_OPT_DC_REPLAY_EXACT && (value == 0 || value == 1)) { const int old = c->dc_replay_exact; c->dc_replay_exact = value; return old; }
     if (key == BSCGPU_OPT_DC_HIST_EXACT && (value == 0 || value == 1)) { const int old = c->dc_hist_exact; c->dc_hist_exact = value; return old; }
     if (key == BSCGPU_OPT_BATCH_FRONT && (value == 0 || value == 1)) { const int old = c->batch_front; c->batch_front = value; return old; }
@@ -422,6 +426,9 @@ extern "C" int bscgpu_option_get(bscgpu_ctx* c, int key)
     if (key == BSCGPU_OPT_DEVICE_LZP) return c->device_lzp;
     if (key == BSCGPU_CNT_LZP_BLOCKS) return c->cnt_lzp_blocks;
     if (key == BSCGPU_CNT_LZP_DECLINED) return c->cnt_lzp_declined;
+    if (key == BSCGPU_OPT_BATCH_DEVICE_LZP) return c->batch_device_lzp;
+    if (key == BSCGPU_CNT_BATCH_LZP_PASSES) return c->cnt_batch_lzp_passes;
+    if (key == BSCGPU_CNT_BATCH_LZP_BLOCKS) return c->cnt_batch_lzp_blocks;
     if (key >= BSCGPU_CNT_LZP_MATCHES && key <= BSCGPU_CNT_LZP_RAW_CHUNKS) {      // (in the order of lzp_staged.h's CNT_*)
         const int64_t v = c->lzp_last[key - BSCGPU_CNT_LZP_MATCHES];
         return v > 0x7fffffff ? 0x7fffffff : (int)v;

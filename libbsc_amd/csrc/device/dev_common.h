@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -230,7 +231,12 @@ struct bscgpu_ctx {
     int  device_lzp = 0;             // BSCGPU_OPT_DEVICE_LZP: a host block with LZP goes up raw and is preprocessed on the device (BSC_DEVICE_LZP=1)
     int  cnt_lzp_blocks = 0, cnt_lzp_declined = 0;   // BSCGPU_CNT_LZP_BLOCKS / _DECLINED: blocks the route gave to the stage / that it declined
     int64_t lzp_last[5] = {0, 0, 0, 0, 0};           // BSCGPU_CNT_LZP_MATCHES .. _RAW_CHUNKS of the last block given to the stage (lzp_staged.h: CNT_*)
+    int  batch_device_lzp = 0;       // BSCGPU_OPT_BATCH_DEVICE_LZP: the members of a host-input pass with LZP go up raw, one run of the stage per pass (BSC_BATCH_DEVICE_LZP=1)
+    int  cnt_batch_lzp_passes = 0, cnt_batch_lzp_blocks = 0;   // BSCGPU_CNT_BATCH_LZP_PASSES / _BLOCKS: passes given to the stage over a pass, and their sorted blocks
     int  lzp_lds_set = 0;            // sweep variants whose dynamic-LDS limit has been raised on this context's device (bit mask)
+    u8*  lzp_tab = nullptr;          // the stage over a pass (lzp.hip: lzp_batch_device): chunk table, result records, piece list, table bytes; allocated on first use
+    u8*  lzp_tab_host = nullptr;     // ... and its pinned mirror
+    size_t lzp_tab_bytes = 0;        // HBM of lzp_tab (bscgpu_arena_bytes counts it once allocated)
     u32  ub_step_cap = UB_STEP_CAP;  // inverse BWT: a walk longer than this between two marked rows is declined (BSC_UNBWT_STEP_CAP, a test knob)
     // pinned host
     u32* hscal  = nullptr;   // SCAL_WORDS u32 (the slot map is above)
@@ -347,6 +353,15 @@ int adler32_device(bscgpu_ctx* c, const u8* d, int64_t n, u32* out);
 // bytes in dOut (HBM, n bytes; may be c->dL); hashSize 10..15, else BSC_NOT_SUPPORTED before anything is launched.  One sync; the
 // frame's copies into dOut are queued behind it, final_sync waits for them too.  c->lzp_last: the paths taken.
 int lzp_device(bscgpu_ctx* c, const u8* dIn, u8* dOut, int n, int hashSize, int minLen, int features, bool final_sync);
+// ... for `count` blocks back to back at dIn (bscgpu_lzp_batch_device without the pointer checks): results[b] = what lzp_compress returns
+// for block b, the bytes at the block's own offset in dOut (dIn's layout; may be c->dL, not dIn, not c->dT).  dIn is read in place.
+// Limits and codes: include/bscgpu.h.  c->lzp_last: the sums over the pass.  final_sync as above.
+// place (or null): the caller packs the pass.  Called once, behind the stage's sync, with the results: it fills dst[b], where block b
+// goes in dOut (preset to lzp::BATCH_NOWHERE: the block gets nothing), and as_it_is[b] != 0 where the block's raw bytes go there
+// instead of a stream; the frame kernel then writes the pass as the caller laid it out (dOut: as many bytes as that takes).
+typedef std::function<void(const int* results, uint32_t* dst, unsigned char* as_it_is)> LzpBatchPlace;
+int lzp_batch_device(bscgpu_ctx* c, const u8* dIn, u8* dOut, const int* sizes, int count, int hashSize, int minLen, int features, int* results,
+                     bool final_sync, const LzpBatchPlace* place = nullptr);
 void launch_seg_scan(bscgpu_ctx* c, u32 num_chunks);
 // The QLFC front end's view of the sort buffers (qlfc_front.hip).  Once a block's (a pass's) L has been emitted nothing of the sorter
 // is live until the next sorter starts, and the front end and whoever reads its run arrays — the copy down, the device model — take

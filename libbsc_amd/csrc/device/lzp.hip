@@ -16,12 +16,17 @@
 //                         position x it skips.  Where the phase decides — behind a failed verify up to retry_after, and the last
 //                         SWEEP_SERIAL_TAIL positions in front of `limit` — thread 0 runs the scanner's own group loop.
 //
+// A pass of small blocks (lzp_batch_device; DESIGN §3.9, "A pass of small blocks"): the same stages over the chunk table of
+// host/lzp_batch_plan.h — lzp_batch_key / _link / _flag / _sweep_kernel, one launch each for all chunks of the pass, the sweep's body
+// (lzp_sweep_chunk) shared with the single block's — and lzp_batch_frame_kernel, which writes every block's frame from a piece list.
+//
 // Every store of the sweep is to out[0, cap) of its chunk: a window is written only after its last byte is known to lie below
 // eob = cap - 8, a group adds at most 6 bytes to an o < eob, a match's length bytes are checked before they are written.  Once o >= eob
 // the chunk is NOT_COMPRESSIBLE whatever follows (o only grows), so the sweep stops there.  All loops are bounded by the chunk's length;
 // no workgroup waits for another, and global memory sees no atomics.
 #include "dev_common.h"
 #include "../host/lzp_staged.h"
+#include "../host/lzp_batch_plan.h"
 
 using namespace bschost::lzp;
 
@@ -95,21 +100,15 @@ __global__ __launch_bounds__(WG) void lzp_flag_kernel(const u8* __restrict__ T, 
 // ---- C --------------------------------------------------------------------------------------------------------------------------------
 struct SweepState { int p, o, retry, cand; u32 seen; int len, win_m, win_e; u32 cnt[CR_WORDS]; u32 scan[8]; };
 
+// The sweep of one chunk by one workgroup: T, the links, the flag and dirty bytes and out are the chunk's own (its first byte at 0), res its
+// result record, table 2^hashSize words of LDS.  The single-block kernel and the pass's kernel differ only in where they take these from.
 template <int W, bool VERIFY>
-__global__ __launch_bounds__(WG) void lzp_sweep_kernel(const u8* __restrict__ Tall, u32 n, int nc, int hashSize, int minLen, int single_cap,
-                                                        const u32* __restrict__ prev0_all, const u32* __restrict__ next0_all,
-                                                        const u8* __restrict__ flags_all, u8* dirty_all, u8* out_all, u32* __restrict__ res)
+__device__ __forceinline__ void lzp_sweep_chunk(const u8* const T, const int size, const int cap, int hashSize, int minLen,
+                                                const u32* const prev0, const u32* const next0, const u8* const flags, u8* const dirty,
+                                                u8* const out, u32* const res, u32* const table, SweepState& S)
 {
-    extern __shared__ u32 table[];                             // 2^hashSize words: the last VISITED position of every slot, 0 = none
-    __shared__ SweepState S;
-    const int tid = (int)threadIdx.x, b = (int)blockIdx.x;
-    const u32 start = (u32)b * (n / (u32)nc);
-    const int size = (int)(b != nc - 1 ? n / (u32)nc : n - start);
-    const u8* const T = Tall + start;
-    const u32* const prev0 = prev0_all + start; const u32* const next0 = next0_all + start;
-    const u8* const flags = flags_all + start;
-    u8* const dirty = dirty_all + start; u8* const out = out_all + start;
-    const int cap = nc == 1 ? single_cap : size, eob = cap - 8, limit = size - narrow_guard(minLen);
+    const int tid = (int)threadIdx.x;
+    const int eob = cap - 8, limit = size - narrow_guard(minLen);
     const u32 mask = (1u << hashSize) - 1;
 
     for (u32 i = (u32)tid; i <= mask; i += WG) table[i] = 0;
@@ -257,9 +256,134 @@ __global__ __launch_bounds__(WG) void lzp_sweep_kernel(const u8* __restrict__ Ta
     }
     __syncthreads();
     if (tid == 0) {
-        res[b * CR_WORDS + CR_RES] = (spent || o >= eob) ? (u32)BSC_NOT_COMPRESSIBLE : (u32)o;
-        for (int t = 1; t < CR_WORDS; ++t) res[b * CR_WORDS + t] = S.cnt[t];
+        res[CR_RES] = (spent || o >= eob) ? (u32)BSC_NOT_COMPRESSIBLE : (u32)o;
+        for (int t = 1; t < CR_WORDS; ++t) res[t] = S.cnt[t];
     }
+}
+
+template <int W, bool VERIFY>
+__global__ __launch_bounds__(WG) void lzp_sweep_kernel(const u8* __restrict__ Tall, u32 n, int nc, int hashSize, int minLen, int single_cap,
+                                                        const u32* __restrict__ prev0_all, const u32* __restrict__ next0_all,
+                                                        const u8* __restrict__ flags_all, u8* dirty_all, u8* out_all, u32* __restrict__ res)
+{
+    extern __shared__ u32 table[];                             // 2^hashSize words: the last VISITED position of every slot, 0 = none
+    __shared__ SweepState S;
+    const int b = (int)blockIdx.x;
+    const u32 start = (u32)b * (n / (u32)nc);
+    const int size = (int)(b != nc - 1 ? n / (u32)nc : n - start);
+    lzp_sweep_chunk<W, VERIFY>(Tall + start, size, nc == 1 ? single_cap : size, hashSize, minLen, prev0_all + start, next0_all + start,
+                               flags_all + start, dirty_all + start, out_all + start, res + b * CR_WORDS, table, S);
+}
+
+// ---- a pass of small blocks: the same three stages over the chunk table of lzp_batch_plan.h --------------------------------------------
+// Keys are slot << 45 | chunk << 32 | position in the chunk, sorted (stable) on the slot bits alone: chunks ascend in the pass, so inside
+// a slot the positions stay grouped by chunk and ascending, and neighbours with the same upper word are predecessor and successor.  A
+// position that belongs to no chunk (a block refused by size) or that the scanner never enters gets the slot 2^hashSize, behind all.
+constexpr int BK_SLOT_SHIFT = 45, BK_CHUNK_SHIFT = 32;
+static_assert(BATCH_LZP_MAX_CHUNKS <= 1 << (BK_SLOT_SHIFT - BK_CHUNK_SHIFT), "a chunk's number fits below the slot");
+
+// The chunk that holds position g, from the chunk of a position g0 <= g found before (or -1): the last chunk that starts at or before
+// g, if g lies inside it; else -1.  Advances by at most the chunks that start in (g0, g].
+__device__ __forceinline__ int batch_chunk_first(const BatchChunk* __restrict__ chunks, int nchunks, u32 g0)
+{
+    if (nchunks == 0 || chunks[0].start > g0) return -1;
+    int lo = 0, hi = nchunks;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (chunks[mid].start <= g0) lo = mid; else hi = mid; }
+    return lo;
+}
+__device__ __forceinline__ int batch_chunk_of(const BatchChunk* __restrict__ chunks, int nchunks, int from, u32 g)
+{
+    int k = from;
+    while (k + 1 < nchunks && chunks[k + 1].start <= g) ++k;
+    return k >= 0 && g - chunks[k].start < chunks[k].size ? k : -1;
+}
+
+__global__ __launch_bounds__(WG) void lzp_batch_key_kernel(const u8* __restrict__ T, u32 n, const BatchChunk* __restrict__ chunks, int nchunks,
+                                                            int hashSize, u64* __restrict__ keys)
+{
+    const u32 g = blockIdx.x * WG + threadIdx.x;
+    if (g >= n) return;
+    const int k = batch_chunk_of(chunks, nchunks, batch_chunk_first(chunks, nchunks, blockIdx.x * WG), g);
+    u64 key = (u64)(1u << hashSize) << BK_SLOT_SHIFT;
+    if (k >= 0) {
+        const u32 q = g - chunks[k].start;
+        key |= q;
+        if (q >= 4) key = (u64)slot_of(ctx_of(T, g), (1u << hashSize) - 1) << BK_SLOT_SHIFT | (u64)k << BK_CHUNK_SHIFT | q;
+    }
+    keys[g] = key;
+}
+
+__global__ __launch_bounds__(WG) void lzp_batch_link_kernel(const u64* __restrict__ keys, u32 n, const BatchChunk* __restrict__ chunks, int nchunks,
+                                                             int hashSize, u32* __restrict__ prev0, u32* __restrict__ next0)
+{
+    const u32 i = blockIdx.x * WG + threadIdx.x;
+    if (i >= n) return;
+    const u64 key = keys[i];
+    const u32 hi = (u32)(key >> 32), q = (u32)key;
+    if (hi >> (BK_SLOT_SHIFT - 32 + hashSize)) return;
+    const u32 k = hi & ((1u << (BK_SLOT_SHIFT - BK_CHUNK_SHIFT)) - 1);
+    if (k >= (u32)nchunks || q >= chunks[k].size) return;      // (cannot be: the key kernel made it from a position of chunk k)
+    const u32 g = chunks[k].start + q;
+    const u64 kp = i > 0 ? keys[i - 1] : ~0ull, kn = i + 1 < n ? keys[i + 1] : ~0ull;
+    prev0[g] = (u32)(kp >> 32) == hi ? (u32)kp : 0u;
+    next0[g] = (u32)(kn >> 32) == hi ? (u32)kn : 0u;
+}
+
+template <int W>
+__global__ __launch_bounds__(WG) void lzp_batch_flag_kernel(const u8* __restrict__ T, u32 n, const BatchChunk* __restrict__ chunks, int nchunks,
+                                                             int minLen, const u32* __restrict__ prev0, u8* __restrict__ flags, u8* __restrict__ dirty)
+{
+    const u32 g = blockIdx.x * WG + threadIdx.x;
+    if (g >= n) return;
+    const int k = batch_chunk_of(chunks, nchunks, batch_chunk_first(chunks, nchunks, blockIdx.x * WG), g);
+    u8 f = 0;
+    if (k >= 0) {
+        const u32 start = chunks[k].start, q = g - start;
+        const int limit = (int)chunks[k].size - narrow_guard(minLen);
+        if (q >= 4) {
+            const u32 pv = prev0[g];
+            f = (pv > 0 ? F_OCC : 0) | (T[g] == FLAG ? F_FLAG : 0);
+            // q + minLen <= limit + 2 + minLen < size: the probe stays inside the chunk
+            if (pv > 0 && (int)q < limit + 3 && d_same<W>(T + start, q, pv, minLen)) f |= F_CAND;
+        }
+    }
+    flags[g] = f;
+    dirty[g] = 0;
+}
+
+template <int W, bool VERIFY>
+__global__ __launch_bounds__(WG) void lzp_batch_sweep_kernel(const u8* __restrict__ Tall, const BatchChunk* __restrict__ chunks, int hashSize,
+                                                              int minLen, const u32* __restrict__ prev0_all, const u32* __restrict__ next0_all,
+                                                              const u8* __restrict__ flags_all, u8* dirty_all, u8* out_all, u32* __restrict__ res)
+{
+    extern __shared__ u32 table[];
+    __shared__ SweepState S;
+    const BatchChunk C = chunks[blockIdx.x];
+    lzp_sweep_chunk<W, VERIFY>(Tall + C.start, (int)C.size, (int)C.cap, hashSize, minLen, prev0_all + C.start, next0_all + C.start,
+                               flags_all + C.start, dirty_all + C.start, out_all + C.start, res + blockIdx.x * CR_WORDS, table, S);
+}
+
+// The frames of a pass in one launch: piece p is moved by the workgroups wg_first[p] .. wg_first[p + 1] - 1, FRAME_SPAN bytes each, as
+// aligned words of the output with the bytes in front of and behind them one by one.
+constexpr u32 FRAME_SPAN = 16384;
+__global__ __launch_bounds__(WG) void lzp_batch_frame_kernel(const BatchPiece* __restrict__ pieces, const u32* __restrict__ wg_first, u32 npieces,
+                                                              const u8* __restrict__ staging, const u8* __restrict__ raw,
+                                                              const u8* __restrict__ tab, u8* __restrict__ out)
+{
+    const u32 tid = threadIdx.x;
+    u32 lo = 0, hi = npieces;
+    while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (wg_first[mid] <= blockIdx.x) lo = mid; else hi = mid; }
+    const BatchPiece P = pieces[lo];
+    const u32 from = (blockIdx.x - wg_first[lo]) * FRAME_SPAN;
+    if (from >= P.len) return;
+    const u32 len = P.len - from < FRAME_SPAN ? P.len - from : FRAME_SPAN;
+    const u8* const src = (P.src == PIECE_STAGING ? staging : P.src == PIECE_RAW ? raw : tab) + P.src_off + from;
+    u8* const dst = out + P.dst_off + from;
+    u32 head = (u32)(0 - (size_t)dst) & 3u; if (head > len) head = len;
+    const u32 words = (len - head) >> 2, behind = head + 4 * words;
+    if (tid < head) dst[tid] = src[tid];
+    for (u32 w = tid; w < words; w += WG) *reinterpret_cast<u32*>(dst + head + 4 * w) = d_ld32(src + head + 4 * w);
+    if (tid < len - behind) dst[behind + tid] = src[behind + tid];
 }
 
 template <int W, bool VERIFY>
@@ -348,6 +472,167 @@ int lzp_device(bscgpu_ctx* c, const u8* dIn, u8* dOut, int n, int hashSize, int 
     }
     if (final_sync) HIP_TRY(c, ctx_sync(c));
     return total;
+}
+
+// ---- the stage over a pass ------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// c->lzp_tab (HBM) and c->lzp_tab_host (pinned), the same map: nothing of it is an arena buffer, so the sort in the middle of the stage
+// and whatever follows the stage leave it alone.
+constexpr size_t LT_CHUNKS = 0;                                                              // BatchChunk [BATCH_LZP_MAX_CHUNKS]
+constexpr size_t LT_RES    = LT_CHUNKS + sizeof(BatchChunk) * BATCH_LZP_MAX_CHUNKS;          // u32 [BATCH_LZP_MAX_CHUNKS][CR_WORDS]
+constexpr size_t LT_PIECES = LT_RES + (size_t)4 * CR_WORDS * BATCH_LZP_MAX_CHUNKS;           // BatchPiece [BATCH_LZP_MAX_PIECES]
+constexpr size_t LT_WG     = LT_PIECES + sizeof(BatchPiece) * BATCH_LZP_MAX_PIECES;          // u32 [BATCH_LZP_MAX_PIECES + 1]
+constexpr size_t LT_TABLE  = LT_WG + (((size_t)4 * (BATCH_LZP_MAX_PIECES + 1) + 255) & ~(size_t)255);   // the blocks' table bytes
+constexpr size_t LT_BYTES  = LT_TABLE + (size_t)BATCH_LZP_TABLE_BYTES * BATCH_LZP_MAX_BLOCKS;
+static_assert(sizeof(BatchChunk) == 16 && sizeof(BatchPiece) == 16, "the kernels read the host's records as they stand");
+
+int lzp_tab_ensure(bscgpu_ctx* c)
+{
+    if (c->lzp_tab && c->lzp_tab_host) return BSC_NO_ERROR;
+    if (!c->lzp_tab_host && hipHostMalloc((void**)&c->lzp_tab_host, LT_BYTES, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError(); c->lzp_tab_host = nullptr;
+        return ctx_fail(c, BSC_NOT_ENOUGH_MEMORY, "LZP stage of a pass: pinned tables", hipSuccess);
+    }
+    if (!c->lzp_tab && hipMalloc((void**)&c->lzp_tab, LT_BYTES) != hipSuccess) {
+        (void)hipGetLastError(); c->lzp_tab = nullptr;
+        return ctx_fail(c, BSC_GPU_NOT_ENOUGH_MEMORY, "LZP stage of a pass: tables", hipSuccess);
+    }
+    c->lzp_tab_bytes = LT_BYTES;
+    return BSC_NO_ERROR;
+}
+
+template <int W, bool VERIFY>
+int launch_batch_sweep(bscgpu_ctx* c, int nchunks, size_t lds, const u8* T, const BatchChunk* chunks, int hashSize, int minLen, const u32* prev0,
+                       const u32* next0, const u8* flags, u8* dirty, u8* out, u32* res)
+{
+    const int bit = 8 << ((W == 8) + VERIFY);                  // (the single-block variants hold bits 0..2)
+    if (!(c->lzp_lds_set & bit)) {
+        HIP_TRY(c, hipFuncSetAttribute((const void*)lzp_batch_sweep_kernel<W, VERIFY>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 << STAGED_MAX_HASH));
+        c->lzp_lds_set |= bit;
+    }
+    hipLaunchKernelGGL((lzp_batch_sweep_kernel<W, VERIFY>), dim3(nchunks), dim3(WG), lds, c->stream, T, chunks, hashSize, minLen,
+                       prev0, next0, flags, dirty, out, res);
+    return BSC_NO_ERROR;
+}
+
+}  // namespace
+
+// Stages A, B and C over the chunk table the host left in the pinned mirror: the table goes up, the chunks' result records come down, one
+// sync.  Arena roles as lzp_device's, sized by max_n and serving a pass as they serve a block: kA / kB the sort's keys, vA / vB the links,
+// flags and SA the flag and dirty bytes, ISA the chunks' staging.  The input is read where it lies.
+static int lzp_batch_sweeps(bscgpu_ctx* c, const u8* dIn, u32 N, int nchunks, int hashSize, int minLen)
+{
+    const u32 grid = (N + WG - 1) / WG;
+    unsigned char* const H = c->lzp_tab_host;
+    u64 *keys = c->kA, *keys_alt = c->kB;
+    u32 *prev0 = c->vA, *next0 = c->vB;
+    u8 *flags = c->flags, *dirty = reinterpret_cast<u8*>(c->SA), *staging = reinterpret_cast<u8*>(c->ISA);
+    const BatchChunk* dchunks = reinterpret_cast<const BatchChunk*>(c->lzp_tab + LT_CHUNKS);
+    u32* res = reinterpret_cast<u32*>(c->lzp_tab + LT_RES);
+    HIP_TRY(c, hipMemcpyAsync(c->lzp_tab + LT_CHUNKS, H + LT_CHUNKS, sizeof(BatchChunk) * (size_t)nchunks, hipMemcpyHostToDevice, c->stream));
+
+    prof_begin(c, BSCGPU_K_LZP, (u64)N * 9, N);
+    hipLaunchKernelGGL(lzp_batch_key_kernel, dim3(grid), dim3(WG), 0, c->stream, dIn, N, dchunks, nchunks, hashSize, keys);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    const int kbits = hashSize + 1;                            // the slot and the bit of the positions behind all slots: two passes
+    const RadixPass passes[2] = {{BK_SLOT_SHIFT, 8}, {BK_SLOT_SHIFT + 8, kbits - 8}};
+    int in_alt = 0;
+    RC_TRY(radix_sort_passes(c, keys, keys_alt, nullptr, nullptr, N, passes, 2, &in_alt, nullptr, /* aux */ true));
+    const u64* sorted = in_alt ? keys_alt : keys;
+
+    const int W = narrow_word(minLen);
+    const bool verify = narrow_verify(minLen);
+    prof_begin(c, BSCGPU_K_LZP, (u64)N * 30, N);
+    hipLaunchKernelGGL(lzp_batch_link_kernel, dim3(grid), dim3(WG), 0, c->stream, sorted, N, dchunks, nchunks, hashSize, prev0, next0);
+    if (W == 4) hipLaunchKernelGGL(lzp_batch_flag_kernel<4>, dim3(grid), dim3(WG), 0, c->stream, dIn, N, dchunks, nchunks, minLen, prev0, flags, dirty);
+    else        hipLaunchKernelGGL(lzp_batch_flag_kernel<8>, dim3(grid), dim3(WG), 0, c->stream, dIn, N, dchunks, nchunks, minLen, prev0, flags, dirty);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+
+    const size_t lds = (size_t)4 << hashSize;
+    prof_begin(c, BSCGPU_K_LZP, (u64)N * 4, N);
+    if (verify)      RC_TRY((launch_batch_sweep<8, true >(c, nchunks, lds, dIn, dchunks, hashSize, minLen, prev0, next0, flags, dirty, staging, res)));
+    else if (W == 8) RC_TRY((launch_batch_sweep<8, false>(c, nchunks, lds, dIn, dchunks, hashSize, minLen, prev0, next0, flags, dirty, staging, res)));
+    else             RC_TRY((launch_batch_sweep<4, false>(c, nchunks, lds, dIn, dchunks, hashSize, minLen, prev0, next0, flags, dirty, staging, res)));
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(H + LT_RES, res, (size_t)nchunks * CR_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, ctx_sync(c));
+    prof_collect(c);
+    return BSC_NO_ERROR;
+}
+
+int lzp_batch_device(bscgpu_ctx* c, const u8* dIn, u8* dOut, const int* sizes, int count, int hashSize, int minLen, int features, int* results,
+                     bool final_sync, const LzpBatchPlace* place)
+{
+    for (auto& v : c->lzp_last) v = 0;
+    if (hashSize > STAGED_MAX_HASH) return BSC_NOT_SUPPORTED;
+    if (count < 0 || count > BATCH_LZP_MAX_BLOCKS) return BSC_BAD_PARAMETER;
+    RC_TRY(lzp_tab_ensure(c));
+    unsigned char* const H = c->lzp_tab_host;
+    BatchChunk* const hchunks = reinterpret_cast<BatchChunk*>(H + LT_CHUNKS);
+    const int nchunks = batch_plan(sizes, count, minLen, hchunks);
+    if (nchunks < 0) return nchunks;
+    int64_t total = 0;
+    for (int b = 0; b < count; ++b) total += sizes[b];
+    if (total > c->max_n) return BSC_BAD_PARAMETER;
+    BatchPiece* const hpieces = reinterpret_cast<BatchPiece*>(H + LT_PIECES);
+    const u32 N = (u32)total;
+    u8* const staging = reinterpret_cast<u8*>(c->ISA);
+    const u32* hres = reinterpret_cast<const u32*>(H + LT_RES);
+    if (nchunks > 0) RC_TRY(lzp_batch_sweeps(c, dIn, N, nchunks, hashSize, minLen));
+    else if (place) HIP_TRY(c, ctx_sync(c));                   // (no block reaches the encoder; the piece list of the call before may still be going up)
+
+    std::vector<int> own((size_t)nchunks);
+    for (int k = 0; k < nchunks; ++k) {
+        const u32* r = hres + (size_t)k * CR_WORDS;
+        own[(size_t)k] = (int)r[CR_RES];
+        if (own[(size_t)k] >= 0 && (u32)own[(size_t)k] > hchunks[k].cap)
+            return ctx_fail(c, BSC_GPU_ERROR, "LZP stage of a pass: a chunk's size is out of range", hipSuccess);
+        c->lzp_last[CNT_MATCHES] += r[CR_MATCHES]; c->lzp_last[CNT_DIRTY] += r[CR_DIRTY];
+        c->lzp_last[CNT_ZONES] += r[CR_ZONES]; c->lzp_last[CNT_ESCAPES] += r[CR_ESCAPES];
+    }
+    int64_t raw_chunks = 0;
+    std::vector<u32> dst;
+    std::vector<unsigned char> as_it_is;
+    if (place) {                                               // the caller packs the pass: it says where every block goes once it knows the results
+        batch_results(sizes, count, minLen, features, own.data(), results);
+        dst.assign((size_t)count + 1, BATCH_NOWHERE); as_it_is.assign((size_t)count + 1, 0);
+        (*place)(results, dst.data(), as_it_is.data());
+    }
+    const int np = batch_frame(sizes, count, minLen, features, own.data(), results, hpieces, H + LT_TABLE, &raw_chunks,
+                               place ? dst.data() : nullptr, place ? as_it_is.data() : nullptr);
+    c->lzp_last[CNT_RAW_CHUNKS] = raw_chunks;
+    if (np > 0) {
+        u32* const hwg = reinterpret_cast<u32*>(H + LT_WG);
+        u32 wgs = 0, tab_bytes = 0;
+        for (int p = 0; p < np; ++p) {
+            hwg[p] = wgs; wgs += (hpieces[p].len + FRAME_SPAN - 1) / FRAME_SPAN;
+            if (hpieces[p].src == PIECE_TABLE) tab_bytes = hpieces[p].src_off + hpieces[p].len;
+        }
+        hwg[np] = wgs;
+        HIP_TRY(c, hipMemcpyAsync(c->lzp_tab + LT_PIECES, hpieces, sizeof(BatchPiece) * (size_t)np, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->lzp_tab + LT_WG, hwg, (size_t)4 * (np + 1), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->lzp_tab + LT_TABLE, H + LT_TABLE, tab_bytes, hipMemcpyHostToDevice, c->stream));
+        prof_begin(c, BSCGPU_K_LZP, (u64)N * 2, N);
+        hipLaunchKernelGGL(lzp_batch_frame_kernel, dim3(wgs), dim3(WG), 0, c->stream, reinterpret_cast<const BatchPiece*>(c->lzp_tab + LT_PIECES),
+                           reinterpret_cast<const u32*>(c->lzp_tab + LT_WG), (u32)np, staging, dIn, c->lzp_tab + LT_TABLE, dOut);
+        prof_end(c);
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (final_sync) { HIP_TRY(c, ctx_sync(c)); prof_collect(c); }
+    return BSC_NO_ERROR;
+}
+
+extern "C" int bscgpu_lzp_batch_device(bscgpu_ctx* c, const void* dIn, void* dOut, const int* sizes, int count, int hashSize, int minLen,
+                                       int features, int* results)
+{
+    if (!c || !dIn || !dOut || count < 0 || (count > 0 && (!sizes || !results)) || minLen < 4 || minLen > 255 || hashSize < 10 || hashSize > 28)
+        return BSC_BAD_PARAMETER;
+    if (hipSetDevice(c->device) != hipSuccess) return BSC_GPU_ERROR;
+    return lzp_batch_device(c, (const u8*)dIn, (u8*)dOut, sizes, count, hashSize, minLen, features, results, true, nullptr);
 }
 
 static int lzp_args(const bscgpu_ctx* c, const void* in, const void* out, int n, int hashSize, int minLen)

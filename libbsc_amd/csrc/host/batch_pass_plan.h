@@ -115,9 +115,11 @@ static inline BatchClass batch_block_class(int n, int lz, bool st, bool dev, boo
 // ---- a pass's geometry ------------------------------------------------------------------------------------------------------------------
 // psz[i] / prate[i]: size and aux rate (0: a sort transform, -1: not sorted, L = T) of entry i of the pass's table; at[i]: where its L
 // lies in the pass; pos: the bytes of the pass.  Device input: the pass is the caller's own range of HBM, every block in place; host
-// input: the sorted blocks back to back, what LZP left of them.
+// input: the sorted blocks back to back, what LZP left of them.  packed_rides (a pass whose LZP ran on the device, whatever its input:
+// dev is then false): laid out as host input, and a block that rides along keeps riding, with its sizes[i] raw bytes.
 struct BatchGeometry { std::vector<int> psz, prate; std::vector<int64_t> at; int64_t pos; };
-static inline void batch_pass_geometry(const BatchClass* cls, const int* sizes, const int* lz, int count, bool st, bool dev, BatchGeometry* G)
+static inline void batch_pass_geometry(const BatchClass* cls, const int* sizes, const int* lz, int count, bool st, bool dev, BatchGeometry* G,
+                                       bool packed_rides = false)
 {
     G->psz.assign((size_t)count, 0); G->prate.assign((size_t)count, -1); G->at.assign((size_t)count, 0);
     G->pos = 0;
@@ -125,7 +127,7 @@ static inline void batch_pass_geometry(const BatchClass* cls, const int* sizes, 
         const bool sorted = cls[i] == BATCH_SORTED;
         G->at[i] = G->pos;
         G->prate[i] = sorted ? (st ? 0 : aux_rate(lz[i])) : -1;
-        G->psz[i] = dev ? sizes[i] : sorted ? lz[i] : 0;
+        G->psz[i] = dev ? sizes[i] : sorted ? lz[i] : packed_rides && cls[i] == BATCH_RIDES ? sizes[i] : 0;
         G->pos += G->psz[i];
     }
 }

@@ -2266,7 +2266,7 @@ static int device_rc_pass(bscgpu_ctx* c, PassLayout& PL, uint8_t* host_bytes, si
 // ---- the driver of a batched-compress call: what batch_pass_plan.h decides, done in named steps ------------------------------------
 namespace {
 // What every step of a call works on.  One implementation for both entry points: host input (`input`, LZP per block) or input in HBM
-// (`dInput`, no LZP).
+// (`dInput`; LZP, if any, on the device: dlzp).
 struct BatchCall {
     bscgpu_ctx* c;
     const unsigned char* input; const unsigned char* dInput; const int* sizes; int count; unsigned char* output; int* results;
@@ -2281,6 +2281,9 @@ struct BatchCall {
     std::vector<char> single;                     // blocks that are not coded with a pass: batch_leftovers
     std::vector<uint32_t> res, adler;             // what the sort of a pass leaves, until finish_blocks (one pass sorts at a time)
     std::vector<int> stidx;
+    bool dlzp = false;                            // LZP of a pass's members is one run of the device's stage over the raw pass (BatchPass::stage_lzp), not lzp_compress
+                                                  // per block: input in HBM with LZP, or host input with BSCGPU_OPT_BATCH_DEVICE_LZP and parameters the stage takes
+    bool lzp_declined = false;                    // ... the option is on, the stage does not take the parameters: the passes keep host LZP
 
     const unsigned char* in_of(int b) const { return input + in_off[b]; }
     const unsigned char* din_of(int b) const { return dInput + in_off[b]; }
@@ -2288,7 +2291,7 @@ struct BatchCall {
     bool lzp() const { return block_mode_has_lzp(mode); }
     int alone(int b) const                        // a block by the single-block path on the call's context
     {
-        return dev ? bscgpu_compress_device(c, din_of(b), out_of(b), sizes[b], blockSorter, coder, features)
+        return dev ? bscgpu_compress_device_lzp(c, din_of(b), out_of(b), sizes[b], lzpHashSize, lzpMinLen, blockSorter, coder, features)
                    : compress_one_on_ctx(c, in_of(b), out_of(b), sizes[b], lzpHashSize, lzpMinLen, blockSorter, coder, features);
     }
 };
@@ -2310,6 +2313,7 @@ struct BatchPass {
     void prepare(BatchCall* call, int pass, int b0, int e0);
     void prep_block(int i);
     int  stage();
+    int  stage_lzp();
     int  sort();
     int  l_down();
     int  front();
@@ -2381,8 +2385,9 @@ void BatchPass::prepare(BatchCall* call, int pass, int b0, int e0)
     PL.used = false;
     groups.reset();
     hb = K->c->batch_host[p & 1];
-    // in parallel; without LZP there is nothing to spread over threads
-    if (K->lzp()) run_bounded(e - b, K->threads, [this](int i) { prep_block(i); });
+    if (K->lzp_declined) ++K->c->cnt_lzp_declined;
+    // in parallel; without LZP on the host there is nothing to spread over threads
+    if (K->lzp() && !K->dlzp) run_bounded(e - b, K->threads, [this](int i) { prep_block(i); });
     else for (int i = 0; i < e - b; ++i) prep_block(i);
 }
 
@@ -2393,7 +2398,7 @@ void BatchPass::prep_block(int i)
     B.b = q; B.mode = K->mode; B.lz = n;
     B.cls = batch_block_class(n, n, K->st, K->dev, K->pass_of[q] >= 0);            // (before LZP: n stands for what it leaves)
     if (B.cls == BATCH_STORED) K->results[q] = bsc_store(K->in_of(q), K->out_of(q), n, K->features);
-    if (B.cls != BATCH_SORTED || !K->lzp()) return;
+    if (B.cls != BATCH_SORTED || !K->lzp() || K->dlzp) return;      // (dlzp: the member stays raw, stage_lzp settles lz, mode and class)
     B.lzbuf = (unsigned char*)bigbuf_get((size_t)n);
     const int r = B.lzbuf ? lzp_compress(K->in_of(q), B.lzbuf, n, K->lzpHashSize, K->lzpMinLen, K->features) : LIBBSC_NOT_ENOUGH_MEMORY;
     if (r < LIBBSC_NO_ERROR) { B.mode = block_mode_without_lzp(B.mode); bigbuf_put(B.lzbuf); B.lzbuf = nullptr; }
@@ -2405,6 +2410,7 @@ void BatchPass::prep_block(int i)
 // 2. stage: where every block lies in the pass; host input goes into hb and up to the device
 int BatchPass::stage()
 {
+    if (K->dlzp) return stage_lzp();
     const int cnt = e - b;
     std::vector<BatchClass> cls((size_t)cnt);
     std::vector<int> lz((size_t)cnt);
@@ -2420,12 +2426,66 @@ int BatchPass::stage()
     return LIBBSC_NO_ERROR;
 }
 
+// 2'. stage, LZP on the device: the raw pass — the caller's own range of HBM, or the same range of host input uploaded to dT — goes
+// through one run of the LZP stage (lzp.hip: lzp_batch_device), whose frame kernel lays the sorter's input out in dL as the host
+// route would: the sorted blocks' streams back to back, a block the stage finds not compressible with its raw bytes and without LZP
+// in its mode (libbsc.cpp:266-269), a block that rides along with its raw bytes.  Input in HBM: the checksums of the original blocks
+// come from one segmented launch over the raw pass, before the sort (which is then called without its checksum output).
+int BatchPass::stage_lzp()
+{
+    bscgpu_ctx* c = K->c;
+    const int cnt = e - b;
+    const int* sz = K->sizes + b;
+    const int64_t range = K->in_off[e] - K->in_off[b];
+    const u8* raw = K->dev ? K->din_of(b) : c->dT;
+    if (!K->dev && range > 0) {
+        memcpy(hb, K->in_of(b), (size_t)range);
+        if (hipMemcpyAsync(c->dT, hb, (size_t)range, hipMemcpyHostToDevice, c->stream) != hipSuccess) return LIBBSC_GPU_ERROR;
+    }
+    if (K->dev) {
+        const int trc = batch_tab_ensure(c);
+        if (trc < 0) return trc;
+        std::vector<u32> off((size_t)cnt + 1, 0u);
+        for (int i = 0; i < cnt; ++i) off[(size_t)i + 1] = off[(size_t)i] + (u32)sz[i];
+        u32* dadler = c->batch_tab + 18 * BATCH_MAX_BLOCKS + 1;                     // (batch_pass_setup's place for them; the sort comes later)
+        if (hipMemcpyAsync(c->batch_tab, off.data(), off.size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess) return LIBBSC_GPU_ERROR;
+        launch_adler_batch(c, raw, c->batch_tab, (u32)cnt, dadler);
+        if (hipMemcpyAsync(K->adler.data(), dadler, (size_t)cnt * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return LIBBSC_GPU_ERROR;
+    }
+    std::vector<int> lzres((size_t)cnt);
+    int sorted = 0;
+    const LzpBatchPlace place = [&](const int* res, uint32_t* dst, unsigned char* as_it_is) {
+        std::vector<BatchClass> cls((size_t)cnt);
+        std::vector<int> lz((size_t)cnt);
+        for (int i = 0; i < cnt; ++i) {
+            BatchBlock& B = blocks[i];
+            if (B.cls == BATCH_SORTED) {
+                if (res[i] < LIBBSC_NO_ERROR) B.mode = block_mode_without_lzp(B.mode); else B.lz = res[i];
+                B.cls = batch_block_class(sz[i], B.lz, K->st, K->dev, true);
+            }
+            cls[i] = B.cls; lz[i] = B.lz;
+        }
+        batch_pass_geometry(cls.data(), sz, lz.data(), cnt, K->st, false, &G, true);
+        for (int i = 0; i < cnt; ++i) {
+            if (cls[i] != BATCH_SORTED && cls[i] != BATCH_RIDES) continue;
+            dst[i] = (uint32_t)G.at[i];
+            as_it_is[i] = cls[i] == BATCH_RIDES || res[i] < LIBBSC_NO_ERROR;
+            sorted += cls[i] == BATCH_SORTED;
+        }
+    };
+    const int rc = lzp_batch_device(c, raw, c->dL, sz, cnt, K->lzpHashSize, K->lzpMinLen, K->features, lzres.data(), false, &place);
+    if (rc < 0) return rc;
+    ++c->cnt_batch_lzp_passes; c->cnt_batch_lzp_blocks += sorted;
+    return LIBBSC_NO_ERROR;
+}
+
 // 3. sort: one suffix sort or one sort transform for the pass
 int BatchPass::sort()
 {
     bscgpu_ctx* c = K->c;
-    const u8* src = K->dev ? K->din_of(b) : c->dL;
-    u32* adler = K->dev ? K->adler.data() : nullptr;
+    const bool in_place = K->dev && !K->dlzp;                                   // (dlzp: the pass is what stage_lzp left in dL, checksums taken)
+    const u8* src = in_place ? K->din_of(b) : c->dL;
+    u32* adler = in_place ? K->adler.data() : nullptr;
     return K->st ? st_batch_device(c, src, c->dL, G.psz.data(), e - b, K->blockSorter, G.prate.data(), K->stidx.data(), adler)
                  : bwt_batch_device(c, src, c->dL, G.psz.data(), e - b, G.prate.data(), K->res.data(), adler);
 }
@@ -2635,7 +2695,11 @@ int batch_call_begin(BatchCall& K)
 // (both use the context's pinned slots: never at the same time)
 void batch_leftovers(BatchCall& K)
 {
-    auto kind = [&](int b) { return batch_leftover(K.single[b] != 0, K.pass_of[b] >= 0, K.sizes[b], K.c->max_n, K.dev); };
+    // (input in HBM with LZP: the pipe's HBM entry has no LZP form, every block left over goes through bscgpu_compress_device_lzp)
+    auto kind = [&](int b) {
+        const BatchLeftover k = batch_leftover(K.single[b] != 0, K.pass_of[b] >= 0, K.sizes[b], K.c->max_n, K.dev);
+        return k == BATCH_LEFT_PIPE && K.dev && K.lzp() ? BATCH_LEFT_ONE_BY_ONE : k;
+    };
     auto one_by_one = [&](BatchLeftover k) { for (int b = 0; b < K.count; ++b) if (kind(b) == k) K.results[b] = K.alone(b); };
     one_by_one(BATCH_LEFT_ONE_BY_ONE);
     bool any = false;
@@ -2664,6 +2728,10 @@ static int compress_batch_impl(bscgpu_ctx* c, const unsigned char* input, const 
                    dInput != nullptr, blockSorter != LIBBSC_BLOCKSORTER_BWT, {}, {}, {}, 0, 0, {}, {}, {}, {}};
     const int mrc = make_mode(blockSorter, coder, lzpHashSize, lzpMinLen, &K.mode);
     if (mrc != LIBBSC_NO_ERROR) { for (int b = 0; b < count; ++b) results[b] = mrc; return LIBBSC_NO_ERROR; }
+    const bool takes = device_lzp_takes(lzpHashSize);
+    if (K.dev && K.lzp() && !takes) return LIBBSC_NOT_SUPPORTED;                 // as bscgpu_compress_device_lzp: the stage holds a chunk's table in LDS
+    K.dlzp = K.lzp() && takes && (K.dev || c->batch_device_lzp != 0);
+    K.lzp_declined = !K.dev && K.lzp() && !takes && c->batch_device_lzp != 0;
     if (hipSetDevice(c->device) != hipSuccess) return LIBBSC_GPU_ERROR;
     const int npass = batch_call_begin(K);
     if (npass < 0) return npass;
@@ -2723,5 +2791,16 @@ extern "C" BSCGPU_API int bscgpu_compress_batch_device(bscgpu_ctx* c, const void
     if (rc < 0 || count == 0) return rc;
     static const unsigned char empty = 0;       // (a batch of empty blocks may come with no buffer at all)
     return compress_batch_impl(c, nullptr, dInput ? (const unsigned char*)dInput : &empty, sizes, count, output, results, 0, 0,
+                               blockSorter, coder, features);
+}
+
+extern "C" BSCGPU_API int bscgpu_compress_batch_device_lzp(bscgpu_ctx* c, const void* dInput, const int* sizes, int count, unsigned char* output,
+                                                           int* results, int lzpHashSize, int lzpMinLen, int blockSorter, int coder, int features)
+{
+    if (lzpHashSize == 0 && lzpMinLen == 0) return bscgpu_compress_batch_device(c, dInput, sizes, count, output, results, blockSorter, coder, features);
+    const int rc = batch_args(c, dInput, sizes, count, output, results);
+    if (rc < 0 || count == 0) return rc;
+    static const unsigned char empty = 0;
+    return compress_batch_impl(c, nullptr, dInput ? (const unsigned char*)dInput : &empty, sizes, count, output, results, lzpHashSize, lzpMinLen,
                                blockSorter, coder, features);
 }

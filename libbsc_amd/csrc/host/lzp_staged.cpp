@@ -11,6 +11,7 @@
 #include "../../../include/bscgpu.h"
 #include "lzp.h"
 #include "lzp_staged.h"
+#include "lzp_batch_plan.h"
 
 namespace bschost {
 
@@ -223,4 +224,51 @@ extern "C" int bscgpu_lzp_staged_host(const uint8_t* in, uint8_t* out, int n, in
 {
     if (!in || !out || n < 0 || minLen < 4 || minLen > 255 || hashSize < 10 || hashSize > 28) return LIBBSC_BAD_PARAMETER;
     return bschost::lzp_compress_staged(in, out, n, hashSize, minLen, features, counters);
+}
+
+// ---- a pass of small blocks (lzp_batch_plan.h) -------------------------------------------------------------------------------------------
+extern "C" int bscgpu_lzp_batch_plan(const int* sizes, int count, int minLen, int* chunk_block, int* chunk_start, int* chunk_size, int* chunk_cap)
+{
+    using namespace bschost::lzp;
+    if ((count > 0 && !sizes) || !chunk_block || !chunk_start || !chunk_size || !chunk_cap) return LIBBSC_BAD_PARAMETER;
+    std::vector<BatchChunk> t((size_t)BATCH_LZP_MAX_CHUNKS);
+    const int k = batch_plan(sizes, count, minLen, t.data());
+    for (int i = 0; i < k; ++i) {
+        chunk_block[i] = (int)t[(size_t)i].block; chunk_start[i] = (int)t[(size_t)i].start;
+        chunk_size[i] = (int)t[(size_t)i].size; chunk_cap[i] = (int)t[(size_t)i].cap;
+    }
+    return k;
+}
+
+extern "C" int bscgpu_lzp_batch_frame(const int* sizes, int count, int minLen, int features, const int* own, int* results, int* piece_src,
+                                      int* piece_src_off, int* piece_dst_off, int* piece_len, unsigned char* table, int64_t* raw_chunks)
+{
+    using namespace bschost::lzp;
+    if ((count > 0 && (!sizes || !results)) || !piece_src || !piece_src_off || !piece_dst_off || !piece_len || !table) return LIBBSC_BAD_PARAMETER;
+    std::vector<BatchChunk> t((size_t)BATCH_LZP_MAX_CHUNKS);
+    const int k = batch_plan(sizes, count, minLen, t.data());
+    if (k < 0 || (k > 0 && !own)) return LIBBSC_BAD_PARAMETER;
+    std::vector<BatchPiece> p((size_t)BATCH_LZP_MAX_PIECES);
+    const int np = batch_frame(sizes, count, minLen, features, own, results, p.data(), table, raw_chunks);
+    for (int i = 0; i < np; ++i) {
+        piece_src[i] = (int)p[(size_t)i].src; piece_src_off[i] = (int)p[(size_t)i].src_off;
+        piece_dst_off[i] = (int)p[(size_t)i].dst_off; piece_len[i] = (int)p[(size_t)i].len;
+    }
+    return np;
+}
+
+extern "C" int bscgpu_lzp_chunk_staged_host(const uint8_t* in, uint8_t* out, int n, int cap, int hashSize, int minLen, int64_t* counters)
+{
+    using namespace bschost::lzp;
+    if (!in || !out || n < 0 || cap < 0 || cap > n || minLen < 4 || minLen > 255 || hashSize < 10 || hashSize > STAGED_MAX_HASH) return LIBBSC_BAD_PARAMETER;
+    std::vector<uint8_t> staging((size_t)n + 16);                // (as lzp_compress_staged's: the sweep's own slack)
+    bschost::Chunk C;
+    C.T = in; C.n = n; C.out = staging.data(); C.cap = cap; C.hashSize = hashSize; C.minLen = minLen;
+    const int r = C.run();
+    if (counters) {
+        counters[CNT_MATCHES] = C.cnt[CR_MATCHES]; counters[CNT_DIRTY] = C.cnt[CR_DIRTY];
+        counters[CNT_ZONES] = C.cnt[CR_ZONES]; counters[CNT_ESCAPES] = C.cnt[CR_ESCAPES]; counters[CNT_RAW_CHUNKS] = 0;
+    }
+    if (r > 0) memcpy(out, staging.data(), (size_t)r);
+    return r;
 }

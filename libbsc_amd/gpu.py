@@ -238,8 +238,36 @@ class GpuContext:
         r = self.L.bscgpu_lzp_compress(self.h, N.np_ptr(inp), N.np_ptr(out), a.size, hash_size, min_len, features)
         return out[:r].tobytes() if r >= 0 else r
 
+    def lzp_compress_batch(self, blocks, sizes=None, hash_size=15, min_len=128, features=3, device=False, dOut=None):
+        """bscgpu_lzp_batch_device: bsc_lzp_compress of every block of a pass in one run of the stage -> list of bytes, or the negative
+        libbsc code of a block (LIBBSC_NOT_COMPRESSIBLE).  device=True: `blocks` is a uint8 device tensor that holds the blocks back to
+        back and `sizes` their lengths; else `blocks` is a list of bytes / uint8 arrays, which go up first.  dOut: a uint8 device tensor
+        of the pass's size that takes the output (in the input's layout).  Raises GpuError for a batch-level error
+        (LIBBSC_BAD_PARAMETER, LIBBSC_NOT_SUPPORTED for hash_size >= 16).  lzp_counters() gives the sums over the pass."""
+        import torch
+        if device:
+            dT = blocks
+            sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32))
+        else:
+            arrs = [np.frombuffer(bytes(b), np.uint8) if not isinstance(b, np.ndarray) else np.asarray(b, np.uint8).ravel() for b in blocks]
+            sz = np.array([a.size for a in arrs], np.int32)
+            host = np.concatenate(arrs) if arrs and int(sz.sum()) else np.zeros(1, np.uint8)
+            dT = torch.from_numpy(np.ascontiguousarray(host)).cuda(self.device)
+        total = int(sz.astype(np.int64).sum())
+        out = dOut if dOut is not None else torch.empty(max(min(total, int(dT.numel())), 1), dtype=torch.uint8, device=dT.device)
+        results = np.zeros(max(sz.size, 1), np.int32)
+        self._check(self.L.bscgpu_lzp_batch_device(self.h, _dptr(dT), _dptr(out), N.np_ptr(sz), sz.size, hash_size, min_len, features,
+                                                   N.np_ptr(results)))
+        Oh = out[:total].cpu().numpy()
+        res, o = [], 0
+        for b in range(sz.size):
+            r = int(results[b])
+            res.append(Oh[o:o + r].tobytes() if r >= 0 else r)
+            o += int(sz[b])
+        return res
+
     def lzp_counters(self):
-        """the last block given to the LZP stage: dict(matches, dirty, serial_zones, escapes, raw_chunks)"""
+        """the last block (or pass) given to the LZP stage: dict(matches, dirty, serial_zones, escapes, raw_chunks)"""
         return {k: self.option_get(self.CNT_LZP_MATCHES + i) for i, k in enumerate(LZP_COUNTERS)}
 
     # ---- batches of small blocks (one suffix sort per pass, include/bscgpu.h) ----------------
@@ -303,13 +331,18 @@ class GpuContext:
                                                  lzp_hash, lzp_min, sorter, coder, features))
         return self._batch_results(out, sz, results)
 
-    def compress_batch_device(self, dT, sizes, sorter=1, coder=1, features=3):
-        """compress_batch for blocks laid out back to back in a uint8 device tensor (no LZP, as compress_device)"""
+    def compress_batch_device(self, dT, sizes, sorter=1, coder=1, features=3, lzp_hash=0, lzp_min=0):
+        """compress_batch for blocks laid out back to back in a uint8 device tensor.  lzp_hash / lzp_min: with the LZP stage over every
+        pass in front (bscgpu_compress_batch_device_lzp; lzp_hash 10..15, else GpuError LIBBSC_NOT_SUPPORTED)"""
         sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32))
         out = np.empty(int(sz.sum()) + 28 * sz.size + 1, np.uint8)
         results = np.zeros(max(sz.size, 1), np.int32)
-        self._check(self.L.bscgpu_compress_batch_device(self.h, _dptr(dT), N.np_ptr(sz), sz.size, N.np_ptr(out), N.np_ptr(results),
-                                                        sorter, coder, features))
+        if lzp_hash or lzp_min:
+            self._check(self.L.bscgpu_compress_batch_device_lzp(self.h, _dptr(dT), N.np_ptr(sz), sz.size, N.np_ptr(out), N.np_ptr(results),
+                                                                lzp_hash, lzp_min, sorter, coder, features))
+        else:
+            self._check(self.L.bscgpu_compress_batch_device(self.h, _dptr(dT), N.np_ptr(sz), sz.size, N.np_ptr(out), N.np_ptr(results),
+                                                            sorter, coder, features))
         return self._batch_results(out, sz, results)
 
     def qlfc_front_batch(self, dL, sizes):
@@ -492,6 +525,9 @@ class GpuContext:
     # the last block given to the stage (get only): matches, dirty look-ups, failed verifies, escaped literals, chunks kept raw
     OPT_DEVICE_LZP, CNT_LZP_BLOCKS, CNT_LZP_DECLINED = 45, 46, 47
     CNT_LZP_MATCHES, CNT_LZP_DIRTY, CNT_LZP_SERIAL_ZONES, CNT_LZP_ESCAPES, CNT_LZP_RAW_CHUNKS = 48, 49, 50, 51, 52
+    # the members of a host-input pass with LZP go up raw and one run of the stage per pass preprocesses them (default 0); passes of either
+    # batch call that took the stage, and their sorted blocks
+    OPT_BATCH_DEVICE_LZP, CNT_BATCH_LZP_PASSES, CNT_BATCH_LZP_BLOCKS = 53, 54, 55
     DC_FAIL_AVG, DC_FAIL_HIST, DC_FAIL_CAP, DC_FAIL_REPLAY, DC_FAIL_MIX = 2, 4, 8, 16, 32          # BSCGPU_DC_FAIL_*
 
     def option_set(self, key, value):
@@ -541,6 +577,45 @@ def lzp_staged_host(data, hash_size, min_len, features=3):
     out = np.empty(a.size + 64, np.uint8)
     cnt = np.zeros(len(LZP_COUNTERS), np.int64)
     r = N.lib().bscgpu_lzp_staged_host(N.np_ptr(inp), N.np_ptr(out), a.size, hash_size, min_len, features, N.np_ptr(cnt))
+    return (out[:r].tobytes() if r >= 0 else r), dict(zip(LZP_COUNTERS, (int(x) for x in cnt)))
+
+
+LZP_BATCH_MAX_CHUNKS, LZP_BATCH_MAX_PIECES, LZP_BATCH_TABLE_BYTES = 8192, 3 * 4096, 17     # csrc/host/lzp_batch_plan.h
+PIECE_STAGING, PIECE_RAW, PIECE_TABLE = 0, 1, 2
+
+
+def lzp_batch_plan(sizes, min_len):
+    """bscgpu_lzp_batch_plan: the chunk table of the LZP stage over a pass of blocks back to back (no GPU, no context) -> list of
+    (block, start in the pass, size, cap) per chunk in pass order, or the negative libbsc code (LIBBSC_BAD_PARAMETER)"""
+    sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32))
+    t = np.zeros((4, LZP_BATCH_MAX_CHUNKS), np.int32)
+    k = N.lib().bscgpu_lzp_batch_plan(N.np_ptr(sz) if sz.size else None, sz.size, min_len, N.np_ptr(t[0]), N.np_ptr(t[1]), N.np_ptr(t[2]), N.np_ptr(t[3]))
+    return k if k < 0 else [tuple(int(x) for x in t[:, i]) for i in range(k)]
+
+
+def lzp_batch_frame(sizes, min_len, features, own):
+    """bscgpu_lzp_batch_frame: the frames of a pass from its chunks' own results (own[k] for chunk k of lzp_batch_plan) -> (results per
+    block, list of pieces (source, source offset, offset in the output, length), the table bytes, raw chunks)"""
+    sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32))
+    ow = np.ascontiguousarray(np.asarray(own, dtype=np.int32))
+    results = np.zeros(max(sz.size, 1), np.int32)
+    p = np.zeros((4, LZP_BATCH_MAX_PIECES), np.int32)
+    table = np.zeros(max(sz.size, 1) * LZP_BATCH_TABLE_BYTES, np.uint8)
+    raw = np.zeros(1, np.int64)
+    k = N.lib().bscgpu_lzp_batch_frame(N.np_ptr(sz) if sz.size else None, sz.size, min_len, features, N.np_ptr(ow) if ow.size else None,
+                                       N.np_ptr(results), N.np_ptr(p[0]), N.np_ptr(p[1]), N.np_ptr(p[2]), N.np_ptr(p[3]), N.np_ptr(table), N.np_ptr(raw))
+    if k < 0:
+        return k
+    return [int(x) for x in results[:sz.size]], [tuple(int(x) for x in p[:, i]) for i in range(k)], table, int(raw[0])
+
+
+def lzp_chunk_staged_host(data, cap, hash_size, min_len):
+    """bscgpu_lzp_chunk_staged_host: the CPU stand-in's sweep of one chunk under a budget of cap bytes -> (bytes or the negative libbsc
+    code, dict of the path counters)"""
+    a = np.ascontiguousarray(data, dtype=np.uint8)
+    out = np.empty(a.size + 64, np.uint8)
+    cnt = np.zeros(len(LZP_COUNTERS), np.int64)
+    r = N.lib().bscgpu_lzp_chunk_staged_host(N.np_ptr(a), N.np_ptr(out), a.size, cap, hash_size, min_len, N.np_ptr(cnt))
     return (out[:r].tobytes() if r >= 0 else r), dict(zip(LZP_COUNTERS, (int(x) for x in cnt)))
 
 

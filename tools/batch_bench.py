@@ -69,6 +69,13 @@ the same legs and the same sweep; --model-only adds the third fact's kernel on a
 facts stage), the longest chain the facts report, and the chains, longest chain and walk time summed over the pass's segments.  Raw
 output belongs under profiles/batch_adaptive_segments/.
     python tools/batch_bench.py --model --segments [--model-only | --segment-sweep] [--coder 3 | --coder 2] [--reps 3] [--workloads W1,W2,W3]
+
+--lzp H,M: the batch calls with LZP ("A pass of small blocks"), three legs interleaved (host_lzp, option_on, hbm, host_lzp,
+...): compress_batch with lzp_compress per block on the host (today's route), the same call with BSCGPU_OPT_BATCH_DEVICE_LZP on (the
+raw pass goes up, one run of the stage per pass), and compress_batch_device with the LZP parameters (input in HBM).  Every repetition's
+wall time, the medians as MB/s, CPU-s per MB, the passes that took the stage, a SHA-256 of every output against the first leg's.  Raw
+output belongs under profiles/batch_lzp/.
+    python tools/batch_bench.py --lzp 15,128 [--reps 3] [--workloads W1,W2,W3] [--coder 1]
 """
 import argparse
 import ctypes as C
@@ -618,6 +625,58 @@ def model_main(args):
         ctx.close()
 
 
+def lzp_main(args):
+    import hashlib
+    import torch
+    from libbsc_amd import GpuContext
+    h, m = (int(x) for x in args.lzp.split(","))
+    sorter, coder = args.sorter, args.coder
+    ctx = GpuContext(0, max_n=(64 << 20) + 4096)
+
+    def digest(out):
+        d = hashlib.sha256()
+        for o in out:
+            d.update(o if isinstance(o, bytes) else str(o).encode())
+        return d.hexdigest()
+
+    try:
+        for name in args.workloads.split(","):
+            sizes, blocks = workload(name)
+            mb = sum(sizes) / 1e6
+            flat = torch.from_numpy(np.concatenate(blocks)).cuda()
+            torch.cuda.synchronize()
+
+            def leg(which):
+                ctx.option_set(ctx.OPT_BATCH_DEVICE_LZP, 1 if which == "option_on" else 0)
+                if which == "hbm":
+                    return ctx.compress_batch_device(flat, sizes, sorter, coder, lzp_hash=h, lzp_min=m)
+                return ctx.compress_batch(blocks, sorter, coder, lzp_hash=h, lzp_min=m)
+
+            legs = ("host_lzp", "option_on", "hbm")
+            want = digest(leg("host_lzp"))                                       # warm-up, and the outputs to compare with
+            for which in legs[1:]:
+                leg(which)
+            walls, cpus, ok, passes = {k: [] for k in legs}, {k: [] for k in legs}, {k: True for k in legs}, {k: 0 for k in legs}
+            for _ in range(args.reps):
+                for which in legs:
+                    p0 = ctx.option_get(ctx.CNT_BATCH_LZP_PASSES)
+                    out, wall, cpu = timed(lambda: leg(which))
+                    walls[which].append(wall); cpus[which].append(cpu)
+                    passes[which] = ctx.option_get(ctx.CNT_BATCH_LZP_PASSES) - p0
+                    ok[which] = ok[which] and digest(out) == want
+            for which in legs:
+                med = float(np.median(walls[which]))
+                print(json.dumps({"workload": name, "lzp": [h, m], "coder": coder, **({"sorter": sorter} if sorter != 1 else {}), "leg": which,
+                                  "blocks": len(sizes), "MB": round(mb, 2), "MB_s": round(mb / med, 1), "ms": round(med * 1e3, 1),
+                                  "ms_all": [round(w * 1e3, 1) for w in walls[which]],
+                                  "cpu_s_per_MB": round(float(np.median(cpus[which])) / mb, 4), "stage_passes": passes[which],
+                                  "identical_to_host_lzp": bool(ok[which])}), flush=True)
+            del flat
+    finally:
+        ctx.option_set(ctx.OPT_BATCH_DEVICE_LZP, 0)
+        ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -638,7 +697,11 @@ def main():
     ap.add_argument("--segments", action="store_true", help="implies --model: legs model off / on / on + BSCGPU_OPT_BATCH_MODEL_SEGMENTS; with --model-only: the segmented stage")
     ap.add_argument("--packed", action="store_true", help="with --model (and --segments, --model-only): BSCGPU_OPT_BATCH_MODEL_PACKED on / off / model off, interleaved (-e1)")
     ap.add_argument("--segment-sweep", action="store_true", help="with --model: BSC_BATCH_MODEL_SEGMENT over the capacity / 8 .. the capacity, host input (set BSC_BATCH_MODEL_MIN_PASS=0 for one-pass workloads of the fast coder)")
+    ap.add_argument("--lzp", default=None, help="H,M: the batch calls with LZP — host LZP, BSCGPU_OPT_BATCH_DEVICE_LZP on, input in HBM — interleaved")
     args = ap.parse_args()
+    if args.lzp:
+        args.workloads = args.workloads or "W1,W2,W3"
+        return lzp_main(args)
     if args.segment_sweep:
         args.workloads = args.workloads or "W1,W2"
         args.segments = True
