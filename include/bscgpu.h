@@ -167,7 +167,8 @@ BSCGPU_API int bscgpu_compress_device_lzp(bscgpu_ctx* ctx, const void* dInput, u
  * bscgpu_lzp_compress_device: what bsc_lzp_compress returns for the n bytes at dIn (HBM), with the same bytes in dOut (HBM, n bytes; may
  *   be dIn) — or LIBBSC_NOT_SUPPORTED, before anything is launched, for hashSize >= 16: the stage holds a chunk's table in LDS and covers
  *   the narrow scanners only.  Both framings (features & LIBBSC_FEATURE_MULTITHREADING) are exact.  BSCGPU_CNT_LZP_MATCHES.. say which
- *   paths the block took.  n <= the context's max_n.
+ *   paths the block took.  n <= the context's max_n.  Memory: the stage's tables, as for bscgpu_lzp_batch_device below — the same
+ *   allocation, made by whichever call comes first.
  * bscgpu_lzp_compress: the same with host pointers (out: n bytes).
  * bscgpu_lzp_staged_host: the CPU stand-in — the stage's three steps (links, flags, the sweep with its dirty marks and the real table:
  *   written for every visited position, read by dirty positions only) as the device runs them, on the calling thread; no GPU, no context.  counters (or NULL): five values in the order of

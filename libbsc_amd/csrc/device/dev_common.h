@@ -234,7 +234,7 @@ struct bscgpu_ctx {
     int  batch_device_lzp = 0;       // BSCGPU_OPT_BATCH_DEVICE_LZP: the members of a host-input pass with LZP go up raw, one run of the stage per pass (BSC_BATCH_DEVICE_LZP=1)
     int  cnt_batch_lzp_passes = 0, cnt_batch_lzp_blocks = 0;   // BSCGPU_CNT_BATCH_LZP_PASSES / _BLOCKS: passes given to the stage over a pass, and their sorted blocks
     int  lzp_lds_set = 0;            // sweep variants whose dynamic-LDS limit has been raised on this context's device (bit mask)
-    u8*  lzp_tab = nullptr;          // the stage over a pass (lzp.hip: lzp_batch_device): chunk table, result records, piece list, table bytes; allocated on first use
+    u8*  lzp_tab = nullptr;          // the stage's tables, for a block as for a pass (lzp.hip: lzp_stage): chunk table, result records, piece list, table bytes; allocated on first use
     u8*  lzp_tab_host = nullptr;     // ... and its pinned mirror
     size_t lzp_tab_bytes = 0;        // HBM of lzp_tab (bscgpu_arena_bytes counts it once allocated)
     u32  ub_step_cap = UB_STEP_CAP;  // inverse BWT: a walk longer than this between two marked rows is declined (BSC_UNBWT_STEP_CAP, a test knob)
@@ -350,12 +350,14 @@ int unbwt_batch_pass(bscgpu_ctx* c, const u8* dL, u8* out, const int* sizes, con
                      u32* adler, u8* t_host);
 int adler32_device(bscgpu_ctx* c, const u8* d, int64_t n, u32* out);
 // The LZP encoder stage (lzp.hip): dIn (HBM, n bytes; may be c->dT or dOut) -> what lzp_compress returns, with the same
-// bytes in dOut (HBM, n bytes; may be c->dL); hashSize 10..15, else BSC_NOT_SUPPORTED before anything is launched.  One sync; the
-// frame's copies into dOut are queued behind it, final_sync waits for them too.  c->lzp_last: the paths taken.
+// bytes in dOut (HBM, n bytes; may be c->dL, not c->dT); hashSize 10..15, else BSC_NOT_SUPPORTED before anything is launched.  The
+// block is copied to c->dT unless it lies there and runs as a pass of one block through the routine below.  One sync; the frame
+// kernel that writes dOut is queued behind it, final_sync waits for it too.  c->lzp_last: the paths taken.
 int lzp_device(bscgpu_ctx* c, const u8* dIn, u8* dOut, int n, int hashSize, int minLen, int features, bool final_sync);
 // ... for `count` blocks back to back at dIn (bscgpu_lzp_batch_device without the pointer checks): results[b] = what lzp_compress returns
 // for block b, the bytes at the block's own offset in dOut (dIn's layout; may be c->dL, not dIn, not c->dT).  dIn is read in place.
-// Limits and codes: include/bscgpu.h.  c->lzp_last: the sums over the pass.  final_sync as above.
+// The same kernels and the same driver as lzp_device's; the limits of the public batch call (include/bscgpu.h: block size, count, sum)
+// are checked here.  c->lzp_last: the sums over the pass.  final_sync as above.
 // place (or null): the caller packs the pass.  Called once, behind the stage's sync, with the results: it fills dst[b], where block b
 // goes in dOut (preset to lzp::BATCH_NOWHERE: the block gets nothing), and as_it_is[b] != 0 where the block's raw bytes go there
 // instead of a stream; the frame kernel then writes the pass as the caller laid it out (dOut: as many bytes as that takes).

@@ -1,10 +1,14 @@
 // lzp.hip — the LZP encoder on the device, bit-exact with host/lzp.cpp's narrow scanners (hashSize 10..15), in the three stages of
 // DESIGN §3.9.  host/lzp_staged.cpp is the same algorithm on the CPU; the tests hold both to lzp_compress.
 //
-//   A  lzp_key_kernel     thread per byte: key = (chunk << hashSize | slot of the position's context) << 32 | position in the chunk;
-//                         positions 0..3 of a chunk, which the scanner never enters, get a chunk number past the last.
-//      radix_sort_passes  stable, keys only, on the (chunk, slot) bits: two or three 8-bit passes (booked BSCGPU_K_RADIX_AUX)
-//      lzp_link_kernel    thread per sorted key: neighbours with the same (chunk, slot) are predecessor and successor — prev0 / next0,
+// One implementation serves a single block (lzp_device) and all blocks of a batched pass (lzp_batch_device): both hand lzp_stage the
+// chunk table of host/lzp_batch_plan.h — a single block is a pass of one block with 1, 2, 4 or 8 chunks — and every kernel is
+// launched once for all chunks of the table.
+//
+//   A  lzp_key_kernel     thread per byte: key = slot of the position's context << 45 | chunk << 32 | position in the chunk; a
+//                         position outside every chunk, or 0..3 of a chunk, which the scanner never enters, gets the slot 2^hashSize.
+//      radix_sort_passes  stable, keys only, on the slot bits alone: two 8-bit passes (booked BSCGPU_K_RADIX_AUX)
+//      lzp_link_kernel    thread per sorted key: neighbours with the same (slot, chunk) are predecessor and successor — prev0 / next0,
 //                         the table's content "as if every position were visited"
 //   B  lzp_flag_kernel    thread per byte: occupied0 = prev0 > 0, cand0 = the scanner's two-word probe against prev0, is_flag; one
 //                         byte per position.  Also clears the position's dirty byte.
@@ -16,9 +20,8 @@
 //                         position x it skips.  Where the phase decides — behind a failed verify up to retry_after, and the last
 //                         SWEEP_SERIAL_TAIL positions in front of `limit` — thread 0 runs the scanner's own group loop.
 //
-// A pass of small blocks (lzp_batch_device; DESIGN §3.9, "A pass of small blocks"): the same stages over the chunk table of
-// host/lzp_batch_plan.h — lzp_batch_key / _link / _flag / _sweep_kernel, one launch each for all chunks of the pass, the sweep's body
-// (lzp_sweep_chunk) shared with the single block's — and lzp_batch_frame_kernel, which writes every block's frame from a piece list.
+//      lzp_frame_kernel   the frames: every block's table bytes and payloads (coded from the staging area, raw from the input) moved
+//                         into the output from the piece list the host makes of the chunks' results (lzp_batch_plan.h: batch_frame).
 //
 // Every store of the sweep is to out[0, cap) of its chunk: a window is written only after its last byte is known to lie below
 // eob = cap - 8, a group adds at most 6 bytes to an o < eob, a match's length bytes are checked before they are written.  Once o >= eob
@@ -32,9 +35,6 @@ using namespace bschost::lzp;
 
 namespace {
 
-constexpr int DS_LZP = DS_AUX;                                 // dscal / hscal: CR_WORDS per chunk; a context runs no BWT round inside this stage
-constexpr int DS_LZP_TABLE = DS_LZP + 8 * CR_WORDS;            // hscal only: the frame's table on its way up
-static_assert(DS_LZP_TABLE * 4 + 1 + 8 * 8 <= (DS_AUX + DS_AUX_LEN) * 4, "results and table fit the words of the aux indexes");
 static_assert(SWEEP_WINDOW == 4 * WG, "four positions per thread");
 
 __device__ __forceinline__ u32 d_ld32(const u8* p) { u32 v; __builtin_memcpy(&v, p, 4); return v; }
@@ -48,28 +48,54 @@ __device__ __forceinline__ bool d_same(const u8* T, u32 q, u32 ref, int minLen)
 }
 
 // ---- A --------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(WG) void lzp_key_kernel(const u8* __restrict__ T, u32 n, int nc, int hashSize, u64* __restrict__ keys)
+// Keys are slot << 45 | chunk << 32 | position in the chunk, sorted (stable) on the slot bits alone: chunks ascend in the table, so inside
+// a slot the positions stay grouped by chunk and ascending, and neighbours with the same upper word are predecessor and successor.  A
+// position that belongs to no chunk (a block refused by size) or that the scanner never enters gets the slot 2^hashSize, behind all.
+constexpr int BK_SLOT_SHIFT = 45, BK_CHUNK_SHIFT = 32;
+static_assert(BATCH_LZP_MAX_CHUNKS <= 1 << (BK_SLOT_SHIFT - BK_CHUNK_SHIFT), "a chunk's number fits below the slot");
+
+// The chunk that holds position g, from the chunk of a position g0 <= g found before (or -1): the last chunk that starts at or before
+// g, if g lies inside it; else -1.  Advances by at most the chunks that start in (g0, g].
+__device__ __forceinline__ int chunk_first(const BatchChunk* __restrict__ chunks, int nchunks, u32 g0)
+{
+    if (nchunks == 0 || chunks[0].start > g0) return -1;
+    int lo = 0, hi = nchunks;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (chunks[mid].start <= g0) lo = mid; else hi = mid; }
+    return lo;
+}
+__device__ __forceinline__ int chunk_of(const BatchChunk* __restrict__ chunks, int nchunks, int from, u32 g)
+{
+    int k = from;
+    while (k + 1 < nchunks && chunks[k + 1].start <= g) ++k;
+    return k >= 0 && g - chunks[k].start < chunks[k].size ? k : -1;
+}
+
+__global__ __launch_bounds__(WG) void lzp_key_kernel(const u8* __restrict__ T, u32 n, const BatchChunk* __restrict__ chunks, int nchunks,
+                                                      int hashSize, u64* __restrict__ keys)
 {
     const u32 g = blockIdx.x * WG + threadIdx.x;
     if (g >= n) return;
-    const u32 per = n / (u32)nc;
-    u32 b = g / per; if (b >= (u32)nc) b = (u32)nc - 1;
-    const u32 q = g - b * per;
-    u32 hi = 8u << hashSize;                                   // not a position the scanner enters: behind every chunk's keys
-    if (q >= 4) hi = (b << hashSize) | slot_of(ctx_of(T, g), (1u << hashSize) - 1);
-    keys[g] = ((u64)hi << 32) | q;
+    const int k = chunk_of(chunks, nchunks, chunk_first(chunks, nchunks, blockIdx.x * WG), g);
+    u64 key = (u64)(1u << hashSize) << BK_SLOT_SHIFT;
+    if (k >= 0) {
+        const u32 q = g - chunks[k].start;
+        key |= q;
+        if (q >= 4) key = (u64)slot_of(ctx_of(T, g), (1u << hashSize) - 1) << BK_SLOT_SHIFT | (u64)k << BK_CHUNK_SHIFT | q;
+    }
+    keys[g] = key;
 }
 
-__global__ __launch_bounds__(WG) void lzp_link_kernel(const u64* __restrict__ keys, u32 n, int nc, int hashSize,
-                                                       u32* __restrict__ prev0, u32* __restrict__ next0)
+__global__ __launch_bounds__(WG) void lzp_link_kernel(const u64* __restrict__ keys, u32 n, const BatchChunk* __restrict__ chunks, int nchunks,
+                                                       int hashSize, u32* __restrict__ prev0, u32* __restrict__ next0)
 {
     const u32 i = blockIdx.x * WG + threadIdx.x;
     if (i >= n) return;
-    const u64 k = keys[i];
-    const u32 hi = (u32)(k >> 32), q = (u32)k;
-    if (hi >= (8u << hashSize)) return;
-    const u32 g = (hi >> hashSize) * (n / (u32)nc) + q;
-    if (g >= n) return;                                        // (cannot be: the key kernel made it from a position below n)
+    const u64 key = keys[i];
+    const u32 hi = (u32)(key >> 32), q = (u32)key;
+    if (hi >> (BK_SLOT_SHIFT - 32 + hashSize)) return;
+    const u32 k = hi & ((1u << (BK_SLOT_SHIFT - BK_CHUNK_SHIFT)) - 1);
+    if (k >= (u32)nchunks || q >= chunks[k].size) return;      // (cannot be: the key kernel made it from a position of chunk k)
+    const u32 g = chunks[k].start + q;
     const u64 kp = i > 0 ? keys[i - 1] : ~0ull, kn = i + 1 < n ? keys[i + 1] : ~0ull;
     prev0[g] = (u32)(kp >> 32) == hi ? (u32)kp : 0u;
     next0[g] = (u32)(kn >> 32) == hi ? (u32)kn : 0u;
@@ -77,21 +103,22 @@ __global__ __launch_bounds__(WG) void lzp_link_kernel(const u64* __restrict__ ke
 
 // ---- B --------------------------------------------------------------------------------------------------------------------------------
 template <int W>
-__global__ __launch_bounds__(WG) void lzp_flag_kernel(const u8* __restrict__ T, u32 n, int nc, int minLen, const u32* __restrict__ prev0,
-                                                       u8* __restrict__ flags, u8* __restrict__ dirty)
+__global__ __launch_bounds__(WG) void lzp_flag_kernel(const u8* __restrict__ T, u32 n, const BatchChunk* __restrict__ chunks, int nchunks,
+                                                       int minLen, const u32* __restrict__ prev0, u8* __restrict__ flags, u8* __restrict__ dirty)
 {
     const u32 g = blockIdx.x * WG + threadIdx.x;
     if (g >= n) return;
-    const u32 per = n / (u32)nc;
-    u32 b = g / per; if (b >= (u32)nc) b = (u32)nc - 1;
-    const u32 start = b * per, q = g - start;
-    const int size = (int)(b != (u32)nc - 1 ? per : n - start), limit = size - narrow_guard(minLen);
+    const int k = chunk_of(chunks, nchunks, chunk_first(chunks, nchunks, blockIdx.x * WG), g);
     u8 f = 0;
-    if (q >= 4) {
-        const u32 pv = prev0[g];
-        f = (pv > 0 ? F_OCC : 0) | (T[g] == FLAG ? F_FLAG : 0);
-        // q + minLen <= limit + 2 + minLen < size: the probe stays inside the chunk
-        if (pv > 0 && (int)q < limit + 3 && d_same<W>(T + start, q, pv, minLen)) f |= F_CAND;
+    if (k >= 0) {
+        const u32 start = chunks[k].start, q = g - start;
+        const int limit = (int)chunks[k].size - narrow_guard(minLen);
+        if (q >= 4) {
+            const u32 pv = prev0[g];
+            f = (pv > 0 ? F_OCC : 0) | (T[g] == FLAG ? F_FLAG : 0);
+            // q + minLen <= limit + 2 + minLen < size: the probe stays inside the chunk
+            if (pv > 0 && (int)q < limit + 3 && d_same<W>(T + start, q, pv, minLen)) f |= F_CAND;
+        }
     }
     flags[g] = f;
     dirty[g] = 0;
@@ -101,7 +128,7 @@ __global__ __launch_bounds__(WG) void lzp_flag_kernel(const u8* __restrict__ T, 
 struct SweepState { int p, o, retry, cand; u32 seen; int len, win_m, win_e; u32 cnt[CR_WORDS]; u32 scan[8]; };
 
 // The sweep of one chunk by one workgroup: T, the links, the flag and dirty bytes and out are the chunk's own (its first byte at 0), res its
-// result record, table 2^hashSize words of LDS.  The single-block kernel and the pass's kernel differ only in where they take these from.
+// result record, table 2^hashSize words of LDS.
 template <int W, bool VERIFY>
 __device__ __forceinline__ void lzp_sweep_chunk(const u8* const T, const int size, const int cap, int hashSize, int minLen,
                                                 const u32* const prev0, const u32* const next0, const u8* const flags, u8* const dirty,
@@ -262,113 +289,24 @@ __device__ __forceinline__ void lzp_sweep_chunk(const u8* const T, const int siz
 }
 
 template <int W, bool VERIFY>
-__global__ __launch_bounds__(WG) void lzp_sweep_kernel(const u8* __restrict__ Tall, u32 n, int nc, int hashSize, int minLen, int single_cap,
-                                                        const u32* __restrict__ prev0_all, const u32* __restrict__ next0_all,
+__global__ __launch_bounds__(WG) void lzp_sweep_kernel(const u8* __restrict__ Tall, const BatchChunk* __restrict__ chunks, int hashSize,
+                                                        int minLen, const u32* __restrict__ prev0_all, const u32* __restrict__ next0_all,
                                                         const u8* __restrict__ flags_all, u8* dirty_all, u8* out_all, u32* __restrict__ res)
 {
     extern __shared__ u32 table[];                             // 2^hashSize words: the last VISITED position of every slot, 0 = none
-    __shared__ SweepState S;
-    const int b = (int)blockIdx.x;
-    const u32 start = (u32)b * (n / (u32)nc);
-    const int size = (int)(b != nc - 1 ? n / (u32)nc : n - start);
-    lzp_sweep_chunk<W, VERIFY>(Tall + start, size, nc == 1 ? single_cap : size, hashSize, minLen, prev0_all + start, next0_all + start,
-                               flags_all + start, dirty_all + start, out_all + start, res + b * CR_WORDS, table, S);
-}
-
-// ---- a pass of small blocks: the same three stages over the chunk table of lzp_batch_plan.h --------------------------------------------
-// Keys are slot << 45 | chunk << 32 | position in the chunk, sorted (stable) on the slot bits alone: chunks ascend in the pass, so inside
-// a slot the positions stay grouped by chunk and ascending, and neighbours with the same upper word are predecessor and successor.  A
-// position that belongs to no chunk (a block refused by size) or that the scanner never enters gets the slot 2^hashSize, behind all.
-constexpr int BK_SLOT_SHIFT = 45, BK_CHUNK_SHIFT = 32;
-static_assert(BATCH_LZP_MAX_CHUNKS <= 1 << (BK_SLOT_SHIFT - BK_CHUNK_SHIFT), "a chunk's number fits below the slot");
-
-// The chunk that holds position g, from the chunk of a position g0 <= g found before (or -1): the last chunk that starts at or before
-// g, if g lies inside it; else -1.  Advances by at most the chunks that start in (g0, g].
-__device__ __forceinline__ int batch_chunk_first(const BatchChunk* __restrict__ chunks, int nchunks, u32 g0)
-{
-    if (nchunks == 0 || chunks[0].start > g0) return -1;
-    int lo = 0, hi = nchunks;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (chunks[mid].start <= g0) lo = mid; else hi = mid; }
-    return lo;
-}
-__device__ __forceinline__ int batch_chunk_of(const BatchChunk* __restrict__ chunks, int nchunks, int from, u32 g)
-{
-    int k = from;
-    while (k + 1 < nchunks && chunks[k + 1].start <= g) ++k;
-    return k >= 0 && g - chunks[k].start < chunks[k].size ? k : -1;
-}
-
-__global__ __launch_bounds__(WG) void lzp_batch_key_kernel(const u8* __restrict__ T, u32 n, const BatchChunk* __restrict__ chunks, int nchunks,
-                                                            int hashSize, u64* __restrict__ keys)
-{
-    const u32 g = blockIdx.x * WG + threadIdx.x;
-    if (g >= n) return;
-    const int k = batch_chunk_of(chunks, nchunks, batch_chunk_first(chunks, nchunks, blockIdx.x * WG), g);
-    u64 key = (u64)(1u << hashSize) << BK_SLOT_SHIFT;
-    if (k >= 0) {
-        const u32 q = g - chunks[k].start;
-        key |= q;
-        if (q >= 4) key = (u64)slot_of(ctx_of(T, g), (1u << hashSize) - 1) << BK_SLOT_SHIFT | (u64)k << BK_CHUNK_SHIFT | q;
-    }
-    keys[g] = key;
-}
-
-__global__ __launch_bounds__(WG) void lzp_batch_link_kernel(const u64* __restrict__ keys, u32 n, const BatchChunk* __restrict__ chunks, int nchunks,
-                                                             int hashSize, u32* __restrict__ prev0, u32* __restrict__ next0)
-{
-    const u32 i = blockIdx.x * WG + threadIdx.x;
-    if (i >= n) return;
-    const u64 key = keys[i];
-    const u32 hi = (u32)(key >> 32), q = (u32)key;
-    if (hi >> (BK_SLOT_SHIFT - 32 + hashSize)) return;
-    const u32 k = hi & ((1u << (BK_SLOT_SHIFT - BK_CHUNK_SHIFT)) - 1);
-    if (k >= (u32)nchunks || q >= chunks[k].size) return;      // (cannot be: the key kernel made it from a position of chunk k)
-    const u32 g = chunks[k].start + q;
-    const u64 kp = i > 0 ? keys[i - 1] : ~0ull, kn = i + 1 < n ? keys[i + 1] : ~0ull;
-    prev0[g] = (u32)(kp >> 32) == hi ? (u32)kp : 0u;
-    next0[g] = (u32)(kn >> 32) == hi ? (u32)kn : 0u;
-}
-
-template <int W>
-__global__ __launch_bounds__(WG) void lzp_batch_flag_kernel(const u8* __restrict__ T, u32 n, const BatchChunk* __restrict__ chunks, int nchunks,
-                                                             int minLen, const u32* __restrict__ prev0, u8* __restrict__ flags, u8* __restrict__ dirty)
-{
-    const u32 g = blockIdx.x * WG + threadIdx.x;
-    if (g >= n) return;
-    const int k = batch_chunk_of(chunks, nchunks, batch_chunk_first(chunks, nchunks, blockIdx.x * WG), g);
-    u8 f = 0;
-    if (k >= 0) {
-        const u32 start = chunks[k].start, q = g - start;
-        const int limit = (int)chunks[k].size - narrow_guard(minLen);
-        if (q >= 4) {
-            const u32 pv = prev0[g];
-            f = (pv > 0 ? F_OCC : 0) | (T[g] == FLAG ? F_FLAG : 0);
-            // q + minLen <= limit + 2 + minLen < size: the probe stays inside the chunk
-            if (pv > 0 && (int)q < limit + 3 && d_same<W>(T + start, q, pv, minLen)) f |= F_CAND;
-        }
-    }
-    flags[g] = f;
-    dirty[g] = 0;
-}
-
-template <int W, bool VERIFY>
-__global__ __launch_bounds__(WG) void lzp_batch_sweep_kernel(const u8* __restrict__ Tall, const BatchChunk* __restrict__ chunks, int hashSize,
-                                                              int minLen, const u32* __restrict__ prev0_all, const u32* __restrict__ next0_all,
-                                                              const u8* __restrict__ flags_all, u8* dirty_all, u8* out_all, u32* __restrict__ res)
-{
-    extern __shared__ u32 table[];
     __shared__ SweepState S;
     const BatchChunk C = chunks[blockIdx.x];
     lzp_sweep_chunk<W, VERIFY>(Tall + C.start, (int)C.size, (int)C.cap, hashSize, minLen, prev0_all + C.start, next0_all + C.start,
                                flags_all + C.start, dirty_all + C.start, out_all + C.start, res + blockIdx.x * CR_WORDS, table, S);
 }
 
-// The frames of a pass in one launch: piece p is moved by the workgroups wg_first[p] .. wg_first[p + 1] - 1, FRAME_SPAN bytes each, as
-// aligned words of the output with the bytes in front of and behind them one by one.
+// ---- the frames -----------------------------------------------------------------------------------------------------------------------
+// All pieces in one launch: piece p is moved by the workgroups wg_first[p] .. wg_first[p + 1] - 1, FRAME_SPAN bytes each, as aligned
+// words of the output with the bytes in front of and behind them one by one.
 constexpr u32 FRAME_SPAN = 16384;
-__global__ __launch_bounds__(WG) void lzp_batch_frame_kernel(const BatchPiece* __restrict__ pieces, const u32* __restrict__ wg_first, u32 npieces,
-                                                              const u8* __restrict__ staging, const u8* __restrict__ raw,
-                                                              const u8* __restrict__ tab, u8* __restrict__ out)
+__global__ __launch_bounds__(WG) void lzp_frame_kernel(const BatchPiece* __restrict__ pieces, const u32* __restrict__ wg_first, u32 npieces,
+                                                        const u8* __restrict__ staging, const u8* __restrict__ raw,
+                                                        const u8* __restrict__ tab, u8* __restrict__ out)
 {
     const u32 tid = threadIdx.x;
     u32 lo = 0, hi = npieces;
@@ -386,99 +324,9 @@ __global__ __launch_bounds__(WG) void lzp_batch_frame_kernel(const BatchPiece* _
     if (tid < len - behind) dst[behind + tid] = src[behind + tid];
 }
 
-template <int W, bool VERIFY>
-int launch_sweep(bscgpu_ctx* c, int nc, size_t lds, const u8* T, u32 n, int hashSize, int minLen, const u32* prev0, const u32* next0,
-                 const u8* flags, u8* dirty, u8* out, u32* res)
-{
-    const int bit = 1 << ((W == 8) + VERIFY);                  // the limit is a per-device attribute of the function: once per context
-    if (!(c->lzp_lds_set & bit)) {
-        HIP_TRY(c, hipFuncSetAttribute((const void*)lzp_sweep_kernel<W, VERIFY>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 << STAGED_MAX_HASH));
-        c->lzp_lds_set |= bit;
-    }
-    hipLaunchKernelGGL((lzp_sweep_kernel<W, VERIFY>), dim3(nc), dim3(WG), lds, c->stream, T, n, nc, hashSize, minLen, (int)n - 2,
-                       prev0, next0, flags, dirty, out, res);
-    return BSC_NO_ERROR;
-}
-
-}  // namespace
-
-// The stage on c->stream: dIn (HBM, n bytes; may be c->dT, may be dOut) -> what lzp_compress returns, the same bytes in dOut (HBM, n
-// bytes; may be c->dL).  Arena roles, all dead between two blocks: dT the raw input, kA / kB the sort's keys, vA / vB the links, flags
-// and SA the flag and dirty bytes, ISA the chunks' staging.  One sync for the chunks' results; final_sync: a second one behind the
-// frame's copies (a caller that goes on in c->stream does not need it).
-int lzp_device(bscgpu_ctx* c, const u8* dIn, u8* dOut, int n, int hashSize, int minLen, int features, bool final_sync)
-{
-    for (auto& v : c->lzp_last) v = 0;
-    if (hashSize > STAGED_MAX_HASH) return BSC_NOT_SUPPORTED;           // the table of a chunk would not fit LDS; the wide scanner is another algorithm
-    if (n > c->max_n) return BSC_GPU_NOT_ENOUGH_MEMORY;
-    const int nc = num_chunks(n);
-    if (nc == 1 && ((int64_t)n - minLen < 32 || n - 2 < 16)) return BSC_NOT_COMPRESSIBLE;      // lzp.cpp:531 (chunks of a larger block are 128 KiB and more)
-    const u32 N = (u32)n, grid = (N + WG - 1) / WG;
-    u64 *keys = c->kA, *keys_alt = c->kB;
-    u32 *prev0 = c->vA, *next0 = c->vB;
-    u8 *flags = c->flags, *dirty = reinterpret_cast<u8*>(c->SA), *staging = reinterpret_cast<u8*>(c->ISA);
-    u32* res = c->dscal + DS_LZP;
-    if (dIn != c->dT) HIP_TRY(c, hipMemcpyAsync(c->dT, dIn, (size_t)n, hipMemcpyDeviceToDevice, c->stream));
-
-    prof_begin(c, BSCGPU_K_LZP, (u64)n * 9, N);
-    hipLaunchKernelGGL(lzp_key_kernel, dim3(grid), dim3(WG), 0, c->stream, c->dT, N, nc, hashSize, keys);
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    const int kbits = hashSize + 4, npass = (kbits + 7) / 8;
-    RadixPass passes[3];
-    for (int p = 0; p < npass; ++p) { passes[p].shift = 32 + 8 * p; passes[p].bits = kbits - 8 * p < 8 ? kbits - 8 * p : 8; }
-    int in_alt = 0;
-    RC_TRY(radix_sort_passes(c, keys, keys_alt, nullptr, nullptr, N, passes, npass, &in_alt, nullptr, /* aux */ true));
-    const u64* sorted = in_alt ? keys_alt : keys;
-
-    const int W = narrow_word(minLen);
-    const bool verify = narrow_verify(minLen);
-    prof_begin(c, BSCGPU_K_LZP, (u64)n * 30, N);
-    hipLaunchKernelGGL(lzp_link_kernel, dim3(grid), dim3(WG), 0, c->stream, sorted, N, nc, hashSize, prev0, next0);
-    if (W == 4) hipLaunchKernelGGL(lzp_flag_kernel<4>, dim3(grid), dim3(WG), 0, c->stream, c->dT, N, nc, minLen, prev0, flags, dirty);
-    else        hipLaunchKernelGGL(lzp_flag_kernel<8>, dim3(grid), dim3(WG), 0, c->stream, c->dT, N, nc, minLen, prev0, flags, dirty);
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-
-    const size_t lds = (size_t)4 << hashSize;
-    prof_begin(c, BSCGPU_K_LZP, (u64)n * 4, N);
-    if (verify)      RC_TRY((launch_sweep<8, true >(c, nc, lds, c->dT, N, hashSize, minLen, prev0, next0, flags, dirty, staging, res)));
-    else if (W == 8) RC_TRY((launch_sweep<8, false>(c, nc, lds, c->dT, N, hashSize, minLen, prev0, next0, flags, dirty, staging, res)));
-    else             RC_TRY((launch_sweep<4, false>(c, nc, lds, c->dT, N, hashSize, minLen, prev0, next0, flags, dirty, staging, res)));
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->hscal + DS_LZP, res, (size_t)nc * CR_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, ctx_sync(c));
-    prof_collect(c);
-
-    int own[8];
-    for (int b = 0; b < nc; ++b) {
-        const u32* r = c->hscal + DS_LZP + b * CR_WORDS;
-        own[b] = (int)r[CR_RES];
-        if (own[b] >= 0 && own[b] > chunk_size(n, nc, b)) return ctx_fail(c, BSC_GPU_ERROR, "LZP stage: a chunk's size is out of range", hipSuccess);
-        c->lzp_last[CNT_MATCHES] += r[CR_MATCHES]; c->lzp_last[CNT_DIRTY] += r[CR_DIRTY];
-        c->lzp_last[CNT_ZONES] += r[CR_ZONES]; c->lzp_last[CNT_ESCAPES] += r[CR_ESCAPES];
-    }
-    Frame F;
-    const int total = frame_from_own(n, features, own, &F);
-    c->lzp_last[CNT_RAW_CHUNKS] = F.raw_chunks;
-    if (total < 0) return total;
-    unsigned char* tab = reinterpret_cast<unsigned char*>(c->hscal + DS_LZP_TABLE);     // pinned: it goes up behind this call's return
-    const int tab_bytes = frame_table(F, tab);
-    HIP_TRY(c, hipMemcpyAsync(dOut, tab, (size_t)tab_bytes, hipMemcpyHostToDevice, c->stream));
-    for (int b = 0; b < nc; ++b) {
-        const u8* src = (nc > 1 && F.res[b] == F.size[b] ? c->dT : staging) + F.start[b];
-        if (F.res[b] > 0) HIP_TRY(c, hipMemcpyAsync(dOut + F.off[b], src, (size_t)F.res[b], hipMemcpyDeviceToDevice, c->stream));
-    }
-    if (final_sync) HIP_TRY(c, ctx_sync(c));
-    return total;
-}
-
-// ---- the stage over a pass ------------------------------------------------------------------------------------------------------------------
-namespace {
-
+// ---- the stage ------------------------------------------------------------------------------------------------------------------------
 // c->lzp_tab (HBM) and c->lzp_tab_host (pinned), the same map: nothing of it is an arena buffer, so the sort in the middle of the stage
-// and whatever follows the stage leave it alone.
+// and whatever follows the stage leave it alone.  Allocated by the first call of either entry point.
 constexpr size_t LT_CHUNKS = 0;                                                              // BatchChunk [BATCH_LZP_MAX_CHUNKS]
 constexpr size_t LT_RES    = LT_CHUNKS + sizeof(BatchChunk) * BATCH_LZP_MAX_CHUNKS;          // u32 [BATCH_LZP_MAX_CHUNKS][CR_WORDS]
 constexpr size_t LT_PIECES = LT_RES + (size_t)4 * CR_WORDS * BATCH_LZP_MAX_CHUNKS;           // BatchPiece [BATCH_LZP_MAX_PIECES]
@@ -486,42 +334,43 @@ constexpr size_t LT_WG     = LT_PIECES + sizeof(BatchPiece) * BATCH_LZP_MAX_PIEC
 constexpr size_t LT_TABLE  = LT_WG + (((size_t)4 * (BATCH_LZP_MAX_PIECES + 1) + 255) & ~(size_t)255);   // the blocks' table bytes
 constexpr size_t LT_BYTES  = LT_TABLE + (size_t)BATCH_LZP_TABLE_BYTES * BATCH_LZP_MAX_BLOCKS;
 static_assert(sizeof(BatchChunk) == 16 && sizeof(BatchPiece) == 16, "the kernels read the host's records as they stand");
+// a single block has up to eight chunks whatever its size: 8 entries, a table of 1 + 8 * 8 bytes and eight payloads
+static_assert(BATCH_LZP_MAX_CHUNKS >= 8 && BATCH_LZP_MAX_PIECES >= 1 + 8, "a single block's chunks and pieces fit LT_CHUNKS / LT_RES and LT_PIECES / LT_WG");
+static_assert((size_t)BATCH_LZP_TABLE_BYTES * BATCH_LZP_MAX_BLOCKS >= 1 + 8 * 8, "a single block's table fits LT_TABLE");
 
 int lzp_tab_ensure(bscgpu_ctx* c)
 {
     if (c->lzp_tab && c->lzp_tab_host) return BSC_NO_ERROR;
     if (!c->lzp_tab_host && hipHostMalloc((void**)&c->lzp_tab_host, LT_BYTES, hipHostMallocDefault) != hipSuccess) {
         (void)hipGetLastError(); c->lzp_tab_host = nullptr;
-        return ctx_fail(c, BSC_NOT_ENOUGH_MEMORY, "LZP stage of a pass: pinned tables", hipSuccess);
+        return ctx_fail(c, BSC_NOT_ENOUGH_MEMORY, "LZP stage: pinned tables", hipSuccess);
     }
     if (!c->lzp_tab && hipMalloc((void**)&c->lzp_tab, LT_BYTES) != hipSuccess) {
         (void)hipGetLastError(); c->lzp_tab = nullptr;
-        return ctx_fail(c, BSC_GPU_NOT_ENOUGH_MEMORY, "LZP stage of a pass: tables", hipSuccess);
+        return ctx_fail(c, BSC_GPU_NOT_ENOUGH_MEMORY, "LZP stage: tables", hipSuccess);
     }
     c->lzp_tab_bytes = LT_BYTES;
     return BSC_NO_ERROR;
 }
 
 template <int W, bool VERIFY>
-int launch_batch_sweep(bscgpu_ctx* c, int nchunks, size_t lds, const u8* T, const BatchChunk* chunks, int hashSize, int minLen, const u32* prev0,
-                       const u32* next0, const u8* flags, u8* dirty, u8* out, u32* res)
+int launch_sweep(bscgpu_ctx* c, int nchunks, size_t lds, const u8* T, const BatchChunk* chunks, int hashSize, int minLen, const u32* prev0,
+                 const u32* next0, const u8* flags, u8* dirty, u8* out, u32* res)
 {
-    const int bit = 8 << ((W == 8) + VERIFY);                  // (the single-block variants hold bits 0..2)
+    const int bit = 1 << ((W == 8) + VERIFY);                  // the limit is a per-device attribute of the function: once per context
     if (!(c->lzp_lds_set & bit)) {
-        HIP_TRY(c, hipFuncSetAttribute((const void*)lzp_batch_sweep_kernel<W, VERIFY>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 << STAGED_MAX_HASH));
+        HIP_TRY(c, hipFuncSetAttribute((const void*)lzp_sweep_kernel<W, VERIFY>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 << STAGED_MAX_HASH));
         c->lzp_lds_set |= bit;
     }
-    hipLaunchKernelGGL((lzp_batch_sweep_kernel<W, VERIFY>), dim3(nchunks), dim3(WG), lds, c->stream, T, chunks, hashSize, minLen,
+    hipLaunchKernelGGL((lzp_sweep_kernel<W, VERIFY>), dim3(nchunks), dim3(WG), lds, c->stream, T, chunks, hashSize, minLen,
                        prev0, next0, flags, dirty, out, res);
     return BSC_NO_ERROR;
 }
 
-}  // namespace
-
-// Stages A, B and C over the chunk table the host left in the pinned mirror: the table goes up, the chunks' result records come down, one
-// sync.  Arena roles as lzp_device's, sized by max_n and serving a pass as they serve a block: kA / kB the sort's keys, vA / vB the links,
-// flags and SA the flag and dirty bytes, ISA the chunks' staging.  The input is read where it lies.
-static int lzp_batch_sweeps(bscgpu_ctx* c, const u8* dIn, u32 N, int nchunks, int hashSize, int minLen)
+// Stages A, B and C over the chunk table the caller left in the pinned mirror: the table goes up, the chunks' result records come down, one
+// sync.  Arena roles, all dead between two blocks and sized by max_n, serving a pass as they serve a block: kA / kB the sort's keys,
+// vA / vB the links, flags and SA the flag and dirty bytes, ISA the chunks' staging.  The input is read where it lies.
+int lzp_sweeps(bscgpu_ctx* c, const u8* dIn, u32 N, int nchunks, int hashSize, int minLen)
 {
     const u32 grid = (N + WG - 1) / WG;
     unsigned char* const H = c->lzp_tab_host;
@@ -533,7 +382,7 @@ static int lzp_batch_sweeps(bscgpu_ctx* c, const u8* dIn, u32 N, int nchunks, in
     HIP_TRY(c, hipMemcpyAsync(c->lzp_tab + LT_CHUNKS, H + LT_CHUNKS, sizeof(BatchChunk) * (size_t)nchunks, hipMemcpyHostToDevice, c->stream));
 
     prof_begin(c, BSCGPU_K_LZP, (u64)N * 9, N);
-    hipLaunchKernelGGL(lzp_batch_key_kernel, dim3(grid), dim3(WG), 0, c->stream, dIn, N, dchunks, nchunks, hashSize, keys);
+    hipLaunchKernelGGL(lzp_key_kernel, dim3(grid), dim3(WG), 0, c->stream, dIn, N, dchunks, nchunks, hashSize, keys);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     const int kbits = hashSize + 1;                            // the slot and the bit of the positions behind all slots: two passes
@@ -545,17 +394,17 @@ static int lzp_batch_sweeps(bscgpu_ctx* c, const u8* dIn, u32 N, int nchunks, in
     const int W = narrow_word(minLen);
     const bool verify = narrow_verify(minLen);
     prof_begin(c, BSCGPU_K_LZP, (u64)N * 30, N);
-    hipLaunchKernelGGL(lzp_batch_link_kernel, dim3(grid), dim3(WG), 0, c->stream, sorted, N, dchunks, nchunks, hashSize, prev0, next0);
-    if (W == 4) hipLaunchKernelGGL(lzp_batch_flag_kernel<4>, dim3(grid), dim3(WG), 0, c->stream, dIn, N, dchunks, nchunks, minLen, prev0, flags, dirty);
-    else        hipLaunchKernelGGL(lzp_batch_flag_kernel<8>, dim3(grid), dim3(WG), 0, c->stream, dIn, N, dchunks, nchunks, minLen, prev0, flags, dirty);
+    hipLaunchKernelGGL(lzp_link_kernel, dim3(grid), dim3(WG), 0, c->stream, sorted, N, dchunks, nchunks, hashSize, prev0, next0);
+    if (W == 4) hipLaunchKernelGGL(lzp_flag_kernel<4>, dim3(grid), dim3(WG), 0, c->stream, dIn, N, dchunks, nchunks, minLen, prev0, flags, dirty);
+    else        hipLaunchKernelGGL(lzp_flag_kernel<8>, dim3(grid), dim3(WG), 0, c->stream, dIn, N, dchunks, nchunks, minLen, prev0, flags, dirty);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
 
     const size_t lds = (size_t)4 << hashSize;
     prof_begin(c, BSCGPU_K_LZP, (u64)N * 4, N);
-    if (verify)      RC_TRY((launch_batch_sweep<8, true >(c, nchunks, lds, dIn, dchunks, hashSize, minLen, prev0, next0, flags, dirty, staging, res)));
-    else if (W == 8) RC_TRY((launch_batch_sweep<8, false>(c, nchunks, lds, dIn, dchunks, hashSize, minLen, prev0, next0, flags, dirty, staging, res)));
-    else             RC_TRY((launch_batch_sweep<4, false>(c, nchunks, lds, dIn, dchunks, hashSize, minLen, prev0, next0, flags, dirty, staging, res)));
+    if (verify)      RC_TRY((launch_sweep<8, true >(c, nchunks, lds, dIn, dchunks, hashSize, minLen, prev0, next0, flags, dirty, staging, res)));
+    else if (W == 8) RC_TRY((launch_sweep<8, false>(c, nchunks, lds, dIn, dchunks, hashSize, minLen, prev0, next0, flags, dirty, staging, res)));
+    else             RC_TRY((launch_sweep<4, false>(c, nchunks, lds, dIn, dchunks, hashSize, minLen, prev0, next0, flags, dirty, staging, res)));
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(H + LT_RES, res, (size_t)nchunks * CR_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
@@ -564,25 +413,18 @@ static int lzp_batch_sweeps(bscgpu_ctx* c, const u8* dIn, u32 N, int nchunks, in
     return BSC_NO_ERROR;
 }
 
-int lzp_batch_device(bscgpu_ctx* c, const u8* dIn, u8* dOut, const int* sizes, int count, int hashSize, int minLen, int features, int* results,
-                     bool final_sync, const LzpBatchPlace* place)
+// The stage on c->stream for `count` blocks back to back at dIn, N bytes in all, whose chunk table (nchunks entries) the caller has
+// planned into the pinned mirror: the sweeps, then on the host the results and the piece list (batch_frame), then the frame kernel
+// into dOut.  results[b] = what lzp_compress returns for block b; c->lzp_last: the paths taken, summed.  One sync for the chunks'
+// results; final_sync: a second one behind the frame kernel (a caller that goes on in c->stream does not need it).  place: dev_common.h.
+int lzp_stage(bscgpu_ctx* c, const u8* dIn, u8* dOut, const int* sizes, int count, u32 N, int nchunks, int hashSize, int minLen, int features,
+              int* results, bool final_sync, const LzpBatchPlace* place)
 {
-    for (auto& v : c->lzp_last) v = 0;
-    if (hashSize > STAGED_MAX_HASH) return BSC_NOT_SUPPORTED;
-    if (count < 0 || count > BATCH_LZP_MAX_BLOCKS) return BSC_BAD_PARAMETER;
-    RC_TRY(lzp_tab_ensure(c));
     unsigned char* const H = c->lzp_tab_host;
-    BatchChunk* const hchunks = reinterpret_cast<BatchChunk*>(H + LT_CHUNKS);
-    const int nchunks = batch_plan(sizes, count, minLen, hchunks);
-    if (nchunks < 0) return nchunks;
-    int64_t total = 0;
-    for (int b = 0; b < count; ++b) total += sizes[b];
-    if (total > c->max_n) return BSC_BAD_PARAMETER;
+    const BatchChunk* const hchunks = reinterpret_cast<const BatchChunk*>(H + LT_CHUNKS);
     BatchPiece* const hpieces = reinterpret_cast<BatchPiece*>(H + LT_PIECES);
-    const u32 N = (u32)total;
-    u8* const staging = reinterpret_cast<u8*>(c->ISA);
     const u32* hres = reinterpret_cast<const u32*>(H + LT_RES);
-    if (nchunks > 0) RC_TRY(lzp_batch_sweeps(c, dIn, N, nchunks, hashSize, minLen));
+    if (nchunks > 0) RC_TRY(lzp_sweeps(c, dIn, N, nchunks, hashSize, minLen));
     else if (place) HIP_TRY(c, ctx_sync(c));                   // (no block reaches the encoder; the piece list of the call before may still be going up)
 
     std::vector<int> own((size_t)nchunks);
@@ -590,11 +432,9 @@ int lzp_batch_device(bscgpu_ctx* c, const u8* dIn, u8* dOut, const int* sizes, i
         const u32* r = hres + (size_t)k * CR_WORDS;
         own[(size_t)k] = (int)r[CR_RES];
         if (own[(size_t)k] >= 0 && (u32)own[(size_t)k] > hchunks[k].cap)
-            return ctx_fail(c, BSC_GPU_ERROR, "LZP stage of a pass: a chunk's size is out of range", hipSuccess);
-        c->lzp_last[CNT_MATCHES] += r[CR_MATCHES]; c->lzp_last[CNT_DIRTY] += r[CR_DIRTY];
-        c->lzp_last[CNT_ZONES] += r[CR_ZONES]; c->lzp_last[CNT_ESCAPES] += r[CR_ESCAPES];
+            return ctx_fail(c, BSC_GPU_ERROR, "LZP stage: a chunk's size is out of range", hipSuccess);
+        count_chunk(c->lzp_last, r);
     }
-    int64_t raw_chunks = 0;
     std::vector<u32> dst;
     std::vector<unsigned char> as_it_is;
     if (place) {                                               // the caller packs the pass: it says where every block goes once it knows the results
@@ -602,9 +442,8 @@ int lzp_batch_device(bscgpu_ctx* c, const u8* dIn, u8* dOut, const int* sizes, i
         dst.assign((size_t)count + 1, BATCH_NOWHERE); as_it_is.assign((size_t)count + 1, 0);
         (*place)(results, dst.data(), as_it_is.data());
     }
-    const int np = batch_frame(sizes, count, minLen, features, own.data(), results, hpieces, H + LT_TABLE, &raw_chunks,
+    const int np = batch_frame(sizes, count, minLen, features, own.data(), results, hpieces, H + LT_TABLE, &c->lzp_last[CNT_RAW_CHUNKS],
                                place ? dst.data() : nullptr, place ? as_it_is.data() : nullptr);
-    c->lzp_last[CNT_RAW_CHUNKS] = raw_chunks;
     if (np > 0) {
         u32* const hwg = reinterpret_cast<u32*>(H + LT_WG);
         u32 wgs = 0, tab_bytes = 0;
@@ -617,13 +456,48 @@ int lzp_batch_device(bscgpu_ctx* c, const u8* dIn, u8* dOut, const int* sizes, i
         HIP_TRY(c, hipMemcpyAsync(c->lzp_tab + LT_WG, hwg, (size_t)4 * (np + 1), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(c->lzp_tab + LT_TABLE, H + LT_TABLE, tab_bytes, hipMemcpyHostToDevice, c->stream));
         prof_begin(c, BSCGPU_K_LZP, (u64)N * 2, N);
-        hipLaunchKernelGGL(lzp_batch_frame_kernel, dim3(wgs), dim3(WG), 0, c->stream, reinterpret_cast<const BatchPiece*>(c->lzp_tab + LT_PIECES),
-                           reinterpret_cast<const u32*>(c->lzp_tab + LT_WG), (u32)np, staging, dIn, c->lzp_tab + LT_TABLE, dOut);
+        hipLaunchKernelGGL(lzp_frame_kernel, dim3(wgs), dim3(WG), 0, c->stream, reinterpret_cast<const BatchPiece*>(c->lzp_tab + LT_PIECES),
+                           reinterpret_cast<const u32*>(c->lzp_tab + LT_WG), (u32)np, reinterpret_cast<const u8*>(c->ISA), dIn,
+                           c->lzp_tab + LT_TABLE, dOut);
         prof_end(c);
         HIP_TRY(c, hipGetLastError());
     }
     if (final_sync) { HIP_TRY(c, ctx_sync(c)); prof_collect(c); }
     return BSC_NO_ERROR;
+}
+
+}  // namespace
+
+// A single block: a pass of one block, read from c->dT.
+int lzp_device(bscgpu_ctx* c, const u8* dIn, u8* dOut, int n, int hashSize, int minLen, int features, bool final_sync)
+{
+    for (auto& v : c->lzp_last) v = 0;
+    if (hashSize > STAGED_MAX_HASH) return BSC_NOT_SUPPORTED;           // the table of a chunk would not fit LDS; the wide scanner is another algorithm
+    if (n > c->max_n) return BSC_GPU_NOT_ENOUGH_MEMORY;
+    if (num_chunks(n) == 1 && batch_refused_by_size(n, minLen)) return BSC_NOT_COMPRESSIBLE;       // (chunks of a larger block are 128 KiB and more)
+    RC_TRY(lzp_tab_ensure(c));
+    const int nchunks = plan_block(n, minLen, 0, 0, reinterpret_cast<BatchChunk*>(c->lzp_tab_host + LT_CHUNKS));
+    // dOut may be dIn, and the frame kernel reads raw chunks while dOut is being written: the stage reads the block in dT
+    if (dIn != c->dT) HIP_TRY(c, hipMemcpyAsync(c->dT, dIn, (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+    int result = 0;
+    RC_TRY(lzp_stage(c, c->dT, dOut, &n, 1, (u32)n, nchunks, hashSize, minLen, features, &result, final_sync, nullptr));
+    return result;
+}
+
+// A pass: the public batch call's limits (batch_plan), then the stage where the pass lies.
+int lzp_batch_device(bscgpu_ctx* c, const u8* dIn, u8* dOut, const int* sizes, int count, int hashSize, int minLen, int features, int* results,
+                     bool final_sync, const LzpBatchPlace* place)
+{
+    for (auto& v : c->lzp_last) v = 0;
+    if (hashSize > STAGED_MAX_HASH) return BSC_NOT_SUPPORTED;
+    if (count < 0 || count > BATCH_LZP_MAX_BLOCKS) return BSC_BAD_PARAMETER;
+    RC_TRY(lzp_tab_ensure(c));
+    const int nchunks = batch_plan(sizes, count, minLen, reinterpret_cast<BatchChunk*>(c->lzp_tab_host + LT_CHUNKS));
+    if (nchunks < 0) return nchunks;
+    int64_t total = 0;
+    for (int b = 0; b < count; ++b) total += sizes[b];
+    if (total > c->max_n) return BSC_BAD_PARAMETER;
+    return lzp_stage(c, dIn, dOut, sizes, count, (u32)total, nchunks, hashSize, minLen, features, results, final_sync, place);
 }
 
 extern "C" int bscgpu_lzp_batch_device(bscgpu_ctx* c, const void* dIn, void* dOut, const int* sizes, int count, int hashSize, int minLen,
@@ -659,5 +533,6 @@ extern "C" int bscgpu_lzp_compress(bscgpu_ctx* c, const uint8_t* in, uint8_t* ou
     if (r < 0) { (void)ctx_sync(c); return r; }               // (the upload reads the caller's buffer)
     HIP_TRY(c, hipMemcpyAsync(out, c->dL, (size_t)r, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, ctx_sync(c));
+    prof_collect(c);                                           // (the frame kernel's range)
     return r;
 }

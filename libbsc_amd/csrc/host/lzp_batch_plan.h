@@ -1,6 +1,7 @@
-// lzp_batch_plan.h — the LZP stage over all blocks of a batched pass (device/lzp.hip: lzp_batch_device; DESIGN §3.9, "A pass of small
-// blocks"): the chunk table of a pass and the piece list that frames its blocks, as pure functions of the sizes and of the chunks'
-// results.  Plain arithmetic, no HIP; the CPU tests pin both (bscgpu_lzp_batch_plan, bscgpu_lzp_batch_frame).
+// lzp_batch_plan.h — what drives the LZP stage (device/lzp.hip, and its CPU stand-in lzp_staged.cpp): the chunk table of
+// a pass of blocks and the piece list that frames them, as pure functions of the sizes and of the chunks' results.  A single block of
+// any size is a pass of one block (plan_block, batch_frame with count 1); batch_plan adds the limits of the public batch call.
+// Plain arithmetic, no HIP; the CPU tests pin both (bscgpu_lzp_batch_plan, bscgpu_lzp_batch_frame, bscgpu_lzp_staged_host).
 #pragma once
 #include <cstdint>
 #include "lzp_staged.h"
@@ -21,8 +22,21 @@ struct BatchChunk { uint32_t block, start, size, cap; };
 // lzp.cpp:531: the encoder refuses the block by its size, before it looks at a byte (an empty block included)
 inline bool batch_refused_by_size(int n, int minLen) { return (int64_t)n - minLen < 32 || n - 2 < 16; }
 
-// The chunk table of a pass of `count` blocks back to back, in pass order: lzp_staged.h's cut per block; a block the encoder refuses
-// by size owns no chunk.  -> the number of chunks (<= BATCH_LZP_MAX_CHUNKS), or LIBBSC_BAD_PARAMETER with nothing written: count
+// The chunks of block `block`, n bytes (any n up to 2^31 - 1) from `off` of the pass: lzp_staged.h's cut.  -> how many were written
+// (1, 2, 4 or 8), 0: the encoder refuses the block by size and it owns no chunk.
+inline int plan_block(int n, int minLen, uint32_t block, uint32_t off, BatchChunk* out)
+{
+    const int nc = num_chunks(n);
+    if (nc == 1 && batch_refused_by_size(n, minLen)) return 0;
+    for (int i = 0; i < nc; ++i) {
+        out[i].block = block; out[i].start = off + (uint32_t)chunk_start(n, nc, i);
+        out[i].size = (uint32_t)chunk_size(n, nc, i); out[i].cap = (uint32_t)(nc == 1 ? n - 2 : chunk_size(n, nc, i));
+    }
+    return nc;
+}
+
+// The chunk table of a pass of `count` blocks back to back, in pass order: plan_block per block.
+// -> the number of chunks (<= BATCH_LZP_MAX_CHUNKS), or LIBBSC_BAD_PARAMETER with nothing written: count
 // outside 0..BATCH_LZP_MAX_BLOCKS, a size negative or not below BATCH_LZP_MAX_N, a pass of 2^31 bytes or more, minLen outside 4..255.
 inline int batch_plan(const int* sizes, int count, int minLen, BatchChunk* out)
 {
@@ -35,14 +49,7 @@ inline int batch_plan(const int* sizes, int count, int minLen, BatchChunk* out)
     if (total >= 0x7fffffffll) return LIBBSC_BAD_PARAMETER;
     int k = 0;
     uint32_t off = 0;
-    for (int b = 0; b < count; off += (uint32_t)sizes[b], ++b) {
-        const int n = sizes[b], nc = num_chunks(n);
-        if (nc == 1 && batch_refused_by_size(n, minLen)) continue;
-        for (int i = 0; i < nc; ++i, ++k) {
-            out[k].block = (uint32_t)b; out[k].start = off + (uint32_t)chunk_start(n, nc, i);
-            out[k].size = (uint32_t)chunk_size(n, nc, i); out[k].cap = (uint32_t)(nc == 1 ? n - 2 : chunk_size(n, nc, i));
-        }
-    }
+    for (int b = 0; b < count; off += (uint32_t)sizes[b], ++b) k += plan_block(sizes[b], minLen, (uint32_t)b, off, out + k);
     return k;
 }
 
@@ -53,8 +60,9 @@ struct BatchPiece { uint32_t src, src_off, dst_off, len; };
 
 // The frames of a pass from its chunks' own results (own[k] of chunk k of batch_plan's table: the sweep's size or a negative code):
 // frame_from_own per block, both framings.  results[b] = what lzp_compress returns for block b; where that is a size, the block's
-// pieces are appended to `pieces` (<= BATCH_LZP_MAX_PIECES) and its table to `table` (<= count * BATCH_LZP_TABLE_BYTES bytes, in block
-// order).  *raw_chunks (or null): chunks kept raw, whether their block came out or not.  -> the number of pieces.
+// pieces are appended to `pieces` and its table to `table`, in block order: a pass planned by batch_plan has at most
+// BATCH_LZP_MAX_PIECES pieces and count * BATCH_LZP_TABLE_BYTES table bytes, a single block of eight chunks 9 and 65.
+// *raw_chunks (or null): chunks kept raw, whether their block came out or not.  -> the number of pieces.
 // dst (or null: every block at its own offset of the pass): where block b's stream starts in the output, BATCH_NOWHERE: it gets no
 // piece; as_it_is (or null): blocks whose sizes[b] raw bytes go to dst[b] in one piece instead — the caller's choice for a block
 // without a stream.  Both are made from the results (batch_results) by a caller that packs the pass (block.cpp: a batched pass).

@@ -193,29 +193,28 @@ struct Chunk {
 int lzp_compress_staged(const uint8_t* in, uint8_t* out, int n, int hashSize, int minLen, int features, int64_t* counters)
 {
     if (hashSize > STAGED_MAX_HASH) return LIBBSC_NOT_SUPPORTED;
-    if (counters) memset(counters, 0, sizeof(int64_t) * CNT_WORDS);
-    Frame F;
-    const int nc = num_chunks(n);
+    // the device's route (lzp.hip: lzp_stage) for a pass of this one block: chunk table, a sweep per entry, piece list, the pieces moved
+    int64_t cnt[CNT_WORDS] = {0, 0, 0, 0, 0};
+    BatchChunk chunks[8];
+    const int nc = plan_block(n, minLen, 0, 0, chunks);
     std::vector<uint8_t> staging((size_t)n + 16);
     int own[8];
-    for (int b = 0; b < nc; ++b) {
+    for (int k = 0; k < nc; ++k) {
         Chunk C;
-        C.T = in + chunk_start(n, nc, b); C.n = chunk_size(n, nc, b);
-        C.out = staging.data() + chunk_start(n, nc, b); C.cap = nc == 1 ? n - 2 : C.n;
+        C.T = in + chunks[k].start; C.n = (int)chunks[k].size;
+        C.out = staging.data() + chunks[k].start; C.cap = (int)chunks[k].cap;
         C.hashSize = hashSize; C.minLen = minLen;
-        own[b] = C.run();
-        if (counters) {
-            counters[CNT_MATCHES] += C.cnt[CR_MATCHES]; counters[CNT_DIRTY] += C.cnt[CR_DIRTY];
-            counters[CNT_ZONES] += C.cnt[CR_ZONES]; counters[CNT_ESCAPES] += C.cnt[CR_ESCAPES];
-        }
+        own[k] = C.run();
+        count_chunk(cnt, C.cnt);
     }
-    const int total = frame_from_own(n, features, own, &F);
-    if (counters) counters[CNT_RAW_CHUNKS] = F.raw_chunks;
-    if (total < 0) return total;
-    frame_table(F, out);
-    for (int b = 0; b < nc; ++b)
-        memcpy(out + F.off[b], (F.nc > 1 && F.res[b] == F.size[b] ? in : staging.data()) + F.start[b], (size_t)F.res[b]);
-    return total;
+    int result = 0;
+    BatchPiece pieces[1 + 8];
+    unsigned char table[1 + 8 * 8];
+    const int np = batch_frame(&n, 1, minLen, features, own, &result, pieces, table, &cnt[CNT_RAW_CHUNKS]);
+    const uint8_t* const from[3] = {staging.data(), in, table};            // PIECE_STAGING, PIECE_RAW, PIECE_TABLE
+    for (int p = 0; p < np; ++p) memcpy(out + pieces[p].dst_off, from[pieces[p].src] + pieces[p].src_off, pieces[p].len);
+    if (counters) memcpy(counters, cnt, sizeof cnt);
+    return result;
 }
 
 }  // namespace bschost
@@ -265,10 +264,7 @@ extern "C" int bscgpu_lzp_chunk_staged_host(const uint8_t* in, uint8_t* out, int
     bschost::Chunk C;
     C.T = in; C.n = n; C.out = staging.data(); C.cap = cap; C.hashSize = hashSize; C.minLen = minLen;
     const int r = C.run();
-    if (counters) {
-        counters[CNT_MATCHES] = C.cnt[CR_MATCHES]; counters[CNT_DIRTY] = C.cnt[CR_DIRTY];
-        counters[CNT_ZONES] = C.cnt[CR_ZONES]; counters[CNT_ESCAPES] = C.cnt[CR_ESCAPES]; counters[CNT_RAW_CHUNKS] = 0;
-    }
+    if (counters) { memset(counters, 0, sizeof(int64_t) * CNT_WORDS); count_chunk(counters, C.cnt); }
     if (r > 0) memcpy(out, staging.data(), (size_t)r);
     return r;
 }

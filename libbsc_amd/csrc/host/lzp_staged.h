@@ -58,6 +58,13 @@ constexpr int STAGED_MAX_HASH = 15;
 enum { CR_RES = 0, CR_MATCHES, CR_DIRTY, CR_ZONES, CR_ESCAPES, CR_WORDS = 8 };
 // counters[] of bscgpu_lzp_staged_host / bscgpu_lzp_counters
 enum { CNT_MATCHES = 0, CNT_DIRTY, CNT_ZONES, CNT_ESCAPES, CNT_RAW_CHUNKS, CNT_WORDS };
+// a chunk's record added to the counters (raw chunks are the frame's to count)
+template <class Word>
+inline void count_chunk(int64_t* counters, const Word* rec)
+{
+    counters[CNT_MATCHES] += rec[CR_MATCHES]; counters[CNT_DIRTY] += rec[CR_DIRTY];
+    counters[CNT_ZONES] += rec[CR_ZONES]; counters[CNT_ESCAPES] += rec[CR_ESCAPES];
+}
 
 // A block's frame from its chunks' own results.  own[b]: chunk b coded with a budget of size[b] bytes (n - 2 for a single chunk) -> its
 // size or a negative code.  The scanner's decisions do not depend on its budget; the budget only ends it, with NOT_COMPRESSIBLE, once

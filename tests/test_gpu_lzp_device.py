@@ -126,9 +126,62 @@ def test_stage_eight_chunks_golden(torch_cuda, minlen):
             assert len(got) == e["size"] and hashlib.md5(got).hexdigest() == e["md5"], e
             assert got[0] == 8 and c.lzp_counters()["matches"] > 0
         st = c.profile_get()
-        assert st["lzp"]["launches"] == 6 and st["lzp"]["ms"] > 0 and st["radix_aux"]["launches"] > 0, "the stage is a class of its own in the profile"
+        # two calls, four ranges each: key; link + flag; sweep; frame
+        assert st["lzp"]["launches"] == 8 and st["lzp"]["ms"] > 0 and st["radix_aux"]["launches"] > 0, "the stage is a class of its own in the profile"
     finally:
         c.close()
+
+
+@pytest.mark.parametrize("features", I.FEATURES)
+@pytest.mark.parametrize("name", ["first_chunk_raw", "two_chunks"])
+def test_stage_output_over_input(ctx, torch_cuda, name, features):
+    """bscgpu_lzp_compress_device with dOut == dIn: the stage works on its own copy of the block, so a chunk kept raw — read when the
+    output is already being written — and the coded chunks come out as with an output of their own"""
+    key, T = {"first_chunk_raw": ("first_chunk_raw", I.first_chunk_raw()),
+              "two_chunks": (("threshold", 256 * 1024), I.threshold_block()[:256 * 1024])}[name]
+    want = I.want(key, T, 15, 32, features)
+    assert not isinstance(want, int) and want[0] == 2
+    d = torch_cuda.from_numpy(T).cuda()
+    r = ctx.L.bscgpu_lzp_compress_device(ctx.h, d.data_ptr(), d.data_ptr(), T.size, 15, 32, features)
+    assert r == len(want), (name, features)
+    assert d[:r].cpu().numpy().tobytes() == want, (name, features)
+    if name == "first_chunk_raw":
+        assert ctx.lzp_counters()["raw_chunks"] == 1
+
+
+def test_stage_tables_are_counted_once(torch_cuda):
+    """a single block allocates the stage's tables on first use (test_gpu_lzp_batch.py: test_tables_are_counted's bounds); the next
+    block and a pass on the same context find them there"""
+    from libbsc_amd import GpuContext
+    c = GpuContext(0, max_n=1 << 20)
+    try:
+        before = c.arena_bytes
+        T = I.corpora()["zeros"]
+        want = I.want("zeros", T, 15, 32, 3)
+        assert c.lzp_compress(T, 15, 32, features=3) == want
+        grown = c.arena_bytes - before
+        assert 600_000 < grown < 800_000, grown
+        assert c.lzp_compress(T, 15, 32, features=3) == want
+        assert c.arena_bytes - before == grown
+        assert c.lzp_compress_batch([T], None, 15, 32, 3) == [want]
+        assert c.arena_bytes - before == grown
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("h,m", [(15, 8), (10, 40), (15, 128)])
+def test_block_and_pass_share_the_kernels(ctx, torch_cuda, h, m):
+    """one block of two chunks through lzp_compress and as a pass of one block through lzp_compress_batch: the same bytes, the same
+    counters.  The block is the `text` corpus continued to 300 000 bytes (the corpus itself has 150 000, one chunk: the generator
+    with the corpus's seed, whose first 150 000 bytes are the corpus)."""
+    from libbsc_amd.synth import synth_text_v1
+    T = synth_text_v1(3, 300_000)
+    assert T[:150_000].tobytes() == I.corpora()["text"].tobytes()
+    alone = ctx.lzp_compress(T, h, m, features=3)
+    cnt = ctx.lzp_counters()
+    assert alone == I.want(("text300k",), T, h, m, 3)
+    assert ctx.lzp_compress_batch([T], None, h, m, 3) == [alone]
+    assert ctx.lzp_counters() == cnt
 
 
 # ---- the route -------------------------------------------------------------------------------------------------------------------------
